@@ -14,7 +14,8 @@ GPU g plans slices [g*S/N, (g+1)*S/N), the pre-smoothing blocks are gathered to 
 postion_smooth / reduceRPY / flange offset once over the whole list (strong scaling).
 
 Launch: python bench.py --gpus N --steps K --warmup W     (N > 1 via torch.distributed.run)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run reports the headline only (set-up, warm-up, the K timed steps); --full adds
+every other measurement and check (see --help).  --dump-outputs DIR writes the last timed step's robot path as .npy.
 """
 import argparse
 import json
@@ -81,6 +82,22 @@ def emit_record(out):
             line = line[os.write(_RECORD_FD, line):]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Write {name: array} as DIR/<name>.npy in float32 / float64.  An array above DUMP_LIMIT_BYTES (all of them together) is
+    reduced to a fixed sample of its rows (seed 0, in row order), so two runs with the same arguments write the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget and a.shape[0] > 0:
+            keep = max(1, budget // max(a.nbytes // a.shape[0], 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -107,6 +124,13 @@ def main():
     ap.add_argument("--dynamic", action="store_true",
                     help="plan with Dynamic_adjustment = true (the reference's config.txt default; SURVEY.md 8f rank 1): the same "
                          "workload through the slice-to-slice chains -- a measurement beside the headline, not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the one-handle loop, roofline and per-kernel times, "
+                         "latency, the CPU baseline and path error against the oracle, the dynamic-adjustment line, the other BASELINE "
+                         "configurations, the exchange's own figures, the assembled list.  Without it a run sets up, warms up, times "
+                         "the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the robot path the last timed step produced (rank 0's assembled list, float32) to DIR/waypoints.npy")
     args = ap.parse_args()
     if args.rotate is None:
         args.rotate = 8 if (args.gpus == 1 and args.batch == 1 and not args.dynamic) else 0
@@ -131,6 +155,15 @@ def main():
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         raise SystemExit(subprocess.call(cmd))
 
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus and world > 1:
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    # (before the framework is imported: a rank that fails early must not end its siblings before they have said who they are)
+    if os.environ.get("PPP_BENCH_ECHO_RANK") == "1":
+        print("bench.py rank %d of %d: %s, mode %s" % (rank, world, args.config, args.mode), file=sys.stderr, flush=True)
+
     # stdout carries ONE line, the JSON record: whatever native libraries print while they come up (RCCL's version banner goes to
     # stdout) is sent to stderr; the record is written to the saved descriptor at the end
     sys.stdout.flush()
@@ -143,13 +176,6 @@ def main():
     from polishpathplanning_amd import engine, synth
     from polishpathplanning_amd.robot_path import exchange_counts, gather_robot_path
 
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus and world > 1:
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
-    if os.environ.get("PPP_BENCH_ECHO_RANK") == "1":
-        print("bench.py rank %d of %d: %s, mode %s" % (rank, world, args.config, args.mode), file=sys.stderr, flush=True)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the engine has no CPU fallback")
     torch.cuda.set_device(local_rank)
@@ -293,10 +319,12 @@ def main():
     blocks = timed(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and blocks is not None:   # the last timed step's robot path as rank 0 received it
+        dump_outputs(args.dump_outputs, {"waypoints": np.concatenate([b.cpu().numpy() for b in blocks], axis=0)})
     w_local = w_step
     single = None
     side_by_side(1)
-    if turns > 1 and not args.no_single_handle:   # the same K steps on ONE handle, back to back (rounds 1-3's loop), for the record
+    if args.full and turns > 1 and not args.no_single_handle:   # the same K steps on ONE handle, back to back (rounds 1-3's loop), for the record
         run_steps(args.warmup)
         fence()
         t1 = time.perf_counter()
@@ -319,7 +347,7 @@ def main():
     # ---- N > 1: how many ranks took part (as torch.distributed and as the RCCL communicator itself see it), every rank's
     # waypoint count, and what the gather alone costs per step (untimed, after the timed region) ----
     multi = None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         ones = torch.ones(1, dtype=torch.float64, device=dev)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)          # every rank of the communicator adds one
         wl = torch.zeros(max(world, 1), dtype=torch.float64, device=dev)
@@ -368,8 +396,31 @@ def main():
                  "note": "gather_ms_per_step_alone: the collective back to back with a host wait around the loop; inside the timed loop it "
                          "overlaps the next step's planning"}
 
+    head = {
+        "metric": "polishing waypoints/sec for 1M-pt cloud, 256 slices; path L2 err vs ref",
+        "value": value, "unit": "waypoints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": args.config, "points_per_workpiece": n_points, "slices": S,
+                   "waypoints_per_workpiece": int(w_all[0]), "workpieces": world * args.batch, "batch_per_gpu": args.batch,
+                   "parallelism": "one workpiece per GPU, RCCL gather of robot_path to rank 0" if world > 1 else "single GPU",
+                   "pairing": "kd", "walk": "center_int (connect)", "tool_radius_mm": cfg["tool_radius"],
+                   "dynamic_adjustment": bool(args.dynamic),
+                   "handles_taking_turns": turns,
+                   "step_order": ("consecutive steps (independent workpieces) take turns on %d engine handles = %d HIP streams, each with the "
+                                  "same resident cloud and buffers of its own: a step's binning launch runs beside the step before's per-slice "
+                                  "kernel; K steps enqueued, one host wait at the end" % (turns, turns)) if turns > 1 else
+                                 "steps enqueued back to back on one handle (one HIP stream), one host wait at the end"},
+        "full": bool(args.full),
+    }
+    exchange = ("torch.distributed gather to rank 0 over RCCL (direct send/recv of padded blocks), asynchronous behind each "
+                "step in the planner's stream order" if gatherers[0].dist else None)
     out = None
-    if rank == 0:
+    if rank == 0 and not args.full:   # the headline alone; the fields --full fills stay in the record, empty
+        out = dict(head, single_handle=None, roofline=None, cpu_baseline=None, path_l2_err=None, assembled_path=None, latency=None,
+                   dynamic=None, other_configs=None, multi_gpu=None, exchange=exchange)
+        emit_record(out)
+    elif rank == 0:
         # ---- the last step's assembled robot path (untimed check): rank 0's own block is its engine's list, every
         # rank's block has the row count that rank announced ----
         assembled = None
@@ -508,33 +559,8 @@ def main():
                 except Exception as ex:   # the headline line must not depend on these
                     other[key] = {"error": "%s: %s" % (type(ex).__name__, ex)}
 
-        out = {
-            "metric": "polishing waypoints/sec for 1M-pt cloud, 256 slices; path L2 err vs ref",
-            "value": value, "unit": "waypoints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": args.config, "points_per_workpiece": n_points, "slices": S,
-                       "waypoints_per_workpiece": int(w_all[0]), "workpieces": world * args.batch, "batch_per_gpu": args.batch,
-                       "parallelism": "one workpiece per GPU, RCCL gather of robot_path to rank 0" if world > 1 else "single GPU",
-                       "pairing": "kd", "walk": "center_int (connect)", "tool_radius_mm": cfg["tool_radius"],
-                       "dynamic_adjustment": bool(args.dynamic),
-                       "handles_taking_turns": turns,
-                       "step_order": ("consecutive steps (independent workpieces) take turns on %d engine handles = %d HIP streams, each with the "
-                                      "same resident cloud and buffers of its own: a step's binning launch runs beside the step before's per-slice "
-                                      "kernel; K steps enqueued, one host wait at the end" % (turns, turns)) if turns > 1 else
-                                     "steps enqueued back to back on one handle (one HIP stream), one host wait at the end"},
-            "single_handle": single,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "path_l2_err": err,
-            "assembled_path": assembled,
-            "latency": latency,
-            "dynamic": dynamic,
-            "other_configs": other,
-            "multi_gpu": multi,
-            "exchange": ("torch.distributed gather to rank 0 over RCCL (direct send/recv of padded blocks), asynchronous behind each "
-                         "step in the planner's stream order" if gatherers[0].dist else None),
-        }
+        out = dict(head, single_handle=single, roofline=roofline, cpu_baseline=cpu, path_l2_err=err, assembled_path=assembled, latency=latency,
+                   dynamic=dynamic, other_configs=other, multi_gpu=multi, exchange=exchange)
         emit_record(out)
     if world > 1 or force_dist:
         dist.barrier()
@@ -876,11 +902,15 @@ def bench_slices(args, rank, local_rank, world, dev, dist, torch, engine, synth)
     out = None
     if rank == 0:
         assert got.shape[0] == W
-        # untimed check of the last step: the list finished from the gathered blocks is the unsharded handle's list
-        whole = engine.Engine(local_rank, tool_radius=cfg["tool_radius"])
-        whole.set_cloud(pts); whole.gen_path(); whole.get_path()
-        sharded_equals_whole = bool(np.array_equal(eng.waypoints(), whole.waypoints()))
-        whole.close()
+        if args.dump_outputs:   # the last timed step's finished list
+            dump_outputs(args.dump_outputs, {"waypoints": eng.waypoints()})
+        sharded_equals_whole = None
+        if args.full:
+            # untimed check of the last step: the list finished from the gathered blocks is the unsharded handle's list
+            whole = engine.Engine(local_rank, tool_radius=cfg["tool_radius"])
+            whole.set_cloud(pts); whole.gen_path(); whole.get_path()
+            sharded_equals_whole = bool(np.array_equal(eng.waypoints(), whole.waypoints()))
+            whole.close()
         n_points = int(pts.shape[0])
         alg_bytes = 12.0 * n_points + 24.0 * W
         out = {
@@ -897,11 +927,12 @@ def bench_slices(args, rank, local_rank, world, dev, dist, torch, engine, synth)
                          "note": "whole pipeline; every rank streams and indexes its own x interval of the cloud only"},
             "cpu_baseline": None,
             "assembled_path": {"sharded_list_equals_unsharded_handle": sharded_equals_whole, "rows": W},
+            "full": bool(args.full),
         }
         emit_record(out)
     dist.barrier()
     dist.destroy_process_group()
-    if rank == 0 and not out["assembled_path"]["sharded_list_equals_unsharded_handle"]:
+    if rank == 0 and sharded_equals_whole is False:
         raise SystemExit("bench.py --mode slices: the list assembled from the slice ranges differs from the unsharded handle's")
     return out
 

@@ -1763,7 +1763,7 @@ def test_bench_one_rank_rehearsal_reports_what_the_collective_saw(tmp_path):
     env = dict(os.environ)
     env.update(PPP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29591")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "small_40k", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--rotate", "0", "--no-dynamic", "--profile-passes", "2"],
+                        "--no-cpu-baseline", "--rotate", "0", "--no-dynamic", "--profile-passes", "2", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([ln for ln in r.stdout.strip().split("\n") if ln.startswith("{")][-1])
@@ -1848,14 +1848,14 @@ def test_planner_queue_lists_equal_fresh_handles(engine_mod):
 
 
 def test_bench_line_of_a_one_gpu_run(tmp_path):
-    """The default form of bench.py on one GPU (a small workload here): ONE JSON line with the contract's fields; consecutive steps take
+    """bench.py --full on one GPU (a small workload here): ONE JSON line with the contract's fields; consecutive steps take
     turns on three engine handles, every replica's list is the first handle's byte for byte, the one-handle loop is timed beside it, the
     oracle is the checker (path_l2_err) and the CPU baseline, and the roofline object names the dominant kernel with its duration alone
     on the device and under the loop's overlap."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small_40k", "--steps", "12", "--warmup", "3", "--rotate", "2",
-                        "--no-other-configs", "--profile-passes", "4"], capture_output=True, text=True, timeout=900)
+                        "--no-other-configs", "--profile-passes", "4", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.strip().split("\n") if ln.strip()]
     assert len(lines) == 1, lines[:3]
@@ -1874,6 +1874,34 @@ def test_bench_line_of_a_one_gpu_run(tmp_path):
     assert d["path_l2_err"]["waypoints_equal"] and d["path_l2_err"]["max_m"] <= TOL_M
     assert d["dynamic"]["replicas_equal"] and d["dynamic"]["ms_per_step_three_handles"] > 0
     assert d["latency"]["cold_ms"] > 0
+
+
+def test_plain_bench_line_and_its_dumped_outputs(engine_mod, tmp_path):
+    """bench.py without --full: ONE JSON line with the headline fields and nothing measured beside it; --dump-outputs writes the
+    last timed step's robot path, which is the list a fresh handle plans for the same cloud, byte for byte, run after run."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for k in range(2):
+        dump = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "small_40k", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [ln for ln in r.stdout.strip().split("\n") if ln.strip()]
+        assert len(lines) == 1, lines[:3]
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["full"] is False and d["unit"] == "waypoints/s" and d["dtype"] == "f32"
+        assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["waypoints_per_workpiece"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["single_handle"] is None and d["latency"] is None
+        wp = np.load(dump / "waypoints.npy")
+        assert wp.dtype == np.float32 and wp.shape == (d["config"]["waypoints_per_workpiece"], 6)
+        got.append(wp)
+    assert got[0].tobytes() == got[1].tobytes()
+    pts, cfg = synth.make_config("small_40k", seed=sorted(synth.CONFIGS).index("small_40k") + 1)
+    e = engine_mod.Engine(0, tool_radius=cfg["tool_radius"], dynamic_adjustment=0); e.set_cloud(pts); e.gen_path(); e.get_path()
+    assert e.waypoints().tobytes() == got[0].tobytes()
+    e.close()
 
 
 @pytest.mark.parametrize("name,walk,kw", [("small_40k", 1, {}), ("small_40k", 0, {}), ("small_40k", 2, {}), ("small_40k", 3, {}), ("small_40k", 4, {}),
