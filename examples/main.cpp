@@ -1,6 +1,7 @@
 // Mirror of the reference's src/main.cpp (:6-36): ./main workpiece.pcd, tool radius 15.
 // The calls main.cpp:25-29 keeps commented out can be switched on from the environment: PPP_MAIN_VOXEL=1 (voxel_down(0.1, 1, 1)),
-// PPP_MAIN_ALIGN=1 (trans2center), PPP_MAIN_SLICING=1 (slicing_method), PPP_MAIN_SMOOTH=1 (smooth).
+// PPP_MAIN_ALIGN=1 (trans2center), PPP_MAIN_SLICING=1 (slicing_method), PPP_MAIN_SMOOTH=1 (smooth); PPP_MAIN_COVERAGE=1 switches on
+// main.cpp:32's get_coverage() after the contact paths.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -26,6 +27,7 @@ int main(int argc, char **argv)
     if (on("PPP_MAIN_SMOOTH")) path_planner.smooth();
     path_planner.estimate_normal();
     path_planner.Contact_Path_Generation();
+    if (on("PPP_MAIN_COVERAGE")) path_planner.get_coverage();
     path_planner.show();
     return 0;
 }

@@ -5,11 +5,13 @@
  * and Contact_Path_Generation (:689-755) including its dynamic adjustment (compute_transform,
  * Area2Cloud, compute_boundary, bisection, dynamic_adjust_path, :362-634; k = 10 neighbours,
  * depth 0.005, Adjust_Threshold 1, toolthickness 10 as in the reference header :71).
- * compute_coverage / drawpath only colour the viewer's cloud and are not reproduced.
+ * compute_coverage / get_coverage (:463-496, 757-771) run on the engine after the pass (ppp_get_coverage); drawpath only
+ * colours the viewer's cloud (show() dumps it).
  */
 #ifndef PATH_GENERATION
 #define PATH_GENERATION
 
+#include <algorithm>
 #include <chrono>
 #include <fstream>
 #include <string>
@@ -51,7 +53,18 @@ public:
     void Set_kdtree() {}
     void estimate_normal() { planner.estimate_normal(); } /* Path_Generation.cpp:323-333 */
     const std::vector<float> &cloud_normals() const { return planner.cloud_normals(); } /* n x (nx ny nz curvature) */
-    void get_coverage() { note("get_coverage"); }
+    /* Path_Generation.cpp:757-771: yes / no counted by float ++ (saturating at 2^24 as the reference's do), rate in float: 0 / 0
+       (-nan) when no contact pass has run */
+    void get_coverage()
+    {
+        size_t n = 0, covered = 0;
+        if (!planner.coverage(n, covered)) n = covered = 0;
+        const size_t sat = (size_t)1 << 24;
+        float yes = (float)std::min(covered, sat), no = (float)std::min(n - covered, sat), rate;
+        rate = yes / (yes + no);
+        printf("yes: %f, no: %f\n", yes, no);
+        printf("coverage rate: %f\n", rate);
+    }
 
     std::vector<int> rangedX_index(int position) { return planner.rangedX_index(position); }
     std::map<double, std::vector<double>> insert_point(std::vector<int> indices, Eigen::Vector3f PlanePoint)
@@ -86,7 +99,6 @@ private:
         std::ofstream outputFile("output.csv", std::ios::app); /* Path_Generation.cpp:312-320 */
         if (outputFile.is_open()) outputFile << us << std::endl;
     }
-    void note(const char *what) { fprintf(stderr, "ppp: %s() is outside the accelerated path (no-op)\n", what); }
 
     ppp::Planner planner;
     double toolRadius = 15, depth = 0.005, Adjust_Threshold = 1, toolthickness = 10; /* Path_Generate.h:71 */

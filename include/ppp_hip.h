@@ -242,6 +242,16 @@ int ppp_get_nodes(ppp_handle h, int s, double *y, double *x, double *z, size_t c
    from.  *step = the slice's step in its chain (0 = next to the start slice; -1 = the start slice itself, or no dynamic adjustment):
    the order thread_worker adjusts -- and paints -- in.  Evaluate with ppp_spline_create / ppp_spline_eval below. */
 int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_t cap, size_t *m, int *step);
+/* Coverage of the last pass: path_generater::compute_coverage / get_coverage (Path_Generation.cpp:463-467, 483-496, 757-771).
+   Every Area2Cloud(point, 1, 0) of compute_boundary (:508-520) -- on every slice's raw path (:719) and, inside dynamic_adjust_path,
+   on the adjusted paths of slices 1 .. S-2 (:590) -- marks the cloud points within |min x - max x| / 2 of the point (float
+   arithmetic, squared as PCL does).  flags[i] = 1 for a covered cloud point i, 0 otherwise, for the first
+   min(cap, *n) points of the cloud; flags may be NULL (the counts only).  *n = cloud->size(), *covered = the yes count.
+   get_coverage() prints yes = covered, no = n - covered.  Ordered behind the handle's last pass; blocks until the results are on
+   the host.  The first call computes, later calls reuse the result until the next pass or cloud.  PPP_ERR_UNSUPPORTED unless the
+   last pass was PPP_WALK_V1_CONTACT with dynamic_adjustment = 1 on a whole-cloud handle (the only flow the reference computes
+   coverage in); PPP_ERR_ARG before any pass; the pass's own error if it failed. */
+int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

@@ -259,6 +259,17 @@ public:
         if (rc == PPP_OK) rc = ppp_sync(h_);
         return rc == PPP_OK ? true : report(rc);
     }
+    /* coverage of the last pass (ppp_get_coverage: Contact_Path_Generation with the dynamic adjustment only): the cloud's size, the
+       covered points and, when asked for, one flag per cloud point */
+    bool coverage(size_t &n, size_t &covered, std::vector<unsigned char> *flags = nullptr)
+    {
+        int rc = ppp_get_coverage(h_, nullptr, 0, &n, &covered);
+        if (rc == PPP_OK && flags) {
+            flags->assign(n, 0);
+            rc = ppp_get_coverage(h_, flags->data(), n, &n, &covered);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
     /* getPath(): returns the list and writes pathFile exactly like path_translation_alg.cpp:216-228 */
     bool get_path(std::vector<float> &wp6)
     {

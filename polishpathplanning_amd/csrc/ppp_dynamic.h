@@ -249,14 +249,19 @@ __device__ inline void dyn_stage_ellipse(const float *__restrict__ ell_cs, float
 
 /* Area2Cloud(point, flag, key): key 0 = left (min x), 1 = right (max x).  Wave-cooperative.  Returns the number of neighbours
    its search found (0: none, or the point is not a number); L.sel[0] / L.sel_id[0] then still hold the nearest of them, which is
-   what the 1-NN snap of the same point asks for. */
+   what the 1-NN snap of the same point asks for.
+   BOTH_X (the coverage balls, Path_Generation.cpp:457-467): both extrema of the same transformed ellipse, ext_x[0] = min x,
+   ext_x[1] = max x (NaN where the reference's std::min_element / std::max_element return a NaN); key and bound are not used.
+   The chain kernels instantiate the default, whose code this form leaves as it was. */
+template <bool BOTH_X = false>
 __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWaveLds &L, const float4 *__restrict__ normals4,
                                        const float2 *ell, const DynParams &D, const double point[3], int key,
-                                       float bound[3], StampCtx &sc)
+                                       float bound[3], StampCtx &sc, float *ext_x = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const float sp[3] = {(float)point[0], (float)point[1], (float)point[2]};
     bound[0] = bound[1] = bound[2] = NAN;
+    if constexpr (BOTH_X) ext_x[0] = ext_x[1] = NAN;
     if (!(sp[0] == sp[0] && sp[1] == sp[1] && sp[2] == sp[2])) return 0;
     /* computePointPrincipalCurvatures: lane r holds the neighbour of rank r */
     float nn[3] = {0.f, 0.f, 0.f};
@@ -442,6 +447,14 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
     return have ? 1 : 0;
     };
     float res[3];
+    if constexpr (BOTH_X) { /* the same samples folded twice: the minimum, then the maximum (the lambda reads key) */
+        key = 0;
+        if (ellipse_extremum(true, res) == 1) ext_x[0] = res[0];
+        key = 1;
+        if (ellipse_extremum(true, res) == 1) ext_x[1] = res[0];
+        sc.mark(5);
+        return kk;
+    }
     const int st = ellipse_extremum(true, res);
 #ifdef DYN_ELL_CHECK /* test build: the windowed evaluation against all 721 samples, every time */
     {
@@ -693,13 +706,16 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_first_eval(DevMeta *m, D
         const float4 *__restrict__ sorted4, const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
         const float *__restrict__ slab_xmax, const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
         const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
-        const int *__restrict__ node_start, const int *__restrict__ node_cnt, DynBuffers Bf)
+        const int *__restrict__ node_start, const int *__restrict__ node_cnt, DynBuffers Bf, int *__restrict__ raw_sc)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
     __shared__ float2 s_ell[DYN_ELL];
     StampCtx sc; sc.begin(6, blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.y / 2 && threadIdx.x == 0);
     dyn_stage_ellipse(ell_cs, s_ell);
     const DynGrid G = dyn_grid(m);
+    /* the slice's knots as fitted, before the chain repoints node_start at the adjusted ones: the raw paths of the coverage
+       balls (k_cov_balls; the chain appends, so the knots stay where they are) */
+    if (blockIdx.x == 0 && threadIdx.x == 0) { raw_sc[2 * blockIdx.y] = node_start[blockIdx.y]; raw_sc[2 * blockIdx.y + 1] = node_cnt[blockIdx.y]; }
     __syncthreads();
     if (m->err) return;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -737,6 +753,23 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_first_eval(DevMeta *m, D
         else if (got < 1) Bf.first_snap[at] = make_float4(0.f, 0.f, 0.f, 2.f);
         else { const float4 p = V.at(s_w[wv].sel[0]); Bf.first_snap[at] = make_float4(p.y, p.x, p.z, 1.f); }
     }
+}
+
+/* compute_boundary's sample j (Path_Generation.cpp:508-520, path_dynamic_alg.cpp:191-203): dy = miny + 2; dy += toolRadius/4 per
+   sample.  When start and step are multiples of 2^-20 (float knots and the usual radii are) every partial sum is exact in double
+   and the closed form gives the same bits; else accumulate */
+__device__ inline double dyn_boundary_dy(const DynParams &D, double miny, int j)
+{
+    const double dstep = D.tool_radius / 4, dy0 = miny + 2;
+    double dy;
+    if (floor(dstep * 1048576.0) == dstep * 1048576.0 && floor(dy0 * 1048576.0) == dy0 * 1048576.0 &&
+        fabs(dy0) + (double)j * fabs(dstep) < 4294967296.0)
+        dy = dy0 + (double)j * dstep;
+    else {
+        dy = dy0;
+        for (int q = 0; q < j; ++q) dy += dstep;
+    }
+    return dy;
 }
 
 /* Step t, first launch.  Every workgroup begins with the second half of dynamic_adjust_path for the slice of step t-1
@@ -803,17 +836,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_boundary_pts(DevMeta *m,
     float4 *dst = Bf.bnd_pts + (size_t)chain * Bf.maxNB + j;
     if (mm < 3) { if (lane == 0) *dst = make_float4(0, 0, 0, 0); return; }
     const double miny = (double)ky[0], maxy = (double)ky[mm - 1];
-    /* dy = miny + 2; dy += toolRadius/4 per sample.  When start and step are multiples of 2^-20 (float knots and the
-       usual radii are) every partial sum is exact in double and the closed form gives the same bits; else accumulate */
-    const double dstep = D.tool_radius / 4, dy0 = miny + 2;
-    double dy;
-    if (floor(dstep * 1048576.0) == dstep * 1048576.0 && floor(dy0 * 1048576.0) == dy0 * 1048576.0 &&
-        fabs(dy0) + (double)j * fabs(dstep) < 4294967296.0)
-        dy = dy0 + (double)j * dstep;
-    else {
-        dy = dy0;
-        for (int q = 0; q < j; ++q) dy += dstep;
-    }
+    const double dy = dyn_boundary_dy(D, miny, j);
     if (!(dy < maxy - 2)) { if (lane == 0) *dst = make_float4(0, 0, 0, 0); return; }
     sc.mark(0);
     double point[3];
@@ -987,4 +1010,117 @@ __global__ void __launch_bounds__(256) k_dyn_adjust_fit(DevMeta *m, int walk, in
     if (base < 0) return;
     dyn_emit_knots(pts, F, ft, [&](int o, const float4 &p) { node_y[base + o] = p.x == 0.f ? 0.f : p.x; node_x[base + o] = p.y; node_z[base + o] = p.z; });
     if (threadIdx.x == 0) { node_start[c.s] = base; node_cnt[c.s] = tot; }
+}
+
+/* ------------------------------------------------------------------ */
+/* Coverage (path_generater::compute_coverage / get_coverage, Path_Generation.cpp:463-496, 757-771).  Every            */
+/* Area2Cloud(point, 1, 0) of compute_boundary marks the cloud points within half the x-extent of the point's contact   */
+/* ellipse.  In Contact_Path_Generation (:711-725) that is every slice's raw path (:719) and the adjusted path of slice */
+/* s-1 in dynamic_adjust_path of slice s (:590): raw(0..S-1) and adjusted(1..S-2), all known once the pass is done, so */
+/* one launch evaluates all of those balls side by side and marks their points, and a second counts the flags.         */
+/* ------------------------------------------------------------------ */
+
+/* kdtree.radiusSearch(centre, r): flags[i] = 1 for every indexed point within the ball (dist2_flann <= r2, the float
+   square of r as PCL hands it to FLANN).  All 64 lanes together; the candidates come from the y-windows of the slabs the
+   ball touches, as in wave_knn.  Points are only ever set to 1, so balls that overlap need no atomics. */
+__device__ inline void wave_mark_ball(const SlabView &V, const DynGrid &G, DynWaveLds &L, float qx, float qy, float qz, float r,
+                                      float r2, unsigned char *__restrict__ flags)
+{
+    const int lane = threadIdx.x & 63;
+    const float pady = 1e-5f * (fabsf(qy) + r) + 1e-6f, padx = 1e-5f * (fabsf(qx) + r) + 1e-6f;
+    const float ylo = qy - r - pady, yhi = qy + r + pady;
+    const int blo = dyn_slab_of(G, qx - r - padx), bhi = dyn_slab_of(G, qx + r + padx);
+    const int q0 = dyn_ybucket(G, ylo), q1 = dyn_ybucket(G, yhi) + 1;
+    for (int cb = blo; cb <= bhi; cb += 64) {
+        const int bb = cb + lane;
+        int a = 0, e = 0;
+        if (bb <= bhi) {
+            const int s0 = V.slab_start[bb];
+            if (V.ytab) {
+                const int *T = V.ytab + (size_t)bb * (YTB + 1);
+                a = s0 + T[q0]; e = s0 + T[q1];
+            } else {
+                const int s1 = V.slab_start[bb + 1];
+                int l0 = s0, l1 = s1, u0 = s0, u1 = s1;
+                while (l0 < l1 || u0 < u1) {
+                    if (l0 < l1) { const int mid = (l0 + l1) >> 1; if (V.at(mid).y < ylo) l0 = mid + 1; else l1 = mid; }
+                    if (u0 < u1) { const int mid = (u0 + u1) >> 1; if (V.at(mid).y <= yhi) u0 = mid + 1; else u1 = mid; }
+                }
+                a = l0; e = u0 < l0 ? l0 : u0;
+            }
+        }
+        const int cnt = e - a;
+        int inc = cnt;
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
+        const int T = __shfl(inc, 63, 64);
+        __builtin_amdgcn_wave_barrier();
+        L.off[lane] = inc - cnt; L.w0[lane] = a;
+        __builtin_amdgcn_wave_barrier();
+        __threadfence_block();
+        const int wtop = bhi - cb < 63 ? bhi - cb : 63;
+        for (int t = lane; t < T; t += 64) {
+            int lo = 0, hi = wtop; /* the window holding flat position t */
+            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (L.off[mid] <= t) lo = mid; else hi = mid - 1; }
+            const float4 c = V.at(L.w0[lo] + (t - L.off[lo]));
+            if (dist2_flann(qx, qy, qz, c.x, c.y, c.z) <= r2) flags[idx_of(c)] = 1;
+        }
+    }
+}
+
+/* One wave per compute_boundary sample: blockIdx.y = slice, blockIdx.z = 0 the raw path (knots at raw_sc, as k_dyn_first_eval
+   found them), 1 the adjusted one (node_start / node_cnt after the pass; slices 1 .. S-2).  The reference's "last point" call
+   repeats the last sample's ball; a loop that ran zero times adds no ball. */
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_cov_balls(DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
+        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
+        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
+        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
+        const int *__restrict__ node_start, const int *__restrict__ node_cnt, const int *__restrict__ raw_sc, int maxNB,
+        unsigned char *__restrict__ flags)
+{
+    __shared__ DynWaveLds s_w[DYN_WAVES];
+    __shared__ float2 s_ell[DYN_ELL];
+    dyn_stage_ellipse(ell_cs, s_ell);
+    const DynGrid G = dyn_grid(m);
+    const int S = m->S, err = m->err;
+    __syncthreads();
+    if (err) return;
+    const int wv = threadIdx.x >> 6;
+    const int s = blockIdx.y, j = blockIdx.x * DYN_WAVES + wv;
+    const bool adjusted = blockIdx.z == 1;
+    if (s >= S || j >= maxNB || (adjusted && (s < 1 || s > S - 2))) return;
+    const int st = adjusted ? node_start[s] : raw_sc[2 * s], mm = adjusted ? node_cnt[s] : raw_sc[2 * s + 1];
+    if (mm < 3) return;
+    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
+    const double miny = (double)ky[0], maxy = (double)ky[mm - 1];
+    const double dy = dyn_boundary_dy(D, miny, j);
+    if (!(dy < maxy - 2)) return;
+    double point[3];
+    spline_point_f(ky, kx, kz, mm, dy, point);
+    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
+    StampCtx sc; sc.begin(15, false);
+    float b[3], ext[2];
+    wave_area2cloud<true>(V, G, s_w[wv], normals4, s_ell, D, point, 0, b, sc, ext);
+    /* comput_lan = (for_min->x - boundpoint_it->x) / 2 in float (negative); PCL squares it: the float r * r */
+    const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
+    if (!(r2 == r2)) return; /* a NaN radius marks nothing (FLANN: no distance is <= NaN) */
+    wave_mark_ball(V, G, s_w[wv], (float)point[0], (float)point[1], (float)point[2], fabsf(r), r2, flags);
+}
+
+/* get_coverage's yes count: the flags (0 / 1, zero padding up to a multiple of 16 bytes) summed 16 at a time by population
+   count, a wave sum, one atomic per workgroup -- integers, so the count is the same in every run */
+#define COV_T 256
+__global__ void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ flags16, int n16, int *__restrict__ count)
+{
+    __shared__ int s_c;
+    if (threadIdx.x == 0) s_c = 0;
+    __syncthreads();
+    int c = 0;
+    for (int i = blockIdx.x * COV_T + threadIdx.x; i < n16; i += gridDim.x * COV_T) {
+        const uint4 w = flags16[i];
+        c += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+    }
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_c) atomicAdd(count, s_c);
 }

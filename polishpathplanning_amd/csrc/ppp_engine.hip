@@ -157,6 +157,12 @@ struct ppp_handle_s {
     DevBuf<int> dyn_bnd_n;
     int dyn_maxNB = 1, dyn_maxNA = 1;
     bool dyn_keep_all = false;
+    DevBuf<int> dyn_raw_sc;           /* [slice][2]: node_start / node_cnt as fitted, before the chain (k_dyn_first_eval) */
+    /* coverage of the last pass (ppp_get_coverage): flags by cloud index, zero-padded to 16 bytes, and the covered count */
+    DevBuf<unsigned char> cov_flags;
+    DevBuf<int> cov_count;
+    unsigned long long cov_serial = ~0ull; /* the pass (gen_serial) they belong to */
+    size_t cov_covered = 0;
     bool normals_valid = false;
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
@@ -270,7 +276,7 @@ struct ppp_handle_s {
         X.release(); Y.release(); Z.release(); Xp.release(); Yp.release(); Zp.release(); part_idx.release(); unsorted4.release(); sorted4.release();
         slab_cnt.release(); slab_start.release(); slab_cursor.release(); coarse_cursor.release(); slab_ytab.release(); slab_xmin.release(); slab_xmax.release();
         meta.release(); px.release(); lo.release(); hi.release(); node_x.release(); node_y.release(); node_z.release();
-        normals4.release(); dyn_bnd_pts.release(); dyn_adj_pts.release(); dyn_first_ab.release(); dyn_first_snap.release(); dyn_first_node.release(); ell_cs.release(); dyn_bnd_knots.release(); dyn_bnd_n.release(); plan_ticket.release(); plan_auto.release();
+        normals4.release(); dyn_raw_sc.release(); cov_flags.release(); cov_count.release(); dyn_bnd_pts.release(); dyn_adj_pts.release(); dyn_first_ab.release(); dyn_first_snap.release(); dyn_first_node.release(); ell_cs.release(); dyn_bnd_knots.release(); dyn_bnd_n.release(); plan_ticket.release(); plan_auto.release();
         node_start.release(); node_cnt.release(); band_cnt.release(); wp_cnt.release(); wp_off.release(); tail.release(); slice_wpcnt.release();
         wp_xyz.release(); wp_normal.release(); wp_nn.release(); wp_pre.release(); wp_smooth.release(); wp_out.release();
         mm_part.release(); big_slabs.release(); big_slices.release(); arena.release(); scratch.release(); pack_tab.release(); pack_out.release();
@@ -461,6 +467,7 @@ int ensure_dynamic_buffers(ppp_handle h)
     const size_t slot_doubles = 3 * ((size_t)h->dyn_maxNB + 2), nslots = (size_t)std::max(h->S_cap, 2);
     h->dyn_keep_all = nslots * slot_doubles * sizeof(double) <= ((size_t)1 << 30);
     HIPCHK(h, h->dyn_bnd_knots.ensure((h->dyn_keep_all ? nslots : 2) * slot_doubles)); HIPCHK(h, h->dyn_bnd_n.ensure(4 + nslots));
+    HIPCHK(h, h->dyn_raw_sc.ensure(2 * nslots));
     const size_t nfirst = (size_t)std::max(h->S_cap, 1) * h->dyn_maxNA;
     if (nfirst > ((size_t)1 << 27)) /* 56 bytes a node: 7.5 GB */
         return fail(h, PPP_ERR_CAPACITY, "dynamic adjustment: slices x nodes per slice beyond 2^27");
@@ -1042,7 +1049,7 @@ int enqueue_dynamic(ppp_handle h)
     /* every node's first Area2Cloud and snap, for all slices at once: they do not depend on the chains */
     LAUNCH(h, "k_dyn_first_eval", k_dyn_first_eval, dim3(ga.x, S), 64 * DYN_WAVES, 0, h->meta.p, D, walk, centre, h->sorted4.p,
            h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p, h->node_x.p, h->node_y.p,
-           h->node_z.p, h->node_start.p, h->node_cnt.p, Bf);
+           h->node_z.p, h->node_start.p, h->node_cnt.p, Bf, h->dyn_raw_sc.p);
     /* two launches per step: each begins with the fit of what the launch before it sampled */
     for (int t = 0; t < steps; ++t) {
         LAUNCH(h, "k_dyn_boundary_pts", k_dyn_boundary_pts, gb, 64 * DYN_WAVES, lds_b, h->meta.p, D, walk, t, centre, h->sorted4.p,
@@ -3009,6 +3016,41 @@ int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_
     if (k && y) HIPCHK(h, copy_sync(h, y, base, k * 8, hipMemcpyDeviceToHost));
     if (k && x) HIPCHK(h, copy_sync(h, x, base + row, k * 8, hipMemcpyDeviceToHost));
     if (k && z) HIPCHK(h, copy_sync(h, z, base + 2 * row, k * 8, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
+{
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->P.walk != PPP_WALK_V1_CONTACT || !h->P.dynamic_adjustment || h->ranged || h->use_part || h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "coverage: only after a PPP_WALK_V1_CONTACT pass with dynamic_adjustment = 1 on a whole-cloud handle");
+    const size_t N = h->n, n16 = (N + 15) / 16;
+    if (h->cov_serial != h->gen_serial) { /* first question about this pass: two launches, then the count */
+        HIPCHK(h, h->cov_flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, h->cov_count.ensure(1));
+        HIPCHK(h, hipMemsetAsync(h->cov_flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->cov_count.p, 0, sizeof(int), h->stream));
+        const int S = h->hmeta.S;
+        if (S > 0)
+            LAUNCH(h, "k_cov_balls", k_cov_balls, dim3((h->dyn_maxNB + DYN_WAVES - 1) / DYN_WAVES, S, 2), 64 * DYN_WAVES, 0, h->meta.p,
+                   dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
+                   h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->dyn_raw_sc.p,
+                   h->dyn_maxNB, h->cov_flags.p);
+        if (n16)
+            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
+                   (const uint4 *)h->cov_flags.p, (int)n16, h->cov_count.p);
+        int cnt = 0;
+        HIPCHK(h, copy_sync(h, &cnt, h->cov_count.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (cnt < 0 || (size_t)cnt > N) return fail(h, PPP_ERR_HIP, "coverage count corrupt");
+        h->cov_covered = (size_t)cnt;
+        h->cov_serial = h->gen_serial;
+    }
+    if (n) *n = N;
+    if (covered) *covered = h->cov_covered;
+    const size_t k = std::min(cap, N);
+    if (flags && k) HIPCHK(h, copy_sync(h, flags, h->cov_flags.p, k, hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 
