@@ -1,5 +1,7 @@
 // Mirror of the reference's src/connect.cpp / src/connect1.cpp (:7-30): ./connect cloud.pcd
 // reads ../config.txt (or $PPP_CONFIG), plans, writes pathFile.  Build: see examples/Makefile.
+// PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths (get_coverage's two lines, path_dynamic_alg.cpp:155-160
+// keeps them commented out); Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -21,6 +23,8 @@ int main(int argc, char **argv)
     path_generater path_planner = {configFile, pcd};
     path_planner.GenPath();
     path_planner.getPath();
+    const char *cov = std::getenv("PPP_PATH_COVERAGE");
+    if (cov && cov[0] == '1') path_planner.get_path_coverage();
     path_planner.show();
     return 0;
 }

@@ -1,6 +1,6 @@
 // A caller of the RobotPath drop-in (include/robot_path.h): ./robot cloud.pcd [radius].  The reference declares the class
 // (robot_path.h:58-98) but nothing constructs it -- the header does not compile upstream -- so this is the shape of
-// src/connect.cpp with the three-argument constructor.
+// src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -25,6 +25,8 @@ int main(int argc, char **argv)
     RobotPath path_planner(configFile, pcd, radius);
     path_planner.GenPath();
     path_planner.getPath();
+    const char *cov = std::getenv("PPP_PATH_COVERAGE");
+    if (cov && cov[0] == '1') path_planner.get_path_coverage();
     path_planner.show();
     std::cout << "waypoints: " << path_planner.waypoints().size() << std::endl;
     return 0;

@@ -108,6 +108,9 @@ public:
             for (int d = 0; d < 6; ++d) WayPointsList[w][d] = wp[6 * w + d];
     }
     const std::vector<std::vector<float>> &waypoints() const { return WayPointsList; }
+    /* the coverage rate of the planned paths, in get_coverage's two lines (Path_Generation.cpp:766-770; the v2 planner keeps the
+       same lines commented out, path_dynamic_alg.cpp:155-160): the contact model on every slice's final path (ppp_get_path_coverage) */
+    void get_path_coverage() { planner.print_path_coverage(); }
 
 protected:
     virtual void read_config(std::string filename)

@@ -252,6 +252,22 @@ int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_
    last pass was PPP_WALK_V1_CONTACT with dynamic_adjustment = 1 on a whole-cloud handle (the only flow the reference computes
    coverage in); PPP_ERR_ARG before any pass; the pass's own error if it failed. */
 int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered);
+/* Path coverage of the last pass: the contact model of path_generater::compute_coverage / get_coverage (Path_Generation.cpp:
+   463-467, 483-496, 757-771) applied to the paths the pass ends with, for every walk.  For every slice
+   s of the pass, its final knots (adjusted where the dynamic adjustment ran) and the Steffen spline through them are sampled as
+   compute_boundary does (:508-520: dy = miny + 2, step Tool_Radius / 4, while dy < maxy - 2); each sample evaluates Area2Cloud
+   with curvature_k, depth, toolthickness and tool_radius, and marks the cloud points within r = (min x - max x) / 2 of it
+   (float, r * r compared with the squared distance as PCL does; a NaN r marks nothing).  This is the path set as GenPath
+   leaves it: getPath's first / last slice drop and its trim are not applied.  After a PPP_WALK_V1_CONTACT pass with the dynamic
+   adjustment it differs from ppp_get_coverage, which also counts the raw paths.
+   flags[i] = 1 for a covered cloud point i, 0 otherwise, for the first min(cap, *n) points; flags may be NULL (the counts only).
+   *n = cloud->size(), *covered = the yes count.  A slice-range handle marks the balls of its own slices, indexed by whole-cloud
+   point index (OR-ing the flags of ranges that tile the walk gives the whole cloud's); PPP_ERR_CAPACITY when one of its searches
+   would leave the indexed interval (raise range_margin).  The first call after a pass builds what the pass did not (slab
+   index, normal field; a window-path handle stays on the window path) and computes; later calls reuse the result until the
+   next pass or cloud.  Blocks until the results are on the host.  PPP_ERR_ARG before any pass or with curvature_k outside
+   [3, 64]; PPP_ERR_UNSUPPORTED on a part handle (ppp_set_cloud_part); the pass's own error if it failed. */
+int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

@@ -270,6 +270,29 @@ public:
         }
         return rc == PPP_OK ? true : report(rc);
     }
+    /* path coverage of the last pass (ppp_get_path_coverage: the contact model on every slice's final path, every walk): the
+       cloud's size, the covered points and, when asked for, one flag per cloud point */
+    bool path_coverage(size_t &n, size_t &covered, std::vector<unsigned char> *flags = nullptr)
+    {
+        int rc = ppp_get_path_coverage(h_, nullptr, 0, &n, &covered);
+        if (rc == PPP_OK && flags) {
+            flags->assign(n, 0);
+            rc = ppp_get_path_coverage(h_, flags->data(), n, &n, &covered);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* Path_Generation.cpp:766-770 on path_coverage(): yes / no counted by float ++ (saturating at 2^24 as the reference's do),
+       the rate in float (0 / 0 = -nan when there is no pass to measure) */
+    void print_path_coverage()
+    {
+        size_t n = 0, covered = 0;
+        if (!path_coverage(n, covered)) n = covered = 0;
+        const size_t sat = (size_t)1 << 24;
+        float yes = (float)std::min(covered, sat), no = (float)std::min(n - covered, sat), rate;
+        rate = yes / (yes + no);
+        std::printf("yes: %f, no: %f\n", yes, no);
+        std::printf("coverage rate: %f\n", rate);
+    }
     /* getPath(): returns the list and writes pathFile exactly like path_translation_alg.cpp:216-228 */
     bool get_path(std::vector<float> &wp6)
     {
@@ -365,6 +388,15 @@ public:
             if (ppp_eval_spline(h_, s, q.data(), q.size(), xyz.data()) != PPP_OK) continue;
             paint(xyz, path_rgb);
         }
+        if (S > 0 && on_env("PPP_SHOW_COVERAGE")) { /* the gaps of the plan: every point path coverage leaves uncovered, in yellow */
+            std::vector<unsigned char> cov;
+            size_t nc = 0, covered = 0;
+            if (path_coverage(nc, covered, &cov) && nc == n) {
+                for (size_t i = 0; i < n; ++i)
+                    if (!cov[i]) { crgb[3 * i] = 255; crgb[3 * i + 1] = 255; crgb[3 * i + 2] = 0; }
+                std::printf("show(): %zu points left uncovered by the paths painted\n", n - covered);
+            }
+        }
         for (int s = 0; s < S; ++s) nodes.insert(nodes.end(), slice_nodes[s].begin(), slice_nodes[s].end()); /* other_cloud: in slice order */
         if (with_boundaries) std::printf("show(): %zu boundary curves painted\n", painted_boundaries);
         const size_t nn_ = nodes.size() / 3;
@@ -382,6 +414,11 @@ public:
     {   /* the classes without a colour scheme of their own */
         const unsigned char red[3] = {255, 0, 0};
         show_dump(red, red);
+    }
+    static bool on_env(const char *name)
+    {
+        const char *v = std::getenv(name);
+        return v && v[0] == '1';
     }
     static int device_from_env()
     {

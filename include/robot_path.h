@@ -43,6 +43,8 @@ public:
             for (int d = 0; d < 6; ++d) WayPointsList[w][d] = wp[6 * w + d];
     }
     const std::vector<std::vector<float>> &waypoints() const { return WayPointsList; }
+    /* get_coverage's two lines (Path_Generation.cpp:766-770) for the planned paths (ppp_get_path_coverage) */
+    void get_path_coverage() { planner.print_path_coverage(); }
 
 private:
     ppp::Planner planner;

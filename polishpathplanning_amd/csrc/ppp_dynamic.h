@@ -1124,3 +1124,69 @@ __global__ void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ f
     __syncthreads();
     if (threadIdx.x == 0 && s_c) atomicAdd(count, s_c);
 }
+
+/* ------------------------------------------------------------------ */
+/* Path coverage (ppp_get_path_coverage): the same contact model applied to the paths a pass ends with --    */
+/* every slice's final knots (node_start / node_cnt after the pass: adjusted where the adjustment ran), for every walk.     */
+/* One launch marks the balls (k_pcov_balls), k_cov_count counts the flags.                                                */
+/* ------------------------------------------------------------------ */
+
+/* what a slice-range handle indexes: the points with x in [incl_lo, incl_hi] of a cloud that spans [mn_x, mx_x] */
+struct PCovRange { float incl_lo, incl_hi, mn_x, mx_x, normal_radius; int check; };
+
+/* Slice sb + blockIdx.y, one wave per compute_boundary sample: wave w takes samples j = blockIdx.x * DYN_WAVES + w,
+   j + gridDim.x * DYN_WAVES, ... while dy < maxy - 2 (a loop that runs zero times adds no ball, B.15).  The ball of a sample
+   is k_cov_balls's.  With R.check (a slice-range handle) every search a sample makes -- the k-NN of Area2Cloud, the normal
+   neighbourhoods of those neighbours and the ball -- must lie inside the indexed interval, unless that reaches the cloud's end
+   (the DERR_MARGIN test of the waypoints, ppp_kernels.h); err[0] |= 1 where one does not, err[0] |= 2 for a knot table
+   beyond node_cap.  The host then refuses the answer. */
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
+        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
+        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
+        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
+        const int *__restrict__ node_start, const int *__restrict__ node_cnt, int node_cap, int sb, PCovRange R,
+        unsigned char *__restrict__ flags, int *__restrict__ err)
+{
+    __shared__ DynWaveLds s_w[DYN_WAVES];
+    __shared__ float2 s_ell[DYN_ELL];
+    dyn_stage_ellipse(ell_cs, s_ell);
+    const DynGrid G = dyn_grid(m);
+    const int s = sb + blockIdx.y;
+    const int st = node_start[s], mm = node_cnt[s];
+    __syncthreads();
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (mm < 3) return;
+    if (st < 0 || (long long)st + mm > (long long)node_cap) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(err, 2); return; }
+    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
+    const double miny = (double)ky[0], maxy = (double)ky[mm - 1];
+    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
+    DynWaveLds &L = s_w[wv];
+    for (int j = blockIdx.x * DYN_WAVES + wv; j < (1 << 24); j += gridDim.x * DYN_WAVES) {
+        const double dy = dyn_boundary_dy(D, miny, j);
+        if (!(dy < maxy - 2)) return;
+        double point[3];
+        spline_point_f(ky, kx, kz, mm, dy, point);
+        StampCtx sc; sc.begin(15, false);
+        float b[3], ext[2];
+        const int kk = wave_area2cloud<true>(V, G, L, normals4, s_ell, D, point, 0, b, sc, ext);
+        /* comput_lan = (for_min->x - boundpoint_it->x) / 2 in float; PCL squares it: the float r * r */
+        const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
+        const float qx = (float)point[0], qy = (float)point[1], qz = (float)point[2];
+        if (R.check && qx == qx && qy == qy && qz == qz) {
+            /* fewer than k neighbours in the indexed part: the whole cloud may hold more */
+            float lo = kk < D.k ? -INFINITY : INFINITY, hi = kk < D.k ? INFINITY : -INFINITY;
+            if (lane < kk) {
+                const float4 c = V.at(L.sel[lane]);
+                const float dq = sqrtf(dist2_flann(qx, qy, qz, c.x, c.y, c.z)) * 1.0001f;
+                lo = fminf(lo, fminf(qx - dq, c.x - R.normal_radius * 1.0001f));
+                hi = fmaxf(hi, fmaxf(qx + dq, c.x + R.normal_radius * 1.0001f));
+            }
+            if (r2 == r2) { lo = fminf(lo, qx - fabsf(r) * 1.0001f); hi = fmaxf(hi, qx + fabsf(r) * 1.0001f); }
+            lo = wave_min(lo); hi = wave_max(hi);
+            if (lane == 0 && ((lo < R.incl_lo && R.incl_lo > R.mn_x) || (hi > R.incl_hi && R.incl_hi < R.mx_x))) atomicOr(err, 1);
+        }
+        if (!(r2 == r2)) continue; /* a NaN radius marks nothing (B.16) */
+        wave_mark_ball(V, G, L, qx, qy, qz, fabsf(r), r2, flags);
+    }
+    if (lane == 0) atomicOr(err, 2); /* 2^24 samples on one slice: no knot table of a cloud is that long */
+}

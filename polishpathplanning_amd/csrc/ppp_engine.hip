@@ -163,6 +163,12 @@ struct ppp_handle_s {
     DevBuf<int> cov_count;
     unsigned long long cov_serial = ~0ull; /* the pass (gen_serial) they belong to */
     size_t cov_covered = 0;
+    /* path coverage of the last pass (ppp_get_path_coverage): the same, for the final paths of every walk; [1] of the count
+       buffer holds the kernel's refusals (1: a search left the indexed slice range, 2: a knot table out of bounds) */
+    DevBuf<unsigned char> pcov_flags;
+    DevBuf<int> pcov_count;
+    unsigned long long pcov_serial = ~0ull;
+    size_t pcov_covered = 0;
     bool normals_valid = false;
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
@@ -276,7 +282,7 @@ struct ppp_handle_s {
         X.release(); Y.release(); Z.release(); Xp.release(); Yp.release(); Zp.release(); part_idx.release(); unsorted4.release(); sorted4.release();
         slab_cnt.release(); slab_start.release(); slab_cursor.release(); coarse_cursor.release(); slab_ytab.release(); slab_xmin.release(); slab_xmax.release();
         meta.release(); px.release(); lo.release(); hi.release(); node_x.release(); node_y.release(); node_z.release();
-        normals4.release(); dyn_raw_sc.release(); cov_flags.release(); cov_count.release(); dyn_bnd_pts.release(); dyn_adj_pts.release(); dyn_first_ab.release(); dyn_first_snap.release(); dyn_first_node.release(); ell_cs.release(); dyn_bnd_knots.release(); dyn_bnd_n.release(); plan_ticket.release(); plan_auto.release();
+        normals4.release(); dyn_raw_sc.release(); cov_flags.release(); cov_count.release(); pcov_flags.release(); pcov_count.release(); dyn_bnd_pts.release(); dyn_adj_pts.release(); dyn_first_ab.release(); dyn_first_snap.release(); dyn_first_node.release(); ell_cs.release(); dyn_bnd_knots.release(); dyn_bnd_n.release(); plan_ticket.release(); plan_auto.release();
         node_start.release(); node_cnt.release(); band_cnt.release(); wp_cnt.release(); wp_off.release(); tail.release(); slice_wpcnt.release();
         wp_xyz.release(); wp_normal.release(); wp_nn.release(); wp_pre.release(); wp_smooth.release(); wp_out.release();
         mm_part.release(); big_slabs.release(); big_slices.release(); arena.release(); scratch.release(); pack_tab.release(); pack_out.release();
@@ -3051,6 +3057,60 @@ int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, 
     if (covered) *covered = h->cov_covered;
     const size_t k = std::min(cap, N);
     if (flags && k) HIPCHK(h, copy_sync(h, flags, h->cov_flags.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
+{
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "path coverage: the flags address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
+    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+    const size_t N = h->n, n16 = (N + 15) / 16;
+    if (h->pcov_serial != h->gen_serial) { /* first question about this pass */
+        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S);
+        /* what the pass did not build: the slab index (behind a window pass it keeps that pass's run state, as every API
+           mirror's does), the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
+        rc = index_ready(h, false);
+        if (rc) return rc;
+        rc = ensure_dynamic_buffers(h);
+        if (rc) return rc;
+        if (!h->P.dynamic_adjustment) { rc = enqueue_normals(h); if (rc) return rc; }
+        HIPCHK(h, h->pcov_flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, h->pcov_count.ensure(2));
+        HIPCHK(h, hipMemsetAsync(h->pcov_flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->pcov_count.p, 0, 2 * sizeof(int), h->stream));
+        if (se > sb) {
+            /* samples per slice of knots spanning the cloud's y range (the kernel strides past it where adjusted knots reach further) */
+            const double yr = (double)h->h_mx[1] - (double)h->h_mn[1];
+            const int nb = (int)std::min(65536.0, std::max(0.0, yr - 4) / (h->P.tool_radius / 4) + 4);
+            PCovRange R;
+            R.incl_lo = h->incl_lo; R.incl_hi = h->incl_hi; R.mn_x = h->h_mn[0]; R.mx_x = h->h_mx[0];
+            R.normal_radius = h->P.normal_radius; R.check = h->ranged ? 1 : 0;
+            for (int s0 = sb; s0 < se; s0 += 65535) /* (gridDim.y) */
+                LAUNCH(h, "k_pcov_balls", k_pcov_balls, dim3((nb + DYN_WAVES - 1) / DYN_WAVES, std::min(se - s0, 65535)), 64 * DYN_WAVES, 0,
+                       h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
+                       h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->node_cap, s0, R,
+                       h->pcov_flags.p, h->pcov_count.p + 1);
+        }
+        if (n16)
+            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
+                   (const uint4 *)h->pcov_flags.p, (int)n16, h->pcov_count.p);
+        int res[2] = {0, 0};
+        HIPCHK(h, copy_sync(h, res, h->pcov_count.p, sizeof(res), hipMemcpyDeviceToHost));
+        if (res[1] & 2) return fail(h, PPP_ERR_HIP, "path coverage: a slice's knot table lies outside the node buffer");
+        if (res[1] & 1)
+            return fail(h, PPP_ERR_CAPACITY, "path coverage: a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
+        if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, "path coverage count corrupt");
+        h->pcov_covered = (size_t)res[0];
+        h->pcov_serial = h->gen_serial;
+    }
+    if (n) *n = N;
+    if (covered) *covered = h->pcov_covered;
+    const size_t k = std::min(cap, N);
+    if (flags && k) HIPCHK(h, copy_sync(h, flags, h->pcov_flags.p, k, hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

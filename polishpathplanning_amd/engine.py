@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -158,6 +158,7 @@ def lib():
         L.ppp_get_nodes.argtypes = [vp, C.c_int, dp, dp, dp, sz, szp]
         L.ppp_get_boundary.argtypes = [vp, C.c_int, dp, dp, dp, sz, szp, C.POINTER(C.c_int)]
         L.ppp_get_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
+        L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_eval_spline.argtypes = [vp, C.c_int, dp, sz, dp]
         L.ppp_ranged_x_index.argtypes = [vp, C.c_int, ip, sz, szp]
         L.ppp_insert_point.argtypes = [vp, ip, sz, C.c_float, dp, dp, dp, sz, szp]
@@ -685,6 +686,17 @@ class Engine:
         self._chk(self.L.ppp_get_coverage(self.h, None, 0, C.byref(n), C.byref(cov)))
         out = np.zeros(max(n.value, 1), np.uint8)
         self._chk(self.L.ppp_get_coverage(self.h, out.ctypes.data_as(C.POINTER(C.c_ubyte)), n.value, C.byref(n), C.byref(cov)))
+        return out[:n.value], cov.value
+
+    def path_coverage(self, flags=True):
+        """(flags uint8[n], covered) of the last pass's final paths: the contact model of get_coverage applied to every slice's
+        final knots, for every walk (ppp_get_path_coverage); flags=False asks for the count alone and returns (None, covered)"""
+        n = C.c_size_t(); cov = C.c_size_t()
+        self._chk(self.L.ppp_get_path_coverage(self.h, None, 0, C.byref(n), C.byref(cov)))
+        if not flags:
+            return None, cov.value
+        out = np.zeros(max(n.value, 1), np.uint8)
+        self._chk(self.L.ppp_get_path_coverage(self.h, out.ctypes.data_as(C.POINTER(C.c_ubyte)), n.value, C.byref(n), C.byref(cov)))
         return out[:n.value], cov.value
 
     def eval_spline(self, s, y):
