@@ -61,6 +61,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -75,21 +76,35 @@ struct KTimer {
     int used = 0;
 };
 
-template <typename T>
-struct DevBuf {
+/* memory owned by one object: ensure() grows it (the contents are not kept), release() frees it early, the destructor
+   frees it.  Move-only.  Device memory (DevBuf) or pinned host memory (PinBuf). */
+template <typename T, bool PINNED>
+struct OwnedBuf {
     T *p = nullptr;
     size_t cap = 0;
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~OwnedBuf() { release(); }
     hipError_t ensure(size_t n)
     {
         if (n <= cap && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        release();
         if (n == 0) n = 1;
-        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        hipError_t e = PINNED ? hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, n * sizeof(T));
         if (e == hipSuccess) cap = n;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
 };
+template <typename T> using DevBuf = OwnedBuf<T, false>;
+template <typename T> using PinBuf = OwnedBuf<T, true>;
 
 } // namespace
 
@@ -203,7 +218,7 @@ struct ppp_handle_s {
     DevBuf<float> wps_pre;
 
     DevMeta hmeta;
-    DevMeta *hmeta_pinned = nullptr; /* the hot calls end with an async copy of the device meta into it */
+    PinBuf<DevMeta> hmeta_pinned; /* the hot calls end with an async copy of the device meta into it */
     /* a new cloud's plan without the host in the middle: k_ingest_minmax's last workgroup reduces the bounds and walks the slices,
        k_win_census_auto counts the windows, both write their results to pinned memory (PlanAuto + plane table + census) */
     DevBuf<int> plan_ticket;         /* [2], zero between launches */
@@ -223,19 +238,8 @@ struct ppp_handle_s {
     int auto_S = 0;
     float auto_pad = 0.f;
     bool slab_cnt_used = true;       /* a slab-path pass has been enqueued since the slab histogram was last cleared by the plan */
-    char *pin = nullptr;             /* pinned staging for the small copies of the plan (bounds partials, plane table, census) */
-    size_t pin_bytes = 0;
-    hipError_t ensure_pin(size_t bytes)
-    {
-        if (bytes <= pin_bytes) return hipSuccess;
-        if (pin) { (void)hipHostFree(pin); pin = nullptr; pin_bytes = 0; }
-        const size_t want = std::max<size_t>(bytes, 128 * 1024);
-        hipError_t e = hipHostMalloc((void **)&pin, want, hipHostMallocDefault);
-        if (e == hipSuccess) pin_bytes = want;
-        return e;
-    }
-    char *pcd_stage[2] = {nullptr, nullptr}; /* ppp_set_cloud_pcd: two pinned pieces ... */
-    size_t pcd_stage_bytes = 0;
+    PinBuf<char> pin;                /* pinned staging for the small copies of the plan (bounds partials, plane table, census) */
+    PinBuf<char> pcd_stage[2];       /* ppp_set_cloud_pcd: two pinned pieces ... */
     hipEvent_t pcd_ev[2] = {nullptr, nullptr}; /* ... and the event behind each one's copy */
     bool meta_in_flight = false;
     /* A cloud set while the handle holds a window plan of an earlier cloud of the same size and parameters does not wait for its
@@ -253,7 +257,7 @@ struct ppp_handle_s {
     int out2_cap = 0;
     float *last_out2 = nullptr;     /* where the last batch put this handle's list: a re-run after an LDS overflow writes there too */
     int last_out2_cap = 0;
-    std::shared_ptr<struct BatchMetas> bmetas; /* batched launches publish every member's meta block in one pinned array ... */
+    std::shared_ptr<PinBuf<DevMeta>> bmetas; /* batched launches publish every member's meta block in one pinned array ... */
     size_t bslot = 0;                          /* ... this handle's is entry bslot */
     bool meta_from_batch = false;
     int internal = 0;               /* > 0 while GenPath / getPath are enqueued on behalf of a batch or a re-run (keeps last_out2) */
@@ -278,31 +282,17 @@ struct ppp_handle_s {
     void drop_batch();
     ~ppp_handle_s()
     {
+        /* the members' buffers are freed after this body, on the device it selects (`back` lives on the same device) */
         (void)hipSetDevice(device);
-        X.release(); Y.release(); Z.release(); Xp.release(); Yp.release(); Zp.release(); part_idx.release(); unsorted4.release(); sorted4.release();
-        slab_cnt.release(); slab_start.release(); slab_cursor.release(); coarse_cursor.release(); slab_ytab.release(); slab_xmin.release(); slab_xmax.release();
-        meta.release(); px.release(); lo.release(); hi.release(); node_x.release(); node_y.release(); node_z.release();
-        normals4.release(); dyn_raw_sc.release(); cov_flags.release(); cov_count.release(); pcov_flags.release(); pcov_count.release(); dyn_bnd_pts.release(); dyn_adj_pts.release(); dyn_first_ab.release(); dyn_first_snap.release(); dyn_first_node.release(); ell_cs.release(); dyn_bnd_knots.release(); dyn_bnd_n.release(); plan_ticket.release(); plan_auto.release();
-        node_start.release(); node_cnt.release(); band_cnt.release(); wp_cnt.release(); wp_off.release(); tail.release(); slice_wpcnt.release();
-        wp_xyz.release(); wp_normal.release(); wp_nn.release(); wp_pre.release(); wp_smooth.release(); wp_out.release();
-        mm_part.release(); big_slabs.release(); big_slices.release(); arena.release(); scratch.release(); pack_tab.release(); pack_out.release();
-        win_px.release(); win_cnt.release(); win_pts.release(); win_part.release(); wps_xyz.release(); wps_normal.release(); wps_nn.release(); wps_pre.release(); wps_rec.release();
         drop_graph();
         drop_batch();
-        if (hmeta_pinned) (void)hipHostFree(hmeta_pinned);
-        for (int b = 0; b < 2; ++b) { if (pcd_stage[b]) (void)hipHostFree(pcd_stage[b]); if (pcd_ev[b]) (void)hipEventDestroy(pcd_ev[b]); }
-        if (pin) (void)hipHostFree(pin);
+        for (int b = 0; b < 2; ++b) if (pcd_ev[b]) (void)hipEventDestroy(pcd_ev[b]);
         for (auto &t : timers) { for (auto e : t.e0) (void)hipEventDestroy(e); for (auto e : t.e1) (void)hipEventDestroy(e); }
         if (stream) (void)hipStreamDestroy(stream);
         if (back) { delete back; back = nullptr; }
     }
 };
 
-/* the meta blocks of a batch on the host (pinned), shared by the batch graph and the member handles that read them */
-struct BatchMetas {
-    DevMeta *pinned = nullptr;
-    ~BatchMetas() { if (pinned) (void)hipHostFree(pinned); }
-};
 struct BatchGraph {
     std::vector<ppp_handle> hs;
     std::vector<unsigned> epochs;
@@ -326,14 +316,13 @@ struct BatchGraph {
     bool win_staged = false;
     size_t win_lds = 0, win_scat_lds = 0, win_fin_lds = 0;
     DevBuf<DevMeta> metas;
-    std::shared_ptr<BatchMetas> hmetas;
+    std::shared_ptr<PinBuf<DevMeta>> hmetas; /* the meta blocks on the host, shared with the member handles that read them */
     ~BatchGraph()
     {
         if (ge) (void)hipGraphExecDestroy(ge);
         if (g) (void)hipGraphDestroy(g);
         if (fork) (void)hipEventDestroy(fork);
         for (auto e : join) if (e) (void)hipEventDestroy(e);
-        members.release(); wmembers.release(); metas.release();
     }
 };
 void ppp_handle_s::drop_batch()
@@ -506,9 +495,9 @@ int enqueue_normals(ppp_handle h)
     return PPP_OK;
 }
 
-/* pinned layout of the plan results of a new cloud */
+/* pinned layout of the plan results of a new cloud; the staging is never allocated smaller than PIN_MIN */
 constexpr size_t PIN_REC0 = 0, PIN_REC1 = 64, PIN_PX = 128, PIN_CENSUS = PIN_PX + sizeof(float) * WIN_AUTO_SCAP,
-                 PIN_AUTO_BYTES = PIN_CENSUS + sizeof(int) * 3 * WIN_AUTO_SCAP;
+                 PIN_AUTO_BYTES = PIN_CENSUS + sizeof(int) * 3 * WIN_AUTO_SCAP, PIN_MIN = 128 * 1024;
 
 /* Threads of a slice workgroup for a launch of `wgs` of them.  The kernel holds 116 VGPRs, i.e. 16 waves per CU.  While a
    launch has fewer workgroups than the device has room for, a workgroup is as wide as its work can use (a left point per
@@ -582,8 +571,8 @@ int plan_window(ppp_handle h, int S, double per)
     HIPCHK(h, h->win_px.ensure((size_t)S)); HIPCHK(h, h->win_cnt.ensure(std::max<size_t>(3, WIN_CNT_STRIDE) * (size_t)S));
     /* a cloud that has just been set brought its census along (refresh_bounds_and_plan): taken when the device's walk, slice count
        and pad are this plan's, bit for bit */
-    const bool walk_ok = !h->use_part && h->auto_S == S && S <= WIN_AUTO_SCAP && h->pin &&
-                         memcmp(&h->auto_pad, &pad, sizeof(float)) == 0 && memcmp(h->pin + PIN_PX, px.data(), sizeof(float) * (size_t)S) == 0;
+    const bool walk_ok = !h->use_part && h->auto_S == S && S <= WIN_AUTO_SCAP && h->pin.p &&
+                         memcmp(&h->auto_pad, &pad, sizeof(float)) == 0 && memcmp(h->pin.p + PIN_PX, px.data(), sizeof(float) * (size_t)S) == 0;
     const bool from_auto = h->auto_valid && walk_ok;
     /* ... or it brought the walk only, and the capacities of an earlier cloud's plan apply (refresh_bounds_and_plan) */
     const bool inherit = !from_auto && h->auto_px_only && walk_ok && h->inh_valid && h->inh_S == S && memcmp(&h->inh_pad, &pad, sizeof(float)) == 0 &&
@@ -593,7 +582,7 @@ int plan_window(ppp_handle h, int S, double per)
     h->plan_walk_ok = from_auto || inherit;
     int *census = nullptr;
     std::vector<int> inherited;
-    if (from_auto) census = (int *)(h->pin + PIN_CENSUS);
+    if (from_auto) census = (int *)(h->pin.p + PIN_CENSUS);
     else if (inherit) { /* every window as full as the fullest of the earlier cloud, + 4 % */
         inherited.assign(3 * (size_t)S, 0);
         for (int s2 = 0; s2 < S; ++s2) {
@@ -603,8 +592,8 @@ int plan_window(ppp_handle h, int S, double per)
         census = inherited.data();
         h->plan_inherited = true;
     } else {
-    HIPCHK(h, h->ensure_pin(sizeof(float) * 4 * (size_t)S));
-    float *px_pin = (float *)h->pin;
+    HIPCHK(h, h->pin.ensure(std::max(sizeof(float) * 4 * (size_t)S, PIN_MIN)));
+    float *px_pin = (float *)h->pin.p;
     census = (int *)(px_pin + S);
     memcpy(px_pin, px.data(), sizeof(float) * (size_t)S);
     memset(census, 0, sizeof(int) * 3 * (size_t)S);
@@ -728,7 +717,7 @@ WinArgs win_args(const ppp_handle h)
     A.wps_xyz = h->wps_xyz.p; A.wps_normal = h->wps_normal.p; A.wps_nn = h->wps_nn.p; A.wps_pre = h->wps_pre.p; A.wps_rec = h->wps_rec.p;
     A.wp_pre = h->wp_pre.p; A.wp_smooth = h->wp_smooth.p; A.wp_out = h->wp_out.p; A.out2 = h->out2; A.out2_cap = h->out2_cap;
     A.plan_rec = (h->rec_current && h->plan_walk_ok) ? h->plan_auto.p : nullptr;
-    A.meta_host = h->hmeta_pinned; A.fin_ticket = h->fin_ticket.p; /* (a member of a batch of several publishes into the batch's pinned array: upload_members_win) */
+    A.meta_host = h->hmeta_pinned.p; A.fin_ticket = h->fin_ticket.p; /* (a member of a batch of several publishes into the batch's pinned array: upload_members_win) */
     return A;
 }
 size_t win_slice_lds(const ppp_handle h) { return win_slice_lds_for(h, h->win_NBc); }
@@ -767,6 +756,25 @@ int enqueue_window_finish(ppp_handle h)
 {
     const WinArgs A = win_args(h);
     LAUNCH(h, "k_win_finish", k_win_finish, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
+    return PPP_OK;
+}
+
+/* ordered compaction (ppp_preproc.h) of the n elements sel keeps: the block counts in cnt[0 .. n / COMPACT_CHUNK], their
+   scan (the kept total to *total, on the device), the emit.  sized (the range part, whose output is sized by the total):
+   the total is read back first, and sized(total) may point sel at the output before the emit. */
+template <class Sel>
+int compact(ppp_handle h, Sel &sel, int n, int *cnt, int *total, const std::function<int(int)> &sized = nullptr)
+{
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+    LAUNCH(h, "k_compact_count", k_compact_count<Sel>, nblocks, 256, 0, sel, n, cnt);
+    LAUNCH(h, "k_compact_scan", k_compact_scan, 1, 1024, 0, cnt, nblocks, total);
+    if (sized) {
+        int kept = 0;
+        HIPCHK(h, hipMemcpyAsync(&kept, total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (int rc = sized(kept)) return rc;
+    }
+    LAUNCH(h, "k_compact_emit", k_compact_emit<Sel>, nblocks, 256, 0, sel, n, cnt);
     return PPP_OK;
 }
 
@@ -812,30 +820,23 @@ int make_plan(ppp_handle h)
     } else if (h->ranged && h->sb < h->se && n > 0) {
         /* the range's own points, once per plan: the hot path then streams n_part instead of n points (the bounds, the
            walk and the slab grid stay the whole cloud's: they come from the values cached with the cloud) */
-        const int nblocks = (n + VOX_CHUNK - 1) / VOX_CHUNK;
-        DevBuf<int> bcnt;
-        DevBuf<VoxStats> st;
-        hipError_t e = bcnt.ensure(nblocks);
-        if (e == hipSuccess) e = st.ensure(1);
-        if (e != hipSuccess) { bcnt.release(); st.release(); return fail(h, PPP_ERR_HIP, std::string("range part: ") + hipGetErrorString(e)); }
-        VoxStats hst{0};
-        auto run = [&]() -> int {
-            LAUNCH(h, "k_part_count", k_part_count, nblocks, 256, 0, h->X.p, n, h->incl_lo, h->incl_hi, bcnt.p);
-            LAUNCH(h, "k_vox_scan", k_vox_scan, 1, 1024, 0, bcnt.p, nblocks, st.p);
-            HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(VoxStats), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            const size_t np = (size_t)std::max(hst.n_out, 1);
+        const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+        DevBuf<int> bcnt; /* block counts, then the total */
+        hipError_t e = bcnt.ensure((size_t)nblocks + 1);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("range part: ") + hipGetErrorString(e));
+        PartSel sel{h->X.p, h->Y.p, h->Z.p, h->incl_lo, h->incl_hi};
+        int n_part = 0;
+        int rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks, [&](int kept) -> int {
+            const size_t np = (size_t)std::max(kept, 1);
             HIPCHK(h, h->Xp.ensure(np)); HIPCHK(h, h->Yp.ensure(np)); HIPCHK(h, h->Zp.ensure(np)); HIPCHK(h, h->part_idx.ensure(np));
-            LAUNCH(h, "k_part_compact", k_part_compact, nblocks, 256, 0, h->X.p, h->Y.p, h->Z.p, n, h->incl_lo, h->incl_hi, bcnt.p, h->Xp.p,
-                   h->Yp.p, h->Zp.p, h->part_idx.p);
-            HIPCHK(h, hipStreamSynchronize(h->stream));
+            sel.X2 = h->Xp.p; sel.Y2 = h->Yp.p; sel.Z2 = h->Zp.p; sel.idx2 = h->part_idx.p;
+            n_part = kept;
             return PPP_OK;
-        };
-        const int rcp = run();
-        bcnt.release(); st.release();
-        if (rcp != PPP_OK) return rcp;
-        h->n_part = hst.n_out;
-        h->n_range = hst.n_out;
+        });
+        if (rc) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->n_part = n_part;
+        h->n_range = n_part;
         h->use_part = true;
     }
     /* x-slabs: the histogram must fit LDS.  A slice-range handle
@@ -1100,7 +1101,7 @@ int fetch_meta(ppp_handle h)
     { int rc = settle(h); if (rc) return rc; }
     if (h->meta_in_flight) { /* GenPath / getPath already enqueued the copy behind their last kernel */
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->hmeta = (h->meta_from_batch && h->bmetas) ? h->bmetas->pinned[h->bslot] : *h->hmeta_pinned;
+        h->hmeta = (h->meta_from_batch && h->bmetas) ? h->bmetas->p[h->bslot] : *h->hmeta_pinned.p;
         h->meta_in_flight = false;
         h->meta_fresh = true;
         return PPP_OK;
@@ -1116,7 +1117,7 @@ int fetch_meta(ppp_handle h)
 
 int enqueue_meta_copy(ppp_handle h)
 {
-    HIPCHK(h, hipMemcpyAsync(h->hmeta_pinned, h->meta.p, sizeof(DevMeta), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->hmeta_pinned.p, h->meta.p, sizeof(DevMeta), hipMemcpyDeviceToHost, h->stream));
     h->meta_in_flight = true;
     h->meta_from_batch = false;
     return PPP_OK;
@@ -1235,7 +1236,7 @@ bool window_params_ok(const ppp_handle h)
 /* what k_ingest_minmax (and the census behind it) left in pinned memory for the host: bounds, count, the device's walk */
 int adopt_ingest_record(ppp_handle h, bool census, bool reuse)
 {
-    const PlanAuto *rec0 = (const PlanAuto *)(h->pin + PIN_REC0), *rec1 = (const PlanAuto *)(h->pin + PIN_REC1);
+    const PlanAuto *rec0 = (const PlanAuto *)(h->pin.p + PIN_REC0), *rec1 = (const PlanAuto *)(h->pin.p + PIN_REC1);
     if (rec0->S == -2) return fail(h, PPP_ERR_HIP, "the bounds of the new cloud did not arrive");
     h->h_nvalid = rec0->fin.cnt;
     for (int d = 0; d < 3; ++d) { h->h_mn[d] = rec0->fin.mn[d]; h->h_mx[d] = rec0->fin.mx[d]; }
@@ -1255,7 +1256,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
         HIPCHK(h, h->mm_part.ensure(g));
         (void)hipGetLastError();
         if (raw) {
-            HIPCHK(h, h->ensure_pin(PIN_AUTO_BYTES));
+            HIPCHK(h, h->pin.ensure(std::max(PIN_AUTO_BYTES, PIN_MIN)));
             if (!h->plan_ticket.p) {
                 HIPCHK(h, h->plan_ticket.ensure(2)); HIPCHK(h, h->plan_auto.ensure(1));
                 HIPCHK(h, hipMemsetAsync(h->plan_ticket.p, 0, 2 * sizeof(int), h->stream));
@@ -1268,11 +1269,11 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                 HIPCHK(h, hipMemsetAsync(h->win_cnt.p, 0, sizeof(int) * 3 * (size_t)WIN_AUTO_SCAP, h->stream)); /* every census and every pass leaves them cleared */
             }
             PlanAutoArgs PA;
-            PA.ticket = h->plan_ticket.p; PA.dev = h->plan_auto.p; PA.host = (PlanAuto *)(h->pin + PIN_REC0);
+            PA.ticket = h->plan_ticket.p; PA.dev = h->plan_auto.p; PA.host = (PlanAuto *)(h->pin.p + PIN_REC0);
             PA.walk = census ? h->P.walk : -1; PA.tool_radius = h->P.tool_radius; PA.normal_radius = h->P.normal_radius;
             PA.px = h->win_px.p; PA.px_cap = census ? WIN_AUTO_SCAP : 0;
-            PA.px_host = reuse ? (float *)(h->pin + PIN_PX) : nullptr;
-            PlanAuto *rec0 = (PlanAuto *)(h->pin + PIN_REC0), *rec1 = (PlanAuto *)(h->pin + PIN_REC1);
+            PA.px_host = reuse ? (float *)(h->pin.p + PIN_PX) : nullptr;
+            PlanAuto *rec0 = (PlanAuto *)(h->pin.p + PIN_REC0), *rec1 = (PlanAuto *)(h->pin.p + PIN_REC1);
             rec0->S = -2; rec1->census = 0; rec1->S = -2;
             hipLaunchKernelGGL(k_ingest_minmax, dim3(ingest_grid(n)), dim3(MM_T), 0, h->stream, raw, stride_bytes, (int)n, h->P.change_range, h->X.p, h->Y.p,
                                h->Z.p, h->mm_part.p, PA);
@@ -1281,7 +1282,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                 const int gc = std::max(1, std::min(((int)n + 4095) / 4096, 512));
                 hipLaunchKernelGGL(k_win_census_auto, dim3(gc), dim3(256), sizeof(int) * 3 * (size_t)WIN_AUTO_SCAP, h->stream, h->X.p, (int)n,
                                    h->win_px.p, h->plan_auto.p, 1.0f / (float)(int)(h->P.tool_radius * 2), h->win_cnt.p, h->plan_ticket.p + 1, rec1,
-                                   (float *)(h->pin + PIN_PX), (int *)(h->pin + PIN_CENSUS));
+                                   (float *)(h->pin.p + PIN_PX), (int *)(h->pin.p + PIN_CENSUS));
                 HIPCHK(h, hipGetLastError());
             }
             h->rec_current = true;
@@ -1316,8 +1317,8 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                                (int *)nullptr, 0.f, 0.f, (int *)nullptr);
             HIPCHK(h, hipGetLastError());
             /* (through pinned memory: a copy into pageable memory is staged by the runtime, ~10 us more on this critical path) */
-            HIPCHK(h, h->ensure_pin(sizeof(MinMaxPart) * (size_t)g));
-            MinMaxPart *parts = (MinMaxPart *)h->pin;
+            HIPCHK(h, h->pin.ensure(std::max(sizeof(MinMaxPart) * (size_t)g, PIN_MIN)));
+            MinMaxPart *parts = (MinMaxPart *)h->pin.p;
             HIPCHK(h, hipMemcpyAsync(parts, h->mm_part.p, sizeof(MinMaxPart) * g, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             h->h_nvalid = 0;
@@ -1448,7 +1449,7 @@ int ppp_create(int device_id, ppp_handle *out)
        from this block: hipMalloc does not clear it */
     if (hipMemset(h->meta.p, 0, sizeof(DevMeta)) != hipSuccess) { delete h; return PPP_ERR_HIP; }
     if (h->fin_ticket.ensure(1 + WIN_FIN_GROUPS) != hipSuccess || hipMemset(h->fin_ticket.p, 0, sizeof(int) * (1 + WIN_FIN_GROUPS)) != hipSuccess) { delete h; return PPP_ERR_HIP; }
-    if (hipHostMalloc((void **)&h->hmeta_pinned, sizeof(DevMeta), hipHostMallocDefault) != hipSuccess) { delete h; return PPP_ERR_HIP; }
+    if (h->hmeta_pinned.ensure(1) != hipSuccess) { delete h; return PPP_ERR_HIP; }
     int lds = 0;
     if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device_id) == hipSuccess && lds > 0) h->max_lds = lds;
     hipDeviceProp_t prop;
@@ -1606,12 +1607,7 @@ int ppp_set_cloud_pcd(ppp_handle h, const char *path, size_t *n_out, float viewp
     const size_t bytes = L.points * L.record_bytes;
     HIPCHK(h, h->scratch.ensure(bytes));
     const size_t piece = std::min(PCD_PIECE, (bytes + 4095) & ~(size_t)4095);
-    if (h->pcd_stage_bytes < piece) {
-        for (int b = 0; b < 2; ++b) { if (h->pcd_stage[b]) (void)hipHostFree(h->pcd_stage[b]); h->pcd_stage[b] = nullptr; }
-        h->pcd_stage_bytes = 0;
-        for (int b = 0; b < 2; ++b) HIPCHK(h, hipHostMalloc((void **)&h->pcd_stage[b], piece, hipHostMallocDefault));
-        h->pcd_stage_bytes = piece;
-    }
+    for (int b = 0; b < 2; ++b) HIPCHK(h, h->pcd_stage[b].ensure(piece));
     for (int b = 0; b < 2; ++b) if (!h->pcd_ev[b]) HIPCHK(h, hipEventCreateWithFlags(&h->pcd_ev[b], hipEventDisableTiming));
     const int fd = open(path, O_RDONLY | O_CLOEXEC);
     if (fd < 0) return fail(h, PPP_ERR_IO, std::string("cannot open ") + path);
@@ -1620,12 +1616,12 @@ int ppp_set_cloud_pcd(ppp_handle h, const char *path, size_t *n_out, float viewp
     size_t done = 0;
     for (int k = 0; done < bytes && io_ok && he == hipSuccess; ++k) {
         const int b = k & 1;
-        const size_t len = std::min(h->pcd_stage_bytes, bytes - done);
+        const size_t len = std::min(piece, bytes - done);
         if (k >= 2) he = hipEventSynchronize(h->pcd_ev[b]); /* the copy that last read this buffer */
         if (he != hipSuccess) break;
-        io_ok = read_piece(fd, h->pcd_stage[b], len, L.data_offset + (long long)done);
+        io_ok = read_piece(fd, h->pcd_stage[b].p, len, L.data_offset + (long long)done);
         if (!io_ok) break;
-        he = hipMemcpyAsync(h->scratch.p + done, h->pcd_stage[b], len, hipMemcpyHostToDevice, h->stream);
+        he = hipMemcpyAsync(h->scratch.p + done, h->pcd_stage[b].p, len, hipMemcpyHostToDevice, h->stream);
         if (he == hipSuccess) he = hipEventRecord(h->pcd_ev[b], h->stream);
         done += len;
     }
@@ -1776,48 +1772,60 @@ int cloud_changed(ppp_handle h)
     return rc;
 }
 
-} // namespace
-
-int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float *covariance9)
+/* the opening of the preprocessing calls: a whole-cloud handle with a cloud, settled on its device.  bad_arg: the
+   caller's message for an invalid argument, reported between the two checks (ppp_remove_outlier's order) */
+int preproc_begin(ppp_handle h, const char *bad_arg = nullptr)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     { int rcs = settle(h); if (rcs) return rcs; }
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
+    if (bad_arg) return fail(h, PPP_ERR_ARG, bad_arg);
     if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
+    return PPP_OK;
+}
+
+/* the filtered cloud of n points replaces the resident one (filter(*cloud)).  The callers free their scratch first: hipFree
+   waits for the device, and behind this call it would wait for the launches of the new plan. */
+int adopt_cloud(ppp_handle h, DevBuf<float> &X2, DevBuf<float> &Y2, DevBuf<float> &Z2, size_t n)
+{
+    h->X = std::move(X2); h->Y = std::move(Y2); h->Z = std::move(Z2);
+    h->n = n;
+    h->drop_graph();
+    return cloud_changed(h);
+}
+
+} // namespace
+
+int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float *covariance9)
+{
+    int rc = preproc_begin(h);
+    if (rc) return rc;
     if (h->aligned) return fail(h, PPP_ERR_ARG, "the cloud is aligned already (TransAlign would be overwritten): set the cloud again");
     const int n = (int)h->n;
     if (n == 0 || h->h_nvalid == 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
-    const size_t stride = ((size_t)n + 3) & ~(size_t)3;
-    DevBuf<float> V, sums;
-    auto cleanup = [&]() { V.release(); sums.release(); };
-    hipError_t e = V.ensure(6 * stride);
-    if (e == hipSuccess) e = sums.ensure(8);
-    if (e != hipSuccess) { cleanup(); return fail(h, PPP_ERR_HIP, std::string("trans2center buffers: ") + hipGetErrorString(e)); }
     float hs[6] = {0, 0, 0, 0, 0, 0}, c[3] = {0, 0, 0};
     const int hcnt = h->h_nvalid; /* the finite points, counted with the bounds */
     const unsigned gb = (unsigned)((n + 255) / 256);
-    auto phase1 = [&]() -> int { /* pcl::compute3DCentroid: three running float sums, / float(count) */
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        const size_t stride = ((size_t)n + 3) & ~(size_t)3;
+        DevBuf<float> V, sums;
+        hipError_t e = V.ensure(6 * stride);
+        if (e == hipSuccess) e = sums.ensure(8);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("trans2center buffers: ") + hipGetErrorString(e));
+        /* pcl::compute3DCentroid: three running float sums, / float(count) */
         LAUNCH(h, "k_seq_prep_centroid", k_seq_prep_centroid, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, stride, V.p);
         LAUNCH(h, "k_seq_sum", k_seq_sum, 3, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
         HIPCHK(h, hipMemcpyAsync(hs, sums.p, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    auto phase2 = [&]() -> int { /* pcl::computeCovarianceMatrix: six running float sums of float products */
+        if (hcnt <= 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
+        for (int d = 0; d < 3; ++d) c[d] = hs[d] / static_cast<float>(hcnt);
+        /* pcl::computeCovarianceMatrix: six running float sums of float products */
         LAUNCH(h, "k_seq_prep_cov", k_seq_prep_cov, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, c[0], c[1], c[2], stride, V.p);
         LAUNCH(h, "k_seq_sum", k_seq_sum, 6, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
         HIPCHK(h, hipMemcpyAsync(hs, sums.p, 6 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    int rc = phase1();
-    if (rc == PPP_OK && hcnt <= 0) rc = fail(h, PPP_ERR_ARG, "no finite point to align");
-    if (rc == PPP_OK) {
-        for (int d = 0; d < 3; ++d) c[d] = hs[d] / static_cast<float>(hcnt);
-        rc = phase2();
     }
-    if (rc != PPP_OK) { cleanup(); return rc; }
     float cov[3][3];
     cov[1][1] = hs[0]; cov[1][2] = hs[1]; cov[2][2] = hs[2]; cov[0][0] = hs[3]; cov[0][1] = hs[4]; cov[0][2] = hs[5];
     cov[1][0] = cov[0][1]; cov[2][0] = cov[0][2]; cov[2][1] = cov[1][2];
@@ -1825,23 +1833,16 @@ int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float
     if (covariance9) for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) covariance9[3 * i + j] = cov[i][j];
     ppp_align::EigenSolver3f es;
     es.compute(cov);
-    if (es.complex_pair || !es.converged) {
-        cleanup();
+    if (es.complex_pair || !es.converged)
         return fail(h, PPP_ERR_DOMAIN, "trans2center: the float Schur form of the covariance keeps a complex pair (two equal extents) or did not converge");
-    }
     ppp_align::trans_align(es, c, h->TA);
     ppp_align::inverse4(h->TA, h->invTA);
     if (trans_align16) for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) trans_align16[4 * i + j] = h->TA[i][j];
-    auto phase3 = [&]() -> int { /* pcl::transformPointCloud(*cloud, *cloud, TransAlign) */
-        Mat34 M;
-        for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 4; ++cc) M.m[r][cc] = h->TA[r][cc];
-        LAUNCH(h, "k_transform_se3", k_transform_se3, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    rc = phase3();
-    cleanup();
-    if (rc != PPP_OK) return rc;
+    /* pcl::transformPointCloud(*cloud, *cloud, TransAlign) */
+    Mat34 M;
+    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 4; ++cc) M.m[r][cc] = h->TA[r][cc];
+    LAUNCH(h, "k_transform_se3", k_transform_se3, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->aligned = true;
     h->drop_graph();
     return cloud_changed(h);
@@ -1849,18 +1850,9 @@ int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float
 
 int ppp_remove_outlier(ppp_handle h, int mean_k, double stddev_mul, size_t *n_kept, double *threshold)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rcs = settle(h); if (rcs) return rcs; }
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (mean_k < 1 || mean_k > 63) return fail(h, PPP_ERR_ARG, "mean_k must be in [1, 63]");
-    if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
-    int rc = ensure_index(h);
+    int rc = preproc_begin(h, (mean_k < 1 || mean_k > 63) ? "mean_k must be in [1, 63]" : nullptr);
     if (rc) return rc;
-    rc = fetch_meta(h);
-    if (rc) return rc;
-    if (overflowed_fast_path(h)) { h->big_path = true; h->drop_graph(); HIPCHK(h, h->arena.ensure((size_t)64 * std::max<size_t>(h->n, 1) + (1u << 20))); rc = enqueue_index(h); if (rc) return rc; rc = fetch_meta(h); if (rc) return rc; }
-    rc = map_dev_err(h);
+    rc = index_ready(h);
     if (rc) return rc;
     const int n = (int)h->n, ns = h->hmeta.n_sorted;
     if (ns < mean_k + 1) return fail(h, PPP_ERR_ARG, "fewer finite points than mean_k + 1 (PCL reads past its neighbour vectors here)");
@@ -1868,55 +1860,46 @@ int ppp_remove_outlier(ppp_handle h, int mean_k, double stddev_mul, size_t *n_ke
     const double area = ((double)h->h_mx[0] - h->h_mn[0]) * ((double)h->h_mx[1] - h->h_mn[1]);
     const double rho = (area > 0 && h->h_nvalid > 0) ? (double)h->h_nvalid / area : 1.0;
     const float r0 = (float)std::max(0.5, 1.25 * std::sqrt((double)(mean_k + 1) / (3.14159265358979 * rho)));
-    const int nblocks = (n + SOR_CHUNK - 1) / SOR_CHUNK, nparts = std::max(1, std::min(1024, (n + 255) / 256));
-    DevBuf<float> dist, X2, Y2, Z2;
-    DevBuf<double> part;
-    DevBuf<int> bcnt;
-    DevBuf<SorStats> st;
-    auto cleanup = [&]() { dist.release(); X2.release(); Y2.release(); Z2.release(); part.release(); bcnt.release(); st.release(); };
-    hipError_t e = dist.ensure(n);
-    if (e == hipSuccess) e = X2.ensure(n);
-    if (e == hipSuccess) e = Y2.ensure(n);
-    if (e == hipSuccess) e = Z2.ensure(n);
-    if (e == hipSuccess) e = part.ensure(2 * (size_t)nparts);
-    if (e == hipSuccess) e = bcnt.ensure(nblocks);
-    if (e == hipSuccess) e = st.ensure(1);
-    if (e != hipSuccess) { cleanup(); return fail(h, PPP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nparts = std::max(1, std::min(1024, (n + 255) / 256));
+    DevBuf<float> X2, Y2, Z2;
     SorStats hst;
-    auto run = [&]() -> int {
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<float> dist;
+        DevBuf<double> part;
+        DevBuf<int> bcnt;
+        DevBuf<SorStats> st;
+        hipError_t e = dist.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e == hipSuccess) e = part.ensure(2 * (size_t)nparts);
+        if (e == hipSuccess) e = bcnt.ensure(nblocks);
+        if (e == hipSuccess) e = st.ensure(1);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
         HIPCHK(h, hipMemsetAsync(dist.p, 0, sizeof(float) * (size_t)n, h->stream)); /* non-finite points: distance 0 */
         LAUNCH(h, "k_sor_dist", k_sor_dist, (unsigned)((ns + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, h->sorted4.p, h->slab_start.p,
                h->slab_xmin.p, h->slab_xmax.p, mean_k, r0, dist.p);
         LAUNCH(h, "k_sor_partial", k_sor_partial, nparts, 256, 0, dist.p, n, part.p);
         LAUNCH(h, "k_sor_threshold", k_sor_threshold, 1, 256, 0, h->meta.p, part.p, nparts, stddev_mul, st.p);
-        LAUNCH(h, "k_sor_count", k_sor_count, nblocks, 256, 0, dist.p, n, st.p, bcnt.p);
-        LAUNCH(h, "k_sor_scan", k_sor_scan, 1, 1024, 0, bcnt.p, nblocks, st.p);
-        LAUNCH(h, "k_sor_compact", k_sor_compact, nblocks, 256, 0, dist.p, n, st.p, bcnt.p, h->X.p, h->Y.p, h->Z.p, X2.p, Y2.p, Z2.p);
+        SorSel sel{dist.p, st.p, h->X.p, h->Y.p, h->Z.p, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, &st.p->n_kept);
+        if (rc) return rc;
         HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(SorStats), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    rc = run();
-    if (rc == PPP_OK) { h->meta_in_flight = false; h->meta_fresh = false; rc = fetch_meta(h); }
+    }
+    h->meta_in_flight = false; h->meta_fresh = false;
+    rc = fetch_meta(h);
     if (rc == PPP_OK) rc = map_dev_err(h);
-    if (rc != PPP_OK) { cleanup(); return rc; }
-    /* the filtered cloud replaces the resident one (sor.filter(*cloud)) */
-    std::swap(h->X, X2); std::swap(h->Y, Y2); std::swap(h->Z, Z2);
-    h->n = (size_t)hst.n_kept;
-    if (n_kept) *n_kept = h->n;
+    if (rc) return rc;
+    if (n_kept) *n_kept = (size_t)hst.n_kept;
     if (threshold) *threshold = hst.threshold;
-    cleanup();
-    h->drop_graph();
-    return cloud_changed(h);
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)hst.n_kept);
 }
 
 int ppp_voxel_down(ppp_handle h, float lx, float ly, float lz, size_t *n_out, int *overflow)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rcs = settle(h); if (rcs) return rcs; }
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
+    int rc = preproc_begin(h);
+    if (rc) return rc;
     if (!(lx > 0.f) || !(ly > 0.f) || !(lz > 0.f) || !std::isfinite(lx) || !std::isfinite(ly) || !std::isfinite(lz))
         return fail(h, PPP_ERR_ARG, "leaf sizes must be positive and finite");
     if (overflow) *overflow = 0;
@@ -1950,86 +1933,64 @@ int ppp_voxel_down(ppp_handle h, float lx, float ly, float lz, size_t *n_out, in
     g.none = (unsigned)cells;
     int end_bit = 1;
     while (end_bit < 32 && (cells >> end_bit)) ++end_bit;
-    const int nblocks = (n + VOX_CHUNK - 1) / VOX_CHUNK;
-    DevBuf<unsigned> key, key2;
-    DevBuf<int> idx, idx2, bcnt;
-    DevBuf<char> tmp;
-    DevBuf<float4> pts;
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
     DevBuf<float> X2, Y2, Z2;
-    DevBuf<VoxStats> st;
-    auto cleanup = [&]() { key.release(); key2.release(); idx.release(); idx2.release(); bcnt.release(); tmp.release(); pts.release();
-                           X2.release(); Y2.release(); Z2.release(); st.release(); };
-    size_t tmp_bytes = 0;
-    hipError_t e = ppp_sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, end_bit, h->stream);
-    if (e == hipSuccess) e = key.ensure(n);
-    if (e == hipSuccess) e = key2.ensure(n);
-    if (e == hipSuccess) e = idx.ensure(n);
-    if (e == hipSuccess) e = idx2.ensure(n);
-    if (e == hipSuccess) e = bcnt.ensure(nblocks);
-    if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
-    if (e == hipSuccess) e = pts.ensure(n);
-    if (e == hipSuccess) e = X2.ensure(n);
-    if (e == hipSuccess) e = Y2.ensure(n);
-    if (e == hipSuccess) e = Z2.ensure(n);
-    if (e == hipSuccess) e = st.ensure(1);
-    if (e != hipSuccess) { cleanup(); return fail(h, PPP_ERR_HIP, std::string("voxel_down buffers: ") + hipGetErrorString(e)); }
-    VoxStats hst{0};
-    auto run = [&]() -> int {
+    int n_vox = 0;
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<unsigned> key, key2;
+        DevBuf<int> idx, idx2, bcnt;
+        DevBuf<char> tmp;
+        DevBuf<float4> pts;
+        size_t tmp_bytes = 0;
+        hipError_t e = ppp_sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, end_bit, h->stream);
+        if (e == hipSuccess) e = key.ensure(n);
+        if (e == hipSuccess) e = key2.ensure(n);
+        if (e == hipSuccess) e = idx.ensure(n);
+        if (e == hipSuccess) e = idx2.ensure(n);
+        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
+        if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
+        if (e == hipSuccess) e = pts.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("voxel_down buffers: ") + hipGetErrorString(e));
         const unsigned gb = (unsigned)((n + 255) / 256);
         LAUNCH(h, "k_vox_key", k_vox_key, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, g, key.p, idx.p);
         HIPCHK(h, ppp_sort_pairs_u32(tmp.p, &tmp_bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, end_bit, h->stream));
-        LAUNCH(h, "k_vox_count", k_vox_count, nblocks, 256, 0, key2.p, n, g.none, bcnt.p);
-        LAUNCH(h, "k_vox_scan", k_vox_scan, 1, 1024, 0, bcnt.p, nblocks, st.p);
         LAUNCH(h, "k_vox_gather", k_vox_gather, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, idx2.p, n, pts.p);
-        LAUNCH(h, "k_vox_reduce", k_vox_reduce, nblocks, 256, 0, key2.p, pts.p, n, g.none, bcnt.p, X2.p, Y2.p, Z2.p);
-        HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(VoxStats), hipMemcpyDeviceToHost, h->stream));
+        VoxHeadSel sel{key2.p, pts.p, n, g.none, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&n_vox, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    int rc = run();
-    if (rc != PPP_OK) { cleanup(); return rc; }
-    std::swap(h->X, X2); std::swap(h->Y, Y2); std::swap(h->Z, Z2);
-    h->n = (size_t)hst.n_out;
-    if (n_out) *n_out = h->n;
-    cleanup();
-    h->drop_graph();
-    return cloud_changed(h);
+    }
+    if (n_out) *n_out = (size_t)n_vox;
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_vox);
 }
 
 int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rcs = settle(h); if (rcs) return rcs; }
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
+    int rc = preproc_begin(h);
+    if (rc) return rc;
     if (!(search_radius > 0) || !std::isfinite(search_radius)) return fail(h, PPP_ERR_ARG, "search radius must be positive"); /* mls.hpp: "Invalid search radius" */
     if (order < 0 || order > 3) return fail(h, PPP_ERR_ARG, "polynomial order must be in [0, 3]");
-    int rc = ensure_index(h);
-    if (rc) return rc;
-    rc = fetch_meta(h);
-    if (rc) return rc;
-    if (overflowed_fast_path(h)) { h->big_path = true; h->drop_graph(); HIPCHK(h, h->arena.ensure((size_t)64 * std::max<size_t>(h->n, 1) + (1u << 20))); rc = enqueue_index(h); if (rc) return rc; rc = fetch_meta(h); if (rc) return rc; }
-    rc = map_dev_err(h);
+    rc = index_ready(h);
     if (rc) return rc;
     const int n = (int)h->n, ns = h->hmeta.n_sorted;
     if (n_out) *n_out = h->n;
     if (n == 0) return PPP_OK;
-    const int nblocks = (n + VOX_CHUNK - 1) / VOX_CHUNK;
-    DevBuf<float4> rec;
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
     DevBuf<float> X2, Y2, Z2;
-    DevBuf<int> bcnt;
-    DevBuf<VoxStats> st;
-    auto cleanup = [&]() { rec.release(); X2.release(); Y2.release(); Z2.release(); bcnt.release(); st.release(); };
-    hipError_t e = rec.ensure(n);
-    if (e == hipSuccess) e = X2.ensure(n);
-    if (e == hipSuccess) e = Y2.ensure(n);
-    if (e == hipSuccess) e = Z2.ensure(n);
-    if (e == hipSuccess) e = bcnt.ensure(nblocks);
-    if (e == hipSuccess) e = st.ensure(1);
-    if (e != hipSuccess) { cleanup(); return fail(h, PPP_ERR_HIP, std::string("smooth buffers: ") + hipGetErrorString(e)); }
-    VoxStats hst{0};
-    auto run = [&]() -> int {
+    int n_kept = 0;
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<float4> rec;
+        DevBuf<int> bcnt;
+        hipError_t e = rec.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("smooth buffers: ") + hipGetErrorString(e));
         HIPCHK(h, hipMemsetAsync(rec.p, 0, sizeof(float4) * (size_t)n, h->stream));
         const unsigned gb = (unsigned)((std::max(ns, 1) + 255) / 256);
         const float rf = (float)search_radius;
@@ -2037,23 +1998,18 @@ int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
         if (order == 3) LAUNCH(h, "k_mls<3>", k_mls<3>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
         else if (order == 2) LAUNCH(h, "k_mls<2>", k_mls<2>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
         else LAUNCH(h, "k_mls<1>", k_mls<1>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
-        LAUNCH(h, "k_flag_count", k_flag_count, nblocks, 256, 0, rec.p, n, bcnt.p);
-        LAUNCH(h, "k_vox_scan", k_vox_scan, 1, 1024, 0, bcnt.p, nblocks, st.p);
-        LAUNCH(h, "k_flag_compact", k_flag_compact, nblocks, 256, 0, rec.p, n, bcnt.p, X2.p, Y2.p, Z2.p);
-        HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(VoxStats), hipMemcpyDeviceToHost, h->stream));
+        MlsKeptSel sel{rec.p, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&n_kept, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        return PPP_OK;
-    };
-    rc = run();
-    if (rc == PPP_OK) { h->meta_in_flight = false; h->meta_fresh = false; rc = fetch_meta(h); }
+    }
+    h->meta_in_flight = false; h->meta_fresh = false;
+    rc = fetch_meta(h);
     if (rc == PPP_OK) rc = map_dev_err(h);
-    if (rc != PPP_OK) { cleanup(); return rc; }
-    std::swap(h->X, X2); std::swap(h->Y, Y2); std::swap(h->Z, Z2);
-    h->n = (size_t)hst.n_out;
-    if (n_out) *n_out = h->n;
-    cleanup();
-    h->drop_graph();
-    return cloud_changed(h);
+    if (rc) return rc;
+    if (n_out) *n_out = (size_t)n_kept;
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_kept);
 }
 
 int ppp_get_cloud(ppp_handle h, float *xyz, size_t cap, size_t *n)
@@ -2378,7 +2334,7 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
         A = win_args(h);
         /* a member publishes its meta block into the batch's pinned array; a batch of ONE -- a stream of steps on one workpiece -- does
            not publish at all (the arrival counters are a microsecond at the end of every step): the block is fetched when somebody asks */
-        A.meta_host = count > 1 ? bg->hmetas->pinned + i : nullptr;
+        A.meta_host = count > 1 ? bg->hmetas->p + i : nullptr;
         h->out2 = nullptr; h->out2_cap = 0;
         A.g_scatter = std::max(1, (A.n + bg->win_ppt * WSC_T - 1) / (bg->win_ppt * WSC_T)); /* (the members' partials are sized for 4 points per thread) */
         if (bg->win_staged) A.g_scatter = std::min(A.g_scatter, std::max(1, lead->num_cus)); /* (the staged form loops over its chunks) */
@@ -2471,7 +2427,7 @@ int enqueue_batched(ppp_handle lead, BatchGraph *bg)
         return PPP_OK;
     if (bg->win) LAUNCHB(lead, lead->stream, "k_collect_meta", k_collect_meta_win, dim3((unsigned)count), 64, 0, bg->wmembers.p, (int)count, bg->metas.p);
     else LAUNCHB(lead, lead->stream, "k_collect_meta", k_collect_meta, dim3((unsigned)count), 64, 0, bg->members.p, (int)count, bg->metas.p);
-    HIPCHK(lead, hipMemcpyAsync(bg->hmetas->pinned, bg->metas.p, sizeof(DevMeta) * count, hipMemcpyDeviceToHost, lead->stream));
+    HIPCHK(lead, hipMemcpyAsync(bg->hmetas->p, bg->metas.p, sizeof(DevMeta) * count, hipMemcpyDeviceToHost, lead->stream));
     return PPP_OK;
 }
 
@@ -2555,8 +2511,8 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
             hipError_t ea = bg->members.ensure(count);
             if (ea == hipSuccess) ea = bg->wmembers.ensure(count);
             if (ea == hipSuccess) ea = bg->metas.ensure(count);
-            bg->hmetas = std::make_shared<BatchMetas>();
-            if (ea == hipSuccess) ea = hipHostMalloc((void **)&bg->hmetas->pinned, sizeof(DevMeta) * count, hipHostMallocDefault);
+            bg->hmetas = std::make_shared<PinBuf<DevMeta>>();
+            if (ea == hipSuccess) ea = bg->hmetas->ensure(count);
             if (ea != hipSuccess) { discard(); return fail(lead, PPP_ERR_HIP, std::string("batch buffers: ") + hipGetErrorString(ea)); }
             rc = bg->win ? upload_members_win(lead, bg, dst_dev, offset_rows, cap_rows) : upload_members(lead, bg, dst_dev, offset_rows, cap_rows);
             if (rc != PPP_OK) { discard(); return rc; }
@@ -3376,9 +3332,7 @@ int ppp_spline_destroy(ppp_spline sp)
 {
     if (!sp) return PPP_ERR_ARG;
     (void)hipSetDevice(sp->device);
-    if (sp->stream) { (void)hipStreamSynchronize(sp->stream); }
-    sp->knots.release(); sp->scratch.release(); sp->flag.release();
-    if (sp->stream) (void)hipStreamDestroy(sp->stream);
+    if (sp->stream) { (void)hipStreamSynchronize(sp->stream); (void)hipStreamDestroy(sp->stream); }
     delete sp;
     return PPP_OK;
 }

@@ -77,21 +77,29 @@ __global__ void __launch_bounds__(256) k_sor_threshold(const DevMeta *m, const d
     }
 }
 
-/* ordered compaction of the kept points: per-block counts, scan of the counts, scatter */
-#define SOR_CHUNK 1024
-__global__ void __launch_bounds__(256) k_sor_count(const float *__restrict__ dist, int n, const SorStats *st, int *block_cnt)
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* Ordered compaction (the points SOR keeps, the voxel heads, MLS's survivors, a range part): per block of            */
+/* COMPACT_CHUNK elements the number kept (k_compact_count), the scan of those counts (k_compact_scan), then every    */
+/* block writes its kept elements in input order behind its offset (k_compact_emit).  A selector says what is kept:   */
+/* begin() loads its per-workgroup constants, load(i) reads element i, keep(i, v) tests it, emit(i, k, v) writes      */
+/* the kept element i to slot k from the same v.                                                                      */
+/* ------------------------------------------------------------------------------------------------------------------ */
+#define COMPACT_CHUNK 1024
+template <class Sel>
+__global__ void __launch_bounds__(256) k_compact_count(Sel sel, int n, int *block_cnt)
 {
     __shared__ int s_c[4];
-    const double thr = st->threshold;
+    sel.begin();
     int c = 0;
-    for (int i = blockIdx.x * SOR_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * SOR_CHUNK); i += blockDim.x) c += !((double)dist[i] > thr);
+    for (int i = blockIdx.x * COMPACT_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * COMPACT_CHUNK); i += blockDim.x) c += sel.keep(i, sel.load(i));
     c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
 }
 
-__global__ void __launch_bounds__(1024) k_sor_scan(int *block_cnt, int nblocks, SorStats *st)
+/* block counts -> block offsets; the kept total to *total */
+__global__ void __launch_bounds__(1024) k_compact_scan(int *block_cnt, int nblocks, int *total)
 {
     __shared__ int s_scr[17];
     __shared__ int s_run;
@@ -108,31 +116,46 @@ __global__ void __launch_bounds__(1024) k_sor_scan(int *block_cnt, int nblocks, 
         if (threadIdx.x == 0) s_run = run + tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) st->n_kept = s_run;
+    if (threadIdx.x == 0) *total = s_run;
 }
 
-__global__ void __launch_bounds__(256) k_sor_compact(const float *__restrict__ dist, int n, const SorStats *st, const int *__restrict__ block_off,
-                                                     const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z,
-                                                     float *X2, float *Y2, float *Z2)
+template <class Sel>
+__global__ void __launch_bounds__(256) k_compact_emit(Sel sel, int n, const int *__restrict__ block_off)
 {
     __shared__ int s_scr[17];
     __shared__ int s_run;
-    const double thr = st->threshold;
+    sel.begin();
     if (threadIdx.x == 0) s_run = block_off[blockIdx.x];
     __syncthreads();
-    const int i0 = blockIdx.x * SOR_CHUNK, i1 = min(n, i0 + SOR_CHUNK);
+    const int i0 = blockIdx.x * COMPACT_CHUNK, i1 = min(n, i0 + COMPACT_CHUNK);
     for (int base = i0; base < i1; base += blockDim.x) {
         const int i = base + threadIdx.x;
-        const int keep = (i < i1) && !((double)dist[i] > thr);
+        typename Sel::Val v{};
+        int keep = 0;
+        if (i < i1) { v = sel.load(i); keep = sel.keep(i, v); }
         int tot;
         const int pre = block_exscan(keep, s_scr, &tot);
         const int run = s_run;
-        if (keep) { X2[run + pre] = X[i]; Y2[run + pre] = Y[i]; Z2[run + pre] = Z[i]; }
+        if (keep) sel.emit(i, run + pre, v);
         __syncthreads();
         if (threadIdx.x == 0) s_run = run + tot;
         __syncthreads();
     }
 }
+
+/* SOR: the points whose mean distance is not above k_sor_threshold's threshold */
+struct SorSel {
+    using Val = float;
+    const float *dist;
+    const SorStats *st;
+    const float *X, *Y, *Z;
+    float *X2, *Y2, *Z2;
+    double thr;
+    __device__ void begin() { thr = st->threshold; }
+    __device__ float load(int i) const { return dist[i]; }
+    __device__ bool keep(int, float d) const { return !((double)d > thr); }
+    __device__ void emit(int i, int k, float) const { const float x = X[i], y = Y[i], z = Z[i]; X2[k] = x; Y2[k] = y; Z2[k] = z; }
+};
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* voxel_down: path_generater::voxel_down (Path_Generation.cpp:53-59) = pcl::VoxelGrid<PointXYZRGB> with setLeafSize, */
@@ -141,10 +164,10 @@ __global__ void __launch_bounds__(256) k_sor_compact(const float *__restrict__ d
 /* ordered by id, one output point per occupied voxel = float sum of its points / float count (CentroidPoint's        */
 /* AccumulatorXYZ), output in ascending id.  PCL orders with an unstable sort, so the summation order inside a voxel   */
 /* is an artefact of its sort; here it is ascending point index (stable radix sort), as in the oracle.                */
-/* Launches: key -> radix sort of (id, index) [ppp_sort.hip] -> head count / scan -> gather + sequential run sums.    */
+/* Launches: key -> radix sort of (id, index) [ppp_sort.hip] -> gather -> ordered compaction of the voxel heads,      */
+/* whose emit sums each run in order.                                                                                 */
 /* ------------------------------------------------------------------------------------------------------------------ */
 struct VoxGrid { float inv[3]; float min_b[3]; int mul[3]; unsigned none; };
-struct VoxStats { int n_out; };
 
 __global__ void __launch_bounds__(256) k_vox_key(const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int n,
                                                  VoxGrid g, unsigned *key, int *idx)
@@ -164,41 +187,6 @@ __global__ void __launch_bounds__(256) k_vox_key(const float *__restrict__ X, co
     idx[i] = i;
 }
 
-#define VOX_CHUNK 1024
-__global__ void __launch_bounds__(256) k_vox_count(const unsigned *__restrict__ key, int n, unsigned none, int *block_cnt)
-{
-    __shared__ int s_c[4];
-    int c = 0;
-    for (int i = blockIdx.x * VOX_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * VOX_CHUNK); i += blockDim.x) {
-        const unsigned k = key[i];
-        c += (k != none) && (i == 0 || key[i - 1] != k);
-    }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
-
-__global__ void __launch_bounds__(1024) k_vox_scan(int *block_cnt, int nblocks, VoxStats *st)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    if (threadIdx.x == 0) s_run = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        const int c = i < nblocks ? block_cnt[i] : 0;
-        int tot;
-        const int pre = block_exscan(c, s_scr, &tot);
-        const int run = s_run;
-        if (i < nblocks) block_cnt[i] = run + pre;
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) st->n_out = s_run;
-}
-
 /* the points in sorted order, so that a run is contiguous in memory for the sequential sums below */
 __global__ void __launch_bounds__(256) k_vox_gather(const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z,
                                                     const int *__restrict__ idx, int n, float4 *out)
@@ -209,35 +197,26 @@ __global__ void __launch_bounds__(256) k_vox_gather(const float *__restrict__ X,
     out[i] = make_float4(X[j], Y[j], Z[j], 0.f);
 }
 
-/* one thread per occupied voxel: centroid.add(point) in order, then xyz / n */
-__global__ void __launch_bounds__(256) k_vox_reduce(const unsigned *__restrict__ key, const float4 *__restrict__ pts, int n, unsigned none,
-                                                    const int *__restrict__ block_off, float *X2, float *Y2, float *Z2)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    if (threadIdx.x == 0) s_run = block_off[blockIdx.x];
-    __syncthreads();
-    const int i0 = blockIdx.x * VOX_CHUNK, i1 = min(n, i0 + VOX_CHUNK);
-    for (int base = i0; base < i1; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        unsigned k = none;
-        int head = 0;
-        if (i < i1) { k = key[i]; head = (k != none) && (i == 0 || key[i - 1] != k); }
-        int tot;
-        const int pre = block_exscan(head, s_scr, &tot);
-        const int run = s_run;
-        if (head) {
-            float sx = 0.f, sy = 0.f, sz = 0.f;
-            int j = i;
-            do { const float4 p = pts[j]; sx += p.x; sy += p.y; sz += p.z; ++j; } while (j < n && key[j] == k);
-            const float c = (float)(j - i);
-            X2[run + pre] = sx / c; Y2[run + pre] = sy / c; Z2[run + pre] = sz / c;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
+/* the first point of every occupied voxel (in id order); it emits the voxel's centroid: centroid.add(point) in order, then xyz / n */
+struct VoxHeadSel {
+    using Val = unsigned;
+    const unsigned *key;
+    const float4 *pts;
+    int n;
+    unsigned none;
+    float *X2, *Y2, *Z2;
+    __device__ void begin() {}
+    __device__ unsigned load(int i) const { return key[i]; }
+    __device__ bool keep(int i, unsigned k) const { return k != none && (i == 0 || key[i - 1] != k); }
+    __device__ void emit(int i, int s, unsigned k) const
+    {
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        int j = i;
+        do { const float4 p = pts[j]; sx += p.x; sy += p.y; sz += p.z; ++j; } while (j < n && key[j] == k);
+        const float c = (float)(j - i);
+        X2[s] = sx / c; Y2[s] = sy / c; Z2[s] = sz / c;
     }
-}
+};
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* smooth: SectPath::smooth (path_slicing_alg.cpp:111-139; v1 Path_Generation.cpp:340-360) = pcl::MovingLeastSquares  */
@@ -487,39 +466,16 @@ __global__ void __launch_bounds__(256) k_mls(DevMeta *m, const float4 *__restric
     out4[idx_of(p)] = o;
 }
 
-/* ordered compaction of the flagged float4 records (w != 0) into X2 / Y2 / Z2 */
-__global__ void __launch_bounds__(256) k_flag_count(const float4 *__restrict__ rec, int n, int *block_cnt)
-{
-    __shared__ int s_c[4];
-    int c = 0;
-    for (int i = blockIdx.x * VOX_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * VOX_CHUNK); i += blockDim.x) c += rec[i].w != 0.f;
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
-__global__ void __launch_bounds__(256) k_flag_compact(const float4 *__restrict__ rec, int n, const int *__restrict__ block_off,
-                                                      float *X2, float *Y2, float *Z2)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    if (threadIdx.x == 0) s_run = block_off[blockIdx.x];
-    __syncthreads();
-    const int i0 = blockIdx.x * VOX_CHUNK, i1 = min(n, i0 + VOX_CHUNK);
-    for (int base = i0; base < i1; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < i1) r = rec[i];
-        const int keep = r.w != 0.f;
-        int tot;
-        const int pre = block_exscan(keep, s_scr, &tot);
-        const int run = s_run;
-        if (keep) { X2[run + pre] = r.x; Y2[run + pre] = r.y; Z2[run + pre] = r.z; }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
-    }
-}
+/* MLS: the points k_mls kept (w != 0), their projections */
+struct MlsKeptSel {
+    using Val = float4;
+    const float4 *rec;
+    float *X2, *Y2, *Z2;
+    __device__ void begin() {}
+    __device__ float4 load(int i) const { return rec[i]; }
+    __device__ bool keep(int, float4 r) const { return r.w != 0.f; }
+    __device__ void emit(int, int k, float4 r) const { X2[k] = r.x; Y2[k] = r.y; Z2[k] = r.z; }
+};
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* trans2center: SectPath::trans2center (path_slicing_alg.cpp:82-99; v1 Path_Generation.cpp:60-92).                     */
@@ -742,39 +698,14 @@ __global__ void __launch_bounds__(256) k_transform_se3(const float *X, const flo
 /* cloud), with their cloud indices.  Built once per plan; the hot path  */
 /* then streams the part only.                                           */
 /* ------------------------------------------------------------------ */
-__global__ void __launch_bounds__(256) k_part_count(const float *__restrict__ X, int n, float lo, float hi, int *block_cnt)
-{
-    __shared__ int s_c[4];
-    int c = 0;
-    for (int i = blockIdx.x * VOX_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * VOX_CHUNK); i += blockDim.x) {
-        const float x = X[i];
-        c += (x >= lo && x <= hi); /* NaN (a dropped point) fails both */
-    }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
-__global__ void __launch_bounds__(256) k_part_compact(const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z,
-                                                      int n, float lo, float hi, const int *__restrict__ block_off, float *X2, float *Y2,
-                                                      float *Z2, int *idx2)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    if (threadIdx.x == 0) s_run = block_off[blockIdx.x];
-    __syncthreads();
-    const int i0 = blockIdx.x * VOX_CHUNK, i1 = min(n, i0 + VOX_CHUNK);
-    for (int base = i0; base < i1; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        float x = NAN;
-        if (i < i1) x = X[i];
-        const int keep = (x >= lo && x <= hi);
-        int tot;
-        const int pre = block_exscan(keep, s_scr, &tot);
-        const int run = s_run;
-        if (keep) { X2[run + pre] = x; Y2[run + pre] = Y[i]; Z2[run + pre] = Z[i]; idx2[run + pre] = i; }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
-    }
-}
+struct PartSel {
+    using Val = float;
+    const float *X, *Y, *Z;
+    float lo, hi;
+    float *X2, *Y2, *Z2;
+    int *idx2;
+    __device__ void begin() {}
+    __device__ float load(int i) const { return X[i]; }
+    __device__ bool keep(int, float x) const { return x >= lo && x <= hi; } /* NaN (a dropped point) fails both */
+    __device__ void emit(int i, int k, float x) const { const float y = Y[i], z = Z[i]; X2[k] = x; Y2[k] = y; Z2[k] = z; idx2[k] = i; }
+};
