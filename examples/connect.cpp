@@ -1,7 +1,8 @@
 // Mirror of the reference's src/connect.cpp / src/connect1.cpp (:7-30): ./connect cloud.pcd
 // reads ../config.txt (or $PPP_CONFIG), plans, writes pathFile.  Build: see examples/Makefile.
 // PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths (get_coverage's two lines, path_dynamic_alg.cpp:155-160
-// keeps them commented out); Dynamic_adjustment = false in the config plans the same walk without the adjustment.
+// keeps them commented out); PPP_PATH_CONTACTS=1 prints how evenly they cover (the largest and mean contact count, the points
+// two or more slices touch).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -25,6 +26,8 @@ int main(int argc, char **argv)
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");
     if (cov && cov[0] == '1') path_planner.get_path_coverage();
+    const char *con = std::getenv("PPP_PATH_CONTACTS");
+    if (con && con[0] == '1') path_planner.get_path_contacts();
     path_planner.show();
     return 0;
 }

@@ -1,6 +1,7 @@
 // A caller of the RobotPath drop-in (include/robot_path.h): ./robot cloud.pcd [radius].  The reference declares the class
 // (robot_path.h:58-98) but nothing constructs it -- the header does not compile upstream -- so this is the shape of
-// src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths.
+// src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths,
+// PPP_PATH_CONTACTS=1 their contact counts.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -27,6 +28,8 @@ int main(int argc, char **argv)
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");
     if (cov && cov[0] == '1') path_planner.get_path_coverage();
+    const char *con = std::getenv("PPP_PATH_CONTACTS");
+    if (con && con[0] == '1') path_planner.get_path_contacts();
     path_planner.show();
     std::cout << "waypoints: " << path_planner.waypoints().size() << std::endl;
     return 0;

@@ -69,6 +69,8 @@ public:
     /* the same two lines for the paths the last pass ends with, whichever planner ran (ppp_get_path_coverage): after
        Contact_Path_Generation with the adjustment the adjusted paths only, where get_coverage() also counts the raw ones */
     void get_path_coverage() { planner.print_path_coverage(); }
+    /* how evenly those paths cover: the largest and mean contact count, the points two or more slices touch (ppp_get_path_contacts) */
+    void get_path_contacts() { planner.print_path_contacts(); }
 
     std::vector<int> rangedX_index(int position) { return planner.rangedX_index(position); }
     std::map<double, std::vector<double>> insert_point(std::vector<int> indices, Eigen::Vector3f PlanePoint)

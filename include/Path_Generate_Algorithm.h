@@ -111,6 +111,9 @@ public:
     /* the coverage rate of the planned paths, in get_coverage's two lines (Path_Generation.cpp:766-770; the v2 planner keeps the
        same lines commented out, path_dynamic_alg.cpp:155-160): the contact model on every slice's final path (ppp_get_path_coverage) */
     void get_path_coverage() { planner.print_path_coverage(); }
+    /* how evenly the planned paths cover: the largest and mean contact count over the covered points, and the points two or more
+       slices touch (ppp_get_path_contacts) */
+    void get_path_contacts() { planner.print_path_contacts(); }
 
 protected:
     virtual void read_config(std::string filename)

@@ -268,6 +268,25 @@ int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, 
    next pass or cloud.  Blocks until the results are on the host.  PPP_ERR_ARG before any pass or with curvature_k outside
    [3, 64]; PPP_ERR_UNSUPPORTED on a part handle (ppp_set_cloud_part); the pass's own error if it failed. */
 int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered);
+/* Contact counts of the last pass's paths: the balls of ppp_get_path_coverage, counted.  counts[i] =
+   the number of compute_boundary samples whose ball holds cloud point i (at a constant feed, proportional to the tool's dwell
+   there); first_slice[i] / last_slice[i] = the smallest / largest slice index with such a ball, -1 where there is none
+   (last > first: the band where neighbouring passes overlap).  counts[i] > 0 exactly where ppp_get_path_coverage flags i.
+   Each map may be NULL; min(cap, n) entries of each given one are copied.  stats (may be NULL): n = cloud->size(), covered =
+   points with a count, multi_slice = points with last > first, max_count, total = the sum of the counts, hist[c] = points
+   with count c (hist[PPP_CONTACT_BINS - 1]: count >= PPP_CONTACT_BINS - 1).  A slice-range handle counts the balls of its own
+   slices, by global slice index and whole-cloud point index: the counts of ranges that tile the walk add up to the whole
+   cloud's, first / last are the minimum / maximum over the ranges that touch a point.  Builds, reuses and refuses as
+   ppp_get_path_coverage does, with the same codes, and leaves that call's result alone. */
+#define PPP_CONTACT_BINS 64
+typedef struct {
+    size_t n, covered, multi_slice;
+    unsigned int max_count;
+    unsigned long long total;
+    size_t hist[PPP_CONTACT_BINS];
+} ppp_contact_stats;
+int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap,
+                          ppp_contact_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

@@ -14,6 +14,7 @@
 #define PPP_PLANNER_HPP
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -293,6 +294,33 @@ public:
         std::printf("yes: %f, no: %f\n", yes, no);
         std::printf("coverage rate: %f\n", rate);
     }
+    /* contact counts of the last pass's paths (ppp_get_path_contacts: how many contact balls of path_coverage() hold each cloud
+       point, the first and last slice that has one): the statistics and, when asked for, the three maps by cloud index */
+    bool path_contacts(ppp_contact_stats &st, std::vector<unsigned> *counts = nullptr, std::vector<int> *first = nullptr,
+                       std::vector<int> *last = nullptr)
+    {
+        int rc = ppp_get_path_contacts(h_, nullptr, nullptr, nullptr, 0, &st);
+        if (rc == PPP_OK && (counts || first || last)) {
+            const size_t n = st.n;
+            if (counts) counts->assign(n, 0);
+            if (first) first->assign(n, -1);
+            if (last) last->assign(n, -1);
+            rc = ppp_get_path_contacts(h_, counts ? counts->data() : nullptr, first ? first->data() : nullptr,
+                                       last ? last->data() : nullptr, n, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* two lines on path_contacts(): the largest and the mean contact count over the covered points, and the points two or more
+       slices touch (the overlap bands of neighbouring passes) with their share of the cloud */
+    void print_path_contacts()
+    {
+        ppp_contact_stats st = {};
+        if (!path_contacts(st)) st = ppp_contact_stats{};
+        const double mean = st.covered ? (double)st.total / (double)st.covered : 0.0;
+        const double share = st.n ? (double)st.multi_slice / (double)st.n : 0.0;
+        std::printf("contacts: max %u, mean %f over %zu covered points\n", st.max_count, mean, st.covered);
+        std::printf("overlap: %zu points touched by two or more slices (%f of the cloud)\n", st.multi_slice, share);
+    }
     /* getPath(): returns the list and writes pathFile exactly like path_translation_alg.cpp:216-228 */
     bool get_path(std::vector<float> &wp6)
     {
@@ -388,7 +416,18 @@ public:
             if (ppp_eval_spline(h_, s, q.data(), q.size(), xyz.data()) != PPP_OK) continue;
             paint(xyz, path_rgb);
         }
-        if (S > 0 && on_env("PPP_SHOW_COVERAGE")) { /* the gaps of the plan: every point path coverage leaves uncovered, in yellow */
+        const bool show_contacts = S > 0 && on_env("PPP_SHOW_CONTACTS");
+        if (show_contacts) { /* the dwell of the plan: every point by its contact count on a fixed ramp, the uncovered yellow */
+            if (on_env("PPP_SHOW_COVERAGE")) std::printf("show(): PPP_SHOW_CONTACTS paints over PPP_SHOW_COVERAGE\n");
+            ppp_contact_stats st = {};
+            std::vector<unsigned> cnt;
+            if (path_contacts(st, &cnt) && st.n == n) {
+                for (size_t i = 0; i < n; ++i) contact_rgb(cnt[i], st.max_count, &crgb[3 * i]);
+                std::printf("show(): %zu points painted by contact count (max %u), %zu left uncovered\n", st.covered, st.max_count,
+                            n - st.covered);
+            }
+        }
+        if (S > 0 && !show_contacts && on_env("PPP_SHOW_COVERAGE")) { /* the gaps of the plan: every point path coverage leaves uncovered, in yellow */
             std::vector<unsigned char> cov;
             size_t nc = 0, covered = 0;
             if (path_coverage(nc, covered, &cov) && nc == n) {
@@ -409,6 +448,18 @@ public:
         if (ppp_save_pcd_rgb(out, all.data(), rgb.data(), nn_ + n, vp, 1) == PPP_OK)
             std::printf("show(): %zu inserted nodes + %zu cloud points written to %s\n", nn_, n, out);
         else std::fprintf(stderr, "ppp: could not write %s\n", out);
+    }
+    /* PPP_SHOW_CONTACTS's ramp on t = count / max_count: blue (t -> 0) through cyan (1/3) and green (2/3) to red (1); a count of
+       0 is yellow, as PPP_SHOW_COVERAGE paints the uncovered points */
+    static void contact_rgb(unsigned count, unsigned max_count, unsigned char rgb[3])
+    {
+        if (!count || !max_count) { rgb[0] = 255; rgb[1] = 255; rgb[2] = 0; return; }
+        const double t = std::min(1.0, (double)count / (double)max_count);
+        double r, g, b;
+        if (t < 1.0 / 3) { r = 0; g = 3 * t; b = 1; }
+        else if (t < 2.0 / 3) { r = 0; g = 1; b = 1 - 3 * (t - 1.0 / 3); }
+        else { r = 3 * (t - 2.0 / 3); g = 1 - 3 * (t - 2.0 / 3); b = 0; }
+        rgb[0] = (unsigned char)std::lround(255 * r); rgb[1] = (unsigned char)std::lround(255 * g); rgb[2] = (unsigned char)std::lround(255 * b);
     }
     void show_notice()
     {   /* the classes without a colour scheme of their own */

@@ -45,6 +45,8 @@ public:
     const std::vector<std::vector<float>> &waypoints() const { return WayPointsList; }
     /* get_coverage's two lines (Path_Generation.cpp:766-770) for the planned paths (ppp_get_path_coverage) */
     void get_path_coverage() { planner.print_path_coverage(); }
+    /* the contact counts of the planned paths: largest and mean, and the slices' overlap (ppp_get_path_contacts) */
+    void get_path_contacts() { planner.print_path_contacts(); }
 
 private:
     ppp::Planner planner;

@@ -1190,3 +1190,243 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(const DevMeta *m,
     }
     if (lane == 0) atomicOr(err, 2); /* 2^24 samples on one slice: no knot table of a cloud is that long */
 }
+
+/* ------------------------------------------------------------------ */
+/* Path contacts (ppp_get_path_contacts): how many of k_pcov_balls's balls hold each cloud point, and the   */
+/* first and last slice that has one of them.  Point-centric, no atomics on the maps: k_pcon_offsets counts each slice's  */
+/* samples, k_pcon_samples evaluates every sample's ball once into a per-slice table, k_pcon_points walks the slab index   */
+/* and tests every point against the balls of the slices that reach it, k_pcon_stats reduces the count map.               */
+/* ------------------------------------------------------------------ */
+
+#define PCON_T 256
+#define PCON_BINS 64 /* PPP_CONTACT_BINS: bin 63 holds the counts >= 63 */
+
+/* a float as an unsigned that orders like it (NaN aside); 0 is below every key of a number and stands for "none" */
+__device__ inline unsigned pcon_key(float f)
+{
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float pcon_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+/* compute_boundary's sample count on knots from miny to maxy: the first j with !(dyn_boundary_dy(j) < maxy - 2).  dy does not
+   decrease with j (tool_radius > 0: the closed form is exact where it is used, the running sum rounds monotonically), so a
+   doubling search and a bisection find it on the very values k_pcov_balls's loop tests.  1 << 24 = k_pcov_balls's cap. */
+__device__ inline int pcon_sample_count(const DynParams &D, double miny, double maxy)
+{
+    auto in = [&](int j) { return dyn_boundary_dy(D, miny, j) < maxy - 2; };
+    if (!in(0)) return 0;
+    int lo = 0, hi = 1; /* in(lo); hi == 1 << 24 or !in(hi) */
+    while (hi < (1 << 24) && in(hi)) { lo = hi; hi = hi < (1 << 23) ? 2 * hi : (1 << 24); }
+    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (in(mid)) lo = mid; else hi = mid; }
+    return hi;
+}
+
+/* One workgroup: off[i] = the first table row of slice sb + i, off[nsl] = the rows in all, off[nsl + 1] = the refusal word
+   after this launch.  A slice of fewer than 3 knots has none (B.15).  err |= 2 for a knot table beyond node_cap or a slice
+   of 2^24 samples (k_pcov_balls's refusals), 4 for a slice of 2^22 samples or a table of 2^30 rows or more. */
+__global__ void __launch_bounds__(PCON_T) k_pcon_offsets(DynParams D, const float *__restrict__ node_y, const int *__restrict__ node_start,
+        const int *__restrict__ node_cnt, int node_cap, int sb, int nsl, int *__restrict__ off, int *__restrict__ err)
+{
+    __shared__ int s_scan[17];
+    long long run = 0;
+    for (int base = 0; base < nsl; base += PCON_T) {
+        const int i = base + threadIdx.x;
+        int c = 0;
+        if (i < nsl) {
+            const int st = node_start[sb + i], mm = node_cnt[sb + i];
+            if (mm >= 3) {
+                if (st < 0 || (long long)st + mm > (long long)node_cap) atomicOr(err, 2);
+                else {
+                    c = pcon_sample_count(D, (double)node_y[st], (double)node_y[st + mm - 1]);
+                    if (c >= (1 << 24)) { atomicOr(err, 2); c = 0; }
+                    else if (c >= (1 << 22)) { atomicOr(err, 4); c = 0; }
+                }
+            }
+        }
+        int tot;
+        const int pre = block_exscan(c, s_scan, &tot);
+        if (run + tot >= (1ll << 30)) { if (threadIdx.x == 0) atomicOr(err, 4); tot = 0; }
+        else if (i < nsl) off[i] = (int)run + pre;
+        run += tot;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { off[nsl] = (int)run; off[nsl + 1] = atomicOr(err, 0); }
+}
+
+/* Slice sb + s0 + blockIdx.y, one wave per sample (j = blockIdx.x * DYN_WAVES + wave, strided): the ball of k_pcov_balls
+   (same spline point, same Area2Cloud, r = (ext[0] - ext[1]) / 2 and r * r in float) goes to tab[off + j] as (qx, qy, qz,
+   r2); a NaN r2 holds no point.  reach[3 i ..] takes the slice's x-reach and largest |r| as keys (pcon_key; the lower end as
+   the key of its negation), one atomic per workgroup each.  With R.check the refusal of k_pcov_balls, the same test. */
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcon_samples(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
+        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
+        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
+        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
+        const int *__restrict__ node_start, const int *__restrict__ node_cnt, const int *__restrict__ off, int sb, int s0,
+        PCovRange R, float4 *__restrict__ tab, unsigned *__restrict__ reach, int *__restrict__ err)
+{
+    __shared__ DynWaveLds s_w[DYN_WAVES];
+    __shared__ float2 s_ell[DYN_ELL];
+    __shared__ unsigned s_reach[3];
+    dyn_stage_ellipse(ell_cs, s_ell);
+    const DynGrid G = dyn_grid(m);
+    const int i = s0 + blockIdx.y, s = sb + i;
+    const int o0 = off[i], cnt = off[i + 1] - o0;
+    if (threadIdx.x < 3) s_reach[threadIdx.x] = 0;
+    __syncthreads();
+    if (cnt <= 0) return; /* the whole workgroup: no knots, too few, or refused by k_pcon_offsets */
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int st = node_start[s], mm = node_cnt[s];
+    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
+    const double miny = (double)ky[0];
+    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
+    DynWaveLds &L = s_w[wv];
+    float nlo = -INFINITY, hi = -INFINITY, rmax = -INFINITY; /* the wave's: -min(qx - |r|), max(qx + |r|), max |r| */
+    for (int j = blockIdx.x * DYN_WAVES + wv; j < cnt; j += gridDim.x * DYN_WAVES) {
+        const double dy = dyn_boundary_dy(D, miny, j);
+        double point[3];
+        spline_point_f(ky, kx, kz, mm, dy, point);
+        StampCtx sc; sc.begin(15, false);
+        float b[3], ext[2];
+        const int kk = wave_area2cloud<true>(V, G, L, normals4, s_ell, D, point, 0, b, sc, ext);
+        const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
+        const float qx = (float)point[0], qy = (float)point[1], qz = (float)point[2];
+        if (R.check && qx == qx && qy == qy && qz == qz) {
+            float lo = kk < D.k ? -INFINITY : INFINITY, hi2 = kk < D.k ? INFINITY : -INFINITY;
+            if (lane < kk) {
+                const float4 c = V.at(L.sel[lane]);
+                const float dq = sqrtf(dist2_flann(qx, qy, qz, c.x, c.y, c.z)) * 1.0001f;
+                lo = fminf(lo, fminf(qx - dq, c.x - R.normal_radius * 1.0001f));
+                hi2 = fmaxf(hi2, fmaxf(qx + dq, c.x + R.normal_radius * 1.0001f));
+            }
+            if (r2 == r2) { lo = fminf(lo, qx - fabsf(r) * 1.0001f); hi2 = fmaxf(hi2, qx + fabsf(r) * 1.0001f); }
+            lo = wave_min(lo); hi2 = wave_max(hi2);
+            if (lane == 0 && ((lo < R.incl_lo && R.incl_lo > R.mn_x) || (hi2 > R.incl_hi && R.incl_hi < R.mx_x))) atomicOr(err, 1);
+        }
+        if (lane == 0) tab[o0 + j] = make_float4(qx, qy, qz, r2);
+        if (r2 == r2 && qx == qx && qz == qz) { /* a ball that can hold a point */
+            nlo = fmaxf(nlo, fabsf(r) - qx); hi = fmaxf(hi, qx + fabsf(r)); rmax = fmaxf(rmax, fabsf(r));
+        }
+    }
+    if (lane == 0 && rmax >= 0.f) { atomicMax(&s_reach[0], pcon_key(nlo)); atomicMax(&s_reach[1], pcon_key(hi)); atomicMax(&s_reach[2], pcon_key(rmax)); }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_reach[threadIdx.x]) atomicMax(reach + 3 * i + threadIdx.x, s_reach[threadIdx.x]);
+}
+
+/* One thread per position of the slab index, PCON_T consecutive positions a round (one x-interval, a slab or two): the
+   slices whose reach, padded as wave_mark_ball pads, meets the round's x-interval are listed in LDS; for each, the point
+   bisects the slice's table for qy >= y - rmax - pad (qy does not decrease with j), walks to qy > y + rmax + pad and counts
+   the balls with dist2_flann(q, p) <= r2.  count, first and last stay in registers and are written once, at the point's
+   cloud index (idx_of); points that no ball holds keep the 0 / -1 of the memset. */
+__global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
+        const int *__restrict__ off, const unsigned *__restrict__ reach, int sb, int nsl, unsigned *__restrict__ counts,
+        int *__restrict__ first, int *__restrict__ last)
+{
+    __shared__ int s_scan[17];
+    __shared__ float s_x[2][PCON_T / 64];
+    __shared__ int s_k[PCON_T];
+    __shared__ float4 s_sl[PCON_T]; /* lo, hi, rmax of listed slice e; w: its first table row (bits) */
+    const int total = m->n_sorted;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int c0 = blockIdx.x * PCON_T; c0 < total; c0 += gridDim.x * PCON_T) {
+        const int pi = c0 + threadIdx.x;
+        const bool have = pi < total;
+        const float4 p = have ? sorted4[pi] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float wmn = wave_min(have ? p.x : INFINITY), wmx = wave_max(have ? p.x : -INFINITY);
+        __syncthreads(); /* the round before has read its lists */
+        if (lane == 0) { s_x[0][wv] = wmn; s_x[1][wv] = wmx; }
+        __syncthreads();
+        float cmn = s_x[0][0], cmx = s_x[1][0];
+        for (int w = 1; w < PCON_T / 64; ++w) { cmn = fminf(cmn, s_x[0][w]); cmx = fmaxf(cmx, s_x[1][w]); }
+        const float cabs = fmaxf(fabsf(cmn), fabsf(cmx));
+        unsigned cnt = 0;
+        int fs = -1, ls = -1;
+        const float padp = 1e-5f * fabsf(p.x) + 1e-6f, padq = 1e-5f * fabsf(p.y) + 1e-6f;
+        for (int b0 = 0; b0 < nsl; b0 += PCON_T) {
+            const int k = b0 + threadIdx.x;
+            int take = 0;
+            float lo = 0.f, hi = 0.f, rm = 0.f;
+            if (k < nsl) {
+                const unsigned kh = reach[3 * k + 1];
+                if (kh) {
+                    lo = -pcon_unkey(reach[3 * k]); hi = pcon_unkey(kh); rm = pcon_unkey(reach[3 * k + 2]);
+                    const float pad = 1e-5f * (cabs + rm) + 1e-6f;
+                    take = (lo - pad <= cmx && hi + pad >= cmn) ? 1 : 0;
+                }
+            }
+            int nt;
+            const int at = block_exscan(take, s_scan, &nt);
+            if (take) { s_k[at] = k; s_sl[at] = make_float4(lo, hi, rm, __int_as_float(off[k])); }
+            __syncthreads();
+            if (!have) continue;
+            for (int e = 0; e < nt; ++e) {
+                const float4 sl = s_sl[e];
+                const int k2 = s_k[e];
+                const float rm2 = sl.z;
+                const float padx = padp + 1e-5f * rm2;
+                if (p.x < sl.x - padx || p.x > sl.y + padx) continue;
+                const float ry = rm2 + padq + 1e-5f * rm2;
+                const float ylo = p.y - ry, yhi = p.y + ry;
+                int a = __float_as_int(sl.w), z = off[k2 + 1];
+                const int end = z;
+                while (a < z) { const int mid = (a + z) >> 1; if (tab[mid].y < ylo) a = mid + 1; else z = mid; }
+                for (int j = a; j < end; ++j) {
+                    const float4 t = tab[j];
+                    if (t.y > yhi) break;
+                    if (dist2_flann(t.x, t.y, t.z, p.x, p.y, p.z) <= t.w) {
+                        ++cnt;
+                        const int sg = sb + k2;
+                        fs = fs < 0 ? sg : min(fs, sg); ls = max(ls, sg);
+                    }
+                }
+            }
+        }
+        if (have && cnt) { const int id = idx_of(p); counts[id] = cnt; first[id] = fs; last[id] = ls; }
+    }
+}
+
+/* The statistics of the count map: bins 1 .. 63 of the histogram (bin 0 is n - covered), covered, multi_slice (last >
+   first), the sum and the largest count.  Per-workgroup LDS bins, then one integer atomic per non-empty bin and workgroup, as
+   k_cov_count counts: the same result in every run.  acc[0 .. 63] bins, [64] covered, [65] multi_slice, [66] total,
+   [67] max; workgroup 0 also copies the refusal word into [68], so that one read brings everything back. */
+__global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restrict__ counts, const int *__restrict__ first,
+        const int *__restrict__ last, int n, const int *__restrict__ err, unsigned long long *__restrict__ acc)
+{
+    __shared__ int s_bin[PCON_BINS];
+    __shared__ int s_cov, s_multi;
+    __shared__ unsigned s_max;
+    __shared__ unsigned long long s_tot;
+    if (threadIdx.x < PCON_BINS) s_bin[threadIdx.x] = 0;
+    if (threadIdx.x == 0) { s_cov = 0; s_multi = 0; s_max = 0; s_tot = 0; }
+    __syncthreads();
+    int cov = 0, multi = 0;
+    unsigned mx = 0;
+    unsigned long long tot = 0;
+    const int lane = threadIdx.x & 63;
+    for (int b0 = blockIdx.x * PCON_T; b0 < n; b0 += gridDim.x * PCON_T) { /* b0 is the workgroup's: whole waves vote below */
+        const int i = b0 + threadIdx.x;
+        const unsigned c = i < n ? counts[i] : 0u;
+        const int bin = c ? (int)min(c, (unsigned)PCON_BINS - 1) : -1;
+        if (c) { ++cov; tot += c; mx = max(mx, c); multi += last[i] > first[i] ? 1 : 0; }
+        /* a wave's counts take few values: one LDS add per value present, not per point */
+        u64 todo = __ballot(bin >= 0);
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int v = __shfl(bin, lead, 64);
+            const u64 same = __ballot(bin == v);
+            if (lane == lead) atomicAdd(&s_bin[v], __popcll(same));
+            todo &= ~same;
+        }
+    }
+    cov = wave_sum(cov); multi = wave_sum(multi); tot = wave_sum(tot);
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    if ((threadIdx.x & 63) == 0) {
+        if (cov) { atomicAdd(&s_cov, cov); atomicAdd(&s_tot, tot); atomicMax(&s_max, mx); }
+        if (multi) atomicAdd(&s_multi, multi);
+    }
+    __syncthreads();
+    if (threadIdx.x > 0 && threadIdx.x < PCON_BINS && s_bin[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
+    if (threadIdx.x == 0 && s_cov) { atomicAdd(acc + 64, (unsigned long long)s_cov); atomicAdd(acc + 66, s_tot); atomicMax(acc + 67, (unsigned long long)s_max); }
+    if (threadIdx.x == 0 && s_multi) atomicAdd(acc + 65, (unsigned long long)s_multi);
+    if (threadIdx.x == 0 && blockIdx.x == 0) acc[68] = (unsigned long long)(unsigned)*err;
+}

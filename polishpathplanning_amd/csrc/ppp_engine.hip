@@ -184,6 +184,15 @@ struct ppp_handle_s {
     DevBuf<int> pcov_count;
     unsigned long long pcov_serial = ~0ull;
     size_t pcov_covered = 0;
+    /* path contacts of the last pass (ppp_get_path_contacts): the maps by cloud index, the per-slice sample table (rows from
+       pcon_off; its last two entries the row count and k_pcon_offsets's refusals), the slices' reach keys and the statistics
+       (acc: bins, covered, multi_slice, total, max, the refusal word; the int at acc + 69 is where the kernels set it) */
+    DevBuf<unsigned> pcon_counts, pcon_reach;
+    DevBuf<int> pcon_first, pcon_last, pcon_off;
+    DevBuf<float4> pcon_tab;
+    DevBuf<unsigned long long> pcon_acc;
+    unsigned long long pcon_serial = ~0ull;
+    ppp_contact_stats pcon_stats = {};
     bool normals_valid = false;
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
@@ -3067,6 +3076,87 @@ int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t
     if (covered) *covered = h->pcov_covered;
     const size_t k = std::min(cap, N);
     if (flags && k) HIPCHK(h, copy_sync(h, flags, h->pcov_flags.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap, ppp_contact_stats *stats)
+{
+    static_assert(PCON_BINS == PPP_CONTACT_BINS, "k_pcon_stats bins");
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "path contacts: the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
+    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+    const size_t N = h->n;
+    if (h->pcon_serial != h->gen_serial) { /* first question about this pass */
+        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
+        /* what the pass did not build, as ppp_get_path_coverage builds it */
+        rc = index_ready(h, false);
+        if (rc) return rc;
+        rc = ensure_dynamic_buffers(h);
+        if (rc) return rc;
+        if (!h->P.dynamic_adjustment) { rc = enqueue_normals(h); if (rc) return rc; }
+        const size_t N1 = std::max<size_t>(N, 1);
+        HIPCHK(h, h->pcon_counts.ensure(N1)); HIPCHK(h, h->pcon_first.ensure(N1)); HIPCHK(h, h->pcon_last.ensure(N1));
+        HIPCHK(h, h->pcon_acc.ensure(70));
+        HIPCHK(h, hipMemsetAsync(h->pcon_counts.p, 0, N1 * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->pcon_first.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->pcon_last.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(h->pcon_acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
+        int *err = (int *)(h->pcon_acc.p + 69);
+        if (nsl > 0) {
+            HIPCHK(h, h->pcon_off.ensure((size_t)nsl + 2));
+            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), h->node_y.p, h->node_start.p, h->node_cnt.p,
+                   h->node_cap, sb, nsl, h->pcon_off.p, err);
+            std::vector<int> off((size_t)nsl + 2);
+            HIPCHK(h, copy_sync(h, off.data(), h->pcon_off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+            if (off[nsl + 1] & 2) return fail(h, PPP_ERR_HIP, "path contacts: a slice's knot table lies outside the node buffer");
+            if (off[nsl + 1] & 4) return fail(h, PPP_ERR_CAPACITY, "path contacts: more than 2^30 contact samples");
+            const int rows = off[nsl];
+            int most = 0;
+            for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
+            if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, "path contacts: sample table corrupt");
+            if (rows > 0) {
+                HIPCHK(h, h->pcon_tab.ensure((size_t)rows)); HIPCHK(h, h->pcon_reach.ensure(3 * (size_t)nsl));
+                HIPCHK(h, hipMemsetAsync(h->pcon_reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
+                PCovRange R;
+                R.incl_lo = h->incl_lo; R.incl_hi = h->incl_hi; R.mn_x = h->h_mn[0]; R.mx_x = h->h_mx[0];
+                R.normal_radius = h->P.normal_radius; R.check = h->ranged ? 1 : 0;
+                const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
+                for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
+                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0,
+                           h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p,
+                           h->ell_cs.p, h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p,
+                           h->pcon_off.p, sb, s0, R, h->pcon_tab.p, h->pcon_reach.p, err);
+                /* one thread per indexed point (at most N of them), PCON_T a round */
+                LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
+                       h->meta.p, h->sorted4.p, h->pcon_tab.p, h->pcon_off.p, h->pcon_reach.p, sb, nsl, h->pcon_counts.p,
+                       h->pcon_first.p, h->pcon_last.p);
+            }
+        }
+        LAUNCH(h, "k_pcon_stats", k_pcon_stats, (unsigned)std::min<size_t>((N1 + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus), PCON_T, 0,
+               h->pcon_counts.p, h->pcon_first.p, h->pcon_last.p, (int)N, err, h->pcon_acc.p);
+        unsigned long long acc[69];
+        HIPCHK(h, copy_sync(h, acc, h->pcon_acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+        if (acc[68] & 2) return fail(h, PPP_ERR_HIP, "path contacts: a slice's knot table lies outside the node buffer");
+        if (acc[68] & 1)
+            return fail(h, PPP_ERR_CAPACITY, "path contacts: a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
+        if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "path contacts: statistics corrupt");
+        ppp_contact_stats st = {};
+        st.n = N; st.covered = (size_t)acc[64]; st.multi_slice = (size_t)acc[65];
+        st.total = acc[66]; st.max_count = (unsigned)acc[67];
+        st.hist[0] = N - st.covered;
+        for (int b = 1; b < PCON_BINS; ++b) st.hist[b] = (size_t)acc[b];
+        h->pcon_stats = st;
+        h->pcon_serial = h->gen_serial;
+    }
+    if (stats) *stats = h->pcon_stats;
+    const size_t k = std::min(cap, N);
+    if (counts && k) HIPCHK(h, copy_sync(h, counts, h->pcon_counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, h->pcon_first.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, h->pcon_last.p, k * sizeof(int), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -159,6 +159,7 @@ def lib():
         L.ppp_get_boundary.argtypes = [vp, C.c_int, dp, dp, dp, sz, szp, C.POINTER(C.c_int)]
         L.ppp_get_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
+        L.ppp_get_path_contacts.argtypes = [vp, C.POINTER(C.c_uint), ip, ip, sz, C.POINTER(ContactStats)]
         L.ppp_eval_spline.argtypes = [vp, C.c_int, dp, sz, dp]
         L.ppp_ranged_x_index.argtypes = [vp, C.c_int, ip, sz, szp]
         L.ppp_insert_point.argtypes = [vp, ip, sz, C.c_float, dp, dp, dp, sz, szp]
@@ -274,6 +275,15 @@ class PlannerQueue:
             self.close()
         except Exception:
             pass
+
+
+CONTACT_BINS = 64  # PPP_CONTACT_BINS
+
+
+class ContactStats(C.Structure):
+    """ppp_contact_stats"""
+    _fields_ = [("n", C.c_size_t), ("covered", C.c_size_t), ("multi_slice", C.c_size_t), ("max_count", C.c_uint),
+                ("total", C.c_ulonglong), ("hist", C.c_size_t * CONTACT_BINS)]
 
 
 class PcdLayout(C.Structure):
@@ -698,6 +708,28 @@ class Engine:
         out = np.zeros(max(n.value, 1), np.uint8)
         self._chk(self.L.ppp_get_path_coverage(self.h, out.ctypes.data_as(C.POINTER(C.c_ubyte)), n.value, C.byref(n), C.byref(cov)))
         return out[:n.value], cov.value
+
+    def path_contacts(self, maps=True):
+        """(counts uint32[n], first int32[n], last int32[n], stats dict) of the last pass's final paths: how many contact balls of
+        path_coverage hold each cloud point and the first / last slice with one of them (-1: none; ppp_get_path_contacts).
+        stats: n, covered, multi_slice (last > first), max_count, total (the sum of the counts), hist (CONTACT_BINS counts, the
+        last bin holding the counts >= CONTACT_BINS - 1).  maps=False returns (None, None, None, stats)"""
+        st = ContactStats()
+        self._chk(self.L.ppp_get_path_contacts(self.h, None, None, None, 0, C.byref(st)))
+        n = st.n
+        if maps:
+            counts = np.zeros(max(n, 1), np.uint32)
+            first = np.zeros(max(n, 1), np.int32)
+            last = np.zeros(max(n, 1), np.int32)
+            ip = C.POINTER(C.c_int)
+            self._chk(self.L.ppp_get_path_contacts(self.h, counts.ctypes.data_as(C.POINTER(C.c_uint)), first.ctypes.data_as(ip),
+                                                   last.ctypes.data_as(ip), n, C.byref(st)))
+            counts, first, last = counts[:n], first[:n], last[:n]
+        else:
+            counts = first = last = None
+        stats = dict(n=st.n, covered=st.covered, multi_slice=st.multi_slice, max_count=st.max_count, total=st.total,
+                     hist=np.array(st.hist[:], np.int64))
+        return counts, first, last, stats
 
     def eval_spline(self, s, y):
         y = np.ascontiguousarray(y, np.float64)
