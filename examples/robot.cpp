@@ -30,6 +30,8 @@ int main(int argc, char **argv)
     if (cov && cov[0] == '1') path_planner.get_path_coverage();
     const char *con = std::getenv("PPP_PATH_CONTACTS");
     if (con && con[0] == '1') path_planner.get_path_contacts();
+    const char *fld = std::getenv("PPP_CONTACT_FIELD");
+    if (fld && fld[0] == '1') path_planner.get_contact_field();
     path_planner.show();
     std::cout << "waypoints: " << path_planner.waypoints().size() << std::endl;
     return 0;

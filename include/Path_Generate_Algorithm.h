@@ -114,6 +114,9 @@ public:
     /* how evenly the planned paths cover: the largest and mean contact count over the covered points, and the points two or more
        slices touch (ppp_get_path_contacts) */
     void get_path_contacts() { planner.print_path_contacts(); }
+    /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
+       its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
+    void get_contact_field() { planner.print_contact_field(); }
 
 protected:
     virtual void read_config(std::string filename)

@@ -287,6 +287,37 @@ typedef struct {
 } ppp_contact_stats;
 int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap,
                           ppp_contact_stats *stats);
+/* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
+   evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
+     curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query
+     half_width[i] = the float r = (min x - max x) / 2 of the transformed contact ellipse: compute_coverage's comput_lan
+                     (Path_Generation.cpp:464-467), the radius ppp_get_path_coverage marks with; NaN where Area2Cloud gives NaN
+   for the first min(cap, n) points; either map may be NULL; stats may be NULL.  Both maps are bit-identical to the per-query
+   forms: row i of curv5 is ppp_principal_curvatures_at on point i, half_width[i] is
+   (ppp_area2cloud(p_i, 0).x - ppp_area2cloud(p_i, 1).x) / 2 in float -- the same neighbours in ascending (squared distance,
+   cloud index), the same rank-order float sums, the same first-extremum fold.  Points dropped from the index (non-finite) have
+   NaN in both maps and are not valid.  stats: n = cloud->size(), valid = points with a finite half width, narrow = valid points
+   whose contact width 2|r| is below min_width (mm, the cloud's units; 0 when min_width <= 0), min_abs_r / max_abs_r (NaN when
+   nothing is valid), sum_abs_r over the valid points by a fixed-order reduction (the same in every run), hist = valid points
+   by floor(|r| / Tool_Radius * (PPP_CONTACT_BINS - 1)), clamped to the last bin.  min_width only sets what narrow counts: a
+   pass over the stored map, not a recomputation.
+   Needs a cloud and parameters, NOT a pass: it builds the slab index and the normal field if the handle has none, and a
+   window-path handle stays on the window path.  Computed once per (cloud, parameters): later calls answer from the stored
+   result until ppp_set_cloud*, a preprocessing call, or a ppp_set_params that changes tool_radius, depth, toolthickness,
+   curvature_k, normal_radius or change_range.  A pass does not invalidate it, and it leaves the results of the three coverage
+   calls alone.  Blocks until the results are on the host.  PPP_ERR_ARG without a cloud or with curvature_k outside [3, 64];
+   PPP_ERR_UNSUPPORTED on a part handle (ppp_set_cloud_part) and on a slice-range handle (slice_begin / slice_end: its index
+   holds a part of the cloud only; tiling the field over ranges is not done yet). */
+typedef struct {
+    size_t n;            /* cloud->size() */
+    size_t valid;        /* points with a finite half width */
+    size_t narrow;       /* valid points whose contact width 2|r| is below the call's min_width (0 when min_width <= 0) */
+    float  min_abs_r, max_abs_r;
+    double sum_abs_r;    /* over the valid points, added in cloud index order on the host or by a fixed-order reduction */
+    size_t hist[PPP_CONTACT_BINS]; /* valid points by floor(|r| / Tool_Radius * (PPP_CONTACT_BINS - 1)), clamped */
+} ppp_contact_field_stats;
+int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width,
+                          ppp_contact_field_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 
@@ -327,6 +358,10 @@ int ppp_estimate_normals(ppp_handle h, float *out4);
  * (xyz doubles, mm): key 0 = left boundary point (min x of the contact ellipse), 1 = right (max x);
  * out3 = k x 3 floats (NaN where the reference gets NaN) */
 int ppp_area2cloud(ppp_handle h, const double *pts_xyz, size_t k, int key, float *out3);
+/* compute_transform(point, principle_curvature) (path_dynamic_alg.cpp:77-107; v1 Path_Generation.cpp:362-400) for k query
+ * points: out5 = k x (pcx pcy pcz pc1 pc2) -- the principal direction and the two curvatures computePointPrincipalCurvatures
+ * returns for the curvature_k nearest neighbours of q, with the normal of the nearest one. NaN x 5 where q is not finite. */
+int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, float *out5);
 /* kdtree.nearestKSearch(q, 1) on the whole cloud for k query points */
 int ppp_nearest(ppp_handle h, const float *q_xyz, size_t k, int *idx);
 

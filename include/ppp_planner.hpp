@@ -321,6 +321,33 @@ public:
         std::printf("contacts: max %u, mean %f over %zu covered points\n", st.max_count, mean, st.covered);
         std::printf("overlap: %zu points touched by two or more slices (%f of the cloud)\n", st.multi_slice, share);
     }
+    /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
+       ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below
+       min_width -- and, when asked for, the maps by cloud index (curv5: n x 5) */
+    bool contact_field(ppp_contact_field_stats &st, std::vector<float> *curv5 = nullptr, std::vector<float> *half_width = nullptr,
+                       float min_width = 0.f)
+    {
+        int rc = ppp_get_contact_field(h_, nullptr, nullptr, 0, min_width, &st);
+        if (rc == PPP_OK && (curv5 || half_width)) {
+            const size_t n = st.n;
+            if (curv5) curv5->assign(5 * n, 0.f);
+            if (half_width) half_width->assign(n, 0.f);
+            rc = ppp_get_contact_field(h_, curv5 ? curv5->data() : nullptr, half_width ? half_width->data() : nullptr, n, min_width, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* three lines on contact_field(): the points with a contact width, the smallest, mean and largest half width |r|, and the
+       points whose contact width 2|r| is below the fixed slice step int(2 * Tool_Radius): equally spaced slices leave a gap there */
+    void print_contact_field()
+    {
+        const int step = (int)(2 * cfg_.params.tool_radius);
+        ppp_contact_field_stats st = {};
+        if (!contact_field(st, nullptr, nullptr, (float)step)) st = ppp_contact_field_stats{};
+        const double mean = st.valid ? st.sum_abs_r / (double)st.valid : 0.0;
+        std::printf("contact field: %zu of %zu points have a contact width\n", st.valid, st.n);
+        std::printf("half width |r|: min %f, mean %f, max %f\n", st.valid ? st.min_abs_r : 0.f, mean, st.valid ? st.max_abs_r : 0.f);
+        std::printf("narrow: %zu points with a contact width below the slice step %d\n", st.narrow, step);
+    }
     /* getPath(): returns the list and writes pathFile exactly like path_translation_alg.cpp:216-228 */
     bool get_path(std::vector<float> &wp6)
     {
@@ -416,6 +443,19 @@ public:
             if (ppp_eval_spline(h_, s, q.data(), q.size(), xyz.data()) != PPP_OK) continue;
             paint(xyz, path_rgb);
         }
+        if (on_env("PPP_SHOW_WIDTH")) { /* the workpiece as the contact model sees it: every point by |r| / Tool_Radius, no width yellow */
+            ppp_contact_field_stats fs = {};
+            std::vector<float> hw(n ? n : 1);
+            /* (asked of the handle itself: where the call is refused -- a slice-range or part handle -- the dump goes on without) */
+            if (ppp_get_contact_field(h_, nullptr, hw.data(), n, 0.f, &fs) == PPP_OK && fs.n == n) {
+                for (size_t i = 0; i < n; ++i) {
+                    const double a = std::fabs((double)hw[i]);
+                    if (a <= 3.402823466e+38) ramp_rgb(a / cfg_.params.tool_radius, &crgb[3 * i]);
+                    else { crgb[3 * i] = 255; crgb[3 * i + 1] = 255; crgb[3 * i + 2] = 0; }
+                }
+                std::printf("show(): %zu points painted by contact half width over Tool_Radius, %zu have none\n", fs.valid, n - fs.valid);
+            }
+        }
         const bool show_contacts = S > 0 && on_env("PPP_SHOW_CONTACTS");
         if (show_contacts) { /* the dwell of the plan: every point by its contact count on a fixed ramp, the uncovered yellow */
             if (on_env("PPP_SHOW_COVERAGE")) std::printf("show(): PPP_SHOW_CONTACTS paints over PPP_SHOW_COVERAGE\n");
@@ -454,7 +494,12 @@ public:
     static void contact_rgb(unsigned count, unsigned max_count, unsigned char rgb[3])
     {
         if (!count || !max_count) { rgb[0] = 255; rgb[1] = 255; rgb[2] = 0; return; }
-        const double t = std::min(1.0, (double)count / (double)max_count);
+        ramp_rgb((double)count / (double)max_count, rgb);
+    }
+    /* the ramp itself, t clamped to [0, 1] (PPP_SHOW_WIDTH paints |r| / Tool_Radius with it; both paint over the paths) */
+    static void ramp_rgb(double t_in, unsigned char rgb[3])
+    {
+        const double t = std::min(1.0, std::max(0.0, t_in));
         double r, g, b;
         if (t < 1.0 / 3) { r = 0; g = 3 * t; b = 1; }
         else if (t < 2.0 / 3) { r = 0; g = 1; b = 1 - 3 * (t - 1.0 / 3); }

@@ -59,6 +59,58 @@ __device__ inline int dyn_ybucket(const DynGrid &G, float y)
     q = q < 0 ? 0 : q;
     return q >= YTB ? YTB - 1 : q;
 }
+/* The ranking of wave_knn: the `count` candidates in L.key / L.dk / L.pos ordered by (distance, cloud index); the first kk of
+   them go to L.sel / L.sel_id / L.sel_slot.  The writes of the candidates are visible (barrier + fence) before the call, and
+   the selection is after it.  All 64 lanes. */
+__device__ inline void wave_knn_rank(DynWaveLds &L, const int count, const int kk)
+{
+    const int lane = threadIdx.x & 63;
+    /* rank by counting: (distance, cloud index) is a total order.  Distances are almost always all different, so a candidate's
+       rank is the number of smaller DISTANCES -- 32-bit compares on values read four per LDS access (every lane the same
+       address: a broadcast), two candidates per lane in one sweep; candidates that land on the same rank (equal distances)
+       are ranked again on the whole key.  Only ranks below k matter. */
+    const int cpad = (count + 7) & ~7;
+    for (int c = count + lane; c < cpad; c += 64) L.dk[c] = 0xffffffffu;
+    L.cnt[lane] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    int rr[(DYN_KNN_CAP + 127) / 128][2];
+#pragma unroll
+    for (int sw = 0; sw < (DYN_KNN_CAP + 127) / 128; ++sw) {
+        rr[sw][0] = rr[sw][1] = 0x7fffffff;
+        if (sw * 128 >= count) continue; /* (wave-uniform) */
+        const int c0 = sw * 128 + lane, c1 = c0 + 64;
+        const u32 d0 = c0 < count ? L.dk[c0] : 0u, d1 = c1 < count ? L.dk[c1] : 0u;
+        int r0 = 0, r1 = 0;
+        const uint4 *dv = (const uint4 *)L.dk;
+        for (int o = 0; o < cpad / 4; o += 2) {
+            const uint4 a = dv[o], b = dv[o + 1];
+            r0 += (a.x < d0) + (a.y < d0) + (a.z < d0) + (a.w < d0) + (b.x < d0) + (b.y < d0) + (b.z < d0) + (b.w < d0);
+            r1 += (a.x < d1) + (a.y < d1) + (a.z < d1) + (a.w < d1) + (b.x < d1) + (b.y < d1) + (b.z < d1) + (b.w < d1);
+        }
+        if (c0 < count && r0 < kk) { rr[sw][0] = r0; atomicAdd(&L.cnt[r0], 1); }
+        if (c1 < count && r1 < kk) { rr[sw][1] = r1; atomicAdd(&L.cnt[r1], 1); }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+#pragma unroll
+    for (int sw = 0; sw < (DYN_KNN_CAP + 127) / 128; ++sw)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int rank = rr[sw][h];
+            if (rank == 0x7fffffff) continue;
+            const int c = sw * 128 + 64 * h + lane;
+            const u64 kc = L.key[c];
+            if (L.cnt[rank] > 1) { /* equal distances: the whole key decides */
+                rank = 0;
+                for (int j = 0; j < count; ++j) rank += L.key[j] < kc;
+            }
+            if (rank < kk) { L.sel[rank] = L.pos[c]; L.sel_id[rank] = (int)(u32)kc; L.sel_slot[rank] = c; }
+        }
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+}
+
 /* exact k nearest neighbours of q (ascending (distance, cloud index)): returns kk <= k, positions
    in L.sel[0..kk).  All 64 lanes of the wave call this together.
    Every slab the search ball touches gives its y-window from its y-bucket row (own lane each); the windows are then walked
@@ -178,50 +230,7 @@ __device__ inline int wave_knn(const SlabView &V, const DynGrid &G, DynWaveLds &
         if (lane < count) nq0 = normals4[(u32)L.key[lane]];
         if (lane + 64 < count) nq1 = normals4[(u32)L.key[lane + 64]];
     }
-    /* rank by counting: (distance, cloud index) is a total order.  Distances are almost always all different, so a candidate's
-       rank is the number of smaller DISTANCES -- 32-bit compares on values read four per LDS access (every lane the same
-       address: a broadcast), two candidates per lane in one sweep; candidates that land on the same rank (equal distances)
-       are ranked again on the whole key.  Only ranks below k matter. */
-    const int cpad = (count + 7) & ~7;
-    for (int c = count + lane; c < cpad; c += 64) L.dk[c] = 0xffffffffu;
-    L.cnt[lane] = 0;
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-    int rr[(DYN_KNN_CAP + 127) / 128][2];
-#pragma unroll
-    for (int sw = 0; sw < (DYN_KNN_CAP + 127) / 128; ++sw) {
-        rr[sw][0] = rr[sw][1] = 0x7fffffff;
-        if (sw * 128 >= count) continue; /* (wave-uniform) */
-        const int c0 = sw * 128 + lane, c1 = c0 + 64;
-        const u32 d0 = c0 < count ? L.dk[c0] : 0u, d1 = c1 < count ? L.dk[c1] : 0u;
-        int r0 = 0, r1 = 0;
-        const uint4 *dv = (const uint4 *)L.dk;
-        for (int o = 0; o < cpad / 4; o += 2) {
-            const uint4 a = dv[o], b = dv[o + 1];
-            r0 += (a.x < d0) + (a.y < d0) + (a.z < d0) + (a.w < d0) + (b.x < d0) + (b.y < d0) + (b.z < d0) + (b.w < d0);
-            r1 += (a.x < d1) + (a.y < d1) + (a.z < d1) + (a.w < d1) + (b.x < d1) + (b.y < d1) + (b.z < d1) + (b.w < d1);
-        }
-        if (c0 < count && r0 < kk) { rr[sw][0] = r0; atomicAdd(&L.cnt[r0], 1); }
-        if (c1 < count && r1 < kk) { rr[sw][1] = r1; atomicAdd(&L.cnt[r1], 1); }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
-#pragma unroll
-    for (int sw = 0; sw < (DYN_KNN_CAP + 127) / 128; ++sw)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int rank = rr[sw][h];
-            if (rank == 0x7fffffff) continue;
-            const int c = sw * 128 + 64 * h + lane;
-            const u64 kc = L.key[c];
-            if (L.cnt[rank] > 1) { /* equal distances: the whole key decides */
-                rank = 0;
-                for (int j = 0; j < count; ++j) rank += L.key[j] < kc;
-            }
-            if (rank < kk) { L.sel[rank] = L.pos[c]; L.sel_id[rank] = (int)(u32)kc; L.sel_slot[rank] = c; }
-        }
-    __builtin_amdgcn_wave_barrier();
-    __threadfence_block();
+    wave_knn_rank(L, count, kk);
     sc.mark(3);
     if (normals4 != nullptr) { /* lane r: the normal of neighbour r */
         nn[0] = nn[1] = nn[2] = 0.f;
@@ -247,27 +256,27 @@ __device__ inline void dyn_stage_ellipse(const float *__restrict__ ell_cs, float
     for (int a = threadIdx.x; a < DYN_ELL; a += blockDim.x) s_ell[a] = ((const float2 *)ell_cs)[a];
 }
 
-/* Area2Cloud(point, flag, key): key 0 = left (min x), 1 = right (max x).  Wave-cooperative.  Returns the number of neighbours
-   its search found (0: none, or the point is not a number); L.sel[0] / L.sel_id[0] then still hold the nearest of them, which is
-   what the 1-NN snap of the same point asks for.
-   BOTH_X (the coverage balls, Path_Generation.cpp:457-467): both extrema of the same transformed ellipse, ext_x[0] = min x,
-   ext_x[1] = max x (NaN where the reference's std::min_element / std::max_element return a NaN); key and bound are not used.
-   The chain kernels instantiate the default, whose code this form leaves as it was. */
-template <bool BOTH_X = false>
-__device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWaveLds &L, const float4 *__restrict__ normals4,
-                                       const float2 *ell, const DynParams &D, const double point[3], int key,
-                                       float bound[3], StampCtx &sc, float *ext_x = nullptr)
+/* What Area2Cloud does with the neighbours once they are known: lane r holds the normal of the neighbour of rank r in nn[]
+   (zeros beyond kk > 0).  computePointPrincipalCurvatures, compute_transform, the ellipse axes and the fold of the 721
+   transformed samples; bound / ext_x as wave_area2cloud returns them.  CURV: curv5 = (pcx pcy pcz pc1 pc2), what
+   computePointPrincipalCurvatures returned; m takes the DYN_ELL_CHECK test build's verdict.  wave_area2cloud ends here. */
+struct ContactFrame { float cov[6], n0[3], cv[3], pc0, pc1, cr[3]; double longAxis, shortAxis; };
+/* PART 0: all of it.  The contact field (k_field_batch) takes it in three parts, a batch of queries per wave, through F:
+   1 = the sums of one query by the wave (-> F->cov, F->n0); 2 = eigen solve and axes, which use no lane of their own: a LANE per
+   query (F is the lane's: cov, n0 -> cv, pc, cr, axes); 3 = the fold of one query by the wave (F holds its frame).  The same
+   operations in the same order in every part, so the same bits. */
+template <bool BOTH_X, bool CURV, int PART = 0>
+__device__ inline void wave_contact_tail(const DevMeta *m, DynWaveLds &L, const float2 *ell, const DynParams &D, const float sp[3], const float nn[3],
+                                         const int kk, int key, float bound[3], StampCtx &sc, float *ext_x, float *curv5,
+                                         ContactFrame *F = nullptr)
 {
     const int lane = threadIdx.x & 63;
-    const float sp[3] = {(float)point[0], (float)point[1], (float)point[2]};
-    bound[0] = bound[1] = bound[2] = NAN;
-    if constexpr (BOTH_X) ext_x[0] = ext_x[1] = NAN;
-    if (!(sp[0] == sp[0] && sp[1] == sp[1] && sp[2] == sp[2])) return 0;
-    /* computePointPrincipalCurvatures: lane r holds the neighbour of rank r */
-    float nn[3] = {0.f, 0.f, 0.f};
-    const int kk = wave_knn(V, G, L, sp[0], sp[1], sp[2], D.k, D.r0, normals4, nn, sc);
-    if (kk <= 0) return 0;
     float n0[3];
+    float cov[9];
+    if constexpr (PART >= 2) {
+        for (int i = 0; i < 3; ++i) n0[i] = F->n0[i];
+        cov[0] = F->cov[0]; cov[1] = F->cov[1]; cov[2] = F->cov[2]; cov[4] = F->cov[3]; cov[5] = F->cov[4]; cov[8] = F->cov[5];
+    } else {
     for (int i = 0; i < 3; ++i) n0[i] = __shfl(nn[i], 0, 64);
     float proj[3] = {0.f, 0.f, 0.f};
     if (lane < kk)
@@ -313,10 +322,21 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
             acc += a.x * b.x; acc += a.y * b.y; acc += a.z * b.z; acc += a.w * b.w;
         }
     }
-    float cov[9];
     cov[0] = lane_value(acc, 0); cov[1] = lane_value(acc, 1); cov[2] = lane_value(acc, 2);
     cov[4] = lane_value(acc, 3); cov[5] = lane_value(acc, 4); cov[8] = lane_value(acc, 5);
+    }
+    if constexpr (PART == 1) {
+        for (int i = 0; i < 3; ++i) F->n0[i] = n0[i];
+        F->cov[0] = cov[0]; F->cov[1] = cov[1]; F->cov[2] = cov[2]; F->cov[3] = cov[4]; F->cov[4] = cov[5]; F->cov[5] = cov[8];
+        return;
+    }
     sc.mark(10);
+    float cv[3], cr[3], pc0, pc1;
+    double longAxis, shortAxis;
+    if constexpr (PART == 3) {
+        for (int i = 0; i < 3; ++i) { cv[i] = F->cv[i]; cr[i] = F->cr[i]; }
+        pc0 = F->pc0; pc1 = F->pc1; longAxis = F->longAxis; shortAxis = F->shortAxis;
+    } else {
     cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
     /* pcl::eigen33(mat, evals) + computeCorrespondingEigenVector(mat, evals[2]) */
     float scale = 0.f;
@@ -336,17 +356,15 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
     int bi = 0;
     if (len[1] > len[bi]) bi = 1;
     if (len[2] > len[bi]) bi = 2;
-    float cv[3];
     for (int q = 0; q < 3; ++q) cv[q] = cp[bi][q] / len[bi];
     const float inv = 1.0f / (float)kk;
-    const float pc0 = ev[2] * inv, pc1 = ev[1] * inv;
+    pc0 = ev[2] * inv; pc1 = ev[1] * inv;
+    if constexpr (CURV) { curv5[0] = cv[0]; curv5[1] = cv[1]; curv5[2] = cv[2]; curv5[3] = pc0; curv5[4] = pc1; }
     sc.mark(4);
     /* compute_transform: [n x c | c | n | p] */
-    float cr[3];
     cross3f(n0, cv, cr);
     /* ellipse axes (path_dynamic_alg.cpp:123-141), double arithmetic as std::pow / std::sqrt give */
     const double toolRadius = D.tool_radius, depth = D.depth, toolthickness = D.toolthickness;
-    double longAxis, shortAxis;
     if ((pc0 >= 0) && (pc1 >= 0)) {
         const double i1 = (double)(1 / pc1), i0 = (double)(1 / pc0);
         const double a1 = (double)fabsf(1 / pc1) - depth, a0 = (double)fabsf(1 / pc0) - depth;
@@ -360,6 +378,12 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
         if (longAxis > toolthickness) longAxis = toolthickness;
         shortAxis = (double)fabsf(1 / pc0) - sqrt(i0 * i0 - toolRadius * toolRadius);
         if (shortAxis > toolthickness) shortAxis = toolthickness;
+    }
+    }
+    if constexpr (PART == 2) {
+        for (int i = 0; i < 3; ++i) { F->cv[i] = cv[i]; F->cr[i] = cr[i]; }
+        F->pc0 = pc0; F->pc1 = pc1; F->longAxis = longAxis; F->shortAxis = shortAxis;
+        return;
     }
     sc.mark(11);
     /* 721-point ellipse, transformed (SSE order c0*x + (c1*y + (c2*0 + c3))), first extremum in x.  Returns 1 with the point,
@@ -453,7 +477,7 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
         key = 1;
         if (ellipse_extremum(true, res) == 1) ext_x[1] = res[0];
         sc.mark(5);
-        return kk;
+        return;
     }
     const int st = ellipse_extremum(true, res);
 #ifdef DYN_ELL_CHECK /* test build: the windowed evaluation against all 721 samples, every time */
@@ -462,11 +486,35 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
         const int st2 = ellipse_extremum(false, ref);
         if (st != st2 || (st == 1 && (__float_as_uint(res[0]) != __float_as_uint(ref[0]) || __float_as_uint(res[1]) != __float_as_uint(ref[1]) ||
                                       __float_as_uint(res[2]) != __float_as_uint(ref[2]))))
-            set_err(const_cast<DevMeta *>(V.m), DERR_DOMAIN, -1);
+            set_err(const_cast<DevMeta *>(m), DERR_DOMAIN, -1);
     }
 #endif
     if (st == 1) { bound[0] = res[0]; bound[1] = res[1]; bound[2] = res[2]; }
     sc.mark(5);
+}
+
+/* Area2Cloud(point, flag, key): key 0 = left (min x), 1 = right (max x).  Wave-cooperative.  Returns the number of neighbours
+   its search found (0: none, or the point is not a number); L.sel[0] / L.sel_id[0] then still hold the nearest of them, which is
+   what the 1-NN snap of the same point asks for.
+   BOTH_X (the coverage balls, Path_Generation.cpp:457-467): both extrema of the same transformed ellipse, ext_x[0] = min x,
+   ext_x[1] = max x (NaN where the reference's std::min_element / std::max_element return a NaN); key and bound are not used.
+   CURV: curv5 also takes what computePointPrincipalCurvatures returned (NaN x 5 where there is no answer).
+   The chain kernels instantiate the default, whose code these forms leave as it was. */
+template <bool BOTH_X = false, bool CURV = false>
+__device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWaveLds &L, const float4 *__restrict__ normals4,
+                                       const float2 *ell, const DynParams &D, const double point[3], int key,
+                                       float bound[3], StampCtx &sc, float *ext_x = nullptr, float *curv5 = nullptr)
+{
+    const float sp[3] = {(float)point[0], (float)point[1], (float)point[2]};
+    bound[0] = bound[1] = bound[2] = NAN;
+    if constexpr (BOTH_X) ext_x[0] = ext_x[1] = NAN;
+    if constexpr (CURV) curv5[0] = curv5[1] = curv5[2] = curv5[3] = curv5[4] = NAN;
+    if (!(sp[0] == sp[0] && sp[1] == sp[1] && sp[2] == sp[2])) return 0;
+    /* computePointPrincipalCurvatures: lane r holds the neighbour of rank r */
+    float nn[3] = {0.f, 0.f, 0.f};
+    const int kk = wave_knn(V, G, L, sp[0], sp[1], sp[2], D.k, D.r0, normals4, nn, sc);
+    if (kk <= 0) return 0;
+    wave_contact_tail<BOTH_X, CURV>(V.m, L, ell, D, sp, nn, kk, key, bound, sc, ext_x, curv5);
     return kk;
 }
 
@@ -1429,4 +1477,157 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restric
     if (threadIdx.x == 0 && s_cov) { atomicAdd(acc + 64, (unsigned long long)s_cov); atomicAdd(acc + 66, s_tot); atomicMax(acc + 67, (unsigned long long)s_max); }
     if (threadIdx.x == 0 && s_multi) atomicAdd(acc + 65, (unsigned long long)s_multi);
     if (threadIdx.x == 0 && blockIdx.x == 0) acc[68] = (unsigned long long)(unsigned)*err;
+}
+
+/* ------------------------------------------------------------------ */
+/* Contact field (ppp_get_contact_field): compute_transform + Area2Cloud AT every cloud point -- principal   */
+/* curvatures and the half width r of the contact ellipse.  k_field_batch: a wave per 16 consecutive positions of the slab   */
+/* index, one search per point for both extrema, the wave-uniform eigen solve and axes once per batch with a lane per point.  */
+/* k_field_waves, one wave per query, is ppp_principal_curvatures_at.  A workgroup that stages a run's candidates in LDS     */
+/* and selects from there was built and measured slower.                                                      */
+/* ------------------------------------------------------------------ */
+#define FIELD_BINS 64   /* PPP_CONTACT_BINS */
+
+/* ppp_principal_curvatures_at: one wave per query q_xyz[3 j ..], wave_area2cloud<true, true> as k_pcon_samples calls it; row j
+   of curv5 (and of half_width, where one is given) is query j's. */
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_waves(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
+        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
+        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
+        const float *__restrict__ q_xyz, int k, float *__restrict__ curv5, float *__restrict__ half_width)
+{
+    __shared__ DynWaveLds s_w[DYN_WAVES];
+    __shared__ float2 s_ell[DYN_ELL];
+    dyn_stage_ellipse(ell_cs, s_ell);
+    __syncthreads();
+    const int wv = threadIdx.x >> 6;
+    const int j = blockIdx.x * DYN_WAVES + wv;
+    if (j >= k) return;
+    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
+    const DynGrid G = dyn_grid(m);
+    const double p[3] = {(double)q_xyz[3 * j], (double)q_xyz[3 * j + 1], (double)q_xyz[3 * j + 2]};
+    const size_t row = (size_t)j;
+    float bnd[3], ext[2], c5[5];
+    StampCtx sc; sc.begin(15, false);
+    wave_area2cloud<true, true>(V, G, s_w[wv], normals4, s_ell, D, p, 0, bnd, sc, ext, c5);
+    if ((threadIdx.x & 63) == 0) {
+        if (curv5) { float *o = curv5 + 5 * row; o[0] = c5[0]; o[1] = c5[1]; o[2] = c5[2]; o[3] = c5[3]; o[4] = c5[4]; }
+        if (half_width) half_width[row] = (ext[0] - ext[1]) / 2;
+    }
+}
+
+/* The field proper: a wave takes FIELD_Q consecutive positions of the slab index.  Each query's search and rank-order sums by the
+   whole wave, one after the other (wave_knn, wave_contact_tail part 1), the result parked in the lane of the query's number;
+   then the eigen solve and the ellipse axes -- a third of an evaluation's instructions, and the same in all 64 lanes when a wave
+   serves one query -- ONCE for the batch, a lane per query (part 2); then each query's two folds by the whole wave (part 3).
+   Rows by cloud index, as k_field_waves writes them, and the same bits. */
+#define FIELD_Q 16
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_batch(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
+        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
+        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab, int n,
+        float *__restrict__ curv5, float *__restrict__ half_width)
+{
+    __shared__ DynWaveLds s_w[DYN_WAVES];
+    __shared__ float2 s_ell[DYN_ELL];
+    dyn_stage_ellipse(ell_cs, s_ell);
+    __syncthreads();
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int base = (blockIdx.x * DYN_WAVES + wv) * FIELD_Q;
+    if (base >= n) return;
+    const int nq = min(FIELD_Q, n - base);
+    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
+    const DynGrid G = dyn_grid(m);
+    DynWaveLds &L = s_w[wv];
+    auto lane_f = [](float v, int r) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), r)); }; /* r is wave-uniform */
+    auto lane_d = [](double d, int r) {
+        const int lo = __builtin_amdgcn_readlane(__double2loint(d), r), hi = __builtin_amdgcn_readlane(__double2hiint(d), r);
+        return __hiloint2double(hi, lo);
+    };
+    float4 myq = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < nq) myq = sorted4[base + lane];
+    ContactFrame mine = {};
+    int mykk = 0;
+    StampCtx sc; sc.begin(15, false);
+    float bnd[3], ext[2], c5[5];
+    for (int qi = 0; qi < nq; ++qi) {
+        const float sp[3] = {lane_f(myq.x, qi), lane_f(myq.y, qi), lane_f(myq.z, qi)};
+        float nn[3] = {0.f, 0.f, 0.f};
+        const int kk = wave_knn(V, G, L, sp[0], sp[1], sp[2], D.k, D.r0, normals4, nn, sc);
+        ContactFrame F = {};
+        if (kk > 0) wave_contact_tail<true, true, 1>(m, L, s_ell, D, sp, nn, kk, 0, bnd, sc, ext, c5, &F);
+        if (lane == qi) {
+            for (int i = 0; i < 6; ++i) mine.cov[i] = F.cov[i];
+            for (int i = 0; i < 3; ++i) mine.n0[i] = F.n0[i];
+            mykk = kk;
+        }
+        __builtin_amdgcn_wave_barrier(); /* the next search writes where these sums were read */
+    }
+    {
+        const float sp[3] = {myq.x, myq.y, myq.z}, nn[3] = {0.f, 0.f, 0.f};
+        wave_contact_tail<true, true, 2>(m, L, s_ell, D, sp, nn, mykk > 0 ? mykk : 1, 0, bnd, sc, ext, c5, &mine);
+        if (lane < nq && mykk > 0 && curv5) {
+            float *o = curv5 + 5 * (size_t)idx_of(myq);
+            o[0] = c5[0]; o[1] = c5[1]; o[2] = c5[2]; o[3] = c5[3]; o[4] = c5[4];
+        }
+    }
+    if (!half_width) return;
+    for (int qi = 0; qi < nq; ++qi) {
+        if (__builtin_amdgcn_readlane(mykk, qi) <= 0) continue;
+        const float sp[3] = {lane_f(myq.x, qi), lane_f(myq.y, qi), lane_f(myq.z, qi)}, nn[3] = {0.f, 0.f, 0.f};
+        ContactFrame F = {};
+        for (int i = 0; i < 3; ++i) { F.n0[i] = lane_f(mine.n0[i], qi); F.cv[i] = lane_f(mine.cv[i], qi); F.cr[i] = lane_f(mine.cr[i], qi); }
+        F.pc0 = lane_f(mine.pc0, qi); F.pc1 = lane_f(mine.pc1, qi);
+        F.longAxis = lane_d(mine.longAxis, qi); F.shortAxis = lane_d(mine.shortAxis, qi);
+        ext[0] = ext[1] = NAN;
+        wave_contact_tail<true, true, 3>(m, L, s_ell, D, sp, nn, 1, 0, bnd, sc, ext, c5, &F);
+        if (lane == 0) half_width[__builtin_amdgcn_readlane(idx_of(myq), qi)] = (ext[0] - ext[1]) / 2;
+    }
+}
+
+/* The statistics of the half-width map.  Workgroup g takes the contiguous part [g per, (g + 1) per) of the map: counts and
+   bins with integer atomics (per-workgroup LDS bins, then one atomic per non-empty bin, as k_pcon_stats), the smallest and
+   largest |r| as ordered keys, and the part's sum of |r| in double -- every thread its strided share in index order, then a
+   fixed tree over the threads -- to psum[g]: the host adds the parts in order, so the sum is the same in every run.
+   acc[0 .. 63] bins, [64] valid, [65] narrow (2 |r| < min_width, min_width > 0), [66] key of -min |r|, [67] key of max |r|. */
+__global__ void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict__ half_width, int n, int per, double tool_radius,
+        float min_width, unsigned long long *__restrict__ acc, double *__restrict__ psum)
+{
+    __shared__ int s_bin[FIELD_BINS];
+    __shared__ int s_valid, s_narrow;
+    __shared__ unsigned s_lo, s_hi;
+    __shared__ double s_sum[PCON_T];
+    if (threadIdx.x < FIELD_BINS) s_bin[threadIdx.x] = 0;
+    if (threadIdx.x == 0) { s_valid = 0; s_narrow = 0; s_lo = 0; s_hi = 0; }
+    __syncthreads();
+    const int i0 = blockIdx.x * per, i1 = min(n, i0 + per);
+    int valid = 0, narrow = 0;
+    unsigned klo = 0, khi = 0;
+    double sum = 0.0;
+    for (int i = i0 + threadIdx.x; i < i1; i += PCON_T) {
+        const float a = fabsf(half_width[i]);
+        if (!(a <= 3.402823466e+38f)) continue; /* NaN or infinite: no width */
+        ++valid;
+        if (min_width > 0.f && 2.f * a < min_width) ++narrow;
+        klo = max(klo, pcon_key(-a)); khi = max(khi, pcon_key(a));
+        sum += (double)a;
+        int bin = (int)floor((double)a / tool_radius * (double)(FIELD_BINS - 1));
+        bin = bin < 0 ? 0 : (bin > FIELD_BINS - 1 ? FIELD_BINS - 1 : bin);
+        atomicAdd(&s_bin[bin], 1);
+    }
+    s_sum[threadIdx.x] = sum;
+    valid = wave_sum(valid); narrow = wave_sum(narrow);
+    for (int o = 32; o > 0; o >>= 1) { klo = max(klo, (unsigned)__shfl_xor((int)klo, o, 64)); khi = max(khi, (unsigned)__shfl_xor((int)khi, o, 64)); }
+    if ((threadIdx.x & 63) == 0 && valid) { atomicAdd(&s_valid, valid); atomicAdd(&s_narrow, narrow); atomicMax(&s_lo, klo); atomicMax(&s_hi, khi); }
+    __syncthreads();
+    for (int o = PCON_T / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < FIELD_BINS && s_bin[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
+    if (threadIdx.x == 0) {
+        psum[blockIdx.x] = s_sum[0];
+        if (s_valid) {
+            atomicAdd(acc + 64, (unsigned long long)s_valid); atomicAdd(acc + 65, (unsigned long long)s_narrow);
+            atomicMax(acc + 66, (unsigned long long)s_lo); atomicMax(acc + 67, (unsigned long long)s_hi);
+        }
+    }
 }

@@ -194,6 +194,15 @@ struct ppp_handle_s {
     unsigned long long pcon_serial = ~0ull;
     ppp_contact_stats pcon_stats = {};
     bool normals_valid = false;
+    /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
+       valid for field_P's contact parameters until the cloud changes (field_valid) */
+    DevBuf<float> field_curv, field_hw;
+    DevBuf<unsigned long long> field_acc;
+    DevBuf<double> field_psum;
+    bool field_valid = false;
+    ppp_params field_P = {};
+    float field_min_width = 0.f;
+    ppp_contact_field_stats field_stats = {};
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
     DevBuf<float4> wp_xyz, wp_normal;
@@ -1306,7 +1315,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                 h->plan_deferred = true; h->deferred_census = census;
                 h->have_cloud = true;
                 h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false; h->list_final = false;
-                h->normals_valid = false;
+                h->normals_valid = false; h->field_valid = false;
                 return PPP_OK;
             }
 #ifdef PPP_TUNING
@@ -1342,7 +1351,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
     }
     h->have_cloud = true;
     h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false;
+    h->normals_valid = false; h->field_valid = false;
 #ifdef PPP_TUNING
     if (getenv("PPP_COLD_DEBUG")) {
         const auto t_a = std::chrono::steady_clock::now();
@@ -1719,7 +1728,7 @@ int ppp_set_cloud_part(ppp_handle h, const float *xyz_host, size_t n_part, size_
     h->have_cloud = true;
     h->rec_current = false; /* (no conversion pass of the window plan's kind: the bounds came with the call) */
     h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false;
+    h->normals_valid = false; h->field_valid = false;
     h->drop_graph();
     return make_plan(h);
 }
@@ -3278,6 +3287,109 @@ int ppp_area2cloud(ppp_handle h, const double *pts_xyz, size_t k, int key, float
            h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p, dq, (int)k, key, dout);
     HIPCHK(h, hipMemcpyAsync(out3, dout, k * 12, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PPP_OK;
+}
+
+/* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
+   ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The two
+   calls below then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
+static bool pass_left_normals(const ppp_handle h) { return h->gen_done && h->P.dynamic_adjustment; }
+
+int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, float *out5)
+{
+    int rc = index_ready(h, false); /* complete index: slabs beyond the LDS capacity go through the arena pass first */
+    if (rc) return rc;
+    if (!k) return PPP_OK;
+    if (!q_xyz || !out5 || k > 0x7fffffffu / 8) return fail(h, PPP_ERR_ARG, "bad arguments");
+    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+    rc = ensure_dynamic_buffers(h);
+    if (rc) return rc;
+    if (!pass_left_normals(h)) { rc = enqueue_normals(h); if (rc) return rc; }
+    HIPCHK(h, h->scratch.ensure(k * 32 + 64));
+    float *dq = (float *)h->scratch.p, *dout = dq + 3 * k;
+    HIPCHK(h, hipMemcpyAsync(dq, q_xyz, k * 12, hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "k_field_waves", k_field_waves, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, dyn_params(h),
+           h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p, dq, (int)k, dout,
+           (float *)nullptr);
+    HIPCHK(h, hipMemcpyAsync(out5, dout, k * 20, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PPP_OK;
+}
+
+/* the statistics of the stored half-width map for one min_width (k_field_stats) */
+static int field_statistics(ppp_handle h, float min_width)
+{
+    const size_t N = h->n;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
+    const int per = (int)((N + grid - 1) / grid);
+    HIPCHK(h, h->field_acc.ensure(68)); HIPCHK(h, h->field_psum.ensure((size_t)grid));
+    HIPCHK(h, hipMemsetAsync(h->field_acc.p, 0, 68 * sizeof(unsigned long long), h->stream));
+    LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, h->field_hw.p, (int)N, per, h->P.tool_radius, min_width,
+           h->field_acc.p, h->field_psum.p);
+    unsigned long long acc[68];
+    std::vector<double> psum((size_t)grid);
+    HIPCHK(h, copy_sync(h, acc, h->field_acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, psum.data(), h->field_psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "contact field: statistics corrupt");
+    ppp_contact_field_stats st = {};
+    st.n = N; st.valid = (size_t)acc[64]; st.narrow = (size_t)acc[65];
+    auto unkey = [](unsigned k) { unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &u, 4); return f; };
+    st.min_abs_r = st.valid ? -unkey((unsigned)acc[66]) : NAN; st.max_abs_r = st.valid ? unkey((unsigned)acc[67]) : NAN;
+    for (double v : psum) st.sum_abs_r += v;
+    for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
+    h->field_stats = st;
+    h->field_min_width = min_width;
+    return PPP_OK;
+}
+
+int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width, ppp_contact_field_stats *stats)
+{
+    static_assert(FIELD_BINS == PPP_CONTACT_BINS, "k_field_stats bins");
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "contact field: the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
+        return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
+    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+    if (!(min_width > 0.f)) min_width = 0.f;
+    const size_t N = h->n;
+    const ppp_params &P = h->P, &F = h->field_P;
+    const bool same = h->field_valid && P.tool_radius == F.tool_radius && P.depth == F.depth && P.toolthickness == F.toolthickness &&
+                      P.curvature_k == F.curvature_k && P.normal_radius == F.normal_radius && P.change_range == F.change_range;
+    if (!same) {
+        h->field_valid = false;
+        /* the slab index (behind a window pass it keeps that pass's run state, as every API mirror's does), the Area2Cloud
+           buffers and the normal field (a pass with the dynamic adjustment made it) */
+        int rc = index_ready(h, false);
+        if (rc) return rc;
+        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
+        rc = ensure_dynamic_buffers(h);
+        if (rc) return rc;
+        if (!pass_left_normals(h)) { rc = enqueue_normals(h); if (rc) return rc; }
+        const size_t N1 = std::max<size_t>(N, 1);
+        HIPCHK(h, h->field_curv.ensure(5 * N1)); HIPCHK(h, h->field_hw.ensure(N1));
+        HIPCHK(h, hipMemsetAsync(h->field_curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* dropped points: NaN */
+        HIPCHK(h, hipMemsetAsync(h->field_hw.p, 0xff, N1 * sizeof(float), h->stream));
+        const int nsorted = h->hmeta.n_sorted;
+        if (nsorted < 0 || (size_t)nsorted > N) return fail(h, PPP_ERR_HIP, "contact field: index corrupt");
+        if (nsorted > 0) /* a wave per FIELD_Q indexed points, in slab / y order */
+            LAUNCH(h, "k_field_batch", k_field_batch, (unsigned)((nsorted + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
+                   h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
+                   h->slab_ytab.p, nsorted, h->field_curv.p, h->field_hw.p);
+        rc = field_statistics(h, min_width);
+        if (rc) return rc;
+        h->field_P = h->P;
+        h->field_valid = true;
+    } else if (stats && min_width != h->field_min_width) {
+        int rc = field_statistics(h, min_width);
+        if (rc) return rc;
+    }
+    if (stats) *stats = h->field_stats;
+    const size_t k = std::min(cap, N);
+    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, h->field_curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
+    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, h->field_hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

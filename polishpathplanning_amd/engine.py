@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_contact_field", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -160,6 +160,8 @@ def lib():
         L.ppp_get_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_contacts.argtypes = [vp, C.POINTER(C.c_uint), ip, ip, sz, C.POINTER(ContactStats)]
+        L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
+        L.ppp_principal_curvatures_at.argtypes = [vp, fp, sz, fp]
         L.ppp_eval_spline.argtypes = [vp, C.c_int, dp, sz, dp]
         L.ppp_ranged_x_index.argtypes = [vp, C.c_int, ip, sz, szp]
         L.ppp_insert_point.argtypes = [vp, ip, sz, C.c_float, dp, dp, dp, sz, szp]
@@ -284,6 +286,12 @@ class ContactStats(C.Structure):
     """ppp_contact_stats"""
     _fields_ = [("n", C.c_size_t), ("covered", C.c_size_t), ("multi_slice", C.c_size_t), ("max_count", C.c_uint),
                 ("total", C.c_ulonglong), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+class ContactFieldStats(C.Structure):
+    """ppp_contact_field_stats"""
+    _fields_ = [("n", C.c_size_t), ("valid", C.c_size_t), ("narrow", C.c_size_t), ("min_abs_r", C.c_float), ("max_abs_r", C.c_float),
+                ("sum_abs_r", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
 
 
 class PcdLayout(C.Structure):
@@ -730,6 +738,32 @@ class Engine:
         stats = dict(n=st.n, covered=st.covered, multi_slice=st.multi_slice, max_count=st.max_count, total=st.total,
                      hist=np.array(st.hist[:], np.int64))
         return counts, first, last, stats
+
+    def contact_field(self, maps=True, min_width=0.0):
+        """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every
+        cloud point (ppp_get_contact_field) -- pcx pcy pcz pc1 pc2 and the half width r of the contact ellipse, NaN where the
+        model gives none.  Needs no pass.  stats: n, valid, narrow (valid points with 2|r| < min_width), min_abs_r, max_abs_r,
+        sum_abs_r, mean_abs_r, hist (CONTACT_BINS counts of |r| / tool_radius).  maps=False returns (None, None, stats)"""
+        st = ContactFieldStats()
+        self._chk(self.L.ppp_get_contact_field(self.h, None, None, 0, float(min_width), C.byref(st)))
+        n = st.n
+        if maps:
+            curv = np.empty((max(n, 1), 5), np.float32)
+            hw = np.empty(max(n, 1), np.float32)
+            self._chk(self.L.ppp_get_contact_field(self.h, _f(curv), _f(hw), n, float(min_width), C.byref(st)))
+            curv, hw = curv[:n], hw[:n]
+        else:
+            curv = hw = None
+        stats = dict(n=st.n, valid=st.valid, narrow=st.narrow, min_abs_r=st.min_abs_r, max_abs_r=st.max_abs_r, sum_abs_r=st.sum_abs_r,
+                     mean_abs_r=(st.sum_abs_r / st.valid if st.valid else float("nan")), hist=np.array(st.hist[:], np.int64))
+        return curv, hw, stats
+
+    def principal_curvatures_at(self, q):
+        """compute_transform's principal curvatures for query points [k, 3] (float32, mm): [k, 5] = pcx pcy pcz pc1 pc2."""
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        out = np.empty((len(q), 5), np.float32)
+        self._chk(self.L.ppp_principal_curvatures_at(self.h, _f(q), len(q), _f(out)))
+        return out
 
     def eval_spline(self, s, y):
         y = np.ascontiguousarray(y, np.float64)
