@@ -518,28 +518,32 @@ __device__ inline int wave_area2cloud(const SlabView &V, const DynGrid &G, DynWa
     return kk;
 }
 
+/* What an Area2Cloud evaluation reads beside its parameters: the slab index of the cloud, its normal field and the ellipse
+   angles.  Passed by value to the kernels that evaluate outside the chain (the host fills it: contact_index). */
+struct ContactIndex {
+    const DevMeta *m;
+    const float4 *sorted4; const int *slab_start; const float *slab_xmin, *slab_xmax;
+    const float4 *normals4; const float *ell_cs; const int *ytab;
+    __device__ inline SlabView view() const { return SlabView{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab}; }
+};
+
 /* API: Area2Cloud for k query points (one wave each) */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_area2cloud_api(DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-                                                                   const int *__restrict__ slab_start,
-                                                                   const float *__restrict__ slab_xmin,
-                                                                   const float *__restrict__ slab_xmax,
-                                                                   const float4 *__restrict__ normals4,
-                                                                   const float *__restrict__ ell_cs, const int *__restrict__ ytab,
-                                                                   const double *__restrict__ pts, int k, int key, float *out)
+__global__ void __launch_bounds__(64 * DYN_WAVES) k_area2cloud_api(ContactIndex I, DynParams D, const double *__restrict__ pts, int k,
+                                                                   int key, float *out)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
     __shared__ float2 s_ell[DYN_ELL];
-    dyn_stage_ellipse(ell_cs, s_ell);
+    dyn_stage_ellipse(I.ell_cs, s_ell);
     __syncthreads();
     const int wv = threadIdx.x >> 6;
     const int q = blockIdx.x * DYN_WAVES + wv;
     if (q >= k) return;
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    const DynGrid G = dyn_grid(m);
+    const SlabView V = I.view();
+    const DynGrid G = dyn_grid(I.m);
     double p[3] = {pts[3 * q], pts[3 * q + 1], pts[3 * q + 2]};
     float b[3];
     StampCtx sc; sc.begin(15, false);
-    wave_area2cloud(V, G, s_w[wv], normals4, s_ell, D, p, key, b, sc);
+    wave_area2cloud(V, G, s_w[wv], I.normals4, s_ell, D, p, key, b, sc);
     if ((threadIdx.x & 63) == 0) { out[3 * q] = b[0]; out[3 * q + 1] = b[1]; out[3 * q + 2] = b[2]; }
 }
 
@@ -1058,576 +1062,4 @@ __global__ void __launch_bounds__(256) k_dyn_adjust_fit(DevMeta *m, int walk, in
     if (base < 0) return;
     dyn_emit_knots(pts, F, ft, [&](int o, const float4 &p) { node_y[base + o] = p.x == 0.f ? 0.f : p.x; node_x[base + o] = p.y; node_z[base + o] = p.z; });
     if (threadIdx.x == 0) { node_start[c.s] = base; node_cnt[c.s] = tot; }
-}
-
-/* ------------------------------------------------------------------ */
-/* Coverage (path_generater::compute_coverage / get_coverage, Path_Generation.cpp:463-496, 757-771).  Every            */
-/* Area2Cloud(point, 1, 0) of compute_boundary marks the cloud points within half the x-extent of the point's contact   */
-/* ellipse.  In Contact_Path_Generation (:711-725) that is every slice's raw path (:719) and the adjusted path of slice */
-/* s-1 in dynamic_adjust_path of slice s (:590): raw(0..S-1) and adjusted(1..S-2), all known once the pass is done, so */
-/* one launch evaluates all of those balls side by side and marks their points, and a second counts the flags.         */
-/* ------------------------------------------------------------------ */
-
-/* kdtree.radiusSearch(centre, r): flags[i] = 1 for every indexed point within the ball (dist2_flann <= r2, the float
-   square of r as PCL hands it to FLANN).  All 64 lanes together; the candidates come from the y-windows of the slabs the
-   ball touches, as in wave_knn.  Points are only ever set to 1, so balls that overlap need no atomics. */
-__device__ inline void wave_mark_ball(const SlabView &V, const DynGrid &G, DynWaveLds &L, float qx, float qy, float qz, float r,
-                                      float r2, unsigned char *__restrict__ flags)
-{
-    const int lane = threadIdx.x & 63;
-    const float pady = 1e-5f * (fabsf(qy) + r) + 1e-6f, padx = 1e-5f * (fabsf(qx) + r) + 1e-6f;
-    const float ylo = qy - r - pady, yhi = qy + r + pady;
-    const int blo = dyn_slab_of(G, qx - r - padx), bhi = dyn_slab_of(G, qx + r + padx);
-    const int q0 = dyn_ybucket(G, ylo), q1 = dyn_ybucket(G, yhi) + 1;
-    for (int cb = blo; cb <= bhi; cb += 64) {
-        const int bb = cb + lane;
-        int a = 0, e = 0;
-        if (bb <= bhi) {
-            const int s0 = V.slab_start[bb];
-            if (V.ytab) {
-                const int *T = V.ytab + (size_t)bb * (YTB + 1);
-                a = s0 + T[q0]; e = s0 + T[q1];
-            } else {
-                const int s1 = V.slab_start[bb + 1];
-                int l0 = s0, l1 = s1, u0 = s0, u1 = s1;
-                while (l0 < l1 || u0 < u1) {
-                    if (l0 < l1) { const int mid = (l0 + l1) >> 1; if (V.at(mid).y < ylo) l0 = mid + 1; else l1 = mid; }
-                    if (u0 < u1) { const int mid = (u0 + u1) >> 1; if (V.at(mid).y <= yhi) u0 = mid + 1; else u1 = mid; }
-                }
-                a = l0; e = u0 < l0 ? l0 : u0;
-            }
-        }
-        const int cnt = e - a;
-        int inc = cnt;
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
-        const int T = __shfl(inc, 63, 64);
-        __builtin_amdgcn_wave_barrier();
-        L.off[lane] = inc - cnt; L.w0[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        const int wtop = bhi - cb < 63 ? bhi - cb : 63;
-        for (int t = lane; t < T; t += 64) {
-            int lo = 0, hi = wtop; /* the window holding flat position t */
-            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (L.off[mid] <= t) lo = mid; else hi = mid - 1; }
-            const float4 c = V.at(L.w0[lo] + (t - L.off[lo]));
-            if (dist2_flann(qx, qy, qz, c.x, c.y, c.z) <= r2) flags[idx_of(c)] = 1;
-        }
-    }
-}
-
-/* One wave per compute_boundary sample: blockIdx.y = slice, blockIdx.z = 0 the raw path (knots at raw_sc, as k_dyn_first_eval
-   found them), 1 the adjusted one (node_start / node_cnt after the pass; slices 1 .. S-2).  The reference's "last point" call
-   repeats the last sample's ball; a loop that ran zero times adds no ball. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_cov_balls(DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
-        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
-        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
-        const int *__restrict__ node_start, const int *__restrict__ node_cnt, const int *__restrict__ raw_sc, int maxNB,
-        unsigned char *__restrict__ flags)
-{
-    __shared__ DynWaveLds s_w[DYN_WAVES];
-    __shared__ float2 s_ell[DYN_ELL];
-    dyn_stage_ellipse(ell_cs, s_ell);
-    const DynGrid G = dyn_grid(m);
-    const int S = m->S, err = m->err;
-    __syncthreads();
-    if (err) return;
-    const int wv = threadIdx.x >> 6;
-    const int s = blockIdx.y, j = blockIdx.x * DYN_WAVES + wv;
-    const bool adjusted = blockIdx.z == 1;
-    if (s >= S || j >= maxNB || (adjusted && (s < 1 || s > S - 2))) return;
-    const int st = adjusted ? node_start[s] : raw_sc[2 * s], mm = adjusted ? node_cnt[s] : raw_sc[2 * s + 1];
-    if (mm < 3) return;
-    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
-    const double miny = (double)ky[0], maxy = (double)ky[mm - 1];
-    const double dy = dyn_boundary_dy(D, miny, j);
-    if (!(dy < maxy - 2)) return;
-    double point[3];
-    spline_point_f(ky, kx, kz, mm, dy, point);
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    StampCtx sc; sc.begin(15, false);
-    float b[3], ext[2];
-    wave_area2cloud<true>(V, G, s_w[wv], normals4, s_ell, D, point, 0, b, sc, ext);
-    /* comput_lan = (for_min->x - boundpoint_it->x) / 2 in float (negative); PCL squares it: the float r * r */
-    const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
-    if (!(r2 == r2)) return; /* a NaN radius marks nothing (FLANN: no distance is <= NaN) */
-    wave_mark_ball(V, G, s_w[wv], (float)point[0], (float)point[1], (float)point[2], fabsf(r), r2, flags);
-}
-
-/* get_coverage's yes count: the flags (0 / 1, zero padding up to a multiple of 16 bytes) summed 16 at a time by population
-   count, a wave sum, one atomic per workgroup -- integers, so the count is the same in every run */
-#define COV_T 256
-__global__ void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ flags16, int n16, int *__restrict__ count)
-{
-    __shared__ int s_c;
-    if (threadIdx.x == 0) s_c = 0;
-    __syncthreads();
-    int c = 0;
-    for (int i = blockIdx.x * COV_T + threadIdx.x; i < n16; i += gridDim.x * COV_T) {
-        const uint4 w = flags16[i];
-        c += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
-    }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_c) atomicAdd(count, s_c);
-}
-
-/* ------------------------------------------------------------------ */
-/* Path coverage (ppp_get_path_coverage): the same contact model applied to the paths a pass ends with --    */
-/* every slice's final knots (node_start / node_cnt after the pass: adjusted where the adjustment ran), for every walk.     */
-/* One launch marks the balls (k_pcov_balls), k_cov_count counts the flags.                                                */
-/* ------------------------------------------------------------------ */
-
-/* what a slice-range handle indexes: the points with x in [incl_lo, incl_hi] of a cloud that spans [mn_x, mx_x] */
-struct PCovRange { float incl_lo, incl_hi, mn_x, mx_x, normal_radius; int check; };
-
-/* Slice sb + blockIdx.y, one wave per compute_boundary sample: wave w takes samples j = blockIdx.x * DYN_WAVES + w,
-   j + gridDim.x * DYN_WAVES, ... while dy < maxy - 2 (a loop that runs zero times adds no ball, B.15).  The ball of a sample
-   is k_cov_balls's.  With R.check (a slice-range handle) every search a sample makes -- the k-NN of Area2Cloud, the normal
-   neighbourhoods of those neighbours and the ball -- must lie inside the indexed interval, unless that reaches the cloud's end
-   (the DERR_MARGIN test of the waypoints, ppp_kernels.h); err[0] |= 1 where one does not, err[0] |= 2 for a knot table
-   beyond node_cap.  The host then refuses the answer. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
-        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
-        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
-        const int *__restrict__ node_start, const int *__restrict__ node_cnt, int node_cap, int sb, PCovRange R,
-        unsigned char *__restrict__ flags, int *__restrict__ err)
-{
-    __shared__ DynWaveLds s_w[DYN_WAVES];
-    __shared__ float2 s_ell[DYN_ELL];
-    dyn_stage_ellipse(ell_cs, s_ell);
-    const DynGrid G = dyn_grid(m);
-    const int s = sb + blockIdx.y;
-    const int st = node_start[s], mm = node_cnt[s];
-    __syncthreads();
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (mm < 3) return;
-    if (st < 0 || (long long)st + mm > (long long)node_cap) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(err, 2); return; }
-    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
-    const double miny = (double)ky[0], maxy = (double)ky[mm - 1];
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    DynWaveLds &L = s_w[wv];
-    for (int j = blockIdx.x * DYN_WAVES + wv; j < (1 << 24); j += gridDim.x * DYN_WAVES) {
-        const double dy = dyn_boundary_dy(D, miny, j);
-        if (!(dy < maxy - 2)) return;
-        double point[3];
-        spline_point_f(ky, kx, kz, mm, dy, point);
-        StampCtx sc; sc.begin(15, false);
-        float b[3], ext[2];
-        const int kk = wave_area2cloud<true>(V, G, L, normals4, s_ell, D, point, 0, b, sc, ext);
-        /* comput_lan = (for_min->x - boundpoint_it->x) / 2 in float; PCL squares it: the float r * r */
-        const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
-        const float qx = (float)point[0], qy = (float)point[1], qz = (float)point[2];
-        if (R.check && qx == qx && qy == qy && qz == qz) {
-            /* fewer than k neighbours in the indexed part: the whole cloud may hold more */
-            float lo = kk < D.k ? -INFINITY : INFINITY, hi = kk < D.k ? INFINITY : -INFINITY;
-            if (lane < kk) {
-                const float4 c = V.at(L.sel[lane]);
-                const float dq = sqrtf(dist2_flann(qx, qy, qz, c.x, c.y, c.z)) * 1.0001f;
-                lo = fminf(lo, fminf(qx - dq, c.x - R.normal_radius * 1.0001f));
-                hi = fmaxf(hi, fmaxf(qx + dq, c.x + R.normal_radius * 1.0001f));
-            }
-            if (r2 == r2) { lo = fminf(lo, qx - fabsf(r) * 1.0001f); hi = fmaxf(hi, qx + fabsf(r) * 1.0001f); }
-            lo = wave_min(lo); hi = wave_max(hi);
-            if (lane == 0 && ((lo < R.incl_lo && R.incl_lo > R.mn_x) || (hi > R.incl_hi && R.incl_hi < R.mx_x))) atomicOr(err, 1);
-        }
-        if (!(r2 == r2)) continue; /* a NaN radius marks nothing (B.16) */
-        wave_mark_ball(V, G, L, qx, qy, qz, fabsf(r), r2, flags);
-    }
-    if (lane == 0) atomicOr(err, 2); /* 2^24 samples on one slice: no knot table of a cloud is that long */
-}
-
-/* ------------------------------------------------------------------ */
-/* Path contacts (ppp_get_path_contacts): how many of k_pcov_balls's balls hold each cloud point, and the   */
-/* first and last slice that has one of them.  Point-centric, no atomics on the maps: k_pcon_offsets counts each slice's  */
-/* samples, k_pcon_samples evaluates every sample's ball once into a per-slice table, k_pcon_points walks the slab index   */
-/* and tests every point against the balls of the slices that reach it, k_pcon_stats reduces the count map.               */
-/* ------------------------------------------------------------------ */
-
-#define PCON_T 256
-#define PCON_BINS 64 /* PPP_CONTACT_BINS: bin 63 holds the counts >= 63 */
-
-/* a float as an unsigned that orders like it (NaN aside); 0 is below every key of a number and stands for "none" */
-__device__ inline unsigned pcon_key(float f)
-{
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float pcon_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-/* compute_boundary's sample count on knots from miny to maxy: the first j with !(dyn_boundary_dy(j) < maxy - 2).  dy does not
-   decrease with j (tool_radius > 0: the closed form is exact where it is used, the running sum rounds monotonically), so a
-   doubling search and a bisection find it on the very values k_pcov_balls's loop tests.  1 << 24 = k_pcov_balls's cap. */
-__device__ inline int pcon_sample_count(const DynParams &D, double miny, double maxy)
-{
-    auto in = [&](int j) { return dyn_boundary_dy(D, miny, j) < maxy - 2; };
-    if (!in(0)) return 0;
-    int lo = 0, hi = 1; /* in(lo); hi == 1 << 24 or !in(hi) */
-    while (hi < (1 << 24) && in(hi)) { lo = hi; hi = hi < (1 << 23) ? 2 * hi : (1 << 24); }
-    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (in(mid)) lo = mid; else hi = mid; }
-    return hi;
-}
-
-/* One workgroup: off[i] = the first table row of slice sb + i, off[nsl] = the rows in all, off[nsl + 1] = the refusal word
-   after this launch.  A slice of fewer than 3 knots has none (B.15).  err |= 2 for a knot table beyond node_cap or a slice
-   of 2^24 samples (k_pcov_balls's refusals), 4 for a slice of 2^22 samples or a table of 2^30 rows or more. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_offsets(DynParams D, const float *__restrict__ node_y, const int *__restrict__ node_start,
-        const int *__restrict__ node_cnt, int node_cap, int sb, int nsl, int *__restrict__ off, int *__restrict__ err)
-{
-    __shared__ int s_scan[17];
-    long long run = 0;
-    for (int base = 0; base < nsl; base += PCON_T) {
-        const int i = base + threadIdx.x;
-        int c = 0;
-        if (i < nsl) {
-            const int st = node_start[sb + i], mm = node_cnt[sb + i];
-            if (mm >= 3) {
-                if (st < 0 || (long long)st + mm > (long long)node_cap) atomicOr(err, 2);
-                else {
-                    c = pcon_sample_count(D, (double)node_y[st], (double)node_y[st + mm - 1]);
-                    if (c >= (1 << 24)) { atomicOr(err, 2); c = 0; }
-                    else if (c >= (1 << 22)) { atomicOr(err, 4); c = 0; }
-                }
-            }
-        }
-        int tot;
-        const int pre = block_exscan(c, s_scan, &tot);
-        if (run + tot >= (1ll << 30)) { if (threadIdx.x == 0) atomicOr(err, 4); tot = 0; }
-        else if (i < nsl) off[i] = (int)run + pre;
-        run += tot;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) { off[nsl] = (int)run; off[nsl + 1] = atomicOr(err, 0); }
-}
-
-/* Slice sb + s0 + blockIdx.y, one wave per sample (j = blockIdx.x * DYN_WAVES + wave, strided): the ball of k_pcov_balls
-   (same spline point, same Area2Cloud, r = (ext[0] - ext[1]) / 2 and r * r in float) goes to tab[off + j] as (qx, qy, qz,
-   r2); a NaN r2 holds no point.  reach[3 i ..] takes the slice's x-reach and largest |r| as keys (pcon_key; the lower end as
-   the key of its negation), one atomic per workgroup each.  With R.check the refusal of k_pcov_balls, the same test. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcon_samples(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
-        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
-        const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
-        const int *__restrict__ node_start, const int *__restrict__ node_cnt, const int *__restrict__ off, int sb, int s0,
-        PCovRange R, float4 *__restrict__ tab, unsigned *__restrict__ reach, int *__restrict__ err)
-{
-    __shared__ DynWaveLds s_w[DYN_WAVES];
-    __shared__ float2 s_ell[DYN_ELL];
-    __shared__ unsigned s_reach[3];
-    dyn_stage_ellipse(ell_cs, s_ell);
-    const DynGrid G = dyn_grid(m);
-    const int i = s0 + blockIdx.y, s = sb + i;
-    const int o0 = off[i], cnt = off[i + 1] - o0;
-    if (threadIdx.x < 3) s_reach[threadIdx.x] = 0;
-    __syncthreads();
-    if (cnt <= 0) return; /* the whole workgroup: no knots, too few, or refused by k_pcon_offsets */
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int st = node_start[s], mm = node_cnt[s];
-    const float *ky = node_y + st, *kx = node_x + st, *kz = node_z + st;
-    const double miny = (double)ky[0];
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    DynWaveLds &L = s_w[wv];
-    float nlo = -INFINITY, hi = -INFINITY, rmax = -INFINITY; /* the wave's: -min(qx - |r|), max(qx + |r|), max |r| */
-    for (int j = blockIdx.x * DYN_WAVES + wv; j < cnt; j += gridDim.x * DYN_WAVES) {
-        const double dy = dyn_boundary_dy(D, miny, j);
-        double point[3];
-        spline_point_f(ky, kx, kz, mm, dy, point);
-        StampCtx sc; sc.begin(15, false);
-        float b[3], ext[2];
-        const int kk = wave_area2cloud<true>(V, G, L, normals4, s_ell, D, point, 0, b, sc, ext);
-        const float r = (ext[0] - ext[1]) / 2, r2 = r * r;
-        const float qx = (float)point[0], qy = (float)point[1], qz = (float)point[2];
-        if (R.check && qx == qx && qy == qy && qz == qz) {
-            float lo = kk < D.k ? -INFINITY : INFINITY, hi2 = kk < D.k ? INFINITY : -INFINITY;
-            if (lane < kk) {
-                const float4 c = V.at(L.sel[lane]);
-                const float dq = sqrtf(dist2_flann(qx, qy, qz, c.x, c.y, c.z)) * 1.0001f;
-                lo = fminf(lo, fminf(qx - dq, c.x - R.normal_radius * 1.0001f));
-                hi2 = fmaxf(hi2, fmaxf(qx + dq, c.x + R.normal_radius * 1.0001f));
-            }
-            if (r2 == r2) { lo = fminf(lo, qx - fabsf(r) * 1.0001f); hi2 = fmaxf(hi2, qx + fabsf(r) * 1.0001f); }
-            lo = wave_min(lo); hi2 = wave_max(hi2);
-            if (lane == 0 && ((lo < R.incl_lo && R.incl_lo > R.mn_x) || (hi2 > R.incl_hi && R.incl_hi < R.mx_x))) atomicOr(err, 1);
-        }
-        if (lane == 0) tab[o0 + j] = make_float4(qx, qy, qz, r2);
-        if (r2 == r2 && qx == qx && qz == qz) { /* a ball that can hold a point */
-            nlo = fmaxf(nlo, fabsf(r) - qx); hi = fmaxf(hi, qx + fabsf(r)); rmax = fmaxf(rmax, fabsf(r));
-        }
-    }
-    if (lane == 0 && rmax >= 0.f) { atomicMax(&s_reach[0], pcon_key(nlo)); atomicMax(&s_reach[1], pcon_key(hi)); atomicMax(&s_reach[2], pcon_key(rmax)); }
-    __syncthreads();
-    if (threadIdx.x < 3 && s_reach[threadIdx.x]) atomicMax(reach + 3 * i + threadIdx.x, s_reach[threadIdx.x]);
-}
-
-/* One thread per position of the slab index, PCON_T consecutive positions a round (one x-interval, a slab or two): the
-   slices whose reach, padded as wave_mark_ball pads, meets the round's x-interval are listed in LDS; for each, the point
-   bisects the slice's table for qy >= y - rmax - pad (qy does not decrease with j), walks to qy > y + rmax + pad and counts
-   the balls with dist2_flann(q, p) <= r2.  count, first and last stay in registers and are written once, at the point's
-   cloud index (idx_of); points that no ball holds keep the 0 / -1 of the memset. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
-        const int *__restrict__ off, const unsigned *__restrict__ reach, int sb, int nsl, unsigned *__restrict__ counts,
-        int *__restrict__ first, int *__restrict__ last)
-{
-    __shared__ int s_scan[17];
-    __shared__ float s_x[2][PCON_T / 64];
-    __shared__ int s_k[PCON_T];
-    __shared__ float4 s_sl[PCON_T]; /* lo, hi, rmax of listed slice e; w: its first table row (bits) */
-    const int total = m->n_sorted;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int c0 = blockIdx.x * PCON_T; c0 < total; c0 += gridDim.x * PCON_T) {
-        const int pi = c0 + threadIdx.x;
-        const bool have = pi < total;
-        const float4 p = have ? sorted4[pi] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float wmn = wave_min(have ? p.x : INFINITY), wmx = wave_max(have ? p.x : -INFINITY);
-        __syncthreads(); /* the round before has read its lists */
-        if (lane == 0) { s_x[0][wv] = wmn; s_x[1][wv] = wmx; }
-        __syncthreads();
-        float cmn = s_x[0][0], cmx = s_x[1][0];
-        for (int w = 1; w < PCON_T / 64; ++w) { cmn = fminf(cmn, s_x[0][w]); cmx = fmaxf(cmx, s_x[1][w]); }
-        const float cabs = fmaxf(fabsf(cmn), fabsf(cmx));
-        unsigned cnt = 0;
-        int fs = -1, ls = -1;
-        const float padp = 1e-5f * fabsf(p.x) + 1e-6f, padq = 1e-5f * fabsf(p.y) + 1e-6f;
-        for (int b0 = 0; b0 < nsl; b0 += PCON_T) {
-            const int k = b0 + threadIdx.x;
-            int take = 0;
-            float lo = 0.f, hi = 0.f, rm = 0.f;
-            if (k < nsl) {
-                const unsigned kh = reach[3 * k + 1];
-                if (kh) {
-                    lo = -pcon_unkey(reach[3 * k]); hi = pcon_unkey(kh); rm = pcon_unkey(reach[3 * k + 2]);
-                    const float pad = 1e-5f * (cabs + rm) + 1e-6f;
-                    take = (lo - pad <= cmx && hi + pad >= cmn) ? 1 : 0;
-                }
-            }
-            int nt;
-            const int at = block_exscan(take, s_scan, &nt);
-            if (take) { s_k[at] = k; s_sl[at] = make_float4(lo, hi, rm, __int_as_float(off[k])); }
-            __syncthreads();
-            if (!have) continue;
-            for (int e = 0; e < nt; ++e) {
-                const float4 sl = s_sl[e];
-                const int k2 = s_k[e];
-                const float rm2 = sl.z;
-                const float padx = padp + 1e-5f * rm2;
-                if (p.x < sl.x - padx || p.x > sl.y + padx) continue;
-                const float ry = rm2 + padq + 1e-5f * rm2;
-                const float ylo = p.y - ry, yhi = p.y + ry;
-                int a = __float_as_int(sl.w), z = off[k2 + 1];
-                const int end = z;
-                while (a < z) { const int mid = (a + z) >> 1; if (tab[mid].y < ylo) a = mid + 1; else z = mid; }
-                for (int j = a; j < end; ++j) {
-                    const float4 t = tab[j];
-                    if (t.y > yhi) break;
-                    if (dist2_flann(t.x, t.y, t.z, p.x, p.y, p.z) <= t.w) {
-                        ++cnt;
-                        const int sg = sb + k2;
-                        fs = fs < 0 ? sg : min(fs, sg); ls = max(ls, sg);
-                    }
-                }
-            }
-        }
-        if (have && cnt) { const int id = idx_of(p); counts[id] = cnt; first[id] = fs; last[id] = ls; }
-    }
-}
-
-/* The statistics of the count map: bins 1 .. 63 of the histogram (bin 0 is n - covered), covered, multi_slice (last >
-   first), the sum and the largest count.  Per-workgroup LDS bins, then one integer atomic per non-empty bin and workgroup, as
-   k_cov_count counts: the same result in every run.  acc[0 .. 63] bins, [64] covered, [65] multi_slice, [66] total,
-   [67] max; workgroup 0 also copies the refusal word into [68], so that one read brings everything back. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restrict__ counts, const int *__restrict__ first,
-        const int *__restrict__ last, int n, const int *__restrict__ err, unsigned long long *__restrict__ acc)
-{
-    __shared__ int s_bin[PCON_BINS];
-    __shared__ int s_cov, s_multi;
-    __shared__ unsigned s_max;
-    __shared__ unsigned long long s_tot;
-    if (threadIdx.x < PCON_BINS) s_bin[threadIdx.x] = 0;
-    if (threadIdx.x == 0) { s_cov = 0; s_multi = 0; s_max = 0; s_tot = 0; }
-    __syncthreads();
-    int cov = 0, multi = 0;
-    unsigned mx = 0;
-    unsigned long long tot = 0;
-    const int lane = threadIdx.x & 63;
-    for (int b0 = blockIdx.x * PCON_T; b0 < n; b0 += gridDim.x * PCON_T) { /* b0 is the workgroup's: whole waves vote below */
-        const int i = b0 + threadIdx.x;
-        const unsigned c = i < n ? counts[i] : 0u;
-        const int bin = c ? (int)min(c, (unsigned)PCON_BINS - 1) : -1;
-        if (c) { ++cov; tot += c; mx = max(mx, c); multi += last[i] > first[i] ? 1 : 0; }
-        /* a wave's counts take few values: one LDS add per value present, not per point */
-        u64 todo = __ballot(bin >= 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int v = __shfl(bin, lead, 64);
-            const u64 same = __ballot(bin == v);
-            if (lane == lead) atomicAdd(&s_bin[v], __popcll(same));
-            todo &= ~same;
-        }
-    }
-    cov = wave_sum(cov); multi = wave_sum(multi); tot = wave_sum(tot);
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
-    if ((threadIdx.x & 63) == 0) {
-        if (cov) { atomicAdd(&s_cov, cov); atomicAdd(&s_tot, tot); atomicMax(&s_max, mx); }
-        if (multi) atomicAdd(&s_multi, multi);
-    }
-    __syncthreads();
-    if (threadIdx.x > 0 && threadIdx.x < PCON_BINS && s_bin[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
-    if (threadIdx.x == 0 && s_cov) { atomicAdd(acc + 64, (unsigned long long)s_cov); atomicAdd(acc + 66, s_tot); atomicMax(acc + 67, (unsigned long long)s_max); }
-    if (threadIdx.x == 0 && s_multi) atomicAdd(acc + 65, (unsigned long long)s_multi);
-    if (threadIdx.x == 0 && blockIdx.x == 0) acc[68] = (unsigned long long)(unsigned)*err;
-}
-
-/* ------------------------------------------------------------------ */
-/* Contact field (ppp_get_contact_field): compute_transform + Area2Cloud AT every cloud point -- principal   */
-/* curvatures and the half width r of the contact ellipse.  k_field_batch: a wave per 16 consecutive positions of the slab   */
-/* index, one search per point for both extrema, the wave-uniform eigen solve and axes once per batch with a lane per point.  */
-/* k_field_waves, one wave per query, is ppp_principal_curvatures_at.  A workgroup that stages a run's candidates in LDS     */
-/* and selects from there was built and measured slower.                                                      */
-/* ------------------------------------------------------------------ */
-#define FIELD_BINS 64   /* PPP_CONTACT_BINS */
-
-/* ppp_principal_curvatures_at: one wave per query q_xyz[3 j ..], wave_area2cloud<true, true> as k_pcon_samples calls it; row j
-   of curv5 (and of half_width, where one is given) is query j's. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_waves(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
-        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
-        const float *__restrict__ q_xyz, int k, float *__restrict__ curv5, float *__restrict__ half_width)
-{
-    __shared__ DynWaveLds s_w[DYN_WAVES];
-    __shared__ float2 s_ell[DYN_ELL];
-    dyn_stage_ellipse(ell_cs, s_ell);
-    __syncthreads();
-    const int wv = threadIdx.x >> 6;
-    const int j = blockIdx.x * DYN_WAVES + wv;
-    if (j >= k) return;
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    const DynGrid G = dyn_grid(m);
-    const double p[3] = {(double)q_xyz[3 * j], (double)q_xyz[3 * j + 1], (double)q_xyz[3 * j + 2]};
-    const size_t row = (size_t)j;
-    float bnd[3], ext[2], c5[5];
-    StampCtx sc; sc.begin(15, false);
-    wave_area2cloud<true, true>(V, G, s_w[wv], normals4, s_ell, D, p, 0, bnd, sc, ext, c5);
-    if ((threadIdx.x & 63) == 0) {
-        if (curv5) { float *o = curv5 + 5 * row; o[0] = c5[0]; o[1] = c5[1]; o[2] = c5[2]; o[3] = c5[3]; o[4] = c5[4]; }
-        if (half_width) half_width[row] = (ext[0] - ext[1]) / 2;
-    }
-}
-
-/* The field proper: a wave takes FIELD_Q consecutive positions of the slab index.  Each query's search and rank-order sums by the
-   whole wave, one after the other (wave_knn, wave_contact_tail part 1), the result parked in the lane of the query's number;
-   then the eigen solve and the ellipse axes -- a third of an evaluation's instructions, and the same in all 64 lanes when a wave
-   serves one query -- ONCE for the batch, a lane per query (part 2); then each query's two folds by the whole wave (part 3).
-   Rows by cloud index, as k_field_waves writes them, and the same bits. */
-#define FIELD_Q 16
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_batch(const DevMeta *m, DynParams D, const float4 *__restrict__ sorted4,
-        const int *__restrict__ slab_start, const float *__restrict__ slab_xmin, const float *__restrict__ slab_xmax,
-        const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab, int n,
-        float *__restrict__ curv5, float *__restrict__ half_width)
-{
-    __shared__ DynWaveLds s_w[DYN_WAVES];
-    __shared__ float2 s_ell[DYN_ELL];
-    dyn_stage_ellipse(ell_cs, s_ell);
-    __syncthreads();
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int base = (blockIdx.x * DYN_WAVES + wv) * FIELD_Q;
-    if (base >= n) return;
-    const int nq = min(FIELD_Q, n - base);
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab};
-    const DynGrid G = dyn_grid(m);
-    DynWaveLds &L = s_w[wv];
-    auto lane_f = [](float v, int r) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), r)); }; /* r is wave-uniform */
-    auto lane_d = [](double d, int r) {
-        const int lo = __builtin_amdgcn_readlane(__double2loint(d), r), hi = __builtin_amdgcn_readlane(__double2hiint(d), r);
-        return __hiloint2double(hi, lo);
-    };
-    float4 myq = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < nq) myq = sorted4[base + lane];
-    ContactFrame mine = {};
-    int mykk = 0;
-    StampCtx sc; sc.begin(15, false);
-    float bnd[3], ext[2], c5[5];
-    for (int qi = 0; qi < nq; ++qi) {
-        const float sp[3] = {lane_f(myq.x, qi), lane_f(myq.y, qi), lane_f(myq.z, qi)};
-        float nn[3] = {0.f, 0.f, 0.f};
-        const int kk = wave_knn(V, G, L, sp[0], sp[1], sp[2], D.k, D.r0, normals4, nn, sc);
-        ContactFrame F = {};
-        if (kk > 0) wave_contact_tail<true, true, 1>(m, L, s_ell, D, sp, nn, kk, 0, bnd, sc, ext, c5, &F);
-        if (lane == qi) {
-            for (int i = 0; i < 6; ++i) mine.cov[i] = F.cov[i];
-            for (int i = 0; i < 3; ++i) mine.n0[i] = F.n0[i];
-            mykk = kk;
-        }
-        __builtin_amdgcn_wave_barrier(); /* the next search writes where these sums were read */
-    }
-    {
-        const float sp[3] = {myq.x, myq.y, myq.z}, nn[3] = {0.f, 0.f, 0.f};
-        wave_contact_tail<true, true, 2>(m, L, s_ell, D, sp, nn, mykk > 0 ? mykk : 1, 0, bnd, sc, ext, c5, &mine);
-        if (lane < nq && mykk > 0 && curv5) {
-            float *o = curv5 + 5 * (size_t)idx_of(myq);
-            o[0] = c5[0]; o[1] = c5[1]; o[2] = c5[2]; o[3] = c5[3]; o[4] = c5[4];
-        }
-    }
-    if (!half_width) return;
-    for (int qi = 0; qi < nq; ++qi) {
-        if (__builtin_amdgcn_readlane(mykk, qi) <= 0) continue;
-        const float sp[3] = {lane_f(myq.x, qi), lane_f(myq.y, qi), lane_f(myq.z, qi)}, nn[3] = {0.f, 0.f, 0.f};
-        ContactFrame F = {};
-        for (int i = 0; i < 3; ++i) { F.n0[i] = lane_f(mine.n0[i], qi); F.cv[i] = lane_f(mine.cv[i], qi); F.cr[i] = lane_f(mine.cr[i], qi); }
-        F.pc0 = lane_f(mine.pc0, qi); F.pc1 = lane_f(mine.pc1, qi);
-        F.longAxis = lane_d(mine.longAxis, qi); F.shortAxis = lane_d(mine.shortAxis, qi);
-        ext[0] = ext[1] = NAN;
-        wave_contact_tail<true, true, 3>(m, L, s_ell, D, sp, nn, 1, 0, bnd, sc, ext, c5, &F);
-        if (lane == 0) half_width[__builtin_amdgcn_readlane(idx_of(myq), qi)] = (ext[0] - ext[1]) / 2;
-    }
-}
-
-/* The statistics of the half-width map.  Workgroup g takes the contiguous part [g per, (g + 1) per) of the map: counts and
-   bins with integer atomics (per-workgroup LDS bins, then one atomic per non-empty bin, as k_pcon_stats), the smallest and
-   largest |r| as ordered keys, and the part's sum of |r| in double -- every thread its strided share in index order, then a
-   fixed tree over the threads -- to psum[g]: the host adds the parts in order, so the sum is the same in every run.
-   acc[0 .. 63] bins, [64] valid, [65] narrow (2 |r| < min_width, min_width > 0), [66] key of -min |r|, [67] key of max |r|. */
-__global__ void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict__ half_width, int n, int per, double tool_radius,
-        float min_width, unsigned long long *__restrict__ acc, double *__restrict__ psum)
-{
-    __shared__ int s_bin[FIELD_BINS];
-    __shared__ int s_valid, s_narrow;
-    __shared__ unsigned s_lo, s_hi;
-    __shared__ double s_sum[PCON_T];
-    if (threadIdx.x < FIELD_BINS) s_bin[threadIdx.x] = 0;
-    if (threadIdx.x == 0) { s_valid = 0; s_narrow = 0; s_lo = 0; s_hi = 0; }
-    __syncthreads();
-    const int i0 = blockIdx.x * per, i1 = min(n, i0 + per);
-    int valid = 0, narrow = 0;
-    unsigned klo = 0, khi = 0;
-    double sum = 0.0;
-    for (int i = i0 + threadIdx.x; i < i1; i += PCON_T) {
-        const float a = fabsf(half_width[i]);
-        if (!(a <= 3.402823466e+38f)) continue; /* NaN or infinite: no width */
-        ++valid;
-        if (min_width > 0.f && 2.f * a < min_width) ++narrow;
-        klo = max(klo, pcon_key(-a)); khi = max(khi, pcon_key(a));
-        sum += (double)a;
-        int bin = (int)floor((double)a / tool_radius * (double)(FIELD_BINS - 1));
-        bin = bin < 0 ? 0 : (bin > FIELD_BINS - 1 ? FIELD_BINS - 1 : bin);
-        atomicAdd(&s_bin[bin], 1);
-    }
-    s_sum[threadIdx.x] = sum;
-    valid = wave_sum(valid); narrow = wave_sum(narrow);
-    for (int o = 32; o > 0; o >>= 1) { klo = max(klo, (unsigned)__shfl_xor((int)klo, o, 64)); khi = max(khi, (unsigned)__shfl_xor((int)khi, o, 64)); }
-    if ((threadIdx.x & 63) == 0 && valid) { atomicAdd(&s_valid, valid); atomicAdd(&s_narrow, narrow); atomicMax(&s_lo, klo); atomicMax(&s_hi, khi); }
-    __syncthreads();
-    for (int o = PCON_T / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x < FIELD_BINS && s_bin[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
-    if (threadIdx.x == 0) {
-        psum[blockIdx.x] = s_sum[0];
-        if (s_valid) {
-            atomicAdd(acc + 64, (unsigned long long)s_valid); atomicAdd(acc + 65, (unsigned long long)s_narrow);
-            atomicMax(acc + 66, (unsigned long long)s_lo); atomicMax(acc + 67, (unsigned long long)s_hi);
-        }
-    }
 }

@@ -13,7 +13,8 @@
 #else
 #include "ppp_window_decl.h" /* their kernels are ppp_window.hip's */
 #endif
-#include "ppp_preproc.h"
+#include "ppp_preproc.h" /* (ppp_dynamic.h with it) */
+#include "ppp_contact.h"
 #include "ppp_sort.h"
 #include "ppp_align.h"
 #include "ppp_gather.h"
@@ -174,35 +175,32 @@ struct ppp_handle_s {
     bool dyn_keep_all = false;
     DevBuf<int> dyn_raw_sc;           /* [slice][2]: node_start / node_cnt as fitted, before the chain (k_dyn_first_eval) */
     /* coverage of the last pass (ppp_get_coverage): flags by cloud index, zero-padded to 16 bytes, and the covered count */
-    DevBuf<unsigned char> cov_flags;
-    DevBuf<int> cov_count;
-    unsigned long long cov_serial = ~0ull; /* the pass (gen_serial) they belong to */
-    size_t cov_covered = 0;
     /* path coverage of the last pass (ppp_get_path_coverage): the same, for the final paths of every walk; [1] of the count
        buffer holds the kernel's refusals (1: a search left the indexed slice range, 2: a knot table out of bounds) */
-    DevBuf<unsigned char> pcov_flags;
-    DevBuf<int> pcov_count;
-    unsigned long long pcov_serial = ~0ull;
-    size_t pcov_covered = 0;
+    struct FlagCoverage { DevBuf<unsigned char> flags; DevBuf<int> count; unsigned long long serial = ~0ull /* the pass (gen_serial) they belong to */; size_t covered = 0; } cov, pcov;
     /* path contacts of the last pass (ppp_get_path_contacts): the maps by cloud index, the per-slice sample table (rows from
-       pcon_off; its last two entries the row count and k_pcon_offsets's refusals), the slices' reach keys and the statistics
+       off; its last two entries the row count and k_pcon_offsets's refusals), the slices' reach keys and the statistics
        (acc: bins, covered, multi_slice, total, max, the refusal word; the int at acc + 69 is where the kernels set it) */
-    DevBuf<unsigned> pcon_counts, pcon_reach;
-    DevBuf<int> pcon_first, pcon_last, pcon_off;
-    DevBuf<float4> pcon_tab;
-    DevBuf<unsigned long long> pcon_acc;
-    unsigned long long pcon_serial = ~0ull;
-    ppp_contact_stats pcon_stats = {};
+    struct PathContacts {
+        DevBuf<unsigned> counts, reach;
+        DevBuf<int> first, last, off;
+        DevBuf<float4> tab;
+        DevBuf<unsigned long long> acc;
+        unsigned long long serial = ~0ull;
+        ppp_contact_stats stats = {};
+    } pcon;
     bool normals_valid = false;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
-       valid for field_P's contact parameters until the cloud changes (field_valid) */
-    DevBuf<float> field_curv, field_hw;
-    DevBuf<unsigned long long> field_acc;
-    DevBuf<double> field_psum;
-    bool field_valid = false;
-    ppp_params field_P = {};
-    float field_min_width = 0.f;
-    ppp_contact_field_stats field_stats = {};
+       valid for P's contact parameters until the cloud changes (valid) */
+    struct ContactField {
+        DevBuf<float> curv, hw;
+        DevBuf<unsigned long long> acc;
+        DevBuf<double> psum;
+        bool valid = false;
+        ppp_params P = {};
+        float min_width = 0.f;
+        ppp_contact_field_stats stats = {};
+    } field;
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
     DevBuf<float4> wp_xyz, wp_normal;
@@ -469,6 +467,16 @@ DynParams dyn_params(const ppp_handle h)
     if (const char *ev = tuning_env("PPP_DYN_R0F")) D.r0 = (float)std::max(0.5, atof(ev) * std::sqrt((double)D.k / (3.14159265358979 * rho))); /* tuning runs only */
     D.r1 = (float)std::max(0.25, 2.0 * std::sqrt(1.0 / (3.14159265358979 * rho)));
     return D;
+}
+
+/* the kernels' views of the handle's slab index / normal field and of its knot tables, as they stand when the launch is made */
+ContactIndex contact_index(const ppp_handle h)
+{
+    return ContactIndex{h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p};
+}
+KnotTable knot_table(const ppp_handle h)
+{
+    return KnotTable{h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->node_cap};
 }
 
 int ensure_dynamic_buffers(ppp_handle h)
@@ -1315,7 +1323,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                 h->plan_deferred = true; h->deferred_census = census;
                 h->have_cloud = true;
                 h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false; h->list_final = false;
-                h->normals_valid = false; h->field_valid = false;
+                h->normals_valid = false; h->field.valid = false;
                 return PPP_OK;
             }
 #ifdef PPP_TUNING
@@ -1351,7 +1359,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
     }
     h->have_cloud = true;
     h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false; h->field_valid = false;
+    h->normals_valid = false; h->field.valid = false;
 #ifdef PPP_TUNING
     if (getenv("PPP_COLD_DEBUG")) {
         const auto t_a = std::chrono::steady_clock::now();
@@ -1728,7 +1736,7 @@ int ppp_set_cloud_part(ppp_handle h, const float *xyz_host, size_t n_part, size_
     h->have_cloud = true;
     h->rec_current = false; /* (no conversion pass of the window plan's kind: the bounds came with the call) */
     h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false; h->field_valid = false;
+    h->normals_valid = false; h->field.valid = false;
     h->drop_graph();
     return make_plan(h);
 }
@@ -2999,6 +3007,88 @@ int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_
     return PPP_OK;
 }
 
+/* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
+   ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The
+   contact queries then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
+static bool pass_left_normals(const ppp_handle h) { return h->gen_done && h->P.dynamic_adjustment; }
+
+/* behind index_ready: the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
+static int contact_buffers(ppp_handle h)
+{
+    int rc = ensure_dynamic_buffers(h);
+    if (rc) return rc;
+    return pass_left_normals(h) ? PPP_OK : enqueue_normals(h);
+}
+
+/* What a pass did not build of what a contact query reads: the slab index (behind a window pass it keeps that pass's run
+   state, gen_done with it, as every API mirror's does) and contact_buffers */
+static int contact_prerequisites(ppp_handle h)
+{
+    int rc = index_ready(h, false);
+    return rc ? rc : contact_buffers(h);
+}
+
+/* the opening of a query about the paths of a finished pass whose maps go by cloud index */
+static int contact_query_begin(ppp_handle h, const char *what)
+{
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, std::string(what) + ": the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
+    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+    return PPP_OK;
+}
+
+static PCovRange pcov_range(const ppp_handle h)
+{
+    return PCovRange{h->incl_lo, h->incl_hi, h->h_mn[0], h->h_mx[0], h->P.normal_radius, h->ranged ? 1 : 0};
+}
+
+/* the refusal word of the sample kernels: 1 wave_ball_leaves_range, 2 KnotTable::slice (or 2^24 samples on a slice), 4 the
+   caps of k_pcon_offsets */
+static int contact_refusal(ppp_handle h, const char *what, unsigned long long bits)
+{
+    const std::string w(what);
+    if (bits & 2) return fail(h, PPP_ERR_HIP, w + ": a slice's knot table lies outside the node buffer");
+    if (bits & 4) return fail(h, PPP_ERR_CAPACITY, w + ": more than 2^30 contact samples");
+    if (bits & 1)
+        return fail(h, PPP_ERR_CAPACITY, w + ": a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
+    return PPP_OK;
+}
+
+/* What both coverage calls share.  On the first question about a pass: the flags by cloud index (n16 uint4s: zero padding up to
+   a multiple of 16 bytes) and the two result words zeroed, `mark` launches the balls (flags at C.flags.p, refusal word at
+   C.count.p + 1), k_cov_count counts into C.count.p[0], one read brings both back.  Later questions answer from the result. */
+static int flag_coverage(ppp_handle h, ppp_handle_s::FlagCoverage &C, const char *what, const std::function<int()> &mark, unsigned char *flags,
+                         size_t cap, size_t *n, size_t *covered)
+{
+    const size_t N = h->n, n16 = (N + 15) / 16;
+    if (C.serial != h->gen_serial) {
+        HIPCHK(h, C.flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, C.count.ensure(2));
+        HIPCHK(h, hipMemsetAsync(C.flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.count.p, 0, 2 * sizeof(int), h->stream));
+        int rc = mark();
+        if (rc) return rc;
+        if (n16)
+            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
+                   (const uint4 *)C.flags.p, (int)n16, C.count.p);
+        int res[2] = {0, 0};
+        HIPCHK(h, copy_sync(h, res, C.count.p, sizeof(res), hipMemcpyDeviceToHost));
+        rc = contact_refusal(h, what, (unsigned)res[1]);
+        if (rc) return rc;
+        if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, std::string(what) + " count corrupt");
+        C.covered = (size_t)res[0];
+        C.serial = h->gen_serial;
+    }
+    if (n) *n = N;
+    if (covered) *covered = C.covered;
+    const size_t k = std::min(cap, N);
+    if (flags && k) HIPCHK(h, copy_sync(h, flags, C.flags.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
 int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
 {
     int rc = ensure_ready(h, true, false);
@@ -3007,165 +3097,97 @@ int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, 
     if (rc) return rc;
     if (h->P.walk != PPP_WALK_V1_CONTACT || !h->P.dynamic_adjustment || h->ranged || h->use_part || h->part_given)
         return fail(h, PPP_ERR_UNSUPPORTED, "coverage: only after a PPP_WALK_V1_CONTACT pass with dynamic_adjustment = 1 on a whole-cloud handle");
-    const size_t N = h->n, n16 = (N + 15) / 16;
-    if (h->cov_serial != h->gen_serial) { /* first question about this pass: two launches, then the count */
-        HIPCHK(h, h->cov_flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, h->cov_count.ensure(1));
-        HIPCHK(h, hipMemsetAsync(h->cov_flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
-        HIPCHK(h, hipMemsetAsync(h->cov_count.p, 0, sizeof(int), h->stream));
+    auto balls = [h]() -> int { /* raw and adjusted paths of every slice, one launch */
         const int S = h->hmeta.S;
         if (S > 0)
-            LAUNCH(h, "k_cov_balls", k_cov_balls, dim3((h->dyn_maxNB + DYN_WAVES - 1) / DYN_WAVES, S, 2), 64 * DYN_WAVES, 0, h->meta.p,
-                   dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
-                   h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->dyn_raw_sc.p,
-                   h->dyn_maxNB, h->cov_flags.p);
-        if (n16)
-            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
-                   (const uint4 *)h->cov_flags.p, (int)n16, h->cov_count.p);
-        int cnt = 0;
-        HIPCHK(h, copy_sync(h, &cnt, h->cov_count.p, sizeof(int), hipMemcpyDeviceToHost));
-        if (cnt < 0 || (size_t)cnt > N) return fail(h, PPP_ERR_HIP, "coverage count corrupt");
-        h->cov_covered = (size_t)cnt;
-        h->cov_serial = h->gen_serial;
-    }
-    if (n) *n = N;
-    if (covered) *covered = h->cov_covered;
-    const size_t k = std::min(cap, N);
-    if (flags && k) HIPCHK(h, copy_sync(h, flags, h->cov_flags.p, k, hipMemcpyDeviceToHost));
-    return PPP_OK;
+            LAUNCH(h, "k_cov_balls", k_cov_balls, dim3((h->dyn_maxNB + DYN_WAVES - 1) / DYN_WAVES, S, 2), 64 * DYN_WAVES, 0, contact_index(h),
+                   dyn_params(h), knot_table(h), h->dyn_raw_sc.p, h->dyn_maxNB, h->cov.flags.p);
+        return PPP_OK;
+    };
+    return flag_coverage(h, h->cov, "coverage", balls, flags, cap, n, covered);
 }
 
 int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
 {
-    int rc = ensure_ready(h, true, false);
+    int rc = contact_query_begin(h, "path coverage");
     if (rc) return rc;
-    rc = map_dev_err(h);
-    if (rc) return rc;
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "path coverage: the flags address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    const size_t N = h->n, n16 = (N + 15) / 16;
-    if (h->pcov_serial != h->gen_serial) { /* first question about this pass */
+    auto balls = [h]() -> int {
+        int rc = contact_prerequisites(h);
+        if (rc) return rc;
         const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S);
-        /* what the pass did not build: the slab index (behind a window pass it keeps that pass's run state, as every API
-           mirror's does), the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
-        rc = index_ready(h, false);
-        if (rc) return rc;
-        rc = ensure_dynamic_buffers(h);
-        if (rc) return rc;
-        if (!h->P.dynamic_adjustment) { rc = enqueue_normals(h); if (rc) return rc; }
-        HIPCHK(h, h->pcov_flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, h->pcov_count.ensure(2));
-        HIPCHK(h, hipMemsetAsync(h->pcov_flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
-        HIPCHK(h, hipMemsetAsync(h->pcov_count.p, 0, 2 * sizeof(int), h->stream));
-        if (se > sb) {
-            /* samples per slice of knots spanning the cloud's y range (the kernel strides past it where adjusted knots reach further) */
-            const double yr = (double)h->h_mx[1] - (double)h->h_mn[1];
-            const int nb = (int)std::min(65536.0, std::max(0.0, yr - 4) / (h->P.tool_radius / 4) + 4);
-            PCovRange R;
-            R.incl_lo = h->incl_lo; R.incl_hi = h->incl_hi; R.mn_x = h->h_mn[0]; R.mx_x = h->h_mx[0];
-            R.normal_radius = h->P.normal_radius; R.check = h->ranged ? 1 : 0;
-            for (int s0 = sb; s0 < se; s0 += 65535) /* (gridDim.y) */
-                LAUNCH(h, "k_pcov_balls", k_pcov_balls, dim3((nb + DYN_WAVES - 1) / DYN_WAVES, std::min(se - s0, 65535)), 64 * DYN_WAVES, 0,
-                       h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
-                       h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->node_cap, s0, R,
-                       h->pcov_flags.p, h->pcov_count.p + 1);
-        }
-        if (n16)
-            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
-                   (const uint4 *)h->pcov_flags.p, (int)n16, h->pcov_count.p);
-        int res[2] = {0, 0};
-        HIPCHK(h, copy_sync(h, res, h->pcov_count.p, sizeof(res), hipMemcpyDeviceToHost));
-        if (res[1] & 2) return fail(h, PPP_ERR_HIP, "path coverage: a slice's knot table lies outside the node buffer");
-        if (res[1] & 1)
-            return fail(h, PPP_ERR_CAPACITY, "path coverage: a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
-        if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, "path coverage count corrupt");
-        h->pcov_covered = (size_t)res[0];
-        h->pcov_serial = h->gen_serial;
-    }
-    if (n) *n = N;
-    if (covered) *covered = h->pcov_covered;
-    const size_t k = std::min(cap, N);
-    if (flags && k) HIPCHK(h, copy_sync(h, flags, h->pcov_flags.p, k, hipMemcpyDeviceToHost));
-    return PPP_OK;
+        if (se <= sb) return PPP_OK;
+        /* samples per slice of knots spanning the cloud's y range (the kernel strides past it where adjusted knots reach further) */
+        const double yr = (double)h->h_mx[1] - (double)h->h_mn[1];
+        const int nb = (int)std::min(65536.0, std::max(0.0, yr - 4) / (h->P.tool_radius / 4) + 4);
+        for (int s0 = sb; s0 < se; s0 += 65535) /* (gridDim.y) */
+            LAUNCH(h, "k_pcov_balls", k_pcov_balls, dim3((nb + DYN_WAVES - 1) / DYN_WAVES, std::min(se - s0, 65535)), 64 * DYN_WAVES, 0,
+                   contact_index(h), dyn_params(h), knot_table(h), s0, pcov_range(h), h->pcov.flags.p, h->pcov.count.p + 1);
+        return PPP_OK;
+    };
+    return flag_coverage(h, h->pcov, "path coverage", balls, flags, cap, n, covered);
 }
 
 int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap, ppp_contact_stats *stats)
 {
-    static_assert(PCON_BINS == PPP_CONTACT_BINS, "k_pcon_stats bins");
-    int rc = ensure_ready(h, true, false);
+    int rc = contact_query_begin(h, "path contacts");
     if (rc) return rc;
-    rc = map_dev_err(h);
-    if (rc) return rc;
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "path contacts: the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
     const size_t N = h->n;
-    if (h->pcon_serial != h->gen_serial) { /* first question about this pass */
+    auto &C = h->pcon;
+    if (C.serial != h->gen_serial) { /* first question about this pass */
         const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
-        /* what the pass did not build, as ppp_get_path_coverage builds it */
-        rc = index_ready(h, false);
+        rc = contact_prerequisites(h);
         if (rc) return rc;
-        rc = ensure_dynamic_buffers(h);
-        if (rc) return rc;
-        if (!h->P.dynamic_adjustment) { rc = enqueue_normals(h); if (rc) return rc; }
         const size_t N1 = std::max<size_t>(N, 1);
-        HIPCHK(h, h->pcon_counts.ensure(N1)); HIPCHK(h, h->pcon_first.ensure(N1)); HIPCHK(h, h->pcon_last.ensure(N1));
-        HIPCHK(h, h->pcon_acc.ensure(70));
-        HIPCHK(h, hipMemsetAsync(h->pcon_counts.p, 0, N1 * sizeof(unsigned), h->stream));
-        HIPCHK(h, hipMemsetAsync(h->pcon_first.p, 0xff, N1 * sizeof(int), h->stream));
-        HIPCHK(h, hipMemsetAsync(h->pcon_last.p, 0xff, N1 * sizeof(int), h->stream));
-        HIPCHK(h, hipMemsetAsync(h->pcon_acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
-        int *err = (int *)(h->pcon_acc.p + 69);
+        HIPCHK(h, C.counts.ensure(N1)); HIPCHK(h, C.first.ensure(N1)); HIPCHK(h, C.last.ensure(N1));
+        HIPCHK(h, C.acc.ensure(70));
+        HIPCHK(h, hipMemsetAsync(C.counts.p, 0, N1 * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.first.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.last.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
+        int *err = (int *)(C.acc.p + 69);
         if (nsl > 0) {
-            HIPCHK(h, h->pcon_off.ensure((size_t)nsl + 2));
-            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), h->node_y.p, h->node_start.p, h->node_cnt.p,
-                   h->node_cap, sb, nsl, h->pcon_off.p, err);
+            HIPCHK(h, C.off.ensure((size_t)nsl + 2));
+            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), knot_table(h), sb, nsl, C.off.p, err);
             std::vector<int> off((size_t)nsl + 2);
-            HIPCHK(h, copy_sync(h, off.data(), h->pcon_off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
-            if (off[nsl + 1] & 2) return fail(h, PPP_ERR_HIP, "path contacts: a slice's knot table lies outside the node buffer");
-            if (off[nsl + 1] & 4) return fail(h, PPP_ERR_CAPACITY, "path contacts: more than 2^30 contact samples");
+            HIPCHK(h, copy_sync(h, off.data(), C.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+            rc = contact_refusal(h, "path contacts", (unsigned)off[nsl + 1]);
+            if (rc) return rc;
             const int rows = off[nsl];
             int most = 0;
             for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
             if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, "path contacts: sample table corrupt");
             if (rows > 0) {
-                HIPCHK(h, h->pcon_tab.ensure((size_t)rows)); HIPCHK(h, h->pcon_reach.ensure(3 * (size_t)nsl));
-                HIPCHK(h, hipMemsetAsync(h->pcon_reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
-                PCovRange R;
-                R.incl_lo = h->incl_lo; R.incl_hi = h->incl_hi; R.mn_x = h->h_mn[0]; R.mx_x = h->h_mx[0];
-                R.normal_radius = h->P.normal_radius; R.check = h->ranged ? 1 : 0;
+                HIPCHK(h, C.tab.ensure((size_t)rows)); HIPCHK(h, C.reach.ensure(3 * (size_t)nsl));
+                HIPCHK(h, hipMemsetAsync(C.reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
                 const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
                 for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
-                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0,
-                           h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p,
-                           h->ell_cs.p, h->slab_ytab.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p,
-                           h->pcon_off.p, sb, s0, R, h->pcon_tab.p, h->pcon_reach.p, err);
+                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0, contact_index(h),
+                           dyn_params(h), knot_table(h), C.off.p, sb, s0, pcov_range(h), C.tab.p, C.reach.p, err);
                 /* one thread per indexed point (at most N of them), PCON_T a round */
                 LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
-                       h->meta.p, h->sorted4.p, h->pcon_tab.p, h->pcon_off.p, h->pcon_reach.p, sb, nsl, h->pcon_counts.p,
-                       h->pcon_first.p, h->pcon_last.p);
+                       h->meta.p, h->sorted4.p, C.tab.p, C.off.p, C.reach.p, sb, nsl, C.counts.p, C.first.p, C.last.p);
             }
         }
         LAUNCH(h, "k_pcon_stats", k_pcon_stats, (unsigned)std::min<size_t>((N1 + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus), PCON_T, 0,
-               h->pcon_counts.p, h->pcon_first.p, h->pcon_last.p, (int)N, err, h->pcon_acc.p);
+               C.counts.p, C.first.p, C.last.p, (int)N, err, C.acc.p);
         unsigned long long acc[69];
-        HIPCHK(h, copy_sync(h, acc, h->pcon_acc.p, sizeof(acc), hipMemcpyDeviceToHost));
-        if (acc[68] & 2) return fail(h, PPP_ERR_HIP, "path contacts: a slice's knot table lies outside the node buffer");
-        if (acc[68] & 1)
-            return fail(h, PPP_ERR_CAPACITY, "path contacts: a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
+        HIPCHK(h, copy_sync(h, acc, C.acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+        rc = contact_refusal(h, "path contacts", acc[68]);
+        if (rc) return rc;
         if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "path contacts: statistics corrupt");
         ppp_contact_stats st = {};
         st.n = N; st.covered = (size_t)acc[64]; st.multi_slice = (size_t)acc[65];
         st.total = acc[66]; st.max_count = (unsigned)acc[67];
         st.hist[0] = N - st.covered;
-        for (int b = 1; b < PCON_BINS; ++b) st.hist[b] = (size_t)acc[b];
-        h->pcon_stats = st;
-        h->pcon_serial = h->gen_serial;
+        for (int b = 1; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
+        C.stats = st;
+        C.serial = h->gen_serial;
     }
-    if (stats) *stats = h->pcon_stats;
+    if (stats) *stats = C.stats;
     const size_t k = std::min(cap, N);
-    if (counts && k) HIPCHK(h, copy_sync(h, counts, h->pcon_counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, h->pcon_first.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, h->pcon_last.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (counts && k) HIPCHK(h, copy_sync(h, counts, C.counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, C.first.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, C.last.p, k * sizeof(int), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 
@@ -3283,17 +3305,12 @@ int ppp_area2cloud(ppp_handle h, const double *pts_xyz, size_t k, int key, float
     double *dq = (double *)h->scratch.p;
     float *dout = (float *)(dq + 3 * k);
     HIPCHK(h, hipMemcpyAsync(dq, pts_xyz, k * 24, hipMemcpyHostToDevice, h->stream));
-    LAUNCH(h, "k_area2cloud_api", k_area2cloud_api, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, dyn_params(h),
-           h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p, dq, (int)k, key, dout);
+    LAUNCH(h, "k_area2cloud_api", k_area2cloud_api, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
+           dq, (int)k, key, dout);
     HIPCHK(h, hipMemcpyAsync(out3, dout, k * 12, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PPP_OK;
 }
-
-/* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
-   ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The two
-   calls below then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
-static bool pass_left_normals(const ppp_handle h) { return h->gen_done && h->P.dynamic_adjustment; }
 
 int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, float *out5)
 {
@@ -3302,15 +3319,13 @@ int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, floa
     if (!k) return PPP_OK;
     if (!q_xyz || !out5 || k > 0x7fffffffu / 8) return fail(h, PPP_ERR_ARG, "bad arguments");
     if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    rc = ensure_dynamic_buffers(h);
+    rc = contact_buffers(h);
     if (rc) return rc;
-    if (!pass_left_normals(h)) { rc = enqueue_normals(h); if (rc) return rc; }
     HIPCHK(h, h->scratch.ensure(k * 32 + 64));
     float *dq = (float *)h->scratch.p, *dout = dq + 3 * k;
     HIPCHK(h, hipMemcpyAsync(dq, q_xyz, k * 12, hipMemcpyHostToDevice, h->stream));
-    LAUNCH(h, "k_field_waves", k_field_waves, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, dyn_params(h),
-           h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p, dq, (int)k, dout,
-           (float *)nullptr);
+    LAUNCH(h, "k_field_waves", k_field_waves, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
+           dq, (int)k, dout, (float *)nullptr);
     HIPCHK(h, hipMemcpyAsync(out5, dout, k * 20, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PPP_OK;
@@ -3320,31 +3335,29 @@ int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, floa
 static int field_statistics(ppp_handle h, float min_width)
 {
     const size_t N = h->n;
+    auto &C = h->field;
     const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
     const int per = (int)((N + grid - 1) / grid);
-    HIPCHK(h, h->field_acc.ensure(68)); HIPCHK(h, h->field_psum.ensure((size_t)grid));
-    HIPCHK(h, hipMemsetAsync(h->field_acc.p, 0, 68 * sizeof(unsigned long long), h->stream));
-    LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, h->field_hw.p, (int)N, per, h->P.tool_radius, min_width,
-           h->field_acc.p, h->field_psum.p);
+    HIPCHK(h, C.acc.ensure(68)); HIPCHK(h, C.psum.ensure((size_t)grid));
+    HIPCHK(h, hipMemsetAsync(C.acc.p, 0, 68 * sizeof(unsigned long long), h->stream));
+    LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, C.hw.p, (int)N, per, h->P.tool_radius, min_width, C.acc.p, C.psum.p);
     unsigned long long acc[68];
     std::vector<double> psum((size_t)grid);
-    HIPCHK(h, copy_sync(h, acc, h->field_acc.p, sizeof(acc), hipMemcpyDeviceToHost));
-    HIPCHK(h, copy_sync(h, psum.data(), h->field_psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, acc, C.acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, psum.data(), C.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
     if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "contact field: statistics corrupt");
     ppp_contact_field_stats st = {};
     st.n = N; st.valid = (size_t)acc[64]; st.narrow = (size_t)acc[65];
-    auto unkey = [](unsigned k) { unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &u, 4); return f; };
-    st.min_abs_r = st.valid ? -unkey((unsigned)acc[66]) : NAN; st.max_abs_r = st.valid ? unkey((unsigned)acc[67]) : NAN;
+    st.min_abs_r = st.valid ? -ordered_unkey((unsigned)acc[66]) : NAN; st.max_abs_r = st.valid ? ordered_unkey((unsigned)acc[67]) : NAN;
     for (double v : psum) st.sum_abs_r += v;
     for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
-    h->field_stats = st;
-    h->field_min_width = min_width;
+    C.stats = st;
+    C.min_width = min_width;
     return PPP_OK;
 }
 
 int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width, ppp_contact_field_stats *stats)
 {
-    static_assert(FIELD_BINS == PPP_CONTACT_BINS, "k_field_stats bins");
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
@@ -3355,41 +3368,38 @@ int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t 
     if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
     if (!(min_width > 0.f)) min_width = 0.f;
     const size_t N = h->n;
-    const ppp_params &P = h->P, &F = h->field_P;
-    const bool same = h->field_valid && P.tool_radius == F.tool_radius && P.depth == F.depth && P.toolthickness == F.toolthickness &&
+    auto &C = h->field;
+    const ppp_params &P = h->P, &F = C.P;
+    const bool same = C.valid && P.tool_radius == F.tool_radius && P.depth == F.depth && P.toolthickness == F.toolthickness &&
                       P.curvature_k == F.curvature_k && P.normal_radius == F.normal_radius && P.change_range == F.change_range;
     if (!same) {
-        h->field_valid = false;
-        /* the slab index (behind a window pass it keeps that pass's run state, as every API mirror's does), the Area2Cloud
-           buffers and the normal field (a pass with the dynamic adjustment made it) */
-        int rc = index_ready(h, false);
+        C.valid = false;
+        int rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
         if (rc) return rc;
         if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
-        rc = ensure_dynamic_buffers(h);
+        rc = contact_buffers(h);
         if (rc) return rc;
-        if (!pass_left_normals(h)) { rc = enqueue_normals(h); if (rc) return rc; }
         const size_t N1 = std::max<size_t>(N, 1);
-        HIPCHK(h, h->field_curv.ensure(5 * N1)); HIPCHK(h, h->field_hw.ensure(N1));
-        HIPCHK(h, hipMemsetAsync(h->field_curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* dropped points: NaN */
-        HIPCHK(h, hipMemsetAsync(h->field_hw.p, 0xff, N1 * sizeof(float), h->stream));
+        HIPCHK(h, C.curv.ensure(5 * N1)); HIPCHK(h, C.hw.ensure(N1));
+        HIPCHK(h, hipMemsetAsync(C.curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* dropped points: NaN */
+        HIPCHK(h, hipMemsetAsync(C.hw.p, 0xff, N1 * sizeof(float), h->stream));
         const int nsorted = h->hmeta.n_sorted;
         if (nsorted < 0 || (size_t)nsorted > N) return fail(h, PPP_ERR_HIP, "contact field: index corrupt");
         if (nsorted > 0) /* a wave per FIELD_Q indexed points, in slab / y order */
             LAUNCH(h, "k_field_batch", k_field_batch, (unsigned)((nsorted + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
-                   h->meta.p, dyn_params(h), h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p,
-                   h->slab_ytab.p, nsorted, h->field_curv.p, h->field_hw.p);
+                   contact_index(h), dyn_params(h), nsorted, C.curv.p, C.hw.p);
         rc = field_statistics(h, min_width);
         if (rc) return rc;
-        h->field_P = h->P;
-        h->field_valid = true;
-    } else if (stats && min_width != h->field_min_width) {
+        C.P = h->P;
+        C.valid = true;
+    } else if (stats && min_width != C.min_width) {
         int rc = field_statistics(h, min_width);
         if (rc) return rc;
     }
-    if (stats) *stats = h->field_stats;
+    if (stats) *stats = C.stats;
     const size_t k = std::min(cap, N);
-    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, h->field_curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
-    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, h->field_hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
+    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 
