@@ -117,6 +117,9 @@ public:
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }
+    /* where the planned paths leave the workpiece untouched: the uncovered points as connected regions, one line per region of
+       PPP_GAPS_MIN points or more with its size, extent and centre (ppp_get_regions) */
+    void get_gaps() { planner.print_gaps(); }
 
 protected:
     virtual void read_config(std::string filename)

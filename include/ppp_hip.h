@@ -318,6 +318,46 @@ typedef struct {
 } ppp_contact_field_stats;
 int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width,
                           ppp_contact_field_stats *stats);
+/* Connected regions of selected cloud points: WHERE the points a contact query singles out lie, in
+   how many pieces, and how large each piece is.  source picks the points: those ppp_get_path_coverage does not flag, those
+   with last_slice > first_slice in ppp_get_path_contacts, the valid points of ppp_get_contact_field whose contact width 2|r| is
+   below threshold (mm; threshold is read for this source only), or the caller's mask.  Points dropped from the index
+   (non-finite) are never selected, whatever the source or the mask says.  Two selected points are LINKED when their squared
+   distance, in float as every radius search of the engine computes it (((dx*dx) + dy*dy) + dz*dz), is <= link_radius *
+   link_radius (the float product); link_radius <= 0 means the handle's normal_radius.  A region is a connected component of
+   that graph.
+     labels[i]  = the region's label for a selected point i, -1 otherwise, for the first min(cap, n) points
+     regions[]  = the regions in ascending label, the first min(region_cap, stats->regions) of them
+   A region's label is the smallest cloud index in it: its name, the same in every run.  count is exact; mn / mx are the exact
+   float minima / maxima of its points; centroid[c] = (the sum over its points of llrint((double)p[c] * 2^20), taken in 64-bit
+   integers) / count / 2^20 in double -- an integer sum has no order, so labels, rows and stats are the same bits in every run
+   and on every fresh handle.  If max |coordinate| * 2^20 * selected could reach 2^62, all centroids are NaN and nothing else
+   changes.  stats: n = cloud->size(), selected, regions, singletons = regions of one point, largest = the largest count.
+   Every output pointer may be NULL; cap = 0 / region_cap = 0 is the size query.
+   Builds, reuses and refuses like its source: UNCOVERED / OVERLAP need a finished pass and go through ppp_get_path_coverage /
+   ppp_get_path_contacts (building that result if the handle does not hold it, leaving it untouched if it does); NARROW needs a
+   cloud and parameters only, as ppp_get_contact_field; MASK needs a cloud only (it builds the slab index if the handle has
+   none).  A window-path handle stays on the window path.  The result is kept per (source, threshold, link radius, the source's
+   result): a repeated call launches nothing; a MASK call always recomputes.  No region call invalidates or recomputes one of
+   the four contact results.  Blocks until the results are on the host.
+   PPP_ERR_ARG: no cloud; UNCOVERED / OVERLAP before any pass; an unknown source; MASK with mask == NULL; NARROW with a threshold
+   that is not a positive finite number; a NaN or infinite link_radius; curvature_k outside [3, 64] where the source refuses it.
+   PPP_ERR_UNSUPPORTED on a slice-range handle (slice_begin / slice_end) and on a part handle (ppp_set_cloud_part): a region does
+   not stop at a range border; tiling regions over ranges is a later step.  The pass's own error if it failed.  PPP_ERR_CAPACITY
+   if a walk of the union-find reaches its trip cap (no sound input does). */
+enum { PPP_REGIONS_UNCOVERED = 0,  /* points ppp_get_path_coverage does not flag (indexed points only)            */
+       PPP_REGIONS_OVERLAP   = 1,  /* points with last_slice > first_slice in ppp_get_path_contacts               */
+       PPP_REGIONS_NARROW    = 2,  /* valid points of ppp_get_contact_field with 2|r| < threshold (mm)            */
+       PPP_REGIONS_MASK      = 3   /* the caller's mask: n bytes on the host, non-zero = selected                 */ };
+typedef struct {
+    int          label;        /* the smallest cloud index in the region: its name, the same in every run */
+    unsigned int count;        /* points in it */
+    float        mn[3], mx[3]; /* bounding box, resident coordinates (mm after ChangeRange) */
+    double       centroid[3];  /* fixed-point mean (see above) */
+} ppp_region;
+typedef struct { size_t n, selected, regions, singletons, largest; } ppp_region_stats;
+int ppp_get_regions(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius,
+                    int *labels, size_t cap, ppp_region *regions, size_t region_cap, ppp_region_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

@@ -348,6 +348,42 @@ public:
         std::printf("half width |r|: min %f, mean %f, max %f\n", st.valid ? st.min_abs_r : 0.f, mean, st.valid ? st.max_abs_r : 0.f);
         std::printf("narrow: %zu points with a contact width below the slice step %d\n", st.narrow, step);
     }
+    /* connected regions of the points a contact query singles out (ppp_get_regions: by default the points path_coverage() does
+       not flag, linked within link_radius, <= 0: normal_radius): the statistics and, when asked for, the region rows in ascending
+       label and the label of every cloud point (-1: not selected) */
+    bool regions(ppp_region_stats &st, std::vector<ppp_region> *rows = nullptr, std::vector<int> *labels = nullptr,
+                 int source = PPP_REGIONS_UNCOVERED, const unsigned char *mask = nullptr, float threshold = 0.f, float link_radius = 0.f)
+    {
+        int rc = ppp_get_regions(h_, source, mask, threshold, link_radius, nullptr, 0, nullptr, 0, &st);
+        if (rc == PPP_OK && (rows || labels)) {
+            if (rows) rows->assign(st.regions, ppp_region{});
+            if (labels) labels->assign(st.n, -1);
+            rc = ppp_get_regions(h_, source, mask, threshold, link_radius, labels ? labels->data() : nullptr, labels ? st.n : 0,
+                                 rows ? rows->data() : nullptr, rows ? st.regions : 0, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* where the planned paths leave the workpiece untouched: the uncovered points as regions -- one line of totals, one line per
+       region of at least PPP_GAPS_MIN points (environment, default 10), largest first and ties by label, and the count of the
+       smaller ones */
+    void print_gaps()
+    {
+        const char *ev = std::getenv("PPP_GAPS_MIN");
+        const long least = ev && std::atol(ev) > 0 ? std::atol(ev) : 10;
+        ppp_region_stats st = {};
+        std::vector<ppp_region> rows;
+        if (!regions(st, &rows)) { st = ppp_region_stats{}; rows.clear(); }
+        std::printf("gaps: %zu of %zu points uncovered in %zu regions (link %g mm)\n", st.selected, st.n, st.regions,
+                    (double)cfg_.params.normal_radius);
+        std::vector<const ppp_region *> big;
+        for (const ppp_region &r : rows)
+            if ((long)r.count >= least) big.push_back(&r);
+        std::stable_sort(big.begin(), big.end(), [](const ppp_region *a, const ppp_region *b) { return a->count > b->count; });
+        for (const ppp_region *r : big)
+            std::printf("gap %d: %u points, x [%f, %f] y [%f, %f], centre (%f, %f, %f)\n", r->label, r->count, r->mn[0], r->mx[0], r->mn[1],
+                        r->mx[1], r->centroid[0], r->centroid[1], r->centroid[2]);
+        std::printf("gaps: %zu regions below %ld points\n", rows.size() - big.size(), least);
+    }
     /* getPath(): returns the list and writes pathFile exactly like path_translation_alg.cpp:216-228 */
     bool get_path(std::vector<float> &wp6)
     {

@@ -15,6 +15,7 @@
 #endif
 #include "ppp_preproc.h" /* (ppp_dynamic.h with it) */
 #include "ppp_contact.h"
+#include "ppp_regions.h"
 #include "ppp_sort.h"
 #include "ppp_align.h"
 #include "ppp_gather.h"
@@ -197,10 +198,26 @@ struct ppp_handle_s {
         DevBuf<unsigned long long> acc;
         DevBuf<double> psum;
         bool valid = false;
+        unsigned long long built = 0; /* how many times the maps were computed: what a result derived from them belongs to */
         ppp_params P = {};
         float min_width = 0.f;
         ppp_contact_field_stats stats = {};
     } field;
+    /* connected regions (ppp_get_regions): the selection by slab-index position, the dense list of the selected positions and
+       its inverse (ord), the union-find and the accumulators by ordinal, the labels by cloud index, the region rows in label
+       order; tot: regions, singletons, largest, the refusal word, then the two compaction totals.  Kept for (source, threshold,
+       link, serial of the source's result) */
+    struct Regions {
+        DevBuf<unsigned char> sel, mask;
+        DevBuf<int> list, ord, parent, labels, head_root, cnt;
+        DevBuf<RegAcc> acc, rows;
+        DevBuf<unsigned> tot;
+        bool valid = false, nan_centroid = false;
+        int source = -1;
+        float threshold = 0.f, link = 0.f;
+        unsigned long long serial = 0;
+        ppp_region_stats stats = {};
+    } regions;
     DevBuf<int> node_start, node_cnt, band_cnt;
     DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
     DevBuf<float4> wp_xyz, wp_normal;
@@ -3391,7 +3408,7 @@ int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t 
         rc = field_statistics(h, min_width);
         if (rc) return rc;
         C.P = h->P;
-        C.valid = true;
+        C.valid = true; ++C.built;
     } else if (stats && min_width != C.min_width) {
         int rc = field_statistics(h, min_width);
         if (rc) return rc;
@@ -3400,6 +3417,137 @@ int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t 
     const size_t k = std::min(cap, N);
     if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
     if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* lanes per selected point in k_reg_link */
+#ifndef REG_GROUP
+#define REG_GROUP 8
+#endif
+
+int ppp_get_regions(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius, int *labels, size_t cap,
+                    ppp_region *regions, size_t region_cap, ppp_region_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
+    if (source < PPP_REGIONS_UNCOVERED || source > PPP_REGIONS_MASK) return fail(h, PPP_ERR_ARG, "regions: unknown source");
+    if (source == PPP_REGIONS_MASK && !mask) return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_MASK needs a mask");
+    if (source == PPP_REGIONS_NARROW && !(threshold > 0.f && threshold <= 3.402823466e+38f))
+        return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_NARROW needs a positive finite threshold");
+    if (!(fabsf(link_radius) <= 3.402823466e+38f)) return fail(h, PPP_ERR_ARG, "regions: link_radius is not a finite number");
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "regions: a region does not stop at a part's border: this handle holds a part (ppp_set_cloud_part)");
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
+        return fail(h, PPP_ERR_UNSUPPORTED, "regions: a region does not stop at a range border: a slice-range handle indexes a part of the cloud only");
+    const float link = link_radius > 0.f ? link_radius : h->P.normal_radius;
+    if (source != PPP_REGIONS_NARROW) threshold = 0.f;
+    /* the source's own call: builds its result if the handle does not hold it, answers from it if it does, refuses as it does */
+    unsigned long long serial = 0;
+    int rc = PPP_OK;
+    if (source == PPP_REGIONS_UNCOVERED) { rc = ppp_get_path_coverage(h, nullptr, 0, nullptr, nullptr); serial = h->pcov.serial; }
+    else if (source == PPP_REGIONS_OVERLAP) { rc = ppp_get_path_contacts(h, nullptr, nullptr, nullptr, 0, nullptr); serial = h->pcon.serial; }
+    else if (source == PPP_REGIONS_NARROW) { rc = ppp_get_contact_field(h, nullptr, nullptr, 0, 0.f, nullptr); serial = h->field.built; }
+    if (rc) return rc;
+    const size_t N = h->n;
+    auto &R = h->regions;
+    const bool reuse = source != PPP_REGIONS_MASK && R.valid && R.source == source && R.threshold == threshold && R.link == link &&
+                       R.serial == serial && R.stats.n == N;
+    if (!reuse) {
+        R.valid = false;
+        rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+        if (rc) return rc;
+        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "regions: a slice-range handle indexes a part of the cloud only");
+        const int ns = h->hmeta.n_sorted;
+        if (ns < 0 || (size_t)ns > N || N > 0x7fffffffu) return fail(h, PPP_ERR_HIP, "regions: index corrupt");
+        double reach = 0.0; /* the largest |coordinate| of the index */
+        for (int d = 0; d < 3; ++d) reach = std::max(reach, std::max(std::fabs((double)h->hmeta.mn[d]), std::fabs((double)h->hmeta.mx[d])));
+        const size_t N1 = std::max<size_t>(N, 1);
+        const int nb_sel = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nb_head = (int)((N + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+        HIPCHK(h, R.labels.ensure(N1)); HIPCHK(h, R.head_root.ensure(N1)); HIPCHK(h, R.tot.ensure(8));
+        HIPCHK(h, R.cnt.ensure((size_t)std::max(nb_sel, nb_head) + 1));
+        HIPCHK(h, hipMemsetAsync(R.labels.p, 0xff, N1 * sizeof(int), h->stream)); /* not selected: -1 */
+        HIPCHK(h, hipMemsetAsync(R.tot.p, 0, 8 * sizeof(unsigned), h->stream));
+        int *err = (int *)R.tot.p + 3;
+        size_t nsel = 0, nreg = 0;
+        if (ns > 0) {
+            HIPCHK(h, R.sel.ensure((size_t)ns)); HIPCHK(h, R.ord.ensure((size_t)ns));
+            HIPCHK(h, hipMemsetAsync(R.ord.p, 0xff, (size_t)ns * sizeof(int), h->stream));
+            RegSource S = {source, nullptr, nullptr, nullptr, nullptr, threshold};
+            if (source == PPP_REGIONS_UNCOVERED) S.bytes = h->pcov.flags.p;
+            else if (source == PPP_REGIONS_OVERLAP) { S.first = h->pcon.first.p; S.last = h->pcon.last.p; }
+            else if (source == PPP_REGIONS_NARROW) S.half_width = h->field.hw.p;
+            else {
+                HIPCHK(h, R.mask.ensure(N1));
+                HIPCHK(h, hipMemcpyAsync(R.mask.p, mask, N, hipMemcpyHostToDevice, h->stream));
+                S.bytes = R.mask.p;
+            }
+            LAUNCH(h, "k_reg_select", k_reg_select, (unsigned)((ns + REG_T - 1) / REG_T), REG_T, 0, h->sorted4.p, ns, S, R.sel.p);
+            RegSel sel = {R.sel.p, nullptr, R.ord.p, nullptr, nullptr};
+            rc = compact(h, sel, ns, R.cnt.p, (int *)R.tot.p + 4, [&](int kept) -> int {
+                if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "regions: selection count corrupt");
+                nsel = (size_t)kept;
+                HIPCHK(h, R.list.ensure(nsel)); HIPCHK(h, R.parent.ensure(nsel)); HIPCHK(h, R.acc.ensure(nsel));
+                sel.list = R.list.p; sel.parent = R.parent.p; sel.acc = R.acc.p;
+                return PPP_OK;
+            });
+            if (rc) return rc;
+        }
+        if (nsel > 0) {
+            const float r2 = link * link;
+            int grp = REG_GROUP;
+            if (const char *ev = tuning_env("PPP_REG_GROUP")) grp = atoi(ev); /* tuning runs only */
+            const unsigned gl = (unsigned)((nsel * (size_t)grp + REG_T - 1) / REG_T), gp = (unsigned)((nsel + REG_T - 1) / REG_T);
+#define PPP_REG_LINK(G) LAUNCH(h, "k_reg_link", k_reg_link<G>, gl, REG_T, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_ytab.p, R.list.p, (int)nsel, R.ord.p, R.parent.p, link, r2, err)
+            if (grp == 1) PPP_REG_LINK(1);
+            else if (grp == 4) PPP_REG_LINK(4);
+            else if (grp == 16) PPP_REG_LINK(16);
+            else if (grp == 64) PPP_REG_LINK(64);
+            else if (grp == 8) PPP_REG_LINK(8);
+            else return fail(h, PPP_ERR_ARG, "regions: PPP_REG_GROUP must be 1, 4, 8, 16 or 64");
+#undef PPP_REG_LINK
+            LAUNCH(h, "k_reg_flatten", k_reg_flatten, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, err);
+            LAUNCH(h, "k_reg_labels", k_reg_labels, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, (int)N, R.labels.p,
+                   R.head_root.p, R.tot.p);
+            RegHeadSel heads = {R.labels.p, R.head_root.p, R.acc.p, nullptr};
+            rc = compact(h, heads, (int)N, R.cnt.p, (int *)R.tot.p + 5, [&](int kept) -> int {
+                if (kept < 0 || (size_t)kept > nsel) return fail(h, PPP_ERR_HIP, "regions: region count corrupt");
+                nreg = (size_t)kept;
+                HIPCHK(h, R.rows.ensure(nreg));
+                heads.rows = R.rows.p;
+                return PPP_OK;
+            });
+            if (rc) return rc;
+        }
+        unsigned tot[4];
+        HIPCHK(h, copy_sync(h, tot, R.tot.p, sizeof(tot), hipMemcpyDeviceToHost));
+        if (tot[3]) return fail(h, PPP_ERR_CAPACITY, "regions: a union-find walk reached its trip cap");
+        if (tot[0] != nreg || tot[1] > nreg || tot[2] > nsel) return fail(h, PPP_ERR_HIP, "regions: totals corrupt");
+        ppp_region_stats st = {};
+        st.n = N; st.selected = nsel; st.regions = nreg; st.singletons = tot[1]; st.largest = tot[2];
+        R.stats = st;
+        /* could a region's fixed-point sum leave 64 bits?  then no centroid is given (B.34) */
+        R.nan_centroid = reach * REG_FIXED * (double)nsel >= 4611686018427387904.0;
+        R.source = source; R.threshold = threshold; R.link = link; R.serial = serial;
+        R.valid = true;
+    }
+    if (stats) *stats = R.stats;
+    const size_t k = std::min(cap, N);
+    if (labels && k) HIPCHK(h, copy_sync(h, labels, R.labels.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    const size_t kr = std::min(region_cap, R.stats.regions);
+    if (regions && kr) {
+        std::vector<RegAcc> rows(kr);
+        HIPCHK(h, copy_sync(h, rows.data(), R.rows.p, kr * sizeof(RegAcc), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < kr; ++i) {
+            const RegAcc &a = rows[i];
+            ppp_region &o = regions[i];
+            o.label = a.label; o.count = a.count;
+            for (int c = 0; c < 3; ++c) {
+                o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]);
+                o.centroid[c] = R.nan_centroid ? (double)NAN : (double)a.sum[c] / (double)a.count / REG_FIXED;
+            }
+        }
+    }
     return PPP_OK;
 }
 

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_contact_field", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_contact_field", "ppp_get_regions", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -161,6 +161,8 @@ def lib():
         L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_contacts.argtypes = [vp, C.POINTER(C.c_uint), ip, ip, sz, C.POINTER(ContactStats)]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
+        L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
+                                      C.POINTER(RegionStats)]
         L.ppp_principal_curvatures_at.argtypes = [vp, fp, sz, fp]
         L.ppp_eval_spline.argtypes = [vp, C.c_int, dp, sz, dp]
         L.ppp_ranged_x_index.argtypes = [vp, C.c_int, ip, sz, szp]
@@ -292,6 +294,23 @@ class ContactFieldStats(C.Structure):
     """ppp_contact_field_stats"""
     _fields_ = [("n", C.c_size_t), ("valid", C.c_size_t), ("narrow", C.c_size_t), ("min_abs_r", C.c_float), ("max_abs_r", C.c_float),
                 ("sum_abs_r", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+REGIONS_UNCOVERED, REGIONS_OVERLAP, REGIONS_NARROW, REGIONS_MASK = range(4)  # PPP_REGIONS_*
+
+
+class Region(C.Structure):
+    """ppp_region"""
+    _fields_ = [("label", C.c_int), ("count", C.c_uint), ("mn", C.c_float * 3), ("mx", C.c_float * 3), ("centroid", C.c_double * 3)]
+
+
+class RegionStats(C.Structure):
+    """ppp_region_stats"""
+    _fields_ = [("n", C.c_size_t), ("selected", C.c_size_t), ("regions", C.c_size_t), ("singletons", C.c_size_t), ("largest", C.c_size_t)]
+
+
+REGION_DTYPE = np.dtype([("label", np.int32), ("count", np.uint32), ("mn", np.float32, 3), ("mx", np.float32, 3),
+                         ("centroid", np.float64, 3)], align=True)
 
 
 class PcdLayout(C.Structure):
@@ -757,6 +776,31 @@ class Engine:
         stats = dict(n=st.n, valid=st.valid, narrow=st.narrow, min_abs_r=st.min_abs_r, max_abs_r=st.max_abs_r, sum_abs_r=st.sum_abs_r,
                      mean_abs_r=(st.sum_abs_r / st.valid if st.valid else float("nan")), hist=np.array(st.hist[:], np.int64))
         return curv, hw, stats
+
+    def regions(self, source=REGIONS_UNCOVERED, mask=None, threshold=0.0, link_radius=0.0, labels=True):
+        """(labels int32[n] | None, regions, stats dict): the connected regions of the points `source` selects, two selected
+        points being linked when they are within link_radius (<= 0: the handle's normal_radius) of each other (ppp_get_regions).
+        source: REGIONS_UNCOVERED (points path_coverage() does not flag), REGIONS_OVERLAP (last > first in path_contacts()),
+        REGIONS_NARROW (valid points of contact_field() with 2|r| < threshold) or REGIONS_MASK (mask: n bytes, non-zero =
+        selected).  labels[i] = the label of point i's region (its smallest cloud index), -1 where i is not selected; regions =
+        a structured array (REGION_DTYPE: label, count, mn, mx, centroid) in ascending label; stats: n, selected, regions,
+        singletons, largest.  labels=False returns None for the labels"""
+        st = RegionStats()
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.ndim != 1 or mask.size != getattr(self, "n", mask.size):
+                raise ValueError("mask must hold one byte per cloud point")
+            mp = mask.ctypes.data_as(C.POINTER(C.c_ubyte))
+        args = (int(source), mp, float(threshold), float(link_radius))
+        self._chk(self.L.ppp_get_regions(self.h, *args, None, 0, None, 0, C.byref(st)))      # the sizes
+        lab = np.empty(max(st.n, 1), np.int32) if labels else None
+        rows = np.zeros(max(st.regions, 1), REGION_DTYPE)
+        if labels or st.regions:  # (answered from the result the first call left; a mask's is computed again)
+            self._chk(self.L.ppp_get_regions(self.h, *args, None if lab is None else _i(lab), st.n if labels else 0,
+                                             rows.ctypes.data_as(C.POINTER(Region)), st.regions, C.byref(st)))
+        stats = dict(n=st.n, selected=st.selected, regions=st.regions, singletons=st.singletons, largest=st.largest)
+        return (lab[:st.n] if labels else None), rows[:st.regions], stats
 
     def principal_curvatures_at(self, q):
         """compute_transform's principal curvatures for query points [k, 3] (float32, mm): [k, 5] = pcx pcy pcz pc1 pc2."""
