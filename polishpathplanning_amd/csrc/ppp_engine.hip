@@ -108,6 +108,80 @@ struct OwnedBuf {
 template <typename T> using DevBuf = OwnedBuf<T, false>;
 template <typename T> using PinBuf = OwnedBuf<T, true>;
 
+/* where the meta block of the pass just enqueued will turn up on the host */
+struct MetaAt {
+    enum Kind { ON_DEMAND /* nowhere: copied when somebody asks */, PINNED /* the handle's hmeta_pinned */, BATCH_SLOT /* entry slot of a batch's pinned array */ };
+    Kind kind = ON_DEMAND;
+    std::shared_ptr<PinBuf<DevMeta>> batch; /* batched launches publish every member's meta block in one pinned array, shared with the members that read it */
+    size_t slot = 0;
+    static MetaAt on_demand() { return MetaAt(); }
+    static MetaAt pinned() { MetaAt a; a.kind = PINNED; return a; }
+    static MetaAt batch_slot(const std::shared_ptr<PinBuf<DevMeta>> &metas, size_t i) { MetaAt a; a.kind = BATCH_SLOT; a.batch = metas; a.slot = i; return a; }
+};
+
+/* What a handle knows about its plan and its last pass.  The members change only through the transitions below, each named
+   for what happened on the handle; the queries' caches (coverage, contacts, regions, the knots' host copy) key on serial(). */
+class PassState {
+    bool planned_ = false, index_built_ = false, gen_done_ = false, path_done_ = false;
+    bool list_final_ = false;    /* wp_out holds a finished WayPointsList */
+    bool stage_compact_ = true;  /* wp_xyz / wp_nn / wp_normal hold the list order (a window pass leaves them in per-slice slots) */
+    unsigned long long serial_ = 0; /* counts the GenPaths enqueued */
+    bool meta_fresh_ = false;    /* hmeta is the device's block as of now: nothing was launched on this handle since it was fetched (every launch clears it) */
+    MetaAt meta_at_;             /* where the copy enqueued behind the last pass lands (ON_DEMAND: none was enqueued) */
+    hipStream_t pending_stream_ = nullptr; /* a batch graph launched on another handle's stream carries this handle's work */
+    void withdraw_results() { index_built_ = false; gen_done_ = false; meta_fresh_ = false; path_done_ = false; list_final_ = false; }
+
+public:
+    bool planned() const { return planned_; }
+    bool index_built() const { return index_built_; }
+    bool gen_done() const { return gen_done_; }
+    bool path_done() const { return path_done_; }
+    bool list_final() const { return list_final_; }
+    bool stage_compact() const { return stage_compact_; }
+    unsigned long long serial() const { return serial_; }
+    bool meta_fresh() const { return meta_fresh_; }
+    bool meta_in_flight() const { return meta_at_.kind != MetaAt::ON_DEMAND; }
+    /* the block the copy in flight lands in (handle_block: the handle's own pinned one) */
+    const DevMeta *meta_landing(const DevMeta *handle_block) const
+    {
+        return (meta_at_.kind == MetaAt::BATCH_SLOT && meta_at_.batch) ? meta_at_.batch->p + meta_at_.slot : handle_block;
+    }
+    hipStream_t pending_stream() const { return pending_stream_; }
+
+    /* no plan, no index, no results */
+    void withdraw_plan() { planned_ = false; withdraw_results(); }
+    void plan_made() { stage_compact_ = true; planned_ = true; withdraw_results(); }
+    /* a cloud was set without waiting for its bounds: results and index are gone, the plan stays */
+    void cloud_replaced_under_plan() { withdraw_results(); }
+    void index_enqueued() { index_built_ = true; }
+    void gen_enqueued(bool window) { if (window) stage_compact_ = false; gen_done_ = true; ++serial_; path_done_ = false; }
+    /* getPath (a window pass's stage lists stay as they are: still in slots, or gathered since) */
+    void path_enqueued(bool final, bool window) { path_done_ = true; list_final_ = final; if (!window) stage_compact_ = true; }
+    /* GenPath and getPath at once (a graph launch); carrier: the other handle's stream the work runs on */
+    void pass_enqueued(bool window, bool final, MetaAt at, hipStream_t carrier = nullptr)
+    {
+        if (!window) index_built_ = true;
+        stage_compact_ = !window;
+        gen_done_ = true; ++serial_; path_done_ = true;
+        list_final_ = final;
+        meta_will_arrive(std::move(at));
+        pending_stream_ = carrier;
+    }
+    /* a new plan turned out to ask for the very launches the last pass ran: its results stand */
+    void restore_results(bool had_path, bool was_final) { gen_done_ = true; path_done_ = had_path; list_final_ = was_final; }
+    void stages_gathered() { stage_compact_ = true; }
+    void streams_settled() { pending_stream_ = nullptr; }
+    /* (a batch's pinned array stays referenced until a later batch's takes its place, whatever arrives in between: no getter
+       ends up freeing pinned memory) */
+    void meta_will_arrive(MetaAt at)
+    {
+        if (at.kind == MetaAt::BATCH_SLOT) meta_at_ = std::move(at); else meta_at_.kind = at.kind;
+        meta_fresh_ = false;
+    }
+    void meta_stale() { meta_fresh_ = false; }
+    void meta_read() { meta_at_.kind = MetaAt::ON_DEMAND; meta_fresh_ = true; }
+};
+
 } // namespace
 
 struct ppp_handle_s {
@@ -117,11 +191,12 @@ struct ppp_handle_s {
     ppp_params P;
     float vp[3] = {0, 0, 0};
     size_t n = 0;
-    bool have_cloud = false, planned = false, index_built = false, gen_done = false, path_done = false;
+    bool have_cloud = false;
+    PassState pass; /* the plan and the last pass: what is planned, built, enqueued, and where its meta block arrives */
     /* host copy of the knots of the last pass (slice tables + node arrays), fetched whole by the first ppp_get_nodes after a pass:
        the planner classes ask slice by slice (a Spline view per slice: 2 calls x 256 slices), and a synchronous copy of a few
        bytes costs ~20 us on this runtime -- 60 ms of GenPath() for 0.07 ms of planning before this cache */
-    unsigned long long gen_serial = 0, hn_serial = ~0ull;
+    unsigned long long hn_serial = ~0ull; /* the pass (pass.serial()) the copy belongs to */
     std::vector<int> hn_off;    /* S + 1 offsets into ... */
     std::vector<float> hn_xyz;  /* ... three planes (x | y | z) of hn_off[S] floats */
     DevBuf<int> pack_tab;       /* device: node_start as the host validated it, then the offsets */
@@ -145,7 +220,6 @@ struct ppp_handle_s {
     int sb = 0, se = 0;           /* the range, resolved against the walk */
     float incl_lo = -INFINITY, incl_hi = INFINITY;
     int n_range = 0;              /* expected number of indexed points */
-    bool list_final = false;      /* wp_out holds a finished WayPointsList */
 
     DevBuf<float> X, Y, Z;
     /* slice-range handles: the points of [incl_lo, incl_hi] in cloud order with their cloud indices (built by make_plan):
@@ -178,7 +252,7 @@ struct ppp_handle_s {
     /* coverage of the last pass (ppp_get_coverage): flags by cloud index, zero-padded to 16 bytes, and the covered count */
     /* path coverage of the last pass (ppp_get_path_coverage): the same, for the final paths of every walk; [1] of the count
        buffer holds the kernel's refusals (1: a search left the indexed slice range, 2: a knot table out of bounds) */
-    struct FlagCoverage { DevBuf<unsigned char> flags; DevBuf<int> count; unsigned long long serial = ~0ull /* the pass (gen_serial) they belong to */; size_t covered = 0; } cov, pcov;
+    struct FlagCoverage { DevBuf<unsigned char> flags; DevBuf<int> count; unsigned long long serial = ~0ull /* the pass (pass.serial()) they belong to */; size_t covered = 0; } cov, pcov;
     /* path contacts of the last pass (ppp_get_path_contacts): the maps by cloud index, the per-slice sample table (rows from
        off; its last two entries the row count and k_pcon_offsets's refusals), the slices' reach keys and the statistics
        (acc: bins, covered, multi_slice, total, max, the refusal word; the int at acc + 69 is where the kernels set it) */
@@ -190,7 +264,6 @@ struct ppp_handle_s {
         unsigned long long serial = ~0ull;
         ppp_contact_stats stats = {};
     } pcon;
-    bool normals_valid = false;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {
@@ -234,7 +307,6 @@ struct ppp_handle_s {
     bool win_disabled = false;  /* a pass was handed back (overflow / reach / stale plan): this cloud + parameters stay on the slab path */
     bool win_path = false;      /* the current plan runs the window path */
     bool win_staged = false;    /* the binning launch writes through LDS in window order (large clouds, ppp_window.h) */
-    bool stage_compact = true;  /* wp_xyz / wp_nn / wp_normal hold the list order (a window pass leaves them in per-slice slots) */
     float win_pad = 4.f;
     int win_NBc_thr = 0; /* y-buckets per class in launches of several workgroups per CU: the most that cost no workgroup its place in the LDS */
     int win_capw = 0, win_cap_el = 0, win_NB = 0, win_NBc = 0, win_stride = 1, win_threads = 256, win_ppt = 4, win_gs = 1;
@@ -274,7 +346,6 @@ struct ppp_handle_s {
     PinBuf<char> pin;                /* pinned staging for the small copies of the plan (bounds partials, plane table, census) */
     PinBuf<char> pcd_stage[2];       /* ppp_set_cloud_pcd: two pinned pieces ... */
     hipEvent_t pcd_ev[2] = {nullptr, nullptr}; /* ... and the event behind each one's copy */
-    bool meta_in_flight = false;
     /* A cloud set while the handle holds a window plan of an earlier cloud of the same size and parameters does not wait for its
        bounds: the conversion pass is enqueued, the plan stays, and the pass of the new cloud may be enqueued right
        behind it -- the device checks walk length, pad, bounds and capacities against the record that pass leaves, and hands a
@@ -284,21 +355,16 @@ struct ppp_handle_s {
     bool plan_deferred = false, deferred_census = false;
     bool rec_current = false;   /* plan_auto holds the record of the resident cloud (it came through k_ingest_minmax and was not altered since) */
     bool plan_walk_ok = false;  /* the window plan's S, pad and plane table are the device's own, bit for bit (plan_window: census that came with the cloud, or inherited) */
-    bool meta_fresh = false; /* hmeta is the device's block as of now: nothing was launched on this handle since it was fetched (every launch clears it) */
     bool chain_calls = false;       /* GenPath is followed by getPath in the same enqueue: its meta copy is skipped */
     float *out2 = nullptr;          /* batched form: the emitting launch also writes the list here (at most out2_cap rows) */
     int out2_cap = 0;
     float *last_out2 = nullptr;     /* where the last batch put this handle's list: a re-run after an LDS overflow writes there too */
     int last_out2_cap = 0;
-    std::shared_ptr<PinBuf<DevMeta>> bmetas; /* batched launches publish every member's meta block in one pinned array ... */
-    size_t bslot = 0;                          /* ... this handle's is entry bslot */
-    bool meta_from_batch = false;
     int internal = 0;               /* > 0 while GenPath / getPath are enqueued on behalf of a batch or a re-run (keeps last_out2) */
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     unsigned epoch = 0;                 /* bumped whenever the launch sequence of this handle changes */
     unsigned graph_epoch_seen = ~0u;    /* ppp_run_async: the plan epoch of the last call (the first call of a plan runs eagerly) */
-    hipStream_t pending_stream = nullptr; /* a batch graph launched on another handle's stream carries this handle's work */
     struct BatchGraph *batches[2] = {nullptr, nullptr}; /* cached batch graphs (lead handle only): two, so a caller can
                                                            alternate between two destination buffers (double buffering) */
     int batch_next = 0;                                 /* slot the next new graph replaces */
@@ -313,6 +379,13 @@ struct ppp_handle_s {
         ++epoch;
     }
     void drop_batch();
+    /* the resident cloud changed: what was made of the old points goes, the contact field with it.  under_plan: the cloud was
+       set without waiting for its bounds (refresh_bounds_and_plan), and the plan stays */
+    void cloud_replaced(bool under_plan = false)
+    {
+        if (under_plan) pass.cloud_replaced_under_plan(); else pass.withdraw_plan();
+        field.valid = false;
+    }
     ~ppp_handle_s()
     {
         /* the members' buffers are freed after this body, on the device it selects (`back` lives on the same device) */
@@ -429,12 +502,24 @@ hipError_t copy_sync(ppp_handle h, void *dst, const void *src, size_t bytes, hip
         KTimer *_t = (h)->timing ? timer_for((h), name) : nullptr;                                    \
         if (_t) (void)hipEventRecord(_t->e0[_t->used], (h)->stream);                                  \
         (void)hipGetLastError(); /* the check below must not pick up an older, unrelated error */     \
-        (h)->meta_fresh = false;                                                                      \
+        (h)->pass.meta_stale();                                                                       \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(block), (shmem), (h)->stream, __VA_ARGS__);         \
         if (_t) { (void)hipEventRecord(_t->e1[_t->used], (h)->stream); _t->used++; }                  \
         hipError_t _le = hipGetLastError();                                                           \
         if (_le != hipSuccess) return fail((h), PPP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(_le)); \
     } while (0)
+
+/* kernels instantiated per 256 threads of budget: f(std::integral_constant<int, N>) for the smallest N of 256, 512, 768, 1024
+   that holds a workgroup of T threads */
+template <class F>
+int with_block_size(int T, F &&f)
+{
+    if (T <= 256) return f(std::integral_constant<int, 256>());
+    if (T <= 512) return f(std::integral_constant<int, 512>());
+    if (T <= 768) return f(std::integral_constant<int, 768>());
+    return f(std::integral_constant<int, 1024>());
+}
+static_assert(POSE_T == 1024, "k_pose's widest instantiation is the ladder's top rung");
 
 int validate_params(ppp_handle h, const ppp_params *p)
 {
@@ -787,12 +872,10 @@ int enqueue_window_gen(ppp_handle h)
     const int T = h->win_threads;
     const size_t lds = win_slice_lds_for(h, A.NBc);
     const int extra = tuning_env("PPP_WIN_NO_VERIFY") ? 0 : 1; /* (tuning runs only: what the checking workgroup costs the launch) */
-    if (T <= 256) LAUNCH(h, "k_win_slice", k_win_slice<256>, A.g_slice + extra, T, lds, A);
-    else if (T <= 512) LAUNCH(h, "k_win_slice", k_win_slice<512>, A.g_slice + extra, T, lds, A);
-    else if (T <= 768) LAUNCH(h, "k_win_slice", k_win_slice<768>, A.g_slice + extra, T, lds, A);
-    else LAUNCH(h, "k_win_slice", k_win_slice<1024>, A.g_slice + extra, T, lds, A);
-    h->stage_compact = false;
-    return PPP_OK;
+    return with_block_size(T, [&](auto bs) -> int {
+        LAUNCH(h, "k_win_slice", k_win_slice<decltype(bs)::value>, A.g_slice + extra, T, lds, A);
+        return PPP_OK;
+    });
 }
 /* the rest of getPath: offsets, compaction, postion_smooth / reduceRPY / flange */
 int enqueue_window_finish(ppp_handle h)
@@ -828,7 +911,7 @@ int make_plan(ppp_handle h)
     /* from here on the handle's members are rewritten step by step: a re-plan that fails half way (a slice range wider
        than the part this handle holds, an allocation) must leave no old plan, no finished-looking results and no
        captured graph behind for a later ppp_run_async to replay against the new members */
-    h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false; h->list_final = false;
+    h->pass.withdraw_plan();
     h->drop_graph();
     const int n = (int)h->n;
     /* exact slice count from the cached bounds (the device recomputes the same walk) */
@@ -979,9 +1062,7 @@ int make_plan(ppp_handle h)
     HIPCHK(h, h->wp_out.ensure(6 * (size_t)h->W_cap));
     h->sm_tiles = smooth_tiles(h->W_cap);
     { int rcw = plan_window(h, S, per); if (rcw) return rcw; }
-    h->stage_compact = true;
-    h->planned = true;
-    h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false; h->list_final = false;
+    h->pass.plan_made();
     h->drop_graph(); /* buffer addresses and launch geometry are baked into the captured graph */
     return PPP_OK;
 }
@@ -1005,7 +1086,7 @@ int enqueue_index(ppp_handle h)
     const int *idmap = h->use_part ? h->part_idx.p : ((h->part_given && h->part_has_idx) ? h->part_idx.p : nullptr);
     DevParams D = dev_params(h);
     h->slab_cnt_used = true;
-    D.keep_run_state = (h->win_path && h->gen_done) ? 1 : 0; /* an API mirror asks for the slab index behind a finished window pass */
+    D.keep_run_state = (h->win_path && h->pass.gen_done()) ? 1 : 0; /* an API mirror asks for the slab index behind a finished window pass */
     size_t hist_lds = sizeof(int) * (size_t)h->B;
     /* slab grid from the bounds cached when the cloud was set (identical to what k_minmax finds) */
     const float slab_x0 = h->h_mn[0];
@@ -1066,7 +1147,7 @@ int enqueue_index(ppp_handle h)
     if (h->big_path)
         LAUNCH(h, "k_slab_sort_arena", k_slab_sort<true>, h->B, SORT_T, 0, h->unsorted4.p, h->slab_start.p, h->sorted4.p,
                h->slab_xmin.p, h->slab_xmax.p, h->meta.p, h->slab_cap, h->big_slabs.p, h->arena.p, (unsigned long long)h->arena.cap, h->slab_ytab.p, 0, (int *)nullptr);
-    h->index_built = true;
+    h->pass.index_enqueued();
     return PPP_OK;
 }
 
@@ -1117,9 +1198,9 @@ int enqueue_dynamic(ppp_handle h)
 /* work enqueued for this handle by a batch graph runs on the lead handle's stream */
 int settle_streams(ppp_handle h)
 {
-    if (h->pending_stream) {
-        HIPCHK(h, hipStreamSynchronize(h->pending_stream));
-        h->pending_stream = nullptr;
+    if (h->pass.pending_stream()) {
+        HIPCHK(h, hipStreamSynchronize(h->pass.pending_stream()));
+        h->pass.streams_settled();
     }
     return PPP_OK;
 }
@@ -1135,34 +1216,32 @@ int settle(ppp_handle h)
    path, same size and parameters) before that cloud's bounds have come back */
 int settle_enqueue_only(ppp_handle h)
 {
-    if (h->plan_deferred && h->planned && h->win_path) return settle_streams(h);
+    if (h->plan_deferred && h->pass.planned() && h->win_path) return settle_streams(h);
     return settle(h);
 }
 
 int fetch_meta(ppp_handle h)
 {
     { int rc = settle(h); if (rc) return rc; }
-    if (h->meta_in_flight) { /* GenPath / getPath already enqueued the copy behind their last kernel */
+    if (h->pass.meta_in_flight()) { /* GenPath / getPath already enqueued the copy behind their last kernel */
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->hmeta = (h->meta_from_batch && h->bmetas) ? h->bmetas->p[h->bslot] : *h->hmeta_pinned.p;
-        h->meta_in_flight = false;
-        h->meta_fresh = true;
+        h->hmeta = *h->pass.meta_landing(h->hmeta_pinned.p);
+        h->pass.meta_read();
         return PPP_OK;
     }
     /* (a planner class asks per slice -- a Spline view per slice, two questions each: a copy and a wait per question were
        11 ms of GenPath() at 256 slices) */
-    if (h->meta_fresh) return PPP_OK;
+    if (h->pass.meta_fresh()) return PPP_OK;
     HIPCHK(h, hipMemcpyAsync(&h->hmeta, h->meta.p, sizeof(DevMeta), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->meta_fresh = true;
+    h->pass.meta_read();
     return PPP_OK;
 }
 
 int enqueue_meta_copy(ppp_handle h)
 {
     HIPCHK(h, hipMemcpyAsync(h->hmeta_pinned.p, h->meta.p, sizeof(DevMeta), hipMemcpyDeviceToHost, h->stream));
-    h->meta_in_flight = true;
-    h->meta_from_batch = false;
+    h->pass.meta_will_arrive(MetaAt::pinned());
     return PPP_OK;
 }
 
@@ -1187,11 +1266,38 @@ int map_dev_err(ppp_handle h)
     return fail(h, PPP_ERR_HIP, "unknown device error");
 }
 
+/* turn the arena passes on: the LDS-overflow kernels follow the fast ones from the next launch sequence on */
+int enable_arena(ppp_handle h)
+{
+    h->big_path = true;
+    h->drop_graph();
+    HIPCHK(h, h->arena.ensure((size_t)64 * std::max<size_t>(h->n, 1) + (1u << 20)));
+    return PPP_OK;
+}
+
+int row_cap(size_t cap_rows) { return (int)std::min<size_t>(cap_rows, 0x7fffffff); }
+
+/* A whole pass on behalf of a batch, a graph or a re-run: GenPath, then getPath where wanted.  dst_rows: the emitting launch
+   also writes the list there (at most cap_rows rows).  chained: getPath follows in the same enqueue, GenPath skips its meta
+   copy.  The error, if any, is in h->err; a capture in progress is the caller's to end. */
+int enqueue_pass(ppp_handle h, float *dst_rows, size_t cap_rows, bool chained, bool want_path = true)
+{
+    ++h->internal;
+    if (chained) h->chain_calls = true;
+    int rc = ppp_gen_path_async(h);
+    h->chain_calls = false;
+    if (dst_rows) { h->out2 = dst_rows; h->out2_cap = row_cap(cap_rows); }
+    if (rc == PPP_OK && want_path) rc = ppp_get_path_async(h);
+    h->out2 = nullptr; h->out2_cap = 0;
+    --h->internal;
+    return rc;
+}
+
 /* An overflow of the LDS-resident fast path is not an error of the input: turn the arena passes on
    and run the same calls again, once. */
 int rerun_with_arena(ppp_handle h)
 {
-    const bool had_path = h->path_done;
+    const bool had_path = h->pass.path_done();
     if (h->win_path && h->hmeta.win_flag && getenv("PPP_WIN_DEBUG"))
         fprintf(stderr, "[ppp] window pass handed back: flags %d (1 overflow, 2 reach, 4 stale plan)%s\n", h->hmeta.win_flag, h->plan_inherited ? ", capacities were inherited" : "");
     if (h->win_path && h->hmeta.win_flag && h->plan_inherited && !(h->hmeta.win_flag & ~WIN_FLAG_OVERFLOW)) {
@@ -1206,17 +1312,11 @@ int rerun_with_arena(ppp_handle h)
         int rcp = make_plan(h);
         if (rcp) return rcp;
     } else {
-        h->big_path = true;
-        h->drop_graph();
-        HIPCHK(h, h->arena.ensure((size_t)64 * (size_t)std::max<size_t>(h->n, 1) + (1u << 20)));
+        int rca = enable_arena(h);
+        if (rca) return rca;
     }
-    ++h->internal;
-    int rc = ppp_gen_path_async(h);
     /* a member of a batch: the re-planned list must land where the batch put the first one (the caller's gather buffer) */
-    h->out2 = h->last_out2; h->out2_cap = h->last_out2_cap;
-    if (rc == PPP_OK && had_path) rc = ppp_get_path_async(h);
-    h->out2 = nullptr; h->out2_cap = 0;
-    --h->internal;
+    int rc = enqueue_pass(h, h->last_out2, (size_t)h->last_out2_cap, false, had_path);
     if (rc) return rc;
     return fetch_meta(h);
 }
@@ -1233,8 +1333,8 @@ int ensure_ready(ppp_handle h, bool need_gen, bool need_path)
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (need_gen && !h->gen_done) return fail(h, PPP_ERR_ARG, "call ppp_gen_path_async first");
-    if (need_path && !h->path_done) return fail(h, PPP_ERR_ARG, "call ppp_get_path_async first");
+    if (need_gen && !h->pass.gen_done()) return fail(h, PPP_ERR_ARG, "call ppp_gen_path_async first");
+    if (need_path && !h->pass.path_done()) return fail(h, PPP_ERR_ARG, "call ppp_get_path_async first");
     int rc = fetch_meta(h);
     if (rc) return rc;
     /* a pass handed back by the window path runs on the slab index, whose LDS fast path may overflow in turn (arena passes) */
@@ -1248,8 +1348,8 @@ int ensure_index(ppp_handle h)
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
     { int rcs = settle(h); if (rcs) return rcs; }
-    if (!h->planned) { int rc = make_plan(h); if (rc) return rc; }
-    if (!h->index_built) { int rc = enqueue_index(h); if (rc) return rc; }
+    if (!h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
+    if (!h->pass.index_built()) { int rc = enqueue_index(h); if (rc) return rc; }
     return PPP_OK;
 }
 
@@ -1335,12 +1435,11 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
                (settle_enqueue_only); walk length, pad, bounds and every capacity are checked on the device against the record
                this launch leaves (win_verify_body), and the first call that needs the host's view of the cloud reads it
                (resolve_deferred). */
-            if (may_defer && reuse && h->planned && h->win_path && h->plan_walk_ok && !h->ranged && !h->use_part && h->sb == 0 && h->se == h->S_cap &&
+            if (may_defer && reuse && h->pass.planned() && h->win_path && h->plan_walk_ok && !h->ranged && !h->use_part && h->sb == 0 && h->se == h->S_cap &&
                 h->inh_S == h->S_cap && !getenv("PPP_NO_DEFERRED_PLAN")) {
                 h->plan_deferred = true; h->deferred_census = census;
                 h->have_cloud = true;
-                h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false; h->list_final = false;
-                h->normals_valid = false; h->field.valid = false;
+                h->cloud_replaced(true);
                 return PPP_OK;
             }
 #ifdef PPP_TUNING
@@ -1375,8 +1474,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
         if (!h->h_nvalid) for (int d = 0; d < 3; ++d) { h->h_mn[d] = 3.402823466e+38f; h->h_mx[d] = -3.402823466e+38f; }
     }
     h->have_cloud = true;
-    h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false; h->field.valid = false;
+    h->cloud_replaced();
 #ifdef PPP_TUNING
     if (getenv("PPP_COLD_DEBUG")) {
         const auto t_a = std::chrono::steady_clock::now();
@@ -1398,7 +1496,7 @@ int resolve_deferred(ppp_handle h)
     if (!h->plan_deferred) return PPP_OK;
     h->plan_deferred = false;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const bool ran = h->gen_done, had_path = h->path_done, was_final = h->list_final;
+    const bool ran = h->pass.gen_done(), had_path = h->pass.path_done(), was_final = h->pass.list_final();
     auto signature = [](ppp_handle q) {
         WinArgs A = win_args(q);
         memset(&A.P, 0, sizeof(A.P)); /* the parameters are the same by the rule of refresh_bounds_and_plan; what of them follows the bounds is a hint */
@@ -1421,17 +1519,11 @@ int resolve_deferred(ppp_handle h)
     const bool same = was_window && h->win_path && memcmp(&before, &after, sizeof(WinArgs)) == 0;
     if (!ran) return PPP_OK;
     if (same) {
-        h->gen_done = true; h->path_done = had_path; h->list_final = was_final; /* (make_plan withdrew them) */
+        h->pass.restore_results(had_path, was_final); /* (make_plan withdrew them) */
         return PPP_OK;
     }
     if (getenv("PPP_WIN_DEBUG")) fprintf(stderr, "[ppp] the pass enqueued ahead of this cloud's bounds ran on another plan than the cloud's own: repeated\n");
-    ++h->internal;
-    rc = ppp_gen_path_async(h);
-    h->out2 = h->last_out2; h->out2_cap = h->last_out2_cap; /* (the caller's output buffer of the first attempt) */
-    if (rc == PPP_OK && had_path) rc = ppp_get_path_async(h);
-    h->out2 = nullptr; h->out2_cap = 0;
-    --h->internal;
-    return rc;
+    return enqueue_pass(h, h->last_out2, (size_t)h->last_out2_cap, false, had_path); /* (to the caller's output buffer of the first attempt) */
 }
 
 int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_bytes, const float *viewpoint, bool may_defer = false)
@@ -1752,8 +1844,7 @@ int ppp_set_cloud_part(ppp_handle h, const float *xyz_host, size_t n_part, size_
     h->big_path = false;
     h->have_cloud = true;
     h->rec_current = false; /* (no conversion pass of the window plan's kind: the bounds came with the call) */
-    h->planned = false; h->index_built = false; h->gen_done = false; h->meta_fresh = false; h->path_done = false;
-    h->normals_valid = false; h->field.valid = false;
+    h->cloud_replaced();
     h->drop_graph();
     return make_plan(h);
 }
@@ -1768,8 +1859,7 @@ int index_ready(ppp_handle h, bool strict = true)
     rc = fetch_meta(h);
     if (rc) return rc;
     if (overflowed_fast_path(h)) {
-        h->big_path = true; h->drop_graph();
-        HIPCHK(h, h->arena.ensure((size_t)64 * std::max<size_t>(h->n, 1) + (1u << 20)));
+        rc = enable_arena(h); if (rc) return rc;
         rc = enqueue_index(h); if (rc) return rc;
         rc = fetch_meta(h); if (rc) return rc;
     }
@@ -1930,7 +2020,7 @@ int ppp_remove_outlier(ppp_handle h, int mean_k, double stddev_mul, size_t *n_ke
         HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(SorStats), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    h->meta_in_flight = false; h->meta_fresh = false;
+    h->pass.meta_will_arrive(MetaAt::on_demand());
     rc = fetch_meta(h);
     if (rc == PPP_OK) rc = map_dev_err(h);
     if (rc) return rc;
@@ -2047,7 +2137,7 @@ int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
         HIPCHK(h, hipMemcpyAsync(&n_kept, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    h->meta_in_flight = false; h->meta_fresh = false;
+    h->pass.meta_will_arrive(MetaAt::on_demand());
     rc = fetch_meta(h);
     if (rc == PPP_OK) rc = map_dev_err(h);
     if (rc) return rc;
@@ -2088,12 +2178,11 @@ int ppp_gen_path_async(ppp_handle h)
     { int rcs = settle_enqueue_only(h); if (rcs) return rcs; }
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
     if (!h->internal) { h->last_out2 = nullptr; h->last_out2_cap = 0; } /* a plain call: the list stays in the handle */
-    if (!h->planned) { int rc = make_plan(h); if (rc) return rc; }
+    if (!h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
     if (h->win_path) { /* bounds + binning into the slices' windows, then everything per slice in one launch (ppp_window.h) */
         int rcw = enqueue_window_gen(h);
         if (rcw) return rcw;
-        h->gen_done = true; ++h->gen_serial;
-        h->path_done = false;
+        h->pass.gen_enqueued(true);
         if (h->chain_calls) return PPP_OK;
         return enqueue_meta_copy(h);
     }
@@ -2123,8 +2212,7 @@ int ppp_gen_path_async(ppp_handle h)
         int rc2 = enqueue_dynamic(h);
         if (rc2) return rc2;
     }
-    h->gen_done = true; ++h->gen_serial;
-    h->path_done = false;
+    h->pass.gen_enqueued(false);
     if (h->chain_calls) return PPP_OK; /* getPath follows in the same enqueue and ends with the copy */
     return enqueue_meta_copy(h);
 }
@@ -2144,13 +2232,12 @@ int ppp_get_path_async(ppp_handle h)
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     { int rcs = settle_enqueue_only(h); if (rcs) return rcs; }
-    if (!h->gen_done) return fail(h, PPP_ERR_ARG, "call ppp_gen_path_async first");
+    if (!h->pass.gen_done()) return fail(h, PPP_ERR_ARG, "call ppp_gen_path_async first");
     if (h->win_path) { /* the per-waypoint half ran with the slices: offsets, compaction and getPath's list-wide second half */
         int rcw = enqueue_window_finish(h);
         if (rcw) return rcw;
-        h->path_done = true;
-        h->list_final = !h->ranged;
-        h->meta_in_flight = true; h->meta_from_batch = false; /* the finish launch's last workgroup leaves the meta block in hmeta_pinned */
+        h->pass.path_enqueued(!h->ranged, true);
+        h->pass.meta_will_arrive(MetaAt::pinned()); /* the finish launch's last workgroup leaves the meta block in hmeta_pinned */
         return PPP_OK;
     }
     DevParams D = dev_params(h);
@@ -2160,7 +2247,7 @@ int ppp_get_path_async(ppp_handle h)
     const int *cnt_in = (h->P.pairing == PPP_PAIR_KD && !h->P.dynamic_adjustment) ? h->slice_wpcnt.p : nullptr;
     if (h->aligned) {
         if (h->ranged) return fail(h, PPP_ERR_UNSUPPORTED, "Alignment with a slice range");
-        if (!h->back || !h->back->index_built) return fail(h, PPP_ERR_ARG, "aligned cloud without its sensor-frame index");
+        if (!h->back || !h->back->pass.index_built()) return fail(h, PPP_ERR_ARG, "aligned cloud without its sensor-frame index");
         PB.sorted4 = h->back->sorted4.p; PB.slab_start = h->back->slab_start.p; PB.slab_xmin = h->back->slab_xmin.p; PB.slab_xmax = h->back->slab_xmax.p;
         PB.m = h->back->meta.p; PB.ytab = h->back->slab_ytab.p;
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) PB.inv[r][c] = h->invTA[r][c];
@@ -2170,24 +2257,21 @@ int ppp_get_path_async(ppp_handle h)
                h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p, h->wp_pre.p, PB, h->slab_ytab.p, cnt_in);
     } else
     {
-#define PPP_POSE_ARGS h->meta.p, D, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, \
-           h->slab_xmax.p, h->px.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->wp_cnt.p, h->wp_off.p, \
-           h->tail.p, h->W_cap, h->big_path ? 1 : 0, h->knot_cap, h->stage_cap, h->tab_slabs, h->pose_pad, \
-           h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p, h->wp_pre.p, PB, h->slab_ytab.p, cnt_in
-        if (h->pose_threads <= 256) LAUNCH(h, "k_pose", (k_pose<false, 256>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), PPP_POSE_ARGS);
-        else if (h->pose_threads <= 512) LAUNCH(h, "k_pose", (k_pose<false, 512>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), PPP_POSE_ARGS);
-        else if (h->pose_threads <= 768) LAUNCH(h, "k_pose", (k_pose<false, 768>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), PPP_POSE_ARGS);
-        else LAUNCH(h, "k_pose", (k_pose<false, POSE_T>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), PPP_POSE_ARGS);
-#undef PPP_POSE_ARGS
+        int rcp = with_block_size(h->pose_threads, [&](auto bs) -> int {
+            LAUNCH(h, "k_pose", (k_pose<false, decltype(bs)::value>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), h->meta.p, D, h->sorted4.p, h->slab_start.p, h->slab_xmin.p,
+                   h->slab_xmax.p, h->px.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->wp_cnt.p, h->wp_off.p,
+                   h->tail.p, h->W_cap, h->big_path ? 1 : 0, h->knot_cap, h->stage_cap, h->tab_slabs, h->pose_pad,
+                   h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p, h->wp_pre.p, PB, h->slab_ytab.p, cnt_in);
+            return PPP_OK;
+        });
+        if (rcp) return rcp;
     }
-    h->path_done = true;
-    h->list_final = false;
-    h->stage_compact = true;
+    h->pass.path_enqueued(false, false); /* the per-waypoint half: the stage lists, no finished list yet */
     /* a slice-range handle stops here: postion_smooth couples the slices of different handles */
     if (!h->ranged) {
         int rc = enqueue_finish(h, D); /* publishes the meta block itself */
         if (rc) return rc;
-        h->list_final = true;
+        h->pass.path_enqueued(true, false);
         return PPP_OK;
     }
     return enqueue_meta_copy(h);
@@ -2199,18 +2283,18 @@ int ppp_finish_path_async(ppp_handle h, const float *pre6_dev, size_t W, const i
     HIPCHK(h, hipSetDevice(h->device));
     { int rcs = settle(h); if (rcs) return rcs; }
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (!h->planned) { int rc = make_plan(h); if (rc) return rc; }
+    if (!h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
     if ((W && !pre6_dev) || (nkept && !counts)) return fail(h, PPP_ERR_ARG, "bad arguments");
     if (W > (size_t)h->W_cap || nkept > (size_t)h->S_cap) return fail(h, PPP_ERR_CAPACITY, "the list is larger than this handle's plan (other cloud or parameters?)");
-    if (!h->index_built && !h->win_path) { int rc = enqueue_index(h); if (rc) return rc; } /* the meta block is initialised by k_setup (k_count_given sets what the finish reads) */
+    if (!h->pass.index_built() && !h->win_path) { int rc = enqueue_index(h); if (rc) return rc; } /* the meta block is initialised by k_setup (k_count_given sets what the finish reads) */
     DevParams D = dev_params(h);
     if (nkept) HIPCHK(h, hipMemcpyAsync(h->wp_cnt.p, counts, nkept * sizeof(int), hipMemcpyHostToDevice, h->stream));
     LAUNCH(h, "k_count_given", k_count_given, 1, 1024, 0, h->meta.p, D, (int)nkept, (int)W, h->wp_cnt.p, h->wp_off.p, h->tail.p, h->W_cap);
     if (W) LAUNCH(h, "k_load_pre", k_load_pre, (unsigned)((W + 255) / 256), 256, 0, h->meta.p, pre6_dev, h->wp_pre.p);
     int rc = enqueue_finish(h, D);
     if (rc) return rc;
-    h->gen_done = true; ++h->gen_serial; h->path_done = true; h->list_final = true;
-    h->stage_compact = true; /* (no per-waypoint stage lists belong to a list finished from gathered blocks) */
+    h->pass.gen_enqueued(false);
+    h->pass.path_enqueued(true, false); /* (in list order: no per-waypoint stage lists belong to a list finished from gathered blocks) */
     return PPP_OK;
 }
 
@@ -2220,33 +2304,19 @@ int ppp_run_async(ppp_handle h)
     HIPCHK(h, hipSetDevice(h->device));
     { int rcs = settle_enqueue_only(h); if (rcs) return rcs; }
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (!h->planned) { int rc = make_plan(h); if (rc) return rc; }
+    if (!h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
     h->last_out2 = nullptr; h->last_out2_cap = 0;
-    if (h->timing) {
-        int rc = ppp_gen_path_async(h);
-        return rc ? rc : ppp_get_path_async(h);
-    }
+    if (h->timing) return enqueue_pass(h, nullptr, 0, false);
     if (!h->graph_exec && h->graph_epoch_seen != h->epoch) {
         /* the first pass of a plan (a new cloud, new parameters) is enqueued directly: six launches cost the host less than
            capturing and instantiating a graph does (~0.1 ms), and a planner fed with a new cloud every time never replays.
            The second call of the same plan captures. */
         h->graph_epoch_seen = h->epoch;
-        h->chain_calls = true;
-        ++h->internal;
-        int rc = ppp_gen_path_async(h);
-        h->chain_calls = false;
-        if (rc == PPP_OK) rc = ppp_get_path_async(h);
-        --h->internal;
-        return rc;
+        return enqueue_pass(h, nullptr, 0, true);
     }
     if (!h->graph_exec) {
         HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        h->chain_calls = true;
-        ++h->internal;
-        int rc = ppp_gen_path_async(h);
-        h->chain_calls = false;
-        if (rc == PPP_OK) rc = ppp_get_path_async(h);
-        --h->internal;
+        int rc = enqueue_pass(h, nullptr, 0, true);
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(h->stream, &g);
         if (rc != PPP_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -2255,14 +2325,9 @@ int ppp_run_async(ppp_handle h)
         e = hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0);
         if (e != hipSuccess) { h->drop_graph(); return fail(h, PPP_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
     }
-    h->meta_fresh = false;
+    h->pass.meta_stale();
     HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
-    if (!h->win_path) h->index_built = true;
-    h->stage_compact = !h->win_path;
-    h->gen_done = true; ++h->gen_serial; h->path_done = true;
-    h->list_final = !h->ranged;
-    h->meta_in_flight = true; /* the captured sequence ends with the meta copy */
-    h->meta_from_batch = false;
+    h->pass.pass_enqueued(h->win_path, !h->ranged, MetaAt::pinned()); /* the captured sequence ends with the meta copy */
     return PPP_OK;
 }
 
@@ -2402,6 +2467,9 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
     return PPP_OK;
 }
 
+/* did this member's pass take the window path?  (batched launches: all members or none; else every member its own) */
+bool batch_member_ran_window(const BatchGraph *bg, const ppp_handle h) { return bg->batched ? bg->win : h->win_path; }
+
 /* one launch per stage over all members (blockIdx.y = member); ends with ONE copy of all meta blocks */
 /* the stage launches over members [first, first + n) of a batch, on `strm` (timers: the lead's, eager runs only) */
 static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t strm, size_t first, size_t n)
@@ -2416,11 +2484,11 @@ static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t s
         else if (bg->win_staged) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<4, true>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
         else if (bg->win_ppt == 8) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<8, false>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
         else LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<4, false>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
-        const int T = bg->win_threads;
-        if (T <= 256) LAUNCHB(lead, strm, "k_win_slice_b", k_win_slice_b<256>, dim3(bg->gx_slice, gy), T, bg->win_lds, wm);
-        else if (T <= 512) LAUNCHB(lead, strm, "k_win_slice_b", k_win_slice_b<512>, dim3(bg->gx_slice, gy), T, bg->win_lds, wm);
-        else if (T <= 768) LAUNCHB(lead, strm, "k_win_slice_b", k_win_slice_b<768>, dim3(bg->gx_slice, gy), T, bg->win_lds, wm);
-        else LAUNCHB(lead, strm, "k_win_slice_b", k_win_slice_b<1024>, dim3(bg->gx_slice, gy), T, bg->win_lds, wm);
+        const int rcs = with_block_size(bg->win_threads, [&](auto bs) -> int {
+            LAUNCHB(lead, strm, "k_win_slice_b", k_win_slice_b<decltype(bs)::value>, dim3(bg->gx_slice, gy), bg->win_threads, bg->win_lds, wm);
+            return PPP_OK;
+        });
+        if (rcs) return rcs;
         LAUNCHB(lead, strm, "k_win_finish_b", k_win_finish_b, dim3(bg->gx_wfin, gy), SMF_T, bg->win_fin_lds, wm);
         return PPP_OK;
     }
@@ -2432,10 +2500,11 @@ static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t s
     else LAUNCHB(lead, strm, "k_slab_scatter_b", k_slab_scatter_b<4>, dim3(gx_scat + 1, gy), SCAT_T, 2 * hist_lds, mem);
     LAUNCHB(lead, strm, "k_slab_sort_b", k_slab_sort_b, dim3(gx_sort, gy), full_slabs ? SORT_T : 256, (size_t)max_slab_cap * 12 + 16, mem);
     LAUNCHB(lead, strm, "k_slice_kd_b", k_slice_kd_b, dim3(gx_slice, gy), bg->slice_thr, slice_kd_bytes(max_capb), mem);
-    if (bg->pose_threads <= 256) LAUNCHB(lead, strm, "k_pose_b", k_pose_b<256>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
-    else if (bg->pose_threads <= 512) LAUNCHB(lead, strm, "k_pose_b", k_pose_b<512>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
-    else if (bg->pose_threads <= 768) LAUNCHB(lead, strm, "k_pose_b", k_pose_b<768>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
-    else LAUNCHB(lead, strm, "k_pose_b", k_pose_b<POSE_T>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
+    const int rcp = with_block_size(bg->pose_threads, [&](auto bs) -> int {
+        LAUNCHB(lead, strm, "k_pose_b", k_pose_b<decltype(bs)::value>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
+        return PPP_OK;
+    });
+    if (rcp) return rcp;
     LAUNCHB(lead, strm, "k_smooth_solve_b", k_smooth_solve_b, dim3(gx_smooth, gy), SMF_T, 0, mem);
     return PPP_OK;
 }
@@ -2468,8 +2537,7 @@ int enqueue_batched(ppp_handle lead, BatchGraph *bg)
                        (ppp_sync_batch, a getter) -- in a stream of steps on one workpiece a 200-byte copy behind every pass is a
                        fourth launch (a blit kernel, 4.4 us of a 68 us step) whose result only the last pass's reader looks at */
         return PPP_OK;
-    if (bg->win) LAUNCHB(lead, lead->stream, "k_collect_meta", k_collect_meta_win, dim3((unsigned)count), 64, 0, bg->wmembers.p, (int)count, bg->metas.p);
-    else LAUNCHB(lead, lead->stream, "k_collect_meta", k_collect_meta, dim3((unsigned)count), 64, 0, bg->members.p, (int)count, bg->metas.p);
+    LAUNCHB(lead, lead->stream, "k_collect_meta", k_collect_meta, dim3((unsigned)count), 64, 0, bg->members.p, (int)count, bg->metas.p);
     HIPCHK(lead, hipMemcpyAsync(bg->hmetas->p, bg->metas.p, sizeof(DevMeta) * count, hipMemcpyDeviceToHost, lead->stream));
     return PPP_OK;
 }
@@ -2493,7 +2561,7 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
         if (!h->have_cloud) return fail(lead, PPP_ERR_ARG, "a handle of the batch has no cloud");
         int rc = settle(h);
         if (rc) return rc;
-        if (!h->planned) { rc = make_plan(h); if (rc) { lead->err = h->err; return rc; } }
+        if (!h->pass.planned()) { rc = make_plan(h); if (rc) { lead->err = h->err; return rc; } }
         plain = plain || h->timing;
         batched = batched && batch_eligible(h);
         allwin = allwin && h->win_path;
@@ -2503,21 +2571,18 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
        (mixed batches take one graph branch per member, each on its own path). */
     if (allwin) batched = true;
     else for (size_t i = 0; i < count; ++i) if (hs[i]->win_path) batched = false;
+    /* member i's place in the caller's buffer */
+    auto dst_of = [&](size_t i) -> float * { return dst_dev ? dst_dev + 6 * offset_rows[i] : nullptr; };
+    auto cap_of = [&](size_t i) -> size_t { return dst_dev ? cap_rows[i] : 0; };
     auto remember_dst = [&](size_t i) { /* where a re-run after an LDS overflow must put the list (rerun_with_arena) */
-        hs[i]->last_out2 = dst_dev ? dst_dev + 6 * offset_rows[i] : nullptr;
-        hs[i]->last_out2_cap = dst_dev ? (int)std::min<size_t>(cap_rows[i], 0x7fffffff) : 0;
+        hs[i]->last_out2 = dst_of(i); hs[i]->last_out2_cap = row_cap(cap_of(i));
     };
     /* kernel timing brackets every launch with events: the batched launches run eagerly on the lead's stream (timers of the
        lead), members that need their own launch sequence run as plain per-handle calls */
     const bool eager = plain && batched;
     if (plain && !batched) {
         for (size_t i = 0; i < count; ++i) {
-            ++hs[i]->internal;
-            int rc = ppp_gen_path_async(hs[i]);
-            if (dst_dev) { hs[i]->out2 = dst_dev + 6 * offset_rows[i]; hs[i]->out2_cap = (int)std::min<size_t>(cap_rows[i], 0x7fffffff); }
-            if (rc == PPP_OK) rc = ppp_get_path_async(hs[i]);
-            hs[i]->out2 = nullptr; hs[i]->out2_cap = 0;
-            --hs[i]->internal;
+            int rc = enqueue_pass(hs[i], dst_of(i), cap_of(i), false);
             remember_dst(i);
             if (rc) { lead->err = hs[i]->err; return rc; }
         }
@@ -2553,7 +2618,7 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
             /* ONE launch per stage over all members.  Records and meta array first, outside the capture. */
             hipError_t ea = bg->members.ensure(count);
             if (ea == hipSuccess) ea = bg->wmembers.ensure(count);
-            if (ea == hipSuccess) ea = bg->metas.ensure(count);
+            if (ea == hipSuccess && !bg->win) ea = bg->metas.ensure(count); /* (a window member's finish launch publishes its meta block itself) */
             bg->hmetas = std::make_shared<PinBuf<DevMeta>>();
             if (ea == hipSuccess) ea = bg->hmetas->ensure(count);
             if (ea != hipSuccess) { discard(); return fail(lead, PPP_ERR_HIP, std::string("batch buffers: ") + hipGetErrorString(ea)); }
@@ -2583,14 +2648,8 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
             }
             for (size_t i = 0; i < count && e == hipSuccess && rc == PPP_OK; ++i) {
                 ppp_handle h = hs[i];
-                h->chain_calls = true;
-                ++h->internal;
-                rc = ppp_gen_path_async(h);
-                h->chain_calls = false;
-                if (dst_dev) { h->out2 = dst_dev + 6 * offset_rows[i]; h->out2_cap = (int)std::min<size_t>(cap_rows[i], 0x7fffffff); }
-                if (rc == PPP_OK) rc = ppp_get_path_async(h); /* the emitting launch also writes the list to its place in dst_dev */
-                h->out2 = nullptr; h->out2_cap = 0;
-                --h->internal;
+                /* (the emitting launch also writes the list to its place in dst_dev) */
+                rc = enqueue_pass(h, dst_of(i), cap_of(i), true);
                 if (rc != PPP_OK) lead->err = "batch member " + std::to_string(i) + ": " + h->err;
                 if (i && e == hipSuccess && rc == PPP_OK) {
                     e = hipEventRecord(bg->join[i], h->stream);
@@ -2619,15 +2678,10 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
     else HIPCHK(lead, hipGraphLaunch(bg->ge, lead->stream));
     for (size_t i = 0; i < count; ++i) {
         ppp_handle h = hs[i];
-        if (!(bg->batched && bg->win) && !(!bg->batched && h->win_path)) h->index_built = true;
-        h->stage_compact = !((bg->batched && bg->win) || (!bg->batched && h->win_path));
-        h->gen_done = true; ++h->gen_serial; h->path_done = true;
-        h->list_final = !h->ranged;
-        h->meta_fresh = false;
-        h->meta_in_flight = !(bg->batched && count == 1); /* a batch of one does not publish its meta block: fetched on demand */
-        h->meta_from_batch = bg->batched && count > 1;
-        if (bg->batched && count > 1) { h->bmetas = bg->hmetas; h->bslot = i; }
-        h->pending_stream = (i == 0) ? nullptr : lead->stream;
+        /* batched launches publish the members' meta blocks in the batch's pinned array -- a batch of one does not publish at all:
+           fetched on demand --; a member with a branch of its own ends with its own copy */
+        const MetaAt at = !bg->batched ? MetaAt::pinned() : (count > 1 ? MetaAt::batch_slot(bg->hmetas, i) : MetaAt::on_demand());
+        h->pass.pass_enqueued(batch_member_ran_window(bg, h), !h->ranged, at, i == 0 ? nullptr : lead->stream);
         remember_dst(i);
     }
     return PPP_OK;
@@ -2672,7 +2726,7 @@ int ppp_gather_waypoints(ppp_handle h, void *nccl_comm, int rank, int nranks, in
     HIPCHK(h, hipSetDevice(h->device));
     { int rcs = settle(h); if (rcs) return rcs; }
     if (nranks < 1 || rank < 0 || rank >= nranks || root < 0 || root >= nranks || !counts_rows) return fail(h, PPP_ERR_ARG, "bad rank / root / counts");
-    if (!h->path_done || !h->list_final) return fail(h, PPP_ERR_ARG, "no finished list on this handle (call ppp_get_path_async / ppp_run_async first)");
+    if (!h->pass.path_done() || !h->pass.list_final()) return fail(h, PPP_ERR_ARG, "no finished list on this handle (call ppp_get_path_async / ppp_run_async first)");
     if (counts_rows[rank] > (size_t)h->W_cap) return fail(h, PPP_ERR_CAPACITY, "counts_rows[rank] exceeds this handle's list capacity");
     if (rank == root && !recv_dev) return fail(h, PPP_ERR_ARG, "the root needs a receive buffer");
     /* one rank WITH a communicator (a one-rank group: the pre-flight of this exchange on one GPU): the block travels through librccl's
@@ -2718,7 +2772,7 @@ int ppp_sync_batch(ppp_handle *hs, size_t count, size_t *failed)
        a wait per handle, one after the other, cost three handles 90 us at the end of a loop) */
     for (size_t i = 0; i < count; ++i) {
         ppp_handle h = hs[i];
-        if (h && h->have_cloud && !h->plan_deferred && !h->pending_stream && !h->meta_in_flight && !h->meta_fresh && hipSetDevice(h->device) == hipSuccess)
+        if (h && h->have_cloud && !h->plan_deferred && !h->pass.pending_stream() && !h->pass.meta_in_flight() && !h->pass.meta_fresh() && hipSetDevice(h->device) == hipSuccess)
             (void)enqueue_meta_copy(h);
     }
     for (size_t i = 0; i < count; ++i) {
@@ -2767,7 +2821,7 @@ int ppp_get_waypoints(ppp_handle h, float *out6, size_t cap, size_t *W)
 {
     int rc = ensure_ready(h, true, true);
     if (rc) return rc;
-    if (!h->list_final) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
+    if (!h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
     rc = map_dev_err(h);
     if (rc) return rc;
     size_t w = (size_t)h->hmeta.W;
@@ -2783,7 +2837,7 @@ int ppp_get_waypoints_device(ppp_handle h, const float **dptr, size_t *W)
 {
     int rc = ensure_ready(h, true, true);
     if (rc) return rc;
-    if (!h->list_final) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
+    if (!h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
     rc = map_dev_err(h);
     if (rc) return rc;
     if (dptr) *dptr = h->wp_out.p;
@@ -2795,7 +2849,7 @@ int ppp_copy_waypoints_to_device(ppp_handle h, float *dst_dev, size_t cap, size_
 {
     int rc = ensure_ready(h, true, true);
     if (rc) return rc;
-    if (!h->list_final) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
+    if (!h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
     rc = map_dev_err(h);
     if (rc) return rc;
     size_t w = (size_t)h->hmeta.W;
@@ -2812,7 +2866,7 @@ int ppp_get_tail_index(ppp_handle h, int *tail, size_t cap, size_t *n)
 {
     int rc = ensure_ready(h, true, true);
     if (rc) return rc;
-    if (!h->list_final) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
+    if (!h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
     rc = map_dev_err(h);
     if (rc) return rc;
     size_t nk = (size_t)h->hmeta.nkept;
@@ -2847,7 +2901,7 @@ int ppp_copy_stage_to_device(ppp_handle h, int stage, float *dst_dev, size_t cap
     if (rc) return rc;
     const float *src = stage == PPP_STAGE_WP_PRESMOOTH ? h->wp_pre.p : stage == PPP_STAGE_WP_SMOOTHED ? h->wp_smooth.p : nullptr;
     if (!src) return fail(h, PPP_ERR_ARG, "stage must be PPP_STAGE_WP_PRESMOOTH or PPP_STAGE_WP_SMOOTHED");
-    if (stage == PPP_STAGE_WP_SMOOTHED && !h->list_final) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
+    if (stage == PPP_STAGE_WP_SMOOTHED && !h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
     size_t w = (size_t)h->hmeta.W;
     if (W) *W = w;
     size_t k = std::min(cap, w);
@@ -2861,7 +2915,7 @@ int ppp_copy_stage_to_device(ppp_handle h, int stage, float *dst_dev, size_t cap
 /* bounds and slice tables of the resident cloud: left by the last window pass (its checking workgroup), else by the slab index */
 static int bounds_ready(ppp_handle h)
 {
-    if (h && h->have_cloud && h->planned && h->win_path && h->gen_done) {
+    if (h && h->have_cloud && h->pass.planned() && h->win_path && h->pass.gen_done()) {
         HIPCHK(h, hipSetDevice(h->device));
         return PPP_OK;
     }
@@ -2900,7 +2954,7 @@ static int band_indices(ppp_handle h, float lo, float hi, int *out, size_t cap, 
     HIPCHK(h, h->scratch.ensure(sizeof(int) * (size_t)capb));
     LAUNCH(h, "k_band_indices", k_band_indices, 1, 256, slice_lds_bytes(capb), h->sorted4.p, h->slab_start.p, h->meta.p, lo, hi,
            capb, (int *)h->scratch.p, capb);
-    h->meta_in_flight = false; h->meta_fresh = false; /* the kernel above wrote meta: take a fresh copy */
+    h->pass.meta_will_arrive(MetaAt::on_demand()); /* the kernel above wrote meta: take a fresh copy */
     int rc = fetch_meta(h);
     if (rc) return rc;
     const int *src = (const int *)h->scratch.p;
@@ -2916,7 +2970,7 @@ static int band_indices(ppp_handle h, float lo, float hi, int *out, size_t cap, 
         int *hist = (int *)(srt + cnt);
         LAUNCH(h, "k_band_indices_big", k_band_indices_big, 1, 256, 0, h->sorted4.p, h->slab_start.p, h->meta.p, lo, hi, (int)h->n, tmp,
                srt, hist, NB, (int)cnt, dout);
-        h->meta_in_flight = false; h->meta_fresh = false;
+        h->pass.meta_will_arrive(MetaAt::on_demand());
         rc = fetch_meta(h);
         if (rc) return rc;
         if (h->hmeta.api_flag) return fail(h, PPP_ERR_CAPACITY, "rangedX_index: band changed size between passes");
@@ -2955,7 +3009,7 @@ int ppp_get_nodes(ppp_handle h, int s, double *y, double *x, double *z, size_t c
     int rc = ensure_ready(h, true, false);
     if (rc) return rc;
     if (s < 0 || s >= h->hmeta.S) return fail(h, PPP_ERR_ARG, "slice out of range");
-    if (h->hn_serial != h->gen_serial) { /* first question about this pass: every slice's knots, packed on the device, in one copy */
+    if (h->hn_serial != h->pass.serial()) { /* first question about this pass: every slice's knots, packed on the device, in one copy */
         const size_t S = (size_t)h->hmeta.S;
         std::vector<int> tab(2 * S + 1);
         int *start = tab.data(), *off = tab.data() + S;
@@ -2981,7 +3035,7 @@ int ppp_get_nodes(ppp_handle h, int s, double *y, double *x, double *z, size_t c
                    h->pack_out.p);
             HIPCHK(h, copy_sync(h, h->hn_xyz.data(), h->pack_out.p, 3 * total * 4, hipMemcpyDeviceToHost));
         }
-        h->hn_serial = h->gen_serial;
+        h->hn_serial = h->pass.serial();
     }
     const size_t st = (size_t)h->hn_off[(size_t)s], cnt = (size_t)(h->hn_off[(size_t)s + 1] - h->hn_off[(size_t)s]), total = (size_t)h->hn_off.back();
     if (m) *m = cnt;
@@ -3027,7 +3081,7 @@ int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_
 /* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
    ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The
    contact queries then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
-static bool pass_left_normals(const ppp_handle h) { return h->gen_done && h->P.dynamic_adjustment; }
+static bool pass_left_normals(const ppp_handle h) { return h->pass.gen_done() && h->P.dynamic_adjustment; }
 
 /* behind index_ready: the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
 static int contact_buffers(ppp_handle h)
@@ -3082,7 +3136,7 @@ static int flag_coverage(ppp_handle h, ppp_handle_s::FlagCoverage &C, const char
                          size_t cap, size_t *n, size_t *covered)
 {
     const size_t N = h->n, n16 = (N + 15) / 16;
-    if (C.serial != h->gen_serial) {
+    if (C.serial != h->pass.serial()) {
         HIPCHK(h, C.flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, C.count.ensure(2));
         HIPCHK(h, hipMemsetAsync(C.flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
         HIPCHK(h, hipMemsetAsync(C.count.p, 0, 2 * sizeof(int), h->stream));
@@ -3097,7 +3151,7 @@ static int flag_coverage(ppp_handle h, ppp_handle_s::FlagCoverage &C, const char
         if (rc) return rc;
         if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, std::string(what) + " count corrupt");
         C.covered = (size_t)res[0];
-        C.serial = h->gen_serial;
+        C.serial = h->pass.serial();
     }
     if (n) *n = N;
     if (covered) *covered = C.covered;
@@ -3150,7 +3204,7 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
     if (rc) return rc;
     const size_t N = h->n;
     auto &C = h->pcon;
-    if (C.serial != h->gen_serial) { /* first question about this pass */
+    if (C.serial != h->pass.serial()) { /* first question about this pass */
         const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
         rc = contact_prerequisites(h);
         if (rc) return rc;
@@ -3198,7 +3252,7 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
         st.hist[0] = N - st.covered;
         for (int b = 1; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
         C.stats = st;
-        C.serial = h->gen_serial;
+        C.serial = h->pass.serial();
     }
     if (stats) *stats = C.stats;
     const size_t k = std::min(cap, N);
@@ -3221,7 +3275,7 @@ int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz)
     LAUNCH(h, "k_eval_api", k_eval_api, (unsigned)((k + 127) / 128), 128, 0, h->meta.p, h->node_x.p, h->node_y.p, h->node_z.p,
            h->node_start.p, h->node_cnt.p, s, dq, (int)k, dout);
     HIPCHK(h, hipMemcpyAsync(xyz, dout, k * 24, hipMemcpyDeviceToHost, h->stream));
-    h->meta_in_flight = false; h->meta_fresh = false;
+    h->pass.meta_will_arrive(MetaAt::on_demand());
     rc = fetch_meta(h);
     if (rc) return rc;
     if (h->hmeta.api_flag == DERR_DOMAIN) return fail(h, PPP_ERR_DOMAIN, "y outside [miny, bigy] (GSL_EDOM)");
@@ -3244,7 +3298,7 @@ int ppp_insert_point(ppp_handle h, const int *indices, size_t n, float plane_x, 
     if (n) HIPCHK(h, hipMemcpyAsync(didx, indices, n * 4, hipMemcpyHostToDevice, h->stream));
     LAUNCH(h, "k_insert_api", k_insert_api, 1, 256, slice_lds_bytes(capb), h->X.p, h->Y.p, h->Z.p, (int)h->n, didx, (int)n, plane_x,
            h->P.pairing, capb, h->meta.p, dy, dz, capb);
-    h->meta_in_flight = false; h->meta_fresh = false;
+    h->pass.meta_will_arrive(MetaAt::on_demand());
     int rc = fetch_meta(h);
     if (rc) return rc;
     if (h->hmeta.api_flag == DERR_SLICE) return fail(h, PPP_ERR_SLICE, "insert_point: empty right side (the reference crashes here)");
@@ -3571,10 +3625,10 @@ int ppp_nearest(ppp_handle h, const float *q_xyz, size_t k, int *idx)
 /* a window pass leaves the per-waypoint stage lists in per-slice slots: into list order when somebody asks */
 static int ensure_stage_lists(ppp_handle h)
 {
-    if (h->stage_compact || !h->win_path) return PPP_OK;
+    if (h->pass.stage_compact() || !h->win_path) return PPP_OK;
     const WinArgs A = win_args(h);
     if (A.nkept > 0) LAUNCH(h, "k_win_gather_stage", k_win_gather_stage, A.nkept, 256, 0, A, h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p);
-    h->stage_compact = true;
+    h->pass.stages_gathered();
     return PPP_OK;
 }
 
@@ -3760,7 +3814,7 @@ int ppp_get_fast_path(ppp_handle h, int *active)
 {
     if (!h || !active) return PPP_ERR_ARG;
     if (h->have_cloud) { HIPCHK(h, hipSetDevice(h->device)); int rcs = settle(h); if (rcs) return rcs; }
-    if (h->have_cloud && !h->planned) { int rc = make_plan(h); if (rc) return rc; }
+    if (h->have_cloud && !h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
     *active = (h->have_cloud && h->win_path) ? 1 : 0;
     return PPP_OK;
 }

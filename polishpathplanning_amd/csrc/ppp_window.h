@@ -1434,12 +1434,3 @@ __global__ void __launch_bounds__(SMF_T) k_win_finish_b(const WinArgs *__restric
     win_finish_body(A, blockIdx.x);
     win_publish_meta(A);
 }
-/* the members' meta blocks side by side, so that ONE copy publishes the batch to the host */
-__global__ void __launch_bounds__(64) k_collect_meta_win(const WinArgs *__restrict__ mem, int count, DevMeta *out)
-{
-    const int i = blockIdx.x;
-    if (i >= count) return;
-    const int *src = (const int *)mem[i].m;
-    int *dst = (int *)(out + i);
-    for (int q = threadIdx.x; q < (int)(sizeof(DevMeta) / sizeof(int)); q += blockDim.x) dst[q] = src[q];
-}

@@ -88,7 +88,6 @@ template <int TMAX> __global__ void k_win_slice(WinArgs A);
 template <int TMAX> __global__ void k_win_slice_b(const WinArgs *__restrict__ mem);
 __global__ void k_win_finish(WinArgs A);
 __global__ void k_win_finish_b(const WinArgs *__restrict__ mem);
-__global__ void k_collect_meta_win(const WinArgs *__restrict__ mem, int count, DevMeta *out);
 __global__ void k_win_gather_stage(WinArgs A, float4 *wp_xyz, int *wp_nn, float4 *wp_normal);
 template <bool IN_LDS>
 __global__ void k_win_census(const float *__restrict__ X, int n, const float *__restrict__ px, int S, float px0, float inv_step, float pad,
