@@ -300,7 +300,7 @@ struct ppp_handle_s {
     DevBuf<int> big_slabs, big_slices; /* work lists of the LDS-overflow fallback kernels */
     DevBuf<char> arena;                /* their global scratch, allocated on first need */
     bool big_path = false;             /* launch the fallback kernels (set by the plan or after an overflow) */
-    int mm_grid = 1, mm_grid_used = 1, sm_tiles = 1;
+    int mm_grid = 1, sm_tiles = 1;
     DevBuf<char> scratch; /* API staging */
     /* window path (ppp_window.h): three launches, every point binned once into the window of its slice */
     bool win_allowed = true;    /* ppp_set_fast_path */
@@ -399,6 +399,44 @@ struct ppp_handle_s {
     }
 };
 
+/* Launch geometry of a slab pass: what the stage launches need beside the record (SlabArgs).  slab_geom decides it for ONE
+   handle; a batch joins its members' and launches every stage once with the result.  The defaults are the floors a batch
+   starts from. */
+struct SlabGeom {
+    float slab_x0 = 0.f, slab_invw = 0.f; /* the slab grid */
+    int g_minmax = 1, g_scatter = 1, g_scatter2 = 1, g_sort = 1, g_slice = 1, g_pose = 1, g_smooth = 1; /* workgroups per stage (g_scatter2: the second level of the two-level scatter, 4 points per thread) */
+    int first_slab = 0;         /* a slice-range handle sorts the g_sort slabs of its interval only */
+    int ppt = 4;                /* points per scatter thread: 4, 8 or 16 */
+    int B = 1, slab_cap = 2048, capb = 1024; /* slabs, points of a slab and of a band in LDS */
+    bool full_slabs = false;    /* slabs beyond the planned 832 points: the sort's wide form */
+    bool two_fit = true;        /* two slice workgroups' bands fit a CU's LDS */
+    long long slices = 0;       /* slice workgroups of the launch */
+    int pose_threads = 256;
+    size_t pose_lds = 0;
+    size_t hist_lds() const { return sizeof(int) * (size_t)B; }
+    /* threads per slab: 256 while a slab holds the planned 832 points on average (more slabs in flight per CU: cfg 2 sorts in
+       15.3 us against 17.0), SORT_T for the fuller slabs of clouds beyond the 8192-slab cap (cfg 5: 125 us against 157) */
+    int sort_threads() const { return full_slabs ? SORT_T : 256; }
+    size_t sort_lds() const { return (size_t)slab_cap * 12 + 16; }
+    /* Threads of a k_slice_kd workgroup.  One workgroup per slice with the band in LDS: 1024 threads finish a slice soonest
+       (one round of nearest-neighbour queries for bands of up to 2048 points), and that is what counts while the slices of a
+       launch fit the GPU in one go.  With several times more slices than CUs (batches of workpieces) two 512-thread
+       workgroups per CU get more slices through -- if two bands fit the CU's LDS. */
+    int slice_threads(int num_cus) const { return (two_fit && slices >= 2LL * num_cus) ? 512 : SLICE_KD_T; }
+    size_t slice_lds() const { return slice_kd_bytes(capb); }
+    size_t brute_lds() const { return slice_lds_bytes(capb); } /* k_slice, the brute pairing's generic form */
+    /* a batch: every stage is launched for its widest member (a narrower member's surplus workgroups leave at once) */
+    void join(const SlabGeom &o)
+    {
+        g_minmax = std::max(g_minmax, o.g_minmax); g_scatter = std::max(g_scatter, o.g_scatter); g_sort = std::max(g_sort, o.g_sort);
+        g_slice = std::max(g_slice, o.g_slice); g_pose = std::max(g_pose, o.g_pose); g_smooth = std::max(g_smooth, o.g_smooth);
+        ppt = std::max(ppt, o.ppt); B = std::max(B, o.B); slab_cap = std::max(slab_cap, o.slab_cap); capb = std::max(capb, o.capb);
+        full_slabs = full_slabs || o.full_slabs; two_fit = two_fit && o.two_fit;
+        slices += o.slices; /* (summed: the two-workgroup rule looks at the launch, and the launch is the batch's) */
+        pose_threads = std::max(pose_threads, o.pose_threads); pose_lds = std::max(pose_lds, o.pose_lds);
+    }
+};
+
 struct BatchGraph {
     std::vector<ppp_handle> hs;
     std::vector<unsigned> epochs;
@@ -410,15 +448,11 @@ struct BatchGraph {
     std::vector<hipEvent_t> join;
     /* batched form (one launch per stage over all members): the members' records and meta blocks */
     bool batched = false, eager = false; /* eager: launched directly every time (kernel timing), no graph */
-    int maxB = 1, max_slab_cap = 2048, max_capb = 1024; /* launch geometry over all members */
-    int pose_threads = 256, slice_thr = SLICE_KD_T;
-    size_t pose_lds = 0;
-    int gx_mm = 1, gx_scat = 1, gx_sort = 1, gx_slice = 1, gx_pose = 1, gx_smooth = 1;
-    bool full_slabs = false, ppt8 = false;
-    DevBuf<BatchMember> members;
+    SlabGeom geom; /* launch geometry over all members (slab path) */
+    DevBuf<SlabArgs> members;
     bool win = false;              /* every member runs the window path: the three k_win_*_b launches */
     DevBuf<WinArgs> wmembers;
-    int win_ppt = 4, win_threads = 256, gx_wfin = 1;
+    int win_ppt = 4, win_threads = 256, gx_scat = 1, gx_slice = 1, gx_wfin = 1;
     bool win_staged = false;
     size_t win_lds = 0, win_scat_lds = 0, win_fin_lds = 0;
     DevBuf<DevMeta> metas;
@@ -520,6 +554,13 @@ int with_block_size(int T, F &&f)
     return f(std::integral_constant<int, 1024>());
 }
 static_assert(POSE_T == 1024, "k_pose's widest instantiation is the ladder's top rung");
+/* the scatter kernels are instantiated per points per thread: f(std::integral_constant<int, 16 | 8 | 4>) */
+template <bool WITH16 = true, class F>
+int with_ppt(int ppt, F &&f)
+{
+    if constexpr (WITH16) if (ppt == 16) return f(std::integral_constant<int, 16>());
+    return ppt >= 8 ? f(std::integral_constant<int, 8>()) : f(std::integral_constant<int, 4>());
+}
 
 int validate_params(ppp_handle h, const ppp_params *p)
 {
@@ -1067,88 +1108,100 @@ int make_plan(ppp_handle h)
     return PPP_OK;
 }
 
-/* Threads of a k_slice_kd workgroup.  One workgroup per slice with the band in LDS: 1024 threads finish a slice soonest
-   (one round of nearest-neighbour queries for bands of up to 2048 points), and that is what counts while the slices of a
-   launch fit the GPU in one go.  With several times more slices than CUs (batches of workpieces) two 512-thread
-   workgroups per CU get more slices through -- if two bands fit the CU's LDS. */
-int slice_threads(const ppp_handle h, long long slices_in_launch)
+int scatter_grid(int n, int ppt) { return std::max(1, (n + ppt * SCAT_T - 1) / (ppt * SCAT_T)); }
+
+/* the launch geometry of this handle's slab pass: every stage's grid, block size and LDS, decided here and nowhere else */
+SlabGeom slab_geom(const ppp_handle h)
 {
-    const bool two_fit = 2 * (slice_kd_bytes(h->capb) + 1024) <= (size_t)h->max_lds;
-    return (two_fit && slices_in_launch >= 2LL * h->num_cus) ? 512 : SLICE_KD_T;
+    SlabGeom G;
+    const int n = h->use_part ? h->n_part : (int)h->n;
+    /* slab grid from the bounds cached when the cloud was set (identical to what k_minmax finds) */
+    const float xr = h->h_mx[0] - h->h_mn[0];
+    G.slab_x0 = h->h_mn[0];
+    G.slab_invw = (h->h_nvalid && xr > 0.f) ? (float)h->B / xr : 0.f;
+    /* a2 and the slab histogram in ONE pass over the cloud: at most PPP_MM_GRID_MAX workgroups: each flushes its LDS histogram
+       with one global atomic per non-empty slab, and that flush, not the streaming, is what grows with the grid */
+    G.g_minmax = std::max(1, std::min(h->mm_grid, PPP_MM_GRID_MAX));
+    /* points per scatter workgroup: every workgroup reserves its share of each slab with one global atomic per
+       non-empty (workgroup, slab) pair, so larger clouds use 8 or 16 instead of 4 points per thread */
+    G.ppt = (n > PPP_PPT16_FROM && !h->two_pass_scatter) ? 16 : (n > PPP_PPT8_FROM ? 8 : 4);
+    G.g_scatter = scatter_grid(n, G.ppt); G.g_scatter2 = scatter_grid(n, 4);
+    G.B = h->B; G.slab_cap = h->slab_cap;
+    G.full_slabs = h->B > 0 && h->h_nvalid / h->B > 1000;
+    /* a slice-range handle sorts the slabs of its interval only (the others are empty and are never looked at) */
+    G.first_slab = 0; G.g_sort = h->B;
+    if (h->use_part && G.slab_invw > 0.f) {
+        auto slab_of_host = [&](float x) { int b = (int)((x - G.slab_x0) * G.slab_invw); b = b < 0 ? 0 : b; return b >= h->B ? h->B - 1 : b; };
+        G.first_slab = slab_of_host(h->incl_lo);
+        G.g_sort = slab_of_host(h->incl_hi) - G.first_slab + 1;
+    }
+    G.capb = h->capb;
+    G.two_fit = 2 * (slice_kd_bytes(h->capb) + 1024) <= (size_t)h->max_lds;
+    G.slices = h->S_cap; G.g_slice = h->S_cap; G.g_pose = std::max(1, h->S_cap); G.g_smooth = h->sm_tiles;
+    G.pose_threads = h->pose_threads; G.pose_lds = pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs);
+    return G;
+}
+
+/* the slab pass's launch record of this handle, from its state at enqueue time (the window path's: win_args) */
+SlabArgs slab_args(const ppp_handle h, const SlabGeom &G)
+{
+    SlabArgs A;
+    memset(&A, 0, sizeof(A));
+    A.m = h->meta.p; A.P = dev_params(h);
+    /* a slice-range handle streams its own part of the cloud (make_plan), everything else the whole cloud */
+    A.X = h->use_part ? h->Xp.p : h->X.p; A.Y = h->use_part ? h->Yp.p : h->Y.p; A.Z = h->use_part ? h->Zp.p : h->Z.p;
+    A.idmap = h->use_part ? h->part_idx.p : ((h->part_given && h->part_has_idx) ? h->part_idx.p : nullptr);
+    A.n = h->use_part ? h->n_part : (int)h->n; A.ncloud = (int)h->n;
+    A.mm_part = h->mm_part.p;
+    A.slab_x0 = G.slab_x0; A.slab_invw = G.slab_invw;
+    A.B = h->B; A.S_cap = h->S_cap; A.slab_cap = h->slab_cap; A.capb = h->capb; A.node_cap = h->node_cap; A.W_cap = h->W_cap;
+    A.knot_cap = h->knot_cap; A.stage_cap = h->stage_cap; A.tab_slabs = h->tab_slabs; A.pose_pad = h->pose_pad;
+    A.first_slab = G.first_slab; A.arena_ran = h->big_path ? 1 : 0;
+    A.g_minmax = G.g_minmax; A.g_scatter = G.g_scatter; A.g_sort = G.g_sort; A.g_slice = G.g_slice; A.g_pose = G.g_pose; A.g_smooth = G.g_smooth;
+    A.slab_cnt = h->slab_cnt.p; A.slab_start = h->slab_start.p; A.slab_cursor = h->slab_cursor.p; A.coarse_cursor = h->coarse_cursor.p;
+    A.px = h->px.p; A.lo = h->lo.p; A.hi = h->hi.p;
+    A.unsorted4 = h->unsorted4.p; A.sorted4 = h->sorted4.p; A.slab_xmin = h->slab_xmin.p; A.slab_xmax = h->slab_xmax.p;
+    A.big_slabs = h->big_slabs.p; A.big_slices = h->big_slices.p; A.arena = h->arena.p; A.arena_cap = (unsigned long long)h->arena.cap;
+    A.node_x = h->node_x.p; A.node_y = h->node_y.p; A.node_z = h->node_z.p;
+    A.node_start = h->node_start.p; A.node_cnt = h->node_cnt.p; A.band_cnt = h->band_cnt.p;
+    A.wp_cnt = h->wp_cnt.p; A.wp_off = h->wp_off.p; A.tail = h->tail.p;
+    A.wp_xyz = h->wp_xyz.p; A.wp_normal = h->wp_normal.p; A.wp_nn = h->wp_nn.p;
+    A.wp_pre = h->wp_pre.p; A.wp_smooth = h->wp_smooth.p; A.wp_out = h->wp_out.p; A.out2 = h->out2; A.out2_cap = h->out2_cap;
+    A.ytab = h->slab_ytab.p;
+    /* the pairing kernel leaves every slice's waypoint count for k_pose -- unless the dynamic adjustment re-fits the knots after it */
+    A.slice_wpcnt = (h->P.pairing == PPP_PAIR_KD && !h->P.dynamic_adjustment) ? h->slice_wpcnt.p : nullptr;
+    return A;
 }
 
 /* a2 + a3 + the x-slab index (generalised slice binning) */
-int enqueue_index(ppp_handle h)
+int enqueue_index(ppp_handle h, const SlabGeom &G, SlabArgs A)
 {
-    /* a slice-range handle streams its own part of the cloud (make_plan), everything else the whole cloud */
-    const int n = h->use_part ? h->n_part : (int)h->n;
-    const float *sX = h->use_part ? h->Xp.p : h->X.p, *sY = h->use_part ? h->Yp.p : h->Y.p, *sZ = h->use_part ? h->Zp.p : h->Z.p;
-    const int *idmap = h->use_part ? h->part_idx.p : ((h->part_given && h->part_has_idx) ? h->part_idx.p : nullptr);
-    DevParams D = dev_params(h);
     h->slab_cnt_used = true;
-    D.keep_run_state = (h->win_path && h->pass.gen_done()) ? 1 : 0; /* an API mirror asks for the slab index behind a finished window pass */
-    size_t hist_lds = sizeof(int) * (size_t)h->B;
-    /* slab grid from the bounds cached when the cloud was set (identical to what k_minmax finds) */
-    const float slab_x0 = h->h_mn[0];
-    const float xr = h->h_mx[0] - h->h_mn[0];
-    const float slab_invw = (h->h_nvalid && xr > 0.f) ? (float)h->B / xr : 0.f;
-    {   /* a2 and the slab histogram in ONE pass over the cloud (the slab grid comes from the bounds cached with the
-           cloud).  At most PPP_MM_GRID_MAX workgroups: each flushes its LDS histogram with one global atomic per non-empty slab, and
-           that flush, not the streaming, is what grows with the grid. */
-        const int gf = std::max(1, std::min(h->mm_grid, PPP_MM_GRID_MAX));
-        LAUNCH(h, "k_minmax", k_minmax<true>, gf, MM_T, hist_lds, sX, sY, sZ, n, h->mm_part.p, slab_x0, slab_invw, h->B, h->slab_cnt.p,
-               h->incl_lo, h->incl_hi, h->slab_cursor.p);
-        h->mm_grid_used = gf;
-    }
-    /* points per scatter workgroup: every workgroup reserves its share of each slab with one global atomic per
-       non-empty (workgroup, slab) pair, so larger clouds use 8 instead of 4 points per thread */
-    const bool ppt8 = n > PPP_PPT8_FROM;
-    const bool ppt16 = n > PPP_PPT16_FROM && !h->two_pass_scatter;
-    const int chunk = (ppt16 ? 16 : (ppt8 ? 8 : 4)) * SCAT_T;
-    const int gs = std::max(1, (n + chunk - 1) / chunk);
-    if (h->two_pass_scatter)
-        LAUNCH(h, "k_setup", k_setup, 1, SETUP_T, 0, h->meta.p, D, h->mm_part.p, h->mm_grid_used, h->px.p, h->lo.p, h->hi.p, h->S_cap, h->B,
-               h->slab_cnt.p, slab_x0, slab_invw, h->slab_start.p, h->slab_cursor.p, h->coarse_cursor.p);
+    A.P.keep_run_state = (h->win_path && h->pass.gen_done()) ? 1 : 0; /* an API mirror asks for the slab index behind a finished window pass */
+    LAUNCH(h, "k_minmax", k_minmax<true>, A.g_minmax, MM_T, G.hist_lds(), A);
     if (!h->two_pass_scatter) {
         /* one level: the set-up rides in the scatter's launch as its last workgroup (k_scatter_setup) */
-        ScatGrid G;
-        G.x0 = slab_x0; G.invw = slab_invw; G.xlo = h->incl_lo; G.xhi = h->incl_hi; G.B = h->B;
-        if (ppt16)
-            LAUNCH(h, "k_scatter_setup", k_scatter_setup<16>, gs + 1, SCAT_T, 2 * hist_lds, sX, sY, sZ, n, G, h->slab_cnt.p, h->slab_cursor.p,
-                   h->unsorted4.p, idmap, gs, h->meta.p, D, h->mm_part.p, h->mm_grid_used, h->px.p, h->lo.p, h->hi.p, h->S_cap, h->slab_start.p);
-        else if (ppt8)
-            LAUNCH(h, "k_scatter_setup", k_scatter_setup<8>, gs + 1, SCAT_T, 2 * hist_lds, sX, sY, sZ, n, G, h->slab_cnt.p, h->slab_cursor.p,
-                   h->unsorted4.p, idmap, gs, h->meta.p, D, h->mm_part.p, h->mm_grid_used, h->px.p, h->lo.p, h->hi.p, h->S_cap, h->slab_start.p);
-        else
-            LAUNCH(h, "k_scatter_setup", k_scatter_setup<4>, gs + 1, SCAT_T, 2 * hist_lds, sX, sY, sZ, n, G, h->slab_cnt.p, h->slab_cursor.p,
-                   h->unsorted4.p, idmap, gs, h->meta.p, D, h->mm_part.p, h->mm_grid_used, h->px.p, h->lo.p, h->hi.p, h->S_cap, h->slab_start.p);
+        const int rcs = with_ppt(G.ppt, [&](auto ppt) -> int {
+            LAUNCH(h, "k_scatter_setup", k_scatter_setup<decltype(ppt)::value>, A.g_scatter + 1, SCAT_T, 2 * G.hist_lds(), A);
+            return PPP_OK;
+        });
+        if (rcs) return rcs;
     } else {
         /* coarse bins into sorted4 (free until k_slab_sort writes it), then from there into the slabs */
-        LAUNCH(h, "k_slab_scatter", (k_slab_scatter<1, 8>), gs, SCAT_T, hist_lds, sX, sY, sZ, (const float4 *)nullptr, n, h->meta.p,
-               h->coarse_cursor.p, h->sorted4.p, idmap);
-        const int gs2 = std::max(1, (n + 4 * SCAT_T - 1) / (4 * SCAT_T));
-        LAUNCH(h, "k_slab_scatter2", (k_slab_scatter<2, 4>), gs2, SCAT_T, hist_lds, sX, sY, sZ, (const float4 *)h->sorted4.p, n,
-               h->meta.p, h->slab_cursor.p, h->unsorted4.p, (const int *)nullptr);
+        LAUNCH(h, "k_setup", k_setup, 1, SETUP_T, 0, A);
+        LAUNCH(h, "k_slab_scatter", (k_slab_scatter<1, 8>), A.g_scatter, SCAT_T, G.hist_lds(), A);
+        LAUNCH(h, "k_slab_scatter2", (k_slab_scatter<2, 4>), G.g_scatter2, SCAT_T, G.hist_lds(), A);
     }
-    size_t sort_lds = (size_t)h->slab_cap * 12 + 16;
-    /* threads per slab: 256 while a slab holds the planned 832 points on average (more slabs in flight per CU: cfg 2 sorts in
-       15.3 us against 17.0), SORT_T for the fuller slabs of clouds beyond the 8192-slab cap (cfg 5: 125 us against 157) */
-    const int sort_threads = (h->B > 0 && h->h_nvalid / h->B > 1000) ? SORT_T : 256;
-    /* a slice-range handle sorts the slabs of its interval only (the others are empty and are never looked at) */
-    int first_slab = 0, nslabs = h->B;
-    if (h->use_part && slab_invw > 0.f) {
-        auto slab_of_host = [&](float x) { int b = (int)((x - slab_x0) * slab_invw); b = b < 0 ? 0 : b; return b >= h->B ? h->B - 1 : b; };
-        first_slab = slab_of_host(h->incl_lo);
-        nslabs = slab_of_host(h->incl_hi) - first_slab + 1;
-    }
-    LAUNCH(h, "k_slab_sort", k_slab_sort<false>, nslabs, sort_threads, sort_lds, h->unsorted4.p, h->slab_start.p, h->sorted4.p,
-           h->slab_xmin.p, h->slab_xmax.p, h->meta.p, h->slab_cap, h->big_slabs.p, h->arena.p, (unsigned long long)h->arena.cap, h->slab_ytab.p,
-           first_slab, h->slab_cnt.p);
-    if (h->big_path)
-        LAUNCH(h, "k_slab_sort_arena", k_slab_sort<true>, h->B, SORT_T, 0, h->unsorted4.p, h->slab_start.p, h->sorted4.p,
-               h->slab_xmin.p, h->slab_xmax.p, h->meta.p, h->slab_cap, h->big_slabs.p, h->arena.p, (unsigned long long)h->arena.cap, h->slab_ytab.p, 0, (int *)nullptr);
+    LAUNCH(h, "k_slab_sort", k_slab_sort<false>, A.g_sort, G.sort_threads(), G.sort_lds(), A);
+    if (h->big_path) LAUNCH(h, "k_slab_sort_arena", k_slab_sort<true>, h->B, SORT_T, 0, A);
     h->pass.index_enqueued();
     return PPP_OK;
+}
+
+int enqueue_index(ppp_handle h)
+{
+    const SlabGeom G = slab_geom(h);
+    return enqueue_index(h, G, slab_args(h, G));
 }
 
 /* centre slice of the centre-out walk = number of slices left of it (path_dynamic_alg.cpp:310-313) */
@@ -1455,8 +1508,10 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
             { int rca = adopt_ingest_record(h, census, reuse); if (rca) return rca; }
         } else {
             h->rec_current = false; /* (the cloud was altered on the device: the conversion pass's record is another cloud's) */
-            hipLaunchKernelGGL(k_minmax<false>, dim3(g), dim3(MM_T), 0, h->stream, h->X.p, h->Y.p, h->Z.p, (int)n, h->mm_part.p, 0.f, 0.f, 0,
-                               (int *)nullptr, 0.f, 0.f, (int *)nullptr);
+            SlabArgs A; /* (bounds only: no slab grid, no histogram) */
+            memset(&A, 0, sizeof(A));
+            A.X = h->X.p; A.Y = h->Y.p; A.Z = h->Z.p; A.n = (int)n; A.mm_part = h->mm_part.p; A.g_minmax = g;
+            hipLaunchKernelGGL(k_minmax<false>, dim3(g), dim3(MM_T), 0, h->stream, A);
             HIPCHK(h, hipGetLastError());
             /* (through pinned memory: a copy into pageable memory is staged by the runtime, ~10 us more on this critical path) */
             HIPCHK(h, h->pin.ensure(std::max(sizeof(MinMaxPart) * (size_t)g, PIN_MIN)));
@@ -1596,8 +1651,6 @@ int ppp_create(int device_id, ppp_handle *out)
     (void)hipFuncSetAttribute((const void *)k_slice, hipFuncAttributeMaxDynamicSharedMemorySize, h->max_lds - 1024);
     (void)hipFuncSetAttribute((const void *)k_slice_kd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, h->max_lds - 1024);
     (void)hipFuncSetAttribute((const void *)k_minmax<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
-    (void)hipFuncSetAttribute((const void *)k_slab_scatter<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
-    (void)hipFuncSetAttribute((const void *)k_slab_scatter<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
     (void)hipFuncSetAttribute((const void *)k_slab_scatter<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
     (void)hipFuncSetAttribute((const void *)k_slab_scatter<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
     (void)hipFuncSetAttribute((const void *)k_minmax_b, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 4);
@@ -2187,26 +2240,16 @@ int ppp_gen_path_async(ppp_handle h)
         return enqueue_meta_copy(h);
     }
     if (!slice_lds_ok(h, h->capb)) return fail(h, PPP_ERR_CAPACITY, "band capacity exceeds the LDS of this device");
-    int rc = enqueue_index(h);
+    const SlabGeom G = slab_geom(h);
+    const SlabArgs A = slab_args(h, G);
+    int rc = enqueue_index(h, G, A);
     if (rc) return rc;
-    /* the pairing kernel leaves every slice's waypoint count for k_pose -- unless the dynamic adjustment re-fits the knots after it */
-    int *cnt_out = (h->P.pairing == PPP_PAIR_KD && !h->P.dynamic_adjustment) ? h->slice_wpcnt.p : nullptr;
     if (h->P.pairing == PPP_PAIR_KD) {
-        LAUNCH(h, "k_slice_kd", k_slice_kd<false>, h->S_cap, slice_threads(h, h->S_cap), slice_kd_bytes(h->capb), h->sorted4.p, h->slab_start.p, h->meta.p,
-               h->px.p, h->lo.p, h->hi.p, h->capb, h->node_x.p, h->node_y.p, h->node_z.p, h->node_cap, h->node_start.p, h->node_cnt.p,
-               h->band_cnt.p, h->big_slices.p, h->arena.p, (unsigned long long)h->arena.cap, h->P.trim, h->P.path_resolution, h->W_cap, cnt_out);
-        if (h->big_path)
-            LAUNCH(h, "k_slice_kd_arena", k_slice_kd<true>, h->S_cap, SLICE_KD_T, 0, h->sorted4.p, h->slab_start.p, h->meta.p, h->px.p,
-                   h->lo.p, h->hi.p, h->capb, h->node_x.p, h->node_y.p, h->node_z.p, h->node_cap, h->node_start.p, h->node_cnt.p,
-                   h->band_cnt.p, h->big_slices.p, h->arena.p, (unsigned long long)h->arena.cap, h->P.trim, h->P.path_resolution, h->W_cap, cnt_out);
+        LAUNCH(h, "k_slice_kd", k_slice_kd<false>, A.g_slice, G.slice_threads(h->num_cus), G.slice_lds(), A);
+        if (h->big_path) LAUNCH(h, "k_slice_kd_arena", k_slice_kd<true>, A.g_slice, SLICE_KD_T, 0, A);
     } else {
-        LAUNCH(h, "k_slice", k_slice, h->S_cap, K_SLICE_T, slice_lds_bytes(h->capb), h->sorted4.p, h->slab_start.p, h->meta.p, h->px.p,
-               h->lo.p, h->hi.p, h->P.pairing, h->capb, h->node_x.p, h->node_y.p, h->node_z.p, h->node_cap, h->node_start.p,
-               h->node_cnt.p, h->band_cnt.p, h->big_slices.p);
-        if (h->big_path)
-            LAUNCH(h, "k_slice_brute_arena", k_slice_brute_arena, h->S_cap, 1024, 0, h->sorted4.p, h->slab_start.p, h->meta.p, h->px.p,
-                   h->lo.p, h->hi.p, h->P.pairing, (int)h->n, h->node_x.p, h->node_y.p, h->node_z.p, h->node_cap, h->node_start.p,
-                   h->node_cnt.p, h->band_cnt.p, h->big_slices.p, h->arena.p, (unsigned long long)h->arena.cap);
+        LAUNCH(h, "k_slice", k_slice, A.g_slice, K_SLICE_T, G.brute_lds(), A);
+        if (h->big_path) LAUNCH(h, "k_slice_brute_arena", k_slice_brute_arena, A.g_slice, 1024, 0, A);
     }
     if (h->P.dynamic_adjustment) {
         int rc2 = enqueue_dynamic(h);
@@ -2218,12 +2261,11 @@ int ppp_gen_path_async(ppp_handle h)
 }
 
 /* getPath's second half: postion_smooth, reduceRPY, TransFlangeposition (path_translation_alg.cpp:212-214) */
-int enqueue_finish(ppp_handle h, const DevParams &D)
+int enqueue_finish(ppp_handle h, const SlabArgs &A)
 {
     /* postion_smooth solved directly (one 65-tap filter per waypoint), then reduceRPY, the flange offset and the copy into
        the caller's buffer of the batched form: ONE launch */
-    LAUNCH(h, "k_smooth_solve", k_smooth_solve, h->sm_tiles, SMF_T, 0, h->meta.p, D, h->W_cap, h->wp_pre.p, h->wp_smooth.p, h->wp_out.p,
-           h->tail.p, h->out2, h->out2_cap);
+    LAUNCH(h, "k_smooth_solve", k_smooth_solve, A.g_smooth, SMF_T, 0, A);
     return enqueue_meta_copy(h);
 }
 
@@ -2240,28 +2282,20 @@ int ppp_get_path_async(ppp_handle h)
         h->pass.meta_will_arrive(MetaAt::pinned()); /* the finish launch's last workgroup leaves the meta block in hmeta_pinned */
         return PPP_OK;
     }
-    DevParams D = dev_params(h);
-    int nk = std::max(1, h->S_cap);
+    const SlabGeom G = slab_geom(h);
+    const SlabArgs A = slab_args(h, G);
     PoseBack PB;
     memset(&PB, 0, sizeof(PB));
-    const int *cnt_in = (h->P.pairing == PPP_PAIR_KD && !h->P.dynamic_adjustment) ? h->slice_wpcnt.p : nullptr;
     if (h->aligned) {
         if (h->ranged) return fail(h, PPP_ERR_UNSUPPORTED, "Alignment with a slice range");
         if (!h->back || !h->back->pass.index_built()) return fail(h, PPP_ERR_ARG, "aligned cloud without its sensor-frame index");
         PB.sorted4 = h->back->sorted4.p; PB.slab_start = h->back->slab_start.p; PB.slab_xmin = h->back->slab_xmin.p; PB.slab_xmax = h->back->slab_xmax.p;
         PB.m = h->back->meta.p; PB.ytab = h->back->slab_ytab.p;
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) PB.inv[r][c] = h->invTA[r][c];
-        LAUNCH(h, "k_pose<aligned>", (k_pose<true, POSE_T>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), h->meta.p, D, h->sorted4.p, h->slab_start.p, h->slab_xmin.p,
-               h->slab_xmax.p, h->px.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->wp_cnt.p, h->wp_off.p,
-               h->tail.p, h->W_cap, h->big_path ? 1 : 0, h->knot_cap, h->stage_cap, h->tab_slabs, h->pose_pad,
-               h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p, h->wp_pre.p, PB, h->slab_ytab.p, cnt_in);
-    } else
-    {
-        int rcp = with_block_size(h->pose_threads, [&](auto bs) -> int {
-            LAUNCH(h, "k_pose", (k_pose<false, decltype(bs)::value>), nk, h->pose_threads, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs), h->meta.p, D, h->sorted4.p, h->slab_start.p, h->slab_xmin.p,
-                   h->slab_xmax.p, h->px.p, h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->wp_cnt.p, h->wp_off.p,
-                   h->tail.p, h->W_cap, h->big_path ? 1 : 0, h->knot_cap, h->stage_cap, h->tab_slabs, h->pose_pad,
-                   h->wp_xyz.p, h->wp_nn.p, h->wp_normal.p, h->wp_pre.p, PB, h->slab_ytab.p, cnt_in);
+        LAUNCH(h, "k_pose<aligned>", (k_pose<true, POSE_T>), A.g_pose, G.pose_threads, G.pose_lds, A, PB);
+    } else {
+        const int rcp = with_block_size(G.pose_threads, [&](auto bs) -> int {
+            LAUNCH(h, "k_pose", (k_pose<false, decltype(bs)::value>), A.g_pose, G.pose_threads, G.pose_lds, A, PB);
             return PPP_OK;
         });
         if (rcp) return rcp;
@@ -2269,7 +2303,7 @@ int ppp_get_path_async(ppp_handle h)
     h->pass.path_enqueued(false, false); /* the per-waypoint half: the stage lists, no finished list yet */
     /* a slice-range handle stops here: postion_smooth couples the slices of different handles */
     if (!h->ranged) {
-        int rc = enqueue_finish(h, D); /* publishes the meta block itself */
+        int rc = enqueue_finish(h, A); /* publishes the meta block itself */
         if (rc) return rc;
         h->pass.path_enqueued(true, false);
         return PPP_OK;
@@ -2291,7 +2325,7 @@ int ppp_finish_path_async(ppp_handle h, const float *pre6_dev, size_t W, const i
     if (nkept) HIPCHK(h, hipMemcpyAsync(h->wp_cnt.p, counts, nkept * sizeof(int), hipMemcpyHostToDevice, h->stream));
     LAUNCH(h, "k_count_given", k_count_given, 1, 1024, 0, h->meta.p, D, (int)nkept, (int)W, h->wp_cnt.p, h->wp_off.p, h->tail.p, h->W_cap);
     if (W) LAUNCH(h, "k_load_pre", k_load_pre, (unsigned)((W + 255) / 256), 256, 0, h->meta.p, pre6_dev, h->wp_pre.p);
-    int rc = enqueue_finish(h, D);
+    int rc = enqueue_finish(h, slab_args(h, slab_geom(h)));
     if (rc) return rc;
     h->pass.gen_enqueued(false);
     h->pass.path_enqueued(true, false); /* (in list order: no per-waypoint stage lists belong to a list finished from gathered blocks) */
@@ -2353,65 +2387,30 @@ bool batch_eligible(const ppp_handle h)
         if (_le != hipSuccess) return fail((lead), PPP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(_le)); \
     } while (0)
 
-/* the members' records (host -> device, synchronous, outside any capture) and the launch geometry of the batch */
+/* the members' records (host -> device, synchronous, outside any capture) and the launch geometry of the batch: every member's
+   own record and geometry, then what depends on the company it is planned in */
 int upload_members(ppp_handle lead, BatchGraph *bg, float *dst_dev, const size_t *offset_rows, const size_t *cap_rows)
 {
     const size_t count = bg->hs.size();
-    std::vector<BatchMember> mem(count);
-    int &maxB = bg->maxB, &max_slab_cap = bg->max_slab_cap, &max_capb = bg->max_capb;
-    int &gx_mm = bg->gx_mm, &gx_scat = bg->gx_scat, &gx_sort = bg->gx_sort, &gx_slice = bg->gx_slice, &gx_pose = bg->gx_pose, &gx_smooth = bg->gx_smooth;
-    bool &full_slabs = bg->full_slabs, &ppt8 = bg->ppt8;
-    int max_n = 0;
-    long long slices_total = 0;
-    bg->pose_threads = 256; bg->pose_lds = 0;
-    for (size_t i = 0; i < count; ++i) max_n = std::max(max_n, (int)bg->hs[i]->n);
-    ppt8 = max_n > PPP_PPT8_FROM;
-    const int chunk = (ppt8 ? 8 : 4) * SCAT_T;
+    std::vector<SlabGeom> geo(count);
+    std::vector<SlabArgs> mem(count);
+    int ppt = 4;
+    for (size_t i = 0; i < count; ++i) { geo[i] = slab_geom(bg->hs[i]); ppt = std::max(ppt, geo[i].ppt); }
+    ppt = std::min(ppt, 8); /* one scatter form for the batch, and no 16-point one: that threshold was measured on single clouds */
     /* the bounds + histogram pass: about 2048 workgroups over the whole batch (each flushes its LDS histogram with one
-       atomic per non-empty slab) */
+       atomic per non-empty slab), so a member's grid is capped by its share */
     const int mm_share = std::max(4, (int)(2048 / count));
     for (size_t i = 0; i < count; ++i) {
         ppp_handle h = bg->hs[i];
-        BatchMember &M = mem[i];
-        memset(&M, 0, sizeof(M));
-        M.m = h->meta.p; M.P = dev_params(h);
-        M.X = h->X.p; M.Y = h->Y.p; M.Z = h->Z.p; M.n = (int)h->n;
-        M.mm_part = h->mm_part.p;
-        const float xr = h->h_mx[0] - h->h_mn[0];
-        M.slab_x0 = h->h_mn[0]; M.slab_invw = (h->h_nvalid && xr > 0.f) ? (float)h->B / xr : 0.f; /* as enqueue_index */
-        M.incl_lo = h->incl_lo; M.incl_hi = h->incl_hi;
-        M.B = h->B; M.S_cap = h->S_cap; M.slab_cap = h->slab_cap; M.capb = h->capb; M.node_cap = h->node_cap; M.W_cap = h->W_cap;
-        M.knot_cap = h->knot_cap; M.stage_cap = h->stage_cap; M.tab_slabs = h->tab_slabs; M.pose_pad = h->pose_pad;
-        bg->pose_threads = std::max(bg->pose_threads, h->pose_threads);
-        bg->pose_lds = std::max(bg->pose_lds, pose_lds_bytes(h->knot_cap, h->stage_cap, h->tab_slabs));
-        slices_total += h->S_cap;
-        M.out2 = dst_dev ? dst_dev + 6 * offset_rows[i] : nullptr;
-        M.out2_cap = dst_dev ? (int)std::min<size_t>(cap_rows[i], 0x7fffffff) : 0;
-        M.g_minmax = std::max(1, std::min(std::min(h->mm_grid, PPP_MM_GRID_MAX), mm_share));
-        M.g_scatter = std::max(1, ((int)h->n + chunk - 1) / chunk);
-        M.g_sort = h->B; M.g_slice = h->S_cap; M.g_pose = std::max(1, h->S_cap); M.g_smooth = h->sm_tiles;
+        SlabGeom &G = geo[i];
+        G.ppt = ppt; G.g_scatter = scatter_grid((int)h->n, ppt); G.g_minmax = std::min(G.g_minmax, mm_share);
+        mem[i] = slab_args(h, G);
+        mem[i].out2 = dst_dev ? dst_dev + 6 * offset_rows[i] : nullptr;
+        mem[i].out2_cap = dst_dev ? (int)std::min<size_t>(cap_rows[i], 0x7fffffff) : 0;
         h->slab_cnt_used = true;
-        M.slab_cnt = h->slab_cnt.p; M.slab_start = h->slab_start.p; M.slab_cursor = h->slab_cursor.p; M.coarse_cursor = h->coarse_cursor.p;
-        M.px = h->px.p; M.lo = h->lo.p; M.hi = h->hi.p;
-        M.unsorted4 = h->unsorted4.p; M.sorted4 = h->sorted4.p; M.slab_xmin = h->slab_xmin.p; M.slab_xmax = h->slab_xmax.p;
-        M.big_slabs = h->big_slabs.p; M.big_slices = h->big_slices.p;
-        M.node_x = h->node_x.p; M.node_y = h->node_y.p; M.node_z = h->node_z.p;
-        M.node_start = h->node_start.p; M.node_cnt = h->node_cnt.p; M.band_cnt = h->band_cnt.p;
-        M.wp_cnt = h->wp_cnt.p; M.wp_off = h->wp_off.p; M.tail = h->tail.p;
-        M.wp_xyz = h->wp_xyz.p; M.wp_normal = h->wp_normal.p; M.wp_nn = h->wp_nn.p;
-        M.wp_pre = h->wp_pre.p; M.wp_smooth = h->wp_smooth.p; M.wp_out = h->wp_out.p; M.ytab = h->slab_ytab.p; M.slice_wpcnt = h->slice_wpcnt.p;
-        h->mm_grid_used = M.g_minmax;
-        maxB = std::max(maxB, h->B); max_slab_cap = std::max(max_slab_cap, h->slab_cap); max_capb = std::max(max_capb, h->capb);
-        full_slabs = full_slabs || (h->B > 0 && h->h_nvalid / h->B > 1000);
-        gx_mm = std::max(gx_mm, M.g_minmax); gx_scat = std::max(gx_scat, M.g_scatter); gx_sort = std::max(gx_sort, M.g_sort);
-        gx_slice = std::max(gx_slice, M.g_slice); gx_pose = std::max(gx_pose, M.g_pose); gx_smooth = std::max(gx_smooth, M.g_smooth);
+        bg->geom.join(G);
     }
-    {   /* two 512-thread slice workgroups per CU when every member's band leaves room for two (see slice_threads) */
-        bool two_fit = true;
-        for (size_t i = 0; i < count; ++i) two_fit = two_fit && 2 * (slice_kd_bytes(bg->hs[i]->capb) + 1024) <= (size_t)lead->max_lds;
-        bg->slice_thr = (two_fit && slices_total >= 2LL * lead->num_cus) ? 512 : SLICE_KD_T;
-    }
-    HIPCHK(lead, copy_sync(lead, bg->members.p, mem.data(), sizeof(BatchMember) * count, hipMemcpyHostToDevice));
+    HIPCHK(lead, copy_sync(lead, bg->members.p, mem.data(), sizeof(SlabArgs) * count, hipMemcpyHostToDevice));
     return PPP_OK;
 }
 
@@ -2474,9 +2473,6 @@ bool batch_member_ran_window(const BatchGraph *bg, const ppp_handle h) { return 
 /* the stage launches over members [first, first + n) of a batch, on `strm` (timers: the lead's, eager runs only) */
 static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t strm, size_t first, size_t n)
 {
-    const int maxB = bg->maxB, max_slab_cap = bg->max_slab_cap, max_capb = bg->max_capb;
-    const int gx_mm = bg->gx_mm, gx_scat = bg->gx_scat, gx_sort = bg->gx_sort, gx_slice = bg->gx_slice, gx_pose = bg->gx_pose, gx_smooth = bg->gx_smooth;
-    const bool full_slabs = bg->full_slabs, ppt8 = bg->ppt8;
     const unsigned gy = (unsigned)n;
     if (bg->win) { /* the window path: bounds + binning, the per-slice kernel, the finish -- three launches for the whole batch */
         const WinArgs *wm = bg->wmembers.p + first;
@@ -2492,20 +2488,23 @@ static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t s
         LAUNCHB(lead, strm, "k_win_finish_b", k_win_finish_b, dim3(bg->gx_wfin, gy), SMF_T, bg->win_fin_lds, wm);
         return PPP_OK;
     }
-    const BatchMember *mem = bg->members.p + first;
-    const size_t hist_lds = sizeof(int) * (size_t)maxB;
-    LAUNCHB(lead, strm, "k_minmax_b", k_minmax_b, dim3(gx_mm, gy), MM_T, hist_lds, mem);
+    const SlabArgs *mem = bg->members.p + first;
+    const SlabGeom &G = bg->geom;
+    LAUNCHB(lead, strm, "k_minmax_b", k_minmax_b, dim3(G.g_minmax, gy), MM_T, G.hist_lds(), mem);
     /* (the set-up of every member rides in the scatter launch as that member's last workgroup) */
-    if (ppt8) LAUNCHB(lead, strm, "k_slab_scatter_b", k_slab_scatter_b<8>, dim3(gx_scat + 1, gy), SCAT_T, 2 * hist_lds, mem);
-    else LAUNCHB(lead, strm, "k_slab_scatter_b", k_slab_scatter_b<4>, dim3(gx_scat + 1, gy), SCAT_T, 2 * hist_lds, mem);
-    LAUNCHB(lead, strm, "k_slab_sort_b", k_slab_sort_b, dim3(gx_sort, gy), full_slabs ? SORT_T : 256, (size_t)max_slab_cap * 12 + 16, mem);
-    LAUNCHB(lead, strm, "k_slice_kd_b", k_slice_kd_b, dim3(gx_slice, gy), bg->slice_thr, slice_kd_bytes(max_capb), mem);
-    const int rcp = with_block_size(bg->pose_threads, [&](auto bs) -> int {
-        LAUNCHB(lead, strm, "k_pose_b", k_pose_b<decltype(bs)::value>, dim3(gx_pose, gy), bg->pose_threads, bg->pose_lds, mem);
+    const int rcs = with_ppt<false>(G.ppt, [&](auto ppt) -> int {
+        LAUNCHB(lead, strm, "k_slab_scatter_b", k_slab_scatter_b<decltype(ppt)::value>, dim3(G.g_scatter + 1, gy), SCAT_T, 2 * G.hist_lds(), mem);
+        return PPP_OK;
+    });
+    if (rcs) return rcs;
+    LAUNCHB(lead, strm, "k_slab_sort_b", k_slab_sort_b, dim3(G.g_sort, gy), G.sort_threads(), G.sort_lds(), mem);
+    LAUNCHB(lead, strm, "k_slice_kd_b", k_slice_kd_b, dim3(G.g_slice, gy), G.slice_threads(lead->num_cus), G.slice_lds(), mem);
+    const int rcp = with_block_size(G.pose_threads, [&](auto bs) -> int {
+        LAUNCHB(lead, strm, "k_pose_b", k_pose_b<decltype(bs)::value>, dim3(G.g_pose, gy), G.pose_threads, G.pose_lds, mem);
         return PPP_OK;
     });
     if (rcp) return rcp;
-    LAUNCHB(lead, strm, "k_smooth_solve_b", k_smooth_solve_b, dim3(gx_smooth, gy), SMF_T, 0, mem);
+    LAUNCHB(lead, strm, "k_smooth_solve_b", k_smooth_solve_b, dim3(G.g_smooth, gy), SMF_T, 0, mem);
     return PPP_OK;
 }
 

@@ -119,6 +119,45 @@ PPP_KERNEL void k_ingest(const char *raw, size_t stride, int n, int scale, float
 
 struct MinMaxPart { float mn[3], mx[3]; int cnt, pad; };
 
+/* ------------------------------------------------------------------ */
+/* The slab pass's launch record: ONE handle's pass, completely -- its   */
+/* buffers, capacities and per-stage grids (slab_args in the engine      */
+/* fills it, as win_args does for the window path).  The single launch   */
+/* forms take it by value (kernel arguments), the batched forms index an */
+/* array of it in device memory through a uniform address (scalar loads  */
+/* either way).  Block sizes and LDS bytes are the launch's: slab_geom.  */
+/* ------------------------------------------------------------------ */
+struct SlabArgs {
+    DevMeta *m;
+    DevParams P;
+    const float *X, *Y, *Z; /* the streamed source: the whole cloud, or a slice-range handle's part ... */
+    const int *idmap;       /* ... with the cloud indices of its points (or NULL: position = index) */
+    int n, ncloud;          /* points of the source, of the whole cloud */
+    MinMaxPart *mm_part;
+    float slab_x0, slab_invw; /* the slab grid, from the bounds cached with the cloud */
+    int B, S_cap, slab_cap, capb, node_cap, W_cap, out2_cap, knot_cap, stage_cap, tab_slabs;
+    int first_slab;  /* a slice-range handle sorts the g_sort slabs of its interval only */
+    int arena_ran;   /* the arena passes follow the LDS passes in this sequence */
+    float pose_pad;
+    int g_minmax, g_scatter, g_sort, g_slice, g_pose, g_smooth; /* workgroups of this handle per stage */
+    int *slab_cnt, *slab_start, *slab_cursor, *coarse_cursor;
+    float *px, *lo, *hi;
+    float4 *unsorted4, *sorted4;
+    float *slab_xmin, *slab_xmax;
+    int *big_slabs, *big_slices;
+    char *arena;
+    unsigned long long arena_cap;
+    float *node_x, *node_y, *node_z;
+    int *node_start, *node_cnt, *band_cnt;
+    int *wp_cnt, *wp_off, *tail;
+    float4 *wp_xyz, *wp_normal;
+    int *wp_nn;
+    float *wp_pre, *wp_smooth, *wp_out, *out2;
+    int *ytab;
+    int *slice_wpcnt; /* the slices' waypoint counts from k_slice_kd to k_pose, or NULL: the dynamic adjustment re-fits the knots, brute pairing leaves none */
+};
+static_assert(sizeof(SlabArgs) <= 1024, "a kernel argument (576 bytes today): well below the 4 KiB limit");
+
 /* a2: pcl::getMinMax3D (path_slicing_alg.cpp:303, path_dynamic_alg.cpp:345).  One partial per
    workgroup, no atomics (same-address atomics serialise at ~11 ns each on this part). */
 /* HIST: the same pass also builds the x-slab histogram (LDS-privatised, flushed with one global
@@ -217,11 +256,9 @@ __device__ __forceinline__ void minmax_body(const float *__restrict__ X, const f
     }
 }
 template <bool HIST>
-__global__ void __launch_bounds__(MM_T) k_minmax(const float *__restrict__ X, const float *__restrict__ Y,
-                                                const float *__restrict__ Z, int n, MinMaxPart *part, float x0, float invw,
-                                                int B, int *slab_cnt, float xlo, float xhi, int *cursor)
-{
-    minmax_body<HIST>(X, Y, Z, n, part, x0, invw, B, slab_cnt, xlo, xhi, cursor, blockIdx.x, gridDim.x);
+__global__ void __launch_bounds__(MM_T) k_minmax(SlabArgs A)
+{   /* (also the plan-time bounds pass: HIST = false reads X, Y, Z, n, mm_part and g_minmax only) */
+    minmax_body<HIST>(A.X, A.Y, A.Z, A.n, A.mm_part, A.slab_x0, A.slab_invw, A.B, A.slab_cnt, A.P.incl_lo, A.P.incl_hi, A.slab_cursor, blockIdx.x, A.g_minmax);
 }
 
 /* Device form of ppp_slice_walk for one thread: identical values, but without a data dependent
@@ -451,11 +488,12 @@ PPP_KERNEL void __launch_bounds__(MM_T) k_ingest_minmax(const char *__restrict__
 #ifndef SETUP_T
 #define SETUP_T 1024
 #endif
-__device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const MinMaxPart *__restrict__ part, int nparts,
-                                           float *px, float *lo, float *hi, int S_cap, int B, int *slab_cnt, float slab_x0,
-                                           float slab_invw, int *slab_start, int *slab_cursor, int *coarse_cursor, const bool own_launch = true)
+__device__ __forceinline__ void setup_body(const SlabArgs &A, const bool own_launch)
 {   /* own_launch = false: this is the extra workgroup of the one-level scatter launch -- the scatter workgroups beside it read
        the histogram too (each scans it for itself), so it is left alone (k_slab_sort clears it), and they keep their own cursors */
+    DevMeta *const m = A.m;
+    const DevParams &P = A.P;
+    const int B = A.B;
     __shared__ int s_scan[17];
     __shared__ float s_mn[3][SETUP_T / 64], s_mx[3][SETUP_T / 64];
     __shared__ int s_cnt[SETUP_T / 64];
@@ -466,8 +504,8 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     int cnt = 0;
     STAMP_BEGIN();
-    for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-        MinMaxPart r = part[i];
+    for (int i = threadIdx.x; i < A.g_minmax; i += blockDim.x) {
+        MinMaxPart r = A.mm_part[i];
         cnt += r.cnt;
         for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], r.mn[d]); mx[d] = fmaxf(mx[d], r.mx[d]); }
     }
@@ -481,8 +519,8 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
        scanned there, and go out coalesced: a thread reading its own run of counts from global one after the other was 80 %
        of this kernel at 8192 slabs. */
     {
-        for (int i = threadIdx.x; i < B; i += blockDim.x) s_cnts[i] = slab_cnt[i]; /* (loads only: they pipeline) */
-        if (own_launch) for (int i = threadIdx.x; i < B; i += blockDim.x) slab_cnt[i] = 0;
+        for (int i = threadIdx.x; i < B; i += blockDim.x) s_cnts[i] = A.slab_cnt[i]; /* (loads only: they pipeline) */
+        if (own_launch) for (int i = threadIdx.x; i < B; i += blockDim.x) A.slab_cnt[i] = 0;
         __syncthreads();
         const int per = (B + blockDim.x - 1) / blockDim.x;
         const int b0 = threadIdx.x * per;
@@ -496,11 +534,11 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
         __syncthreads();
         for (int i = threadIdx.x; i < B; i += blockDim.x) {
             const int v = s_cnts[i];
-            slab_start[i] = v;
-            if (own_launch) slab_cursor[i] = v;
-            if (coarse_cursor && (i & ((1 << SCAT_COARSE_SHIFT) - 1)) == 0) coarse_cursor[i >> SCAT_COARSE_SHIFT] = v;
+            A.slab_start[i] = v;
+            if (own_launch) A.slab_cursor[i] = v;
+            if (own_launch && (i & ((1 << SCAT_COARSE_SHIFT) - 1)) == 0) A.coarse_cursor[i >> SCAT_COARSE_SHIFT] = v;
         }
-        if (threadIdx.x == 0) { slab_start[B] = total; s_total = total; }
+        if (threadIdx.x == 0) { A.slab_start[B] = total; s_total = total; }
     }
     __syncthreads();
     STAMP(5, 1); /* slab scan */
@@ -539,15 +577,15 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
             if (imax > cc + istep && cc + istep > imin) nback = (imax - cc - 1) / istep;
             S = nfront + 1 + nback;
             s_nfront = nfront; s_c = cc; s_mid = (r.mn[0] + r.mx[0]) / 2;
-        } else if (c) S = slice_walk_device(P.walk, r.mn[0], r.mx[0], P.tool_radius, px, S_cap, s_front, 4096);
-        if (S > S_cap) { r.err = DERR_CAPACITY; S = S_cap; }
+        } else if (c) S = slice_walk_device(P.walk, r.mn[0], r.mx[0], P.tool_radius, A.px, A.S_cap, s_front, 4096);
+        if (S > A.S_cap) { r.err = DERR_CAPACITY; S = A.S_cap; }
         r.S = S;
         r.first_kept = P.drop_ends ? 1 : 0;
         int nk = P.drop_ends ? S - 2 : S;
         r.nkept = nk < 0 ? 0 : nk;
         r.B = B;
-        r.slab_x0 = slab_x0;     /* the grid k_minmax<true> binned with */
-        r.slab_invw = slab_invw;
+        r.slab_x0 = A.slab_x0;     /* the grid k_minmax<true> binned with */
+        r.slab_invw = A.slab_invw;
         r.sb = P.slice_begin < 0 ? 0 : (P.slice_begin > S ? S : P.slice_begin);
         r.se = (P.slice_end <= 0 || P.slice_end > S) ? S : P.slice_end;
         r.incl_lo = P.incl_lo; r.incl_hi = P.incl_hi;
@@ -561,10 +599,10 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
     const int S = s_S;
     const int nfront = s_nfront, istep = (int)(P.tool_radius * 2);
     for (int s = threadIdx.x; s < S; s += blockDim.x) {
-        if (nfront >= 0) px[s] = s < nfront ? (float)(s_c - (nfront - s) * istep) : (s == nfront ? s_mid : (float)(s_c + (s - nfront) * istep));
-        int position = (int)px[s];
-        lo[s] = (float)(-2 + position);
-        hi[s] = (float)(2 + position);
+        if (nfront >= 0) A.px[s] = s < nfront ? (float)(s_c - (nfront - s) * istep) : (s == nfront ? s_mid : (float)(s_c + (s - nfront) * istep));
+        int position = (int)A.px[s];
+        A.lo[s] = (float)(-2 + position);
+        A.hi[s] = (float)(2 + position);
     }
     STAMP(5, 3); /* band limits */
 }
@@ -576,7 +614,7 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
 #ifndef SCAT_T
 #define SCAT_T 1024
 #endif
-/* LEVEL 0: the cloud straight into its slabs (one pass; the writes of a workgroup are runs of chunk / B points).
+/* One level (scatter_setup_body): the cloud straight into its slabs (one pass; the writes of a workgroup are runs of chunk / B points).
    Large clouds have thousands of slabs and those runs shrink to a point or two -- 16-byte writes scattered over the
    whole array.  They go in two passes instead: LEVEL 1 bins into COARSE groups of 64 neighbouring slabs (runs of
    hundreds of points, written to `out4` = the sorted4 buffer used as scratch), LEVEL 2 reads that -- each chunk now
@@ -584,14 +622,16 @@ __device__ __forceinline__ void setup_body(DevMeta *m, const DevParams &P, const
    which k_slab_sort fixes anyway. */
 /* Every thread keeps its PPT points in registers between the counting and the writing pass: the input is read once. */
 template <int LEVEL, int PPT>
-__device__ __forceinline__ void slab_scatter_body(const float *__restrict__ X, const float *__restrict__ Y,
-                                                  const float *__restrict__ Z, const float4 *__restrict__ in4, int n,
-                                                  const DevMeta *m, int *cursor, float4 *out4, const int *__restrict__ idmap, const int bx)
+__device__ __forceinline__ void slab_scatter_body(const SlabArgs &A, const int bx)
 {
+    static_assert(LEVEL == 1 || LEVEL == 2, "the one-level scatter is scatter_setup_body");
     extern __shared__ __attribute__((aligned(16))) int s_hist[];
+    const DevMeta *m = A.m;
+    int *cursor = LEVEL == 1 ? A.coarse_cursor : A.slab_cursor;
+    float4 *out4 = LEVEL == 1 ? A.sorted4 : A.unsorted4; /* (level 1 parks its bins in sorted4, level 2 reads them back) */
     const int B = LEVEL == 1 ? ((m->B + (1 << SCAT_COARSE_SHIFT) - 1) >> SCAT_COARSE_SHIFT) : m->B;
     const float xlo = m->incl_lo, xhi = m->incl_hi;
-    if (LEVEL == 2) n = m->n_sorted; /* the scratch holds the kept points only */
+    const int n = LEVEL == 2 ? m->n_sorted : A.n; /* the scratch holds the kept points only */
     auto bin = [&](float x) { return LEVEL == 1 ? (slab_of(m, x) >> SCAT_COARSE_SHIFT) : slab_of(m, x); };
     STAMP_BEGIN();
     /* this thread's points: i0 + threadIdx.x + k * blockDim.x (coalesced), requested before anything else */
@@ -603,8 +643,8 @@ __device__ __forceinline__ void slab_scatter_body(const float *__restrict__ X, c
         const int i = i0 + threadIdx.x + k * (int)blockDim.x;
         pb[k] = -1;
         if (i < n) {
-            if (LEVEL == 2) p[k] = in4[i];
-            else p[k] = make_float4(X[i], Y[i], Z[i], __int_as_float(idmap ? idmap[i] : i)); /* idmap: cloud indices of a part */
+            if (LEVEL == 2) p[k] = A.sorted4[i];
+            else p[k] = make_float4(A.X[i], A.Y[i], A.Z[i], __int_as_float(A.idmap ? A.idmap[i] : i)); /* idmap: cloud indices of a part */
         } else p[k] = make_float4(NAN, 0.f, 0.f, 0.f);
     }
     for (int b = threadIdx.x; b < B; b += blockDim.x) s_hist[b] = 0;
@@ -638,10 +678,9 @@ __device__ __forceinline__ void slab_scatter_body(const float *__restrict__ X, c
 #define SORT_T 512
 #endif
 template <bool ARENA>
-__device__ __forceinline__ void slab_sort_body(const float4 *__restrict__ unsorted4, const int *__restrict__ slab_start,
-                                               float4 *sorted4, float *slab_xmin, float *slab_xmax, DevMeta *m, int cap,
-                                               int *big_list, char *arena, unsigned long long arena_cap, int *ytab, int *slab_cnt, const int bx)
+__device__ __forceinline__ void slab_sort_body(const SlabArgs &A, const int bx)
 {   /* (bx: slab number; a slice-range handle launches only the slabs of its interval, offset by the first one) */
+    DevMeta *const m = A.m;
     extern __shared__ __attribute__((aligned(16))) char s_raw[];
     __shared__ float s_mn[SORT_T / 64], s_mx[SORT_T / 64];
     __shared__ int s_scr[17];
@@ -649,10 +688,10 @@ __device__ __forceinline__ void slab_sort_body(const float4 *__restrict__ unsort
     int b = bx;
     if (ARENA) {
         if (b >= m->big_slabs) return;
-        b = big_list[b];
+        b = A.big_slabs[b];
     }
-    const int s0 = slab_start[b], c = slab_start[b + 1] - s0;
-    if (!ARENA && slab_cnt && threadIdx.x == 0) slab_cnt[b] = 0; /* the histogram is used up (k_setup clears it itself when it has its own launch) */
+    const int s0 = A.slab_start[b], c = A.slab_start[b + 1] - s0;
+    if (!ARENA && A.slab_cnt && threadIdx.x == 0) A.slab_cnt[b] = 0; /* the histogram is used up (k_setup clears it itself when it has its own launch) */
     u64 *key;
     int *hist;
     int NB;
@@ -661,32 +700,32 @@ __device__ __forceinline__ void slab_sort_body(const float4 *__restrict__ unsort
         const unsigned long long need = (unsigned long long)c * 8 + (unsigned long long)(NB + 1) * 4 + 16;
         if (threadIdx.x == 0) s_off = atomicAdd(&m->arena_cursor, (need + 15) & ~15ull);
         __syncthreads();
-        if (s_off + need > arena_cap) { if (threadIdx.x == 0) set_err(m, DERR_CAPACITY, -1); return; }
-        key = (u64 *)(arena + s_off);
+        if (s_off + need > A.arena_cap) { if (threadIdx.x == 0) set_err(m, DERR_CAPACITY, -1); return; }
+        key = (u64 *)(A.arena + s_off);
         hist = (int *)(key + c);
     } else {
-        if (c > cap) {
-            if (threadIdx.x == 0) big_list[atomicAdd(&m->big_slabs, 1)] = b;
+        if (c > A.slab_cap) {
+            if (threadIdx.x == 0) A.big_slabs[atomicAdd(&m->big_slabs, 1)] = b;
             /* Until the arena pass has sorted it the slab holds its points in arrival order, an empty y-bucket row and no x
                bounds.  The kernels behind this launch in the stream (whole-cloud normals, the Area2Cloud searches of the dynamic
                adjustment) walk the whole index before the host knows that it is incomplete and runs the pass again: whatever a
                slab's places and row held from an earlier plan -- cloud indices, offsets -- sent them outside their buffers
                (found by a randomised case: an aligned 123 x 124 plate, brute pairing, dynamic adjustment). */
-            for (int i = threadIdx.x; i < c; i += blockDim.x) sorted4[s0 + i] = unsorted4[s0 + i];
-            if (ytab) for (int q = threadIdx.x; q <= YTB; q += blockDim.x) ytab[(size_t)b * (YTB + 1) + q] = 0;
-            if (threadIdx.x == 0) { slab_xmin[b] = -INFINITY; slab_xmax[b] = INFINITY; }
+            for (int i = threadIdx.x; i < c; i += blockDim.x) A.sorted4[s0 + i] = A.unsorted4[s0 + i];
+            if (A.ytab) for (int q = threadIdx.x; q <= YTB; q += blockDim.x) A.ytab[(size_t)b * (YTB + 1) + q] = 0;
+            if (threadIdx.x == 0) { A.slab_xmin[b] = -INFINITY; A.slab_xmax[b] = INFINITY; }
             return;
         }
-        NB = min(cap, next_pow2(c));
+        NB = min(A.slab_cap, next_pow2(c));
         key = (u64 *)s_raw;
-        hist = (int *)(key + cap);
+        hist = (int *)(key + A.slab_cap);
     }
     float mn = INFINITY, mx = -INFINITY;
     if (c > 0) {
         const float y0 = m->mn[1];
         const float yr = m->mx[1] - y0;
         const float scale = yr > 0.f ? (float)NB / yr : 0.f;
-        const float4 *src = unsorted4 + s0;
+        const float4 *src = A.unsorted4 + s0;
         auto gen = [&](int i) { return YK_MAKE(src[i].y, i); };
         auto bucket = [&](u64 k) {
             int q = (int)((ord2f(YK_Y(k)) - y0) * scale);
@@ -699,10 +738,10 @@ __device__ __forceinline__ void slab_sort_body(const float4 *__restrict__ unsort
         };
         if (!ARENA && c <= 8 * (int)blockDim.x) block_bucket_sort_cached<8>(key, c, hist, NB, s_scr, gen, bucket, less); /* y read once */
         else block_bucket_sort(key, c, hist, NB, s_scr, gen, bucket, less);
-        int *tab = ytab ? ytab + (size_t)b * (YTB + 1) : nullptr;
+        int *tab = A.ytab ? A.ytab + (size_t)b * (YTB + 1) : nullptr;
         for (int i = threadIdx.x; i < c; i += blockDim.x) {
             float4 p = src[YK_POS(key[i])];
-            sorted4[s0 + i] = p;
+            A.sorted4[s0 + i] = p;
             mn = fminf(mn, p.x); mx = fmaxf(mx, p.x);
             if (tab) { /* the table entries between the previous point's bucket and this point's: i points lie below them */
                 const int bi = ytab_bucket(m, p.y);
@@ -711,15 +750,15 @@ __device__ __forceinline__ void slab_sort_body(const float4 *__restrict__ unsort
                 if (i == c - 1) for (int q = bi + 1; q <= YTB; ++q) tab[q] = c;
             }
         }
-    } else if (ytab) {
-        for (int q = threadIdx.x; q <= YTB; q += blockDim.x) ytab[(size_t)b * (YTB + 1) + q] = 0;
+    } else if (A.ytab) {
+        for (int q = threadIdx.x; q <= YTB; q += blockDim.x) A.ytab[(size_t)b * (YTB + 1) + q] = 0;
     }
     mn = wave_min(mn); mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); } /* launched with 256 or SORT_T threads */
-        slab_xmin[b] = mn; slab_xmax[b] = mx;
+        A.slab_xmin[b] = mn; A.slab_xmax[b] = mx;
     }
 }
 
@@ -992,31 +1031,29 @@ __device__ inline int flatten_nodes(const SliceLds &L, int ncand, float *out_y, 
 #ifndef K_SLICE_T
 #define K_SLICE_T 512 /* threads of the generic insert_point kernel (brute flavour, API mirror): 1 M points / 256 slices 663 (256 threads) -> 409 us; 1024: 404 */
 #endif
-PPP_KERNEL void __launch_bounds__(K_SLICE_T) k_slice(const float4 *__restrict__ sorted4, const int *__restrict__ slab_start,
-                                               DevMeta *m, const float *__restrict__ px, const float *__restrict__ lo,
-                                               const float *__restrict__ hi, int pairing, int capb, float *node_x, float *node_y,
-                                               float *node_z, int node_cap, int *node_start, int *node_cnt, int *band_cnt, int *big_list)
+PPP_KERNEL void __launch_bounds__(K_SLICE_T) k_slice(SlabArgs A)
 {
+    DevMeta *const m = A.m;
     extern __shared__ __attribute__((aligned(16))) char s_raw[];
     __shared__ int s_scr[17];
     __shared__ int s_n, s_base;
     const int s = blockIdx.x;
     if (s >= m->S) return;
     if (s < m->sb || s >= m->se) { /* another handle's slice */
-        if (threadIdx.x == 0) { node_start[s] = 0; node_cnt[s] = 0; band_cnt[s] = 0; }
+        if (threadIdx.x == 0) { A.node_start[s] = 0; A.node_cnt[s] = 0; A.band_cnt[s] = 0; }
         return;
     }
-    SliceLds L = carve_slice_lds(s_raw, capb);
-    const float Px = px[s];
-    int n = band_gather_sorted(L, capb, sorted4, slab_start, m, lo[s], hi[s], &s_n);
+    SliceLds L = carve_slice_lds(s_raw, A.capb);
+    const float Px = A.px[s];
+    int n = band_gather_sorted(L, A.capb, A.sorted4, A.slab_start, m, A.lo[s], A.hi[s], &s_n);
     if (n < 0) { /* does not fit LDS: leave it to the arena pass (k_slice_brute_arena) */
-        if (threadIdx.x == 0) { big_list[atomicAdd(&m->big_slices, 1)] = s; node_start[s] = 0; node_cnt[s] = 0; band_cnt[s] = s_n; }
+        if (threadIdx.x == 0) { A.big_slices[atomicAdd(&m->big_slices, 1)] = s; A.node_start[s] = 0; A.node_cnt[s] = 0; A.band_cnt[s] = s_n; }
         return;
     }
-    if (threadIdx.x == 0) band_cnt[s] = n;
-    int ncand = insert_point_lds(L, n, Px, pairing, s_scr);
+    if (threadIdx.x == 0) A.band_cnt[s] = n;
+    int ncand = insert_point_lds(L, n, Px, A.P.pairing, s_scr);
     if (ncand < 0) {
-        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); node_start[s] = 0; node_cnt[s] = 0; }
+        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); A.node_start[s] = 0; A.node_cnt[s] = 0; }
         return;
     }
     /* count distinct keys first to reserve the segment, then write */
@@ -1027,16 +1064,16 @@ PPP_KERNEL void __launch_bounds__(K_SLICE_T) k_slice(const float4 *__restrict__ 
     block_exscan(mcount, s_scr, &tot);
     if (threadIdx.x == 0) {
         int base = atomicAdd(&m->node_cursor, tot);
-        if (base + tot > node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
+        if (base + tot > A.node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
         s_base = base;
-        node_start[s] = base;
-        node_cnt[s] = tot;
+        A.node_start[s] = base;
+        A.node_cnt[s] = tot;
         if (tot < 3) set_err(m, DERR_SLICE, s); /* gsl_spline_alloc needs >= 3 knots */
     }
     __syncthreads();
-    if (node_cnt[s] == 0 && tot != 0) return;
-    flatten_nodes(L, ncand, node_y + s_base, node_z + s_base, tot, s_scr);
-    for (int i = threadIdx.x; i < tot; i += blockDim.x) node_x[s_base + i] = Px; /* insert_cloud.points[i].x = PlanePoint[0] */
+    if (A.node_cnt[s] == 0 && tot != 0) return;
+    flatten_nodes(L, ncand, A.node_y + s_base, A.node_z + s_base, tot, s_scr);
+    for (int i = threadIdx.x; i < tot; i += blockDim.x) A.node_x[s_base + i] = Px; /* insert_cloud.points[i].x = PlanePoint[0] */
 }
 
 /* insert_point of v1 (Path_Generation.cpp:107-206, either pairing) for a band that does not fit LDS: the same steps as
@@ -1046,38 +1083,36 @@ __host__ __device__ inline size_t slice_brute_bytes(size_t n)
 {   /* a4 16 + keys 8 + el er rstar lstar pairL pairR 24 + hist 4 (NB <= n) + flags */
     return n * 52 + (n / 4) + 256;
 }
-PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(const float4 *__restrict__ sorted4, const int *__restrict__ slab_start,
-                                                            DevMeta *m, const float *__restrict__ px, const float *__restrict__ lo,
-                                                            const float *__restrict__ hi, int pairing, int ncloud, float *node_x, float *node_y,
-                                                            float *node_z, int node_cap, int *node_start, int *node_cnt, const int *band_cnt,
-                                                            const int *big_list, char *arena, unsigned long long arena_cap)
+PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(SlabArgs A)
 {
+    DevMeta *const m = A.m;
     __shared__ int s_scr[17];
     __shared__ int s_n, s_nl, s_nr, s_np, s_base, s_m;
     __shared__ unsigned long long s_off;
     if ((int)blockIdx.x >= m->big_slices) return;
-    const int s = big_list[blockIdx.x];
-    const size_t cap = (size_t)band_cnt[s];
+    const int s = A.big_slices[blockIdx.x];
+    const size_t cap = (size_t)A.band_cnt[s];
     const unsigned long long need = slice_brute_bytes(cap);
     if (threadIdx.x == 0) { s_off = atomicAdd(&m->arena_cursor, (need + 15) & ~15ull); s_n = 0; s_nl = 0; s_nr = 0; s_m = 0; }
     __syncthreads();
-    if (s_off + need > arena_cap) {
-        if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); node_start[s] = 0; node_cnt[s] = 0; }
+    if (s_off + need > A.arena_cap) {
+        if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); A.node_start[s] = 0; A.node_cnt[s] = 0; }
         return;
     }
-    char *mem = arena + s_off;
+    char *mem = A.arena + s_off;
     float4 *a4 = (float4 *)mem;
     u64 *keys = (u64 *)(a4 + cap);
     int *el = (int *)(keys + cap), *er = el + cap, *rstar = er + cap, *lstar = rstar + cap, *pairL = lstar + cap, *pairR = pairL + cap;
     int *hist = pairR + cap;                    /* cap + 1 ints at most (NB <= cap / 2 .. cap) */
     u64 *flags = (u64 *)(((uintptr_t)(hist + cap + 2) + 7) & ~(uintptr_t)7);
-    const float Px = px[s], blo = lo[s], bhi = hi[s];
+    const float Px = A.px[s], blo = A.lo[s], bhi = A.hi[s];
     /* rangedX_index: the PassThrough band, every point of it */
     if (blo <= bhi && m->n_valid > 0) {
         const int b0 = slab_of(m, blo), b1 = slab_of(m, bhi);
-        const int i0 = slab_start[b0], i1 = slab_start[b1 + 1];
+        const int i0 = A.slab_start[b0], i1 = A.slab_start[b1 + 1];
         for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-            const float4 p = sorted4[i];
+            const float4 *src = A.sorted4 + i; /* (member by member: the struct copy went through a private temporary, which the compiler parks in LDS) */
+            const float4 p = make_float4(src->x, src->y, src->z, src->w);
             if (!(p.x < blo || p.x > bhi)) {
                 const int slot = atomicAdd(&s_n, 1);
                 if ((size_t)slot < cap) a4[slot] = p;
@@ -1086,10 +1121,10 @@ PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(const float4 *__rest
     }
     __syncthreads();
     const int n = s_n;
-    if ((size_t)n > cap) { if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); node_start[s] = 0; node_cnt[s] = 0; } return; }
+    if ((size_t)n > cap) { if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); A.node_start[s] = 0; A.node_cnt[s] = 0; } return; }
     int NB = next_pow2(max(n, 64)) >> 1;
     {   /* ascending cloud index, as PassThrough returns the indices */
-        const double scale = (double)NB / (double)max(ncloud, 1);
+        const double scale = (double)NB / (double)max(A.ncloud, 1);
         auto gen = [&](int i) { return ((u64)(u32)idx_of(a4[i]) << 32) | (u32)i; };
         auto bucket = [&](u64 k) { int q = (int)((double)(u32)(k >> 32) * scale); return q < 0 ? 0 : (q >= NB ? NB - 1 : q); };
         auto less = [&](u64 a, u64 b) { return a < b; };
@@ -1118,12 +1153,12 @@ PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(const float4 *__rest
     }
     const int nEl = s_nl, nEr = s_nr;
     if (nEl == 0 || nEr == 0) { /* empty map -> fewer than 3 knots; empty right side: the reference crashes */
-        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); node_start[s] = 0; node_cnt[s] = 0; }
+        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); A.node_start[s] = 0; A.node_cnt[s] = 0; }
         return;
     }
     int ncand = 0;
     float *cy = (float *)rstar, *cz = (float *)lstar; /* reused once the pairs are read */
-    if (pairing == 0) {
+    if (A.P.pairing == 0) {
         for (int i = threadIdx.x; i < nEl; i += blockDim.x) {
             const float4 q = a4[el[i]];
             float best = INFINITY; int br = 0;
@@ -1217,16 +1252,16 @@ PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(const float4 *__rest
     block_exscan(mcount, s_scr, &tot);
     if (threadIdx.x == 0) {
         int base = atomicAdd(&m->node_cursor, tot);
-        if (base + tot > node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
+        if (base + tot > A.node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
         s_base = base; s_np = tot;
-        node_start[s] = base;
-        node_cnt[s] = tot;
+        A.node_start[s] = base;
+        A.node_cnt[s] = tot;
         if (tot < 3) set_err(m, DERR_SLICE, s);
     }
     __syncthreads();
     const int nk = s_np;
     if (nk == 0) return;
-    for (int i = threadIdx.x; i < nk; i += blockDim.x) node_x[s_base + i] = Px;
+    for (int i = threadIdx.x; i < nk; i += blockDim.x) A.node_x[s_base + i] = Px;
     for (int base = 0; base < ncand; base += blockDim.x) {
         const int j = base + threadIdx.x;
         int keep = 0;
@@ -1235,7 +1270,7 @@ PPP_KERNEL void __launch_bounds__(1024) k_slice_brute_arena(const float4 *__rest
         int t2;
         const int pre = block_exscan(keep, s_scr, &t2);
         const int o = s_m;
-        if (keep) { node_y[s_base + o + pre] = ord2f((u32)(k >> 32)); node_z[s_base + o + pre] = cz[(u32)k]; }
+        if (keep) { A.node_y[s_base + o + pre] = ord2f((u32)(k >> 32)); A.node_z[s_base + o + pre] = cz[(u32)k]; }
         __syncthreads();
         if (threadIdx.x == 0) s_m = o + t2;
         __syncthreads();
@@ -1343,14 +1378,10 @@ __device__ inline int nn_sorted_side(const u64 *keys, const float4 *a4, int a, i
 #define SLICE_KD_T 1024
 #endif
 template <bool ARENA>
-__device__ __forceinline__ void slice_kd_body(const float4 *__restrict__ sorted4, const int *__restrict__ slab_start,
-                                              DevMeta *m, const float *__restrict__ px, const float *__restrict__ lo,
-                                              const float *__restrict__ hi, int capb_lds, float *node_x, float *node_y,
-                                              float *node_z, int node_cap, int *node_start, int *node_cnt, int *band_cnt, int *big_list,
-                                              char *arena, unsigned long long arena_cap, double trim, double res, int W_cap, int *slice_wpcnt,
-                                              const int bx)
+__device__ __forceinline__ void slice_kd_body(const SlabArgs &A, const int bx)
 {   /* slice_wpcnt (optional): the slice's waypoint count -- getPath's sampling loop over [first knot + trim, last knot - trim) --
        left for k_pose, whose every workgroup needs the counts of ALL slices for its offset in the list */
+    DevMeta *const m = A.m;
     extern __shared__ __attribute__((aligned(16))) char s_raw[];
     __shared__ int s_scr[17];
     __shared__ int s_n, s_plane, s_ner, s_base, s_m;
@@ -1358,37 +1389,37 @@ __device__ __forceinline__ void slice_kd_body(const float4 *__restrict__ sorted4
     int s = bx;
     if (ARENA) {
         if (s >= m->big_slices) return;
-        s = big_list[s];
+        s = A.big_slices[s];
     } else {
         if (s >= m->S) return;
         if (s < m->sb || s >= m->se) { /* another handle's slice */
-            if (threadIdx.x == 0) { node_start[s] = 0; node_cnt[s] = 0; band_cnt[s] = 0; if (slice_wpcnt) slice_wpcnt[s] = 0; }
+            if (threadIdx.x == 0) { A.node_start[s] = 0; A.node_cnt[s] = 0; A.band_cnt[s] = 0; if (A.slice_wpcnt) A.slice_wpcnt[s] = 0; }
             return;
         }
     }
     STAMP_BEGIN();
-    const float Px = px[s], blo = lo[s], bhi = hi[s];
+    const float Px = A.px[s], blo = A.lo[s], bhi = A.hi[s];
     const int b0 = slab_of(m, blo), b1 = slab_of(m, bhi);
-    const int i0 = slab_start[b0], i1 = slab_start[b1 + 1];
-    size_t capb = (size_t)capb_lds;
+    const int i0 = A.slab_start[b0], i1 = A.slab_start[b1 + 1];
+    size_t capb = (size_t)A.capb;
     char *mem = s_raw;
     if (ARENA) { /* size the arena segment from the band count of the first pass */
-        capb = (size_t)band_cnt[s];
+        capb = (size_t)A.band_cnt[s];
         const unsigned long long need = slice_kd_bytes(capb);
         if (threadIdx.x == 0) s_off = atomicAdd(&m->arena_cursor, (need + 15) & ~15ull);
         __syncthreads();
-        if (s_off + need > arena_cap) {
-            if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); node_start[s] = 0; node_cnt[s] = 0; if (slice_wpcnt) slice_wpcnt[s] = 0; }
+        if (s_off + need > A.arena_cap) {
+            if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, s); A.node_start[s] = 0; A.node_cnt[s] = 0; if (A.slice_wpcnt) A.slice_wpcnt[s] = 0; }
             return;
         }
-        mem = arena + s_off;
+        mem = A.arena + s_off;
     }
     SliceKdMem L = carve_slice_kd(mem, capb);
     if (threadIdx.x == 0) { s_n = 0; s_plane = 0; s_ner = 0; s_m = 0; }
     __syncthreads();
     /* rangedX_index: the PassThrough band, minus points exactly on the plane (neither side) */
     for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-        float4 p = sorted4[i];
+        float4 p = A.sorted4[i];
         if (!(p.x < blo || p.x > bhi)) {
             float distance2plane = (p.x - Px) * 1.f + (p.y - 0.f) * 0.f + (p.z - 0.f) * 0.f;
             if (distance2plane > 0 || distance2plane < 0) {
@@ -1401,9 +1432,9 @@ __device__ __forceinline__ void slice_kd_body(const float4 *__restrict__ sorted4
     STAMP(0, 0); /* band gather */
     const int n = s_n;
     if (!ARENA) {
-        if (threadIdx.x == 0) band_cnt[s] = n + s_plane;
+        if (threadIdx.x == 0) A.band_cnt[s] = n + s_plane;
         if ((size_t)n > capb) { /* does not fit LDS: leave it to the arena pass */
-            if (threadIdx.x == 0) { big_list[atomicAdd(&m->big_slices, 1)] = s; node_start[s] = 0; node_cnt[s] = 0; if (slice_wpcnt) slice_wpcnt[s] = 0; }
+            if (threadIdx.x == 0) { A.big_slices[atomicAdd(&m->big_slices, 1)] = s; A.node_start[s] = 0; A.node_cnt[s] = 0; if (A.slice_wpcnt) A.slice_wpcnt[s] = 0; }
             return;
         }
     }
@@ -1433,7 +1464,7 @@ __device__ __forceinline__ void slice_kd_body(const float4 *__restrict__ sorted4
     const int nEr = s_ner, nEl = n - nEr;
     if (nEl == 0 || nEr == 0) {
         /* empty left side: empty map -> < 3 knots; empty right side: empty FLANN tree */
-        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); node_start[s] = 0; node_cnt[s] = 0; if (slice_wpcnt) slice_wpcnt[s] = 0; }
+        if (threadIdx.x == 0) { set_err(m, DERR_SLICE, s); A.node_start[s] = 0; A.node_cnt[s] = 0; if (A.slice_wpcnt) A.slice_wpcnt[s] = 0; }
         return;
     }
     for (int i0q = 0; i0q < nEl; i0q += blockDim.x) {
@@ -1501,23 +1532,23 @@ __device__ __forceinline__ void slice_kd_body(const float4 *__restrict__ sorted4
     if (threadIdx.x == 0) {
         int tot = s_m;
         int base = atomicAdd(&m->node_cursor, tot);
-        if (base + tot > node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
+        if (base + tot > A.node_cap) { set_err(m, DERR_CAPACITY, s); base = 0; tot = 0; }
         s_base = base;
         s_plane = tot; /* (s_plane is free again: the knot count, for the workgroup, without re-reading node_cnt from memory) */
-        node_start[s] = base;
-        node_cnt[s] = tot;
+        A.node_start[s] = base;
+        A.node_cnt[s] = tot;
         if (tot < 3) set_err(m, DERR_SLICE, s);
     }
     __syncthreads();
     const int nknots = s_plane;
-    if (slice_wpcnt && threadIdx.x == 0)
-        slice_wpcnt[s] = nknots >= 1 ? sample_count((double)L.cy[L.hist_cand[0]], (double)L.cy[L.hist_cand[nknots - 1]], trim, res, W_cap) : 0;
+    if (A.slice_wpcnt && threadIdx.x == 0)
+        A.slice_wpcnt[s] = nknots >= 1 ? sample_count((double)L.cy[L.hist_cand[0]], (double)L.cy[L.hist_cand[nknots - 1]], A.P.trim, A.P.path_resolution, A.W_cap) : 0;
     if (nknots == 0) return;
     for (int i = threadIdx.x; i < nknots; i += blockDim.x) {
         const int ci = L.hist_cand[i];
-        node_x[s_base + i] = Px; /* insert_cloud.points[i].x = PlanePoint[0] */
-        node_y[s_base + i] = L.cy[ci];
-        node_z[s_base + i] = L.cz[ci];
+        A.node_x[s_base + i] = Px; /* insert_cloud.points[i].x = PlanePoint[0] */
+        A.node_y[s_base + i] = L.cy[ci];
+        A.node_z[s_base + i] = L.cz[ci];
     }
     STAMP(0, 4); /* map flattening + node write */
 }
@@ -2122,58 +2153,52 @@ struct PoseBack {
     const int *ytab;
 };
 template <bool ALIGNED, int PRE>
-__device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const float4 *__restrict__ sorted4,
-                                          const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
-                                          const float *__restrict__ slab_xmax, const float *__restrict__ px,
-                                          const float *__restrict__ node_x, const float *__restrict__ node_y,
-                                          const float *__restrict__ node_z,
-                                          const int *__restrict__ node_start, const int *__restrict__ node_cnt,
-                                          int *wp_cnt, int *wp_off, int *tail, int W_cap, int arena_ran, int knot_cap, int stage_cap,
-                                          int tab_slabs, float pad, float4 *wp_xyz, int *wp_nn, float4 *wp_normal, float *wp_pre, const PoseBack &back,
-                                          const int *__restrict__ ytab, const int *__restrict__ slice_wpcnt, const int bx)
+__device__ __forceinline__ void pose_body(const SlabArgs &A, const PoseBack &back, const int bx)
 {
+    DevMeta *const m = A.m;
+    const DevParams &P = A.P;
     extern __shared__ __attribute__((aligned(16))) char s_raw[];
     float4 *s_pts = (float4 *)s_raw;
-    float *s_ny = (float *)(s_pts + stage_cap);
-    float *s_nz = s_ny + knot_cap;
-    float *s_nx = s_nz + knot_cap;
-    int *s_tab = (int *)(s_nx + knot_cap); /* tab_slabs rows of YTB + 1 */
+    float *s_ny = (float *)(s_pts + A.stage_cap);
+    float *s_nz = s_ny + A.knot_cap;
+    float *s_nx = s_nz + A.knot_cap;
+    int *s_tab = (int *)(s_nx + A.knot_cap); /* tab_slabs rows of YTB + 1 */
     __shared__ int s_scan[17];
     __shared__ int s_mycnt, s_myoff, s_run;
     const int k = bx;
     const int nk = m->nkept;
     if (m->err || k >= nk) return;
     /* work was left for the arena passes but they were not launched: report, the host re-runs */
-    if (!arena_ran && (m->big_slabs > 0 || m->big_slices > 0)) { if (threadIdx.x == 0) atomicCAS(&m->err, 0, DERR_CAPACITY); return; }
+    if (!A.arena_ran && (m->big_slabs > 0 || m->big_slices > 0)) { if (threadIdx.x == 0) atomicCAS(&m->err, 0, DERR_CAPACITY); return; }
     /* Everything this workgroup will stage -- the slabs around its plane (widest symmetric range that fits), their y-bucket
        rows, the slice's knots -- is REQUESTED here, into registers, in as few dependent rounds as the data allow (plane and
        knot segment; slab offsets; then points, rows and knots together with the slices' waypoint counts): the trips from
        memory run beside each other and beside the bookkeeping below instead of one after the other. */
     const int s = k + m->first_kept;
-    const float Px = px[s];
-    const int st = node_start[s], mm = node_cnt[s];
+    const float Px = A.px[s];
+    const int st = A.node_start[s], mm = A.node_cnt[s];
     const int first_kept = m->first_kept, sb = m->sb, se = m->se;
     int c2_first = 0; /* waypoint count of slice threadIdx.x (the first chunk of the scan below) */
-    if (slice_wpcnt && (int)threadIdx.x < nk) {
+    if (A.slice_wpcnt && (int)threadIdx.x < nk) {
         const int s2 = (int)threadIdx.x + first_kept;
-        if (s2 >= sb && s2 < se) c2_first = slice_wpcnt[s2];
+        if (s2 >= sb && s2 < se) c2_first = A.slice_wpcnt[s2];
     }
-    int bL = slab_of(m, Px - pad), bR = slab_of(m, Px + pad);
-    while (slab_start[bR + 1] - slab_start[bL] > stage_cap && bL < bR) {
+    int bL = slab_of(m, Px - A.pose_pad), bR = slab_of(m, Px + A.pose_pad);
+    while (A.slab_start[bR + 1] - A.slab_start[bL] > A.stage_cap && bL < bR) {
         const int bc = slab_of(m, Px);
         if (bR - bc >= bc - bL) --bR; else ++bL;
     }
-    int lds_lo = slab_start[bL], lds_hi = slab_start[bR + 1];
-    if (lds_hi - lds_lo > stage_cap || ALIGNED) lds_hi = lds_lo; /* one over-full slab: no staging (nor for the other frame's index) */
+    int lds_lo = A.slab_start[bL], lds_hi = A.slab_start[bR + 1];
+    if (lds_hi - lds_lo > A.stage_cap || ALIGNED) lds_hi = lds_lo; /* one over-full slab: no staging (nor for the other frame's index) */
     float4 pre4[PRE > 0 ? PRE : 1];
 #pragma unroll
     for (int q = 0; q < PRE; ++q) {
         const int i = lds_lo + (int)threadIdx.x + q * (int)blockDim.x;
-        pre4[q] = i < lds_hi ? sorted4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        pre4[q] = i < lds_hi ? A.sorted4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const int *yt = ALIGNED ? back.ytab : ytab;
+    const int *yt = ALIGNED ? back.ytab : A.ytab;
     int tab_lo = 0, tab_hi = 0;
-    if (yt && lds_hi > lds_lo && bR - bL + 1 <= tab_slabs) { tab_lo = bL; tab_hi = bR + 1; }
+    if (yt && lds_hi > lds_lo && bR - bL + 1 <= A.tab_slabs) { tab_lo = bL; tab_hi = bR + 1; }
     const int tab_n = (tab_hi - tab_lo) * (YTB + 1);
     constexpr int TPRE = PRE > 0 ? 2 : 0, KPRE = PRE > 0 ? 2 : 0;
     int tpre[TPRE > 0 ? TPRE : 1];
@@ -2182,13 +2207,13 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
         const int i = (int)threadIdx.x + q * (int)blockDim.x;
         tpre[q] = i < tab_n ? yt[(size_t)tab_lo * (YTB + 1) + i] : 0;
     }
-    const bool nodes_in_lds = mm <= knot_cap;
+    const bool nodes_in_lds = mm <= A.knot_cap;
     float kpre[KPRE > 0 ? KPRE : 1][3];
 #pragma unroll
     for (int q = 0; q < KPRE; ++q) {
         const int i = (int)threadIdx.x + q * (int)blockDim.x;
         const bool in = nodes_in_lds && i < mm;
-        kpre[q][0] = in ? node_y[st + i] : 0.f; kpre[q][1] = in ? node_z[st + i] : 0.f; kpre[q][2] = in ? node_x[st + i] : 0.f;
+        kpre[q][0] = in ? A.node_y[st + i] : 0.f; kpre[q][1] = in ? A.node_z[st + i] : 0.f; kpre[q][2] = in ? A.node_x[st + i] : 0.f;
     }
     /* a9 bookkeeping (the former k_count launch): every workgroup scans the waypoint counts of ALL kept slices -- left by
        k_slice_kd, or recomputed here from two knots and a closed form each -- to know its own offset in the list and W */
@@ -2200,10 +2225,10 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
         if (k2 < nk) {
             const int s2 = k2 + first_kept;
             if (s2 >= sb && s2 < se) {
-                if (slice_wpcnt) c2 = base == 0 ? c2_first : slice_wpcnt[s2];
+                if (A.slice_wpcnt) c2 = base == 0 ? c2_first : A.slice_wpcnt[s2];
                 else {
-                    const int st2 = node_start[s2], mm2 = node_cnt[s2];
-                    if (mm2 >= 1) c2 = sample_count((double)node_y[st2], (double)node_y[st2 + mm2 - 1], P.trim, P.path_resolution, W_cap);
+                    const int st2 = A.node_start[s2], mm2 = A.node_cnt[s2];
+                    if (mm2 >= 1) c2 = sample_count((double)A.node_y[st2], (double)A.node_y[st2 + mm2 - 1], P.trim, P.path_resolution, A.W_cap);
                 }
             }
         }
@@ -2216,12 +2241,12 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
         __syncthreads();
     }
     const int W = s_run, cnt = s_mycnt, off = s_myoff;
-    if (W > W_cap) { if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, -1); if (k == 0) m->W = 0; } return; }
+    if (W > A.W_cap) { if (threadIdx.x == 0) { set_err(m, DERR_CAPACITY, -1); if (k == 0) m->W = 0; } return; }
     if (threadIdx.x == 0) {
-        wp_cnt[k] = cnt; wp_off[k] = off;
-        tail[k] = off + cnt - 1; /* TailIndex.push_back(WayPointsList.size()-1) */
+        A.wp_cnt[k] = cnt; A.wp_off[k] = off;
+        A.tail[k] = off + cnt - 1; /* TailIndex.push_back(WayPointsList.size()-1) */
         if (P.rpy_resolution > 2 && cnt <= (int)P.rpy_resolution) m->any_short = 1;
-        if (k == 0) { m->W = W; wp_off[nk] = W; }
+        if (k == 0) { m->W = W; A.wp_off[nk] = W; }
     }
     if (W == 0 || cnt == 0) return;
     STAMP_BEGIN();
@@ -2231,7 +2256,7 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
         const int i = lds_lo + (int)threadIdx.x + q * (int)blockDim.x;
         if (i < lds_hi) s_pts[i - lds_lo] = pre4[q];
     }
-    for (int i = lds_lo + (int)threadIdx.x + PRE * (int)blockDim.x; i < lds_hi; i += blockDim.x) s_pts[i - lds_lo] = sorted4[i];
+    for (int i = lds_lo + (int)threadIdx.x + PRE * (int)blockDim.x; i < lds_hi; i += blockDim.x) s_pts[i - lds_lo] = A.sorted4[i];
 #pragma unroll
     for (int q = 0; q < TPRE; ++q) {
         const int i = (int)threadIdx.x + q * (int)blockDim.x;
@@ -2244,15 +2269,15 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
             const int i = (int)threadIdx.x + q * (int)blockDim.x;
             if (i < mm) { s_ny[i] = kpre[q][0]; s_nz[i] = kpre[q][1]; s_nx[i] = kpre[q][2]; }
         }
-        for (int i = (int)threadIdx.x + KPRE * (int)blockDim.x; i < mm; i += blockDim.x) { s_ny[i] = node_y[st + i]; s_nz[i] = node_z[st + i]; s_nx[i] = node_x[st + i]; }
+        for (int i = (int)threadIdx.x + KPRE * (int)blockDim.x; i < mm; i += blockDim.x) { s_ny[i] = A.node_y[st + i]; s_nz[i] = A.node_z[st + i]; s_nx[i] = A.node_x[st + i]; }
     }
     __syncthreads();
     STAMP(1, 0); /* staging */
-    SlabView V{sorted4, slab_start, slab_xmin, slab_xmax, m, s_pts, lds_lo, lds_hi};
+    SlabView V{A.sorted4, A.slab_start, A.slab_xmin, A.slab_xmax, m, s_pts, lds_lo, lds_hi};
     V.ytab = yt; V.lds_tab = s_tab; V.tab_lo = tab_lo; V.tab_hi = tab_hi;
     if (ALIGNED) { V.sorted4 = back.sorted4; V.slab_start = back.slab_start; V.slab_xmin = back.slab_xmin; V.slab_xmax = back.slab_xmax; V.m = back.m; }
-    const float *ny = nodes_in_lds ? s_ny : node_y + st, *nz = nodes_in_lds ? s_nz : node_z + st;
-    const float *nx = nodes_in_lds ? s_nx : node_x + st; /* the plane x, or cloud x after the dynamic adjustment */
+    const float *ny = nodes_in_lds ? s_ny : A.node_y + st, *nz = nodes_in_lds ? s_nz : A.node_z + st;
+    const float *nx = nodes_in_lds ? s_nx : A.node_x + st; /* the plane x, or cloud x after the dynamic adjustment */
     auto Yf = [&](int i) { return (double)ny[i]; };
     auto Zf = [&](int i) { return (double)nz[i]; };
     auto Xf = [&](int i) { return (double)nx[i]; };
@@ -2311,10 +2336,10 @@ __device__ __forceinline__ void pose_body(DevMeta *m, const DevParams &P, const 
                 else { wp[0] = q.x; wp[1] = q.y; wp[2] = q.z; }
                 wp[3] = rpy[0]; wp[4] = rpy[1]; wp[5] = rpy[2];
                 handeye_apply(HE, P.handeye, wp);
-                wp_xyz[w] = q;
-                wp_nn[w] = id;
-                wp_normal[w] = make_float4(n4[0], n4[1], n4[2], n4[3]);
-                for (int d = 0; d < 6; ++d) wp_pre[6 * (size_t)w + d] = wp[d];
+                A.wp_xyz[w] = q;
+                A.wp_nn[w] = id;
+                A.wp_normal[w] = make_float4(n4[0], n4[1], n4[2], n4[3]);
+                for (int d = 0; d < 6; ++d) A.wp_pre[6 * (size_t)w + d] = wp[d];
             }
             STAMP(1, 4); /* pose + hand-eye */
         }
@@ -2619,10 +2644,10 @@ __device__ inline double smooth_rpow(double r, int k)
     return v;
 }
 
-__device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P, int W_cap, const float *__restrict__ wp_pre,
-                                                  float *wp_smooth, float *wp_out, const int *__restrict__ tail,
-                                                  float *dst2, int cap2, const int bx)
+__device__ __forceinline__ void smooth_solve_body(const SlabArgs &A, const int bx)
 {
+    DevMeta *const m = A.m;
+    const DevParams &P = A.P;
     __shared__ float s_x[3][SMF_M];
     __shared__ int s_tail[4096];
     __shared__ int s_last;
@@ -2648,15 +2673,15 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
     for (int l = threadIdx.x; l < SMF_M; l += blockDim.x) {
         const int g = base + l;
         const bool src = g >= 1 && g <= W - 2;
-        for (int j = 0; j < 3; ++j) s_x[j][l] = src ? wp_pre[6 * (size_t)g + j] : 0.f;
+        for (int j = 0; j < 3; ++j) s_x[j][l] = src ? A.wp_pre[6 * (size_t)g + j] : 0.f;
     }
     const bool in_order = P.rpy_resolution > 2 && m->any_short; /* App. B.6: overlapping segments, finished by one thread below */
-    const bool copy2 = dst2 != nullptr && W <= cap2;
-    if (dst2 != nullptr && W > cap2 && tile == 0 && threadIdx.x == 0) set_err(m, DERR_CAPACITY, -1);
+    const bool copy2 = A.out2 != nullptr && W <= A.out2_cap;
+    if (A.out2 != nullptr && W > A.out2_cap && tile == 0 && threadIdx.x == 0) set_err(m, DERR_CAPACITY, -1);
     /* TailIndex in LDS: every waypoint's segment search is then eight LDS reads instead of eight dependent trips to L2 */
-    const int *tl = tail;
+    const int *tl = A.tail;
     if (!in_order && P.rpy_resolution > 2 && m->nkept <= 4096) {
-        for (int i = threadIdx.x; i < m->nkept; i += blockDim.x) s_tail[i] = tail[i];
+        for (int i = threadIdx.x; i < m->nkept; i += blockDim.x) s_tail[i] = A.tail[i];
         tl = s_tail;
     }
     /* tiles within SMF_END waypoints of an end also need that end's homogeneous term: p at the end is a one-sided sum over
@@ -2669,9 +2694,9 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
         if (j < 3) {
             const int k = (lane & 31) + 1;
             const int gq = lane < 32 ? k : W - 1 - k;
-            double v = (gq >= 1 && gq <= W - 2) ? (double)wp_pre[6 * (size_t)gq + j] * smooth_rpow(r, k) : 0.0;
+            double v = (gq >= 1 && gq <= W - 2) ? (double)A.wp_pre[6 * (size_t)gq + j] * smooth_rpow(r, k) : 0.0;
             for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if ((lane & 31) == 0) s_e[lane >> 5][j] = (double)wp_pre[6 * (size_t)(lane < 32 ? 0 : W - 1) + j] - c * v;
+            if ((lane & 31) == 0) s_e[lane >> 5][j] = (double)A.wp_pre[6 * (size_t)(lane < 32 ? 0 : W - 1) + j] - c * v;
         }
     }
     __syncthreads();
@@ -2679,7 +2704,7 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
     if (g < W) {
 #pragma clang fp contract(on) /* the 65-tap filter and the flange offset: continuous output only (same text as win_finish_body, so a list finished from gathered blocks carries the same bits) */
         float p[6];
-        for (int d = 0; d < 6; ++d) p[d] = wp_pre[6 * (size_t)g + d];
+        for (int d = 0; d < 6; ++d) p[d] = A.wp_pre[6 * (size_t)g + d];
         if (solve) {
             const int l = g - base;
             double y[3];
@@ -2703,10 +2728,10 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
             }
             if (g >= 1 && g <= W - 2) { p[0] = (float)y[0]; p[1] = (float)y[1]; p[2] = (float)y[2]; } /* the ends stay what they are */
         }
-        for (int d = 0; d < 6; ++d) wp_smooth[6 * (size_t)g + d] = p[d];
-        if (!in_order) finish_one_waypoint(m, P, tl, wp_pre, g, p);
-        for (int d = 0; d < 6; ++d) wp_out[6 * (size_t)g + d] = p[d];
-        if (copy2 && !in_order) for (int d = 0; d < 6; ++d) dst2[6 * (size_t)g + d] = p[d];
+        for (int d = 0; d < 6; ++d) A.wp_smooth[6 * (size_t)g + d] = p[d];
+        if (!in_order) finish_one_waypoint(m, P, tl, A.wp_pre, g, p);
+        for (int d = 0; d < 6; ++d) A.wp_out[6 * (size_t)g + d] = p[d];
+        if (copy2 && !in_order) for (int d = 0; d < 6; ++d) A.out2[6 * (size_t)g + d] = p[d];
     }
     if (in_order) { /* the last tile to arrive finishes the whole list */
         __threadfence();
@@ -2715,10 +2740,10 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
         __syncthreads();
         if (s_last) {
             __threadfence();
-            if (threadIdx.x == 0) { finish_list_in_order(m, P, tail, wp_out); m->emit_ticket = 0; }
+            if (threadIdx.x == 0) { finish_list_in_order(m, P, A.tail, A.wp_out); m->emit_ticket = 0; }
             __threadfence();
             __syncthreads();
-            if (copy2) for (size_t i = threadIdx.x; i < 6 * (size_t)W; i += blockDim.x) dst2[i] = wp_out[i];
+            if (copy2) for (size_t i = threadIdx.x; i < 6 * (size_t)W; i += blockDim.x) A.out2[i] = A.wp_out[i];
         }
     }
     if (tile == 0 && threadIdx.x == 0) { m->sweeps = 0; m->smooth_done = 0; }
@@ -2726,60 +2751,28 @@ __device__ __forceinline__ void smooth_solve_body(DevMeta *m, const DevParams &P
 
 /* ------------------------------------------------------------------ */
 /* Launch forms of the pipeline kernels.                                 */
-/* Single: one cloud per launch, blockIdx.x = workgroup.                 */
+/* Single: one cloud per launch, blockIdx.x = workgroup, the handle's    */
+/* SlabArgs record by value.                                             */
 /* Batched (BASELINE config 3: many small workpieces on ONE GPU): the    */
 /* same bodies over ALL members of a batch in one launch per stage --    */
 /* blockIdx.y = member, blockIdx.x = that member's workgroup; a member   */
 /* with fewer workgroups than the widest one leaves its surplus at once. */
-/* Every member is described by a BatchMember record in device memory    */
-/* (its handle's buffers, sizes and per-stage grids), read through a     */
-/* uniform address (scalar loads).                                       */
+/* Every member is described by its SlabArgs record in device memory,    */
+/* read through a uniform address (scalar loads).                        */
 /* ------------------------------------------------------------------ */
-struct BatchMember {
-    DevMeta *m;
-    DevParams P;
-    const float *X, *Y, *Z;
-    int n;
-    MinMaxPart *mm_part;
-    float slab_x0, slab_invw, incl_lo, incl_hi;
-    int B, S_cap, slab_cap, capb, node_cap, W_cap, out2_cap, knot_cap, stage_cap, tab_slabs;
-    float pose_pad;
-    int g_minmax, g_scatter, g_sort, g_slice, g_pose, g_smooth; /* workgroups of this member per stage */
-    int *slab_cnt, *slab_start, *slab_cursor, *coarse_cursor;
-    float *px, *lo, *hi;
-    float4 *unsorted4, *sorted4;
-    float *slab_xmin, *slab_xmax;
-    int *big_slabs, *big_slices;
-    float *node_x, *node_y, *node_z;
-    int *node_start, *node_cnt, *band_cnt;
-    int *wp_cnt, *wp_off, *tail;
-    float4 *wp_xyz, *wp_normal;
-    int *wp_nn;
-    float *wp_pre, *wp_smooth, *wp_out, *out2;
-    int *ytab, *slice_wpcnt;
-};
-
-PPP_KERNEL void __launch_bounds__(SETUP_T) k_setup(DevMeta *m, DevParams P, const MinMaxPart *__restrict__ part, int nparts,
-                                               float *px, float *lo, float *hi, int S_cap, int B, int *slab_cnt, float slab_x0,
-                                               float slab_invw, int *slab_start, int *slab_cursor, int *coarse_cursor)
-{
-    setup_body(m, P, part, nparts, px, lo, hi, S_cap, B, slab_cnt, slab_x0, slab_invw, slab_start, slab_cursor, coarse_cursor);
-}
+PPP_KERNEL void __launch_bounds__(SETUP_T) k_setup(SlabArgs A) { setup_body(A, true); }
 /* The one-level scatter with k_setup folded into its launch (clouds below the two-pass size: one launch and ~7 us less per
-   pass).  Workgroup `nscat` (one past the scatter workgroups) is the set-up workgroup: bounds, walk, band limits, CSR offsets
+   pass).  Workgroup g_scatter (one past the scatter workgroups) is the set-up workgroup: bounds, walk, band limits, CSR offsets
    and the meta block for the kernels that follow.  The scatter workgroups do not wait for it: each scans the slab histogram
    for itself in LDS (B <= 4096 counts: a microsecond) and reserves its runs on zero-based per-slab cursors (cleared by
-   k_minmax); the slab grid and the kept interval come as arguments instead of from the meta block. */
-struct ScatGrid { float x0, invw, xlo, xhi; int B; };
+   k_minmax); the slab grid and the kept interval come from the record instead of from the meta block. */
 template <int PPT>
-__device__ __forceinline__ void slab_scatter_fused_body(const float *__restrict__ X, const float *__restrict__ Y,
-                                                        const float *__restrict__ Z, int n, const ScatGrid &G,
-                                                        const int *__restrict__ slab_cnt, int *cursor, float4 *out4,
-                                                        const int *__restrict__ idmap, const int bx)
+__device__ __forceinline__ void scatter_setup_body(const SlabArgs &A, const int bx)
 {
+    if (bx == A.g_scatter) { setup_body(A, false); return; }
     extern __shared__ __attribute__((aligned(16))) int s_hist[];
     __shared__ int s_scan[17];
-    const int B = G.B;
+    const int B = A.B, n = A.n;
     int *s_start = s_hist + B;
     const int i0 = bx * (PPT * (int)blockDim.x);
     float4 p[PPT];
@@ -2788,10 +2781,10 @@ __device__ __forceinline__ void slab_scatter_fused_body(const float *__restrict_
     for (int k = 0; k < PPT; ++k) {
         const int i = i0 + threadIdx.x + k * (int)blockDim.x;
         pb[k] = -1;
-        if (i < n) p[k] = make_float4(X[i], Y[i], Z[i], __int_as_float(idmap ? idmap[i] : i));
+        if (i < n) p[k] = make_float4(A.X[i], A.Y[i], A.Z[i], __int_as_float(A.idmap ? A.idmap[i] : i));
         else p[k] = make_float4(NAN, 0.f, 0.f, 0.f);
     }
-    for (int b = threadIdx.x; b < B; b += blockDim.x) { s_hist[b] = 0; s_start[b] = slab_cnt[b]; }
+    for (int b = threadIdx.x; b < B; b += blockDim.x) { s_hist[b] = 0; s_start[b] = A.slab_cnt[b]; }
     __syncthreads();
     {   /* exclusive scan of the histogram: this workgroup's own copy of slab_start */
         const int per = (B + blockDim.x - 1) / blockDim.x;
@@ -2805,138 +2798,82 @@ __device__ __forceinline__ void slab_scatter_fused_body(const float *__restrict_
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const float x = p[k].x;
-        if (x >= G.xlo && x <= G.xhi) { pb[k] = slab_of_grid(x, G.x0, G.invw, B); atomicAdd(&s_hist[pb[k]], 1); } /* NaN fails both */
+        if (x >= A.P.incl_lo && x <= A.P.incl_hi) { pb[k] = slab_of_grid(x, A.slab_x0, A.slab_invw, B); atomicAdd(&s_hist[pb[k]], 1); } /* NaN fails both */
     }
     __syncthreads();
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         const int c = s_hist[b];
-        if (c) s_hist[b] = s_start[b] + atomicAdd(&cursor[b], c);
+        if (c) s_hist[b] = s_start[b] + atomicAdd(&A.slab_cursor[b], c);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < PPT; ++k)
-        if (pb[k] >= 0) out4[atomicAdd(&s_hist[pb[k]], 1)] = p[k];
+        if (pb[k] >= 0) A.unsorted4[atomicAdd(&s_hist[pb[k]], 1)] = p[k];
 }
-template <int PPT>
-__global__ void __launch_bounds__(SCAT_T) k_scatter_setup(const float *__restrict__ X, const float *__restrict__ Y,
-                                                          const float *__restrict__ Z, int n, ScatGrid G, int *slab_cnt, int *cursor,
-                                                          float4 *out4, const int *idmap, int nscat,
-                                                          DevMeta *m, DevParams P, const MinMaxPart *__restrict__ part, int nparts, float *px,
-                                                          float *lo, float *hi, int S_cap, int *slab_start)
+template <int PPT> __global__ void __launch_bounds__(SCAT_T) k_scatter_setup(SlabArgs A) { scatter_setup_body<PPT>(A, blockIdx.x); }
+template <int LEVEL, int PPT> __global__ void __launch_bounds__(SCAT_T) k_slab_scatter(SlabArgs A) { slab_scatter_body<LEVEL, PPT>(A, blockIdx.x); }
+/* (a slice-range handle launches only the g_sort slabs of its interval, from first_slab on; the arena pass walks the work list) */
+template <bool ARENA> __global__ void __launch_bounds__(SORT_T) k_slab_sort(SlabArgs A)
 {
-    if ((int)blockIdx.x == nscat) {
-        setup_body(m, P, part, nparts, px, lo, hi, S_cap, G.B, slab_cnt, G.x0, G.invw, slab_start, nullptr, nullptr, false);
-        return;
-    }
-    slab_scatter_fused_body<PPT>(X, Y, Z, n, G, slab_cnt, cursor, out4, idmap, blockIdx.x);
+    slab_sort_body<ARENA>(A, ARENA ? (int)blockIdx.x : A.first_slab + (int)blockIdx.x);
 }
-template <int LEVEL, int PPT>
-__global__ void __launch_bounds__(SCAT_T) k_slab_scatter(const float *__restrict__ X, const float *__restrict__ Y,
-                                                      const float *__restrict__ Z, const float4 *__restrict__ in4, int n,
-                                                      const DevMeta *m, int *cursor, float4 *out4, const int *idmap)
+/* The body reads the record where it lies, in the kernel-argument segment (a kernel's first argument sits at offset 0 of it), so
+   that every field is fetched where it is used, as the batched form does from its array.  Through `A` the compiler fetches all
+   of them on entry and holds the knot arrays, the sampling constants and the counters -- needed on the kernel's last lines --
+   in 22 SGPRs across both sorts: 102 SGPRs and a wave less per SIMD than the loose arguments had (92); this way 81. */
+template <bool ARENA> __global__ void __launch_bounds__(SLICE_KD_T) k_slice_kd(SlabArgs A)
 {
-    slab_scatter_body<LEVEL, PPT>(X, Y, Z, in4, n, m, cursor, out4, idmap, blockIdx.x);
-}
-template <bool ARENA>
-__global__ void __launch_bounds__(SORT_T) k_slab_sort(const float4 *__restrict__ unsorted4, const int *__restrict__ slab_start,
-                                                   float4 *sorted4, float *slab_xmin, float *slab_xmax, DevMeta *m, int cap,
-                                                   int *big_list, char *arena, unsigned long long arena_cap, int *ytab, int first_slab,
-                                                   int *slab_cnt)
-{
-    slab_sort_body<ARENA>(unsorted4, slab_start, sorted4, slab_xmin, slab_xmax, m, cap, big_list, arena, arena_cap, ytab, slab_cnt,
-                          ARENA ? (int)blockIdx.x : first_slab + (int)blockIdx.x);
-}
-template <bool ARENA>
-__global__ void __launch_bounds__(SLICE_KD_T) k_slice_kd(const float4 *__restrict__ sorted4, const int *__restrict__ slab_start,
-                                                  DevMeta *m, const float *__restrict__ px, const float *__restrict__ lo,
-                                                  const float *__restrict__ hi, int capb_lds, float *node_x, float *node_y,
-                                                  float *node_z, int node_cap, int *node_start, int *node_cnt, int *band_cnt, int *big_list,
-                                                  char *arena, unsigned long long arena_cap, double trim, double res, int W_cap, int *slice_wpcnt)
-{
-    slice_kd_body<ARENA>(sorted4, slab_start, m, px, lo, hi, capb_lds, node_x, node_y, node_z, node_cap, node_start, node_cnt, band_cnt,
-                         big_list, arena, arena_cap, trim, res, W_cap, slice_wpcnt, blockIdx.x);
+    slice_kd_body<ARENA>(*(const SlabArgs *)__builtin_amdgcn_kernarg_segment_ptr(), blockIdx.x);
 }
 /* TMAX: the most threads a launch uses (256, 512 or POSE_T): the register budget follows from it -- the 1024-thread form is
    held to 128 VGPRs and spills a few values, the smaller forms are not */
-template <bool ALIGNED, int TMAX>
-__global__ void __launch_bounds__(TMAX) k_pose(DevMeta *m, DevParams P, const float4 *__restrict__ sorted4,
-                                              const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
-                                              const float *__restrict__ slab_xmax, const float *__restrict__ px,
-                                              const float *__restrict__ node_x, const float *__restrict__ node_y,
-                                              const float *__restrict__ node_z,
-                                              const int *__restrict__ node_start, const int *__restrict__ node_cnt,
-                                              int *wp_cnt, int *wp_off, int *tail, int W_cap, int arena_ran, int knot_cap, int stage_cap,
-                                              int tab_slabs, float pad, float4 *wp_xyz, int *wp_nn, float4 *wp_normal, float *wp_pre, PoseBack back, const int *ytab,
-                                              const int *slice_wpcnt)
+template <bool ALIGNED, int TMAX> __global__ void __launch_bounds__(TMAX) k_pose(SlabArgs A, PoseBack back)
 {
-    pose_body<ALIGNED, (TMAX <= 768 ? POSE_PRE : 0)>(m, P, sorted4, slab_start, slab_xmin, slab_xmax, px, node_x, node_y, node_z, node_start, node_cnt, wp_cnt, wp_off,
-                       tail, W_cap, arena_ran, knot_cap, stage_cap, tab_slabs, pad, wp_xyz, wp_nn, wp_normal, wp_pre, back, ytab, slice_wpcnt, blockIdx.x);
+    pose_body<ALIGNED, (TMAX <= 768 ? POSE_PRE : 0)>(A, back, blockIdx.x);
 }
-PPP_KERNEL void __launch_bounds__(SMF_T) k_smooth_solve(DevMeta *m, DevParams P, int W_cap, const float *__restrict__ wp_pre,
-                                                        float *wp_smooth, float *wp_out, const int *__restrict__ tail,
-                                                        float *dst2, int cap2)
-{
-    smooth_solve_body(m, P, W_cap, wp_pre, wp_smooth, wp_out, tail, dst2, cap2, blockIdx.x);
-}
+PPP_KERNEL void __launch_bounds__(SMF_T) k_smooth_solve(SlabArgs A) { smooth_solve_body(A, blockIdx.x); }
 
-/* ---- batched forms ---- */
-PPP_KERNEL void __launch_bounds__(MM_T) k_minmax_b(const BatchMember *__restrict__ mem)
+/* ---- batched forms (batches are whole clouds on the LDS fast path: no first_slab, no arena, no sensor-frame index) ---- */
+PPP_KERNEL void __launch_bounds__(MM_T) k_minmax_b(const SlabArgs *__restrict__ mem)
 {
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x >= M.g_minmax) return;
-    minmax_body<true>(M.X, M.Y, M.Z, M.n, M.mm_part, M.slab_x0, M.slab_invw, M.B, M.slab_cnt, M.incl_lo, M.incl_hi, M.slab_cursor, blockIdx.x, M.g_minmax);
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x >= A.g_minmax) return;
+    minmax_body<true>(A.X, A.Y, A.Z, A.n, A.mm_part, A.slab_x0, A.slab_invw, A.B, A.slab_cnt, A.P.incl_lo, A.P.incl_hi, A.slab_cursor, blockIdx.x, A.g_minmax);
 }
-PPP_KERNEL void __launch_bounds__(SETUP_T) k_setup_b(const BatchMember *__restrict__ mem)
-{
-    const BatchMember &M = mem[blockIdx.y];
-    setup_body(M.m, M.P, M.mm_part, M.g_minmax, M.px, M.lo, M.hi, M.S_cap, M.B, M.slab_cnt, M.slab_x0, M.slab_invw, M.slab_start,
-               M.slab_cursor, M.coarse_cursor);
-}
-template <int PPT>
-__global__ void __launch_bounds__(SCAT_T) k_slab_scatter_b(const BatchMember *__restrict__ mem)
+template <int PPT> __global__ void __launch_bounds__(SCAT_T) k_slab_scatter_b(const SlabArgs *__restrict__ mem)
 {   /* the fused form (k_scatter_setup): workgroup g_scatter of every member is its set-up workgroup */
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x > M.g_scatter) return;
-    ScatGrid G;
-    G.x0 = M.slab_x0; G.invw = M.slab_invw; G.xlo = M.incl_lo; G.xhi = M.incl_hi; G.B = M.B;
-    if ((int)blockIdx.x == M.g_scatter) {
-        setup_body(M.m, M.P, M.mm_part, M.g_minmax, M.px, M.lo, M.hi, M.S_cap, M.B, M.slab_cnt, M.slab_x0, M.slab_invw, M.slab_start,
-                   nullptr, nullptr, false);
-        return;
-    }
-    slab_scatter_fused_body<PPT>(M.X, M.Y, M.Z, M.n, G, M.slab_cnt, M.slab_cursor, M.unsorted4, nullptr, blockIdx.x);
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x > A.g_scatter) return;
+    scatter_setup_body<PPT>(A, blockIdx.x);
 }
-PPP_KERNEL void __launch_bounds__(SORT_T) k_slab_sort_b(const BatchMember *__restrict__ mem)
+PPP_KERNEL void __launch_bounds__(SORT_T) k_slab_sort_b(const SlabArgs *__restrict__ mem)
 {
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x >= M.g_sort) return;
-    slab_sort_body<false>(M.unsorted4, M.slab_start, M.sorted4, M.slab_xmin, M.slab_xmax, M.m, M.slab_cap, M.big_slabs, nullptr, 0ull, M.ytab, M.slab_cnt, blockIdx.x);
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x >= A.g_sort) return;
+    slab_sort_body<false>(A, blockIdx.x);
 }
-PPP_KERNEL void __launch_bounds__(SLICE_KD_T) k_slice_kd_b(const BatchMember *__restrict__ mem)
+PPP_KERNEL void __launch_bounds__(SLICE_KD_T) k_slice_kd_b(const SlabArgs *__restrict__ mem)
 {
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x >= M.g_slice) return;
-    slice_kd_body<false>(M.sorted4, M.slab_start, M.m, M.px, M.lo, M.hi, M.capb, M.node_x, M.node_y, M.node_z, M.node_cap, M.node_start,
-                         M.node_cnt, M.band_cnt, M.big_slices, nullptr, 0ull, M.P.trim, M.P.path_resolution, M.W_cap, M.slice_wpcnt, blockIdx.x);
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x >= A.g_slice) return;
+    slice_kd_body<false>(A, blockIdx.x);
 }
-template <int TMAX>
-__global__ void __launch_bounds__(TMAX) k_pose_b(const BatchMember *__restrict__ mem)
+template <int TMAX> __global__ void __launch_bounds__(TMAX) k_pose_b(const SlabArgs *__restrict__ mem)
 {
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x >= M.g_pose) return;
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x >= A.g_pose) return;
     PoseBack none;
     none.sorted4 = nullptr; none.slab_start = nullptr; none.slab_xmin = nullptr; none.slab_xmax = nullptr; none.m = nullptr; none.ytab = nullptr;
-    pose_body<false, (TMAX <= 768 ? POSE_PRE : 0)>(M.m, M.P, M.sorted4, M.slab_start, M.slab_xmin, M.slab_xmax, M.px, M.node_x, M.node_y, M.node_z, M.node_start, M.node_cnt,
-                     M.wp_cnt, M.wp_off, M.tail, M.W_cap, 0, M.knot_cap, M.stage_cap, M.tab_slabs, M.pose_pad, M.wp_xyz, M.wp_nn, M.wp_normal, M.wp_pre, none, M.ytab, M.slice_wpcnt, blockIdx.x);
+    pose_body<false, (TMAX <= 768 ? POSE_PRE : 0)>(A, none, blockIdx.x);
 }
-PPP_KERNEL void __launch_bounds__(SMF_T) k_smooth_solve_b(const BatchMember *__restrict__ mem)
+PPP_KERNEL void __launch_bounds__(SMF_T) k_smooth_solve_b(const SlabArgs *__restrict__ mem)
 {
-    const BatchMember &M = mem[blockIdx.y];
-    if ((int)blockIdx.x >= M.g_smooth) return;
-    smooth_solve_body(M.m, M.P, M.W_cap, M.wp_pre, M.wp_smooth, M.wp_out, M.tail, M.out2, M.out2_cap, blockIdx.x);
+    const SlabArgs &A = mem[blockIdx.y];
+    if ((int)blockIdx.x >= A.g_smooth) return;
+    smooth_solve_body(A, blockIdx.x);
 }
 /* the members' meta blocks side by side, so that ONE copy publishes the batch to the host */
-PPP_KERNEL void __launch_bounds__(64) k_collect_meta(const BatchMember *__restrict__ mem, int count, DevMeta *out)
+PPP_KERNEL void __launch_bounds__(64) k_collect_meta(const SlabArgs *__restrict__ mem, int count, DevMeta *out)
 {
     const int i = blockIdx.x;
     if (i >= count) return;

@@ -1265,6 +1265,31 @@ def test_batched_launches_random_members_match_single_handles(engine_mod):
                 assert got.tobytes() == np.concatenate(good).tobytes()
 
 
+def test_batched_member_with_a_given_part_keeps_its_index_map(engine_mod):
+    """A member fed through ppp_set_cloud_part (all slices, the cloud in another order with its cloud indices) is one launch
+    record for its own launches and for the batched ones: the nearest-point stage carries CLOUD indices either way, the ones a
+    handle holding the cloud in its own order finds."""
+    pts, cfg = synth.make_config("small_40k")
+    scaled = (pts * np.float32(1000)).astype(np.float32)
+    mn, mx = scaled.min(axis=0), scaled.max(axis=0)
+    perm = np.random.default_rng(5).permutation(len(pts))
+    ref = engine_mod.Engine(0, tool_radius=6.0, fast_path=False); ref.set_cloud(pts); ref.gen_path(); ref.get_path()
+    want_nn, want = ref.stage(engine_mod.STAGE_WP_NN), ref.waypoints()
+    engines = []
+    for _ in range(3):
+        g = engine_mod.Engine(0, tool_radius=6.0, fast_path=False)
+        lo, hi, _ = g.range_interval(mn[0], mx[0])
+        g.set_cloud_part(pts[perm], perm, mn, mx, len(pts), lo, hi)
+        g.gen_path(); g.get_path()
+        assert np.array_equal(g.stage(engine_mod.STAGE_WP_NN), want_nn)      # its own launches
+        engines.append(g)
+    for _ in range(2):                                                       # capture + replay
+        engine_mod.run_batch_async(engines); engine_mod.sync_batch(engines)
+        for g in engines:
+            assert np.array_equal(g.stage(engine_mod.STAGE_WP_NN), want_nn)  # the batched launches
+            assert g.waypoints().tobytes() == want.tobytes()
+
+
 def test_batch_member_that_overflows_lds_lands_in_the_batch_buffer(engine_mod, oracle_mod):
     """A member whose bands do not fit the LDS fast path is re-planned with the arena passes by ppp_sync_batch: the
     re-planned list must also reach that member's rows of the batch destination (the RCCL send buffer)."""
