@@ -13,6 +13,8 @@
 #include "ppp_kernels.h"
 
 #define DYN_KNN_CAP 448   /* candidates a wave keeps while growing the search radius */
+#define DYN_KNN_TRIES 128 /* search radii a query may try: 48 of growing reach 2.8e8 r0, a bisection ends by itself within 32 more; a search
+                             that can never have k points ends here with none (its radius may have become infinite: the casts are clamped) */
 #ifndef DYN_WAVES
 #define DYN_WAVES 4       /* waves (= Area2Cloud evaluations) per workgroup; 1, 2, 4 measure the same, 8 slower */
 #endif
@@ -47,17 +49,17 @@ __device__ inline DynGrid dyn_grid(const DevMeta *m)
     G.B = m->B; G.total = m->n_sorted; G.x0 = m->slab_x0; G.invw = m->slab_invw; G.y0 = m->mn[1]; G.ysc = m->ytab_scale;
     return G;
 }
+/* (clamped as floats, then cast: the same slab / bucket for every value the cast can take, and a defined one for those it
+   cannot -- a search radius that has grown past the grid by twenty orders of magnitude, an infinite one, a NaN) */
 __device__ inline int dyn_slab_of(const DynGrid &G, float x)
 {
-    int b = (int)((x - G.x0) * G.invw);
-    b = b < 0 ? 0 : b;
-    return b >= G.B ? G.B - 1 : b;
+    const float t = (x - G.x0) * G.invw;
+    return (int)fminf(fmaxf(t, 0.f), (float)(G.B - 1));
 }
 __device__ inline int dyn_ybucket(const DynGrid &G, float y)
 {
-    int q = (int)((y - G.y0) * G.ysc);
-    q = q < 0 ? 0 : q;
-    return q >= YTB ? YTB - 1 : q;
+    const float t = (y - G.y0) * G.ysc;
+    return (int)fminf(fmaxf(t, 0.f), (float)(YTB - 1));
 }
 /* The ranking of wave_knn: the `count` candidates in L.key / L.dk / L.pos ordered by (distance, cloud index); the first kk of
    them go to L.sel / L.sel_id / L.sel_slot.  The writes of the candidates are visible (barrier + fence) before the call, and
@@ -131,8 +133,15 @@ __device__ inline int wave_knn(const SlabView &V, const DynGrid &G, DynWaveLds &
     const int B = G.B;
     const int total = G.total;
     float r = r0;
+    /* The radius schedule: a ball with at least k and at most DYN_KNN_CAP points is wanted.  Until a radius has
+       failed on either side the radius is multiplied (x 1.5 after too few, x 0.8 after too many); from then on the count is
+       known below k at r_few and above the capacity at r_many, the count is monotone in r, and the interval is bisected --
+       however narrow the window of good radii is (a query 300 mm above a sheet: 0.5 mm), it is found while it holds one
+       float.  Where it holds none (more than DYN_KNN_CAP - k points at the k-th distance) the search has no answer. */
+    float r_few = 0.f, r_many = 0.f; /* 0: none yet */
     int count = 0;
-    for (int attempt = 0; attempt < 48; ++attempt) {
+    int attempt = 0;
+    for (; attempt < DYN_KNN_TRIES; ++attempt) {
         const float r2 = r * r;
         count = 0;
         bool overflow = false;
@@ -214,10 +223,16 @@ __device__ inline int wave_knn(const SlabView &V, const DynGrid &G, DynWaveLds &
                 }
             }
         }
-        if (overflow) { r *= 0.8f; continue; }
-        if (count >= k || count >= total) break;
-        r *= 1.5f;
+        if (!overflow && (count >= k || count >= total)) break;
+        if (overflow) r_many = r; else r_few = r;
+        if (r_few > 0.f && r_many > 0.f) {
+            r = 0.5f * (r_few + r_many);
+            if (!(r > r_few && r < r_many)) { attempt = DYN_KNN_TRIES; break; } /* neighbouring floats: no radius between them */
+        } else
+            r *= overflow ? 0.8f : 1.5f;
     }
+    /* no radius found: the query has no neighbours (never more candidates than the arrays hold, never fewer than exist) */
+    if (attempt >= DYN_KNN_TRIES) count = 0;
     __builtin_amdgcn_wave_barrier();
     __threadfence_block();
     sc.mark(2);

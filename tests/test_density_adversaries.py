@@ -1,0 +1,608 @@
+"""The neighbour searches on clouds that are not a uniform sheet.
+
+Every other cloud of the suite is one sheet on a jittered 1.5 mm grid (synth.make_plate): the k-NN search of the contact model
+(wave_knn) accepts its first or second radius there, the normal kernels never fill their neighbour lists.  The
+two clouds built here take the other branches:
+
+FAR    tiny_5k, 40 of its points copied and moved 40 .. 400 mm off the sheet along z (either sign), and a "fixture": a 12 x 12
+       patch at 1.5 mm spacing, 120 mm lower than the sheet and 380 mm beside it in y.  (Directly underneath, the fixture would
+       be the nearest 144 neighbours of every point moved downwards, and the window condition below could not hold: 55 % instead
+       of 97.5 % of the lifted points.)  A query at height D over a sheet of density rho holds rho pi (r^2 - D^2) points in its
+       ball, so the radii with at least k and at most DYN_KNN_CAP points are [sqrt(D^2 + k / rho pi), sqrt(D^2 + 448 / rho pi)]:
+       0.5 mm wide at D = 300 mm.  A schedule that multiplies the radius steps over it.  (The fixture beside the sheet also widens
+       the xy bounding box that dyn_params' mean density is taken over: the first radius at k = 50 is 17.5 mm instead of the
+       7.3 mm of tiny_5k alone, and a point of the sheet holds some 420 points in it, just under the capacity.)
+BARE   FAR without its 40 lifted points.  A lifted point has no normal (fewer than three points within normal_radius), and one
+       of them is among the k nearest of nearly every query further than 60 mm from the sheet: on FAR the oracle's answer to
+       such a query is NaN, and what a test compares there is the PLACE of the NaNs.  On BARE every query has a finite answer,
+       and the same queries compare the VALUES behind a bisected radius.
+PATCH  make_plate(80, 40, "wavy", amp=8) with a 20 x 20 mm hole and a 30 x 20 mm patch at 0.4 mm spacing on the same surface:
+       more than DYN_KNN_CAP points inside the first search radius, more than NRM_CAP points inside normal_radius.
+
+The CPU tests show from the oracle, numpy and scipy alone that the clouds are the adversaries they claim to be; the GPU tests
+compare the engine with the oracle and the existing restatements: bit equality, or the waypoint list's 1e-4 m / 1e-4 rad."""
+import numpy as np
+import pytest
+from scipy.spatial import cKDTree
+
+from polishpathplanning_amd import synth
+from test_contact_field import NAN_CAP, bits, check_stats, flann_dist2, restate_field
+from test_coverage import V1 as V1_CONTACT, restate_coverage
+from test_path_contacts import check_stats as check_contact_stats, restate_path_contacts
+from test_path_coverage import restate_path_coverage
+from test_regions import MASK, assert_same, restate_regions
+
+DYN_KNN_CAP = 448   # ppp_dynamic.h:15   #define DYN_KNN_CAP 448: candidates a wave keeps while it looks for the search radius
+NRM_CAP = 48        # ppp_kernels.h:1828 #define NRM_CAP 48: neighbour list of a waypoint normal (rescan beyond it, :1896)
+NRM_LDS_CAP = 12    # ppp_kernels.h:2374 #define NRM_LDS_CAP 12: neighbour list of k_normals_all in LDS
+OLD_TRIES = 48      # attempts of the radius schedule this module was written against (x 1.5 after too few, x 0.8 after too many)
+
+TOL_M = 1e-4        # test_gpu_parity.TOL_M / TOL_RAD: the project's list tolerance
+TOL_RAD = 1e-4
+FAR_SEED = 0
+PATCH_SEED = 0
+N_BASE, N_LIFT = 5000, 40
+DISPLACEMENTS_MM = (0, 5, 30, 60, 90, 100, 150, 200, 300, 500)
+PASSED_OVER = 37    # candidates far_queries passes over for equal distances, for the 300 it keeps
+R_FAR, R_PATCH = 6.0, 4.0   # PATCH at tool_radius 4: 15 slices (at 6: S = 9, W = 42)
+
+
+# ---------------------------------------------------------------- the clouds
+
+
+def far_cloud():
+    """float32 [5184, 3] in metres: rows [0, 5000) tiny_5k, [5000, 5040) the lifted copies, [5040, 5184) the fixture"""
+    base, _ = synth.make_config("tiny_5k")
+    assert len(base) == N_BASE
+    rng = np.random.default_rng(FAR_SEED)
+    lift = base[rng.choice(N_BASE, N_LIFT, replace=False)].copy()
+    dz = rng.uniform(40.0, 400.0, N_LIFT) * rng.choice([-1.0, 1.0], N_LIFT)
+    lift[:, 2] = (lift[:, 2].astype(np.float64) + dz / 1000.0).astype(np.float32)
+    fixture = synth.make_plate(12, 12, kind="wavy", amp=8.0, seed=FAR_SEED + 1, x0_mm=60.0, z0_mm=synth.Z0_MM - 120.0)
+    fixture[:, 1] -= np.float32(0.380)
+    return np.ascontiguousarray(np.concatenate([base, lift, fixture]), np.float32)
+
+
+def bare_rows(a):
+    """the rows of BARE in an array over FAR's points"""
+    return np.ascontiguousarray(np.concatenate([a[:N_BASE], a[N_BASE + N_LIFT:]]))
+
+
+def nearest_have_equal_distances(q, P, k):
+    """the no-tie condition of test_contact_field: two of q's k + 1 nearest points of P at one float32 flann_dist2"""
+    d2 = flann_dist2(q, P)
+    return len(np.unique(np.partition(d2, k)[: k + 1])) != k + 1 or int((d2 <= np.partition(d2, k)[k]).sum()) != k + 1
+
+
+def far_queries(P):
+    """(300 off-surface queries, candidates passed over) in the resident unit (P = the resident FAR cloud, mm): points of the
+    sheet displaced along z by each of DISPLACEMENTS_MM, 15 up and 15 down.  The sheet points are taken in a seeded order; one
+    whose query would have two of its 51 nearest neighbours at one float32 distance, in FAR or in BARE, is passed over (the
+    oracle's order among equal distances is traversal-defined).  No seed could do without: at 500 mm the 51 squared distances
+    fall into some 2 300 floats.  37 candidates (PASSED_OVER) are passed over for the 300 kept (asserted below)."""
+    PB = bare_rows(P)
+    order = np.random.default_rng(FAR_SEED + 2).permutation(N_BASE)
+    out, at = [], 0
+    for D in DISPLACEMENTS_MM:
+        for sign in (1.0, -1.0):
+            have = 0
+            while have < 15:
+                q = P[order[at % N_BASE]].copy()
+                at += 1
+                q[2] = np.float32(np.float64(q[2]) + sign * D)
+                if nearest_have_equal_distances(q, P, 50) or nearest_have_equal_distances(q, PB, 50):
+                    continue
+                out.append(q)
+                have += 1
+    assert at < N_BASE                            # no point of the sheet serves twice
+    return np.ascontiguousarray(np.stack(out), np.float32), at - len(out)
+
+
+def patch_cloud():
+    """float32 [6769, 3] in metres, permuted: the plate without its hole, and the dense patch on the plate's surface"""
+    base = synth.make_plate(80, 40, kind="wavy", amp=8.0, seed=PATCH_SEED, permute=False).astype(np.float64) * 1000.0
+    hole = (base[:, 0] >= 20.0) & (base[:, 0] < 40.0) & (np.abs(base[:, 1]) < 10.0)
+    rng = np.random.default_rng(PATCH_SEED + 1)
+    gx, gy = np.meshgrid(70.0 + 0.4 * np.arange(75), -10.0 + 0.4 * np.arange(50), indexing="ij")
+    gx = gx + rng.uniform(-0.1, 0.1, gx.shape)
+    gy = gy + rng.uniform(-0.1, 0.1, gy.shape)
+    gz = synth._surface("wavy", gx, gy, 8.0) + synth.Z0_MM
+    cloud = np.concatenate([base[~hole], np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1)])
+    cloud = cloud[rng.permutation(len(cloud))]
+    return np.ascontiguousarray((cloud / 1000.0).astype(np.float32))
+
+
+def first_radius(P, k):
+    """dyn_params' r0 (ppp_engine.hip:601): k points of a sheet of the mean density over the xy bounding box, + 25 %"""
+    mn, mx = P.min(axis=0).astype(np.float64), P.max(axis=0).astype(np.float64)
+    rho = len(P) / ((mx[0] - mn[0]) * (mx[1] - mn[1]))
+    return np.float32(max(0.5, 1.25 * np.sqrt(k / (np.pi * rho))))
+
+
+def multiplying_schedule_settles(tree, q, k, r0, n):
+    """the radius schedule before the bisection, counts from scipy: True when some attempt holds k .. DYN_KNN_CAP points"""
+    r = np.float32(r0)
+    for _ in range(OLD_TRIES):
+        c = tree.query_ball_point(q.astype(np.float64), float(r), return_length=True)
+        if c > DYN_KNN_CAP:
+            r = np.float32(r * np.float32(0.8))
+        elif c >= k or c >= n:
+            return True
+        else:
+            r = np.float32(r * np.float32(1.5))
+    return False
+
+
+_cache = {}
+
+
+def shared(name, make):
+    """a cloud or an expectation computed once and shared by the tests that need it (they leave it unchanged)"""
+    if name not in _cache:
+        _cache[name] = make()
+    return _cache[name]
+
+
+def far_setup(oracle_mod):
+    """(pts in metres, resident points, queries)"""
+    def make():
+        pts = far_cloud()
+        o = oracle_mod.Oracle(pts, tool_radius=R_FAR)
+        P = o.points()
+        o.close()
+        Q, passed = far_queries(P)
+        _cache["passed over"] = passed
+        return pts, P, Q
+    return shared("far", make)
+
+
+def bare_finite_rows(oracle_mod, k):
+    """the oracle's curvature rows at the queries on BARE, and which of them are finite"""
+    def make():
+        pts, _, Q = far_setup(oracle_mod)
+        o = oracle_mod.Oracle(bare_rows(pts), tool_radius=R_FAR, curvature_k=k)
+        want = np.stack([o.principal_curvature(q) for q in Q])
+        o.close()
+        return want
+    want = shared(("bare curvature", k), make)
+    return want, np.isfinite(want).all(axis=1)
+
+
+def patch_setup(oracle_mod):
+    def make():
+        pts = patch_cloud()
+        o = oracle_mod.Oracle(pts, tool_radius=R_PATCH)
+        P = o.points()
+        o.close()
+        return pts, P
+    return shared("patch", make)
+
+
+def oracle_field(oracle_mod, name, pts, **kw):
+    """restate_field at every point of a cloud, once; the oracle's own NaN share is asserted before anything is compared"""
+    def make():
+        o = oracle_mod.Oracle(pts, **kw)
+        want = restate_field(o)
+        o.close()
+        return want
+    curv, hw = shared(("field", name), make)
+    assert np.isnan(hw).mean() <= NAN_CAP, (name, float(np.isnan(hw).mean()))
+    return curv, hw
+
+
+def window_ratio(tree, q, k):
+    """(449th-neighbour distance) / ((k + 1)-th): below 1.05 the window of good radii is narrower than any step x 1.5 or x 0.8"""
+    d, _ = tree.query(q.astype(np.float64), DYN_KNN_CAP + 1)
+    return d[:, DYN_KNN_CAP] / d[:, k]
+
+
+# ---------------------------------------------------------------- CPU: the inputs are the adversaries they claim to be
+
+
+def test_far_lifted_points_have_narrow_windows(oracle_mod):
+    pts, P, _ = far_setup(oracle_mod)
+    assert bits(P).tobytes() == bits(pts * np.float32(1000)).tobytes() and len(P) == N_BASE + N_LIFT + 144
+    tree = cKDTree(P.astype(np.float64))
+    lifted = P[N_BASE:N_BASE + N_LIFT]
+    share50 = float((window_ratio(tree, lifted, 50) < 1.05).mean())
+    share10 = float((window_ratio(tree, lifted, 10) < 1.05).mean())
+    print("lifted points with r449 / r51 < 1.05: %.3f; r449 / r11: %.3f" % (share50, share10))
+    assert share50 >= 0.90
+    assert share10 >= 0.20
+
+
+def test_far_queries_have_narrow_windows_and_the_multiplying_schedule_does_not_settle(oracle_mod):
+    """300 queries, both signs of every displacement; at least a third with a window ratio below 1.05.
+    The schedule that multiplied the radius (r0 of dyn_params, x 1.5 / x 0.8, 48 attempts; counts from scipy) ends without a
+    ball of k .. 448 points for 143 of the 300 queries at k = 50 and none at k = 10, and for 26 (mean_k 50) and 1 (mean_k 10) of
+    the cloud's own 184 lifted and fixture points as remove_outlier asks (k = mean_k + 1): it went on with fewer than k
+    neighbours, or with more candidates than its arrays hold.  On FAR the oracle's answer is NaN for all of those 143 queries (a
+    lifted point, which has no normal, is among their neighbours) and for the 24 cloud points the contact field loses (lifted
+    points themselves): there the GPU tests compare where the NaNs are, and remove_outlier compares the distances.  On BARE
+    the schedule loses 134 of the same 300 queries at k = 50 (none at k = 10) and the oracle's curvature is finite for every
+    one of them: those are the rows whose VALUES test_off_surface_queries_match_the_oracle[bare-50] would have failed."""
+    pts, P, Q = far_setup(oracle_mod)
+    assert Q.shape == (300, 3)
+    for j, q in enumerate(Q):                     # 30 per displacement, 15 up and then 15 down, each over a point of the sheet
+        D, sign = DISPLACEMENTS_MM[j // 30], (1.0 if j % 30 < 15 else -1.0)
+        src = np.nonzero((P[:N_BASE, 0] == q[0]) & (P[:N_BASE, 1] == q[1]))[0]
+        assert len(src) == 1 and abs(float(q[2]) - float(P[src[0], 2]) - sign * D) < 1e-3, j
+    tree = cKDTree(P.astype(np.float64))
+    narrow = float((window_ratio(tree, Q, 50) < 1.05).mean())
+    print("queries with r449 / r51 < 1.05: %.3f" % narrow)
+    assert narrow >= 1.0 / 3
+    lost = {k: sum(not multiplying_schedule_settles(tree, q, k, first_radius(P, k), len(P)) for q in Q) for k in (50, 10)}
+    lost_sor = {mk: sum(not multiplying_schedule_settles(tree, q, mk + 1, first_radius(P, mk + 1), len(P)) for q in P[N_BASE:])
+                for mk in (50, 10)}
+    print("multiplying schedule, queries that do not settle: %s of 300; remove_outlier's own: %s of %d" % (lost, lost_sor, len(P) - N_BASE))
+    assert lost[50] >= 30 and lost_sor[50] >= 1
+    PB = bare_rows(P)
+    tree_b = cKDTree(PB.astype(np.float64))
+    lost_b = np.array([not multiplying_schedule_settles(tree_b, q, 50, first_radius(PB, 50), len(PB)) for q in Q])
+    narrow_b = window_ratio(tree_b, Q, 50) < 1.05
+    for k in (50, 10):
+        want, finite = bare_finite_rows(oracle_mod, k)
+        print("BARE k=%d: finite curvature rows %d of 300; narrow windows %d, of them finite %d; not settling at k = 50: %d, of them finite %d"
+              % (k, int(finite.sum()), int(narrow_b.sum()), int((narrow_b & finite).sum()), int(lost_b.sum()), int((lost_b & finite).sum())))
+        assert finite.sum() >= 290
+        assert (lost_b & finite).sum() >= 100 and (narrow_b & finite).sum() >= 100
+    print("candidates passed over for equal distances: %d" % _cache["passed over"])
+    assert _cache["passed over"] == PASSED_OVER
+
+
+def test_far_queries_have_no_equal_distances(oracle_mod):
+    """for every FAR query no two of its k + 1 nearest neighbours have equal float32 flann_dist2 (k = 50, hence k = 10), in FAR
+    and in BARE"""
+    pts, P, Q = far_setup(oracle_mod)
+    for cloud, R in ((pts, P), (bare_rows(pts), bare_rows(P))):
+        o = oracle_mod.Oracle(cloud, tool_radius=R_FAR)
+        assert bits(o.points()).tobytes() == bits(R).tobytes()
+        for k in (50, 10):
+            for q in Q:
+                nb = o.knn(q, k + 1)
+                assert len(nb) == k + 1 and len(np.unique(flann_dist2(q, R[nb]))) == k + 1
+        o.close()
+
+
+def test_patch_exceeds_the_capacities(oracle_mod):
+    pts, P = patch_setup(oracle_mod)
+    assert 6500 < len(P) < 7100
+    tree = cKDTree(P.astype(np.float64))
+    r0 = first_radius(P, 50)
+    in_r0 = tree.query_ball_point(P.astype(np.float64), float(r0), return_length=True)
+    in_nr = tree.query_ball_point(P.astype(np.float64), 2.5, return_length=True)
+    in_nr4 = tree.query_ball_point(P.astype(np.float64), 4.0, return_length=True)
+    print("PATCH: %d points, r0(k=50) %.3f mm: %d points with more than %d inside; more than %d within 2.5 mm: %d (fewest %d), within "
+          "4.0 mm: %d" % (len(P), r0, int((in_r0 > DYN_KNN_CAP).sum()), DYN_KNN_CAP, NRM_CAP, int((in_nr > NRM_CAP).sum()),
+                         int(in_nr.min()), int((in_nr4 > NRM_CAP).sum())))
+    assert (in_r0 > DYN_KNN_CAP).sum() >= 1000
+    assert (in_nr > NRM_CAP).sum() >= 1000 and (in_nr > NRM_LDS_CAP).sum() >= 1000
+    assert (in_nr4 > NRM_CAP).sum() >= 1000
+    assert in_nr.min() >= 3                       # every normal exists
+    for kw in (dict(walk=1, dynamic_adjustment=0), dict(walk=1, dynamic_adjustment=1)):
+        o = oracle_mod.Oracle(pts, tool_radius=R_PATCH, **kw)
+        assert o.gen_path() > 12 and o.get_path() > 0
+        o.close()
+
+
+def test_oracle_contact_fields_stay_within_the_nan_cap(oracle_mod):
+    """FAR: exactly the 40 lifted points have no width in the oracle (0.8 %; no normal exists where fewer than three points are
+    within normal_radius), the rest of the 2 % is headroom for the sheet's own points; PATCH within the cap as well"""
+    pts, _, _ = far_setup(oracle_mod)
+    _, hw = oracle_field(oracle_mod, "far", pts, tool_radius=R_FAR)
+    assert np.isnan(hw[N_BASE:N_BASE + N_LIFT]).all()
+    print("FAR NaN half widths: %d of %d (40 lifted)" % (int(np.isnan(hw).sum()), len(hw)))
+    ppts, _ = patch_setup(oracle_mod)
+    _, phw = oracle_field(oracle_mod, "patch", ppts, tool_radius=R_PATCH)
+    print("PATCH NaN half widths: %d of %d" % (int(np.isnan(phw).sum()), len(phw)))
+
+
+def test_oracle_knn_and_principal_curvature_on_patch_match_numpy(oracle_mod):
+    """test_knn_matches_brute_force and test_principal_curvature_matches_numpy of test_oracle_crosschecks, at 200 seeded points
+    of PATCH (cloud points and points around them)"""
+    pts, P = patch_setup(oracle_mod)
+    o = oracle_mod.Oracle(pts, tool_radius=R_PATCH)
+    rng = np.random.default_rng(3)
+    for qi in P[rng.integers(0, len(P), 200)] + rng.normal(0, 1.0, (200, 3)).astype(np.float32):
+        d = qi[None, :] - P
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        assert np.array_equal(o.knn(qi, 50), np.lexsort((np.arange(len(d2)), d2))[:50])
+    normals = o.estimate_normals().astype(np.float64)[:, :3]
+    assert not np.isnan(normals).any()
+    rng = np.random.default_rng(4)
+    for qi in P[rng.integers(0, len(P), 200)]:
+        nb = o.knn(qi, 50)
+        n = normals[nb[0]]
+        proj = normals[nb] @ (np.eye(3) - np.outer(n, n)).T
+        dm = proj - proj.mean(0)
+        w, v = np.linalg.eigh(dm.T @ dm)
+        pc = o.principal_curvature(qi)
+        assert abs(pc[3] - w[2] / 50) <= 2e-3 * max(w[2] / 50, 1e-9) + 1e-9
+        assert abs(pc[4] - w[1] / 50) <= 5e-2 * max(w[2] / 50, 1e-9) + 1e-9   # float closed-form roots
+        assert abs(abs(np.dot(pc[:3], v[:, 2])) - 1) < 1e-3
+    o.close()
+
+
+# ---------------------------------------------------------------- GPU
+
+
+def same_floats(got, want, what):
+    """bit-equal, NaNs in the same places"""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    assert got.shape == want.shape, what
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (what, int((np.isnan(got) != np.isnan(want)).sum()))
+    bad = np.nonzero(((bits(got) != bits(want)) & ~np.isnan(want)).reshape(len(got), -1).any(axis=1))[0]
+    print("%s: %d of %d rows differ" % (what, len(bad), len(got)))
+    assert len(bad) == 0, (what, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [50, 10])
+@pytest.mark.parametrize("cloud", ["far", "bare"])
+def test_off_surface_queries_match_the_oracle(engine_mod, oracle_mod, cloud, k):
+    """principal_curvatures_at and area2cloud (both keys) at the 300 off-surface queries: bit-equal, NaNs in the same places.
+    On FAR the oracle has values for the 94 queries nearest the sheet only (no lifted point among their neighbours) and the
+    rest compares the places of the NaNs; on BARE the oracle has a value for every query (asserted), those behind a bisected
+    radius included"""
+    pts, P, Q = far_setup(oracle_mod)
+    if cloud == "bare":
+        pts, P = bare_rows(pts), bare_rows(P)
+    o = oracle_mod.Oracle(pts, tool_radius=R_FAR, curvature_k=k)
+    e = engine_mod.Engine(0, tool_radius=R_FAR, curvature_k=k)
+    e.set_cloud(pts)
+    assert bits(e.cloud()).tobytes() == bits(P).tobytes()
+    want = np.stack([o.principal_curvature(q) for q in Q])
+    finite = np.isfinite(want).all(axis=1)
+    print("%s k=%d: the oracle has a curvature for %d of 300 queries" % (cloud, k, int(finite.sum())))
+    if cloud == "bare":
+        assert bits(want).tobytes() == bits(bare_finite_rows(oracle_mod, k)[0]).tobytes() and finite.sum() >= 290
+    else:
+        assert finite[:60].all()                         # (0 and 5 mm off the sheet)
+    same_floats(e.principal_curvatures_at(Q), want, "%s principal_curvatures_at k=%d" % (cloud, k))
+    q64 = Q.astype(np.float64)
+    for key in (0, 1):
+        want = np.stack([o.area2cloud(p, key) for p in q64])
+        if cloud == "bare":
+            assert np.isfinite(want).all(axis=1).sum() >= 290
+        same_floats(e.area2cloud(q64, key), want, "%s area2cloud k=%d key=%d" % (cloud, k, key))
+    e.close(); o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cloud", ["far", "patch"])
+def test_contact_field_at_every_point(engine_mod, oracle_mod, cloud):
+    """every row bit-equal, NaNs in the same places.  PATCH: 2 396 points overflow the first radius and settle on a smaller one,
+    all with values.  FAR: the points that need a bisected radius are lifted points, which have no width in the oracle: the
+    engine must have none either (values behind a bisected radius: test_off_surface_queries_match_the_oracle[bare-*])"""
+    pts = far_setup(oracle_mod)[0] if cloud == "far" else patch_setup(oracle_mod)[0]
+    R = R_FAR if cloud == "far" else R_PATCH
+    want_c, want_h = oracle_field(oracle_mod, cloud, pts, tool_radius=R)
+    e = engine_mod.Engine(0, tool_radius=R)
+    e.set_cloud(pts)
+    step = float(int(2 * R))
+    curv, hw, st = e.contact_field(min_width=step)
+    same_floats(hw, want_h, "%s half_width" % cloud)
+    same_floats(curv, want_c, "%s curv5" % cloud)
+    check_stats(hw, st, R, step)
+    e.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cloud", ["far", "patch"])
+@pytest.mark.parametrize("mean_k", [50, 10])
+def test_remove_outlier_on_the_adversaries(engine_mod, oracle_mod, cloud, mean_k):
+    """n_kept, the threshold as a double and the surviving cloud equal the oracle's; on FAR every lifted point goes"""
+    pts = far_setup(oracle_mod)[0] if cloud == "far" else patch_setup(oracle_mod)[0]
+    R = R_FAR if cloud == "far" else R_PATCH
+    o = oracle_mod.Oracle(pts, tool_radius=R)
+    e = engine_mod.Engine(0, tool_radius=R)
+    e.set_cloud(pts)
+    n_o, thr_o, _ = o.remove_outlier(mean_k, 1.0)
+    n_e, thr_e = e.remove_outlier(mean_k, 1.0)
+    print("%s mean_k %d: kept %d (oracle %d) of %d, threshold %r (oracle %r)" % (cloud, mean_k, n_e, n_o, len(pts), thr_e, thr_o))
+    assert n_e == n_o < len(pts)
+    if cloud == "far":
+        assert n_o <= len(pts) - N_LIFT
+    assert thr_e == thr_o
+    assert bits(e.cloud()).tobytes() == bits(o.points()).tobytes()
+    e.close(); o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("normal_radius", [2.5, 4.0])
+def test_normal_fields_on_patch(engine_mod, oracle_mod, normal_radius):
+    """estimate_normals: test_whole_cloud_normal_field's comparison (same bits, same NaNs, angle); normals_at at 400 seeded
+    indices against Oracle.normal_at: test_nearest_and_normals_api's.  Most neighbourhoods of the patch overflow both neighbour lists"""
+    pts, _ = patch_setup(oracle_mod)
+    kw = dict(tool_radius=R_PATCH, normal_radius=normal_radius)
+    o = oracle_mod.Oracle(pts, **kw)
+    e = engine_mod.Engine(0, **kw)
+    e.set_cloud(pts)
+    n, on = e.estimate_normals(), o.estimate_normals()
+    nan = np.isnan(on[:, 0])
+    assert not nan.any() and np.array_equal(np.isnan(n[:, 0]), nan)
+    print("estimate_normals r=%g: %d of %d rows differ in a bit" % (normal_radius, int((bits(n) != bits(on)).any(axis=1).sum()), len(n)))
+    assert np.array_equal(bits(n), bits(on))
+    ang = np.arctan2(np.linalg.norm(np.cross(n[:, :3], on[:, :3]), axis=1), np.sum(n[:, :3] * on[:, :3], axis=1))
+    assert ang.max() < 1e-4 and np.abs(n[:, 3] - on[:, 3]).max() < 1e-5
+    idx = np.random.default_rng(5).integers(0, len(pts), 400).astype(np.int32)
+    na = e.normals_at(idx)
+    assert not np.isnan(na).any()
+    oa = np.stack([o.normal_at(i) for i in idx])
+    assert not np.isnan(oa).any()
+    print("normals_at r=%g: %d of 400 rows differ in a bit" % (normal_radius, int((bits(na) != bits(oa)).any(axis=1).sum())))
+    ang = np.arctan2(np.linalg.norm(np.cross(na[:, :3], oa[:, :3]), axis=1), np.sum(na[:, :3] * oa[:, :3], axis=1))
+    assert ang.max() < 1e-4 and np.abs(na[:, 3] - oa[:, 3]).max() < 1e-5
+    e.close(); o.close()
+
+
+PIPELINES = [
+    dict(walk=1, dynamic_adjustment=0),
+    dict(walk=1, dynamic_adjustment=1),
+    dict(V1_CONTACT, dynamic_adjustment=1),     # walk 3, pairing 1 (Contact_Path_Generation): the pass ppp_get_coverage belongs to
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kw", PIPELINES, ids=["walk1", "walk1-adjusted", "walk3-brute-adjusted"])
+def test_pipeline_and_contact_queries_on_patch(engine_mod, oracle_mod, kw):
+    """knots of every slice bit-equal, S and W equal, waypoints within 1e-4 m / 1e-4 rad, tail index equal -- or both sides
+    name the same failing slice, as the randomised sweep accepts; then every contact query of the pass against its restatement"""
+    pts, _ = patch_setup(oracle_mod)
+    kw = dict(kw, tool_radius=R_PATCH)
+    o = oracle_mod.Oracle(pts, **kw)
+    e = engine_mod.Engine(0, **kw)
+    e.set_cloud(pts)
+    So = o.gen_path()
+    if So < 0:
+        with pytest.raises(engine_mod.PPPError):
+            e.gen_path()
+        assert e.failed_slice() == -(So + 1)
+        e.close(); o.close()
+        return
+    S = e.gen_path()
+    assert S == So > 12
+    for s in range(S):
+        assert all(np.array_equal(a, b) for a, b in zip(e.nodes(s), o.nodes(s))), s
+    Wo = o.get_path(); W = e.get_path()
+    assert W == Wo > 0
+    wp, owp = e.waypoints(), o.waypoints()
+    assert np.array_equal(np.isnan(wp), np.isnan(owp)) and not np.isnan(owp).any()
+    assert np.linalg.norm(wp[:, :3] - owp[:, :3], axis=1).max() <= TOL_M
+    d = np.abs(wp[:, 3:] - owp[:, 3:])
+    assert np.minimum(d, np.abs(d - 2 * np.pi)).max() <= TOL_RAD
+    assert np.array_equal(e.tail_index(), o.tail_index())
+    o.close()
+    want_flags, S2 = restate_path_coverage(pts, kw, oracle_mod)
+    assert S2 == S
+    flags, covered = e.path_coverage()
+    assert np.array_equal(flags, want_flags), (int(flags.sum()), int(want_flags.sum()), int((flags != want_flags).sum()))
+    assert covered == int(want_flags.sum()) and 0 < covered < len(pts)
+    want_c, want_f, want_l, _ = restate_path_contacts(pts, kw, oracle_mod)
+    counts, first, last, st = e.path_contacts()
+    assert np.array_equal(counts, want_c), int((counts != want_c).sum())
+    assert np.array_equal(first, want_f) and np.array_equal(last, want_l)
+    check_contact_stats(counts, first, last, st)
+    if kw["walk"] == 3:
+        want_cov = restate_coverage(pts, R_PATCH, oracle_mod)
+        cflags, ccov = e.coverage()
+        assert np.array_equal(cflags, want_cov), (int(cflags.sum()), int(want_cov.sum()), int((cflags != want_cov).sum()))
+        assert ccov == int(want_cov.sum())
+    got = e.regions(engine_mod.REGIONS_UNCOVERED, link_radius=2.5)
+    want = restate_regions(e.cloud(), want_flags == 0, 2.5)
+    print("%s: S %d W %d covered %d; %d uncovered in %d regions; near-threshold pairs %d" % (kw, S, W, covered, want[2]["selected"], want[2]["regions"], want[3]))
+    assert_same(got, want, str(kw))
+    e.close()
+
+
+@pytest.mark.gpu
+def test_regions_on_dense_links(engine_mod, oracle_mod):
+    """the full mask at link 2.5 (hundreds of links per point inside the patch) and a 30 % Bernoulli mask at link 1.0"""
+    pts, _ = patch_setup(oracle_mod)
+    e = engine_mod.Engine(0, tool_radius=R_PATCH)
+    e.set_cloud(pts)
+    P = e.cloud()
+    n = len(pts)
+    for mask, link in ((np.ones(n, np.uint8), 2.5), ((np.random.default_rng(n).random(n) < 0.30).astype(np.uint8), 1.0)):
+        got = e.regions(MASK, mask=mask, link_radius=link)
+        want = restate_regions(P, mask != 0, link)
+        print("PATCH link %g: %d selected, %d regions, largest %d, singletons %d; near-threshold pairs %d"
+              % (link, want[2]["selected"], want[2]["regions"], want[2]["largest"], want[2]["singletons"], want[3]))
+        assert_same(got, want, "link %g" % link)
+    e.close()
+
+
+def contact_answers(e, engine_mod, with_pass=True):
+    """what the contact queries return, as bytes and values that compare with =="""
+    curv, hw, st = e.contact_field(min_width=12.0)
+    out = [bits(curv).tobytes(), bits(hw).tobytes(), {k: v for k, v in st.items() if k != "hist"}, st["hist"].tobytes(), len(hw)]
+    if with_pass:
+        flags, covered = e.path_coverage()
+        counts, first, last, cst = e.path_contacts()
+        labels, rows, rst = e.regions(engine_mod.REGIONS_UNCOVERED, link_radius=2.5)
+        out += [flags.tobytes(), covered, counts.tobytes(), first.tobytes(), last.tobytes(),
+                {k: v for k, v in cst.items() if k != "hist"}, cst["hist"].tobytes(), labels.tobytes(), rows.tobytes(), rst, len(flags), len(labels)]
+    return out
+
+
+@pytest.mark.gpu
+def test_millimetre_cloud_without_change_range_gives_the_same_bytes(engine_mod):
+    """tiny_5k as pts * float32(1000) with change_range = 0 against the metres cloud with change_range = 1: contact field, path
+    coverage, path contacts and regions"""
+    pts, cfg = synth.make_config("tiny_5k")
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+    a = engine_mod.Engine(0, **kw)
+    a.set_cloud(pts)
+    b = engine_mod.Engine(0, change_range=0, **kw)
+    b.set_cloud(pts * np.float32(1000))
+    assert bits(a.cloud()).tobytes() == bits(b.cloud()).tobytes()
+    assert a.gen_path() == b.gen_path() > 2
+    ra, rb = contact_answers(a, engine_mod), contact_answers(b, engine_mod)
+    for i, (x, y) in enumerate(zip(ra, rb)):
+        assert x == y, i
+    assert ra[6] > 0
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
+def test_viewpoint_above_the_cloud_matches_the_oracle(engine_mod, oracle_mod):
+    """viewpoint = [0, 0, 3000] (every normal flips): contact field and path coverage equal the oracle built with it"""
+    pts, cfg = synth.make_config("tiny_5k")
+    R = cfg["tool_radius"]
+    vp = [0.0, 0.0, 3000.0]
+    want_c, want_h = oracle_field(oracle_mod, "tiny-viewpoint", pts, tool_radius=R, viewpoint=vp)
+    kw = dict(tool_radius=R, walk=1, pairing=0, dynamic_adjustment=0)
+    want_flags, S = restate_path_coverage(pts, dict(kw, viewpoint=vp), oracle_mod)
+    e = engine_mod.Engine(0, **kw)
+    e.set_cloud(pts, viewpoint=vp)
+    curv, hw, st = e.contact_field(min_width=12.0)
+    same_floats(hw, want_h, "viewpoint half_width")
+    same_floats(curv, want_c, "viewpoint curv5")
+    check_stats(hw, st, R, 12.0)
+    assert e.gen_path() == S
+    flags, covered = e.path_coverage()
+    assert np.array_equal(flags, want_flags) and covered == int(want_flags.sum()) and 0 < covered < len(pts)
+    d = engine_mod.Engine(0, **kw)                       # and the viewpoint was used: the default one gives the opposite normals
+    d.set_cloud(pts)
+    assert (np.sum(d.estimate_normals()[:, :3] * e.estimate_normals()[:, :3], axis=1) < 0).all()
+    e.close(); d.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["remove_outlier", "voxel_down"])
+def test_results_do_not_outlive_their_cloud(engine_mod, oracle_mod, how):
+    """FAR: contact field, path coverage, path contacts and uncovered regions are asked for, then preprocessing changes the
+    resident cloud, then every query is made again: each answer has the new length and equals, bit for bit, a fresh handle's
+    that was given the resident cloud as it is (millimetres, change_range = 0: the units test above)"""
+    pts, _, _ = far_setup(oracle_mod)
+    kw = dict(tool_radius=R_FAR, walk=1)
+    e = engine_mod.Engine(0, **kw)
+    e.set_cloud(pts)
+    assert e.gen_path() > 2
+    before = contact_answers(e, engine_mod)
+    assert before[4] == len(pts)
+    if how == "remove_outlier":
+        n_new, _ = e.remove_outlier(50, 1.0)
+        assert n_new <= len(pts) - N_LIFT
+    else:
+        n_new, overflow = e.voxel_down(0.5, 0.5, 5.0)
+        assert not overflow
+    P = e.cloud()
+    assert 0 < n_new == len(P) <= len(pts)
+    assert n_new < len(pts) or bits(P).tobytes() != bits(pts * np.float32(1000)).tobytes()   # (0.5 mm leaves: every point stays, in voxel order)
+    field_first = contact_answers(e, engine_mod, with_pass=False)     # needs no pass: asked for before one
+    assert e.gen_path() > 2
+    after = contact_answers(e, engine_mod)
+    f = engine_mod.Engine(0, change_range=0, **kw)
+    f.set_cloud(P)
+    assert bits(f.cloud()).tobytes() == bits(P).tobytes()
+    fresh_field = contact_answers(f, engine_mod, with_pass=False)
+    assert f.gen_path() == e.num_slices()
+    fresh = contact_answers(f, engine_mod)
+    for i, (x, y) in enumerate(zip(field_first, fresh_field)):
+        assert x == y, ("field before the new pass", i)
+    for i, (x, y) in enumerate(zip(after, fresh)):
+        assert x == y, i
+    assert after[4] == n_new and after[-1] == n_new and after[-2] == n_new
+    print("%s: %d -> %d points" % (how, len(pts), n_new))
+    e.close(); f.close()

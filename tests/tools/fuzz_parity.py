@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle sweep over cloud shapes, tool radii, walks, pairings and the dynamic adjustment.
 Every case must agree on S, the knots of every slice (bit-exact), W and the waypoints (<= 1e-4 m), or both
-sides must report the same failing slice.  usage: python tests/tools/fuzz_parity.py [cases] [seed]"""
+sides must report the same failing slice.  usage: python tests/tools/fuzz_parity.py [cases] [seed]
+PPP_FUZZ_FAR=1 adds 0-30 points lifted off the plate and a dense patch to every case and compares the contact field at
+200 seeded points with the oracle's (a developer's sweep; the suite's 208 cases run without it)."""
 import os
 import sys
 import time
@@ -11,6 +13,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from polishpathplanning_amd import engine, synth  # noqa: E402
 from oracle import ppo  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from test_contact_field import bits, flann_dist2, restate_field  # noqa: E402  (PPP_FUZZ_FAR)
 
 
 rng2 = np.random.default_rng(12345)  # choices that must not disturb the case stream
@@ -107,6 +111,18 @@ def one_case_hard(rng, i, only=None, verbose=False, big=None):
         desc = "odd R %.1f res %.1f rpy %.1f trim %.0f | " % (kw["tool_radius"], kw["path_resolution"], kw["rpy_resolution"], kw["trim"])
     else:
         desc = ""
+    far = os.environ.get("PPP_FUZZ_FAR") == "1"           # off-surface points and a dense patch (tests/test_density_adversaries.py)
+    if far:
+        nl = int(rng2.integers(0, 31))                    # 0 .. 30 points lifted 40 .. 400 mm off the plate, either sign
+        lift = pts[rng2.integers(0, len(pts), nl)].copy()
+        lift[:, 2] += (rng2.uniform(0.040, 0.400, nl) * rng2.choice([-1.0, 1.0], nl)).astype(np.float32)
+        c = pts[int(rng2.integers(0, len(pts)))]          # a 12 x 12 mm patch at 0.4 mm spacing around a point of the plate,
+        if not np.isfinite(c).all():                      # on the plane through it
+            c = np.nanmean(pts, axis=0).astype(np.float32)
+        g = (np.stack(np.meshgrid(np.arange(30), np.arange(30), indexing="ij"), axis=-1).reshape(-1, 2) * 0.4 - 6.0
+             + rng2.uniform(-0.1, 0.1, (900, 2))) / 1000.0
+        dense = np.concatenate([c[None, :2] + g, np.full((900, 1), c[2])], axis=1).astype(np.float32)
+        pts = np.concatenate([pts, lift, dense])[rng2.permutation(len(pts) + nl + 900)]
     unit = 1.0
     if rng2.random() < 0.1:                               # ChangeRange = false: the file is already in millimetres
         pts = pts * np.float32(1000.0)
@@ -143,6 +159,28 @@ def one_case_hard(rng, i, only=None, verbose=False, big=None):
     o = ppo.Oracle(pts, **okw)
     e = engine.Engine(0, **kw)
     e.set_cloud(pts, viewpoint=viewpoint)
+    if far:                                                # the contact field at 200 seeded points against the oracle's
+        Pm = o.points()
+        ok = np.nonzero(np.isfinite(Pm).all(axis=1))[0]    # a non-finite row has no answer on either side
+        idx = rng2.choice(ok, min(200, len(ok)), replace=False)
+        kq = int(kw.get("curvature_k", 50))
+        tied = []
+        for j in idx:                                      # the oracle's order among equal distances (duplicated points) is traversal-defined:
+            d2 = flann_dist2(Pm[j], Pm[ok])                # such a row is not compared, as in tests/test_contact_field.py
+            cut = np.partition(d2, min(kq, len(d2) - 1))[min(kq, len(d2) - 1)]
+            near = d2[d2 <= cut]
+            tied.append(len(np.unique(near)) != len(near))
+        idx = idx[~np.array(tied, bool)]
+        want_c, want_h = restate_field(o, idx)
+        try:
+            curv, hw, _ = e.contact_field()
+        except engine.PPPError as ex:
+            return "contact_field GPU error %s" % ex, desc
+        for got, want, what in ((hw[idx], want_h, "half widths"), (curv[idx], want_c, "curvatures")):
+            if not np.array_equal(np.isnan(got), np.isnan(want)):
+                return "contact field: NaN %s in different places" % what, desc
+            if not np.array_equal(bits(got)[~np.isnan(want)], bits(want)[~np.isnan(want)]):
+                return "contact field: %s differ" % what, desc
     if pre is not None:                                    # the constructors' order: smooth, align, remove (path_slicing_alg.cpp:27-29); voxel_down is v1's
         if pre["vox"] is not None:
             r_o = o.voxel_down(*pre["vox"])
