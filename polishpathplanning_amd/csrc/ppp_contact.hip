@@ -1,0 +1,776 @@
+/*
+ * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
+ * path coverage, path contacts, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h and ppp_regions.h; of the handle and the pass it
+ * sees what ppp_handle.h declares.  Compiled with the engine's flags.
+ */
+#ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
+#define PPP_KERNELS_FOREIGN /* ppp_kernels.h, ppp_dynamic.h, ppp_compact.h: types and device helpers only -- their kernels are the engine's */
+#endif
+#include "ppp_handle.h"
+#include "ppp_contact.h"
+#include "ppp_regions.h"
+#include <cstring>
+
+extern "C" {
+
+/* the kernels' views of the handle's slab index / normal field and of its knot tables, as they stand when the launch is made */
+static ContactIndex contact_index(const ppp_handle h)
+{
+    return ContactIndex{h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p};
+}
+static KnotTable knot_table(const ppp_handle h)
+{
+    return KnotTable{h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->node_cap};
+}
+
+/* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
+   ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The
+   contact queries then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
+static bool pass_left_normals(const ppp_handle h) { return h->pass.gen_done() && h->P.dynamic_adjustment; }
+
+/* behind index_ready: the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
+static int contact_buffers(ppp_handle h)
+{
+    int rc = ensure_dynamic_buffers(h);
+    if (rc) return rc;
+    return pass_left_normals(h) ? PPP_OK : enqueue_normals(h);
+}
+
+/* What a pass did not build of what a contact query reads: the slab index (behind a window pass it keeps that pass's run
+   state, gen_done with it, as every API mirror's does) and contact_buffers */
+static int contact_prerequisites(ppp_handle h)
+{
+    int rc = index_ready(h, false);
+    return rc ? rc : contact_buffers(h);
+}
+
+/* the opening of a query about the paths of a finished pass whose maps go by cloud index */
+static int contact_query_begin(ppp_handle h, const char *what)
+{
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, std::string(what) + ": the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
+    return curvature_k_ok(h, h->P.curvature_k);
+}
+
+static PCovRange pcov_range(const ppp_handle h)
+{
+    return PCovRange{h->incl_lo, h->incl_hi, h->h_mn[0], h->h_mx[0], h->P.normal_radius, h->ranged ? 1 : 0};
+}
+
+/* the refusal word of the sample kernels: 1 wave_ball_leaves_range, 2 KnotTable::slice (or 2^24 samples on a slice), 4 the
+   caps of k_pcon_offsets */
+static int contact_refusal(ppp_handle h, const char *what, unsigned long long bits)
+{
+    const std::string w(what);
+    if (bits & 2) return fail(h, PPP_ERR_HIP, w + ": a slice's knot table lies outside the node buffer");
+    if (bits & 4) return fail(h, PPP_ERR_CAPACITY, w + ": more than 2^30 contact samples");
+    if (bits & 1)
+        return fail(h, PPP_ERR_CAPACITY, w + ": a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
+    return PPP_OK;
+}
+
+/* What both coverage calls share.  On the first question about a pass: the flags by cloud index (n16 uint4s: zero padding up to
+   a multiple of 16 bytes) and the two result words zeroed, `mark` launches the balls (flags at C.flags.p, refusal word at
+   C.count.p + 1), k_cov_count counts into C.count.p[0], one read brings both back.  Later questions answer from the result. */
+static int flag_coverage(ppp_handle h, ppp_handle_s::FlagCoverage &C, const char *what, const std::function<int()> &mark, unsigned char *flags,
+                         size_t cap, size_t *n, size_t *covered)
+{
+    const size_t N = h->n, n16 = (N + 15) / 16;
+    if (C.serial != h->pass.serial()) {
+        HIPCHK(h, C.flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, C.count.ensure(2));
+        HIPCHK(h, hipMemsetAsync(C.flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.count.p, 0, 2 * sizeof(int), h->stream));
+        int rc = mark();
+        if (rc) return rc;
+        if (n16)
+            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
+                   (const uint4 *)C.flags.p, (int)n16, C.count.p);
+        int res[2] = {0, 0};
+        HIPCHK(h, copy_sync(h, res, C.count.p, sizeof(res), hipMemcpyDeviceToHost));
+        rc = contact_refusal(h, what, (unsigned)res[1]);
+        if (rc) return rc;
+        if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, std::string(what) + " count corrupt");
+        C.covered = (size_t)res[0];
+        C.serial = h->pass.serial();
+    }
+    if (n) *n = N;
+    if (covered) *covered = C.covered;
+    const size_t k = std::min(cap, N);
+    if (flags && k) HIPCHK(h, copy_sync(h, flags, C.flags.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
+{
+    int rc = ensure_ready(h, true, false);
+    if (rc) return rc;
+    rc = map_dev_err(h);
+    if (rc) return rc;
+    if (h->P.walk != PPP_WALK_V1_CONTACT || !h->P.dynamic_adjustment || h->ranged || h->use_part || h->part_given)
+        return fail(h, PPP_ERR_UNSUPPORTED, "coverage: only after a PPP_WALK_V1_CONTACT pass with dynamic_adjustment = 1 on a whole-cloud handle");
+    auto balls = [h]() -> int { /* raw and adjusted paths of every slice, one launch */
+        const int S = h->hmeta.S;
+        if (S > 0)
+            LAUNCH(h, "k_cov_balls", k_cov_balls, dim3((h->dyn_maxNB + DYN_WAVES - 1) / DYN_WAVES, S, 2), 64 * DYN_WAVES, 0, contact_index(h),
+                   dyn_params(h), knot_table(h), h->dyn_raw_sc.p, h->dyn_maxNB, h->cov.flags.p);
+        return PPP_OK;
+    };
+    return flag_coverage(h, h->cov, "coverage", balls, flags, cap, n, covered);
+}
+
+int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
+{
+    int rc = contact_query_begin(h, "path coverage");
+    if (rc) return rc;
+    auto balls = [h]() -> int {
+        int rc = contact_prerequisites(h);
+        if (rc) return rc;
+        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S);
+        if (se <= sb) return PPP_OK;
+        /* samples per slice of knots spanning the cloud's y range (the kernel strides past it where adjusted knots reach further) */
+        const double yr = (double)h->h_mx[1] - (double)h->h_mn[1];
+        const int nb = (int)std::min(65536.0, std::max(0.0, yr - 4) / (h->P.tool_radius / 4) + 4);
+        for (int s0 = sb; s0 < se; s0 += 65535) /* (gridDim.y) */
+            LAUNCH(h, "k_pcov_balls", k_pcov_balls, dim3((nb + DYN_WAVES - 1) / DYN_WAVES, std::min(se - s0, 65535)), 64 * DYN_WAVES, 0,
+                   contact_index(h), dyn_params(h), knot_table(h), s0, pcov_range(h), h->pcov.flags.p, h->pcov.count.p + 1);
+        return PPP_OK;
+    };
+    return flag_coverage(h, h->pcov, "path coverage", balls, flags, cap, n, covered);
+}
+
+int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap, ppp_contact_stats *stats)
+{
+    int rc = contact_query_begin(h, "path contacts");
+    if (rc) return rc;
+    const size_t N = h->n;
+    auto &C = h->pcon;
+    if (C.serial != h->pass.serial()) { /* first question about this pass */
+        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
+        rc = contact_prerequisites(h);
+        if (rc) return rc;
+        const size_t N1 = std::max<size_t>(N, 1);
+        HIPCHK(h, C.counts.ensure(N1)); HIPCHK(h, C.first.ensure(N1)); HIPCHK(h, C.last.ensure(N1));
+        HIPCHK(h, C.acc.ensure(70));
+        HIPCHK(h, hipMemsetAsync(C.counts.p, 0, N1 * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.first.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.last.p, 0xff, N1 * sizeof(int), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
+        int *err = (int *)(C.acc.p + 69);
+        if (nsl > 0) {
+            HIPCHK(h, C.off.ensure((size_t)nsl + 2));
+            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), knot_table(h), sb, nsl, C.off.p, err);
+            std::vector<int> off((size_t)nsl + 2);
+            HIPCHK(h, copy_sync(h, off.data(), C.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+            rc = contact_refusal(h, "path contacts", (unsigned)off[nsl + 1]);
+            if (rc) return rc;
+            const int rows = off[nsl];
+            int most = 0;
+            for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
+            if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, "path contacts: sample table corrupt");
+            if (rows > 0) {
+                HIPCHK(h, C.tab.ensure((size_t)rows)); HIPCHK(h, C.reach.ensure(3 * (size_t)nsl));
+                HIPCHK(h, hipMemsetAsync(C.reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
+                const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
+                for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
+                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0, contact_index(h),
+                           dyn_params(h), knot_table(h), C.off.p, sb, s0, pcov_range(h), C.tab.p, C.reach.p, err);
+                /* one thread per indexed point (at most N of them), PCON_T a round */
+                LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
+                       h->meta.p, h->sorted4.p, C.tab.p, C.off.p, C.reach.p, sb, nsl, C.counts.p, C.first.p, C.last.p);
+            }
+        }
+        LAUNCH(h, "k_pcon_stats", k_pcon_stats, (unsigned)std::min<size_t>((N1 + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus), PCON_T, 0,
+               C.counts.p, C.first.p, C.last.p, (int)N, err, C.acc.p);
+        unsigned long long acc[69];
+        HIPCHK(h, copy_sync(h, acc, C.acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+        rc = contact_refusal(h, "path contacts", acc[68]);
+        if (rc) return rc;
+        if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "path contacts: statistics corrupt");
+        ppp_contact_stats st = {};
+        st.n = N; st.covered = (size_t)acc[64]; st.multi_slice = (size_t)acc[65];
+        st.total = acc[66]; st.max_count = (unsigned)acc[67];
+        st.hist[0] = N - st.covered;
+        for (int b = 1; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
+        C.stats = st;
+        C.serial = h->pass.serial();
+    }
+    if (stats) *stats = C.stats;
+    const size_t k = std::min(cap, N);
+    if (counts && k) HIPCHK(h, copy_sync(h, counts, C.counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, C.first.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, C.last.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_area2cloud(ppp_handle h, const double *pts_xyz, size_t k, int key, float *out3)
+{
+    int rc = index_ready(h, false); /* complete index: slabs beyond the LDS capacity go through the arena pass first */
+    if (rc) return rc;
+    if (!k) return PPP_OK;
+    if (!pts_xyz || !out3 || (key != 0 && key != 1)) return fail(h, PPP_ERR_ARG, "bad arguments");
+    if (int rck = curvature_k_ok(h, h->P.curvature_k)) return rck;
+    rc = ensure_dynamic_buffers(h);
+    if (rc) return rc;
+    rc = enqueue_normals(h);
+    if (rc) return rc;
+    HIPCHK(h, h->scratch.ensure(k * 36 + 64));
+    double *dq = (double *)h->scratch.p;
+    float *dout = (float *)(dq + 3 * k);
+    HIPCHK(h, hipMemcpyAsync(dq, pts_xyz, k * 24, hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "k_area2cloud_api", k_area2cloud_api, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
+           dq, (int)k, key, dout);
+    HIPCHK(h, hipMemcpyAsync(out3, dout, k * 12, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PPP_OK;
+}
+
+int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, float *out5)
+{
+    int rc = index_ready(h, false); /* complete index: slabs beyond the LDS capacity go through the arena pass first */
+    if (rc) return rc;
+    if (!k) return PPP_OK;
+    if (!q_xyz || !out5 || k > 0x7fffffffu / 8) return fail(h, PPP_ERR_ARG, "bad arguments");
+    if (int rck = curvature_k_ok(h, h->P.curvature_k)) return rck;
+    rc = contact_buffers(h);
+    if (rc) return rc;
+    HIPCHK(h, h->scratch.ensure(k * 32 + 64));
+    float *dq = (float *)h->scratch.p, *dout = dq + 3 * k;
+    HIPCHK(h, hipMemcpyAsync(dq, q_xyz, k * 12, hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "k_field_waves", k_field_waves, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
+           dq, (int)k, dout, (float *)nullptr);
+    HIPCHK(h, hipMemcpyAsync(out5, dout, k * 20, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PPP_OK;
+}
+
+/* the opening of the field and region calls: a handle, on its device, that holds a cloud and holds all of it.  what: the call's
+   name in the refusal, why: what a part cannot give it */
+static int whole_cloud_begin(ppp_handle h, const char *what, const char *why)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
+    if (h->part_given) return fail(h, PPP_ERR_UNSUPPORTED, std::string(what) + ": " + why + ": this handle holds a part (ppp_set_cloud_part)");
+    return PPP_OK;
+}
+
+/* the parameters a contact field depends on */
+static bool same_contact_params(const ppp_params &P, const ppp_params &F)
+{
+    return P.tool_radius == F.tool_radius && P.depth == F.depth && P.toolthickness == F.toolthickness && P.curvature_k == F.curvature_k &&
+           P.normal_radius == F.normal_radius && P.change_range == F.change_range;
+}
+
+/* the statistics of a stored half-width map for one min_width (k_field_stats): hw = N half widths by cloud index */
+static int field_statistics(ppp_handle h, const float *hw, DevBuf<unsigned long long> &dacc, DevBuf<double> &dpsum, float min_width,
+                            ppp_contact_field_stats &st)
+{
+    const size_t N = h->n;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
+    const int per = (int)((N + grid - 1) / grid);
+    HIPCHK(h, dacc.ensure(68)); HIPCHK(h, dpsum.ensure((size_t)grid));
+    HIPCHK(h, hipMemsetAsync(dacc.p, 0, 68 * sizeof(unsigned long long), h->stream));
+    LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, hw, (int)N, per, h->P.tool_radius, min_width, dacc.p, dpsum.p);
+    unsigned long long acc[68];
+    std::vector<double> psum((size_t)grid);
+    HIPCHK(h, copy_sync(h, acc, dacc.p, sizeof(acc), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, psum.data(), dpsum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "contact field: statistics corrupt");
+    st = {};
+    st.n = N; st.valid = (size_t)acc[64]; st.narrow = (size_t)acc[65];
+    st.min_abs_r = st.valid ? -ordered_unkey((unsigned)acc[66]) : NAN; st.max_abs_r = st.valid ? ordered_unkey((unsigned)acc[67]) : NAN;
+    for (double v : psum) st.sum_abs_r += v;
+    for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
+    return PPP_OK;
+}
+static int field_statistics(ppp_handle h, float min_width)
+{
+    auto &C = h->field;
+    int rc = field_statistics(h, C.hw.p, C.acc, C.psum, min_width, C.stats);
+    if (!rc) C.min_width = min_width;
+    return rc;
+}
+
+int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width, ppp_contact_field_stats *stats)
+{
+    if (int rcb = whole_cloud_begin(h, "contact field", "the maps address the whole cloud")) return rcb;
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
+        return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
+    if (int rck = curvature_k_ok(h, h->P.curvature_k)) return rck;
+    if (!(min_width > 0.f)) min_width = 0.f;
+    const size_t N = h->n;
+    auto &C = h->field;
+    const ppp_params &P = h->P, &F = C.P;
+    const bool same = C.valid && same_contact_params(P, F);
+    if (!same) {
+        C.valid = false;
+        int rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+        if (rc) return rc;
+        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
+        rc = contact_buffers(h);
+        if (rc) return rc;
+        const size_t N1 = std::max<size_t>(N, 1);
+        HIPCHK(h, C.curv.ensure(5 * N1)); HIPCHK(h, C.hw.ensure(N1));
+        HIPCHK(h, hipMemsetAsync(C.curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* dropped points: NaN */
+        HIPCHK(h, hipMemsetAsync(C.hw.p, 0xff, N1 * sizeof(float), h->stream));
+        const int nsorted = h->hmeta.n_sorted;
+        if (nsorted < 0 || (size_t)nsorted > N) return fail(h, PPP_ERR_HIP, "contact field: index corrupt");
+        if (nsorted > 0) /* a wave per FIELD_Q indexed points, in slab / y order */
+            LAUNCH(h, "k_field_batch", k_field_batch, (unsigned)((nsorted + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
+                   contact_index(h), dyn_params(h), nsorted, C.curv.p, C.hw.p);
+        rc = field_statistics(h, min_width);
+        if (rc) return rc;
+        C.P = h->P;
+        C.valid = true; ++C.built;
+    } else if (stats && min_width != C.min_width) {
+        int rc = field_statistics(h, min_width);
+        if (rc) return rc;
+    }
+    if (stats) *stats = C.stats;
+    const size_t k = std::min(cap, N);
+    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
+    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* What this handle's tile evaluates and owns, behind a plan: the cuts of its range [sb, se) on the walk of the
+   whole cloud's bounds, widened by halo; a whole-cloud handle owns and evaluates everything. */
+static int tile_range(ppp_handle h, float halo, TileRange &T)
+{
+    T = TileRange{-INFINITY, INFINITY, -INFINITY, INFINITY};
+    if (!h->ranged) return PPP_OK;
+    const int S = h->S_cap;
+    std::vector<float> px((size_t)S);
+    if (ppp_slice_walk(h->P.walk, h->h_mn[0], h->h_mx[0], h->P.tool_radius, px.data(), S) != S) return fail(h, PPP_ERR_HIP, "tile: the slice walk changed under the plan");
+    owned_cuts(px.data(), S, h->sb, h->se, &T.own_lo, &T.own_hi);
+    T.ev_lo = T.own_lo - halo; T.ev_hi = T.own_hi + halo;
+    return PPP_OK;
+}
+
+/* does the interval [lo, hi] leave what the handle indexes at a side that is not the cloud's end? (wave_ball_leaves_range's test) */
+static bool leaves_indexed_range(const ppp_handle h, float lo, float hi)
+{
+    return h->ranged && lo <= hi && ((lo < h->incl_lo && h->incl_lo > h->h_mn[0]) || (hi > h->incl_hi && h->incl_hi < h->h_mx[0]));
+}
+
+/* the positions [pos0, pos1) of the slabs that meet the tile's evaluated interval (one slab more on either side: the kernels
+   test every point themselves), behind index_ready */
+static int tile_positions(ppp_handle h, const TileRange &T, int &pos0, int &pos1)
+{
+    pos0 = pos1 = 0;
+    const int ns = h->hmeta.n_sorted;
+    if (ns < 0 || (size_t)ns > h->n) return fail(h, PPP_ERR_HIP, "tile: index corrupt");
+    if (!(T.ev_lo <= T.ev_hi) || ns == 0) return PPP_OK;
+    const SlabGeom G = slab_geom(h);
+    auto slab_of_host = [&](float x) { return (int)fminf(fmaxf((x - G.slab_x0) * G.slab_invw, 0.f), (float)(h->B - 1)); };
+    const int b0 = std::max(0, slab_of_host(T.ev_lo) - 1), b1 = std::min(h->B - 1, slab_of_host(T.ev_hi) + 1);
+    HIPCHK(h, copy_sync(h, &pos0, h->slab_start.p + b0, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, &pos1, h->slab_start.p + b1 + 1, sizeof(int), hipMemcpyDeviceToHost));
+    if (pos0 < 0 || pos1 < pos0 || pos1 > ns) return fail(h, PPP_ERR_HIP, "tile: slab table corrupt");
+    return PPP_OK;
+}
+
+static void tile_field_stats(ppp_contact_field_tile_stats &o, const ppp_contact_field_stats &st)
+{
+    o.n = st.n; o.valid = st.valid; o.narrow = st.narrow; o.min_abs_r = st.min_abs_r; o.max_abs_r = st.max_abs_r; o.sum_abs_r = st.sum_abs_r;
+    memcpy(o.hist, st.hist, sizeof(o.hist));
+}
+
+int ppp_get_contact_field_tile(ppp_handle h, float *curv5, float *half_width, unsigned char *owned, size_t cap, float halo,
+                               float min_width, ppp_contact_field_tile_stats *stats)
+{
+    if (int rcb = whole_cloud_begin(h, "contact field tile", "the maps address the whole cloud")) return rcb;
+    if (int rck = curvature_k_ok(h, h->P.curvature_k)) return rck;
+    if (!(halo >= 0.f && halo <= 3.402823466e+38f)) return fail(h, PPP_ERR_ARG, "contact field tile: halo must be a finite number >= 0");
+    if (!(min_width > 0.f)) min_width = 0.f;
+    const size_t N = h->n;
+    auto &C = h->ftile;
+    const ppp_params &P = h->P, &F = C.P;
+    const bool same = C.valid && same_contact_params(P, F) && P.walk == F.walk && P.slice_begin == F.slice_begin && P.slice_end == F.slice_end &&
+                      P.range_margin == F.range_margin && halo == C.halo;
+    if (!same) {
+        C.valid = false;
+        int rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+        if (rc) return rc;
+        rc = contact_buffers(h);
+        if (rc) return rc;
+        TileRange T;
+        rc = tile_range(h, halo, T);
+        if (rc) return rc;
+        int pos0, pos1;
+        rc = tile_positions(h, T, pos0, pos1);
+        if (rc) return rc;
+        const size_t N1 = std::max<size_t>(N, 1);
+        HIPCHK(h, C.curv.ensure(5 * N1)); HIPCHK(h, C.hw.ensure(N1)); HIPCHK(h, C.hw_own.ensure(N1)); HIPCHK(h, C.owned.ensure(N1));
+        HIPCHK(h, C.cnt.ensure(4));
+        HIPCHK(h, hipMemsetAsync(C.curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* not evaluated: NaN */
+        HIPCHK(h, hipMemsetAsync(C.hw.p, 0xff, N1 * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.hw_own.p, 0xff, N1 * sizeof(float), h->stream));
+        HIPCHK(h, hipMemsetAsync(C.owned.p, 0, N1, h->stream));
+        HIPCHK(h, hipMemsetAsync(C.cnt.p, 0, 4 * sizeof(int), h->stream));
+        if (pos1 > pos0) {
+            const int np = pos1 - pos0;
+            LAUNCH(h, "k_tile_mark", k_tile_mark, (unsigned)((np + PCON_T - 1) / PCON_T), PCON_T, 0, h->sorted4.p, pos0, pos1, T, C.owned.p, C.cnt.p);
+            LAUNCH(h, "k_field_tile", k_field_tile, (unsigned)((np + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
+                   contact_index(h), dyn_params(h), pos0, pos1, T, pcov_range(h), C.curv.p, C.hw.p, C.hw_own.p, C.cnt.p + 2);
+        }
+        int cnt[3];
+        HIPCHK(h, copy_sync(h, cnt, C.cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
+        if (cnt[2])
+            return fail(h, PPP_ERR_CAPACITY, "contact field tile: a search of an evaluated point (its neighbours or their normals) reaches beyond the indexed slice range: raise range_margin");
+        if (cnt[0] < 0 || cnt[1] < cnt[0] || (size_t)cnt[1] > N) return fail(h, PPP_ERR_HIP, "contact field tile: counts corrupt");
+        ppp_contact_field_stats st;
+        rc = field_statistics(h, C.hw_own.p, C.acc, C.psum, min_width, st);
+        if (rc) return rc;
+        C.stats = {};
+        C.stats.owned = (size_t)cnt[0]; C.stats.evaluated = (size_t)cnt[1]; C.stats.own_lo = T.own_lo; C.stats.own_hi = T.own_hi;
+        tile_field_stats(C.stats, st);
+        C.P = h->P; C.halo = halo; C.min_width = min_width;
+        C.valid = true; ++C.built;
+    } else if (stats && min_width != C.min_width) {
+        ppp_contact_field_stats st;
+        int rc = field_statistics(h, C.hw_own.p, C.acc, C.psum, min_width, st);
+        if (rc) return rc;
+        tile_field_stats(C.stats, st);
+        C.min_width = min_width;
+    }
+    if (stats) *stats = C.stats;
+    const size_t k = std::min(cap, N);
+    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
+    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    if (owned && k) HIPCHK(h, copy_sync(h, owned, C.owned.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* lanes per selected point in k_reg_link */
+#ifndef REG_GROUP
+#define REG_GROUP 8
+#endif
+
+/* The device work of a region call, behind index_ready and the source's own call: select inside T's evaluated interval, list,
+   link, flatten (T's owned points count), label, the rows in ascending label -- into h->regions' buffers.  half_width: the map
+   PPP_REGIONS_NARROW reads.  nsel / nreg: the listed points and the regions (a tile's: every component of the list). */
+static int regions_compute(ppp_handle h, int source, const unsigned char *mask, const float *half_width, float threshold, float link,
+                           const TileRange &T, size_t &nsel, size_t &nreg, unsigned tot[4])
+{
+    const size_t N = h->n;
+    auto &R = h->regions;
+    R.valid = false;
+    nsel = nreg = 0;
+    const int ns = h->hmeta.n_sorted;
+    if (ns < 0 || (size_t)ns > N || N > 0x7fffffffu) return fail(h, PPP_ERR_HIP, "regions: index corrupt");
+    const size_t N1 = std::max<size_t>(N, 1);
+    const int nb_sel = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nb_head = (int)((N + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+    HIPCHK(h, R.labels.ensure(N1)); HIPCHK(h, R.head_root.ensure(N1)); HIPCHK(h, R.tot.ensure(8));
+    HIPCHK(h, R.cnt.ensure((size_t)std::max(nb_sel, nb_head) + 1));
+    HIPCHK(h, hipMemsetAsync(R.labels.p, 0xff, N1 * sizeof(int), h->stream)); /* not selected: -1 */
+    HIPCHK(h, hipMemsetAsync(R.tot.p, 0, 8 * sizeof(unsigned), h->stream));
+    int *err = (int *)R.tot.p + 3;
+    int rc = PPP_OK;
+    if (ns > 0) {
+        HIPCHK(h, R.sel.ensure((size_t)ns)); HIPCHK(h, R.ord.ensure((size_t)ns));
+        HIPCHK(h, hipMemsetAsync(R.ord.p, 0xff, (size_t)ns * sizeof(int), h->stream));
+        RegSource S = {source, nullptr, nullptr, nullptr, nullptr, threshold};
+        if (source == PPP_REGIONS_UNCOVERED) S.bytes = h->pcov.flags.p;
+        else if (source == PPP_REGIONS_OVERLAP) { S.first = h->pcon.first.p; S.last = h->pcon.last.p; }
+        else if (source == PPP_REGIONS_NARROW) S.half_width = half_width;
+        else {
+            HIPCHK(h, R.mask.ensure(N1));
+            HIPCHK(h, hipMemcpyAsync(R.mask.p, mask, N, hipMemcpyHostToDevice, h->stream));
+            S.bytes = R.mask.p;
+        }
+        LAUNCH(h, "k_reg_select", k_reg_select, (unsigned)((ns + REG_T - 1) / REG_T), REG_T, 0, h->sorted4.p, ns, S, T, R.sel.p);
+        RegSel sel = {R.sel.p, nullptr, R.ord.p, nullptr, nullptr};
+        rc = compact(h, sel, ns, R.cnt.p, (int *)R.tot.p + 4, [&](int kept) -> int {
+            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "regions: selection count corrupt");
+            nsel = (size_t)kept;
+            HIPCHK(h, R.list.ensure(nsel)); HIPCHK(h, R.parent.ensure(nsel)); HIPCHK(h, R.acc.ensure(nsel));
+            sel.list = R.list.p; sel.parent = R.parent.p; sel.acc = R.acc.p;
+            return PPP_OK;
+        });
+        if (rc) return rc;
+    }
+    if (nsel > 0) {
+        const float r2 = link * link;
+        int grp = REG_GROUP;
+        if (const char *ev = tuning_env("PPP_REG_GROUP")) grp = atoi(ev); /* tuning runs only */
+        const unsigned gl = (unsigned)((nsel * (size_t)grp + REG_T - 1) / REG_T), gp = (unsigned)((nsel + REG_T - 1) / REG_T);
+#define PPP_REG_LINK(G) LAUNCH(h, "k_reg_link", k_reg_link<G>, gl, REG_T, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_ytab.p, R.list.p, (int)nsel, R.ord.p, R.parent.p, link, r2, err)
+        if (grp == 1) PPP_REG_LINK(1);
+        else if (grp == 4) PPP_REG_LINK(4);
+        else if (grp == 16) PPP_REG_LINK(16);
+        else if (grp == 64) PPP_REG_LINK(64);
+        else if (grp == 8) PPP_REG_LINK(8);
+        else return fail(h, PPP_ERR_ARG, "regions: PPP_REG_GROUP must be 1, 4, 8, 16 or 64");
+#undef PPP_REG_LINK
+        LAUNCH(h, "k_reg_flatten", k_reg_flatten, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, T, err);
+        LAUNCH(h, "k_reg_labels", k_reg_labels, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, (int)N, R.labels.p,
+               R.head_root.p, R.tot.p);
+        RegHeadSel heads = {R.labels.p, R.head_root.p, R.acc.p, nullptr};
+        rc = compact(h, heads, (int)N, R.cnt.p, (int *)R.tot.p + 5, [&](int kept) -> int {
+            if (kept < 0 || (size_t)kept > nsel) return fail(h, PPP_ERR_HIP, "regions: region count corrupt");
+            nreg = (size_t)kept;
+            HIPCHK(h, R.rows.ensure(nreg));
+            heads.rows = R.rows.p;
+            return PPP_OK;
+        });
+        if (rc) return rc;
+    }
+    HIPCHK(h, copy_sync(h, tot, R.tot.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (tot[3]) return fail(h, PPP_ERR_CAPACITY, "regions: a union-find walk reached its trip cap");
+    if (tot[0] != nreg || tot[1] > nreg || tot[2] > nsel) return fail(h, PPP_ERR_HIP, "regions: totals corrupt");
+    return PPP_OK;
+}
+
+/* the opening of every region call (whole_cloud_begin) and its argument checks */
+static int regions_begin(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius)
+{
+    if (int rcb = whole_cloud_begin(h, "regions", "a region does not stop at a part's border")) return rcb;
+    if (source < PPP_REGIONS_UNCOVERED || source > PPP_REGIONS_MASK) return fail(h, PPP_ERR_ARG, "regions: unknown source");
+    if (source == PPP_REGIONS_MASK && !mask) return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_MASK needs a mask");
+    if (source == PPP_REGIONS_NARROW && !(threshold > 0.f && threshold <= 3.402823466e+38f))
+        return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_NARROW needs a positive finite threshold");
+    if (!(fabsf(link_radius) <= 3.402823466e+38f)) return fail(h, PPP_ERR_ARG, "regions: link_radius is not a finite number");
+    return PPP_OK;
+}
+
+/* could a region's fixed-point sum leave 64 bits?  then no centroid is given (B.34) */
+static bool regions_nan_centroid(double reach, size_t selected) { return reach * REG_FIXED * (double)selected >= 4611686018427387904.0; }
+
+int ppp_get_regions(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius, int *labels, size_t cap,
+                    ppp_region *regions, size_t region_cap, ppp_region_stats *stats)
+{
+    { int rca = regions_begin(h, source, mask, threshold, link_radius); if (rca) return rca; }
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
+        return fail(h, PPP_ERR_UNSUPPORTED, "regions: a region does not stop at a range border: a slice-range handle indexes a part of the cloud only");
+    const float link = link_radius > 0.f ? link_radius : h->P.normal_radius;
+    if (source != PPP_REGIONS_NARROW) threshold = 0.f;
+    /* the source's own call: builds its result if the handle does not hold it, answers from it if it does, refuses as it does */
+    unsigned long long serial = 0;
+    int rc = PPP_OK;
+    if (source == PPP_REGIONS_UNCOVERED) { rc = ppp_get_path_coverage(h, nullptr, 0, nullptr, nullptr); serial = h->pcov.serial; }
+    else if (source == PPP_REGIONS_OVERLAP) { rc = ppp_get_path_contacts(h, nullptr, nullptr, nullptr, 0, nullptr); serial = h->pcon.serial; }
+    else if (source == PPP_REGIONS_NARROW) { rc = ppp_get_contact_field(h, nullptr, nullptr, 0, 0.f, nullptr); serial = h->field.built; }
+    if (rc) return rc;
+    const size_t N = h->n;
+    auto &R = h->regions;
+    const bool reuse = source != PPP_REGIONS_MASK && R.valid && R.source == source && R.threshold == threshold && R.link == link &&
+                       R.serial == serial && R.stats.n == N;
+    if (!reuse) {
+        R.valid = false;
+        rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+        if (rc) return rc;
+        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "regions: a slice-range handle indexes a part of the cloud only");
+        double reach = 0.0; /* the largest |coordinate| of the index */
+        for (int d = 0; d < 3; ++d) reach = std::max(reach, std::max(std::fabs((double)h->hmeta.mn[d]), std::fabs((double)h->hmeta.mx[d])));
+        size_t nsel = 0, nreg = 0;
+        unsigned tot[4];
+        rc = regions_compute(h, source, mask, h->field.hw.p, threshold, link, TileRange{-INFINITY, INFINITY, -INFINITY, INFINITY}, nsel, nreg, tot);
+        if (rc) return rc;
+        ppp_region_stats st = {};
+        st.n = N; st.selected = nsel; st.regions = nreg; st.singletons = tot[1]; st.largest = tot[2];
+        R.stats = st;
+        R.nan_centroid = regions_nan_centroid(reach, nsel);
+        R.source = source; R.threshold = threshold; R.link = link; R.serial = serial;
+        R.valid = true;
+    }
+    if (stats) *stats = R.stats;
+    const size_t k = std::min(cap, N);
+    if (labels && k) HIPCHK(h, copy_sync(h, labels, R.labels.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    const size_t kr = std::min(region_cap, R.stats.regions);
+    if (regions && kr) {
+        std::vector<RegAcc> rows(kr);
+        HIPCHK(h, copy_sync(h, rows.data(), R.rows.p, kr * sizeof(RegAcc), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < kr; ++i) {
+            const RegAcc &a = rows[i];
+            ppp_region &o = regions[i];
+            o.label = a.label; o.count = a.count;
+            for (int c = 0; c < 3; ++c) {
+                o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]);
+                o.centroid[c] = R.nan_centroid ? (double)NAN : (double)a.sum[c] / (double)a.count / REG_FIXED;
+            }
+        }
+    }
+    return PPP_OK;
+}
+
+int ppp_get_regions_tile(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius, int *labels, size_t cap,
+                         ppp_region_part *parts, size_t part_cap, ppp_region_halo *halos, size_t halo_cap, ppp_region_tile_stats *stats)
+{
+    int rc = regions_begin(h, source, mask, threshold, link_radius);
+    if (rc) return rc;
+    if (source == PPP_REGIONS_UNCOVERED || source == PPP_REGIONS_OVERLAP)
+        return fail(h, PPP_ERR_UNSUPPORTED, "regions tile: a range's coverage knows its own slices' balls only: OR the ranges' flags (ppp_get_path_coverage) and pass the result as a mask (PPP_REGIONS_MASK)");
+    const float link = link_radius > 0.f ? link_radius : h->P.normal_radius;
+    if (source != PPP_REGIONS_NARROW) threshold = 0.f;
+    unsigned long long serial = 0;
+    if (source == PPP_REGIONS_NARROW) { /* the field of the owned points and a halo of one link radius */
+        rc = ppp_get_contact_field_tile(h, nullptr, nullptr, nullptr, 0, link, 0.f, nullptr);
+        if (rc) return rc;
+        serial = h->ftile.built;
+    }
+    const size_t N = h->n;
+    auto &Q = h->rtile;
+    const bool reuse = source != PPP_REGIONS_MASK && Q.valid && Q.source == source && Q.threshold == threshold && Q.link == link &&
+                       Q.serial == serial && Q.stats.n == N;
+    if (!reuse) {
+        Q.valid = false;
+        rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+        if (rc) return rc;
+        TileRange T;
+        rc = tile_range(h, link, T);
+        if (rc) return rc;
+        if (leaves_indexed_range(h, T.ev_lo, T.ev_hi))
+            return fail(h, PPP_ERR_CAPACITY, "regions tile: the owned interval widened by the link radius reaches beyond the indexed slice range: raise range_margin");
+        const unsigned char *owned_map = h->ftile.owned.p;
+        if (source == PPP_REGIONS_MASK) { /* the owned map of this range and link */
+            int pos0, pos1;
+            rc = tile_positions(h, T, pos0, pos1);
+            if (rc) return rc;
+            const size_t N1 = std::max<size_t>(N, 1);
+            HIPCHK(h, Q.owned.ensure(N1)); HIPCHK(h, Q.cnt.ensure(2));
+            HIPCHK(h, hipMemsetAsync(Q.owned.p, 0, N1, h->stream));
+            HIPCHK(h, hipMemsetAsync(Q.cnt.p, 0, 2 * sizeof(int), h->stream));
+            if (pos1 > pos0)
+                LAUNCH(h, "k_tile_mark", k_tile_mark, (unsigned)((pos1 - pos0 + PCON_T - 1) / PCON_T), PCON_T, 0, h->sorted4.p, pos0, pos1, T,
+                       Q.owned.p, Q.cnt.p);
+            owned_map = Q.owned.p;
+        }
+        size_t nsel = 0, nreg = 0;
+        unsigned tot[4];
+        rc = regions_compute(h, source, mask, h->ftile.hw.p, threshold, link, T, nsel, nreg, tot);
+        if (rc) return rc;
+        /* the tile's view of the device result: labels of the owned points, the components with an owned point, their halo points */
+        std::vector<unsigned char> own(N);
+        std::vector<RegAcc> rows(nreg);
+        Q.labels.assign(N, -1);
+        if (N) HIPCHK(h, copy_sync(h, own.data(), owned_map, N, hipMemcpyDeviceToHost));
+        if (N && nsel) HIPCHK(h, copy_sync(h, Q.labels.data(), h->regions.labels.p, N * sizeof(int), hipMemcpyDeviceToHost));
+        if (nreg) HIPCHK(h, copy_sync(h, rows.data(), h->regions.rows.p, nreg * sizeof(RegAcc), hipMemcpyDeviceToHost));
+        Q.parts.clear(); Q.halos.clear();
+        size_t selected = 0;
+        for (const RegAcc &a : rows) {
+            if (!a.count) continue; /* a component of halo points alone: its owners' tiles report it */
+            ppp_region_part o;
+            o.label = a.label; o.count = a.count;
+            for (int c = 0; c < 3; ++c) { o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]); o.fsum[c] = a.sum[c]; }
+            Q.parts.push_back(o);
+            selected += a.count;
+        }
+        auto has_part = [&](int label) {
+            auto it = std::lower_bound(Q.parts.begin(), Q.parts.end(), label, [](const ppp_region_part &r, int l) { return r.label < l; });
+            return it != Q.parts.end() && it->label == label;
+        };
+        for (size_t i = 0; i < N; ++i) {
+            if (own[i] == 1 || Q.labels[i] < 0) continue;
+            if (own[i] == 2 && has_part(Q.labels[i])) Q.halos.push_back(ppp_region_halo{(int)i, Q.labels[i]});
+            Q.labels[i] = -1;
+        }
+        ppp_region_tile_stats st = {};
+        st.n = N; st.selected = selected; st.parts = Q.parts.size(); st.halo_points = Q.halos.size();
+        for (int d = 0; d < 3; ++d) /* the whole cloud's bounds: the same on every handle of the cloud */
+            st.max_abs_coord = std::max(st.max_abs_coord, std::max(std::fabs((double)h->h_mn[d]), std::fabs((double)h->h_mx[d])));
+        st.own_lo = T.own_lo; st.own_hi = T.own_hi;
+        Q.stats = st;
+        Q.source = source; Q.threshold = threshold; Q.link = link; Q.serial = serial;
+        Q.valid = true;
+    }
+    if (stats) *stats = Q.stats;
+    const size_t k = std::min(cap, N), kp = std::min(part_cap, Q.parts.size()), kh = std::min(halo_cap, Q.halos.size());
+    if (labels && k) memcpy(labels, Q.labels.data(), k * sizeof(int));
+    if (parts && kp) memcpy(parts, Q.parts.data(), kp * sizeof(ppp_region_part));
+    if (halos && kh) memcpy(halos, Q.halos.data(), kh * sizeof(ppp_region_halo));
+    return PPP_OK;
+}
+
+int ppp_merge_region_tiles(size_t tiles, const int *const *labels, const ppp_region_part *const *parts, const ppp_region_halo *const *halos,
+                           const ppp_region_tile_stats *stats, int *out_labels, size_t cap, ppp_region *regions, size_t region_cap,
+                           ppp_region_stats *out_stats)
+{
+    if (!tiles || !labels || !parts || !halos || !stats) return PPP_ERR_ARG;
+    const size_t N = stats[0].n;
+    std::vector<size_t> first(tiles + 1, 0); /* node of (t, part j) = first[t] + j */
+    size_t selected = 0;
+    double reach = 0.0;
+    for (size_t t = 0; t < tiles; ++t) {
+        if (stats[t].n != N || !labels[t] || (stats[t].parts && !parts[t]) || (stats[t].halo_points && !halos[t])) return PPP_ERR_ARG;
+        for (size_t j = 1; j < stats[t].parts; ++j) if (!(parts[t][j - 1].label < parts[t][j].label)) return PPP_ERR_ARG;
+        first[t + 1] = first[t] + stats[t].parts;
+        selected += stats[t].selected;
+        reach = std::max(reach, stats[t].max_abs_coord);
+    }
+    auto node_of = [&](size_t t, int label) -> long long { /* -1: tile t has no part of that label */
+        const ppp_region_part *b = parts[t], *e = b + stats[t].parts;
+        const ppp_region_part *it = std::lower_bound(b, e, label, [](const ppp_region_part &r, int l) { return r.label < l; });
+        return it != e && it->label == label ? (long long)(first[t] + (size_t)(it - b)) : -1;
+    };
+    /* who owns a point: the one tile that labels it */
+    std::vector<int> owner(N, -1);
+    for (size_t t = 0; t < tiles; ++t)
+        for (size_t i = 0; i < N; ++i)
+            if (labels[t][i] >= 0) {
+                if (owner[i] >= 0) return PPP_ERR_ARG; /* owned twice */
+                owner[i] = (int)t;
+            }
+    const size_t nodes = first[tiles];
+    std::vector<size_t> parent(nodes);
+    for (size_t v = 0; v < nodes; ++v) parent[v] = v;
+    auto find = [&](size_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
+    for (size_t t = 0; t < tiles; ++t)
+        for (size_t e = 0; e < stats[t].halo_points; ++e) {
+            const ppp_region_halo &hp = halos[t][e];
+            if (hp.cloud_index < 0 || (size_t)hp.cloud_index >= N || owner[(size_t)hp.cloud_index] < 0) return PPP_ERR_ARG; /* nobody's point */
+            const size_t u = (size_t)owner[(size_t)hp.cloud_index];
+            const long long a = node_of(t, hp.label), b = node_of(u, labels[u][(size_t)hp.cloud_index]);
+            if (a < 0 || b < 0) return PPP_ERR_ARG;
+            const size_t ra = find((size_t)a), rb = find((size_t)b);
+            if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+        }
+    /* the merged rows: integer sums, minima and maxima (as ordered keys: the order the device's atomics fold in) */
+    struct Row { int label; unsigned long long count; unsigned kmn[3], kmx[3]; long long sum[3]; };
+    std::vector<Row> acc(nodes, Row{0x7fffffff, 0, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}});
+    for (size_t t = 0; t < tiles; ++t)
+        for (size_t j = 0; j < stats[t].parts; ++j) {
+            const ppp_region_part &p = parts[t][j];
+            Row &r = acc[find(first[t] + j)];
+            r.label = std::min(r.label, p.label); r.count += p.count;
+            for (int c = 0; c < 3; ++c) {
+                r.kmn[c] = std::max(r.kmn[c], ordered_key(-p.mn[c])); r.kmx[c] = std::max(r.kmx[c], ordered_key(p.mx[c]));
+                r.sum[c] = (long long)((unsigned long long)r.sum[c] + (unsigned long long)p.fsum[c]);
+            }
+        }
+    std::vector<size_t> roots;
+    for (size_t v = 0; v < nodes; ++v) if (parent[v] == v) roots.push_back(v);
+    std::sort(roots.begin(), roots.end(), [&](size_t a, size_t b) { return acc[a].label < acc[b].label; });
+    ppp_region_stats st = {};
+    st.n = N; st.selected = selected; st.regions = roots.size();
+    for (size_t v : roots) { st.singletons += acc[v].count == 1; st.largest = std::max(st.largest, (size_t)acc[v].count); }
+    if (out_stats) *out_stats = st;
+    const bool nan_centroid = regions_nan_centroid(reach, selected);
+    const size_t kr = std::min(region_cap, roots.size());
+    for (size_t i = 0; regions && i < kr; ++i) {
+        const Row &a = acc[roots[i]];
+        ppp_region &o = regions[i];
+        o.label = a.label; o.count = (unsigned)a.count;
+        for (int c = 0; c < 3; ++c) {
+            o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]);
+            o.centroid[c] = nan_centroid ? (double)NAN : (double)a.sum[c] / (double)o.count / REG_FIXED;
+        }
+    }
+    const size_t k = std::min(cap, N);
+    for (size_t i = 0; out_labels && i < k; ++i) {
+        out_labels[i] = -1;
+        if (owner[i] < 0) continue;
+        const long long v = node_of((size_t)owner[i], labels[(size_t)owner[i]][i]);
+        if (v < 0) return PPP_ERR_ARG; /* a label without its part row */
+        out_labels[i] = acc[find((size_t)v)].label;
+    }
+    return PPP_OK;
+}
+
+} // extern "C"

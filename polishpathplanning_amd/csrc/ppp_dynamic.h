@@ -542,7 +542,13 @@ struct ContactIndex {
     __device__ inline SlabView view() const { return SlabView{sorted4, slab_start, slab_xmin, slab_xmax, m, nullptr, 0, 0, ytab}; }
 };
 
-/* API: Area2Cloud for k query points (one wave each) */
+/* API: Area2Cloud for k query points (one wave each).  ppp_area2cloud (ppp_contact.hip) launches it; it is compiled in the engine's
+   unit beside the chain kernels below, as it always was: wave_area2cloud is inlined into them in a different order without this
+   caller next to them, and k_dyn_adjust_pts and k_dyn_first_eval come out with other register counts (193 for 195 VGPRs, 103
+   for 104 SGPRs) */
+#ifdef PPP_KERNELS_FOREIGN
+__global__ void k_area2cloud_api(ContactIndex I, DynParams D, const double *__restrict__ pts, int k, int key, float *out);
+#else
 __global__ void __launch_bounds__(64 * DYN_WAVES) k_area2cloud_api(ContactIndex I, DynParams D, const double *__restrict__ pts, int k,
                                                                    int key, float *out)
 {
@@ -561,6 +567,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_area2cloud_api(ContactIndex 
     wave_area2cloud(V, G, s_w[wv], I.normals4, s_ell, D, p, key, b, sc);
     if ((threadIdx.x & 63) == 0) { out[3 * q] = b[0]; out[3 * q + 1] = b[1]; out[3 * q + 2] = b[2]; }
 }
+#endif
 
 /* ------------------------------------------------------------------ */
 /* The slice-to-slice chains (thread_worker, path_dynamic_alg.cpp:308-334; GenPath of            */
@@ -769,7 +776,7 @@ __device__ inline void spline_point_f(const float *ny, const float *nx, const fl
    from the slice's own spline (:278-284), and so is the final snap (:291-294) of a node the bisection leaves where it is:
    neither depends on the neighbour's boundary.  They are evaluated here for all slices at once, ahead of the chain, which
    then starts every node at its first comparison.  One wave per node; blockIdx.y = slice. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_first_eval(DevMeta *m, DynParams D, int walk, int centre,
+PPP_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_dyn_first_eval(DevMeta *m, DynParams D, int walk, int centre,
         const float4 *__restrict__ sorted4, const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
         const float *__restrict__ slab_xmax, const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
         const float *__restrict__ node_x, const float *__restrict__ node_y, const float *__restrict__ node_z,
@@ -844,7 +851,7 @@ __device__ inline double dyn_boundary_dy(const DynParams &D, double miny, int j)
    itself, which costs less than a launch of its own between two dependent kernels; one extra workgroup per chain, which
    has no samples, commits the knots to the node arrays -- and goes on with compute_boundary's first half (:191-203) on those knots: one wave per
    sample of the previous path. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_boundary_pts(DevMeta *m, DynParams D, int walk, int t, int centre,
+PPP_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_dyn_boundary_pts(DevMeta *m, DynParams D, int walk, int t, int centre,
         const float4 *__restrict__ sorted4, const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
         const float *__restrict__ slab_xmax, const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
         float *node_x, float *node_y, float *node_z, int node_cap, int *node_start, int *node_cnt, DynBuffers Bf)
@@ -921,7 +928,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_boundary_pts(DevMeta *m,
    workgroup for itself, the knots staying in its LDS; workgroup 0 of the chain keeps the copy in HBM that a later step falls
    back to when its own boundary has fewer than 3 knots -- and goes on with dynamic_adjust_path's first half (:278-295),
    one wave per node, from the node's first comparison on (its first Area2Cloud is k_dyn_first_eval's). */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_adjust_pts(DevMeta *m, DynParams D, int walk, int t, int centre,
+PPP_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_dyn_adjust_pts(DevMeta *m, DynParams D, int walk, int t, int centre,
         const float4 *__restrict__ sorted4, const int *__restrict__ slab_start, const float *__restrict__ slab_xmin,
         const float *__restrict__ slab_xmax, const float4 *__restrict__ normals4, const float *__restrict__ ell_cs, const int *__restrict__ ytab,
         int S_cap, DynBuffers Bf)
@@ -1046,7 +1053,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_dyn_adjust_pts(DevMeta *m, D
 
 /* dynamic_adjust_path, second half (:297-305) as a launch of its own: after the last step of the chains (every earlier step
    is finished by the next step's first launch) */
-__global__ void __launch_bounds__(256) k_dyn_adjust_fit(DevMeta *m, int walk, int t, int centre, DynBuffers Bf, float *node_x,
+PPP_KERNEL void __launch_bounds__(256) k_dyn_adjust_fit(DevMeta *m, int walk, int t, int centre, DynBuffers Bf, float *node_x,
                                                         float *node_y, float *node_z, int node_cap, int *node_start, int *node_cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char s_raw[];

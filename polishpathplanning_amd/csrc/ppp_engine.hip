@@ -1,23 +1,21 @@
 /*
- * ppp_engine.hip -- host side of the C ABI declared in include/ppp_hip.h.
+ * ppp_engine.hip -- host side of the C ABI declared in include/ppp_hip.h: the handle, the plan and the passes.
  *
  * One handle = one device, one HIP stream, one resident cloud.  All device memory is
  * allocated when the cloud / parameters are set (the "plan"); the two hot calls
  * ppp_gen_path_async / ppp_get_path_async only enqueue kernels -- no allocation, no host
  * synchronisation -- so a caller may overlap handles, capture them, or time them.
  * There is no CPU fallback: without a HIP device every entry point fails loudly.
+ *
+ * Here: create / destroy, parameters, cloud ingest, the plan, the slab and window passes, the dynamic chain, the arena re-run,
+ * graphs and batches, gather, sync, the getters, the API mirrors, ppp_spline_*, settings and kernel timing.  The contact
+ * queries are ppp_contact.hip's, the preprocessing calls ppp_preproc.hip's; what the three share is ppp_handle.h.
  */
 #include "ppp_kernels.h"
-#ifdef PPP_SINGLE_TU /* diagnostic builds (in-kernel stamps share one g_stamps array): the window kernels in this translation unit */
+#ifdef PPP_SINGLE_TU /* diagnostic builds (in-kernel stamps share one g_stamps array): every kernel in this translation unit */
 #include "ppp_window.h"
-#else
-#include "ppp_window_decl.h" /* their kernels are ppp_window.hip's */
 #endif
-#include "ppp_preproc.h" /* (ppp_dynamic.h with it) */
-#include "ppp_contact.h"
-#include "ppp_regions.h"
-#include "ppp_sort.h"
-#include "ppp_align.h"
+#include "ppp_handle.h" /* (the window kernels' declarations with it: they are ppp_window.hip's) */
 #include "ppp_gather.h"
 #include <atomic>
 #include <cerrno>
@@ -70,449 +68,21 @@
 
 #define PPP_VERSION_STR "polishpathplanning_amd 0.1 (gfx950)"
 
-namespace {
-
-struct KTimer {
-    std::string name;
-    std::vector<hipEvent_t> e0, e1; /* one pair per launch of this kernel in a pass */
-    int used = 0;
-};
-
-/* memory owned by one object: ensure() grows it (the contents are not kept), release() frees it early, the destructor
-   frees it.  Move-only.  Device memory (DevBuf) or pinned host memory (PinBuf). */
-template <typename T, bool PINNED>
-struct OwnedBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    OwnedBuf() = default;
-    OwnedBuf(const OwnedBuf &) = delete;
-    OwnedBuf &operator=(const OwnedBuf &) = delete;
-    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    OwnedBuf &operator=(OwnedBuf &&o) noexcept
-    {
-        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~OwnedBuf() { release(); }
-    hipError_t ensure(size_t n)
-    {
-        if (n <= cap && p) return hipSuccess;
-        release();
-        if (n == 0) n = 1;
-        hipError_t e = PINNED ? hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, n * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() { if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
-};
-template <typename T> using DevBuf = OwnedBuf<T, false>;
-template <typename T> using PinBuf = OwnedBuf<T, true>;
-
-/* where the meta block of the pass just enqueued will turn up on the host */
-struct MetaAt {
-    enum Kind { ON_DEMAND /* nowhere: copied when somebody asks */, PINNED /* the handle's hmeta_pinned */, BATCH_SLOT /* entry slot of a batch's pinned array */ };
-    Kind kind = ON_DEMAND;
-    std::shared_ptr<PinBuf<DevMeta>> batch; /* batched launches publish every member's meta block in one pinned array, shared with the members that read it */
-    size_t slot = 0;
-    static MetaAt on_demand() { return MetaAt(); }
-    static MetaAt pinned() { MetaAt a; a.kind = PINNED; return a; }
-    static MetaAt batch_slot(const std::shared_ptr<PinBuf<DevMeta>> &metas, size_t i) { MetaAt a; a.kind = BATCH_SLOT; a.batch = metas; a.slot = i; return a; }
-};
-
-/* What a handle knows about its plan and its last pass.  The members change only through the transitions below, each named
-   for what happened on the handle; the queries' caches (coverage, contacts, regions, the knots' host copy) key on serial(). */
-class PassState {
-    bool planned_ = false, index_built_ = false, gen_done_ = false, path_done_ = false;
-    bool list_final_ = false;    /* wp_out holds a finished WayPointsList */
-    bool stage_compact_ = true;  /* wp_xyz / wp_nn / wp_normal hold the list order (a window pass leaves them in per-slice slots) */
-    unsigned long long serial_ = 0; /* counts the GenPaths enqueued */
-    bool meta_fresh_ = false;    /* hmeta is the device's block as of now: nothing was launched on this handle since it was fetched (every launch clears it) */
-    MetaAt meta_at_;             /* where the copy enqueued behind the last pass lands (ON_DEMAND: none was enqueued) */
-    hipStream_t pending_stream_ = nullptr; /* a batch graph launched on another handle's stream carries this handle's work */
-    void withdraw_results() { index_built_ = false; gen_done_ = false; meta_fresh_ = false; path_done_ = false; list_final_ = false; }
-
-public:
-    bool planned() const { return planned_; }
-    bool index_built() const { return index_built_; }
-    bool gen_done() const { return gen_done_; }
-    bool path_done() const { return path_done_; }
-    bool list_final() const { return list_final_; }
-    bool stage_compact() const { return stage_compact_; }
-    unsigned long long serial() const { return serial_; }
-    bool meta_fresh() const { return meta_fresh_; }
-    bool meta_in_flight() const { return meta_at_.kind != MetaAt::ON_DEMAND; }
-    /* the block the copy in flight lands in (handle_block: the handle's own pinned one) */
-    const DevMeta *meta_landing(const DevMeta *handle_block) const
-    {
-        return (meta_at_.kind == MetaAt::BATCH_SLOT && meta_at_.batch) ? meta_at_.batch->p + meta_at_.slot : handle_block;
-    }
-    hipStream_t pending_stream() const { return pending_stream_; }
-
-    /* no plan, no index, no results */
-    void withdraw_plan() { planned_ = false; withdraw_results(); }
-    void plan_made() { stage_compact_ = true; planned_ = true; withdraw_results(); }
-    /* a cloud was set without waiting for its bounds: results and index are gone, the plan stays */
-    void cloud_replaced_under_plan() { withdraw_results(); }
-    void index_enqueued() { index_built_ = true; }
-    void gen_enqueued(bool window) { if (window) stage_compact_ = false; gen_done_ = true; ++serial_; path_done_ = false; }
-    /* getPath (a window pass's stage lists stay as they are: still in slots, or gathered since) */
-    void path_enqueued(bool final, bool window) { path_done_ = true; list_final_ = final; if (!window) stage_compact_ = true; }
-    /* GenPath and getPath at once (a graph launch); carrier: the other handle's stream the work runs on */
-    void pass_enqueued(bool window, bool final, MetaAt at, hipStream_t carrier = nullptr)
-    {
-        if (!window) index_built_ = true;
-        stage_compact_ = !window;
-        gen_done_ = true; ++serial_; path_done_ = true;
-        list_final_ = final;
-        meta_will_arrive(std::move(at));
-        pending_stream_ = carrier;
-    }
-    /* a new plan turned out to ask for the very launches the last pass ran: its results stand */
-    void restore_results(bool had_path, bool was_final) { gen_done_ = true; path_done_ = had_path; list_final_ = was_final; }
-    void stages_gathered() { stage_compact_ = true; }
-    void streams_settled() { pending_stream_ = nullptr; }
-    /* (a batch's pinned array stays referenced until a later batch's takes its place, whatever arrives in between: no getter
-       ends up freeing pinned memory) */
-    void meta_will_arrive(MetaAt at)
-    {
-        if (at.kind == MetaAt::BATCH_SLOT) meta_at_ = std::move(at); else meta_at_.kind = at.kind;
-        meta_fresh_ = false;
-    }
-    void meta_stale() { meta_fresh_ = false; }
-    void meta_read() { meta_at_.kind = MetaAt::ON_DEMAND; meta_fresh_ = true; }
-};
-
-} // namespace
-
-struct ppp_handle_s {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    ppp_params P;
-    float vp[3] = {0, 0, 0};
-    size_t n = 0;
-    bool have_cloud = false;
-    PassState pass; /* the plan and the last pass: what is planned, built, enqueued, and where its meta block arrives */
-    /* host copy of the knots of the last pass (slice tables + node arrays), fetched whole by the first ppp_get_nodes after a pass:
-       the planner classes ask slice by slice (a Spline view per slice: 2 calls x 256 slices), and a synchronous copy of a few
-       bytes costs ~20 us on this runtime -- 60 ms of GenPath() for 0.07 ms of planning before this cache */
-    unsigned long long hn_serial = ~0ull; /* the pass (pass.serial()) the copy belongs to */
-    std::vector<int> hn_off;    /* S + 1 offsets into ... */
-    std::vector<float> hn_xyz;  /* ... three planes (x | y | z) of hn_off[S] floats */
-    DevBuf<int> pack_tab;       /* device: node_start as the host validated it, then the offsets */
-    DevBuf<float> pack_out;
-    int max_lds = 65536;
-    int num_cus = 256;
-
-    /* plan */
-    int B = 1, slab_cap = 4096, S_cap = 1, capb = 2048, W_cap = 1, node_cap = 1;
-    int knot_cap = 2048, stage_cap = POSE_STAGE_CAP, tab_slabs = 8, pose_threads = POSE_T, cnt_est = 1; /* launch geometry of k_pose (make_plan) */
-    float pose_pad = 8.f;
-    float h_mn[3] = {0, 0, 0}, h_mx[3] = {0, 0, 0};
-    int h_nvalid = 0;
-    /* slice-range handles (SURVEY.md 8e case ii) */
-    bool ranged = false;          /* plans a strict sub-range of the slices: getPath stops after a12 */
-    /* trans2center ran (Alignment = true): TransAlign, its inverse, and a second handle holding the cloud carried back by
-       the inverse with its own slab index (path_translation_alg.cpp:171-174 searches and estimates normals there) */
-    bool aligned = false;
-    float TA[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}}, invTA[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    ppp_handle back = nullptr;
-    int sb = 0, se = 0;           /* the range, resolved against the walk */
-    float incl_lo = -INFINITY, incl_hi = INFINITY;
-    int n_range = 0;              /* expected number of indexed points */
-
-    DevBuf<float> X, Y, Z;
-    /* slice-range handles: the points of [incl_lo, incl_hi] in cloud order with their cloud indices (built by make_plan):
-       the hot path streams these instead of the whole cloud */
-    DevBuf<float> Xp, Yp, Zp;
-    DevBuf<int> part_idx;
-    int n_part = 0;
-    bool use_part = false;
-    /* ppp_set_cloud_part: the resident cloud IS a part (every point with x in [part_lo, part_hi], cloud order); the whole
-       cloud's bounds and point count came with it, part_idx (optional) holds the points' cloud indices */
-    bool part_given = false;
-    bool part_has_idx = false;
-    float part_lo = 0.f, part_hi = 0.f;
-    DevBuf<float4> unsorted4, sorted4;
-    DevBuf<int> slab_cnt, slab_start, slab_cursor, coarse_cursor, slab_ytab;
-    bool two_pass_scatter = false; /* large clouds: coarse bins first (see k_slab_scatter) */
-    DevBuf<float> slab_xmin, slab_xmax;
-    DevBuf<DevMeta> meta;
-    DevBuf<float> px, lo, hi;
-    DevBuf<float> node_x, node_y, node_z;
-    /* dynamic adjustment (allocated when Dynamic_adjustment is on or ppp_area2cloud is used) */
-    DevBuf<float4> normals4, dyn_bnd_pts, dyn_adj_pts, dyn_first_ab, dyn_first_snap;
-    DevBuf<double> dyn_first_node;
-    DevBuf<float> ell_cs;
-    DevBuf<double> dyn_bnd_knots;
-    DevBuf<int> dyn_bnd_n;
-    int dyn_maxNB = 1, dyn_maxNA = 1;
-    bool dyn_keep_all = false;
-    DevBuf<int> dyn_raw_sc;           /* [slice][2]: node_start / node_cnt as fitted, before the chain (k_dyn_first_eval) */
-    /* coverage of the last pass (ppp_get_coverage): flags by cloud index, zero-padded to 16 bytes, and the covered count */
-    /* path coverage of the last pass (ppp_get_path_coverage): the same, for the final paths of every walk; [1] of the count
-       buffer holds the kernel's refusals (1: a search left the indexed slice range, 2: a knot table out of bounds) */
-    struct FlagCoverage { DevBuf<unsigned char> flags; DevBuf<int> count; unsigned long long serial = ~0ull /* the pass (pass.serial()) they belong to */; size_t covered = 0; } cov, pcov;
-    /* path contacts of the last pass (ppp_get_path_contacts): the maps by cloud index, the per-slice sample table (rows from
-       off; its last two entries the row count and k_pcon_offsets's refusals), the slices' reach keys and the statistics
-       (acc: bins, covered, multi_slice, total, max, the refusal word; the int at acc + 69 is where the kernels set it) */
-    struct PathContacts {
-        DevBuf<unsigned> counts, reach;
-        DevBuf<int> first, last, off;
-        DevBuf<float4> tab;
-        DevBuf<unsigned long long> acc;
-        unsigned long long serial = ~0ull;
-        ppp_contact_stats stats = {};
-    } pcon;
-    /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
-       valid for P's contact parameters until the cloud changes (valid) */
-    struct ContactField {
-        DevBuf<float> curv, hw;
-        DevBuf<unsigned long long> acc;
-        DevBuf<double> psum;
-        bool valid = false;
-        unsigned long long built = 0; /* how many times the maps were computed: what a result derived from them belongs to */
-        ppp_params P = {};
-        float min_width = 0.f;
-        ppp_contact_field_stats stats = {};
-    } field;
-    /* the contact field of the points this handle owns (ppp_get_contact_field_tile): the maps of the evaluated points by cloud
-       index, hw_own = the half widths of the owned points alone (what the statistics read), the owned map, cnt = owned points,
-       evaluated points, the refusal word; kept for P's contact parameters and range and for halo until the cloud changes */
-    struct FieldTile {
-        DevBuf<float> curv, hw, hw_own;
-        DevBuf<unsigned char> owned;
-        DevBuf<int> cnt;
-        DevBuf<unsigned long long> acc;
-        DevBuf<double> psum;
-        bool valid = false;
-        unsigned long long built = 0;
-        ppp_params P = {};
-        float halo = 0.f, min_width = 0.f;
-        ppp_contact_field_tile_stats stats = {};
-    } ftile;
-    /* the regions of this handle's tile (ppp_get_regions_tile), as the call hands them out; the device work runs in `regions` */
-    struct RegionTile {
-        bool valid = false;
-        int source = -1;
-        float threshold = 0.f, link = 0.f;
-        unsigned long long serial = 0;
-        std::vector<int> labels;
-        std::vector<ppp_region_part> parts;
-        std::vector<ppp_region_halo> halos;
-        ppp_region_tile_stats stats = {};
-        DevBuf<unsigned char> owned; /* a MASK call's owned map (NARROW reads the field tile's: the same range and halo) */
-        DevBuf<int> cnt;
-    } rtile;
-    /* connected regions (ppp_get_regions): the selection by slab-index position, the dense list of the selected positions and
-       its inverse (ord), the union-find and the accumulators by ordinal, the labels by cloud index, the region rows in label
-       order; tot: regions, singletons, largest, the refusal word, then the two compaction totals.  Kept for (source, threshold,
-       link, serial of the source's result) */
-    struct Regions {
-        DevBuf<unsigned char> sel, mask;
-        DevBuf<int> list, ord, parent, labels, head_root, cnt;
-        DevBuf<RegAcc> acc, rows;
-        DevBuf<unsigned> tot;
-        bool valid = false, nan_centroid = false;
-        int source = -1;
-        float threshold = 0.f, link = 0.f;
-        unsigned long long serial = 0;
-        ppp_region_stats stats = {};
-    } regions;
-    DevBuf<int> node_start, node_cnt, band_cnt;
-    DevBuf<int> wp_cnt, wp_off, tail, slice_wpcnt;
-    DevBuf<float4> wp_xyz, wp_normal;
-    DevBuf<int> wp_nn;
-    DevBuf<float> wp_pre, wp_smooth, wp_out;
-    DevBuf<MinMaxPart> mm_part;
-    DevBuf<int> big_slabs, big_slices; /* work lists of the LDS-overflow fallback kernels */
-    DevBuf<char> arena;                /* their global scratch, allocated on first need */
-    bool big_path = false;             /* launch the fallback kernels (set by the plan or after an overflow) */
-    int mm_grid = 1, sm_tiles = 1;
-    DevBuf<char> scratch; /* API staging */
-    /* window path (ppp_window.h): three launches, every point binned once into the window of its slice */
-    bool win_allowed = true;    /* ppp_set_fast_path */
-    bool win_disabled = false;  /* a pass was handed back (overflow / reach / stale plan): this cloud + parameters stay on the slab path */
-    bool win_path = false;      /* the current plan runs the window path */
-    bool win_staged = false;    /* the binning launch writes through LDS in window order (large clouds, ppp_window.h) */
-    float win_pad = 4.f;
-    int win_NBc_thr = 0; /* y-buckets per class in launches of several workgroups per CU: the most that cost no workgroup its place in the LDS */
-    int win_capw = 0, win_cap_el = 0, win_NB = 0, win_NBc = 0, win_stride = 1, win_threads = 256, win_ppt = 4, win_gs = 1;
-    int win_rec_lds = 0; /* waypoint records parked in the slice workgroup's LDS (0: in global slots) */
-    int win_nkept = 0, win_first_kept = 0, win_el_expect = 0;
-    float win_px0 = 0.f;
-    DevBuf<float> win_px;
-    DevBuf<int> win_cnt;
-    DevBuf<float4> win_pts;
-    DevBuf<MinMaxPart> win_part;
-    DevBuf<float4> wps_xyz, wps_normal, wps_rec;
-    DevBuf<int> fin_ticket; /* arrivals of the window finish launch's workgroups (the last one publishes the meta block) */
-    DevBuf<int> wps_nn;
-    DevBuf<float> wps_pre;
-
-    DevMeta hmeta;
-    PinBuf<DevMeta> hmeta_pinned; /* the hot calls end with an async copy of the device meta into it */
-    /* a new cloud's plan without the host in the middle: k_ingest_minmax's last workgroup reduces the bounds and walks the slices,
-       k_win_census_auto counts the windows, both write their results to pinned memory (PlanAuto + plane table + census) */
-    DevBuf<int> plan_ticket;         /* [2], zero between launches */
-    DevBuf<PlanAuto> plan_auto;
-    bool auto_valid = false;         /* the pinned census belongs to the cloud just set, with auto_S slices and auto_pad */
-    /* Plan reuse: a planner that is fed one scan after the other plans clouds of one size with one set of parameters.  The first
-       plan takes its window capacities from a census of that cloud; a later cloud with the same point count, parameters, slice
-       count and pad inherits them (+4 %) and skips the census launch -- the pass itself detects a window that does not fit
-       (WIN_FLAG_OVERFLOW), and the plan is then made again from a census of its own */
-    bool plan_reuse = true;          /* ppp_set_plan_reuse */
-    bool inh_valid = false;          /* the members below describe a census-based window plan of this handle */
-    int inh_S = 0, inh_n = 0, inh_max_w = 0, inh_max_el = 0;
-    float inh_pad = 0.f;
-    ppp_params inh_P;
-    bool auto_px_only = false;       /* the cloud just set brought walk + pad along (auto_S, auto_pad, pinned plane table), but no census */
-    bool plan_inherited = false;     /* the current window plan's capacities are inherited */
-    int auto_S = 0;
-    float auto_pad = 0.f;
-    bool slab_cnt_used = true;       /* a slab-path pass has been enqueued since the slab histogram was last cleared by the plan */
-    PinBuf<char> pin;                /* pinned staging for the small copies of the plan (bounds partials, plane table, census) */
-    PinBuf<char> pcd_stage[2];       /* ppp_set_cloud_pcd: two pinned pieces ... */
-    hipEvent_t pcd_ev[2] = {nullptr, nullptr}; /* ... and the event behind each one's copy */
-    /* A cloud set while the handle holds a window plan of an earlier cloud of the same size and parameters does not wait for its
-       bounds: the conversion pass is enqueued, the plan stays, and the pass of the new cloud may be enqueued right
-       behind it -- the device checks walk length, pad, bounds and capacities against the record that pass leaves, and hands a
-       pass back whose plan does not fit.  plan_deferred: that record has not been read yet (resolve_deferred does, at the first
-       call that is not one of the three enqueue-only entry points). */
-    int side_by_side = 1; /* handles the caller runs side by side on this device (ppp_set_side_by_side): from two on the slice workgroups of small windows stay at 512 threads */
-    bool plan_deferred = false, deferred_census = false;
-    bool rec_current = false;   /* plan_auto holds the record of the resident cloud (it came through k_ingest_minmax and was not altered since) */
-    bool plan_walk_ok = false;  /* the window plan's S, pad and plane table are the device's own, bit for bit (plan_window: census that came with the cloud, or inherited) */
-    bool chain_calls = false;       /* GenPath is followed by getPath in the same enqueue: its meta copy is skipped */
-    float *out2 = nullptr;          /* batched form: the emitting launch also writes the list here (at most out2_cap rows) */
-    int out2_cap = 0;
-    float *last_out2 = nullptr;     /* where the last batch put this handle's list: a re-run after an LDS overflow writes there too */
-    int last_out2_cap = 0;
-    int internal = 0;               /* > 0 while GenPath / getPath are enqueued on behalf of a batch or a re-run (keeps last_out2) */
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    unsigned epoch = 0;                 /* bumped whenever the launch sequence of this handle changes */
-    unsigned graph_epoch_seen = ~0u;    /* ppp_run_async: the plan epoch of the last call (the first call of a plan runs eagerly) */
-    struct BatchGraph *batches[2] = {nullptr, nullptr}; /* cached batch graphs (lead handle only): two, so a caller can
-                                                           alternate between two destination buffers (double buffering) */
-    int batch_next = 0;                                 /* slot the next new graph replaces */
-    bool timing = false;
-    std::vector<KTimer> timers;
-
-    void drop_graph()
-    {
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        graph_exec = nullptr; graph = nullptr;
-        ++epoch;
-    }
-    void drop_batch();
-    /* the resident cloud changed: what was made of the old points goes, the contact field with it.  under_plan: the cloud was
-       set without waiting for its bounds (refresh_bounds_and_plan), and the plan stays */
-    void cloud_replaced(bool under_plan = false)
-    {
-        if (under_plan) pass.cloud_replaced_under_plan(); else pass.withdraw_plan();
-        field.valid = false; ftile.valid = false; rtile.valid = false;
-    }
-    ~ppp_handle_s()
-    {
-        /* the members' buffers are freed after this body, on the device it selects (`back` lives on the same device) */
-        (void)hipSetDevice(device);
-        drop_graph();
-        drop_batch();
-        for (int b = 0; b < 2; ++b) if (pcd_ev[b]) (void)hipEventDestroy(pcd_ev[b]);
-        for (auto &t : timers) { for (auto e : t.e0) (void)hipEventDestroy(e); for (auto e : t.e1) (void)hipEventDestroy(e); }
-        if (stream) (void)hipStreamDestroy(stream);
-        if (back) { delete back; back = nullptr; }
-    }
-};
-
-/* Launch geometry of a slab pass: what the stage launches need beside the record (SlabArgs).  slab_geom decides it for ONE
-   handle; a batch joins its members' and launches every stage once with the result.  The defaults are the floors a batch
-   starts from. */
-struct SlabGeom {
-    float slab_x0 = 0.f, slab_invw = 0.f; /* the slab grid */
-    int g_minmax = 1, g_scatter = 1, g_scatter2 = 1, g_sort = 1, g_slice = 1, g_pose = 1, g_smooth = 1; /* workgroups per stage (g_scatter2: the second level of the two-level scatter, 4 points per thread) */
-    int first_slab = 0;         /* a slice-range handle sorts the g_sort slabs of its interval only */
-    int ppt = 4;                /* points per scatter thread: 4, 8 or 16 */
-    int B = 1, slab_cap = 2048, capb = 1024; /* slabs, points of a slab and of a band in LDS */
-    bool full_slabs = false;    /* slabs beyond the planned 832 points: the sort's wide form */
-    bool two_fit = true;        /* two slice workgroups' bands fit a CU's LDS */
-    long long slices = 0;       /* slice workgroups of the launch */
-    int pose_threads = 256;
-    size_t pose_lds = 0;
-    size_t hist_lds() const { return sizeof(int) * (size_t)B; }
-    /* threads per slab: 256 while a slab holds the planned 832 points on average (more slabs in flight per CU: cfg 2 sorts in
-       15.3 us against 17.0), SORT_T for the fuller slabs of clouds beyond the 8192-slab cap (cfg 5: 125 us against 157) */
-    int sort_threads() const { return full_slabs ? SORT_T : 256; }
-    size_t sort_lds() const { return (size_t)slab_cap * 12 + 16; }
-    /* Threads of a k_slice_kd workgroup.  One workgroup per slice with the band in LDS: 1024 threads finish a slice soonest
-       (one round of nearest-neighbour queries for bands of up to 2048 points), and that is what counts while the slices of a
-       launch fit the GPU in one go.  With several times more slices than CUs (batches of workpieces) two 512-thread
-       workgroups per CU get more slices through -- if two bands fit the CU's LDS. */
-    int slice_threads(int num_cus) const { return (two_fit && slices >= 2LL * num_cus) ? 512 : SLICE_KD_T; }
-    size_t slice_lds() const { return slice_kd_bytes(capb); }
-    size_t brute_lds() const { return slice_lds_bytes(capb); } /* k_slice, the brute pairing's generic form */
-    /* a batch: every stage is launched for its widest member (a narrower member's surplus workgroups leave at once) */
-    void join(const SlabGeom &o)
-    {
-        g_minmax = std::max(g_minmax, o.g_minmax); g_scatter = std::max(g_scatter, o.g_scatter); g_sort = std::max(g_sort, o.g_sort);
-        g_slice = std::max(g_slice, o.g_slice); g_pose = std::max(g_pose, o.g_pose); g_smooth = std::max(g_smooth, o.g_smooth);
-        ppt = std::max(ppt, o.ppt); B = std::max(B, o.B); slab_cap = std::max(slab_cap, o.slab_cap); capb = std::max(capb, o.capb);
-        full_slabs = full_slabs || o.full_slabs; two_fit = two_fit && o.two_fit;
-        slices += o.slices; /* (summed: the two-workgroup rule looks at the launch, and the launch is the batch's) */
-        pose_threads = std::max(pose_threads, o.pose_threads); pose_lds = std::max(pose_lds, o.pose_lds);
-    }
-};
-
-struct BatchGraph {
-    std::vector<ppp_handle> hs;
-    std::vector<unsigned> epochs;
-    float *dst = nullptr;
-    std::vector<size_t> off, cap;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    hipEvent_t fork = nullptr;
-    std::vector<hipEvent_t> join;
-    /* batched form (one launch per stage over all members): the members' records and meta blocks */
-    bool batched = false, eager = false; /* eager: launched directly every time (kernel timing), no graph */
-    SlabGeom geom; /* launch geometry over all members (slab path) */
-    DevBuf<SlabArgs> members;
-    bool win = false;              /* every member runs the window path: the three k_win_*_b launches */
-    DevBuf<WinArgs> wmembers;
-    int win_ppt = 4, win_threads = 256, gx_scat = 1, gx_slice = 1, gx_wfin = 1;
-    bool win_staged = false;
-    size_t win_lds = 0, win_scat_lds = 0, win_fin_lds = 0;
-    DevBuf<DevMeta> metas;
-    std::shared_ptr<PinBuf<DevMeta>> hmetas; /* the meta blocks on the host, shared with the member handles that read them */
-    ~BatchGraph()
-    {
-        if (ge) (void)hipGraphExecDestroy(ge);
-        if (g) (void)hipGraphDestroy(g);
-        if (fork) (void)hipEventDestroy(fork);
-        for (auto e : join) if (e) (void)hipEventDestroy(e);
-    }
-};
 void ppp_handle_s::drop_batch()
 {
     for (auto &b : batches) { delete b; b = nullptr; }
 }
 
-namespace {
+/* the helpers of ppp_handle.h and this unit's own (static); the attribute as in the header: a definition takes its visibility from
+   the block it stands in */
+namespace ppp_internal __attribute__((visibility("hidden"))) {
 
 int fail(ppp_handle h, int code, const std::string &msg)
 {
     if (h) h->err = msg;
     return code;
 }
-#define HIPCHK(h, expr)                                                                               \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess)                                                                         \
-            return fail(h, PPP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
-    } while (0)
-
-DevParams dev_params(const ppp_handle h)
+static DevParams dev_params(const ppp_handle h)
 {
     DevParams D;
     memset(&D, 0, sizeof(D));
@@ -558,23 +128,10 @@ hipError_t copy_sync(ppp_handle h, void *dst, const void *src, size_t bytes, hip
     return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
 }
 
-/* launch helper: optional hipEvent bracket on the handle's stream */
-#define LAUNCH(h, name, kern, grid, block, shmem, ...)                                                \
-    do {                                                                                              \
-        KTimer *_t = (h)->timing ? timer_for((h), name) : nullptr;                                    \
-        if (_t) (void)hipEventRecord(_t->e0[_t->used], (h)->stream);                                  \
-        (void)hipGetLastError(); /* the check below must not pick up an older, unrelated error */     \
-        (h)->pass.meta_stale();                                                                       \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), (shmem), (h)->stream, __VA_ARGS__);         \
-        if (_t) { (void)hipEventRecord(_t->e1[_t->used], (h)->stream); _t->used++; }                  \
-        hipError_t _le = hipGetLastError();                                                           \
-        if (_le != hipSuccess) return fail((h), PPP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(_le)); \
-    } while (0)
-
 /* kernels instantiated per 256 threads of budget: f(std::integral_constant<int, N>) for the smallest N of 256, 512, 768, 1024
    that holds a workgroup of T threads */
 template <class F>
-int with_block_size(int T, F &&f)
+static int with_block_size(int T, F &&f)
 {
     if (T <= 256) return f(std::integral_constant<int, 256>());
     if (T <= 512) return f(std::integral_constant<int, 512>());
@@ -584,13 +141,19 @@ int with_block_size(int T, F &&f)
 static_assert(POSE_T == 1024, "k_pose's widest instantiation is the ladder's top rung");
 /* the scatter kernels are instantiated per points per thread: f(std::integral_constant<int, 16 | 8 | 4>) */
 template <bool WITH16 = true, class F>
-int with_ppt(int ppt, F &&f)
+static int with_ppt(int ppt, F &&f)
 {
     if constexpr (WITH16) if (ppt == 16) return f(std::integral_constant<int, 16>());
     return ppt >= 8 ? f(std::integral_constant<int, 8>()) : f(std::integral_constant<int, 4>());
 }
 
-int validate_params(ppp_handle h, const ppp_params *p)
+/* the neighbours of a curvature fit: the lanes of a wave hold them (every call that evaluates the contact model asks) */
+int curvature_k_ok(ppp_handle h, int k)
+{
+    return (k < 3 || k > 64) ? fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]") : PPP_OK;
+}
+
+static int validate_params(ppp_handle h, const ppp_params *p)
 {
     if (!(p->tool_radius > 0) || (int)(p->tool_radius * 2) <= 0) return fail(h, PPP_ERR_ARG, "Tool_Radius must give an integer step >= 1");
     if (!(p->path_resolution > 0)) return fail(h, PPP_ERR_ARG, "PathResolution must be > 0");
@@ -608,22 +171,10 @@ int validate_params(ppp_handle h, const ppp_params *p)
     if (p->dynamic_adjustment) {
         if (p->walk != PPP_WALK_CENTER_INT && p->walk != PPP_WALK_SDIR_INT && p->walk != PPP_WALK_V1_CONTACT)
             return fail(h, PPP_ERR_UNSUPPORTED, "Dynamic_adjustment exists for the connect / connect1 / main planners only (walks center_int, sdir_int, v1_contact); SectPath and slicing_method have none");
-        if (p->curvature_k < 3 || p->curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
+        if (int rc = curvature_k_ok(h, p->curvature_k)) return rc;
         if (!(p->depth > 0) || !(p->adjust_threshold >= 0) || !(p->toolthickness > 0)) return fail(h, PPP_ERR_ARG, "depth / Adjust_Threshold / toolthickness");
     }
     return PPP_OK;
-}
-
-/* Launch-geometry / search-radius overrides of the tuning scripts (tools/_run_*.sh): read only by builds made with -DPPP_TUNING
-   (make variant NAME=tune DEFS=-DPPP_TUNING); the product library ignores them, so a stray variable cannot change a plan. */
-static inline const char *tuning_env(const char *name)
-{
-#ifdef PPP_TUNING
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
 }
 
 DynParams dyn_params(const ppp_handle h)
@@ -638,16 +189,6 @@ DynParams dyn_params(const ppp_handle h)
     if (const char *ev = tuning_env("PPP_DYN_R0F")) D.r0 = (float)std::max(0.5, atof(ev) * std::sqrt((double)D.k / (3.14159265358979 * rho))); /* tuning runs only */
     D.r1 = (float)std::max(0.25, 2.0 * std::sqrt(1.0 / (3.14159265358979 * rho)));
     return D;
-}
-
-/* the kernels' views of the handle's slab index / normal field and of its knot tables, as they stand when the launch is made */
-ContactIndex contact_index(const ppp_handle h)
-{
-    return ContactIndex{h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, h->normals4.p, h->ell_cs.p, h->slab_ytab.p};
-}
-KnotTable knot_table(const ppp_handle h)
-{
-    return KnotTable{h->node_x.p, h->node_y.p, h->node_z.p, h->node_start.p, h->node_cnt.p, h->node_cap};
 }
 
 int ensure_dynamic_buffers(ppp_handle h)
@@ -701,14 +242,14 @@ constexpr size_t PIN_REC0 = 0, PIN_REC1 = 64, PIN_PX = 128, PIN_CENSUS = PIN_PX 
    thread in the pairing, 4 .. 8 lanes per waypoint in the pose stage): the launch ends with its slowest workgroup.  A launch
    of several rounds of workgroups (batches, cfg 5) is about throughput: as many workgroups per CU as the LDS allows, the 16
    waves shared between them (measured, 64 x 250 k points: 256 threads 0.42 ms, 320 .. 512 threads 0.58 .. 0.64 ms). */
-size_t win_slice_lds_for(const ppp_handle h, int NBc)
+static size_t win_slice_lds_for(const ppp_handle h, int NBc)
 {   /* (the checking workgroup of the launch keeps the walk and its scratch there) */
     return std::max(win_slice_lds_bytes(h->win_capw, h->win_cap_el, WIN_CLASSES * NBc), sizeof(float) * ((size_t)h->S_cap + 2048) + 64);
 }
 /* several workgroups per CU, at once or one after the other? */
-bool win_throughput_launch(const ppp_handle h, long long wgs) { return wgs > (long long)h->num_cus; }
+static bool win_throughput_launch(const ppp_handle h, long long wgs) { return wgs > (long long)h->num_cus; }
 
-int win_pick_threads(const ppp_handle h, long long wgs)
+static int win_pick_threads(const ppp_handle h, long long wgs)
 {
     const int capw = h->win_capw, cap_el = h->win_cap_el;
     int tmin = std::max(128, 64 * ((capw + 64 * WIN_EMAX - 1) / (64 * WIN_EMAX)));
@@ -743,7 +284,7 @@ int win_pick_threads(const ppp_handle h, long long wgs)
    [Px - pad, Px + pad] that do not overlap (tool steps of about 2 pad + 2 mm and more) and that fit a workgroup's LDS.  Everything
    else -- and every pass the window path hands back -- runs on the slab index.  Sizes come from the cached bounds, as the slab
    grid's do; the device re-derives bounds and walk in every pass and checks them against this plan. */
-int plan_window(ppp_handle h, int S, double per)
+static int plan_window(ppp_handle h, int S, double per)
 {
     h->win_path = false;
     h->plan_walk_ok = false;
@@ -887,7 +428,7 @@ int plan_window(ppp_handle h, int S, double per)
 }
 
 /* the arguments of the three window launches for this handle */
-WinArgs win_args(const ppp_handle h)
+static WinArgs win_args(const ppp_handle h)
 {
     WinArgs A;
     memset(&A, 0, sizeof(A));
@@ -917,9 +458,9 @@ WinArgs win_args(const ppp_handle h)
     A.meta_host = h->hmeta_pinned.p; A.fin_ticket = h->fin_ticket.p; /* (a member of a batch of several publishes into the batch's pinned array: upload_members_win) */
     return A;
 }
-size_t win_slice_lds(const ppp_handle h) { return win_slice_lds_for(h, h->win_NBc); }
+static size_t win_slice_lds(const ppp_handle h) { return win_slice_lds_for(h, h->win_NBc); }
 /* the same arguments with the bucket table of a many-workgroups-per-CU launch */
-void win_args_throughput(const ppp_handle h, WinArgs &A)
+static void win_args_throughput(const ppp_handle h, WinArgs &A)
 {
     A.NBc = h->win_NBc_thr; A.NB = WIN_CLASSES * A.NBc;
     const float yr = h->h_mx[1] - h->h_mn[1];
@@ -927,7 +468,7 @@ void win_args_throughput(const ppp_handle h, WinArgs &A)
 }
 
 /* GenPath on the window path: bounds + binning, then the per-slice kernel (which also does getPath's per-waypoint half) */
-int enqueue_window_gen(ppp_handle h)
+static int enqueue_window_gen(ppp_handle h)
 {
     WinArgs A = win_args(h);
     const bool thr = win_throughput_launch(h, A.g_slice);
@@ -947,34 +488,15 @@ int enqueue_window_gen(ppp_handle h)
     });
 }
 /* the rest of getPath: offsets, compaction, postion_smooth / reduceRPY / flange */
-int enqueue_window_finish(ppp_handle h)
+static int enqueue_window_finish(ppp_handle h)
 {
     const WinArgs A = win_args(h);
     LAUNCH(h, "k_win_finish", k_win_finish, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
     return PPP_OK;
 }
 
-/* ordered compaction (ppp_preproc.h) of the n elements sel keeps: the block counts in cnt[0 .. n / COMPACT_CHUNK], their
-   scan (the kept total to *total, on the device), the emit.  sized (the range part, whose output is sized by the total):
-   the total is read back first, and sized(total) may point sel at the output before the emit. */
-template <class Sel>
-int compact(ppp_handle h, Sel &sel, int n, int *cnt, int *total, const std::function<int(int)> &sized = nullptr)
-{
-    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
-    LAUNCH(h, "k_compact_count", k_compact_count<Sel>, nblocks, 256, 0, sel, n, cnt);
-    LAUNCH(h, "k_compact_scan", k_compact_scan, 1, 1024, 0, cnt, nblocks, total);
-    if (sized) {
-        int kept = 0;
-        HIPCHK(h, hipMemcpyAsync(&kept, total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (int rc = sized(kept)) return rc;
-    }
-    LAUNCH(h, "k_compact_emit", k_compact_emit<Sel>, nblocks, 256, 0, sel, n, cnt);
-    return PPP_OK;
-}
-
 /* sizes every workspace from the resident cloud + parameters; no kernel of the hot path allocates */
-int make_plan(ppp_handle h)
+static int make_plan(ppp_handle h)
 {
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
     /* from here on the handle's members are rewritten step by step: a re-plan that fails half way (a slice range wider
@@ -1140,7 +662,7 @@ int make_plan(ppp_handle h)
     return PPP_OK;
 }
 
-int scatter_grid(int n, int ppt) { return std::max(1, (n + ppt * SCAT_T - 1) / (ppt * SCAT_T)); }
+static int scatter_grid(int n, int ppt) { return std::max(1, (n + ppt * SCAT_T - 1) / (ppt * SCAT_T)); }
 
 /* the launch geometry of this handle's slab pass: every stage's grid, block size and LDS, decided here and nowhere else */
 SlabGeom slab_geom(const ppp_handle h)
@@ -1175,7 +697,7 @@ SlabGeom slab_geom(const ppp_handle h)
 }
 
 /* the slab pass's launch record of this handle, from its state at enqueue time (the window path's: win_args) */
-SlabArgs slab_args(const ppp_handle h, const SlabGeom &G)
+static SlabArgs slab_args(const ppp_handle h, const SlabGeom &G)
 {
     SlabArgs A;
     memset(&A, 0, sizeof(A));
@@ -1206,7 +728,7 @@ SlabArgs slab_args(const ppp_handle h, const SlabGeom &G)
 }
 
 /* a2 + a3 + the x-slab index (generalised slice binning) */
-int enqueue_index(ppp_handle h, const SlabGeom &G, SlabArgs A)
+static int enqueue_index(ppp_handle h, const SlabGeom &G, SlabArgs A)
 {
     h->slab_cnt_used = true;
     A.P.keep_run_state = (h->win_path && h->pass.gen_done()) ? 1 : 0; /* an API mirror asks for the slab index behind a finished window pass */
@@ -1230,14 +752,14 @@ int enqueue_index(ppp_handle h, const SlabGeom &G, SlabArgs A)
     return PPP_OK;
 }
 
-int enqueue_index(ppp_handle h)
+static int enqueue_index(ppp_handle h)
 {
     const SlabGeom G = slab_geom(h);
     return enqueue_index(h, G, slab_args(h, G));
 }
 
 /* centre slice of the centre-out walk = number of slices left of it (path_dynamic_alg.cpp:310-313) */
-int host_centre_index(const ppp_handle h)
+static int host_centre_index(const ppp_handle h)
 {
     const int step = (int)(h->P.tool_radius * 2);
     const int imin = (int)h->h_mn[0], imax = (int)h->h_mx[0];
@@ -1246,7 +768,7 @@ int host_centre_index(const ppp_handle h)
 }
 
 /* GenPath with Adjust = true: whole-cloud normals, then the slice-to-slice chains */
-int enqueue_dynamic(ppp_handle h)
+static int enqueue_dynamic(ppp_handle h)
 {
     if (h->dyn_maxNB > 4096 || h->dyn_maxNA > 4096)
         return fail(h, PPP_ERR_CAPACITY, "dynamic adjustment: more than 4096 boundary or path samples per slice");
@@ -1281,7 +803,7 @@ int enqueue_dynamic(ppp_handle h)
 }
 
 /* work enqueued for this handle by a batch graph runs on the lead handle's stream */
-int settle_streams(ppp_handle h)
+static int settle_streams(ppp_handle h)
 {
     if (h->pass.pending_stream()) {
         HIPCHK(h, hipStreamSynchronize(h->pass.pending_stream()));
@@ -1289,7 +811,7 @@ int settle_streams(ppp_handle h)
     }
     return PPP_OK;
 }
-int resolve_deferred(ppp_handle h);
+static int resolve_deferred(ppp_handle h);
 /* every entry point but the three that only enqueue a pass: nothing pending on another stream, and the plan is this cloud's */
 int settle(ppp_handle h)
 {
@@ -1299,7 +821,7 @@ int settle(ppp_handle h)
 }
 /* ppp_run_async / ppp_gen_path_async / ppp_get_path_async: a pass may be enqueued on the plan a cloud was set under (window
    path, same size and parameters) before that cloud's bounds have come back */
-int settle_enqueue_only(ppp_handle h)
+static int settle_enqueue_only(ppp_handle h)
 {
     if (h->plan_deferred && h->pass.planned() && h->win_path) return settle_streams(h);
     return settle(h);
@@ -1323,7 +845,7 @@ int fetch_meta(ppp_handle h)
     return PPP_OK;
 }
 
-int enqueue_meta_copy(ppp_handle h)
+static int enqueue_meta_copy(ppp_handle h)
 {
     HIPCHK(h, hipMemcpyAsync(h->hmeta_pinned.p, h->meta.p, sizeof(DevMeta), hipMemcpyDeviceToHost, h->stream));
     h->pass.meta_will_arrive(MetaAt::pinned());
@@ -1352,7 +874,7 @@ int map_dev_err(ppp_handle h)
 }
 
 /* turn the arena passes on: the LDS-overflow kernels follow the fast ones from the next launch sequence on */
-int enable_arena(ppp_handle h)
+static int enable_arena(ppp_handle h)
 {
     h->big_path = true;
     h->drop_graph();
@@ -1360,12 +882,12 @@ int enable_arena(ppp_handle h)
     return PPP_OK;
 }
 
-int row_cap(size_t cap_rows) { return (int)std::min<size_t>(cap_rows, 0x7fffffff); }
+static int row_cap(size_t cap_rows) { return (int)std::min<size_t>(cap_rows, 0x7fffffff); }
 
 /* A whole pass on behalf of a batch, a graph or a re-run: GenPath, then getPath where wanted.  dst_rows: the emitting launch
    also writes the list there (at most cap_rows rows).  chained: getPath follows in the same enqueue, GenPath skips its meta
    copy.  The error, if any, is in h->err; a capture in progress is the caller's to end. */
-int enqueue_pass(ppp_handle h, float *dst_rows, size_t cap_rows, bool chained, bool want_path = true)
+static int enqueue_pass(ppp_handle h, float *dst_rows, size_t cap_rows, bool chained, bool want_path = true)
 {
     ++h->internal;
     if (chained) h->chain_calls = true;
@@ -1380,7 +902,7 @@ int enqueue_pass(ppp_handle h, float *dst_rows, size_t cap_rows, bool chained, b
 
 /* An overflow of the LDS-resident fast path is not an error of the input: turn the arena passes on
    and run the same calls again, once. */
-int rerun_with_arena(ppp_handle h)
+static int rerun_with_arena(ppp_handle h)
 {
     const bool had_path = h->pass.path_done();
     if (h->win_path && h->hmeta.win_flag && getenv("PPP_WIN_DEBUG"))
@@ -1406,7 +928,7 @@ int rerun_with_arena(ppp_handle h)
     return fetch_meta(h);
 }
 
-bool overflowed_fast_path(ppp_handle h)
+static bool overflowed_fast_path(ppp_handle h)
 {
     /* (a GenPath on its own leaves no error behind: the slices parked for the arena pass are simply not planned yet) */
     if (h->win_path && h->hmeta.win_flag) return true; /* the window path handed the pass back */
@@ -1427,7 +949,7 @@ int ensure_ready(ppp_handle h, bool need_gen, bool need_path)
     return PPP_OK;
 }
 
-int ensure_index(ppp_handle h)
+static int ensure_index(ppp_handle h)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1438,20 +960,20 @@ int ensure_index(ppp_handle h)
     return PPP_OK;
 }
 
-int slice_lds_ok(ppp_handle h, int capb)
+static int slice_lds_ok(ppp_handle h, int capb)
 {
     return std::max(slice_lds_bytes(capb), slice_kd_bytes(capb)) + 1024 <= (size_t)h->max_lds;
 }
 
 /* workgroups of the bounds pass over n points (k_minmax<false> / k_ingest_minmax) */
-int bounds_grid(size_t n) { return std::max(1, std::min(((int)n / 4 + 255) / 256, 2048)); }
+static int bounds_grid(size_t n) { return std::max(1, std::min(((int)n / 4 + 255) / 256, 2048)); }
 /* ... of the conversion pass of a new cloud (k_ingest_minmax): about one workgroup per CU, eight points per thread.  Its workgroups
    end on ONE ticket counter, and same-address atomics serialise at ~11 ns each: the 977 workgroups bounds_grid gives a million
    points spent 10 us of a 23 us launch queueing there */
-int ingest_grid(size_t n) { return std::max(1, std::min(((int)n / 8 + MM_T - 1) / MM_T, 256)); }
+static int ingest_grid(size_t n) { return std::max(1, std::min(((int)n / 8 + MM_T - 1) / MM_T, 256)); }
 
 /* may the window path apply to the next plan, as far as the parameters say (plan_window decides with the bounds in hand)? */
-bool window_params_ok(const ppp_handle h)
+static bool window_params_ok(const ppp_handle h)
 {
     return h->win_allowed && !h->win_disabled && !getenv("PPP_NO_WINDOW_PATH") && !h->P.dynamic_adjustment &&
            !h->aligned && !h->big_path && (int)(h->P.tool_radius * 2) >= 1;
@@ -1462,7 +984,7 @@ bool window_params_ok(const ppp_handle h)
    pinned memory, and where the window path may apply its census follows in the same stream: two launches, one wait, no copy or
    fill command (each of those costs the host 10-20 us here; this path was 150 us for 30 us of kernels) */
 /* what k_ingest_minmax (and the census behind it) left in pinned memory for the host: bounds, count, the device's walk */
-int adopt_ingest_record(ppp_handle h, bool census, bool reuse)
+static int adopt_ingest_record(ppp_handle h, bool census, bool reuse)
 {
     const PlanAuto *rec0 = (const PlanAuto *)(h->pin.p + PIN_REC0), *rec1 = (const PlanAuto *)(h->pin.p + PIN_REC1);
     if (rec0->S == -2) return fail(h, PPP_ERR_HIP, "the bounds of the new cloud did not arrive");
@@ -1473,7 +995,7 @@ int adopt_ingest_record(ppp_handle h, bool census, bool reuse)
     return PPP_OK;
 }
 
-int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stride_bytes = 0, bool may_defer = false)
+int refresh_bounds_and_plan(ppp_handle h, const char *raw, size_t stride_bytes, bool may_defer)
 {
     const size_t n = h->n;
     h->auto_valid = false; h->auto_px_only = false;
@@ -1578,7 +1100,7 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stri
    ppp_set_cloud* would have.  A pass that already ran keeps its results when that plan asks for the launches and buffers the
    pass used (the rule for a cloud of the same kind: capacities are inherited either way); else it runs again on the right plan.
    What the device found wrong with the pass itself (WIN_FLAG_*) is in its meta block and handled where every pass's is. */
-int resolve_deferred(ppp_handle h)
+static int resolve_deferred(ppp_handle h)
 {
     if (!h->plan_deferred) return PPP_OK;
     h->plan_deferred = false;
@@ -1613,7 +1135,7 @@ int resolve_deferred(ppp_handle h)
     return enqueue_pass(h, h->last_out2, (size_t)h->last_out2_cap, false, had_path); /* (to the caller's output buffer of the first attempt) */
 }
 
-int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_bytes, const float *viewpoint, bool may_defer = false)
+static int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_bytes, const float *viewpoint, bool may_defer = false)
 {
     if (n > 0x7fffffffu / 8) return fail(h, PPP_ERR_CAPACITY, "cloud too large");
     h->n = n;
@@ -1633,7 +1155,7 @@ int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_
 }
 
 
-} // namespace
+} // namespace ppp_internal
 
 extern "C" {
 
@@ -1889,14 +1411,6 @@ int ppp_range_interval(const ppp_params *p, float min_x, float max_x, float *lo,
     return PPP_OK;
 }
 
-/* the cuts of ownership: [cut(sb), cut(se)) of the walk px[0 .. S), the midpoints of neighbouring slices in float */
-static void owned_cuts(const float *px, int S, int sb, int se, float *own_lo, float *own_hi)
-{
-    if (sb >= se) { *own_lo = INFINITY; *own_hi = -INFINITY; return; } /* an empty range owns nothing */
-    *own_lo = sb <= 0 ? -INFINITY : (px[sb - 1] + px[sb]) * 0.5f;
-    *own_hi = se >= S ? INFINITY : (px[se - 1] + px[se]) * 0.5f;
-}
-
 int ppp_range_owned(const ppp_params *p, float min_x, float max_x, float *own_lo, float *own_hi)
 {
     if (!p || !own_lo || !own_hi) return PPP_ERR_ARG;
@@ -1955,10 +1469,9 @@ int ppp_set_cloud_part(ppp_handle h, const float *xyz_host, size_t n_part, size_
     return make_plan(h);
 }
 
-namespace {
 
 /* the slab index of a handle, complete: built, its meta block read back, the arena passes run if a slab overflowed */
-int index_ready(ppp_handle h, bool strict = true)
+int index_ready(ppp_handle h, bool strict)
 {
     int rc = ensure_index(h);
     if (rc) return rc;
@@ -1973,282 +1486,6 @@ int index_ready(ppp_handle h, bool strict = true)
        read the index: an earlier GenPath's slice error is not theirs, a slab that fits nowhere is */
     if (!strict && h->hmeta.err != DERR_CAPACITY) return PPP_OK;
     return map_dev_err(h);
-}
-
-/* path_translation_alg.cpp:171-174: the cloud carried back by invTransAlign, with its own slab index (same point
-   indices).  The cloud is fixed between runs, so this happens once per cloud change, not per getPath. */
-int rebuild_back(ppp_handle h)
-{
-    if (!h->back) {
-        int rc = ppp_create(h->device, &h->back);
-        if (rc) return fail(h, rc, "sensor-frame handle");
-    }
-    ppp_handle b = h->back;
-    b->P = h->P;
-    b->P.tool_radius = 1.0e6; b->P.dynamic_adjustment = 0; b->P.slice_begin = 0; b->P.slice_end = 0; /* one slice: this handle only ever serves its index */
-    b->n = h->n;
-    memcpy(b->vp, h->vp, sizeof(b->vp));
-    HIPCHK(h, b->X.ensure(h->n)); HIPCHK(h, b->Y.ensure(h->n)); HIPCHK(h, b->Z.ensure(h->n));
-    if (h->n) {
-        Mat34 M;
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) M.m[r][c] = h->invTA[r][c];
-        LAUNCH(h, "k_transform_se3", k_transform_se3, (unsigned)((h->n + 255) / 256), 256, 0, h->X.p, h->Y.p, h->Z.p, (int)h->n, M, b->X.p, b->Y.p, b->Z.p);
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    b->big_path = false;
-    int rc = refresh_bounds_and_plan(b);
-    if (rc == PPP_OK) rc = index_ready(b);
-    if (rc == PPP_OK) { hipError_t e = hipStreamSynchronize(b->stream); if (e != hipSuccess) rc = PPP_ERR_HIP; }
-    if (rc != PPP_OK) return fail(h, rc, std::string("sensor-frame index: ") + b->err);
-    return PPP_OK;
-}
-
-/* the resident cloud was replaced or moved: bounds, plan, and the sensor-frame copy when the cloud is aligned */
-int cloud_changed(ppp_handle h)
-{
-    int rc = refresh_bounds_and_plan(h);
-    if (rc == PPP_OK && h->aligned) rc = rebuild_back(h);
-    return rc;
-}
-
-/* the opening of the preprocessing calls: a whole-cloud handle with a cloud, settled on its device.  bad_arg: the
-   caller's message for an invalid argument, reported between the two checks (ppp_remove_outlier's order) */
-int preproc_begin(ppp_handle h, const char *bad_arg = nullptr)
-{
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rcs = settle(h); if (rcs) return rcs; }
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (bad_arg) return fail(h, PPP_ERR_ARG, bad_arg);
-    if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
-    return PPP_OK;
-}
-
-/* the filtered cloud of n points replaces the resident one (filter(*cloud)).  The callers free their scratch first: hipFree
-   waits for the device, and behind this call it would wait for the launches of the new plan. */
-int adopt_cloud(ppp_handle h, DevBuf<float> &X2, DevBuf<float> &Y2, DevBuf<float> &Z2, size_t n)
-{
-    h->X = std::move(X2); h->Y = std::move(Y2); h->Z = std::move(Z2);
-    h->n = n;
-    h->drop_graph();
-    return cloud_changed(h);
-}
-
-} // namespace
-
-int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float *covariance9)
-{
-    int rc = preproc_begin(h);
-    if (rc) return rc;
-    if (h->aligned) return fail(h, PPP_ERR_ARG, "the cloud is aligned already (TransAlign would be overwritten): set the cloud again");
-    const int n = (int)h->n;
-    if (n == 0 || h->h_nvalid == 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
-    float hs[6] = {0, 0, 0, 0, 0, 0}, c[3] = {0, 0, 0};
-    const int hcnt = h->h_nvalid; /* the finite points, counted with the bounds */
-    const unsigned gb = (unsigned)((n + 255) / 256);
-    { /* scratch, freed before the re-plan (adopt_cloud) */
-        const size_t stride = ((size_t)n + 3) & ~(size_t)3;
-        DevBuf<float> V, sums;
-        hipError_t e = V.ensure(6 * stride);
-        if (e == hipSuccess) e = sums.ensure(8);
-        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("trans2center buffers: ") + hipGetErrorString(e));
-        /* pcl::compute3DCentroid: three running float sums, / float(count) */
-        LAUNCH(h, "k_seq_prep_centroid", k_seq_prep_centroid, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, stride, V.p);
-        LAUNCH(h, "k_seq_sum", k_seq_sum, 3, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
-        HIPCHK(h, hipMemcpyAsync(hs, sums.p, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (hcnt <= 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
-        for (int d = 0; d < 3; ++d) c[d] = hs[d] / static_cast<float>(hcnt);
-        /* pcl::computeCovarianceMatrix: six running float sums of float products */
-        LAUNCH(h, "k_seq_prep_cov", k_seq_prep_cov, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, c[0], c[1], c[2], stride, V.p);
-        LAUNCH(h, "k_seq_sum", k_seq_sum, 6, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
-        HIPCHK(h, hipMemcpyAsync(hs, sums.p, 6 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    float cov[3][3];
-    cov[1][1] = hs[0]; cov[1][2] = hs[1]; cov[2][2] = hs[2]; cov[0][0] = hs[3]; cov[0][1] = hs[4]; cov[0][2] = hs[5];
-    cov[1][0] = cov[0][1]; cov[2][0] = cov[0][2]; cov[2][1] = cov[1][2];
-    if (centroid3) memcpy(centroid3, c, sizeof(c));
-    if (covariance9) for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) covariance9[3 * i + j] = cov[i][j];
-    ppp_align::EigenSolver3f es;
-    es.compute(cov);
-    if (es.complex_pair || !es.converged)
-        return fail(h, PPP_ERR_DOMAIN, "trans2center: the float Schur form of the covariance keeps a complex pair (two equal extents) or did not converge");
-    ppp_align::trans_align(es, c, h->TA);
-    ppp_align::inverse4(h->TA, h->invTA);
-    if (trans_align16) for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) trans_align16[4 * i + j] = h->TA[i][j];
-    /* pcl::transformPointCloud(*cloud, *cloud, TransAlign) */
-    Mat34 M;
-    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 4; ++cc) M.m[r][cc] = h->TA[r][cc];
-    LAUNCH(h, "k_transform_se3", k_transform_se3, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->aligned = true;
-    h->drop_graph();
-    return cloud_changed(h);
-}
-
-int ppp_remove_outlier(ppp_handle h, int mean_k, double stddev_mul, size_t *n_kept, double *threshold)
-{
-    int rc = preproc_begin(h, (mean_k < 1 || mean_k > 63) ? "mean_k must be in [1, 63]" : nullptr);
-    if (rc) return rc;
-    rc = index_ready(h);
-    if (rc) return rc;
-    const int n = (int)h->n, ns = h->hmeta.n_sorted;
-    if (ns < mean_k + 1) return fail(h, PPP_ERR_ARG, "fewer finite points than mean_k + 1 (PCL reads past its neighbour vectors here)");
-    /* first radius of the k-NN gather: mean_k + 1 points of a sheet of the cloud's mean areal density, +25 % */
-    const double area = ((double)h->h_mx[0] - h->h_mn[0]) * ((double)h->h_mx[1] - h->h_mn[1]);
-    const double rho = (area > 0 && h->h_nvalid > 0) ? (double)h->h_nvalid / area : 1.0;
-    const float r0 = (float)std::max(0.5, 1.25 * std::sqrt((double)(mean_k + 1) / (3.14159265358979 * rho)));
-    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nparts = std::max(1, std::min(1024, (n + 255) / 256));
-    DevBuf<float> X2, Y2, Z2;
-    SorStats hst;
-    { /* scratch, freed before the re-plan (adopt_cloud) */
-        DevBuf<float> dist;
-        DevBuf<double> part;
-        DevBuf<int> bcnt;
-        DevBuf<SorStats> st;
-        hipError_t e = dist.ensure(n);
-        if (e == hipSuccess) e = X2.ensure(n);
-        if (e == hipSuccess) e = Y2.ensure(n);
-        if (e == hipSuccess) e = Z2.ensure(n);
-        if (e == hipSuccess) e = part.ensure(2 * (size_t)nparts);
-        if (e == hipSuccess) e = bcnt.ensure(nblocks);
-        if (e == hipSuccess) e = st.ensure(1);
-        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-        HIPCHK(h, hipMemsetAsync(dist.p, 0, sizeof(float) * (size_t)n, h->stream)); /* non-finite points: distance 0 */
-        LAUNCH(h, "k_sor_dist", k_sor_dist, (unsigned)((ns + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, h->sorted4.p, h->slab_start.p,
-               h->slab_xmin.p, h->slab_xmax.p, mean_k, r0, dist.p);
-        LAUNCH(h, "k_sor_partial", k_sor_partial, nparts, 256, 0, dist.p, n, part.p);
-        LAUNCH(h, "k_sor_threshold", k_sor_threshold, 1, 256, 0, h->meta.p, part.p, nparts, stddev_mul, st.p);
-        SorSel sel{dist.p, st.p, h->X.p, h->Y.p, h->Z.p, X2.p, Y2.p, Z2.p};
-        rc = compact(h, sel, n, bcnt.p, &st.p->n_kept);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(SorStats), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->pass.meta_will_arrive(MetaAt::on_demand());
-    rc = fetch_meta(h);
-    if (rc == PPP_OK) rc = map_dev_err(h);
-    if (rc) return rc;
-    if (n_kept) *n_kept = (size_t)hst.n_kept;
-    if (threshold) *threshold = hst.threshold;
-    return adopt_cloud(h, X2, Y2, Z2, (size_t)hst.n_kept);
-}
-
-int ppp_voxel_down(ppp_handle h, float lx, float ly, float lz, size_t *n_out, int *overflow)
-{
-    int rc = preproc_begin(h);
-    if (rc) return rc;
-    if (!(lx > 0.f) || !(ly > 0.f) || !(lz > 0.f) || !std::isfinite(lx) || !std::isfinite(ly) || !std::isfinite(lz))
-        return fail(h, PPP_ERR_ARG, "leaf sizes must be positive and finite");
-    if (overflow) *overflow = 0;
-    if (n_out) *n_out = h->n;
-    const int n = (int)h->n;
-    if (n == 0) return PPP_OK;
-    /* voxel_grid.hpp applyFilter: inverse_leaf_size_ = 1 / leaf_size_ (float), the index-overflow test on the float extents,
-       min_b_ / max_b_ / div_b_ / divb_mul_ */
-    const float inv[3] = {1.0f / lx, 1.0f / ly, 1.0f / lz};
-    VoxGrid g;
-    long long cells = 1, dxyz = 1;
-    int div_b[3];
-    if (h->h_nvalid > 0) {
-        for (int d = 0; d < 3; ++d) {
-            dxyz *= (long long)((h->h_mx[d] - h->h_mn[d]) * inv[d]) + 1;
-            const int min_b = (int)std::floor(h->h_mn[d] * inv[d]), max_b = (int)std::floor(h->h_mx[d] * inv[d]);
-            div_b[d] = max_b - min_b + 1;
-            cells *= div_b[d];
-            g.inv[d] = inv[d];
-            g.min_b[d] = (float)min_b;
-            if (dxyz > 0x7fffffffLL || cells > 0x7fffffffLL || dxyz <= 0 || cells <= 0) {
-                /* "Leaf size is too small for the input dataset. Integer indices would overflow.": output = input */
-                if (overflow) *overflow = 1;
-                return PPP_OK;
-            }
-        }
-        g.mul[0] = 1; g.mul[1] = div_b[0]; g.mul[2] = div_b[0] * div_b[1];
-    } else {
-        for (int d = 0; d < 3; ++d) { g.inv[d] = inv[d]; g.min_b[d] = 0.f; g.mul[d] = 0; }
-    }
-    g.none = (unsigned)cells;
-    int end_bit = 1;
-    while (end_bit < 32 && (cells >> end_bit)) ++end_bit;
-    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
-    DevBuf<float> X2, Y2, Z2;
-    int n_vox = 0;
-    { /* scratch, freed before the re-plan (adopt_cloud) */
-        DevBuf<unsigned> key, key2;
-        DevBuf<int> idx, idx2, bcnt;
-        DevBuf<char> tmp;
-        DevBuf<float4> pts;
-        size_t tmp_bytes = 0;
-        hipError_t e = ppp_sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, end_bit, h->stream);
-        if (e == hipSuccess) e = key.ensure(n);
-        if (e == hipSuccess) e = key2.ensure(n);
-        if (e == hipSuccess) e = idx.ensure(n);
-        if (e == hipSuccess) e = idx2.ensure(n);
-        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
-        if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
-        if (e == hipSuccess) e = pts.ensure(n);
-        if (e == hipSuccess) e = X2.ensure(n);
-        if (e == hipSuccess) e = Y2.ensure(n);
-        if (e == hipSuccess) e = Z2.ensure(n);
-        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("voxel_down buffers: ") + hipGetErrorString(e));
-        const unsigned gb = (unsigned)((n + 255) / 256);
-        LAUNCH(h, "k_vox_key", k_vox_key, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, g, key.p, idx.p);
-        HIPCHK(h, ppp_sort_pairs_u32(tmp.p, &tmp_bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, end_bit, h->stream));
-        LAUNCH(h, "k_vox_gather", k_vox_gather, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, idx2.p, n, pts.p);
-        VoxHeadSel sel{key2.p, pts.p, n, g.none, X2.p, Y2.p, Z2.p};
-        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(&n_vox, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    if (n_out) *n_out = (size_t)n_vox;
-    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_vox);
-}
-
-int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
-{
-    int rc = preproc_begin(h);
-    if (rc) return rc;
-    if (!(search_radius > 0) || !std::isfinite(search_radius)) return fail(h, PPP_ERR_ARG, "search radius must be positive"); /* mls.hpp: "Invalid search radius" */
-    if (order < 0 || order > 3) return fail(h, PPP_ERR_ARG, "polynomial order must be in [0, 3]");
-    rc = index_ready(h);
-    if (rc) return rc;
-    const int n = (int)h->n, ns = h->hmeta.n_sorted;
-    if (n_out) *n_out = h->n;
-    if (n == 0) return PPP_OK;
-    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
-    DevBuf<float> X2, Y2, Z2;
-    int n_kept = 0;
-    { /* scratch, freed before the re-plan (adopt_cloud) */
-        DevBuf<float4> rec;
-        DevBuf<int> bcnt;
-        hipError_t e = rec.ensure(n);
-        if (e == hipSuccess) e = X2.ensure(n);
-        if (e == hipSuccess) e = Y2.ensure(n);
-        if (e == hipSuccess) e = Z2.ensure(n);
-        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
-        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("smooth buffers: ") + hipGetErrorString(e));
-        HIPCHK(h, hipMemsetAsync(rec.p, 0, sizeof(float4) * (size_t)n, h->stream));
-        const unsigned gb = (unsigned)((std::max(ns, 1) + 255) / 256);
-        const float rf = (float)search_radius;
-        const double sq = search_radius * search_radius;
-        if (order == 3) LAUNCH(h, "k_mls<3>", k_mls<3>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
-        else if (order == 2) LAUNCH(h, "k_mls<2>", k_mls<2>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
-        else LAUNCH(h, "k_mls<1>", k_mls<1>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
-        MlsKeptSel sel{rec.p, X2.p, Y2.p, Z2.p};
-        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(&n_kept, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->pass.meta_will_arrive(MetaAt::on_demand());
-    rc = fetch_meta(h);
-    if (rc == PPP_OK) rc = map_dev_err(h);
-    if (rc) return rc;
-    if (n_out) *n_out = (size_t)n_kept;
-    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_kept);
 }
 
 int ppp_get_cloud(ppp_handle h, float *xyz, size_t cap, size_t *n)
@@ -3130,190 +2367,6 @@ int ppp_get_boundary(ppp_handle h, int s, double *y, double *x, double *z, size_
     return PPP_OK;
 }
 
-/* A finished pass with the dynamic adjustment left the normal field of THIS cloud and THESE parameters in normals4: every
-   ppp_set_params and every cloud change plans again, which withdraws gen_done (a changed normal_radius included).  The
-   contact queries then skip the launch; ppp_area2cloud, older than they are, builds the field every time and is left as it was. */
-static bool pass_left_normals(const ppp_handle h) { return h->pass.gen_done() && h->P.dynamic_adjustment; }
-
-/* behind index_ready: the Area2Cloud buffers and the normal field (a pass with the dynamic adjustment made it) */
-static int contact_buffers(ppp_handle h)
-{
-    int rc = ensure_dynamic_buffers(h);
-    if (rc) return rc;
-    return pass_left_normals(h) ? PPP_OK : enqueue_normals(h);
-}
-
-/* What a pass did not build of what a contact query reads: the slab index (behind a window pass it keeps that pass's run
-   state, gen_done with it, as every API mirror's does) and contact_buffers */
-static int contact_prerequisites(ppp_handle h)
-{
-    int rc = index_ready(h, false);
-    return rc ? rc : contact_buffers(h);
-}
-
-/* the opening of a query about the paths of a finished pass whose maps go by cloud index */
-static int contact_query_begin(ppp_handle h, const char *what)
-{
-    int rc = ensure_ready(h, true, false);
-    if (rc) return rc;
-    rc = map_dev_err(h);
-    if (rc) return rc;
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, std::string(what) + ": the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    return PPP_OK;
-}
-
-static PCovRange pcov_range(const ppp_handle h)
-{
-    return PCovRange{h->incl_lo, h->incl_hi, h->h_mn[0], h->h_mx[0], h->P.normal_radius, h->ranged ? 1 : 0};
-}
-
-/* the refusal word of the sample kernels: 1 wave_ball_leaves_range, 2 KnotTable::slice (or 2^24 samples on a slice), 4 the
-   caps of k_pcon_offsets */
-static int contact_refusal(ppp_handle h, const char *what, unsigned long long bits)
-{
-    const std::string w(what);
-    if (bits & 2) return fail(h, PPP_ERR_HIP, w + ": a slice's knot table lies outside the node buffer");
-    if (bits & 4) return fail(h, PPP_ERR_CAPACITY, w + ": more than 2^30 contact samples");
-    if (bits & 1)
-        return fail(h, PPP_ERR_CAPACITY, w + ": a contact search (Area2Cloud's neighbours, their normals or a ball) reaches beyond the indexed slice range: raise range_margin");
-    return PPP_OK;
-}
-
-/* What both coverage calls share.  On the first question about a pass: the flags by cloud index (n16 uint4s: zero padding up to
-   a multiple of 16 bytes) and the two result words zeroed, `mark` launches the balls (flags at C.flags.p, refusal word at
-   C.count.p + 1), k_cov_count counts into C.count.p[0], one read brings both back.  Later questions answer from the result. */
-static int flag_coverage(ppp_handle h, ppp_handle_s::FlagCoverage &C, const char *what, const std::function<int()> &mark, unsigned char *flags,
-                         size_t cap, size_t *n, size_t *covered)
-{
-    const size_t N = h->n, n16 = (N + 15) / 16;
-    if (C.serial != h->pass.serial()) {
-        HIPCHK(h, C.flags.ensure(16 * std::max<size_t>(n16, 1))); HIPCHK(h, C.count.ensure(2));
-        HIPCHK(h, hipMemsetAsync(C.flags.p, 0, 16 * std::max<size_t>(n16, 1), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.count.p, 0, 2 * sizeof(int), h->stream));
-        int rc = mark();
-        if (rc) return rc;
-        if (n16)
-            LAUNCH(h, "k_cov_count", k_cov_count, (unsigned)std::min<size_t>((n16 + COV_T - 1) / COV_T, 4 * (size_t)h->num_cus), COV_T, 0,
-                   (const uint4 *)C.flags.p, (int)n16, C.count.p);
-        int res[2] = {0, 0};
-        HIPCHK(h, copy_sync(h, res, C.count.p, sizeof(res), hipMemcpyDeviceToHost));
-        rc = contact_refusal(h, what, (unsigned)res[1]);
-        if (rc) return rc;
-        if (res[0] < 0 || (size_t)res[0] > N) return fail(h, PPP_ERR_HIP, std::string(what) + " count corrupt");
-        C.covered = (size_t)res[0];
-        C.serial = h->pass.serial();
-    }
-    if (n) *n = N;
-    if (covered) *covered = C.covered;
-    const size_t k = std::min(cap, N);
-    if (flags && k) HIPCHK(h, copy_sync(h, flags, C.flags.p, k, hipMemcpyDeviceToHost));
-    return PPP_OK;
-}
-
-int ppp_get_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
-{
-    int rc = ensure_ready(h, true, false);
-    if (rc) return rc;
-    rc = map_dev_err(h);
-    if (rc) return rc;
-    if (h->P.walk != PPP_WALK_V1_CONTACT || !h->P.dynamic_adjustment || h->ranged || h->use_part || h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "coverage: only after a PPP_WALK_V1_CONTACT pass with dynamic_adjustment = 1 on a whole-cloud handle");
-    auto balls = [h]() -> int { /* raw and adjusted paths of every slice, one launch */
-        const int S = h->hmeta.S;
-        if (S > 0)
-            LAUNCH(h, "k_cov_balls", k_cov_balls, dim3((h->dyn_maxNB + DYN_WAVES - 1) / DYN_WAVES, S, 2), 64 * DYN_WAVES, 0, contact_index(h),
-                   dyn_params(h), knot_table(h), h->dyn_raw_sc.p, h->dyn_maxNB, h->cov.flags.p);
-        return PPP_OK;
-    };
-    return flag_coverage(h, h->cov, "coverage", balls, flags, cap, n, covered);
-}
-
-int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t *n, size_t *covered)
-{
-    int rc = contact_query_begin(h, "path coverage");
-    if (rc) return rc;
-    auto balls = [h]() -> int {
-        int rc = contact_prerequisites(h);
-        if (rc) return rc;
-        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S);
-        if (se <= sb) return PPP_OK;
-        /* samples per slice of knots spanning the cloud's y range (the kernel strides past it where adjusted knots reach further) */
-        const double yr = (double)h->h_mx[1] - (double)h->h_mn[1];
-        const int nb = (int)std::min(65536.0, std::max(0.0, yr - 4) / (h->P.tool_radius / 4) + 4);
-        for (int s0 = sb; s0 < se; s0 += 65535) /* (gridDim.y) */
-            LAUNCH(h, "k_pcov_balls", k_pcov_balls, dim3((nb + DYN_WAVES - 1) / DYN_WAVES, std::min(se - s0, 65535)), 64 * DYN_WAVES, 0,
-                   contact_index(h), dyn_params(h), knot_table(h), s0, pcov_range(h), h->pcov.flags.p, h->pcov.count.p + 1);
-        return PPP_OK;
-    };
-    return flag_coverage(h, h->pcov, "path coverage", balls, flags, cap, n, covered);
-}
-
-int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap, ppp_contact_stats *stats)
-{
-    int rc = contact_query_begin(h, "path contacts");
-    if (rc) return rc;
-    const size_t N = h->n;
-    auto &C = h->pcon;
-    if (C.serial != h->pass.serial()) { /* first question about this pass */
-        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
-        rc = contact_prerequisites(h);
-        if (rc) return rc;
-        const size_t N1 = std::max<size_t>(N, 1);
-        HIPCHK(h, C.counts.ensure(N1)); HIPCHK(h, C.first.ensure(N1)); HIPCHK(h, C.last.ensure(N1));
-        HIPCHK(h, C.acc.ensure(70));
-        HIPCHK(h, hipMemsetAsync(C.counts.p, 0, N1 * sizeof(unsigned), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.first.p, 0xff, N1 * sizeof(int), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.last.p, 0xff, N1 * sizeof(int), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
-        int *err = (int *)(C.acc.p + 69);
-        if (nsl > 0) {
-            HIPCHK(h, C.off.ensure((size_t)nsl + 2));
-            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), knot_table(h), sb, nsl, C.off.p, err);
-            std::vector<int> off((size_t)nsl + 2);
-            HIPCHK(h, copy_sync(h, off.data(), C.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
-            rc = contact_refusal(h, "path contacts", (unsigned)off[nsl + 1]);
-            if (rc) return rc;
-            const int rows = off[nsl];
-            int most = 0;
-            for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
-            if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, "path contacts: sample table corrupt");
-            if (rows > 0) {
-                HIPCHK(h, C.tab.ensure((size_t)rows)); HIPCHK(h, C.reach.ensure(3 * (size_t)nsl));
-                HIPCHK(h, hipMemsetAsync(C.reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
-                const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
-                for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
-                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0, contact_index(h),
-                           dyn_params(h), knot_table(h), C.off.p, sb, s0, pcov_range(h), C.tab.p, C.reach.p, err);
-                /* one thread per indexed point (at most N of them), PCON_T a round */
-                LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
-                       h->meta.p, h->sorted4.p, C.tab.p, C.off.p, C.reach.p, sb, nsl, C.counts.p, C.first.p, C.last.p);
-            }
-        }
-        LAUNCH(h, "k_pcon_stats", k_pcon_stats, (unsigned)std::min<size_t>((N1 + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus), PCON_T, 0,
-               C.counts.p, C.first.p, C.last.p, (int)N, err, C.acc.p);
-        unsigned long long acc[69];
-        HIPCHK(h, copy_sync(h, acc, C.acc.p, sizeof(acc), hipMemcpyDeviceToHost));
-        rc = contact_refusal(h, "path contacts", acc[68]);
-        if (rc) return rc;
-        if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "path contacts: statistics corrupt");
-        ppp_contact_stats st = {};
-        st.n = N; st.covered = (size_t)acc[64]; st.multi_slice = (size_t)acc[65];
-        st.total = acc[66]; st.max_count = (unsigned)acc[67];
-        st.hist[0] = N - st.covered;
-        for (int b = 1; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
-        C.stats = st;
-        C.serial = h->pass.serial();
-    }
-    if (stats) *stats = C.stats;
-    const size_t k = std::min(cap, N);
-    if (counts && k) HIPCHK(h, copy_sync(h, counts, C.counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, C.first.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, C.last.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    return PPP_OK;
-}
-
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz)
 {
     int rc = ensure_ready(h, true, false);
@@ -3410,575 +2463,6 @@ int ppp_estimate_normals(ppp_handle h, float *out4)
                h->slab_xmin.p, h->slab_xmax.p, h->slab_ytab.p, nsorted, (float4 *)h->scratch.p);
     HIPCHK(h, hipMemcpyAsync(out4, h->scratch.p, n * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PPP_OK;
-}
-
-int ppp_area2cloud(ppp_handle h, const double *pts_xyz, size_t k, int key, float *out3)
-{
-    int rc = index_ready(h, false); /* complete index: slabs beyond the LDS capacity go through the arena pass first */
-    if (rc) return rc;
-    if (!k) return PPP_OK;
-    if (!pts_xyz || !out3 || (key != 0 && key != 1)) return fail(h, PPP_ERR_ARG, "bad arguments");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    rc = ensure_dynamic_buffers(h);
-    if (rc) return rc;
-    rc = enqueue_normals(h);
-    if (rc) return rc;
-    HIPCHK(h, h->scratch.ensure(k * 36 + 64));
-    double *dq = (double *)h->scratch.p;
-    float *dout = (float *)(dq + 3 * k);
-    HIPCHK(h, hipMemcpyAsync(dq, pts_xyz, k * 24, hipMemcpyHostToDevice, h->stream));
-    LAUNCH(h, "k_area2cloud_api", k_area2cloud_api, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
-           dq, (int)k, key, dout);
-    HIPCHK(h, hipMemcpyAsync(out3, dout, k * 12, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PPP_OK;
-}
-
-int ppp_principal_curvatures_at(ppp_handle h, const float *q_xyz, size_t k, float *out5)
-{
-    int rc = index_ready(h, false); /* complete index: slabs beyond the LDS capacity go through the arena pass first */
-    if (rc) return rc;
-    if (!k) return PPP_OK;
-    if (!q_xyz || !out5 || k > 0x7fffffffu / 8) return fail(h, PPP_ERR_ARG, "bad arguments");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    rc = contact_buffers(h);
-    if (rc) return rc;
-    HIPCHK(h, h->scratch.ensure(k * 32 + 64));
-    float *dq = (float *)h->scratch.p, *dout = dq + 3 * k;
-    HIPCHK(h, hipMemcpyAsync(dq, q_xyz, k * 12, hipMemcpyHostToDevice, h->stream));
-    LAUNCH(h, "k_field_waves", k_field_waves, (unsigned)((k + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), dyn_params(h),
-           dq, (int)k, dout, (float *)nullptr);
-    HIPCHK(h, hipMemcpyAsync(out5, dout, k * 20, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return PPP_OK;
-}
-
-/* the parameters a contact field depends on */
-static bool same_contact_params(const ppp_params &P, const ppp_params &F)
-{
-    return P.tool_radius == F.tool_radius && P.depth == F.depth && P.toolthickness == F.toolthickness && P.curvature_k == F.curvature_k &&
-           P.normal_radius == F.normal_radius && P.change_range == F.change_range;
-}
-
-/* the statistics of a stored half-width map for one min_width (k_field_stats): hw = N half widths by cloud index */
-static int field_statistics(ppp_handle h, const float *hw, DevBuf<unsigned long long> &dacc, DevBuf<double> &dpsum, float min_width,
-                            ppp_contact_field_stats &st)
-{
-    const size_t N = h->n;
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
-    const int per = (int)((N + grid - 1) / grid);
-    HIPCHK(h, dacc.ensure(68)); HIPCHK(h, dpsum.ensure((size_t)grid));
-    HIPCHK(h, hipMemsetAsync(dacc.p, 0, 68 * sizeof(unsigned long long), h->stream));
-    LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, hw, (int)N, per, h->P.tool_radius, min_width, dacc.p, dpsum.p);
-    unsigned long long acc[68];
-    std::vector<double> psum((size_t)grid);
-    HIPCHK(h, copy_sync(h, acc, dacc.p, sizeof(acc), hipMemcpyDeviceToHost));
-    HIPCHK(h, copy_sync(h, psum.data(), dpsum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "contact field: statistics corrupt");
-    st = {};
-    st.n = N; st.valid = (size_t)acc[64]; st.narrow = (size_t)acc[65];
-    st.min_abs_r = st.valid ? -ordered_unkey((unsigned)acc[66]) : NAN; st.max_abs_r = st.valid ? ordered_unkey((unsigned)acc[67]) : NAN;
-    for (double v : psum) st.sum_abs_r += v;
-    for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[b];
-    return PPP_OK;
-}
-static int field_statistics(ppp_handle h, float min_width)
-{
-    auto &C = h->field;
-    int rc = field_statistics(h, C.hw.p, C.acc, C.psum, min_width, C.stats);
-    if (!rc) C.min_width = min_width;
-    return rc;
-}
-
-int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t cap, float min_width, ppp_contact_field_stats *stats)
-{
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "contact field: the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
-    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
-        return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    if (!(min_width > 0.f)) min_width = 0.f;
-    const size_t N = h->n;
-    auto &C = h->field;
-    const ppp_params &P = h->P, &F = C.P;
-    const bool same = C.valid && same_contact_params(P, F);
-    if (!same) {
-        C.valid = false;
-        int rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-        if (rc) return rc;
-        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "contact field: a slice-range handle indexes a part of the cloud only");
-        rc = contact_buffers(h);
-        if (rc) return rc;
-        const size_t N1 = std::max<size_t>(N, 1);
-        HIPCHK(h, C.curv.ensure(5 * N1)); HIPCHK(h, C.hw.ensure(N1));
-        HIPCHK(h, hipMemsetAsync(C.curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* dropped points: NaN */
-        HIPCHK(h, hipMemsetAsync(C.hw.p, 0xff, N1 * sizeof(float), h->stream));
-        const int nsorted = h->hmeta.n_sorted;
-        if (nsorted < 0 || (size_t)nsorted > N) return fail(h, PPP_ERR_HIP, "contact field: index corrupt");
-        if (nsorted > 0) /* a wave per FIELD_Q indexed points, in slab / y order */
-            LAUNCH(h, "k_field_batch", k_field_batch, (unsigned)((nsorted + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
-                   contact_index(h), dyn_params(h), nsorted, C.curv.p, C.hw.p);
-        rc = field_statistics(h, min_width);
-        if (rc) return rc;
-        C.P = h->P;
-        C.valid = true; ++C.built;
-    } else if (stats && min_width != C.min_width) {
-        int rc = field_statistics(h, min_width);
-        if (rc) return rc;
-    }
-    if (stats) *stats = C.stats;
-    const size_t k = std::min(cap, N);
-    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
-    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
-    return PPP_OK;
-}
-
-/* What this handle's tile evaluates and owns, behind a plan: the cuts of its range [sb, se) on the walk of the
-   whole cloud's bounds, widened by halo; a whole-cloud handle owns and evaluates everything. */
-static int tile_range(ppp_handle h, float halo, TileRange &T)
-{
-    T = TileRange{-INFINITY, INFINITY, -INFINITY, INFINITY};
-    if (!h->ranged) return PPP_OK;
-    const int S = h->S_cap;
-    std::vector<float> px((size_t)S);
-    if (ppp_slice_walk(h->P.walk, h->h_mn[0], h->h_mx[0], h->P.tool_radius, px.data(), S) != S) return fail(h, PPP_ERR_HIP, "tile: the slice walk changed under the plan");
-    owned_cuts(px.data(), S, h->sb, h->se, &T.own_lo, &T.own_hi);
-    T.ev_lo = T.own_lo - halo; T.ev_hi = T.own_hi + halo;
-    return PPP_OK;
-}
-
-/* does the interval [lo, hi] leave what the handle indexes at a side that is not the cloud's end? (wave_ball_leaves_range's test) */
-static bool leaves_indexed_range(const ppp_handle h, float lo, float hi)
-{
-    return h->ranged && lo <= hi && ((lo < h->incl_lo && h->incl_lo > h->h_mn[0]) || (hi > h->incl_hi && h->incl_hi < h->h_mx[0]));
-}
-
-/* the positions [pos0, pos1) of the slabs that meet the tile's evaluated interval (one slab more on either side: the kernels
-   test every point themselves), behind index_ready */
-static int tile_positions(ppp_handle h, const TileRange &T, int &pos0, int &pos1)
-{
-    pos0 = pos1 = 0;
-    const int ns = h->hmeta.n_sorted;
-    if (ns < 0 || (size_t)ns > h->n) return fail(h, PPP_ERR_HIP, "tile: index corrupt");
-    if (!(T.ev_lo <= T.ev_hi) || ns == 0) return PPP_OK;
-    const SlabGeom G = slab_geom(h);
-    auto slab_of_host = [&](float x) { return (int)fminf(fmaxf((x - G.slab_x0) * G.slab_invw, 0.f), (float)(h->B - 1)); };
-    const int b0 = std::max(0, slab_of_host(T.ev_lo) - 1), b1 = std::min(h->B - 1, slab_of_host(T.ev_hi) + 1);
-    HIPCHK(h, copy_sync(h, &pos0, h->slab_start.p + b0, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(h, copy_sync(h, &pos1, h->slab_start.p + b1 + 1, sizeof(int), hipMemcpyDeviceToHost));
-    if (pos0 < 0 || pos1 < pos0 || pos1 > ns) return fail(h, PPP_ERR_HIP, "tile: slab table corrupt");
-    return PPP_OK;
-}
-
-static void tile_field_stats(ppp_contact_field_tile_stats &o, const ppp_contact_field_stats &st)
-{
-    o.n = st.n; o.valid = st.valid; o.narrow = st.narrow; o.min_abs_r = st.min_abs_r; o.max_abs_r = st.max_abs_r; o.sum_abs_r = st.sum_abs_r;
-    memcpy(o.hist, st.hist, sizeof(o.hist));
-}
-
-int ppp_get_contact_field_tile(ppp_handle h, float *curv5, float *half_width, unsigned char *owned, size_t cap, float halo,
-                               float min_width, ppp_contact_field_tile_stats *stats)
-{
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "contact field tile: the maps address the whole cloud: this handle holds a part (ppp_set_cloud_part)");
-    if (h->P.curvature_k < 3 || h->P.curvature_k > 64) return fail(h, PPP_ERR_ARG, "curvature_k must be in [3, 64]");
-    if (!(halo >= 0.f && halo <= 3.402823466e+38f)) return fail(h, PPP_ERR_ARG, "contact field tile: halo must be a finite number >= 0");
-    if (!(min_width > 0.f)) min_width = 0.f;
-    const size_t N = h->n;
-    auto &C = h->ftile;
-    const ppp_params &P = h->P, &F = C.P;
-    const bool same = C.valid && same_contact_params(P, F) && P.walk == F.walk && P.slice_begin == F.slice_begin && P.slice_end == F.slice_end &&
-                      P.range_margin == F.range_margin && halo == C.halo;
-    if (!same) {
-        C.valid = false;
-        int rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-        if (rc) return rc;
-        rc = contact_buffers(h);
-        if (rc) return rc;
-        TileRange T;
-        rc = tile_range(h, halo, T);
-        if (rc) return rc;
-        int pos0, pos1;
-        rc = tile_positions(h, T, pos0, pos1);
-        if (rc) return rc;
-        const size_t N1 = std::max<size_t>(N, 1);
-        HIPCHK(h, C.curv.ensure(5 * N1)); HIPCHK(h, C.hw.ensure(N1)); HIPCHK(h, C.hw_own.ensure(N1)); HIPCHK(h, C.owned.ensure(N1));
-        HIPCHK(h, C.cnt.ensure(4));
-        HIPCHK(h, hipMemsetAsync(C.curv.p, 0xff, 5 * N1 * sizeof(float), h->stream)); /* not evaluated: NaN */
-        HIPCHK(h, hipMemsetAsync(C.hw.p, 0xff, N1 * sizeof(float), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.hw_own.p, 0xff, N1 * sizeof(float), h->stream));
-        HIPCHK(h, hipMemsetAsync(C.owned.p, 0, N1, h->stream));
-        HIPCHK(h, hipMemsetAsync(C.cnt.p, 0, 4 * sizeof(int), h->stream));
-        if (pos1 > pos0) {
-            const int np = pos1 - pos0;
-            LAUNCH(h, "k_tile_mark", k_tile_mark, (unsigned)((np + PCON_T - 1) / PCON_T), PCON_T, 0, h->sorted4.p, pos0, pos1, T, C.owned.p, C.cnt.p);
-            LAUNCH(h, "k_field_tile", k_field_tile, (unsigned)((np + FIELD_Q * DYN_WAVES - 1) / (FIELD_Q * DYN_WAVES)), 64 * DYN_WAVES, 0,
-                   contact_index(h), dyn_params(h), pos0, pos1, T, pcov_range(h), C.curv.p, C.hw.p, C.hw_own.p, C.cnt.p + 2);
-        }
-        int cnt[3];
-        HIPCHK(h, copy_sync(h, cnt, C.cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
-        if (cnt[2])
-            return fail(h, PPP_ERR_CAPACITY, "contact field tile: a search of an evaluated point (its neighbours or their normals) reaches beyond the indexed slice range: raise range_margin");
-        if (cnt[0] < 0 || cnt[1] < cnt[0] || (size_t)cnt[1] > N) return fail(h, PPP_ERR_HIP, "contact field tile: counts corrupt");
-        ppp_contact_field_stats st;
-        rc = field_statistics(h, C.hw_own.p, C.acc, C.psum, min_width, st);
-        if (rc) return rc;
-        C.stats = {};
-        C.stats.owned = (size_t)cnt[0]; C.stats.evaluated = (size_t)cnt[1]; C.stats.own_lo = T.own_lo; C.stats.own_hi = T.own_hi;
-        tile_field_stats(C.stats, st);
-        C.P = h->P; C.halo = halo; C.min_width = min_width;
-        C.valid = true; ++C.built;
-    } else if (stats && min_width != C.min_width) {
-        ppp_contact_field_stats st;
-        int rc = field_statistics(h, C.hw_own.p, C.acc, C.psum, min_width, st);
-        if (rc) return rc;
-        tile_field_stats(C.stats, st);
-        C.min_width = min_width;
-    }
-    if (stats) *stats = C.stats;
-    const size_t k = std::min(cap, N);
-    if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
-    if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
-    if (owned && k) HIPCHK(h, copy_sync(h, owned, C.owned.p, k, hipMemcpyDeviceToHost));
-    return PPP_OK;
-}
-
-/* lanes per selected point in k_reg_link */
-#ifndef REG_GROUP
-#define REG_GROUP 8
-#endif
-
-/* The device work of a region call, behind index_ready and the source's own call: select inside T's evaluated interval, list,
-   link, flatten (T's owned points count), label, the rows in ascending label -- into h->regions' buffers.  half_width: the map
-   PPP_REGIONS_NARROW reads.  nsel / nreg: the listed points and the regions (a tile's: every component of the list). */
-static int regions_compute(ppp_handle h, int source, const unsigned char *mask, const float *half_width, float threshold, float link,
-                           const TileRange &T, size_t &nsel, size_t &nreg, unsigned tot[4])
-{
-    const size_t N = h->n;
-    auto &R = h->regions;
-    R.valid = false;
-    nsel = nreg = 0;
-    const int ns = h->hmeta.n_sorted;
-    if (ns < 0 || (size_t)ns > N || N > 0x7fffffffu) return fail(h, PPP_ERR_HIP, "regions: index corrupt");
-    const size_t N1 = std::max<size_t>(N, 1);
-    const int nb_sel = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nb_head = (int)((N + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
-    HIPCHK(h, R.labels.ensure(N1)); HIPCHK(h, R.head_root.ensure(N1)); HIPCHK(h, R.tot.ensure(8));
-    HIPCHK(h, R.cnt.ensure((size_t)std::max(nb_sel, nb_head) + 1));
-    HIPCHK(h, hipMemsetAsync(R.labels.p, 0xff, N1 * sizeof(int), h->stream)); /* not selected: -1 */
-    HIPCHK(h, hipMemsetAsync(R.tot.p, 0, 8 * sizeof(unsigned), h->stream));
-    int *err = (int *)R.tot.p + 3;
-    int rc = PPP_OK;
-    if (ns > 0) {
-        HIPCHK(h, R.sel.ensure((size_t)ns)); HIPCHK(h, R.ord.ensure((size_t)ns));
-        HIPCHK(h, hipMemsetAsync(R.ord.p, 0xff, (size_t)ns * sizeof(int), h->stream));
-        RegSource S = {source, nullptr, nullptr, nullptr, nullptr, threshold};
-        if (source == PPP_REGIONS_UNCOVERED) S.bytes = h->pcov.flags.p;
-        else if (source == PPP_REGIONS_OVERLAP) { S.first = h->pcon.first.p; S.last = h->pcon.last.p; }
-        else if (source == PPP_REGIONS_NARROW) S.half_width = half_width;
-        else {
-            HIPCHK(h, R.mask.ensure(N1));
-            HIPCHK(h, hipMemcpyAsync(R.mask.p, mask, N, hipMemcpyHostToDevice, h->stream));
-            S.bytes = R.mask.p;
-        }
-        LAUNCH(h, "k_reg_select", k_reg_select, (unsigned)((ns + REG_T - 1) / REG_T), REG_T, 0, h->sorted4.p, ns, S, T, R.sel.p);
-        RegSel sel = {R.sel.p, nullptr, R.ord.p, nullptr, nullptr};
-        rc = compact(h, sel, ns, R.cnt.p, (int *)R.tot.p + 4, [&](int kept) -> int {
-            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "regions: selection count corrupt");
-            nsel = (size_t)kept;
-            HIPCHK(h, R.list.ensure(nsel)); HIPCHK(h, R.parent.ensure(nsel)); HIPCHK(h, R.acc.ensure(nsel));
-            sel.list = R.list.p; sel.parent = R.parent.p; sel.acc = R.acc.p;
-            return PPP_OK;
-        });
-        if (rc) return rc;
-    }
-    if (nsel > 0) {
-        const float r2 = link * link;
-        int grp = REG_GROUP;
-        if (const char *ev = tuning_env("PPP_REG_GROUP")) grp = atoi(ev); /* tuning runs only */
-        const unsigned gl = (unsigned)((nsel * (size_t)grp + REG_T - 1) / REG_T), gp = (unsigned)((nsel + REG_T - 1) / REG_T);
-#define PPP_REG_LINK(G) LAUNCH(h, "k_reg_link", k_reg_link<G>, gl, REG_T, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_ytab.p, R.list.p, (int)nsel, R.ord.p, R.parent.p, link, r2, err)
-        if (grp == 1) PPP_REG_LINK(1);
-        else if (grp == 4) PPP_REG_LINK(4);
-        else if (grp == 16) PPP_REG_LINK(16);
-        else if (grp == 64) PPP_REG_LINK(64);
-        else if (grp == 8) PPP_REG_LINK(8);
-        else return fail(h, PPP_ERR_ARG, "regions: PPP_REG_GROUP must be 1, 4, 8, 16 or 64");
-#undef PPP_REG_LINK
-        LAUNCH(h, "k_reg_flatten", k_reg_flatten, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, T, err);
-        LAUNCH(h, "k_reg_labels", k_reg_labels, gp, REG_T, 0, h->sorted4.p, R.list.p, (int)nsel, R.parent.p, R.acc.p, (int)N, R.labels.p,
-               R.head_root.p, R.tot.p);
-        RegHeadSel heads = {R.labels.p, R.head_root.p, R.acc.p, nullptr};
-        rc = compact(h, heads, (int)N, R.cnt.p, (int *)R.tot.p + 5, [&](int kept) -> int {
-            if (kept < 0 || (size_t)kept > nsel) return fail(h, PPP_ERR_HIP, "regions: region count corrupt");
-            nreg = (size_t)kept;
-            HIPCHK(h, R.rows.ensure(nreg));
-            heads.rows = R.rows.p;
-            return PPP_OK;
-        });
-        if (rc) return rc;
-    }
-    HIPCHK(h, copy_sync(h, tot, R.tot.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (tot[3]) return fail(h, PPP_ERR_CAPACITY, "regions: a union-find walk reached its trip cap");
-    if (tot[0] != nreg || tot[1] > nreg || tot[2] > nsel) return fail(h, PPP_ERR_HIP, "regions: totals corrupt");
-    return PPP_OK;
-}
-
-/* the argument checks every region call makes */
-static int regions_arguments(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius)
-{
-    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
-    if (source < PPP_REGIONS_UNCOVERED || source > PPP_REGIONS_MASK) return fail(h, PPP_ERR_ARG, "regions: unknown source");
-    if (source == PPP_REGIONS_MASK && !mask) return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_MASK needs a mask");
-    if (source == PPP_REGIONS_NARROW && !(threshold > 0.f && threshold <= 3.402823466e+38f))
-        return fail(h, PPP_ERR_ARG, "regions: PPP_REGIONS_NARROW needs a positive finite threshold");
-    if (!(fabsf(link_radius) <= 3.402823466e+38f)) return fail(h, PPP_ERR_ARG, "regions: link_radius is not a finite number");
-    if (h->part_given)
-        return fail(h, PPP_ERR_UNSUPPORTED, "regions: a region does not stop at a part's border: this handle holds a part (ppp_set_cloud_part)");
-    return PPP_OK;
-}
-
-/* could a region's fixed-point sum leave 64 bits?  then no centroid is given (B.34) */
-static bool regions_nan_centroid(double reach, size_t selected) { return reach * REG_FIXED * (double)selected >= 4611686018427387904.0; }
-
-int ppp_get_regions(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius, int *labels, size_t cap,
-                    ppp_region *regions, size_t region_cap, ppp_region_stats *stats)
-{
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    { int rca = regions_arguments(h, source, mask, threshold, link_radius); if (rca) return rca; }
-    if (h->P.slice_begin != 0 || h->P.slice_end != 0)
-        return fail(h, PPP_ERR_UNSUPPORTED, "regions: a region does not stop at a range border: a slice-range handle indexes a part of the cloud only");
-    const float link = link_radius > 0.f ? link_radius : h->P.normal_radius;
-    if (source != PPP_REGIONS_NARROW) threshold = 0.f;
-    /* the source's own call: builds its result if the handle does not hold it, answers from it if it does, refuses as it does */
-    unsigned long long serial = 0;
-    int rc = PPP_OK;
-    if (source == PPP_REGIONS_UNCOVERED) { rc = ppp_get_path_coverage(h, nullptr, 0, nullptr, nullptr); serial = h->pcov.serial; }
-    else if (source == PPP_REGIONS_OVERLAP) { rc = ppp_get_path_contacts(h, nullptr, nullptr, nullptr, 0, nullptr); serial = h->pcon.serial; }
-    else if (source == PPP_REGIONS_NARROW) { rc = ppp_get_contact_field(h, nullptr, nullptr, 0, 0.f, nullptr); serial = h->field.built; }
-    if (rc) return rc;
-    const size_t N = h->n;
-    auto &R = h->regions;
-    const bool reuse = source != PPP_REGIONS_MASK && R.valid && R.source == source && R.threshold == threshold && R.link == link &&
-                       R.serial == serial && R.stats.n == N;
-    if (!reuse) {
-        R.valid = false;
-        rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-        if (rc) return rc;
-        if (h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, "regions: a slice-range handle indexes a part of the cloud only");
-        double reach = 0.0; /* the largest |coordinate| of the index */
-        for (int d = 0; d < 3; ++d) reach = std::max(reach, std::max(std::fabs((double)h->hmeta.mn[d]), std::fabs((double)h->hmeta.mx[d])));
-        size_t nsel = 0, nreg = 0;
-        unsigned tot[4];
-        rc = regions_compute(h, source, mask, h->field.hw.p, threshold, link, TileRange{-INFINITY, INFINITY, -INFINITY, INFINITY}, nsel, nreg, tot);
-        if (rc) return rc;
-        ppp_region_stats st = {};
-        st.n = N; st.selected = nsel; st.regions = nreg; st.singletons = tot[1]; st.largest = tot[2];
-        R.stats = st;
-        R.nan_centroid = regions_nan_centroid(reach, nsel);
-        R.source = source; R.threshold = threshold; R.link = link; R.serial = serial;
-        R.valid = true;
-    }
-    if (stats) *stats = R.stats;
-    const size_t k = std::min(cap, N);
-    if (labels && k) HIPCHK(h, copy_sync(h, labels, R.labels.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    const size_t kr = std::min(region_cap, R.stats.regions);
-    if (regions && kr) {
-        std::vector<RegAcc> rows(kr);
-        HIPCHK(h, copy_sync(h, rows.data(), R.rows.p, kr * sizeof(RegAcc), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < kr; ++i) {
-            const RegAcc &a = rows[i];
-            ppp_region &o = regions[i];
-            o.label = a.label; o.count = a.count;
-            for (int c = 0; c < 3; ++c) {
-                o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]);
-                o.centroid[c] = R.nan_centroid ? (double)NAN : (double)a.sum[c] / (double)a.count / REG_FIXED;
-            }
-        }
-    }
-    return PPP_OK;
-}
-
-int ppp_get_regions_tile(ppp_handle h, int source, const unsigned char *mask, float threshold, float link_radius, int *labels, size_t cap,
-                         ppp_region_part *parts, size_t part_cap, ppp_region_halo *halos, size_t halo_cap, ppp_region_tile_stats *stats)
-{
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = regions_arguments(h, source, mask, threshold, link_radius);
-    if (rc) return rc;
-    if (source == PPP_REGIONS_UNCOVERED || source == PPP_REGIONS_OVERLAP)
-        return fail(h, PPP_ERR_UNSUPPORTED, "regions tile: a range's coverage knows its own slices' balls only: OR the ranges' flags (ppp_get_path_coverage) and pass the result as a mask (PPP_REGIONS_MASK)");
-    const float link = link_radius > 0.f ? link_radius : h->P.normal_radius;
-    if (source != PPP_REGIONS_NARROW) threshold = 0.f;
-    unsigned long long serial = 0;
-    if (source == PPP_REGIONS_NARROW) { /* the field of the owned points and a halo of one link radius */
-        rc = ppp_get_contact_field_tile(h, nullptr, nullptr, nullptr, 0, link, 0.f, nullptr);
-        if (rc) return rc;
-        serial = h->ftile.built;
-    }
-    const size_t N = h->n;
-    auto &Q = h->rtile;
-    const bool reuse = source != PPP_REGIONS_MASK && Q.valid && Q.source == source && Q.threshold == threshold && Q.link == link &&
-                       Q.serial == serial && Q.stats.n == N;
-    if (!reuse) {
-        Q.valid = false;
-        rc = index_ready(h, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-        if (rc) return rc;
-        TileRange T;
-        rc = tile_range(h, link, T);
-        if (rc) return rc;
-        if (leaves_indexed_range(h, T.ev_lo, T.ev_hi))
-            return fail(h, PPP_ERR_CAPACITY, "regions tile: the owned interval widened by the link radius reaches beyond the indexed slice range: raise range_margin");
-        const unsigned char *owned_map = h->ftile.owned.p;
-        if (source == PPP_REGIONS_MASK) { /* the owned map of this range and link */
-            int pos0, pos1;
-            rc = tile_positions(h, T, pos0, pos1);
-            if (rc) return rc;
-            const size_t N1 = std::max<size_t>(N, 1);
-            HIPCHK(h, Q.owned.ensure(N1)); HIPCHK(h, Q.cnt.ensure(2));
-            HIPCHK(h, hipMemsetAsync(Q.owned.p, 0, N1, h->stream));
-            HIPCHK(h, hipMemsetAsync(Q.cnt.p, 0, 2 * sizeof(int), h->stream));
-            if (pos1 > pos0)
-                LAUNCH(h, "k_tile_mark", k_tile_mark, (unsigned)((pos1 - pos0 + PCON_T - 1) / PCON_T), PCON_T, 0, h->sorted4.p, pos0, pos1, T,
-                       Q.owned.p, Q.cnt.p);
-            owned_map = Q.owned.p;
-        }
-        size_t nsel = 0, nreg = 0;
-        unsigned tot[4];
-        rc = regions_compute(h, source, mask, h->ftile.hw.p, threshold, link, T, nsel, nreg, tot);
-        if (rc) return rc;
-        /* the tile's view of the device result: labels of the owned points, the components with an owned point, their halo points */
-        std::vector<unsigned char> own(N);
-        std::vector<RegAcc> rows(nreg);
-        Q.labels.assign(N, -1);
-        if (N) HIPCHK(h, copy_sync(h, own.data(), owned_map, N, hipMemcpyDeviceToHost));
-        if (N && nsel) HIPCHK(h, copy_sync(h, Q.labels.data(), h->regions.labels.p, N * sizeof(int), hipMemcpyDeviceToHost));
-        if (nreg) HIPCHK(h, copy_sync(h, rows.data(), h->regions.rows.p, nreg * sizeof(RegAcc), hipMemcpyDeviceToHost));
-        Q.parts.clear(); Q.halos.clear();
-        size_t selected = 0;
-        for (const RegAcc &a : rows) {
-            if (!a.count) continue; /* a component of halo points alone: its owners' tiles report it */
-            ppp_region_part o;
-            o.label = a.label; o.count = a.count;
-            for (int c = 0; c < 3; ++c) { o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]); o.fsum[c] = a.sum[c]; }
-            Q.parts.push_back(o);
-            selected += a.count;
-        }
-        auto has_part = [&](int label) {
-            auto it = std::lower_bound(Q.parts.begin(), Q.parts.end(), label, [](const ppp_region_part &r, int l) { return r.label < l; });
-            return it != Q.parts.end() && it->label == label;
-        };
-        for (size_t i = 0; i < N; ++i) {
-            if (own[i] == 1 || Q.labels[i] < 0) continue;
-            if (own[i] == 2 && has_part(Q.labels[i])) Q.halos.push_back(ppp_region_halo{(int)i, Q.labels[i]});
-            Q.labels[i] = -1;
-        }
-        ppp_region_tile_stats st = {};
-        st.n = N; st.selected = selected; st.parts = Q.parts.size(); st.halo_points = Q.halos.size();
-        for (int d = 0; d < 3; ++d) /* the whole cloud's bounds: the same on every handle of the cloud */
-            st.max_abs_coord = std::max(st.max_abs_coord, std::max(std::fabs((double)h->h_mn[d]), std::fabs((double)h->h_mx[d])));
-        st.own_lo = T.own_lo; st.own_hi = T.own_hi;
-        Q.stats = st;
-        Q.source = source; Q.threshold = threshold; Q.link = link; Q.serial = serial;
-        Q.valid = true;
-    }
-    if (stats) *stats = Q.stats;
-    const size_t k = std::min(cap, N), kp = std::min(part_cap, Q.parts.size()), kh = std::min(halo_cap, Q.halos.size());
-    if (labels && k) memcpy(labels, Q.labels.data(), k * sizeof(int));
-    if (parts && kp) memcpy(parts, Q.parts.data(), kp * sizeof(ppp_region_part));
-    if (halos && kh) memcpy(halos, Q.halos.data(), kh * sizeof(ppp_region_halo));
-    return PPP_OK;
-}
-
-int ppp_merge_region_tiles(size_t tiles, const int *const *labels, const ppp_region_part *const *parts, const ppp_region_halo *const *halos,
-                           const ppp_region_tile_stats *stats, int *out_labels, size_t cap, ppp_region *regions, size_t region_cap,
-                           ppp_region_stats *out_stats)
-{
-    if (!tiles || !labels || !parts || !halos || !stats) return PPP_ERR_ARG;
-    const size_t N = stats[0].n;
-    std::vector<size_t> first(tiles + 1, 0); /* node of (t, part j) = first[t] + j */
-    size_t selected = 0;
-    double reach = 0.0;
-    for (size_t t = 0; t < tiles; ++t) {
-        if (stats[t].n != N || !labels[t] || (stats[t].parts && !parts[t]) || (stats[t].halo_points && !halos[t])) return PPP_ERR_ARG;
-        for (size_t j = 1; j < stats[t].parts; ++j) if (!(parts[t][j - 1].label < parts[t][j].label)) return PPP_ERR_ARG;
-        first[t + 1] = first[t] + stats[t].parts;
-        selected += stats[t].selected;
-        reach = std::max(reach, stats[t].max_abs_coord);
-    }
-    auto node_of = [&](size_t t, int label) -> long long { /* -1: tile t has no part of that label */
-        const ppp_region_part *b = parts[t], *e = b + stats[t].parts;
-        const ppp_region_part *it = std::lower_bound(b, e, label, [](const ppp_region_part &r, int l) { return r.label < l; });
-        return it != e && it->label == label ? (long long)(first[t] + (size_t)(it - b)) : -1;
-    };
-    /* who owns a point: the one tile that labels it */
-    std::vector<int> owner(N, -1);
-    for (size_t t = 0; t < tiles; ++t)
-        for (size_t i = 0; i < N; ++i)
-            if (labels[t][i] >= 0) {
-                if (owner[i] >= 0) return PPP_ERR_ARG; /* owned twice */
-                owner[i] = (int)t;
-            }
-    const size_t nodes = first[tiles];
-    std::vector<size_t> parent(nodes);
-    for (size_t v = 0; v < nodes; ++v) parent[v] = v;
-    auto find = [&](size_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
-    for (size_t t = 0; t < tiles; ++t)
-        for (size_t e = 0; e < stats[t].halo_points; ++e) {
-            const ppp_region_halo &hp = halos[t][e];
-            if (hp.cloud_index < 0 || (size_t)hp.cloud_index >= N || owner[(size_t)hp.cloud_index] < 0) return PPP_ERR_ARG; /* nobody's point */
-            const size_t u = (size_t)owner[(size_t)hp.cloud_index];
-            const long long a = node_of(t, hp.label), b = node_of(u, labels[u][(size_t)hp.cloud_index]);
-            if (a < 0 || b < 0) return PPP_ERR_ARG;
-            const size_t ra = find((size_t)a), rb = find((size_t)b);
-            if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
-        }
-    /* the merged rows: integer sums, minima and maxima (as ordered keys: the order the device's atomics fold in) */
-    struct Row { int label; unsigned long long count; unsigned kmn[3], kmx[3]; long long sum[3]; };
-    std::vector<Row> acc(nodes, Row{0x7fffffff, 0, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}});
-    for (size_t t = 0; t < tiles; ++t)
-        for (size_t j = 0; j < stats[t].parts; ++j) {
-            const ppp_region_part &p = parts[t][j];
-            Row &r = acc[find(first[t] + j)];
-            r.label = std::min(r.label, p.label); r.count += p.count;
-            for (int c = 0; c < 3; ++c) {
-                r.kmn[c] = std::max(r.kmn[c], ordered_key(-p.mn[c])); r.kmx[c] = std::max(r.kmx[c], ordered_key(p.mx[c]));
-                r.sum[c] = (long long)((unsigned long long)r.sum[c] + (unsigned long long)p.fsum[c]);
-            }
-        }
-    std::vector<size_t> roots;
-    for (size_t v = 0; v < nodes; ++v) if (parent[v] == v) roots.push_back(v);
-    std::sort(roots.begin(), roots.end(), [&](size_t a, size_t b) { return acc[a].label < acc[b].label; });
-    ppp_region_stats st = {};
-    st.n = N; st.selected = selected; st.regions = roots.size();
-    for (size_t v : roots) { st.singletons += acc[v].count == 1; st.largest = std::max(st.largest, (size_t)acc[v].count); }
-    if (out_stats) *out_stats = st;
-    const bool nan_centroid = regions_nan_centroid(reach, selected);
-    const size_t kr = std::min(region_cap, roots.size());
-    for (size_t i = 0; regions && i < kr; ++i) {
-        const Row &a = acc[roots[i]];
-        ppp_region &o = regions[i];
-        o.label = a.label; o.count = (unsigned)a.count;
-        for (int c = 0; c < 3; ++c) {
-            o.mn[c] = -ordered_unkey(a.kmn[c]); o.mx[c] = ordered_unkey(a.kmx[c]);
-            o.centroid[c] = nan_centroid ? (double)NAN : (double)a.sum[c] / (double)o.count / REG_FIXED;
-        }
-    }
-    const size_t k = std::min(cap, N);
-    for (size_t i = 0; out_labels && i < k; ++i) {
-        out_labels[i] = -1;
-        if (owner[i] < 0) continue;
-        const long long v = node_of((size_t)owner[i], labels[(size_t)owner[i]][i]);
-        if (v < 0) return PPP_ERR_ARG; /* a label without its part row */
-        out_labels[i] = acc[find((size_t)v)].label;
-    }
     return PPP_OK;
 }
 
@@ -4230,3 +2714,8 @@ int ppp_get_kernel_times(ppp_handle h, char *names, float *ms, int *launches, si
 }
 
 } /* extern "C" */
+
+#ifdef PPP_SINGLE_TU /* (see the top: the other units' kernels stamp into the same g_stamps) */
+#include "ppp_contact.hip"
+#include "ppp_preproc.hip"
+#endif

@@ -13,9 +13,12 @@
  * LDS bandwidth and by dependent-load latency.
  */
 #pragma once
-/* The kernels of this header belong to the engine's translation unit.  A translation unit that needs the header's types and device
-   helpers only (ppp_window.hip) defines PPP_KERNELS_FOREIGN: the non-template kernels are templates there and, never launched,
-   never instantiated (a static kernel would still be compiled and emitted: 47 functions in that translation unit's code object). */
+/* Every kernel is compiled in exactly one translation unit.  The kernels of this header, the chain kernels of ppp_dynamic.h and
+   k_area2cloud_api, and k_compact_scan (ppp_compact.h) belong to the engine's (ppp_engine.hip); ppp_contact.hip owns the kernels of
+   ppp_contact.h and ppp_regions.h, ppp_preproc.hip those of ppp_preproc.h and ppp_align.h, ppp_window.hip those of ppp_window.h.  A
+   unit that needs the engine's headers for their types and device helpers only defines PPP_KERNELS_FOREIGN: the non-template
+   kernels are templates there and, never launched, never instantiated (a static kernel would still be compiled and emitted: 47
+   functions in that translation unit's code object); the two that such a unit launches itself are plain declarations there. */
 #ifdef PPP_KERNELS_FOREIGN
 #define PPP_KERNEL template <typename PPP_NEVER_ = void> __global__
 #else

@@ -11,6 +11,7 @@
  */
 #pragma once
 #include "ppp_dynamic.h"
+#include "ppp_compact.h"
 
 struct SorStats { double sum, sq_sum, threshold; int valid, n_kept; };
 
@@ -74,72 +75,6 @@ __global__ void __launch_bounds__(256) k_sor_threshold(const DevMeta *m, const d
         const double variance = (sq_sum - sum * sum / valid) / (valid - 1);
         st->sum = sum; st->sq_sum = sq_sum; st->valid = m->n_sorted;
         st->threshold = mean + std_mul * sqrt(variance);
-    }
-}
-
-/* ------------------------------------------------------------------------------------------------------------------ */
-/* Ordered compaction (the points SOR keeps, the voxel heads, MLS's survivors, a range part): per block of            */
-/* COMPACT_CHUNK elements the number kept (k_compact_count), the scan of those counts (k_compact_scan), then every    */
-/* block writes its kept elements in input order behind its offset (k_compact_emit).  A selector says what is kept:   */
-/* begin() loads its per-workgroup constants, load(i) reads element i, keep(i, v) tests it, emit(i, k, v) writes      */
-/* the kept element i to slot k from the same v.                                                                      */
-/* ------------------------------------------------------------------------------------------------------------------ */
-#define COMPACT_CHUNK 1024
-template <class Sel>
-__global__ void __launch_bounds__(256) k_compact_count(Sel sel, int n, int *block_cnt)
-{
-    __shared__ int s_c[4];
-    sel.begin();
-    int c = 0;
-    for (int i = blockIdx.x * COMPACT_CHUNK + threadIdx.x; i < min(n, (blockIdx.x + 1) * COMPACT_CHUNK); i += blockDim.x) c += sel.keep(i, sel.load(i));
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-}
-
-/* block counts -> block offsets; the kept total to *total */
-__global__ void __launch_bounds__(1024) k_compact_scan(int *block_cnt, int nblocks, int *total)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    if (threadIdx.x == 0) s_run = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        const int c = i < nblocks ? block_cnt[i] : 0;
-        int tot;
-        const int pre = block_exscan(c, s_scr, &tot);
-        const int run = s_run;
-        if (i < nblocks) block_cnt[i] = run + pre;
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = s_run;
-}
-
-template <class Sel>
-__global__ void __launch_bounds__(256) k_compact_emit(Sel sel, int n, const int *__restrict__ block_off)
-{
-    __shared__ int s_scr[17];
-    __shared__ int s_run;
-    sel.begin();
-    if (threadIdx.x == 0) s_run = block_off[blockIdx.x];
-    __syncthreads();
-    const int i0 = blockIdx.x * COMPACT_CHUNK, i1 = min(n, i0 + COMPACT_CHUNK);
-    for (int base = i0; base < i1; base += blockDim.x) {
-        const int i = base + threadIdx.x;
-        typename Sel::Val v{};
-        int keep = 0;
-        if (i < i1) { v = sel.load(i); keep = sel.keep(i, v); }
-        int tot;
-        const int pre = block_exscan(keep, s_scr, &tot);
-        const int run = s_run;
-        if (keep) sel.emit(i, run + pre, v);
-        __syncthreads();
-        if (threadIdx.x == 0) s_run = run + tot;
-        __syncthreads();
     }
 }
 
@@ -690,22 +625,3 @@ __global__ void __launch_bounds__(256) k_transform_se3(const float *X, const flo
     }
     X2[i] = o[0]; Y2[i] = o[1]; Z2[i] = o[2];
 }
-
-/* ------------------------------------------------------------------ */
-/* Slice-range handles (SURVEY.md 8e case ii): the points of the cloud   */
-/* whose x lies in [lo, hi] -- the interval a handle indexes --, in the  */
-/* cloud's own order (ties on the cloud index break as in the whole      */
-/* cloud), with their cloud indices.  Built once per plan; the hot path  */
-/* then streams the part only.                                           */
-/* ------------------------------------------------------------------ */
-struct PartSel {
-    using Val = float;
-    const float *X, *Y, *Z;
-    float lo, hi;
-    float *X2, *Y2, *Z2;
-    int *idx2;
-    __device__ void begin() {}
-    __device__ float load(int i) const { return X[i]; }
-    __device__ bool keep(int, float x) const { return x >= lo && x <= hi; } /* NaN (a dropped point) fails both */
-    __device__ void emit(int i, int k, float x) const { const float y = Y[i], z = Z[i]; X2[k] = x; Y2[k] = y; Z2[k] = z; idx2[k] = i; }
-};

@@ -1,0 +1,296 @@
+/*
+ * ppp_preproc.hip -- the preprocessing calls of the C ABI (include/ppp_hip.h) on the resident cloud: ppp_trans2center,
+ * ppp_remove_outlier, ppp_voxel_down, ppp_smooth_mls, and what they share (the opening, the adoption of the filtered cloud,
+ * the sensor-frame copy of an aligned cloud).  The unit owns the kernels of ppp_preproc.h and ppp_align.h; of the handle and
+ * the plan it sees what ppp_handle.h declares.  Compiled with the engine's flags.
+ */
+#ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
+#define PPP_KERNELS_FOREIGN /* ppp_kernels.h, ppp_dynamic.h, ppp_compact.h: types and device helpers only -- their kernels are the engine's */
+#endif
+#include "ppp_handle.h"
+#include "ppp_preproc.h"
+#include "ppp_align.h"
+#include "ppp_sort.h"
+#include <cstring>
+
+extern "C" {
+
+namespace {
+
+/* path_translation_alg.cpp:171-174: the cloud carried back by invTransAlign, with its own slab index (same point
+   indices).  The cloud is fixed between runs, so this happens once per cloud change, not per getPath. */
+int rebuild_back(ppp_handle h)
+{
+    if (!h->back) {
+        int rc = ppp_create(h->device, &h->back);
+        if (rc) return fail(h, rc, "sensor-frame handle");
+    }
+    ppp_handle b = h->back;
+    b->P = h->P;
+    b->P.tool_radius = 1.0e6; b->P.dynamic_adjustment = 0; b->P.slice_begin = 0; b->P.slice_end = 0; /* one slice: this handle only ever serves its index */
+    b->n = h->n;
+    memcpy(b->vp, h->vp, sizeof(b->vp));
+    HIPCHK(h, b->X.ensure(h->n)); HIPCHK(h, b->Y.ensure(h->n)); HIPCHK(h, b->Z.ensure(h->n));
+    if (h->n) {
+        Mat34 M;
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) M.m[r][c] = h->invTA[r][c];
+        LAUNCH(h, "k_transform_se3", k_transform_se3, (unsigned)((h->n + 255) / 256), 256, 0, h->X.p, h->Y.p, h->Z.p, (int)h->n, M, b->X.p, b->Y.p, b->Z.p);
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    b->big_path = false;
+    int rc = refresh_bounds_and_plan(b);
+    if (rc == PPP_OK) rc = index_ready(b);
+    if (rc == PPP_OK) { hipError_t e = hipStreamSynchronize(b->stream); if (e != hipSuccess) rc = PPP_ERR_HIP; }
+    if (rc != PPP_OK) return fail(h, rc, std::string("sensor-frame index: ") + b->err);
+    return PPP_OK;
+}
+
+/* the resident cloud was replaced or moved: bounds, plan, and the sensor-frame copy when the cloud is aligned */
+int cloud_changed(ppp_handle h)
+{
+    int rc = refresh_bounds_and_plan(h);
+    if (rc == PPP_OK && h->aligned) rc = rebuild_back(h);
+    return rc;
+}
+
+/* the opening of the preprocessing calls: a whole-cloud handle with a cloud, settled on its device.  bad_arg: the
+   caller's message for an invalid argument, reported between the two checks (ppp_remove_outlier's order) */
+int preproc_begin(ppp_handle h, const char *bad_arg = nullptr)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcs = settle(h); if (rcs) return rcs; }
+    if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
+    if (bad_arg) return fail(h, PPP_ERR_ARG, bad_arg);
+    if (h->ranged || h->part_given) return fail(h, PPP_ERR_ARG, "preprocess the cloud on a whole-cloud handle");
+    return PPP_OK;
+}
+
+/* the filtered cloud of n points replaces the resident one (filter(*cloud)).  The callers free their scratch first: hipFree
+   waits for the device, and behind this call it would wait for the launches of the new plan. */
+int adopt_cloud(ppp_handle h, DevBuf<float> &X2, DevBuf<float> &Y2, DevBuf<float> &Z2, size_t n)
+{
+    h->X = std::move(X2); h->Y = std::move(Y2); h->Z = std::move(Z2);
+    h->n = n;
+    h->drop_graph();
+    return cloud_changed(h);
+}
+
+} // namespace
+
+int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float *covariance9)
+{
+    int rc = preproc_begin(h);
+    if (rc) return rc;
+    if (h->aligned) return fail(h, PPP_ERR_ARG, "the cloud is aligned already (TransAlign would be overwritten): set the cloud again");
+    const int n = (int)h->n;
+    if (n == 0 || h->h_nvalid == 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
+    float hs[6] = {0, 0, 0, 0, 0, 0}, c[3] = {0, 0, 0};
+    const int hcnt = h->h_nvalid; /* the finite points, counted with the bounds */
+    const unsigned gb = (unsigned)((n + 255) / 256);
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        const size_t stride = ((size_t)n + 3) & ~(size_t)3;
+        DevBuf<float> V, sums;
+        hipError_t e = V.ensure(6 * stride);
+        if (e == hipSuccess) e = sums.ensure(8);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("trans2center buffers: ") + hipGetErrorString(e));
+        /* pcl::compute3DCentroid: three running float sums, / float(count) */
+        LAUNCH(h, "k_seq_prep_centroid", k_seq_prep_centroid, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, stride, V.p);
+        LAUNCH(h, "k_seq_sum", k_seq_sum, 3, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
+        HIPCHK(h, hipMemcpyAsync(hs, sums.p, 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (hcnt <= 0) return fail(h, PPP_ERR_ARG, "no finite point to align");
+        for (int d = 0; d < 3; ++d) c[d] = hs[d] / static_cast<float>(hcnt);
+        /* pcl::computeCovarianceMatrix: six running float sums of float products */
+        LAUNCH(h, "k_seq_prep_cov", k_seq_prep_cov, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, c[0], c[1], c[2], stride, V.p);
+        LAUNCH(h, "k_seq_sum", k_seq_sum, 6, 64 * SEQ_WAVES, 0, V.p, stride, n, sums.p);
+        HIPCHK(h, hipMemcpyAsync(hs, sums.p, 6 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    float cov[3][3];
+    cov[1][1] = hs[0]; cov[1][2] = hs[1]; cov[2][2] = hs[2]; cov[0][0] = hs[3]; cov[0][1] = hs[4]; cov[0][2] = hs[5];
+    cov[1][0] = cov[0][1]; cov[2][0] = cov[0][2]; cov[2][1] = cov[1][2];
+    if (centroid3) memcpy(centroid3, c, sizeof(c));
+    if (covariance9) for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) covariance9[3 * i + j] = cov[i][j];
+    ppp_align::EigenSolver3f es;
+    es.compute(cov);
+    if (es.complex_pair || !es.converged)
+        return fail(h, PPP_ERR_DOMAIN, "trans2center: the float Schur form of the covariance keeps a complex pair (two equal extents) or did not converge");
+    ppp_align::trans_align(es, c, h->TA);
+    ppp_align::inverse4(h->TA, h->invTA);
+    if (trans_align16) for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) trans_align16[4 * i + j] = h->TA[i][j];
+    /* pcl::transformPointCloud(*cloud, *cloud, TransAlign) */
+    Mat34 M;
+    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 4; ++cc) M.m[r][cc] = h->TA[r][cc];
+    LAUNCH(h, "k_transform_se3", k_transform_se3, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->aligned = true;
+    h->drop_graph();
+    return cloud_changed(h);
+}
+
+int ppp_remove_outlier(ppp_handle h, int mean_k, double stddev_mul, size_t *n_kept, double *threshold)
+{
+    int rc = preproc_begin(h, (mean_k < 1 || mean_k > 63) ? "mean_k must be in [1, 63]" : nullptr);
+    if (rc) return rc;
+    rc = index_ready(h);
+    if (rc) return rc;
+    const int n = (int)h->n, ns = h->hmeta.n_sorted;
+    if (ns < mean_k + 1) return fail(h, PPP_ERR_ARG, "fewer finite points than mean_k + 1 (PCL reads past its neighbour vectors here)");
+    /* first radius of the k-NN gather: mean_k + 1 points of a sheet of the cloud's mean areal density, +25 % */
+    const double area = ((double)h->h_mx[0] - h->h_mn[0]) * ((double)h->h_mx[1] - h->h_mn[1]);
+    const double rho = (area > 0 && h->h_nvalid > 0) ? (double)h->h_nvalid / area : 1.0;
+    const float r0 = (float)std::max(0.5, 1.25 * std::sqrt((double)(mean_k + 1) / (3.14159265358979 * rho)));
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK, nparts = std::max(1, std::min(1024, (n + 255) / 256));
+    DevBuf<float> X2, Y2, Z2;
+    SorStats hst;
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<float> dist;
+        DevBuf<double> part;
+        DevBuf<int> bcnt;
+        DevBuf<SorStats> st;
+        hipError_t e = dist.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e == hipSuccess) e = part.ensure(2 * (size_t)nparts);
+        if (e == hipSuccess) e = bcnt.ensure(nblocks);
+        if (e == hipSuccess) e = st.ensure(1);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        HIPCHK(h, hipMemsetAsync(dist.p, 0, sizeof(float) * (size_t)n, h->stream)); /* non-finite points: distance 0 */
+        LAUNCH(h, "k_sor_dist", k_sor_dist, (unsigned)((ns + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, h->meta.p, h->sorted4.p, h->slab_start.p,
+               h->slab_xmin.p, h->slab_xmax.p, mean_k, r0, dist.p);
+        LAUNCH(h, "k_sor_partial", k_sor_partial, nparts, 256, 0, dist.p, n, part.p);
+        LAUNCH(h, "k_sor_threshold", k_sor_threshold, 1, 256, 0, h->meta.p, part.p, nparts, stddev_mul, st.p);
+        SorSel sel{dist.p, st.p, h->X.p, h->Y.p, h->Z.p, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, &st.p->n_kept);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&hst, st.p, sizeof(SorStats), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->pass.meta_will_arrive(MetaAt::on_demand());
+    rc = fetch_meta(h);
+    if (rc == PPP_OK) rc = map_dev_err(h);
+    if (rc) return rc;
+    if (n_kept) *n_kept = (size_t)hst.n_kept;
+    if (threshold) *threshold = hst.threshold;
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)hst.n_kept);
+}
+
+int ppp_voxel_down(ppp_handle h, float lx, float ly, float lz, size_t *n_out, int *overflow)
+{
+    int rc = preproc_begin(h);
+    if (rc) return rc;
+    if (!(lx > 0.f) || !(ly > 0.f) || !(lz > 0.f) || !std::isfinite(lx) || !std::isfinite(ly) || !std::isfinite(lz))
+        return fail(h, PPP_ERR_ARG, "leaf sizes must be positive and finite");
+    if (overflow) *overflow = 0;
+    if (n_out) *n_out = h->n;
+    const int n = (int)h->n;
+    if (n == 0) return PPP_OK;
+    /* voxel_grid.hpp applyFilter: inverse_leaf_size_ = 1 / leaf_size_ (float), the index-overflow test on the float extents,
+       min_b_ / max_b_ / div_b_ / divb_mul_ */
+    const float inv[3] = {1.0f / lx, 1.0f / ly, 1.0f / lz};
+    VoxGrid g;
+    long long cells = 1, dxyz = 1;
+    int div_b[3];
+    if (h->h_nvalid > 0) {
+        for (int d = 0; d < 3; ++d) {
+            dxyz *= (long long)((h->h_mx[d] - h->h_mn[d]) * inv[d]) + 1;
+            const int min_b = (int)std::floor(h->h_mn[d] * inv[d]), max_b = (int)std::floor(h->h_mx[d] * inv[d]);
+            div_b[d] = max_b - min_b + 1;
+            cells *= div_b[d];
+            g.inv[d] = inv[d];
+            g.min_b[d] = (float)min_b;
+            if (dxyz > 0x7fffffffLL || cells > 0x7fffffffLL || dxyz <= 0 || cells <= 0) {
+                /* "Leaf size is too small for the input dataset. Integer indices would overflow.": output = input */
+                if (overflow) *overflow = 1;
+                return PPP_OK;
+            }
+        }
+        g.mul[0] = 1; g.mul[1] = div_b[0]; g.mul[2] = div_b[0] * div_b[1];
+    } else {
+        for (int d = 0; d < 3; ++d) { g.inv[d] = inv[d]; g.min_b[d] = 0.f; g.mul[d] = 0; }
+    }
+    g.none = (unsigned)cells;
+    int end_bit = 1;
+    while (end_bit < 32 && (cells >> end_bit)) ++end_bit;
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+    DevBuf<float> X2, Y2, Z2;
+    int n_vox = 0;
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<unsigned> key, key2;
+        DevBuf<int> idx, idx2, bcnt;
+        DevBuf<char> tmp;
+        DevBuf<float4> pts;
+        size_t tmp_bytes = 0;
+        hipError_t e = ppp_sort_pairs_u32(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)n, end_bit, h->stream);
+        if (e == hipSuccess) e = key.ensure(n);
+        if (e == hipSuccess) e = key2.ensure(n);
+        if (e == hipSuccess) e = idx.ensure(n);
+        if (e == hipSuccess) e = idx2.ensure(n);
+        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
+        if (e == hipSuccess) e = tmp.ensure(tmp_bytes);
+        if (e == hipSuccess) e = pts.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("voxel_down buffers: ") + hipGetErrorString(e));
+        const unsigned gb = (unsigned)((n + 255) / 256);
+        LAUNCH(h, "k_vox_key", k_vox_key, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, g, key.p, idx.p);
+        HIPCHK(h, ppp_sort_pairs_u32(tmp.p, &tmp_bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, end_bit, h->stream));
+        LAUNCH(h, "k_vox_gather", k_vox_gather, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, idx2.p, n, pts.p);
+        VoxHeadSel sel{key2.p, pts.p, n, g.none, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&n_vox, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (n_out) *n_out = (size_t)n_vox;
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_vox);
+}
+
+int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
+{
+    int rc = preproc_begin(h);
+    if (rc) return rc;
+    if (!(search_radius > 0) || !std::isfinite(search_radius)) return fail(h, PPP_ERR_ARG, "search radius must be positive"); /* mls.hpp: "Invalid search radius" */
+    if (order < 0 || order > 3) return fail(h, PPP_ERR_ARG, "polynomial order must be in [0, 3]");
+    rc = index_ready(h);
+    if (rc) return rc;
+    const int n = (int)h->n, ns = h->hmeta.n_sorted;
+    if (n_out) *n_out = h->n;
+    if (n == 0) return PPP_OK;
+    const int nblocks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+    DevBuf<float> X2, Y2, Z2;
+    int n_kept = 0;
+    { /* scratch, freed before the re-plan (adopt_cloud) */
+        DevBuf<float4> rec;
+        DevBuf<int> bcnt;
+        hipError_t e = rec.ensure(n);
+        if (e == hipSuccess) e = X2.ensure(n);
+        if (e == hipSuccess) e = Y2.ensure(n);
+        if (e == hipSuccess) e = Z2.ensure(n);
+        if (e == hipSuccess) e = bcnt.ensure((size_t)nblocks + 1); /* block counts, then the total */
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("smooth buffers: ") + hipGetErrorString(e));
+        HIPCHK(h, hipMemsetAsync(rec.p, 0, sizeof(float4) * (size_t)n, h->stream));
+        const unsigned gb = (unsigned)((std::max(ns, 1) + 255) / 256);
+        const float rf = (float)search_radius;
+        const double sq = search_radius * search_radius;
+        if (order == 3) LAUNCH(h, "k_mls<3>", k_mls<3>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
+        else if (order == 2) LAUNCH(h, "k_mls<2>", k_mls<2>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
+        else LAUNCH(h, "k_mls<1>", k_mls<1>, gb, 256, 0, h->meta.p, h->sorted4.p, h->slab_start.p, h->slab_xmin.p, h->slab_xmax.p, rf, sq, rec.p);
+        MlsKeptSel sel{rec.p, X2.p, Y2.p, Z2.p};
+        rc = compact(h, sel, n, bcnt.p, bcnt.p + nblocks);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&n_kept, bcnt.p + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->pass.meta_will_arrive(MetaAt::on_demand());
+    rc = fetch_meta(h);
+    if (rc == PPP_OK) rc = map_dev_err(h);
+    if (rc) return rc;
+    if (n_out) *n_out = (size_t)n_kept;
+    return adopt_cloud(h, X2, Y2, Z2, (size_t)n_kept);
+}
+
+} // extern "C"

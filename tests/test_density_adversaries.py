@@ -113,7 +113,7 @@ def patch_cloud():
 
 
 def first_radius(P, k):
-    """dyn_params' r0 (ppp_engine.hip:601): k points of a sheet of the mean density over the xy bounding box, + 25 %"""
+    """dyn_params' r0 (dyn_params in ppp_engine.hip): k points of a sheet of the mean density over the xy bounding box, + 25 %"""
     mn, mx = P.min(axis=0).astype(np.float64), P.max(axis=0).astype(np.float64)
     rho = len(P) / ((mx[0] - mn[0]) * (mx[1] - mn[1]))
     return np.float32(max(0.5, 1.25 * np.sqrt(k / (np.pi * rho))))
