@@ -71,6 +71,9 @@ public:
     void get_path_coverage() { planner.print_path_coverage(); }
     /* how evenly those paths cover: the largest and mean contact count, the points two or more slices touch (ppp_get_path_contacts) */
     void get_path_contacts() { planner.print_path_contacts(); }
+    /* how much the planned paths take off and how evenly: touched points, path length, mean / min / max removal and cv with the
+       Hertzian profile (ppp_get_path_removal) */
+    void get_path_removal() { planner.print_path_removal(); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }

@@ -287,6 +287,34 @@ typedef struct {
 } ppp_contact_stats;
 int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap,
                           ppp_contact_stats *stats);
+/* Predicted material removal of the last pass's paths: the balls of ppp_get_path_contacts -- the same
+   slices, samples and float test dist2 <= r2 -- each weighted instead of counted.  A sample stands for the path length
+   ds = half the segment to the sample before it plus half the one to the sample after it on its slice (double, from the float
+   sample positions; an end sample has one segment, a lone sample none; a segment with a non-finite end is 0), and a held point
+   at squared distance d2 inside a ball of squared radius r2 weighs, with u = (double)d2 / (double)r2 (0 when r2 == 0):
+     PPP_REMOVAL_FLAT       w = 1            (dwell alone)
+     PPP_REMOVAL_PARABOLIC  w = 1 - u
+     PPP_REMOVAL_HERTZ      w = sqrt(1 - u)  (the Hertzian pressure profile of a sphere on a surface)
+   removal[i] = the sum of w * ds over the balls that hold cloud point i, one double accumulator adding in ascending (slice,
+   sample) order: the same bits in every run; 0 for a point no ball holds.  The unit is millimetres of weighted tool travel:
+   Preston's constant, the peak pressure, the surface speed and the feed are the caller's factor.  min(cap, n) entries are
+   copied; removal may be NULL, stats may be NULL, cap = 0 asks for the statistics alone.  stats: n = cloud->size(), touched =
+   points held by at least one ball (ppp_get_path_contacts's covered, whatever the weights), min_removal / max_removal over
+   the touched points (NaN when there are none), sum / sum_sq over the touched points by a fixed-order reduction (the same in
+   every run), path_length = the sum of every ds of the handle's slices in (slice, sample) order, hist[b] = touched points
+   with min(63, floor(removal / max_removal * 63)) == b (all in bin 0 when max_removal == 0).  A slice-range handle sums the
+   balls of its own slices by whole-cloud point index: over ranges that tile the walk the maps and the path lengths add up to
+   the whole cloud's to within rounding (the association differs, so not bit for bit).  Kept per (pass, profile): a repeated
+   call launches nothing.  Builds, reuses and refuses as ppp_get_path_contacts does, with the same codes, shares that call's
+   sample table where the handle holds one for the pass, and leaves the results of the other contact calls alone;
+   PPP_ERR_ARG for an unknown profile. */
+enum { PPP_REMOVAL_FLAT = 0, PPP_REMOVAL_PARABOLIC = 1, PPP_REMOVAL_HERTZ = 2 };
+typedef struct {
+    size_t n, touched;
+    double min_removal, max_removal, sum, sum_sq, path_length;
+    size_t hist[PPP_CONTACT_BINS];
+} ppp_removal_stats;
+int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap, ppp_removal_stats *stats);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

@@ -321,6 +321,32 @@ public:
         std::printf("contacts: max %u, mean %f over %zu covered points\n", st.max_count, mean, st.covered);
         std::printf("overlap: %zu points touched by two or more slices (%f of the cloud)\n", st.multi_slice, share);
     }
+    /* predicted material removal of the last pass's paths (ppp_get_path_removal: the balls of path_contacts(), each weighted by the
+       path length its sample stands for and by the profile's pressure at the point, in millimetres of weighted tool travel): the
+       statistics and, when asked for, the map by cloud index */
+    bool path_removal(ppp_removal_stats &st, int profile = PPP_REMOVAL_HERTZ, std::vector<double> *removal = nullptr)
+    {
+        int rc = ppp_get_path_removal(h_, profile, nullptr, 0, &st);
+        if (rc == PPP_OK && removal) {
+            removal->assign(st.n, 0.0);
+            rc = ppp_get_path_removal(h_, profile, removal->data(), st.n, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* two lines on path_removal() with the Hertzian profile: the touched points and the length of the path their balls were
+       sampled on, then the mean, the smallest and the largest removal over the touched points and cv = the standard deviation /
+       the mean, the one figure of how evenly the paths polish */
+    void print_path_removal()
+    {
+        ppp_removal_stats st = {};
+        if (!path_removal(st)) st = ppp_removal_stats{};
+        const double mean = st.touched ? st.sum / (double)st.touched : 0.0;
+        const double var = st.touched ? std::max(0.0, st.sum_sq / (double)st.touched - mean * mean) : 0.0;
+        const double cv = mean > 0.0 ? std::sqrt(var) / mean : 0.0;
+        std::printf("removal: %zu touched points, path length %f mm\n", st.touched, st.path_length);
+        std::printf("removal: mean %f, min %f, max %f, cv %f (mm of Hertz-weighted tool travel)\n", mean, st.touched ? st.min_removal : 0.0,
+                    st.touched ? st.max_removal : 0.0, cv);
+    }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
        ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below
        min_width -- and, when asked for, the maps by cloud index (curv5: n x 5) */

@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h and ppp_regions.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h and ppp_removal.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -10,6 +10,7 @@
 #include "ppp_handle.h"
 #include "ppp_contact.h"
 #include "ppp_regions.h"
+#include "ppp_removal.h"
 #include <cstring>
 
 extern "C" {
@@ -143,6 +144,42 @@ int ppp_get_path_coverage(ppp_handle h, unsigned char *flags, size_t cap, size_t
     return flag_coverage(h, h->pcov, "path coverage", balls, flags, cap, n, covered);
 }
 
+/* The per-slice sample table of the last pass in h->pcon (off, tab, reach; k_pcon_offsets, k_pcon_samples), which the path
+   contacts and the path removal both read: built on the first question about the pass, with what the pass left out
+   (contact_prerequisites).  err: the device word the two kernels OR their refusals into, zeroed by the caller; the caller reads
+   it back with its own results and only then calls pcon_table_accept, so a refused table is never reused. */
+static int pcon_sample_table(ppp_handle h, const char *what, int *err)
+{
+    auto &C = h->pcon;
+    if (C.tab_serial == h->pass.serial()) return PPP_OK;
+    const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
+    int rc = contact_prerequisites(h);
+    if (rc) return rc;
+    C.tab_sb = sb; C.tab_nsl = nsl; C.tab_rows = 0;
+    if (nsl <= 0) return PPP_OK;
+    HIPCHK(h, C.off.ensure((size_t)nsl + 2));
+    LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), knot_table(h), sb, nsl, C.off.p, err);
+    std::vector<int> off((size_t)nsl + 2);
+    HIPCHK(h, copy_sync(h, off.data(), C.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+    rc = contact_refusal(h, what, (unsigned)off[nsl + 1]);
+    if (rc) return rc;
+    const int rows = off[nsl];
+    int most = 0;
+    for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
+    if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, std::string(what) + ": sample table corrupt");
+    if (rows > 0) {
+        HIPCHK(h, C.tab.ensure((size_t)rows)); HIPCHK(h, C.reach.ensure(3 * (size_t)nsl));
+        HIPCHK(h, hipMemsetAsync(C.reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
+        const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
+        for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
+            LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0, contact_index(h),
+                   dyn_params(h), knot_table(h), C.off.p, sb, s0, pcov_range(h), C.tab.p, C.reach.p, err);
+    }
+    C.tab_rows = rows;
+    return PPP_OK;
+}
+static void pcon_table_accept(ppp_handle h) { h->pcon.tab_serial = h->pass.serial(); }
+
 int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, int *last_slice, size_t cap, ppp_contact_stats *stats)
 {
     int rc = contact_query_begin(h, "path contacts");
@@ -150,9 +187,6 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
     const size_t N = h->n;
     auto &C = h->pcon;
     if (C.serial != h->pass.serial()) { /* first question about this pass */
-        const int S = h->hmeta.S, sb = std::min(h->sb, S), se = std::min(h->se, S), nsl = std::max(se - sb, 0);
-        rc = contact_prerequisites(h);
-        if (rc) return rc;
         const size_t N1 = std::max<size_t>(N, 1);
         HIPCHK(h, C.counts.ensure(N1)); HIPCHK(h, C.first.ensure(N1)); HIPCHK(h, C.last.ensure(N1));
         HIPCHK(h, C.acc.ensure(70));
@@ -161,29 +195,11 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
         HIPCHK(h, hipMemsetAsync(C.last.p, 0xff, N1 * sizeof(int), h->stream));
         HIPCHK(h, hipMemsetAsync(C.acc.p, 0, 70 * sizeof(unsigned long long), h->stream));
         int *err = (int *)(C.acc.p + 69);
-        if (nsl > 0) {
-            HIPCHK(h, C.off.ensure((size_t)nsl + 2));
-            LAUNCH(h, "k_pcon_offsets", k_pcon_offsets, 1, PCON_T, 0, dyn_params(h), knot_table(h), sb, nsl, C.off.p, err);
-            std::vector<int> off((size_t)nsl + 2);
-            HIPCHK(h, copy_sync(h, off.data(), C.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
-            rc = contact_refusal(h, "path contacts", (unsigned)off[nsl + 1]);
-            if (rc) return rc;
-            const int rows = off[nsl];
-            int most = 0;
-            for (int i = 0; i < nsl; ++i) most = std::max(most, off[i + 1] - off[i]);
-            if (rows < 0 || most < 0) return fail(h, PPP_ERR_HIP, "path contacts: sample table corrupt");
-            if (rows > 0) {
-                HIPCHK(h, C.tab.ensure((size_t)rows)); HIPCHK(h, C.reach.ensure(3 * (size_t)nsl));
-                HIPCHK(h, hipMemsetAsync(C.reach.p, 0, 3 * (size_t)nsl * sizeof(unsigned), h->stream));
-                const int gx = std::min((most + DYN_WAVES - 1) / DYN_WAVES, 16384);
-                for (int s0 = 0; s0 < nsl; s0 += 65535) /* (gridDim.y) */
-                    LAUNCH(h, "k_pcon_samples", k_pcon_samples, dim3(gx, std::min(nsl - s0, 65535)), 64 * DYN_WAVES, 0, contact_index(h),
-                           dyn_params(h), knot_table(h), C.off.p, sb, s0, pcov_range(h), C.tab.p, C.reach.p, err);
-                /* one thread per indexed point (at most N of them), PCON_T a round */
-                LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
-                       h->meta.p, h->sorted4.p, C.tab.p, C.off.p, C.reach.p, sb, nsl, C.counts.p, C.first.p, C.last.p);
-            }
-        }
+        rc = pcon_sample_table(h, "path contacts", err);
+        if (rc) return rc;
+        if (C.tab_rows > 0) /* one thread per indexed point (at most N of them), PCON_T a round */
+            LAUNCH(h, "k_pcon_points", k_pcon_points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0,
+                   h->meta.p, h->sorted4.p, C.tab.p, C.off.p, C.reach.p, C.tab_sb, C.tab_nsl, C.counts.p, C.first.p, C.last.p);
         LAUNCH(h, "k_pcon_stats", k_pcon_stats, (unsigned)std::min<size_t>((N1 + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus), PCON_T, 0,
                C.counts.p, C.first.p, C.last.p, (int)N, err, C.acc.p);
         unsigned long long acc[69];
@@ -191,6 +207,7 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
         rc = contact_refusal(h, "path contacts", acc[68]);
         if (rc) return rc;
         if (acc[64] > N || acc[65] > acc[64]) return fail(h, PPP_ERR_HIP, "path contacts: statistics corrupt");
+        pcon_table_accept(h);
         ppp_contact_stats st = {};
         st.n = N; st.covered = (size_t)acc[64]; st.multi_slice = (size_t)acc[65];
         st.total = acc[66]; st.max_count = (unsigned)acc[67];
@@ -204,6 +221,77 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
     if (counts && k) HIPCHK(h, copy_sync(h, counts, C.counts.p, k * sizeof(unsigned), hipMemcpyDeviceToHost));
     if (first_slice && k) HIPCHK(h, copy_sync(h, first_slice, C.first.p, k * sizeof(int), hipMemcpyDeviceToHost));
     if (last_slice && k) HIPCHK(h, copy_sync(h, last_slice, C.last.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The predicted removal: the sample table of the path contacts (shared with that call when the handle holds
+   one for the pass), the path length of every sample (k_prem_ds, once per pass), the point walk with the profile's weight
+   (k_prem_points) and the statistics in two phases (k_prem_range, k_prem_stats); kept per (pass, profile). */
+int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap, ppp_removal_stats *stats)
+{
+    int rc = contact_query_begin(h, "path removal");
+    if (rc) return rc;
+    if (profile != PPP_REMOVAL_FLAT && profile != PPP_REMOVAL_PARABOLIC && profile != PPP_REMOVAL_HERTZ)
+        return fail(h, PPP_ERR_ARG, "path removal: unknown profile (PPP_REMOVAL_FLAT, _PARABOLIC or _HERTZ)");
+    const size_t N = h->n;
+    auto &R = h->prem;
+    auto &M = R.slot[profile];
+    const auto &T = h->pcon;
+    if (M.serial != h->pass.serial()) { /* first question about this pass with this profile */
+        const size_t N1 = std::max<size_t>(N, 1);
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
+        const int per = (int)((N + grid - 1) / grid);
+        HIPCHK(h, M.map.ensure(N1)); HIPCHK(h, R.held.ensure(N1));
+        HIPCHK(h, R.acc.ensure(PREM_ACC_WORDS)); HIPCHK(h, R.psum.ensure(2 * (size_t)grid));
+        HIPCHK(h, hipMemsetAsync(M.map.p, 0, N1 * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(R.held.p, 0, N1, h->stream));
+        HIPCHK(h, hipMemsetAsync(R.acc.p, 0, PREM_ACC_WORDS * sizeof(unsigned long long), h->stream));
+        rc = pcon_sample_table(h, "path removal", (int *)(R.acc.p + PREM_ACC_ERR));
+        if (rc) return rc;
+        const bool new_ds = R.ds_serial != h->pass.serial();
+        if (T.tab_rows > 0) {
+            if (new_ds) {
+                HIPCHK(h, R.ds.ensure((size_t)T.tab_rows)); HIPCHK(h, R.slice_len.ensure((size_t)T.tab_nsl));
+                LAUNCH(h, "k_prem_ds", k_prem_ds, (unsigned)T.tab_nsl, PCON_T, 0, T.tab.p, T.off.p, R.ds.p, R.slice_len.p);
+            }
+            auto points = profile == PPP_REMOVAL_FLAT ? k_prem_points<PPP_REMOVAL_FLAT>
+                        : profile == PPP_REMOVAL_PARABOLIC ? k_prem_points<PPP_REMOVAL_PARABOLIC> : k_prem_points<PPP_REMOVAL_HERTZ>;
+            LAUNCH(h, "k_prem_points", points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0, h->meta.p,
+                   h->sorted4.p, T.tab.p, R.ds.p, T.off.p, T.reach.p, T.tab_nsl, M.map.p, R.held.p);
+        }
+        LAUNCH(h, "k_prem_range", k_prem_range, (unsigned)grid, PCON_T, 0, M.map.p, R.held.p, (int)N, R.acc.p);
+        LAUNCH(h, "k_prem_stats", k_prem_stats, (unsigned)grid, PCON_T, 0, M.map.p, R.held.p, (int)N, per, R.acc.p, R.acc.p + PREM_ACC_BINS,
+               R.psum.p, R.psum.p + grid);
+        unsigned long long acc[PREM_ACC_WORDS];
+        std::vector<double> psum(2 * (size_t)grid), len;
+        HIPCHK(h, copy_sync(h, acc, R.acc.p, sizeof(acc), hipMemcpyDeviceToHost));
+        rc = contact_refusal(h, "path removal", (unsigned)acc[PREM_ACC_ERR]);
+        if (rc) return rc;
+        if (acc[0] > N) return fail(h, PPP_ERR_HIP, "path removal: statistics corrupt");
+        pcon_table_accept(h);
+        HIPCHK(h, copy_sync(h, psum.data(), R.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (new_ds) { /* the slices' lengths in slice order */
+            R.path_length = 0.0;
+            if (T.tab_rows > 0) {
+                len.resize((size_t)T.tab_nsl);
+                HIPCHK(h, copy_sync(h, len.data(), R.slice_len.p, len.size() * sizeof(double), hipMemcpyDeviceToHost));
+                for (double v : len) R.path_length += v;
+            }
+            R.ds_serial = h->pass.serial();
+        }
+        ppp_removal_stats st = {};
+        st.n = N; st.touched = (size_t)acc[0];
+        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
+        st.max_removal = st.touched ? as_double(acc[1]) : (double)NAN; st.min_removal = st.touched ? as_double(~acc[2]) : (double)NAN;
+        for (int g = 0; g < grid; ++g) { st.sum += psum[(size_t)g]; st.sum_sq += psum[(size_t)grid + g]; }
+        st.path_length = R.path_length;
+        for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[PREM_ACC_BINS + b];
+        M.stats = st;
+        M.serial = h->pass.serial();
+    }
+    if (stats) *stats = M.stats;
+    const size_t k = std::min(cap, N);
+    if (removal && k) HIPCHK(h, copy_sync(h, removal, M.map.p, k * sizeof(double), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

@@ -221,7 +221,22 @@ struct ppp_handle_s {
         DevBuf<unsigned long long> acc;
         unsigned long long serial = ~0ull;
         ppp_contact_stats stats = {};
+        /* the sample table alone (off, tab, reach), which ppp_get_path_removal shares: the pass it belongs to -- set once a
+           caller has read the sample kernels' refusal word back clean -- the first slice, the slices and the rows it holds */
+        unsigned long long tab_serial = ~0ull;
+        int tab_sb = 0, tab_nsl = 0, tab_rows = 0;
     } pcon;
+    /* predicted removal of the last pass (ppp_get_path_removal): per table row the path length its sample stands for and per
+       slice their sum (ds_serial: the pass), the held flags by cloud index (the same for every profile, written by each map's
+       launch), the statistics' accumulators, and per profile the map by cloud index with its statistics */
+    struct PathRemoval {
+        DevBuf<double> ds, slice_len, psum;
+        DevBuf<unsigned char> held;
+        DevBuf<unsigned long long> acc;
+        unsigned long long ds_serial = ~0ull;
+        double path_length = 0.0;
+        struct Slot { DevBuf<double> map; unsigned long long serial = ~0ull; ppp_removal_stats stats = {}; } slot[3];
+    } prem;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {

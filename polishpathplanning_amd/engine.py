@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -160,6 +160,7 @@ def lib():
         L.ppp_get_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_contacts.argtypes = [vp, C.POINTER(C.c_uint), ip, ip, sz, C.POINTER(ContactStats)]
+        L.ppp_get_path_removal.argtypes = [vp, C.c_int, C.POINTER(C.c_double), sz, C.POINTER(RemovalStats)]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -294,6 +295,15 @@ class ContactStats(C.Structure):
     """ppp_contact_stats"""
     _fields_ = [("n", C.c_size_t), ("covered", C.c_size_t), ("multi_slice", C.c_size_t), ("max_count", C.c_uint),
                 ("total", C.c_ulonglong), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+REMOVAL_FLAT, REMOVAL_PARABOLIC, REMOVAL_HERTZ = range(3)  # PPP_REMOVAL_*
+
+
+class RemovalStats(C.Structure):
+    """ppp_removal_stats"""
+    _fields_ = [("n", C.c_size_t), ("touched", C.c_size_t), ("min_removal", C.c_double), ("max_removal", C.c_double),
+                ("sum", C.c_double), ("sum_sq", C.c_double), ("path_length", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
 
 
 class ContactFieldStats(C.Structure):
@@ -828,6 +838,27 @@ class Engine:
         stats = dict(n=st.n, covered=st.covered, multi_slice=st.multi_slice, max_count=st.max_count, total=st.total,
                      hist=np.array(st.hist[:], np.int64))
         return counts, first, last, stats
+
+    def path_removal(self, profile=REMOVAL_HERTZ, maps=True):
+        """(removal float64[n], stats dict) of the last pass's final paths: the balls of path_contacts(), each weighted by the
+        path length its sample stands for and by the point's place inside it -- REMOVAL_FLAT 1, REMOVAL_PARABOLIC 1 - u,
+        REMOVAL_HERTZ sqrt(1 - u) with u = d2 / r2 -- in millimetres of weighted tool travel (ppp_get_path_removal).  stats: n,
+        touched, min_removal, max_removal, sum, sum_sq, path_length, hist (CONTACT_BINS counts of removal / max_removal), and
+        mean = sum / touched, cv = the standard deviation over the touched points / mean (NaN when nothing is touched).
+        maps=False returns (None, stats)"""
+        st = RemovalStats()
+        self._chk(self.L.ppp_get_path_removal(self.h, int(profile), None, 0, C.byref(st)))
+        n = st.n
+        removal = None
+        if maps:
+            removal = np.zeros(max(n, 1), np.float64)
+            self._chk(self.L.ppp_get_path_removal(self.h, int(profile), removal.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(st)))
+            removal = removal[:n]
+        mean = st.sum / st.touched if st.touched else float("nan")
+        cv = float(np.sqrt(max(0.0, st.sum_sq / st.touched - mean * mean))) / mean if st.touched and mean > 0 else float("nan")
+        stats = dict(n=st.n, touched=st.touched, min_removal=st.min_removal, max_removal=st.max_removal, sum=st.sum, sum_sq=st.sum_sq,
+                     path_length=st.path_length, hist=np.array(st.hist[:], np.int64), mean=mean, cv=cv)
+        return removal, stats
 
     def contact_field(self, maps=True, min_width=0.0):
         """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every
