@@ -3,7 +3,8 @@
 // PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths (get_coverage's two lines, path_dynamic_alg.cpp:155-160
 // keeps them commented out); PPP_PATH_CONTACTS=1 prints how evenly they cover (the largest and mean contact count, the points
 // two or more slices touch); PPP_PATH_REMOVAL=1 prints how much they take off and how evenly (touched points, path length, mean /
-// min / max removal and cv with the Hertzian profile); PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
+// min / max removal and cv with the Hertzian profile); PPP_PATH_DWELL=1 prints what a feed schedule could do about it (the dwell
+// factors' range, the residual before and after, the time factor); PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
 // regions, PPP_GAPS_MIN points or more each).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +33,8 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
+    const char *dwl = std::getenv("PPP_PATH_DWELL");
+    if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fld = std::getenv("PPP_CONTACT_FIELD");
     if (fld && fld[0] == '1') path_planner.get_contact_field();
     const char *gap = std::getenv("PPP_GAPS");

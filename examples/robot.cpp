@@ -1,7 +1,8 @@
 // A caller of the RobotPath drop-in (include/robot_path.h): ./robot cloud.pcd [radius].  The reference declares the class
 // (robot_path.h:58-98) but nothing constructs it -- the header does not compile upstream -- so this is the shape of
 // src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths,
-// PPP_PATH_CONTACTS=1 their contact counts, PPP_PATH_REMOVAL=1 the predicted removal, PPP_GAPS=1 the regions they leave uncovered.
+// PPP_PATH_CONTACTS=1 their contact counts, PPP_PATH_REMOVAL=1 the predicted removal, PPP_PATH_DWELL=1 a dwell schedule
+// towards a uniform removal, PPP_GAPS=1 the regions they leave uncovered.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -32,6 +33,8 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
+    const char *dwl = std::getenv("PPP_PATH_DWELL");
+    if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fld = std::getenv("PPP_CONTACT_FIELD");
     if (fld && fld[0] == '1') path_planner.get_contact_field();
     const char *gap = std::getenv("PPP_GAPS");

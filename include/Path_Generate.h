@@ -74,6 +74,9 @@ public:
     /* how much the planned paths take off and how evenly: touched points, path length, mean / min / max removal and cv with the
        Hertzian profile (ppp_get_path_removal) */
     void get_path_removal() { planner.print_path_removal(); }
+    /* what a feed schedule could do about it: a dwell factor per sample towards a uniform removal -- the factors' range, the
+       residual before and after, the time factor (ppp_get_path_dwell) */
+    void get_path_dwell() { planner.print_path_dwell(); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }

@@ -315,6 +315,42 @@ typedef struct {
     size_t hist[PPP_CONTACT_BINS];
 } ppp_removal_stats;
 int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap, ppp_removal_stats *stats);
+/* A dwell schedule for the last pass's paths: a factor t_j per row j of the sample table of
+   ppp_get_path_contacts -- how many times longer than planned the tool stays on the stretch ds_j of sample j -- that steers the
+   predicted removal R_i = sum_j a_ij (ds_j t_j) (a_ij: the profile's weight of ppp_get_path_removal for a held pair) towards a
+   target map T.  target: n doubles by cloud index, finite and >= 0 at every touched point, or NULL for "uniform, same total":
+   T_i = L.  L (stats->level) = the mean of T over the touched points by a fixed-order reduction; with a NULL target the mean
+   sum / touched that ppp_get_path_removal reports for the profile.  From t = 1, `iterations` rounds of a multiplicative update:
+     g_i = R_i > 0 ? min(max(T_i / R_i, 2^-6), 2^6) : 1                                   per touched point
+     num_j = sum_i llrint((a_ij g_i) 2^28), den_j = sum_i llrint(a_ij 2^28)               signed 64-bit sums over ball j's points
+     t_j = min(max(t_j ((double)num_j / (double)den_j), dwell_min), dwell_max)            where den_j > 0; else t_j stays
+   with R computed from the rounded products ds_j t_j by the removal's own walk in ascending (slice, sample) order: integer
+   sums have no order, so every output is the same bits in every run.  rows[j] (min(row_cap, stats->rows) of them, in (slice,
+   sample) order): the slice's index in the walk, the sample's float position, r = the float square root of the r2 its ball
+   tests with (NaN: the ball holds nothing, dwell 1), ds, and the final factor.  removal[i] (min(cap, n)): the map the final
+   factors predict, 0 for a point no ball holds.  stats: at_min / at_max, min_dwell / max_dwell over the rows with den_j > 0
+   (NaN when there are none); residual_before / residual_after = sqrt(mean over the touched points of ((R_i - T_i) / L)^2) at
+   t = 1 and at the result (fixed-order sums); path_length = ppp_get_path_removal's; time_factor = (the sum of the rounded
+   ds_j t_j, per slice in sample order, the slices in order) / path_length.  touched == 0 or L == 0: every factor stays 1, the
+   residuals are NaN, PPP_OK.  The feed cannot raise what lies between two slices: the residual falls to the cross-slice
+   ripple of the plan and stays there (7h).  PPP_ERR_ARG: iterations outside [1, 64], bounds that are not finite or not
+   0 < dwell_min <= 1 <= dwell_max, an unknown profile, a bad target entry, no pass yet.  PPP_ERR_UNSUPPORTED: a slice-range
+   handle (neighbouring ranges share the points of their overlap bands: a range cannot solve alone) and a part handle.
+   Otherwise builds, shares and refuses as ppp_get_path_removal does (it asks that call for the unit-feed map first) and
+   leaves every other contact result alone.  With a NULL target the result is kept per (pass, profile, iterations, bounds): a
+   repeated call launches nothing; with a target every call computes again.  Any output may be NULL. */
+typedef struct { int slice; float x, y, z, r; double ds, dwell; } ppp_dwell_row;
+typedef struct {
+    size_t n, touched, rows;        /* cloud->size(); points a ball holds; rows of the sample table */
+    size_t at_min, at_max;          /* rows whose factor ended on a bound */
+    int    iterations;
+    double level;                   /* L, see above */
+    double residual_before, residual_after;   /* sqrt(mean over touched of ((R_i - T_i) / L)^2), at t = 1 and at the result */
+    double min_dwell, max_dwell;    /* over rows with den > 0; NaN when there are none */
+    double path_length, time_factor;/* sum ds_j ; sum ds_j t_j / sum ds_j, both in (slice, sample) order */
+} ppp_dwell_stats;
+int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,
+                       ppp_dwell_row *rows, size_t row_cap, double *removal, size_t cap, ppp_dwell_stats *stats);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

@@ -347,6 +347,38 @@ public:
         std::printf("removal: mean %f, min %f, max %f, cv %f (mm of Hertz-weighted tool travel)\n", mean, st.touched ? st.min_removal : 0.0,
                     st.touched ? st.max_removal : 0.0, cv);
     }
+    /* a dwell schedule for the last pass's paths (ppp_get_path_dwell: a factor per sample of path_contacts()'s table that steers
+       path_removal(profile) towards target -- one value per cloud point, or nullptr for "uniform, same total" -- after
+       `iterations` rounds, the factors kept in [dwell_min, dwell_max]): the statistics and, when asked for, the rows in (slice,
+       sample) order and the map the factors predict.  With a target every call computes again: ask for rows and map at once */
+    bool path_dwell(ppp_dwell_stats &st, int profile = PPP_REMOVAL_HERTZ, const std::vector<double> *target = nullptr, int iterations = 8,
+                    double dwell_min = 0.25, double dwell_max = 4.0, std::vector<ppp_dwell_row> *rows = nullptr,
+                    std::vector<double> *removal = nullptr)
+    {
+        const double *tg = target ? target->data() : nullptr;
+        int rc = ppp_get_path_dwell(h_, profile, tg, iterations, dwell_min, dwell_max, nullptr, 0, nullptr, 0, &st);
+        if (rc == PPP_OK && (rows || removal)) {
+            if (rows) rows->assign(st.rows, ppp_dwell_row{});
+            if (removal) removal->assign(st.n, 0.0);
+            rc = ppp_get_path_dwell(h_, profile, tg, iterations, dwell_min, dwell_max, rows ? rows->data() : nullptr, rows ? st.rows : 0,
+                                    removal ? removal->data() : nullptr, removal ? st.n : 0, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* two lines on path_dwell() with the Hertzian profile, a uniform target and the default rounds and bounds: the rows, the
+       smallest and the largest factor and how many rows ended on a bound, then what the schedule buys -- the rms of (removal -
+       target) / level before and after -- and what it costs: the time along the path against the unit feed */
+    void print_path_dwell()
+    {
+        ppp_dwell_stats st = {};
+        if (!path_dwell(st)) st = ppp_dwell_stats{};
+        const bool any = st.min_dwell == st.min_dwell;
+        std::printf("dwell: %zu samples, factor %f to %f, %zu at the lower and %zu at the upper bound\n", st.rows, any ? st.min_dwell : 1.0,
+                    any ? st.max_dwell : 1.0, st.at_min, st.at_max);
+        std::printf("dwell: residual %f -> %f after %d rounds, time factor %f\n", st.residual_before == st.residual_before ? st.residual_before : 0.0,
+                    st.residual_after == st.residual_after ? st.residual_after : 0.0, st.iterations,
+                    st.time_factor == st.time_factor ? st.time_factor : 1.0);
+    }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
        ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below
        min_width -- and, when asked for, the maps by cloud index (curv5: n x 5) */

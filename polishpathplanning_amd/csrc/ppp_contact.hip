@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, path removal, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h and ppp_removal.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, the dwell schedule, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h and ppp_dwell.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -11,6 +11,7 @@
 #include "ppp_contact.h"
 #include "ppp_regions.h"
 #include "ppp_removal.h"
+#include "ppp_dwell.h"
 #include <cstring>
 
 extern "C" {
@@ -292,6 +293,159 @@ int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap,
     if (stats) *stats = M.stats;
     const size_t k = std::min(cap, N);
     if (removal && k) HIPCHK(h, copy_sync(h, removal, M.map.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The dwell schedule: the unit-feed map, the sample table, ds and the held flags come from
+   ppp_get_path_removal's own call (built if the handle does not hold them, refused as it refuses); then every round's kernels
+   back to back on the stream -- forward (k_dwell_scale + k_prem_points; the first round reads the unit-feed map, which IS the
+   forward pass at t = 1), k_dwell_ratio, k_dwell_back, k_dwell_update -- the last forward pass, the residuals and the factors'
+   statistics, and one wait.  Kept per (pass, profile, iterations, bounds) when there is no target. */
+int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,
+                       ppp_dwell_row *rows, size_t row_cap, double *removal, size_t cap, ppp_dwell_stats *stats)
+{
+    int rc = contact_query_begin(h, "path dwell");
+    if (rc) return rc;
+    if (profile != PPP_REMOVAL_FLAT && profile != PPP_REMOVAL_PARABOLIC && profile != PPP_REMOVAL_HERTZ)
+        return fail(h, PPP_ERR_ARG, "path dwell: unknown profile (PPP_REMOVAL_FLAT, _PARABOLIC or _HERTZ)");
+    if (iterations < 1 || iterations > 64) return fail(h, PPP_ERR_ARG, "path dwell: iterations must lie in [1, 64]");
+    if (!(std::isfinite(dwell_min) && std::isfinite(dwell_max) && dwell_min > 0.0 && dwell_min <= 1.0 && dwell_max >= 1.0))
+        return fail(h, PPP_ERR_ARG, "path dwell: the bounds must be finite with 0 < dwell_min <= 1 <= dwell_max");
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0 || h->ranged || h->use_part)
+        return fail(h, PPP_ERR_UNSUPPORTED, "path dwell: neighbouring slice ranges share the points of their overlap bands: a slice-range handle cannot solve alone");
+    const size_t N = h->n;
+    auto &D = h->dwell;
+    const bool reuse = !target && D.valid && D.serial == h->pass.serial() && D.profile == profile && D.iterations == iterations &&
+                       D.dmin == dwell_min && D.dmax == dwell_max;
+    if (!reuse) {
+        D.valid = false;
+        ppp_removal_stats rs = {};
+        rc = ppp_get_path_removal(h, profile, nullptr, 0, &rs);
+        if (rc) return rc;
+        auto &R = h->prem;
+        const auto &M = R.slot[profile];
+        const auto &T = h->pcon;
+        const int nrow = T.tab_rows, nsl = T.tab_nsl;
+        const size_t N1 = std::max<size_t>(N, 1), R1 = (size_t)std::max(nrow, 1), touched = rs.touched;
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
+        const int per = (int)((N + grid - 1) / grid);
+        const unsigned gn = (unsigned)((N1 + PCON_T - 1) / PCON_T), gr = (unsigned)((R1 + PCON_T - 1) / PCON_T);
+        HIPCHK(h, D.t.ensure(R1)); HIPCHK(h, D.dst.ensure(R1)); HIPCHK(h, D.num.ensure(R1)); HIPCHK(h, D.den.ensure(R1));
+        HIPCHK(h, D.g.ensure(N1)); HIPCHK(h, D.map.ensure(N1)); HIPCHK(h, D.psum.ensure(2 * (size_t)grid));
+        HIPCHK(h, D.acc.ensure(PREM_ACC_WORDS));
+        double level = touched ? rs.sum / (double)touched : (double)NAN;
+        const double *dtarget = nullptr;
+        if (target) {
+            if (touched) { /* the entries the solve reads */
+                std::vector<unsigned char> held(N);
+                HIPCHK(h, copy_sync(h, held.data(), R.held.p, N, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < N; ++i)
+                    if (held[i] && !(target[i] >= 0.0 && std::isfinite(target[i])))
+                        return fail(h, PPP_ERR_ARG, "path dwell: the target must be finite and >= 0 at every touched point");
+            }
+            HIPCHK(h, D.target.ensure(N1));
+            if (N) HIPCHK(h, copy_sync(h, D.target.p, target, N * sizeof(double), hipMemcpyHostToDevice));
+            dtarget = D.target.p;
+            if (touched) { /* L = the mean of T over the touched points, as k_prem_stats adds a map (its bins: all in bin 0, not read) */
+                HIPCHK(h, hipMemsetAsync(D.acc.p, 0, PREM_ACC_WORDS * sizeof(unsigned long long), h->stream));
+                LAUNCH(h, "k_prem_stats", k_prem_stats, (unsigned)grid, PCON_T, 0, D.target.p, R.held.p, (int)N, per, D.acc.p, D.acc.p + PREM_ACC_BINS,
+                       D.psum.p, D.psum.p + grid);
+                std::vector<double> ps((size_t)grid);
+                HIPCHK(h, copy_sync(h, ps.data(), D.psum.p, ps.size() * sizeof(double), hipMemcpyDeviceToHost));
+                double sum = 0.0;
+                for (double v : ps) sum += v;
+                level = sum / (double)touched;
+            }
+        }
+        const bool walk = nrow > 0 && touched > 0, solve = walk && level > 0.0;
+        HIPCHK(h, hipMemsetAsync(D.map.p, 0, N1 * sizeof(double), h->stream));
+        HIPCHK(h, hipMemsetAsync(D.acc.p, 0, 4 * sizeof(unsigned long long), h->stream));
+        std::vector<double> tv((size_t)nrow, 1.0), dsv((size_t)nrow);
+        if (walk) {
+            HIPCHK(h, hipMemsetAsync(D.g.p, 0, N1 * sizeof(double), h->stream));
+            HIPCHK(h, copy_sync(h, D.t.p, tv.data(), tv.size() * sizeof(double), hipMemcpyHostToDevice));
+            const ContactIndex I = contact_index(h);
+            const unsigned gb = (unsigned)((nrow + DYN_WAVES - 1) / DYN_WAVES);
+            auto forward = [&]() -> int { /* D.map = the removal the factors predict */
+                LAUNCH(h, "k_dwell_scale", k_dwell_scale, gr, PCON_T, 0, R.ds.p, D.t.p, nrow, D.dst.p);
+                auto points = profile == PPP_REMOVAL_FLAT ? k_prem_points<PPP_REMOVAL_FLAT>
+                            : profile == PPP_REMOVAL_PARABOLIC ? k_prem_points<PPP_REMOVAL_PARABOLIC> : k_prem_points<PPP_REMOVAL_HERTZ>;
+                LAUNCH(h, "k_prem_points", points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0, h->meta.p,
+                       h->sorted4.p, T.tab.p, D.dst.p, T.off.p, T.reach.p, T.tab_nsl, D.map.p, R.held.p);
+                return PPP_OK;
+            };
+            auto back = [&](bool with_den) -> int {
+#define PPP_DWELL_BACK(P) do { if (with_den) LAUNCH(h, "k_dwell_back", (k_dwell_back<P, true>), gb, 64 * DYN_WAVES, 0, I, T.tab.p, nrow, D.g.p, D.num.p, D.den.p); \
+                               else LAUNCH(h, "k_dwell_back", (k_dwell_back<P, false>), gb, 64 * DYN_WAVES, 0, I, T.tab.p, nrow, D.g.p, D.num.p, D.den.p); } while (0)
+                if (profile == PPP_REMOVAL_FLAT) PPP_DWELL_BACK(PPP_REMOVAL_FLAT);
+                else if (profile == PPP_REMOVAL_PARABOLIC) PPP_DWELL_BACK(PPP_REMOVAL_PARABOLIC);
+                else PPP_DWELL_BACK(PPP_REMOVAL_HERTZ);
+#undef PPP_DWELL_BACK
+                return PPP_OK;
+            };
+            const double *cur = M.map.p; /* the forward pass at t = 1 */
+            if (solve) LAUNCH(h, "k_dwell_resid", k_dwell_resid, (unsigned)grid, PCON_T, 0, cur, dtarget, level, R.held.p, (int)N, per, D.psum.p);
+            for (int it = 0; solve && it < iterations; ++it) { /* no host wait in here */
+                if (it > 0) { rc = forward(); if (rc) return rc; cur = D.map.p; }
+                LAUNCH(h, "k_dwell_ratio", k_dwell_ratio, gn, PCON_T, 0, cur, dtarget, level, R.held.p, (int)N, D.g.p);
+                rc = back(it == 0);
+                if (rc) return rc;
+                LAUNCH(h, "k_dwell_update", k_dwell_update, gr, PCON_T, 0, D.num.p, D.den.p, nrow, dwell_min, dwell_max, D.t.p);
+            }
+            if (!solve) { rc = back(true); if (rc) return rc; } /* den alone: which rows hold something */
+            rc = forward();
+            if (rc) return rc;
+            if (solve) LAUNCH(h, "k_dwell_resid", k_dwell_resid, (unsigned)grid, PCON_T, 0, D.map.p, dtarget, level, R.held.p, (int)N, per, D.psum.p + grid);
+            LAUNCH(h, "k_dwell_stats", k_dwell_stats, (unsigned)std::min<size_t>(gr, 2 * (size_t)h->num_cus), PCON_T, 0, D.t.p, D.den.p, nrow, dwell_min,
+                   dwell_max, D.acc.p);
+        }
+        unsigned long long acc[4];
+        std::vector<double> psum(2 * (size_t)grid, 0.0);
+        HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+        if (solve) HIPCHK(h, copy_sync(h, psum.data(), D.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (acc[0] > (size_t)nrow || acc[1] > (size_t)nrow) return fail(h, PPP_ERR_HIP, "path dwell: statistics corrupt");
+        D.rows.assign((size_t)nrow, ppp_dwell_row{});
+        double wsum = 0.0;
+        if (nrow > 0) {
+            std::vector<float4> tab((size_t)nrow);
+            std::vector<int> off((size_t)nsl + 1);
+            if (walk) HIPCHK(h, copy_sync(h, tv.data(), D.t.p, tv.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(h, copy_sync(h, dsv.data(), R.ds.p, dsv.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(h, copy_sync(h, tab.data(), T.tab.p, tab.size() * sizeof(float4), hipMemcpyDeviceToHost));
+            HIPCHK(h, copy_sync(h, off.data(), T.off.p, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+            if (off[0] != 0 || off[(size_t)nsl] != nrow) return fail(h, PPP_ERR_HIP, "path dwell: sample table corrupt");
+            for (int i = 0; i < nsl; ++i) {
+                if (off[(size_t)i + 1] < off[(size_t)i]) return fail(h, PPP_ERR_HIP, "path dwell: sample table corrupt");
+                double len = 0.0; /* the slice's scaled lengths in sample order, the slices in order: path_length's scheme */
+                for (int j = off[(size_t)i]; j < off[(size_t)i + 1]; ++j) {
+                    const float4 &q = tab[(size_t)j];
+                    const double scaled = dsv[(size_t)j] * tv[(size_t)j];
+                    len += scaled;
+                    D.rows[(size_t)j] = ppp_dwell_row{T.tab_sb + i, q.x, q.y, q.z, std::sqrt(q.w), dsv[(size_t)j], tv[(size_t)j]};
+                }
+                wsum += len;
+            }
+        }
+        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
+        ppp_dwell_stats st = {};
+        st.n = N; st.touched = touched; st.rows = (size_t)nrow; st.at_min = (size_t)acc[0]; st.at_max = (size_t)acc[1];
+        st.iterations = iterations; st.level = level;
+        st.residual_before = st.residual_after = (double)NAN;
+        if (solve) {
+            double before = 0.0, after = 0.0;
+            for (int g = 0; g < grid; ++g) { before += psum[(size_t)g]; after += psum[(size_t)grid + g]; }
+            st.residual_before = std::sqrt(before / (double)touched); st.residual_after = std::sqrt(after / (double)touched);
+        }
+        st.max_dwell = acc[3] ? as_double(acc[2]) : (double)NAN; st.min_dwell = acc[3] ? as_double(~acc[3]) : (double)NAN;
+        st.path_length = rs.path_length; st.time_factor = wsum / rs.path_length;
+        D.stats = st;
+        D.serial = h->pass.serial(); D.profile = profile; D.iterations = iterations; D.dmin = dwell_min; D.dmax = dwell_max;
+        D.valid = !target;
+    }
+    if (stats) *stats = D.stats;
+    const size_t kr = std::min(row_cap, D.rows.size()), k = std::min(cap, N);
+    if (rows && kr) memcpy(rows, D.rows.data(), kr * sizeof(ppp_dwell_row));
+    if (removal && k) HIPCHK(h, copy_sync(h, removal, D.map.p, k * sizeof(double), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

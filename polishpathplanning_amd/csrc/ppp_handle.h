@@ -237,6 +237,21 @@ struct ppp_handle_s {
         double path_length = 0.0;
         struct Slot { DevBuf<double> map; unsigned long long serial = ~0ull; ppp_removal_stats stats = {}; } slot[3];
     } prem;
+    /* dwell schedule of the last pass (ppp_get_path_dwell): per table row the factor t, the scaled length dst = ds * t and the
+       fixed-point sums num / den of the transposed walk; by cloud index the ratio g, the caller's target and the map the factors
+       predict -- maps of its own: prem's unit-feed maps stay as they are.  The result of a call without a target is kept for
+       (serial, profile, iterations, dmin, dmax): rows and stats on the host, the map on the device. */
+    struct PathDwell {
+        DevBuf<double> t, dst, g, target, map, psum;
+        DevBuf<long long> num, den;
+        DevBuf<unsigned long long> acc;
+        bool valid = false;
+        unsigned long long serial = ~0ull;
+        int profile = 0, iterations = 0;
+        double dmin = 0.0, dmax = 0.0;
+        std::vector<ppp_dwell_row> rows;
+        ppp_dwell_stats stats = {};
+    } dwell;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -161,6 +161,8 @@ def lib():
         L.ppp_get_path_coverage.argtypes = [vp, C.POINTER(C.c_ubyte), sz, szp, szp]
         L.ppp_get_path_contacts.argtypes = [vp, C.POINTER(C.c_uint), ip, ip, sz, C.POINTER(ContactStats)]
         L.ppp_get_path_removal.argtypes = [vp, C.c_int, C.POINTER(C.c_double), sz, C.POINTER(RemovalStats)]
+        L.ppp_get_path_dwell.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.POINTER(DwellRow), sz,
+                                         C.POINTER(C.c_double), sz, C.POINTER(DwellStats)]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -304,6 +306,19 @@ class RemovalStats(C.Structure):
     """ppp_removal_stats"""
     _fields_ = [("n", C.c_size_t), ("touched", C.c_size_t), ("min_removal", C.c_double), ("max_removal", C.c_double),
                 ("sum", C.c_double), ("sum_sq", C.c_double), ("path_length", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+class DwellRow(C.Structure):
+    """ppp_dwell_row"""
+    _fields_ = [("slice", C.c_int), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("r", C.c_float), ("ds", C.c_double),
+                ("dwell", C.c_double)]
+
+
+class DwellStats(C.Structure):
+    """ppp_dwell_stats"""
+    _fields_ = [("n", C.c_size_t), ("touched", C.c_size_t), ("rows", C.c_size_t), ("at_min", C.c_size_t), ("at_max", C.c_size_t),
+                ("iterations", C.c_int), ("level", C.c_double), ("residual_before", C.c_double), ("residual_after", C.c_double),
+                ("min_dwell", C.c_double), ("max_dwell", C.c_double), ("path_length", C.c_double), ("time_factor", C.c_double)]
 
 
 class ContactFieldStats(C.Structure):
@@ -859,6 +874,36 @@ class Engine:
         stats = dict(n=st.n, touched=st.touched, min_removal=st.min_removal, max_removal=st.max_removal, sum=st.sum, sum_sq=st.sum_sq,
                      path_length=st.path_length, hist=np.array(st.hist[:], np.int64), mean=mean, cv=cv)
         return removal, stats
+
+    def path_dwell(self, profile=REMOVAL_HERTZ, target=None, iterations=8, dwell_min=0.25, dwell_max=4.0, maps=True):
+        """(rows, removal float64[n], stats dict): a dwell factor per sample of the last pass's final paths that steers the
+        predicted removal of path_removal(profile) towards target (float64[n] by cloud index; None: uniform, same total), after
+        `iterations` rounds of the multiplicative update with the factors kept in [dwell_min, dwell_max] (ppp_get_path_dwell).
+        rows: a structured array (slice, x, y, z, r, ds, dwell) in (slice, sample) order; removal: the map the factors predict;
+        stats: n, touched, rows, at_min, at_max, iterations, level, residual_before, residual_after, min_dwell, max_dwell,
+        path_length, time_factor.  maps=False returns (None, None, stats)"""
+        tg = None
+        if target is not None:
+            tg = np.ascontiguousarray(target, np.float64)
+            if tg.shape != (self.n,):
+                raise ValueError("target must hold one value per cloud point")
+        tp = tg.ctypes.data_as(C.POINTER(C.c_double)) if tg is not None else None
+        args = (int(profile), tp, int(iterations), float(dwell_min), float(dwell_max))
+        st = DwellStats()
+        rows = removal = None
+        if not maps:
+            self._chk(self.L.ppp_get_path_dwell(self.h, *args, None, 0, None, 0, C.byref(st)))
+        else:
+            # the sizes first: without a target the result is kept and the second call launches nothing; with one both compute
+            self._chk(self.L.ppp_get_path_dwell(self.h, *args, None, 0, None, 0, C.byref(st)))
+            nrow, n = st.rows, st.n
+            rows = np.zeros(max(nrow, 1), np.dtype(DwellRow))
+            removal = np.zeros(max(n, 1), np.float64)
+            self._chk(self.L.ppp_get_path_dwell(self.h, *args, rows.ctypes.data_as(C.POINTER(DwellRow)), nrow,
+                                                removal.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(st)))
+            rows, removal = rows[:st.rows], removal[:st.n]
+        stats = {k: getattr(st, k) for k, _ in DwellStats._fields_}
+        return rows, removal, stats
 
     def contact_field(self, maps=True, min_width=0.0):
         """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every
