@@ -4,7 +4,8 @@
 // keeps them commented out); PPP_PATH_CONTACTS=1 prints how evenly they cover (the largest and mean contact count, the points
 // two or more slices touch); PPP_PATH_REMOVAL=1 prints how much they take off and how evenly (touched points, path length, mean /
 // min / max removal and cv with the Hertzian profile); PPP_PATH_DWELL=1 prints what a feed schedule could do about it (the dwell
-// factors' range, the residual before and after, the time factor); PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
+// factors' range, the residual before and after, the time factor); PPP_PATH_FEED=1 times the list (the waypoints by what limits
+// their feed, the feed's range, the duration) and writes <pathFile>.feed, pathFile's columns with t and feed; PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
 // regions, PPP_GAPS_MIN points or more each).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +36,8 @@ int main(int argc, char **argv)
     if (rem && rem[0] == '1') path_planner.get_path_removal();
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
+    const char *fed = std::getenv("PPP_PATH_FEED");
+    if (fed && fed[0] == '1') path_planner.get_path_feed();
     const char *fld = std::getenv("PPP_CONTACT_FIELD");
     if (fld && fld[0] == '1') path_planner.get_contact_field();
     const char *gap = std::getenv("PPP_GAPS");

@@ -2,7 +2,7 @@
 // (robot_path.h:58-98) but nothing constructs it -- the header does not compile upstream -- so this is the shape of
 // src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths,
 // PPP_PATH_CONTACTS=1 their contact counts, PPP_PATH_REMOVAL=1 the predicted removal, PPP_PATH_DWELL=1 a dwell schedule
-// towards a uniform removal, PPP_GAPS=1 the regions they leave uncovered.
+// towards a uniform removal, PPP_PATH_FEED=1 the timed feed schedule of the list (written to <pathFile>.feed), PPP_GAPS=1 the regions they leave uncovered.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -35,6 +35,8 @@ int main(int argc, char **argv)
     if (rem && rem[0] == '1') path_planner.get_path_removal();
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
+    const char *fed = std::getenv("PPP_PATH_FEED");
+    if (fed && fed[0] == '1') path_planner.get_path_feed();
     const char *fld = std::getenv("PPP_CONTACT_FIELD");
     if (fld && fld[0] == '1') path_planner.get_contact_field();
     const char *gap = std::getenv("PPP_GAPS");

@@ -120,6 +120,10 @@ public:
     /* what a feed schedule could do about it: a dwell factor per sample towards a uniform removal -- the factors' range, the
        residual before and after, the time factor (ppp_get_path_dwell) */
     void get_path_dwell() { planner.print_path_dwell(); }
+    /* a timed feed schedule for the WayPointsList (needs getPath()): the dwell factor, the feed under a cap and an acceleration
+       limit and the time per waypoint -- the waypoints by what limits them, the feed's range, the duration; writes
+       <pathFile>.feed: pathFile's columns, then t and feed (ppp_get_path_feed, ppp_write_feed_file) */
+    void get_path_feed() { planner.print_path_feed((std::string(planner.path_file()) + ".feed").c_str()); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }

@@ -351,6 +351,51 @@ typedef struct {
 } ppp_dwell_stats;
 int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,
                        ppp_dwell_row *rows, size_t row_cap, double *removal, size_t cap, ppp_dwell_stats *stats);
+/* A timed feed schedule for the WayPointsList of the last pass: for every row of the list the dwell
+   factor there, the feed the tool's contact point may have there under a cap and an acceleration limit, and the time at which
+   the waypoint is reached.  Positions are the float rows of PPP_STAGE_WP_XYZ (mm, list order, before hand-eye, smoothing and
+   flange offset); the kept slices are the walk's in list order (without the first and the last where drop_ends is set), each
+   with the count ppp_get_waypoint_counts gives; a kept slice without waypoints has no rows and is skipped.
+     dwell  the rows of ppp_get_path_dwell(profile, target, iterations, dwell_min, dwell_max) on the waypoint's slice, linear in
+            (double)y between the last row a with (double)y_a <= y and a + 1 (t_a + u (t_b - t_a), u = (y - y_a) / (y_b - y_a);
+            y_b == y_a: t_a); before the first row its factor, at or after the last row its factor; no rows, or a NaN y: 1
+     s      (double)S_i 2^-20: S_0 = 0, S_{i+1} = S_i + llrint(d_i 2^20) in signed 64-bit integers along the slice, d_i the double
+            distance of waypoints i and i + 1 (differences of the floats in double; 0 when an end is not finite)
+     feed   c_i = min(feed / dwell_i, feed_max), at a slice's first and last waypoint also end_feed (>= 0); accel == +INFINITY:
+            c_i; else sqrt(min over the slice's j of (c_j c_j + (2 accel) ((double)|S_i - S_j| 2^-20))): the exact
+            forward-backward speed limit with braking distance
+     limit  what gave the minimum: 0 dwell, 1 feed_max, 2 end (the lowest number on a tie), 3 the acceleration (minimum < c_i c_i)
+     t      (the sum of llrint(dt 2^30) over every segment and link before the waypoint in list order) 2^-30.  A segment:
+            0 for D_i == 0; 2 sqrt((D_i 2^-20) / accel) when both ends rest; else (2 (D_i 2^-20)) / (v_i + v_{i+1}).  A link,
+            from a slice's last waypoint to the first of the next slice that has any: its length l (as d) / link_feed
+   Integer sums and minima of exact doubles have no order: every field of every row and of the statistics is the same bits in
+   every run.  rows receives the first min(cap, stats->W) rows; cap = 0 with rows == NULL asks for the size (stats->W).  The
+   first six arguments are ppp_get_path_dwell's: the call asks that call for its rows, and builds, shares and refuses as it
+   does; it leaves every other contact result alone.  PPP_ERR_ARG: no finished ppp_get_path of the handle's last pass, a
+   ppp_feed_params field outside its range, fp == NULL.  PPP_ERR_UNSUPPORTED: a slice-range or part handle, and a cloud under
+   ppp_trans2center (PPP_STAGE_WP_XYZ is then in the scanner's frame, the dwell rows in the aligned one).  Blocks until the
+   results are on the host.  With a NULL target the result is kept per (pass, profile, iterations, bounds, feed parameters): a
+   repeated call launches nothing.  Any output may be NULL. */
+typedef struct {
+    double feed;        /* nominal feed of the contact point, mm/s: finite, > 0 */
+    double feed_max;    /* cap on the feed, mm/s: finite, >= feed */
+    double accel;       /* limit on |dv/dt| along a slice, mm/s^2: > 0; +INFINITY: no limit */
+    double end_feed;    /* cap at the first and last waypoint of every slice, mm/s: finite >= 0; < 0: none */
+    double link_feed;   /* feed of the move from a slice's last waypoint to the next slice's first, mm/s: finite, > 0 */
+} ppp_feed_params;
+typedef struct { int slice; int limit; double dwell, s, feed, t; } ppp_feed_row;   /* one per row of the WayPointsList */
+typedef struct {
+    size_t W, slices;                 /* waypoints; kept slices with at least one waypoint */
+    size_t by_dwell, by_feed_max, by_end, by_accel;   /* waypoints by what binds them (limit 0 / 1 / 2 / 3) */
+    double min_feed, max_feed;        /* over all waypoints; NaN when W == 0 */
+    double path_length, link_length;  /* mm */
+    double duration, duration_links, duration_nominal;  /* s: the whole list; its link moves; path_length / feed */
+} ppp_feed_stats;
+int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,
+                      const ppp_feed_params *fp, ppp_feed_row *rows, size_t cap, ppp_feed_stats *stats);
+void ppp_default_feed_params(ppp_feed_params *fp);   /* 20, 30, 100, 0, 100 */
+/* "x y z r p y t feed " per line: ppp_write_path_file's six columns and format, then t and feed (host only) */
+int ppp_write_feed_file(const char *path, const float *wp6, const ppp_feed_row *rows, size_t W);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

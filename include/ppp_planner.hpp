@@ -379,6 +379,47 @@ public:
                     st.residual_after == st.residual_after ? st.residual_after : 0.0, st.iterations,
                     st.time_factor == st.time_factor ? st.time_factor : 1.0);
     }
+    /* a timed feed schedule for the WayPointsList of the last getPath (ppp_get_path_feed: per waypoint the dwell factor of
+       path_dwell() there, the feed of the contact point under fp's cap and acceleration limit, the time at which it is
+       reached): the statistics and, when asked for, the rows, one per row of the list.  With a target every call computes
+       again: ask for the rows at once */
+    bool path_feed(ppp_feed_stats &st, const ppp_feed_params &fp, std::vector<ppp_feed_row> *rows = nullptr, int profile = PPP_REMOVAL_HERTZ,
+                   const std::vector<double> *target = nullptr, int iterations = 8, double dwell_min = 0.25, double dwell_max = 4.0)
+    {
+        const double *tg = target ? target->data() : nullptr;
+        size_t W = 0;
+        int rc = rows ? ppp_num_waypoints(h_, &W) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (rows) rows->assign(W, ppp_feed_row{});
+            rc = ppp_get_path_feed(h_, profile, tg, iterations, dwell_min, dwell_max, &fp, rows ? rows->data() : nullptr, rows ? W : 0, &st);
+        }
+        if (rc == PPP_OK && rows && st.W < rows->size()) rows->resize(st.W);
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* three lines on path_feed() with the default feed parameters, the Hertzian profile, a uniform target and the default
+       rounds and bounds: the waypoints by what limits their feed, the feed's range and the lengths, then the duration against
+       the nominal one; with feed_file the list's six columns, t and feed go to that file (ppp_write_feed_file) */
+    void print_path_feed(const char *feed_file = nullptr)
+    {
+        ppp_feed_params fp;
+        ppp_default_feed_params(&fp);
+        ppp_feed_stats st = {};
+        std::vector<ppp_feed_row> rows;
+        if (!path_feed(st, fp, feed_file ? &rows : nullptr)) { st = ppp_feed_stats{}; rows.clear(); }
+        const bool any = st.W > 0;
+        std::printf("feed: %zu waypoints on %zu slices: %zu limited by the dwell, %zu by feed_max, %zu by end_feed, %zu by the acceleration\n", st.W,
+                    st.slices, st.by_dwell, st.by_feed_max, st.by_end, st.by_accel);
+        std::printf("feed: %f to %f mm/s along %f mm of path and %f mm of links\n", any ? st.min_feed : 0.0, any ? st.max_feed : 0.0, st.path_length,
+                    st.link_length);
+        std::printf("feed: duration %f s (%f s in links), %f s at the nominal feed\n", st.duration, st.duration_links, st.duration_nominal);
+        if (!feed_file || !any) return;
+        std::vector<float> wp6(6 * st.W);
+        size_t W = 0;
+        int rc = ppp_get_waypoints(h_, wp6.data(), st.W, &W);
+        if (rc != PPP_OK) { report(rc); return; }
+        if (W == st.W && ppp_write_feed_file(feed_file, wp6.data(), rows.data(), W) == PPP_OK) std::cout << "File saved: " << feed_file << std::endl;
+    }
+    const char *path_file() const { return cfg_.path_file; }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
        ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below
        min_width -- and, when asked for, the maps by cloud index (curv5: n x 5) */

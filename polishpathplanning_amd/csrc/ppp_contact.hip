@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, path removal, the dwell schedule, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h and ppp_dwell.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h and ppp_feed.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -12,6 +12,7 @@
 #include "ppp_regions.h"
 #include "ppp_removal.h"
 #include "ppp_dwell.h"
+#include "ppp_feed.h"
 #include <cstring>
 
 extern "C" {
@@ -446,6 +447,128 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
     const size_t kr = std::min(row_cap, D.rows.size()), k = std::min(cap, N);
     if (rows && kr) memcpy(rows, D.rows.data(), kr * sizeof(ppp_dwell_row));
     if (removal && k) HIPCHK(h, copy_sync(h, removal, D.map.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+void ppp_default_feed_params(ppp_feed_params *fp)
+{
+    if (!fp) return;
+    fp->feed = 20.0; fp->feed_max = 30.0; fp->accel = 100.0; fp->end_feed = 0.0; fp->link_feed = 100.0;
+}
+
+/* The feed schedule: the dwell rows come from ppp_get_path_dwell's own call (built if the handle does not hold
+   them, refused as it refuses), the list from the last getPath (its stage list gathered into list order if a window pass left
+   it in slots).  The kept slices' offsets into the list and into the rows are made on the host from the counts; then
+   k_feed_map, k_feed_scan, k_feed_env, k_feed_time and its two followers and k_feed_stats back to back on the stream, and one
+   wait.  Kept per (pass, profile, iterations, bounds, feed parameters) when there is no target. */
+int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,
+                      const ppp_feed_params *fp, ppp_feed_row *rows, size_t cap, ppp_feed_stats *stats)
+{
+    int rc = contact_query_begin(h, "path feed");
+    if (rc) return rc;
+    if (!fp) return fail(h, PPP_ERR_ARG, "path feed: no feed parameters");
+    if (!(std::isfinite(fp->feed) && fp->feed > 0.0)) return fail(h, PPP_ERR_ARG, "path feed: feed must be finite and > 0");
+    if (!(std::isfinite(fp->feed_max) && fp->feed_max >= fp->feed)) return fail(h, PPP_ERR_ARG, "path feed: feed_max must be finite and >= feed");
+    if (!(fp->accel > 0.0)) return fail(h, PPP_ERR_ARG, "path feed: accel must be > 0 (+INFINITY: no limit)");
+    if (!std::isfinite(fp->end_feed)) return fail(h, PPP_ERR_ARG, "path feed: end_feed must be finite (< 0: no cap at a slice's ends)");
+    if (!(std::isfinite(fp->link_feed) && fp->link_feed > 0.0)) return fail(h, PPP_ERR_ARG, "path feed: link_feed must be finite and > 0");
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0 || h->ranged || h->use_part)
+        return fail(h, PPP_ERR_UNSUPPORTED, "path feed: the dwell schedule it times cannot be solved on a slice-range handle");
+    if (h->aligned)
+        return fail(h, PPP_ERR_UNSUPPORTED, "path feed: under ppp_trans2center the list's points are in the scanner's frame and the dwell rows in the aligned one");
+    rc = ensure_ready(h, true, true); /* the waypoints must exist */
+    if (rc) return rc;
+    auto &F = h->feed;
+    const ppp_feed_params P = *fp;
+    const bool reuse = !target && F.valid && F.serial == h->pass.serial() && F.profile == profile && F.iterations == iterations &&
+                       F.dmin == dwell_min && F.dmax == dwell_max && memcmp(&F.fp, &P, sizeof(P)) == 0;
+    if (!reuse) {
+        F.valid = false;
+        ppp_dwell_stats dst = {};
+        rc = ppp_get_path_dwell(h, profile, target, iterations, dwell_min, dwell_max, nullptr, 0, nullptr, 0, &dst);
+        if (rc) return rc;
+        const std::vector<ppp_dwell_row> &DR = h->dwell.rows;
+        size_t Wl = 0, nkl = 0;
+        rc = ppp_get_stage(h, PPP_STAGE_WP_XYZ, nullptr, 0, &Wl); /* the list order of wp_xyz */
+        if (rc) return rc;
+        rc = ppp_get_waypoint_counts(h, nullptr, 0, &nkl);
+        if (rc) return rc;
+        if (Wl > 0x7ffffff0u || nkl > 0x7ffffff0u) return fail(h, PPP_ERR_CAPACITY, "path feed: more than 2^31 waypoints");
+        const int W = (int)Wl, nk = (int)nkl, first_kept = h->hmeta.first_kept;
+        std::vector<int> off((size_t)nk + 1, 0), rowoff((size_t)nk + 1, 0);
+        if (nk) { rc = ppp_get_waypoint_counts(h, off.data() + 1, nkl, &nkl); if (rc) return rc; }
+        std::vector<int2> tiles;
+        size_t slices = 0;
+        for (int k = 0; k < nk; ++k) {
+            const int m = off[(size_t)k + 1];
+            if (m < 0 || m > W - off[(size_t)k]) return fail(h, PPP_ERR_HIP, "path feed: waypoint counts corrupt");
+            off[(size_t)k + 1] = off[(size_t)k] + m;
+            slices += m > 0;
+            for (int i0 = 0; i0 < m; i0 += FEED_TILE) tiles.push_back(make_int2(k, i0));
+        }
+        if (off[(size_t)nk] != W) return fail(h, PPP_ERR_HIP, "path feed: waypoint counts corrupt");
+        /* the rows come in (slice, sample) order: slice k's are those of walk slice first_kept + k */
+        const size_t R = DR.size();
+        std::vector<float> ry(R);
+        std::vector<double> rt(R);
+        {
+            size_t j = 0;
+            for (int k = 0; k < nk; ++k) {
+                while (j < R && DR[j].slice < first_kept + k) ++j;
+                rowoff[(size_t)k] = (int)j;
+            }
+            while (j < R && DR[j].slice < first_kept + nk) ++j;
+            rowoff[(size_t)nk] = (int)j;
+            for (j = 0; j < R; ++j) { ry[j] = DR[j].y; rt[j] = DR[j].dwell; }
+        }
+        F.host_rows.assign((size_t)W, ppp_feed_row{});
+        unsigned long long acc[FEED_ACC_WORDS] = {};
+        if (W > 0) {
+            const size_t W1 = (size_t)W, K1 = (size_t)nk, R1 = std::max<size_t>(R, 1);
+            HIPCHK(h, F.off.ensure(K1 + 1)); HIPCHK(h, F.rowoff.ensure(K1 + 1)); HIPCHK(h, F.tiles.ensure(tiles.size()));
+            HIPCHK(h, F.ry.ensure(R1)); HIPCHK(h, F.rt.ensure(R1)); HIPCHK(h, F.cap.ensure(W1)); HIPCHK(h, F.D.ensure(W1));
+            HIPCHK(h, F.tloc.ensure(W1)); HIPCHK(h, F.rec.ensure(W1)); HIPCHK(h, F.rows.ensure(W1)); HIPCHK(h, F.linkD.ensure(K1));
+            HIPCHK(h, F.linkT.ensure(K1)); HIPCHK(h, F.slice_len.ensure(K1)); HIPCHK(h, F.slice_t.ensure(K1)); HIPCHK(h, F.acc.ensure(FEED_ACC_WORDS));
+            HIPCHK(h, copy_sync(h, F.off.p, off.data(), (K1 + 1) * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(h, copy_sync(h, F.rowoff.p, rowoff.data(), (K1 + 1) * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(h, copy_sync(h, F.tiles.p, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
+            if (R) {
+                HIPCHK(h, copy_sync(h, F.ry.p, ry.data(), R * sizeof(float), hipMemcpyHostToDevice));
+                HIPCHK(h, copy_sync(h, F.rt.p, rt.data(), R * sizeof(double), hipMemcpyHostToDevice));
+            }
+            HIPCHK(h, hipMemsetAsync(F.linkD.p, 0, K1 * sizeof(long long), h->stream));
+            HIPCHK(h, hipMemsetAsync(F.linkT.p, 0, K1 * sizeof(long long), h->stream));
+            HIPCHK(h, hipMemsetAsync(F.acc.p, 0, FEED_ACC_WORDS * sizeof(unsigned long long), h->stream));
+            const unsigned gw = (unsigned)((W1 + PCON_T - 1) / PCON_T);
+            LAUNCH(h, "k_feed_map", k_feed_map, gw, PCON_T, 0, h->wp_xyz.p, F.off.p, nk, W, first_kept, F.rowoff.p, F.ry.p, F.rt.p, P.feed, P.feed_max,
+                   P.end_feed, P.link_feed, F.rows.p, F.cap.p, F.D.p, F.linkD.p, F.linkT.p);
+            LAUNCH(h, "k_feed_scan", k_feed_scan, (unsigned)nk, PCON_T, 0, F.off.p, F.D.p, F.cap.p, F.rec.p, F.slice_len.p);
+            LAUNCH(h, "k_feed_env", k_feed_env, (unsigned)tiles.size(), FEED_TILE, 0, F.tiles.p, F.off.p, F.rec.p, P.accel, F.rows.p);
+            LAUNCH(h, "k_feed_time", k_feed_time, (unsigned)nk, PCON_T, 0, F.off.p, F.rows.p, F.D.p, F.linkT.p, P.accel, F.tloc.p, F.slice_t.p);
+            LAUNCH(h, "k_feed_time_slices", k_feed_time_slices, 1, PCON_T, 0, nk, F.slice_t.p, F.linkT.p, F.slice_len.p, F.linkD.p, F.acc.p);
+            LAUNCH(h, "k_feed_time_rows", k_feed_time_rows, gw, PCON_T, 0, W, first_kept, F.tloc.p, F.slice_t.p, F.rows.p);
+            LAUNCH(h, "k_feed_stats", k_feed_stats, std::min<unsigned>(gw, 2u * (unsigned)h->num_cus), PCON_T, 0, F.rows.p, W, F.acc.p);
+            HIPCHK(h, copy_sync(h, acc, F.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+            HIPCHK(h, copy_sync(h, F.host_rows.data(), F.rows.p, W1 * sizeof(ppp_feed_row), hipMemcpyDeviceToHost));
+            if (acc[0] + acc[1] + acc[2] + acc[3] != (unsigned long long)W) return fail(h, PPP_ERR_HIP, "path feed: statistics corrupt");
+        }
+        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
+        auto fixed = [](unsigned long long k, double one) { return (double)(long long)k * (1.0 / one); };
+        ppp_feed_stats st = {};
+        st.W = (size_t)W; st.slices = slices;
+        st.by_dwell = (size_t)acc[FEED_ACC_LIMIT]; st.by_feed_max = (size_t)acc[FEED_ACC_LIMIT + 1]; st.by_end = (size_t)acc[FEED_ACC_LIMIT + 2];
+        st.by_accel = (size_t)acc[FEED_ACC_LIMIT + 3];
+        st.max_feed = W ? as_double(acc[FEED_ACC_MAX]) : (double)NAN; st.min_feed = W ? as_double(~acc[FEED_ACC_NMIN]) : (double)NAN;
+        st.path_length = fixed(acc[FEED_ACC_PATH], FEED_LEN_FIXED); st.link_length = fixed(acc[FEED_ACC_LINK], FEED_LEN_FIXED);
+        st.duration = fixed(acc[FEED_ACC_DUR], FEED_TIME_FIXED); st.duration_links = fixed(acc[FEED_ACC_DUR_LINKS], FEED_TIME_FIXED);
+        st.duration_nominal = st.path_length / P.feed;
+        F.stats = st;
+        F.serial = h->pass.serial(); F.profile = profile; F.iterations = iterations; F.dmin = dwell_min; F.dmax = dwell_max; F.fp = P;
+        F.valid = !target;
+    }
+    if (stats) *stats = F.stats;
+    const size_t k = std::min(cap, F.host_rows.size());
+    if (rows && k) memcpy(rows, F.host_rows.data(), k * sizeof(ppp_feed_row));
     return PPP_OK;
 }
 

@@ -5,7 +5,7 @@
  *
  *   ppp_engine.hip   the handle, the plan and the passes, graphs and batches, the getters and the API mirrors; it defines
  *                    every helper declared here
- *   ppp_contact.hip  the contact queries: coverage, path coverage, path contacts, the contact field, the regions
+ *   ppp_contact.hip  the contact queries: coverage, path coverage, path contacts, the contact field, the regions, the schedules
  *   ppp_preproc.hip  the four preprocessing calls on the resident cloud
  *
  * A helper that only one unit calls is static in that unit and is not declared here.
@@ -24,6 +24,7 @@
 #include <vector>
 
 struct RegAcc; /* ppp_regions.h: a region's accumulators (the handle owns buffers of them; only the contact unit looks inside) */
+struct FeedRec; /* ppp_feed.h: what the feed envelope reads of a waypoint (likewise) */
 
 /* The types and helpers of the host units.  Hidden: the library is linked without visibility flags, and names like `fail` or
    `compact` are not for its dynamic symbol table. */
@@ -252,6 +253,28 @@ struct ppp_handle_s {
         std::vector<ppp_dwell_row> rows;
         ppp_dwell_stats stats = {};
     } dwell;
+    /* feed schedule of the last pass's WayPointsList (ppp_get_path_feed): the kept slices' offsets into the list and into the
+       dwell rows, those rows' y and factors, the (slice, tile) list of the envelope's workgroups; per waypoint the cap, the
+       segment's fixed-point length D, the envelope's record, the time ahead of it on its slice and the row; per kept slice
+       the link's length and time, the slice's length and time.  The result of a call without a target is kept on the host for
+       (serial, profile, iterations, dmin, dmax, the feed parameters). */
+    struct PathFeed {
+        DevBuf<int> off, rowoff;
+        DevBuf<int2> tiles;
+        DevBuf<float> ry;
+        DevBuf<double> rt, cap;
+        DevBuf<long long> D, tloc, linkD, linkT, slice_len, slice_t;
+        DevBuf<FeedRec> rec;
+        DevBuf<ppp_feed_row> rows;
+        DevBuf<unsigned long long> acc;
+        bool valid = false;
+        unsigned long long serial = ~0ull;
+        int profile = 0, iterations = 0;
+        double dmin = 0.0, dmax = 0.0;
+        ppp_feed_params fp = {};
+        std::vector<ppp_feed_row> host_rows;
+        ppp_feed_stats stats = {};
+    } feed;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {

@@ -633,6 +633,37 @@ static int write_path_file_impl(const char *path, const float *wp6, size_t W)
 }
 
 
+/* The feed file: pathFile's line, then the time at which the waypoint is reached and the feed there, both as `ofstream << double`
+   writes them (%g), each followed by a blank. */
+static int write_feed_file_impl(const char *path, const float *wp6, const ppp_feed_row *rows, size_t W)
+{
+    if (!path || ((!wp6 || !rows) && W)) return PPP_ERR_ARG;
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        std::cerr << "Unable to open file: " << path << std::endl;
+        return PPP_ERR_IO;
+    }
+    const size_t per = 8 * 16 + 1;
+    std::unique_ptr<char[]> text;
+    try { text.reset(new char[std::max<size_t>(W, 1) * per]); } catch (...) { fclose(f); return PPP_ERR_IO; }
+    char *o = text.get();
+    for (size_t w = 0; w < W; ++w) {
+        for (int i = 0; i < 6; i++) {
+            o = format_g6(o, wp6[6 * w + i]);
+            *o++ = ' ';
+        }
+        o += snprintf(o, 15, "%g", rows[w].t);
+        *o++ = ' ';
+        o += snprintf(o, 15, "%g", rows[w].feed);
+        *o++ = ' ';
+        *o++ = '\n';
+    }
+    const size_t len = (size_t)(o - text.get());
+    const bool ok = fwrite(text.get(), 1, len, f) == len;
+    return (fclose(f) == 0 && ok) ? PPP_OK : PPP_ERR_IO;
+}
+
+
 /* The boundary never lets a C++ exception (std::bad_alloc on a header that promises 10^12 points, ...) escape. */
 int ppp_load_pcd(const char *path, float **xyz, size_t *n, float viewpoint[7])
 {
@@ -657,5 +688,9 @@ int ppp_read_config(const char *path, ppp_config *c)
 int ppp_write_path_file(const char *path, const float *wp6, size_t W)
 {
     try { return write_path_file_impl(path, wp6, W); } catch (...) { return PPP_ERR_IO; }
+}
+int ppp_write_feed_file(const char *path, const float *wp6, const ppp_feed_row *rows, size_t W)
+{
+    try { return write_feed_file_impl(path, wp6, rows, W); } catch (...) { return PPP_ERR_IO; }
 }
 } /* extern "C" */

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -163,6 +163,11 @@ def lib():
         L.ppp_get_path_removal.argtypes = [vp, C.c_int, C.POINTER(C.c_double), sz, C.POINTER(RemovalStats)]
         L.ppp_get_path_dwell.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.POINTER(DwellRow), sz,
                                          C.POINTER(C.c_double), sz, C.POINTER(DwellStats)]
+        L.ppp_get_path_feed.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.POINTER(FeedParams),
+                                        C.POINTER(FeedRow), sz, C.POINTER(FeedStats)]
+        L.ppp_default_feed_params.argtypes = [C.POINTER(FeedParams)]
+        L.ppp_default_feed_params.restype = None
+        L.ppp_write_feed_file.argtypes = [C.c_char_p, fp, C.POINTER(FeedRow), sz]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -321,6 +326,30 @@ class DwellStats(C.Structure):
                 ("min_dwell", C.c_double), ("max_dwell", C.c_double), ("path_length", C.c_double), ("time_factor", C.c_double)]
 
 
+FEED_TILE = 256  # FEED_TILE (csrc/ppp_feed.h): waypoints of a k_feed_env workgroup
+FEED_LIMIT_DWELL, FEED_LIMIT_FEED_MAX, FEED_LIMIT_END, FEED_LIMIT_ACCEL = range(4)   # ppp_feed_row.limit
+
+
+class FeedParams(C.Structure):
+    """ppp_feed_params"""
+    _fields_ = [("feed", C.c_double), ("feed_max", C.c_double), ("accel", C.c_double), ("end_feed", C.c_double),
+                ("link_feed", C.c_double)]
+
+
+class FeedRow(C.Structure):
+    """ppp_feed_row"""
+    _fields_ = [("slice", C.c_int), ("limit", C.c_int), ("dwell", C.c_double), ("s", C.c_double), ("feed", C.c_double),
+                ("t", C.c_double)]
+
+
+class FeedStats(C.Structure):
+    """ppp_feed_stats"""
+    _fields_ = [("W", C.c_size_t), ("slices", C.c_size_t), ("by_dwell", C.c_size_t), ("by_feed_max", C.c_size_t),
+                ("by_end", C.c_size_t), ("by_accel", C.c_size_t), ("min_feed", C.c_double), ("max_feed", C.c_double),
+                ("path_length", C.c_double), ("link_length", C.c_double), ("duration", C.c_double),
+                ("duration_links", C.c_double), ("duration_nominal", C.c_double)]
+
+
 class ContactFieldStats(C.Structure):
     """ppp_contact_field_stats"""
     _fields_ = [("n", C.c_size_t), ("valid", C.c_size_t), ("narrow", C.c_size_t), ("min_abs_r", C.c_float), ("max_abs_r", C.c_float),
@@ -435,6 +464,17 @@ def read_config(path):
 def write_path_file(path, wp6):
     wp6 = np.ascontiguousarray(wp6, np.float32)
     rc = lib().ppp_write_path_file(path.encode(), _f(wp6), wp6.shape[0])
+    if rc:
+        raise PPPError(rc, "cannot write %s" % path)
+
+
+def write_feed_file(path, wp6, rows):
+    """pathFile's six columns, then t and feed of path_feed()'s rows (ppp_write_feed_file)"""
+    wp6 = np.ascontiguousarray(wp6, np.float32)
+    rows = np.ascontiguousarray(rows, np.dtype(FeedRow))
+    if wp6.ndim != 2 or wp6.shape[1] != 6 or rows.shape != (wp6.shape[0],):
+        raise ValueError("wp6 must be W x 6 and rows hold one row per waypoint")
+    rc = lib().ppp_write_feed_file(path.encode(), _f(wp6), rows.ctypes.data_as(C.POINTER(FeedRow)), wp6.shape[0])
     if rc:
         raise PPPError(rc, "cannot write %s" % path)
 
@@ -904,6 +944,34 @@ class Engine:
             rows, removal = rows[:st.rows], removal[:st.n]
         stats = {k: getattr(st, k) for k, _ in DwellStats._fields_}
         return rows, removal, stats
+
+    def path_feed(self, profile=REMOVAL_HERTZ, target=None, iterations=8, dwell_min=0.25, dwell_max=4.0, feed=20.0, feed_max=30.0,
+                  accel=100.0, end_feed=0.0, link_feed=100.0, maps=True):
+        """(rows, stats dict): a timed feed schedule for the WayPointsList of the last pass (ppp_get_path_feed; needs
+        get_path()).  The first five arguments are path_dwell()'s; feed, feed_max, end_feed (< 0: none) and link_feed in mm/s,
+        accel in mm/s^2 (inf: no limit).  rows: a structured array (slice, limit, dwell, s, feed, t), one per row of
+        waypoints(); stats: W, slices, by_dwell, by_feed_max, by_end, by_accel, min_feed, max_feed, path_length, link_length,
+        duration, duration_links, duration_nominal.  maps=False returns (None, stats)"""
+        tg = None
+        if target is not None:
+            tg = np.ascontiguousarray(target, np.float64)
+            if tg.shape != (self.n,):
+                raise ValueError("target must hold one value per cloud point")
+        tp = tg.ctypes.data_as(C.POINTER(C.c_double)) if tg is not None else None
+        fp = FeedParams(float(feed), float(feed_max), float(accel), float(end_feed), float(link_feed))
+        args = (int(profile), tp, int(iterations), float(dwell_min), float(dwell_max), C.byref(fp))
+        st = FeedStats()
+        rows = None
+        if not maps:
+            self._chk(self.L.ppp_get_path_feed(self.h, *args, None, 0, C.byref(st)))
+        else:
+            # with a target every call computes again: one call sized by the list, which the call cannot outgrow
+            W = self.num_waypoints()
+            rows = np.zeros(max(W, 1), np.dtype(FeedRow))
+            self._chk(self.L.ppp_get_path_feed(self.h, *args, rows.ctypes.data_as(C.POINTER(FeedRow)), W, C.byref(st)))
+            rows = rows[:min(W, st.W)]
+        stats = {k: getattr(st, k) for k, _ in FeedStats._fields_}
+        return rows, stats
 
     def contact_field(self, maps=True, min_width=0.0):
         """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every

@@ -1,0 +1,627 @@
+"""The timed feed schedule (ppp_get_path_feed): per row of the WayPointsList the dwell factor
+there, the feed under a cap and an acceleration limit, and the time at which the waypoint is reached.
+
+restate_feed below is the definitions in numpy, O(m^2) per slice: np.rint for llrint, int64 sums, the envelope as the minimum
+over a full m x m table.  Integer sums and minima of exact doubles have no order, so every field of every row and of the
+statistics is expected bit for bit.  Its CPU inputs come from the oracle (get_path(), waypoints_xyz(), tail_index(); the dwell
+rows from test_path_dwell's pairs and Solver), its GPU inputs from the engine's existing getters (stage(STAGE_WP_XYZ),
+waypoint_counts(), path_dwell()), so a failure on the GPU points at the new code alone."""
+import ctypes
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from polishpathplanning_amd import synth
+from test_path_coverage import CASES, case_params
+from test_path_dwell import BOUNDS, HERTZ, FLAT, PARABOLIC, Solver, pairs_of, same, sine_target
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F20, F30 = 2.0 ** 20, 2.0 ** 30
+INF = float("inf")
+
+PARAMS_DECL = ("typedef struct {\n"
+               "    double feed;        /* nominal feed of the contact point, mm/s: finite, > 0 */\n"
+               "    double feed_max;    /* cap on the feed, mm/s: finite, >= feed */\n"
+               "    double accel;       /* limit on |dv/dt| along a slice, mm/s^2: > 0; +INFINITY: no limit */\n"
+               "    double end_feed;    /* cap at the first and last waypoint of every slice, mm/s: finite >= 0; < 0: none */\n"
+               "    double link_feed;   /* feed of the move from a slice's last waypoint to the next slice's first, mm/s: finite, > 0 */\n"
+               "} ppp_feed_params;")
+ROW_DECL = "typedef struct { int slice; int limit; double dwell, s, feed, t; } ppp_feed_row;   /* one per row of the WayPointsList */"
+STATS_DECL = ("typedef struct {\n"
+              "    size_t W, slices;                 /* waypoints; kept slices with at least one waypoint */\n"
+              "    size_t by_dwell, by_feed_max, by_end, by_accel;   /* waypoints by what binds them (limit 0 / 1 / 2 / 3) */\n"
+              "    double min_feed, max_feed;        /* over all waypoints; NaN when W == 0 */\n"
+              "    double path_length, link_length;  /* mm */\n"
+              "    double duration, duration_links, duration_nominal;  /* s: the whole list; its link moves; path_length / feed */\n"
+              "} ppp_feed_stats;")
+CALL_DECL = ("int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int iterations, double dwell_min, double dwell_max,\n"
+             "                      const ppp_feed_params *fp, ppp_feed_row *rows, size_t cap, ppp_feed_stats *stats);")
+DEFAULT_DECL = "void ppp_default_feed_params(ppp_feed_params *fp);   /* 20, 30, 100, 0, 100 */"
+WRITE_DECL = "int ppp_write_feed_file(const char *path, const float *wp6, const ppp_feed_row *rows, size_t W);"
+PARAMS_FIELDS = ("feed", "feed_max", "accel", "end_feed", "link_feed")
+ROW_FIELDS = ("slice", "limit", "dwell", "s", "feed", "t")
+STATS_FIELDS = ("W", "slices", "by_dwell", "by_feed_max", "by_end", "by_accel", "min_feed", "max_feed", "path_length", "link_length",
+                "duration", "duration_links", "duration_nominal")
+ROW_DT = np.dtype([("slice", np.int32), ("limit", np.int32), ("dwell", np.float64), ("s", np.float64), ("feed", np.float64),
+                   ("t", np.float64)])
+
+# The issue's numbers but for feed_max and accel.  With feed_max 22 and accel 50 the restatement leaves regimes empty: the lists
+# are sampled every 7 mm and 50 mm/s^2 brakes 20 mm/s within 4 mm, so no waypoint is bound by the acceleration (by_accel 0 on
+# cases 1, 5 and 7), and on dome_brute_v1 every factor is below 20 / 22, so none is bound by its dwell (by_dwell 0).  feed_max
+# 23.4 and accel 25 populate all four on cases 1 and 5 (test_restatement_on_oracle_input; DESIGN.md 7i notes the values).
+FEED = dict(feed=20.0, feed_max=23.4, accel=25.0, end_feed=0.0, link_feed=100.0)
+ROUNDS = 3
+
+
+# ---------------------------------------------------------------- the restatement
+
+
+def dist(a, b):
+    """d of step 2: float32[k, 3] each; the differences in double, sqrt(((dx dx) + dy dy) + dz dz); 0 where an end is not finite"""
+    ok = np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1)
+    d = b.astype(np.float64) - a.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.sqrt(((d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    return np.where(ok, v, 0.0)
+
+
+def dwell_at(y, ry, rt):
+    """step 1: y float64[m] of a slice's waypoints; ry (float64 of the float y), rt: the slice's rows of the dwell table"""
+    out = np.ones(len(y))
+    if not len(ry):
+        return out
+    last = np.searchsorted(ry, y, side="right") - 1            # the last row with ry <= y
+    for i in range(len(y)):
+        yi = float(y[i])
+        if yi != yi:
+            continue
+        if yi < ry[0]:
+            out[i] = rt[0]
+        elif yi >= ry[-1]:
+            out[i] = rt[-1]
+        else:
+            a = int(last[i]); b = a + 1
+            ya, yb, ta, tb = float(ry[a]), float(ry[b]), float(rt[a]), float(rt[b])
+            if yb == ya:
+                out[i] = ta
+            else:
+                u = (yi - ya) / (yb - ya)
+                out[i] = ta + u * (tb - ta)
+    return out
+
+
+def envelope(S, c, accel):
+    """step 4 on one slice: (q, first minimiser, the least |i - j| over the minimisers); S int64[m], c float64[m]"""
+    c2 = c * c
+    A = np.abs(S[:, None] - S[None, :]).astype(np.float64) * 2.0 ** -20
+    terms = c2[None, :] + (2.0 * accel) * A
+    q = terms.min(axis=1)
+    idx = np.arange(len(S))
+    away = np.where(terms == q[:, None], np.abs(idx[:, None] - idx[None, :]), len(S)).min(axis=1)
+    return q, terms.argmin(axis=1), away
+
+
+def restate_feed(xyz, counts, first_kept, drows, feed, feed_max, accel, end_feed, link_feed):
+    """(rows ROW_DT[W], stats dict, away int[W]): xyz float32[W, 3] in list order, counts per kept slice, drows a structured
+    array with the dwell table's slice, y and dwell.  away[w]: how many waypoints the nearest minimiser of step 4 lies from w
+    (0 without an acceleration limit)"""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    W = len(xyz)
+    rows = np.zeros(W, ROW_DT)
+    away = np.zeros(W, np.int64)
+    off = np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))])
+    assert off[-1] == W
+    tick = 0                                                  # everything before the waypoint, in 2^-30 s
+    path_fixed = link_fixed = links_tick = 0
+    prev_last = None
+    slices = 0
+    for k, m in enumerate(counts):
+        if m == 0:
+            continue
+        slices += 1
+        o = int(off[k])
+        P = xyz[o:o + m]
+        if prev_last is not None:                             # the link from the last slice that had waypoints
+            l = float(dist(xyz[prev_last:prev_last + 1], P[:1])[0])
+            link_fixed += int(np.rint(l * F20))
+            lt = int(np.rint((l / link_feed) * F30))
+            links_tick += lt
+            tick += lt
+        sel = drows["slice"] == first_kept + k
+        ry, rt = drows["y"][sel].astype(np.float64), drows["dwell"][sel].astype(np.float64)
+        dwell = dwell_at(P[:, 1].astype(np.float64), ry, rt)
+        c = feed / dwell
+        limit = np.zeros(m, np.int32)
+        limit[feed_max < c] = 1
+        c = np.where(feed_max < c, feed_max, c)
+        if end_feed >= 0:
+            for i in {0, m - 1}:
+                if end_feed < c[i]:
+                    c[i] = end_feed; limit[i] = 2
+        D = np.rint(dist(P[:-1], P[1:]) * F20).astype(np.int64)
+        S = np.concatenate([[0], np.cumsum(D)]).astype(np.int64)
+        if accel == INF:
+            v = c.copy()
+        else:
+            q, _, aw = envelope(S, c, accel)
+            v = np.sqrt(q)
+            limit[q < c * c] = 3
+            away[o:o + m] = aw
+        x = D.astype(np.float64) * 2.0 ** -20
+        vs = v[:-1] + v[1:]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dt = np.where(D == 0, 0.0, np.where(vs == 0, 2.0 * np.sqrt(x / accel), (2.0 * x) / vs))
+        dtq = np.rint(dt * F30).astype(np.int64)
+        T = tick + np.concatenate([[0], np.cumsum(dtq)]).astype(np.int64)
+        rows["slice"][o:o + m] = first_kept + k
+        rows["limit"][o:o + m] = limit
+        rows["dwell"][o:o + m] = dwell
+        rows["s"][o:o + m] = S.astype(np.float64) * 2.0 ** -20
+        rows["feed"][o:o + m] = v
+        rows["t"][o:o + m] = T.astype(np.float64) * 2.0 ** -30
+        tick = int(T[-1])
+        path_fixed += int(S[-1])
+        prev_last = o + m - 1
+    path_length = float(path_fixed) * 2.0 ** -20
+    stats = dict(W=W, slices=slices, by_dwell=int((rows["limit"] == 0).sum()), by_feed_max=int((rows["limit"] == 1).sum()),
+                 by_end=int((rows["limit"] == 2).sum()), by_accel=int((rows["limit"] == 3).sum()),
+                 min_feed=float(rows["feed"].min()) if W else float("nan"), max_feed=float(rows["feed"].max()) if W else float("nan"),
+                 path_length=path_length, link_length=float(link_fixed) * 2.0 ** -20, duration=float(tick) * 2.0 ** -30,
+                 duration_links=float(links_tick) * 2.0 ** -30, duration_nominal=path_length / feed)
+    return rows, stats, away
+
+
+NO_ROWS = np.zeros(0, np.dtype([("slice", np.int32), ("y", np.float32), ("dwell", np.float64)]))
+
+
+def line(m, step):
+    """m waypoints on a straight line along y, `step` apart (a power of two: every coordinate and length is exact)"""
+    xyz = np.zeros((m, 3), np.float32)
+    xyz[:, 1] = np.arange(m) * step
+    return xyz
+
+
+# ---------------------------------------------------------------- CPU
+
+
+def test_header_declares_and_engine_exports_path_feed(engine_mod):
+    hdr = open(os.path.join(ROOT, "include", "ppp_hip.h")).read()
+    for decl in (PARAMS_DECL, ROW_DECL, STATS_DECL, CALL_DECL, DEFAULT_DECL, WRITE_DECL):
+        assert decl in hdr, decl
+    assert (hdr.index("int ppp_get_path_dwell(") < hdr.index(PARAMS_DECL) < hdr.index(ROW_DECL) < hdr.index(STATS_DECL)
+            < hdr.index(CALL_DECL) < hdr.index(DEFAULT_DECL) < hdr.index(WRITE_DECL) < hdr.index("int ppp_get_contact_field("))
+    for sym in ("ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file"):
+        assert sym in engine_mod.EXPORTS
+    assert hasattr(engine_mod.Engine, "path_feed") and hasattr(engine_mod, "write_feed_file")
+    kernels = open(os.path.join(ROOT, "polishpathplanning_amd", "csrc", "ppp_feed.h")).read()
+    assert "#define FEED_TILE %d " % engine_mod.FEED_TILE in kernels
+    for h in ("Path_Generate.h", "Path_Generate_Algorithm.h", "robot_path.h"):
+        assert "void get_path_feed()" in open(os.path.join(ROOT, "include", h)).read(), h
+    planner = open(os.path.join(ROOT, "include", "ppp_planner.hpp")).read()
+    assert "bool path_feed(ppp_feed_stats &st, " in planner and "void print_path_feed(" in planner
+
+
+def test_header_is_c99_clean_with_path_feed(tmp_path):
+    src = tmp_path / "c99.c"
+    src.write_text('#include "ppp_hip.h"\nint main(void) {\n'
+                   '    int (*f)(ppp_handle, int, const double *, int, double, double, const ppp_feed_params *, ppp_feed_row *, size_t,\n'
+                   '             ppp_feed_stats *) = ppp_get_path_feed;\n'
+                   '    void (*g)(ppp_feed_params *) = ppp_default_feed_params;\n'
+                   '    int (*w)(const char *, const float *, const ppp_feed_row *, size_t) = ppp_write_feed_file;\n'
+                   '    ppp_feed_stats st;\n    ppp_feed_row row;\n    ppp_feed_params fp;\n'
+                   '    st.duration_nominal = 0.0; st.by_accel = 0; row.slice = 0; row.limit = 3; row.t = 1.0; fp.link_feed = 100.0;\n'
+                   '    return f == 0 || g == 0 || w == 0 || st.by_accel != 0 || row.slice != 0 || fp.link_feed < 1.0;\n}\n')
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"),
+                           str(src)])
+
+
+def test_feed_structs_layout_matches_the_header(engine_mod, tmp_path):
+    """the ctypes mirrors of ppp_feed_params, ppp_feed_row and ppp_feed_stats have the C structs' sizes and offsets"""
+    src = tmp_path / "layout.c"
+    structs = (("ppp_feed_params", PARAMS_FIELDS, engine_mod.FeedParams), ("ppp_feed_row", ROW_FIELDS, engine_mod.FeedRow),
+               ("ppp_feed_stats", STATS_FIELDS, engine_mod.FeedStats))
+    args, want = [], []
+    for name, fields, T in structs:
+        args += ["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields]
+        want += [ctypes.sizeof(T)] + [getattr(T, f).offset for f in fields]
+        assert tuple(f for f, _ in T._fields_) == fields
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppp_hip.h"\nint main(void) {\n'
+                   '    printf("' + " ".join(["%zu"] * len(args)) + '\\n", ' + ", ".join(args) + ');\n    return 0;\n}\n')
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert got == want
+    Rw = engine_mod.FeedRow
+    assert np.dtype(Rw).itemsize == ctypes.sizeof(Rw) == ROW_DT.itemsize and np.dtype(Rw).names == ROW_FIELDS
+    fp = engine_mod.FeedParams()
+    engine_mod.lib().ppp_default_feed_params(ctypes.byref(fp))
+    assert [getattr(fp, f) for f in PARAMS_FIELDS] == [20.0, 30.0, 100.0, 0.0, 100.0]
+
+
+def test_examples_build_with_the_path_feed_switch(engine_mod):
+    for ex in ("connect.cpp", "robot.cpp"):
+        src = open(os.path.join(ROOT, "examples", ex)).read()
+        assert 'getenv("PPP_PATH_FEED")' in src and "get_path_feed()" in src, ex
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), "connect", "connect1", "robot", "main"])
+    for exe in ("connect", "connect1", "robot", "main"):
+        assert os.access(os.path.join(ROOT, "examples", exe), os.X_OK)
+
+
+def test_write_feed_file_round_trips(engine_mod, tmp_path):
+    """a hand-made list: the first six columns are ppp_write_path_file's bytes, then t and feed"""
+    wp6 = np.array([[1.5, -2.25, 3.0, 0.1, -0.2, 3.14159], [1e-5, 123456.0, 1234567.0, -0.0, 1e10, 0.333333333],
+                    [0.0, 7.0, -7.5, 1.0, 2.0, 3.0]], np.float32)
+    rows = np.zeros(3, ROW_DT)
+    rows["t"] = [0.0, 0.25, 1234.5678]
+    rows["feed"] = [0.0, 20.0, 13.333333333333334]
+    a, b = str(tmp_path / "path.txt"), str(tmp_path / "path.txt.feed")
+    engine_mod.write_path_file(a, wp6)
+    engine_mod.write_feed_file(b, wp6, rows)
+    plain, timed = open(a, "rb").read().split(b"\n"), open(b, "rb").read().split(b"\n")
+    assert len(plain) == len(timed) == 4 and plain[3] == timed[3] == b""
+    for i in range(3):
+        assert timed[i].startswith(plain[i]) and plain[i].endswith(b" ")
+        t, f = timed[i][len(plain[i]):].split()
+        assert timed[i].endswith(b" ") and t == b"%g" % rows["t"][i] and f == b"%g" % rows["feed"][i]
+        assert abs(float(t) - rows["t"][i]) <= 1e-5 * max(1.0, rows["t"][i]) and abs(float(f) - rows["feed"][i]) <= 1e-4
+    with pytest.raises(ValueError):
+        engine_mod.write_feed_file(b, wp6, rows[:2])
+
+
+def test_restatement_reproduces_the_trapezoid():
+    """a straight 100 mm line, 801 waypoints 0.125 mm apart, constant cap 20 mm/s, accel 50 mm/s^2, rest at both ends: the
+    duration is the textbook L / v + v / a = 5.4 s (800 roundings to 2^-30 s: below 4e-7 s)"""
+    xyz = line(801, 0.125)
+    rows, st, _ = restate_feed(xyz, [801], 0, NO_ROWS, 20.0, 20.0, 50.0, 0.0, 100.0)
+    print("duration %r, path %r" % (st["duration"], st["path_length"]))
+    assert st["path_length"] == 100.0 and st["slices"] == 1 and st["link_length"] == 0.0 and st["duration_links"] == 0.0
+    assert abs(st["duration"] - (100.0 / 20.0 + 20.0 / 50.0)) <= 1e-6
+    assert st["duration_nominal"] == 5.0 and rows["t"][-1] == st["duration"] and rows["t"][0] == 0.0
+    assert np.all(rows["dwell"] == 1.0) and rows["feed"][0] == 0.0 and rows["feed"][-1] == 0.0 and st["max_feed"] == 20.0
+    # 4 mm = 32 segments of ramp on either side: the acceleration binds inside them, the cap between them
+    # (feed / dwell and feed_max tie at 20: the lowest number, the dwell's, wins)
+    assert list(rows["limit"][:2]) == [2, 3] and rows["limit"][31] == 3 and np.all(rows["limit"][32:769] == 0)
+    assert st["by_end"] == 2 and st["by_accel"] == 62 and st["by_dwell"] == 737 and st["by_feed_max"] == 0
+    assert np.all(np.diff(rows["t"]) > 0)
+
+
+def hand_made_slice(seed, m):
+    rng = np.random.default_rng(seed)
+    xyz = np.zeros((m, 3), np.float32)
+    xyz[:, 1] = np.cumsum(rng.uniform(0.05, 1.5, m))
+    xyz[:, 0] = rng.uniform(-1, 1, m)
+    xyz[:, 2] = 5 * np.sin(xyz[:, 1] / 9.0)
+    dr = np.zeros(24, NO_ROWS.dtype)
+    dr["y"] = np.sort(rng.uniform(xyz[2, 1], xyz[-3, 1], 24))
+    dr["dwell"] = rng.uniform(0.5, 2.5, 24)
+    return xyz, dr
+
+
+@pytest.mark.parametrize("seed,m,accel", [(1, 300, 40.0), (2, 257, 15.0), (3, 64, 3.0)])
+def test_restatement_envelope_is_the_forward_backward_sweep(seed, m, accel):
+    """random caps on random spacing: the O(m^2) envelope equals a sequential forward-backward sweep within 1e-12 (relative),
+    |q_{i+1} - q_i| <= 2 accel d_i (1 + 1e-12), and v_i <= c_i everywhere"""
+    xyz, dr = hand_made_slice(seed, m)
+    rows, st, _ = restate_feed(xyz, [m], 0, dr, 20.0, 30.0, accel, 0.0, 100.0)
+    c = np.minimum(20.0 / rows["dwell"], 30.0)
+    c[0] = c[-1] = 0.0
+    d = np.diff(rows["s"])
+    q = c * c
+    for i in range(m - 1):
+        q[i + 1] = min(q[i + 1], q[i] + 2.0 * accel * d[i])
+    for i in range(m - 2, -1, -1):
+        q[i] = min(q[i], q[i + 1] + 2.0 * accel * d[i])
+    got = rows["feed"] * rows["feed"]
+    print("largest relative difference %r" % float(np.max(np.abs(got - q) / np.maximum(q, 1e-300))))
+    assert np.all(np.abs(got - q) <= 1e-12 * q)
+    assert np.all(np.abs(np.diff(got)) <= 2.0 * accel * d * (1 + 1e-12))
+    assert np.all(rows["feed"] <= c)
+    assert len(np.unique(rows["dwell"])) > 20 and st["by_accel"] > 0 and st["by_end"] == 2
+    assert np.all(rows["limit"][rows["feed"] < c] == 3)
+
+
+def test_restatement_dwell_lookup_and_degenerate_slices():
+    """step 1's cases (before the first row, at and after the last, equal y, a NaN y, a slice without rows), a slice of one
+    waypoint, a slice without waypoints between two others, a non-finite end of a segment, rest to rest"""
+    dr = np.zeros(4, NO_ROWS.dtype)
+    dr["slice"] = 3
+    dr["y"] = [1.0, 2.0, 2.0, 4.0]
+    dr["dwell"] = [0.5, 1.0, 2.0, 4.0]
+    y = np.array([0.0, 1.0, 1.5, 2.0, 3.0, 4.0, 5.0, np.nan])
+    assert list(dwell_at(y, dr["y"].astype(np.float64), dr["dwell"])) == [0.5, 0.5, 0.75, 2.0, 3.0, 4.0, 4.0, 1.0]
+    xyz = np.zeros((8, 3), np.float32)
+    xyz[:, 1] = [0, 1, 1, 2, 5, 6, np.nan, 8]               # slices of 4, 0, 1, 3 waypoints; walk slices 2 .. 5
+    xyz[:, 0] = [0, 0, 0, 0, 7, 9, 9, 9]
+    rows, st, _ = restate_feed(xyz, [4, 0, 1, 3], 2, dr, 10.0, 40.0, 2.0, -1.0, 50.0)
+    assert list(rows["slice"]) == [2, 2, 2, 2, 4, 5, 5, 5] and st["slices"] == 3 and st["W"] == 8
+    assert list(rows["dwell"]) == [1.0] * 5 + [1.0] * 3 and st["by_end"] == 0   # walk slice 3 holds the rows and no waypoint
+    assert list(rows["s"][:4]) == [0.0, 1.0, 1.0, 2.0] and rows["t"][1] == rows["t"][2]       # D == 0: no time
+    assert list(rows["s"][5:]) == [0.0, 0.0, 0.0] and rows["t"][7] == rows["t"][5]          # a NaN end: no length
+    assert st["path_length"] == 2.0 and st["link_length"] == float(np.rint(np.sqrt(58.0) * F20) + np.rint(np.sqrt(5.0) * F20)) / F20
+    assert rows["t"][4] - rows["t"][3] == float(np.rint(np.sqrt(58.0) / 50.0 * F30)) / F30
+    rest, _, _ = restate_feed(line(2, 0.5), [2], 0, NO_ROWS, 10.0, 10.0, 2.0, 0.0, 50.0)
+    assert list(rest["feed"]) == [0.0, 0.0] and rest["t"][1] == 2.0 * np.sqrt(0.5 / 2.0)
+    free, _, _ = restate_feed(line(2, 0.5), [2], 0, NO_ROWS, 10.0, 10.0, INF, 0.0, 50.0)
+    assert free["t"][1] == 0.0                              # no limit and rest at both ends: sqrt(x / inf)
+    none, st0, _ = restate_feed(np.zeros((0, 3), np.float32), [0, 0], 1, NO_ROWS, 10.0, 10.0, 2.0, 0.0, 50.0)
+    assert len(none) == 0 and st0["W"] == 0 and st0["min_feed"] != st0["min_feed"] and st0["duration"] == 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_list(ci):
+    from oracle import ppo
+    ppo.build()
+    pts, kw = case_params(*CASES[ci])
+    o = ppo.Oracle(pts, **kw)
+    S = o.gen_path()
+    o.get_path()
+    xyz = o.waypoints_xyz()
+    tail = o.tail_index()
+    first_kept = 1 if o.params.drop_ends else 0
+    o.close()
+    counts = np.diff(np.concatenate([[-1], tail])).astype(np.int64)
+    return S, xyz, counts, first_kept
+
+
+def oracle_dwell_rows(ci, oracle_mod, profile=HERTZ):
+    """the dwell table of CASES[ci] by test_path_dwell's restatement: uniform target, ROUNDS rounds, BOUNDS"""
+    w = pairs_of(ci, oracle_mod)
+    s = Solver(w, profile)
+    L = s.unit_level()
+    t, _, _, _ = s.solve(np.full(s.n, L), L, ROUNDS, *BOUNDS)
+    dr = np.zeros(len(t), NO_ROWS.dtype)
+    dr["slice"], dr["y"], dr["dwell"] = w["rows"]["slice"], w["rows"]["y"], t
+    return dr
+
+
+@pytest.mark.parametrize("ci", [1, 5, 7], ids=["%s-w%d" % CASES[ci][:2] for ci in (1, 5, 7)])
+def test_restatement_on_oracle_input(oracle_mod, ci):
+    """the restatement alone on the oracle's list and dwell rows (Hertz, 3 rounds, bounds (0.85, 1.5), feed 20, feed_max 23.4,
+    accel 25, end_feed 0, link_feed 100: FEED above): every regime is populated on cases 1 and 5.  short_slices walk 3
+    has kept slices without a waypoint; whether it also has a waypoint on a slice without rows is printed and asserted
+    below as found: it has none -- a slice long enough for a waypoint (trim 10 on either side) is long enough for a
+    contact sample (2 mm on either side) -- so that branch of step 1 is covered by the hand-made slices above alone."""
+    S, xyz, counts, first_kept = _oracle_list(ci)
+    dr = oracle_dwell_rows(ci, oracle_mod)
+    rows, st, _ = restate_feed(xyz, counts, first_kept, dr, **FEED)
+    print("S %d kept %d W %d stats %r" % (S, len(counts), len(xyz), st))
+    assert st["W"] == len(xyz) > 0 and len(counts) == S - 2 * first_kept
+    assert st["by_dwell"] + st["by_feed_max"] + st["by_end"] + st["by_accel"] == st["W"]
+    assert st["duration"] > st["duration_nominal"] > 0 and st["duration_links"] > 0 and rows["t"][-1] <= st["duration"]
+    assert np.all(np.diff(rows["t"]) >= 0) and st["min_feed"] == 0.0 and st["max_feed"] <= FEED["feed_max"]
+    if ci in (1, 5):
+        assert min(st["by_dwell"], st["by_feed_max"], st["by_end"], st["by_accel"]) > 0
+    else:
+        have = set(dr["slice"].tolist())
+        without = [first_kept + k for k, m in enumerate(counts) if m > 0 and first_kept + k not in have]
+        print("kept slices without waypoints %d, with waypoints but without rows %r" % (int((counts == 0).sum()), without))
+        assert (counts == 0).any() and st["slices"] < len(counts)
+        assert without == []
+
+
+# ---------------------------------------------------------------- GPU
+
+KERNELS = ("k_feed_map", "k_feed_scan", "k_feed_env", "k_feed_time", "k_feed_time_slices", "k_feed_time_rows", "k_feed_stats")
+
+
+def engine_list(e):
+    """the restatement's inputs from the engine's own, separately tested getters"""
+    xyz = e.stage(0)                                          # STAGE_WP_XYZ
+    counts = e.waypoint_counts().astype(np.int64)
+    return xyz, counts, 1 if e.params.drop_ends else 0
+
+
+def dwell_rows_of(e, profile, target, iterations):
+    got = e.path_dwell(profile, target, iterations, *BOUNDS)[0]
+    dr = np.zeros(len(got), NO_ROWS.dtype)
+    dr["slice"], dr["y"], dr["dwell"] = got["slice"], got["y"], got["dwell"]
+    return dr
+
+
+def check_parity(e, profile=HERTZ, target=None, iterations=ROUNDS, **feed):
+    fp = dict(FEED, **feed)
+    xyz, counts, first_kept = engine_list(e)
+    want_rows, want, away = restate_feed(xyz, counts, first_kept, dwell_rows_of(e, profile, target, iterations), **fp)
+    rows, st = e.path_feed(profile, target, iterations, *BOUNDS, **fp)
+    print("stats: got %r\n       want %r" % (st, want))
+    assert rows.shape == want_rows.shape and st["W"] == e.num_waypoints()
+    for f in ROW_FIELDS:
+        bad = np.nonzero(np.ascontiguousarray(rows[f]).view(np.int32 if f in ("slice", "limit") else np.int64)
+                         != np.ascontiguousarray(want_rows[f]).view(np.int32 if f in ("slice", "limit") else np.int64))[0]
+        print("%s: %d of %d rows differ%s" % (f, len(bad), len(rows), "" if not len(bad) else
+                                             " (first %d: got %r want %r)" % (bad[0], rows[f][bad[0]], want_rows[f][bad[0]])))
+    for f in ROW_FIELDS:
+        assert same(np.ascontiguousarray(rows[f]), np.ascontiguousarray(want_rows[f])), f
+    assert list(st) == list(STATS_FIELDS) and same(st, want), (st, want)
+    none = e.path_feed(profile, target, iterations, *BOUNDS, maps=False, **fp)
+    assert none[0] is None and same(none[1], st)
+    return rows, st, away, counts
+
+
+def engine_for(engine_mod, ci, **more):
+    pts, kw = case_params(*CASES[ci])
+    e = engine_mod.Engine(0, **dict(kw, **more))
+    e.set_cloud(pts)
+    e.gen_path(); e.get_path()
+    return e, pts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ci", [1, 5, 7], ids=["%s-w%d" % CASES[ci][:2] for ci in (1, 5, 7)])
+def test_path_feed_matches_the_restatement(engine_mod, ci):
+    """every field of every row and of the statistics bit for bit, the issue's numbers"""
+    e, _ = engine_for(engine_mod, ci)
+    rows, st, _, counts = check_parity(e)
+    if ci in (1, 5):
+        assert min(st["by_dwell"], st["by_feed_max"], st["by_end"], st["by_accel"]) > 0
+    else:
+        assert (counts == 0).any()
+    e.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["no_accel_limit", "no_end_cap", "sine_target"])
+def test_path_feed_variants_match_the_restatement(engine_mod, variant):
+    """small_40k walk 1 without an acceleration limit, without the cap at the slices' ends, and towards a target map"""
+    e, pts = engine_for(engine_mod, 1)
+    if variant == "no_accel_limit":
+        _, st, _, _ = check_parity(e, accel=INF)
+        assert st["by_accel"] == 0 and st["by_end"] > 0
+    elif variant == "no_end_cap":
+        _, st, _, _ = check_parity(e, end_feed=-1.0)
+        assert st["by_end"] == 0 and st["min_feed"] > 0
+    else:
+        level = e.path_removal(HERTZ)[1]["mean"]
+        T = sine_target(dict(cloud=(pts * np.float32(1000)).astype(np.float32)), level)
+        check_parity(e, target=T)
+    e.close()
+
+
+@pytest.mark.gpu
+def test_path_feed_on_slices_longer_than_two_tiles(engine_mod):
+    """small_40k walk 0 sampled every 0.2 mm: the longest slice has more than 2 FEED_TILE waypoints (about 645), and with accel
+    2 mm/s^2 the braking distance from 20 mm/s, 100 mm, spans more than FEED_TILE waypoints: a minimiser lies in another tile"""
+    pts, cfg = synth.make_config("small_40k")
+    e = engine_mod.Engine(0, tool_radius=cfg["tool_radius"], walk=0, path_resolution=0.2)
+    e.set_cloud(pts)
+    e.gen_path(); e.get_path()
+    rows, st, away, counts = check_parity(e, accel=2.0)
+    print("longest slice %d waypoints, farthest minimiser %d waypoints away" % (counts.max(), away.max()))
+    assert counts.max() > 2 * engine_mod.FEED_TILE
+    assert away.max() > engine_mod.FEED_TILE and st["by_accel"] > 0
+    e.close()
+
+
+@pytest.mark.gpu
+def test_path_feed_is_the_same_in_every_run_and_kept_without_a_target(engine_mod):
+    """two fresh handles give the same bytes; a repeated call without a target launches none of the feed kernels; a changed
+    accel launches k_feed_env again but not k_dwell_back"""
+    a, _ = engine_for(engine_mod, 1)
+    b, pts = engine_for(engine_mod, 1)
+    a.enable_timing(True)
+    a.kernel_times()
+    first = a.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED)
+    _, launches = a.kernel_times(with_launches=True)
+    assert all(launches.get(k) == 1 for k in KERNELS) and launches.get("k_dwell_back") == ROUNDS, launches
+    again = a.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED)
+    _, launches = a.kernel_times(with_launches=True)
+    assert not any(launches.get(k) for k in KERNELS + ("k_dwell_back",)), launches
+    assert same(again, first) and same(b.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED), first)
+    assert first[1]["W"] > 0 and first[1]["duration"] > 0
+    other = a.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **dict(FEED, accel=FEED["accel"] / 2))
+    _, launches = a.kernel_times(with_launches=True)
+    assert launches.get("k_feed_env") == 1 and not launches.get("k_dwell_back"), launches
+    assert not same(other[0]["feed"].copy(), first[0]["feed"].copy()) and other[1]["duration"] > first[1]["duration"]
+    T = np.full(len(pts), a.path_dwell(HERTZ, None, ROUNDS, *BOUNDS, maps=False)[2]["level"])
+    a.kernel_times()
+    for _ in range(2):                                        # with a target every call computes again
+        got = a.path_feed(HERTZ, T, ROUNDS, *BOUNDS, maps=False, **FEED)
+        _, launches = a.kernel_times(with_launches=True)
+        assert launches.get("k_feed_env") == 1 and launches.get("k_dwell_back") == ROUNDS, launches
+    assert got[1]["W"] == first[1]["W"] and got[1]["slices"] == first[1]["slices"]
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
+def test_window_path_and_slab_path_give_the_same_feed(engine_mod):
+    pts, cfg = synth.make_config("small_40k")
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+    a = engine_mod.Engine(0, **kw)
+    b = engine_mod.Engine(0, fast_path=False, **kw)
+    for e in (a, b):
+        e.set_cloud(pts)
+        e.gen_path(); e.get_path()
+    assert a.fast_path() and not b.fast_path()
+    assert same(a.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED), b.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED))
+    assert a.fast_path()
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
+def test_path_feed_leaves_the_other_results_alone(engine_mod):
+    """path_coverage(), path_contacts(), path_removal() of all three profiles, path_dwell() and a regions() result taken before
+    and after a feed call are identical, and are those of a handle that never asked for one; so is the list"""
+    pts, cfg = synth.make_config("small_40k")
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+
+    def results(e):
+        f, c = e.path_coverage()
+        con = e.path_contacts()
+        rem = [e.path_removal(p) for p in (FLAT, PARABOLIC, HERTZ)]
+        dw = e.path_dwell(HERTZ, None, 2, *BOUNDS)
+        reg = e.regions(engine_mod.REGIONS_OVERLAP)
+        return f, c, con, rem, dw, reg, e.waypoints()
+
+    def fresh():
+        e = engine_mod.Engine(0, **kw)
+        e.set_cloud(pts)
+        e.gen_path(); e.get_path()
+        return e
+
+    never = fresh()
+    want = results(never)
+    e = fresh()
+    before = results(e)
+    st = None
+    for p in (HERTZ, FLAT, PARABOLIC):
+        st = e.path_feed(p, None, 2, *BOUNDS, **FEED)[1]
+        e.path_feed(p, np.full(len(pts), 1.0), 1, *BOUNDS, maps=False, **FEED)
+    assert st["W"] > 0
+    assert same(before, results(e)) and same(before, want)
+    f = fresh()                                              # the feed first: the other calls build on what it left
+    f.path_feed(HERTZ, None, 2, *BOUNDS, **FEED)
+    assert same(want, results(f))
+    never.close(); e.close(); f.close()
+
+
+@pytest.mark.gpu
+def test_path_feed_refusals(engine_mod):
+    from polishpathplanning_amd.robot_path import slice_ranges
+    pts, cfg = synth.make_config("small_40k")
+    R = cfg["tool_radius"]
+    e = engine_mod.Engine(0, tool_radius=R, walk=1)
+    e.set_cloud(pts)
+
+    def refused(h, code, *a, **k):
+        for maps in (False, True):
+            with pytest.raises(engine_mod.PPPError) as ex:
+                h.path_feed(*a, maps=maps, **k)
+            assert ex.value.code == code, (a, k, maps, ex.value)
+
+    refused(e, engine_mod.ERR_ARG)                                   # before any pass
+    S = e.gen_path()
+    refused(e, engine_mod.ERR_ARG)                                   # a pass, but no list
+    e.get_path()
+    nan = float("nan")
+    for bad in (dict(feed=0.0), dict(feed=-1.0), dict(feed=nan), dict(feed=INF, feed_max=INF), dict(feed_max=19.0), dict(feed_max=INF),
+                dict(feed_max=nan), dict(accel=0.0), dict(accel=-1.0), dict(accel=nan), dict(end_feed=nan), dict(end_feed=INF),
+                dict(end_feed=-INF), dict(link_feed=0.0), dict(link_feed=nan), dict(link_feed=INF)):
+        refused(e, engine_mod.ERR_ARG, **dict(FEED, **bad))
+    refused(e, engine_mod.ERR_ARG, 3)                                # ppp_get_path_dwell's own refusals
+    refused(e, engine_mod.ERR_ARG, iterations=0)
+    refused(e, engine_mod.ERR_ARG, dwell_min=1.5, dwell_max=2.0)
+    st = engine_mod.FeedStats()                                      # the size query
+    fp = engine_mod.FeedParams(*[FEED[k] for k in PARAMS_FIELDS])
+    assert e.L.ppp_get_path_feed(e.h, HERTZ, None, ROUNDS, BOUNDS[0], BOUNDS[1], ctypes.byref(fp), None, 0, ctypes.byref(st)) == 0
+    assert st.W == e.num_waypoints() > 0
+    assert e.L.ppp_get_path_feed(e.h, HERTZ, None, ROUNDS, BOUNDS[0], BOUNDS[1], None, None, 0, ctypes.byref(st)) == engine_mod.ERR_ARG
+    few = np.zeros(5, np.dtype(engine_mod.FeedRow))                  # the first min(cap, W) rows
+    assert e.L.ppp_get_path_feed(e.h, HERTZ, None, ROUNDS, BOUNDS[0], BOUNDS[1], ctypes.byref(fp),
+                                 few.ctypes.data_as(ctypes.POINTER(engine_mod.FeedRow)), 4, None) == 0
+    assert few[:4].tobytes() == e.path_feed(HERTZ, None, ROUNDS, *BOUNDS, **FEED)[0][:4].tobytes() and few[4].tobytes() == bytes(40)
+    e.close()
+    b, en = slice_ranges(S, 4)[1]
+    h = engine_mod.Engine(0, tool_radius=R, walk=1, slice_begin=b, slice_end=en)
+    h.set_cloud(pts)
+    h.gen_path(); h.get_path()
+    refused(h, engine_mod.ERR_UNSUPPORTED)
+    h.close()
+    g = engine_mod.Engine(0, tool_radius=R, walk=1)
+    g.set_cloud(pts)
+    g.trans2center()
+    g.gen_path(); g.get_path()
+    refused(g, engine_mod.ERR_UNSUPPORTED)
+    g.close()
