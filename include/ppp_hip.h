@@ -675,9 +675,17 @@ const char *ppp_queue_last_error(ppp_queue q);
 int ppp_set_plan_reuse(ppp_handle h, int on);
 /* How many handles the caller runs side by side on this device (default 1).  From two on the plan trades a little of a pass's own
  * latency for room on the CUs: the per-slice workgroups of small windows stay at 512 threads, so that a neighbouring pass's binning
- * and finish workgroups fit beside them (1 M points / 256 slices on three handles: 0.038 -> 0.029 ms per workpiece; one pass alone
+ * and finish workgroups fit beside them; from three on the binning launch of a large cloud narrows too (ppp_get_binning_form) (1 M points / 256 slices on three handles: 0.038 -> 0.029 ms per workpiece; one pass alone
  * 0.065 -> 0.068 ms).  Same lists either way.  ppp_queue_create sets it on its lanes. */
 int ppp_set_side_by_side(ppp_handle h, int handles);
+/* The form of the window path's binning launch in THIS HANDLE'S plan: threads of a workgroup and points per thread (both 0 while
+ * the plan runs the slab-index path).  1024 threads for a pass alone; 512 threads x 16 points where ppp_set_side_by_side announced
+ * three or more handles and the cloud is large (about 0.8 M points and more; measured on 1 M points / 256 slices: two handles lose
+ * with it and keep the form of a pass alone, four neither gain nor lose).  It is the form of the handle's own launches
+ * (ppp_run_async, ppp_gen_path_async).  A batch (ppp_run_batch_async) launches once for all members: in this form only if every
+ * member planned this same form, none bins through the staged form and the batch's slices together are no launch of several rounds
+ * of workgroups; otherwise in the 1024-thread form.  The getter does not report a batch's launch. */
+int ppp_get_binning_form(ppp_handle h, int *threads, int *points_per_thread);
 /* The engine has two launch sequences for the same hot path, with the same results up to the last bits of the normals'
  * float sums (both within the tolerances of tests/): the WINDOW path (three launches: every point binned once into the
  * window of its slice, one fused per-slice kernel, the finish; kd pairing, no dynamic adjustment / alignment, tool steps

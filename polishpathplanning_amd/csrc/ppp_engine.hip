@@ -41,6 +41,23 @@
 #define PPP_WIN_PPT8_FROM 1200000 /* the window path's binning launch: what it costs is its workgroups' reservations (one global atomic per workgroup and
                                      non-empty window) -- 1 M points / 256 windows: 122 workgroups of 8 points per thread 20.1 us, 244 of 4 18.8 us, 488 22.7-23.8, 977 33 us */
 #endif
+/* ... while THREE OR MORE passes share the device (ppp_set_side_by_side, win_pick_scatter): 512 threads x 16 points, the best
+   three-handle row of profiles/scatter_side_by_side.txt.  1 M points / 256 slices, ms per step by handles, parent -> this form:
+   two 0.0365-0.0369 -> 0.0381 (a LOSS: two handles keep the form of a pass alone), three 0.0284 -> 0.0274 (bench.py 0.02915 -> 0.02847),
+   four 0.0386-0.0388 -> 0.0386 (nothing either way).  Only where the form leaves PPP_WIN_SBS_MIN_WGS workgroups: 123 at 1 M points
+   gain, 31 at 250 k and 7 at 50 k lose 7-8 % on three handles (0.0194 -> 0.0207, 0.0170 -> 0.0184); no cloud between 250 k and 1 M
+   points was measured, the threshold keeps to the measured side.  A form that is not instantiated (win_scatter_form_ok; e.g.
+   PPP_WIN_SBS_SCAT_T = WSC_T with PPP_WIN_SBS_PPT = 0) switches the choice off: every launch is then the form of a pass alone. */
+#ifndef PPP_WIN_SBS_SCAT_T
+#define PPP_WIN_SBS_SCAT_T 512
+#endif
+#ifndef PPP_WIN_SBS_PPT
+#define PPP_WIN_SBS_PPT 16
+#endif
+#ifndef PPP_WIN_SBS_MIN_WGS
+#define PPP_WIN_SBS_MIN_WGS 96
+#endif
+#define PPP_WIN_SBS_FROM 3 /* handles side by side from which the binning launch takes that form (the slice workgroup narrows from 2) */
 #ifndef PPP_PPT16_FROM
 #define PPP_PPT16_FROM 1500000 /* ... and 16: a workgroup's run in a slab grows to ~7 points = most of a 128-byte line (2 M points: scatter 36.4 -> 32.4 us) */
 #endif
@@ -147,6 +164,21 @@ static int with_ppt(int ppt, F &&f)
     return ppt >= 8 ? f(std::integral_constant<int, 8>()) : f(std::integral_constant<int, 4>());
 }
 
+/* the binning launch of the window path: which (threads, points per thread) are instantiated (ppp_window.hip).  1024 threads: the
+   forms of a pass alone (2 points per thread: the single launch only, a tuning form); 512 and 256: the plain form's narrow ones */
+static bool win_scatter_form_ok(int T, int ppt)
+{
+    if (T == WSC_T) return ppt == 2 || ppt == 4 || ppt == 8;
+    return (T == 512 || T == 256) && (ppt == 8 || ppt == 16);
+}
+/* ... and the narrow ones as f(std::integral_constant<int, ppt>, std::integral_constant<int, T>) */
+template <class F>
+static int with_narrow_scatter(int T, int ppt, F &&f)
+{
+    if (T == 512) return ppt == 16 ? f(std::integral_constant<int, 16>(), std::integral_constant<int, 512>()) : f(std::integral_constant<int, 8>(), std::integral_constant<int, 512>());
+    return ppt == 16 ? f(std::integral_constant<int, 16>(), std::integral_constant<int, 256>()) : f(std::integral_constant<int, 8>(), std::integral_constant<int, 256>());
+}
+
 /* the neighbours of a curvature fit: the lanes of a wave hold them (every call that evaluates the contact model asks) */
 int curvature_k_ok(ppp_handle h, int k)
 {
@@ -237,7 +269,7 @@ int enqueue_normals(ppp_handle h)
 constexpr size_t PIN_REC0 = 0, PIN_REC1 = 64, PIN_PX = 128, PIN_CENSUS = PIN_PX + sizeof(float) * WIN_AUTO_SCAP,
                  PIN_AUTO_BYTES = PIN_CENSUS + sizeof(int) * 3 * WIN_AUTO_SCAP, PIN_MIN = 128 * 1024;
 
-/* Threads of a slice workgroup for a launch of `wgs` of them.  The kernel holds 116 VGPRs, i.e. 16 waves per CU.  While a
+/* Threads of a slice workgroup for a launch of `wgs` of them.  The kernel holds 101 VGPRs (allocated as 104), i.e. 16 waves per CU.  While a
    launch has fewer workgroups than the device has room for, a workgroup is as wide as its work can use (a left point per
    thread in the pairing, 4 .. 8 lanes per waypoint in the pose stage): the launch ends with its slowest workgroup.  A launch
    of several rounds of workgroups (batches, cfg 5) is about throughput: as many workgroups per CU as the LDS allows, the 16
@@ -278,6 +310,27 @@ static int win_pick_threads(const ppp_handle h, long long wgs)
         if (tv >= tmin && tv <= 1024 && tv % 64 == 0) T = tv;
     }
     return T;
+}
+
+/* The form of the binning launch: h->win_scat_threads x h->win_ppt, from the form of a pass alone (1024 threads x h->win_ppt_alone).
+   Where three or more passes share the device, under the conditions that narrow the slice workgroup above, the plain form of a
+   large enough cloud runs as PPP_WIN_SBS_SCAT_T x PPP_WIN_SBS_PPT (measured there, and only there, to gain: see those constants).
+   The staged form is one 1024-thread workgroup per CU by its LDS. */
+static void win_pick_scatter(ppp_handle h, long long wgs, int n_src)
+{
+    int T = WSC_T, ppt = h->win_ppt_alone;
+    if (!h->win_staged) {
+        if (h->side_by_side >= PPP_WIN_SBS_FROM && !win_throughput_launch(h, wgs) && h->win_capw <= 3072 && win_scatter_form_ok(PPP_WIN_SBS_SCAT_T, PPP_WIN_SBS_PPT) &&
+            n_src >= PPP_WIN_SBS_MIN_WGS * (PPP_WIN_SBS_SCAT_T * PPP_WIN_SBS_PPT)) {
+            T = PPP_WIN_SBS_SCAT_T; ppt = PPP_WIN_SBS_PPT;
+        }
+        int tv = T, pv = ppt; /* tuning runs only */
+        if (const char *ev = tuning_env("PPP_WIN_PPT")) pv = atoi(ev);
+        if (const char *ev = tuning_env("PPP_WIN_SCAT_T")) tv = atoi(ev);
+        if (win_scatter_form_ok(tv, pv)) { T = tv; ppt = pv; }
+        if (T == WSC_T) h->win_ppt_alone = ppt;
+    }
+    h->win_scat_threads = T; h->win_ppt = ppt;
 }
 
 /* The window path (ppp_window.h) for this plan, when it applies: kd pairing without dynamic adjustment or alignment, windows
@@ -376,7 +429,7 @@ static int plan_window(ppp_handle h, int S, double per)
     int T = win_pick_threads(h, std::max(1, h->se - h->sb));
     if (!T) return PPP_OK;
     /* points per thread of the binning launch: 8 from 1.2 million points on (16 was slower at 10 M points: 107 against 100 us) */
-    h->win_ppt = n_src > PPP_WIN_PPT8_FROM ? 8 : 4;
+    h->win_ppt_alone = n_src > PPP_WIN_PPT8_FROM ? 8 : 4;
     /* large clouds leave the binning launch through LDS in window order (write amplification 2.1 -> ~1.3 at 10 M points), with
        as many points per thread as the stage has room for */
     {
@@ -385,12 +438,12 @@ static int plan_window(ppp_handle h, int S, double per)
         h->win_staged = n_src > from && !tuning_env("PPP_WIN_NO_STAGE");
     }
     if (h->win_staged) {
-        h->win_ppt = 8;
-        if (win_scatter_lds_bytes(S, 8, WSC_T, true) + 2048 > (size_t)h->max_lds) h->win_ppt = 4;
-        if (win_scatter_lds_bytes(S, h->win_ppt, WSC_T, true) + 2048 > (size_t)h->max_lds) { h->win_staged = false; h->win_ppt = 8; }
+        h->win_ppt_alone = 8;
+        if (win_scatter_lds_bytes(S, 8, WSC_T, true) + 2048 > (size_t)h->max_lds) h->win_ppt_alone = 4;
+        if (win_scatter_lds_bytes(S, h->win_ppt_alone, WSC_T, true) + 2048 > (size_t)h->max_lds) { h->win_staged = false; h->win_ppt_alone = 8; }
     }
-    if (const char *ev = tuning_env("PPP_WIN_PPT")) { const int pv = atoi(ev); if ((pv == 2 || pv == 4 || pv == 8) && !h->win_staged) h->win_ppt = pv; } /* tuning runs only */
-    h->win_gs = std::max(1, (n_src + h->win_ppt * WSC_T - 1) / (h->win_ppt * WSC_T));
+    win_pick_scatter(h, std::max(1, h->se - h->sb), n_src);
+    h->win_gs = std::max(1, (n_src + h->win_ppt * h->win_scat_threads - 1) / (h->win_ppt * h->win_scat_threads));
     if (h->win_staged) h->win_gs = std::min(h->win_gs, std::max(1, h->num_cus)); /* the staged form loops over its chunks: a workgroup per CU (its LDS admits no second) */
     h->win_pad = pad; h->win_capw = capw; h->win_cap_el = cap_el; h->win_NB = NB; h->win_NBc = NBc; h->win_threads = T;
     h->win_stride = std::max(1, (int)per);
@@ -404,7 +457,7 @@ static int plan_window(ppp_handle h, int S, double per)
     h->win_first_kept = h->P.drop_ends ? 1 : 0;
     h->win_nkept = std::max(0, h->P.drop_ends ? S - 2 : S);
     h->win_px0 = px[0];
-    HIPCHK(h, h->win_part.ensure((size_t)std::max(h->win_gs, (n_src + 2 * WSC_T - 1) / (2 * WSC_T)))); /* (a batch may bin with fewer points per thread) */
+    HIPCHK(h, h->win_part.ensure((size_t)std::max(h->win_gs, (n_src + 2 * 256 - 1) / (2 * 256)))); /* (the largest grid of any form: a batch may bin in another one than this plan) */
     HIPCHK(h, h->win_pts.ensure((size_t)S * (size_t)capw));
     {   /* the knot arrays hold a cap_el segment per slice on this path */
         const double need = (double)S * (double)cap_el;
@@ -421,8 +474,8 @@ static int plan_window(ppp_handle h, int S, double per)
         h->inh_valid = true; h->inh_S = S; h->inh_n = n_src; h->inh_max_w = max_w; h->inh_max_el = max_el; h->inh_pad = pad; h->inh_P = h->P;
     }
     if (getenv("PPP_WIN_DEBUG"))
-        fprintf(stderr, "[ppp] window plan: S %d [%d,%d) pad %.2f capw %d cap_el %d NBc %d (throughput %d) threads %d ppt %d lds %zu B max window %d max left side %d census %s\n",
-                S, h->sb, h->se, pad, capw, cap_el, NBc, h->win_NBc_thr, T, h->win_ppt, win_slice_lds_for(h, NBc), max_w, max_el,
+        fprintf(stderr, "[ppp] window plan: S %d [%d,%d) pad %.2f capw %d cap_el %d NBc %d (throughput %d) threads %d ppt %d x %d threads lds %zu B max window %d max left side %d census %s\n",
+                S, h->sb, h->se, pad, capw, cap_el, NBc, h->win_NBc_thr, T, h->win_ppt, h->win_scat_threads, win_slice_lds_for(h, NBc), max_w, max_el,
                 from_auto ? "came with the cloud" : (inherit ? "inherited from an earlier cloud of this size" : "at plan time"));
     return PPP_OK;
 }
@@ -473,8 +526,15 @@ static int enqueue_window_gen(ppp_handle h)
     WinArgs A = win_args(h);
     const bool thr = win_throughput_launch(h, A.g_slice);
     if (thr) win_args_throughput(h, A);
-    const size_t scat_lds = win_scatter_lds_bytes(A.S, h->win_ppt, WSC_T, h->win_staged);
-    if (h->win_staged && h->win_ppt == 8) LAUNCH(h, "k_win_scatter", (k_win_scatter<8, true>), A.g_scatter, WSC_T, scat_lds, A);
+    const size_t scat_lds = win_scatter_lds_bytes(A.S, h->win_ppt, h->win_scat_threads, h->win_staged);
+    if (h->win_scat_threads != WSC_T) {
+        const int rcn = with_narrow_scatter(h->win_scat_threads, h->win_ppt, [&](auto ppt, auto st) -> int {
+            LAUNCH(h, "k_win_scatter", (k_win_scatter<decltype(ppt)::value, false, decltype(st)::value>), A.g_scatter, decltype(st)::value, scat_lds, A);
+            return PPP_OK;
+        });
+        if (rcn) return rcn;
+    }
+    else if (h->win_staged && h->win_ppt == 8) LAUNCH(h, "k_win_scatter", (k_win_scatter<8, true>), A.g_scatter, WSC_T, scat_lds, A);
     else if (h->win_staged) LAUNCH(h, "k_win_scatter", (k_win_scatter<4, true>), A.g_scatter, WSC_T, scat_lds, A);
     else if (h->win_ppt == 8) LAUNCH(h, "k_win_scatter", (k_win_scatter<8, false>), A.g_scatter, WSC_T, scat_lds, A);
     else if (h->win_ppt == 2) LAUNCH(h, "k_win_scatter", (k_win_scatter<2, false>), A.g_scatter, WSC_T, scat_lds, A);
@@ -1239,6 +1299,12 @@ int ppp_create(int device_id, ppp_handle *out)
     (void)hipFuncSetAttribute((const void *)k_win_scatter<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WIN_S_MAX);
     (void)hipFuncSetAttribute((const void *)k_win_scatter_b<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WIN_S_MAX);
     (void)hipFuncSetAttribute((const void *)k_win_scatter_b<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WIN_S_MAX);
+    for (int st : {512, 256}) for (int pp : {8, 16})
+        (void)with_narrow_scatter(st, pp, [&](auto ppt, auto t) -> int {
+            (void)hipFuncSetAttribute((const void *)k_win_scatter<decltype(ppt)::value, false, decltype(t)::value>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WIN_S_MAX);
+            (void)hipFuncSetAttribute((const void *)k_win_scatter_b<decltype(ppt)::value, false, decltype(t)::value>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WIN_S_MAX);
+            return PPP_OK;
+        });
     (void)hipFuncSetAttribute((const void *)k_win_scatter<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->max_lds - 2048);
     (void)hipFuncSetAttribute((const void *)k_win_scatter<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->max_lds - 2048);
     (void)hipFuncSetAttribute((const void *)k_win_scatter_b<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->max_lds - 2048);
@@ -1709,13 +1775,13 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
 {
     const size_t count = bg->hs.size();
     std::vector<WinArgs> mem(count);
-    bg->win_ppt = 4; bg->win_threads = 256; bg->win_lds = 0; bg->win_scat_lds = 0; bg->win_fin_lds = 0;
+    bg->win_ppt = 4; bg->win_scat_threads = WSC_T; bg->win_threads = 256; bg->win_lds = 0; bg->win_scat_lds = 0; bg->win_fin_lds = 0;
     bg->gx_scat = 1; bg->gx_slice = 1; bg->gx_wfin = 1;
     long long slices_total = 0;
     /* one form of the binning launch for the batch: staged when any member is, with the points per thread all staged members have room for */
     bg->win_staged = false;
     for (size_t i = 0; i < count; ++i) bg->win_staged = bg->win_staged || bg->hs[i]->win_staged;
-    for (size_t i = 0; i < count; ++i) bg->win_ppt = std::max(bg->win_ppt, bg->hs[i]->win_ppt);
+    for (size_t i = 0; i < count; ++i) bg->win_ppt = std::max(bg->win_ppt, bg->hs[i]->win_ppt_alone);
     if (bg->win_staged) {
         int smax = 1;
         for (size_t i = 0; i < count; ++i) smax = std::max(smax, bg->hs[i]->S_cap);
@@ -1723,6 +1789,18 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
         if (win_scatter_lds_bytes(smax, 8, WSC_T, true) + 2048 > (size_t)lead->max_lds) bg->win_ppt = 4;
         if (win_scatter_lds_bytes(smax, bg->win_ppt, WSC_T, true) + 2048 > (size_t)lead->max_lds) { bg->win_staged = false; bg->win_ppt = 8; }
     }
+    /* ... or the narrow form of passes that share the device (win_pick_scatter), where every member's plan chose that one form and the
+       batch's slice launch is no throughput launch either (a stream of steps on one workpiece is a batch of one) */
+    if (!bg->win_staged && bg->hs[0]->win_scat_threads != WSC_T) {
+        long long slices = 0;
+        bool one_form = true;
+        for (size_t i = 0; i < count; ++i) {
+            slices += std::max(0, bg->hs[i]->se - bg->hs[i]->sb);
+            one_form = one_form && !bg->hs[i]->win_staged && bg->hs[i]->win_scat_threads == bg->hs[0]->win_scat_threads && bg->hs[i]->win_ppt == bg->hs[0]->win_ppt;
+        }
+        if (one_form && !win_throughput_launch(lead, slices)) { bg->win_scat_threads = bg->hs[0]->win_scat_threads; bg->win_ppt = bg->hs[0]->win_ppt; }
+    }
+    const int scat_pts = bg->win_ppt * bg->win_scat_threads; /* points of a binning workgroup */
     for (size_t i = 0; i < count; ++i) {
         ppp_handle h = bg->hs[i];
         h->out2 = dst_dev ? dst_dev + 6 * offset_rows[i] : nullptr;
@@ -1733,11 +1811,11 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
            not publish at all (the arrival counters are a microsecond at the end of every step): the block is fetched when somebody asks */
         A.meta_host = count > 1 ? bg->hmetas->p + i : nullptr;
         h->out2 = nullptr; h->out2_cap = 0;
-        A.g_scatter = std::max(1, (A.n + bg->win_ppt * WSC_T - 1) / (bg->win_ppt * WSC_T)); /* (the members' partials are sized for 4 points per thread) */
+        A.g_scatter = std::max(1, (A.n + scat_pts - 1) / scat_pts); /* (the members' partials are sized for the largest grid of any form) */
         if (bg->win_staged) A.g_scatter = std::min(A.g_scatter, std::max(1, lead->num_cus)); /* (the staged form loops over its chunks) */
         slices_total += A.g_slice;
         /* (NB / NBc / yscale of the launch kind are set below, once the launch's total of slices is known) */
-        bg->win_scat_lds = std::max(bg->win_scat_lds, win_scatter_lds_bytes(A.S, bg->win_ppt, WSC_T, bg->win_staged));
+        bg->win_scat_lds = std::max(bg->win_scat_lds, win_scatter_lds_bytes(A.S, bg->win_ppt, bg->win_scat_threads, bg->win_staged));
         bg->win_fin_lds = std::max(bg->win_fin_lds, sizeof(int) * ((size_t)A.nkept + 2));
         bg->gx_scat = std::max(bg->gx_scat, A.g_scatter); bg->gx_slice = std::max(bg->gx_slice, A.g_slice + 1); bg->gx_wfin = std::max(bg->gx_wfin, A.g_finish);
     }
@@ -1751,7 +1829,7 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
         bg->win_threads = std::max(bg->win_threads, t);
     }
     if (getenv("PPP_WIN_DEBUG"))
-        fprintf(stderr, "[ppp] window batch: %zu members, %lld slices, threads %d, NBc %d, lds %zu B, ppt %d\n", count, slices_total, bg->win_threads, mem[0].NBc, bg->win_lds, bg->win_ppt);
+        fprintf(stderr, "[ppp] window batch: %zu members, %lld slices, threads %d, NBc %d, lds %zu B, ppt %d x %d threads\n", count, slices_total, bg->win_threads, mem[0].NBc, bg->win_lds, bg->win_ppt, bg->win_scat_threads);
     HIPCHK(lead, copy_sync(lead, bg->wmembers.p, mem.data(), sizeof(WinArgs) * count, hipMemcpyHostToDevice));
     return PPP_OK;
 }
@@ -1766,7 +1844,14 @@ static int enqueue_batched_stages(ppp_handle lead, BatchGraph *bg, hipStream_t s
     const unsigned gy = (unsigned)n;
     if (bg->win) { /* the window path: bounds + binning, the per-slice kernel, the finish -- three launches for the whole batch */
         const WinArgs *wm = bg->wmembers.p + first;
-        if (bg->win_staged && bg->win_ppt == 8) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<8, true>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
+        if (bg->win_scat_threads != WSC_T) {
+            const int rcn = with_narrow_scatter(bg->win_scat_threads, bg->win_ppt, [&](auto ppt, auto st) -> int {
+                LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<decltype(ppt)::value, false, decltype(st)::value>), dim3(bg->gx_scat, gy), decltype(st)::value, bg->win_scat_lds, wm);
+                return PPP_OK;
+            });
+            if (rcn) return rcn;
+        }
+        else if (bg->win_staged && bg->win_ppt == 8) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<8, true>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
         else if (bg->win_staged) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<4, true>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
         else if (bg->win_ppt == 8) LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<8, false>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
         else LAUNCHB(lead, strm, "k_win_scatter_b", (k_win_scatter_b<4, false>), dim3(bg->gx_scat, gy), WSC_T, bg->win_scat_lds, wm);
@@ -2643,7 +2728,8 @@ int ppp_set_side_by_side(ppp_handle h, int handles)
 {
     if (!h || handles < 1) return PPP_ERR_ARG;
     if (handles == h->side_by_side) return PPP_OK;
-    const bool changes = (handles >= 2) != (h->side_by_side >= 2);
+    const bool changes = (handles >= 2) != (h->side_by_side >= 2) ||                               /* the slice workgroup's width */
+                         (handles >= PPP_WIN_SBS_FROM) != (h->side_by_side >= PPP_WIN_SBS_FROM); /* the binning launch's form */
     h->side_by_side = handles;
     if (changes && h->have_cloud) {
         HIPCHK(h, hipSetDevice(h->device));
@@ -2677,6 +2763,17 @@ int ppp_get_fast_path(ppp_handle h, int *active)
     if (h->have_cloud) { HIPCHK(h, hipSetDevice(h->device)); int rcs = settle(h); if (rcs) return rcs; }
     if (h->have_cloud && !h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
     *active = (h->have_cloud && h->win_path) ? 1 : 0;
+    return PPP_OK;
+}
+
+int ppp_get_binning_form(ppp_handle h, int *threads, int *points_per_thread)
+{
+    if (!h || !threads || !points_per_thread) return PPP_ERR_ARG;
+    if (h->have_cloud) { HIPCHK(h, hipSetDevice(h->device)); int rcs = settle(h); if (rcs) return rcs; }
+    if (h->have_cloud && !h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
+    const bool win = h->have_cloud && h->win_path;
+    *threads = win ? h->win_scat_threads : 0;
+    *points_per_thread = win ? h->win_ppt : 0;
     return PPP_OK;
 }
 

@@ -349,6 +349,8 @@ struct ppp_handle_s {
     float win_pad = 4.f;
     int win_NBc_thr = 0; /* y-buckets per class in launches of several workgroups per CU: the most that cost no workgroup its place in the LDS */
     int win_capw = 0, win_cap_el = 0, win_NB = 0, win_NBc = 0, win_stride = 1, win_threads = 256, win_ppt = 4, win_gs = 1;
+    int win_scat_threads = WSC_T; /* threads of a binning workgroup (win_pick_scatter: narrower where passes share the device) */
+    int win_ppt_alone = 4;        /* points per thread of the 1024-thread form: what a batch falls back to whose members chose different forms */
     int win_rec_lds = 0; /* waypoint records parked in the slice workgroup's LDS (0: in global slots) */
     int win_nkept = 0, win_first_kept = 0, win_el_expect = 0;
     float win_px0 = 0.f;
@@ -390,7 +392,7 @@ struct ppp_handle_s {
        behind it -- the device checks walk length, pad, bounds and capacities against the record that pass leaves, and hands a
        pass back whose plan does not fit.  plan_deferred: that record has not been read yet (resolve_deferred does, at the first
        call that is not one of the three enqueue-only entry points). */
-    int side_by_side = 1; /* handles the caller runs side by side on this device (ppp_set_side_by_side): from two on the slice workgroups of small windows stay at 512 threads */
+    int side_by_side = 1; /* handles the caller runs side by side on this device (ppp_set_side_by_side): from two on the slice workgroups of small windows stay at 512 threads, from three on the binning launch of a large cloud takes its narrow form */
     bool plan_deferred = false, deferred_census = false;
     bool rec_current = false;   /* plan_auto holds the record of the resident cloud (it came through k_ingest_minmax and was not altered since) */
     bool plan_walk_ok = false;  /* the window plan's S, pad and plane table are the device's own, bit for bit (plan_window: census that came with the cloud, or inherited) */
@@ -491,7 +493,7 @@ struct BatchGraph {
     DevBuf<SlabArgs> members;
     bool win = false;              /* every member runs the window path: the three k_win_*_b launches */
     DevBuf<WinArgs> wmembers;
-    int win_ppt = 4, win_threads = 256, gx_scat = 1, gx_slice = 1, gx_wfin = 1;
+    int win_ppt = 4, win_scat_threads = WSC_T, win_threads = 256, gx_scat = 1, gx_slice = 1, gx_wfin = 1;
     bool win_staged = false;
     size_t win_lds = 0, win_scat_lds = 0, win_fin_lds = 0;
     DevBuf<DevMeta> metas;

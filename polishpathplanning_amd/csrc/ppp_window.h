@@ -30,15 +30,15 @@
 /* ------------------------------------------------------------------ */
 /* launch 1: bounds + window binning                                    */
 /* ------------------------------------------------------------------ */
-template <int PPT, bool STAGED>
+template <int PPT, bool STAGED, int T = WSC_T>
 __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
 {
     extern __shared__ __attribute__((aligned(16))) int s_dyn[];
     float *s_px = (float *)s_dyn;       /* S plane positions; STAGED: later the windows' places in the stage */
     int *s_cnt = s_dyn + A.S;           /* S counts, then bases */
     __shared__ int s_scr[17];
-    __shared__ float s_mn[3][WSC_T / 64], s_mx[3][WSC_T / 64];
-    __shared__ int s_n[WSC_T / 64];
+    __shared__ float s_mn[3][T / 64], s_mx[3][T / 64];
+    __shared__ int s_n[T / 64];
     const int S = A.S, n = A.n;
     const int i0 = bx * (PPT * (int)blockDim.x);
     STAMP_BEGIN();
@@ -61,11 +61,18 @@ __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
     STAMP(7, 0); /* loads issued, plane table staged */
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     int cnt = 0;
-    int pw[PPT], pr[PPT]; /* window (or -1) and rank inside this workgroup's run */
+    /* window (or -1) and rank inside this workgroup's run; from 16 points per thread on both in one word (window < WIN_S_MAX = 2^13 in
+       the upper half, rank < T * PPT <= 2^14 in the lower; -1: none), which keeps that form's 16 x 5 live words clear of scratch */
+    constexpr bool PACKED = PPT >= 16;
+    static_assert(!PACKED || (T * PPT <= 65536 && WIN_S_MAX <= 32768), "window and rank share a word");
+    int pw[PPT], pr[PACKED ? 1 : PPT];
+    auto put = [&](int k, int w, int r) { if constexpr (PACKED) pw[k] = (w << 16) | r; else { pw[k] = w; pr[k] = r; } };
+    auto win_of = [&](int k) -> int { if constexpr (PACKED) return pw[k] >> 16; else return pw[k]; };
+    auto rank_of = [&](int k) -> int { if constexpr (PACKED) return pw[k] & 0xffff; else return pr[k]; };
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const float x = p[k].x;
-        pw[k] = -1; pr[k] = 0;
+        pw[k] = -1; if constexpr (!PACKED) pr[k] = 0;
         if (x == x) {
             mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
             mn[1] = fminf(mn[1], p[k].y); mx[1] = fmaxf(mx[1], p[k].y);
@@ -79,7 +86,9 @@ __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
             const float da = fabsf(x - s_px[ja]), dj = fabsf(x - s_px[j]), db = fabsf(x - s_px[jb]);
             int w = -1;
             if (dj <= A.pad) w = j; else if (da <= A.pad) w = ja; else if (db <= A.pad) w = jb; /* windows are disjoint (plan) */
-            if (w >= A.sb && w < A.se) { pw[k] = w; pr[k] = atomicAdd(&s_cnt[w], 1); }
+            if (w >= A.sb && w < A.se) {
+                put(k, w, atomicAdd(&s_cnt[w], 1));
+            }
         }
     }
     __syncthreads();
@@ -94,8 +103,9 @@ __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             if (pw[k] >= 0) {
-                const int pos = s_cnt[pw[k]] + pr[k];
-                if (pos < A.capw) A.win_pts[(size_t)pw[k] * A.capw + pos] = p[k]; /* beyond: the slice sees count > capw and hands the run back */
+                const int w = win_of(k);
+                const int pos = s_cnt[w] + rank_of(k);
+                if (pos < A.capw) A.win_pts[(size_t)w * A.capw + pos] = p[k]; /* beyond: the slice sees count > capw and hands the run back */
             }
         }
     } else {
@@ -122,8 +132,8 @@ __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             if (pw[k] >= 0) {
-                const int q = s_loc[pw[k]] + pr[k];
-                stage[q] = p[k]; widx[q] = (u16)pw[k];
+                const int q = s_loc[win_of(k)] + rank_of(k);
+                stage[q] = p[k]; widx[q] = (u16)win_of(k);
             }
         }
         __syncthreads();
@@ -1369,19 +1379,23 @@ __global__ void __launch_bounds__(256) k_win_census_auto(const float *__restrict
 }
 
 /* ---- launch forms: single (arguments by value) and batched (blockIdx.y = member of the batch) ---- */
-template <int PPT, bool STAGED>
-__global__ void __launch_bounds__(WSC_T) k_win_scatter(WinArgs A)
+/* T: threads of a binning workgroup.  1024 for a pass that has the device to itself; 512 or 256 (plain form only) where passes share
+   it and what counts is the wave slots and registers a launch holds (win_pick_scatter) */
+template <int PPT, bool STAGED, int T>
+__global__ void __launch_bounds__(T) k_win_scatter(WinArgs A)
 {
+    static_assert(!STAGED || T == WSC_T, "the staged form is one workgroup of WSC_T threads per CU");
     if (STAGED) win_scatter_staged_loop<PPT>(A, blockIdx.x, A.g_scatter); /* g_scatter workgroups share the chunks of the cloud */
-    else win_scatter_body<PPT, false>(A, blockIdx.x);
+    else win_scatter_body<PPT, false, T>(A, blockIdx.x);
 }
-template <int PPT, bool STAGED>
-__global__ void __launch_bounds__(WSC_T) k_win_scatter_b(const WinArgs *__restrict__ mem)
+template <int PPT, bool STAGED, int T>
+__global__ void __launch_bounds__(T) k_win_scatter_b(const WinArgs *__restrict__ mem)
 {
+    static_assert(!STAGED || T == WSC_T, "the staged form is one workgroup of WSC_T threads per CU");
     const WinArgs &A = mem[blockIdx.y];
     if ((int)blockIdx.x >= A.g_scatter) return;
     if (STAGED) win_scatter_staged_loop<PPT>(A, blockIdx.x, A.g_scatter);
-    else win_scatter_body<PPT, false>(A, blockIdx.x);
+    else win_scatter_body<PPT, false, T>(A, blockIdx.x);
 }
 template <int TMAX>
 __global__ void __launch_bounds__(TMAX) k_win_slice(WinArgs A)

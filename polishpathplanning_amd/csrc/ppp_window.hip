@@ -10,6 +10,15 @@
 template __global__ void k_win_scatter<2, false>(WinArgs);
 template __global__ void k_win_scatter<4, false>(WinArgs);
 template __global__ void k_win_scatter<8, false>(WinArgs);
+/* the narrow forms of passes that share the device (win_pick_scatter) */
+template __global__ void k_win_scatter<8, false, 512>(WinArgs);
+template __global__ void k_win_scatter<16, false, 512>(WinArgs);
+template __global__ void k_win_scatter<8, false, 256>(WinArgs);
+template __global__ void k_win_scatter<16, false, 256>(WinArgs);
+template __global__ void k_win_scatter_b<8, false, 512>(const WinArgs *__restrict__);
+template __global__ void k_win_scatter_b<16, false, 512>(const WinArgs *__restrict__);
+template __global__ void k_win_scatter_b<8, false, 256>(const WinArgs *__restrict__);
+template __global__ void k_win_scatter_b<16, false, 256>(const WinArgs *__restrict__);
 template __global__ void k_win_scatter<4, true>(WinArgs);
 template __global__ void k_win_scatter<8, true>(WinArgs);
 template __global__ void k_win_scatter_b<4, false>(const WinArgs *__restrict__);

@@ -82,8 +82,8 @@ __host__ __device__ inline size_t win_scatter_lds_bytes(int S, int ppt, int thre
 #define WIN_AUTO_SCAP 4096 /* slices the LDS counters of this form have room for */
 
 /* ---- the launches (defined in ppp_window.h, instantiated in ppp_window.hip) ---- */
-template <int PPT, bool STAGED> __global__ void k_win_scatter(WinArgs A);
-template <int PPT, bool STAGED> __global__ void k_win_scatter_b(const WinArgs *__restrict__ mem);
+template <int PPT, bool STAGED, int T = WSC_T> __global__ void k_win_scatter(WinArgs A);
+template <int PPT, bool STAGED, int T = WSC_T> __global__ void k_win_scatter_b(const WinArgs *__restrict__ mem);
 template <int TMAX> __global__ void k_win_slice(WinArgs A);
 template <int TMAX> __global__ void k_win_slice_b(const WinArgs *__restrict__ mem);
 __global__ void k_win_finish(WinArgs A);
