@@ -81,6 +81,36 @@ struct TileRange {
 __host__ __device__ inline unsigned ordered_key(float f) { unsigned u; __builtin_memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __host__ __device__ inline float ordered_unkey(unsigned k) { k = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; __builtin_memcpy(&f, &k, 4); return f; }
 
+/* the largest of a wave's unsigned words, in every lane: ordered keys, counts, the bit patterns of doubles >= +0 (which order as
+   their bits do) and, for a minimum, their complements */
+template <typename U>
+__device__ inline U wave_max_bits(U v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+/* The fixed-order sum of a map's part over a workgroup of PCON_T threads (B.30, B.46): every thread hands in the sum of its
+   strided share, added in index order; the tree below adds the threads in one fixed order and leaves the result in s[0] (s:
+   PCON_T doubles of LDS).  The same tree gives the same bits; the host adds the workgroups' parts in order.  The four-argument
+   form sums a second value (s2, v2) in the same tree steps, on the same barriers; which form is compiled is fixed by the
+   overload, so the loop has no test on it.  A barrier ahead of the first read and one behind the last: the LDS writes before
+   the call are visible after it. */
+#define PCON_T 256
+template <bool TWO>
+__device__ inline void block_tree_sums(double *s, double v, double *s2, double v2)
+{
+    s[threadIdx.x] = v;
+    if (TWO) s2[threadIdx.x] = v2;
+    __syncthreads();
+    for (int o = PCON_T / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { s[threadIdx.x] += s[threadIdx.x + o]; if (TWO) s2[threadIdx.x] += s2[threadIdx.x + o]; }
+        __syncthreads();
+    }
+}
+__device__ inline void block_tree_sum(double *s, double v) { block_tree_sums<false>(s, v, nullptr, 0.0); }
+__device__ inline void block_tree_sum(double *s, double v, double *s2, double v2) { block_tree_sums<true>(s, v, s2, v2); }
+
 /* ------------------------------------------------------------------ */
 /* Coverage (path_generater::compute_coverage / get_coverage, Path_Generation.cpp:463-496, 757-771).  Every            */
 /* Area2Cloud(point, 1, 0) of compute_boundary marks the cloud points within half the x-extent of the point's contact   */
@@ -89,51 +119,68 @@ __host__ __device__ inline float ordered_unkey(unsigned k) { k = (k & 0x80000000
 /* one launch evaluates all of those balls side by side and marks their points, and a second counts the flags.         */
 /* ------------------------------------------------------------------ */
 
-/* kdtree.radiusSearch(centre, r): flags[i] = 1 for every indexed point within the ball (dist2_flann <= r2, the float
-   square of r as PCL hands it to FLANN).  All 64 lanes together; the candidates come from the y-windows of the slabs the
-   ball touches, as in wave_knn.  Points are only ever set to 1, so balls that overlap need no atomics. */
-__device__ inline void wave_mark_ball(const SlabView &V, const DynGrid &G, DynWaveLds &L, float qx, float qy, float qz, float r,
-                                      float r2, unsigned char *__restrict__ flags)
+/* The slabs and the y-buckets a ball of radius r about (qx, qy) can touch, padded against the rounding of the float
+   positions; every search of the unit over a ball's points (wave_ball_candidates, k_reg_link) begins here.  window: slab bb's
+   positions in those buckets, [a, e), a superset of the slab's points with y in the padded interval -- the caller tests the
+   distance.  s0 = slab_start[bb].  The y-bucket table is always there: make_plan allocates slab_ytab for every plan (B >= 1)
+   and no query gets as far as a launch without a plan, so there is no bisection of the slab's rows here as wave_knn has one. */
+struct BallSlabs {
+    int blo, bhi, q0, q1;
+    __device__ inline void window(const int *__restrict__ ytab, int bb, int s0, int &a, int &e) const
+    {
+        const int *T = ytab + (size_t)bb * (YTB + 1);
+        a = s0 + T[q0]; e = s0 + T[q1];
+    }
+};
+__device__ inline BallSlabs ball_slabs(const DynGrid &G, float qx, float qy, float r)
+{
+    const float pady = 1e-5f * (fabsf(qy) + r) + 1e-6f, padx = 1e-5f * (fabsf(qx) + r) + 1e-6f;
+    return BallSlabs{dyn_slab_of(G, qx - r - padx), dyn_slab_of(G, qx + r + padx), dyn_ybucket(G, qy - r - pady),
+                     dyn_ybucket(G, qy + r + pady) + 1};
+}
+
+/* The ball walk, all 64 lanes together: visit(c) for every indexed point c in the y-windows of the slabs the ball touches
+   (ball_slabs), as in wave_knn -- 64 slabs a round, a lane per slab finds its window, an exclusive prefix of the windows' sizes
+   goes to L.off and their first positions to L.w0 (all that is used of L: DynWaveLds or the small DwellWaveLds), then the lanes
+   stride over the flat positions and bisect L.off for the window of each.  A window lists a point once and the slabs' windows
+   are disjoint, so a point is visited once; which lane visits it is fixed, the order among lanes is not: visit may set flags
+   or add integers, nothing whose result depends on an order.  Wave barriers only. */
+template <typename Lds, typename Visit>
+__device__ __attribute__((always_inline)) inline void wave_ball_candidates(const SlabView &V, const DynGrid &G, Lds &L, float qx, float qy,
+                                                                          float r, Visit &&visit)
 {
     const int lane = threadIdx.x & 63;
-    const float pady = 1e-5f * (fabsf(qy) + r) + 1e-6f, padx = 1e-5f * (fabsf(qx) + r) + 1e-6f;
-    const float ylo = qy - r - pady, yhi = qy + r + pady;
-    const int blo = dyn_slab_of(G, qx - r - padx), bhi = dyn_slab_of(G, qx + r + padx);
-    const int q0 = dyn_ybucket(G, ylo), q1 = dyn_ybucket(G, yhi) + 1;
-    for (int cb = blo; cb <= bhi; cb += 64) {
+    const BallSlabs S = ball_slabs(G, qx, qy, r);
+    for (int cb = S.blo; cb <= S.bhi; cb += 64) {
         const int bb = cb + lane;
         int a = 0, e = 0;
-        if (bb <= bhi) {
-            const int s0 = V.slab_start[bb];
-            if (V.ytab) {
-                const int *T = V.ytab + (size_t)bb * (YTB + 1);
-                a = s0 + T[q0]; e = s0 + T[q1];
-            } else {
-                const int s1 = V.slab_start[bb + 1];
-                int l0 = s0, l1 = s1, u0 = s0, u1 = s1;
-                while (l0 < l1 || u0 < u1) {
-                    if (l0 < l1) { const int mid = (l0 + l1) >> 1; if (V.at(mid).y < ylo) l0 = mid + 1; else l1 = mid; }
-                    if (u0 < u1) { const int mid = (u0 + u1) >> 1; if (V.at(mid).y <= yhi) u0 = mid + 1; else u1 = mid; }
-                }
-                a = l0; e = u0 < l0 ? l0 : u0;
-            }
-        }
+        if (bb <= S.bhi) S.window(V.ytab, bb, V.slab_start[bb], a, e);
         const int cnt = e - a;
         int inc = cnt;
         for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
         const int T = __shfl(inc, 63, 64);
-        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_wave_barrier(); /* the round before has read its windows */
         L.off[lane] = inc - cnt; L.w0[lane] = a;
         __builtin_amdgcn_wave_barrier();
         __threadfence_block();
-        const int wtop = bhi - cb < 63 ? bhi - cb : 63;
+        const int wtop = S.bhi - cb < 63 ? S.bhi - cb : 63;
         for (int t = lane; t < T; t += 64) {
             int lo = 0, hi = wtop; /* the window holding flat position t */
             while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (L.off[mid] <= t) lo = mid; else hi = mid - 1; }
-            const float4 c = V.at(L.w0[lo] + (t - L.off[lo]));
-            if (dist2_flann(qx, qy, qz, c.x, c.y, c.z) <= r2) flags[idx_of(c)] = 1;
+            visit(V.at(L.w0[lo] + (t - L.off[lo])));
         }
     }
+}
+
+/* kdtree.radiusSearch(centre, r): flags[i] = 1 for every indexed point within the ball (dist2_flann <= r2, the float
+   square of r as PCL hands it to FLANN), by the ball walk.  Points are only ever set to 1, so balls that overlap need no
+   atomics. */
+__device__ inline void wave_mark_ball(const SlabView &V, const DynGrid &G, DynWaveLds &L, float qx, float qy, float qz, float r,
+                                      float r2, unsigned char *__restrict__ flags)
+{
+    wave_ball_candidates(V, G, L, qx, qy, r, [&](const float4 &c) {
+        if (dist2_flann(qx, qy, qz, c.x, c.y, c.z) <= r2) flags[idx_of(c)] = 1;
+    });
 }
 
 /* One wave per compute_boundary sample: blockIdx.y = slice, blockIdx.z = 0 the raw path (knots at raw_sc, as k_dyn_first_eval
@@ -227,8 +274,6 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(ContactIndex I, D
 /* and tests every point against the balls of the slices that reach it, k_pcon_stats reduces the count map.               */
 /* ------------------------------------------------------------------ */
 
-#define PCON_T 256
-
 /* compute_boundary's sample count on knots from miny to maxy: the first j with !(dyn_boundary_dy(j) < maxy - 2).  dy does not
    decrease with j (tool_radius > 0: the closed form is exact where it is used, the running sum rounds monotonically), so a
    doubling search and a bisection find it on the very values k_pcov_balls's loop tests.  1 << 24 = k_pcov_balls's cap. */
@@ -311,14 +356,18 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_pcon_samples(ContactIndex I,
     if (threadIdx.x < 3 && s_reach[threadIdx.x]) atomicMax(reach + 3 * i + threadIdx.x, s_reach[threadIdx.x]);
 }
 
-/* One thread per position of the slab index, PCON_T consecutive positions a round (one x-interval, a slab or two): the
-   slices whose reach, padded as wave_mark_ball pads, meets the round's x-interval are listed in LDS; for each, the point
-   bisects the slice's table for qy >= y - rmax - pad (qy does not decrease with j), walks to qy > y + rmax + pad and counts
-   the balls with dist2_flann(q, p) <= r2.  count, first and last stay in registers and are written once, at the point's
-   cloud index (idx_of); points that no ball holds keep the 0 / -1 of the memset. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
-        const int *__restrict__ off, const unsigned *__restrict__ reach, int sb, int nsl, unsigned *__restrict__ counts,
-        int *__restrict__ first, int *__restrict__ last)
+/* The point walk.  One thread per position of the slab index, PCON_T consecutive positions a round (one x-interval, a slab or
+   two): the slices whose reach, padded as ball_slabs pads, meets the round's x-interval are listed in LDS; for each, the point
+   bisects the slice's table for qy >= y - rmax - pad (qy does not decrease with j) and walks to qy > y + rmax + pad;
+   held(acc, k, j, d2, r2) for every row j, of listed slice k, whose ball holds the point (d2 = dist2_flann(q, p) <= r2), then
+   store(acc, p) once per point.  acc is the caller's Acc, made anew for every point and kept in registers; store writes it at
+   the point's cloud index (idx_of) if a ball held the point -- the caller's own test, on what it gathered, so that the walk
+   keeps no flag of its own beside the caller's count.  block_exscan lists the slices in ASCENDING order and a slice's rows are
+   walked upwards, so a point meets its balls in ascending (slice, sample) order: a float sum that held adds in that order is
+   the same in every run (B.45) -- keep the listing ordered.  All threads of the workgroup call (two barriers a round). */
+template <typename Acc, typename Held, typename Store>
+__device__ __attribute__((always_inline)) inline void pcon_walk_points(const DevMeta *m, const float4 *__restrict__ sorted4,
+        const float4 *__restrict__ tab, const int *__restrict__ off, const unsigned *__restrict__ reach, int nsl, Held &&held, Store &&store)
 {
     __shared__ int s_scan[17];
     __shared__ float s_x[2][PCON_T / 64];
@@ -337,8 +386,7 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const 
         float cmn = s_x[0][0], cmx = s_x[1][0];
         for (int w = 1; w < PCON_T / 64; ++w) { cmn = fminf(cmn, s_x[0][w]); cmx = fmaxf(cmx, s_x[1][w]); }
         const float cabs = fmaxf(fabsf(cmn), fabsf(cmx));
-        unsigned cnt = 0;
-        int fs = -1, ls = -1;
+        Acc acc;
         const float padp = 1e-5f * fabsf(p.x) + 1e-6f, padq = 1e-5f * fabsf(p.y) + 1e-6f;
         for (int b0 = 0; b0 < nsl; b0 += PCON_T) {
             const int k = b0 + threadIdx.x;
@@ -371,16 +419,25 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const 
                 for (int j = a; j < end; ++j) {
                     const float4 t = tab[j];
                     if (t.y > yhi) break;
-                    if (dist2_flann(t.x, t.y, t.z, p.x, p.y, p.z) <= t.w) {
-                        ++cnt;
-                        const int sg = sb + k2;
-                        fs = fs < 0 ? sg : min(fs, sg); ls = max(ls, sg);
-                    }
+                    const float d2 = dist2_flann(t.x, t.y, t.z, p.x, p.y, p.z);
+                    if (d2 <= t.w) held(acc, k2, j, d2, t.w);
                 }
             }
         }
-        if (have && cnt) { const int id = idx_of(p); counts[id] = cnt; first[id] = fs; last[id] = ls; }
+        if (have) store(acc, p);
     }
+}
+
+/* The count map by the point walk (pcon_walk_points): how many balls hold the point, and the first and last slice that has
+   one of them.  Points that no ball holds keep the 0 / -1 of the memset. */
+struct PconAcc { unsigned cnt = 0; int fs = -1, ls = -1; };
+__global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
+        const int *__restrict__ off, const unsigned *__restrict__ reach, int sb, int nsl, unsigned *__restrict__ counts,
+        int *__restrict__ first, int *__restrict__ last)
+{
+    pcon_walk_points<PconAcc>(m, sorted4, tab, off, reach, nsl,
+        [&](PconAcc &a, int k, int, float, float) { ++a.cnt; const int sg = sb + k; a.fs = a.fs < 0 ? sg : min(a.fs, sg); a.ls = max(a.ls, sg); },
+        [&](const PconAcc &a, const float4 &p) { if (a.cnt) { const int id = idx_of(p); counts[id] = a.cnt; first[id] = a.fs; last[id] = a.ls; } });
 }
 
 /* The statistics of the count map: bins 1 .. 63 of the histogram (bin 0 is n - covered), covered, multi_slice (last >
@@ -417,7 +474,7 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restric
         }
     }
     cov = wave_sum(cov); multi = wave_sum(multi); tot = wave_sum(tot);
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    mx = wave_max_bits(mx);
     if ((threadIdx.x & 63) == 0) {
         if (cov) { atomicAdd(&s_cov, cov); atomicAdd(&s_tot, tot); atomicMax(&s_max, mx); }
         if (multi) atomicAdd(&s_multi, multi);
@@ -625,8 +682,8 @@ __global__ void __launch_bounds__(PCON_T) k_tile_mark(const float4 *__restrict__
 
 /* The statistics of the half-width map.  Workgroup g takes the contiguous part [g per, (g + 1) per) of the map: counts and
    bins with integer atomics (per-workgroup LDS bins, then one atomic per non-empty bin, as k_pcon_stats), the smallest and
-   largest |r| as ordered keys, and the part's sum of |r| in double -- every thread its strided share in index order, then a
-   fixed tree over the threads -- to psum[g]: the host adds the parts in order, so the sum is the same in every run.
+   largest |r| as ordered keys, and the part's sum of |r| in double -- every thread its strided share in index order, then
+   block_tree_sum -- to psum[g]: the host adds the parts in order, so the sum is the same in every run.
    acc[0 .. 63] bins, [64] valid, [65] narrow (2 |r| < min_width, min_width > 0), [66] key of -min |r|, [67] key of max |r|. */
 __global__ void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict__ half_width, int n, int per, double tool_radius,
         float min_width, unsigned long long *__restrict__ acc, double *__restrict__ psum)
@@ -653,15 +710,10 @@ __global__ void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict_
         bin = bin < 0 ? 0 : (bin > PPP_CONTACT_BINS - 1 ? PPP_CONTACT_BINS - 1 : bin);
         atomicAdd(&s_bin[bin], 1);
     }
-    s_sum[threadIdx.x] = sum;
     valid = wave_sum(valid); narrow = wave_sum(narrow);
-    for (int o = 32; o > 0; o >>= 1) { klo = max(klo, (unsigned)__shfl_xor((int)klo, o, 64)); khi = max(khi, (unsigned)__shfl_xor((int)khi, o, 64)); }
+    klo = wave_max_bits(klo); khi = wave_max_bits(khi);
     if ((threadIdx.x & 63) == 0 && valid) { atomicAdd(&s_valid, valid); atomicAdd(&s_narrow, narrow); atomicMax(&s_lo, klo); atomicMax(&s_hi, khi); }
-    __syncthreads();
-    for (int o = PCON_T / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(s_sum, sum);
     if (threadIdx.x < PPP_CONTACT_BINS && s_bin[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
     if (threadIdx.x == 0) {
         psum[blockIdx.x] = s_sum[0];

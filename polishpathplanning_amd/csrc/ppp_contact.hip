@@ -226,6 +226,57 @@ int ppp_get_path_contacts(ppp_handle h, unsigned int *counts, int *first_slice, 
     return PPP_OK;
 }
 
+/* the double whose bit pattern an accumulator word holds (k_prem_range, k_dwell_stats, k_feed_stats) */
+static double bits_as_double(unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; }
+
+/* The partition of a map of N entries for a fixed-order sum (B.46, block_tree_sum): workgroup g of grid takes [g per, (g + 1) per);
+   the host adds the workgroups' parts in order */
+struct MapParts {
+    int grid, per;
+    MapParts(const ppp_handle h, size_t N)
+        : grid((int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus))), per((int)((N + grid - 1) / grid)) {}
+};
+
+static int removal_profile_ok(ppp_handle h, const char *what, int profile)
+{
+    if (profile != PPP_REMOVAL_FLAT && profile != PPP_REMOVAL_PARABOLIC && profile != PPP_REMOVAL_HERTZ)
+        return fail(h, PPP_ERR_ARG, std::string(what) + ": unknown profile (PPP_REMOVAL_FLAT, _PARABOLIC or _HERTZ)");
+    return PPP_OK;
+}
+
+/* a call that needs every slice of the walk on one handle refuses a slice-range handle */
+static int whole_walk_only(ppp_handle h, const char *what, const char *why)
+{
+    if (h->P.slice_begin != 0 || h->P.slice_end != 0 || h->ranged || h->use_part) return fail(h, PPP_ERR_UNSUPPORTED, std::string(what) + ": " + why);
+    return PPP_OK;
+}
+
+/* The point walk with the profile's weight over the handle's sample table: map[cloud index] = the sum of w * ds over the balls
+   that hold the point, held flags beside it.  The one place that picks k_prem_points's instantiation. */
+static int launch_prem_points(ppp_handle h, int profile, const double *ds, double *map)
+{
+    const auto &T = h->pcon;
+    auto points = profile == PPP_REMOVAL_FLAT ? k_prem_points<PPP_REMOVAL_FLAT>
+                : profile == PPP_REMOVAL_PARABOLIC ? k_prem_points<PPP_REMOVAL_PARABOLIC> : k_prem_points<PPP_REMOVAL_HERTZ>;
+    LAUNCH(h, "k_prem_points", points, (unsigned)std::min<size_t>((h->n + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0, h->meta.p, h->sorted4.p,
+           T.tab.p, ds, T.off.p, T.reach.p, T.tab_nsl, map, h->prem.held.p);
+    return PPP_OK;
+}
+
+/* the transposed walk of every row of the handle's sample table (k_dwell_back): num, and den where with_den.  The one place
+   that picks k_dwell_back's instantiation. */
+static int launch_dwell_back(ppp_handle h, int profile, bool with_den, const double *g, long long *num, long long *den)
+{
+    const auto &T = h->pcon;
+    auto form = [with_den](auto with, auto without) { return with_den ? with : without; };
+    auto back = profile == PPP_REMOVAL_FLAT ? form(k_dwell_back<PPP_REMOVAL_FLAT, true>, k_dwell_back<PPP_REMOVAL_FLAT, false>)
+              : profile == PPP_REMOVAL_PARABOLIC ? form(k_dwell_back<PPP_REMOVAL_PARABOLIC, true>, k_dwell_back<PPP_REMOVAL_PARABOLIC, false>)
+                                                 : form(k_dwell_back<PPP_REMOVAL_HERTZ, true>, k_dwell_back<PPP_REMOVAL_HERTZ, false>);
+    LAUNCH(h, "k_dwell_back", back, (unsigned)((T.tab_rows + DYN_WAVES - 1) / DYN_WAVES), 64 * DYN_WAVES, 0, contact_index(h), T.tab.p, T.tab_rows, g,
+           num, den);
+    return PPP_OK;
+}
+
 /* The predicted removal: the sample table of the path contacts (shared with that call when the handle holds
    one for the pass), the path length of every sample (k_prem_ds, once per pass), the point walk with the profile's weight
    (k_prem_points) and the statistics in two phases (k_prem_range, k_prem_stats); kept per (pass, profile). */
@@ -233,16 +284,16 @@ int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap,
 {
     int rc = contact_query_begin(h, "path removal");
     if (rc) return rc;
-    if (profile != PPP_REMOVAL_FLAT && profile != PPP_REMOVAL_PARABOLIC && profile != PPP_REMOVAL_HERTZ)
-        return fail(h, PPP_ERR_ARG, "path removal: unknown profile (PPP_REMOVAL_FLAT, _PARABOLIC or _HERTZ)");
+    rc = removal_profile_ok(h, "path removal", profile);
+    if (rc) return rc;
     const size_t N = h->n;
     auto &R = h->prem;
     auto &M = R.slot[profile];
     const auto &T = h->pcon;
     if (M.serial != h->pass.serial()) { /* first question about this pass with this profile */
         const size_t N1 = std::max<size_t>(N, 1);
-        const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
-        const int per = (int)((N + grid - 1) / grid);
+        const MapParts parts(h, N);
+        const int grid = parts.grid, per = parts.per;
         HIPCHK(h, M.map.ensure(N1)); HIPCHK(h, R.held.ensure(N1));
         HIPCHK(h, R.acc.ensure(PREM_ACC_WORDS)); HIPCHK(h, R.psum.ensure(2 * (size_t)grid));
         HIPCHK(h, hipMemsetAsync(M.map.p, 0, N1 * sizeof(double), h->stream));
@@ -256,10 +307,8 @@ int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap,
                 HIPCHK(h, R.ds.ensure((size_t)T.tab_rows)); HIPCHK(h, R.slice_len.ensure((size_t)T.tab_nsl));
                 LAUNCH(h, "k_prem_ds", k_prem_ds, (unsigned)T.tab_nsl, PCON_T, 0, T.tab.p, T.off.p, R.ds.p, R.slice_len.p);
             }
-            auto points = profile == PPP_REMOVAL_FLAT ? k_prem_points<PPP_REMOVAL_FLAT>
-                        : profile == PPP_REMOVAL_PARABOLIC ? k_prem_points<PPP_REMOVAL_PARABOLIC> : k_prem_points<PPP_REMOVAL_HERTZ>;
-            LAUNCH(h, "k_prem_points", points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0, h->meta.p,
-                   h->sorted4.p, T.tab.p, R.ds.p, T.off.p, T.reach.p, T.tab_nsl, M.map.p, R.held.p);
+            rc = launch_prem_points(h, profile, R.ds.p, M.map.p);
+            if (rc) return rc;
         }
         LAUNCH(h, "k_prem_range", k_prem_range, (unsigned)grid, PCON_T, 0, M.map.p, R.held.p, (int)N, R.acc.p);
         LAUNCH(h, "k_prem_stats", k_prem_stats, (unsigned)grid, PCON_T, 0, M.map.p, R.held.p, (int)N, per, R.acc.p, R.acc.p + PREM_ACC_BINS,
@@ -283,8 +332,7 @@ int ppp_get_path_removal(ppp_handle h, int profile, double *removal, size_t cap,
         }
         ppp_removal_stats st = {};
         st.n = N; st.touched = (size_t)acc[0];
-        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
-        st.max_removal = st.touched ? as_double(acc[1]) : (double)NAN; st.min_removal = st.touched ? as_double(~acc[2]) : (double)NAN;
+        st.max_removal = st.touched ? bits_as_double(acc[1]) : (double)NAN; st.min_removal = st.touched ? bits_as_double(~acc[2]) : (double)NAN;
         for (int g = 0; g < grid; ++g) { st.sum += psum[(size_t)g]; st.sum_sq += psum[(size_t)grid + g]; }
         st.path_length = R.path_length;
         for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[PREM_ACC_BINS + b];
@@ -307,13 +355,13 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
 {
     int rc = contact_query_begin(h, "path dwell");
     if (rc) return rc;
-    if (profile != PPP_REMOVAL_FLAT && profile != PPP_REMOVAL_PARABOLIC && profile != PPP_REMOVAL_HERTZ)
-        return fail(h, PPP_ERR_ARG, "path dwell: unknown profile (PPP_REMOVAL_FLAT, _PARABOLIC or _HERTZ)");
+    rc = removal_profile_ok(h, "path dwell", profile);
+    if (rc) return rc;
     if (iterations < 1 || iterations > 64) return fail(h, PPP_ERR_ARG, "path dwell: iterations must lie in [1, 64]");
     if (!(std::isfinite(dwell_min) && std::isfinite(dwell_max) && dwell_min > 0.0 && dwell_min <= 1.0 && dwell_max >= 1.0))
         return fail(h, PPP_ERR_ARG, "path dwell: the bounds must be finite with 0 < dwell_min <= 1 <= dwell_max");
-    if (h->P.slice_begin != 0 || h->P.slice_end != 0 || h->ranged || h->use_part)
-        return fail(h, PPP_ERR_UNSUPPORTED, "path dwell: neighbouring slice ranges share the points of their overlap bands: a slice-range handle cannot solve alone");
+    rc = whole_walk_only(h, "path dwell", "neighbouring slice ranges share the points of their overlap bands: a slice-range handle cannot solve alone");
+    if (rc) return rc;
     const size_t N = h->n;
     auto &D = h->dwell;
     const bool reuse = !target && D.valid && D.serial == h->pass.serial() && D.profile == profile && D.iterations == iterations &&
@@ -328,8 +376,8 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
         const auto &T = h->pcon;
         const int nrow = T.tab_rows, nsl = T.tab_nsl;
         const size_t N1 = std::max<size_t>(N, 1), R1 = (size_t)std::max(nrow, 1), touched = rs.touched;
-        const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
-        const int per = (int)((N + grid - 1) / grid);
+        const MapParts parts(h, N);
+        const int grid = parts.grid, per = parts.per;
         const unsigned gn = (unsigned)((N1 + PCON_T - 1) / PCON_T), gr = (unsigned)((R1 + PCON_T - 1) / PCON_T);
         HIPCHK(h, D.t.ensure(R1)); HIPCHK(h, D.dst.ensure(R1)); HIPCHK(h, D.num.ensure(R1)); HIPCHK(h, D.den.ensure(R1));
         HIPCHK(h, D.g.ensure(N1)); HIPCHK(h, D.map.ensure(N1)); HIPCHK(h, D.psum.ensure(2 * (size_t)grid));
@@ -365,25 +413,11 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
         if (walk) {
             HIPCHK(h, hipMemsetAsync(D.g.p, 0, N1 * sizeof(double), h->stream));
             HIPCHK(h, copy_sync(h, D.t.p, tv.data(), tv.size() * sizeof(double), hipMemcpyHostToDevice));
-            const ContactIndex I = contact_index(h);
-            const unsigned gb = (unsigned)((nrow + DYN_WAVES - 1) / DYN_WAVES);
             auto forward = [&]() -> int { /* D.map = the removal the factors predict */
                 LAUNCH(h, "k_dwell_scale", k_dwell_scale, gr, PCON_T, 0, R.ds.p, D.t.p, nrow, D.dst.p);
-                auto points = profile == PPP_REMOVAL_FLAT ? k_prem_points<PPP_REMOVAL_FLAT>
-                            : profile == PPP_REMOVAL_PARABOLIC ? k_prem_points<PPP_REMOVAL_PARABOLIC> : k_prem_points<PPP_REMOVAL_HERTZ>;
-                LAUNCH(h, "k_prem_points", points, (unsigned)std::min<size_t>((N + PCON_T - 1) / PCON_T, 1u << 20), PCON_T, 0, h->meta.p,
-                       h->sorted4.p, T.tab.p, D.dst.p, T.off.p, T.reach.p, T.tab_nsl, D.map.p, R.held.p);
-                return PPP_OK;
+                return launch_prem_points(h, profile, D.dst.p, D.map.p);
             };
-            auto back = [&](bool with_den) -> int {
-#define PPP_DWELL_BACK(P) do { if (with_den) LAUNCH(h, "k_dwell_back", (k_dwell_back<P, true>), gb, 64 * DYN_WAVES, 0, I, T.tab.p, nrow, D.g.p, D.num.p, D.den.p); \
-                               else LAUNCH(h, "k_dwell_back", (k_dwell_back<P, false>), gb, 64 * DYN_WAVES, 0, I, T.tab.p, nrow, D.g.p, D.num.p, D.den.p); } while (0)
-                if (profile == PPP_REMOVAL_FLAT) PPP_DWELL_BACK(PPP_REMOVAL_FLAT);
-                else if (profile == PPP_REMOVAL_PARABOLIC) PPP_DWELL_BACK(PPP_REMOVAL_PARABOLIC);
-                else PPP_DWELL_BACK(PPP_REMOVAL_HERTZ);
-#undef PPP_DWELL_BACK
-                return PPP_OK;
-            };
+            auto back = [&](bool with_den) { return launch_dwell_back(h, profile, with_den, D.g.p, D.num.p, D.den.p); };
             const double *cur = M.map.p; /* the forward pass at t = 1 */
             if (solve) LAUNCH(h, "k_dwell_resid", k_dwell_resid, (unsigned)grid, PCON_T, 0, cur, dtarget, level, R.held.p, (int)N, per, D.psum.p);
             for (int it = 0; solve && it < iterations; ++it) { /* no host wait in here */
@@ -427,7 +461,6 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
                 wsum += len;
             }
         }
-        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
         ppp_dwell_stats st = {};
         st.n = N; st.touched = touched; st.rows = (size_t)nrow; st.at_min = (size_t)acc[0]; st.at_max = (size_t)acc[1];
         st.iterations = iterations; st.level = level;
@@ -437,7 +470,7 @@ int ppp_get_path_dwell(ppp_handle h, int profile, const double *target, int iter
             for (int g = 0; g < grid; ++g) { before += psum[(size_t)g]; after += psum[(size_t)grid + g]; }
             st.residual_before = std::sqrt(before / (double)touched); st.residual_after = std::sqrt(after / (double)touched);
         }
-        st.max_dwell = acc[3] ? as_double(acc[2]) : (double)NAN; st.min_dwell = acc[3] ? as_double(~acc[3]) : (double)NAN;
+        st.max_dwell = acc[3] ? bits_as_double(acc[2]) : (double)NAN; st.min_dwell = acc[3] ? bits_as_double(~acc[3]) : (double)NAN;
         st.path_length = rs.path_length; st.time_factor = wsum / rs.path_length;
         D.stats = st;
         D.serial = h->pass.serial(); D.profile = profile; D.iterations = iterations; D.dmin = dwell_min; D.dmax = dwell_max;
@@ -472,8 +505,8 @@ int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int itera
     if (!(fp->accel > 0.0)) return fail(h, PPP_ERR_ARG, "path feed: accel must be > 0 (+INFINITY: no limit)");
     if (!std::isfinite(fp->end_feed)) return fail(h, PPP_ERR_ARG, "path feed: end_feed must be finite (< 0: no cap at a slice's ends)");
     if (!(std::isfinite(fp->link_feed) && fp->link_feed > 0.0)) return fail(h, PPP_ERR_ARG, "path feed: link_feed must be finite and > 0");
-    if (h->P.slice_begin != 0 || h->P.slice_end != 0 || h->ranged || h->use_part)
-        return fail(h, PPP_ERR_UNSUPPORTED, "path feed: the dwell schedule it times cannot be solved on a slice-range handle");
+    rc = whole_walk_only(h, "path feed", "the dwell schedule it times cannot be solved on a slice-range handle");
+    if (rc) return rc;
     if (h->aligned)
         return fail(h, PPP_ERR_UNSUPPORTED, "path feed: under ppp_trans2center the list's points are in the scanner's frame and the dwell rows in the aligned one");
     rc = ensure_ready(h, true, true); /* the waypoints must exist */
@@ -552,13 +585,12 @@ int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int itera
             HIPCHK(h, copy_sync(h, F.host_rows.data(), F.rows.p, W1 * sizeof(ppp_feed_row), hipMemcpyDeviceToHost));
             if (acc[0] + acc[1] + acc[2] + acc[3] != (unsigned long long)W) return fail(h, PPP_ERR_HIP, "path feed: statistics corrupt");
         }
-        auto as_double = [](unsigned long long k) { double d; memcpy(&d, &k, sizeof(d)); return d; };
         auto fixed = [](unsigned long long k, double one) { return (double)(long long)k * (1.0 / one); };
         ppp_feed_stats st = {};
         st.W = (size_t)W; st.slices = slices;
         st.by_dwell = (size_t)acc[FEED_ACC_LIMIT]; st.by_feed_max = (size_t)acc[FEED_ACC_LIMIT + 1]; st.by_end = (size_t)acc[FEED_ACC_LIMIT + 2];
         st.by_accel = (size_t)acc[FEED_ACC_LIMIT + 3];
-        st.max_feed = W ? as_double(acc[FEED_ACC_MAX]) : (double)NAN; st.min_feed = W ? as_double(~acc[FEED_ACC_NMIN]) : (double)NAN;
+        st.max_feed = W ? bits_as_double(acc[FEED_ACC_MAX]) : (double)NAN; st.min_feed = W ? bits_as_double(~acc[FEED_ACC_NMIN]) : (double)NAN;
         st.path_length = fixed(acc[FEED_ACC_PATH], FEED_LEN_FIXED); st.link_length = fixed(acc[FEED_ACC_LINK], FEED_LEN_FIXED);
         st.duration = fixed(acc[FEED_ACC_DUR], FEED_TIME_FIXED); st.duration_links = fixed(acc[FEED_ACC_DUR_LINKS], FEED_TIME_FIXED);
         st.duration_nominal = st.path_length / P.feed;
@@ -636,8 +668,8 @@ static int field_statistics(ppp_handle h, const float *hw, DevBuf<unsigned long 
                             ppp_contact_field_stats &st)
 {
     const size_t N = h->n;
-    const int grid = (int)std::max<size_t>(1, std::min<size_t>((N + PCON_T - 1) / PCON_T, 2 * (size_t)h->num_cus));
-    const int per = (int)((N + grid - 1) / grid);
+    const MapParts parts(h, N);
+    const int grid = parts.grid, per = parts.per;
     HIPCHK(h, dacc.ensure(68)); HIPCHK(h, dpsum.ensure((size_t)grid));
     HIPCHK(h, hipMemsetAsync(dacc.p, 0, 68 * sizeof(unsigned long long), h->stream));
     LAUNCH(h, "k_field_stats", k_field_stats, (unsigned)grid, PCON_T, 0, hw, (int)N, per, h->P.tool_radius, min_width, dacc.p, dpsum.p);

@@ -29,65 +29,28 @@ __global__ void __launch_bounds__(PCON_T) k_dwell_ratio(const double *__restrict
     g[i] = r > 0.0 ? fmin(fmax(tg / r, 1.0 / DWELL_G_MAX), DWELL_G_MAX) : 1.0;
 }
 
-/* the y-windows of 64 neighbouring slabs: exclusive prefix of their sizes and their first positions (what wave_mark_ball keeps
-   in DynWaveLds) */
+/* the y-windows of 64 neighbouring slabs: exclusive prefix of their sizes and their first positions -- what the ball walk
+   (wave_ball_candidates, ppp_contact.h) uses of a wave's LDS block */
 struct DwellWaveLds { int off[64], w0[64]; };
 
 /* The transposed walk of one ball, all 64 lanes together: num = the sum over the held points i of llrint((a_ij * g_i) * F),
    den = the sum of llrint(a_ij * F) (den only where WITH_DEN), a_ij = prem_weight<PROFILE>(d2, r2), held = dist2_flann <= r2
-   -- k_prem_points's pairs.  The candidates come from the y-windows of the slabs the ball touches exactly as wave_mark_ball
-   finds them (same pads, ytab where present, bisection where not); every lane adds the integers of the candidates it tests,
-   then one wave reduction: every lane returns the ball's sums.  A window lists a point once and the slabs' windows are
-   disjoint, so a pair is added once. */
+   -- k_prem_points's pairs.  The candidates are wave_ball_candidates's, the very ones wave_mark_ball tests; every lane adds the
+   integers of the candidates it tests, then one wave reduction: every lane returns the ball's sums.  The walk visits a point
+   once, so a pair is added once. */
 template <int PROFILE, bool WITH_DEN>
 __device__ inline void wave_ball_sums(const SlabView &V, const DynGrid &G, DwellWaveLds &L, float qx, float qy, float qz, float r, float r2,
                                       const double *__restrict__ g, long long &num, long long &den)
 {
-    const int lane = threadIdx.x & 63;
-    const float pady = 1e-5f * (fabsf(qy) + r) + 1e-6f, padx = 1e-5f * (fabsf(qx) + r) + 1e-6f;
-    const float ylo = qy - r - pady, yhi = qy + r + pady;
-    const int blo = dyn_slab_of(G, qx - r - padx), bhi = dyn_slab_of(G, qx + r + padx);
-    const int q0 = dyn_ybucket(G, ylo), q1 = dyn_ybucket(G, yhi) + 1;
     long long sn = 0, sd = 0;
-    for (int cb = blo; cb <= bhi; cb += 64) {
-        const int bb = cb + lane;
-        int a = 0, e = 0;
-        if (bb <= bhi) {
-            const int s0 = V.slab_start[bb];
-            if (V.ytab) {
-                const int *T = V.ytab + (size_t)bb * (YTB + 1);
-                a = s0 + T[q0]; e = s0 + T[q1];
-            } else {
-                const int s1 = V.slab_start[bb + 1];
-                int l0 = s0, l1 = s1, u0 = s0, u1 = s1;
-                while (l0 < l1 || u0 < u1) {
-                    if (l0 < l1) { const int mid = (l0 + l1) >> 1; if (V.at(mid).y < ylo) l0 = mid + 1; else l1 = mid; }
-                    if (u0 < u1) { const int mid = (u0 + u1) >> 1; if (V.at(mid).y <= yhi) u0 = mid + 1; else u1 = mid; }
-                }
-                a = l0; e = u0 < l0 ? l0 : u0;
-            }
+    wave_ball_candidates(V, G, L, qx, qy, r, [&](const float4 &c) {
+        const float d2 = dist2_flann(qx, qy, qz, c.x, c.y, c.z);
+        if (d2 <= r2) {
+            const double w = prem_weight<PROFILE>(d2, r2);
+            sn += llrint((w * g[idx_of(c)]) * DWELL_FIXED);
+            if (WITH_DEN) sd += llrint(w * DWELL_FIXED);
         }
-        const int cnt = e - a;
-        int inc = cnt;
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(inc, o, 64); if (lane >= o) inc += v; }
-        const int T = __shfl(inc, 63, 64);
-        __builtin_amdgcn_wave_barrier(); /* the round before has read its windows */
-        L.off[lane] = inc - cnt; L.w0[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        const int wtop = bhi - cb < 63 ? bhi - cb : 63;
-        for (int t = lane; t < T; t += 64) {
-            int lo = 0, hi = wtop; /* the window holding flat position t */
-            while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (L.off[mid] <= t) lo = mid; else hi = mid - 1; }
-            const float4 c = V.at(L.w0[lo] + (t - L.off[lo]));
-            const float d2 = dist2_flann(qx, qy, qz, c.x, c.y, c.z);
-            if (d2 <= r2) {
-                const double w = prem_weight<PROFILE>(d2, r2);
-                sn += llrint((w * g[idx_of(c)]) * DWELL_FIXED);
-                if (WITH_DEN) sd += llrint(w * DWELL_FIXED);
-            }
-        }
-    }
+    });
     num = wave_sum(sn);
     den = WITH_DEN ? wave_sum(sd) : 0;
 }
@@ -133,13 +96,12 @@ __global__ void __launch_bounds__(PCON_T) k_dwell_stats(const double *__restrict
         const unsigned long long k = (unsigned long long)__double_as_longlong(v);
         lo += v == dmin; hi += v == dmax; mx = max(mx, k); nmn = max(nmn, ~k);
     }
-    lo = wave_sum(lo); hi = wave_sum(hi);
-    for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o, 64)); nmn = max(nmn, __shfl_xor(nmn, o, 64)); }
+    lo = wave_sum(lo); hi = wave_sum(hi); mx = wave_max_bits(mx); nmn = wave_max_bits(nmn);
     if ((threadIdx.x & 63) == 0 && nmn) { atomicAdd(acc, lo); atomicAdd(acc + 1, hi); atomicMax(acc + 2, mx); atomicMax(acc + 3, nmn); }
 }
 
 /* The residual's sum by k_prem_stats's fixed-order scheme: workgroup g takes the contiguous part [g per, (g + 1) per) of the
-   map, every thread its strided share in index order, a fixed tree over the threads, psum[g] for the host to add in order.
+   map, every thread its strided share in index order, block_tree_sum over the threads, psum[g] for the host to add in order.
    e_i = (R_i - T_i) / level over the held points, the sum of e_i * e_i; target == nullptr: T_i = level. */
 __global__ void __launch_bounds__(PCON_T) k_dwell_resid(const double *__restrict__ removal, const double *__restrict__ target, double level,
         const unsigned char *__restrict__ held, int n, int per, double *__restrict__ psum)
@@ -152,11 +114,6 @@ __global__ void __launch_bounds__(PCON_T) k_dwell_resid(const double *__restrict
         const double e = (removal[i] - (target ? target[i] : level)) / level;
         sum += e * e;
     }
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = PCON_T / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(s_sum, sum);
     if (threadIdx.x == 0) psum[blockIdx.x] = s_sum[0];
 }

@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(PCON_T) k_feed_stats(const ppp_feed_row *__res
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) cnt[b] = wave_sum(cnt[b]);
-    for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o, 64)); nmn = max(nmn, __shfl_xor(nmn, o, 64)); }
+    mx = wave_max_bits(mx); nmn = wave_max_bits(nmn);
     if ((threadIdx.x & 63) == 0 && nmn) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) if (cnt[b]) atomicAdd(acc + FEED_ACC_LIMIT + b, cnt[b]);

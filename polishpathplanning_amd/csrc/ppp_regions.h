@@ -123,10 +123,9 @@ __device__ inline bool reg_unite(int *parent, int a, int b, int &trips)
 }
 
 /* A group of GRP lanes per selected point q (ordinal k, position pos): the y-windows of the slabs that [x - r, x + r] touches,
-   found as wave_mark_ball finds them (same pads, the y-bucket table where there is one, bisection where not), cut off at pos:
-   every selected candidate at a LOWER position with dist2_flann <= r2 is united with q, so each edge is met once.  The
-   lanes of a group stride over a window's candidates; finds and hooks are each lane's own (lock-free).  err |= 1 where a
-   walk reaches REG_TRIPS. */
+   found as the ball walk finds them (ball_slabs and its window, ppp_contact.h), cut off at pos: every selected candidate at a
+   LOWER position with dist2_flann <= r2 is united with q, so each edge is met once.  The lanes of a group stride over a
+   window's candidates; finds and hooks are each lane's own (lock-free).  err |= 1 where a walk reaches REG_TRIPS. */
 template <int GRP>
 __global__ void __launch_bounds__(REG_T) k_reg_link(const DevMeta *m, const float4 *__restrict__ sorted4, const int *__restrict__ slab_start,
         const int *__restrict__ ytab, const int *__restrict__ list, int nsel, const int *__restrict__ ord, int *parent, float r, float r2,
@@ -138,28 +137,14 @@ __global__ void __launch_bounds__(REG_T) k_reg_link(const DevMeta *m, const floa
     if (k >= nsel) return;
     const int pos = list[k];
     const float4 q = sorted4[pos];
-    const float pady = 1e-5f * (fabsf(q.y) + r) + 1e-6f, padx = 1e-5f * (fabsf(q.x) + r) + 1e-6f;
-    const float ylo = q.y - r - pady, yhi = q.y + r + pady;
-    const int blo = dyn_slab_of(G, q.x - r - padx), bhi = dyn_slab_of(G, q.x + r + padx);
-    const int q0 = dyn_ybucket(G, ylo), q1 = dyn_ybucket(G, yhi) + 1;
+    const BallSlabs S = ball_slabs(G, q.x, q.y, r);
     int trips = 0;
     bool ok = true;
-    for (int bb = blo; bb <= bhi && ok; ++bb) {
+    for (int bb = S.blo; bb <= S.bhi && ok; ++bb) {
         const int s0 = slab_start[bb];
         if (s0 >= pos) break; /* this slab and those after it lie above q */
         int a, e;
-        if (ytab) {
-            const int *T = ytab + (size_t)bb * (YTB + 1);
-            a = s0 + T[q0]; e = s0 + T[q1];
-        } else {
-            const int s1 = slab_start[bb + 1];
-            int l0 = s0, l1 = s1, u0 = s0, u1 = s1;
-            for (int it = 0; it < 32 && (l0 < l1 || u0 < u1); ++it) {
-                if (l0 < l1) { const int mid = (l0 + l1) >> 1; if (sorted4[mid].y < ylo) l0 = mid + 1; else l1 = mid; }
-                if (u0 < u1) { const int mid = (u0 + u1) >> 1; if (sorted4[mid].y <= yhi) u0 = mid + 1; else u1 = mid; }
-            }
-            a = l0; e = u0 < l0 ? l0 : u0;
-        }
+        S.window(ytab, bb, s0, a, e);
         e = e < pos ? e : pos;
         for (int c = a + sub; c < e; c += GRP) {
             const int oc = ord[c];

@@ -58,76 +58,21 @@ __device__ inline double prem_weight(float d2, float r2)
     return PROFILE == PPP_REMOVAL_PARABOLIC ? 1.0 - u : sqrt(1.0 - u);
 }
 
-/* k_pcon_points's walk with a sum in place of the count: one thread per position of the slab index, PCON_T positions a round,
-   the slices whose padded reach meets the round's x-interval listed in LDS, the slice's table bisected on qy, the exact test
-   dist2_flann(q, p) <= r2 on every candidate.  block_exscan lists the slices in ASCENDING order and a slice's rows are walked
-   upwards, so a point meets its balls in ascending (slice, sample) order: the one double accumulator adds w * ds in that
-   order and the sum is the same in every run -- keep the listing ordered.  The profile is a template parameter: the inner loop
-   has no branch on it; the division and the square root are paid per held pair, not per candidate.  One 8-byte store at the
-   point's cloud index, and held[index] = 1 (a held point's sum may be 0: a rim point, a lone sample); points that no ball
-   holds keep the zeros of the memsets. */
+/* The removal map by the point walk (pcon_walk_points, ppp_contact.h): a sum in place of k_pcon_points's count.  The walk hands
+   over a point's held pairs in ascending (slice, sample) order (see there), so the one double accumulator adds w * ds in that
+   order and the sum is the same in every run.  The profile is a template parameter: the inner loop has no branch on it; the
+   division and the square root are paid per held pair, not per candidate.  One 8-byte store at the point's cloud index, and
+   held[index] = 1 (a held point's sum may be 0: a rim point, a lone sample); points that no ball holds keep the zeros of the
+   memsets. */
+struct PremAcc { double sum = 0.0; bool hit = false; };
 template <int PROFILE>
 __global__ void __launch_bounds__(PCON_T) k_prem_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
         const double *__restrict__ ds, const int *__restrict__ off, const unsigned *__restrict__ reach, int nsl, double *__restrict__ removal,
         unsigned char *__restrict__ held)
 {
-    __shared__ int s_scan[17];
-    __shared__ float s_x[2][PCON_T / 64];
-    __shared__ int s_k[PCON_T];
-    __shared__ float4 s_sl[PCON_T]; /* lo, hi, rmax of listed slice e; w: its first table row (bits) */
-    const int total = m->n_sorted;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int c0 = blockIdx.x * PCON_T; c0 < total; c0 += gridDim.x * PCON_T) {
-        const int pi = c0 + threadIdx.x;
-        const bool have = pi < total;
-        const float4 p = have ? sorted4[pi] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float wmn = wave_min(have ? p.x : INFINITY), wmx = wave_max(have ? p.x : -INFINITY);
-        __syncthreads(); /* the round before has read its lists */
-        if (lane == 0) { s_x[0][wv] = wmn; s_x[1][wv] = wmx; }
-        __syncthreads();
-        float cmn = s_x[0][0], cmx = s_x[1][0];
-        for (int w = 1; w < PCON_T / 64; ++w) { cmn = fminf(cmn, s_x[0][w]); cmx = fmaxf(cmx, s_x[1][w]); }
-        const float cabs = fmaxf(fabsf(cmn), fabsf(cmx));
-        double sum = 0.0;
-        bool hit = false;
-        const float padp = 1e-5f * fabsf(p.x) + 1e-6f, padq = 1e-5f * fabsf(p.y) + 1e-6f;
-        for (int b0 = 0; b0 < nsl; b0 += PCON_T) {
-            const int k = b0 + threadIdx.x;
-            int take = 0;
-            float lo = 0.f, hi = 0.f, rm = 0.f;
-            if (k < nsl) {
-                const unsigned kh = reach[3 * k + 1];
-                if (kh) {
-                    lo = -ordered_unkey(reach[3 * k]); hi = ordered_unkey(kh); rm = ordered_unkey(reach[3 * k + 2]);
-                    const float pad = 1e-5f * (cabs + rm) + 1e-6f;
-                    take = (lo - pad <= cmx && hi + pad >= cmn) ? 1 : 0;
-                }
-            }
-            int nt;
-            const int at = block_exscan(take, s_scan, &nt);
-            if (take) { s_k[at] = k; s_sl[at] = make_float4(lo, hi, rm, __int_as_float(off[k])); }
-            __syncthreads();
-            if (!have) continue;
-            for (int e = 0; e < nt; ++e) {
-                const float4 sl = s_sl[e];
-                const float rm2 = sl.z;
-                const float padx = padp + 1e-5f * rm2;
-                if (p.x < sl.x - padx || p.x > sl.y + padx) continue;
-                const float ry = rm2 + padq + 1e-5f * rm2;
-                const float ylo = p.y - ry, yhi = p.y + ry;
-                int a = __float_as_int(sl.w), z = off[s_k[e] + 1];
-                const int end = z;
-                while (a < z) { const int mid = (a + z) >> 1; if (tab[mid].y < ylo) a = mid + 1; else z = mid; }
-                for (int j = a; j < end; ++j) {
-                    const float4 t = tab[j];
-                    if (t.y > yhi) break;
-                    const float d2 = dist2_flann(t.x, t.y, t.z, p.x, p.y, p.z);
-                    if (d2 <= t.w) { hit = true; sum += prem_weight<PROFILE>(d2, t.w) * ds[j]; }
-                }
-            }
-        }
-        if (have && hit) { const int id = idx_of(p); removal[id] = sum; held[id] = 1; }
-    }
+    pcon_walk_points<PremAcc>(m, sorted4, tab, off, reach, nsl,
+        [&](PremAcc &a, int, int j, float d2, float r2) { a.hit = true; a.sum += prem_weight<PROFILE>(d2, r2) * ds[j]; },
+        [&](const PremAcc &a, const float4 &p) { if (a.hit) { const int id = idx_of(p); removal[id] = a.sum; held[id] = 1; } });
 }
 
 /* The accumulators of the removal statistics: [0] touched, [1] the largest removal of a touched point as its bit pattern (a
@@ -151,8 +96,7 @@ __global__ void __launch_bounds__(PCON_T) k_prem_range(const double *__restrict_
         const unsigned long long k = (unsigned long long)__double_as_longlong(removal[i]);
         ++cnt; hi = max(hi, k); nlo = max(nlo, ~k);
     }
-    cnt = wave_sum(cnt);
-    for (int o = 32; o > 0; o >>= 1) { hi = max(hi, __shfl_xor(hi, o, 64)); nlo = max(nlo, __shfl_xor(nlo, o, 64)); }
+    cnt = wave_sum(cnt); hi = wave_max_bits(hi); nlo = wave_max_bits(nlo);
     if ((threadIdx.x & 63) == 0 && cnt) { atomicAdd(&s_a[0], cnt); atomicMax(&s_a[1], hi); atomicMax(&s_a[2], nlo); }
     __syncthreads();
     if (threadIdx.x == 0 && s_a[0]) { atomicAdd(acc, s_a[0]); atomicMax(acc + 1, s_a[1]); atomicMax(acc + 2, s_a[2]); }
@@ -161,7 +105,7 @@ __global__ void __launch_bounds__(PCON_T) k_prem_range(const double *__restrict_
 /* second phase, behind the first: the histogram against the maximum (range[1]; min(63, floor(removal / max * 63)) in double,
    everything in bin 0 when the maximum is 0) with per-workgroup LDS bins and one integer atomic per non-empty bin, and the
    sums as k_field_stats adds them: workgroup g takes the contiguous part [g per, (g + 1) per) of the map, every thread its
-   strided share in index order, a fixed tree over the threads, psum[g] / psq[g] for the host to add in order. */
+   strided share in index order, block_tree_sum over the threads, psum[g] / psq[g] for the host to add in order. */
 __global__ void __launch_bounds__(PCON_T) k_prem_stats(const double *__restrict__ removal, const unsigned char *__restrict__ held, int n, int per,
         const unsigned long long *range, unsigned long long *bins, double *__restrict__ psum, double *__restrict__ psq)
 {
@@ -180,12 +124,7 @@ __global__ void __launch_bounds__(PCON_T) k_prem_stats(const double *__restrict_
         if (mx > 0.0) { bin = (int)floor(r / mx * (double)(PPP_CONTACT_BINS - 1)); bin = bin > PPP_CONTACT_BINS - 1 ? PPP_CONTACT_BINS - 1 : bin; }
         atomicAdd(&s_bin[bin], 1);
     }
-    s_sum[threadIdx.x] = sum; s_sq[threadIdx.x] = sq;
-    __syncthreads();
-    for (int o = PCON_T / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s_sum[threadIdx.x] += s_sum[threadIdx.x + o]; s_sq[threadIdx.x] += s_sq[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    block_tree_sum(s_sum, sum, s_sq, sq);
     if (threadIdx.x < PPP_CONTACT_BINS && s_bin[threadIdx.x]) atomicAdd(bins + threadIdx.x, (unsigned long long)s_bin[threadIdx.x]);
     if (threadIdx.x == 0) { psum[blockIdx.x] = s_sum[0]; psq[blockIdx.x] = s_sq[0]; }
 }
