@@ -6,7 +6,9 @@
 // min / max removal and cv with the Hertzian profile); PPP_PATH_DWELL=1 prints what a feed schedule could do about it (the dwell
 // factors' range, the residual before and after, the time factor); PPP_PATH_FEED=1 times the list (the waypoints by what limits
 // their feed, the feed's range, the duration) and writes <pathFile>.feed, pathFile's columns with t and feed; PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
-// regions, PPP_GAPS_MIN points or more each).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
+// regions, PPP_GAPS_MIN points or more each).  PPP_DEVIATION=<reference.pcd> loads the nominal (or pre-process) cloud into a second planner and prints where the
+// planned cloud, the scan, stands proud of it (points by status, the deviation's range, mean and rms; PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN set the
+// parameters); with PPP_PATH_DWELL=1 or PPP_PATH_FEED=1 the schedule steers towards that target.  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -34,6 +36,11 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
+    const char *devf = std::getenv("PPP_DEVIATION");
+    if (devf && devf[0]) { /* before the schedules: they take its target */
+        path_generater reference = {configFile, devf};
+        path_planner.get_deviation(reference);
+    }
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fed = std::getenv("PPP_PATH_FEED");

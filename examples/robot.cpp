@@ -2,7 +2,8 @@
 // (robot_path.h:58-98) but nothing constructs it -- the header does not compile upstream -- so this is the shape of
 // src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths,
 // PPP_PATH_CONTACTS=1 their contact counts, PPP_PATH_REMOVAL=1 the predicted removal, PPP_PATH_DWELL=1 a dwell schedule
-// towards a uniform removal, PPP_PATH_FEED=1 the timed feed schedule of the list (written to <pathFile>.feed), PPP_GAPS=1 the regions they leave uncovered.
+// towards a uniform removal, PPP_PATH_FEED=1 the timed feed schedule of the list (written to <pathFile>.feed), PPP_GAPS=1 the regions they leave uncovered,
+// PPP_DEVIATION=<reference.pcd> the deviation of the cloud against that reference (its target goes to PPP_PATH_DWELL / PPP_PATH_FEED).
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -33,6 +34,11 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
+    const char *devf = std::getenv("PPP_DEVIATION");
+    if (devf && devf[0]) { /* before the schedules: they take its target */
+        RobotPath reference(configFile, devf, radius);
+        path_planner.get_deviation(reference);
+    }
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fed = std::getenv("PPP_PATH_FEED");

@@ -396,6 +396,59 @@ int ppp_get_path_feed(ppp_handle h, int profile, const double *target, int itera
 void ppp_default_feed_params(ppp_feed_params *fp);   /* 20, 30, 100, 0, 100 */
 /* "x y z r p y t feed " per line: ppp_write_path_file's six columns and format, then t and feed (host only) */
 int ppp_write_feed_file(const char *path, const float *wp6, const ppp_feed_row *rows, size_t W);
+/* The deviation map of a scan against a reference cloud: for every point of h's resident cloud (the
+   scan) its signed distance to the surface of ref's resident cloud (the nominal part, or the scan before the process), that
+   distance locally averaged, and a target map that ppp_get_path_dwell and ppp_get_path_feed accept as it is.  p_i is resident
+   point i of h, q_j resident point j of ref: the floats each handle holds after its own x1000 and preprocessing.  The two
+   clouds are taken as registered in one frame: registration is out of scope.  n_j is row j of ppp_estimate_normals(ref),
+   oriented to ref's viewpoint.
+     nearest    d2(i, j) = ((dx dx) + dy dy) + dz dz in float; j*(i) is the indexed point of ref with the smallest (d2, j): a tie
+                goes to the lower cloud index.  md2 = max_dist * max_dist in float (+INFINITY: no limit).
+     status     PPP_DEV_DROPPED if p_i is not finite; PPP_DEV_TOO_FAR if ref indexes no point or d2(i, j*) > md2 (a point at
+                exactly md2 matches); PPP_DEV_NO_NORMAL if n_j* has a NaN; otherwise PPP_DEV_MATCHED
+     ref_index  j* for MATCHED and NO_NORMAL, -1 otherwise
+     deviation  MATCHED points: ((ex nx) + ey ny) + ez nz in double, ex = (double)p.x - (double)q.x and so on: positive where the
+                scan lies on the viewpoint's side of the reference surface -- material to take off.  NaN for every other point.
+     smoothed   smooth_radius > 0, MATCHED points: N_i = the MATCHED points k of h with d2(p_i, p_k) <= smooth_radius *
+                smooth_radius (the float product; i itself belongs to it); ((double)(the sum over N_i of llrint(deviation_k 2^24),
+                in signed 64-bit integers) / (double)|N_i|) 2^-24.  NaN for every other point.  smooth_radius == 0: deviation.
+     target     gain (v_i - allowance) where that difference is > 0, else +0, v_i = smoothed[i]; +0 for every point that is not
+                MATCHED: all entries finite and >= 0
+   stats: n = cloud->size() of h; the points by status; proud / below = MATCHED points with v > allowance / v < 0; min_dev /
+   max_dev over v (-0 below +0); mean_dev = ((double)(the integer sum of llrint(v_i 2^24)) / (double)matched) 2^-24; rms_dev =
+   sqrt(S / matched), S the sum of v_i v_i in the fixed order of ppp_removal_stats' sums; target_sum likewise; max_dist2 = the
+   largest float d2 of a MATCHED point; hist[b] = MATCHED points with b = min(63, max(0, (int)floor((v / span + 1) 32))), span =
+   max(|min_dev|, |max_dev|), all in bin 32 when span == 0.  NaN for the six numbers when nothing is matched.  Integer sums and
+   minima over (d2, j) have no order: every map and every statistic is the same bits in every run.
+   Needs clouds and parameters, not a pass.  Builds each handle's slab index, and ref's normal field, where they are missing, as
+   ppp_get_contact_field does; a window-path handle stays on the window path.  Waits for ref's stream, runs on h's stream and
+   blocks until the results are on the host.  Every call computes again (ref may have changed) and touches no result of the
+   other contact calls.  Each map receives its first min(cap, n) entries; every output may be NULL, cap = 0 asks for the
+   statistics alone.  h == ref is allowed: every matched deviation is then 0.
+   PPP_ERR_ARG: dp or ref NULL; max_dist not > 0 (NaN included); smooth_radius negative or not finite; allowance not finite;
+   gain negative or not finite; no cloud on either handle; handles on different devices; smooth_radius > 0 with a max_dist that
+   is not finite or with (double)max_dist 2^24 n >= 2^62 (the integer sum could overflow).  PPP_ERR_UNSUPPORTED when either
+   handle is a slice-range handle (slice_begin / slice_end) or a part handle (ppp_set_cloud_part). */
+enum { PPP_DEV_MATCHED = 0, PPP_DEV_TOO_FAR = 1, PPP_DEV_NO_NORMAL = 2, PPP_DEV_DROPPED = 3 };
+typedef struct {
+    float  max_dist;       /* mm, resident units: > 0 finite, or +INFINITY for no limit */
+    float  smooth_radius;  /* mm: 0 = no smoothing; else > 0 finite */
+    double allowance;      /* mm, finite: deviation that is left standing */
+    double gain;           /* finite, >= 0: target units per mm of excess */
+} ppp_deviation_params;
+typedef struct {
+    size_t n, matched, too_far, no_normal, dropped;
+    size_t proud, below;                 /* matched points with v > allowance ; with v < 0 */
+    double min_dev, max_dev;             /* over v of the matched points; NaN when matched == 0 */
+    double mean_dev, rms_dev;            /* see above */
+    float  max_dist2;                    /* largest float d2 of a matched point; NaN when none */
+    double target_sum;
+    size_t hist[PPP_CONTACT_BINS];
+} ppp_deviation_stats;
+void ppp_default_deviation_params(ppp_deviation_params *dp);   /* +INFINITY, 0, 0, 1 */
+int  ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp,
+                       double *deviation, double *smoothed, int *ref_index, unsigned char *status,
+                       double *target, size_t cap, ppp_deviation_stats *stats);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

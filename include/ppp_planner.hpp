@@ -368,10 +368,12 @@ public:
     /* two lines on path_dwell() with the Hertzian profile, a uniform target and the default rounds and bounds: the rows, the
        smallest and the largest factor and how many rows ended on a bound, then what the schedule buys -- the rms of (removal -
        target) / level before and after -- and what it costs: the time along the path against the unit feed */
-    void print_path_dwell()
+    void print_path_dwell() { print_path_dwell(nullptr); }
+    /* the same towards a target map (deviation()'s, one value per cloud point); nullptr: the uniform target */
+    void print_path_dwell(const std::vector<double> *target)
     {
         ppp_dwell_stats st = {};
-        if (!path_dwell(st)) st = ppp_dwell_stats{};
+        if (!path_dwell(st, PPP_REMOVAL_HERTZ, target)) st = ppp_dwell_stats{};
         const bool any = st.min_dwell == st.min_dwell;
         std::printf("dwell: %zu samples, factor %f to %f, %zu at the lower and %zu at the upper bound\n", st.rows, any ? st.min_dwell : 1.0,
                     any ? st.max_dwell : 1.0, st.at_min, st.at_max);
@@ -398,14 +400,15 @@ public:
     }
     /* three lines on path_feed() with the default feed parameters, the Hertzian profile, a uniform target and the default
        rounds and bounds: the waypoints by what limits their feed, the feed's range and the lengths, then the duration against
-       the nominal one; with feed_file the list's six columns, t and feed go to that file (ppp_write_feed_file) */
-    void print_path_feed(const char *feed_file = nullptr)
+       the nominal one; with feed_file the list's six columns, t and feed go to that file (ppp_write_feed_file); with target
+       (deviation()'s map) the dwell schedule steers towards it */
+    void print_path_feed(const char *feed_file = nullptr, const std::vector<double> *target = nullptr)
     {
         ppp_feed_params fp;
         ppp_default_feed_params(&fp);
         ppp_feed_stats st = {};
         std::vector<ppp_feed_row> rows;
-        if (!path_feed(st, fp, feed_file ? &rows : nullptr)) { st = ppp_feed_stats{}; rows.clear(); }
+        if (!path_feed(st, fp, feed_file ? &rows : nullptr, PPP_REMOVAL_HERTZ, target)) { st = ppp_feed_stats{}; rows.clear(); }
         const bool any = st.W > 0;
         std::printf("feed: %zu waypoints on %zu slices: %zu limited by the dwell, %zu by feed_max, %zu by end_feed, %zu by the acceleration\n", st.W,
                     st.slices, st.by_dwell, st.by_feed_max, st.by_end, st.by_accel);
@@ -418,6 +421,50 @@ public:
         int rc = ppp_get_waypoints(h_, wp6.data(), st.W, &W);
         if (rc != PPP_OK) { report(rc); return; }
         if (W == st.W && ppp_write_feed_file(feed_file, wp6.data(), rows.data(), W) == PPP_OK) std::cout << "File saved: " << feed_file << std::endl;
+    }
+    /* the deviation map of this planner's cloud, the scan, against the cloud of ref (ppp_get_deviation: per scan point the
+       signed distance to the reference surface within dp.max_dist, its mean over dp.smooth_radius, and the target gain *
+       max(v - allowance, 0); needs no pass; the two clouds are taken as registered in one frame): the statistics and, when
+       asked for, the target by cloud index -- what path_dwell() and path_feed() take as it is -- and the smoothed deviation.
+       Every call computes again: ask for the maps at once */
+    bool deviation(const Planner &ref, ppp_deviation_stats &st, const ppp_deviation_params &dp, std::vector<double> *target = nullptr,
+                   std::vector<double> *smoothed = nullptr, std::vector<unsigned char> *status = nullptr)
+    {
+        size_t n = 0;
+        int rc = (target || smoothed || status) ? ppp_num_points(h_, &n) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (target) target->assign(n, 0.0);
+            if (smoothed) smoothed->assign(n, 0.0);
+            if (status) status->assign(n, (unsigned char)PPP_DEV_DROPPED);
+            rc = ppp_get_deviation(h_, ref.h_, &dp, nullptr, smoothed ? smoothed->data() : nullptr, nullptr, status ? status->data() : nullptr,
+                                   target ? target->data() : nullptr, n, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* ppp_default_deviation_params with what the environment sets of PPP_DEVIATION_MAXDIST, PPP_DEVIATION_SMOOTH,
+       PPP_DEVIATION_ALLOWANCE and PPP_DEVIATION_GAIN (the example programs' knobs) */
+    static ppp_deviation_params deviation_params_env()
+    {
+        ppp_deviation_params dp;
+        ppp_default_deviation_params(&dp);
+        if (const char *v = std::getenv("PPP_DEVIATION_MAXDIST")) dp.max_dist = (float)std::atof(v);
+        if (const char *v = std::getenv("PPP_DEVIATION_SMOOTH")) dp.smooth_radius = (float)std::atof(v);
+        if (const char *v = std::getenv("PPP_DEVIATION_ALLOWANCE")) dp.allowance = std::atof(v);
+        if (const char *v = std::getenv("PPP_DEVIATION_GAIN")) dp.gain = std::atof(v);
+        return dp;
+    }
+    /* three lines on deviation(): the scan's points by status, the deviation's range, mean and rms, and the points that stand
+       proud of the allowance with the target's sum; the target goes to *target when given */
+    void print_deviation(const Planner &ref, const ppp_deviation_params &dp, std::vector<double> *target = nullptr)
+    {
+        ppp_deviation_stats st = {};
+        if (!deviation(ref, st, dp, target)) { st = ppp_deviation_stats{}; if (target) target->clear(); }
+        const bool any = st.matched > 0;
+        std::printf("deviation: %zu points: %zu matched, %zu too far, %zu without a normal, %zu dropped\n", st.n, st.matched, st.too_far, st.no_normal,
+                    st.dropped);
+        std::printf("deviation: %f to %f mm, mean %f, rms %f\n", any ? st.min_dev : 0.0, any ? st.max_dev : 0.0, any ? st.mean_dev : 0.0,
+                    any ? st.rms_dev : 0.0);
+        std::printf("deviation: %zu points proud of %f mm, %zu below the reference, target sum %f\n", st.proud, dp.allowance, st.below, st.target_sum);
     }
     const char *path_file() const { return cfg_.path_file; }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact

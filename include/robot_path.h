@@ -52,11 +52,16 @@ public:
     void get_path_removal() { planner.print_path_removal(); }
     /* what a feed schedule could do about it: a dwell factor per sample towards a uniform removal -- the factors' range, the
        residual before and after, the time factor (ppp_get_path_dwell) */
-    void get_path_dwell() { planner.print_path_dwell(); }
+    void get_path_dwell() { planner.print_path_dwell(deviation_target.empty() ? nullptr : &deviation_target); }
     /* a timed feed schedule for the WayPointsList (needs getPath()): the dwell factor, the feed under a cap and an acceleration
        limit and the time per waypoint -- the waypoints by what limits them, the feed's range, the duration; writes
        <pathFile>.feed: pathFile's columns, then t and feed (ppp_get_path_feed, ppp_write_feed_file) */
-    void get_path_feed() { planner.print_path_feed((std::string(planner.path_file()) + ".feed").c_str()); }
+    void get_path_feed() { planner.print_path_feed((std::string(planner.path_file()) + ".feed").c_str(), deviation_target.empty() ? nullptr : &deviation_target); }
+    /* where this planner's cloud, the scan, stands proud of the cloud of ref (the nominal part, or the scan before the process;
+       both registered in one frame): the scan's points by status, the deviation's range, mean and rms, the proud points
+       (ppp_get_deviation; max_dist, smooth_radius, allowance and gain from PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN).
+       Needs no pass.  The target map is kept: get_path_dwell() and get_path_feed() after it steer the removal towards it */
+    void get_deviation(const RobotPath &ref) { planner.print_deviation(ref.planner, ppp::Planner::deviation_params_env(), &deviation_target); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }
@@ -66,6 +71,7 @@ public:
 
 private:
     ppp::Planner planner;
+    std::vector<double> deviation_target; /* get_deviation()'s target map; empty: a uniform target */
     std::vector<Spline> Path_set;
     std::string cloud_name;
     std::vector<std::vector<float>> WayPointsList;

@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h and ppp_feed.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h and ppp_deviation.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -13,6 +13,7 @@
 #include "ppp_removal.h"
 #include "ppp_dwell.h"
 #include "ppp_feed.h"
+#include "ppp_deviation.h"
 #include <cstring>
 
 extern "C" {
@@ -732,6 +733,108 @@ int ppp_get_contact_field(ppp_handle h, float *curv5, float *half_width, size_t 
     const size_t k = std::min(cap, N);
     if (curv5 && k) HIPCHK(h, copy_sync(h, curv5, C.curv.p, 5 * k * sizeof(float), hipMemcpyDeviceToHost));
     if (half_width && k) HIPCHK(h, copy_sync(h, half_width, C.hw.p, k * sizeof(float), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+void ppp_default_deviation_params(ppp_deviation_params *dp)
+{
+    if (!dp) return;
+    dp->max_dist = INFINITY; dp->smooth_radius = 0.f; dp->allowance = 0.0; dp->gain = 1.0;
+}
+
+/* a handle of ppp_get_deviation, scan or reference: a cloud, all of it, its slab index complete.  Refusals and errors are
+   reported on h (the scan's handle, the call's first argument), whichever handle they are about */
+static int deviation_side(ppp_handle h, ppp_handle side, const char *who)
+{
+    const std::string w = std::string("deviation: ") + who;
+    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
+    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
+    if (side->P.slice_begin != 0 || side->P.slice_end != 0) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
+    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
+    if (side->ranged || side->use_part) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
+    const int ns = side->hmeta.n_sorted;
+    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
+    return PPP_OK;
+}
+
+/* The deviation map: the reference's index and normal field on its own stream, one wait for that stream, then
+   k_dev_nearest, k_dev_smooth where asked, k_dev_target and k_dev_stats back to back on the scan's stream, and one wait. */
+int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, double *deviation, double *smoothed, int *ref_index,
+                      unsigned char *status, double *target, size_t cap, ppp_deviation_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !dp) return fail(h, PPP_ERR_ARG, "deviation: no reference handle or no parameters");
+    const ppp_deviation_params P = *dp;
+    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, "deviation: max_dist must be > 0 (+INFINITY: no limit)");
+    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, "deviation: smooth_radius must be finite and >= 0");
+    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, "deviation: allowance must be finite");
+    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, "deviation: gain must be finite and >= 0");
+    const bool smooth = P.smooth_radius > 0.f;
+    if (smooth && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, "deviation: smoothing needs a finite max_dist");
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "deviation: the two handles are on different devices");
+    int rc = deviation_side(h, ref, "the reference");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side(h, h, "the scan"); if (rc) return rc; }
+    const size_t N = h->n;
+    /* the integer sum of a neighbourhood or of the statistics: |deviation| <= about max_dist, n terms of it in 2^-24 mm */
+    if (smooth && (double)P.max_dist * DEV_FIXED * (double)N >= 4611686018427387904.0)
+        return fail(h, PPP_ERR_ARG, "deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    rc = contact_buffers(ref); /* the normal field, on ref's stream */
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("deviation: the reference: ") + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    const MapParts parts(h, N);
+    const int grid = parts.grid, per = parts.per, nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS)); HIPCHK(h, D.psum.ensure(2 * (size_t)grid));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    HIPCHK(h, hipMemsetAsync(D.status.p, PPP_DEV_DROPPED, N1, h->stream)); /* points outside the index: not finite */
+    HIPCHK(h, hipMemsetAsync(D.ref_index.p, 0xff, N1 * sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEV_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    const unsigned gq = (unsigned)((nq + DEV_T - 1) / DEV_T);
+    if (nq > 0) {
+        LAUNCH(h, "k_dev_nearest", k_dev_nearest, gq, DEV_T, 0, h->sorted4.p, nq, contact_index(ref), nref, P.max_dist * P.max_dist, D.dev.p, D.fix.p,
+               D.d2.p, D.ref_index.p, D.status.p);
+        if (smooth)
+            LAUNCH(h, "k_dev_smooth", k_dev_smooth, gq, DEV_T, 0, contact_index(h), nq, P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p,
+                   D.smoothed.p);
+    }
+    LAUNCH(h, "k_dev_target", k_dev_target, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, 2 * (size_t)h->num_cus), DEV_T, 0, D.status.p,
+           D.dev.p, v, D.d2.p, (int)N, P.allowance, P.gain, D.target.p, D.acc.p);
+    LAUNCH(h, "k_dev_stats", k_dev_stats, (unsigned)grid, PCON_T, 0, D.status.p, v, D.target.p, (int)N, per, D.acc.p, D.psum.p, D.psum.p + grid);
+    unsigned long long acc[DEV_ACC_WORDS];
+    std::vector<double> psum(2 * (size_t)grid);
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, psum.data(), D.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc[0] + acc[1] + acc[2] + acc[3] != N || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
+        return fail(h, PPP_ERR_HIP, "deviation: statistics corrupt");
+    if (stats) {
+        ppp_deviation_stats st = {};
+        const size_t m = (size_t)acc[0];
+        st.n = N; st.matched = m; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2]; st.dropped = (size_t)acc[3];
+        st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
+        double sq = 0.0;
+        for (int g = 0; g < grid; ++g) { sq += psum[(size_t)g]; st.target_sum += psum[(size_t)grid + g]; }
+        st.min_dev = st.max_dev = st.mean_dev = st.rms_dev = (double)NAN; st.max_dist2 = NAN;
+        if (m) {
+            st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
+            st.mean_dev = (double)(long long)acc[DEV_ACC_FIXSUM] / (double)m * (1.0 / DEV_FIXED);
+            st.rms_dev = std::sqrt(sq / (double)m);
+            st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
+        }
+        for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[DEV_ACC_BINS + b];
+        *stats = st;
+    }
+    const size_t k = std::min(cap, N);
+    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
+    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

@@ -275,6 +275,17 @@ struct ppp_handle_s {
         std::vector<ppp_feed_row> host_rows;
         ppp_feed_stats stats = {};
     } feed;
+    /* deviation of this handle's cloud against another handle's (ppp_get_deviation): by cloud index the deviation, its local
+       mean, its fixed-point term, the float d2, the reference index, the status and the target; the statistics' accumulators and
+       the workgroups' parts of the two fixed-order sums.  Nothing is kept between calls: the reference may have changed. */
+    struct Deviation {
+        DevBuf<double> dev, smoothed, target, psum;
+        DevBuf<long long> fix;
+        DevBuf<float> d2;
+        DevBuf<int> ref_index;
+        DevBuf<unsigned char> status;
+        DevBuf<unsigned long long> acc;
+    } deviation;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -169,6 +169,9 @@ def lib():
         L.ppp_default_feed_params.argtypes = [C.POINTER(FeedParams)]
         L.ppp_default_feed_params.restype = None
         L.ppp_write_feed_file.argtypes = [C.c_char_p, fp, C.POINTER(FeedRow), sz]
+        L.ppp_default_deviation_params.argtypes = [C.POINTER(DeviationParams)]
+        L.ppp_default_deviation_params.restype = None
+        L.ppp_get_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, ip, C.POINTER(C.c_ubyte), dp, sz, C.POINTER(DeviationStats)]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -349,6 +352,21 @@ class FeedStats(C.Structure):
                 ("by_end", C.c_size_t), ("by_accel", C.c_size_t), ("min_feed", C.c_double), ("max_feed", C.c_double),
                 ("path_length", C.c_double), ("link_length", C.c_double), ("duration", C.c_double),
                 ("duration_links", C.c_double), ("duration_nominal", C.c_double)]
+
+
+DEV_MATCHED, DEV_TOO_FAR, DEV_NO_NORMAL, DEV_DROPPED = range(4)  # PPP_DEV_*
+
+
+class DeviationParams(C.Structure):
+    """ppp_deviation_params"""
+    _fields_ = [("max_dist", C.c_float), ("smooth_radius", C.c_float), ("allowance", C.c_double), ("gain", C.c_double)]
+
+
+class DeviationStats(C.Structure):
+    """ppp_deviation_stats"""
+    _fields_ = [("n", C.c_size_t), ("matched", C.c_size_t), ("too_far", C.c_size_t), ("no_normal", C.c_size_t), ("dropped", C.c_size_t),
+                ("proud", C.c_size_t), ("below", C.c_size_t), ("min_dev", C.c_double), ("max_dev", C.c_double), ("mean_dev", C.c_double),
+                ("rms_dev", C.c_double), ("max_dist2", C.c_float), ("target_sum", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
 
 
 class ContactFieldStats(C.Structure):
@@ -980,6 +998,36 @@ class Engine:
             rows = rows[:min(W, st.W)]
         stats = {k: getattr(st, k) for k, _ in FeedStats._fields_}
         return rows, stats
+
+    def deviation(self, ref, max_dist=float("inf"), smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(deviation float64[n], smoothed float64[n], ref_index int32[n], status uint8[n], target float64[n], stats dict) of this
+        engine's cloud, the scan, against the cloud of the engine `ref` (ppp_get_deviation): per scan point the signed distance
+        to the reference surface along the normal of its nearest reference point within max_dist mm (positive: on the
+        viewpoint's side, material to take off), that distance averaged over the matched scan points within smooth_radius mm
+        (0: none), and target = gain * max(smoothed - allowance, 0), which path_dwell() and path_feed() take as it is.  status:
+        DEV_MATCHED, DEV_TOO_FAR, DEV_NO_NORMAL, DEV_DROPPED; the maps are NaN (ref_index -1, target 0) where it is not
+        DEV_MATCHED.  Needs clouds, not a pass; the two clouds are taken as registered in one frame.  stats: n, matched, too_far,
+        no_normal, dropped, proud, below, min_dev, max_dev, mean_dev, rms_dev, max_dist2, target_sum, hist (CONTACT_BINS counts
+        over [-span, span]).  maps=False returns five Nones and stats"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = DeviationStats()
+        dev = sm = idx = status = target = None
+        if not maps:
+            self._chk(self.L.ppp_get_deviation(self.h, ref.h, C.byref(dp), None, None, None, None, None, 0, C.byref(st)))
+        else:
+            # every call computes again: one call sized by the resident cloud (preprocessing may have changed its size)
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            dev, sm, target = (np.zeros(max(n, 1), np.float64) for _ in range(3))
+            idx = np.zeros(max(n, 1), np.int32)
+            status = np.zeros(max(n, 1), np.uint8)
+            self._chk(self.L.ppp_get_deviation(self.h, ref.h, C.byref(dp), _d(dev), _d(sm), _i(idx), status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                               _d(target), n, C.byref(st)))
+            dev, sm, idx, status, target = dev[:n], sm[:n], idx[:n], status[:n], target[:n]
+        stats = {k: getattr(st, k) for k, _ in DeviationStats._fields_ if k != "hist"}
+        stats["hist"] = np.array(st.hist[:], np.int64)
+        return dev, sm, idx, status, target, stats
 
     def contact_field(self, maps=True, min_width=0.0):
         """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every
