@@ -8,10 +8,13 @@
 // their feed, the feed's range, the duration) and writes <pathFile>.feed, pathFile's columns with t and feed; PPP_GAPS=1 prints where they leave the workpiece untouched (the uncovered points as connected
 // regions, PPP_GAPS_MIN points or more each).  PPP_DEVIATION=<reference.pcd> loads the nominal (or pre-process) cloud into a second planner and prints where the
 // planned cloud, the scan, stands proud of it (points by status, the deviation's range, mean and rms; PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN set the
-// parameters); with PPP_PATH_DWELL=1 or PPP_PATH_FEED=1 the schedule steers towards that target.  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
+// parameters); with PPP_PATH_DWELL=1 or PPP_PATH_FEED=1 the schedule steers towards that target.  PPP_REGISTER=1 beside it
+// registers the scan to that reference first (point-to-plane ICP from the identity: pairs, rms before and after, steps, locked unknowns and T are printed;
+// PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP), before the path is planned and before the deviation is taken.  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include "Path_Generate_Algorithm.h"
 
 int main(int argc, char **argv)
@@ -28,6 +31,11 @@ int main(int argc, char **argv)
     const char *cfg = std::getenv("PPP_CONFIG");
     std::string configFile = cfg ? cfg : "../config.txt";
     path_generater path_planner = {configFile, pcd};
+    const char *devf = std::getenv("PPP_DEVIATION");
+    std::unique_ptr<path_generater> reference;
+    if (devf && devf[0]) reference.reset(new path_generater{configFile, devf});
+    const char *reg = std::getenv("PPP_REGISTER");
+    if (reference && reg && reg[0] == '1') path_planner.register_to(*reference); /* before the plan: it moves the cloud */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");
@@ -36,11 +44,7 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
-    const char *devf = std::getenv("PPP_DEVIATION");
-    if (devf && devf[0]) { /* before the schedules: they take its target */
-        path_generater reference = {configFile, devf};
-        path_planner.get_deviation(reference);
-    }
+    if (reference) path_planner.get_deviation(*reference); /* before the schedules: they take its target */
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fed = std::getenv("PPP_PATH_FEED");

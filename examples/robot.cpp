@@ -3,10 +3,12 @@
 // src/connect.cpp with the three-argument constructor.  PPP_PATH_COVERAGE=1 prints the coverage rate of the planned paths,
 // PPP_PATH_CONTACTS=1 their contact counts, PPP_PATH_REMOVAL=1 the predicted removal, PPP_PATH_DWELL=1 a dwell schedule
 // towards a uniform removal, PPP_PATH_FEED=1 the timed feed schedule of the list (written to <pathFile>.feed), PPP_GAPS=1 the regions they leave uncovered,
-// PPP_DEVIATION=<reference.pcd> the deviation of the cloud against that reference (its target goes to PPP_PATH_DWELL / PPP_PATH_FEED).
+// PPP_DEVIATION=<reference.pcd> the deviation of the cloud against that reference (its target goes to PPP_PATH_DWELL / PPP_PATH_FEED);
+// PPP_REGISTER=1 beside it registers the cloud to that reference first, before the path is planned (pairs, rms before and after, steps, locked unknowns, T).
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include "ppp_planner.hpp"
 #include "robot_path.h"
 
@@ -26,6 +28,11 @@ int main(int argc, char **argv)
     const char *cfg = std::getenv("PPP_CONFIG");
     std::string configFile = cfg ? cfg : "../config.txt";
     RobotPath path_planner(configFile, pcd, radius);
+    const char *devf = std::getenv("PPP_DEVIATION");
+    std::unique_ptr<RobotPath> reference;
+    if (devf && devf[0]) reference.reset(new RobotPath(configFile, devf, radius));
+    const char *reg = std::getenv("PPP_REGISTER");
+    if (reference && reg && reg[0] == '1') path_planner.register_to(*reference); /* before the plan: it moves the cloud */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");
@@ -34,11 +41,7 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
-    const char *devf = std::getenv("PPP_DEVIATION");
-    if (devf && devf[0]) { /* before the schedules: they take its target */
-        RobotPath reference(configFile, devf, radius);
-        path_planner.get_deviation(reference);
-    }
+    if (reference) path_planner.get_deviation(*reference); /* before the schedules: they take its target */
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fed = std::getenv("PPP_PATH_FEED");

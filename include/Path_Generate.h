@@ -86,6 +86,11 @@ public:
        (ppp_get_deviation; max_dist, smooth_radius, allowance and gain from PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN).
        Needs no pass.  The target map is kept: get_path_dwell() and get_path_feed() after it steer the removal towards it */
     void get_deviation(const path_generater &ref) { planner.print_deviation(ref.planner, ppp::Planner::deviation_params_env(), &deviation_target); }
+    /* this planner's cloud, the scan, registered to the cloud of ref by point-to-plane ICP from the identity (ppp_register;
+       max_dist, iterations and min_step from PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP): prints the pairs and the rms before
+       and after, the steps, the locked unknowns and T, and moves the cloud by T when the loop converged (ppp_transform_cloud:
+       plan again afterwards).  ICP needs a start within the basin: a fixturing error, not an unknown pose */
+    void register_to(const path_generater &ref) { planner.print_registration(ref.planner, ppp::Planner::registration_params_env()); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }

@@ -449,6 +449,84 @@ void ppp_default_deviation_params(ppp_deviation_params *dp);   /* +INFINITY, 0, 
 int  ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp,
                        double *deviation, double *smoothed, int *ref_index, unsigned char *status,
                        double *target, size_t cap, ppp_deviation_stats *stats);
+/* Registration of a scan to a reference cloud: point-to-plane ICP.  h holds the scan, ref the nominal
+   cloud (or the scan before the process); the result T = (R | t), row-major 3 x 4 in double, carries a resident point of h into
+   ref's frame.  ppp_get_deviation does not register; these calls do, and ppp_transform_cloud applies their result.  ICP is a
+   local method: it needs a start T0 within the basin of the answer -- a fixturing error of millimetres and a few degrees, not
+   an unknown pose; a global (coarse) alignment is the caller's.  Everything below is + - * / in double with one rounding per
+   written operation, and integers wherever a sum has no fixed order: the same bits in every run.
+     centre     mn, mx = ppp_minmax(ref); c[d] = ((double)mn[d] + (double)mx[d]) * 0.5; e = (double)mx - (double)mn;
+                Ln = (((ex + ey) + ez) * 0.5) + (double)max_dist
+     shift      min(40, 60 - clog2(max(2, n)) - clog2(max(1, ceil((double)(max_dist * max_dist))))), the product in float, n =
+                cloud->size() of h, clog2(x) the smallest e with 2^e >= x; the fixed point is 2^shift
+     moved      p an indexed (finite) point of h: p'[r] = ((T[4r] px + T[4r+1] py) + T[4r+2] pz) + T[4r+3]; the query is (float)p';
+                a query that is not finite is no pair
+     pair       j* = the nearest indexed point of ref to the query under ppp_get_deviation's rule (float d2, a point at exactly
+                max_dist * max_dist matches, a tie goes to the lower index); a pair where j* exists and row j* of
+                ppp_estimate_normals(ref), n, has no NaN
+     terms      e = p' - (double)q; r = ((ex nx) + ey ny) + ez nz; u[d] = (p'[d] - c[d]) / Ln; a = (uy nz - uz ny, uz nx - ux nz,
+                ux ny - uy nx); J = (a, n); A_ik += llrint((J_i J_k) 2^shift), b_i += llrint((J_i r) 2^shift),
+                E += llrint((r r) 2^shift), pairs += 1
+     solve      M = (double)A, g = -(double)b, big = the largest M_ii; LDL^T in index order: v = M_ii - (the sum over the
+                unlocked k < i, ascending, from 0, of (L_ik L_ik) d_k); !(v > lock_eps big) locks i: x_i = 0 and i takes no part
+                in any later sum; else d_i = v, L_ji = (M_ji - the sum over the unlocked k < i of (L_jk L_ik) d_k) / v;
+                z_i = g_i - the sum of L_ik z_k; x_i = z_i / d_i - the sum over the unlocked k > i, ascending, of L_ki x_k
+     no step    from an evaluation with pairs < 6 or all six unknowns locked (the loop ends, converged = 0), and from one whose
+                six b are all zero with pairs >= 6 (T is a stationary point: the loop ends, converged = 1)
+     step       w = x[0..2] / Ln, h = w * 0.5, s = (hx hx + hy hy) + hz hz, dR = ((1 - s) I + 2 h h^T + 2 [h]x) / (1 + s) (Cayley's
+                form, every entry (diagonal + 2 (h_i h_j) +- 2 h_k) / (1 + s)), dt = x[3..5]; R' = dR R, each entry
+                ((a0 b0) + a1 b1) + a2 b2; t' = (dR (t - c) + c) + dt; step2 = max((x0 x0 + x1 x1) + x2 x2, (x3 x3 + x4 x4) + x5 x5);
+                the loop ends after a step with step2 < min_step * min_step (converged = 1), else after `iterations` steps
+   ppp_get_registration_terms evaluates once at T12 (NULL: the identity) and takes no step: *row is that evaluation (locked 63,
+   step2 NaN); stats has n, indexed, shift, centre, length, T = T12, steps = converged = locked = 0 and the row's numbers in both
+   the _before and the _after fields.  ppp_register runs the loop from T0_12 (NULL: the identity): rows[k] holds the terms at T_k
+   for k = 0 .. steps, the last of them the evaluation at the result (locked 63, step2 NaN); the first min(row_cap, steps + 1)
+   rows are copied, rows may be NULL with row_cap = 0; stats.locked is the OR of the masks of the rows a step was taken from.
+   Both build each handle's slab index and ref's normal field where they are missing, wait once for ref's stream, enqueue the
+   whole chain (iterations + 1 evaluations, iterations steps, no host round trip per iteration) on h's stream and wait once.
+   Neither changes either handle's cloud, plan or any stored contact result.  h == ref is allowed: row 0 has b = 0 and E = 0.
+   row, rows and stats may be NULL.  PPP_ERR_ARG: rp or ref NULL; rows NULL with row_cap > 0; max_dist not finite and > 0, or its float
+   square not finite; iterations outside [1, 64]; min_step not finite and >= 0; lock_eps outside (0, 1); a T entry that is not
+   finite; no cloud on either handle; handles on different devices; shift < 16 (the integer sums could overflow).
+   PPP_ERR_UNSUPPORTED when either handle is a slice-range handle or a part handle. */
+typedef struct {
+    float  max_dist;     /* mm, resident units: finite, > 0: a scan point pairs with a reference point within it */
+    int    iterations;   /* at most this many steps: 1 .. 64 */
+    double min_step;     /* mm, finite, >= 0: stop once a step moves nothing farther than this */
+    double lock_eps;     /* in (0, 1): pivot rule of the solve, see below */
+} ppp_registration_params;                       /* defaults: 2, 30, 1e-6, 1e-9 */
+
+typedef struct {
+    double    T[12];     /* row-major 3 x 4 (R | t): the transform the terms were taken at */
+    size_t    pairs;
+    long long A[21];     /* upper triangle of J^T J, row-major (00 01 .. 05 11 12 .. 55), fixed point */
+    long long b[6];      /* J^T r */
+    long long E;         /* r^T r */
+    int       locked;    /* bit i: unknown i took no step here (pivot rule); 63 on a row no step was taken from */
+    double    step2;     /* max(|scaled rotation|^2, |translation|^2) of the step taken from here; NaN: none */
+} ppp_registration_row;
+
+typedef struct {
+    size_t n, indexed;                  /* scan: cloud->size(), finite points */
+    int    steps, converged, locked;    /* steps taken; step2 < min_step^2 reached; OR of the rows' masks */
+    int    shift;                       /* the fixed point is 2^shift */
+    double centre[3], length;           /* c and Ln below */
+    double T[12];                       /* the result: scan -> reference frame */
+    size_t pairs_before, pairs_after;
+    double rms_before, rms_after;       /* sqrt((double)E 2^-shift / pairs) at T0 and at T; NaN when pairs == 0 */
+} ppp_registration_stats;
+
+void ppp_default_registration_params(ppp_registration_params *rp);
+int  ppp_get_registration_terms(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12,
+                                ppp_registration_row *row, ppp_registration_stats *stats);
+int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0_12,
+                  ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats);
+/* T applied to the resident cloud: T12 (row-major 3 x 4, NULL: the identity) is rounded to float and every finite point
+   becomes m0 x + (m1 y + (m2 z + m3)) per row, pcl::transformPointCloud's arithmetic; a point that is not finite passes
+   unchanged.  The cloud has changed: bounds, plan, index and every stored result are withdrawn, as after ppp_trans2center.
+   Does not set the alignment of ppp_trans2center.  PPP_ERR_ARG: no cloud, a slice-range or part handle (the preprocessing
+   calls' refusals), a handle under ppp_trans2center, a T entry that is not finite. */
+int  ppp_transform_cloud(ppp_handle h, const double *T12);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

@@ -466,6 +466,53 @@ public:
                     any ? st.rms_dev : 0.0);
         std::printf("deviation: %zu points proud of %f mm, %zu below the reference, target sum %f\n", st.proud, dp.allowance, st.below, st.target_sum);
     }
+    /* point-to-plane ICP of this planner's cloud, the scan, to the cloud of ref (ppp_register): st.T carries a scan
+       point into ref's frame -- transform_cloud(st.T) applies it; rows, when asked for, receives the evaluations at T_0 .. T_steps.
+       Started at T0 (3 x 4 row-major, nullptr: the identity): ICP needs a start within the basin of the answer.  Needs no pass
+       and changes neither cloud */
+    bool register_to(const Planner &ref, ppp_registration_stats &st, const ppp_registration_params &rp, const double *T0 = nullptr,
+                     std::vector<ppp_registration_row> *rows = nullptr)
+    {
+        if (rows) rows->assign((size_t)(rp.iterations > 0 ? rp.iterations : 0) + 1, ppp_registration_row{});
+        int rc = ppp_register(h_, ref.h_, &rp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, &st);
+        if (rc != PPP_OK) { if (rows) rows->clear(); return report(rc); }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* the resident cloud moved by T (ppp_transform_cloud; 3 x 4 row-major in double): plan and results are withdrawn, as after
+       any change of the cloud; the normals estimate_normal() left are the old cloud's and are dropped */
+    bool transform_cloud(const double *T12)
+    {
+        int rc = ppp_transform_cloud(h_, T12);
+        normals_.clear();
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* ppp_default_registration_params with what the environment sets of PPP_REGISTER_MAXDIST, PPP_REGISTER_ITERATIONS and
+       PPP_REGISTER_MINSTEP (the example programs' knobs) */
+    static ppp_registration_params registration_params_env()
+    {
+        ppp_registration_params rp;
+        ppp_default_registration_params(&rp);
+        if (const char *v = std::getenv("PPP_REGISTER_MAXDIST")) rp.max_dist = (float)std::atof(v);
+        if (const char *v = std::getenv("PPP_REGISTER_ITERATIONS")) rp.iterations = std::atoi(v);
+        if (const char *v = std::getenv("PPP_REGISTER_MINSTEP")) rp.min_step = std::atof(v);
+        return rp;
+    }
+    /* register_to() from the identity, five lines on it -- the pairs and the rms of the point-to-plane residual before and
+       after, the steps with what ended them and the locked unknowns, the three rows of T -- and, with apply, the cloud moved by
+       T when the loop converged.  Returns whether the cloud was moved */
+    bool print_registration(const Planner &ref, const ppp_registration_params &rp, bool apply = true)
+    {
+        ppp_registration_stats st = {};
+        const bool ran = register_to(ref, st, rp);
+        if (!ran) st = ppp_registration_stats{};
+        std::printf("registration: %zu of %zu points paired, rms %f mm; after %d steps %zu paired, rms %f mm\n", st.pairs_before, st.indexed,
+                    st.pairs_before ? st.rms_before : 0.0, st.steps, st.pairs_after, st.pairs_after ? st.rms_after : 0.0);
+        std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",
+                    st.converged ? "converged" : (ran && st.steps == rp.iterations ? "out of iterations" : "no step possible"), st.locked);
+        for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
+        return ran && apply && st.converged && transform_cloud(st.T);
+    }
     const char *path_file() const { return cfg_.path_file; }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
        ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below

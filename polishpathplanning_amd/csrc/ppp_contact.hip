@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h and ppp_deviation.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map, the registration, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h, ppp_deviation.h and ppp_registration.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -14,6 +14,7 @@
 #include "ppp_dwell.h"
 #include "ppp_feed.h"
 #include "ppp_deviation.h"
+#include "ppp_registration.h"
 #include <cstring>
 
 extern "C" {
@@ -744,9 +745,9 @@ void ppp_default_deviation_params(ppp_deviation_params *dp)
 
 /* a handle of ppp_get_deviation, scan or reference: a cloud, all of it, its slab index complete.  Refusals and errors are
    reported on h (the scan's handle, the call's first argument), whichever handle they are about */
-static int deviation_side(ppp_handle h, ppp_handle side, const char *who)
+static int deviation_side(ppp_handle h, ppp_handle side, const char *who, const char *what = "deviation")
 {
-    const std::string w = std::string("deviation: ") + who;
+    const std::string w = std::string(what) + ": " + who;
     if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
     if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
     if (side->P.slice_begin != 0 || side->P.slice_end != 0) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
@@ -836,6 +837,117 @@ int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *
     if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
     if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
     return PPP_OK;
+}
+
+void ppp_default_registration_params(ppp_registration_params *rp)
+{
+    if (!rp) return;
+    rp->max_dist = 2.f; rp->iterations = 30; rp->min_step = 1e-6; rp->lock_eps = 1e-9;
+}
+
+/* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
+   then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
+   transforms, the sums and the rows stay on the device, a chain that has ended turns the rest of its launches into returns --
+   and one wait.  !loop: the one evaluation of ppp_get_registration_terms. */
+static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0, bool loop,
+                              ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !rp) return fail(h, PPP_ERR_ARG, "registration: no reference handle or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "registration: rows is NULL with row_cap > 0");
+    const ppp_registration_params P = *rp;
+    IcpFrame F;
+    F.md2 = P.max_dist * P.max_dist;
+    if (!(P.max_dist > 0.f && std::isfinite(P.max_dist) && std::isfinite(F.md2)))
+        return fail(h, PPP_ERR_ARG, "registration: max_dist must be finite and > 0 (and so its float square)");
+    if (P.iterations < 1 || P.iterations > 64) return fail(h, PPP_ERR_ARG, "registration: iterations must be in [1, 64]");
+    if (!(P.min_step >= 0.0 && std::isfinite(P.min_step))) return fail(h, PPP_ERR_ARG, "registration: min_step must be finite and >= 0");
+    if (!(P.lock_eps > 0.0 && P.lock_eps < 1.0)) return fail(h, PPP_ERR_ARG, "registration: lock_eps must be in (0, 1)");
+    const int iterations = loop ? P.iterations : 0;
+    double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    if (T0) memcpy(T, T0, sizeof(T));
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return fail(h, PPP_ERR_ARG, "registration: the transform has an entry that is not finite");
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration: the two handles are on different devices");
+    int rc = deviation_side(h, ref, "the reference", "registration");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side(h, h, "the scan", "registration"); if (rc) return rc; }
+    rc = fetch_meta(ref);
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
+    const size_t N = h->n;
+    const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    const int shift = icp_shift(N, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    double ext[3];
+    for (int d = 0; d < 3; ++d) {
+        F.c[d] = ((double)ref->hmeta.mn[d] + (double)ref->hmeta.mx[d]) * 0.5;
+        ext[d] = (double)ref->hmeta.mx[d] - (double)ref->hmeta.mn[d];
+    }
+    F.Ln = (((ext[0] + ext[1]) + ext[2]) * 0.5) + (double)P.max_dist;
+    F.scale = std::ldexp(1.0, shift);
+    F.lock_eps = P.lock_eps; F.min_step2 = P.min_step * P.min_step;
+    rc = contact_buffers(ref); /* the normal field, on ref's stream */
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    static_assert(sizeof(IcpCtl) == 5 * sizeof(int), "IcpCtl is five ints");
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ICP_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * evals * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
+    /* grid-stride: the workgroups, and with them the atomics of an evaluation, are capped by the device, not by the cloud */
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
+    for (int k = 0; k <= iterations; ++k) {
+        LAUNCH(h, "k_reg_terms", k_reg_terms, grid, ICP_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
+               G.acc.p + ICP_WORDS * (size_t)k);
+        if (k < iterations)
+            LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, G.acc.p + ICP_WORDS * (size_t)k, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    IcpCtl C;
+    HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
+    if (C.steps < 0 || C.steps > iterations || (!C.done && C.steps != iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
+    const size_t last = (size_t)C.steps;
+    std::vector<ppp_registration_row> R(last + 1);
+    HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    if (!C.done) { /* the evaluation behind the last step: no step kernel follows it */
+        unsigned long long acc[ICP_WORDS];
+        double Tl[12];
+        HIPCHK(h, copy_sync(h, acc, G.acc.p + ICP_WORDS * last, sizeof(acc), hipMemcpyDeviceToHost));
+        HIPCHK(h, copy_sync(h, Tl, G.T.p + 12 * last, sizeof(Tl), hipMemcpyDeviceToHost));
+        icp_row_terms(&R[last], Tl, acc);
+    }
+    if (R[0].pairs > (size_t)std::max(nq, 0) || R[last].pairs > (size_t)std::max(nq, 0)) return fail(h, PPP_ERR_HIP, "registration: sums corrupt");
+    if (stats) {
+        ppp_registration_stats st = {};
+        st.n = N; st.indexed = (size_t)nq;
+        st.steps = C.steps; st.converged = C.converged; st.locked = C.locked; st.shift = shift;
+        for (int d = 0; d < 3; ++d) st.centre[d] = F.c[d];
+        st.length = F.Ln;
+        memcpy(st.T, R[last].T, sizeof(st.T));
+        auto rms = [&](const ppp_registration_row &r) {
+            return r.pairs ? std::sqrt(std::ldexp((double)r.E, -shift) / (double)r.pairs) : (double)NAN;
+        };
+        st.pairs_before = R[0].pairs; st.rms_before = rms(R[0]);
+        st.pairs_after = R[last].pairs; st.rms_after = rms(R[last]);
+        *stats = st;
+    }
+    const size_t k = std::min(row_cap, last + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    return PPP_OK;
+}
+
+int ppp_get_registration_terms(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                               ppp_registration_stats *stats)
+{
+    return registration_chain(h, ref, rp, T12, false, row, row ? 1 : 0, stats);
+}
+
+int ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0_12, ppp_registration_row *rows, size_t row_cap,
+                 ppp_registration_stats *stats)
+{
+    return registration_chain(h, ref, rp, T0_12, true, rows, row_cap, stats);
 }
 
 /* What this handle's tile evaluates and owns, behind a plan: the cuts of its range [sb, se) on the walk of the

@@ -286,6 +286,15 @@ struct ppp_handle_s {
         DevBuf<unsigned char> status;
         DevBuf<unsigned long long> acc;
     } deviation;
+    /* registration of this handle's cloud to another handle's (ppp_get_registration_terms, ppp_register): the chain's transforms
+       (12 doubles each), the 29 integer sums of every evaluation, the rows and the control words (IcpCtl, as ints).  Nothing is
+       kept between calls. */
+    struct Registration {
+        DevBuf<double> T;
+        DevBuf<unsigned long long> acc;
+        DevBuf<ppp_registration_row> rows;
+        DevBuf<int> ctl;
+    } registration;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */
     struct ContactField {

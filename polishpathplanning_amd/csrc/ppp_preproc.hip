@@ -1,5 +1,5 @@
 /*
- * ppp_preproc.hip -- the preprocessing calls of the C ABI (include/ppp_hip.h) on the resident cloud: ppp_trans2center,
+ * ppp_preproc.hip -- the preprocessing calls of the C ABI (include/ppp_hip.h) on the resident cloud: ppp_trans2center, ppp_transform_cloud,
  * ppp_remove_outlier, ppp_voxel_down, ppp_smooth_mls, and what they share (the opening, the adoption of the filtered cloud,
  * the sensor-frame copy of an aligned cloud).  The unit owns the kernels of ppp_preproc.h and ppp_align.h; of the handle and
  * the plan it sees what ppp_handle.h declares.  Compiled with the engine's flags.
@@ -125,6 +125,27 @@ int ppp_trans2center(ppp_handle h, float *trans_align16, float *centroid3, float
     LAUNCH(h, "k_transform_se3", k_transform_se3, gb, 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->aligned = true;
+    h->drop_graph();
+    return cloud_changed(h);
+}
+
+/* T applied to the resident cloud (the result of ppp_register): pcl::transformPointCloud's arithmetic with the float of T, in
+   place, then what ppp_trans2center does behind its own transform -- but the cloud is not "aligned": no TransAlign is kept */
+int ppp_transform_cloud(ppp_handle h, const double *T12)
+{
+    int rc = preproc_begin(h);
+    if (rc) return rc;
+    if (h->aligned) return fail(h, PPP_ERR_ARG, "transform_cloud: the cloud is aligned (ppp_trans2center): its sensor-frame copy would not follow");
+    Mat34 M = {{{1.f, 0.f, 0.f, 0.f}, {0.f, 1.f, 0.f, 0.f}, {0.f, 0.f, 1.f, 0.f}}};
+    if (T12)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                if (!std::isfinite(T12[4 * r + c])) return fail(h, PPP_ERR_ARG, "transform_cloud: the transform has an entry that is not finite");
+                M.m[r][c] = (float)T12[4 * r + c];
+            }
+    const int n = (int)h->n;
+    if (n) LAUNCH(h, "k_transform_se3", k_transform_se3, (unsigned)((n + 255) / 256), 256, 0, h->X.p, h->Y.p, h->Z.p, n, M, h->X.p, h->Y.p, h->Z.p);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->drop_graph();
     return cloud_changed(h);
 }

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_transform_cloud", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -172,6 +172,11 @@ def lib():
         L.ppp_default_deviation_params.argtypes = [C.POINTER(DeviationParams)]
         L.ppp_default_deviation_params.restype = None
         L.ppp_get_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, ip, C.POINTER(C.c_ubyte), dp, sz, C.POINTER(DeviationStats)]
+        L.ppp_default_registration_params.argtypes = [C.POINTER(RegistrationParams)]
+        L.ppp_default_registration_params.restype = None
+        L.ppp_get_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
+        L.ppp_register.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
+        L.ppp_transform_cloud.argtypes = [vp, dp]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -367,6 +372,44 @@ class DeviationStats(C.Structure):
     _fields_ = [("n", C.c_size_t), ("matched", C.c_size_t), ("too_far", C.c_size_t), ("no_normal", C.c_size_t), ("dropped", C.c_size_t),
                 ("proud", C.c_size_t), ("below", C.c_size_t), ("min_dev", C.c_double), ("max_dev", C.c_double), ("mean_dev", C.c_double),
                 ("rms_dev", C.c_double), ("max_dist2", C.c_float), ("target_sum", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+class RegistrationParams(C.Structure):
+    """ppp_registration_params"""
+    _fields_ = [("max_dist", C.c_float), ("iterations", C.c_int), ("min_step", C.c_double), ("lock_eps", C.c_double)]
+
+
+class RegistrationRow(C.Structure):
+    """ppp_registration_row"""
+    _fields_ = [("T", C.c_double * 12), ("pairs", C.c_size_t), ("A", C.c_longlong * 21), ("b", C.c_longlong * 6), ("E", C.c_longlong),
+                ("locked", C.c_int), ("step2", C.c_double)]
+
+
+class RegistrationStats(C.Structure):
+    """ppp_registration_stats"""
+    _fields_ = [("n", C.c_size_t), ("indexed", C.c_size_t), ("steps", C.c_int), ("converged", C.c_int), ("locked", C.c_int),
+                ("shift", C.c_int), ("centre", C.c_double * 3), ("length", C.c_double), ("T", C.c_double * 12),
+                ("pairs_before", C.c_size_t), ("pairs_after", C.c_size_t), ("rms_before", C.c_double), ("rms_after", C.c_double)]
+
+
+def _registration_row(r):
+    """a RegistrationRow as a dict: T float64[3, 4], pairs, A int64[21], b int64[6], E, locked, step2"""
+    return dict(T=np.array(r.T[:], np.float64).reshape(3, 4), pairs=int(r.pairs), A=np.array(r.A[:], np.int64), b=np.array(r.b[:], np.int64),
+                E=int(r.E), locked=int(r.locked), step2=float(r.step2))
+
+
+def _registration_stats(st):
+    out = {k: getattr(st, k) for k, _ in RegistrationStats._fields_}
+    out["centre"] = np.array(st.centre[:], np.float64)
+    out["T"] = np.array(st.T[:], np.float64).reshape(3, 4)
+    return out
+
+
+def _t12(T):
+    """a 3 x 4 (or 4 x 4: its first three rows) transform as 12 doubles for the library; None stays None: the identity"""
+    if T is None:
+        return None
+    return np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
 
 
 class ContactFieldStats(C.Structure):
@@ -1028,6 +1071,37 @@ class Engine:
         stats = {k: getattr(st, k) for k, _ in DeviationStats._fields_ if k != "hist"}
         stats["hist"] = np.array(st.hist[:], np.int64)
         return dev, sm, idx, status, target, stats
+
+    def registration_terms(self, ref, T=None, max_dist=2.0, lock_eps=1e-9):
+        """(row, stats) of one evaluation of the point-to-plane terms of this engine's cloud, the scan, moved by T (3 x 4, None:
+        the identity), against the cloud of the engine `ref` (ppp_get_registration_terms): row = dict(T, pairs, A int64[21] the
+        upper triangle of J^T J, b int64[6], E, locked 63, step2 NaN) in fixed point 2^stats["shift"]; no step is taken"""
+        rp = RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps))
+        row, st = RegistrationRow(), RegistrationStats()
+        t = _t12(T)
+        self._chk(self.L.ppp_get_registration_terms(self.h, ref.h, C.byref(rp), None if t is None else _d(t), C.byref(row), C.byref(st)))
+        return _registration_row(row), _registration_stats(st)
+
+    def register(self, ref, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+        """(T float64[3, 4], rows, stats): point-to-plane ICP of this engine's cloud, the scan, to the cloud of the engine `ref`
+        (ppp_register), started at T0 (None: the identity; ICP needs a start within the basin of the answer).  T carries a scan
+        point into the reference's frame: transform_cloud(T) applies it.  rows[k] is the evaluation at T_k, k = 0 .. steps (dicts
+        as registration_terms gives them; the last has locked 63 and step2 NaN); stats: n, indexed, steps, converged, locked,
+        shift, centre, length, T, pairs_before / _after, rms_before / _after.  Neither cloud is changed"""
+        rp = RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps))
+        cap = max(int(iterations), 0) + 1
+        rows = (RegistrationRow * cap)()
+        st = RegistrationStats()
+        t = _t12(T0)
+        self._chk(self.L.ppp_register(self.h, ref.h, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st)))
+        stats = _registration_stats(st)
+        return stats["T"].copy(), [_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], stats
+
+    def transform_cloud(self, T):
+        """ppp_transform_cloud: the resident cloud moved by T (3 x 4 in double, rounded to float; pcl::transformPointCloud's
+        arithmetic).  Plan, index and stored results are withdrawn, as after any change of the cloud"""
+        t = _t12(T)
+        self._chk(self.L.ppp_transform_cloud(self.h, None if t is None else _d(t)))
 
     def contact_field(self, maps=True, min_width=0.0):
         """(curv5 float32[n, 5], half_width float32[n], stats dict) of the resident cloud: compute_transform + Area2Cloud at every
