@@ -25,6 +25,7 @@ import pytest
 from polishpathplanning_amd import synth
 from test_path_coverage import CASES, case_params
 from test_path_dwell import HERTZ, same
+from test_path_removal import past_the_grid_cap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F24 = 2.0 ** 24
@@ -234,6 +235,30 @@ def main_restated_cpu(smooth):
     o.close()
     assert Q.tobytes() == ref.tobytes()
     return restate_deviation(scan, Q, N, dict(MAIN, smooth_radius=smooth))
+
+
+@functools.lru_cache(maxsize=None)
+def large_clouds():
+    """(reference float32[1922, 3], scan float32[141877, 3], notes dict), in millimetres; nobody writes to them.  The scan is
+    larger than 2 * 256 CUs * 256 threads = 131 072, so that the grid-stride kernels whose grid is capped at two workgroups
+    per CU (k_dev_target, k_reg_terms) take a second trip and k_dev_stats's parts are longer than a workgroup; the reference is
+    two patches under the scan's two ends in x, with hundreds of empty slabs between them: either trip finds pairs"""
+    scan = plate_mm(421, 337, "wavy", 41, 20.0)
+    assert len(scan) == 141877 and len(scan) % 256 == 53
+    xmax = float(scan[:, 0].max())
+    ref = np.concatenate([plate_mm(40, 24, "wavy", 42, 22.0), plate_mm(40, 24, "wavy", 43, xmax - 62.0)]).astype(np.float32)
+
+    def scan_point_near(x, y):
+        return int(((scan[:, 0] - x) ** 2 + (scan[:, 1] - y) ** 2).argmin())
+
+    # two isolated reference points between the patches, each beside a scan point and inside the patches' box: no normal there
+    iso = [scan[scan_point_near(x, y)] + np.float32([0.25, 0.125, 0.0625]) for x, y in ((250.0, 10.0), (400.0, -10.0))]
+    ref = np.concatenate([ref, np.asarray(iso, np.float32)]).astype(np.float32)
+    inf_at, nan_at = scan_point_near(300.0, 100.0), scan_point_near(350.0, -100.0)      # far from either patch
+    scan[inf_at, 1] = np.float32(INF)
+    scan[nan_at] = np.float32(np.nan)
+    ref.setflags(write=False); scan.setflags(write=False)
+    return ref, scan, dict(inf_at=inf_at, nan_at=nan_at, iso=[len(ref) - 2, len(ref) - 1])
 
 
 # ---------------------------------------------------------------- CPU
@@ -569,3 +594,28 @@ def test_deviation_feeds_the_dwell_schedule(engine_mod):
     assert len(inside) > 10 and len(outside) > 10
     assert np.median(inside) > np.median(outside)
     r.close(); s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_dist", [3.0, INF])
+def test_deviation_beyond_the_grid_cap(engine_mod, max_dist):
+    """large_clouds(): 141 877 scan points against two patches of 960.  k_dev_target takes a second trip of its capped grid and
+    k_dev_stats's parts are longer than a workgroup: maps and statistics bit for bit, the two ordered sums within the bound.
+    max_dist 3: most of the scan is too far; +INFINITY: every point walks to a patch, up to tens of centimetres away.  No
+    smoothing: k_dev_smooth is launched a thread per point, uncapped, and its n x n restatement is out of reach here."""
+    ref, scan, notes = large_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    n = len(scan)
+    past_the_grid_cap(n - 2)
+    got, want = check_parity(s, r, max_dist=max_dist, smooth_radius=0.0, allowance=0.05, gain=2.0)
+    st = got["stats"]
+    assert st["n"] == n and st["dropped"] == 2 and got["status"][notes["inf_at"]] == DROPPED and got["status"][notes["nan_at"]] == DROPPED
+    first = np.nonzero(got["status"] == MATCHED)[0] < 131072
+    print("matched cloud indices below 131072: %d, at or above: %d" % (first.sum(), (~first).sum()))
+    assert first.sum() >= 100 and (~first).sum() >= 100                      # either trip of k_dev_target has matched points
+    if max_dist == INF:
+        assert st["too_far"] == 0 and st["matched"] + st["no_normal"] == n - 2 and st["max_dist2"] > 100.0 ** 2
+    else:
+        assert min(st["matched"], st["too_far"], st["no_normal"], st["dropped"]) > 0 and st["too_far"] > 0.9 * n
+    r.close(); s.close()
+

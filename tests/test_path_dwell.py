@@ -16,7 +16,7 @@ import pytest
 
 from polishpathplanning_amd import synth
 from test_path_coverage import CASES, boundary_samples, case_params
-from test_path_removal import sample_lengths
+from test_path_removal import past_the_grid_cap, sample_lengths
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAT, PARABOLIC, HERTZ = 0, 1, 2
@@ -488,3 +488,40 @@ def test_path_dwell_refusals(engine_mod):
     g.gen_path()
     refused(g, engine_mod.ERR_UNSUPPORTED)
     g.close()
+
+
+@pytest.mark.gpu
+def test_path_dwell_beyond_the_grid_cap(engine_mod):
+    """cfg3_250k_s128, walk 1, 2 rounds: k_dwell_resid's parts are longer than a workgroup.  No restatement at this size: the
+    same bytes from two fresh handles, the integer fields against path_removal() and path_contacts(), the level as
+    check_parity has it, and the two residuals from the maps the engine returns -- Solver.residual's expression, within
+    check_parity's bound"""
+    pts, cfg = synth.make_config("cfg3_250k_s128")
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+    n = len(pts)
+    past_the_grid_cap(n)
+    out = []
+    for _ in range(2):
+        e = engine_mod.Engine(0, **kw)
+        e.set_cloud(pts)
+        assert e.gen_path() == cfg["slices"]
+        out.append(e.path_dwell(HERTZ, None, 2, *BOUNDS))
+        unit, ust = e.path_removal(HERTZ)
+        held = e.path_contacts()[0] > 0
+        e.close()
+    rows, removal, st = out[0]
+    assert same(out[1], out[0])
+    touched = int(held.sum())
+    assert (st["n"], st["touched"], st["rows"], st["iterations"]) == (n, touched, len(rows), 2) and touched == ust["touched"] and len(rows) > 0
+    assert st["at_min"] + st["at_max"] <= len(rows) and removal.shape == (n,)
+    L = st["level"]
+    assert L == ust["mean"] and st["path_length"] == ust["path_length"]
+
+    def residual(R):
+        e = (R[held] - L) / L
+        return float(np.sqrt(np.sum(e * e) / touched))
+
+    for got, want in ((st["residual_before"], residual(unit)), (st["residual_after"], residual(removal))):
+        print("residual: got %r numpy %r bound %r" % (got, want, n * EPS * want))
+        assert abs(got - want) <= n * EPS * want
+    assert st["residual_after"] < st["residual_before"]

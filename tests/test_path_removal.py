@@ -8,6 +8,7 @@ import ctypes
 import functools
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -117,11 +118,30 @@ def same(x, y):
     return np.array([x]).tobytes() == np.array([y]).tobytes()
 
 
-def check_stats(removal, touched, st, path_length):
-    """the statistics are those of the map, of the touched points and of the sample table's lengths"""
+@functools.lru_cache(maxsize=None)
+def compute_units():
+    """multi_processor_count of device 0 as torch reports it, asked once, in a process of its own: torch finds no device in a
+    process in which the engine's HIP runtime is already at work"""
+    out = subprocess.check_output([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"])
+    return int(out.split()[-1])
+
+
+def past_the_grid_cap(n_sorted):
+    """the precondition of every test beyond the grid cap: on this device the capped grids (two workgroups of 256 threads per
+    CU) no longer hold n_sorted threads, so a second trip is taken; returns that cap"""
+    cap = 2 * compute_units() * 256
+    print("n_sorted %d, grid cap %d threads (%d workgroups)" % (n_sorted, cap, cap // 256))
+    assert n_sorted > cap, "this device needs more than %d points to reach a second trip" % n_sorted
+    return cap
+
+
+def check_stats(removal, touched, st, path_length=None):
+    """the statistics are those of the map, of the touched points and of the sample table's lengths (path_length None: the
+    caller has no restated length)"""
     t = removal[touched]
     assert st["n"] == len(removal) and st["touched"] == int(touched.sum())
-    assert st["path_length"] == path_length, (st["path_length"], path_length)
+    if path_length is not None:
+        assert st["path_length"] == path_length, (st["path_length"], path_length)
     assert st["hist"].shape == (BINS,) and int(st["hist"].sum()) == len(t)
     if not len(t):
         assert np.isnan(st["min_removal"]) and np.isnan(st["max_removal"]) and st["sum"] == 0 and st["sum_sq"] == 0
@@ -394,3 +414,30 @@ def test_path_removal_refusals(engine_mod):
     removal, st = e.path_removal(PARABOLIC)
     assert st["touched"] > 0 and removal.shape == (len(pts),)
     e.close()
+
+
+@pytest.mark.gpu
+def test_path_removal_beyond_the_grid_cap(engine_mod):
+    """cfg3_250k_s128, walk 1: more points than two workgroups of 256 threads per CU, so k_prem_range takes a second trip of
+    its capped grid and k_prem_stats's parts are longer than a workgroup.  The statistics against the downloaded map (the
+    restated path length costs too much at this size), and the same bytes from two fresh handles"""
+    pts, cfg = synth.make_config("cfg3_250k_s128")
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+    n = len(pts)
+    cap = past_the_grid_cap(n)
+    out = []
+    for _ in range(2):
+        e = engine_mod.Engine(0, **kw)
+        e.set_cloud(pts)
+        assert e.gen_path() == cfg["slices"]
+        removal, st = e.path_removal(HERTZ)
+        counts, _, _, cst = e.path_contacts()
+        out.append((removal, st, counts))
+        e.close()
+    removal, st, counts = out[0]
+    touched = counts > 0
+    print("touched %d of %d: %d with a cloud index below %d, %d at or above" % (touched.sum(), n, touched[:cap].sum(), cap, touched[cap:].sum()))
+    assert st["touched"] == cst["covered"] and touched[:cap].sum() > 1000 and touched[cap:].sum() > 1000
+    assert not np.any((removal > 0) & ~touched) and st["path_length"] > 0
+    check_stats(removal, touched, st)
+    assert same(out[1], out[0])

@@ -22,7 +22,8 @@ import numpy as np
 import pytest
 
 from polishpathplanning_amd import synth
-from test_deviation import KW0, d2_table, engines, main_clouds, plate_mm
+from test_deviation import INF, KW0, MAIN, d2_table, engines, large_clouds, main_clouds, past_the_grid_cap, plate_mm
+from test_deviation import check_parity as deviation_parity
 from test_path_dwell import same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -461,6 +462,68 @@ def test_census_of_the_parity_case():
     assert st["steps"] >= 3 and st["converged"] == 1 and st["locked"] == 0b011100
 
 
+# The case beyond the grid cap (test_deviation.large_clouds): n max_dist^2 > 2^20, so the fixed point is 2^38 and not 2^40
+LARGE = dict(max_dist=3.0, iterations=2, min_step=1e-6, lock_eps=1e-3)
+LARGE_SHIFT = 38
+CAP_256 = 131072                                        # 2 workgroups * 256 CUs * 256 threads: where the second trip begins on an MI355X
+MARGIN = 5000                                           # x-rank against sorted position: see x_ranks
+
+
+def large_T0():
+    ref, _, _ = large_clouds()
+    return motion_about(box_centre(ref)[2], (0.05, 0.0, 0.0), (0.4, 0.3, -0.2))
+
+
+def x_ranks(P):
+    """(rank int64[n], the largest slab population): the rank by x among the finite points (-1: not finite).  The index orders
+    the points by x-slab, then inside a slab by y, so a point's sorted position differs from its x-rank by less than its slab's
+    population; the slabs are the engine's, ceil(finite / 832) of equal width over the x range, in float"""
+    P = np.asarray(P, np.float32)
+    rows = np.nonzero(np.isfinite(P).all(axis=1))[0]
+    x = P[rows, 0]
+    rank = np.full(len(P), -1, np.int64)
+    rank[rows[np.argsort(x, kind="stable")]] = np.arange(len(rows))
+    B = max(1, min((len(rows) + 831) // 832, 8192))
+    x0 = x.min()
+    invw = np.float32(B) / (x.max() - x0)
+    slab = np.minimum(B - 1, np.maximum(0, ((x - x0) * invw).astype(np.int64)))
+    return rank, int(np.bincount(slab, minlength=B).max())
+
+
+def sides(rank, which, cap=CAP_256, margin=MARGIN):
+    """how many of the points `which` have an x-rank below cap - margin, and how many at or above cap + margin"""
+    k = rank[which]
+    return int((k < cap - margin).sum()), int((k >= cap + margin).sum())
+
+
+def test_census_of_the_large_case():
+    """by restatement alone, with the oracle's normals: the scan is past the grid cap of a 256-CU device, both trips of the
+    capped grids meet pairs, and the fixed point is 2^38"""
+    ref, scan, notes = large_clouds()
+    n = len(scan)
+    mn, mx, _ = box_centre(ref)
+    N = oracle_normals(ref)
+    at0 = restate_terms(scan, ref, N, mn, mx, LARGE["max_dist"], IDENTITY)
+    rank, densest = x_ranks(scan)
+    matched = np.concatenate([np.nonzero(at0["partner"] >= 0)[0], at0["no_normal"]])
+    lo, hi = sides(rank, matched)
+    late = int((matched >= CAP_256).sum())
+    print("n %d indexed %d, matched within 3 mm at the identity %d (pairs %d); x-rank below %d: %d, at or above %d: %d; cloud index >= %d: %d; "
+          "densest slab %d; shift %d" % (n, at0["indexed"], len(matched), at0["pairs"], CAP_256 - MARGIN, lo, CAP_256 + MARGIN, hi, CAP_256, late,
+                                         densest, at0["shift"]))
+    assert n == 141877 and at0["indexed"] == n - 2 > CAP_256 + MARGIN
+    assert densest < MARGIN
+    assert lo >= 300 and hi >= 300 and late >= 100
+    assert len(at0["no_normal"]) >= 1 and set(at0["partner"][at0["partner"] >= 0]).isdisjoint(notes["iso"])
+    before, after = box_centre(ref[:-2]), box_centre(ref)
+    assert same(before, after)                                               # the isolated points lie inside the patches' box
+    assert at0["shift"] == LARGE_SHIFT
+    atT = restate_terms(scan, ref, N, mn, mx, LARGE["max_dist"], large_T0())
+    plo, phi = sides(rank, atT["partner"] >= 0)
+    print("pairs at T0 %d: x-rank below %d: %d, at or above %d: %d" % (atT["pairs"], CAP_256 - MARGIN, plo, CAP_256 + MARGIN, phi))
+    assert atT["pairs"] >= 1500 and plo >= 300 and phi >= 300 and atT["shift"] == LARGE_SHIFT
+
+
 # ---------------------------------------------------------------- GPU
 
 
@@ -686,3 +749,225 @@ def test_registration_of_a_cloud_to_itself_and_refusals(engine_mod):
     assert w.register(w, max_dist=3.0)[2]["converged"] == 1
     for e in (r, s, w, h):
         e.close()
+
+
+# ---------------------------------------------------------------- GPU: beyond the grid cap
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("at", ["T0", "identity"])
+def test_terms_beyond_the_grid_cap(engine_mod, at):
+    """large_clouds(): k_reg_terms strides over the scan a second time, with pairs in either trip, and the terms are scaled
+    by 2^38: all 29 words against the restatement, the same bits on a repeat"""
+    ref, scan, _ = large_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    T = large_T0() if at == "T0" else None
+    row, st = s.registration_terms(r, T=T, max_dist=LARGE["max_dist"])
+    cap = past_the_grid_cap(st["indexed"])
+    mn, mx = r.minmax()
+    want = restate_terms(s.cloud(), r.cloud(), r.estimate_normals(), mn, mx, LARGE["max_dist"], IDENTITY if T is None else T)
+    rank, densest = x_ranks(s.cloud())
+    lo, hi = sides(rank, want["partner"] >= 0, cap)
+    print("pairs %d (want %d) E %d (want %d) shift %d; restated pairs with x-rank below %d: %d, at or above %d: %d (densest slab %d)"
+          % (row["pairs"], want["pairs"], row["E"], want["E"], st["shift"], cap - MARGIN, lo, cap + MARGIN, hi, densest))
+    assert densest < MARGIN and lo >= 300 and hi >= 300
+    want.update(locked=ALL_LOCKED, step2=NAN)
+    rows_equal([row], [want])
+    assert row["pairs"] >= 1500
+    assert st["shift"] == want["shift"] == LARGE_SHIFT and same(st["centre"], want["centre"]) and same(st["length"], want["length"])
+    assert st["n"] == len(scan) and st["indexed"] == want["indexed"] == len(scan) - 2 and st["steps"] == 0 and st["converged"] == 0
+    assert st["pairs_before"] == st["pairs_after"] == row["pairs"] and same(st["rms_before"], st["rms_after"])
+    assert same(st["rms_before"], rms_of(want, want["shift"])) and same(st["T"], want["T"])
+    again = s.registration_terms(r, T=T, max_dist=LARGE["max_dist"])
+    assert same(again, (row, st))                                            # the same bits in every run
+    r.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_chain_beyond_the_grid_cap(engine_mod):
+    """large_clouds() from large_T0() with iterations 2: two steps, both taken from sums of two trips, and the third
+    evaluation's row built by the host; rows, statistics and T bit for bit"""
+    ref, scan, _ = large_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    T, rows, st = s.register(r, T0=large_T0(), **LARGE)
+    past_the_grid_cap(st["indexed"])
+    wT, wrows, wst = restated_from(s, r, T0=large_T0(), **LARGE)
+    print("steps %d (want %d) converged %d masks %r pairs %r rms %r -> %r" % (st["steps"], wst["steps"], st["converged"], [w["locked"] for w in rows],
+                                                                          [w["pairs"] for w in rows], st["rms_before"], st["rms_after"]))
+    assert wst["steps"] == 2 and wst["shift"] == LARGE_SHIFT and wst["pairs_after"] >= 1500
+    rows_equal(rows, wrows)
+    stats_equal(st, wst)
+    assert same(T, wT)
+    r.close(); s.close()
+
+
+# ---------------------------------------------------------------- GPU: every way a chain can end
+
+
+def chain_parity(engine_mod, ref, scan, T0=None, **p):
+    """(T, rows, stats) of s.register on fresh handles, equal bit for bit to the restatement fed by the engine's getters"""
+    r, s = engines(engine_mod, ref, scan)
+    T, rows, st = s.register(r, T0=T0, **p)
+    wT, wrows, wst = restated_from(s, r, T0=T0, **p)
+    print("steps %d (want %d) converged %d (want %d) masks %r (want %r) pairs %r rms %r -> %r"
+          % (st["steps"], wst["steps"], st["converged"], wst["converged"], [w["locked"] for w in rows], [w["locked"] for w in wrows],
+             [w["pairs"] for w in rows], st["rms_before"], st["rms_after"]))
+    rows_equal(rows, wrows)
+    stats_equal(st, wst)
+    assert same(T, wT) and same(T, rows[-1]["T"]) and rows[-1]["locked"] == ALL_LOCKED and math.isnan(rows[-1]["step2"])
+    r.close(); s.close()
+    return T, rows, st, wrows
+
+
+@pytest.mark.gpu
+def test_a_chain_that_uses_up_its_iterations(engine_mod):
+    """the census case with iterations 2: no step kernel follows the third evaluation, so the host builds its row"""
+    ref, scan, _ = main_clouds()
+    T, rows, st, wrows = chain_parity(engine_mod, ref, scan, T0=census_T0(), **dict(CENSUS, iterations=2))
+    assert st["steps"] == 2 and st["converged"] == 0 and len(rows) == 3
+    assert [w["locked"] for w in rows] == [0b011100, 0b011100, ALL_LOCKED] and st["locked"] == 0b011100
+    last, want = rows[2], wrows[2]
+    for f in ("pairs", "A", "b", "E", "T"):
+        assert same(last[f], want[f]), f
+    assert last["pairs"] >= 0.7 * len(scan) and np.any(last["A"]) and np.any(last["b"]) and last["E"] > 0
+
+
+@pytest.mark.gpu
+def test_a_flat_plate_on_the_gpu(engine_mod):
+    """test_a_flat_plate_locks_what_it_cannot_see's chain: the partial lock, bit for bit"""
+    ref, scan, moved, Tm = flat_clouds()
+    T, rows, st, _ = chain_parity(engine_mod, ref, moved, **KNOWN)
+    assert st["steps"] >= 1 and all(w["locked"] == 0b011100 for w in rows[:-1]) and st["locked"] == 0b011100 and st["converged"] == 1
+
+
+@pytest.mark.gpu
+def test_known_motion_row_by_row(engine_mod):
+    """the known motion with lock_eps 1e-9: nothing locked, every step a full 6 x 6 solve and a composition in double, and every
+    row of the chain bit for bit"""
+    ref, scan, moved, Tm = known_clouds()
+    T, rows, st, _ = chain_parity(engine_mod, ref, moved, **KNOWN)
+    assert st["steps"] >= 3 and st["converged"] == 1 and st["locked"] == 0 and all(w["locked"] == 0 for w in rows[:-1])
+    assert worst_error(T, moved, scan) <= CAP_MM
+
+
+FEW_AT = ((45.0, -20.0), (50.0, 10.0), (75.0, 5.0), (120.0, -15.0), (130.0, 20.0), (140.0, -5.0))      # (x, y), well inside the reference
+
+
+def few_pairs_scan(k):
+    """(the main scan with all but k points moved 1 000 mm in z: finite, indexed, unmatched; the k points' cloud indices)"""
+    _, scan, _ = main_clouds()
+    keep = []
+    for x, y in FEW_AT[:k]:
+        d = (scan[:, 0] - x) ** 2 + (scan[:, 1] - y) ** 2
+        d[keep] = np.inf
+        keep.append(int(np.nanargmin(d)))
+    out = scan.copy()
+    rest = np.ones(len(scan), bool)
+    rest[keep] = False
+    out[rest, 2] += np.float32(1000.0)
+    return out, keep
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,lock_eps", [(0, 1e-3), (5, 1e-3), (6, 1e-3), (6, 1e-9)])
+def test_few_pairs(engine_mod, k, lock_eps):
+    """0 and 5 pairs: no step, not converged, one row (rms NaN without a pair); 6 pairs: a step is tried on a system that 6
+    pairs on a nearly flat plate cannot determine -- parity with the restatement, whatever the pivot rule locks.  With the
+    oracle's normals the restatement locks 0b011100 under lock_eps 1e-3 and converges in 3 steps on the 6 pairs; under 1e-9 it
+    locks 0b010000 alone, the step throws the scan hundreds of millimetres away and the chain ends on an evaluation without
+    a pair (1 step, not converged, rms_after NaN)"""
+    ref, _, _ = main_clouds()
+    scan, keep = few_pairs_scan(k)
+    T, rows, st, wrows = chain_parity(engine_mod, ref, scan, **dict(CENSUS, lock_eps=lock_eps))
+    partner = wrows[0]["partner"]
+    assert np.all(partner[keep] >= 0) and int((partner >= 0).sum()) == k     # each chosen point pairs with a point that has a normal
+    assert rows[0]["pairs"] == st["pairs_before"] == k and st["indexed"] == len(scan) - 1
+    print("k %d: mask of the first row %s, steps %d" % (k, bin(rows[0]["locked"]), st["steps"]))
+    if k < 6:
+        assert st["steps"] == 0 and st["converged"] == 0 and len(rows) == 1 and st["locked"] == 0 and same(T, IDENTITY)
+        assert st["pairs_after"] == k
+        if k == 0:
+            assert math.isnan(st["rms_before"]) and math.isnan(st["rms_after"]) and rows[0]["E"] == 0 and not np.any(rows[0]["A"])
+        else:
+            assert math.isfinite(st["rms_before"]) and same(st["rms_before"], st["rms_after"])
+    else:
+        assert st["steps"] >= 1 and rows[0]["locked"] not in (0, ALL_LOCKED)
+
+
+@pytest.mark.gpu
+def test_lock_eps_close_to_one(engine_mod):
+    """lock_eps = 1 - 2^-20 on the census case: only a pivot within 2^-20 of the largest diagonal entry passes the rule"""
+    ref, scan, _ = main_clouds()
+    T, rows, st, _ = chain_parity(engine_mod, ref, scan, T0=census_T0(), **dict(CENSUS, lock_eps=1.0 - 2.0 ** -20))
+    assert st["steps"] >= 1 and rows[0]["locked"] not in (0, 0b011100, ALL_LOCKED)
+
+
+@pytest.mark.gpu
+def test_row_cap_below_the_number_of_rows(engine_mod):
+    """ppp_register with row_cap 2 on the census chain (4 rows or more): the first two rows, the whole call's statistics, and
+    nothing written beyond the second entry"""
+    ref, scan, _ = main_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    T, rows, st = s.register(r, T0=census_T0(), **CENSUS)
+    assert len(rows) >= 4
+    rp = engine_mod.RegistrationParams(CENSUS["max_dist"], CENSUS["iterations"], CENSUS["min_step"], CENSUS["lock_eps"])
+    t0 = np.ascontiguousarray(census_T0().reshape(12))
+    raw = engine_mod.RegistrationStats()
+    buf = (engine_mod.RegistrationRow * 5)()
+    size = ctypes.sizeof(engine_mod.RegistrationRow)
+    ctypes.memset(buf, 0xA5, 5 * size)
+    assert s.L.ppp_register(s.h, r.h, ctypes.byref(rp), t0.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), buf, 2, ctypes.byref(raw)) == 0
+    rows_equal([engine_mod._registration_row(buf[0]), engine_mod._registration_row(buf[1])], rows[:2])
+    stats_equal(engine_mod._registration_stats(raw), st)
+    assert ctypes.string_at(ctypes.addressof(buf) + 2 * size, 3 * size) == b"\xa5" * (3 * size)
+    r.close(); s.close()
+
+
+# ---------------------------------------------------------------- GPU: a scan wholly outside the reference
+
+
+def outside(ref):
+    """float64[3, 4]: the translation by twice the reference's extent in x and in y"""
+    ok = np.isfinite(ref).all(axis=1)
+    e = ref[ok].max(axis=0).astype(np.float64) - ref[ok].min(axis=0).astype(np.float64)
+    return np.array([[1, 0, 0, 2 * e[0]], [0, 1, 0, 2 * e[1]], [0, 0, 1, 0]], np.float64)
+
+
+@pytest.mark.gpu
+def test_terms_of_a_scan_wholly_outside_the_reference(engine_mod):
+    """every query beyond the reference's box in x and in y: no pair, every word 0"""
+    ref, scan, _ = main_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    T = outside(ref)
+    mn, mx = r.minmax()
+    want = restate_terms(s.cloud(), r.cloud(), r.estimate_normals(), mn, mx, CENSUS["max_dist"], T)
+    row, st = s.registration_terms(r, T=T, max_dist=CENSUS["max_dist"])
+    want.update(locked=ALL_LOCKED, step2=NAN)
+    rows_equal([row], [want])
+    assert row["pairs"] == 0 and not np.any(row["A"]) and not np.any(row["b"]) and row["E"] == 0
+    assert st["pairs_before"] == 0 and math.isnan(st["rms_before"]) and math.isnan(st["rms_after"]) and same(st["T"], T)
+    r.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_deviation_of_a_scan_wholly_outside_the_reference(engine_mod):
+    """the main scan moved by twice the reference's extent in x and in y: every query enters dev_nearest_within through the
+    clamps of slab_of and of the y-bucket row.  Without a limit no side closes before a candidate is found and every point is
+    matched (or meets a point without a normal); within 2 mm nothing is matched and the extrema and the mean are NaN"""
+    ref, scan, _ = main_clouds()
+    r, s = engines(engine_mod, ref, scan)
+    T = outside(ref)
+    want = transform_f32(T, s.cloud())
+    s.transform_cloud(T)
+    assert s.cloud().tobytes() == want.tobytes()
+    ok = np.isfinite(want).all(axis=1)
+    mx = r.minmax()[1]
+    assert np.all(want[ok, 0] > mx[0]) and np.all(want[ok, 1] > mx[1])
+    got, _ = deviation_parity(s, r, max_dist=INF, smooth_radius=0.0, allowance=0.1, gain=3.0)
+    st = got["stats"]
+    assert st["too_far"] == 0 and st["matched"] > 0 and st["matched"] + st["no_normal"] == int(ok.sum()) and st["dropped"] == len(scan) - int(ok.sum())
+    got, _ = deviation_parity(s, r, smooth_radius=0.0, **MAIN)
+    st = got["stats"]
+    assert st["matched"] == 0 and st["no_normal"] == 0 and st["too_far"] == int(ok.sum())
+    assert all(math.isnan(st[f]) for f in ("min_dev", "max_dev", "mean_dev", "rms_dev", "max_dist2")) and st["target_sum"] == 0
+    r.close(); s.close()
