@@ -453,7 +453,7 @@ int  ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params 
    cloud (or the scan before the process); the result T = (R | t), row-major 3 x 4 in double, carries a resident point of h into
    ref's frame.  ppp_get_deviation does not register; these calls do, and ppp_transform_cloud applies their result.  ICP is a
    local method: it needs a start T0 within the basin of the answer -- a fixturing error of millimetres and a few degrees, not
-   an unknown pose; a global (coarse) alignment is the caller's.  Everything below is + - * / in double with one rounding per
+   an unknown pose; ppp_register_global, further down, finds one.  Everything below is + - * / in double with one rounding per
    written operation, and integers wherever a sum has no fixed order: the same bits in every run.
      centre     mn, mx = ppp_minmax(ref); c[d] = ((double)mn[d] + (double)mx[d]) * 0.5; e = (double)mx - (double)mn;
                 Ln = (((ex + ey) + ez) * 0.5) + (double)max_dist
@@ -527,6 +527,94 @@ int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *r
    Does not set the alignment of ppp_trans2center.  PPP_ERR_ARG: no cloud, a slice-range or part handle (the preprocessing
    calls' refusals), a handle under ppp_trans2center, a T entry that is not finite. */
 int  ppp_transform_cloud(ppp_handle h, const double *T12);
+/* Global registration: the start ppp_register needs, from the two clouds alone.  Each cloud's
+   principal frame -- mean and eigenvectors of its points' covariance -- is taken from ten order-free integer sums; two frames
+   imply a rigid motion up to the 24 proper signed permutations G of the axes; a short coarse chain of ppp_register's iteration
+   runs from each of them, side by side on a thinned scan, and the cheapest start seeds the fine chain.
+     moments    n = cloud->size(); mn, mx = ppp_minmax; c[d] = ((double)mn[d] + (double)mx[d]) * 0.5, e = (double)mx - (double)mn,
+                L = ((ex + ey) + ez) * 0.5; u = ((double)p - c) / L for every indexed (finite) point p; ms = min(40, 60 -
+                clog2(max(2, n))); words[0] = the count, words[1 + d] = the sum of llrint(u_d 2^ms), words[4 ..] = the sums of
+                llrint((u_d u_k) 2^ms) for dk = xx xy xz yy yz zz, in signed 64-bit integers
+     frame      m_d = ((double)S1_d / (double)count) 2^-ms; C_dk = ((double)S2_dk / (double)count) 2^-ms - m_d m_k; the eigenpairs
+                of C by 12 cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2): a pair with C_pq == 0 is skipped, else
+                theta = (C_qq - C_pp) / (2 C_pq), t = sgn(theta) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1),
+                s = t c; C_pp -= t C_pq, C_qq += t C_pq, C_pq = 0, the third index r: (C_rp, C_rq) <- (c C_rp - s C_rq,
+                s C_rp + c C_rq), every row of V (from I) likewise.  Eigenvalues descending, a tie to the lower original column;
+                each of the first two axes signed so that its component of largest magnitude is positive (the lowest index on a
+                tie); the third axis = the cross product of the first two.  mean = c + L m (resident units), eigenvalues =
+                (lambda L) L (mm^2), axes[3 d + k] = component d of axis k.
+     starts     the G in this order: the identity; the half turns about axis 0, axis 1, axis 2 (diag(1,-1,-1), diag(-1,1,-1),
+                diag(-1,-1,1)); the other 20, G's column k = sgn[k] e_perm[k], ascending in (perm[0], perm[1], perm[2], sgn[0],
+                sgn[1], sgn[2]) with +1 before -1.  R_G = (V_ref G) V_scan^T, t_G = mean_ref - R_G mean_scan, every entry
+                ((a0 b0) + a1 b1) + a2 b2.  candidates = 4 takes the first four: right where the three eigenvalues are well
+                apart; 24 also covers axes that swap.
+     coarse     the queries are the indexed points of h whose cloud index is a multiple of stride; from every start a chain of
+                ppp_register with the parameters `coarse` on those queries alone, with ppp_register's c, Ln and shift for
+                coarse.max_dist and n = cloud->size() of h (with stride 1 each chain IS ppp_register from that start)
+     cost       of a start, from its last row: E + (queries - pairs) * llrint((double)md2 2^shift), md2 the float square of
+                coarse.max_dist, in signed 64-bit integers: an unpaired query costs what the farthest pair could.  The smallest
+                cost wins, a tie goes to the lower index.
+     fine       ppp_register with the parameters `fine` from the winner's T: rows and stats.fine are that call's
+   ppp_get_cloud_moments fills *frame for h's resident cloud (one kernel, one wait).  ppp_cloud_frame_from_moments and
+   ppp_registration_starts are host only: no handle, no device.  ppp_register_global builds both handles' indices and ref's
+   normal field where they are missing, takes both clouds' moments, enqueues coarse.iterations + 1 evaluations and
+   coarse.iterations steps of all starts back to back on h's stream, waits once, then runs the fine chain.  cands receives the
+   first min(cand_cap, candidates) starts' results, rows the first min(row_cap, steps + 1) rows of the fine chain; each may be
+   NULL with a cap of 0; stats may be NULL.  stats.second_cost is the lowest cost among the starts whose T differs from the
+   winner's (-1: none): close to winner_cost on a part that is ambiguous.  Neither cloud, plan nor any stored contact result
+   changes.  h == ref is allowed.
+   The defaults -- 24 candidates, stride 16, coarse 10 mm / 8 iterations / min_step 1e-3 / lock_eps 1e-9, fine =
+   ppp_default_registration_params -- are a guess for parts of a few hundred millimetres.
+   Limits: the two clouds must cover the same extent of the part -- the frames are those of the points, so a partial scan or a
+   very uneven density moves the mean (ppp_voxel_down evens the density); a part whose relief is symmetric under one of the 24
+   motions is ambiguous by nature: the tie rule answers and second_cost shows it.  No feature matching, no orientation test on
+   the scan's own normals, no scale.
+   PPP_ERR_ARG: ppp_register's refusals for `coarse` and for `fine`; gp NULL; candidates not 4 or 24; stride < 1; cands NULL
+   with cand_cap > 0; no indexed point on either cloud; L == 0 on either cloud; no query left.  ppp_cloud_frame_from_moments:
+   frame, words or c NULL, words[0] <= 0, ms outside [0, 62], L not finite and > 0.  ppp_registration_starts: a NULL
+   argument, candidates not 4 or 24.  PPP_ERR_UNSUPPORTED when either handle is a slice-range handle or a part handle. */
+typedef struct {
+    size_t    count;            /* indexed (finite) points */
+    int       ms;               /* the words' fixed point is 2^ms */
+    double    c[3], L;          /* centre of the box and half the sum of its extents */
+    long long words[10];        /* count, S1[x y z], S2[xx xy xz yy yz zz] */
+    double    mean[3];          /* resident units */
+    double    axes[9];          /* axes[3 d + k]: component d of axis k; a proper rotation */
+    double    eigenvalues[3];   /* mm^2, descending */
+} ppp_cloud_frame;
+
+typedef struct {
+    int candidates;                  /* 4 or 24 */
+    int stride;                      /* >= 1: every stride-th cloud index is a query of the coarse stage */
+    ppp_registration_params coarse;  /* the K chains side by side */
+    ppp_registration_params fine;    /* the chain from the winner */
+} ppp_global_registration_params;    /* defaults: 24, 16, (10, 8, 1e-3, 1e-9), (2, 30, 1e-6, 1e-9) */
+
+typedef struct {
+    int       index;                    /* of the start, in the order above */
+    double    T0[12], T[12];            /* the start and where its chain ended */
+    int       steps, converged, locked;
+    size_t    pairs0, pairs;            /* at T0 and at T */
+    long long E0, E;
+    long long cost;
+} ppp_registration_candidate;
+
+typedef struct {
+    ppp_registration_stats fine;        /* the fine chain's; fine.T is the result */
+    ppp_cloud_frame scan, ref;
+    size_t    queries;                  /* of the coarse stage */
+    int       shift;                    /* the coarse stage's fixed point is 2^shift */
+    int       candidates, winner;
+    long long winner_cost, second_cost;
+} ppp_global_registration_stats;
+
+int  ppp_get_cloud_moments(ppp_handle h, ppp_cloud_frame *frame);
+int  ppp_cloud_frame_from_moments(const long long *words10, int ms, const double *c3, double L, ppp_cloud_frame *frame);
+int  ppp_registration_starts(const ppp_cloud_frame *scan, const ppp_cloud_frame *ref, int candidates, double *T12s);
+void ppp_default_global_registration_params(ppp_global_registration_params *gp);
+int  ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registration_params *gp,
+                         ppp_registration_candidate *cands, size_t cand_cap, ppp_registration_row *rows, size_t row_cap,
+                         ppp_global_registration_stats *stats);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

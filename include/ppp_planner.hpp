@@ -513,6 +513,49 @@ public:
         for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
         return ran && apply && st.converged && transform_cloud(st.T);
     }
+    /* global registration of this planner's cloud, the scan, to the cloud of ref (ppp_register_global): the starts
+       the two clouds' principal frames imply, a coarse chain from each side by side, the fine chain from the cheapest.  st.fine.T
+       carries a scan point into ref's frame; cands, when asked for, receives one entry per start.  Needs no pass and no start,
+       and changes neither cloud */
+    bool register_global_to(const Planner &ref, ppp_global_registration_stats &st, const ppp_global_registration_params &gp,
+                            std::vector<ppp_registration_candidate> *cands = nullptr)
+    {
+        if (cands) cands->assign((size_t)(gp.candidates > 0 ? gp.candidates : 0), ppp_registration_candidate{});
+        int rc = ppp_register_global(h_, ref.h_, &gp, cands ? cands->data() : nullptr, cands ? cands->size() : 0, nullptr, 0, &st);
+        if (rc != PPP_OK) { if (cands) cands->clear(); return report(rc); }
+        return true;
+    }
+    /* ppp_default_global_registration_params with registration_params_env()'s knobs on the fine chain and, for the coarse stage,
+       what the environment sets of PPP_REGISTER_CANDIDATES, PPP_REGISTER_STRIDE and PPP_REGISTER_COARSE_MAXDIST */
+    static ppp_global_registration_params global_registration_params_env()
+    {
+        ppp_global_registration_params gp;
+        ppp_default_global_registration_params(&gp);
+        gp.fine = registration_params_env();
+        if (const char *v = std::getenv("PPP_REGISTER_CANDIDATES")) gp.candidates = std::atoi(v);
+        if (const char *v = std::getenv("PPP_REGISTER_STRIDE")) gp.stride = std::atoi(v);
+        if (const char *v = std::getenv("PPP_REGISTER_COARSE_MAXDIST")) gp.coarse.max_dist = (float)std::atof(v);
+        return gp;
+    }
+    /* register_global_to(), two lines on the coarse stage -- the queries, the winner with its cost and the second cost: close
+       to each other on an ambiguous part -- then print_registration()'s lines on the fine chain and, with apply, the cloud
+       moved by T when the fine chain converged.  Returns whether the cloud was moved */
+    bool print_global_registration(const Planner &ref, const ppp_global_registration_params &gp, bool apply = true)
+    {
+        ppp_global_registration_stats g = {};
+        const bool ran = register_global_to(ref, g, gp);
+        if (!ran) g = ppp_global_registration_stats{};
+        const ppp_registration_stats &st = g.fine;
+        std::printf("global registration: %d starts on %zu queries; eigenvalues %f %f %f mm^2 against %f %f %f\n", g.candidates, g.queries,
+                    g.scan.eigenvalues[0], g.scan.eigenvalues[1], g.scan.eigenvalues[2], g.ref.eigenvalues[0], g.ref.eigenvalues[1], g.ref.eigenvalues[2]);
+        std::printf("global registration: start %d wins at cost %lld, the next other pose at %lld\n", g.winner, g.winner_cost, g.second_cost);
+        std::printf("registration: %zu of %zu points paired, rms %f mm; after %d steps %zu paired, rms %f mm\n", st.pairs_before, st.indexed,
+                    st.pairs_before ? st.rms_before : 0.0, st.steps, st.pairs_after, st.pairs_after ? st.rms_after : 0.0);
+        std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",
+                    st.converged ? "converged" : (ran && st.steps == gp.fine.iterations ? "out of iterations" : "no step possible"), st.locked);
+        for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
+        return ran && apply && st.converged && transform_cloud(st.T);
+    }
     const char *path_file() const { return cfg_.path_file; }
     /* the contact field of the resident cloud (ppp_get_contact_field: principal curvatures and the half width r of the contact
        ellipse at every cloud point; needs no pass): the statistics -- narrow counts the points whose contact width 2|r| is below

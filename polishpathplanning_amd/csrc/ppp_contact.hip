@@ -845,6 +845,44 @@ void ppp_default_registration_params(ppp_registration_params *rp)
     rp->max_dist = 2.f; rp->iterations = 30; rp->min_step = 1e-6; rp->lock_eps = 1e-9;
 }
 
+/* a chain's parameters, checked; F takes what they set */
+static int registration_params_ok(ppp_handle h, const ppp_registration_params &P, IcpFrame &F)
+{
+    F.md2 = P.max_dist * P.max_dist;
+    if (!(P.max_dist > 0.f && std::isfinite(P.max_dist) && std::isfinite(F.md2)))
+        return fail(h, PPP_ERR_ARG, "registration: max_dist must be finite and > 0 (and so its float square)");
+    if (P.iterations < 1 || P.iterations > 64) return fail(h, PPP_ERR_ARG, "registration: iterations must be in [1, 64]");
+    if (!(P.min_step >= 0.0 && std::isfinite(P.min_step))) return fail(h, PPP_ERR_ARG, "registration: min_step must be finite and >= 0");
+    if (!(P.lock_eps > 0.0 && P.lock_eps < 1.0)) return fail(h, PPP_ERR_ARG, "registration: lock_eps must be in (0, 1)");
+    F.lock_eps = P.lock_eps; F.min_step2 = P.min_step * P.min_step;
+    return PPP_OK;
+}
+
+/* what a chain needs before its first launch: both handles' indices, the rest of F (B.67) and the shift (B.68), the reference's
+   normal field on its own stream and one wait for that stream */
+static int registration_setup(ppp_handle h, ppp_handle ref, const ppp_registration_params &P, IcpFrame &F, int &shift)
+{
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration: the two handles are on different devices");
+    int rc = deviation_side(h, ref, "the reference", "registration");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side(h, h, "the scan", "registration"); if (rc) return rc; }
+    rc = fetch_meta(ref);
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
+    shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    double ext[3];
+    for (int d = 0; d < 3; ++d) {
+        F.c[d] = ((double)ref->hmeta.mn[d] + (double)ref->hmeta.mx[d]) * 0.5;
+        ext[d] = (double)ref->hmeta.mx[d] - (double)ref->hmeta.mn[d];
+    }
+    F.Ln = (((ext[0] + ext[1]) + ext[2]) * 0.5) + (double)P.max_dist;
+    F.scale = std::ldexp(1.0, shift);
+    rc = contact_buffers(ref); /* the normal field, on ref's stream */
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    return PPP_OK;
+}
+
 /* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
    then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
    transforms, the sums and the rows stay on the device, a chain that has ended turns the rest of its launches into returns --
@@ -858,37 +896,17 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
     if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "registration: rows is NULL with row_cap > 0");
     const ppp_registration_params P = *rp;
     IcpFrame F;
-    F.md2 = P.max_dist * P.max_dist;
-    if (!(P.max_dist > 0.f && std::isfinite(P.max_dist) && std::isfinite(F.md2)))
-        return fail(h, PPP_ERR_ARG, "registration: max_dist must be finite and > 0 (and so its float square)");
-    if (P.iterations < 1 || P.iterations > 64) return fail(h, PPP_ERR_ARG, "registration: iterations must be in [1, 64]");
-    if (!(P.min_step >= 0.0 && std::isfinite(P.min_step))) return fail(h, PPP_ERR_ARG, "registration: min_step must be finite and >= 0");
-    if (!(P.lock_eps > 0.0 && P.lock_eps < 1.0)) return fail(h, PPP_ERR_ARG, "registration: lock_eps must be in (0, 1)");
+    int rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
     const int iterations = loop ? P.iterations : 0;
     double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     if (T0) memcpy(T, T0, sizeof(T));
     for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return fail(h, PPP_ERR_ARG, "registration: the transform has an entry that is not finite");
-    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration: the two handles are on different devices");
-    int rc = deviation_side(h, ref, "the reference", "registration");
+    int shift = 0;
+    rc = registration_setup(h, ref, P, F, shift);
     if (rc) return rc;
-    if (ref != h) { rc = deviation_side(h, h, "the scan", "registration"); if (rc) return rc; }
-    rc = fetch_meta(ref);
-    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
     const size_t N = h->n;
     const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
-    const int shift = icp_shift(N, F.md2);
-    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
-    double ext[3];
-    for (int d = 0; d < 3; ++d) {
-        F.c[d] = ((double)ref->hmeta.mn[d] + (double)ref->hmeta.mx[d]) * 0.5;
-        ext[d] = (double)ref->hmeta.mx[d] - (double)ref->hmeta.mn[d];
-    }
-    F.Ln = (((ext[0] + ext[1]) + ext[2]) * 0.5) + (double)P.max_dist;
-    F.scale = std::ldexp(1.0, shift);
-    F.lock_eps = P.lock_eps; F.min_step2 = P.min_step * P.min_step;
-    rc = contact_buffers(ref); /* the normal field, on ref's stream */
-    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
-    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
     static_assert(sizeof(IcpCtl) == 5 * sizeof(int), "IcpCtl is five ints");
     auto &G = h->registration;
     const size_t evals = (size_t)iterations + 1;
@@ -948,6 +966,179 @@ int ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp
                  ppp_registration_stats *stats)
 {
     return registration_chain(h, ref, rp, T0_12, true, rows, row_cap, stats);
+}
+
+/* The ten words of side's cloud (k_cloud_moments on side's stream, one wait) and the frame they imply; side's index is
+   complete (deviation_side).  Errors are reported on h. */
+static int cloud_moments(ppp_handle h, ppp_handle side, const char *who, ppp_cloud_frame *frame)
+{
+    const std::string w = std::string("cloud moments: ") + who;
+    auto run = [&]() -> int {
+        int rc = fetch_meta(side);
+        if (rc) return rc;
+        const int nq = side->hmeta.n_sorted;
+        if (nq <= 0) return fail(side, PPP_ERR_ARG, "no indexed point");
+        MomFrame F;
+        double ext[3];
+        for (int d = 0; d < 3; ++d) {
+            F.c[d] = ((double)side->hmeta.mn[d] + (double)side->hmeta.mx[d]) * 0.5;
+            ext[d] = (double)side->hmeta.mx[d] - (double)side->hmeta.mn[d];
+        }
+        F.L = ((ext[0] + ext[1]) + ext[2]) * 0.5;
+        if (!(F.L > 0.0 && std::isfinite(F.L))) return fail(side, PPP_ERR_ARG, "the box of the cloud has no extent (L == 0)");
+        const int ms = mom_shift(side->n);
+        F.scale = std::ldexp(1.0, ms);
+        auto &G = side->registration;
+        HIPCHK(side, G.mom.ensure(MOM_WORDS));
+        HIPCHK(side, hipMemsetAsync(G.mom.p, 0, MOM_WORDS * sizeof(unsigned long long), side->stream));
+        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + MOM_T - 1) / MOM_T, 2 * (size_t)side->num_cus));
+        LAUNCH(side, "k_cloud_moments", k_cloud_moments, grid, MOM_T, 0, side->sorted4.p, nq, F, G.mom.p);
+        unsigned long long acc[MOM_WORDS];
+        HIPCHK(side, copy_sync(side, acc, G.mom.p, sizeof(acc), hipMemcpyDeviceToHost));
+        long long words[MOM_WORDS];
+        for (int i = 0; i < MOM_WORDS; ++i) words[i] = (long long)acc[i];
+        if (words[0] != (long long)nq) return fail(side, PPP_ERR_HIP, "sums corrupt");
+        if (!cloud_frame_from_words(words, ms, F.c, F.L, frame)) return fail(side, PPP_ERR_HIP, "sums corrupt");
+        return PPP_OK;
+    };
+    const int rc = run();
+    return rc ? fail(h, rc, w + ": " + side->err) : PPP_OK;
+}
+
+int ppp_get_cloud_moments(ppp_handle h, ppp_cloud_frame *frame)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!frame) return fail(h, PPP_ERR_ARG, "cloud moments: frame is NULL");
+    int rc = deviation_side(h, h, "the cloud", "cloud moments");
+    if (rc) return rc;
+    return cloud_moments(h, h, "the cloud", frame);
+}
+
+int ppp_cloud_frame_from_moments(const long long *words10, int ms, const double *c3, double L, ppp_cloud_frame *frame)
+{
+    if (!words10 || !c3 || !frame) return PPP_ERR_ARG;
+    return cloud_frame_from_words(words10, ms, c3, L, frame) ? PPP_OK : PPP_ERR_ARG;
+}
+
+int ppp_registration_starts(const ppp_cloud_frame *scan, const ppp_cloud_frame *ref, int candidates, double *T12s)
+{
+    if (!scan || !ref || !T12s || (candidates != 4 && candidates != 24)) return PPP_ERR_ARG;
+    registration_starts(scan, ref, candidates, T12s);
+    return PPP_OK;
+}
+
+void ppp_default_global_registration_params(ppp_global_registration_params *gp)
+{
+    if (!gp) return;
+    gp->candidates = 24; gp->stride = 16;
+    gp->coarse.max_dist = 10.f; gp->coarse.iterations = 8; gp->coarse.min_step = 1e-3; gp->coarse.lock_eps = 1e-9;
+    ppp_default_registration_params(&gp->fine);
+}
+
+/* Global registration: both clouds' moments, the starts their frames imply, then every start's coarse chain
+   side by side -- coarse.iterations + 1 launches of k_reg_terms_multi and coarse.iterations of k_reg_step_multi back to back
+   on h's stream, on the queries compacted once -- one wait, the winner by cost on the host, and registration_chain from it. */
+int ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registration_params *gp, ppp_registration_candidate *cands, size_t cand_cap,
+                        ppp_registration_row *rows, size_t row_cap, ppp_global_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !gp) return fail(h, PPP_ERR_ARG, "global registration: no reference handle or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "global registration: rows is NULL with row_cap > 0");
+    if (!cands && cand_cap) return fail(h, PPP_ERR_ARG, "global registration: cands is NULL with cand_cap > 0");
+    const ppp_global_registration_params P = *gp;
+    if (P.candidates != 4 && P.candidates != 24) return fail(h, PPP_ERR_ARG, "global registration: candidates must be 4 or 24");
+    if (P.stride < 1) return fail(h, PPP_ERR_ARG, "global registration: stride must be >= 1");
+    IcpFrame F, Ffine;
+    int rc = registration_params_ok(h, P.coarse, F);
+    if (rc) return rc;
+    rc = registration_params_ok(h, P.fine, Ffine);
+    if (rc) return rc;
+    int shift = 0;
+    rc = registration_setup(h, ref, P.coarse, F, shift);
+    if (rc) return rc;
+    if (icp_shift(h->n, Ffine.md2) < 16)
+        return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    ppp_global_registration_stats st = {};
+    rc = cloud_moments(h, h, "the scan", &st.scan);
+    if (rc) return rc;
+    if (ref == h) st.ref = st.scan;
+    else { rc = cloud_moments(h, ref, "the reference", &st.ref); if (rc) return rc; }
+    const int K = P.candidates, iterations = P.coarse.iterations;
+    const size_t evals = (size_t)iterations + 1;
+    std::vector<double> T((size_t)K * evals * 12, 0.0), T0((size_t)K * 12);
+    registration_starts(&st.scan, &st.ref, K, T0.data());
+    for (double v : T0) if (!std::isfinite(v)) return fail(h, PPP_ERR_ARG, "global registration: a start has an entry that is not finite");
+    for (int s = 0; s < K; ++s) memcpy(&T[(size_t)s * evals * 12], &T0[(size_t)s * 12], 12 * sizeof(double));
+    const int ns = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    auto &G = h->registration;
+    static_assert(sizeof(IcpCtl) == 5 * sizeof(int), "IcpCtl is five ints");
+    const size_t ns1 = (size_t)std::max(ns, 1);
+    HIPCHK(h, G.queries.ensure(ns1)); HIPCHK(h, G.qcnt.ensure((ns1 + COMPACT_CHUNK - 1) / COMPACT_CHUNK + 1));
+    HIPCHK(h, G.mT.ensure(T.size())); HIPCHK(h, G.macc.ensure(ICP_WORDS * evals * K)); HIPCHK(h, G.mrows.ensure(evals * K)); HIPCHK(h, G.mctl.ensure(5 * (size_t)K));
+    int nq = 0;
+    if (ns > 0) {
+        const int nblocks = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+        StrideSel sel = {h->sorted4.p, P.stride, G.queries.p};
+        rc = compact(h, sel, ns, G.qcnt.p, G.qcnt.p + nblocks, [&](int kept) -> int {
+            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "global registration: query count corrupt");
+            nq = kept;
+            return PPP_OK;
+        });
+        if (rc) return rc;
+    }
+    if (nq <= 0) return fail(h, PPP_ERR_ARG, "global registration: no query left (no indexed point has a cloud index that is a multiple of stride)");
+    HIPCHK(h, hipMemsetAsync(G.macc.p, 0, ICP_WORDS * evals * K * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.mctl.p, 0, 5 * (size_t)K * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.mT.p, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.mctl.p);
+    /* all starts together stay at two workgroups per CU, and never below one per start */
+    const size_t per = std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus / (size_t)K));
+    const size_t tstride = 12 * evals, astride = ICP_WORDS * evals;
+    for (int k = 0; k <= iterations; ++k) {
+        LAUNCH(h, "k_reg_terms_multi", k_reg_terms_multi, dim3((unsigned)per, (unsigned)K), ICP_T, 0, G.queries.p, nq, contact_index(ref), nref, F,
+               G.mT.p + 12 * (size_t)k, tstride, ctl, G.macc.p + ICP_WORDS * (size_t)k, astride);
+        if (k < iterations)
+            LAUNCH(h, "k_reg_step_multi", k_reg_step_multi, K, 64, 0, G.macc.p + ICP_WORDS * (size_t)k, astride, F, G.mT.p + 12 * (size_t)k, tstride,
+                   G.mrows.p + k, evals, ctl);
+    }
+    std::vector<IcpCtl> C((size_t)K);
+    std::vector<ppp_registration_row> R(evals * K);
+    std::vector<unsigned long long> acc(ICP_WORDS * evals * K);
+    HIPCHK(h, copy_sync(h, C.data(), G.mctl.p, C.size() * sizeof(IcpCtl), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, R.data(), G.mrows.p, R.size() * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, acc.data(), G.macc.p, acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, T.data(), G.mT.p, T.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long far = llrint((double)F.md2 * F.scale);
+    std::vector<ppp_registration_candidate> cd((size_t)K);
+    int win = 0;
+    for (int s = 0; s < K; ++s) {
+        const IcpCtl &c = C[(size_t)s];
+        if (c.steps < 0 || c.steps > iterations || (!c.done && c.steps != iterations)) return fail(h, PPP_ERR_HIP, "global registration: control words corrupt");
+        const size_t first = (size_t)s * evals, last = first + (size_t)c.steps;
+        if (!c.done) icp_row_terms(&R[last], &T[12 * last], &acc[ICP_WORDS * last]); /* the evaluation behind the last step: no step kernel follows it */
+        if (R[first].pairs > (size_t)nq || R[last].pairs > (size_t)nq) return fail(h, PPP_ERR_HIP, "global registration: sums corrupt");
+        ppp_registration_candidate &o = cd[(size_t)s];
+        o = ppp_registration_candidate{};
+        o.index = s;
+        memcpy(o.T0, &T0[12 * (size_t)s], sizeof(o.T0)); memcpy(o.T, R[last].T, sizeof(o.T));
+        o.steps = c.steps; o.converged = c.converged; o.locked = c.locked;
+        o.pairs0 = R[first].pairs; o.E0 = R[first].E; o.pairs = R[last].pairs; o.E = R[last].E;
+        o.cost = o.E + (long long)((size_t)nq - o.pairs) * far;
+        if (o.cost < cd[(size_t)win].cost) win = s;
+    }
+    long long second = -1;
+    for (int s = 0; s < K; ++s)
+        if (memcmp(cd[(size_t)s].T, cd[(size_t)win].T, sizeof(cd[0].T)) != 0 && (second < 0 || cd[(size_t)s].cost < second)) second = cd[(size_t)s].cost;
+    rc = registration_chain(h, ref, &P.fine, cd[(size_t)win].T, true, rows, row_cap, &st.fine);
+    if (rc) return rc;
+    st.queries = (size_t)nq; st.shift = shift; st.candidates = K; st.winner = win;
+    st.winner_cost = cd[(size_t)win].cost; st.second_cost = second;
+    if (stats) *stats = st;
+    const size_t k = std::min(cand_cap, (size_t)K);
+    if (cands && k) memcpy(cands, cd.data(), k * sizeof(ppp_registration_candidate));
+    return PPP_OK;
 }
 
 /* What this handle's tile evaluates and owns, behind a plan: the cuts of its range [sb, se) on the walk of the

@@ -294,6 +294,13 @@ struct ppp_handle_s {
         DevBuf<unsigned long long> acc;
         DevBuf<ppp_registration_row> rows;
         DevBuf<int> ctl;
+        /* ppp_get_cloud_moments: the ten words.  ppp_register_global's coarse stage: per start the transforms, sums, rows and
+           control words of its chain, the compacted queries and the compaction's block counts and total */
+        DevBuf<unsigned long long> mom, macc;
+        DevBuf<double> mT;
+        DevBuf<ppp_registration_row> mrows;
+        DevBuf<int> mctl, qcnt;
+        DevBuf<float4> queries;
     } registration;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */

@@ -6,9 +6,14 @@
  * transform.  The transforms, the sums and the rows stay on the device: the host enqueues the whole chain and waits once.
  * Integer sums wherever a sum has no order, + - * / in double with one rounding per written operation everywhere else: the
  * same bits in every run.  No float atomics, no transcendental on the path that decides anything.
+ * Global registration (ppp_get_cloud_moments, ppp_register_global): k_cloud_moments, the ten integer
+ * words of a cloud's first and second moments; cloud_frame_from_words, the principal frame they imply, and registration_starts,
+ * the rigid motions two such frames imply (host); k_reg_terms_multi and k_reg_step_multi, K chains side by side -- start
+ * blockIdx.y of the evaluation, workgroup blockIdx.x of the step -- on the queries StrideSel compacts once.
  */
 #pragma once
 #include "ppp_deviation.h"
+#include "ppp_compact.h"
 
 #define ICP_T 256
 #define ICP_PAIRS 0  /* the words of one evaluation: pairs, the upper triangle of J^T J (21), J^T r (6), r^T r */
@@ -142,10 +147,11 @@ __host__ __device__ inline double icp_compose(const double *x, const double *c, 
    64-bit integers.  They are added over the wave, over the workgroup through LDS, and the workgroup adds every non-zero word
    with one 64-bit integer atomic: the grid is capped by the host, so the atomics do not grow with the cloud.  Two's complement
    words: b may be negative.  T is read from device memory -- the step kernel before this launch wrote it. */
-__global__ void __launch_bounds__(ICP_T) k_reg_terms(const float4 *__restrict__ q4, int nq, const ContactIndex R, int nref, const IcpFrame F,
-        const double *__restrict__ T, const IcpCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
+/* k_reg_terms's body, for workgroup `block` of `blocks`: one chain's evaluation at T into acc.  Both the single chain's kernel
+   and the side-by-side one call it, so a row is the same bits from either. */
+__device__ __forceinline__ void reg_terms_body(const float4 *__restrict__ q4, int nq, const ContactIndex &R, int nref, const IcpFrame &F,
+        const double *__restrict__ T, unsigned long long *__restrict__ acc, int block, int blocks)
 {
-    if (ctl->done) return;
     __shared__ unsigned long long s_a[ICP_T / 64][ICP_WORDS];
     unsigned long long a[ICP_WORDS];
 #pragma unroll
@@ -154,7 +160,7 @@ __global__ void __launch_bounds__(ICP_T) k_reg_terms(const float4 *__restrict__ 
 #pragma unroll
     for (int i = 0; i < 12; ++i) t[i] = T[i];
     const SlabView V = R.view();
-    for (int at = blockIdx.x * ICP_T + threadIdx.x; at < nq; at += gridDim.x * ICP_T) {
+    for (int at = block * ICP_T + threadIdx.x; at < nq; at += blocks * ICP_T) {
         const float4 p = q4[at];
         const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
         double m[3];
@@ -197,14 +203,31 @@ __global__ void __launch_bounds__(ICP_T) k_reg_terms(const float4 *__restrict__ 
     }
 }
 
+__global__ void __launch_bounds__(ICP_T) k_reg_terms(const float4 *__restrict__ q4, int nq, const ContactIndex R, int nref, const IcpFrame F,
+        const double *__restrict__ T, const IcpCtl *__restrict__ ctl, unsigned long long *__restrict__ acc)
+{
+    if (ctl->done) return;
+    reg_terms_body(q4, nq, R, nref, F, T, acc, blockIdx.x, gridDim.x);
+}
+
+/* K chains side by side (B.76): start blockIdx.y evaluates at its own transform into its own 29 words -- T, acc and ctl are
+   those of start 0, a start's lie tstride doubles, astride words and one IcpCtl behind its predecessor's -- with gridDim.x
+   workgroups striding over the nq queries, so the lanes of a workgroup walk the same windows of the reference's index.  A
+   chain that has ended returns at its first instruction, whatever the others do. */
+__global__ void __launch_bounds__(ICP_T) k_reg_terms_multi(const float4 *__restrict__ q4, int nq, const ContactIndex R, int nref, const IcpFrame F,
+        const double *__restrict__ T, size_t tstride, const IcpCtl *__restrict__ ctl, unsigned long long *__restrict__ acc, size_t astride)
+{
+    if (ctl[blockIdx.y].done) return;
+    reg_terms_body(q4, nq, R, nref, F, T + blockIdx.y * tstride, acc + blockIdx.y * astride, blockIdx.x, gridDim.x);
+}
+
 /* One thread: the evaluation k of a chain (its 29 words in acc, its transform T) becomes row k, and, where a step is taken
    from it, T + 12 the next transform.  No step is taken -- the row keeps locked = 63 and step2 = NaN and the chain ends --
    behind a step below min_step (ctl->stop: converged), where J^T r is zero in every word (T is a stationary point: converged),
    with fewer than 6 pairs, and where the pivot rule locks all six unknowns (not converged). */
-__global__ void __launch_bounds__(64) k_reg_step(const unsigned long long *__restrict__ acc, const IcpFrame F, double *T,
+__device__ __forceinline__ void reg_step_body(const unsigned long long *__restrict__ acc, const IcpFrame &F, double *T,
         ppp_registration_row *__restrict__ row, IcpCtl *ctl)
 {
-    if (ctl->done || threadIdx.x != 0 || blockIdx.x != 0) return;
     ppp_registration_row rw;
     icp_row_terms(&rw, T, acc);
     bool zero = true;
@@ -222,4 +245,185 @@ __global__ void __launch_bounds__(64) k_reg_step(const unsigned long long *__res
     ctl->steps += 1;
     ctl->locked |= mask;
     if (rw.step2 < F.min_step2) { ctl->stop = 1; ctl->converged = 1; }
+}
+
+__global__ void __launch_bounds__(64) k_reg_step(const unsigned long long *__restrict__ acc, const IcpFrame F, double *T,
+        ppp_registration_row *__restrict__ row, IcpCtl *ctl)
+{
+    if (ctl->done || threadIdx.x != 0 || blockIdx.x != 0) return;
+    reg_step_body(acc, F, T, row, ctl);
+}
+
+/* the steps of K chains: workgroup blockIdx.x is start blockIdx.x, in which thread 0 works; the strides are k_reg_terms_multi's,
+   rstride rows lie between two starts' */
+__global__ void __launch_bounds__(64) k_reg_step_multi(const unsigned long long *__restrict__ acc, size_t astride, const IcpFrame F, double *T,
+        size_t tstride, ppp_registration_row *__restrict__ row, size_t rstride, IcpCtl *ctl)
+{
+    const size_t s = blockIdx.x;
+    if (ctl[s].done || threadIdx.x != 0) return;
+    reg_step_body(acc + s * astride, F, T + s * tstride, row + s * rstride, ctl + s);
+}
+
+/* The coarse stage's queries (B.76): the indexed points of the scan whose cloud index is a multiple of stride, in slab order */
+struct StrideSel {
+    using Val = float4;
+    const float4 *q4;
+    int stride;
+    float4 *out;
+    __device__ void begin() {}
+    __device__ float4 load(int i) const { return q4[i]; }
+    __device__ bool keep(int, const float4 &p) const { return idx_of(p) % stride == 0; }
+    __device__ void emit(int, int k, const float4 &p) const { out[k] = p; }
+};
+
+/* ---------------------------------------------------------------------------------------------------------------------- */
+/* The principal frame of a cloud (B.73, B.74) and the starts two frames imply (B.75)                                     */
+/* ---------------------------------------------------------------------------------------------------------------------- */
+#define MOM_T 256
+#define MOM_WORDS 10 /* the count, S1[x y z], S2[xx xy xz yy yz zz] */
+#define MOM_SWEEPS 12
+
+struct MomFrame { double c[3], L, scale; };
+
+/* B.73: min(40, 60 - clog2(max(2, n))), n = cloud->size() */
+__host__ __device__ inline int mom_shift(size_t n)
+{
+    const int s = 60 - icp_clog2((double)(n < 2 ? (size_t)2 : n));
+    return s < 40 ? s : 40;
+}
+
+/* A thread per indexed point in slab order, grid-stride: u = ((double)p - c) / L, the ten words rounded to 2^-ms (F.scale =
+   2^ms) into the thread's 64-bit integers, added over the wave, over the workgroup through LDS, and by one 64-bit integer
+   atomic per workgroup and non-zero word: k_reg_terms's pattern.  |u_d| <= 1 and n 2^ms <= 2^60: no word overflows. */
+__global__ void __launch_bounds__(MOM_T) k_cloud_moments(const float4 *__restrict__ q4, int nq, const MomFrame F, unsigned long long *__restrict__ acc)
+{
+    __shared__ unsigned long long s_a[MOM_T / 64][MOM_WORDS];
+    unsigned long long a[MOM_WORDS];
+#pragma unroll
+    for (int w = 0; w < MOM_WORDS; ++w) a[w] = 0;
+    for (int at = blockIdx.x * MOM_T + threadIdx.x; at < nq; at += gridDim.x * MOM_T) {
+        const float4 p = q4[at];
+        const double u[3] = {((double)p.x - F.c[0]) / F.L, ((double)p.y - F.c[1]) / F.L, ((double)p.z - F.c[2]) / F.L};
+        a[0] += 1;
+        int w = 4;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            a[1 + d] += (unsigned long long)llrint(u[d] * F.scale);
+#pragma unroll
+            for (int k = d; k < 3; ++k, ++w) a[w] += (unsigned long long)llrint((u[d] * u[k]) * F.scale);
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < MOM_WORDS; ++w) a[w] = wave_sum(a[w]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int w = 0; w < MOM_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
+    }
+    __syncthreads();
+    if (threadIdx.x < MOM_WORDS) {
+        unsigned long long s = 0;
+        for (int v = 0; v < MOM_T / 64; ++v) s += s_a[v][threadIdx.x];
+        if (s) atomicAdd(acc + threadIdx.x, s);
+    }
+}
+
+/* B.74: the frame the ten words imply.  Mean and covariance of u in double; the eigenpairs by MOM_SWEEPS cyclic Jacobi sweeps
+   over the pairs (0,1), (0,2), (1,2) -- a pair whose off-diagonal entry is zero is skipped; theta = (a_qq - a_pp) / (2 a_pq),
+   t = sgn(theta) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0,
+   the third index r: (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq), every row k of V likewise -- + - * / and sqrt, one
+   rounding per written operation; eigenvalues descending, a tie to the lower original column; the first two axes signed so
+   that the component of largest magnitude is positive (the lowest index on a tie), the third their cross product.
+   false: no point, or L not finite and > 0. */
+inline bool cloud_frame_from_words(const long long *words, int ms, const double *c, double L, ppp_cloud_frame *f)
+{
+    if (words[0] <= 0 || !(L > 0.0) || !(L < INFINITY) || ms < 0 || ms > 62) return false;
+    f->count = (size_t)words[0]; f->ms = ms; f->L = L;
+    for (int d = 0; d < 3; ++d) f->c[d] = c[d];
+    for (int w = 0; w < MOM_WORDS; ++w) f->words[w] = words[w];
+    double inv = 1.0;
+    for (int i = 0; i < ms; ++i) inv = inv * 0.5; /* 2^-ms */
+    const double cnt = (double)words[0];
+    double m[3], A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int d = 0; d < 3; ++d) m[d] = ((double)words[1 + d] / cnt) * inv;
+    for (int d = 0, w = 4; d < 3; ++d)
+        for (int k = d; k < 3; ++k, ++w) A[d][k] = A[k][d] = ((double)words[w] / cnt) * inv - m[d] * m[k];
+    static const int PQ[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};
+    for (int sweep = 0; sweep < MOM_SWEEPS; ++sweep)
+        for (int e = 0; e < 3; ++e) {
+            const int p = PQ[e][0], q = PQ[e][1], r = PQ[e][2];
+            const double apq = A[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double at = theta < 0.0 ? -theta : theta;
+            const double den = at + std::sqrt(theta * theta + 1.0);
+            const double t = theta < 0.0 ? -1.0 / den : 1.0 / den;
+            const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+            A[p][p] = A[p][p] - t * apq;
+            A[q][q] = A[q][q] + t * apq;
+            A[p][q] = A[q][p] = 0.0;
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = cs * arp - sn * arq;
+            A[r][q] = A[q][r] = sn * arp + cs * arq;
+            for (int k = 0; k < 3; ++k) {
+                const double vp = V[k][p], vq = V[k][q];
+                V[k][p] = cs * vp - sn * vq;
+                V[k][q] = sn * vp + cs * vq;
+            }
+        }
+    int ord[3] = {0, 1, 2}; /* descending, stable: a tie keeps the lower original column first */
+    for (int i = 1; i < 3; ++i)
+        for (int k = i; k > 0 && A[ord[k]][ord[k]] > A[ord[k - 1]][ord[k - 1]]; --k) { const int o = ord[k]; ord[k] = ord[k - 1]; ord[k - 1] = o; }
+    double ax[3][3]; /* ax[k] = axis k */
+    for (int k = 0; k < 2; ++k) {
+        int big = 0;
+        for (int d = 1; d < 3; ++d) if (std::fabs(V[d][ord[k]]) > std::fabs(V[big][ord[k]])) big = d;
+        const bool neg = V[big][ord[k]] < 0.0;
+        for (int d = 0; d < 3; ++d) ax[k][d] = neg ? -V[d][ord[k]] : V[d][ord[k]];
+    }
+    ax[2][0] = ax[0][1] * ax[1][2] - ax[0][2] * ax[1][1];
+    ax[2][1] = ax[0][2] * ax[1][0] - ax[0][0] * ax[1][2];
+    ax[2][2] = ax[0][0] * ax[1][1] - ax[0][1] * ax[1][0];
+    for (int d = 0; d < 3; ++d) {
+        f->mean[d] = c[d] + L * m[d];
+        f->eigenvalues[d] = (A[ord[d]][ord[d]] * L) * L;
+        for (int k = 0; k < 3; ++k) f->axes[3 * d + k] = ax[k][d];
+    }
+    return true;
+}
+
+/* B.75: the proper signed permutations G in their fixed order -- column k of G has the entry sgn[k] in row perm[k] -- the
+   identity, the half turns about the first, the second and the third axis, then the other 20 ascending in (perm[0], perm[1],
+   perm[2], sgn[0], sgn[1], sgn[2]) with + before - */
+struct StartG { int perm[3], sgn[3]; };
+inline void registration_start_table(StartG *G)
+{
+    static const int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    static const int PAR[6] = {1, -1, -1, 1, 1, -1};
+    static const int HEAD[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+    int n = 0;
+    for (int i = 0; i < 4; ++i, ++n)
+        for (int k = 0; k < 3; ++k) { G[n].perm[k] = k; G[n].sgn[k] = HEAD[i][k]; }
+    for (int p = 0; p < 6; ++p)
+        for (int b = 0; b < 8; ++b) {
+            const int s[3] = {(b & 4) ? -1 : 1, (b & 2) ? -1 : 1, (b & 1) ? -1 : 1};
+            if (PAR[p] * s[0] * s[1] * s[2] != 1 || p == 0) continue;
+            for (int k = 0; k < 3; ++k) { G[n].perm[k] = P[p][k]; G[n].sgn[k] = s[k]; }
+            ++n;
+        }
+}
+
+/* T12s[12 g ..] = (R_G | t_G): R_G = (V_ref G) V_scan^T, t_G = mean_ref - R_G mean_scan, every sum ((a0 b0) + a1 b1) + a2 b2 */
+inline void registration_starts(const ppp_cloud_frame *scan, const ppp_cloud_frame *ref, int candidates, double *T12s)
+{
+    StartG G[24];
+    registration_start_table(G);
+    for (int g = 0; g < candidates; ++g) {
+        double *T = T12s + 12 * g;
+        for (int r = 0; r < 3; ++r) {
+            double a[3];
+            for (int k = 0; k < 3; ++k) { const double v = ref->axes[3 * r + G[g].perm[k]]; a[k] = G[g].sgn[k] < 0 ? -v : v; }
+            for (int cc = 0; cc < 3; ++cc) T[4 * r + cc] = ((a[0] * scan->axes[3 * cc]) + a[1] * scan->axes[3 * cc + 1]) + a[2] * scan->axes[3 * cc + 2];
+            T[4 * r + 3] = ref->mean[r] - (((T[4 * r] * scan->mean[0]) + T[4 * r + 1] * scan->mean[1]) + T[4 * r + 2] * scan->mean[2]);
+        }
+    }
 }

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_transform_cloud", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -177,6 +177,13 @@ def lib():
         L.ppp_get_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
         L.ppp_register.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
         L.ppp_transform_cloud.argtypes = [vp, dp]
+        L.ppp_get_cloud_moments.argtypes = [vp, C.POINTER(CloudFrame)]
+        L.ppp_cloud_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
+        L.ppp_registration_starts.argtypes = [C.POINTER(CloudFrame), C.POINTER(CloudFrame), C.c_int, dp]
+        L.ppp_default_global_registration_params.argtypes = [C.POINTER(GlobalRegistrationParams)]
+        L.ppp_default_global_registration_params.restype = None
+        L.ppp_register_global.argtypes = [vp, vp, C.POINTER(GlobalRegistrationParams), C.POINTER(RegistrationCandidate), sz, C.POINTER(RegistrationRow), sz,
+                                          C.POINTER(GlobalRegistrationStats)]
         L.ppp_get_contact_field.argtypes = [vp, fp, fp, sz, C.c_float, C.POINTER(ContactFieldStats)]
         L.ppp_get_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte), C.c_float, C.c_float, ip, sz, C.POINTER(Region), sz,
                                       C.POINTER(RegionStats)]
@@ -402,6 +409,78 @@ def _registration_stats(st):
     out = {k: getattr(st, k) for k, _ in RegistrationStats._fields_}
     out["centre"] = np.array(st.centre[:], np.float64)
     out["T"] = np.array(st.T[:], np.float64).reshape(3, 4)
+    return out
+
+
+class CloudFrame(C.Structure):
+    """ppp_cloud_frame"""
+    _fields_ = [("count", C.c_size_t), ("ms", C.c_int), ("c", C.c_double * 3), ("L", C.c_double), ("words", C.c_longlong * 10),
+                ("mean", C.c_double * 3), ("axes", C.c_double * 9), ("eigenvalues", C.c_double * 3)]
+
+
+class GlobalRegistrationParams(C.Structure):
+    """ppp_global_registration_params"""
+    _fields_ = [("candidates", C.c_int), ("stride", C.c_int), ("coarse", RegistrationParams), ("fine", RegistrationParams)]
+
+
+class RegistrationCandidate(C.Structure):
+    """ppp_registration_candidate"""
+    _fields_ = [("index", C.c_int), ("T0", C.c_double * 12), ("T", C.c_double * 12), ("steps", C.c_int), ("converged", C.c_int),
+                ("locked", C.c_int), ("pairs0", C.c_size_t), ("pairs", C.c_size_t), ("E0", C.c_longlong), ("E", C.c_longlong),
+                ("cost", C.c_longlong)]
+
+
+class GlobalRegistrationStats(C.Structure):
+    """ppp_global_registration_stats"""
+    _fields_ = [("fine", RegistrationStats), ("scan", CloudFrame), ("ref", CloudFrame), ("queries", C.c_size_t), ("shift", C.c_int),
+                ("candidates", C.c_int), ("winner", C.c_int), ("winner_cost", C.c_longlong), ("second_cost", C.c_longlong)]
+
+
+def _cloud_frame(f):
+    """a CloudFrame as a dict: count, ms, c float64[3], L, words int64[10], mean float64[3], axes float64[3, 3] (column k is
+    axis k), eigenvalues float64[3]"""
+    return dict(count=int(f.count), ms=int(f.ms), c=np.array(f.c[:], np.float64), L=float(f.L), words=np.array(f.words[:], np.int64),
+                mean=np.array(f.mean[:], np.float64), axes=np.array(f.axes[:], np.float64).reshape(3, 3),
+                eigenvalues=np.array(f.eigenvalues[:], np.float64))
+
+
+def _frame_struct(frame):
+    f = CloudFrame()
+    f.count, f.ms, f.L = int(frame["count"]), int(frame["ms"]), float(frame["L"])
+    f.c[:] = [float(v) for v in frame["c"]]
+    f.words[:] = [int(v) for v in frame["words"]]
+    f.mean[:] = [float(v) for v in frame["mean"]]
+    f.axes[:] = [float(v) for v in np.asarray(frame["axes"], np.float64).reshape(9)]
+    f.eigenvalues[:] = [float(v) for v in frame["eigenvalues"]]
+    return f
+
+
+def _registration_candidate(c):
+    return dict(index=int(c.index), T0=np.array(c.T0[:], np.float64).reshape(3, 4), T=np.array(c.T[:], np.float64).reshape(3, 4),
+                steps=int(c.steps), converged=int(c.converged), locked=int(c.locked), pairs0=int(c.pairs0), pairs=int(c.pairs),
+                E0=int(c.E0), E=int(c.E), cost=int(c.cost))
+
+
+def cloud_frame_from_moments(words, ms, c, L):
+    """ppp_cloud_frame_from_moments (host only, no device): the frame dict of the ten integer words, their fixed point 2^ms, the
+    box centre c and the length L"""
+    w = (C.c_longlong * 10)(*[int(v) for v in words])
+    cc = (C.c_double * 3)(*[float(v) for v in c])
+    f = CloudFrame()
+    rc = lib().ppp_cloud_frame_from_moments(w, int(ms), cc, float(L), C.byref(f))
+    if rc:
+        raise PPPError(rc, "ppp_cloud_frame_from_moments: bad arguments")
+    return _cloud_frame(f)
+
+
+def registration_starts(scan_frame, ref_frame, candidates=24):
+    """ppp_registration_starts (host only, no device): float64[candidates, 3, 4], the rigid motions the two frame dicts imply,
+    in the header's fixed order; candidates is 4 or 24"""
+    out = np.zeros((max(int(candidates), 0), 3, 4), np.float64)
+    a, b = _frame_struct(scan_frame), _frame_struct(ref_frame)
+    rc = lib().ppp_registration_starts(C.byref(a), C.byref(b), int(candidates), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc:
+        raise PPPError(rc, "ppp_registration_starts: bad arguments")
     return out
 
 
@@ -1096,6 +1175,40 @@ class Engine:
         self._chk(self.L.ppp_register(self.h, ref.h, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st)))
         stats = _registration_stats(st)
         return stats["T"].copy(), [_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], stats
+
+    def cloud_moments(self):
+        """ppp_get_cloud_moments: the frame dict of the resident cloud (count, ms, c, L, the ten integer words, mean, axes with
+        column k the k-th principal axis, eigenvalues in mm^2, descending)"""
+        f = CloudFrame()
+        self._chk(self.L.ppp_get_cloud_moments(self.h, C.byref(f)))
+        return _cloud_frame(f)
+
+    def register_global(self, ref, candidates=24, stride=16, coarse=None, fine=None):
+        """(T float64[3, 4], cands, rows, stats): ppp_register_global of this engine's cloud, the scan, to the cloud of the engine
+        `ref`, from the two clouds alone: the starts their principal frames imply, a coarse chain from each side by side on every
+        stride-th point, the fine chain from the cheapest.  coarse / fine: dicts of register()'s parameters over the defaults
+        (10, 8, 1e-3, 1e-9) and (2, 30, 1e-6, 1e-9).  cands: one dict per start (index, T0, T, steps, converged, locked, pairs0,
+        pairs, E0, E, cost); rows: the fine chain's; stats: fine (register()'s stats), scan / ref (frame dicts), queries, shift,
+        candidates, winner, winner_cost, second_cost"""
+        gp = GlobalRegistrationParams()
+        self.L.ppp_default_global_registration_params(C.byref(gp))
+        gp.candidates, gp.stride = int(candidates), int(stride)
+        for part, kw in ((gp.coarse, coarse), (gp.fine, fine)):
+            for k, v in (kw or {}).items():
+                if k not in ("max_dist", "iterations", "min_step", "lock_eps"):
+                    raise TypeError("unknown registration parameter %r" % k)
+                setattr(part, k, int(v) if k == "iterations" else float(v))
+        ncand = max(gp.candidates, 1)
+        cap = max(gp.fine.iterations, 0) + 1
+        cands = (RegistrationCandidate * ncand)()
+        rows = (RegistrationRow * cap)()
+        st = GlobalRegistrationStats()
+        self._chk(self.L.ppp_register_global(self.h, ref.h, C.byref(gp), cands, ncand, rows, cap, C.byref(st)))
+        stats = dict(fine=_registration_stats(st.fine), scan=_cloud_frame(st.scan), ref=_cloud_frame(st.ref), queries=int(st.queries),
+                     shift=int(st.shift), candidates=int(st.candidates), winner=int(st.winner), winner_cost=int(st.winner_cost),
+                     second_cost=int(st.second_cost))
+        return (stats["fine"]["T"].copy(), [_registration_candidate(cands[k]) for k in range(min(ncand, st.candidates))],
+                [_registration_row(rows[k]) for k in range(min(cap, st.fine.steps + 1))], stats)
 
     def transform_cloud(self, T):
         """ppp_transform_cloud: the resident cloud moved by T (3 x 4 in double, rounded to float; pcl::transformPointCloud's
