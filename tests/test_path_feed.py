@@ -350,11 +350,10 @@ def test_restatement_dwell_lookup_and_degenerate_slices():
     assert len(none) == 0 and st0["W"] == 0 and st0["min_feed"] != st0["min_feed"] and st0["duration"] == 0.0
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle_list(ci):
+def oracle_list_of(pts, kw):
+    """(S, xyz, counts per kept slice, first_kept): the oracle's WayPointsList of one cloud and its parameters"""
     from oracle import ppo
     ppo.build()
-    pts, kw = case_params(*CASES[ci])
     o = ppo.Oracle(pts, **kw)
     S = o.gen_path()
     o.get_path()
@@ -366,9 +365,18 @@ def _oracle_list(ci):
     return S, xyz, counts, first_kept
 
 
+@functools.lru_cache(maxsize=None)
+def _oracle_list(ci):
+    return oracle_list_of(*case_params(*CASES[ci]))
+
+
 def oracle_dwell_rows(ci, oracle_mod, profile=HERTZ):
     """the dwell table of CASES[ci] by test_path_dwell's restatement: uniform target, ROUNDS rounds, BOUNDS"""
-    w = pairs_of(ci, oracle_mod)
+    return dwell_rows_from(pairs_of(ci, oracle_mod), profile)
+
+
+def dwell_rows_from(w, profile=HERTZ):
+    """the same table from the pairs w of any cloud (test_path_dwell.restate_pairs)"""
     s = Solver(w, profile)
     L = s.unit_level()
     t, _, _, _ = s.solve(np.full(s.n, L), L, ROUNDS, *BOUNDS)
