@@ -548,9 +548,10 @@ static int enqueue_window_gen(ppp_handle h)
     });
 }
 /* the rest of getPath: offsets, compaction, postion_smooth / reduceRPY / flange */
-static int enqueue_window_finish(ppp_handle h)
+static int enqueue_window_finish(ppp_handle h, bool finish_lists)
 {
-    const WinArgs A = win_args(h);
+    WinArgs A = win_args(h);
+    A.stage_lists = finish_lists ? 1 : 0;
     LAUNCH(h, "k_win_finish", k_win_finish, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
     return PPP_OK;
 }
@@ -1632,9 +1633,12 @@ int ppp_get_path_async(ppp_handle h)
     { int rcs = settle_enqueue_only(h); if (rcs) return rcs; }
     if (!h->pass.gen_done()) return fail(h, PPP_ERR_ARG, "call ppp_gen_path_async first");
     if (h->win_path) { /* the per-waypoint half ran with the slices: offsets, compaction and getPath's list-wide second half */
-        int rcw = enqueue_window_finish(h);
+        /* wp_pre / wp_smooth: written by the pass for a caller who goes call by call (and may look at every stage); a pass of a
+           graph, a batch or a re-run leaves them to whoever asks (ensure_finish_lists) */
+        const bool finish_lists = h->ranged || !h->internal;
+        int rcw = enqueue_window_finish(h, finish_lists);
         if (rcw) return rcw;
-        h->pass.path_enqueued(!h->ranged, true);
+        h->pass.path_enqueued(!h->ranged, true, finish_lists);
         h->pass.meta_will_arrive(MetaAt::pinned()); /* the finish launch's last workgroup leaves the meta block in hmeta_pinned */
         return PPP_OK;
     }
@@ -2267,12 +2271,24 @@ int ppp_get_waypoint_counts(ppp_handle h, int *counts, size_t cap, size_t *nkept
     return PPP_OK;
 }
 
+/* wp_pre / wp_smooth of a window pass whose finish launch did not write them (A.stage_lists == 0): the pass left wps_pre, wp_off
+   and wp_cnt in place, and the finish launch's own text makes the two lists from them, bit for bit what the pass would have written */
+static int ensure_finish_lists(ppp_handle h)
+{
+    if (!h->pass.finish_lists_stale() || !h->win_path) return PPP_OK;
+    const WinArgs A = win_args(h);
+    LAUNCH(h, "k_win_stage_lists", k_win_stage_lists, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
+    h->pass.finish_lists_made();
+    return PPP_OK;
+}
+
 int ppp_copy_stage_to_device(ppp_handle h, int stage, float *dst_dev, size_t cap, size_t *W)
 {
     int rc = ensure_ready(h, true, true);
     if (rc) return rc;
     rc = map_dev_err(h);
     if (rc) return rc;
+    if (stage == PPP_STAGE_WP_PRESMOOTH || stage == PPP_STAGE_WP_SMOOTHED) { rc = ensure_finish_lists(h); if (rc) return rc; }
     const float *src = stage == PPP_STAGE_WP_PRESMOOTH ? h->wp_pre.p : stage == PPP_STAGE_WP_SMOOTHED ? h->wp_smooth.p : nullptr;
     if (!src) return fail(h, PPP_ERR_ARG, "stage must be PPP_STAGE_WP_PRESMOOTH or PPP_STAGE_WP_SMOOTHED");
     if (stage == PPP_STAGE_WP_SMOOTHED && !h->pass.list_final()) return fail(h, PPP_ERR_ARG, NOT_FINAL_MSG);
@@ -2585,6 +2601,7 @@ int ppp_get_stage(ppp_handle h, int stage, void *out, size_t cap_bytes, size_t *
     rc = map_dev_err(h);
     if (rc) return rc;
     if (stage == PPP_STAGE_WP_XYZ || stage == PPP_STAGE_WP_NN || stage == PPP_STAGE_WP_NORMAL) { rc = ensure_stage_lists(h); if (rc) return rc; }
+    if (stage == PPP_STAGE_WP_PRESMOOTH || stage == PPP_STAGE_WP_SMOOTHED) { rc = ensure_finish_lists(h); if (rc) return rc; }
     size_t W = (size_t)h->hmeta.W;
     if (count) *count = W;
     if (!out || !cap_bytes || !W) return PPP_OK;

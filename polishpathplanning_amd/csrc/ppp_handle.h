@@ -83,6 +83,7 @@ class PassState {
     bool planned_ = false, index_built_ = false, gen_done_ = false, path_done_ = false;
     bool list_final_ = false;    /* wp_out holds a finished WayPointsList */
     bool stage_compact_ = true;  /* wp_xyz / wp_nn / wp_normal hold the list order (a window pass leaves them in per-slice slots) */
+    bool finish_lists_stale_ = false; /* wp_pre / wp_smooth are an earlier pass's: the window path's finish launch writes them only for a pass enqueued call by call */
     unsigned long long serial_ = 0; /* counts the GenPaths enqueued */
     bool meta_fresh_ = false;    /* hmeta is the device's block as of now: nothing was launched on this handle since it was fetched (every launch clears it) */
     MetaAt meta_at_;             /* where the copy enqueued behind the last pass lands (ON_DEMAND: none was enqueued) */
@@ -96,6 +97,7 @@ public:
     bool path_done() const { return path_done_; }
     bool list_final() const { return list_final_; }
     bool stage_compact() const { return stage_compact_; }
+    bool finish_lists_stale() const { return finish_lists_stale_; }
     unsigned long long serial() const { return serial_; }
     bool meta_fresh() const { return meta_fresh_; }
     bool meta_in_flight() const { return meta_at_.kind != MetaAt::ON_DEMAND; }
@@ -114,12 +116,17 @@ public:
     void index_enqueued() { index_built_ = true; }
     void gen_enqueued(bool window) { if (window) stage_compact_ = false; gen_done_ = true; ++serial_; path_done_ = false; }
     /* getPath (a window pass's stage lists stay as they are: still in slots, or gathered since) */
-    void path_enqueued(bool final, bool window) { path_done_ = true; list_final_ = final; if (!window) stage_compact_ = true; }
+    void path_enqueued(bool final, bool window, bool finish_lists = true)
+    {
+        path_done_ = true; list_final_ = final; finish_lists_stale_ = !finish_lists;
+        if (!window) stage_compact_ = true;
+    }
     /* GenPath and getPath at once (a graph launch); carrier: the other handle's stream the work runs on */
     void pass_enqueued(bool window, bool final, MetaAt at, hipStream_t carrier = nullptr)
     {
         if (!window) index_built_ = true;
         stage_compact_ = !window;
+        finish_lists_stale_ = window && final; /* (a slice-range handle's finish launch stops at wp_pre and always writes it) */
         gen_done_ = true; ++serial_; path_done_ = true;
         list_final_ = final;
         meta_will_arrive(std::move(at));
@@ -128,6 +135,7 @@ public:
     /* a new plan turned out to ask for the very launches the last pass ran: its results stand */
     void restore_results(bool had_path, bool was_final) { gen_done_ = true; path_done_ = had_path; list_final_ = was_final; }
     void stages_gathered() { stage_compact_ = true; }
+    void finish_lists_made() { finish_lists_stale_ = false; }
     void streams_settled() { pending_stream_ = nullptr; }
     /* (a batch's pinned array stays referenced until a later batch's takes its place, whatever arrives in between: no getter
        ends up freeing pinned memory) */

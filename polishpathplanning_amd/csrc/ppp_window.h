@@ -1064,6 +1064,15 @@ __device__ __forceinline__ void win_verify_body(const WinArgs &A)
    the block to the host (win_publish_meta) sees them without any workgroup paying a release fence -- on this device a fence at
    agent scope writes back the whole L2, once per workgroup that executes it (64 x 250 k points: the finish launch 25 -> 126 us) */
 #define META_PUT(ptr, val) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+/* What a waypoint's thread asks memory for is asked for at ONE place, as soon as the offsets stand (the launch was a string of
+   dependent round trips: error word, counts, own row, three halo words one by one, the end terms, and behind the filter reduceRPY's
+   key waypoints angle by angle): every address first -- they come from s_off, and a wait for LDS also waits for the loads in
+   flight when the pointers are generic, as in the batched form --, then all the loads, then the work.
+   The two stage lists wp_pre / wp_smooth are written only where the pass needs them (A.stage_lists, a slice-range handle, the
+   in-order finish): nobody reads them in a stream of passes.
+   ONDEMAND: the form behind ppp_get_stage / ppp_copy_stage_to_device for such a pass, which left wps_pre, wp_off and wp_cnt in
+   place: the same text writes the two lists and nothing else -- no meta word, no offsets, no finished list. */
+template <bool ONDEMAND>
 __device__ __forceinline__ void win_finish_body(const WinArgs &A, const int bx)
 {
     extern __shared__ __attribute__((aligned(16))) int s_off[]; /* nkept + 1 offsets */
@@ -1075,34 +1084,62 @@ __device__ __forceinline__ void win_finish_body(const WinArgs &A, const int bx)
     DevMeta *m = A.m;
     const DevParams &P = A.P;
     const int nk = A.nkept, tid = (int)threadIdx.x;
-    if (tid == 0) { s_err = m->err | m->win_flag; s_run = 0; s_short = 0; }
-    __syncthreads();
-    if (s_err) return; /* a failed slice -- or a pass that is handed back (its slots and counts are another plan's: nothing list-wide may walk them) */
-    /* a9 bookkeeping: every workgroup scans the waypoint counts of all kept slices (left by the slice workgroups) */
     const int res_i = (int)P.rpy_resolution;
-    for (int base = 0; base < nk; base += blockDim.x) {
-        const int k2 = base + tid;
-        int c2 = 0;
-        if (k2 < nk) {
-            const int s2 = k2 + A.first_kept;
-            if (s2 >= A.sb && s2 < A.se) c2 = A.wp_cnt[k2];
+    /* a9 bookkeeping: every workgroup scans the waypoint counts of all kept slices (left by the slice workgroups) */
+    int W;
+    if (nk <= 4 * SMF_T) {
+        /* one round: a thread carries four neighbouring counts, asked for BEFORE the error word is looked at (they do not depend
+           on it; a pass that is handed back scans another plan's counts for nothing and leaves below), and one block scan */
+        int c4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k2 = 4 * tid + u, s2 = k2 + A.first_kept;
+            c4[u] = (k2 < nk && s2 >= A.sb && s2 < A.se) ? A.wp_cnt[k2] : 0;
         }
+        if (tid == 0) { s_err = m->err | m->win_flag; s_short = 0; }
         int tot;
-        const int pre = block_exscan_w(c2, s_scan, &tot);
-        const int run = s_run;
-        if (k2 < nk) {
-            s_off[k2] = run + pre;
-            if (P.rpy_resolution > 2 && c2 <= res_i) s_short = 1; /* App. B.6: reduceRPY reads past a slice this short */
+        int pre = block_exscan_w(c4[0] + c4[1] + c4[2] + c4[3], s_scan, &tot); /* (its barriers publish s_err and s_short = 0) */
+        if (s_err) return; /* a failed slice -- or a pass that is handed back (its slots and counts are another plan's: nothing list-wide may walk them) */
+        bool shrt = false;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k2 = 4 * tid + u;
+            if (k2 < nk) {
+                s_off[k2] = pre;
+                pre += c4[u];
+                if (c4[u] <= res_i) shrt = true; /* App. B.6: reduceRPY reads past a slice this short */
+            }
         }
+        if (P.rpy_resolution > 2 && shrt) s_short = 1;
+        W = tot;
+    } else {
+        if (tid == 0) { s_err = m->err | m->win_flag; s_run = 0; s_short = 0; }
         __syncthreads();
-        if (tid == 0) s_run = run + tot;
-        __syncthreads();
+        if (s_err) return;
+        for (int base = 0; base < nk; base += blockDim.x) {
+            const int k2 = base + tid;
+            int c2 = 0;
+            if (k2 < nk) {
+                const int s2 = k2 + A.first_kept;
+                if (s2 >= A.sb && s2 < A.se) c2 = A.wp_cnt[k2];
+            }
+            int tot;
+            const int pre = block_exscan_w(c2, s_scan, &tot);
+            const int run = s_run;
+            if (k2 < nk) {
+                s_off[k2] = run + pre;
+                if (P.rpy_resolution > 2 && c2 <= res_i) s_short = 1;
+            }
+            __syncthreads();
+            if (tid == 0) s_run = run + tot;
+            __syncthreads();
+        }
+        W = s_run;
     }
-    const int W = s_run;
     if (tid == 0) s_off[nk] = W;
     __syncthreads();
-    if (W > A.W_cap) { if (bx == 0 && tid == 0) { set_err(m, DERR_CAPACITY, -1); META_PUT(&m->W, 0); } return; }
-    if (bx == 0) { /* TailIndex.push_back(WayPointsList.size() - 1), the offsets, W: for the host and for the in-order finish */
+    if (W > A.W_cap) { if (!ONDEMAND && bx == 0 && tid == 0) { set_err(m, DERR_CAPACITY, -1); META_PUT(&m->W, 0); } return; }
+    if (!ONDEMAND && bx == 0) { /* TailIndex.push_back(WayPointsList.size() - 1), the offsets, W: for the host and for the in-order finish */
         for (int k2 = tid; k2 < nk; k2 += blockDim.x) {
             A.wp_off[k2] = s_off[k2]; A.tail[k2] = s_off[k2 + 1] - 1;
             const int s2 = k2 + A.first_kept;
@@ -1130,59 +1167,109 @@ __device__ __forceinline__ void win_finish_body(const WinArgs &A, const int bx)
     const int t0 = tile * SMF_T;
     const int base = t0 - SMF_K;
     const bool solve = A.finish && P.smooth && W > 2;
-    /* this thread's waypoint: its slice and its six values, requested once; the position part also fills the filter's tile */
+    const bool in_order = A.finish && P.rpy_resolution > 2 && s_short;
+    const bool lists = ONDEMAND || A.stage_lists || !A.finish || in_order; /* (launch-uniform: s_short is the whole list's) */
+    const bool near_end = solve && (t0 < SMF_END || t0 + SMF_T - 1 > W - 1 - SMF_END);
+    /* ---- the addresses ---- */
+    /* this thread's waypoint: its slice and its row */
     const int g = t0 + tid;
     int kk = 0;
     size_t rowbase = 0;
-    float p[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (g < W) {
         kk = slice_of(g);
         rowbase = (size_t)kk * A.stride - (size_t)s_off[kk]; /* row of list index w of this slice = rowbase + w */
-#pragma unroll
-        for (int d = 0; d < 6; ++d) p[d] = A.wps_pre[6 * (rowbase + g) + d];
     }
+    /* the halo: SMF_K waypoints either side of the tile */
+    const bool halo = A.finish && tid < 2 * SMF_K;
+    const int hl = tid < SMF_K ? tid : SMF_T + tid;
+    bool hsrc = false;
+    size_t hrow = 0;
+    if (halo) {
+        const int g2 = base + hl;
+        hsrc = g2 >= 1 && g2 <= W - 2;
+        if (hsrc) hrow = row_of(g2);
+    }
+    /* reduceRPY's key waypoints of this one (see finish_one_waypoint): the slice of g is known, no search over TailIndex */
+    int kmode = 0, wi = 0; /* 1: behind the slice's last key, which it copies (kb); 2: between the keys kb and ka, wi steps from kb */
+    size_t krow_a = 0, krow_b = 0;
+    if (!ONDEMAND && g < W && A.finish && !in_order && P.rpy_resolution > 2) {
+        const int res = res_i;
+        const int p0 = s_off[kk], tl = s_off[kk + 1] - 1;
+        const int nfull = (tl - p0) / res;
+        const int lastkey = p0 + nfull * res;
+        const int rr = g - p0;
+        if (g > lastkey) { kmode = 1; krow_b = rowbase + (size_t)lastkey; }
+        else if (rr % res != 0) {
+            const int pre = p0 + (rr / res) * res, last = pre + res;
+            kmode = 2; krow_b = rowbase + (size_t)pre; krow_a = rowbase + (size_t)last; wi = g - pre;
+        }
+    }
+    /* the two end terms (tiles near an end): wave j = coordinate j, lanes 0..31 the front end, 32..63 the back end */
+    const int ej = tid >> 6, lane = tid & 63;
+    const bool eterm = near_end && ej < 3;
+    const int kq = (lane & 31) + 1;
+    bool qsrc = false;
+    size_t qrow = 0, erow = 0;
+    if (eterm) {
+        const int gq = lane < 32 ? kq : W - 1 - kq;
+        qsrc = gq >= 1 && gq <= W - 2;
+        if (qsrc) qrow = row_of(gq);
+        if ((lane & 31) == 0) erow = row_of(lane < 32 ? 0 : W - 1);
+    }
+    /* ---- the loads, all of them: one stretch without a branch, so that none waits for another (a thread with nothing to ask
+       for asks for row 0, which every plan has, and drops the value); through a global pointer, so that the waits for LDS and
+       for the launch arguments in between do not count them ---- */
+    typedef const __attribute__((address_space(1))) float *gfloat_p;
+    const gfloat_p wps = (gfloat_p)A.wps_pre;
+    const size_t orow = g < W ? rowbase + (size_t)g : 0;
+    const int ejc = ej < 3 ? ej : 0;
+    float p[6], hx[3], ka[3], kb[3];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) p[d] = wps[6 * orow + d];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) hx[j] = wps[6 * hrow + j];
+#pragma unroll
+    for (int D = 3; D < 6; ++D) kb[D - 3] = wps[6 * krow_b + D];
+#pragma unroll
+    for (int D = 3; D < 6; ++D) ka[D - 3] = wps[6 * krow_a + D];
+    const float qv = wps[6 * qrow + ejc], ev = wps[6 * erow + ejc];
+    /* ---- the filter's tile ---- */
     if (A.finish) {
         const bool src = g >= 1 && g <= W - 2; /* the sources are the INTERIOR waypoints: the two fixed ends enter through A and B */
         for (int j = 0; j < 3; ++j) s_x[j][tid + SMF_K] = src ? p[j] : 0.f;
-        if (tid < 2 * SMF_K) { /* the halo: SMF_K waypoints either side of the tile */
-            const int l = tid < SMF_K ? tid : SMF_T + tid;
-            const int g2 = base + l;
-            const bool src2 = g2 >= 1 && g2 <= W - 2;
-            size_t row = 0;
-            if (src2) row = row_of(g2);
-            for (int j = 0; j < 3; ++j) s_x[j][l] = src2 ? A.wps_pre[6 * row + j] : 0.f;
-        }
+        /* (a thread without a halo slot writes its own slot again: an unconditional write keeps the halo's load up with the others) */
+        const int hslot = halo ? hl : tid + SMF_K;
+        for (int j = 0; j < 3; ++j) s_x[j][hslot] = halo ? (hsrc ? hx[j] : 0.f) : (src ? p[j] : 0.f);
     }
-    const bool in_order = A.finish && P.rpy_resolution > 2 && s_short;
-    const bool copy2 = A.finish && A.out2 != nullptr && W <= A.out2_cap;
-    if (A.finish && A.out2 != nullptr && W > A.out2_cap && tile == 0 && tid == 0) set_err(m, DERR_CAPACITY, -1);
-    const bool near_end = solve && (t0 < SMF_END || t0 + SMF_T - 1 > W - 1 - SMF_END);
+    const bool copy2 = !ONDEMAND && A.finish && A.out2 != nullptr && W <= A.out2_cap;
+    if (!ONDEMAND && A.finish && A.out2 != nullptr && W > A.out2_cap && tile == 0 && tid == 0) set_err(m, DERR_CAPACITY, -1);
     if (near_end) {
         if (tid < SMF_END) s_rp[tid] = smooth_rpow(r, tid);
-        const int j = tid >> 6, lane = tid & 63;
-        if (j < 3) {
-            const int kq = (lane & 31) + 1;
-            const int gq = lane < 32 ? kq : W - 1 - kq;
-            double v = (gq >= 1 && gq <= W - 2) ? (double)A.wps_pre[6 * row_of(gq) + j] * smooth_rpow(r, kq) : 0.0;
+        if (ej < 3) {
+            double v = qsrc ? (double)qv * smooth_rpow(r, kq) : 0.0;
             for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if ((lane & 31) == 0) s_e[lane >> 5][j] = (double)A.wps_pre[6 * row_of(lane < 32 ? 0 : W - 1) + j] - c * v;
+            if ((lane & 31) == 0) s_e[lane >> 5][ej] = (double)ev - c * v;
         }
     }
     __syncthreads();
     if (g < W) {
 #pragma clang fp contract(on) /* the 65-tap filter and the flange offset: continuous output only (same text as smooth_solve_body) */
-        for (int d = 0; d < 6; ++d) A.wp_pre[6 * (size_t)g + d] = p[d]; /* the compact list after HandEyeTransform */
+        if (lists) for (int d = 0; d < 6; ++d) A.wp_pre[6 * (size_t)g + d] = p[d]; /* the compact list after HandEyeTransform */
         if (A.finish) {
             if (solve) {
                 const int l = g - base;
-                double y[3];
+                /* the three coordinates' Horner chains side by side: each value by the operations, in the order, of the one-chain
+                   loop (a chain of 32 dependent FP64 operations three times over was what the loop waited for) */
+                double acc[3], y[3];
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double acc = (double)s_x[j][l - SMF_K] + (double)s_x[j][l + SMF_K];
+                for (int j = 0; j < 3; ++j) acc[j] = (double)s_x[j][l - SMF_K] + (double)s_x[j][l + SMF_K];
 #pragma unroll 8
-                    for (int q = SMF_K - 1; q >= 1; --q) acc = ((double)s_x[j][l - q] + (double)s_x[j][l + q]) + r * acc;
-                    y[j] = c * ((double)s_x[j][l] + r * acc);
+                for (int q = SMF_K - 1; q >= 1; --q) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) acc[j] = ((double)s_x[j][l - q] + (double)s_x[j][l + q]) + r * acc[j];
                 }
+#pragma unroll
+                for (int j = 0; j < 3; ++j) y[j] = c * ((double)s_x[j][l] + r * acc[j]);
                 if (near_end) {
                     const double D = W - 1 < SMF_END ? s_rp[W - 1] : 0.0;
                     const double r0 = g < SMF_END ? s_rp[g] : 0.0, r1 = W - 1 - g < SMF_END ? s_rp[W - 1 - g] : 0.0;
@@ -1196,51 +1283,46 @@ __device__ __forceinline__ void win_finish_body(const WinArgs &A, const int bx)
                 }
                 if (g >= 1 && g <= W - 2) { p[0] = (float)y[0]; p[1] = (float)y[1]; p[2] = (float)y[2]; }
             }
-            for (int d = 0; d < 6; ++d) A.wp_smooth[6 * (size_t)g + d] = p[d];
-            if (!in_order) {
-                /* reduceRPY for one waypoint (see finish_one_waypoint): the slice of g is known, no search over TailIndex */
-                if (P.rpy_resolution > 2) {
-                    const int res = res_i;
-                    const int p0 = s_off[kk], tl = s_off[kk + 1] - 1;
-                    const int nfull = (tl - p0) / res;
-                    const int lastkey = p0 + nfull * res;
-                    const int rr = g - p0;
-                    const float *src = A.wps_pre + 6 * rowbase;
-                    if (g > lastkey) {
-                        for (int D = 3; D < 6; ++D) p[D] = src[6 * (size_t)lastkey + D];
-                    } else if (rr % res != 0) {
-                        const int pre = p0 + (rr / res) * res, last = pre + res, wi = g - pre;
-                        for (int D = 3; D < 6; D++) {
-                            const float a = src[6 * (size_t)last + D], bb = src[6 * (size_t)pre + D];
-                            double dr;
-                            if (a * bb >= 0) {
-                                dr = (double)((a - bb) / res);
-                            } else {
-                                double no1, no2;
-                                if (a < 0) { no2 = bb; no1 = 2 * M_PI + a; }
-                                else { no2 = 2 * M_PI + bb; no1 = a; }
-                                dr = (double)fabsf(a - bb) < fabs(no1 - no2) ? (double)(a - bb) : (no1 - no2);
-                                dr /= res;
+            if (lists) for (int d = 0; d < 6; ++d) A.wp_smooth[6 * (size_t)g + d] = p[d];
+            if (!ONDEMAND) {
+                if (!in_order) {
+                    if (P.rpy_resolution > 2) {
+                        const int res = res_i;
+                        if (kmode == 1) {
+                            for (int D = 3; D < 6; ++D) p[D] = kb[D - 3];
+                        } else if (kmode == 2) {
+                            for (int D = 3; D < 6; D++) {
+                                const float a = ka[D - 3], bb = kb[D - 3];
+                                double dr;
+                                if (a * bb >= 0) {
+                                    dr = (double)((a - bb) / res);
+                                } else {
+                                    double no1, no2;
+                                    if (a < 0) { no2 = bb; no1 = 2 * M_PI + a; }
+                                    else { no2 = 2 * M_PI + bb; no1 = a; }
+                                    dr = (double)fabsf(a - bb) < fabs(no1 - no2) ? (double)(a - bb) : (no1 - no2);
+                                    dr /= res;
+                                }
+                                float v = bb;
+                                for (int q = 1; q <= wi; ++q) v = (float)(dr + v); /* the reference accumulates in float */
+                                p[D] = v;
                             }
-                            float v = bb;
-                            for (int q = 1; q <= wi; ++q) v = (float)(dr + v); /* the reference accumulates in float */
-                            p[D] = v;
                         }
+                        for (int D = 3; D < 6; ++D) p[D] = (double)p[D] > M_PI ? (float)((double)p[D] - 2 * M_PI) : p[D];
                     }
-                    for (int D = 3; D < 6; ++D) p[D] = (double)p[D] > M_PI ? (float)((double)p[D] - 2 * M_PI) : p[D];
+                    float R[3][3];
+                    rot_zyx(p[3], p[4], p[5], R);
+                    const float ee[3] = {0.f, 0.f, -P.ee_length};
+                    float t[3];
+                    for (int i = 0; i < 3; ++i) t[i] = R[i][0] * ee[0] + R[i][1] * ee[1] + R[i][2] * ee[2] + p[i] * 1.f;
+                    p[0] = t[0]; p[1] = t[1]; p[2] = t[2];
                 }
-                float R[3][3];
-                rot_zyx(p[3], p[4], p[5], R);
-                const float ee[3] = {0.f, 0.f, -P.ee_length};
-                float t[3];
-                for (int i = 0; i < 3; ++i) t[i] = R[i][0] * ee[0] + R[i][1] * ee[1] + R[i][2] * ee[2] + p[i] * 1.f;
-                p[0] = t[0]; p[1] = t[1]; p[2] = t[2];
+                for (int d = 0; d < 6; ++d) A.wp_out[6 * (size_t)g + d] = p[d];
+                if (copy2 && !in_order) for (int d = 0; d < 6; ++d) A.out2[6 * (size_t)g + d] = p[d];
             }
-            for (int d = 0; d < 6; ++d) A.wp_out[6 * (size_t)g + d] = p[d];
-            if (copy2 && !in_order) for (int d = 0; d < 6; ++d) A.out2[6 * (size_t)g + d] = p[d];
         }
     }
-    if (in_order) { /* App. B.6: a slice shorter than RPYres + 1 -- the last tile to arrive finishes the whole list in order */
+    if (!ONDEMAND && in_order) { /* App. B.6: a slice shorter than RPYres + 1 -- the last tile to arrive finishes the whole list in order */
         __threadfence();
         __syncthreads();
         if (tid == 0) s_last = atomicAdd(&m->emit_ticket, 1) == ntiles - 1;
@@ -1440,11 +1522,14 @@ __device__ __forceinline__ void win_publish_meta(const WinArgs &A)
     for (int q = threadIdx.x; q < (int)(sizeof(DevMeta) / sizeof(int)); q += blockDim.x) dst[q] = __hip_atomic_load(src + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0) __hip_atomic_store(A.fin_ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__global__ void __launch_bounds__(SMF_T) k_win_finish(WinArgs A) { win_finish_body(A, blockIdx.x); win_publish_meta(A); }
+__global__ void __launch_bounds__(SMF_T) k_win_finish(WinArgs A) { win_finish_body<false>(A, blockIdx.x); win_publish_meta(A); }
 __global__ void __launch_bounds__(SMF_T) k_win_finish_b(const WinArgs *__restrict__ mem)
 {
     const WinArgs &A = mem[blockIdx.y];
     if ((int)blockIdx.x >= A.g_finish) return;
-    win_finish_body(A, blockIdx.x);
+    win_finish_body<false>(A, blockIdx.x);
     win_publish_meta(A);
 }
+/* wp_pre and wp_smooth of a pass whose finish launch did not write them: only when a caller asks for them (ppp_get_stage,
+   ppp_copy_stage_to_device) */
+__global__ void __launch_bounds__(SMF_T) k_win_stage_lists(WinArgs A) { win_finish_body<true>(A, blockIdx.x); }

@@ -40,6 +40,7 @@ struct WinArgs {
     int rec_lds; /* waypoint records in the slice workgroup's LDS (the pairing scratch the knots leave free): waypoints per word row; 0: in the waypoints' global slots (wps_rec) */
     int g_scatter, g_slice, g_finish; /* workgroups of this workpiece per launch */
     int finish; /* 0: a slice-range handle stops after HandEyeTransform (the list is compacted only) */
+    int stage_lists; /* 1: the finish launch also writes wp_pre / wp_smooth (a slice-range handle's and the in-order finish's launch always does); 0: k_win_stage_lists makes them when somebody asks */
     int *win_cnt;
     float4 *win_pts;
     MinMaxPart *win_part;
@@ -88,6 +89,7 @@ template <int TMAX> __global__ void k_win_slice(WinArgs A);
 template <int TMAX> __global__ void k_win_slice_b(const WinArgs *__restrict__ mem);
 __global__ void k_win_finish(WinArgs A);
 __global__ void k_win_finish_b(const WinArgs *__restrict__ mem);
+__global__ void k_win_stage_lists(WinArgs A);
 __global__ void k_win_gather_stage(WinArgs A, float4 *wp_xyz, int *wp_nn, float4 *wp_normal);
 template <bool IN_LDS>
 __global__ void k_win_census(const float *__restrict__ X, int n, const float *__restrict__ px, int S, float px0, float inv_step, float pad,
