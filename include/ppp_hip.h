@@ -521,6 +521,49 @@ int  ppp_get_registration_terms(ppp_handle h, ppp_handle ref, const ppp_registra
                                 ppp_registration_row *row, ppp_registration_stats *stats);
 int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0_12,
                   ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats);
+/* Trimmed registration: ppp_register's loop in which only the share `keep` of an evaluation's pairs
+   with the smallest pair distance enters its sums (trimmed ICP, Chetverikov et al.).  A scan from a cell carries what the
+   reference does not show -- a clamp pad, a strip of the table, a burr, an edge -- within max_dist of it; such points pair, pull
+   ppp_register's fit, and are cut off here as long as keep lies below the share of the scan that does show the reference.
+     pair       ppp_register's, word for word (moved, the float query, the nearest point and its tie rule, a point at exactly
+                max_dist * max_dist matches, no pair where the normal has a NaN or the query is not finite); paired = their number
+     key        the bit pattern of the pair's float d2 as a 32-bit unsigned integer: d2 is a sum of squares, never negative and
+                never NaN, so the keys order as the floats do
+     cut        k = (size_t)ceil(keep * (double)paired), one double product and one ceil, clamped to [1, paired]; tau = the k-th
+                smallest key (1-based); KEPT = the pairs with key <= tau: every pair that ties with the k-th is kept, kept >= k,
+                and nothing depends on an order among equal keys; trim_d2 = the float with the bits of tau.  paired == 0:
+                kept = 0 and trim_d2 is the float quiet NaN 0x7fc00000 (the double 0x7ff8000000000000 of step2, narrowed)
+     terms      ppp_register's 29 words over the KEPT pairs only, row.pairs = kept; shift, centre and Ln are ppp_register's for
+                the same n and max_dist
+     the rest   solve, step, composition and the loop's endings are ppp_register's with pairs read as kept ("fewer than 6
+                pairs" is kept < 6); stats is ppp_register's with pairs_* = kept and rms_* over the kept pairs
+     maps       status and d2, by cloud index of h, the first min(cap, n) entries, of the LAST evaluation (the one at the
+                result, rows[steps]): PPP_TRIM_DROPPED and NaN for a point that is not finite, PPP_TRIM_UNPAIRED and NaN for
+                one without a pair, else PPP_TRIM_KEPT or PPP_TRIM_TRIMMED and the pair's float d2 (every NaN is 0x7fc00000).
+                A caller masks ppp_get_deviation's maps with them.
+   keep == 1 keeps every pair: rows[k].row, T and stats are ppp_register's bits from the same start.  rows, status, d2 and stats
+   may be NULL (rows with row_cap = 0; status and d2 with any cap).  The whole chain -- per evaluation the search with the top
+   digit's histogram, two passes over the stored keys, the sums, the step -- is enqueued at once on h's stream with one wait at
+   its end; neither handle's cloud, plan or stored results change.  PPP_ERR_ARG: ppp_register's refusals; tp NULL; keep NaN,
+   <= 0 or > 1.  PPP_ERR_UNSUPPORTED when either handle is a slice-range handle or a part handle. */
+typedef struct {
+    ppp_registration_params icp;   /* ppp_register's four, with its ranges */
+    double keep;                   /* in (0, 1]: the share of an evaluation's pairs that enter its sums */
+} ppp_trimmed_registration_params;          /* defaults: ppp_default_registration_params, 0.8 */
+
+typedef struct {
+    ppp_registration_row row;      /* as ppp_register's, but pairs / A / b / E are over the KEPT pairs */
+    size_t paired;                 /* pairs found by the search at row.T (what ppp_register would sum) */
+    float  trim_d2;                /* the cut: the largest float d2 that is kept; NaN when paired == 0 */
+} ppp_trimmed_registration_row;
+
+enum { PPP_TRIM_KEPT = 0, PPP_TRIM_TRIMMED = 1, PPP_TRIM_UNPAIRED = 2, PPP_TRIM_DROPPED = 3 };
+
+void ppp_default_trimmed_registration_params(ppp_trimmed_registration_params *tp);
+int  ppp_register_trimmed(ppp_handle h, ppp_handle ref, const ppp_trimmed_registration_params *tp, const double *T0_12,
+                          ppp_trimmed_registration_row *rows, size_t row_cap,
+                          unsigned char *status, float *d2, size_t cap,
+                          ppp_registration_stats *stats);
 /* T applied to the resident cloud: T12 (row-major 3 x 4, NULL: the identity) is rounded to float and every finite point
    becomes m0 x + (m1 y + (m2 z + m3)) per row, pcl::transformPointCloud's arithmetic; a point that is not finite passes
    unchanged.  The cloud has changed: bounds, plan, index and every stored result are withdrawn, as after ppp_trans2center.

@@ -513,6 +513,62 @@ public:
         for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
         return ran && apply && st.converged && transform_cloud(st.T);
     }
+    /* trimmed point-to-plane ICP (ppp_register_trimmed): register_to() in which only the share tp.keep of an
+       evaluation's pairs with the smallest pair distance enters its sums, for a scan that shows a clamp, a burr or an edge the
+       reference does not have.  rows, when asked for, receives the evaluations with their kept / paired counts and cuts;
+       status and d2, when asked for, the last evaluation's maps by cloud index (PPP_TRIM_*) */
+    bool register_trimmed_to(const Planner &ref, ppp_registration_stats &st, const ppp_trimmed_registration_params &tp, const double *T0 = nullptr,
+                             std::vector<ppp_trimmed_registration_row> *rows = nullptr, std::vector<unsigned char> *status = nullptr,
+                             std::vector<float> *d2 = nullptr)
+    {
+        if (rows) rows->assign((size_t)(tp.icp.iterations > 0 ? tp.icp.iterations : 0) + 1, ppp_trimmed_registration_row{});
+        size_t n = 0;
+        if (status || d2) {
+            int rc = ppp_num_points(h_, &n);
+            if (rc != PPP_OK) return report(rc);
+            if (status) status->assign(n, PPP_TRIM_DROPPED);
+            if (d2) d2->assign(n, 0.f);
+        }
+        int rc = ppp_register_trimmed(h_, ref.h_, &tp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, status ? status->data() : nullptr,
+                                      d2 ? d2->data() : nullptr, n, &st);
+        if (rc != PPP_OK) { if (rows) rows->clear(); if (status) status->clear(); if (d2) d2->clear(); return report(rc); }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* registration_params_env() with keep from PPP_REGISTER_KEEP (the default 0.8 where it is not set) */
+    static ppp_trimmed_registration_params trimmed_registration_params_env()
+    {
+        ppp_trimmed_registration_params tp;
+        ppp_default_trimmed_registration_params(&tp);
+        tp.icp = registration_params_env();
+        if (const char *v = std::getenv("PPP_REGISTER_KEEP")) tp.keep = std::atof(v);
+        return tp;
+    }
+    /* whether PPP_REGISTER_KEEP asks for the trimmed loop: set, and a share below 1 (anything else leaves register_to() as it is) */
+    static bool trimmed_registration_asked()
+    {
+        const char *v = std::getenv("PPP_REGISTER_KEEP");
+        return v && v[0] && std::atof(v) < 1.0;
+    }
+    /* print_registration() on register_trimmed_to(): a line with the kept and the paired counts and the cut before and after,
+       then print_registration()'s lines over the kept pairs */
+    bool print_registration(const Planner &ref, const ppp_trimmed_registration_params &tp, bool apply = true)
+    {
+        ppp_registration_stats st = {};
+        std::vector<ppp_trimmed_registration_row> rows;
+        const bool ran = register_trimmed_to(ref, st, tp, nullptr, &rows);
+        if (!ran) st = ppp_registration_stats{};
+        const ppp_trimmed_registration_row none = {};
+        const ppp_trimmed_registration_row &first = rows.empty() ? none : rows.front(), &last = rows.empty() ? none : rows.back();
+        std::printf("registration: keep %f: %zu of %zu pairs kept within %f mm^2; after %d steps %zu of %zu within %f mm^2\n", tp.keep, first.row.pairs,
+                    first.paired, first.paired ? first.trim_d2 : 0.0, st.steps, last.row.pairs, last.paired, last.paired ? last.trim_d2 : 0.0);
+        std::printf("registration: %zu of %zu points kept, rms %f mm; after %d steps %zu kept, rms %f mm\n", st.pairs_before, st.indexed,
+                    st.pairs_before ? st.rms_before : 0.0, st.steps, st.pairs_after, st.pairs_after ? st.rms_after : 0.0);
+        std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",
+                    st.converged ? "converged" : (ran && st.steps == tp.icp.iterations ? "out of iterations" : "no step possible"), st.locked);
+        for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
+        return ran && apply && st.converged && transform_cloud(st.T);
+    }
     /* global registration of this planner's cloud, the scan, to the cloud of ref (ppp_register_global): the starts
        the two clouds' principal frames imply, a coarse chain from each side by side, the fine chain from the cheapest.  st.fine.T
        carries a scan point into ref's frame; cands, when asked for, receives one entry per start.  Needs no pass and no start,

@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
  * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map, the registration, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h, ppp_deviation.h and ppp_registration.h; of the handle and the pass it
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h, ppp_deviation.h, ppp_registration.h and ppp_trimmed.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -15,6 +15,7 @@
 #include "ppp_feed.h"
 #include "ppp_deviation.h"
 #include "ppp_registration.h"
+#include "ppp_trimmed.h"
 #include <cstring>
 
 extern "C" {
@@ -886,14 +887,25 @@ static int registration_setup(ppp_handle h, ppp_handle ref, const ppp_registrati
 /* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
    then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
    transforms, the sums and the rows stay on the device, a chain that has ended turns the rest of its launches into returns --
-   and one wait.  !loop: the one evaluation of ppp_get_registration_terms. */
+   and one wait.  !loop: the one evaluation of ppp_get_registration_terms.  trim (ppp_register_trimmed): an
+   evaluation is k_trim_pair, k_trim_narrow<1>, k_trim_narrow<2> and k_trim_terms instead of k_reg_terms -- its 29 words are over
+   the kept pairs --, k_trim_scatter follows the chain, and the rows and the maps go to trim's arrays. */
+struct TrimCall {
+    double keep;
+    ppp_trimmed_registration_row *rows;
+    unsigned char *status;
+    float *d2;
+    size_t cap;
+};
+
 static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0, bool loop,
-                              ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats)
+                              ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats, const TrimCall *trim = nullptr)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!ref || !rp) return fail(h, PPP_ERR_ARG, "registration: no reference handle or no parameters");
-    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "registration: rows is NULL with row_cap > 0");
+    if (!rows && !(trim && trim->rows) && row_cap) return fail(h, PPP_ERR_ARG, "registration: rows is NULL with row_cap > 0");
+    if (trim && !(trim->keep > 0.0 && trim->keep <= 1.0)) return fail(h, PPP_ERR_ARG, "trimmed registration: keep must be in (0, 1]");
     const ppp_registration_params P = *rp;
     IcpFrame F;
     int rc = registration_params_ok(h, P, F);
@@ -917,12 +929,38 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
     HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
     /* grid-stride: the workgroups, and with them the atomics of an evaluation, are capped by the device, not by the cloud */
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
+    const size_t N1 = std::max<size_t>(N, 1);
+    TrimCut *cuts = nullptr;
+    if (trim) {
+        static_assert(sizeof(TrimCut) == 8 * sizeof(unsigned), "TrimCut is eight words");
+        HIPCHK(h, G.partner.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1))); HIPCHK(h, G.key.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1)));
+        HIPCHK(h, G.hist.ensure(TRIM_WORDS * evals)); HIPCHK(h, G.cuts.ensure(8 * evals));
+        HIPCHK(h, G.tstatus.ensure(N1)); HIPCHK(h, G.td2.ensure(N1));
+        cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+        /* every evaluation has histograms of its own: one clear on the stream before the chain, none between iterations */
+        HIPCHK(h, hipMemsetAsync(G.hist.p, 0, TRIM_WORDS * evals * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(G.cuts.p, 0, 8 * evals * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(G.tstatus.p, PPP_TRIM_DROPPED, N1, h->stream)); /* points outside the index: not finite */
+        HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(G.td2.p), (int)TRIM_NAN, N1, h->stream));
+    }
     for (int k = 0; k <= iterations; ++k) {
-        LAUNCH(h, "k_reg_terms", k_reg_terms, grid, ICP_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
-               G.acc.p + ICP_WORDS * (size_t)k);
+        if (trim) {
+            unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+            LAUNCH(h, "k_trim_pair", k_trim_pair, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
+                   G.partner.p, G.key.p, hist);
+            LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, trim->keep, cuts + k);
+            LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, trim->keep,
+                   cuts + k);
+            LAUNCH(h, "k_trim_terms", k_trim_terms, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), F, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+                   G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.acc.p + ICP_WORDS * (size_t)k);
+        } else
+            LAUNCH(h, "k_reg_terms", k_reg_terms, grid, ICP_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
+                   G.acc.p + ICP_WORDS * (size_t)k);
         if (k < iterations)
             LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, G.acc.p + ICP_WORDS * (size_t)k, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
     }
+    if (trim)
+        LAUNCH(h, "k_trim_scatter", k_trim_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, ctl, cuts, (int)evals, (int)N1, G.tstatus.p, G.td2.p);
     IcpCtl C;
     HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
     if (C.steps < 0 || C.steps > iterations || (!C.done && C.steps != iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
@@ -953,6 +991,23 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
     }
     const size_t k = std::min(row_cap, last + 1);
     if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    if (trim) {
+        std::vector<TrimCut> cut(last + 1);
+        HIPCHK(h, copy_sync(h, cut.data(), G.cuts.p, (last + 1) * sizeof(TrimCut), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i <= last; ++i)
+            if (cut[i].paired > (unsigned)std::max(nq, 0) || R[i].pairs > cut[i].paired || (cut[i].paired && R[i].pairs < cut[i].k))
+                return fail(h, PPP_ERR_HIP, "trimmed registration: cut corrupt");
+        for (size_t i = 0; trim->rows && i < k; ++i) {
+            ppp_trimmed_registration_row &o = trim->rows[i];
+            memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
+            o.row = R[i];
+            o.paired = cut[i].paired;
+            memcpy(&o.trim_d2, &cut[i].tau, sizeof(float));
+        }
+        const size_t m = std::min(trim->cap, N);
+        if (trim->status && m) HIPCHK(h, copy_sync(h, trim->status, G.tstatus.p, m, hipMemcpyDeviceToHost));
+        if (trim->d2 && m) HIPCHK(h, copy_sync(h, trim->d2, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return PPP_OK;
 }
 
@@ -966,6 +1021,23 @@ int ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp
                  ppp_registration_stats *stats)
 {
     return registration_chain(h, ref, rp, T0_12, true, rows, row_cap, stats);
+}
+
+void ppp_default_trimmed_registration_params(ppp_trimmed_registration_params *tp)
+{
+    if (!tp) return;
+    ppp_default_registration_params(&tp->icp);
+    tp->keep = 0.8;
+}
+
+int ppp_register_trimmed(ppp_handle h, ppp_handle ref, const ppp_trimmed_registration_params *tp, const double *T0_12,
+                         ppp_trimmed_registration_row *rows, size_t row_cap, unsigned char *status, float *d2, size_t cap,
+                         ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    if (!tp) return fail(h, PPP_ERR_ARG, "trimmed registration: no parameters");
+    const TrimCall trim = {tp->keep, rows, status, d2, cap};
+    return registration_chain(h, ref, &tp->icp, T0_12, true, nullptr, row_cap, stats, &trim);
 }
 
 /* The ten words of side's cloud (k_cloud_moments on side's stream, one wait) and the frame they imply; side's index is

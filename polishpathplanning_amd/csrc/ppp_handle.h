@@ -309,6 +309,13 @@ struct ppp_handle_s {
         DevBuf<ppp_registration_row> mrows;
         DevBuf<int> mctl, qcnt;
         DevBuf<float4> queries;
+        /* ppp_register_trimmed: per query in slab order the reference point of its pair and the key of the pair's d2 (the last
+           evaluation's), per evaluation the three digit histograms and the cut (TrimCut, as words), and the two maps by cloud
+           index */
+        DevBuf<float4> partner;
+        DevBuf<unsigned> key, hist, cuts;
+        DevBuf<unsigned char> tstatus;
+        DevBuf<float> td2;
     } registration;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */

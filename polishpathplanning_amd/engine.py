@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -176,6 +176,10 @@ def lib():
         L.ppp_default_registration_params.restype = None
         L.ppp_get_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
         L.ppp_register.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
+        L.ppp_default_trimmed_registration_params.argtypes = [C.POINTER(TrimmedRegistrationParams)]
+        L.ppp_default_trimmed_registration_params.restype = None
+        L.ppp_register_trimmed.argtypes = [vp, vp, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow), sz, C.POINTER(C.c_ubyte), fp,
+                                           sz, C.POINTER(RegistrationStats)]
         L.ppp_transform_cloud.argtypes = [vp, dp]
         L.ppp_get_cloud_moments.argtypes = [vp, C.POINTER(CloudFrame)]
         L.ppp_cloud_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
@@ -397,6 +401,29 @@ class RegistrationStats(C.Structure):
     _fields_ = [("n", C.c_size_t), ("indexed", C.c_size_t), ("steps", C.c_int), ("converged", C.c_int), ("locked", C.c_int),
                 ("shift", C.c_int), ("centre", C.c_double * 3), ("length", C.c_double), ("T", C.c_double * 12),
                 ("pairs_before", C.c_size_t), ("pairs_after", C.c_size_t), ("rms_before", C.c_double), ("rms_after", C.c_double)]
+
+
+class TrimmedRegistrationParams(C.Structure):
+    """ppp_trimmed_registration_params"""
+    _fields_ = [("icp", RegistrationParams), ("keep", C.c_double)]
+
+
+class TrimmedRegistrationRow(C.Structure):
+    """ppp_trimmed_registration_row"""
+    _fields_ = [("row", RegistrationRow), ("paired", C.c_size_t), ("trim_d2", C.c_float)]
+
+
+TRIM_KEPT, TRIM_TRIMMED, TRIM_UNPAIRED, TRIM_DROPPED = range(4)  # PPP_TRIM_*
+
+
+def _trimmed_registration_row(r):
+    """a TrimmedRegistrationRow as a dict: _registration_row's fields (pairs = kept) with paired and trim_d2 (a Python float of
+    the float32; trim_bits its bit pattern)"""
+    out = _registration_row(r.row)
+    out["paired"] = int(r.paired)
+    out["trim_d2"] = float(r.trim_d2)
+    out["trim_bits"] = int(np.array([r.trim_d2], np.float32).view(np.uint32)[0])
+    return out
 
 
 def _registration_row(r):
@@ -1175,6 +1202,35 @@ class Engine:
         self._chk(self.L.ppp_register(self.h, ref.h, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st)))
         stats = _registration_stats(st)
         return stats["T"].copy(), [_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], stats
+
+    def register_trimmed(self, ref, keep=0.8, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
+        """(T float64[3, 4], rows, status uint8[n], d2 float32[n], stats): trimmed point-to-plane ICP (ppp_register_trimmed):
+        register()'s loop in which only the share `keep` of an evaluation's pairs with the smallest pair distance enters its
+        sums, so that what the scan shows and the reference does not (a clamp, a burr, an overhang) does not pull the fit.
+        rows[k]: register()'s row over the kept pairs (pairs = kept) with paired, trim_d2 (the largest kept d2; NaN without a
+        pair) and trim_bits; status / d2 describe the last evaluation by cloud index: TRIM_KEPT, TRIM_TRIMMED, TRIM_UNPAIRED,
+        TRIM_DROPPED and the pair's float d2 (NaN without one); stats as register()'s over the kept pairs.  keep = 1 is
+        register() bit for bit.  maps=False returns None for the two maps"""
+        tp = TrimmedRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(keep))
+        cap = max(int(iterations), 0) + 1
+        rows = (TrimmedRegistrationRow * cap)()
+        st = RegistrationStats()
+        t = _t12(T0)
+        status = d2 = None
+        n = 0
+        if maps:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            status = np.zeros(max(n, 1), np.uint8)
+            d2 = np.zeros(max(n, 1), np.float32)
+        self._chk(self.L.ppp_register_trimmed(self.h, ref.h, C.byref(tp), None if t is None else _d(t), rows, cap,
+                                              None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                              None if d2 is None else d2.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(st)))
+        stats = _registration_stats(st)
+        if maps:
+            status, d2 = status[:n], d2[:n]
+        return stats["T"].copy(), [_trimmed_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, d2, stats
 
     def cloud_moments(self):
         """ppp_get_cloud_moments: the frame dict of the resident cloud (count, ms, c, L, the ten integer words, mean, axes with
