@@ -428,7 +428,8 @@ int ppp_write_feed_file(const char *path, const float *wp6, const ppp_feed_row *
    PPP_ERR_ARG: dp or ref NULL; max_dist not > 0 (NaN included); smooth_radius negative or not finite; allowance not finite;
    gain negative or not finite; no cloud on either handle; handles on different devices; smooth_radius > 0 with a max_dist that
    is not finite or with (double)max_dist 2^24 n >= 2^62 (the integer sum could overflow).  PPP_ERR_UNSUPPORTED when either
-   handle is a slice-range handle (slice_begin / slice_end) or a part handle (ppp_set_cloud_part). */
+   handle is a slice-range handle (slice_begin / slice_end; ppp_get_deviation_tile, further down, answers for the points such a
+   handle owns) or a part handle (ppp_set_cloud_part). */
 enum { PPP_DEV_MATCHED = 0, PPP_DEV_TOO_FAR = 1, PPP_DEV_NO_NORMAL = 2, PPP_DEV_DROPPED = 3 };
 typedef struct {
     float  max_dist;       /* mm, resident units: > 0 finite, or +INFINITY for no limit */
@@ -809,6 +810,59 @@ int ppp_get_regions_tile(ppp_handle h, int source, const unsigned char *mask, fl
 int ppp_merge_region_tiles(size_t tiles, const int *const *labels, const ppp_region_part *const *parts,
                            const ppp_region_halo *const *halos, const ppp_region_tile_stats *stats,
                            int *out_labels, size_t cap, ppp_region *regions, size_t region_cap, ppp_region_stats *out_stats);
+/* ---- the deviation map tiled over slice ranges ----
+   ppp_get_deviation for the points a handle owns.  h: a slice-range handle of the scan (it holds the whole cloud and indexes
+   its range plus range_margin), or a whole-cloud handle, which owns every indexed point; ownership is ppp_range_owned's rule
+   and no other.  ref: a whole-cloud handle of the reference, or a slice-range handle of it.  The two clouds are registered in
+   one frame, so the scan's cuts are x coordinates of the reference as well.
+     halo      mm, finite, >= max_dist + smooth_radius (the float sum; so max_dist must be finite): how far beyond the owned
+               interval [own_lo, own_hi) the call may have to look -- a partner lies within max_dist of a point that is evaluated
+               because it lies within smooth_radius of an owned one.  W(r) = [nextbelow(own_lo - 1.0001f r), nextabove(own_hi +
+               1.0001f r)] in float: the interval widened by r with room for the roundings of a float distance test.  ref must
+               index W(halo + ref's normal_radius) (a partner's normal reads that neighbourhood) unless its index reaches the
+               reference's end on that side; h must index W(smooth_radius) likewise, and evaluates the points in it.  Both are
+               decided on the host from the two handles' plans, before any launch: no index is built and no kernel runs on
+               either handle for a call that is refused (a handle plans when its cloud is set; only one whose parameters
+               changed since makes its plan first).  What does not reach is PPP_ERR_ARG, never a silent TOO_FAR.
+     maps      by cloud index of h, the first min(cap, n) entries.  For every OWNED point all five hold exactly the bits
+               ppp_get_deviation gives for the same two clouds on whole-cloud handles with the same dp: the slab grids and point
+               orders are the whole clouds', a reference range handle's points carry their whole-cloud indices (the tie rule and
+               ref_index are the whole reference's), and the smoothing sums integers.  Every other point has status
+               PPP_DEV_DROPPED, ref_index -1, deviation and smoothed the NaN, target +0, and owned[i] = 0 (owned[i] = 1 for an
+               owned point).  The halo points the smoothing needed are evaluated, enter the owned points' sums and are reported
+               nowhere.
+     part      over the OWNED points: n = cloud->size() of h; owned, and evaluated = owned + halo points; matched, too_far,
+               no_normal (an owned point is indexed: never DROPPED); proud, below; min_dev / max_dev over v (NaN when matched ==
+               0); fix_sum = the integer sum of llrint(v_i 2^24); max_dist2; the owned interval; sum_parts = the number of
+               contiguous parts ppp_get_deviation's fixed-order sums cut a map of n entries into on h's device.
+   Needs clouds and parameters, not a pass; builds what ppp_get_deviation builds, waits and blocks as it does, keeps nothing and
+   changes nothing stored on either handle; a window-path handle stays on the window path.  Every output may be NULL.
+   PPP_ERR_ARG as ppp_get_deviation, and: max_dist not finite, halo below max_dist + smooth_radius or not finite, the two range
+   conditions above.  PPP_ERR_UNSUPPORTED when either handle is a part handle (ppp_set_cloud_part). */
+typedef struct {
+    size_t n, owned, evaluated;
+    size_t matched, too_far, no_normal;  /* the owned points by status */
+    size_t proud, below;
+    double min_dev, max_dev;             /* over v of the owned matched points; NaN when matched == 0 */
+    long long fix_sum;                   /* the sum of llrint(v 2^24) over them */
+    float  max_dist2;                    /* NaN when matched == 0 */
+    float  own_lo, own_hi;               /* the owned interval [own_lo, own_hi) */
+    int    sum_parts;
+} ppp_deviation_tile_stats;
+int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, float halo,
+                           double *deviation, double *smoothed, int *ref_index, unsigned char *status,
+                           double *target, unsigned char *owned, size_t cap, ppp_deviation_tile_stats *part);
+/* Merges the parts of tiles whose ranges tile the walk into ppp_get_deviation's statistics of the whole cloud, bit for bit
+   (host only: no handle, no device).  tile t gives parts[t] and its maps as ppp_get_deviation_tile returned them, n entries
+   each: v[t] (its smoothed map: the deviation where smooth_radius == 0), status[t], target[t], owned[t].  The counts, fix_sum
+   and the extrema merge by addition and minimum / maximum; dropped = n - the owned points.  hist depends on the span of the
+   WHOLE cloud, and rms_dev / target_sum are sums of doubles in ppp_removal_stats' fixed order -- sum_parts contiguous parts of
+   the map, inside a part 256 strided shares in index order and a fixed tree over them, the parts in order --, which no tile can
+   add up on its own: the merge computes these three here, on the host, from the union of the owned entries in that order.
+   PPP_ERR_ARG: a NULL argument, tiles that disagree on n or sum_parts, a point two tiles own, a part that is not its maps'. */
+int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *parts, const double *const *v,
+                              const unsigned char *const *status, const double *const *target,
+                              const unsigned char *const *owned, ppp_deviation_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

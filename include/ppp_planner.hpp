@@ -441,6 +441,27 @@ public:
         }
         return rc == PPP_OK ? true : report(rc);
     }
+    /* deviation() for the points this planner owns (ppp_get_deviation_tile): this planner holds the scan with a
+       slice range (or whole: it then owns everything), ref the reference, whole or a slice range that covers the owned interval
+       widened by halo >= dp.max_dist + dp.smooth_radius.  part is what ppp_merge_deviation_tiles takes, with the maps asked for
+       here: smoothed, status, target and owned, by cloud index */
+    bool deviation_tile(const Planner &ref, ppp_deviation_tile_stats &part, const ppp_deviation_params &dp, float halo,
+                        std::vector<double> *target = nullptr, std::vector<double> *smoothed = nullptr,
+                        std::vector<unsigned char> *status = nullptr, std::vector<unsigned char> *owned = nullptr)
+    {
+        size_t n = 0;
+        int rc = (target || smoothed || status || owned) ? ppp_num_points(h_, &n) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (target) target->assign(n, 0.0);
+            if (smoothed) smoothed->assign(n, 0.0);
+            if (status) status->assign(n, (unsigned char)PPP_DEV_DROPPED);
+            if (owned) owned->assign(n, (unsigned char)0);
+            rc = ppp_get_deviation_tile(h_, ref.h_, &dp, halo, nullptr, smoothed ? smoothed->data() : nullptr, nullptr,
+                                        status ? status->data() : nullptr, target ? target->data() : nullptr, owned ? owned->data() : nullptr, n,
+                                        &part);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
     /* ppp_default_deviation_params with what the environment sets of PPP_DEVIATION_MAXDIST, PPP_DEVIATION_SMOOTH,
        PPP_DEVIATION_ALLOWANCE and PPP_DEVIATION_GAIN (the example programs' knobs) */
     static ppp_deviation_params deviation_params_env()

@@ -1,7 +1,7 @@
 /*
  * ppp_contact.hip -- the contact queries of the C ABI (include/ppp_hip.h) on a finished pass or a resident cloud: coverage,
- * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map, the registration, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
- * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h, ppp_deviation.h, ppp_registration.h and ppp_trimmed.h; of the handle and the pass it
+ * path coverage, path contacts, path removal, the dwell schedule, the feed schedule, the deviation map and its tiles, the registration, ppp_area2cloud, the principal curvatures, the contact field and its tiles, the regions,
+ * their tiles and the merge.  The unit owns the kernels of ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h, ppp_feed.h, ppp_deviation.h, ppp_deviation_tile.h, ppp_registration.h and ppp_trimmed.h; of the handle and the pass it
  * sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -14,6 +14,7 @@
 #include "ppp_dwell.h"
 #include "ppp_feed.h"
 #include "ppp_deviation.h"
+#include "ppp_deviation_tile.h"
 #include "ppp_registration.h"
 #include "ppp_trimmed.h"
 #include <cstring>
@@ -1645,6 +1646,216 @@ int ppp_merge_region_tiles(size_t tiles, const int *const *labels, const ppp_reg
         if (v < 0) return PPP_ERR_ARG; /* a label without its part row */
         out_labels[i] = acc[find((size_t)v)].label;
     }
+    return PPP_OK;
+}
+
+/* a handle of ppp_get_deviation_tile, scan or reference: a cloud, whole or a slice range of it.  Two steps, with the range
+   checks of the call between them: the plan (what the handle indexes and owns; no index is built for it), then the slab index,
+   complete.  Errors are reported on h, as deviation_side's. */
+static int deviation_tile_plan(ppp_handle h, ppp_handle side, const char *who)
+{
+    const std::string w = std::string("deviation tile: ") + who;
+    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
+    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
+    int rc = plan_ready(side);
+    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
+    return PPP_OK;
+}
+static int deviation_tile_index(ppp_handle h, ppp_handle side, const char *who)
+{
+    const std::string w = std::string("deviation tile: ") + who;
+    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
+    const int ns = side->hmeta.n_sorted;
+    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
+    return PPP_OK;
+}
+
+/* [own_lo, own_hi) widened by r with room for the roundings (B.82): r times the 1.0001 of the margin tests, which covers the
+   float product dx dx against r r, and one float further out, which covers the rounding of the sum itself -- at coordinates of
+   metres half an ulp is more than r / 10 000.  An empty interval stays empty. */
+static void widened(const TileRange &T, float r, float &lo, float &hi)
+{
+    lo = nextafterf(T.own_lo - r * 1.0001f, -INFINITY); hi = nextafterf(T.own_hi + r * 1.0001f, INFINITY);
+}
+
+/* the slabs [b0, b1) a handle's index sorted: all of them, or those of a slice-range handle's interval (slab_geom) */
+static void sorted_slabs(const ppp_handle s, int &b0, int &b1)
+{
+    const SlabGeom G = slab_geom(s);
+    b0 = G.first_slab; b1 = std::min(s->B, G.first_slab + G.g_sort);
+}
+
+/* The deviation map of the points h owns: both plans, the range checks on the host, both indices, then the
+   reference's normal field on its own stream, one wait for that stream, k_devt_fill, k_devt_nearest, k_devt_smooth where asked and
+   k_devt_target back to back on the scan's stream, and one wait.  The buffers are ppp_get_deviation's: nothing is kept. */
+int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, float halo, double *deviation, double *smoothed,
+                           int *ref_index, unsigned char *status, double *target, unsigned char *owned, size_t cap,
+                           ppp_deviation_tile_stats *part)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !dp) return fail(h, PPP_ERR_ARG, "deviation tile: no reference handle or no parameters");
+    const ppp_deviation_params P = *dp;
+    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, "deviation tile: max_dist must be > 0");
+    if (!std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, "deviation tile: a tile needs a finite max_dist: the halo must hold every partner");
+    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, "deviation tile: smooth_radius must be finite and >= 0");
+    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, "deviation tile: allowance must be finite");
+    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, "deviation tile: gain must be finite and >= 0");
+    if (!(halo >= P.max_dist + P.smooth_radius && halo <= 3.402823466e+38f))
+        return fail(h, PPP_ERR_ARG, "deviation tile: halo must be finite and at least max_dist + smooth_radius");
+    const bool smooth = P.smooth_radius > 0.f;
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "deviation tile: the two handles are on different devices");
+    int rc = deviation_tile_plan(h, ref, "the reference");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_tile_plan(h, h, "the scan"); if (rc) return rc; }
+    const size_t N = h->n;
+    if (smooth && (double)P.max_dist * DEV_FIXED * (double)N >= 4611686018427387904.0)
+        return fail(h, PPP_ERR_ARG, "deviation tile: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    /* From the two plans alone, before an index is built or a kernel launched.  What is evaluated: the owned interval widened by
+       smooth_radius.  What the reference must index: the owned interval widened by halo, and by its normal_radius beyond that --
+       the normal of a partner at the halo's edge reads that neighbourhood. */
+    TileRange T;
+    rc = tile_range(h, 0.f, T);
+    if (rc) return rc;
+    widened(T, P.smooth_radius, T.ev_lo, T.ev_hi);
+    if (leaves_indexed_range(h, T.ev_lo, T.ev_hi))
+        return fail(h, PPP_ERR_ARG, "deviation tile: the owned interval widened by smooth_radius reaches beyond the scan's indexed slice range: raise range_margin");
+    float need_lo, need_hi;
+    widened(T, halo + ref->P.normal_radius, need_lo, need_hi);
+    if (leaves_indexed_range(ref, need_lo, need_hi))
+        return fail(h, PPP_ERR_ARG, "deviation tile: the reference's indexed slice range does not cover the owned interval widened by halo + normal_radius");
+    rc = deviation_tile_index(h, ref, "the reference");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_tile_index(h, h, "the scan"); if (rc) return rc; }
+    rc = contact_buffers(ref); /* the normal field, on ref's stream */
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("deviation tile: the reference: ") + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    int pos0, pos1, hb0, hb1, rb0, rb1;
+    rc = tile_positions(h, T, pos0, pos1);
+    if (rc) return rc;
+    sorted_slabs(h, hb0, hb1); sorted_slabs(ref, rb0, rb1);
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.owned.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEVT_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    const size_t cap_grid = 2 * (size_t)h->num_cus;
+    LAUNCH(h, "k_devt_fill", k_devt_fill, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, cap_grid), DEV_T, 0, (int)N, D.dev.p,
+           smooth ? D.smoothed.p : nullptr, D.target.p, D.ref_index.p, D.status.p, D.owned.p);
+    if (pos1 > pos0) {
+        const size_t gq = ((size_t)(pos1 - pos0) + DEV_T - 1) / DEV_T;
+        LAUNCH(h, "k_devt_nearest", k_devt_nearest, (unsigned)gq, DEV_T, 0, h->sorted4.p, pos0, pos1, T, contact_index(ref), ref->hmeta.n_sorted,
+               rb0, rb1, P.max_dist * P.max_dist, D.dev.p, D.fix.p, D.d2.p, D.ref_index.p, D.status.p, D.owned.p);
+        if (smooth)
+            LAUNCH(h, "k_devt_smooth", k_devt_smooth, (unsigned)gq, DEV_T, 0, contact_index(h), pos0, pos1, T, hb0, hb1,
+                   P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p, D.smoothed.p);
+        LAUNCH(h, "k_devt_target", k_devt_target, (unsigned)std::min(gq, cap_grid), DEV_T, 0, h->sorted4.p, pos0, pos1, T, D.status.p, D.dev.p, v,
+               D.d2.p, D.ref_index.p, P.allowance, P.gain, D.target.p, D.acc.p);
+    }
+    unsigned long long acc[DEVT_ACC_WORDS];
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    const unsigned long long own = acc[0] + acc[1] + acc[2];
+    if (own + acc[DEVT_ACC_HALO] > (unsigned long long)(pos1 - pos0) || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
+        return fail(h, PPP_ERR_HIP, "deviation tile: statistics corrupt");
+    if (part) {
+        ppp_deviation_tile_stats st = {};
+        st.n = N; st.owned = (size_t)own; st.evaluated = (size_t)(own + acc[DEVT_ACC_HALO]);
+        st.matched = (size_t)acc[0]; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2];
+        st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
+        st.min_dev = st.max_dev = (double)NAN; st.max_dist2 = NAN;
+        if (st.matched) {
+            st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
+            st.fix_sum = (long long)acc[DEV_ACC_FIXSUM];
+            st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
+        }
+        st.own_lo = T.own_lo; st.own_hi = T.own_hi;
+        st.sum_parts = MapParts(h, N).grid;
+        *part = st;
+    }
+    const size_t k = std::min(cap, N);
+    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
+    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (owned && k) HIPCHK(h, copy_sync(h, owned, D.owned.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The merge of ppp_get_deviation_tile's parts (host only).  The integer fields add and fold; hist needs the global span, and
+   rms_dev / target_sum are ppp_get_deviation's fixed-order sums (B.46: k_dev_stats's partition into sum_parts contiguous parts
+   of the map, inside a part every one of PCON_T threads its strided share in index order, block_tree_sum's tree over the
+   threads, the parts in order), which no per-tile number can give: they are computed here from the union of the owned entries. */
+int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *parts, const double *const *v, const unsigned char *const *status,
+                              const double *const *target, const unsigned char *const *owned, ppp_deviation_stats *stats)
+{
+    if (!tiles || !parts || !v || !status || !target || !owned || !stats) return PPP_ERR_ARG;
+    const size_t N = parts[0].n;
+    const int grid = parts[0].sum_parts;
+    if (N > 0x7fffffffu || grid < 1 || (size_t)grid > std::max<size_t>(1, (N + PCON_T - 1) / PCON_T)) return PPP_ERR_ARG;
+    ppp_deviation_stats st = {};
+    unsigned long long knmin = 0, kmax = 0, fsum = 0;
+    unsigned kd2 = 0;
+    std::vector<int> owner(N, -1); /* who owns a point: the one tile whose owned map marks it */
+    size_t all_owned = 0;
+    for (size_t t = 0; t < tiles; ++t) {
+        const ppp_deviation_tile_stats &p = parts[t];
+        if (p.n != N || p.sum_parts != grid || (N && (!v[t] || !status[t] || !target[t] || !owned[t]))) return PPP_ERR_ARG;
+        if (p.matched + p.too_far + p.no_normal != p.owned || p.proud > p.matched || p.below > p.matched) return PPP_ERR_ARG;
+        size_t mine = 0, matched = 0;
+        for (size_t i = 0; i < N; ++i) {
+            if (!owned[t][i]) continue;
+            if (owner[i] >= 0) return PPP_ERR_ARG; /* owned twice */
+            owner[i] = (int)t;
+            ++mine; matched += status[t][i] == PPP_DEV_MATCHED;
+        }
+        if (mine != p.owned || matched != p.matched) return PPP_ERR_ARG; /* the part is not the maps' */
+        all_owned += mine;
+        st.matched += p.matched; st.too_far += p.too_far; st.no_normal += p.no_normal; st.proud += p.proud; st.below += p.below;
+        if (p.matched) {
+            knmin = std::max(knmin, ordered_key64(-p.min_dev)); kmax = std::max(kmax, ordered_key64(p.max_dev));
+            fsum += (unsigned long long)p.fix_sum;
+            kd2 = std::max(kd2, ordered_key(p.max_dist2));
+        }
+    }
+    st.n = N; st.dropped = N - all_owned; /* nobody's points: the non-finite ones */
+    st.min_dev = st.max_dev = st.mean_dev = st.rms_dev = (double)NAN; st.max_dist2 = NAN;
+    double span = 0.0;
+    if (st.matched) {
+        st.min_dev = -ordered_unkey64(knmin); st.max_dev = ordered_unkey64(kmax);
+        st.mean_dev = (double)(long long)fsum / (double)st.matched * (1.0 / DEV_FIXED);
+        st.max_dist2 = ordered_unkey(kd2);
+        span = fmax(fabs(st.min_dev), fabs(st.max_dev));
+    }
+    const size_t per = (N + (size_t)grid - 1) / (size_t)grid;
+    std::vector<double> s_sq(PCON_T), s_tg(PCON_T);
+    double sq_all = 0.0;
+    for (size_t g = 0; g < (size_t)grid; ++g) {
+        const size_t i0 = g * per, i1 = std::min(N, i0 + per);
+        for (size_t t = 0; t < PCON_T; ++t) {
+            double sq = 0.0, tg = 0.0;
+            for (size_t i = i0 + t; i < i1; i += PCON_T) {
+                if (owner[i] < 0 || status[(size_t)owner[i]][i] != PPP_DEV_MATCHED) continue;
+                const double x = v[(size_t)owner[i]][i];
+                sq += x * x; tg += target[(size_t)owner[i]][i];
+                int bin = PPP_CONTACT_BINS / 2;
+                if (span > 0.0) {
+                    const double f = floor((x / span + 1.0) * (double)(PPP_CONTACT_BINS / 2));
+                    bin = f < 0.0 ? 0 : (f > (double)(PPP_CONTACT_BINS - 1) ? PPP_CONTACT_BINS - 1 : (int)f);
+                }
+                ++st.hist[bin];
+            }
+            s_sq[t] = sq; s_tg[t] = tg;
+        }
+        for (size_t o = PCON_T / 2; o > 0; o >>= 1)
+            for (size_t t = 0; t < o; ++t) { s_sq[t] += s_sq[t + o]; s_tg[t] += s_tg[t + o]; }
+        sq_all += s_sq[0]; st.target_sum += s_tg[0];
+    }
+    if (st.matched) st.rms_dev = std::sqrt(sq_all / (double)st.matched);
+    *stats = st;
     return PPP_OK;
 }
 

@@ -1010,13 +1010,21 @@ int ensure_ready(ppp_handle h, bool need_gen, bool need_path)
     return PPP_OK;
 }
 
-static int ensure_index(ppp_handle h)
+/* the plan of the resident cloud, current: the range a handle indexes and owns is known (sb, se, incl_lo / incl_hi, S_cap) and no
+   index has been built for the asking.  A handle plans when its cloud is set; only one whose parameters changed since plans here. */
+int plan_ready(ppp_handle h)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->have_cloud) return fail(h, PPP_ERR_ARG, "no cloud set");
     { int rcs = settle(h); if (rcs) return rcs; }
     if (!h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
+    return PPP_OK;
+}
+
+static int ensure_index(ppp_handle h)
+{
+    { int rcp = plan_ready(h); if (rcp) return rcp; }
     if (!h->pass.index_built()) { int rc = enqueue_index(h); if (rc) return rc; }
     return PPP_OK;
 }

@@ -285,13 +285,14 @@ struct ppp_handle_s {
     } feed;
     /* deviation of this handle's cloud against another handle's (ppp_get_deviation): by cloud index the deviation, its local
        mean, its fixed-point term, the float d2, the reference index, the status and the target; the statistics' accumulators and
-       the workgroups' parts of the two fixed-order sums.  Nothing is kept between calls: the reference may have changed. */
+       the workgroups' parts of the two fixed-order sums.  Nothing is kept between calls: the reference may have changed.
+       ppp_get_deviation_tile runs in the same buffers, with the owned map beside them. */
     struct Deviation {
         DevBuf<double> dev, smoothed, target, psum;
         DevBuf<long long> fix;
         DevBuf<float> d2;
         DevBuf<int> ref_index;
-        DevBuf<unsigned char> status;
+        DevBuf<unsigned char> status, owned;
         DevBuf<unsigned long long> acc;
     } deviation;
     /* registration of this handle's cloud to another handle's (ppp_get_registration_terms, ppp_register): the chain's transforms
@@ -570,6 +571,7 @@ int settle(ppp_handle h);
 int fetch_meta(ppp_handle h);
 int map_dev_err(ppp_handle h);
 int ensure_ready(ppp_handle h, bool need_gen, bool need_path);
+int plan_ready(ppp_handle h);
 int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stride_bytes = 0, bool may_defer = false);
 
 #define HIPCHK(h, expr)                                                                               \

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -197,6 +197,11 @@ def lib():
                                            C.POINTER(RegionHalo), sz, C.POINTER(RegionTileStats)]
         L.ppp_merge_region_tiles.argtypes = [sz, C.POINTER(ip), C.POINTER(C.POINTER(RegionPart)), C.POINTER(C.POINTER(RegionHalo)),
                                              C.POINTER(RegionTileStats), ip, sz, C.POINTER(Region), sz, C.POINTER(RegionStats)]
+        ubp = C.POINTER(C.c_ubyte)
+        L.ppp_get_deviation_tile.argtypes = [vp, vp, C.POINTER(DeviationParams), C.c_float, dp, dp, ip, ubp, dp, ubp, sz,
+                                             C.POINTER(DeviationTileStats)]
+        L.ppp_merge_deviation_tiles.argtypes = [sz, C.POINTER(DeviationTileStats), C.POINTER(dp), C.POINTER(ubp), C.POINTER(dp), C.POINTER(ubp),
+                                                C.POINTER(DeviationStats)]
         L.ppp_principal_curvatures_at.argtypes = [vp, fp, sz, fp]
         L.ppp_eval_spline.argtypes = [vp, C.c_int, dp, sz, dp]
         L.ppp_ranged_x_index.argtypes = [vp, C.c_int, ip, sz, szp]
@@ -383,6 +388,48 @@ class DeviationStats(C.Structure):
     _fields_ = [("n", C.c_size_t), ("matched", C.c_size_t), ("too_far", C.c_size_t), ("no_normal", C.c_size_t), ("dropped", C.c_size_t),
                 ("proud", C.c_size_t), ("below", C.c_size_t), ("min_dev", C.c_double), ("max_dev", C.c_double), ("mean_dev", C.c_double),
                 ("rms_dev", C.c_double), ("max_dist2", C.c_float), ("target_sum", C.c_double), ("hist", C.c_size_t * CONTACT_BINS)]
+
+
+class DeviationTileStats(C.Structure):
+    """ppp_deviation_tile_stats"""
+    _fields_ = [("n", C.c_size_t), ("owned", C.c_size_t), ("evaluated", C.c_size_t), ("matched", C.c_size_t), ("too_far", C.c_size_t),
+                ("no_normal", C.c_size_t), ("proud", C.c_size_t), ("below", C.c_size_t), ("min_dev", C.c_double), ("max_dev", C.c_double),
+                ("fix_sum", C.c_longlong), ("max_dist2", C.c_float), ("own_lo", C.c_float), ("own_hi", C.c_float), ("sum_parts", C.c_int)]
+
+
+def _deviation_stats(st):
+    stats = {k: getattr(st, k) for k, _ in DeviationStats._fields_ if k != "hist"}
+    stats["hist"] = np.array(st.hist[:], np.int64)
+    return stats
+
+
+def merge_deviation_tiles(tiles):
+    """ppp_deviation_stats of the whole cloud, as Engine.deviation()'s dict and bit for bit, from the tiles of ranges that tile the
+    walk (ppp_merge_deviation_tiles: host only).  tiles = a sequence of Engine.deviation_tile() results (deviation, smoothed,
+    ref_index, status, target, owned, part).  The counts, the integer sum and the extrema merge from the parts; hist, rms_dev and
+    target_sum are computed here from the union of the owned entries of smoothed, status and target, in the whole-cloud call's
+    fixed order."""
+    L = lib()
+    T = len(tiles)
+    ub = C.POINTER(C.c_ubyte)
+    keep = [(np.ascontiguousarray(t[1], np.float64), np.ascontiguousarray(t[3], np.uint8), np.ascontiguousarray(t[4], np.float64),
+             np.ascontiguousarray(t[5], np.uint8)) for t in tiles]
+    dpp = C.POINTER(C.c_double)
+    vv = (dpp * T)(*[_d(k[0]) for k in keep])
+    ss = (ub * T)(*[k[1].ctypes.data_as(ub) for k in keep])
+    tt = (dpp * T)(*[_d(k[2]) for k in keep])
+    oo = (ub * T)(*[k[3].ctypes.data_as(ub) for k in keep])
+    parts = (DeviationTileStats * T)()
+    for i, t in enumerate(tiles):
+        for f, _ in DeviationTileStats._fields_:
+            setattr(parts[i], f, t[6][f])
+        if any(len(a) != t[6]["n"] for a in keep[i]):
+            raise PPPError(ERR_ARG, "ppp_merge_deviation_tiles: tile %d's maps do not hold n entries" % i)
+    st = DeviationStats()
+    rc = L.ppp_merge_deviation_tiles(T, parts, vv, ss, tt, oo, C.byref(st))
+    if rc:
+        raise PPPError(rc, "ppp_merge_deviation_tiles: a point owned twice, a part that is not its maps', or tiles that do not belong together")
+    return _deviation_stats(st)
 
 
 class RegistrationParams(C.Structure):
@@ -1174,9 +1221,34 @@ class Engine:
             self._chk(self.L.ppp_get_deviation(self.h, ref.h, C.byref(dp), _d(dev), _d(sm), _i(idx), status.ctypes.data_as(C.POINTER(C.c_ubyte)),
                                                _d(target), n, C.byref(st)))
             dev, sm, idx, status, target = dev[:n], sm[:n], idx[:n], status[:n], target[:n]
-        stats = {k: getattr(st, k) for k, _ in DeviationStats._fields_ if k != "hist"}
-        stats["hist"] = np.array(st.hist[:], np.int64)
-        return dev, sm, idx, status, target, stats
+        return dev, sm, idx, status, target, _deviation_stats(st)
+
+    def deviation_tile(self, ref, halo, max_dist=2.0, smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(deviation, smoothed, ref_index, status, target, owned uint8[n], part dict) of the points this engine OWNS -- a
+        slice-range engine of the scan, or a whole-cloud one, which owns every indexed point -- against the cloud of the engine
+        `ref`, whole or a slice range of the reference (ppp_get_deviation_tile).  The maps go by cloud index; an owned point's
+        entries are deviation()'s bits on whole-cloud engines, every other point has DEV_DROPPED, -1, NaN, 0 and owned 0.  halo
+        (mm) >= max_dist + smooth_radius, max_dist finite; `ref` must index the owned interval widened by halo and its
+        normal_radius, this engine's range_margin must cover smooth_radius.  part: n, owned, evaluated, matched, too_far,
+        no_normal, proud, below, min_dev, max_dev, fix_sum, max_dist2, own_lo, own_hi, sum_parts -- what merge_deviation_tiles()
+        takes.  maps=False returns six Nones and part"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = DeviationTileStats()
+        dev = sm = idx = status = target = owned = None
+        ub = C.POINTER(C.c_ubyte)
+        if not maps:
+            self._chk(self.L.ppp_get_deviation_tile(self.h, ref.h, C.byref(dp), float(halo), None, None, None, None, None, None, 0, C.byref(st)))
+        else:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            dev, sm, target = (np.zeros(max(n, 1), np.float64) for _ in range(3))
+            idx = np.zeros(max(n, 1), np.int32)
+            status, owned = (np.zeros(max(n, 1), np.uint8) for _ in range(2))
+            self._chk(self.L.ppp_get_deviation_tile(self.h, ref.h, C.byref(dp), float(halo), _d(dev), _d(sm), _i(idx), status.ctypes.data_as(ub),
+                                                    _d(target), owned.ctypes.data_as(ub), n, C.byref(st)))
+            dev, sm, idx, status, target, owned = dev[:n], sm[:n], idx[:n], status[:n], target[:n], owned[:n]
+        return dev, sm, idx, status, target, owned, {k: getattr(st, k) for k, _ in DeviationTileStats._fields_}
 
     def registration_terms(self, ref, T=None, max_dist=2.0, lock_eps=1e-9):
         """(row, stats) of one evaluation of the point-to-plane terms of this engine's cloud, the scan, moved by T (3 x 4, None:
