@@ -552,6 +552,7 @@ static int enqueue_window_finish(ppp_handle h, bool finish_lists)
 {
     WinArgs A = win_args(h);
     A.stage_lists = finish_lists ? 1 : 0;
+    if (h->quiet_finish) A.meta_host = nullptr; /* (win_publish_meta: no arrival counters, no write to pinned memory) */
     LAUNCH(h, "k_win_finish", k_win_finish, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
     return PPP_OK;
 }
@@ -958,6 +959,18 @@ static int enqueue_pass(ppp_handle h, float *dst_rows, size_t cap_rows, bool cha
     if (rc == PPP_OK && want_path) rc = ppp_get_path_async(h);
     h->out2 = nullptr; h->out2_cap = 0;
     --h->internal;
+    return rc;
+}
+
+/* A batch of ONE window-path member -- a stream of steps on one workpiece: the member's own three launches with their arguments
+   by value (a workgroup of the batched forms reads the kernel argument, a pointer, and then the member's record through it: a
+   dependent round trip at the front of each of three dependent launches, which only a batch of several needs).  The list goes
+   to the caller's rows, and the meta block is not published (as the batched forms do for one member: fetched on demand). */
+static int enqueue_solo_pass(ppp_handle h, float *dst_rows, size_t cap_rows)
+{
+    h->quiet_finish = true;
+    const int rc = enqueue_pass(h, dst_rows, cap_rows, true);
+    h->quiet_finish = false;
     return rc;
 }
 
@@ -1647,7 +1660,8 @@ int ppp_get_path_async(ppp_handle h)
         int rcw = enqueue_window_finish(h, finish_lists);
         if (rcw) return rcw;
         h->pass.path_enqueued(!h->ranged, true, finish_lists);
-        h->pass.meta_will_arrive(MetaAt::pinned()); /* the finish launch's last workgroup leaves the meta block in hmeta_pinned */
+        /* the finish launch's last workgroup leaves the meta block in hmeta_pinned (not for a batch of one: fetched on demand) */
+        h->pass.meta_will_arrive(h->quiet_finish ? MetaAt::on_demand() : MetaAt::pinned());
         return PPP_OK;
     }
     const SlabGeom G = slab_geom(h);
@@ -1819,8 +1833,8 @@ int upload_members_win(ppp_handle lead, BatchGraph *bg, float *dst_dev, const si
         h->out2_cap = dst_dev ? (int)std::min<size_t>(cap_rows[i], 0x7fffffff) : 0;
         WinArgs &A = mem[i];
         A = win_args(h);
-        /* a member publishes its meta block into the batch's pinned array; a batch of ONE -- a stream of steps on one workpiece -- does
-           not publish at all (the arrival counters are a microsecond at the end of every step): the block is fetched when somebody asks */
+        /* a member publishes its meta block into the batch's pinned array (a batch of ONE does not come here: ppp_run_batch_async runs
+           it by value, enqueue_solo_pass, and does not publish at all -- the arrival counters are a microsecond at the end of every step) */
         A.meta_host = count > 1 ? bg->hmetas->p + i : nullptr;
         h->out2 = nullptr; h->out2_cap = 0;
         A.g_scatter = std::max(1, (A.n + scat_pts - 1) / scat_pts); /* (the members' partials are sized for the largest grid of any form) */
@@ -1965,6 +1979,14 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
     };
     /* kernel timing brackets every launch with events: the batched launches run eagerly on the lead's stream (timers of the
        lead), members that need their own launch sequence run as plain per-handle calls */
+    /* one window-path member: its own by-value launches (enqueue_solo_pass), timed under their own names or captured as the graph
+       (a plan of 2 points per binning thread -- tuning builds only -- keeps the batched launch, which runs 4 at least) */
+    const bool solo = count == 1 && allwin && lead->win_ppt >= 4;
+    if (solo && plain) {
+        int rc = enqueue_solo_pass(lead, dst_of(0), cap_of(0));
+        remember_dst(0);
+        return rc;
+    }
     const bool eager = plain && batched;
     if (plain && !batched) {
         for (size_t i = 0; i < count; ++i) {
@@ -1976,7 +1998,7 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
     }
     BatchGraph *bg = nullptr;
     for (BatchGraph *cand : lead->batches) {
-        bool same = cand && cand->hs.size() == count && cand->dst == dst_dev && cand->batched == batched && cand->eager == eager && cand->win == allwin;
+        bool same = cand && cand->hs.size() == count && cand->dst == dst_dev && cand->batched == batched && cand->eager == eager && cand->win == allwin && cand->solo == solo;
         for (size_t i = 0; same && i < count; ++i)
             same = cand->hs[i] == hs[i] && cand->epochs[i] == hs[i]->epoch && (!dst_dev || (cand->off[i] == offset_rows[i] && cand->cap[i] == cap_rows[i]));
         if (same) { bg = cand; break; }
@@ -1995,12 +2017,20 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
         bg->batched = batched;
         bg->win = allwin;
         bg->eager = eager;
+        bg->solo = solo;
         if (dst_dev) { bg->off.assign(offset_rows, offset_rows + count); bg->cap.assign(cap_rows, cap_rows + count); }
         auto discard = [&]() { delete lead->batches[slot]; lead->batches[slot] = nullptr; };
         int rc = PPP_OK;
         const char *where = "";
         hipError_t e = hipSuccess;
-        if (batched) {
+        if (solo) { /* the member's own pass, arguments by value: nothing to upload, no meta array */
+            if (getenv("PPP_WIN_DEBUG")) /* (the record upload_members_win prints for a batch of several, with this plan's own forms) */
+                fprintf(stderr, "[ppp] window batch: 1 members, %d slices, threads %d, NBc %d, lds %zu B, ppt %d x %d threads (by value)\n", std::max(0, lead->se - lead->sb),
+                        lead->win_threads, win_throughput_launch(lead, lead->se - lead->sb) ? lead->win_NBc_thr : lead->win_NBc,
+                        win_slice_lds_for(lead, win_throughput_launch(lead, lead->se - lead->sb) ? lead->win_NBc_thr : lead->win_NBc), lead->win_ppt, lead->win_scat_threads);
+            HIPCHK(lead, hipStreamBeginCapture(lead->stream, hipStreamCaptureModeThreadLocal));
+            rc = enqueue_solo_pass(lead, dst_of(0), cap_of(0));
+        } else if (batched) {
             /* ONE launch per stage over all members.  Records and meta array first, outside the capture. */
             hipError_t ea = bg->members.ensure(count);
             if (ea == hipSuccess) ea = bg->wmembers.ensure(count);
@@ -2064,8 +2094,9 @@ int ppp_run_batch_async(ppp_handle *hs, size_t count, float *dst_dev, const size
     else HIPCHK(lead, hipGraphLaunch(bg->ge, lead->stream));
     for (size_t i = 0; i < count; ++i) {
         ppp_handle h = hs[i];
-        /* batched launches publish the members' meta blocks in the batch's pinned array -- a batch of one does not publish at all:
-           fetched on demand --; a member with a branch of its own ends with its own copy */
+        /* batched launches publish the members' meta blocks in the batch's pinned array -- a batch of one (by value on the window
+           path, batched launches on the slab path) does not publish at all: fetched on demand --; a member with a branch of its own
+           ends with its own copy */
         const MetaAt at = !bg->batched ? MetaAt::pinned() : (count > 1 ? MetaAt::batch_slot(bg->hmetas, i) : MetaAt::on_demand());
         h->pass.pass_enqueued(batch_member_ran_window(bg, h), !h->ranged, at, i == 0 ? nullptr : lead->stream);
         remember_dst(i);

@@ -440,6 +440,7 @@ struct ppp_handle_s {
     bool rec_current = false;   /* plan_auto holds the record of the resident cloud (it came through k_ingest_minmax and was not altered since) */
     bool plan_walk_ok = false;  /* the window plan's S, pad and plane table are the device's own, bit for bit (plan_window: census that came with the cloud, or inherited) */
     bool chain_calls = false;       /* GenPath is followed by getPath in the same enqueue: its meta copy is skipped */
+    bool quiet_finish = false;      /* the window path's finish launch does not publish the meta block (a batch of one: fetched when somebody asks) */
     float *out2 = nullptr;          /* batched form: the emitting launch also writes the list here (at most out2_cap rows) */
     int out2_cap = 0;
     float *last_out2 = nullptr;     /* where the last batch put this handle's list: a re-run after an LDS overflow writes there too */
@@ -535,6 +536,7 @@ struct BatchGraph {
     SlabGeom geom; /* launch geometry over all members (slab path) */
     DevBuf<SlabArgs> members;
     bool win = false;              /* every member runs the window path: the three k_win_*_b launches */
+    bool solo = false;             /* ONE window-path member: its own three launches with the arguments by value (no record, no meta array) */
     DevBuf<WinArgs> wmembers;
     int win_ppt = 4, win_scat_threads = WSC_T, win_threads = 256, gx_scat = 1, gx_slice = 1, gx_wfin = 1;
     bool win_staged = false;

@@ -1479,9 +1479,22 @@ __global__ void __launch_bounds__(T) k_win_scatter_b(const WinArgs *__restrict__
     if (STAGED) win_scatter_staged_loop<PPT>(A, blockIdx.x, A.g_scatter);
     else win_scatter_body<PPT, false, T>(A, blockIdx.x);
 }
-template <int TMAX>
-__global__ void __launch_bounds__(TMAX) k_win_slice(WinArgs A)
+/* The arguments of a by-value launch, read where they lie: in the kernel-argument segment, field by field, when a phase needs
+   them -- as the batched forms read a member's record, without the pointer in between.  (Through the parameter itself the compiler
+   knows every field to be loadable at the kernel's entry and hoists all the loads there: the slice kernel then starts with 55
+   dwords of scalar loads in three dependent rounds, parks 69 scalar registers in the lanes of a VGPR and reserves 20 bytes of scratch
+   memory per thread for the rest of its spill slots.)  The record is the kernel's first and only explicit argument: offset 0 of
+   the segment.  The empty asm keeps the address opaque. */
+__device__ __forceinline__ const WinArgs &win_args_in_place()
 {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const WinArgs *)p;
+}
+template <int TMAX>
+__global__ void __launch_bounds__(TMAX) k_win_slice(WinArgs)
+{
+    const WinArgs &A = win_args_in_place();
     if ((int)blockIdx.x == A.g_slice) { win_verify_body(A); return; }
     win_slice_body<TMAX>(A, blockIdx.x);
 }
