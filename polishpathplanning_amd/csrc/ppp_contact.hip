@@ -19,6 +19,18 @@
 #include "ppp_trimmed.h"
 #include <cstring>
 
+/* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
+template <typename Stats>
+static void dev_stats_words(Stats &st, size_t N, const unsigned long long *acc)
+{
+    st.n = N; st.matched = (size_t)acc[0]; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2];
+    st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
+    st.min_dev = st.max_dev = (double)NAN; st.max_dist2 = NAN;
+    if (!st.matched) return;
+    st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
+    st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
+}
+
 extern "C" {
 
 /* the kernels' views of the handle's slab index / normal field and of its knot tables, as they stand when the launch is made */
@@ -745,19 +757,77 @@ void ppp_default_deviation_params(ppp_deviation_params *dp)
     dp->max_dist = INFINITY; dp->smooth_radius = 0.f; dp->allowance = 0.0; dp->gain = 1.0;
 }
 
-/* a handle of ppp_get_deviation, scan or reference: a cloud, all of it, its slab index complete.  Refusals and errors are
-   reported on h (the scan's handle, the call's first argument), whichever handle they are about */
+/* The checks of a scan-against-reference call's handle, scan or reference (w: "<call>: <which handle>"); refusals and errors are
+   reported on h, the call's first argument, whichever handle they are about.  deviation_side_cloud builds no index and launches
+   nothing (plan: the tile call's, whose range checks want what the handle owns); deviation_side_index builds the slab index. */
+static int deviation_side_cloud(ppp_handle h, ppp_handle side, const std::string &w, bool plan)
+{
+    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
+    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
+    const int rc = plan ? plan_ready(side) : PPP_OK;
+    return rc && side != h ? fail(h, rc, w + ": " + side->err) : rc;
+}
+static int deviation_side_index(ppp_handle h, ppp_handle side, const std::string &w, bool whole)
+{
+    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
+    if (whole && (side->ranged || side->use_part)) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
+    const int ns = side->hmeta.n_sorted;
+    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
+    return PPP_OK;
+}
+/* a handle of ppp_get_deviation, scan or reference: a cloud, all of it, its slab index complete */
 static int deviation_side(ppp_handle h, ppp_handle side, const char *who, const char *what = "deviation")
 {
     const std::string w = std::string(what) + ": " + who;
-    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
-    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
+    int rc = deviation_side_cloud(h, side, w, false);
+    if (rc) return rc;
     if (side->P.slice_begin != 0 || side->P.slice_end != 0) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
-    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
-    if (side->ranged || side->use_part) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
-    const int ns = side->hmeta.n_sorted;
-    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
+    return deviation_side_index(h, side, w, true);
+}
+
+/* both deviation calls' checks before they look at a handle, in the order they fire; w: the call's name, halo: the tile call's */
+static int deviation_call_ok(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, const std::string &w, const float *halo)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !dp) return fail(h, PPP_ERR_ARG, w + ": no reference handle or no parameters");
+    const ppp_deviation_params &P = *dp;
+    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, w + (halo ? ": max_dist must be > 0" : ": max_dist must be > 0 (+INFINITY: no limit)"));
+    if (halo && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": a tile needs a finite max_dist: the halo must hold every partner");
+    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, w + ": smooth_radius must be finite and >= 0");
+    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, w + ": allowance must be finite");
+    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, w + ": gain must be finite and >= 0");
+    if (!halo && P.smooth_radius > 0.f && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": smoothing needs a finite max_dist");
+    if (halo && !(*halo >= P.max_dist + P.smooth_radius && *halo <= 3.402823466e+38f))
+        return fail(h, PPP_ERR_ARG, w + ": halo must be finite and at least max_dist + smooth_radius");
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the two handles are on different devices");
+    return PPP_OK;
+}
+
+/* the integer sum of a neighbourhood or of the statistics: |deviation| <= about max_dist, n terms of it in 2^-24 mm */
+static bool deviation_sum_overflows(const ppp_deviation_params &P, size_t n) { return P.smooth_radius > 0.f && (double)P.max_dist * DEV_FIXED * (double)n >= 4611686018427387904.0; }
+
+/* the reference's normal field, on ref's stream, and the one wait for that stream */
+static int reference_normals(ppp_handle h, ppp_handle ref, const char *what)
+{
+    int rc = contact_buffers(ref);
+    if (rc) return ref == h ? rc : fail(h, rc, std::string(what) + ": the reference: " + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    return PPP_OK;
+}
+
+/* the maps' first k entries to the caller's arrays, those it gave (owned: the tile call's, behind the five maps) */
+static int deviation_copy_out(ppp_handle h, size_t k, const double *v, double *deviation, double *smoothed, int *ref_index, unsigned char *status, double *target,
+                              unsigned char *owned = nullptr)
+{
+    auto &D = h->deviation;
+    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
+    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (owned && k) HIPCHK(h, copy_sync(h, owned, D.owned.p, k, hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 
@@ -766,27 +836,17 @@ static int deviation_side(ppp_handle h, ppp_handle side, const char *who, const 
 int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, double *deviation, double *smoothed, int *ref_index,
                       unsigned char *status, double *target, size_t cap, ppp_deviation_stats *stats)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!ref || !dp) return fail(h, PPP_ERR_ARG, "deviation: no reference handle or no parameters");
+    int rc = deviation_call_ok(h, ref, dp, "deviation", nullptr);
+    if (rc) return rc;
     const ppp_deviation_params P = *dp;
-    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, "deviation: max_dist must be > 0 (+INFINITY: no limit)");
-    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, "deviation: smooth_radius must be finite and >= 0");
-    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, "deviation: allowance must be finite");
-    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, "deviation: gain must be finite and >= 0");
     const bool smooth = P.smooth_radius > 0.f;
-    if (smooth && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, "deviation: smoothing needs a finite max_dist");
-    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "deviation: the two handles are on different devices");
-    int rc = deviation_side(h, ref, "the reference");
+    rc = deviation_side(h, ref, "the reference");
     if (rc) return rc;
     if (ref != h) { rc = deviation_side(h, h, "the scan"); if (rc) return rc; }
     const size_t N = h->n;
-    /* the integer sum of a neighbourhood or of the statistics: |deviation| <= about max_dist, n terms of it in 2^-24 mm */
-    if (smooth && (double)P.max_dist * DEV_FIXED * (double)N >= 4611686018427387904.0)
-        return fail(h, PPP_ERR_ARG, "deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
-    rc = contact_buffers(ref); /* the normal field, on ref's stream */
-    if (rc) return ref == h ? rc : fail(h, rc, std::string("deviation: the reference: ") + ref->err);
-    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    rc = reference_normals(h, ref, "deviation");
+    if (rc) return rc;
     auto &D = h->deviation;
     const size_t N1 = std::max<size_t>(N, 1);
     const MapParts parts(h, N);
@@ -817,28 +877,16 @@ int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *
         return fail(h, PPP_ERR_HIP, "deviation: statistics corrupt");
     if (stats) {
         ppp_deviation_stats st = {};
-        const size_t m = (size_t)acc[0];
-        st.n = N; st.matched = m; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2]; st.dropped = (size_t)acc[3];
-        st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
+        dev_stats_words(st, N, acc);
+        st.dropped = (size_t)acc[3];
         double sq = 0.0;
         for (int g = 0; g < grid; ++g) { sq += psum[(size_t)g]; st.target_sum += psum[(size_t)grid + g]; }
-        st.min_dev = st.max_dev = st.mean_dev = st.rms_dev = (double)NAN; st.max_dist2 = NAN;
-        if (m) {
-            st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
-            st.mean_dev = (double)(long long)acc[DEV_ACC_FIXSUM] / (double)m * (1.0 / DEV_FIXED);
-            st.rms_dev = std::sqrt(sq / (double)m);
-            st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
-        }
+        st.mean_dev = st.matched ? (double)(long long)acc[DEV_ACC_FIXSUM] / (double)st.matched * (1.0 / DEV_FIXED) : (double)NAN;
+        st.rms_dev = st.matched ? std::sqrt(sq / (double)st.matched) : (double)NAN;
         for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[DEV_ACC_BINS + b];
         *stats = st;
     }
-    const size_t k = std::min(cap, N);
-    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
-    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
-    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
-    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
-    return PPP_OK;
+    return deviation_copy_out(h, std::min(cap, N), v, deviation, smoothed, ref_index, status, target);
 }
 
 void ppp_default_registration_params(ppp_registration_params *rp)
@@ -879,11 +927,11 @@ static int registration_setup(ppp_handle h, ppp_handle ref, const ppp_registrati
     }
     F.Ln = (((ext[0] + ext[1]) + ext[2]) * 0.5) + (double)P.max_dist;
     F.scale = std::ldexp(1.0, shift);
-    rc = contact_buffers(ref); /* the normal field, on ref's stream */
-    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
-    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
-    return PPP_OK;
+    return reference_normals(h, ref, "registration");
 }
+
+/* a chain's control words behind the one wait: 0 <= steps <= iterations, and a chain that has not ended took every step */
+static bool chain_ctl_ok(const IcpCtl &c, int iterations) { return c.steps >= 0 && c.steps <= iterations && (c.done || c.steps == iterations); }
 
 /* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
    then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
@@ -964,7 +1012,7 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
         LAUNCH(h, "k_trim_scatter", k_trim_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, ctl, cuts, (int)evals, (int)N1, G.tstatus.p, G.td2.p);
     IcpCtl C;
     HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
-    if (C.steps < 0 || C.steps > iterations || (!C.done && C.steps != iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
+    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
     const size_t last = (size_t)C.steps;
     std::vector<ppp_registration_row> R(last + 1);
     HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
@@ -1188,7 +1236,7 @@ int ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registrat
     int win = 0;
     for (int s = 0; s < K; ++s) {
         const IcpCtl &c = C[(size_t)s];
-        if (c.steps < 0 || c.steps > iterations || (!c.done && c.steps != iterations)) return fail(h, PPP_ERR_HIP, "global registration: control words corrupt");
+        if (!chain_ctl_ok(c, iterations)) return fail(h, PPP_ERR_HIP, "global registration: control words corrupt");
         const size_t first = (size_t)s * evals, last = first + (size_t)c.steps;
         if (!c.done) icp_row_terms(&R[last], &T[12 * last], &acc[ICP_WORDS * last]); /* the evaluation behind the last step: no step kernel follows it */
         if (R[first].pairs > (size_t)nq || R[last].pairs > (size_t)nq) return fail(h, PPP_ERR_HIP, "global registration: sums corrupt");
@@ -1649,28 +1697,6 @@ int ppp_merge_region_tiles(size_t tiles, const int *const *labels, const ppp_reg
     return PPP_OK;
 }
 
-/* a handle of ppp_get_deviation_tile, scan or reference: a cloud, whole or a slice range of it.  Two steps, with the range
-   checks of the call between them: the plan (what the handle indexes and owns; no index is built for it), then the slab index,
-   complete.  Errors are reported on h, as deviation_side's. */
-static int deviation_tile_plan(ppp_handle h, ppp_handle side, const char *who)
-{
-    const std::string w = std::string("deviation tile: ") + who;
-    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
-    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
-    int rc = plan_ready(side);
-    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
-    return PPP_OK;
-}
-static int deviation_tile_index(ppp_handle h, ppp_handle side, const char *who)
-{
-    const std::string w = std::string("deviation tile: ") + who;
-    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
-    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
-    const int ns = side->hmeta.n_sorted;
-    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
-    return PPP_OK;
-}
-
 /* [own_lo, own_hi) widened by r with room for the roundings (B.82): r times the 1.0001 of the margin tests, which covers the
    float product dx dx against r r, and one float further out, which covers the rounding of the sum itself -- at coordinates of
    metres half an ulp is more than r / 10 000.  An empty interval stays empty. */
@@ -1693,25 +1719,15 @@ int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_par
                            int *ref_index, unsigned char *status, double *target, unsigned char *owned, size_t cap,
                            ppp_deviation_tile_stats *part)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!ref || !dp) return fail(h, PPP_ERR_ARG, "deviation tile: no reference handle or no parameters");
-    const ppp_deviation_params P = *dp;
-    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, "deviation tile: max_dist must be > 0");
-    if (!std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, "deviation tile: a tile needs a finite max_dist: the halo must hold every partner");
-    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, "deviation tile: smooth_radius must be finite and >= 0");
-    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, "deviation tile: allowance must be finite");
-    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, "deviation tile: gain must be finite and >= 0");
-    if (!(halo >= P.max_dist + P.smooth_radius && halo <= 3.402823466e+38f))
-        return fail(h, PPP_ERR_ARG, "deviation tile: halo must be finite and at least max_dist + smooth_radius");
-    const bool smooth = P.smooth_radius > 0.f;
-    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "deviation tile: the two handles are on different devices");
-    int rc = deviation_tile_plan(h, ref, "the reference");
+    int rc = deviation_call_ok(h, ref, dp, "deviation tile", &halo);
     if (rc) return rc;
-    if (ref != h) { rc = deviation_tile_plan(h, h, "the scan"); if (rc) return rc; }
+    const ppp_deviation_params P = *dp;
+    const bool smooth = P.smooth_radius > 0.f;
+    rc = deviation_side_cloud(h, ref, "deviation tile: the reference", true);
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side_cloud(h, h, "deviation tile: the scan", true); if (rc) return rc; }
     const size_t N = h->n;
-    if (smooth && (double)P.max_dist * DEV_FIXED * (double)N >= 4611686018427387904.0)
-        return fail(h, PPP_ERR_ARG, "deviation tile: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "deviation tile: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
     /* From the two plans alone, before an index is built or a kernel launched.  What is evaluated: the owned interval widened by
        smooth_radius.  What the reference must index: the owned interval widened by halo, and by its normal_radius beyond that --
        the normal of a partner at the halo's edge reads that neighbourhood. */
@@ -1725,12 +1741,11 @@ int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_par
     widened(T, halo + ref->P.normal_radius, need_lo, need_hi);
     if (leaves_indexed_range(ref, need_lo, need_hi))
         return fail(h, PPP_ERR_ARG, "deviation tile: the reference's indexed slice range does not cover the owned interval widened by halo + normal_radius");
-    rc = deviation_tile_index(h, ref, "the reference");
+    rc = deviation_side_index(h, ref, "deviation tile: the reference", false);
     if (rc) return rc;
-    if (ref != h) { rc = deviation_tile_index(h, h, "the scan"); if (rc) return rc; }
-    rc = contact_buffers(ref); /* the normal field, on ref's stream */
-    if (rc) return ref == h ? rc : fail(h, rc, std::string("deviation tile: the reference: ") + ref->err);
-    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    if (ref != h) { rc = deviation_side_index(h, h, "deviation tile: the scan", false); if (rc) return rc; }
+    rc = reference_normals(h, ref, "deviation tile");
+    if (rc) return rc;
     int pos0, pos1, hb0, hb1, rb0, rb1;
     rc = tile_positions(h, T, pos0, pos1);
     if (rc) return rc;
@@ -1762,27 +1777,14 @@ int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_par
         return fail(h, PPP_ERR_HIP, "deviation tile: statistics corrupt");
     if (part) {
         ppp_deviation_tile_stats st = {};
-        st.n = N; st.owned = (size_t)own; st.evaluated = (size_t)(own + acc[DEVT_ACC_HALO]);
-        st.matched = (size_t)acc[0]; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2];
-        st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
-        st.min_dev = st.max_dev = (double)NAN; st.max_dist2 = NAN;
-        if (st.matched) {
-            st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
-            st.fix_sum = (long long)acc[DEV_ACC_FIXSUM];
-            st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
-        }
+        dev_stats_words(st, N, acc);
+        st.owned = (size_t)own; st.evaluated = (size_t)(own + acc[DEVT_ACC_HALO]);
+        if (st.matched) st.fix_sum = (long long)acc[DEV_ACC_FIXSUM];
         st.own_lo = T.own_lo; st.own_hi = T.own_hi;
         st.sum_parts = MapParts(h, N).grid;
         *part = st;
     }
-    const size_t k = std::min(cap, N);
-    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
-    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
-    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
-    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
-    if (owned && k) HIPCHK(h, copy_sync(h, owned, D.owned.p, k, hipMemcpyDeviceToHost));
-    return PPP_OK;
+    return deviation_copy_out(h, std::min(cap, N), v, deviation, smoothed, ref_index, status, target, owned);
 }
 
 /* The merge of ppp_get_deviation_tile's parts (host only).  The integer fields add and fold; hist needs the global span, and
@@ -1841,12 +1843,7 @@ int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *part
                 if (owner[i] < 0 || status[(size_t)owner[i]][i] != PPP_DEV_MATCHED) continue;
                 const double x = v[(size_t)owner[i]][i];
                 sq += x * x; tg += target[(size_t)owner[i]][i];
-                int bin = PPP_CONTACT_BINS / 2;
-                if (span > 0.0) {
-                    const double f = floor((x / span + 1.0) * (double)(PPP_CONTACT_BINS / 2));
-                    bin = f < 0.0 ? 0 : (f > (double)(PPP_CONTACT_BINS - 1) ? PPP_CONTACT_BINS - 1 : (int)f);
-                }
-                ++st.hist[bin];
+                ++st.hist[dev_bin(x, span)];
             }
             s_sq[t] = sq; s_tg[t] = tg;
         }

@@ -1,7 +1,7 @@
 /*
  * ppp_registration.h -- point-to-plane ICP of one handle's cloud, the scan, to another handle's, the reference
  * (ppp_get_registration_terms, ppp_register).  An iteration is k_reg_terms -- the scan's points, moved
- * by the current transform, through the reference's slab index (dev_nearest_within, as k_dev_nearest walks it) and the 29
+ * by the current transform, through the reference's slab index (dev_nearest_within and k_dev_nearest's pair rule) and the 29
  * integer sums of the normal equations -- and k_reg_step, one thread that solves the 6 x 6 system and composes the next
  * transform.  The transforms, the sums and the rows stay on the device: the host enqueues the whole chain and waits once.
  * Integer sums wherever a sum has no order, + - * / in double with one rounding per written operation everywhere else: the
@@ -141,12 +141,62 @@ __host__ __device__ inline double icp_compose(const double *x, const double *c, 
     return rot > tr ? rot : tr;
 }
 
+/* m = T p in double: ((t0 px + t1 py) + t2 pz) + t3 per row, one rounding per written operation */
+__device__ __attribute__((always_inline)) inline void icp_move(const double *t, const float4 &p, double *m)
+{
+    const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) m[r] = ((t[4 * r] * px + t[4 * r + 1] * py) + t[4 * r + 2] * pz) + t[4 * r + 3];
+}
+
+/* a pair's 29 terms -- the moved point m, its partner q with the normal n -- each rounded to 2^-shift (F.scale = 2^shift), added
+   to the thread's 64-bit integers a.  Two's complement words: b may be negative. */
+__device__ __attribute__((always_inline)) inline void icp_add_terms(unsigned long long *a, const double *m, const float4 &q, const float4 &n,
+                                                                   const IcpFrame &F)
+{
+    const double nx = (double)n.x, ny = (double)n.y, nz = (double)n.z;
+    const double ex = m[0] - (double)q.x, ey = m[1] - (double)q.y, ez = m[2] - (double)q.z;
+    const double r = ((ex * nx) + ey * ny) + ez * nz;
+    const double ux = (m[0] - F.c[0]) / F.Ln, uy = (m[1] - F.c[1]) / F.Ln, uz = (m[2] - F.c[2]) / F.Ln;
+    const double J[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
+    a[ICP_PAIRS] += 1;
+    int w = ICP_A;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int k = i; k < 6; ++k, ++w) a[w] += (unsigned long long)llrint((J[i] * J[k]) * F.scale);
+        a[ICP_B + i] += (unsigned long long)llrint((J[i] * r) * F.scale);
+    }
+    a[ICP_E] += (unsigned long long)llrint((r * r) * F.scale);
+}
+
+/* the threads' words of a workgroup of T threads into acc: over the wave, over the workgroup through LDS, and one 64-bit
+   integer atomic per non-zero word */
+template <int T>
+__device__ __attribute__((always_inline)) inline void icp_flush(unsigned long long *a, unsigned long long (*s_a)[ICP_WORDS],
+                                                               unsigned long long *__restrict__ acc)
+{
+#pragma unroll
+    for (int w = 0; w < ICP_WORDS; ++w) a[w] = wave_sum(a[w]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int w = 0; w < ICP_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
+    }
+    __syncthreads();
+    if (threadIdx.x < ICP_WORDS) {
+        unsigned long long s = 0;
+        for (int v = 0; v < T / 64; ++v) s += s_a[v][threadIdx.x];
+        if (s) atomicAdd(acc + threadIdx.x, s);
+    }
+}
+
 /* The hot path (B.69): a thread per indexed point of the scan, in the scan's slab order (q4 = its sorted4, nq = its n_sorted),
-   grid-stride.  The point is moved by T in double, the float of the moved point is searched in the reference's index R with
-   k_dev_nearest's walk and rule, and a pair adds its 29 terms, each rounded to 2^-shift (F.scale = 2^shift), to the thread's
-   64-bit integers.  They are added over the wave, over the workgroup through LDS, and the workgroup adds every non-zero word
-   with one 64-bit integer atomic: the grid is capped by the host, so the atomics do not grow with the cloud.  Two's complement
-   words: b may be negative.  T is read from device memory -- the step kernel before this launch wrote it. */
+   grid-stride.  The point is moved by T in double (icp_move), the float of the moved point is searched in the reference's whole
+   index R (dev_nearest_within<true>) and paired by dev_pair's rule -- written out here, not called: with the pair handed back as
+   dev_pair's record this kernel came to 155 - 157 VGPRs for 148 and ran 0.4 - 1.2 % slower in ppp_register's chains
+   (profiles/scan_reference_fold_ab.txt); k_trim_pair, which calls dev_pair, is compared with it bit for bit at keep = 1 -- and a
+   pair adds its 29 terms (icp_add_terms).  icp_flush: the grid is capped by the host, so the atomics do not grow with the
+   cloud.  T is read from device memory -- the step kernel before this launch wrote it. */
 /* k_reg_terms's body, for workgroup `block` of `blocks`: one chain's evaluation at T into acc.  Both the single chain's kernel
    and the side-by-side one call it, so a row is the same bits from either. */
 __device__ __forceinline__ void reg_terms_body(const float4 *__restrict__ q4, int nq, const ContactIndex &R, int nref, const IcpFrame &F,
@@ -159,48 +209,20 @@ __device__ __forceinline__ void reg_terms_body(const float4 *__restrict__ q4, in
     double t[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) t[i] = T[i];
-    const SlabView V = R.view();
     for (int at = block * ICP_T + threadIdx.x; at < nq; at += blocks * ICP_T) {
-        const float4 p = q4[at];
-        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
         double m[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) m[r] = ((t[4 * r] * px + t[4 * r + 1] * py) + t[4 * r + 2] * pz) + t[4 * r + 3];
+        icp_move(t, q4[at], m);
         const float qx = (float)m[0], qy = (float)m[1], qz = (float)m[2];
         if (!(isfinite(qx) && isfinite(qy) && isfinite(qz)) || nref <= 0) continue;
         float4 q = make_float4(NAN, NAN, NAN, 0.f);
         float dd = NAN;
-        const int j = dev_nearest_within(V, qx, qy, qz, F.md2, &q, &dd);
+        const int j = dev_nearest_within<true>(R.view(), 0, 0, qx, qy, qz, F.md2, &q, &dd);
         if (j < 0) continue;
         const float4 n = R.normals4[j];
         if (!(n.x == n.x && n.y == n.y && n.z == n.z && n.w == n.w)) continue;
-        const double nx = (double)n.x, ny = (double)n.y, nz = (double)n.z;
-        const double ex = m[0] - (double)q.x, ey = m[1] - (double)q.y, ez = m[2] - (double)q.z;
-        const double r = ((ex * nx) + ey * ny) + ez * nz;
-        const double ux = (m[0] - F.c[0]) / F.Ln, uy = (m[1] - F.c[1]) / F.Ln, uz = (m[2] - F.c[2]) / F.Ln;
-        const double J[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
-        a[ICP_PAIRS] += 1;
-        int w = ICP_A;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-#pragma unroll
-            for (int k = i; k < 6; ++k, ++w) a[w] += (unsigned long long)llrint((J[i] * J[k]) * F.scale);
-            a[ICP_B + i] += (unsigned long long)llrint((J[i] * r) * F.scale);
-        }
-        a[ICP_E] += (unsigned long long)llrint((r * r) * F.scale);
+        icp_add_terms(a, m, q, n, F);
     }
-#pragma unroll
-    for (int w = 0; w < ICP_WORDS; ++w) a[w] = wave_sum(a[w]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int w = 0; w < ICP_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_WORDS) {
-        unsigned long long s = 0;
-        for (int v = 0; v < ICP_T / 64; ++v) s += s_a[v][threadIdx.x];
-        if (s) atomicAdd(acc + threadIdx.x, s);
-    }
+    icp_flush<ICP_T>(a, s_a, acc);
 }
 
 __global__ void __launch_bounds__(ICP_T) k_reg_terms(const float4 *__restrict__ q4, int nq, const ContactIndex R, int nref, const IcpFrame F,

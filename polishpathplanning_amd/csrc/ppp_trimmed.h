@@ -74,8 +74,8 @@ __device__ __forceinline__ void trim_flush(const u32 *s_h, int bins, u32 *__rest
     }
 }
 
-/* B.77: a thread per indexed point of the scan in slab order, grid-stride -- reg_terms_body's moved point, query, search and
-   pair rule, word for word.  A pair leaves the reference point it found (w: its cloud index) and its key; any other query the
+/* B.77: a thread per indexed point of the scan in slab order, grid-stride -- reg_terms_body's moved point (icp_move), query
+   and pair rule (dev_pair).  A pair leaves the reference point it found (w: its cloud index) and its key; any other query the
    key TRIM_NONE.  The keys' top digits are counted in LDS and flushed once per workgroup. */
 __global__ void __launch_bounds__(TRIM_T) k_trim_pair(const float4 *__restrict__ q4, int nq, const ContactIndex R, int nref, const IcpFrame F,
         const double *__restrict__ T, const IcpCtl *__restrict__ ctl, float4 *__restrict__ partner, u32 *__restrict__ key, u32 *__restrict__ hist0)
@@ -87,27 +87,16 @@ __global__ void __launch_bounds__(TRIM_T) k_trim_pair(const float4 *__restrict__
     double t[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) t[i] = T[i];
-    const SlabView V = R.view();
     for (int at = blockIdx.x * TRIM_T + threadIdx.x; at < nq; at += gridDim.x * TRIM_T) {
-        const float4 p = q4[at];
-        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
         double m[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) m[r] = ((t[4 * r] * px + t[4 * r + 1] * py) + t[4 * r + 2] * pz) + t[4 * r + 3];
+        icp_move(t, q4[at], m);
         const float qx = (float)m[0], qy = (float)m[1], qz = (float)m[2];
         u32 kk = TRIM_NONE;
-        if (isfinite(qx) && isfinite(qy) && isfinite(qz) && nref > 0) {
-            float4 q = make_float4(NAN, NAN, NAN, 0.f);
-            float dd = NAN;
-            const int j = dev_nearest_within(V, qx, qy, qz, F.md2, &q, &dd);
-            if (j >= 0) {
-                const float4 n = R.normals4[j];
-                if (n.x == n.x && n.y == n.y && n.z == n.z && n.w == n.w) {
-                    kk = __float_as_uint(dd);
-                    partner[at] = q;
-                    atomicAdd(&s_h[kk >> 21], 1u);
-                }
-            }
+        DevPair P;
+        if (isfinite(qx) && isfinite(qy) && isfinite(qz) && dev_pair<true>(R, nref, 0, 0, qx, qy, qz, F.md2, P) == PPP_DEV_MATCHED) {
+            kk = __float_as_uint(P.d2);
+            partner[at] = P.q;
+            atomicAdd(&s_h[kk >> 21], 1u);
         }
         key[at] = kk;
     }
@@ -146,9 +135,9 @@ __global__ void __launch_bounds__(TRIM_T) k_trim_narrow(const u32 *__restrict__ 
     trim_flush(s_h, BINS, next);
 }
 
-/* B.78's last digit and B.79: tau from hist (PASS 2's counts) at the rank PASS 2 left, then reg_terms_body's 29 words over the
-   queries with key <= tau -- the moved point is made again from T, the reference point and the key are read back -- and its
-   wave -> LDS -> one 64-bit integer atomic per workgroup and non-zero word.  acc[ICP_PAIRS] is `kept`. */
+/* B.78's last digit and B.79: tau from hist (PASS 2's counts) at the rank PASS 2 left, then reg_terms_body's 29 words
+   (icp_add_terms) over the queries with key <= tau -- the moved point is made again from T (icp_move), the reference point and
+   the key are read back -- and icp_flush.  acc[ICP_PAIRS] is `kept`. */
 __global__ void __launch_bounds__(TRIM_T) k_trim_terms(const float4 *__restrict__ q4, int nq, const ContactIndex R, const IcpFrame F,
         const double *__restrict__ T, const IcpCtl *__restrict__ ctl, const float4 *__restrict__ partner, const u32 *__restrict__ key,
         const u32 *hist, TrimCut *cut, unsigned long long *__restrict__ acc)
@@ -172,40 +161,12 @@ __global__ void __launch_bounds__(TRIM_T) k_trim_terms(const float4 *__restrict_
     for (int i = 0; i < 12; ++i) t[i] = T[i];
     for (int at = blockIdx.x * TRIM_T + threadIdx.x; at < nq; at += gridDim.x * TRIM_T) {
         if (key[at] > tau) continue;
-        const float4 p = q4[at];
-        const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
         double m[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) m[r] = ((t[4 * r] * px + t[4 * r + 1] * py) + t[4 * r + 2] * pz) + t[4 * r + 3];
+        icp_move(t, q4[at], m);
         const float4 q = partner[at];
-        const float4 n = R.normals4[idx_of(q)];
-        const double nx = (double)n.x, ny = (double)n.y, nz = (double)n.z;
-        const double ex = m[0] - (double)q.x, ey = m[1] - (double)q.y, ez = m[2] - (double)q.z;
-        const double r = ((ex * nx) + ey * ny) + ez * nz;
-        const double ux = (m[0] - F.c[0]) / F.Ln, uy = (m[1] - F.c[1]) / F.Ln, uz = (m[2] - F.c[2]) / F.Ln;
-        const double J[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
-        a[ICP_PAIRS] += 1;
-        int w = ICP_A;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-#pragma unroll
-            for (int k = i; k < 6; ++k, ++w) a[w] += (unsigned long long)llrint((J[i] * J[k]) * F.scale);
-            a[ICP_B + i] += (unsigned long long)llrint((J[i] * r) * F.scale);
-        }
-        a[ICP_E] += (unsigned long long)llrint((r * r) * F.scale);
+        icp_add_terms(a, m, q, R.normals4[idx_of(q)], F);
     }
-#pragma unroll
-    for (int w = 0; w < ICP_WORDS; ++w) a[w] = wave_sum(a[w]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int w = 0; w < ICP_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_WORDS) {
-        unsigned long long s = 0;
-        for (int v = 0; v < TRIM_T / 64; ++v) s += s_a[v][threadIdx.x];
-        if (s) atomicAdd(acc + threadIdx.x, s);
-    }
+    icp_flush<TRIM_T>(a, s_a, acc);
 }
 
 /* B.80: once behind the chain.  The keys are those of the last evaluation that ran -- evaluation ctl->steps, the one at the

@@ -293,6 +293,47 @@ def test_merge_of_hand_made_parts_equals_the_restatement(engine_mod, parts):
         assert ex.value.code == E.ERR_ARG
 
 
+def test_merge_bins_the_ends_of_the_span_the_zeros_and_a_zero_span(engine_mod):
+    """the histogram's bin rule, through the merge of two hand-made parts, against the formula written out: bin min(63, max(0,
+    floor((v / span + 1) 32))) for v at -span and +span (bins 0 and 63: the clamp), at -0.0 and +0.0 (bin 32), at the largest
+    double below span and the smallest above -span, and at a few values between; with every value a zero span == 0 and all of
+    them land in bin 32.  An owned point that is not matched is in no bin."""
+    E = engine_mod
+
+    def bins_of(x, span):
+        if not span > 0.0:
+            return np.full(len(x), 32)
+        return np.minimum(63, np.maximum(0, np.floor((x / span + 1.0) * 32.0))).astype(np.int64)
+
+    def hand_tile(v, st, mine):
+        m = mine & (st == MATCHED)
+        w = v[m]
+        lo = -0.0 if (w.min() == 0 and np.signbit(w[w == 0]).any()) else float(w.min())
+        hi = 0.0 if (w.max() == 0 and not np.signbit(w[w == 0]).all()) else float(w.max())
+        part = dict(n=len(v), owned=int(mine.sum()), evaluated=int(mine.sum()), matched=int(m.sum()), too_far=int((mine & (st == TOO_FAR)).sum()),
+                    no_normal=0, proud=0, below=int((w < 0).sum()), min_dev=lo, max_dev=hi,
+                    fix_sum=int(np.rint(w * F24).astype(np.int64).sum(dtype=np.int64)), max_dist2=1.0, own_lo=0.0, own_hi=1.0, sum_parts=1)
+        status = np.where(mine, st, DROPPED).astype(np.uint8)
+        return (np.where(m, v, NAN_BITS), np.where(m, v, NAN_BITS), np.full(len(v), -1, np.int32), status, np.zeros(len(v)), mine.astype(np.uint8), part)
+
+    cases = [(span, np.array([-span, span, -0.0, 0.0, np.nextafter(span, 0.0), np.nextafter(-span, 0.0), span / 3.0, -span / 64.0,
+                              -span / 32.0, span * 0.984375, float("nan")])) for span in (0.3, 1.0, 2.0 ** -30)]
+    cases.append((0.0, np.array([-0.0, 0.0, 0.0, -0.0, float("nan")])))
+    for span, v in cases:
+        st = np.where(np.isnan(v), TOO_FAR, MATCHED)
+        first = np.arange(len(v)) % 2 == 0
+        got = E.merge_deviation_tiles([hand_tile(v, st, first), hand_tile(v, st, ~first)])
+        m = st == MATCHED
+        want = np.bincount(bins_of(v[m], span), minlength=64)
+        print("span %r: bins %r" % (span, bins_of(v[m], span).tolist()))
+        assert max(abs(got["min_dev"]), abs(got["max_dev"])) == span and got["matched"] == m.sum() and got["too_far"] == 1
+        assert np.array_equal(np.asarray(got["hist"]), want) and want.sum() == m.sum()
+        if span > 0.0:
+            assert want[0] >= 1 and want[63] >= 2 and want[32] == 2      # -span; +span and the double below it; the two zeros
+        else:
+            assert want[32] == m.sum()
+
+
 # ---------------------------------------------------------------- GPU
 
 _WHOLE = {}
@@ -393,6 +434,30 @@ def test_tiles_equal_the_whole_deviation(engine_mod, smooth, ref_ranged):
     assert all(t[6]["matched"] > 0 and t[6]["too_far"] > 0 for t in tiles)
     if smooth:
         assert all(t[6]["evaluated"] > t[6]["owned"] for t in tiles)                     # every tile evaluated halo points
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("smooth", [0.0, SMOOTH])
+def test_a_whole_cloud_handle_is_one_tile_that_owns_everything(engine_mod, smooth):
+    """main_clouds, scan and reference on whole-cloud handles (no slice range): the tile call owns exactly the finite rows, its
+    five maps are ppp_get_deviation's bytes over all n entries, it evaluates what it owns, and the merge of that single part is
+    the whole-cloud statistics field for field by bits"""
+    E = engine_mod
+    ref, scan, _ = main_clouds()
+    dp = dict(MAIN, smooth_radius=smooth)
+    whole = whole_of(E, "main", ref, scan, **dp)
+    h, r = handle(E, scan), handle(E, ref)
+    tile = h.deviation_tile(r, MAIN["max_dist"] + smooth, **dp)
+    h.close(); r.close()
+    mine = check_tile(E, tile, whole, scan, -INF, INF, "whole-cloud handle, smooth %r" % smooth)
+    assert np.array_equal(mine, finite_rows(scan)) and tile[6]["evaluated"] == tile[6]["owned"] == mine.sum()
+    for f, got, want in zip(MAPS, tile[:5], whole[:5]):
+        assert got.dtype == want.dtype and got.tobytes() == want.tobytes(), f
+    merged, ws = E.merge_deviation_tiles([tile]), whole[5]
+    print("merged %r\nwhole  %r" % ({k: v for k, v in merged.items() if k != "hist"}, {k: v for k, v in ws.items() if k != "hist"}))
+    assert list(merged) == list(STATS_FIELDS)
+    for f in STATS_FIELDS:
+        assert same(merged[f], ws[f]), f
 
 
 @pytest.mark.gpu
