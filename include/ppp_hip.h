@@ -863,6 +863,68 @@ int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_par
 int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *parts, const double *const *v,
                               const unsigned char *const *status, const double *const *target,
                               const unsigned char *const *owned, ppp_deviation_stats *stats);
+/* ---- registration of a scan held as slice-range tiles ----
+   ppp_register's evaluation is 29 signed 64-bit integer sums over the scan's pairs; integer sums have no order and the owned
+   sets of ranges that tile the walk partition the indexed points (ppp_range_owned), so the whole cloud's words are the
+   word-by-word sum of the tiles' words, bit for bit.  The solve and the step are the device chain's own routines, run on the
+   host.  Nothing here approximates.
+   ppp_get_registration_terms_tile (B.88-B.90): ppp_get_registration_terms over the points h owns.  h: a slice-range handle of
+   the scan (it holds the whole cloud), or a whole-cloud handle, which owns every indexed point; ownership goes by the
+   resident, unmoved x.  ref: a whole-cloud or a slice-range handle of the reference.  centre, length and shift are the WHOLE
+   clouds': the reference's bounds (a range handle keeps the whole cloud's, cached with its plan) and n = cloud->size() of h.
+     row       T = T12 (NULL: the identity), pairs / A / b / E over the owned points' pairs, locked 63, step2 NaN
+     part      owned = the indexed points h owns, evaluated = the index positions visited (the slabs that meet the owned
+               interval), the owned interval [own_lo, own_hi), n, shift, centre, length: what the merge and the step take
+     range     a query is moved by T, so the two plans cannot decide what the reference must index.  With reach = 1.0001f *
+               (max_dist + ref's normal_radius), the float sum: for every owned query with a finite moved x', the interval
+               [nextbelow(x' - reach), nextabove(x' + reach)] must lie inside ref's indexed x interval, a side where that
+               interval ends at the reference cloud's own end exempt.  One query that does not: PPP_ERR_CAPACITY (raise
+               range_margin); a call is never answered with fewer pairs.  The test is conservative: it refuses even where no
+               pair would have been found.  A whole-cloud reference never refuses.
+   Builds what ppp_get_registration_terms builds, keeps nothing, changes no plan, path or stored result of either handle.
+   PPP_ERR_ARG as ppp_get_registration_terms (B.72); PPP_ERR_UNSUPPORTED when either handle is a part handle
+   (ppp_set_cloud_part).  h == ref is allowed.  row and part may be NULL.
+   ppp_merge_registration_terms (B.91; host only): the 29 words and pairs add as signed 64-bit integers (two's complement),
+   owned and evaluated add, the owned interval is the hull; out_row->T = T12 (NULL: the identity), locked 63, step2 NaN.
+   out_part may be NULL.  PPP_ERR_ARG: rows, parts or out_row NULL, count == 0, parts that disagree on n, shift, centre or
+   length (compared bit for bit), owned intervals that overlap (equal ends that meet are fine: ownership is half-open; an
+   interval with own_lo >= own_hi is empty and overlaps nothing).
+   ppp_registration_step (B.92; host only): the step ppp_register takes from an evaluation.  T12 (NULL: row->T) is the
+   transform the row was taken at, part gives centre and length.  Returns PPP_STEP_TAKEN with T12_out, *locked (the mask) and
+   *step2; or, with T12_out = T12, *locked = 63 and *step2 = NaN, PPP_STEP_FEW_PAIRS (pairs < 6), PPP_STEP_STATIONARY (all six b
+   zero: T is a stationary point, ppp_register ends converged) or PPP_STEP_ALL_LOCKED (the pivot rule locked all six
+   unknowns).  locked and step2 may be NULL.  PPP_ERR_ARG: row, part or T12_out NULL, lock_eps outside (0, 1), part->length not
+   finite and > 0.
+   ppp_register_tiles (B.93, B.94): ppp_register's loop over tiles.  hs[i] holds the scan with range i, refs[i] is the
+   reference handle of tile i (the same whole-cloud handle may stand in every slot); tiles may sit on different devices, a tile
+   and its own reference on the same one.  Each reference's index and normal field are built once, before the loop.  Per
+   evaluation T goes to every tile's device, every tile's evaluation is enqueued on its own handle's stream, the words come back
+   with one asynchronous copy per tile, the host waits for all tiles, merges, steps and records the row: one host round trip
+   per evaluation, where ppp_register has none.  For ranges that tile the walk T, every row (words, locked, step2) and every
+   field of stats->reg are the bits of ppp_register on whole-cloud handles with the same parameters and T0.  A tile's error
+   ends the loop and is returned (the text on that tile's handle), with the tile's index in stats->failed_tile (-1 otherwise).
+   PPP_ERR_ARG: hs, refs or params NULL, count == 0, a NULL handle, a handle twice in hs, rows NULL with row_cap > 0, and
+   ppp_register's own. */
+typedef struct {
+    size_t owned, evaluated;   /* indexed points owned; index positions visited */
+    float  own_lo, own_hi;     /* the owned interval [own_lo, own_hi) */
+    size_t n;                  /* cloud->size() of the whole scan */
+    int    shift;              /* the fixed point is 2^shift */
+    double centre[3], length;  /* c and Ln of ppp_register, from the whole reference */
+} ppp_registration_part;
+typedef struct {
+    ppp_registration_stats reg; /* ppp_register's statistics */
+    int failed_tile;            /* the tile whose error ended the loop; -1: none */
+} ppp_register_tiles_stats;
+enum { PPP_STEP_TAKEN = 0, PPP_STEP_FEW_PAIRS = 1, PPP_STEP_STATIONARY = 2, PPP_STEP_ALL_LOCKED = 3 };
+int ppp_get_registration_terms_tile(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12,
+                                    ppp_registration_row *row, ppp_registration_part *part);
+int ppp_merge_registration_terms(const ppp_registration_row *rows, const ppp_registration_part *parts, size_t count,
+                                 const double *T12, ppp_registration_row *out_row, ppp_registration_part *out_part);
+int ppp_registration_step(const ppp_registration_row *row, const ppp_registration_part *part, double lock_eps,
+                          const double *T12, double *T12_out, int *locked, double *step2);
+int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp,
+                       const double *T0_12, ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

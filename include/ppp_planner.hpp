@@ -462,6 +462,16 @@ public:
         }
         return rc == PPP_OK ? true : report(rc);
     }
+    /* the registration terms at T12 (nullptr: the identity) over the points this planner owns (ppp_get_registration_terms_tile;
+       DESIGN.md 7o): this planner holds the scan with a slice range (or whole: it then owns everything), ref the reference, whole
+       or a slice range that indexes max_dist + its normal_radius around every moved point.  row and part are what
+       ppp_merge_registration_terms and ppp_registration_step take */
+    bool registration_terms_tile(const Planner &ref, ppp_registration_row &row, ppp_registration_part &part, const ppp_registration_params &rp,
+                                 const double *T12 = nullptr)
+    {
+        const int rc = ppp_get_registration_terms_tile(h_, ref.h_, &rp, T12, &row, &part);
+        return rc == PPP_OK ? true : report(rc);
+    }
     /* ppp_default_deviation_params with what the environment sets of PPP_DEVIATION_MAXDIST, PPP_DEVIATION_SMOOTH,
        PPP_DEVIATION_ALLOWANCE and PPP_DEVIATION_GAIN (the example programs' knobs) */
     static ppp_deviation_params deviation_params_env()
@@ -878,6 +888,27 @@ private:
     bool loaded_ = false;
     std::vector<float> normals_;
 };
+
+/* register_to() for a scan held as slice-range planners (ppp_register_tiles): tiles[i] holds the scan with range
+   i, refs[i] its reference (one whole-cloud planner may stand in every slot).  st.reg is register_to()'s st, bit for bit, for
+   ranges that tile the walk; every evaluation is a host round trip.  A tile's error is reported with its index */
+inline bool register_tiles(std::vector<Planner *> &tiles, std::vector<Planner *> &refs, ppp_register_tiles_stats &st,
+                           const ppp_registration_params &rp, const double *T0 = nullptr, std::vector<ppp_registration_row> *rows = nullptr)
+{
+    if (tiles.empty() || refs.size() != tiles.size()) { std::fprintf(stderr, "ppp error %d: register_tiles: one reference per tile\n", PPP_ERR_ARG); return false; }
+    std::vector<ppp_handle> hs, rs;
+    for (size_t i = 0; i < tiles.size(); ++i) { hs.push_back(tiles[i] ? tiles[i]->handle() : nullptr); rs.push_back(refs[i] ? refs[i]->handle() : nullptr); }
+    if (rows) rows->assign((size_t)(rp.iterations > 0 ? rp.iterations : 0) + 1, ppp_registration_row{});
+    const int rc = ppp_register_tiles(hs.data(), rs.data(), hs.size(), &rp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, &st);
+    if (rc != PPP_OK) {
+        if (rows) rows->clear();
+        const ppp_handle at = hs[st.failed_tile >= 0 ? (size_t)st.failed_tile : 0];
+        std::fprintf(stderr, "ppp error %d: tile %d: %s\n", rc, st.failed_tile, at ? ppp_last_error(at) : "no handle");
+        return false;
+    }
+    if (rows) rows->resize(std::min(rows->size(), (size_t)st.reg.steps + 1));
+    return true;
+}
 
 } // namespace ppp
 #endif

@@ -17,6 +17,7 @@
 #include "ppp_deviation_tile.h"
 #include "ppp_registration.h"
 #include "ppp_trimmed.h"
+#include "ppp_registration_tile.h"
 #include <cstring>
 
 /* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
@@ -1853,6 +1854,273 @@ int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *part
     }
     if (st.matched) st.rms_dev = std::sqrt(sq_all / (double)st.matched);
     *stats = st;
+    return PPP_OK;
+}
+
+/* ---- registration of a scan held as slice-range tiles ---- */
+
+/* one tile of a call: the scan's handle, its reference, and what k_regt_terms is launched with */
+struct RegtTile {
+    ppp_handle h = nullptr, ref = nullptr;
+    TileRange own;
+    RegtNeed need;
+    int pos0 = 0, pos1 = 0, rb0 = 0, rb1 = 0, nref = 0;
+    unsigned grid = 1;
+    ppp_registration_part part;
+};
+
+/* the tile's pinned memory: REGT_WORDS words coming back, then the 12 doubles of T going out */
+static double *regt_pinned_T(const RegtTile &t) { return reinterpret_cast<double *>(t.h->registration.tpin.p + REGT_WORDS); }
+
+/* What a tile needs before its first evaluation: the checks (B.72's, a part handle), both plans, both indices -- the
+   reference's index and normal field only where build_ref says so: a handle that stands in several slots is built once --, the
+   frame and the shift of the WHOLE clouds (B.90), the positions, the reference's sorted slabs and indexed interval, the
+   buffers, and the frame on the device. */
+static int regt_prepare(RegtTile &t, const ppp_registration_params &P, IcpFrame F, bool build_ref)
+{
+    ppp_handle h = t.h, ref = t.ref;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration tile: the tile and its reference are on different devices");
+    int rc = deviation_side_cloud(h, ref, "registration tile: the reference", true);
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side_cloud(h, h, "registration tile: the scan", true); if (rc) return rc; }
+    int shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration tile: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    rc = tile_range(h, 0.f, t.own);
+    if (rc) return rc;
+    if (build_ref) { rc = deviation_side_index(h, ref, "registration tile: the reference", false); if (rc) return rc; }
+    if (ref != h) { rc = deviation_side_index(h, h, "registration tile: the scan", false); if (rc) return rc; }
+    /* B.90: the whole reference's bounds.  A whole-cloud handle answers ppp_minmax with them (registration_setup reads the same
+       block); a range handle's launches see its part only and are handed the whole cloud's bounds cached with its plan: those */
+    float mn[3], mx[3];
+    if (ref->ranged) { for (int d = 0; d < 3; ++d) { mn[d] = ref->h_mn[d]; mx[d] = ref->h_mx[d]; } }
+    else {
+        rc = fetch_meta(ref);
+        if (rc) return ref == h ? rc : fail(h, rc, std::string("registration tile: the reference: ") + ref->err);
+        for (int d = 0; d < 3; ++d) { mn[d] = ref->hmeta.mn[d]; mx[d] = ref->hmeta.mx[d]; }
+    }
+    double ext[3];
+    for (int d = 0; d < 3; ++d) {
+        F.c[d] = ((double)mn[d] + (double)mx[d]) * 0.5;
+        ext[d] = (double)mx[d] - (double)mn[d];
+    }
+    F.Ln = (((ext[0] + ext[1]) + ext[2]) * 0.5) + (double)P.max_dist;
+    F.scale = std::ldexp(1.0, shift);
+    if (build_ref) { rc = reference_normals(h, ref, "registration tile"); if (rc) return rc; }
+    rc = tile_positions(h, t.own, t.pos0, t.pos1);
+    if (rc) return rc;
+    sorted_slabs(ref, t.rb0, t.rb1);
+    t.nref = ref->hmeta.n_sorted;
+    t.need = RegtNeed{ref->incl_lo, ref->incl_hi, 1.0001f * (P.max_dist + ref->P.normal_radius), ref->ranged && ref->incl_lo > ref->h_mn[0],
+                      ref->ranged && ref->incl_hi < ref->h_mx[0]};
+    t.grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)(t.pos1 - t.pos0) + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
+    ppp_registration_part &p = t.part;
+    p = ppp_registration_part{};
+    p.evaluated = (size_t)(t.pos1 - t.pos0);
+    p.own_lo = t.own.own_lo; p.own_hi = t.own.own_hi;
+    p.n = h->n; p.shift = shift;
+    for (int d = 0; d < 3; ++d) p.centre[d] = F.c[d];
+    p.length = F.Ln;
+    auto &G = h->registration;
+    HIPCHK(h, G.T.ensure(12)); HIPCHK(h, G.acc.ensure(REGT_WORDS)); HIPCHK(h, G.tframe.ensure(1)); HIPCHK(h, G.tpin.ensure(REGT_WORDS + 12));
+    HIPCHK(h, copy_sync(h, G.tframe.p, &F, sizeof(F), hipMemcpyHostToDevice));
+    return PPP_OK;
+}
+
+/* one evaluation of a tile at T, enqueued on its handle's stream: T to the device, the words cleared, k_regt_terms, the words
+   back to pinned memory.  Nobody waits here. */
+static int regt_enqueue(RegtTile &t, const double *T)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, REGT_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_regt_terms", k_regt_terms, t.grid, ICP_T, 0, h->sorted4.p, t.pos0, t.pos1, t.own, contact_index(t.ref), t.nref, t.rb0, t.rb1, t.need,
+               G.tframe.p, G.T.p, G.acc.p);
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, REGT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the wait for a tile's evaluation, and its row: the refusal (B.89), the words' sanity, the terms */
+static int regt_collect(RegtTile &t, const double *T, ppp_registration_row *row)
+{
+    ppp_handle h = t.h;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned long long *w = h->registration.tpin.p;
+    if (w[REGT_REFUSED])
+        return fail(h, PPP_ERR_CAPACITY, "registration tile: " + std::to_string(w[REGT_REFUSED]) + " moved queries reach beyond the reference's indexed slice range "
+                    "(max_dist + normal_radius around the moved point): raise range_margin of the reference's handle");
+    if (w[REGT_OWNED] > (unsigned long long)(t.pos1 - t.pos0) || w[ICP_PAIRS] > w[REGT_OWNED]) return fail(h, PPP_ERR_HIP, "registration tile: sums corrupt");
+    t.part.owned = (size_t)w[REGT_OWNED];
+    *row = ppp_registration_row{};
+    icp_row_terms(row, T, w);
+    return PPP_OK;
+}
+
+/* the checks every tiled call makes before it looks at a handle: the parameters and the transform (errors on h) */
+static int regt_call_ok(ppp_handle h, const ppp_registration_params *rp, const double *T0, IcpFrame &F, double *T)
+{
+    if (!h) return PPP_ERR_ARG;
+    if (!rp) return fail(h, PPP_ERR_ARG, "registration tile: no parameters");
+    int rc = registration_params_ok(h, *rp, F);
+    if (rc) return rc;
+    static const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    memcpy(T, T0 ? T0 : I, sizeof(I));
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return fail(h, PPP_ERR_ARG, "registration tile: the transform has an entry that is not finite");
+    return PPP_OK;
+}
+
+int ppp_get_registration_terms_tile(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                                    ppp_registration_part *part)
+{
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h, rp, T12, F, T);
+    if (rc) return rc;
+    if (!ref) return fail(h, PPP_ERR_ARG, "registration tile: no reference handle");
+    RegtTile t;
+    t.h = h; t.ref = ref;
+    rc = regt_prepare(t, *rp, F, true);
+    if (rc) return rc;
+    rc = regt_enqueue(t, T);
+    if (rc) return rc;
+    ppp_registration_row r;
+    rc = regt_collect(t, T, &r);
+    if (rc) return rc;
+    if (row) *row = r;
+    if (part) *part = t.part;
+    return PPP_OK;
+}
+
+int ppp_merge_registration_terms(const ppp_registration_row *rows, const ppp_registration_part *parts, size_t count, const double *T12,
+                                 ppp_registration_row *out_row, ppp_registration_part *out_part)
+{
+    if (!rows || !parts || !count || !out_row) return PPP_ERR_ARG;
+    std::vector<size_t> by_lo;
+    for (size_t i = 0; i < count; ++i) {
+        if (!regt_same_frame(parts[i], parts[0])) return PPP_ERR_ARG;
+        if (parts[i].own_lo < parts[i].own_hi) by_lo.push_back(i); /* (an empty interval, or one with a NaN, overlaps nothing) */
+    }
+    std::sort(by_lo.begin(), by_lo.end(), [&](size_t a, size_t b) { return parts[a].own_lo < parts[b].own_lo; });
+    for (size_t k = 1; k < by_lo.size(); ++k)
+        if (parts[by_lo[k]].own_lo < parts[by_lo[k - 1]].own_hi) return PPP_ERR_ARG; /* half-open: equal ends meet */
+    unsigned long long acc[ICP_WORDS] = {};
+    ppp_registration_part m = parts[0];
+    m.owned = m.evaluated = 0; m.own_lo = INFINITY; m.own_hi = -INFINITY;
+    for (size_t i = 0; i < count; ++i) {
+        const ppp_registration_row &r = rows[i];
+        acc[ICP_PAIRS] += (unsigned long long)r.pairs;
+        for (int w = 0; w < 21; ++w) acc[ICP_A + w] += (unsigned long long)r.A[w];
+        for (int w = 0; w < 6; ++w) acc[ICP_B + w] += (unsigned long long)r.b[w];
+        acc[ICP_E] += (unsigned long long)r.E;
+        m.owned += parts[i].owned; m.evaluated += parts[i].evaluated;
+        if (parts[i].own_lo < parts[i].own_hi) { m.own_lo = std::min(m.own_lo, parts[i].own_lo); m.own_hi = std::max(m.own_hi, parts[i].own_hi); }
+    }
+    static const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    *out_row = ppp_registration_row{};
+    icp_row_terms(out_row, T12 ? T12 : I, acc);
+    if (out_part) *out_part = m;
+    return PPP_OK;
+}
+
+int ppp_registration_step(const ppp_registration_row *row, const ppp_registration_part *part, double lock_eps, const double *T12, double *T12_out,
+                          int *locked, double *step2)
+{
+    if (!row || !part || !T12_out || !(lock_eps > 0.0 && lock_eps < 1.0) || !(part->length > 0.0 && part->length < INFINITY)) return PPP_ERR_ARG;
+    double T[12], Tn[12];
+    memcpy(T, T12 ? T12 : row->T, sizeof(T));
+    memcpy(Tn, T, sizeof(Tn));
+    int mask;
+    double s2;
+    const int rc = regt_step(*row, part->centre, part->length, lock_eps, T, Tn, &mask, &s2);
+    memcpy(T12_out, Tn, sizeof(Tn));
+    if (locked) *locked = mask;
+    if (step2) *step2 = s2;
+    return rc;
+}
+
+/* The tiled loop (B.93): ppp_register's chain with the host in the place of k_reg_step -- reg_step_body's control flow, word for
+   word: `stop` behind a step below min_step makes the next evaluation the last, an evaluation no step is taken from ends the
+   loop, and the evaluation behind the last of `iterations` steps is a row without a step. */
+int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp, const double *T0_12,
+                       ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !refs || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, rp, T0_12, F, T);
+    if (rc) return rc;
+    if (!rows && row_cap) return fail(h0, PPP_ERR_ARG, "registration tiles: rows is NULL with row_cap > 0");
+    for (size_t i = 0; i < count; ++i) {
+        if (!hs[i] || !refs[i]) return fail(h0, PPP_ERR_ARG, "registration tiles: a NULL handle");
+        for (size_t k = 0; k < i; ++k) if (hs[k] == hs[i]) return fail(h0, PPP_ERR_ARG, "registration tiles: a scan handle stands in two slots");
+    }
+    const ppp_registration_params P = *rp;
+    auto failed = [&](size_t i, int code) { if (stats) stats->failed_tile = (int)i; return code; };
+    std::vector<RegtTile> tiles(count);
+    for (size_t i = 0; i < count; ++i) {
+        tiles[i].h = hs[i]; tiles[i].ref = refs[i];
+        bool first = true; /* the reference's index and normal field: once per reference handle */
+        for (size_t k = 0; k < i; ++k) first = first && refs[k] != refs[i];
+        rc = regt_prepare(tiles[i], P, F, first);
+        if (rc) return failed(i, rc);
+    }
+    std::vector<ppp_registration_row> part_rows(count), R;
+    std::vector<ppp_registration_part> parts(count);
+    ppp_registration_part whole = {};
+    IcpCtl C = {};
+    for (int k = 0; k <= P.iterations; ++k) {
+        for (size_t i = 0; i < count; ++i) { rc = regt_enqueue(tiles[i], T); if (rc) return failed(i, rc); }
+        int first_rc = PPP_OK;
+        size_t first_at = 0;
+        for (size_t i = 0; i < count; ++i) { /* every tile is waited for, whatever an earlier one answered */
+            rc = regt_collect(tiles[i], T, &part_rows[i]);
+            if (rc && !first_rc) { first_rc = rc; first_at = i; }
+            parts[i] = tiles[i].part;
+        }
+        if (first_rc) return failed(first_at, first_rc);
+        ppp_registration_row rw;
+        rc = ppp_merge_registration_terms(part_rows.data(), parts.data(), count, T, &rw, &whole);
+        if (rc) return fail(h0, rc, "registration tiles: the tiles' ranges overlap, or the tiles do not hold one scan against one reference");
+        if (rw.pairs > whole.owned) return fail(h0, PPP_ERR_HIP, "registration tiles: sums corrupt");
+        if (k == P.iterations) { R.push_back(rw); break; } /* the evaluation behind the last step */
+        double Tn[12];
+        int mask = ICP_ALL_LOCKED;
+        double step2 = icp_nan();
+        if (!C.stop) {
+            const int sc = regt_step(rw, whole.centre, whole.length, F.lock_eps, T, Tn, &mask, &step2);
+            if (sc == PPP_STEP_STATIONARY) C.converged = 1;
+        }
+        if (mask == ICP_ALL_LOCKED) { R.push_back(rw); C.done = 1; break; }
+        rw.locked = mask; rw.step2 = step2;
+        R.push_back(rw);
+        C.steps += 1; C.locked |= mask;
+        if (step2 < F.min_step2) { C.stop = 1; C.converged = 1; }
+        memcpy(T, Tn, sizeof(T));
+    }
+    const size_t last = (size_t)C.steps;
+    if (stats) {
+        ppp_registration_stats st = {};
+        st.n = whole.n; st.indexed = whole.owned;
+        st.steps = C.steps; st.converged = C.converged; st.locked = C.locked; st.shift = whole.shift;
+        for (int d = 0; d < 3; ++d) st.centre[d] = whole.centre[d];
+        st.length = whole.length;
+        memcpy(st.T, R[last].T, sizeof(st.T));
+        auto rms = [&](const ppp_registration_row &r) {
+            return r.pairs ? std::sqrt(std::ldexp((double)r.E, -whole.shift) / (double)r.pairs) : (double)NAN;
+        };
+        st.pairs_before = R[0].pairs; st.rms_before = rms(R[0]);
+        st.pairs_after = R[last].pairs; st.rms_after = rms(R[last]);
+        stats->reg = st;
+    }
+    const size_t k = std::min(row_cap, last + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
     return PPP_OK;
 }
 

@@ -25,6 +25,7 @@
 
 struct RegAcc; /* ppp_regions.h: a region's accumulators (the handle owns buffers of them; only the contact unit looks inside) */
 struct FeedRec; /* ppp_feed.h: what the feed envelope reads of a waypoint (likewise) */
+struct IcpFrame; /* ppp_registration.h: what does not change along a registration chain (likewise) */
 
 /* The types and helpers of the host units.  Hidden: the library is linked without visibility flags, and names like `fail` or
    `compact` are not for its dynamic symbol table. */
@@ -317,6 +318,10 @@ struct ppp_handle_s {
         DevBuf<unsigned> key, hist, cuts;
         DevBuf<unsigned char> tstatus;
         DevBuf<float> td2;
+        /* ppp_get_registration_terms_tile, ppp_register_tiles: the frame the tile's kernel reads, and pinned host memory for
+           the transform on its way to the device and the words on their way back */
+        DevBuf<IcpFrame> tframe;
+        PinBuf<unsigned long long> tpin;
     } registration;
     /* contact field of the resident cloud (ppp_get_contact_field): the maps by cloud index and the statistics' accumulators;
        valid for P's contact parameters until the cloud changes (valid) */

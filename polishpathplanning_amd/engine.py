@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -176,6 +176,12 @@ def lib():
         L.ppp_default_registration_params.restype = None
         L.ppp_get_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
         L.ppp_register.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
+        L.ppp_get_registration_terms_tile.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationPart)]
+        L.ppp_merge_registration_terms.argtypes = [C.POINTER(RegistrationRow), C.POINTER(RegistrationPart), sz, dp, C.POINTER(RegistrationRow),
+                                                   C.POINTER(RegistrationPart)]
+        L.ppp_registration_step.argtypes = [C.POINTER(RegistrationRow), C.POINTER(RegistrationPart), C.c_double, dp, dp, ip, dp]
+        L.ppp_register_tiles.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz,
+                                         C.POINTER(RegisterTilesStats)]
         L.ppp_default_trimmed_registration_params.argtypes = [C.POINTER(TrimmedRegistrationParams)]
         L.ppp_default_trimmed_registration_params.restype = None
         L.ppp_register_trimmed.argtypes = [vp, vp, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow), sz, C.POINTER(C.c_ubyte), fp,
@@ -450,6 +456,20 @@ class RegistrationStats(C.Structure):
                 ("pairs_before", C.c_size_t), ("pairs_after", C.c_size_t), ("rms_before", C.c_double), ("rms_after", C.c_double)]
 
 
+class RegistrationPart(C.Structure):
+    """ppp_registration_part"""
+    _fields_ = [("owned", C.c_size_t), ("evaluated", C.c_size_t), ("own_lo", C.c_float), ("own_hi", C.c_float), ("n", C.c_size_t),
+                ("shift", C.c_int), ("centre", C.c_double * 3), ("length", C.c_double)]
+
+
+class RegisterTilesStats(C.Structure):
+    """ppp_register_tiles_stats"""
+    _fields_ = [("reg", RegistrationStats), ("failed_tile", C.c_int)]
+
+
+STEP_TAKEN, STEP_FEW_PAIRS, STEP_STATIONARY, STEP_ALL_LOCKED = range(4)  # PPP_STEP_*
+
+
 class TrimmedRegistrationParams(C.Structure):
     """ppp_trimmed_registration_params"""
     _fields_ = [("icp", RegistrationParams), ("keep", C.c_double)]
@@ -484,6 +504,92 @@ def _registration_stats(st):
     out["centre"] = np.array(st.centre[:], np.float64)
     out["T"] = np.array(st.T[:], np.float64).reshape(3, 4)
     return out
+
+
+def _registration_part(p):
+    """a RegistrationPart as a dict: owned, evaluated, own_lo, own_hi, n, shift, centre float64[3], length"""
+    out = {k: getattr(p, k) for k, _ in RegistrationPart._fields_}
+    out["centre"] = np.array(p.centre[:], np.float64)
+    return out
+
+
+def _row_struct(row, into=None):
+    r = RegistrationRow() if into is None else into
+    r.T[:] = [float(v) for v in np.asarray(row["T"], np.float64).reshape(12)]
+    r.pairs = int(row["pairs"])
+    r.A[:] = [int(v) for v in row["A"]]
+    r.b[:] = [int(v) for v in row["b"]]
+    r.E = int(row["E"])
+    r.locked = int(row.get("locked", 63))
+    r.step2 = float(row.get("step2", float("nan")))
+    return r
+
+
+def _part_struct(part, into=None):
+    p = RegistrationPart() if into is None else into
+    for k in ("owned", "evaluated", "own_lo", "own_hi", "n", "shift", "length"):
+        setattr(p, k, part[k])
+    p.centre[:] = [float(v) for v in part["centre"]]
+    return p
+
+
+def merge_registration_terms(tiles, T=None):
+    """(row, part) of the whole cloud from the tiles of ranges that tile the walk (ppp_merge_registration_terms: host only).
+    tiles = a sequence of Engine.registration_terms_tile() results (row, part).  The 29 words and pairs add as signed 64-bit
+    integers, owned and evaluated add; row["T"] = T (3 x 4, None: the identity).  The row is Engine.registration_terms()'s on
+    whole-cloud engines, bit for bit.  PPPError(ERR_ARG): no tile, parts that disagree on n, shift, centre or length, owned
+    intervals that overlap"""
+    k = len(tiles)
+    rows, parts = (RegistrationRow * max(k, 1))(), (RegistrationPart * max(k, 1))()
+    for i, (row, part) in enumerate(tiles):
+        _row_struct(row, rows[i])
+        _part_struct(part, parts[i])
+    out, opart = RegistrationRow(), RegistrationPart()
+    t = _t12(T)
+    rc = lib().ppp_merge_registration_terms(rows, parts, k, None if t is None else _d(t), C.byref(out), C.byref(opart))
+    if rc:
+        raise PPPError(rc, "ppp_merge_registration_terms: no tile, tiles that do not belong together, or owned intervals that overlap")
+    return _registration_row(out), _registration_part(opart)
+
+
+def registration_step(row, part, lock_eps=1e-9, T=None):
+    """(code, T' float64[3, 4], locked, step2): the step ppp_register takes from the evaluation `row` (ppp_registration_step: host
+    only); part gives centre and length, T (None: row["T"]) the transform the row was taken at.  code STEP_TAKEN, or -- with T'
+    = T, locked 63 and step2 NaN -- STEP_FEW_PAIRS, STEP_STATIONARY or STEP_ALL_LOCKED"""
+    r, p = _row_struct(row), _part_struct(part)
+    t = _t12(T)
+    out = np.zeros(12, np.float64)
+    locked, step2 = C.c_int(), C.c_double()
+    rc = lib().ppp_registration_step(C.byref(r), C.byref(p), float(lock_eps), None if t is None else _d(t), _d(out), C.byref(locked), C.byref(step2))
+    if rc < 0:
+        raise PPPError(rc, "ppp_registration_step: bad arguments")
+    return rc, out.reshape(3, 4), int(locked.value), float(step2.value)
+
+
+def register_tiles(engines, refs, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+    """(T float64[3, 4], rows, stats) as Engine.register() gives them, bit for bit, for a scan held as slice-range engines
+    (ppp_register_tiles): engines[i] holds the scan with range i, refs[i] is its reference engine (one whole-cloud engine may
+    stand in every slot; refs may also be that one engine).  Every evaluation is a host round trip: the tiles' words come back,
+    the host merges, solves and steps.  A tile's error is raised with its index in the message"""
+    engines = list(engines)
+    refs = [refs] * len(engines) if isinstance(refs, Engine) else list(refs)
+    if len(refs) != len(engines):
+        raise PPPError(ERR_ARG, "register_tiles: one reference per tile")
+    k = len(engines)
+    hs = (C.c_void_p * max(k, 1))(*[e.h for e in engines])
+    rs = (C.c_void_p * max(k, 1))(*[e.h for e in refs])
+    rp = RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps))
+    cap = max(int(iterations), 0) + 1
+    rows = (RegistrationRow * cap)()
+    st = RegisterTilesStats()
+    t = _t12(T0)
+    rc = lib().ppp_register_tiles(hs, rs, k, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st))
+    if rc:
+        at = st.failed_tile if st.failed_tile >= 0 else 0
+        text = engines[at].L.ppp_last_error(engines[at].h).decode() if k else "no tile"
+        raise PPPError(rc, "tile %d: %s" % (st.failed_tile, text))
+    stats = _registration_stats(st.reg)
+    return stats["T"].copy(), [_registration_row(rows[i]) for i in range(min(cap, st.reg.steps + 1))], stats
 
 
 class CloudFrame(C.Structure):
@@ -1259,6 +1365,19 @@ class Engine:
         t = _t12(T)
         self._chk(self.L.ppp_get_registration_terms(self.h, ref.h, C.byref(rp), None if t is None else _d(t), C.byref(row), C.byref(st)))
         return _registration_row(row), _registration_stats(st)
+
+    def registration_terms_tile(self, ref, T=None, max_dist=2.0, lock_eps=1e-9):
+        """(row, part): registration_terms() over the points this engine OWNS -- a slice-range engine of the scan, or a whole-cloud
+        one, which owns every indexed point -- against the cloud of the engine `ref`, whole or a slice range of the reference
+        (ppp_get_registration_terms_tile).  row as registration_terms() gives it; part = dict(owned, evaluated, own_lo, own_hi, n,
+        shift, centre, length), the frame and the shift being the whole clouds': what merge_registration_terms() and
+        registration_step() take.  A slice-range `ref` must index max_dist + its normal_radius around every moved query:
+        PPPError(ERR_CAPACITY) otherwise"""
+        rp = RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps))
+        row, part = RegistrationRow(), RegistrationPart()
+        t = _t12(T)
+        self._chk(self.L.ppp_get_registration_terms_tile(self.h, ref.h, C.byref(rp), None if t is None else _d(t), C.byref(row), C.byref(part)))
+        return _registration_row(row), _registration_part(part)
 
     def register(self, ref, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
         """(T float64[3, 4], rows, stats): point-to-plane ICP of this engine's cloud, the scan, to the cloud of the engine `ref`

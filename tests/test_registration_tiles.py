@@ -1,0 +1,749 @@
+"""Registration of a scan held as slice-range tiles (ppp_get_registration_terms_tile, ppp_merge_registration_terms,
+ppp_registration_step, ppp_register_tiles).
+
+Every comparison is for equality.  An evaluation is 29 signed 64-bit integer sums over the scan's pairs, integer sums have no
+order and the owned sets of ranges that tile the walk partition the indexed points: the merged row must be
+ppp_get_registration_terms' row on whole-cloud handles in every word, and test_registration's restatement.  The host step runs
+the device chain's own routines, so the tiled loop must be ppp_register's T, rows and statistics bit for bit.  No tolerance
+appears anywhere in this file.
+
+The clouds are test_registration's known motion (reference 94 x 52, scan 80 x 44 moved by 1 degree and 0.8 mm: 5 slices of the
+default walk, cut into [0, 1), [1, 3), [3, 5) -- the middle tile is interior, with a seam at x = 53 and one at x = 101.5) and
+test_deviation's large_clouds past the grid cap.  range_margin is the default 24 mm: a reference range indexes from
+int(px[sb]) - 2 - 24, and the census asserts by restatement that this covers max_dist + normal_radius = 5.5 mm around every
+moved query of every transform the loop visits."""
+import ctypes
+import functools
+import itertools
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from polishpathplanning_amd import synth
+from polishpathplanning_amd.robot_path import slice_ranges
+from test_contact_tiles import RANGE_MARGIN
+from test_deviation import INF, KW0, bumped, large_clouds, past_the_grid_cap
+from test_deviation_tiles import cuts_of, device_count, finite_rows, handle, ranges3
+from test_registration import (ALL_LOCKED, IDENTITY, KNOWN, LARGE, NAN, box_centre, flat_clouds, known_clouds, large_T0, oracle_normals,
+                               restate_register, restate_step, restate_terms, rows_equal, stats_equal)
+from test_path_dwell import same
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NORMAL_RADIUS = 2.5                          # ppp_default_params
+PART_FIELDS = ("owned", "evaluated", "own_lo", "own_hi", "n", "shift", "centre", "length")
+PART_DECL = ("typedef struct {\n"
+             "    size_t owned, evaluated;   /* indexed points owned; index positions visited */\n"
+             "    float  own_lo, own_hi;     /* the owned interval [own_lo, own_hi) */\n"
+             "    size_t n;                  /* cloud->size() of the whole scan */\n"
+             "    int    shift;              /* the fixed point is 2^shift */\n"
+             "    double centre[3], length;  /* c and Ln of ppp_register, from the whole reference */\n"
+             "} ppp_registration_part;")
+TILES_STATS_DECL = ("typedef struct {\n"
+                    "    ppp_registration_stats reg; /* ppp_register's statistics */\n"
+                    "    int failed_tile;            /* the tile whose error ended the loop; -1: none */\n"
+                    "} ppp_register_tiles_stats;")
+STEP_DECL = "enum { PPP_STEP_TAKEN = 0, PPP_STEP_FEW_PAIRS = 1, PPP_STEP_STATIONARY = 2, PPP_STEP_ALL_LOCKED = 3 };"
+FUNC_DECLS = ("int ppp_get_registration_terms_tile(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12,\n"
+              "                                    ppp_registration_row *row, ppp_registration_part *part);",
+              "int ppp_merge_registration_terms(const ppp_registration_row *rows, const ppp_registration_part *parts, size_t count,\n"
+              "                                 const double *T12, ppp_registration_row *out_row, ppp_registration_part *out_part);",
+              "int ppp_registration_step(const ppp_registration_row *row, const ppp_registration_part *part, double lock_eps,\n"
+              "                          const double *T12, double *T12_out, int *locked, double *step2);",
+              "int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp,\n"
+              "                       const double *T0_12, ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats);")
+SYMBOLS = ("ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles")
+# what the census below measured with the oracle's normals, per tile of ranges3(5): the owned points, and the pairs at the
+# identity and at the chain's second transform (every owned point pairs: the scan lies inside the reference)
+KNOWN_OWNED = (670, 1429, 1421)
+KNOWN_PAIRS = {"identity": (670, 1429, 1421), "second": (670, 1429, 1421)}
+
+
+# ---------------------------------------------------------------- the definitions, in numpy
+
+
+def reach_of(max_dist, normal_radius=NORMAL_RADIUS):
+    """B.89: 1.0001f * (max_dist + normal_radius), the sum and the product in float"""
+    return np.float32(1.0001) * (np.float32(max_dist) + np.float32(normal_radius))
+
+
+def indexed_interval(E, P, rng, **kw):
+    """the x interval a handle of the cloud P with the slice range rng indexes (ppp_range_interval: host arithmetic)"""
+    f = finite_rows(P)
+    p = E.default_params(**dict(KW0, slice_begin=rng[0], slice_end=rng[1], **kw))
+    lo, hi, S = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+    assert E.lib().ppp_range_interval(ctypes.byref(p), float(P[f, 0].min()), float(P[f, 0].max()), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(S)) == 0
+    return np.float32(lo.value), np.float32(hi.value)
+
+
+def refusing(qx, lo, hi, ref_mn, ref_mx, reach):
+    """B.89 for the float32 moved x of the owned queries: which of them reach beyond [lo, hi] at a side that is not the cloud's end"""
+    qx = np.asarray(qx, np.float32)
+    left = np.nextafter(qx - reach, np.float32(-INF))
+    right = np.nextafter(qx + reach, np.float32(INF))
+    return ((left < lo) & (lo > ref_mn)) | ((right > hi) & (hi < ref_mx))
+
+
+def moved_x(T, P):
+    """the float32 x of the points P moved by T as the engine moves them (B.69)"""
+    T = np.asarray(T, np.float64).reshape(3, 4)
+    p = P.astype(np.float64)
+    return (((T[0, 0] * p[:, 0] + T[0, 1] * p[:, 1]) + T[0, 2] * p[:, 2]) + T[0, 3]).astype(np.float32)
+
+
+def owned_rows(P, cuts, rng):
+    return finite_rows(P) & (P[:, 0] >= cuts[rng[0]]) & (P[:, 0] < cuts[rng[1]])
+
+
+def part_of(whole, owned, lo=-INF, hi=INF, evaluated=None):
+    """a hand-made ppp_registration_part in the frame of the restatement's row `whole`"""
+    return dict(owned=int(owned), evaluated=int(owned if evaluated is None else evaluated), own_lo=float(lo), own_hi=float(hi), n=int(whole["n"]),
+                shift=int(whole["shift"]), centre=np.asarray(whole["centre"], np.float64).copy(), length=float(whole["length"]))
+
+
+@functools.lru_cache(maxsize=None)
+def known_restated_cpu():
+    """(T, rows, stats) of the known motion by restatement with the oracle's normals; computed once, nobody writes to it"""
+    ref, scan, moved, Tm = known_clouds()
+    mn, mx, _ = box_centre(ref)
+    return restate_register(moved, ref, oracle_normals(ref), mn, mx, **KNOWN)
+
+
+# ---------------------------------------------------------------- CPU: header and ABI
+
+
+def test_header_declares_and_engine_exports_the_registration_tiles(engine_mod):
+    hdr = open(os.path.join(ROOT, "include", "ppp_hip.h")).read()
+    decls = (PART_DECL, TILES_STATS_DECL, STEP_DECL) + FUNC_DECLS
+    for decl in decls:
+        assert decl in hdr, decl
+    at = [hdr.index("int ppp_merge_deviation_tiles(")] + [hdr.index(d) for d in decls] + [hdr.index("int ppp_eval_spline(")]
+    assert at == sorted(at)
+    assert "DESIGN.md 7o, B.88-B.94" in hdr and "The test is conservative" in hdr and "raise\n               range_margin" in hdr
+    for sym in SYMBOLS:
+        assert sym in engine_mod.EXPORTS and hasattr(engine_mod.lib(), sym), sym
+    assert hasattr(engine_mod.Engine, "registration_terms_tile")
+    for f in ("merge_registration_terms", "registration_step", "register_tiles"):
+        assert callable(getattr(engine_mod, f)), f
+    planner = open(os.path.join(ROOT, "include", "ppp_planner.hpp")).read()
+    assert "bool registration_terms_tile(const Planner &ref, ppp_registration_row &row, ppp_registration_part &part, " in planner
+    assert "inline bool register_tiles(std::vector<Planner *> &tiles, std::vector<Planner *> &refs, ppp_register_tiles_stats &st," in planner
+
+
+def test_header_is_c99_clean_with_the_registration_tiles(tmp_path):
+    src = tmp_path / "c99.c"
+    src.write_text('#include "ppp_hip.h"\nint main(void) {\n'
+                   '    int (*f)(ppp_handle, ppp_handle, const ppp_registration_params *, const double *, ppp_registration_row *,\n'
+                   '             ppp_registration_part *) = ppp_get_registration_terms_tile;\n'
+                   '    int (*g)(const ppp_registration_row *, const ppp_registration_part *, size_t, const double *, ppp_registration_row *,\n'
+                   '             ppp_registration_part *) = ppp_merge_registration_terms;\n'
+                   '    int (*s)(const ppp_registration_row *, const ppp_registration_part *, double, const double *, double *, int *,\n'
+                   '             double *) = ppp_registration_step;\n'
+                   '    int (*l)(const ppp_handle *, const ppp_handle *, size_t, const ppp_registration_params *, const double *,\n'
+                   '             ppp_registration_row *, size_t, ppp_register_tiles_stats *) = ppp_register_tiles;\n'
+                   '    ppp_registration_part p;\n    ppp_register_tiles_stats st;\n'
+                   '    p.owned = 0; p.evaluated = 0; p.own_hi = 0.f; p.shift = 40; p.centre[2] = 0.0; p.length = 1.0; st.failed_tile = -1; st.reg.steps = 0;\n'
+                   '    return f == 0 || g == 0 || s == 0 || l == 0 || p.shift != 40 || st.failed_tile != -1 || PPP_STEP_ALL_LOCKED != 3;\n}\n')
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
+
+
+def test_registration_part_layout_matches_the_header(engine_mod, tmp_path):
+    E = engine_mod
+    structs = (("ppp_registration_part", PART_FIELDS, E.RegistrationPart), ("ppp_register_tiles_stats", ("reg", "failed_tile"), E.RegisterTilesStats))
+    args, want = [], []
+    for name, fields, T in structs:
+        args += ["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields]
+        want += [ctypes.sizeof(T)] + [getattr(T, f).offset for f in fields]
+        assert tuple(f for f, _ in T._fields_) == fields
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppp_hip.h"\nint main(void) {\n'
+                   '    printf("' + " ".join(["%zu"] * len(args)) + '\\n", ' + ", ".join(args) + ');\n    return 0;\n}\n')
+    exe = str(tmp_path / "layout")
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", exe, str(src)])
+    got = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert got == want
+    assert (E.STEP_TAKEN, E.STEP_FEW_PAIRS, E.STEP_STATIONARY, E.STEP_ALL_LOCKED) == (0, 1, 2, 3)
+
+
+def test_the_library_is_built_without_contraction():
+    """the host step and the device step are one source (icp_solve, icp_compose): both sides of the unit that holds them must
+    round every written operation once, so the unit's flags carry -ffp-contract=off and no rule of the Makefile overrides them
+    for it (test_host_step_equals_the_restatement decides the bits)"""
+    mk = open(os.path.join(ROOT, "polishpathplanning_amd", "csrc", "Makefile")).read()
+    flags = [l for l in mk.splitlines() if l.startswith("HIPFLAGS")]
+    assert len(flags) == 1 and "-ffp-contract=off" in flags[0]
+    assert "ppp_contact" in [l for l in mk.splitlines() if l.startswith("UNITS")][0]
+    assert not any(l.startswith("ppp_contact.o: HIPFLAGS") for l in mk.splitlines())
+    assert "ppp_registration_tile.h" in [l for l in mk.splitlines() if l.startswith("CONTACT_HDR")][0]
+
+
+# ---------------------------------------------------------------- CPU: the census
+
+
+def test_census_of_the_tiled_known_motion(engine_mod):
+    """by restatement alone, with the oracle's normals: the known motion in ranges3(5) at the identity and at the chain's second
+    transform -- per tile the owned points and the pairs, at least 6 pairs in every tile, at every interior seam owned points
+    whose partner lies on the other side of the reference's matching cut, and for every transform the chain visits every moved
+    query's reach inside what the reference's matching default range handle indexes (B.89)"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    T, rows, st = known_restated_cpu()
+    S, cuts = cuts_of(E, moved)
+    Sr, rcuts = cuts_of(E, ref)
+    print("scan: %d slices, cuts %r; reference: %d slices, cuts %r; chain of %d steps" % (S, cuts.tolist(), Sr, rcuts.tolist(), st["steps"]))
+    assert S == Sr == 5 and st["steps"] >= 3 and st["converged"] == 1
+    assert cuts[1] == rcuts[1] == np.float32(53.0) and cuts[3] > np.float32(101.0) and rcuts[3] > np.float32(101.0)
+    rng, rrng = ranges3(S), ranges3(Sr)
+    assert rng == rrng == [(0, 1), (1, 3), (3, 5)]
+    mn, mx, _ = box_centre(ref)
+    x = moved[:, 0]
+    assert sum(int(owned_rows(moved, cuts, r).sum()) for r in rng) == st["indexed"] == len(moved)
+    for name, row in (("identity", rows[0]), ("second", rows[1])):
+        assert name != "identity" or same(row["T"], IDENTITY)
+        owned, pairs = [], []
+        for t, (b, e) in enumerate(rng):
+            mine = owned_rows(moved, cuts, (b, e))
+            pr = mine & (row["partner"] >= 0)
+            owned.append(int(mine.sum())); pairs.append(int(pr.sum()))
+        print("%s: owned %r pairs %r (whole %d)" % (name, owned, pairs, row["pairs"]))
+        assert tuple(owned) == KNOWN_OWNED and tuple(pairs) == KNOWN_PAIRS[name] and sum(pairs) == row["pairs"] and min(pairs) >= 6
+        for s in (1, 3):                                                    # the interior seams: cut(1) and cut(3)
+            below = (x < cuts[s]) & (row["partner"] >= 0)
+            above = (x >= cuts[s]) & (row["partner"] >= 0)
+            px = np.where(row["partner"] >= 0, ref[np.maximum(row["partner"], 0), 0], np.float32(NAN))
+            across = int((below & (px >= rcuts[s])).sum()) + int((above & (px < rcuts[s])).sum())
+            print("    seam %d at %r (reference %r): %d owned points paired across the reference's cut" % (s, cuts[s], rcuts[s], across))
+            assert across >= 1
+    reach = reach_of(KNOWN["max_dist"])
+    for k, row in enumerate(rows):
+        for t, r in enumerate(rng):
+            lo, hi = indexed_interval(E, ref, rrng[t])
+            q = moved_x(row["T"], moved[owned_rows(moved, cuts, r)])
+            bad = refusing(q, lo, hi, mn[0], mx[0], reach)
+            if k < 2:
+                print("    row %d tile %d: moved x in [%r, %r], the reference's range %r indexes [%r, %r]" % (k, t, q.min(), q.max(), rrng[t], lo, hi))
+            assert not bad.any(), (k, t)
+
+
+def test_census_of_the_refusal_case(engine_mod):
+    """the middle tile of the known motion against the reference's range (1, 3) with range_margin 17: every moved query's reach
+    lies inside the indexed interval at the identity, and a shift of 5 mm in x carries some beyond its upper end"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    S, cuts = cuts_of(E, moved)
+    mn, mx, _ = box_centre(ref)
+    mine = moved[owned_rows(moved, cuts, ranges3(S)[1])]
+    lo, hi = indexed_interval(E, ref, (1, 3), range_margin=THIN_MARGIN)
+    reach = reach_of(KNOWN["max_dist"])
+    at0 = refusing(moved_x(IDENTITY, mine), lo, hi, mn[0], mx[0], reach)
+    at5 = refusing(moved_x(SHIFT_5MM, mine), lo, hi, mn[0], mx[0], reach)
+    print("range (1, 3) with margin %r indexes [%r, %r]; refusing queries: %d at the identity, %d shifted by 5 mm" % (THIN_MARGIN, lo, hi, at0.sum(), at5.sum()))
+    assert mn[0] < lo and hi < mx[0] and not at0.any() and at5.any()
+
+
+THIN_MARGIN = 17.0
+SHIFT_5MM = np.array([[1, 0, 0, 5.0], [0, 1, 0, 0], [0, 0, 1, 0]], np.float64)
+
+
+# ---------------------------------------------------------------- CPU: the merge
+
+
+def hand_row(seed, big=0, neg=False):
+    rs = np.random.RandomState(seed)
+    A = rs.randint(-2 ** 40, 2 ** 40, 21).astype(np.int64) + np.int64(big)
+    b = rs.randint(-2 ** 40, 2 ** 40, 6).astype(np.int64)
+    if neg:
+        b = -np.abs(b) - np.int64(2 ** 45)
+    return dict(T=IDENTITY.copy(), pairs=int(rs.randint(6, 1000)), A=A, b=b, E=int(rs.randint(0, 2 ** 50)) + int(big), locked=ALL_LOCKED, step2=NAN)
+
+
+def test_merge_of_hand_made_parts(engine_mod):
+    """words that carry into bit 62, negative b, an empty part that adds nothing, any order of the parts, and every PPP_ERR_ARG"""
+    E = engine_mod
+    frame = dict(n=5000, shift=40, centre=np.array([1.5, -2.25, 0.125]), length=77.0)
+    rows = [hand_row(1, big=2 ** 61 + 2 ** 43), hand_row(2, big=2 ** 61 + 2 ** 43 + 7), hand_row(3, neg=True)]
+    zero = dict(T=IDENTITY.copy(), pairs=0, A=np.zeros(21, np.int64), b=np.zeros(6, np.int64), E=0, locked=ALL_LOCKED, step2=NAN)
+    parts = [part_of(frame, 100, -INF, 10.0, 120), part_of(frame, 200, 10.0, 20.0, 260), part_of(frame, 300, 20.0, INF, 310)]
+    empty = part_of(frame, 0, INF, -INF, 0)
+    tiles = list(zip(rows, parts))
+    T = np.arange(12, dtype=np.float64).reshape(3, 4) * 0.5
+    row, part = E.merge_registration_terms(tiles, T)
+    for f, n in (("A", 21), ("b", 6)):
+        for w in range(n):
+            assert int(row[f][w]) == sum(int(r[f][w]) for r in rows), (f, w)
+    assert row["E"] == sum(r["E"] for r in rows) and row["pairs"] == sum(r["pairs"] for r in rows)
+    assert int(row["A"][0]) >= 2 ** 62 and row["E"] >= 2 ** 62 and all(int(v) < 0 for v in rows[2]["b"])
+    assert same(row["T"], T) and row["locked"] == ALL_LOCKED and math.isnan(row["step2"])
+    assert (part["owned"], part["evaluated"], part["own_lo"], part["own_hi"]) == (600, 690, -INF, INF)
+    assert (part["n"], part["shift"], part["length"]) == (5000, 40, 77.0) and same(part["centre"], frame["centre"])
+    assert same(E.merge_registration_terms(tiles)[0]["T"], IDENTITY)        # T = None: the identity
+    with_empty = tiles + [(zero, empty)]
+    for order in itertools.permutations(range(4)):
+        got = E.merge_registration_terms([with_empty[i] for i in order], T)
+        assert same(got, (row, part)), order
+    # a part whose interval owns no point but is not empty, between two that meet it: equal ends are fine
+    assert same(E.merge_registration_terms([tiles[0], (zero, part_of(frame, 0, 10.0, 10.0)), tiles[1], tiles[2]], T)[0], row)
+    # a single part is itself
+    one = E.merge_registration_terms([tiles[2]], T)
+    assert all(same(one[0][f], rows[2][f]) for f in ("pairs", "A", "b", "E"))
+
+    def refused(bad):
+        with pytest.raises(E.PPPError) as ex:
+            E.merge_registration_terms(bad, T)
+        assert ex.value.code == E.ERR_ARG
+
+    refused([])                                                             # count == 0
+    for k, v in (("n", 5001), ("shift", 39), ("length", np.nextafter(77.0, 78.0)), ("centre", np.array([1.5, -2.25, np.nextafter(0.125, 1.0)]))):
+        refused([tiles[0], (rows[1], dict(parts[1], **{k: v})), tiles[2]])
+    refused([(rows[0], dict(parts[0], centre=np.array([0.0, 0.0, 0.0]))), (rows[1], dict(parts[1], centre=np.array([0.0, -0.0, 0.0])))])   # bit for bit
+    refused([tiles[0], (rows[1], dict(parts[1], own_lo=np.nextafter(np.float32(10.0), np.float32(0.0)))), tiles[2]])   # overlaps by one float
+    refused([tiles[0], (rows[1], part_of(frame, 5, -INF, INF))])            # a whole-cloud part beside another
+    L = E.lib()
+    r3, p3 = (E.RegistrationRow * 3)(), (E.RegistrationPart * 3)()
+    for i, (r, p) in enumerate(tiles):
+        E._row_struct(r, r3[i]); E._part_struct(p, p3[i])
+    out, opart = E.RegistrationRow(), E.RegistrationPart()
+    assert L.ppp_merge_registration_terms(r3, p3, 3, None, ctypes.byref(out), ctypes.byref(opart)) == 0
+    assert L.ppp_merge_registration_terms(r3, p3, 3, None, ctypes.byref(out), None) == 0                      # out_part is optional
+    assert L.ppp_merge_registration_terms(None, p3, 3, None, ctypes.byref(out), ctypes.byref(opart)) == E.ERR_ARG
+    assert L.ppp_merge_registration_terms(r3, None, 3, None, ctypes.byref(out), ctypes.byref(opart)) == E.ERR_ARG
+    assert L.ppp_merge_registration_terms(r3, p3, 3, None, None, ctypes.byref(opart)) == E.ERR_ARG
+    assert L.ppp_merge_registration_terms(r3, p3, 0, None, ctypes.byref(out), ctypes.byref(opart)) == E.ERR_ARG
+
+
+def test_merge_of_restated_tiles_is_the_restated_whole(engine_mod):
+    """the restatement's own terms over each tile's owned points, merged by the C call, are the restatement's terms over the
+    whole scan in every word: at the identity and at the chain's second transform"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    T, rows, st = known_restated_cpu()
+    S, cuts = cuts_of(E, moved)
+    mn, mx, _ = box_centre(ref)
+    N = oracle_normals(ref)
+    for whole in rows[:2]:
+        tiles = []
+        for r in ranges3(S):
+            mine = owned_rows(moved, cuts, r)
+            P = moved.copy()
+            P[~mine] = np.float32(NAN)                                      # not indexed: the tile's scan with n unchanged
+            got = restate_terms(P, ref, N, mn, mx, KNOWN["max_dist"], whole["T"])
+            assert got["indexed"] == mine.sum() and got["shift"] == whole["shift"]
+            tiles.append((got, part_of(whole, mine.sum(), cuts[r[0]], cuts[r[1]])))
+        row, part = E.merge_registration_terms(tiles, whole["T"])
+        for f in ("T", "pairs", "A", "b", "E"):
+            assert same(row[f], whole[f]), f
+        assert part["owned"] == whole["indexed"] and (part["own_lo"], part["own_hi"]) == (-INF, INF)
+
+
+# ---------------------------------------------------------------- CPU: the host step
+
+
+def step_cases():
+    """(label, row, centre, length, lock_eps): every row of the known motion's chain (nothing locked) and of the flat plate's
+    (0b011100 locked), and hand-made rows with fewer than 6 pairs, with six zero b, and with a system that locks everything"""
+    out = []
+    T, rows, st = known_restated_cpu()
+    out += [("known %d" % k, r, st["centre"], st["length"], KNOWN["lock_eps"]) for k, r in enumerate(rows)]
+    ref, scan, moved, Tm = flat_clouds()
+    mn, mx, _ = box_centre(ref)
+    T, rows, st = restate_register(moved, ref, oracle_normals(ref), mn, mx, **KNOWN)
+    out += [("flat %d" % k, r, st["centre"], st["length"], KNOWN["lock_eps"]) for k, r in enumerate(rows)]
+    base = rows[0]
+    out.append(("five pairs", dict(base, pairs=5), st["centre"], st["length"], 1e-9))
+    out.append(("zero b", dict(base, b=np.zeros(6, np.int64)), st["centre"], st["length"], 1e-9))
+    out.append(("zero b, five pairs", dict(base, pairs=5, b=np.zeros(6, np.int64)), st["centre"], st["length"], 1e-9))
+    out.append(("all locked", dict(base, A=np.zeros(21, np.int64)), st["centre"], st["length"], 1e-9))
+    neg = base["A"].copy()
+    neg[[0, 6, 11, 15, 18, 20]] = -np.abs(neg[[0, 6, 11, 15, 18, 20]])      # a negative diagonal: no pivot passes
+    out.append(("all locked, negative diagonal", dict(base, A=neg), st["centre"], st["length"], 1e-9))
+    out.append(("lock_eps close to one", base, st["centre"], st["length"], 1.0 - 2.0 ** -20))
+    return out
+
+
+def test_host_step_equals_the_restatement(engine_mod):
+    """ppp_registration_step against restate_step: the mask, T' and step2 bit for bit where a step is taken, and no step exactly
+    where restate_step takes none, with the code that tells why"""
+    E = engine_mod
+    taken = masks = 0
+    for label, row, c, Ln, eps in step_cases():
+        part = dict(owned=row["indexed"], evaluated=row["indexed"], own_lo=-INF, own_hi=INF, n=row["n"], shift=row["shift"], centre=c, length=Ln)
+        want = restate_step(row, c, Ln, eps)
+        code, Tn, locked, step2 = E.registration_step(row, part, eps)
+        print("%-32s code %d locked %s step2 %r" % (label, code, bin(locked), step2))
+        if want is None:
+            why = E.STEP_FEW_PAIRS if row["pairs"] < 6 else E.STEP_STATIONARY if not np.any(row["b"]) else E.STEP_ALL_LOCKED
+            assert code == why and locked == ALL_LOCKED and math.isnan(step2) and same(Tn, np.asarray(row["T"], np.float64)), label
+            continue
+        mask, x, wT, wstep2 = want
+        assert code == E.STEP_TAKEN and locked == mask and same(step2, wstep2) and same(Tn, wT), label
+        taken += 1; masks += mask == 0b011100
+        other = np.asarray(row["T"], np.float64) + 0.25                    # T12 given: composed with it, not with row.T
+        assert same(E.registration_step(row, part, eps, T=other)[1], restate_step(dict(row, T=other), c, Ln, eps)[2]), label
+    assert taken >= 6 and masks >= 1
+    # the chain, re-walked by the host step: every T of the restated chain comes back
+    T, rows, st = known_restated_cpu()
+    part = part_of(rows[0], rows[0]["indexed"])
+    for k in range(st["steps"]):
+        code, Tn, locked, step2 = E.registration_step(rows[k], part, KNOWN["lock_eps"])
+        assert code == E.STEP_TAKEN and same(Tn, rows[k + 1]["T"]) and locked == rows[k]["locked"] and same(step2, rows[k]["step2"])
+    L = E.lib()
+    r, p = E._row_struct(rows[0]), E._part_struct(part)
+    out = (ctypes.c_double * 12)()
+    assert L.ppp_registration_step(ctypes.byref(r), ctypes.byref(p), 1e-9, None, out, None, None) == E.STEP_TAKEN      # locked, step2 optional
+    assert L.ppp_registration_step(None, ctypes.byref(p), 1e-9, None, out, None, None) == E.ERR_ARG
+    assert L.ppp_registration_step(ctypes.byref(r), None, 1e-9, None, out, None, None) == E.ERR_ARG
+    assert L.ppp_registration_step(ctypes.byref(r), ctypes.byref(p), 1e-9, None, None, None, None) == E.ERR_ARG
+    for eps in (0.0, 1.0, NAN, -1.0):
+        assert L.ppp_registration_step(ctypes.byref(r), ctypes.byref(p), eps, None, out, None, None) == E.ERR_ARG
+    for length in (0.0, INF, NAN):
+        q = E._part_struct(dict(part, length=length))
+        assert L.ppp_registration_step(ctypes.byref(r), ctypes.byref(q), 1e-9, None, out, None, None) == E.ERR_ARG
+
+
+# ---------------------------------------------------------------- GPU
+
+_WHOLE = {}
+
+
+def whole_of(E, key, ref, scan, T0=None, **p):
+    """(register's (T, rows, stats), the restatement's from the engine's own getters) on whole-cloud handles, once per case"""
+    k = (key, None if T0 is None else np.asarray(T0).tobytes(), tuple(sorted(p.items())))
+    if k not in _WHOLE:
+        r, s = handle(E, ref), handle(E, scan)
+        got = s.register(r, T0=T0, **p)
+        mn, mx = r.minmax()
+        want = restate_register(s.cloud(), r.cloud(), r.estimate_normals(), mn, mx, T0=T0, **p)
+        _WHOLE[k] = (got, want)
+        r.close(); s.close()
+    return _WHOLE[k]
+
+
+def open_tiles(E, ref, scan, ranges, ref_ranges=None, **refkw):
+    """(the scan's range handles, their reference handles, everything to close)"""
+    hs = [handle(E, scan, r) for r in ranges]
+    if ref_ranges is None:
+        whole = handle(E, ref)
+        return hs, [whole] * len(hs), hs + [whole]
+    rs = [handle(E, ref, r, **refkw) for r in ref_ranges]
+    return hs, rs, hs + rs
+
+
+def check_parts(parts, scan, cuts, ranges, first):
+    """every part against the cuts: the owned set's size, the interval, the whole clouds' frame; the owned sum"""
+    for (b, e), part in zip(ranges, parts):
+        mine = owned_rows(scan, cuts, (b, e))
+        print("    range [%d, %d): owned %d evaluated %d interval [%r, %r)" % (b, e, part["owned"], part["evaluated"], part["own_lo"], part["own_hi"]))
+        assert part["owned"] == mine.sum() and part["evaluated"] >= part["owned"]
+        assert (np.float32(part["own_lo"]), np.float32(part["own_hi"])) == (cuts[b], cuts[e])
+        assert (part["n"], part["shift"], part["length"]) == (first["n"], first["shift"], first["length"]) and same(part["centre"], first["centre"])
+    assert sum(p["owned"] for p in parts) == first["indexed"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ref_ranged", [False, True])
+def test_tiles_add_up_to_the_whole_terms(engine_mod, ref_ranged):
+    """the known motion in three ranges, at the identity and at the chain's second transform, the reference whole or in its own
+    three default ranges: the merged row is ppp_get_registration_terms' on whole-cloud handles in every word, and the
+    restatement's; a whole-cloud scan handle is one tile that owns everything and equals it alone"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    (T, rows, st), (wT, wrows, wst) = whole_of(E, "known", ref, moved, **KNOWN)
+    S, cuts = cuts_of(E, moved)
+    Sr, _ = cuts_of(E, ref)
+    ranges = ranges3(S)
+    hs, rs, everything = open_tiles(E, ref, moved, ranges, ranges3(Sr) if ref_ranged else None)
+    r_whole, s_whole = handle(E, ref), handle(E, moved)
+    for at in (None, wrows[1]["T"]):
+        whole_row, whole_st = s_whole.registration_terms(r_whole, T=at, max_dist=KNOWN["max_dist"])
+        tiles = [h.registration_terms_tile(r, T=at, max_dist=KNOWN["max_dist"]) for h, r in zip(hs, rs)]
+        print("T %s: pairs per tile %r, whole %d" % ("identity" if at is None else "second", [t[0]["pairs"] for t in tiles], whole_row["pairs"]))
+        check_parts([t[1] for t in tiles], moved, cuts, ranges, wrows[0])
+        assert all(t[0]["pairs"] >= 6 and t[0]["locked"] == ALL_LOCKED and math.isnan(t[0]["step2"]) for t in tiles)
+        row, part = E.merge_registration_terms(tiles, at)
+        rows_equal([row], [whole_row])
+        rows_equal([row], [dict(wrows[0 if at is None else 1], locked=ALL_LOCKED, step2=NAN)])
+        assert part["owned"] == whole_st["indexed"] and (part["own_lo"], part["own_hi"]) == (-INF, INF)
+        again = [h.registration_terms_tile(r, T=at, max_dist=KNOWN["max_dist"]) for h, r in zip(hs, rs)]
+        assert same(again, tiles)                                           # the same bits in every run
+        one_row, one_part = s_whole.registration_terms_tile(rs[0] if not ref_ranged else r_whole, T=at, max_dist=KNOWN["max_dist"])
+        rows_equal([one_row], [whole_row])
+        assert one_part["owned"] == one_part["evaluated"] == whole_st["indexed"] and (one_part["own_lo"], one_part["own_hi"]) == (-INF, INF)
+        assert (one_part["n"], one_part["shift"], one_part["length"]) == (whole_st["n"], whole_st["shift"], whole_st["length"])
+        assert same(one_part["centre"], whole_st["centre"])
+    for e in everything + [r_whole, s_whole]:
+        e.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ref_ranged", [False, True])
+def test_tiled_loop_equals_the_whole_loop(engine_mod, ref_ranged):
+    """ppp_register_tiles on the three ranges against ppp_register on whole-cloud handles and against the restatement: T, every
+    row and every statistic bit for bit; the chain takes at least 3 steps"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    (T, rows, st), (wT, wrows, wst) = whole_of(E, "known", ref, moved, **KNOWN)
+    assert wst["steps"] >= 3 and wst["converged"] == 1
+    S, _ = cuts_of(E, moved)
+    Sr, _ = cuts_of(E, ref)
+    hs, rs, everything = open_tiles(E, ref, moved, ranges3(S), ranges3(Sr) if ref_ranged else None)
+    gT, grows, gst = E.register_tiles(hs, rs, **KNOWN)
+    print("steps %d (whole %d, restated %d) converged %d rms %r -> %r" % (gst["steps"], st["steps"], wst["steps"], gst["converged"], gst["rms_before"],
+                                                                          gst["rms_after"]))
+    rows_equal(grows, rows); stats_equal(gst, st); assert same(gT, T)
+    rows_equal(grows, wrows); stats_equal(gst, wst); assert same(gT, wT)
+    again = E.register_tiles(hs, rs, **KNOWN)
+    assert same(again, (gT, grows, gst))
+    # iterations used up: the last row is an evaluation no step follows; row_cap below the number of rows
+    (T2, rows2, st2), _ = whole_of(E, "known", ref, moved, **dict(KNOWN, iterations=2))
+    g2 = E.register_tiles(hs, rs, **dict(KNOWN, iterations=2))
+    rows_equal(g2[1], rows2); stats_equal(g2[2], st2)
+    assert st2["steps"] == 2 and st2["converged"] == 0 and len(g2[1]) == 3
+    k = len(hs)
+    hv = (ctypes.c_void_p * k)(*[h.h for h in hs]); rv = (ctypes.c_void_p * k)(*[r.h for r in rs])
+    rp = E.RegistrationParams(KNOWN["max_dist"], KNOWN["iterations"], KNOWN["min_step"], KNOWN["lock_eps"])
+    buf = (E.RegistrationRow * 4)()
+    size = ctypes.sizeof(E.RegistrationRow)
+    ctypes.memset(buf, 0xA5, 4 * size)
+    raw = E.RegisterTilesStats()
+    assert E.lib().ppp_register_tiles(hv, rv, k, ctypes.byref(rp), None, buf, 2, ctypes.byref(raw)) == 0 and raw.failed_tile == -1
+    rows_equal([E._registration_row(buf[0]), E._registration_row(buf[1])], rows[:2])
+    stats_equal(E._registration_stats(raw.reg), st)
+    assert ctypes.string_at(ctypes.addressof(buf) + 2 * size, 2 * size) == b"\xa5" * (2 * size)
+    assert E.lib().ppp_register_tiles(hv, rv, k, ctypes.byref(rp), None, None, 0, None) == 0                  # rows and stats are optional
+    for e in everything:
+        e.close()
+
+
+@pytest.mark.gpu
+def test_seams(engine_mod):
+    """a scan point whose x is exactly cut(s) is owned by the upper tile and by no other; a range that owns no point gives a
+    zero row and PPP_OK; with a tile of fewer than 6 pairs the tiled loop still steps and equals the whole loop"""
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    S, cuts = cuts_of(E, moved)
+    P = moved.copy()
+    x = P[:, 0]
+    at = [int(np.abs(x - cuts[s]).argmin()) for s in (1, 3)]
+    for i, s in zip(at, (1, 3)):
+        P[i, 0] = cuts[s]                                                   # exactly on the cut; the bounds stay: interior points
+    # a gap over all of slice 2's owned interval [cut(2), cut(3)): the rows are taken out, the walk stays
+    gap = (x >= cuts[2]) & (x < cuts[3])
+    P = P[~gap]
+    # all but three of tile 0's points 1 000 mm off in z: finite, indexed, owned, unpaired
+    low = np.nonzero(P[:, 0] < cuts[1])[0]
+    P[low[3:], 2] += np.float32(1000.0)
+    assert cuts_of(E, P)[1].tobytes() == cuts.tobytes()
+    ranges = [(0, 1), (1, 2), (2, 3), (3, 5)]
+    want_owned = [int(owned_rows(P, cuts, r).sum()) for r in ranges]
+    assert want_owned[2] == 0 and min(want_owned[0], want_owned[1], want_owned[3]) > 6
+    assert (P[:, 0] == cuts[1]).sum() == 1 and (P[:, 0] == cuts[3]).sum() == 1
+    hs, rs, everything = open_tiles(E, ref, P, ranges)
+    tiles = [h.registration_terms_tile(r, max_dist=KNOWN["max_dist"]) for h, r in zip(hs, rs)]
+    print("owned %r (want %r) pairs %r" % ([t[1]["owned"] for t in tiles], want_owned, [t[0]["pairs"] for t in tiles]))
+    # half-open at the cut: the point at exactly cut(1) is in range 1's count and not in range 0's, the one at cut(3) in range 3's
+    assert [t[1]["owned"] for t in tiles] == want_owned and sum(want_owned) == len(P)
+    empty = tiles[2][0]
+    assert empty["pairs"] == 0 and not np.any(empty["A"]) and not np.any(empty["b"]) and empty["E"] == 0 and tiles[2][1]["owned"] == 0
+    assert tiles[0][0]["pairs"] == 3
+    (T, rows, st), (wT, wrows, wst) = whole_of(E, "seams", ref, P, **KNOWN)
+    row, part = E.merge_registration_terms(tiles)
+    rows_equal([row], [dict(rows[0], locked=ALL_LOCKED, step2=NAN)])
+    assert part["owned"] == st["indexed"] == len(P)
+    gT, grows, gst = E.register_tiles(hs, rs, **KNOWN)
+    print("steps %d (whole %d)" % (gst["steps"], st["steps"]))
+    assert gst["steps"] >= 1
+    rows_equal(grows, rows); stats_equal(gst, st); assert same(gT, T)
+    rows_equal(grows, wrows); stats_equal(gst, wst)
+    for e in everything:
+        e.close()
+
+
+@pytest.mark.gpu
+def test_tiles_beyond_the_grid_cap(engine_mod):
+    """large_clouds in two ranges, the first all slices but the last: its tile visits more positions than the capped grid of
+    k_regt_terms holds threads, so the grid-stride loop takes a second trip; terms at large_T0 and the chain of two steps"""
+    E = engine_mod
+    ref, scan, notes = large_clouds()
+    S, cuts = cuts_of(E, scan)
+    ranges = [(0, S - 1), (S - 1, S)]
+    hs, rs, everything = open_tiles(E, ref, scan, ranges)
+    r_whole, s_whole = rs[0], handle(E, scan)
+    whole_row, whole_st = s_whole.registration_terms(r_whole, T=large_T0(), max_dist=LARGE["max_dist"])
+    tiles = [h.registration_terms_tile(r, T=large_T0(), max_dist=LARGE["max_dist"]) for h, r in zip(hs, rs)]
+    cap = past_the_grid_cap(tiles[0][1]["evaluated"])
+    print("evaluated %r owned %r pairs %r (whole %d), cap %d" % ([t[1]["evaluated"] for t in tiles], [t[1]["owned"] for t in tiles],
+                                                               [t[0]["pairs"] for t in tiles], whole_row["pairs"], cap))
+    assert tiles[0][1]["owned"] > cap and tiles[1][1]["owned"] > 0 and tiles[0][0]["pairs"] >= 300
+    assert [t[1]["owned"] for t in tiles] == [int(owned_rows(scan, cuts, r).sum()) for r in ranges]
+    row, part = E.merge_registration_terms(tiles, large_T0())
+    rows_equal([row], [whole_row])
+    assert part["owned"] == whole_st["indexed"] == len(scan) - 2 and part["shift"] == whole_st["shift"] == 38
+    T, rows, st = s_whole.register(r_whole, T0=large_T0(), **LARGE)
+    gT, grows, gst = E.register_tiles(hs, rs, T0=large_T0(), **LARGE)
+    assert st["steps"] == 2
+    rows_equal(grows, rows); stats_equal(gst, st); assert same(gT, T)
+    for e in everything + [s_whole]:
+        e.close()
+
+
+@pytest.mark.gpu
+def test_registration_tile_refusals(engine_mod):
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    S, _ = cuts_of(E, moved)
+    rng = ranges3(S)
+    h, r = handle(E, moved, rng[1]), handle(E, ref)
+    thin = handle(E, ref, (1, 3), range_margin=THIN_MARGIN)
+    # a reference range whose margin does not cover the reach of the queries moved by 5 mm: CAPACITY naming range_margin; the
+    # same margin at the identity, and the same transform against the whole reference, succeed
+    ok0 = h.registration_terms_tile(thin, max_dist=KNOWN["max_dist"])
+    whole5 = h.registration_terms_tile(r, T=SHIFT_5MM, max_dist=KNOWN["max_dist"])
+    assert same(ok0[0], h.registration_terms_tile(r, max_dist=KNOWN["max_dist"])[0]) and whole5[0]["pairs"] >= 6
+    with pytest.raises(E.PPPError) as ex:
+        h.registration_terms_tile(thin, T=SHIFT_5MM, max_dist=KNOWN["max_dist"])
+    assert ex.value.code == E.ERR_CAPACITY and "range_margin" in str(ex.value)
+    with pytest.raises(E.PPPError) as ex:
+        E.register_tiles([h], [thin], T0=SHIFT_5MM, **KNOWN)
+    assert ex.value.code == E.ERR_CAPACITY and "range_margin" in str(ex.value) and "tile 0" in str(ex.value)
+    hv, tv = (ctypes.c_void_p * 1)(h.h), (ctypes.c_void_p * 1)(thin.h)
+    rp = E.RegistrationParams(KNOWN["max_dist"], KNOWN["iterations"], KNOWN["min_step"], KNOWN["lock_eps"])
+    t5 = np.ascontiguousarray(SHIFT_5MM.reshape(12))
+    dp = ctypes.POINTER(ctypes.c_double)
+    raw = E.RegisterTilesStats()
+    L = E.lib()
+    assert L.ppp_register_tiles(hv, tv, 1, ctypes.byref(rp), t5.ctypes.data_as(dp), None, 0, ctypes.byref(raw)) == E.ERR_CAPACITY and raw.failed_tile == 0
+
+    def refused(hh, other, code, T=None, **k):
+        p = dict(KNOWN, **k)
+        with pytest.raises(E.PPPError) as ex:
+            hh.registration_terms_tile(other, T=T, max_dist=p["max_dist"], lock_eps=p["lock_eps"])
+        assert ex.value.code == code, (k, ex.value)
+        with pytest.raises(E.PPPError) as ex:
+            E.register_tiles([hh], [other], T0=T, **p)
+        assert ex.value.code == code, (k, ex.value)
+
+    # B.72's, for a tile
+    for bad in (dict(max_dist=0.0), dict(max_dist=-1.0), dict(max_dist=NAN), dict(max_dist=INF), dict(max_dist=1e30), dict(max_dist=1e9),
+                dict(lock_eps=0.0), dict(lock_eps=1.0), dict(lock_eps=NAN)):
+        refused(h, r, E.ERR_ARG, **bad)
+    for bad in (dict(iterations=0), dict(iterations=65), dict(iterations=-3), dict(min_step=-1.0), dict(min_step=NAN), dict(min_step=INF)):
+        with pytest.raises(E.PPPError) as ex:
+            E.register_tiles([h], [r], **dict(KNOWN, **bad))
+        assert ex.value.code == E.ERR_ARG, bad
+    for v in (NAN, INF):
+        Tb = IDENTITY.copy(); Tb[0, 3] = v
+        refused(h, r, E.ERR_ARG, T=Tb)
+    empty = E.Engine(0, **KW0)
+    refused(h, empty, E.ERR_ARG)
+    refused(empty, r, E.ERR_ARG)
+    # a part handle on either side
+    f = finite_rows(moved)
+    mn, mx = moved[f].min(axis=0), moved[f].max(axis=0)
+    p = E.Engine(0, slice_begin=rng[1][0], slice_end=rng[1][1], **KW0)
+    lo, hi, _ = p.range_interval(mn[0], mx[0])
+    keep = np.nonzero(f & (moved[:, 0] >= lo) & (moved[:, 0] <= hi))[0]
+    p.set_cloud_part(moved[keep], keep, mn, mx, int(f.sum()), lo, hi)
+    refused(p, r, E.ERR_UNSUPPORTED)
+    refused(h, p, E.ERR_UNSUPPORTED)
+    # NULL arguments
+    row, part = E.RegistrationRow(), E.RegistrationPart()
+    rv = (ctypes.c_void_p * 1)(r.h)
+    assert L.ppp_get_registration_terms_tile(None, r.h, ctypes.byref(rp), None, ctypes.byref(row), ctypes.byref(part)) == E.ERR_ARG
+    assert L.ppp_get_registration_terms_tile(h.h, None, ctypes.byref(rp), None, ctypes.byref(row), ctypes.byref(part)) == E.ERR_ARG
+    assert L.ppp_get_registration_terms_tile(h.h, r.h, None, None, ctypes.byref(row), ctypes.byref(part)) == E.ERR_ARG
+    assert L.ppp_get_registration_terms_tile(h.h, r.h, ctypes.byref(rp), None, None, None) == 0               # row and part are optional
+    assert L.ppp_register_tiles(None, rv, 1, ctypes.byref(rp), None, None, 0, ctypes.byref(raw)) == E.ERR_ARG
+    assert L.ppp_register_tiles(hv, None, 1, ctypes.byref(rp), None, None, 0, ctypes.byref(raw)) == E.ERR_ARG
+    assert L.ppp_register_tiles(hv, rv, 0, ctypes.byref(rp), None, None, 0, ctypes.byref(raw)) == E.ERR_ARG
+    assert L.ppp_register_tiles(hv, rv, 1, None, None, None, 0, ctypes.byref(raw)) == E.ERR_ARG
+    assert L.ppp_register_tiles(hv, rv, 1, ctypes.byref(rp), None, None, 3, ctypes.byref(raw)) == E.ERR_ARG   # rows NULL with row_cap > 0
+    none = (ctypes.c_void_p * 1)(None)
+    assert L.ppp_register_tiles(hv, none, 1, ctypes.byref(rp), None, None, 0, ctypes.byref(raw)) == E.ERR_ARG
+    two = (ctypes.c_void_p * 2)(h.h, h.h)
+    assert L.ppp_register_tiles(two, (ctypes.c_void_p * 2)(r.h, r.h), 2, ctypes.byref(rp), None, None, 0, ctypes.byref(raw)) == E.ERR_ARG   # a handle twice
+    # tiles whose ranges overlap: the merge refuses
+    over = handle(E, moved, (0, 2))
+    with pytest.raises(E.PPPError) as ex:
+        E.register_tiles([over, h], r, **KNOWN)
+    assert ex.value.code == E.ERR_ARG
+    # h == ref is allowed: a cloud against itself is a stationary point
+    sT, srows, sst = E.register_tiles([r], [r], **KNOWN)
+    assert sst["steps"] == 0 and sst["converged"] == 1 and same(sT, IDENTITY) and not np.any(srows[0]["b"]) and srows[0]["E"] == 0
+    # every refusal left the handles usable and the answer unchanged
+    assert same(h.registration_terms_tile(thin, max_dist=KNOWN["max_dist"]), ok0)
+    for e in (h, r, thin, empty, p, over):
+        e.close()
+
+
+@pytest.mark.gpu
+def test_tile_and_reference_on_different_devices_are_refused(engine_mod):
+    if device_count() < 2:
+        pytest.skip("needs two GPUs in one process: this machine shows %d" % device_count())
+    E = engine_mod
+    ref, scan, moved, Tm = known_clouds()
+    S, _ = cuts_of(E, moved)
+    h = handle(E, moved, ranges3(S)[1])
+    d1 = E.Engine(1, **KW0)
+    d1.set_cloud(ref)
+    with pytest.raises(E.PPPError) as ex:
+        h.registration_terms_tile(d1, max_dist=KNOWN["max_dist"])
+    assert ex.value.code == E.ERR_ARG
+    with pytest.raises(E.PPPError) as ex:
+        E.register_tiles([h], [d1], **KNOWN)
+    assert ex.value.code == E.ERR_ARG
+    h.close(); d1.close()
+
+
+@pytest.mark.gpu
+def test_same_bits_on_fresh_handles_and_nothing_stored_is_touched(engine_mod):
+    """small_40k walk 1 with a bump against itself: a range handle that ran a pass and answered contact queries gives the terms a
+    fresh range handle gives; its path contacts, its path coverage and its deviation tile are as before; a
+    whole-cloud handle on the window path owns everything, equals ppp_get_registration_terms and stays on the window path; the
+    reference keeps its pass too"""
+    E = engine_mod
+    pts, cfg = synth.make_config("small_40k")
+    scan, _ = bumped(pts)
+    kw = dict(tool_radius=cfg["tool_radius"], walk=1)
+    dp = dict(max_dist=3.0, smooth_radius=4.0, allowance=0.05, gain=1.0)
+    r = E.Engine(0, **kw)
+    r.set_cloud(pts)
+    Sr = r.gen_path(); r.get_path()
+    rwp = r.waypoints().copy()
+    w = E.Engine(0, **kw)
+    w.set_cloud(scan)
+    S = w.gen_path(); w.get_path()
+    assert w.fast_path()
+    wwp = w.waypoints().copy()
+    whole_row, whole_st = w.registration_terms(r, max_dist=3.0)
+    whole_dev = w.deviation(r, **dp)
+    one_row, one_part = w.registration_terms_tile(r, max_dist=3.0)
+    rows_equal([one_row], [whole_row])
+    assert one_part["owned"] == whole_st["indexed"] and whole_row["pairs"] >= 6
+    assert w.fast_path() and same(w.waypoints(), wwp) and r.fast_path() and same(r.waypoints(), rwp)
+    assert same(w.deviation(r, **dp), whole_dev)
+    ranges = slice_ranges(S, 4)
+    b, e = ranges[1]
+    a = E.Engine(0, slice_begin=b, slice_end=e, range_margin=RANGE_MARGIN, **kw)
+    a.set_cloud(scan)
+    a.gen_path(); a.get_path()
+    fast, slices, contacts, covered = a.fast_path(), a.num_slices(), a.path_contacts(), a.path_coverage()
+    dev_before = a.deviation_tile(r, 7.0, **dp)
+    first = a.registration_terms_tile(r, max_dist=3.0)
+    again = a.registration_terms_tile(r, max_dist=3.0)
+    fresh = E.Engine(0, slice_begin=b, slice_end=e, range_margin=RANGE_MARGIN, **kw)
+    fresh.set_cloud(scan)
+    other = fresh.registration_terms_tile(r, max_dist=3.0)
+    assert same(first, again) and same(first, other) and first[1]["owned"] > 0 and first[0]["pairs"] >= 6
+    assert a.fast_path() == fast and a.num_slices() == slices and same(a.path_contacts(), contacts) and same(a.path_coverage(), covered)
+    assert same(a.deviation_tile(r, 7.0, **dp), dev_before)
+    assert same(r.waypoints(), rwp) and (Sr, S) == (r.num_slices(), w.num_slices())
+    # the four ranges add up to the whole, on handles that hold passes
+    others = [E.Engine(0, slice_begin=lo, slice_end=hi, range_margin=RANGE_MARGIN, **kw) for lo, hi in ranges if (lo, hi) != (b, e)]
+    for o in others:
+        o.set_cloud(scan)
+    tiles = [first] + [o.registration_terms_tile(r, max_dist=3.0) for o in others]
+    rows_equal([E.merge_registration_terms(tiles)[0]], [whole_row])
+    for h in [r, w, a, fresh] + others:
+        h.close()
