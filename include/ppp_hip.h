@@ -925,6 +925,43 @@ int ppp_registration_step(const ppp_registration_row *row, const ppp_registratio
                           const double *T12, double *T12_out, int *locked, double *step2);
 int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp,
                        const double *T0_12, ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats);
+/* ---- trimmed registration of a scan held as slice-range tiles ----
+   Every quantity of ppp_register_trimmed's evaluation is an integer histogram or an integer sum: pairs and keys are a point's
+   own, the cut is a rank statistic of the union of the keys, the 29 words add.  So the tiles merge exactly, at the price of
+   four host waits per evaluation.
+   ppp_trim_select (B.95; host only): the device's selection rule on a histogram of `bins` counts: *bin = the first bin whose
+   running count reaches rank (1-based), *rank_in_bin = rank minus the counts below that bin (>= 1).  rank 0 or a rank above
+   the total finds nothing: *bin = 0 and *rank_in_bin = 0.  PPP_ERR_ARG: a NULL argument.
+   ppp_trim_rank (B.96; host only): k = (size_t)ceil(keep * (double)paired), one double product and one ceil, clamped to
+   [1, paired]; 0 when paired == 0.
+   ppp_register_trimmed_tiles (B.97-B.100): ppp_register_trimmed's loop over tiles.  hs, refs and count are
+   ppp_register_tiles's, with its rules; each reference's index and normal field are built once, before the loop.  An
+   evaluation is four passes, each enqueued on every tile's own stream with one small asynchronous copy back per tile and one
+   wait per tile: (1) the search, which stores an owned point's partner and key and counts the keys' top 11 bits; the host
+   adds the tiles' histograms bin by bin, takes paired = their total and k = ppp_trim_rank(keep, paired) -- never a tile's own
+   count --, selects the bin (ppp_trim_select) and sends every tile the merged prefix; (2), (3) the middle 11 and the low 10
+   bits of the stored keys that carry the merged prefix, merged and selected likewise, which gives tau; (4) the 29 words over
+   key <= tau, merged as ppp_merge_registration_terms does.  The histograms come back once each: 8 KB, 8 KB, 4 KB.  paired == 0
+   ends the evaluation behind pass (1): trim_d2 = 0x7fc00000, kept 0.  The step is ppp_registration_step's.  For ranges that
+   tile the walk T, every row (the 29 words, pairs = kept, locked, step2, paired, trim_d2), every field of stats->reg and each
+   owned point's status / d2 are the bits of ppp_register_trimmed on whole-cloud handles with the same parameters and T0.
+     status, d2, owned   arrays of `count` per-tile pointers; the array or any entry may be NULL.  Each holds the first
+                         min(cap, n) entries by cloud index of tile i's maps of the LAST evaluation: an indexed point the tile
+                         owns has owned 1 and its status / d2 as ppp_register_trimmed gives them; every other entry has
+                         owned 0, PPP_TRIM_DROPPED and NaN (0x7fc00000).  The owned maps of ranges that tile the walk
+                         partition the indexed points; a point no tile owns is not finite.
+   A tile's error ends the loop and is returned (the text on that tile's handle), with its index in stats->failed_tile (-1
+   otherwise).  PPP_ERR_ARG: ppp_register_tiles's refusals; tp NULL; keep NaN, <= 0 or > 1.  PPP_ERR_CAPACITY (raise
+   range_margin): a moved owned query whose reach leaves a slice-range reference's index, by ppp_get_registration_terms_tile's
+   test; such a call is never answered with fewer pairs.  PPP_ERR_UNSUPPORTED: a part handle.  Neither handle's cloud, plan
+   or stored result changes; nothing is kept. */
+int    ppp_trim_select(const unsigned int *hist, size_t bins, size_t rank, unsigned int *bin, size_t *rank_in_bin);
+size_t ppp_trim_rank(double keep, size_t paired);
+int    ppp_register_trimmed_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count,
+                                  const ppp_trimmed_registration_params *tp, const double *T0_12,
+                                  ppp_trimmed_registration_row *rows, size_t row_cap,
+                                  unsigned char *const *status, float *const *d2, unsigned char *const *owned, size_t cap,
+                                  ppp_register_tiles_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

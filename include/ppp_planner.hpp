@@ -910,5 +910,43 @@ inline bool register_tiles(std::vector<Planner *> &tiles, std::vector<Planner *>
     return true;
 }
 
+/* register_trimmed_to() for a scan held as slice-range planners (ppp_register_trimmed_tiles): tiles and refs as
+   register_tiles() takes them.  st.reg and rows are register_trimmed_to()'s, bit for bit, for ranges that tile the walk; an
+   evaluation is four host round trips.  status, d2 and owned, when asked for, receive one map per tile by cloud index: an
+   indexed point the tile owns has owned 1 and its PPP_TRIM_* status and d2, every other entry owned 0, PPP_TRIM_DROPPED and NaN */
+inline bool register_trimmed_tiles(std::vector<Planner *> &tiles, std::vector<Planner *> &refs, ppp_register_tiles_stats &st,
+                                   const ppp_trimmed_registration_params &tp, const double *T0 = nullptr,
+                                   std::vector<ppp_trimmed_registration_row> *rows = nullptr, std::vector<std::vector<unsigned char>> *status = nullptr,
+                                   std::vector<std::vector<float>> *d2 = nullptr, std::vector<std::vector<unsigned char>> *owned = nullptr)
+{
+    if (tiles.empty() || refs.size() != tiles.size()) { std::fprintf(stderr, "ppp error %d: register_trimmed_tiles: one reference per tile\n", PPP_ERR_ARG); return false; }
+    std::vector<ppp_handle> hs, rs;
+    for (size_t i = 0; i < tiles.size(); ++i) { hs.push_back(tiles[i] ? tiles[i]->handle() : nullptr); rs.push_back(refs[i] ? refs[i]->handle() : nullptr); }
+    if (rows) rows->assign((size_t)(tp.icp.iterations > 0 ? tp.icp.iterations : 0) + 1, ppp_trimmed_registration_row{});
+    size_t n = 0;
+    if ((status || d2 || owned) && hs[0]) {
+        const int rc = ppp_num_points(hs[0], &n);
+        if (rc != PPP_OK) { std::fprintf(stderr, "ppp error %d: tile 0: %s\n", rc, ppp_last_error(hs[0])); return false; }
+    }
+    std::vector<unsigned char *> sp, op;
+    std::vector<float *> dp;
+    if (status) { status->assign(hs.size(), std::vector<unsigned char>(n, PPP_TRIM_DROPPED)); for (auto &m : *status) sp.push_back(m.data()); }
+    if (d2) { d2->assign(hs.size(), std::vector<float>(n, 0.f)); for (auto &m : *d2) dp.push_back(m.data()); }
+    if (owned) { owned->assign(hs.size(), std::vector<unsigned char>(n, 0)); for (auto &m : *owned) op.push_back(m.data()); }
+    const int rc = ppp_register_trimmed_tiles(hs.data(), rs.data(), hs.size(), &tp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0,
+                                              status ? sp.data() : nullptr, d2 ? dp.data() : nullptr, owned ? op.data() : nullptr, n, &st);
+    if (rc != PPP_OK) {
+        if (rows) rows->clear();
+        if (status) status->clear();
+        if (d2) d2->clear();
+        if (owned) owned->clear();
+        const ppp_handle at = hs[st.failed_tile >= 0 ? (size_t)st.failed_tile : 0];
+        std::fprintf(stderr, "ppp error %d: tile %d: %s\n", rc, st.failed_tile, at ? ppp_last_error(at) : "no handle");
+        return false;
+    }
+    if (rows) rows->resize(std::min(rows->size(), (size_t)st.reg.steps + 1));
+    return true;
+}
+
 } // namespace ppp
 #endif

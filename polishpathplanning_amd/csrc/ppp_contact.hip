@@ -18,6 +18,7 @@
 #include "ppp_registration.h"
 #include "ppp_trimmed.h"
 #include "ppp_registration_tile.h"
+#include "ppp_trimmed_tile.h"
 #include <cstring>
 
 /* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
@@ -2043,9 +2044,36 @@ int ppp_registration_step(const ppp_registration_row *row, const ppp_registratio
     return rc;
 }
 
-/* The tiled loop (B.93): ppp_register's chain with the host in the place of k_reg_step -- reg_step_body's control flow, word for
-   word: `stop` behind a step below min_step makes the next evaluation the last, an evaluation no step is taken from ends the
-   loop, and the evaluation behind the last of `iterations` steps is a row without a step. */
+/* the tiles' rows of one evaluation at T as the whole cloud's (B.91), with the checks the loops make of it */
+static int regt_merged(ppp_handle h0, const std::vector<ppp_registration_row> &part_rows, const std::vector<ppp_registration_part> &parts, const double *T,
+                       ppp_registration_row &rw, ppp_registration_part &whole)
+{
+    const int rc = ppp_merge_registration_terms(part_rows.data(), parts.data(), parts.size(), T, &rw, &whole);
+    if (rc) return fail(h0, rc, "registration tiles: the tiles' ranges overlap, or the tiles do not hold one scan against one reference");
+    if (rw.pairs > whole.owned) return fail(h0, PPP_ERR_HIP, "registration tiles: sums corrupt");
+    return PPP_OK;
+}
+
+/* ppp_register's statistics from a tiled loop's rows */
+static ppp_registration_stats regt_stats(const std::vector<ppp_registration_row> &R, const IcpCtl &C, const ppp_registration_part &whole)
+{
+    const size_t last = (size_t)C.steps;
+    ppp_registration_stats st = {};
+    st.n = whole.n; st.indexed = whole.owned;
+    st.steps = C.steps; st.converged = C.converged; st.locked = C.locked; st.shift = whole.shift;
+    for (int d = 0; d < 3; ++d) st.centre[d] = whole.centre[d];
+    st.length = whole.length;
+    memcpy(st.T, R[last].T, sizeof(st.T));
+    auto rms = [&](const ppp_registration_row &r) {
+        return r.pairs ? std::sqrt(std::ldexp((double)r.E, -whole.shift) / (double)r.pairs) : (double)NAN;
+    };
+    st.pairs_before = R[0].pairs; st.rms_before = rms(R[0]);
+    st.pairs_after = R[last].pairs; st.rms_after = rms(R[last]);
+    return st;
+}
+
+/* The tiled loop (B.93): ppp_register's chain with the host in the place of k_reg_step (regt_loop); an evaluation is one
+   k_regt_terms per tile and one wait per tile. */
 int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp, const double *T0_12,
                        ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats)
 {
@@ -2075,52 +2103,283 @@ int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t coun
     std::vector<ppp_registration_part> parts(count);
     ppp_registration_part whole = {};
     IcpCtl C = {};
-    for (int k = 0; k <= P.iterations; ++k) {
-        for (size_t i = 0; i < count; ++i) { rc = regt_enqueue(tiles[i], T); if (rc) return failed(i, rc); }
+    rc = regt_loop(P, F, T, R, C, whole, [&](int, ppp_registration_row &rw) {
+        for (size_t i = 0; i < count; ++i) { int e = regt_enqueue(tiles[i], T); if (e) return failed(i, e); }
         int first_rc = PPP_OK;
         size_t first_at = 0;
         for (size_t i = 0; i < count; ++i) { /* every tile is waited for, whatever an earlier one answered */
-            rc = regt_collect(tiles[i], T, &part_rows[i]);
-            if (rc && !first_rc) { first_rc = rc; first_at = i; }
+            const int e = regt_collect(tiles[i], T, &part_rows[i]);
+            if (e && !first_rc) { first_rc = e; first_at = i; }
             parts[i] = tiles[i].part;
         }
         if (first_rc) return failed(first_at, first_rc);
-        ppp_registration_row rw;
-        rc = ppp_merge_registration_terms(part_rows.data(), parts.data(), count, T, &rw, &whole);
-        if (rc) return fail(h0, rc, "registration tiles: the tiles' ranges overlap, or the tiles do not hold one scan against one reference");
-        if (rw.pairs > whole.owned) return fail(h0, PPP_ERR_HIP, "registration tiles: sums corrupt");
-        if (k == P.iterations) { R.push_back(rw); break; } /* the evaluation behind the last step */
-        double Tn[12];
-        int mask = ICP_ALL_LOCKED;
-        double step2 = icp_nan();
-        if (!C.stop) {
-            const int sc = regt_step(rw, whole.centre, whole.length, F.lock_eps, T, Tn, &mask, &step2);
-            if (sc == PPP_STEP_STATIONARY) C.converged = 1;
-        }
-        if (mask == ICP_ALL_LOCKED) { R.push_back(rw); C.done = 1; break; }
-        rw.locked = mask; rw.step2 = step2;
-        R.push_back(rw);
-        C.steps += 1; C.locked |= mask;
-        if (step2 < F.min_step2) { C.stop = 1; C.converged = 1; }
-        memcpy(T, Tn, sizeof(T));
-    }
-    const size_t last = (size_t)C.steps;
-    if (stats) {
-        ppp_registration_stats st = {};
-        st.n = whole.n; st.indexed = whole.owned;
-        st.steps = C.steps; st.converged = C.converged; st.locked = C.locked; st.shift = whole.shift;
-        for (int d = 0; d < 3; ++d) st.centre[d] = whole.centre[d];
-        st.length = whole.length;
-        memcpy(st.T, R[last].T, sizeof(st.T));
-        auto rms = [&](const ppp_registration_row &r) {
-            return r.pairs ? std::sqrt(std::ldexp((double)r.E, -whole.shift) / (double)r.pairs) : (double)NAN;
-        };
-        st.pairs_before = R[0].pairs; st.rms_before = rms(R[0]);
-        st.pairs_after = R[last].pairs; st.rms_after = rms(R[last]);
-        stats->reg = st;
-    }
-    const size_t k = std::min(row_cap, last + 1);
+        return regt_merged(h0, part_rows, parts, T, rw, whole);
+    });
+    if (rc) return rc;
+    if (stats) stats->reg = regt_stats(R, C, whole);
+    const size_t k = std::min(row_cap, (size_t)C.steps + 1);
     if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    return PPP_OK;
+}
+
+/* ---- trimmed registration of a scan held as slice-range tiles ---- */
+
+int ppp_trim_select(const unsigned int *hist, size_t bins, size_t rank, unsigned int *bin, size_t *rank_in_bin)
+{
+    if (!hist || !bin || !rank_in_bin) return PPP_ERR_ARG;
+    *bin = 0; *rank_in_bin = 0;
+    size_t below = 0;
+    for (size_t b = 0; rank && b < bins; ++b) {
+        if (rank <= below + hist[b]) { *bin = (unsigned)b; *rank_in_bin = rank - below; break; } /* (rank > below: no earlier bin reached it) */
+        below += hist[b];
+    }
+    return PPP_OK;
+}
+
+size_t ppp_trim_rank(double keep, size_t paired) { return trim_rank(keep, paired); }
+
+/* a tile's pinned memory behind ppp_register_tiles' (the words back, T out): one word going out -- the merged prefix, then tau --
+   and the block coming back: the two words and a histogram of at most TRIM_B0 bins */
+static unsigned *trimt_pinned_word(const RegtTile &t) { return reinterpret_cast<unsigned *>(t.h->registration.tpin.p + REGT_WORDS + 12); }
+static unsigned *trimt_pinned_hist(const RegtTile &t) { return reinterpret_cast<unsigned *>(t.h->registration.tpin.p + REGT_WORDS + 13); }
+static const size_t TRIMT_PIN_WORDS = REGT_WORDS + 13 + (TRIMT_HEAD + TRIM_B0) / 2;
+static int trimt_positions(const RegtTile &t) { return t.pos1 - t.pos0; }
+
+/* the buffers of a tile behind regt_prepare: partner and key per position, the two words and the three histograms, the word
+   the host writes, and where the caller wants a map of this tile, status | owned and d2 by cloud index */
+static int trimt_prepare(RegtTile &t, bool maps)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t np = std::max<size_t>((size_t)trimt_positions(t), 1), N1 = std::max<size_t>(h->n, 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, G.partner.ensure(np)); HIPCHK(h, G.key.ensure(np)); HIPCHK(h, G.hist.ensure(TRIMT_HEAD + TRIM_WORDS)); HIPCHK(h, G.cuts.ensure(2));
+    HIPCHK(h, G.tpin.ensure(TRIMT_PIN_WORDS));
+    if (maps) { HIPCHK(h, G.tstatus.ensure(2 * N1)); HIPCHK(h, G.td2.ensure(N1)); }
+    return PPP_OK;
+}
+
+/* the first pass of an evaluation at T, enqueued on the tile's stream: T to the device, the histograms and the words cleared,
+   k_trimt_pair, the two words and the top digits' histogram back to pinned memory.  Nobody waits here. */
+static int trimt_enqueue_pair(RegtTile &t, const double *T)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.hist.p, 0, (TRIMT_HEAD + TRIM_WORDS) * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_pair", k_trimt_pair, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, t.own, contact_index(t.ref), t.nref, t.rb0, t.rb1, t.need,
+               G.tframe.p, G.T.p, G.partner.p, G.key.p, G.hist.p);
+    HIPCHK(h, hipMemcpyAsync(trimt_pinned_hist(t), G.hist.p, (TRIMT_HEAD + TRIM_B0) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* pass 1 or 2: the merged prefix to the device, k_trimt_narrow over the stored keys, that digit's histogram back */
+static int trimt_enqueue_narrow(RegtTile &t, int pass, unsigned prefix)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned *next = G.hist.p + TRIMT_HEAD + (pass == 1 ? TRIM_B0 : TRIM_B0 + TRIM_B1);
+    *trimt_pinned_word(t) = prefix;
+    HIPCHK(h, hipMemcpyAsync(G.cuts.p, trimt_pinned_word(t), sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (t.pos1 > t.pos0) {
+        if (pass == 1) LAUNCH(h, "k_trimt_narrow<1>", k_trimt_narrow<1>, t.grid, TRIM_T, 0, G.key.p, trimt_positions(t), G.cuts.p, next);
+        else LAUNCH(h, "k_trimt_narrow<2>", k_trimt_narrow<2>, t.grid, TRIM_T, 0, G.key.p, trimt_positions(t), G.cuts.p, next);
+    }
+    HIPCHK(h, hipMemcpyAsync(trimt_pinned_hist(t), next, (pass == 1 ? TRIM_B1 : TRIM_B2) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the sums: tau to the device, k_trimt_terms, the 29 words back */
+static int trimt_enqueue_terms(RegtTile &t, unsigned tau)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    *trimt_pinned_word(t) = tau;
+    HIPCHK(h, hipMemcpyAsync(G.cuts.p, trimt_pinned_word(t), sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_terms", k_trimt_terms, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, contact_index(t.ref), G.tframe.p, G.T.p, G.partner.p,
+               G.key.p, G.cuts.p, G.acc.p);
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, ICP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+static int trimt_wait(RegtTile &t)
+{
+    HIPCHK(t.h, hipSetDevice(t.h->device));
+    HIPCHK(t.h, hipStreamSynchronize(t.h->stream));
+    return PPP_OK;
+}
+
+/* behind the loop: the tile's maps filled with DROPPED / NaN / 0, then k_trimt_scatter over the keys the last evaluation left */
+static int trimt_enqueue_scatter(RegtTile &t, unsigned tau, bool none)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t N1 = std::max<size_t>(h->n, 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemsetAsync(G.tstatus.p, PPP_TRIM_DROPPED, N1, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.tstatus.p + N1, 0, N1, h->stream));
+    HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(G.td2.p), (int)TRIM_NAN, N1, h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_scatter", k_trimt_scatter, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, G.key.p, tau, none ? 1 : 0, (int)N1, G.tstatus.p,
+               G.td2.p, G.tstatus.p + N1);
+    return PPP_OK;
+}
+
+/* the first min(cap, n) entries of the maps the caller gave for this tile (each copy waits for the tile's stream) */
+static int trimt_copy_maps(RegtTile &t, unsigned char *status, float *d2, unsigned char *owned, size_t cap)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t N1 = std::max<size_t>(h->n, 1), m = std::min(cap, h->n);
+    if (!m || !(status || d2 || owned)) return PPP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (status) HIPCHK(h, copy_sync(h, status, G.tstatus.p, m, hipMemcpyDeviceToHost));
+    if (d2) HIPCHK(h, copy_sync(h, d2, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
+    if (owned) HIPCHK(h, copy_sync(h, owned, G.tstatus.p + N1, m, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The tiled trimmed loop (B.97-B.99): regt_loop, an evaluation being four passes over the tiles -- k_trimt_pair,
+   k_trimt_narrow<1>, k_trimt_narrow<2>, k_trimt_terms --, each enqueued on every tile's stream and waited for tile by tile; between
+   them the host adds the tiles' histograms, selects the digit on the sum (ppp_trim_select) and sends the next pass the merged
+   prefix, or tau.  An evaluation that finds no pair in any tile ends behind its first pass. */
+int ppp_register_trimmed_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_trimmed_registration_params *tp, const double *T0_12,
+                               ppp_trimmed_registration_row *rows, size_t row_cap, unsigned char *const *status, float *const *d2,
+                               unsigned char *const *owned, size_t cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !refs || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    if (!tp) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: no parameters");
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, &tp->icp, T0_12, F, T);
+    if (rc) return rc;
+    const double keep = tp->keep;
+    if (!(keep > 0.0 && keep <= 1.0)) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: keep must be in (0, 1]");
+    if (!rows && row_cap) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: rows is NULL with row_cap > 0");
+    for (size_t i = 0; i < count; ++i) {
+        if (!hs[i] || !refs[i]) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: a NULL handle");
+        for (size_t k = 0; k < i; ++k) if (hs[k] == hs[i]) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: a scan handle stands in two slots");
+    }
+    const ppp_registration_params P = tp->icp;
+    auto failed = [&](size_t i, int code) { if (stats) stats->failed_tile = (int)i; return code; };
+    auto map_of = [&](auto *const *maps, size_t i) { return maps ? maps[i] : nullptr; };
+    std::vector<RegtTile> tiles(count);
+    for (size_t i = 0; i < count; ++i) {
+        tiles[i].h = hs[i]; tiles[i].ref = refs[i];
+        bool first = true; /* the reference's index and normal field: once per reference handle */
+        for (size_t k = 0; k < i; ++k) first = first && refs[k] != refs[i];
+        rc = regt_prepare(tiles[i], P, F, first);
+        if (!rc) rc = trimt_prepare(tiles[i], map_of(status, i) || map_of(d2, i) || map_of(owned, i));
+        if (rc) return failed(i, rc);
+    }
+    /* every tile is waited for, whatever an earlier one answered; the first error is the call's */
+    auto wait_all = [&]() {
+        int first_rc = PPP_OK;
+        for (size_t i = 0; i < count; ++i) {
+            const int e = trimt_wait(tiles[i]);
+            if (e && !first_rc) first_rc = failed(i, e);
+        }
+        return first_rc;
+    };
+    /* the tiles' histograms of `bins` bins, behind the wait, added bin by bin: a bin's sum is at most the scan's points */
+    std::vector<unsigned> H(TRIM_B0);
+    auto merge_hist = [&](size_t skip, size_t bins) {
+        std::fill(H.begin(), H.end(), 0u);
+        for (size_t i = 0; i < count; ++i) {
+            const unsigned *w = trimt_pinned_hist(tiles[i]) + skip;
+            for (size_t b = 0; b < bins; ++b) H[b] += w[b];
+        }
+    };
+    struct Cut { size_t paired; unsigned tau; };
+    std::vector<Cut> cuts;
+    std::vector<ppp_registration_row> part_rows(count), R;
+    std::vector<ppp_registration_part> parts(count);
+    ppp_registration_part whole = {};
+    IcpCtl C = {};
+    rc = regt_loop(P, F, T, R, C, whole, [&](int, ppp_registration_row &rw) {
+        for (size_t i = 0; i < count; ++i) { const int e = trimt_enqueue_pair(tiles[i], T); if (e) return failed(i, e); }
+        int e = wait_all();
+        if (e) return e;
+        size_t paired = 0;
+        for (size_t i = 0; i < count; ++i) {
+            RegtTile &t = tiles[i];
+            const unsigned *w = trimt_pinned_hist(t);
+            if (w[TRIMT_REFUSED])
+                return failed(i, fail(t.h, PPP_ERR_CAPACITY, "trimmed registration tiles: " + std::to_string(w[TRIMT_REFUSED]) + " moved queries reach beyond the "
+                                      "reference's indexed slice range (max_dist + normal_radius around the moved point): raise range_margin of the "
+                                      "reference's handle"));
+            size_t mine = 0;
+            for (size_t b = 0; b < TRIM_B0; ++b) mine += w[TRIMT_HEAD + b];
+            if (w[TRIMT_OWNED] > (unsigned)trimt_positions(t) || mine > w[TRIMT_OWNED]) return failed(i, fail(t.h, PPP_ERR_HIP, "trimmed registration tiles: histogram corrupt"));
+            t.part.owned = w[TRIMT_OWNED];
+            parts[i] = t.part;
+            part_rows[i] = ppp_registration_row{};
+            paired += mine;
+        }
+        Cut cut = {paired, TRIM_NAN};
+        if (paired) { /* B.78 on the merged histograms; without a pair the evaluation ends here: kept 0, no sums */
+            merge_hist(TRIMT_HEAD, TRIM_B0);
+            unsigned bin, prefix;
+            size_t rank;
+            ppp_trim_select(H.data(), TRIM_B0, trim_rank(keep, paired), &bin, &rank);
+            if (!rank) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+            prefix = bin << 21;
+            for (int pass = 1; pass <= 2; ++pass) {
+                const size_t bins = pass == 1 ? TRIM_B1 : TRIM_B2;
+                for (size_t i = 0; i < count; ++i) { e = trimt_enqueue_narrow(tiles[i], pass, prefix); if (e) return failed(i, e); }
+                e = wait_all();
+                if (e) return e;
+                merge_hist(0, bins);
+                ppp_trim_select(H.data(), bins, rank, &bin, &rank);
+                if (!rank) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+                prefix |= pass == 1 ? bin << 10 : bin;
+            }
+            cut.tau = prefix;
+            for (size_t i = 0; i < count; ++i) { e = trimt_enqueue_terms(tiles[i], cut.tau); if (e) return failed(i, e); }
+            e = wait_all();
+            if (e) return e;
+            for (size_t i = 0; i < count; ++i) {
+                const unsigned long long *w = tiles[i].h->registration.tpin.p;
+                if (w[ICP_PAIRS] > parts[i].owned) return failed(i, fail(tiles[i].h, PPP_ERR_HIP, "trimmed registration tiles: sums corrupt"));
+                icp_row_terms(&part_rows[i], T, w);
+            }
+        }
+        e = regt_merged(h0, part_rows, parts, T, rw, whole);
+        if (e) return e;
+        if (rw.pairs > paired || (paired && rw.pairs < trim_rank(keep, paired))) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+        cuts.push_back(cut);
+        return (int)PPP_OK;
+    });
+    if (rc) return rc;
+    const size_t last = (size_t)C.steps;
+    /* B.99: the maps of the last evaluation -- its keys are the ones the tiles hold --, every tile's launch before any copy */
+    for (size_t i = 0; i < count; ++i)
+        if (map_of(status, i) || map_of(d2, i) || map_of(owned, i)) {
+            rc = trimt_enqueue_scatter(tiles[i], cuts[last].tau, cuts[last].paired == 0);
+            if (rc) return failed(i, rc);
+        }
+    for (size_t i = 0; i < count; ++i) {
+        rc = trimt_copy_maps(tiles[i], map_of(status, i), map_of(d2, i), map_of(owned, i), cap);
+        if (rc) return failed(i, rc);
+    }
+    if (stats) stats->reg = regt_stats(R, C, whole);
+    const size_t k = std::min(row_cap, last + 1);
+    for (size_t i = 0; rows && i < k; ++i) {
+        ppp_trimmed_registration_row &o = rows[i];
+        memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
+        o.row = R[i];
+        o.paired = cuts[i].paired;
+        memcpy(&o.trim_d2, &cuts[i].tau, sizeof(float));
+    }
     return PPP_OK;
 }
 

@@ -10,6 +10,7 @@
 #pragma once
 #include "ppp_registration.h"
 #include <cstring>
+#include <vector>
 
 /* the words a tile's evaluation leaves: the 29 of the sums, the owned points it met, the owned queries that set the refusal */
 #define REGT_OWNED ICP_WORDS
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(ICP_T) k_regt_terms(const float4 *__restrict__
 }
 
 /* ---------------------------------------------------------------------------------------------------------------------- */
-/* Host: the merge (B.91) and the step (B.92)                                                                             */
+/* Host: the merge (B.91), the step (B.92) and the loop (B.93)                                                             */
 /* ---------------------------------------------------------------------------------------------------------------------- */
 
 /* do the parts belong to one evaluation of one scan against one reference?  n, shift, centre and length bit for bit */
@@ -97,4 +98,33 @@ inline int regt_step(const ppp_registration_row &row, const double *c, double Ln
     *step2 = icp_compose(x, c, Ln, T, Tn);
     *locked = mask;
     return PPP_STEP_TAKEN;
+}
+
+/* The host's loop of both tiled registrations (B.93): reg_step_body's control flow, word for word -- `stop` behind a step below
+   min_step makes the next evaluation the last, an evaluation no step is taken from ends the loop, and the evaluation behind the
+   last of `iterations` steps is a row without a step.  eval(k, rw): evaluation k at T, merged over the tiles, or its error. */
+template <typename Eval>
+inline int regt_loop(const ppp_registration_params &P, const IcpFrame &F, double *T, std::vector<ppp_registration_row> &R, IcpCtl &C,
+                     ppp_registration_part &whole, Eval eval)
+{
+    for (int k = 0; k <= P.iterations; ++k) {
+        ppp_registration_row rw;
+        const int rc = eval(k, rw);
+        if (rc) return rc;
+        if (k == P.iterations) { R.push_back(rw); break; } /* the evaluation behind the last step */
+        double Tn[12];
+        int mask = ICP_ALL_LOCKED;
+        double step2 = icp_nan();
+        if (!C.stop) {
+            const int sc = regt_step(rw, whole.centre, whole.length, F.lock_eps, T, Tn, &mask, &step2);
+            if (sc == PPP_STEP_STATIONARY) C.converged = 1;
+        }
+        if (mask == ICP_ALL_LOCKED) { R.push_back(rw); C.done = 1; break; }
+        rw.locked = mask; rw.step2 = step2;
+        R.push_back(rw);
+        C.steps += 1; C.locked |= mask;
+        if (step2 < F.min_step2) { C.stop = 1; C.converged = 1; }
+        memcpy(T, Tn, 12 * sizeof(double));
+    }
+    return PPP_OK;
 }

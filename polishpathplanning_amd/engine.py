@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_trim_select", "ppp_trim_rank", "ppp_register_trimmed_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -186,6 +186,12 @@ def lib():
         L.ppp_default_trimmed_registration_params.restype = None
         L.ppp_register_trimmed.argtypes = [vp, vp, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow), sz, C.POINTER(C.c_ubyte), fp,
                                            sz, C.POINTER(RegistrationStats)]
+        L.ppp_trim_select.argtypes = [C.POINTER(C.c_uint), sz, sz, C.POINTER(C.c_uint), C.POINTER(sz)]
+        L.ppp_trim_rank.argtypes = [C.c_double, sz]
+        L.ppp_trim_rank.restype = sz
+        L.ppp_register_trimmed_tiles.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow),
+                                                 sz, C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(fp), C.POINTER(C.POINTER(C.c_ubyte)), sz,
+                                                 C.POINTER(RegisterTilesStats)]
         L.ppp_transform_cloud.argtypes = [vp, dp]
         L.ppp_get_cloud_moments.argtypes = [vp, C.POINTER(CloudFrame)]
         L.ppp_cloud_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
@@ -590,6 +596,88 @@ def register_tiles(engines, refs, max_dist=2.0, iterations=30, min_step=1e-6, lo
         raise PPPError(rc, "tile %d: %s" % (st.failed_tile, text))
     stats = _registration_stats(st.reg)
     return stats["T"].copy(), [_registration_row(rows[i]) for i in range(min(cap, st.reg.steps + 1))], stats
+
+
+def trim_select(hist, rank):
+    """(bin, rank_in_bin): the bin of the histogram `hist` (counts, uint32) that holds the rank-th smallest entry, 1-based -- the
+    first bin whose running count reaches rank -- and the rank inside it (ppp_trim_select: host only, the device's rule).
+    rank 0 or a rank above the total finds nothing: (0, 0)"""
+    h = np.ascontiguousarray(hist, np.uint32)
+    b, r = C.c_uint(), C.c_size_t()
+    rc = lib().ppp_trim_select(h.ctypes.data_as(C.POINTER(C.c_uint)), len(h), int(rank), C.byref(b), C.byref(r))
+    if rc:
+        raise PPPError(rc, "ppp_trim_select: bad arguments")
+    return int(b.value), int(r.value)
+
+
+def trim_rank(keep, paired):
+    """k of the trimmed cut (ppp_trim_rank: host only): ceil(keep * paired) in double, clamped to [1, paired]; 0 without a pair"""
+    return int(lib().ppp_trim_rank(float(keep), int(paired)))
+
+
+def register_trimmed_tiles(engines, refs, keep=0.8, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
+    """(T float64[3, 4], rows, statuses, d2s, owneds, stats): Engine.register_trimmed()'s T, rows and stats, bit for bit, for a scan
+    held as slice-range engines (ppp_register_trimmed_tiles); engines and refs as register_tiles() takes them.  statuses[i],
+    d2s[i] and owneds[i] are tile i's maps of the last evaluation by cloud index: an indexed point the tile owns has owned 1 and
+    register_trimmed()'s status and d2, every other entry owned 0, TRIM_DROPPED and NaN; merge_trimmed_maps() makes the whole
+    cloud's of them.  An evaluation is four host round trips: three histogram merges and the sums.  maps=False returns None
+    for the three lists.  A tile's error is raised with its index in the message"""
+    engines = list(engines)
+    refs = [refs] * len(engines) if isinstance(refs, Engine) else list(refs)
+    if len(refs) != len(engines):
+        raise PPPError(ERR_ARG, "register_trimmed_tiles: one reference per tile")
+    k = len(engines)
+    hs = (C.c_void_p * max(k, 1))(*[e.h for e in engines])
+    rs = (C.c_void_p * max(k, 1))(*[e.h for e in refs])
+    tp = TrimmedRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(keep))
+    cap = max(int(iterations), 0) + 1
+    rows = (TrimmedRegistrationRow * cap)()
+    st = RegisterTilesStats()
+    t = _t12(T0)
+    statuses = d2s = owneds = sp = dp = op = None
+    n = 0
+    if maps and k:
+        nn = C.c_size_t()
+        engines[0]._chk(lib().ppp_num_points(engines[0].h, C.byref(nn)))
+        n = nn.value
+        ub, fp = C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+        statuses = [np.zeros(max(n, 1), np.uint8) for _ in range(k)]
+        d2s = [np.zeros(max(n, 1), np.float32) for _ in range(k)]
+        owneds = [np.zeros(max(n, 1), np.uint8) for _ in range(k)]
+        sp = (ub * k)(*[a.ctypes.data_as(ub) for a in statuses])
+        dp = (fp * k)(*[a.ctypes.data_as(fp) for a in d2s])
+        op = (ub * k)(*[a.ctypes.data_as(ub) for a in owneds])
+    rc = lib().ppp_register_trimmed_tiles(hs, rs, k, C.byref(tp), None if t is None else _d(t), rows, cap, sp, dp, op, n, C.byref(st))
+    if rc:
+        at = st.failed_tile if st.failed_tile >= 0 else 0
+        text = engines[at].L.ppp_last_error(engines[at].h).decode() if k else "no tile"
+        raise PPPError(rc, "tile %d: %s" % (st.failed_tile, text))
+    stats = _registration_stats(st.reg)
+    if statuses is not None:
+        statuses, d2s, owneds = [a[:n] for a in statuses], [a[:n] for a in d2s], [a[:n] for a in owneds]
+    return (stats["T"].copy(), [_trimmed_registration_row(rows[i]) for i in range(min(cap, st.reg.steps + 1))], statuses, d2s, owneds, stats)
+
+
+def merge_trimmed_maps(statuses, d2s, owneds):
+    """(status uint8[n], d2 float32[n]) of the whole cloud from register_trimmed_tiles()' per-tile maps (numpy only): every point
+    takes the entries of the one tile that owns it; a point nobody owns is not finite: TRIM_DROPPED and NaN.
+    PPPError(ERR_ARG): no tile, maps of different lengths, a point two tiles own"""
+    if not len(statuses) or not (len(statuses) == len(d2s) == len(owneds)):
+        raise PPPError(ERR_ARG, "merge_trimmed_maps: no tile, or lists of different lengths")
+    n = len(statuses[0])
+    status = np.full(n, TRIM_DROPPED, np.uint8)
+    d2 = np.full(n, np.nan, np.float32)
+    seen = np.zeros(n, bool)
+    for s, d, o in zip(statuses, d2s, owneds):
+        if not (len(s) == len(d) == len(o) == n):
+            raise PPPError(ERR_ARG, "merge_trimmed_maps: maps of different lengths")
+        mine = np.asarray(o) != 0
+        if np.any(seen & mine):
+            raise PPPError(ERR_ARG, "merge_trimmed_maps: a point two tiles own")
+        seen |= mine
+        status[mine] = np.asarray(s, np.uint8)[mine]
+        d2[mine] = np.asarray(d, np.float32)[mine]
+    return status, d2
 
 
 class CloudFrame(C.Structure):
@@ -1422,6 +1510,8 @@ class Engine:
         if maps:
             status, d2 = status[:n], d2[:n]
         return stats["T"].copy(), [_trimmed_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, d2, stats
+
+    register_trimmed_tiles = staticmethod(register_trimmed_tiles)   # Engine.register_trimmed_tiles(engines, refs, ...): the module's function
 
     def cloud_moments(self):
         """ppp_get_cloud_moments: the frame dict of the resident cloud (count, ms, c, L, the ten integer words, mean, axes with
