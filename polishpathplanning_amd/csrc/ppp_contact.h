@@ -7,6 +7,14 @@
 #pragma once
 #include "ppp_dynamic.h"
 #include "../../include/ppp_hip.h" /* PPP_CONTACT_BINS */
+/* The kernels of this header are ppp_contact.hip's.  ppp_scan.hip needs the header for its types and device helpers only
+   (TileRange, ordered_key, block_tree_sum, ...) and defines PPP_CONTACT_KERNELS_FOREIGN: the kernels are templates there and,
+   never launched, never instantiated (PPP_KERNEL's idiom, ppp_kernels.h). */
+#ifdef PPP_CONTACT_KERNELS_FOREIGN
+#define PPP_CONTACT_KERNEL template <typename PPP_NEVER_ = void> __global__
+#else
+#define PPP_CONTACT_KERNEL __global__
+#endif
 
 /* The knots of the slices' paths (the host fills it: knot_table). */
 struct SliceKnots { const float *ky, *kx, *kz; int mm; };
@@ -186,7 +194,7 @@ __device__ inline void wave_mark_ball(const SlabView &V, const DynGrid &G, DynWa
 /* One wave per compute_boundary sample: blockIdx.y = slice, blockIdx.z = 0 the raw path (knots at raw_sc, as k_dyn_first_eval
    found them), 1 the adjusted one (node_start / node_cnt after the pass; slices 1 .. S-2).  The reference's "last point" call
    repeats the last sample's ball; a loop that ran zero times adds no ball. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_cov_balls(ContactIndex I, DynParams D, KnotTable T, const int *__restrict__ raw_sc,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_cov_balls(ContactIndex I, DynParams D, KnotTable T, const int *__restrict__ raw_sc,
         int maxNB, unsigned char *__restrict__ flags)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -214,7 +222,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_cov_balls(ContactIndex I, Dy
 /* get_coverage's yes count: the flags (0 / 1, zero padding up to a multiple of 16 bytes) summed 16 at a time by population
    count, a wave sum, one atomic per workgroup -- integers, so the count is the same in every run */
 #define COV_T 256
-__global__ void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ flags16, int n16, int *__restrict__ count)
+PPP_CONTACT_KERNEL void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ flags16, int n16, int *__restrict__ count)
 {
     __shared__ int s_c;
     if (threadIdx.x == 0) s_c = 0;
@@ -240,7 +248,7 @@ __global__ void __launch_bounds__(COV_T) k_cov_count(const uint4 *__restrict__ f
    j + gridDim.x * DYN_WAVES, ... while dy < maxy - 2 (a loop that runs zero times adds no ball, B.15).  The ball of a sample
    is k_cov_balls's.  err[0] |= 1 where a sample's searches leave a slice-range handle's interval (wave_ball_leaves_range),
    err[0] |= 2 for a knot table beyond node_cap.  The host then refuses the answer. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(ContactIndex I, DynParams D, KnotTable T, int sb, PCovRange R,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_pcov_balls(ContactIndex I, DynParams D, KnotTable T, int sb, PCovRange R,
         unsigned char *__restrict__ flags, int *__restrict__ err)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -290,7 +298,7 @@ __device__ inline int pcon_sample_count(const DynParams &D, double miny, double 
 /* One workgroup: off[i] = the first table row of slice sb + i, off[nsl] = the rows in all, off[nsl + 1] = the refusal word
    after this launch.  A slice of fewer than 3 knots has none (B.15).  err |= 2 for a knot table beyond node_cap or a slice
    of 2^24 samples (k_pcov_balls's refusals), 4 for a slice of 2^22 samples or a table of 2^30 rows or more. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_offsets(DynParams D, KnotTable T, int sb, int nsl, int *__restrict__ off,
+PPP_CONTACT_KERNEL void __launch_bounds__(PCON_T) k_pcon_offsets(DynParams D, KnotTable T, int sb, int nsl, int *__restrict__ off,
         int *__restrict__ err)
 {
     __shared__ int s_scan[17];
@@ -324,7 +332,7 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_offsets(DynParams D, KnotTable 
    (same spline point, same Area2Cloud, r = (ext[0] - ext[1]) / 2 and r * r in float) goes to tab[off + j] as (qx, qy, qz,
    r2); a NaN r2 holds no point.  reach[3 i ..] takes the slice's x-reach and largest |r| as keys (ordered_key; the lower end
    as the key of its negation), one atomic per workgroup each.  The refusal of k_pcov_balls (wave_ball_leaves_range). */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_pcon_samples(ContactIndex I, DynParams D, KnotTable T, const int *__restrict__ off,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_pcon_samples(ContactIndex I, DynParams D, KnotTable T, const int *__restrict__ off,
         int sb, int s0, PCovRange R, float4 *__restrict__ tab, unsigned *__restrict__ reach, int *__restrict__ err)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -431,7 +439,7 @@ __device__ __attribute__((always_inline)) inline void pcon_walk_points(const Dev
 /* The count map by the point walk (pcon_walk_points): how many balls hold the point, and the first and last slice that has
    one of them.  Points that no ball holds keep the 0 / -1 of the memset. */
 struct PconAcc { unsigned cnt = 0; int fs = -1, ls = -1; };
-__global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
+PPP_CONTACT_KERNEL void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const float4 *__restrict__ sorted4, const float4 *__restrict__ tab,
         const int *__restrict__ off, const unsigned *__restrict__ reach, int sb, int nsl, unsigned *__restrict__ counts,
         int *__restrict__ first, int *__restrict__ last)
 {
@@ -444,7 +452,7 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_points(const DevMeta *m, const 
    first), the sum and the largest count.  Per-workgroup LDS bins, then one integer atomic per non-empty bin and workgroup, as
    k_cov_count counts: the same result in every run.  acc[0 .. 63] bins, [64] covered, [65] multi_slice, [66] total,
    [67] max; workgroup 0 also copies the refusal word into [68], so that one read brings everything back. */
-__global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restrict__ counts, const int *__restrict__ first,
+PPP_CONTACT_KERNEL void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restrict__ counts, const int *__restrict__ first,
         const int *__restrict__ last, int n, const int *__restrict__ err, unsigned long long *__restrict__ acc)
 {
     __shared__ int s_bin[PPP_CONTACT_BINS];
@@ -496,7 +504,7 @@ __global__ void __launch_bounds__(PCON_T) k_pcon_stats(const unsigned *__restric
 
 /* ppp_principal_curvatures_at: one wave per query q_xyz[3 j ..], wave_area2cloud<true, true> as k_pcon_samples calls it; row j
    of curv5 (and of half_width, where one is given) is query j's. */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_waves(ContactIndex I, DynParams D, const float *__restrict__ q_xyz, int k,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_field_waves(ContactIndex I, DynParams D, const float *__restrict__ q_xyz, int k,
         float *__restrict__ curv5, float *__restrict__ half_width)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -525,7 +533,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_field_waves(ContactIndex I, 
    serves one query -- ONCE for the batch, a lane per query (part 2); then each query's two folds by the whole wave (part 3).
    Rows by cloud index, as k_field_waves writes them, and the same bits. */
 #define FIELD_Q 16
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_batch(ContactIndex I, DynParams D, int n, float *__restrict__ curv5,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_field_batch(ContactIndex I, DynParams D, int n, float *__restrict__ curv5,
         float *__restrict__ half_width)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -590,7 +598,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_field_batch(ContactIndex I, 
    tested against the indexed interval (wave_ball_leaves_range without a ball: the field marks nothing): err[0] |= 1 where one
    leaves it.  hw_own takes the half widths of the owned points alone (the statistics' map).  A kernel of its own: as one
    template with k_field_batch it cost that kernel two registers (104 -> 106 VGPR). */
-__global__ void __launch_bounds__(64 * DYN_WAVES) k_field_tile(ContactIndex I, DynParams D, int pos0, int n, TileRange T, PCovRange R,
+PPP_CONTACT_KERNEL void __launch_bounds__(64 * DYN_WAVES) k_field_tile(ContactIndex I, DynParams D, int pos0, int n, TileRange T, PCovRange R,
         float *__restrict__ curv5, float *__restrict__ half_width, float *__restrict__ hw_own, int *__restrict__ err)
 {
     __shared__ DynWaveLds s_w[DYN_WAVES];
@@ -661,7 +669,7 @@ __global__ void __launch_bounds__(64 * DYN_WAVES) k_field_tile(ContactIndex I, D
 
 /* One thread per position of [pos0, pos1): owned[cloud index] = 1 for a point the tile owns, 2 for an evaluated halo point (0
    of the memset elsewhere); cnt[0] += the owned points, cnt[1] += the evaluated ones (integer atomics, one pair per workgroup). */
-__global__ void __launch_bounds__(PCON_T) k_tile_mark(const float4 *__restrict__ sorted4, int pos0, int pos1, TileRange T,
+PPP_CONTACT_KERNEL void __launch_bounds__(PCON_T) k_tile_mark(const float4 *__restrict__ sorted4, int pos0, int pos1, TileRange T,
         unsigned char *__restrict__ owned, int *__restrict__ cnt)
 {
     __shared__ int s_c[2];
@@ -685,7 +693,7 @@ __global__ void __launch_bounds__(PCON_T) k_tile_mark(const float4 *__restrict__
    largest |r| as ordered keys, and the part's sum of |r| in double -- every thread its strided share in index order, then
    block_tree_sum -- to psum[g]: the host adds the parts in order, so the sum is the same in every run.
    acc[0 .. 63] bins, [64] valid, [65] narrow (2 |r| < min_width, min_width > 0), [66] key of -min |r|, [67] key of max |r|. */
-__global__ void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict__ half_width, int n, int per, double tool_radius,
+PPP_CONTACT_KERNEL void __launch_bounds__(PCON_T) k_field_stats(const float *__restrict__ half_width, int n, int per, double tool_radius,
         float min_width, unsigned long long *__restrict__ acc, double *__restrict__ psum)
 {
     __shared__ int s_bin[PPP_CONTACT_BINS];

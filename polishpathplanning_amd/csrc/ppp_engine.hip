@@ -9,7 +9,8 @@
  *
  * Here: create / destroy, parameters, cloud ingest, the plan, the slab and window passes, the dynamic chain, the arena re-run,
  * graphs and batches, gather, sync, the getters, the API mirrors, ppp_spline_*, settings and kernel timing.  The contact
- * queries are ppp_contact.hip's, the preprocessing calls ppp_preproc.hip's; what the three share is ppp_handle.h.
+ * queries are ppp_contact.hip's, the scan-against-reference calls ppp_scan.hip's, the preprocessing calls ppp_preproc.hip's; what
+ * the four share is ppp_handle.h.
  */
 #include "ppp_kernels.h"
 #ifdef PPP_SINGLE_TU /* diagnostic builds (in-kernel stamps share one g_stamps array): every kernel in this translation unit */
@@ -2870,5 +2871,6 @@ int ppp_get_kernel_times(ppp_handle h, char *names, float *ms, int *launches, si
 
 #ifdef PPP_SINGLE_TU /* (see the top: the other units' kernels stamp into the same g_stamps) */
 #include "ppp_contact.hip"
+#include "ppp_scan.hip"
 #include "ppp_preproc.hip"
 #endif

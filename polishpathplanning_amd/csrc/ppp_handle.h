@@ -6,6 +6,7 @@
  *   ppp_engine.hip   the handle, the plan and the passes, graphs and batches, the getters and the API mirrors; it defines
  *                    every helper declared here
  *   ppp_contact.hip  the contact queries: coverage, path coverage, path contacts, the contact field, the regions, the schedules
+ *   ppp_scan.hip     the calls that hold a scan against a reference cloud: the deviation map, the registrations, their tiles
  *   ppp_preproc.hip  the four preprocessing calls on the resident cloud
  *
  * A helper that only one unit calls is static in that unit and is not declared here.
@@ -25,7 +26,7 @@
 
 struct RegAcc; /* ppp_regions.h: a region's accumulators (the handle owns buffers of them; only the contact unit looks inside) */
 struct FeedRec; /* ppp_feed.h: what the feed envelope reads of a waypoint (likewise) */
-struct IcpFrame; /* ppp_registration.h: what does not change along a registration chain (likewise) */
+struct IcpFrame; /* ppp_registration.h: what does not change along a registration chain (only the scan unit looks inside) */
 
 /* The types and helpers of the host units.  Hidden: the library is linked without visibility flags, and names like `fail` or
    `compact` are not for its dynamic symbol table. */

@@ -15,10 +15,13 @@
 #pragma once
 /* Every kernel is compiled in exactly one translation unit.  The kernels of this header, the chain kernels of ppp_dynamic.h and
    k_area2cloud_api, and k_compact_scan (ppp_compact.h) belong to the engine's (ppp_engine.hip); ppp_contact.hip owns the kernels of
-   ppp_contact.h and ppp_regions.h, ppp_preproc.hip those of ppp_preproc.h and ppp_align.h, ppp_window.hip those of ppp_window.h.  A
+   ppp_contact.h, ppp_regions.h, ppp_removal.h, ppp_dwell.h and ppp_feed.h, ppp_scan.hip those of ppp_deviation.h, ppp_deviation_tile.h,
+   ppp_registration.h, ppp_trimmed.h, ppp_registration_tile.h and ppp_trimmed_tile.h, ppp_preproc.hip those of ppp_preproc.h and
+   ppp_align.h, ppp_window.hip those of ppp_window.h.  A
    unit that needs the engine's headers for their types and device helpers only defines PPP_KERNELS_FOREIGN: the non-template
    kernels are templates there and, never launched, never instantiated (a static kernel would still be compiled and emitted: 47
-   functions in that translation unit's code object); the two that such a unit launches itself are plain declarations there. */
+   functions in that translation unit's code object); the two that such a unit launches itself are plain declarations there.
+   ppp_contact.h does the same for ppp_scan.hip with PPP_CONTACT_KERNELS_FOREIGN. */
 #ifdef PPP_KERNELS_FOREIGN
 #define PPP_KERNEL template <typename PPP_NEVER_ = void> __global__
 #else

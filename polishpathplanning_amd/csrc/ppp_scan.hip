@@ -1,0 +1,1221 @@
+/*
+ * ppp_scan.hip -- the calls of the C ABI (include/ppp_hip.h) that hold a scan against a reference cloud: the deviation map, its
+ * tiles and their merge, the registration chain, its trimmed form, the cloud moments and the global registration, and the
+ * registration and trimmed registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
+ * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_registration_tile.h and ppp_trimmed_tile.h; of the handle it sees
+ * what ppp_handle.h declares, and it shares ppp_query_host.h with ppp_contact.hip.  Compiled with the engine's flags: the host
+ * and the device step share icp_solve and icp_compose, one IEEE rounding per written operation on both sides.
+ */
+#ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
+#define PPP_KERNELS_FOREIGN /* ppp_kernels.h, ppp_dynamic.h, ppp_compact.h: types and device helpers only -- their kernels are the engine's */
+#define PPP_CONTACT_KERNELS_FOREIGN /* ppp_contact.h likewise: its kernels are ppp_contact.hip's */
+#endif
+#include "ppp_query_host.h"
+#include "ppp_deviation.h"
+#include "ppp_deviation_tile.h"
+#include "ppp_registration.h"
+#include "ppp_trimmed.h"
+#include "ppp_registration_tile.h"
+#include "ppp_trimmed_tile.h"
+#include <cstring>
+
+/* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
+template <typename Stats>
+static void dev_stats_words(Stats &st, size_t N, const unsigned long long *acc)
+{
+    st.n = N; st.matched = (size_t)acc[0]; st.too_far = (size_t)acc[1]; st.no_normal = (size_t)acc[2];
+    st.proud = (size_t)acc[DEV_ACC_PROUD]; st.below = (size_t)acc[DEV_ACC_BELOW];
+    st.min_dev = st.max_dev = (double)NAN; st.max_dist2 = NAN;
+    if (!st.matched) return;
+    st.min_dev = -ordered_unkey64(acc[DEV_ACC_NMIN]); st.max_dev = ordered_unkey64(acc[DEV_ACC_MAX]);
+    st.max_dist2 = ordered_unkey((unsigned)acc[DEV_ACC_D2]);
+}
+
+extern "C" {
+
+void ppp_default_deviation_params(ppp_deviation_params *dp)
+{
+    if (!dp) return;
+    dp->max_dist = INFINITY; dp->smooth_radius = 0.f; dp->allowance = 0.0; dp->gain = 1.0;
+}
+
+/* The checks of a scan-against-reference call's handle, scan or reference (w: "<call>: <which handle>"); refusals and errors are
+   reported on h, the call's first argument, whichever handle they are about.  deviation_side_cloud builds no index and launches
+   nothing (plan: the tile call's, whose range checks want what the handle owns); deviation_side_index builds the slab index. */
+static int deviation_side_cloud(ppp_handle h, ppp_handle side, const std::string &w, bool plan)
+{
+    if (!side->have_cloud) return fail(h, PPP_ERR_ARG, w + " holds no cloud");
+    if (side->part_given) return fail(h, PPP_ERR_UNSUPPORTED, w + " holds a part (ppp_set_cloud_part): the maps address the whole cloud");
+    const int rc = plan ? plan_ready(side) : PPP_OK;
+    return rc && side != h ? fail(h, rc, w + ": " + side->err) : rc;
+}
+static int deviation_side_index(ppp_handle h, ppp_handle side, const std::string &w, bool whole)
+{
+    int rc = index_ready(side, false); /* (behind a window pass it keeps that pass's run state, as every API mirror's does) */
+    if (rc) return side == h ? rc : fail(h, rc, w + ": " + side->err);
+    if (whole && (side->ranged || side->use_part)) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
+    const int ns = side->hmeta.n_sorted;
+    if (side->n > 0x7fffffffu || ns < 0 || (size_t)ns > side->n) return fail(h, PPP_ERR_HIP, w + ": index corrupt");
+    return PPP_OK;
+}
+/* a handle of ppp_get_deviation, scan or reference: a cloud, all of it, its slab index complete */
+static int deviation_side(ppp_handle h, ppp_handle side, const char *who, const char *what = "deviation")
+{
+    const std::string w = std::string(what) + ": " + who;
+    int rc = deviation_side_cloud(h, side, w, false);
+    if (rc) return rc;
+    if (side->P.slice_begin != 0 || side->P.slice_end != 0) return fail(h, PPP_ERR_UNSUPPORTED, w + " is a slice-range handle: it indexes a part of the cloud only");
+    return deviation_side_index(h, side, w, true);
+}
+
+/* both deviation calls' checks before they look at a handle, in the order they fire; w: the call's name, halo: the tile call's */
+static int deviation_call_ok(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, const std::string &w, const float *halo)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !dp) return fail(h, PPP_ERR_ARG, w + ": no reference handle or no parameters");
+    const ppp_deviation_params &P = *dp;
+    if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, w + (halo ? ": max_dist must be > 0" : ": max_dist must be > 0 (+INFINITY: no limit)"));
+    if (halo && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": a tile needs a finite max_dist: the halo must hold every partner");
+    if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, w + ": smooth_radius must be finite and >= 0");
+    if (!std::isfinite(P.allowance)) return fail(h, PPP_ERR_ARG, w + ": allowance must be finite");
+    if (!(P.gain >= 0.0 && std::isfinite(P.gain))) return fail(h, PPP_ERR_ARG, w + ": gain must be finite and >= 0");
+    if (!halo && P.smooth_radius > 0.f && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": smoothing needs a finite max_dist");
+    if (halo && !(*halo >= P.max_dist + P.smooth_radius && *halo <= 3.402823466e+38f))
+        return fail(h, PPP_ERR_ARG, w + ": halo must be finite and at least max_dist + smooth_radius");
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the two handles are on different devices");
+    return PPP_OK;
+}
+
+/* the integer sum of a neighbourhood or of the statistics: |deviation| <= about max_dist, n terms of it in 2^-24 mm */
+static bool deviation_sum_overflows(const ppp_deviation_params &P, size_t n) { return P.smooth_radius > 0.f && (double)P.max_dist * DEV_FIXED * (double)n >= 4611686018427387904.0; }
+
+/* the reference's normal field, on ref's stream, and the one wait for that stream */
+static int reference_normals(ppp_handle h, ppp_handle ref, const char *what)
+{
+    int rc = contact_buffers(ref);
+    if (rc) return ref == h ? rc : fail(h, rc, std::string(what) + ": the reference: " + ref->err);
+    if (ref != h) HIPCHK(h, hipStreamSynchronize(ref->stream));
+    return PPP_OK;
+}
+
+/* the maps' first k entries to the caller's arrays, those it gave (owned: the tile call's, behind the five maps) */
+static int deviation_copy_out(ppp_handle h, size_t k, const double *v, double *deviation, double *smoothed, int *ref_index, unsigned char *status, double *target,
+                              unsigned char *owned = nullptr)
+{
+    auto &D = h->deviation;
+    if (deviation && k) HIPCHK(h, copy_sync(h, deviation, D.dev.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (smoothed && k) HIPCHK(h, copy_sync(h, smoothed, v, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (ref_index && k) HIPCHK(h, copy_sync(h, ref_index, D.ref_index.p, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (status && k) HIPCHK(h, copy_sync(h, status, D.status.p, k, hipMemcpyDeviceToHost));
+    if (target && k) HIPCHK(h, copy_sync(h, target, D.target.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (owned && k) HIPCHK(h, copy_sync(h, owned, D.owned.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The deviation map: the reference's index and normal field on its own stream, one wait for that stream, then
+   k_dev_nearest, k_dev_smooth where asked, k_dev_target and k_dev_stats back to back on the scan's stream, and one wait. */
+int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, double *deviation, double *smoothed, int *ref_index,
+                      unsigned char *status, double *target, size_t cap, ppp_deviation_stats *stats)
+{
+    int rc = deviation_call_ok(h, ref, dp, "deviation", nullptr);
+    if (rc) return rc;
+    const ppp_deviation_params P = *dp;
+    const bool smooth = P.smooth_radius > 0.f;
+    rc = deviation_side(h, ref, "the reference");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side(h, h, "the scan"); if (rc) return rc; }
+    const size_t N = h->n;
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    rc = reference_normals(h, ref, "deviation");
+    if (rc) return rc;
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    const MapParts parts(h, N);
+    const int grid = parts.grid, per = parts.per, nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS)); HIPCHK(h, D.psum.ensure(2 * (size_t)grid));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    HIPCHK(h, hipMemsetAsync(D.status.p, PPP_DEV_DROPPED, N1, h->stream)); /* points outside the index: not finite */
+    HIPCHK(h, hipMemsetAsync(D.ref_index.p, 0xff, N1 * sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEV_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    const unsigned gq = (unsigned)((nq + DEV_T - 1) / DEV_T);
+    if (nq > 0) {
+        LAUNCH(h, "k_dev_nearest", k_dev_nearest, gq, DEV_T, 0, h->sorted4.p, nq, contact_index(ref), nref, P.max_dist * P.max_dist, D.dev.p, D.fix.p,
+               D.d2.p, D.ref_index.p, D.status.p);
+        if (smooth)
+            LAUNCH(h, "k_dev_smooth", k_dev_smooth, gq, DEV_T, 0, contact_index(h), nq, P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p,
+                   D.smoothed.p);
+    }
+    LAUNCH(h, "k_dev_target", k_dev_target, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, 2 * (size_t)h->num_cus), DEV_T, 0, D.status.p,
+           D.dev.p, v, D.d2.p, (int)N, P.allowance, P.gain, D.target.p, D.acc.p);
+    LAUNCH(h, "k_dev_stats", k_dev_stats, (unsigned)grid, PCON_T, 0, D.status.p, v, D.target.p, (int)N, per, D.acc.p, D.psum.p, D.psum.p + grid);
+    unsigned long long acc[DEV_ACC_WORDS];
+    std::vector<double> psum(2 * (size_t)grid);
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, psum.data(), D.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc[0] + acc[1] + acc[2] + acc[3] != N || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
+        return fail(h, PPP_ERR_HIP, "deviation: statistics corrupt");
+    if (stats) {
+        ppp_deviation_stats st = {};
+        dev_stats_words(st, N, acc);
+        st.dropped = (size_t)acc[3];
+        double sq = 0.0;
+        for (int g = 0; g < grid; ++g) { sq += psum[(size_t)g]; st.target_sum += psum[(size_t)grid + g]; }
+        st.mean_dev = st.matched ? (double)(long long)acc[DEV_ACC_FIXSUM] / (double)st.matched * (1.0 / DEV_FIXED) : (double)NAN;
+        st.rms_dev = st.matched ? std::sqrt(sq / (double)st.matched) : (double)NAN;
+        for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[DEV_ACC_BINS + b];
+        *stats = st;
+    }
+    return deviation_copy_out(h, std::min(cap, N), v, deviation, smoothed, ref_index, status, target);
+}
+
+void ppp_default_registration_params(ppp_registration_params *rp)
+{
+    if (!rp) return;
+    rp->max_dist = 2.f; rp->iterations = 30; rp->min_step = 1e-6; rp->lock_eps = 1e-9;
+}
+
+/* a chain's parameters, checked; F takes what they set */
+static int registration_params_ok(ppp_handle h, const ppp_registration_params &P, IcpFrame &F)
+{
+    F.md2 = P.max_dist * P.max_dist;
+    if (!(P.max_dist > 0.f && std::isfinite(P.max_dist) && std::isfinite(F.md2)))
+        return fail(h, PPP_ERR_ARG, "registration: max_dist must be finite and > 0 (and so its float square)");
+    if (P.iterations < 1 || P.iterations > 64) return fail(h, PPP_ERR_ARG, "registration: iterations must be in [1, 64]");
+    if (!(P.min_step >= 0.0 && std::isfinite(P.min_step))) return fail(h, PPP_ERR_ARG, "registration: min_step must be finite and >= 0");
+    if (!(P.lock_eps > 0.0 && P.lock_eps < 1.0)) return fail(h, PPP_ERR_ARG, "registration: lock_eps must be in (0, 1)");
+    F.lock_eps = P.lock_eps; F.min_step2 = P.min_step * P.min_step;
+    return PPP_OK;
+}
+
+/* The frame a cloud's bounds imply (B.67, B.68): the box's centre, half the sum of its extents widened by max_dist, and the
+   scale of the integer sums.  The order of the operations is part of the result: every caller's bits come from here. */
+static void frame_from_bounds(const float *mn, const float *mx, double max_dist, int shift, double *c, double *length, double *scale)
+{
+    double ext[3];
+    for (int d = 0; d < 3; ++d) {
+        c[d] = ((double)mn[d] + (double)mx[d]) * 0.5;
+        ext[d] = (double)mx[d] - (double)mn[d];
+    }
+    *length = (((ext[0] + ext[1]) + ext[2]) * 0.5) + max_dist;
+    *scale = std::ldexp(1.0, shift);
+}
+
+/* the transform a chain or a tiled call opens with: T0, the identity where there is none; every entry finite (w: the call's name) */
+static const double ICP_IDENTITY[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+static int opening_transform(ppp_handle h, const char *w, const double *T0, double *T)
+{
+    memcpy(T, T0 ? T0 : ICP_IDENTITY, sizeof(ICP_IDENTITY));
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) return fail(h, PPP_ERR_ARG, std::string(w) + ": the transform has an entry that is not finite");
+    return PPP_OK;
+}
+
+/* what a chain needs before its first launch: both handles' indices, the rest of F (B.67) and the shift (B.68), the reference's
+   normal field on its own stream and one wait for that stream */
+static int registration_setup(ppp_handle h, ppp_handle ref, const ppp_registration_params &P, IcpFrame &F, int &shift)
+{
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration: the two handles are on different devices");
+    int rc = deviation_side(h, ref, "the reference", "registration");
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side(h, h, "the scan", "registration"); if (rc) return rc; }
+    rc = fetch_meta(ref);
+    if (rc) return ref == h ? rc : fail(h, rc, std::string("registration: the reference: ") + ref->err);
+    shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    frame_from_bounds(ref->hmeta.mn, ref->hmeta.mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    return reference_normals(h, ref, "registration");
+}
+
+static_assert(sizeof(IcpCtl) == 5 * sizeof(int), "IcpCtl is five ints");
+/* a chain's control words behind the one wait: 0 <= steps <= iterations, and a chain that has not ended took every step */
+static bool chain_ctl_ok(const IcpCtl &c, int iterations) { return c.steps >= 0 && c.steps <= iterations && (c.done || c.steps == iterations); }
+
+/* ppp_register's statistics from the rows R[0 .. C.steps] of a chain or a tiled loop, its counts, shift and frame */
+static ppp_registration_stats registration_stats(const std::vector<ppp_registration_row> &R, const IcpCtl &C, size_t n, size_t indexed, int shift,
+                                                 const double *centre, double length)
+{
+    const size_t last = (size_t)C.steps;
+    ppp_registration_stats st = {};
+    st.n = n; st.indexed = indexed;
+    st.steps = C.steps; st.converged = C.converged; st.locked = C.locked; st.shift = shift;
+    for (int d = 0; d < 3; ++d) st.centre[d] = centre[d];
+    st.length = length;
+    memcpy(st.T, R[last].T, sizeof(st.T));
+    auto rms = [&](const ppp_registration_row &r) {
+        return r.pairs ? std::sqrt(std::ldexp((double)r.E, -shift) / (double)r.pairs) : (double)NAN;
+    };
+    st.pairs_before = R[0].pairs; st.rms_before = rms(R[0]);
+    st.pairs_after = R[last].pairs; st.rms_after = rms(R[last]);
+    return st;
+}
+
+/* a row of a trimmed chain or loop as the caller gets it: the row, the pairs the search found, the cut's bits as a float */
+static void trimmed_row(ppp_trimmed_registration_row &o, const ppp_registration_row &r, size_t paired, unsigned tau)
+{
+    memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
+    o.row = r;
+    o.paired = paired;
+    memcpy(&o.trim_d2, &tau, sizeof(float));
+}
+
+/* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
+   then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
+   transforms, the sums and the rows stay on the device, a chain that has ended turns the rest of its launches into returns --
+   and one wait.  !loop: the one evaluation of ppp_get_registration_terms.  trim (ppp_register_trimmed): an
+   evaluation is k_trim_pair, k_trim_narrow<1>, k_trim_narrow<2> and k_trim_terms instead of k_reg_terms -- its 29 words are over
+   the kept pairs --, k_trim_scatter follows the chain, and the rows and the maps go to trim's arrays. */
+struct TrimCall {
+    double keep;
+    ppp_trimmed_registration_row *rows;
+    unsigned char *status;
+    float *d2;
+    size_t cap;
+};
+
+static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0, bool loop,
+                              ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats, const TrimCall *trim = nullptr)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !rp) return fail(h, PPP_ERR_ARG, "registration: no reference handle or no parameters");
+    if (!rows && !(trim && trim->rows) && row_cap) return fail(h, PPP_ERR_ARG, "registration: rows is NULL with row_cap > 0");
+    if (trim && !(trim->keep > 0.0 && trim->keep <= 1.0)) return fail(h, PPP_ERR_ARG, "trimmed registration: keep must be in (0, 1]");
+    const ppp_registration_params P = *rp;
+    IcpFrame F;
+    int rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, "registration", T0, T);
+    if (rc) return rc;
+    int shift = 0;
+    rc = registration_setup(h, ref, P, F, shift);
+    if (rc) return rc;
+    const size_t N = h->n;
+    const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ICP_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * evals * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
+    /* grid-stride: the workgroups, and with them the atomics of an evaluation, are capped by the device, not by the cloud */
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
+    const size_t N1 = std::max<size_t>(N, 1);
+    TrimCut *cuts = nullptr;
+    if (trim) {
+        static_assert(sizeof(TrimCut) == 8 * sizeof(unsigned), "TrimCut is eight words");
+        HIPCHK(h, G.partner.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1))); HIPCHK(h, G.key.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1)));
+        HIPCHK(h, G.hist.ensure(TRIM_WORDS * evals)); HIPCHK(h, G.cuts.ensure(8 * evals));
+        HIPCHK(h, G.tstatus.ensure(N1)); HIPCHK(h, G.td2.ensure(N1));
+        cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+        /* every evaluation has histograms of its own: one clear on the stream before the chain, none between iterations */
+        HIPCHK(h, hipMemsetAsync(G.hist.p, 0, TRIM_WORDS * evals * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(G.cuts.p, 0, 8 * evals * sizeof(unsigned), h->stream));
+        HIPCHK(h, hipMemsetAsync(G.tstatus.p, PPP_TRIM_DROPPED, N1, h->stream)); /* points outside the index: not finite */
+        HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(G.td2.p), (int)TRIM_NAN, N1, h->stream));
+    }
+    for (int k = 0; k <= iterations; ++k) {
+        if (trim) {
+            unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+            LAUNCH(h, "k_trim_pair", k_trim_pair, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
+                   G.partner.p, G.key.p, hist);
+            LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, trim->keep, cuts + k);
+            LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, trim->keep,
+                   cuts + k);
+            LAUNCH(h, "k_trim_terms", k_trim_terms, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), F, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+                   G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.acc.p + ICP_WORDS * (size_t)k);
+        } else
+            LAUNCH(h, "k_reg_terms", k_reg_terms, grid, ICP_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl,
+                   G.acc.p + ICP_WORDS * (size_t)k);
+        if (k < iterations)
+            LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, G.acc.p + ICP_WORDS * (size_t)k, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    if (trim)
+        LAUNCH(h, "k_trim_scatter", k_trim_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, ctl, cuts, (int)evals, (int)N1, G.tstatus.p, G.td2.p);
+    IcpCtl C;
+    HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
+    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
+    const size_t last = (size_t)C.steps;
+    std::vector<ppp_registration_row> R(last + 1);
+    HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    if (!C.done) { /* the evaluation behind the last step: no step kernel follows it */
+        unsigned long long acc[ICP_WORDS];
+        double Tl[12];
+        HIPCHK(h, copy_sync(h, acc, G.acc.p + ICP_WORDS * last, sizeof(acc), hipMemcpyDeviceToHost));
+        HIPCHK(h, copy_sync(h, Tl, G.T.p + 12 * last, sizeof(Tl), hipMemcpyDeviceToHost));
+        icp_row_terms(&R[last], Tl, acc);
+    }
+    if (R[0].pairs > (size_t)std::max(nq, 0) || R[last].pairs > (size_t)std::max(nq, 0)) return fail(h, PPP_ERR_HIP, "registration: sums corrupt");
+    if (stats) *stats = registration_stats(R, C, N, (size_t)nq, shift, F.c, F.Ln);
+    const size_t k = std::min(row_cap, last + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    if (trim) {
+        std::vector<TrimCut> cut(last + 1);
+        HIPCHK(h, copy_sync(h, cut.data(), G.cuts.p, (last + 1) * sizeof(TrimCut), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i <= last; ++i)
+            if (cut[i].paired > (unsigned)std::max(nq, 0) || R[i].pairs > cut[i].paired || (cut[i].paired && R[i].pairs < cut[i].k))
+                return fail(h, PPP_ERR_HIP, "trimmed registration: cut corrupt");
+        for (size_t i = 0; trim->rows && i < k; ++i) trimmed_row(trim->rows[i], R[i], cut[i].paired, cut[i].tau);
+        const size_t m = std::min(trim->cap, N);
+        if (trim->status && m) HIPCHK(h, copy_sync(h, trim->status, G.tstatus.p, m, hipMemcpyDeviceToHost));
+        if (trim->d2 && m) HIPCHK(h, copy_sync(h, trim->d2, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return PPP_OK;
+}
+
+int ppp_get_registration_terms(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                               ppp_registration_stats *stats)
+{
+    return registration_chain(h, ref, rp, T12, false, row, row ? 1 : 0, stats);
+}
+
+int ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0_12, ppp_registration_row *rows, size_t row_cap,
+                 ppp_registration_stats *stats)
+{
+    return registration_chain(h, ref, rp, T0_12, true, rows, row_cap, stats);
+}
+
+void ppp_default_trimmed_registration_params(ppp_trimmed_registration_params *tp)
+{
+    if (!tp) return;
+    ppp_default_registration_params(&tp->icp);
+    tp->keep = 0.8;
+}
+
+int ppp_register_trimmed(ppp_handle h, ppp_handle ref, const ppp_trimmed_registration_params *tp, const double *T0_12,
+                         ppp_trimmed_registration_row *rows, size_t row_cap, unsigned char *status, float *d2, size_t cap,
+                         ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    if (!tp) return fail(h, PPP_ERR_ARG, "trimmed registration: no parameters");
+    const TrimCall trim = {tp->keep, rows, status, d2, cap};
+    return registration_chain(h, ref, &tp->icp, T0_12, true, nullptr, row_cap, stats, &trim);
+}
+
+/* The ten words of side's cloud (k_cloud_moments on side's stream, one wait) and the frame they imply; side's index is
+   complete (deviation_side).  Errors are reported on h. */
+static int cloud_moments(ppp_handle h, ppp_handle side, const char *who, ppp_cloud_frame *frame)
+{
+    const std::string w = std::string("cloud moments: ") + who;
+    auto run = [&]() -> int {
+        int rc = fetch_meta(side);
+        if (rc) return rc;
+        const int nq = side->hmeta.n_sorted;
+        if (nq <= 0) return fail(side, PPP_ERR_ARG, "no indexed point");
+        MomFrame F;
+        const int ms = mom_shift(side->n);
+        frame_from_bounds(side->hmeta.mn, side->hmeta.mx, 0.0, ms, F.c, &F.L, &F.scale); /* (+ 0.0 changes no bit of an extent) */
+        if (!(F.L > 0.0 && std::isfinite(F.L))) return fail(side, PPP_ERR_ARG, "the box of the cloud has no extent (L == 0)");
+        auto &G = side->registration;
+        HIPCHK(side, G.mom.ensure(MOM_WORDS));
+        HIPCHK(side, hipMemsetAsync(G.mom.p, 0, MOM_WORDS * sizeof(unsigned long long), side->stream));
+        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + MOM_T - 1) / MOM_T, 2 * (size_t)side->num_cus));
+        LAUNCH(side, "k_cloud_moments", k_cloud_moments, grid, MOM_T, 0, side->sorted4.p, nq, F, G.mom.p);
+        unsigned long long acc[MOM_WORDS];
+        HIPCHK(side, copy_sync(side, acc, G.mom.p, sizeof(acc), hipMemcpyDeviceToHost));
+        long long words[MOM_WORDS];
+        for (int i = 0; i < MOM_WORDS; ++i) words[i] = (long long)acc[i];
+        if (words[0] != (long long)nq) return fail(side, PPP_ERR_HIP, "sums corrupt");
+        if (!cloud_frame_from_words(words, ms, F.c, F.L, frame)) return fail(side, PPP_ERR_HIP, "sums corrupt");
+        return PPP_OK;
+    };
+    const int rc = run();
+    return rc ? fail(h, rc, w + ": " + side->err) : PPP_OK;
+}
+
+int ppp_get_cloud_moments(ppp_handle h, ppp_cloud_frame *frame)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!frame) return fail(h, PPP_ERR_ARG, "cloud moments: frame is NULL");
+    int rc = deviation_side(h, h, "the cloud", "cloud moments");
+    if (rc) return rc;
+    return cloud_moments(h, h, "the cloud", frame);
+}
+
+int ppp_cloud_frame_from_moments(const long long *words10, int ms, const double *c3, double L, ppp_cloud_frame *frame)
+{
+    if (!words10 || !c3 || !frame) return PPP_ERR_ARG;
+    return cloud_frame_from_words(words10, ms, c3, L, frame) ? PPP_OK : PPP_ERR_ARG;
+}
+
+int ppp_registration_starts(const ppp_cloud_frame *scan, const ppp_cloud_frame *ref, int candidates, double *T12s)
+{
+    if (!scan || !ref || !T12s || (candidates != 4 && candidates != 24)) return PPP_ERR_ARG;
+    registration_starts(scan, ref, candidates, T12s);
+    return PPP_OK;
+}
+
+void ppp_default_global_registration_params(ppp_global_registration_params *gp)
+{
+    if (!gp) return;
+    gp->candidates = 24; gp->stride = 16;
+    gp->coarse.max_dist = 10.f; gp->coarse.iterations = 8; gp->coarse.min_step = 1e-3; gp->coarse.lock_eps = 1e-9;
+    ppp_default_registration_params(&gp->fine);
+}
+
+/* Global registration: both clouds' moments, the starts their frames imply, then every start's coarse chain
+   side by side -- coarse.iterations + 1 launches of k_reg_terms_multi and coarse.iterations of k_reg_step_multi back to back
+   on h's stream, on the queries compacted once -- one wait, the winner by cost on the host, and registration_chain from it. */
+int ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registration_params *gp, ppp_registration_candidate *cands, size_t cand_cap,
+                        ppp_registration_row *rows, size_t row_cap, ppp_global_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !gp) return fail(h, PPP_ERR_ARG, "global registration: no reference handle or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "global registration: rows is NULL with row_cap > 0");
+    if (!cands && cand_cap) return fail(h, PPP_ERR_ARG, "global registration: cands is NULL with cand_cap > 0");
+    const ppp_global_registration_params P = *gp;
+    if (P.candidates != 4 && P.candidates != 24) return fail(h, PPP_ERR_ARG, "global registration: candidates must be 4 or 24");
+    if (P.stride < 1) return fail(h, PPP_ERR_ARG, "global registration: stride must be >= 1");
+    IcpFrame F, Ffine;
+    int rc = registration_params_ok(h, P.coarse, F);
+    if (rc) return rc;
+    rc = registration_params_ok(h, P.fine, Ffine);
+    if (rc) return rc;
+    int shift = 0;
+    rc = registration_setup(h, ref, P.coarse, F, shift);
+    if (rc) return rc;
+    if (icp_shift(h->n, Ffine.md2) < 16)
+        return fail(h, PPP_ERR_ARG, "registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    ppp_global_registration_stats st = {};
+    rc = cloud_moments(h, h, "the scan", &st.scan);
+    if (rc) return rc;
+    if (ref == h) st.ref = st.scan;
+    else { rc = cloud_moments(h, ref, "the reference", &st.ref); if (rc) return rc; }
+    const int K = P.candidates, iterations = P.coarse.iterations;
+    const size_t evals = (size_t)iterations + 1;
+    std::vector<double> T((size_t)K * evals * 12, 0.0), T0((size_t)K * 12);
+    registration_starts(&st.scan, &st.ref, K, T0.data());
+    for (double v : T0) if (!std::isfinite(v)) return fail(h, PPP_ERR_ARG, "global registration: a start has an entry that is not finite");
+    for (int s = 0; s < K; ++s) memcpy(&T[(size_t)s * evals * 12], &T0[(size_t)s * 12], 12 * sizeof(double));
+    const int ns = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    auto &G = h->registration;
+    const size_t ns1 = (size_t)std::max(ns, 1);
+    HIPCHK(h, G.queries.ensure(ns1)); HIPCHK(h, G.qcnt.ensure((ns1 + COMPACT_CHUNK - 1) / COMPACT_CHUNK + 1));
+    HIPCHK(h, G.mT.ensure(T.size())); HIPCHK(h, G.macc.ensure(ICP_WORDS * evals * K)); HIPCHK(h, G.mrows.ensure(evals * K)); HIPCHK(h, G.mctl.ensure(5 * (size_t)K));
+    int nq = 0;
+    if (ns > 0) {
+        const int nblocks = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+        StrideSel sel = {h->sorted4.p, P.stride, G.queries.p};
+        rc = compact(h, sel, ns, G.qcnt.p, G.qcnt.p + nblocks, [&](int kept) -> int {
+            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "global registration: query count corrupt");
+            nq = kept;
+            return PPP_OK;
+        });
+        if (rc) return rc;
+    }
+    if (nq <= 0) return fail(h, PPP_ERR_ARG, "global registration: no query left (no indexed point has a cloud index that is a multiple of stride)");
+    HIPCHK(h, hipMemsetAsync(G.macc.p, 0, ICP_WORDS * evals * K * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.mctl.p, 0, 5 * (size_t)K * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.mT.p, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.mctl.p);
+    /* all starts together stay at two workgroups per CU, and never below one per start */
+    const size_t per = std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus / (size_t)K));
+    const size_t tstride = 12 * evals, astride = ICP_WORDS * evals;
+    for (int k = 0; k <= iterations; ++k) {
+        LAUNCH(h, "k_reg_terms_multi", k_reg_terms_multi, dim3((unsigned)per, (unsigned)K), ICP_T, 0, G.queries.p, nq, contact_index(ref), nref, F,
+               G.mT.p + 12 * (size_t)k, tstride, ctl, G.macc.p + ICP_WORDS * (size_t)k, astride);
+        if (k < iterations)
+            LAUNCH(h, "k_reg_step_multi", k_reg_step_multi, K, 64, 0, G.macc.p + ICP_WORDS * (size_t)k, astride, F, G.mT.p + 12 * (size_t)k, tstride,
+                   G.mrows.p + k, evals, ctl);
+    }
+    std::vector<IcpCtl> C((size_t)K);
+    std::vector<ppp_registration_row> R(evals * K);
+    std::vector<unsigned long long> acc(ICP_WORDS * evals * K);
+    HIPCHK(h, copy_sync(h, C.data(), G.mctl.p, C.size() * sizeof(IcpCtl), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, R.data(), G.mrows.p, R.size() * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, acc.data(), G.macc.p, acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, T.data(), G.mT.p, T.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long far = llrint((double)F.md2 * F.scale);
+    std::vector<ppp_registration_candidate> cd((size_t)K);
+    int win = 0;
+    for (int s = 0; s < K; ++s) {
+        const IcpCtl &c = C[(size_t)s];
+        if (!chain_ctl_ok(c, iterations)) return fail(h, PPP_ERR_HIP, "global registration: control words corrupt");
+        const size_t first = (size_t)s * evals, last = first + (size_t)c.steps;
+        if (!c.done) icp_row_terms(&R[last], &T[12 * last], &acc[ICP_WORDS * last]); /* the evaluation behind the last step: no step kernel follows it */
+        if (R[first].pairs > (size_t)nq || R[last].pairs > (size_t)nq) return fail(h, PPP_ERR_HIP, "global registration: sums corrupt");
+        ppp_registration_candidate &o = cd[(size_t)s];
+        o = ppp_registration_candidate{};
+        o.index = s;
+        memcpy(o.T0, &T0[12 * (size_t)s], sizeof(o.T0)); memcpy(o.T, R[last].T, sizeof(o.T));
+        o.steps = c.steps; o.converged = c.converged; o.locked = c.locked;
+        o.pairs0 = R[first].pairs; o.E0 = R[first].E; o.pairs = R[last].pairs; o.E = R[last].E;
+        o.cost = o.E + (long long)((size_t)nq - o.pairs) * far;
+        if (o.cost < cd[(size_t)win].cost) win = s;
+    }
+    long long second = -1;
+    for (int s = 0; s < K; ++s)
+        if (memcmp(cd[(size_t)s].T, cd[(size_t)win].T, sizeof(cd[0].T)) != 0 && (second < 0 || cd[(size_t)s].cost < second)) second = cd[(size_t)s].cost;
+    rc = registration_chain(h, ref, &P.fine, cd[(size_t)win].T, true, rows, row_cap, &st.fine);
+    if (rc) return rc;
+    st.queries = (size_t)nq; st.shift = shift; st.candidates = K; st.winner = win;
+    st.winner_cost = cd[(size_t)win].cost; st.second_cost = second;
+    if (stats) *stats = st;
+    const size_t k = std::min(cand_cap, (size_t)K);
+    if (cands && k) memcpy(cands, cd.data(), k * sizeof(ppp_registration_candidate));
+    return PPP_OK;
+}
+
+/* [own_lo, own_hi) widened by r with room for the roundings (B.82): r times the 1.0001 of the margin tests, which covers the
+   float product dx dx against r r, and one float further out, which covers the rounding of the sum itself -- at coordinates of
+   metres half an ulp is more than r / 10 000.  An empty interval stays empty. */
+static void widened(const TileRange &T, float r, float &lo, float &hi)
+{
+    lo = nextafterf(T.own_lo - r * 1.0001f, -INFINITY); hi = nextafterf(T.own_hi + r * 1.0001f, INFINITY);
+}
+
+/* the slabs [b0, b1) a handle's index sorted: all of them, or those of a slice-range handle's interval (slab_geom) */
+static void sorted_slabs(const ppp_handle s, int &b0, int &b1)
+{
+    const SlabGeom G = slab_geom(s);
+    b0 = G.first_slab; b1 = std::min(s->B, G.first_slab + G.g_sort);
+}
+
+/* The deviation map of the points h owns: both plans, the range checks on the host, both indices, then the
+   reference's normal field on its own stream, one wait for that stream, k_devt_fill, k_devt_nearest, k_devt_smooth where asked and
+   k_devt_target back to back on the scan's stream, and one wait.  The buffers are ppp_get_deviation's: nothing is kept. */
+int ppp_get_deviation_tile(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, float halo, double *deviation, double *smoothed,
+                           int *ref_index, unsigned char *status, double *target, unsigned char *owned, size_t cap,
+                           ppp_deviation_tile_stats *part)
+{
+    int rc = deviation_call_ok(h, ref, dp, "deviation tile", &halo);
+    if (rc) return rc;
+    const ppp_deviation_params P = *dp;
+    const bool smooth = P.smooth_radius > 0.f;
+    rc = deviation_side_cloud(h, ref, "deviation tile: the reference", true);
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side_cloud(h, h, "deviation tile: the scan", true); if (rc) return rc; }
+    const size_t N = h->n;
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "deviation tile: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    /* From the two plans alone, before an index is built or a kernel launched.  What is evaluated: the owned interval widened by
+       smooth_radius.  What the reference must index: the owned interval widened by halo, and by its normal_radius beyond that --
+       the normal of a partner at the halo's edge reads that neighbourhood. */
+    TileRange T;
+    rc = tile_range(h, 0.f, T);
+    if (rc) return rc;
+    widened(T, P.smooth_radius, T.ev_lo, T.ev_hi);
+    if (leaves_indexed_range(h, T.ev_lo, T.ev_hi))
+        return fail(h, PPP_ERR_ARG, "deviation tile: the owned interval widened by smooth_radius reaches beyond the scan's indexed slice range: raise range_margin");
+    float need_lo, need_hi;
+    widened(T, halo + ref->P.normal_radius, need_lo, need_hi);
+    if (leaves_indexed_range(ref, need_lo, need_hi))
+        return fail(h, PPP_ERR_ARG, "deviation tile: the reference's indexed slice range does not cover the owned interval widened by halo + normal_radius");
+    rc = deviation_side_index(h, ref, "deviation tile: the reference", false);
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side_index(h, h, "deviation tile: the scan", false); if (rc) return rc; }
+    rc = reference_normals(h, ref, "deviation tile");
+    if (rc) return rc;
+    int pos0, pos1, hb0, hb1, rb0, rb1;
+    rc = tile_positions(h, T, pos0, pos1);
+    if (rc) return rc;
+    sorted_slabs(h, hb0, hb1); sorted_slabs(ref, rb0, rb1);
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.owned.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEVT_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    const size_t cap_grid = 2 * (size_t)h->num_cus;
+    LAUNCH(h, "k_devt_fill", k_devt_fill, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, cap_grid), DEV_T, 0, (int)N, D.dev.p,
+           smooth ? D.smoothed.p : nullptr, D.target.p, D.ref_index.p, D.status.p, D.owned.p);
+    if (pos1 > pos0) {
+        const size_t gq = ((size_t)(pos1 - pos0) + DEV_T - 1) / DEV_T;
+        LAUNCH(h, "k_devt_nearest", k_devt_nearest, (unsigned)gq, DEV_T, 0, h->sorted4.p, pos0, pos1, T, contact_index(ref), ref->hmeta.n_sorted,
+               rb0, rb1, P.max_dist * P.max_dist, D.dev.p, D.fix.p, D.d2.p, D.ref_index.p, D.status.p, D.owned.p);
+        if (smooth)
+            LAUNCH(h, "k_devt_smooth", k_devt_smooth, (unsigned)gq, DEV_T, 0, contact_index(h), pos0, pos1, T, hb0, hb1,
+                   P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p, D.smoothed.p);
+        LAUNCH(h, "k_devt_target", k_devt_target, (unsigned)std::min(gq, cap_grid), DEV_T, 0, h->sorted4.p, pos0, pos1, T, D.status.p, D.dev.p, v,
+               D.d2.p, D.ref_index.p, P.allowance, P.gain, D.target.p, D.acc.p);
+    }
+    unsigned long long acc[DEVT_ACC_WORDS];
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    const unsigned long long own = acc[0] + acc[1] + acc[2];
+    if (own + acc[DEVT_ACC_HALO] > (unsigned long long)(pos1 - pos0) || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
+        return fail(h, PPP_ERR_HIP, "deviation tile: statistics corrupt");
+    if (part) {
+        ppp_deviation_tile_stats st = {};
+        dev_stats_words(st, N, acc);
+        st.owned = (size_t)own; st.evaluated = (size_t)(own + acc[DEVT_ACC_HALO]);
+        if (st.matched) st.fix_sum = (long long)acc[DEV_ACC_FIXSUM];
+        st.own_lo = T.own_lo; st.own_hi = T.own_hi;
+        st.sum_parts = MapParts(h, N).grid;
+        *part = st;
+    }
+    return deviation_copy_out(h, std::min(cap, N), v, deviation, smoothed, ref_index, status, target, owned);
+}
+
+/* The merge of ppp_get_deviation_tile's parts (host only).  The integer fields add and fold; hist needs the global span, and
+   rms_dev / target_sum are ppp_get_deviation's fixed-order sums (B.46: k_dev_stats's partition into sum_parts contiguous parts
+   of the map, inside a part every one of PCON_T threads its strided share in index order, block_tree_sum's tree over the
+   threads, the parts in order), which no per-tile number can give: they are computed here from the union of the owned entries. */
+int ppp_merge_deviation_tiles(size_t tiles, const ppp_deviation_tile_stats *parts, const double *const *v, const unsigned char *const *status,
+                              const double *const *target, const unsigned char *const *owned, ppp_deviation_stats *stats)
+{
+    if (!tiles || !parts || !v || !status || !target || !owned || !stats) return PPP_ERR_ARG;
+    const size_t N = parts[0].n;
+    const int grid = parts[0].sum_parts;
+    if (N > 0x7fffffffu || grid < 1 || (size_t)grid > std::max<size_t>(1, (N + PCON_T - 1) / PCON_T)) return PPP_ERR_ARG;
+    ppp_deviation_stats st = {};
+    unsigned long long knmin = 0, kmax = 0, fsum = 0;
+    unsigned kd2 = 0;
+    std::vector<int> owner(N, -1); /* who owns a point: the one tile whose owned map marks it */
+    size_t all_owned = 0;
+    for (size_t t = 0; t < tiles; ++t) {
+        const ppp_deviation_tile_stats &p = parts[t];
+        if (p.n != N || p.sum_parts != grid || (N && (!v[t] || !status[t] || !target[t] || !owned[t]))) return PPP_ERR_ARG;
+        if (p.matched + p.too_far + p.no_normal != p.owned || p.proud > p.matched || p.below > p.matched) return PPP_ERR_ARG;
+        size_t mine = 0, matched = 0;
+        for (size_t i = 0; i < N; ++i) {
+            if (!owned[t][i]) continue;
+            if (owner[i] >= 0) return PPP_ERR_ARG; /* owned twice */
+            owner[i] = (int)t;
+            ++mine; matched += status[t][i] == PPP_DEV_MATCHED;
+        }
+        if (mine != p.owned || matched != p.matched) return PPP_ERR_ARG; /* the part is not the maps' */
+        all_owned += mine;
+        st.matched += p.matched; st.too_far += p.too_far; st.no_normal += p.no_normal; st.proud += p.proud; st.below += p.below;
+        if (p.matched) {
+            knmin = std::max(knmin, ordered_key64(-p.min_dev)); kmax = std::max(kmax, ordered_key64(p.max_dev));
+            fsum += (unsigned long long)p.fix_sum;
+            kd2 = std::max(kd2, ordered_key(p.max_dist2));
+        }
+    }
+    st.n = N; st.dropped = N - all_owned; /* nobody's points: the non-finite ones */
+    st.min_dev = st.max_dev = st.mean_dev = st.rms_dev = (double)NAN; st.max_dist2 = NAN;
+    double span = 0.0;
+    if (st.matched) {
+        st.min_dev = -ordered_unkey64(knmin); st.max_dev = ordered_unkey64(kmax);
+        st.mean_dev = (double)(long long)fsum / (double)st.matched * (1.0 / DEV_FIXED);
+        st.max_dist2 = ordered_unkey(kd2);
+        span = fmax(fabs(st.min_dev), fabs(st.max_dev));
+    }
+    const size_t per = (N + (size_t)grid - 1) / (size_t)grid;
+    std::vector<double> s_sq(PCON_T), s_tg(PCON_T);
+    double sq_all = 0.0;
+    for (size_t g = 0; g < (size_t)grid; ++g) {
+        const size_t i0 = g * per, i1 = std::min(N, i0 + per);
+        for (size_t t = 0; t < PCON_T; ++t) {
+            double sq = 0.0, tg = 0.0;
+            for (size_t i = i0 + t; i < i1; i += PCON_T) {
+                if (owner[i] < 0 || status[(size_t)owner[i]][i] != PPP_DEV_MATCHED) continue;
+                const double x = v[(size_t)owner[i]][i];
+                sq += x * x; tg += target[(size_t)owner[i]][i];
+                ++st.hist[dev_bin(x, span)];
+            }
+            s_sq[t] = sq; s_tg[t] = tg;
+        }
+        for (size_t o = PCON_T / 2; o > 0; o >>= 1)
+            for (size_t t = 0; t < o; ++t) { s_sq[t] += s_sq[t + o]; s_tg[t] += s_tg[t + o]; }
+        sq_all += s_sq[0]; st.target_sum += s_tg[0];
+    }
+    if (st.matched) st.rms_dev = std::sqrt(sq_all / (double)st.matched);
+    *stats = st;
+    return PPP_OK;
+}
+
+/* ---- registration of a scan held as slice-range tiles ---- */
+
+/* one tile of a call: the scan's handle, its reference, and what k_regt_terms is launched with */
+struct RegtTile {
+    ppp_handle h = nullptr, ref = nullptr;
+    TileRange own;
+    RegtNeed need;
+    int pos0 = 0, pos1 = 0, rb0 = 0, rb1 = 0, nref = 0;
+    unsigned grid = 1;
+    ppp_registration_part part;
+};
+
+/* the tile's pinned memory: REGT_WORDS words coming back, then the 12 doubles of T going out */
+static double *regt_pinned_T(const RegtTile &t) { return reinterpret_cast<double *>(t.h->registration.tpin.p + REGT_WORDS); }
+
+/* What a tile needs before its first evaluation: the checks (B.72's, a part handle), both plans, both indices -- the
+   reference's index and normal field only where build_ref says so: a handle that stands in several slots is built once --, the
+   frame and the shift of the WHOLE clouds (B.90), the positions, the reference's sorted slabs and indexed interval, the
+   buffers, and the frame on the device. */
+static int regt_prepare(RegtTile &t, const ppp_registration_params &P, IcpFrame F, bool build_ref)
+{
+    ppp_handle h = t.h, ref = t.ref;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, "registration tile: the tile and its reference are on different devices");
+    int rc = deviation_side_cloud(h, ref, "registration tile: the reference", true);
+    if (rc) return rc;
+    if (ref != h) { rc = deviation_side_cloud(h, h, "registration tile: the scan", true); if (rc) return rc; }
+    int shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "registration tile: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    rc = tile_range(h, 0.f, t.own);
+    if (rc) return rc;
+    if (build_ref) { rc = deviation_side_index(h, ref, "registration tile: the reference", false); if (rc) return rc; }
+    if (ref != h) { rc = deviation_side_index(h, h, "registration tile: the scan", false); if (rc) return rc; }
+    /* B.90: the whole reference's bounds.  A whole-cloud handle answers ppp_minmax with them (registration_setup reads the same
+       block); a range handle's launches see its part only and are handed the whole cloud's bounds cached with its plan: those */
+    if (!ref->ranged) {
+        rc = fetch_meta(ref);
+        if (rc) return ref == h ? rc : fail(h, rc, std::string("registration tile: the reference: ") + ref->err);
+    }
+    frame_from_bounds(ref->ranged ? ref->h_mn : ref->hmeta.mn, ref->ranged ? ref->h_mx : ref->hmeta.mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    if (build_ref) { rc = reference_normals(h, ref, "registration tile"); if (rc) return rc; }
+    rc = tile_positions(h, t.own, t.pos0, t.pos1);
+    if (rc) return rc;
+    sorted_slabs(ref, t.rb0, t.rb1);
+    t.nref = ref->hmeta.n_sorted;
+    t.need = RegtNeed{ref->incl_lo, ref->incl_hi, 1.0001f * (P.max_dist + ref->P.normal_radius), ref->ranged && ref->incl_lo > ref->h_mn[0],
+                      ref->ranged && ref->incl_hi < ref->h_mx[0]};
+    t.grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)(t.pos1 - t.pos0) + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
+    ppp_registration_part &p = t.part;
+    p = ppp_registration_part{};
+    p.evaluated = (size_t)(t.pos1 - t.pos0);
+    p.own_lo = t.own.own_lo; p.own_hi = t.own.own_hi;
+    p.n = h->n; p.shift = shift;
+    for (int d = 0; d < 3; ++d) p.centre[d] = F.c[d];
+    p.length = F.Ln;
+    auto &G = h->registration;
+    HIPCHK(h, G.T.ensure(12)); HIPCHK(h, G.acc.ensure(REGT_WORDS)); HIPCHK(h, G.tframe.ensure(1)); HIPCHK(h, G.tpin.ensure(REGT_WORDS + 12));
+    HIPCHK(h, copy_sync(h, G.tframe.p, &F, sizeof(F), hipMemcpyHostToDevice));
+    return PPP_OK;
+}
+
+/* one evaluation of a tile at T, enqueued on its handle's stream: T to the device, the words cleared, k_regt_terms, the words
+   back to pinned memory.  Nobody waits here. */
+static int regt_enqueue(RegtTile &t, const double *T)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, REGT_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_regt_terms", k_regt_terms, t.grid, ICP_T, 0, h->sorted4.p, t.pos0, t.pos1, t.own, contact_index(t.ref), t.nref, t.rb0, t.rb1, t.need,
+               G.tframe.p, G.T.p, G.acc.p);
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, REGT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the wait for what a tile's stream holds */
+static int regt_wait(RegtTile &t)
+{
+    HIPCHK(t.h, hipSetDevice(t.h->device));
+    HIPCHK(t.h, hipStreamSynchronize(t.h->stream));
+    return PPP_OK;
+}
+
+/* the refusal of an evaluation whose moved queries left what the reference indexes (B.89); w: the call's name */
+static std::string regt_refusal(const char *w, unsigned long long queries)
+{
+    return std::string(w) + ": " + std::to_string(queries) + " moved queries reach beyond the reference's indexed slice range "
+           "(max_dist + normal_radius around the moved point): raise range_margin of the reference's handle";
+}
+
+/* the wait for a tile's evaluation, and its row: the refusal (B.89), the words' sanity, the terms */
+static int regt_collect(RegtTile &t, const double *T, ppp_registration_row *row)
+{
+    ppp_handle h = t.h;
+    int rc = regt_wait(t);
+    if (rc) return rc;
+    const unsigned long long *w = h->registration.tpin.p;
+    if (w[REGT_REFUSED]) return fail(h, PPP_ERR_CAPACITY, regt_refusal("registration tile", w[REGT_REFUSED]));
+    if (w[REGT_OWNED] > (unsigned long long)(t.pos1 - t.pos0) || w[ICP_PAIRS] > w[REGT_OWNED]) return fail(h, PPP_ERR_HIP, "registration tile: sums corrupt");
+    t.part.owned = (size_t)w[REGT_OWNED];
+    *row = ppp_registration_row{};
+    icp_row_terms(row, T, w);
+    return PPP_OK;
+}
+
+/* the checks every tiled call makes before it looks at a handle: the parameters and the transform (errors on h) */
+static int regt_call_ok(ppp_handle h, const ppp_registration_params *rp, const double *T0, IcpFrame &F, double *T)
+{
+    if (!h) return PPP_ERR_ARG;
+    if (!rp) return fail(h, PPP_ERR_ARG, "registration tile: no parameters");
+    const int rc = registration_params_ok(h, *rp, F);
+    return rc ? rc : opening_transform(h, "registration tile", T0, T);
+}
+
+int ppp_get_registration_terms_tile(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                                    ppp_registration_part *part)
+{
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h, rp, T12, F, T);
+    if (rc) return rc;
+    if (!ref) return fail(h, PPP_ERR_ARG, "registration tile: no reference handle");
+    RegtTile t;
+    t.h = h; t.ref = ref;
+    rc = regt_prepare(t, *rp, F, true);
+    if (rc) return rc;
+    rc = regt_enqueue(t, T);
+    if (rc) return rc;
+    ppp_registration_row r;
+    rc = regt_collect(t, T, &r);
+    if (rc) return rc;
+    if (row) *row = r;
+    if (part) *part = t.part;
+    return PPP_OK;
+}
+
+int ppp_merge_registration_terms(const ppp_registration_row *rows, const ppp_registration_part *parts, size_t count, const double *T12,
+                                 ppp_registration_row *out_row, ppp_registration_part *out_part)
+{
+    if (!rows || !parts || !count || !out_row) return PPP_ERR_ARG;
+    std::vector<size_t> by_lo;
+    for (size_t i = 0; i < count; ++i) {
+        if (!regt_same_frame(parts[i], parts[0])) return PPP_ERR_ARG;
+        if (parts[i].own_lo < parts[i].own_hi) by_lo.push_back(i); /* (an empty interval, or one with a NaN, overlaps nothing) */
+    }
+    std::sort(by_lo.begin(), by_lo.end(), [&](size_t a, size_t b) { return parts[a].own_lo < parts[b].own_lo; });
+    for (size_t k = 1; k < by_lo.size(); ++k)
+        if (parts[by_lo[k]].own_lo < parts[by_lo[k - 1]].own_hi) return PPP_ERR_ARG; /* half-open: equal ends meet */
+    unsigned long long acc[ICP_WORDS] = {};
+    ppp_registration_part m = parts[0];
+    m.owned = m.evaluated = 0; m.own_lo = INFINITY; m.own_hi = -INFINITY;
+    for (size_t i = 0; i < count; ++i) {
+        const ppp_registration_row &r = rows[i];
+        acc[ICP_PAIRS] += (unsigned long long)r.pairs;
+        for (int w = 0; w < 21; ++w) acc[ICP_A + w] += (unsigned long long)r.A[w];
+        for (int w = 0; w < 6; ++w) acc[ICP_B + w] += (unsigned long long)r.b[w];
+        acc[ICP_E] += (unsigned long long)r.E;
+        m.owned += parts[i].owned; m.evaluated += parts[i].evaluated;
+        if (parts[i].own_lo < parts[i].own_hi) { m.own_lo = std::min(m.own_lo, parts[i].own_lo); m.own_hi = std::max(m.own_hi, parts[i].own_hi); }
+    }
+    *out_row = ppp_registration_row{};
+    icp_row_terms(out_row, T12 ? T12 : ICP_IDENTITY, acc);
+    if (out_part) *out_part = m;
+    return PPP_OK;
+}
+
+int ppp_registration_step(const ppp_registration_row *row, const ppp_registration_part *part, double lock_eps, const double *T12, double *T12_out,
+                          int *locked, double *step2)
+{
+    if (!row || !part || !T12_out || !(lock_eps > 0.0 && lock_eps < 1.0) || !(part->length > 0.0 && part->length < INFINITY)) return PPP_ERR_ARG;
+    double T[12], Tn[12];
+    memcpy(T, T12 ? T12 : row->T, sizeof(T));
+    memcpy(Tn, T, sizeof(Tn));
+    int mask;
+    double s2;
+    const int rc = regt_step(*row, part->centre, part->length, lock_eps, T, Tn, &mask, &s2);
+    memcpy(T12_out, Tn, sizeof(Tn));
+    if (locked) *locked = mask;
+    if (step2) *step2 = s2;
+    return rc;
+}
+
+/* a tiled loop's call: its name in the messages, where a failing tile's slot goes, the tiles, their rows and parts of the evaluation at hand and the whole they merge to */
+struct RegtCall {
+    const char *what;
+    ppp_register_tiles_stats *stats;
+    std::vector<RegtTile> tiles;
+    std::vector<ppp_registration_row> part_rows;
+    std::vector<ppp_registration_part> parts;
+    ppp_registration_part whole;
+    int failed(size_t i, int code) const { if (stats) stats->failed_tile = (int)i; return code; }
+};
+
+/* The opening of a tiled loop behind its parameters' checks (errors on the first handle): rows that are missing, the handles,
+   and every tile prepared, with `also`, the call's own step per tile, behind regt_prepare */
+static int regt_open(RegtCall &call, const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params &P, const IcpFrame &F,
+                     bool rows_missing, const std::function<int(RegtTile &, size_t)> &also = nullptr)
+{
+    ppp_handle h0 = hs[0];
+    const std::string w(call.what);
+    if (rows_missing) return fail(h0, PPP_ERR_ARG, w + ": rows is NULL with row_cap > 0");
+    for (size_t i = 0; i < count; ++i) {
+        if (!hs[i] || !refs[i]) return fail(h0, PPP_ERR_ARG, w + ": a NULL handle");
+        for (size_t k = 0; k < i; ++k) if (hs[k] == hs[i]) return fail(h0, PPP_ERR_ARG, w + ": a scan handle stands in two slots");
+    }
+    call.tiles.assign(count, RegtTile()); call.part_rows.resize(count); call.parts.resize(count);
+    for (size_t i = 0; i < count; ++i) {
+        RegtTile &t = call.tiles[i];
+        t.h = hs[i]; t.ref = refs[i];
+        bool first = true; /* the reference's index and normal field: once per reference handle */
+        for (size_t k = 0; k < i; ++k) first = first && refs[k] != refs[i];
+        int rc = regt_prepare(t, P, F, first);
+        if (!rc && also) rc = also(t, i);
+        if (rc) return call.failed(i, rc);
+    }
+    return PPP_OK;
+}
+
+/* One pass over the tiles: `enqueue` on every tile's stream, then every tile waited for (`wait`, the tile and its slot, where
+   the wait does more than regt_wait), whatever an earlier one answered; the first error is the call's */
+static int regt_pass(RegtCall &call, const std::function<int(RegtTile &)> &enqueue, const std::function<int(RegtTile &, size_t)> &wait = nullptr)
+{
+    for (size_t i = 0; i < call.tiles.size(); ++i) { const int e = enqueue(call.tiles[i]); if (e) return call.failed(i, e); }
+    int first_rc = PPP_OK;
+    for (size_t i = 0; i < call.tiles.size(); ++i) {
+        const int e = wait ? wait(call.tiles[i], i) : regt_wait(call.tiles[i]);
+        if (e && !first_rc) first_rc = call.failed(i, e);
+    }
+    return first_rc;
+}
+
+/* the tiles' rows of one evaluation at T as the whole cloud's (B.91), with the checks the loops make of it */
+static int regt_merged(ppp_handle h0, RegtCall &call, const double *T, ppp_registration_row &rw)
+{
+    const int rc = ppp_merge_registration_terms(call.part_rows.data(), call.parts.data(), call.parts.size(), T, &rw, &call.whole);
+    if (rc) return fail(h0, rc, "registration tiles: the tiles' ranges overlap, or the tiles do not hold one scan against one reference");
+    if (rw.pairs > call.whole.owned) return fail(h0, PPP_ERR_HIP, "registration tiles: sums corrupt");
+    return PPP_OK;
+}
+
+/* The tiled loop (B.93): ppp_register's chain with the host in the place of k_reg_step (regt_loop); an evaluation is one
+   k_regt_terms per tile and one wait per tile. */
+int ppp_register_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_registration_params *rp, const double *T0_12,
+                       ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !refs || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, rp, T0_12, F, T);
+    if (rc) return rc;
+    const ppp_registration_params P = *rp;
+    RegtCall call = {"registration tiles", stats};
+    rc = regt_open(call, hs, refs, count, P, F, !rows && row_cap);
+    if (rc) return rc;
+    std::vector<ppp_registration_row> R;
+    IcpCtl C = {};
+    rc = regt_loop(P, F, T, R, C, call.whole, [&](int, ppp_registration_row &rw) {
+        const int e = regt_pass(call, [&](RegtTile &t) { return regt_enqueue(t, T); }, [&](RegtTile &t, size_t i) {
+            const int ec = regt_collect(t, T, &call.part_rows[i]);
+            call.parts[i] = t.part;
+            return ec;
+        });
+        return e ? e : regt_merged(h0, call, T, rw);
+    });
+    if (rc) return rc;
+    if (stats) stats->reg = registration_stats(R, C, call.whole.n, call.whole.owned, call.whole.shift, call.whole.centre, call.whole.length);
+    const size_t k = std::min(row_cap, (size_t)C.steps + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    return PPP_OK;
+}
+
+/* ---- trimmed registration of a scan held as slice-range tiles ---- */
+
+int ppp_trim_select(const unsigned int *hist, size_t bins, size_t rank, unsigned int *bin, size_t *rank_in_bin)
+{
+    if (!hist || !bin || !rank_in_bin) return PPP_ERR_ARG;
+    *bin = 0; *rank_in_bin = 0;
+    size_t below = 0;
+    for (size_t b = 0; rank && b < bins; ++b) {
+        if (rank <= below + hist[b]) { *bin = (unsigned)b; *rank_in_bin = rank - below; break; } /* (rank > below: no earlier bin reached it) */
+        below += hist[b];
+    }
+    return PPP_OK;
+}
+
+size_t ppp_trim_rank(double keep, size_t paired) { return trim_rank(keep, paired); }
+
+/* a tile's pinned memory behind ppp_register_tiles' (the words back, T out): one word going out -- the merged prefix, then tau --
+   and the block coming back: the two words and a histogram of at most TRIM_B0 bins */
+static unsigned *trimt_pinned_word(const RegtTile &t) { return reinterpret_cast<unsigned *>(t.h->registration.tpin.p + REGT_WORDS + 12); }
+static unsigned *trimt_pinned_hist(const RegtTile &t) { return reinterpret_cast<unsigned *>(t.h->registration.tpin.p + REGT_WORDS + 13); }
+static const size_t TRIMT_PIN_WORDS = REGT_WORDS + 13 + (TRIMT_HEAD + TRIM_B0) / 2;
+static int trimt_positions(const RegtTile &t) { return t.pos1 - t.pos0; }
+
+/* the buffers of a tile behind regt_prepare: partner and key per position, the two words and the three histograms, the word
+   the host writes, and where the caller wants a map of this tile, status | owned and d2 by cloud index */
+static int trimt_prepare(RegtTile &t, bool maps)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t np = std::max<size_t>((size_t)trimt_positions(t), 1), N1 = std::max<size_t>(h->n, 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, G.partner.ensure(np)); HIPCHK(h, G.key.ensure(np)); HIPCHK(h, G.hist.ensure(TRIMT_HEAD + TRIM_WORDS)); HIPCHK(h, G.cuts.ensure(2));
+    HIPCHK(h, G.tpin.ensure(TRIMT_PIN_WORDS));
+    if (maps) { HIPCHK(h, G.tstatus.ensure(2 * N1)); HIPCHK(h, G.td2.ensure(N1)); }
+    return PPP_OK;
+}
+
+/* the first pass of an evaluation at T, enqueued on the tile's stream: T to the device, the histograms and the words cleared,
+   k_trimt_pair, the two words and the top digits' histogram back to pinned memory.  Nobody waits here. */
+static int trimt_enqueue_pair(RegtTile &t, const double *T)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.hist.p, 0, (TRIMT_HEAD + TRIM_WORDS) * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_pair", k_trimt_pair, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, t.own, contact_index(t.ref), t.nref, t.rb0, t.rb1, t.need,
+               G.tframe.p, G.T.p, G.partner.p, G.key.p, G.hist.p);
+    HIPCHK(h, hipMemcpyAsync(trimt_pinned_hist(t), G.hist.p, (TRIMT_HEAD + TRIM_B0) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* pass 1 or 2: the merged prefix to the device, k_trimt_narrow over the stored keys, that digit's histogram back */
+static int trimt_enqueue_narrow(RegtTile &t, int pass, unsigned prefix)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned *next = G.hist.p + TRIMT_HEAD + (pass == 1 ? TRIM_B0 : TRIM_B0 + TRIM_B1);
+    *trimt_pinned_word(t) = prefix;
+    HIPCHK(h, hipMemcpyAsync(G.cuts.p, trimt_pinned_word(t), sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (t.pos1 > t.pos0) {
+        if (pass == 1) LAUNCH(h, "k_trimt_narrow<1>", k_trimt_narrow<1>, t.grid, TRIM_T, 0, G.key.p, trimt_positions(t), G.cuts.p, next);
+        else LAUNCH(h, "k_trimt_narrow<2>", k_trimt_narrow<2>, t.grid, TRIM_T, 0, G.key.p, trimt_positions(t), G.cuts.p, next);
+    }
+    HIPCHK(h, hipMemcpyAsync(trimt_pinned_hist(t), next, (pass == 1 ? TRIM_B1 : TRIM_B2) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the sums: tau to the device, k_trimt_terms, the 29 words back */
+static int trimt_enqueue_terms(RegtTile &t, unsigned tau)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    *trimt_pinned_word(t) = tau;
+    HIPCHK(h, hipMemcpyAsync(G.cuts.p, trimt_pinned_word(t), sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_terms", k_trimt_terms, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, contact_index(t.ref), G.tframe.p, G.T.p, G.partner.p,
+               G.key.p, G.cuts.p, G.acc.p);
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, ICP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* behind the loop: the tile's maps filled with DROPPED / NaN / 0, then k_trimt_scatter over the keys the last evaluation left */
+static int trimt_enqueue_scatter(RegtTile &t, unsigned tau, bool none)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t N1 = std::max<size_t>(h->n, 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemsetAsync(G.tstatus.p, PPP_TRIM_DROPPED, N1, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.tstatus.p + N1, 0, N1, h->stream));
+    HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(G.td2.p), (int)TRIM_NAN, N1, h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_trimt_scatter", k_trimt_scatter, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, G.key.p, tau, none ? 1 : 0, (int)N1, G.tstatus.p,
+               G.td2.p, G.tstatus.p + N1);
+    return PPP_OK;
+}
+
+/* the first min(cap, n) entries of the maps the caller gave for this tile (each copy waits for the tile's stream) */
+static int trimt_copy_maps(RegtTile &t, unsigned char *status, float *d2, unsigned char *owned, size_t cap)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t N1 = std::max<size_t>(h->n, 1), m = std::min(cap, h->n);
+    if (!m || !(status || d2 || owned)) return PPP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (status) HIPCHK(h, copy_sync(h, status, G.tstatus.p, m, hipMemcpyDeviceToHost));
+    if (d2) HIPCHK(h, copy_sync(h, d2, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
+    if (owned) HIPCHK(h, copy_sync(h, owned, G.tstatus.p + N1, m, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The tiled trimmed loop (B.97-B.99): regt_loop, an evaluation being four passes over the tiles -- k_trimt_pair,
+   k_trimt_narrow<1>, k_trimt_narrow<2>, k_trimt_terms --, each enqueued on every tile's stream and waited for tile by tile; between
+   them the host adds the tiles' histograms, selects the digit on the sum (ppp_trim_select) and sends the next pass the merged
+   prefix, or tau.  An evaluation that finds no pair in any tile ends behind its first pass. */
+int ppp_register_trimmed_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_trimmed_registration_params *tp, const double *T0_12,
+                               ppp_trimmed_registration_row *rows, size_t row_cap, unsigned char *const *status, float *const *d2,
+                               unsigned char *const *owned, size_t cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !refs || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    if (!tp) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: no parameters");
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, &tp->icp, T0_12, F, T);
+    if (rc) return rc;
+    const double keep = tp->keep;
+    if (!(keep > 0.0 && keep <= 1.0)) return fail(h0, PPP_ERR_ARG, "trimmed registration tiles: keep must be in (0, 1]");
+    const ppp_registration_params P = tp->icp;
+    auto map_of = [&](auto *const *maps, size_t i) { return maps ? maps[i] : nullptr; };
+    auto wants_maps = [&](size_t i) { return map_of(status, i) || map_of(d2, i) || map_of(owned, i); };
+    RegtCall call = {"trimmed registration tiles", stats};
+    rc = regt_open(call, hs, refs, count, P, F, !rows && row_cap, [&](RegtTile &t, size_t i) { return trimt_prepare(t, wants_maps(i)); });
+    if (rc) return rc;
+    std::vector<RegtTile> &tiles = call.tiles;
+    /* the tiles' histograms of `bins` bins, behind the wait, added bin by bin: a bin's sum is at most the scan's points */
+    std::vector<unsigned> H(TRIM_B0);
+    auto merge_hist = [&](size_t skip, size_t bins) {
+        std::fill(H.begin(), H.end(), 0u);
+        for (size_t i = 0; i < count; ++i) {
+            const unsigned *w = trimt_pinned_hist(tiles[i]) + skip;
+            for (size_t b = 0; b < bins; ++b) H[b] += w[b];
+        }
+    };
+    struct Cut { size_t paired; unsigned tau; };
+    std::vector<Cut> cuts;
+    std::vector<ppp_registration_row> R;
+    IcpCtl C = {};
+    rc = regt_loop(P, F, T, R, C, call.whole, [&](int, ppp_registration_row &rw) {
+        int e = regt_pass(call, [&](RegtTile &t) { return trimt_enqueue_pair(t, T); });
+        if (e) return e;
+        size_t paired = 0;
+        for (size_t i = 0; i < count; ++i) {
+            RegtTile &t = tiles[i];
+            const unsigned *w = trimt_pinned_hist(t);
+            if (w[TRIMT_REFUSED]) return call.failed(i, fail(t.h, PPP_ERR_CAPACITY, regt_refusal(call.what, w[TRIMT_REFUSED])));
+            size_t mine = 0;
+            for (size_t b = 0; b < TRIM_B0; ++b) mine += w[TRIMT_HEAD + b];
+            if (w[TRIMT_OWNED] > (unsigned)trimt_positions(t) || mine > w[TRIMT_OWNED]) return call.failed(i, fail(t.h, PPP_ERR_HIP, "trimmed registration tiles: histogram corrupt"));
+            t.part.owned = w[TRIMT_OWNED];
+            call.parts[i] = t.part;
+            call.part_rows[i] = ppp_registration_row{};
+            paired += mine;
+        }
+        Cut cut = {paired, TRIM_NAN};
+        if (paired) { /* B.78 on the merged histograms; without a pair the evaluation ends here: kept 0, no sums */
+            merge_hist(TRIMT_HEAD, TRIM_B0);
+            unsigned bin, prefix;
+            size_t rank;
+            ppp_trim_select(H.data(), TRIM_B0, trim_rank(keep, paired), &bin, &rank);
+            if (!rank) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+            prefix = bin << 21;
+            for (int pass = 1; pass <= 2; ++pass) {
+                const size_t bins = pass == 1 ? TRIM_B1 : TRIM_B2;
+                e = regt_pass(call, [&](RegtTile &t) { return trimt_enqueue_narrow(t, pass, prefix); });
+                if (e) return e;
+                merge_hist(0, bins);
+                ppp_trim_select(H.data(), bins, rank, &bin, &rank);
+                if (!rank) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+                prefix |= pass == 1 ? bin << 10 : bin;
+            }
+            cut.tau = prefix;
+            e = regt_pass(call, [&](RegtTile &t) { return trimt_enqueue_terms(t, cut.tau); });
+            if (e) return e;
+            for (size_t i = 0; i < count; ++i) {
+                const unsigned long long *w = tiles[i].h->registration.tpin.p;
+                if (w[ICP_PAIRS] > call.parts[i].owned) return call.failed(i, fail(tiles[i].h, PPP_ERR_HIP, "trimmed registration tiles: sums corrupt"));
+                icp_row_terms(&call.part_rows[i], T, w);
+            }
+        }
+        e = regt_merged(h0, call, T, rw);
+        if (e) return e;
+        if (rw.pairs > paired || (paired && rw.pairs < trim_rank(keep, paired))) return fail(h0, PPP_ERR_HIP, "trimmed registration tiles: cut corrupt");
+        cuts.push_back(cut);
+        return (int)PPP_OK;
+    });
+    if (rc) return rc;
+    const size_t last = (size_t)C.steps;
+    /* B.99: the maps of the last evaluation -- its keys are the ones the tiles hold --, every tile's launch before any copy */
+    for (size_t i = 0; i < count; ++i)
+        if (wants_maps(i)) {
+            rc = trimt_enqueue_scatter(tiles[i], cuts[last].tau, cuts[last].paired == 0);
+            if (rc) return call.failed(i, rc);
+        }
+    for (size_t i = 0; i < count; ++i) {
+        rc = trimt_copy_maps(tiles[i], map_of(status, i), map_of(d2, i), map_of(owned, i), cap);
+        if (rc) return call.failed(i, rc);
+    }
+    if (stats) stats->reg = registration_stats(R, C, call.whole.n, call.whole.owned, call.whole.shift, call.whole.centre, call.whole.length);
+    const size_t k = std::min(row_cap, last + 1);
+    for (size_t i = 0; rows && i < k; ++i) trimmed_row(rows[i], R[i], cuts[i].paired, cuts[i].tau);
+    return PPP_OK;
+}
+
+} // extern "C"

@@ -174,9 +174,11 @@ def test_the_library_is_built_without_contraction():
     mk = open(os.path.join(ROOT, "polishpathplanning_amd", "csrc", "Makefile")).read()
     flags = [l for l in mk.splitlines() if l.startswith("HIPFLAGS")]
     assert len(flags) == 1 and "-ffp-contract=off" in flags[0]
-    assert "ppp_contact" in [l for l in mk.splitlines() if l.startswith("UNITS")][0]
-    assert not any(l.startswith("ppp_contact.o: HIPFLAGS") for l in mk.splitlines())
-    assert "ppp_registration_tile.h" in [l for l in mk.splitlines() if l.startswith("CONTACT_HDR")][0]
+    units = [l for l in mk.splitlines() if l.startswith("UNITS")][0].split()
+    for unit in ("ppp_scan", "ppp_contact"):  # (the contact unit's removal and dwell code is host-and-device too)
+        assert unit in units
+        assert not any(l.startswith(unit + ".o: HIPFLAGS") for l in mk.splitlines())
+    assert "ppp_registration_tile.h" in [l for l in mk.splitlines() if l.startswith("SCAN_HDR")][0]
 
 
 # ---------------------------------------------------------------- CPU: the census

@@ -60,7 +60,7 @@ def test_header_declares_and_engine_exports_the_trimmed_tiles(engine_mod):
     planner = open(os.path.join(ROOT, "include", "ppp_planner.hpp")).read()
     assert "inline bool register_trimmed_tiles(std::vector<Planner *> &tiles, std::vector<Planner *> &refs, ppp_register_tiles_stats &st," in planner
     mk = open(os.path.join(ROOT, "polishpathplanning_amd", "csrc", "Makefile")).read()
-    assert "ppp_trimmed_tile.h" in [l for l in mk.splitlines() if l.startswith("CONTACT_HDR")][0]
+    assert "ppp_trimmed_tile.h" in [l for l in mk.splitlines() if l.startswith("SCAN_HDR")][0]
 
 
 def select_restated(hist, rank):
