@@ -10,7 +10,7 @@
 // planned cloud, the scan, stands proud of it (points by status, the deviation's range, mean and rms; PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN set the
 // parameters); with PPP_PATH_DWELL=1 or PPP_PATH_FEED=1 the schedule steers towards that target.  PPP_REGISTER=1 beside it
 // registers the scan to that reference first (point-to-plane ICP from the identity: pairs, rms before and after, steps, locked unknowns and T are printed;
-// PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP), before the path is planned and before the deviation is taken; PPP_REGISTER_KEEP=<share below 1> beside PPP_REGISTER=1 runs the trimmed loop instead (every evaluation keeps that share of its pairs with the smallest pair distance: for a scan with a clamp, a burr or an edge the reference does not have; the kept and the paired counts and the cut are printed); PPP_REGISTER=global does so from an unknown pose (PPP_REGISTER_CANDIDATES, _STRIDE, _COARSE_MAXDIST).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
+// PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP), before the path is planned and before the deviation is taken; PPP_REGISTER_KEEP=<share below 1> beside PPP_REGISTER=1 runs the trimmed loop instead (every evaluation keeps that share of its pairs with the smallest pair distance: for a scan with a clamp, a burr or an edge the reference does not have; the kept and the paired counts and the cut are printed); PPP_REGISTER=global does so from an unknown pose (PPP_REGISTER_CANDIDATES, _STRIDE, _COARSE_MAXDIST).  PPP_REGISTER=robust weighs every pair by Tukey's biweight of its point-to-plane residual, scaled by the median absolute residual of each evaluation (no share to choose; PPP_REGISTER_TUNE, _SIGMA_MIN; the used and the paired counts, the median and sigma are printed).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -40,6 +40,7 @@ int main(int argc, char **argv)
         else path_planner.register_to(*reference);
     }
     if (reference && reg && std::string(reg) == "global") path_planner.register_global_to(*reference); /* from an unknown pose */
+    if (reference && reg && std::string(reg) == "robust") path_planner.register_robust_to(*reference); /* Tukey weights: no keep to choose */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");

@@ -565,6 +565,66 @@ int  ppp_register_trimmed(ppp_handle h, ppp_handle ref, const ppp_trimmed_regist
                           ppp_trimmed_registration_row *rows, size_t row_cap,
                           unsigned char *status, float *d2, size_t cap,
                           ppp_registration_stats *stats);
+/* Robust registration: ppp_register's loop in which every pair enters the sums with Tukey's
+   biweight of its point-to-plane residual, the scale being the median absolute residual of each evaluation.  Nothing has to
+   choose a share of the scan beforehand, as ppp_register_trimmed's keep does: what the reference does not show -- a clamp pad, a
+   strip of the table, a burr -- ends at weight 0 once the fit has tightened around the rest.  The estimator's limit: it needs
+   the median residual to belong to the part that shows the reference.  With a third of the scan raised by 1.5 mm the median
+   residual is about 0.5 mm, the fit tilts and stays tilted; ppp_register_trimmed with a known keep remains the
+   tool for heavy contamination.
+     pair       ppp_register's, word for word (moved, the float query, the nearest point and its tie rule, a point at exactly
+                max_dist * max_dist matches, no pair where the normal has a NaN or the query is not finite); paired = their number
+     residual   r = ((ex nx) + ey ny) + ez nz, ppp_register's double
+     key        the bit pattern of (float)fabs(r) as a 32-bit unsigned integer: never negative and never NaN, so the keys order
+                as the floats do
+     scale      k = ppp_trim_rank(0.5, paired); tau = the k-th smallest key (1-based), found through ppp_register_trimmed's three
+                digit histograms; m = (double) the float with the bits of tau (median_abs); sigma = max(1.4826 * m, sigma_min);
+                cs = tune * sigma.  paired == 0: median_abs is the float quiet NaN 0x7fc00000, sigma the double quiet NaN
+                0x7ff8000000000000, and no step is taken
+     weight     tune == +INFINITY: w = 1.  cs == 0: w = 1 where r == 0, else 0.  Otherwise u = r / cs, v = 1 - u * u,
+                w = fabs(u) < 1 ? v * v : 0; one rounding per written operation, no transcendental
+     terms      A_ik += llrint(((J_i J_k) w) 2^shift), b_i += llrint(((J_i r) w) 2^shift), E += llrint(((r r) w) 2^shift),
+                weight_sum += llrint(w 2^shift); row.pairs = paired; used = the pairs with w > 0; shift, centre, Ln and J are
+                ppp_register's.  With w = 1 every product is exact in that order: the words are ppp_register's
+     the rest   solve, step, composition and the loop's endings are ppp_register's with "fewer than 6 pairs" read as used < 6;
+                stats is ppp_register's with pairs_* = paired and rms_* = sqrt((double)E / (double)weight_sum), NaN when
+                weight_sum == 0
+     maps       status, weight and residual, by cloud index of h, the first min(cap, n) entries, of the LAST evaluation (the one
+                at the result, rows[steps]): PPP_ROBUST_DROPPED for a point that is not finite, PPP_ROBUST_UNPAIRED for one
+                without a pair, else PPP_ROBUST_USED (w > 0) or PPP_ROBUST_REJECTED (w == 0); weight is (float)w and residual
+                is r, the float NaN 0x7fc00000 and the double NaN 0x7ff8000000000000 where there is no pair
+   tune == +INFINITY weighs every pair 1: rows[k].row, T and stats are ppp_register's bits from the same start.
+   ppp_get_robust_registration_terms evaluates once at T12 (NULL: the identity) and takes no step, as
+   ppp_get_registration_terms does; its maps are that evaluation's.  rows, row, the maps and stats may be NULL (rows with
+   row_cap = 0; the maps with any cap).  The whole chain -- per evaluation the search with the top digit's histogram, two passes
+   over the stored keys, the weighted sums, the step -- is enqueued at once on h's stream with one wait at its end; neither
+   handle's cloud, plan or stored results change.  PPP_ERR_ARG: ppp_register's refusals; bp NULL; tune NaN or <= 0 (+INFINITY
+   is allowed); sigma_min not finite or < 0.  PPP_ERR_UNSUPPORTED when either handle is a slice-range handle or a part handle. */
+typedef struct {
+    ppp_registration_params icp;   /* ppp_register's four, with its ranges */
+    double tune;                   /* > 0, +INFINITY allowed: the cut of the biweight in units of sigma */
+    double sigma_min;              /* mm, finite, >= 0: the floor of sigma */
+} ppp_robust_registration_params;           /* defaults: ppp_default_registration_params, 4.685, 1e-4 */
+
+typedef struct {
+    ppp_registration_row row;      /* as ppp_register's: pairs = paired, A / b / E weighted */
+    size_t    used;                /* pairs with a weight above zero */
+    long long weight_sum;          /* the sum of the weights, fixed point */
+    float     median_abs;          /* the median of |r| as a float; NaN when paired == 0 */
+    double    sigma;               /* max(1.4826 * median_abs, sigma_min); NaN when paired == 0 */
+} ppp_robust_registration_row;
+
+enum { PPP_ROBUST_USED = 0, PPP_ROBUST_REJECTED = 1, PPP_ROBUST_UNPAIRED = 2, PPP_ROBUST_DROPPED = 3 };
+
+void ppp_default_robust_registration_params(ppp_robust_registration_params *bp);
+int  ppp_get_robust_registration_terms(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T12,
+                                       ppp_robust_registration_row *row,
+                                       unsigned char *status, float *weight, double *residual, size_t cap,
+                                       ppp_registration_stats *stats);
+int  ppp_register_robust(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T0_12,
+                         ppp_robust_registration_row *rows, size_t row_cap,
+                         unsigned char *status, float *weight, double *residual, size_t cap,
+                         ppp_registration_stats *stats);
 /* T applied to the resident cloud: T12 (row-major 3 x 4, NULL: the identity) is rounded to float and every finite point
    becomes m0 x + (m1 y + (m2 z + m3)) per row, pcl::transformPointCloud's arithmetic; a point that is not finite passes
    unchanged.  The cloud has changed: bounds, plan, index and every stored result are withdrawn, as after ppp_trans2center.

@@ -600,6 +600,67 @@ public:
         for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
         return ran && apply && st.converged && transform_cloud(st.T);
     }
+    /* robust point-to-plane ICP (ppp_register_robust): register_to() in which every pair is weighed by Tukey's
+       biweight of its point-to-plane residual, the scale being 1.4826 times the median absolute residual of each evaluation --
+       no share of the scan has to be chosen, as register_trimmed_to()'s keep must be.  rows, when asked for, receives the
+       evaluations with their used / paired counts, medians and sigmas; status, weight and residual, when asked for, the last
+       evaluation's maps by cloud index (PPP_ROBUST_*) */
+    bool register_robust_to(const Planner &ref, ppp_registration_stats &st, const ppp_robust_registration_params &bp, const double *T0 = nullptr,
+                            std::vector<ppp_robust_registration_row> *rows = nullptr, std::vector<unsigned char> *status = nullptr,
+                            std::vector<float> *weight = nullptr, std::vector<double> *residual = nullptr)
+    {
+        if (rows) rows->assign((size_t)(bp.icp.iterations > 0 ? bp.icp.iterations : 0) + 1, ppp_robust_registration_row{});
+        size_t n = 0;
+        if (status || weight || residual) {
+            int rc = ppp_num_points(h_, &n);
+            if (rc != PPP_OK) return report(rc);
+            if (status) status->assign(n, PPP_ROBUST_DROPPED);
+            if (weight) weight->assign(n, 0.f);
+            if (residual) residual->assign(n, 0.0);
+        }
+        int rc = ppp_register_robust(h_, ref.h_, &bp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, status ? status->data() : nullptr,
+                                     weight ? weight->data() : nullptr, residual ? residual->data() : nullptr, n, &st);
+        if (rc != PPP_OK) {
+            if (rows) rows->clear();
+            if (status) status->clear();
+            if (weight) weight->clear();
+            if (residual) residual->clear();
+            return report(rc);
+        }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* registration_params_env() with tune from PPP_REGISTER_TUNE and sigma_min from PPP_REGISTER_SIGMA_MIN (the defaults 4.685
+       and 1e-4 mm where they are not set) */
+    static ppp_robust_registration_params robust_registration_params_env()
+    {
+        ppp_robust_registration_params bp;
+        ppp_default_robust_registration_params(&bp);
+        bp.icp = registration_params_env();
+        if (const char *v = std::getenv("PPP_REGISTER_TUNE")) bp.tune = std::atof(v);
+        if (const char *v = std::getenv("PPP_REGISTER_SIGMA_MIN")) bp.sigma_min = std::atof(v);
+        return bp;
+    }
+    /* print_registration() on register_robust_to(): a line with the used and the paired counts, the median absolute residual
+       and sigma before and after, then print_registration()'s lines with the weighted rms */
+    bool print_registration(const Planner &ref, const ppp_robust_registration_params &bp, bool apply = true)
+    {
+        ppp_registration_stats st = {};
+        std::vector<ppp_robust_registration_row> rows;
+        const bool ran = register_robust_to(ref, st, bp, nullptr, &rows);
+        if (!ran) st = ppp_registration_stats{};
+        const ppp_robust_registration_row none = {};
+        const ppp_robust_registration_row &first = rows.empty() ? none : rows.front(), &last = rows.empty() ? none : rows.back();
+        std::printf("registration: robust, tune %f: %zu of %zu pairs used, median %f mm, sigma %f mm; after %d steps %zu of %zu, median %f mm, sigma %f mm\n",
+                    bp.tune, first.used, first.row.pairs, first.row.pairs ? first.median_abs : 0.0, first.row.pairs ? first.sigma : 0.0, st.steps, last.used,
+                    last.row.pairs, last.row.pairs ? last.median_abs : 0.0, last.row.pairs ? last.sigma : 0.0);
+        std::printf("registration: %zu of %zu points paired, weighted rms %f mm; after %d steps %zu paired, weighted rms %f mm\n", st.pairs_before, st.indexed,
+                    first.weight_sum ? st.rms_before : 0.0, st.steps, st.pairs_after, last.weight_sum ? st.rms_after : 0.0);
+        std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",
+                    st.converged ? "converged" : (ran && st.steps == bp.icp.iterations ? "out of iterations" : "no step possible"), st.locked);
+        for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
+        return ran && apply && st.converged && transform_cloud(st.T);
+    }
     /* global registration of this planner's cloud, the scan, to the cloud of ref (ppp_register_global): the starts
        the two clouds' principal frames imply, a coarse chain from each side by side, the fine chain from the cheapest.  st.fine.T
        carries a scan point into ref's frame; cands, when asked for, receives one entry per start.  Needs no pass and no start,

@@ -1,8 +1,8 @@
 /*
  * ppp_scan.hip -- the calls of the C ABI (include/ppp_hip.h) that hold a scan against a reference cloud: the deviation map, its
- * tiles and their merge, the registration chain, its trimmed form, the cloud moments and the global registration, and the
- * registration and trimmed registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
- * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_registration_tile.h and ppp_trimmed_tile.h; of the handle it sees
+ * tiles and their merge, the registration chain, its trimmed and its robust form, the cloud moments and the global registration,
+ * and the registration and trimmed registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
+ * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_robust.h, ppp_registration_tile.h and ppp_trimmed_tile.h; of the handle it sees
  * what ppp_handle.h declares, and it shares ppp_query_host.h with ppp_contact.hip.  Compiled with the engine's flags: the host
  * and the device step share icp_solve and icp_compose, one IEEE rounding per written operation on both sides.
  */
@@ -15,6 +15,7 @@
 #include "ppp_deviation_tile.h"
 #include "ppp_registration.h"
 #include "ppp_trimmed.h"
+#include "ppp_robust.h"
 #include "ppp_registration_tile.h"
 #include "ppp_trimmed_tile.h"
 #include <cstring>
@@ -394,6 +395,135 @@ int ppp_register_trimmed(ppp_handle h, ppp_handle ref, const ppp_trimmed_registr
     if (!tp) return fail(h, PPP_ERR_ARG, "trimmed registration: no parameters");
     const TrimCall trim = {tp->keep, rows, status, d2, cap};
     return registration_chain(h, ref, &tp->icp, T0_12, true, nullptr, row_cap, stats, &trim);
+}
+
+void ppp_default_robust_registration_params(ppp_robust_registration_params *bp)
+{
+    if (!bp) return;
+    ppp_default_registration_params(&bp->icp);
+    bp->tune = 4.685; bp->sigma_min = 1e-4;
+}
+
+/* The robust chain: registration_chain's shape -- the reference's index and normal field on its own stream, one
+   wait for that stream, then iterations + 1 evaluations and iterations steps back to back on the scan's stream, and one wait --
+   in which an evaluation is k_rob_pair, k_trim_narrow<1>, k_trim_narrow<2> at keep 0.5 and k_rob_terms, its ROB_WORDS words
+   the weighted sums with `used` in word 0, which is what k_reg_step reads as its pairs; k_rob_scatter follows the chain.
+   !loop: the one evaluation of ppp_get_robust_registration_terms. */
+static int robust_chain(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T0, bool loop,
+                        ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
+                        ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !bp) return fail(h, PPP_ERR_ARG, "robust registration: no reference handle or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "robust registration: rows is NULL with row_cap > 0");
+    if (!(bp->tune > 0.0)) return fail(h, PPP_ERR_ARG, "robust registration: tune must be > 0 (+INFINITY: every weight is 1)");
+    if (!(bp->sigma_min >= 0.0 && std::isfinite(bp->sigma_min))) return fail(h, PPP_ERR_ARG, "robust registration: sigma_min must be finite and >= 0");
+    const ppp_registration_params P = bp->icp;
+    const RobScale S = {bp->tune, bp->sigma_min};
+    IcpFrame F;
+    int rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, "robust registration", T0, T);
+    if (rc) return rc;
+    int shift = 0;
+    rc = registration_setup(h, ref, P, F, shift);
+    if (rc) return rc;
+    const size_t N = h->n, N1 = std::max<size_t>(N, 1);
+    const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    const size_t nq1 = std::max<size_t>((size_t)std::max(nq, 0), 1);
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    static_assert(sizeof(TrimCut) == 8 * sizeof(unsigned), "TrimCut is eight words");
+    HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ROB_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
+    HIPCHK(h, G.partner.ensure(nq1)); HIPCHK(h, G.key.ensure(nq1)); HIPCHK(h, G.rres.ensure(nq1));
+    HIPCHK(h, G.hist.ensure(TRIM_WORDS * evals)); HIPCHK(h, G.cuts.ensure(8 * evals)); HIPCHK(h, G.rsigma.ensure(evals));
+    HIPCHK(h, G.tstatus.ensure(N1)); HIPCHK(h, G.td2.ensure(N1)); HIPCHK(h, G.rresid.ensure(N1));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    TrimCut *cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ROB_WORDS * evals * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
+    /* every evaluation has histograms of its own: one clear on the stream before the chain, none between iterations */
+    HIPCHK(h, hipMemsetAsync(G.hist.p, 0, TRIM_WORDS * evals * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.cuts.p, 0, 8 * evals * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.rsigma.p, 0, evals * sizeof(double), h->stream));
+    HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus));
+    LAUNCH(h, "k_rob_fill", k_rob_fill, (unsigned)std::min<size_t>((N1 + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus), TRIM_T, 0, (int)N1, G.tstatus.p,
+           G.td2.p, G.rresid.p); /* points outside the index: not finite */
+    for (int k = 0; k <= iterations; ++k) {
+        unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+        unsigned long long *acc = G.acc.p + ROB_WORDS * (size_t)k;
+        LAUNCH(h, "k_rob_pair", k_rob_pair, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+               G.rres.p, G.key.p, hist);
+        LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_rob_terms", k_rob_terms, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), F, S, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+               G.rres.p, G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.rsigma.p + k, acc);
+        if (k < iterations) LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, acc, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    LAUNCH(h, "k_rob_scatter", k_rob_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, G.rres.p, ctl, cuts, G.rsigma.p, S, (int)evals, (int)N1,
+           G.tstatus.p, G.td2.p, G.rresid.p);
+    IcpCtl C;
+    HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
+    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, "robust registration: control words corrupt");
+    const size_t last = (size_t)C.steps;
+    std::vector<ppp_registration_row> R(last + 1);
+    std::vector<unsigned long long> acc(ROB_WORDS * (last + 1));
+    std::vector<TrimCut> cut(last + 1);
+    std::vector<double> sigma(last + 1);
+    HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, acc.data(), G.acc.p, acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, cut.data(), G.cuts.p, (last + 1) * sizeof(TrimCut), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, sigma.data(), G.rsigma.p, (last + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    if (!C.done) { /* the evaluation behind the last step: no step kernel follows it */
+        double Tl[12];
+        HIPCHK(h, copy_sync(h, Tl, G.T.p + 12 * last, sizeof(Tl), hipMemcpyDeviceToHost));
+        icp_row_terms(&R[last], Tl, acc.data() + ROB_WORDS * last);
+    }
+    std::vector<ppp_robust_registration_row> out(last + 1);
+    for (size_t i = 0; i <= last; ++i) {
+        const unsigned long long *w = acc.data() + ROB_WORDS * i;
+        if (cut[i].paired > (unsigned)std::max(nq, 0) || w[ROB_USED] > cut[i].paired || R[i].pairs != (size_t)w[ROB_USED])
+            return fail(h, PPP_ERR_HIP, "robust registration: sums corrupt");
+        ppp_robust_registration_row &o = out[i];
+        memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
+        o.row = R[i];
+        o.row.pairs = cut[i].paired; /* the step kernel read `used` there */
+        o.used = (size_t)w[ROB_USED];
+        o.weight_sum = (long long)w[ROB_WSUM];
+        memcpy(&o.median_abs, &cut[i].tau, sizeof(float));
+        o.sigma = sigma[i];
+        R[i].pairs = cut[i].paired;
+    }
+    if (stats) {
+        *stats = registration_stats(R, C, N, (size_t)nq, shift, F.c, F.Ln);
+        auto rms = [](const ppp_robust_registration_row &r) { return r.weight_sum ? std::sqrt((double)r.row.E / (double)r.weight_sum) : (double)NAN; };
+        stats->rms_before = rms(out[0]); stats->rms_after = rms(out[last]);
+    }
+    const size_t k = std::min(row_cap, last + 1);
+    if (rows && k) memcpy(rows, out.data(), k * sizeof(ppp_robust_registration_row));
+    const size_t m = std::min(cap, N);
+    if (status && m) HIPCHK(h, copy_sync(h, status, G.tstatus.p, m, hipMemcpyDeviceToHost));
+    if (weight && m) HIPCHK(h, copy_sync(h, weight, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
+    if (residual && m) HIPCHK(h, copy_sync(h, residual, G.rresid.p, m * sizeof(double), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_robust_registration_terms(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T12,
+                                      ppp_robust_registration_row *row, unsigned char *status, float *weight, double *residual, size_t cap,
+                                      ppp_registration_stats *stats)
+{
+    return robust_chain(h, ref, bp, T12, false, row, row ? 1 : 0, status, weight, residual, cap, stats);
+}
+
+int ppp_register_robust(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T0_12,
+                        ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
+                        ppp_registration_stats *stats)
+{
+    return robust_chain(h, ref, bp, T0_12, true, rows, row_cap, status, weight, residual, cap, stats);
 }
 
 /* The ten words of side's cloud (k_cloud_moments on side's stream, one wait) and the frame they imply; side's index is

@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_trim_select", "ppp_trim_rank", "ppp_register_trimmed_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_default_robust_registration_params", "ppp_get_robust_registration_terms", "ppp_register_robust", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_trim_select", "ppp_trim_rank", "ppp_register_trimmed_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -186,6 +186,12 @@ def lib():
         L.ppp_default_trimmed_registration_params.restype = None
         L.ppp_register_trimmed.argtypes = [vp, vp, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow), sz, C.POINTER(C.c_ubyte), fp,
                                            sz, C.POINTER(RegistrationStats)]
+        L.ppp_default_robust_registration_params.argtypes = [C.POINTER(RobustRegistrationParams)]
+        L.ppp_default_robust_registration_params.restype = None
+        L.ppp_get_robust_registration_terms.argtypes = [vp, vp, C.POINTER(RobustRegistrationParams), dp, C.POINTER(RobustRegistrationRow), C.POINTER(C.c_ubyte),
+                                                        fp, dp, sz, C.POINTER(RegistrationStats)]
+        L.ppp_register_robust.argtypes = [vp, vp, C.POINTER(RobustRegistrationParams), dp, C.POINTER(RobustRegistrationRow), sz, C.POINTER(C.c_ubyte), fp, dp,
+                                          sz, C.POINTER(RegistrationStats)]
         L.ppp_trim_select.argtypes = [C.POINTER(C.c_uint), sz, sz, C.POINTER(C.c_uint), C.POINTER(sz)]
         L.ppp_trim_rank.argtypes = [C.c_double, sz]
         L.ppp_trim_rank.restype = sz
@@ -496,6 +502,31 @@ def _trimmed_registration_row(r):
     out["paired"] = int(r.paired)
     out["trim_d2"] = float(r.trim_d2)
     out["trim_bits"] = int(np.array([r.trim_d2], np.float32).view(np.uint32)[0])
+    return out
+
+
+class RobustRegistrationParams(C.Structure):
+    """ppp_robust_registration_params"""
+    _fields_ = [("icp", RegistrationParams), ("tune", C.c_double), ("sigma_min", C.c_double)]
+
+
+class RobustRegistrationRow(C.Structure):
+    """ppp_robust_registration_row"""
+    _fields_ = [("row", RegistrationRow), ("used", C.c_size_t), ("weight_sum", C.c_longlong), ("median_abs", C.c_float), ("sigma", C.c_double)]
+
+
+ROBUST_USED, ROBUST_REJECTED, ROBUST_UNPAIRED, ROBUST_DROPPED = range(4)  # PPP_ROBUST_*
+
+
+def _robust_registration_row(r):
+    """a RobustRegistrationRow as a dict: _registration_row's fields (pairs = paired, A / b / E weighted) with used, weight_sum,
+    median_abs (a Python float of the float32; median_bits its bit pattern) and sigma"""
+    out = _registration_row(r.row)
+    out["used"] = int(r.used)
+    out["weight_sum"] = int(r.weight_sum)
+    out["median_abs"] = float(r.median_abs)
+    out["median_bits"] = int(np.array([r.median_abs], np.float32).view(np.uint32)[0])
+    out["sigma"] = float(r.sigma)
     return out
 
 
@@ -1510,6 +1541,57 @@ class Engine:
         if maps:
             status, d2 = status[:n], d2[:n]
         return stats["T"].copy(), [_trimmed_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, d2, stats
+
+    def _robust_maps(self, maps):
+        """(n, status, weight, residual) to hand to the robust calls: arrays of the cloud's size, or 0 and three Nones"""
+        if not maps:
+            return 0, None, None, None
+        nn = C.c_size_t()
+        self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+        n = nn.value
+        return n, np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float64)
+
+    def robust_registration_terms(self, ref, T=None, tune=4.685, sigma_min=1e-4, max_dist=2.0, lock_eps=1e-9, maps=True):
+        """(row, status uint8[n], weight float32[n], residual float64[n], stats) of one evaluation of register_robust()'s weighted
+        terms at T (3 x 4, None: the identity) against the cloud of the engine `ref` (ppp_get_robust_registration_terms): no step
+        is taken; row and the maps as register_robust() gives them.  maps=False returns None for the three maps"""
+        bp = RobustRegistrationParams(RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps)), float(tune), float(sigma_min))
+        row, st = RobustRegistrationRow(), RegistrationStats()
+        t = _t12(T)
+        n, status, weight, residual = self._robust_maps(maps)
+        self._chk(self.L.ppp_get_robust_registration_terms(self.h, ref.h, C.byref(bp), None if t is None else _d(t), C.byref(row),
+                                                           None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                           None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
+                                                           None if residual is None else _d(residual), n, C.byref(st)))
+        if maps:
+            status, weight, residual = status[:n], weight[:n], residual[:n]
+        return _robust_registration_row(row), status, weight, residual, _registration_stats(st)
+
+    def register_robust(self, ref, tune=4.685, sigma_min=1e-4, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
+        """(T float64[3, 4], rows, status uint8[n], weight float32[n], residual float64[n], stats): robust point-to-plane ICP
+        (ppp_register_robust): register()'s loop in which every pair enters the sums with Tukey's biweight of its point-to-plane
+        residual r, the scale sigma = max(1.4826 median|r|, sigma_min) taken anew at every evaluation and the weight cut at
+        tune * sigma -- no share of the scan has to be chosen, as register_trimmed()'s keep must be.  rows[k]: register()'s row
+        with the weighted A / b / E (pairs = the pairs found) and used (pairs with a weight above 0), weight_sum, median_abs,
+        median_bits and sigma; the maps describe the last evaluation by cloud index: ROBUST_USED, ROBUST_REJECTED,
+        ROBUST_UNPAIRED, ROBUST_DROPPED, the weight and the residual (NaN without a pair); stats as register()'s with the
+        weighted rms.  tune = inf is register() bit for bit.  It needs the median residual to lie on the part that shows the
+        reference: with a third of the scan off it does not recover the motion (register_trimmed with a known keep does).
+        maps=False returns None for the three maps"""
+        bp = RobustRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(tune), float(sigma_min))
+        cap = max(int(iterations), 0) + 1
+        rows = (RobustRegistrationRow * cap)()
+        st = RegistrationStats()
+        t = _t12(T0)
+        n, status, weight, residual = self._robust_maps(maps)
+        self._chk(self.L.ppp_register_robust(self.h, ref.h, C.byref(bp), None if t is None else _d(t), rows, cap,
+                                             None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                             None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
+                                             None if residual is None else _d(residual), n, C.byref(st)))
+        stats = _registration_stats(st)
+        if maps:
+            status, weight, residual = status[:n], weight[:n], residual[:n]
+        return stats["T"].copy(), [_robust_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, weight, residual, stats
 
     register_trimmed_tiles = staticmethod(register_trimmed_tiles)   # Engine.register_trimmed_tiles(engines, refs, ...): the module's function
 
