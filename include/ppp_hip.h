@@ -1022,6 +1022,50 @@ int    ppp_register_trimmed_tiles(const ppp_handle *hs, const ppp_handle *refs, 
                                   ppp_trimmed_registration_row *rows, size_t row_cap,
                                   unsigned char *const *status, float *const *d2, unsigned char *const *owned, size_t cap,
                                   ppp_register_tiles_stats *stats);
+/* ---- robust registration of a scan held as slice-range tiles ----
+   Everything ppp_register_robust's evaluation needs merges exactly over tiles: a pair, its residual r and its key (the bits of
+   (float)fabs(r)) are a point's own, the median is a rank statistic of the union of the keys -- the three digit histograms add
+   bin by bin --, sigma and the cut cs follow from the merged tau by two double multiplications and a max, the weight is a
+   function of a point's own r and the merged cs, and the 30 words are integer sums.  Nothing is approximated; the price is
+   ppp_register_trimmed_tiles's four host waits per evaluation.
+   ppp_robust_sigma (B.102's rule; host only): sigma = max(1.4826 * m, sigma_min), m the double of the float whose bits are
+   median_bits; none != 0 (an evaluation without a pair): the double quiet NaN 0x7ff8000000000000.  It is the routine the
+   kernels compile, so a caller who reduces the histograms across ranks itself makes the scale as the library does.
+   ppp_robust_weight (B.103's rule; host only): tune == +INFINITY: 1.  cs == 0: 1 where r == 0, else 0.  Otherwise
+   u = r / cs, v = 1 - u * u, fabs(u) < 1 ? v * v : 0, one rounding per written operation.  Neither needs a device or a handle.
+   ppp_register_robust_tiles (B.106-B.110): ppp_register_robust's loop over tiles.  hs, refs and count are
+   ppp_register_tiles's, with its rules; each reference's index and normal field are built once, before the loop.  An
+   evaluation is four passes, each enqueued on every tile's own stream with one small asynchronous copy back per tile and one
+   wait per tile: (1) the search, which stores an owned point's partner, r and key and counts the keys' top 11 bits; the host
+   adds the tiles' histograms bin by bin, takes paired = their total and k = ppp_trim_rank(0.5, paired) -- never a tile's own
+   count --, selects the bin (ppp_trim_select) and sends every tile the merged prefix; (2), (3) the middle 11 and the low 10
+   bits of the stored keys that carry the merged prefix, merged and selected likewise, which gives tau; (4) tau, 4 bytes, goes
+   to every tile, whose kernel makes sigma = ppp_robust_sigma(tau, 0, sigma_min) and cs = tune * sigma itself and adds the 30
+   words over its owned pairs; 240 bytes come back per tile and merge as ppp_merge_registration_terms merges 29.  paired == 0
+   ends the evaluation behind pass (1): median_abs = 0x7fc00000, sigma the double quiet NaN, used 0, no step.  The step is
+   ppp_registration_step's on a row that carries used in pairs ("fewer than 6 pairs" is used < 6); the row that is recorded
+   carries paired.  For ranges that tile the walk T, every row (the 30 words, pairs = paired, used, weight_sum, median_abs,
+   sigma, locked, step2), every field of stats->reg (ppp_register_robust's: pairs_* = paired, rms_* = sqrt((double)E /
+   (double)weight_sum), NaN when weight_sum == 0) and each owned point's status / weight / residual are the bits of
+   ppp_register_robust on whole-cloud handles with the same parameters and T0; tune == +INFINITY gives ppp_register_tiles's rows.
+     status, weight, residual, owned   arrays of `count` per-tile pointers; the array or any entry may be NULL.  Each holds
+                         the first min(cap, n) entries by cloud index of tile i's maps of the LAST evaluation: an indexed
+                         point the tile owns has owned 1 and its status / (float)w / r as ppp_register_robust gives them;
+                         every other entry has owned 0, PPP_ROBUST_DROPPED, the float NaN 0x7fc00000 and the double NaN
+                         0x7ff8000000000000.  The owned maps of ranges that tile the walk partition the indexed points.
+   A tile's error ends the loop and is returned (the text on that tile's handle), with its index in stats->failed_tile (-1
+   otherwise).  PPP_ERR_ARG: ppp_register_tiles's refusals; bp NULL; tune NaN or <= 0 (+INFINITY is allowed); sigma_min not
+   finite or < 0.  PPP_ERR_CAPACITY (raise range_margin): a moved owned query whose reach leaves a slice-range reference's
+   index, by ppp_get_registration_terms_tile's test; such a call is never answered with fewer pairs.  PPP_ERR_UNSUPPORTED: a
+   part handle.  Neither handle's cloud, plan or stored result changes; nothing is kept. */
+double ppp_robust_sigma(unsigned int median_bits, int none, double sigma_min);
+double ppp_robust_weight(double r, double cs, double tune);
+int    ppp_register_robust_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count,
+                                 const ppp_robust_registration_params *bp, const double *T0_12,
+                                 ppp_robust_registration_row *rows, size_t row_cap,
+                                 unsigned char *const *status, float *const *weight, double *const *residual,
+                                 unsigned char *const *owned, size_t cap,
+                                 ppp_register_tiles_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

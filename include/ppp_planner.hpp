@@ -1009,5 +1009,49 @@ inline bool register_trimmed_tiles(std::vector<Planner *> &tiles, std::vector<Pl
     return true;
 }
 
+/* register_robust_to() for a scan held as slice-range planners (ppp_register_robust_tiles): tiles and refs as
+   register_tiles() takes them.  st.reg and rows are register_robust_to()'s, bit for bit, for ranges that tile the walk -- the
+   median is the merged histograms', never a tile's own --; an evaluation is four host round trips.  status, weight, residual
+   and owned, when asked for, receive one map per tile by cloud index: an indexed point the tile owns has owned 1 and its
+   PPP_ROBUST_* status, weight and residual, every other entry owned 0, PPP_ROBUST_DROPPED and NaN */
+inline bool register_robust_tiles(std::vector<Planner *> &tiles, std::vector<Planner *> &refs, ppp_register_tiles_stats &st,
+                                  const ppp_robust_registration_params &bp, const double *T0 = nullptr,
+                                  std::vector<ppp_robust_registration_row> *rows = nullptr, std::vector<std::vector<unsigned char>> *status = nullptr,
+                                  std::vector<std::vector<float>> *weight = nullptr, std::vector<std::vector<double>> *residual = nullptr,
+                                  std::vector<std::vector<unsigned char>> *owned = nullptr)
+{
+    if (tiles.empty() || refs.size() != tiles.size()) { std::fprintf(stderr, "ppp error %d: register_robust_tiles: one reference per tile\n", PPP_ERR_ARG); return false; }
+    std::vector<ppp_handle> hs, rs;
+    for (size_t i = 0; i < tiles.size(); ++i) { hs.push_back(tiles[i] ? tiles[i]->handle() : nullptr); rs.push_back(refs[i] ? refs[i]->handle() : nullptr); }
+    if (rows) rows->assign((size_t)(bp.icp.iterations > 0 ? bp.icp.iterations : 0) + 1, ppp_robust_registration_row{});
+    size_t n = 0;
+    if ((status || weight || residual || owned) && hs[0]) {
+        const int rc = ppp_num_points(hs[0], &n);
+        if (rc != PPP_OK) { std::fprintf(stderr, "ppp error %d: tile 0: %s\n", rc, ppp_last_error(hs[0])); return false; }
+    }
+    std::vector<unsigned char *> sp, op;
+    std::vector<float *> wp;
+    std::vector<double *> rp;
+    if (status) { status->assign(hs.size(), std::vector<unsigned char>(n, PPP_ROBUST_DROPPED)); for (auto &m : *status) sp.push_back(m.data()); }
+    if (weight) { weight->assign(hs.size(), std::vector<float>(n, 0.f)); for (auto &m : *weight) wp.push_back(m.data()); }
+    if (residual) { residual->assign(hs.size(), std::vector<double>(n, 0.0)); for (auto &m : *residual) rp.push_back(m.data()); }
+    if (owned) { owned->assign(hs.size(), std::vector<unsigned char>(n, 0)); for (auto &m : *owned) op.push_back(m.data()); }
+    const int rc = ppp_register_robust_tiles(hs.data(), rs.data(), hs.size(), &bp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0,
+                                             status ? sp.data() : nullptr, weight ? wp.data() : nullptr, residual ? rp.data() : nullptr,
+                                             owned ? op.data() : nullptr, n, &st);
+    if (rc != PPP_OK) {
+        if (rows) rows->clear();
+        if (status) status->clear();
+        if (weight) weight->clear();
+        if (residual) residual->clear();
+        if (owned) owned->clear();
+        const ppp_handle at = hs[st.failed_tile >= 0 ? (size_t)st.failed_tile : 0];
+        std::fprintf(stderr, "ppp error %d: tile %d: %s\n", rc, st.failed_tile, at ? ppp_last_error(at) : "no handle");
+        return false;
+    }
+    if (rows) rows->resize(std::min(rows->size(), (size_t)st.reg.steps + 1));
+    return true;
+}
+
 } // namespace ppp
 #endif

@@ -1,8 +1,8 @@
 /*
  * ppp_scan.hip -- the calls of the C ABI (include/ppp_hip.h) that hold a scan against a reference cloud: the deviation map, its
  * tiles and their merge, the registration chain, its trimmed and its robust form, the cloud moments and the global registration,
- * and the registration and trimmed registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
- * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_robust.h, ppp_registration_tile.h and ppp_trimmed_tile.h; of the handle it sees
+ * and the registration, the trimmed and the robust registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
+ * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_robust.h, ppp_registration_tile.h, ppp_trimmed_tile.h and ppp_robust_tile.h; of the handle it sees
  * what ppp_handle.h declares, and it shares ppp_query_host.h with ppp_contact.hip.  Compiled with the engine's flags: the host
  * and the device step share icp_solve and icp_compose, one IEEE rounding per written operation on both sides.
  */
@@ -18,6 +18,7 @@
 #include "ppp_robust.h"
 #include "ppp_registration_tile.h"
 #include "ppp_trimmed_tile.h"
+#include "ppp_robust_tile.h"
 #include <cstring>
 
 /* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
@@ -1345,6 +1346,214 @@ int ppp_register_trimmed_tiles(const ppp_handle *hs, const ppp_handle *refs, siz
     if (stats) stats->reg = registration_stats(R, C, call.whole.n, call.whole.owned, call.whole.shift, call.whole.centre, call.whole.length);
     const size_t k = std::min(row_cap, last + 1);
     for (size_t i = 0; rows && i < k; ++i) trimmed_row(rows[i], R[i], cuts[i].paired, cuts[i].tau);
+    return PPP_OK;
+}
+
+/* ---- robust registration of a scan held as slice-range tiles ---- */
+
+double ppp_robust_sigma(unsigned int median_bits, int none, double sigma_min) { return rob_sigma(median_bits, none != 0, sigma_min); }
+
+double ppp_robust_weight(double r, double cs, double tune) { return rob_weight(r, cs, tune); }
+
+/* the buffers of a tile behind regt_prepare: trimt_prepare's, the residual per position, and where the caller wants a map of this
+   tile the residual map by cloud index beside status | owned and the weight */
+static int robt_prepare(RegtTile &t, bool maps)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const int rc = trimt_prepare(t, maps);
+    if (rc) return rc;
+    HIPCHK(h, G.rres.ensure(std::max<size_t>((size_t)trimt_positions(t), 1)));
+    if (maps) HIPCHK(h, G.rresid.ensure(std::max<size_t>(h->n, 1)));
+    return PPP_OK;
+}
+
+/* the first pass of an evaluation at T, enqueued on the tile's stream: T to the device, the histograms and the words cleared,
+   k_robt_pair, the two words and the top digits' histogram back to pinned memory.  Nobody waits here. */
+static int robt_enqueue_pair(RegtTile &t, const double *T)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.hist.p, 0, (TRIMT_HEAD + TRIM_WORDS) * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ROB_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_robt_pair", k_robt_pair, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, t.own, contact_index(t.ref), t.nref, t.rb0, t.rb1, t.need,
+               G.tframe.p, G.T.p, G.partner.p, G.rres.p, G.key.p, G.hist.p);
+    HIPCHK(h, hipMemcpyAsync(trimt_pinned_hist(t), G.hist.p, (TRIMT_HEAD + TRIM_B0) * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the sums: the merged tau to the device, k_robt_terms, the 30 words back */
+static int robt_enqueue_terms(RegtTile &t, unsigned tau, const RobScale &S)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    *trimt_pinned_word(t) = tau;
+    HIPCHK(h, hipMemcpyAsync(G.cuts.p, trimt_pinned_word(t), sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_robt_terms", k_robt_terms, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, contact_index(t.ref), G.tframe.p, S, G.T.p, G.partner.p,
+               G.rres.p, G.key.p, G.cuts.p, G.acc.p);
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, ROB_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* behind the loop: the tile's maps filled with DROPPED / NaN / NaN / 0 (k_robt_fill: a double NaN is no memset pattern), then
+   k_robt_scatter over the keys and the residuals the last evaluation left */
+static int robt_enqueue_scatter(RegtTile &t, double cs, double tune, bool none)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    const size_t N1 = std::max<size_t>(h->n, 1);
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH(h, "k_robt_fill", k_robt_fill, (unsigned)std::min<size_t>((N1 + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus), TRIM_T, 0, (int)N1, G.tstatus.p,
+           G.td2.p, G.rresid.p, G.tstatus.p + N1);
+    if (t.pos1 > t.pos0)
+        LAUNCH(h, "k_robt_scatter", k_robt_scatter, t.grid, TRIM_T, 0, h->sorted4.p, t.pos0, t.pos1, G.key.p, G.rres.p, cs, tune, none ? 1 : 0, (int)N1,
+               G.tstatus.p, G.td2.p, G.rresid.p, G.tstatus.p + N1);
+    return PPP_OK;
+}
+
+/* the first min(cap, n) entries of the residual map, where the caller gave one for this tile (the copy waits for the tile's stream) */
+static int robt_copy_residual(RegtTile &t, double *residual, size_t cap)
+{
+    ppp_handle h = t.h;
+    const size_t m = std::min(cap, h->n);
+    if (!m || !residual) return PPP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, copy_sync(h, residual, h->registration.rresid.p, m * sizeof(double), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+/* The tiled robust loop (B.106-B.110): regt_loop, an evaluation being four passes over the tiles -- k_robt_pair,
+   k_trimt_narrow<1>, k_trimt_narrow<2>, k_robt_terms --, each enqueued on every tile's stream and waited for tile by tile; between
+   them the host adds the tiles' histograms, selects the digit of the median on the sum (ppp_trim_select at rank
+   ppp_trim_rank(0.5, paired)) and sends the next pass the merged prefix, or tau.  The row the step reads carries `used` in
+   pairs, as word 0 of the whole-cloud chain does; the row that is recorded carries paired.  An evaluation that finds no pair in
+   any tile ends behind its first pass. */
+int ppp_register_robust_tiles(const ppp_handle *hs, const ppp_handle *refs, size_t count, const ppp_robust_registration_params *bp, const double *T0_12,
+                              ppp_robust_registration_row *rows, size_t row_cap, unsigned char *const *status, float *const *weight,
+                              double *const *residual, unsigned char *const *owned, size_t cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !refs || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    if (!bp) return fail(h0, PPP_ERR_ARG, "robust registration tiles: no parameters");
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, &bp->icp, T0_12, F, T);
+    if (rc) return rc;
+    if (!(bp->tune > 0.0)) return fail(h0, PPP_ERR_ARG, "robust registration tiles: tune must be > 0 (+INFINITY: every weight is 1)");
+    if (!(bp->sigma_min >= 0.0 && std::isfinite(bp->sigma_min))) return fail(h0, PPP_ERR_ARG, "robust registration tiles: sigma_min must be finite and >= 0");
+    const ppp_registration_params P = bp->icp;
+    const RobScale S = {bp->tune, bp->sigma_min};
+    auto map_of = [&](auto *const *maps, size_t i) { return maps ? maps[i] : nullptr; };
+    auto wants_maps = [&](size_t i) { return map_of(status, i) || map_of(weight, i) || map_of(residual, i) || map_of(owned, i); };
+    RegtCall call = {"robust registration tiles", stats};
+    rc = regt_open(call, hs, refs, count, P, F, !rows && row_cap, [&](RegtTile &t, size_t i) { return robt_prepare(t, wants_maps(i)); });
+    if (rc) return rc;
+    std::vector<RegtTile> &tiles = call.tiles;
+    /* the tiles' histograms of `bins` bins, behind the wait, added bin by bin: a bin's sum is at most the scan's points */
+    std::vector<unsigned> H(TRIM_B0);
+    auto merge_hist = [&](size_t skip, size_t bins) {
+        std::fill(H.begin(), H.end(), 0u);
+        for (size_t i = 0; i < count; ++i) {
+            const unsigned *w = trimt_pinned_hist(tiles[i]) + skip;
+            for (size_t b = 0; b < bins; ++b) H[b] += w[b];
+        }
+    };
+    /* what an evaluation leaves beside its row: B.107's scale and the two words the row does not hold */
+    struct Scale { size_t paired, used; unsigned tau; double sigma; long long weight_sum; };
+    std::vector<Scale> scales;
+    std::vector<ppp_registration_row> R;
+    IcpCtl C = {};
+    rc = regt_loop(P, F, T, R, C, call.whole, [&](int, ppp_registration_row &rw) {
+        int e = regt_pass(call, [&](RegtTile &t) { return robt_enqueue_pair(t, T); });
+        if (e) return e;
+        size_t paired = 0;
+        for (size_t i = 0; i < count; ++i) {
+            RegtTile &t = tiles[i];
+            const unsigned *w = trimt_pinned_hist(t);
+            if (w[TRIMT_REFUSED]) return call.failed(i, fail(t.h, PPP_ERR_CAPACITY, regt_refusal(call.what, w[TRIMT_REFUSED])));
+            size_t mine = 0;
+            for (size_t b = 0; b < TRIM_B0; ++b) mine += w[TRIMT_HEAD + b];
+            if (w[TRIMT_OWNED] > (unsigned)trimt_positions(t) || mine > w[TRIMT_OWNED]) return call.failed(i, fail(t.h, PPP_ERR_HIP, "robust registration tiles: histogram corrupt"));
+            t.part.owned = w[TRIMT_OWNED];
+            call.parts[i] = t.part;
+            call.part_rows[i] = ppp_registration_row{};
+            paired += mine;
+        }
+        Scale sc = {paired, 0, TRIM_NAN, rob_sigma(TRIM_NAN, true, S.sigma_min), 0};
+        if (paired) { /* B.102 on the merged histograms; without a pair the evaluation ends here: used 0, no sums */
+            merge_hist(TRIMT_HEAD, TRIM_B0);
+            unsigned bin, prefix;
+            size_t rank;
+            ppp_trim_select(H.data(), TRIM_B0, trim_rank(ROB_KEEP, paired), &bin, &rank);
+            if (!rank) return fail(h0, PPP_ERR_HIP, "robust registration tiles: median corrupt");
+            prefix = bin << 21;
+            for (int pass = 1; pass <= 2; ++pass) {
+                const size_t bins = pass == 1 ? TRIM_B1 : TRIM_B2;
+                e = regt_pass(call, [&](RegtTile &t) { return trimt_enqueue_narrow(t, pass, prefix); });
+                if (e) return e;
+                merge_hist(0, bins);
+                ppp_trim_select(H.data(), bins, rank, &bin, &rank);
+                if (!rank) return fail(h0, PPP_ERR_HIP, "robust registration tiles: median corrupt");
+                prefix |= pass == 1 ? bin << 10 : bin;
+            }
+            sc.tau = prefix;
+            sc.sigma = rob_sigma(sc.tau, false, S.sigma_min);
+            e = regt_pass(call, [&](RegtTile &t) { return robt_enqueue_terms(t, sc.tau, S); });
+            if (e) return e;
+            unsigned long long wsum = 0; /* B.108: word 29 adds as the 29 in front of it do, two's complement */
+            for (size_t i = 0; i < count; ++i) {
+                const unsigned long long *w = tiles[i].h->registration.tpin.p;
+                if (w[ROB_USED] > call.parts[i].owned) return call.failed(i, fail(tiles[i].h, PPP_ERR_HIP, "robust registration tiles: sums corrupt"));
+                icp_row_terms(&call.part_rows[i], T, w);
+                wsum += w[ROB_WSUM];
+            }
+            sc.weight_sum = (long long)wsum;
+        }
+        e = regt_merged(h0, call, T, rw); /* rw.pairs = used: what the step reads (B.104) */
+        if (e) return e;
+        if (rw.pairs > paired) return fail(h0, PPP_ERR_HIP, "robust registration tiles: sums corrupt");
+        sc.used = rw.pairs;
+        scales.push_back(sc);
+        return (int)PPP_OK;
+    });
+    if (rc) return rc;
+    const size_t last = (size_t)C.steps;
+    /* B.109: the maps of the last evaluation -- its keys and residuals are the ones the tiles hold --, every tile's launch before any copy */
+    for (size_t i = 0; i < count; ++i)
+        if (wants_maps(i)) {
+            rc = robt_enqueue_scatter(tiles[i], S.tune * scales[last].sigma, S.tune, scales[last].paired == 0);
+            if (rc) return call.failed(i, rc);
+        }
+    for (size_t i = 0; i < count; ++i) {
+        rc = trimt_copy_maps(tiles[i], map_of(status, i), map_of(weight, i), map_of(owned, i), cap);
+        if (!rc) rc = robt_copy_residual(tiles[i], map_of(residual, i), cap);
+        if (rc) return call.failed(i, rc);
+    }
+    std::vector<ppp_robust_registration_row> out(last + 1);
+    for (size_t i = 0; i <= last; ++i) {
+        ppp_robust_registration_row &o = out[i];
+        memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
+        R[i].pairs = scales[i].paired; /* the step read `used` there */
+        o.row = R[i];
+        o.used = scales[i].used;
+        o.weight_sum = scales[i].weight_sum;
+        memcpy(&o.median_abs, &scales[i].tau, sizeof(float));
+        o.sigma = scales[i].sigma;
+    }
+    if (stats) {
+        stats->reg = registration_stats(R, C, call.whole.n, call.whole.owned, call.whole.shift, call.whole.centre, call.whole.length);
+        auto rms = [](const ppp_robust_registration_row &r) { return r.weight_sum ? std::sqrt((double)r.row.E / (double)r.weight_sum) : (double)NAN; };
+        stats->reg.rms_before = rms(out[0]); stats->reg.rms_after = rms(out[last]);
+    }
+    const size_t k = std::min(row_cap, last + 1);
+    if (rows && k) memcpy(rows, out.data(), k * sizeof(ppp_robust_registration_row));
     return PPP_OK;
 }
 

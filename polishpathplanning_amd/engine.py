@@ -74,7 +74,7 @@ EXPORTS = [
     "ppp_set_cloud", "ppp_set_cloud_device", "ppp_num_points", "ppp_gen_path_async", "ppp_get_path_async", "ppp_run_async",
     "ppp_sync", "ppp_failed_slice", "ppp_num_slices", "ppp_num_waypoints", "ppp_get_waypoints",
     "ppp_get_waypoints_device", "ppp_copy_waypoints_to_device", "ppp_get_tail_index", "ppp_minmax", "ppp_get_slice_positions",
-    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_default_robust_registration_params", "ppp_get_robust_registration_terms", "ppp_register_robust", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_trim_select", "ppp_trim_rank", "ppp_register_trimmed_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
+    "ppp_get_slice_indices", "ppp_get_nodes", "ppp_get_boundary", "ppp_get_coverage", "ppp_get_path_coverage", "ppp_get_path_contacts", "ppp_get_path_removal", "ppp_get_path_dwell", "ppp_get_path_feed", "ppp_default_feed_params", "ppp_write_feed_file", "ppp_default_deviation_params", "ppp_get_deviation", "ppp_default_registration_params", "ppp_get_registration_terms", "ppp_register", "ppp_default_trimmed_registration_params", "ppp_register_trimmed", "ppp_default_robust_registration_params", "ppp_get_robust_registration_terms", "ppp_register_robust", "ppp_transform_cloud", "ppp_get_cloud_moments", "ppp_cloud_frame_from_moments", "ppp_registration_starts", "ppp_default_global_registration_params", "ppp_register_global", "ppp_get_contact_field", "ppp_get_regions", "ppp_range_owned", "ppp_get_contact_field_tile", "ppp_get_regions_tile", "ppp_merge_region_tiles", "ppp_get_deviation_tile", "ppp_merge_deviation_tiles", "ppp_get_registration_terms_tile", "ppp_merge_registration_terms", "ppp_registration_step", "ppp_register_tiles", "ppp_trim_select", "ppp_trim_rank", "ppp_register_trimmed_tiles", "ppp_robust_sigma", "ppp_robust_weight", "ppp_register_robust_tiles", "ppp_principal_curvatures_at", "ppp_eval_spline", "ppp_ranged_x_index", "ppp_insert_point",
     "ppp_normals_at", "ppp_estimate_normals", "ppp_area2cloud", "ppp_nearest", "ppp_get_stage", "ppp_smooth_sweeps", "ppp_enable_timing",
     "ppp_get_kernel_times", "ppp_load_pcd", "ppp_save_pcd", "ppp_free", "ppp_default_config", "ppp_read_config",
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
@@ -198,6 +198,13 @@ def lib():
         L.ppp_register_trimmed_tiles.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(TrimmedRegistrationParams), dp, C.POINTER(TrimmedRegistrationRow),
                                                  sz, C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(fp), C.POINTER(C.POINTER(C.c_ubyte)), sz,
                                                  C.POINTER(RegisterTilesStats)]
+        L.ppp_robust_sigma.argtypes = [C.c_uint, C.c_int, C.c_double]
+        L.ppp_robust_sigma.restype = C.c_double
+        L.ppp_robust_weight.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.ppp_robust_weight.restype = C.c_double
+        L.ppp_register_robust_tiles.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(RobustRegistrationParams), dp, C.POINTER(RobustRegistrationRow),
+                                                sz, C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(fp), C.POINTER(dp), C.POINTER(C.POINTER(C.c_ubyte)), sz,
+                                                C.POINTER(RegisterTilesStats)]
         L.ppp_transform_cloud.argtypes = [vp, dp]
         L.ppp_get_cloud_moments.argtypes = [vp, C.POINTER(CloudFrame)]
         L.ppp_cloud_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
@@ -709,6 +716,89 @@ def merge_trimmed_maps(statuses, d2s, owneds):
         status[mine] = np.asarray(s, np.uint8)[mine]
         d2[mine] = np.asarray(d, np.float32)[mine]
     return status, d2
+
+
+def robust_sigma(median_bits, none, sigma_min):
+    """sigma of a robust evaluation from the bits of its median |r| (ppp_robust_sigma: host only, the routine the kernels compile):
+    max(1.4826 * float32(median_bits), sigma_min); none (no pair): the quiet NaN"""
+    return float(lib().ppp_robust_sigma(int(median_bits) & 0xffffffff, 1 if none else 0, float(sigma_min)))
+
+
+def robust_weight(r, cs, tune):
+    """Tukey's biweight of the residual r at the cut cs = tune * sigma (ppp_robust_weight: host only, the routine the kernels
+    compile): tune = inf: 1; cs = 0: 1 where r = 0, else 0; otherwise (1 - (r / cs)^2)^2 inside the cut and 0 from it on"""
+    return float(lib().ppp_robust_weight(float(r), float(cs), float(tune)))
+
+
+def register_robust_tiles(engines, refs, tune=4.685, sigma_min=1e-4, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
+    """(T float64[3, 4], rows, statuses, weights, residuals, owneds, stats): Engine.register_robust()'s T, rows and stats, bit for
+    bit, for a scan held as slice-range engines (ppp_register_robust_tiles); engines and refs as register_tiles() takes them.
+    statuses[i], weights[i], residuals[i] and owneds[i] are tile i's maps of the last evaluation by cloud index: an indexed point
+    the tile owns has owned 1 and register_robust()'s status, weight and residual, every other entry owned 0, ROBUST_DROPPED and
+    NaN; merge_robust_maps() makes the whole cloud's of them.  The median is taken on the tiles' merged histograms, never on a
+    tile's own: an evaluation is four host round trips, three histogram merges and the sums.  maps=False returns None for the
+    four lists.  A tile's error is raised with its index in the message"""
+    engines = list(engines)
+    refs = [refs] * len(engines) if isinstance(refs, Engine) else list(refs)
+    if len(refs) != len(engines):
+        raise PPPError(ERR_ARG, "register_robust_tiles: one reference per tile")
+    k = len(engines)
+    hs = (C.c_void_p * max(k, 1))(*[e.h for e in engines])
+    rs = (C.c_void_p * max(k, 1))(*[e.h for e in refs])
+    bp = RobustRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(tune), float(sigma_min))
+    cap = max(int(iterations), 0) + 1
+    rows = (RobustRegistrationRow * cap)()
+    st = RegisterTilesStats()
+    t = _t12(T0)
+    statuses = weights = residuals = owneds = sp = wp = rp = op = None
+    n = 0
+    if maps and k:
+        nn = C.c_size_t()
+        engines[0]._chk(lib().ppp_num_points(engines[0].h, C.byref(nn)))
+        n = nn.value
+        ub, fp, dp = C.POINTER(C.c_ubyte), C.POINTER(C.c_float), C.POINTER(C.c_double)
+        statuses = [np.zeros(max(n, 1), np.uint8) for _ in range(k)]
+        weights = [np.zeros(max(n, 1), np.float32) for _ in range(k)]
+        residuals = [np.zeros(max(n, 1), np.float64) for _ in range(k)]
+        owneds = [np.zeros(max(n, 1), np.uint8) for _ in range(k)]
+        sp = (ub * k)(*[a.ctypes.data_as(ub) for a in statuses])
+        wp = (fp * k)(*[a.ctypes.data_as(fp) for a in weights])
+        rp = (dp * k)(*[a.ctypes.data_as(dp) for a in residuals])
+        op = (ub * k)(*[a.ctypes.data_as(ub) for a in owneds])
+    rc = lib().ppp_register_robust_tiles(hs, rs, k, C.byref(bp), None if t is None else _d(t), rows, cap, sp, wp, rp, op, n, C.byref(st))
+    if rc:
+        at = st.failed_tile if st.failed_tile >= 0 else 0
+        text = engines[at].L.ppp_last_error(engines[at].h).decode() if k else "no tile"
+        raise PPPError(rc, "tile %d: %s" % (st.failed_tile, text))
+    stats = _registration_stats(st.reg)
+    if statuses is not None:
+        statuses, weights, residuals, owneds = ([a[:n] for a in m] for m in (statuses, weights, residuals, owneds))
+    return (stats["T"].copy(), [_robust_registration_row(rows[i]) for i in range(min(cap, st.reg.steps + 1))], statuses, weights, residuals, owneds,
+            stats)
+
+
+def merge_robust_maps(statuses, weights, residuals, owneds):
+    """(status uint8[n], weight float32[n], residual float64[n]) of the whole cloud from register_robust_tiles()' per-tile maps
+    (numpy only): every point takes the entries of the one tile that owns it; a point nobody owns is not finite: ROBUST_DROPPED
+    and NaN.  PPPError(ERR_ARG): no tile, maps of different lengths, a point two tiles own"""
+    if not len(statuses) or not (len(statuses) == len(weights) == len(residuals) == len(owneds)):
+        raise PPPError(ERR_ARG, "merge_robust_maps: no tile, or lists of different lengths")
+    n = len(statuses[0])
+    status = np.full(n, ROBUST_DROPPED, np.uint8)
+    weight = np.full(n, np.nan, np.float32)
+    residual = np.full(n, np.nan, np.float64)
+    seen = np.zeros(n, bool)
+    for s, w, r, o in zip(statuses, weights, residuals, owneds):
+        if not (len(s) == len(w) == len(r) == len(o) == n):
+            raise PPPError(ERR_ARG, "merge_robust_maps: maps of different lengths")
+        mine = np.asarray(o) != 0
+        if np.any(seen & mine):
+            raise PPPError(ERR_ARG, "merge_robust_maps: a point two tiles own")
+        seen |= mine
+        status[mine] = np.asarray(s, np.uint8)[mine]
+        weight[mine] = np.asarray(w, np.float32)[mine]
+        residual[mine] = np.asarray(r, np.float64)[mine]
+    return status, weight, residual
 
 
 class CloudFrame(C.Structure):
@@ -1594,6 +1684,7 @@ class Engine:
         return stats["T"].copy(), [_robust_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, weight, residual, stats
 
     register_trimmed_tiles = staticmethod(register_trimmed_tiles)   # Engine.register_trimmed_tiles(engines, refs, ...): the module's function
+    register_robust_tiles = staticmethod(register_robust_tiles)     # Engine.register_robust_tiles(engines, refs, ...) likewise
 
     def cloud_moments(self):
         """ppp_get_cloud_moments: the frame dict of the resident cloud (count, ms, c, L, the ten integer words, mean, axes with
