@@ -2,6 +2,9 @@
 //   api_check cloud.pcd position  -> rangedX_index(position) through the v1 class (public there, Path_Generate.h:50),
 //                                    estimate_normal() + the readable field, class Spline on caller-supplied knots
 //                                    (Spline.h:10-42: constructor, point, miny/bigy, restart, copies by value).
+//   api_check cloud.pcd position mesh.stl  -> also the mesh calls: a two-triangle plate written with ppp_save_stl, read back with
+//                                    ppp_load_stl, sampled through ppp::Planner::set_mesh (ppp_set_cloud_mesh, ppp_default_mesh_params)
+//                                    and through Planner::open of the file (ppp_set_cloud_stl): both give the same cloud.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -50,5 +53,21 @@ int main(int argc, char **argv)
     std::printf("edom %d\n", (out[0] != out[0]) ? 1 : 0);
     Spline bad(2, y2, x2, z2);                 // GSL_EINVAL
     std::printf("einval %d\n", bad.nodes());
+    if (argc > 3) { // the nominal as a triangle mesh
+        const float plate[18] = {0, 0, 1.5f, 0.04f, 0, 1.5f, 0.04f, 0.03f, 1.5f, 0, 0, 1.5f, 0.04f, 0.03f, 1.5f, 0, 0.03f, 1.5f}; /* metres */
+        float *back = nullptr;
+        size_t nt = 0;
+        const int rs = ppp_save_stl(argv[3], plate, 2, 1), rl = ppp_load_stl(argv[3], &back, &nt);
+        ppp_mesh_params mp;
+        ppp_default_mesh_params(&mp);
+        ppp_mesh_stats st1 = {}, st2 = {};
+        ppp::Planner a, b;
+        size_t n1 = 0, n2 = 0;
+        bool ok = rs == PPP_OK && rl == PPP_OK && nt == 2 && a.set_mesh(back, 3 * nt, nullptr, nt, &mp, nullptr, &st1) && b.open(argv[3]);
+        if (ok) ok = ppp_num_points(a.handle(), &n1) == PPP_OK && ppp_num_points(b.handle(), &n2) == PPP_OK;
+        if (ok) ok = ppp_set_cloud_stl(b.handle(), argv[3], &mp, nullptr, &st2) == PPP_OK;
+        ppp_free(back);
+        std::printf("mesh %d %zu %zu %zu %zu %zu\n", ok ? 1 : 0, nt, st1.samples, st2.samples, n1, n2);
+    }
     return 0;
 }

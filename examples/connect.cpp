@@ -11,6 +11,8 @@
 // parameters); with PPP_PATH_DWELL=1 or PPP_PATH_FEED=1 the schedule steers towards that target.  PPP_REGISTER=1 beside it
 // registers the scan to that reference first (point-to-plane ICP from the identity: pairs, rms before and after, steps, locked unknowns and T are printed;
 // PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP), before the path is planned and before the deviation is taken; PPP_REGISTER_KEEP=<share below 1> beside PPP_REGISTER=1 runs the trimmed loop instead (every evaluation keeps that share of its pairs with the smallest pair distance: for a scan with a clamp, a burr or an edge the reference does not have; the kept and the paired counts and the cut are printed); PPP_REGISTER=global does so from an unknown pose (PPP_REGISTER_CANDIDATES, _STRIDE, _COARSE_MAXDIST).  PPP_REGISTER=robust weighs every pair by Tukey's biweight of its point-to-plane residual, scaled by the median absolute residual of each evaluation (no share to choose; PPP_REGISTER_TUNE, _SIGMA_MIN; the used and the paired counts, the median and sigma are printed).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
+// A name that ends in .stl (any case) is a triangle mesh, the nominal part as a CAD export: its surface is sampled on the device into the cloud (PPP_MESH_PITCH, default 0.5 mm; PPP_MESH_FACING=front keeps
+// the triangles that face the origin).  PPP_DEVIATION=<reference.stl> ./connect scan.pcd measures (and with PPP_REGISTER registers) the scan against the mesh; ./connect part.stl plans on the nominal itself.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -23,6 +25,7 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; ++i) {
         size_t n = strlen(argv[i]);
         if (n > 4 && strcmp(argv[i] + n - 4, ".pcd") == 0) pcd = argv[i];
+        if (ppp::Planner::is_stl_name(argv[i])) pcd = argv[i]; /* the nominal as a mesh: the path is planned on its samples */
     }
     if (pcd.empty()) {
         std::cout << "./slicing_method cad_name.pcd" << std::endl;

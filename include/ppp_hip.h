@@ -135,6 +135,45 @@ int ppp_num_points(ppp_handle h, size_t *n);
 /* the resident cloud (after the x1000 and any preprocessing) as n x 3 packed floats in index order */
 int ppp_get_cloud(ppp_handle h, float *xyz, size_t cap, size_t *n);
 
+/* ---- the nominal part as a triangle mesh (a CAD export): sampled on the device into the resident cloud ----
+ * ppp_set_cloud_mesh puts a deterministic sampling of the mesh's surface on the handle; from then on the handle is what
+ * ppp_set_cloud leaves for a cloud whose conversion yields exactly those floats (plan, bounds, viewpoint, caches; a handle with a
+ * slice range indexes its part of the samples; ppp_get_cloud returns them, with no second x1000), so every call that takes a
+ * cloud -- ppp_get_deviation and the registrations with this handle as `ref`, their tiles, the contact field, a plan on the
+ * nominal itself -- works on it unchanged.
+ * verts = n_verts x 3 packed floats in the file's units; tris = n_tris x 3 vertex indices, or NULL for a soup (triangle f uses
+ * vertices 3f, 3f + 1, 3f + 2; n_verts must be 3 n_tris).  Every vertex goes through ppp_set_cloud's conversion (the x1000 when
+ * change_range is set, non-finite -> NaN); the rule below works on those floats widened to double, with + - * /, sqrt and ceil,
+ * one rounding per written operation.  pitch is in resident units (mm after ChangeRange).  Per triangle (a, b, c):
+ *   squared edge lengths ab, bc, ca, each (dx dx + dy dy) + dz dz; rotate cyclically (the winding stays) so that the longest
+ *   edge is (p0, p1) and p2 lies opposite, a tie going to the first of ab, bc, ca; e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2,
+ *   A2 = sqrt((nx nx + ny ny) + nz nz), L = sqrt(longest), hgt = A2 / L;
+ *   degenerate: an index outside [0, n_verts), a coordinate that is not finite, A2 zero or not finite -- skipped and counted;
+ *   PPP_MESH_FRONT: culled -- skipped and counted -- unless ((nx (vx - p0x) + ny (vy - p0y)) + nz (vz - p0z)) > 0, v = viewpoint
+ *   (NULL = origin) in the frame and units in which ppp_estimate_normals orients normals: resident ones.  It trusts the winding;
+ *   rows R = max(1, ceil(hgt / pitch)); row r: t = (r + 0.5) / R, len = L (1 - t), M_r = max(1, ceil(len / pitch));
+ *   column k of row r: s = (k + 0.5) / M_r, w = s (1 - t); the sample is (p0 + e2 t) + e1 w per coordinate, rounded to float.
+ * Samples are ordered by triangle, row, column: the cloud's index order.  Each lies strictly inside its triangle; the density
+ * is about 1 / pitch^2 whatever the triangle's shape (rows run along the longest edge: a sliver 50 long and 0.05 high is one row).
+ * tri_index (optional): the triangle of sample i, the first min(cap, samples) entries.  stats (optional) is filled as far as the
+ * counts were reached: triangles = n_tris = sampled + degenerate + culled; rows and samples are the totals.
+ * PPP_ERR_ARG: NULL verts or mp, pitch not > 0 or not finite, unknown facing, a soup with n_verts != 3 n_tris, n_tris == 0, no
+ * sample at all (every triangle degenerate or culled); PPP_ERR_CAPACITY: more rows or samples than a resident cloud holds
+ * ((2^31 - 1) / 8 points, as ppp_set_cloud); PPP_ERR_UNSUPPORTED: the handle holds a part (ppp_set_cloud_part).  A refused call
+ * leaves the resident cloud and the plan as they were.
+ * Not here: the handle's normals stay the PCA normals of its samples (not the facets'), vertices are not welded, and no call
+ * measures a point against a triangle.
+ * ppp_set_cloud_stl: ppp_load_stl + ppp_set_cloud_mesh of the soup; PPP_ERR_IO for a file that cannot be read. */
+enum { PPP_MESH_ALL = 0, PPP_MESH_FRONT = 1 };
+typedef struct { float pitch; int facing; } ppp_mesh_params;      /* defaults 0.5, PPP_MESH_ALL */
+typedef struct { size_t triangles, sampled, degenerate, culled, rows, samples; } ppp_mesh_stats;
+void ppp_default_mesh_params(ppp_mesh_params *mp);
+int  ppp_set_cloud_mesh(ppp_handle h, const float *verts, size_t n_verts, const int *tris, size_t n_tris,
+                        const ppp_mesh_params *mp, const float *viewpoint,
+                        int *tri_index, size_t cap, ppp_mesh_stats *stats);
+int  ppp_set_cloud_stl(ppp_handle h, const char *path, const ppp_mesh_params *mp, const float *viewpoint,
+                       ppp_mesh_stats *stats);
+
 /* ---- preprocessing of the constructors, on the resident cloud ---- */
 /* SectPath::remove_outlier() (path_slicing_alg.cpp:101-108): pcl::StatisticalOutlierRemoval, setMeanK(mean_k = 50),
  * setStddevMulThresh(stddev_mul = 1.0), sor.filter(*cloud): the filtered cloud replaces the resident one (same order,
@@ -1145,6 +1184,15 @@ int ppp_save_pcd(const char *path, const float *xyz, size_t n, size_t stride_flo
 /* a pcl::PointXYZRGB cloud (FIELDS x y z rgb, colour packed 0x00RRGGBB): what show() would hand to the viewer
  * (path_slicing_alg.cpp:69-80); xyz = n x 3 packed floats, rgb = n x 3 bytes; binary: 0 = ascii, 1 = binary */
 int ppp_save_pcd_rgb(const char *path, const float *xyz, const unsigned char *rgb, size_t n, const float viewpoint[7], int binary);
+/* STL, the triangle soup of a CAD export.  A file is binary when its size is 84 + 50 x the uint32 count at byte 80 (tested before
+ * the word `solid`: binary files may start with it): an 80-byte header, the count, 50-byte records (normal, three vertices,
+ * attribute word) -- the stored normal is ignored.  Anything else is read as ASCII: `facet` ... `vertex x y z` tokens, case and
+ * white space as loosely as the ASCII PCD reader takes them, numbers correctly rounded to float.  *verts9 receives n_tris x 9
+ * floats (a.x a.y a.z b.x ... c.z) allocated by the library (ppp_free).  PPP_ERR_IO: truncated or malformed.
+ * ppp_save_stl: binary 1 = binary, 0 = ASCII (%.9g: reads back to the same floats); the normal written is n / A2 in double
+ * (n = (b - a) x (c - a), A2 its length), or zeros for a degenerate triangle. */
+int ppp_load_stl(const char *path, float **verts9, size_t *n_tris);
+int ppp_save_stl(const char *path, const float *verts9, size_t n_tris, int binary);
 void ppp_free(void *p);
 /* SectPath::read_config / path_generater::read_config (path_slicing_alg.cpp:32-67,
  * path_dynamic_alg.cpp:34-75): same key set and parsing rules; absent keys keep config.txt's values */

@@ -14,6 +14,7 @@
 #define PPP_PLANNER_HPP
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -130,21 +131,8 @@ public:
     /* constructor body of the reference classes: load, recolour (no-op here), scale, keep */
     bool open(const std::string &cloud_name)
     {
-        if (!h_) {
-            dev_ = device_from_env();
-            h_ = HandlePool::take(dev_);
-            if (h_) {
-                /* switches a caller may have thrown through handle() on the earlier workpiece: back to the defaults */
-                ppp_set_fast_path(h_, 1);
-                ppp_enable_timing(h_, 0);
-                ppp_set_plan_reuse(h_, 1);
-            } else if (ppp_create(dev_, &h_) != PPP_OK) {
-                std::fprintf(stderr, "ppp: no MI355X device available (the engine has no CPU fallback)\n");
-                h_ = nullptr;
-                return false;
-            }
-        }
-        if (!apply_params()) return false;
+        if (!acquire()) return false;
+        if (is_stl_name(cloud_name)) return open_stl(cloud_name);
         /* pcl::io::loadPCDFile + the x1000 loop: the file's records go straight to HBM (ppp_set_cloud_pcd) */
         size_t n = 0;
         ppp_pcd_layout lay;
@@ -159,6 +147,73 @@ public:
             loaded_ = false;
             return false;
         }
+        if (rc != PPP_OK) return report(rc);
+        loaded_ = true;
+        return true;
+    }
+    /* the handle (from the pool, or a new one) with the configuration's parameters on it */
+    bool acquire()
+    {
+        if (!h_) {
+            dev_ = device_from_env();
+            h_ = HandlePool::take(dev_);
+            if (h_) {
+                /* switches a caller may have thrown through handle() on the earlier workpiece: back to the defaults */
+                ppp_set_fast_path(h_, 1);
+                ppp_enable_timing(h_, 0);
+                ppp_set_plan_reuse(h_, 1);
+            } else if (ppp_create(dev_, &h_) != PPP_OK) {
+                std::fprintf(stderr, "ppp: no MI355X device available (the engine has no CPU fallback)\n");
+                h_ = nullptr;
+                return false;
+            }
+        }
+        return apply_params();
+    }
+    /* an STL file as the cloud: its triangles sampled on the device (ppp_set_cloud_stl) with mesh_params_from_env() */
+    bool open_stl(const std::string &name)
+    {
+        const ppp_mesh_params mp = mesh_params_from_env();
+        ppp_mesh_stats st;
+        const int rc = ppp_set_cloud_stl(h_, name.c_str(), &mp, nullptr, &st);
+        if (rc == PPP_ERR_IO) {
+            std::fprintf(stderr, "Cloudn't read file!\n");
+            loaded_ = false;
+            return false;
+        }
+        if (rc != PPP_OK) { loaded_ = false; return report(rc); }
+        std::fprintf(stderr, "ppp: %s: %zu triangles (%zu degenerate, %zu culled) sampled at pitch %g into %zu points\n", name.c_str(), st.triangles,
+                     st.degenerate, st.culled, (double)mp.pitch, st.samples);
+        loaded_ = true;
+        return true;
+    }
+    /* a name that ends in .stl, in any case: the nominal part as a triangle mesh */
+    static bool is_stl_name(const std::string &name)
+    {
+        const size_t n = name.size();
+        return n > 4 && name[n - 4] == '.' && std::tolower((unsigned char)name[n - 3]) == 's' && std::tolower((unsigned char)name[n - 2]) == 't' &&
+               std::tolower((unsigned char)name[n - 1]) == 'l';
+    }
+    /* ppp_default_mesh_params with what the environment sets: PPP_MESH_PITCH (resident units: mm after ChangeRange) and
+       PPP_MESH_FACING=front (only the triangles that face the viewpoint, the origin) */
+    static ppp_mesh_params mesh_params_from_env()
+    {
+        ppp_mesh_params mp;
+        ppp_default_mesh_params(&mp);
+        if (const char *v = std::getenv("PPP_MESH_PITCH")) mp.pitch = (float)std::atof(v);
+        if (const char *v = std::getenv("PPP_MESH_FACING")) mp.facing = std::string(v) == "front" ? PPP_MESH_FRONT : PPP_MESH_ALL;
+        return mp;
+    }
+    /* the mesh a caller holds in arrays, sampled into the resident cloud (ppp_set_cloud_mesh; tris == nullptr: a soup).  For a
+       planner that was opened before: it replaces that cloud.  mp == nullptr: mesh_params_from_env() */
+    bool set_mesh(const float *verts, size_t n_verts, const int *tris, size_t n_tris, const ppp_mesh_params *mp = nullptr,
+                  const float *viewpoint = nullptr, ppp_mesh_stats *stats = nullptr)
+    {
+        if (!acquire()) return false;
+        const ppp_mesh_params env = mesh_params_from_env();
+        ppp_mesh_stats st;
+        const int rc = ppp_set_cloud_mesh(h_, verts, n_verts, tris, n_tris, mp ? mp : &env, viewpoint, nullptr, 0, &st);
+        if (stats) *stats = st;
         if (rc != PPP_OK) return report(rc);
         loaded_ = true;
         return true;

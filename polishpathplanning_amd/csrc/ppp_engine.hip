@@ -1078,7 +1078,7 @@ static int adopt_ingest_record(ppp_handle h, bool census, bool reuse)
     return PPP_OK;
 }
 
-int refresh_bounds_and_plan(ppp_handle h, const char *raw, size_t stride_bytes, bool may_defer)
+int refresh_bounds_and_plan(ppp_handle h, const char *raw, size_t stride_bytes, bool may_defer, bool resident)
 {
     const size_t n = h->n;
     h->auto_valid = false; h->auto_px_only = false;
@@ -1108,8 +1108,8 @@ int refresh_bounds_and_plan(ppp_handle h, const char *raw, size_t stride_bytes, 
             PA.px_host = reuse ? (float *)(h->pin.p + PIN_PX) : nullptr;
             PlanAuto *rec0 = (PlanAuto *)(h->pin.p + PIN_REC0), *rec1 = (PlanAuto *)(h->pin.p + PIN_REC1);
             rec0->S = -2; rec1->census = 0; rec1->S = -2;
-            hipLaunchKernelGGL(k_ingest_minmax, dim3(ingest_grid(n)), dim3(MM_T), 0, h->stream, raw, stride_bytes, (int)n, h->P.change_range, h->X.p, h->Y.p,
-                               h->Z.p, h->mm_part.p, PA);
+            hipLaunchKernelGGL(k_ingest_minmax, dim3(ingest_grid(n)), dim3(MM_T), 0, h->stream, raw, stride_bytes, (int)n,
+                               resident ? 0 : h->P.change_range, h->X.p, h->Y.p, h->Z.p, h->mm_part.p, PA);
             HIPCHK(h, hipGetLastError());
             if (census && !reuse) {
                 const int gc = std::max(1, std::min(((int)n + 4095) / 4096, 512));
@@ -1218,7 +1218,8 @@ static int resolve_deferred(ppp_handle h)
     return enqueue_pass(h, h->last_out2, (size_t)h->last_out2_cap, false, had_path); /* (to the caller's output buffer of the first attempt) */
 }
 
-static int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_bytes, const float *viewpoint, bool may_defer = false)
+static int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t stride_bytes, const float *viewpoint, bool may_defer = false,
+                            bool resident = false)
 {
     if (n > 0x7fffffffu / 8) return fail(h, PPP_ERR_CAPACITY, "cloud too large");
     h->n = n;
@@ -1234,7 +1235,12 @@ static int set_cloud_common(ppp_handle h, const char *raw_dev, size_t n, size_t 
         memcpy(h->vp, vp_new, 12);
     }
     HIPCHK(h, h->X.ensure(n)); HIPCHK(h, h->Y.ensure(n)); HIPCHK(h, h->Z.ensure(n));
-    return n ? refresh_bounds_and_plan(h, raw_dev, stride_bytes, may_defer) : refresh_bounds_and_plan(h);
+    return n ? refresh_bounds_and_plan(h, raw_dev, stride_bytes, may_defer, resident) : refresh_bounds_and_plan(h);
+}
+
+int set_cloud_resident(ppp_handle h, const float *xyz_dev, size_t n, const float *viewpoint)
+{
+    return set_cloud_common(h, (const char *)xyz_dev, n, 12, viewpoint, false, true);
 }
 
 

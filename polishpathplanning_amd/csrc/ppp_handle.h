@@ -7,7 +7,7 @@
  *                    every helper declared here
  *   ppp_contact.hip  the contact queries: coverage, path coverage, path contacts, the contact field, the regions, the schedules
  *   ppp_scan.hip     the calls that hold a scan against a reference cloud: the deviation map, the registrations, their tiles
- *   ppp_preproc.hip  the four preprocessing calls on the resident cloud
+ *   ppp_preproc.hip  the four preprocessing calls on the resident cloud, and the mesh sampler that makes one (ppp_set_cloud_mesh)
  *
  * A helper that only one unit calls is static in that unit and is not declared here.
  */
@@ -583,7 +583,9 @@ int fetch_meta(ppp_handle h);
 int map_dev_err(ppp_handle h);
 int ensure_ready(ppp_handle h, bool need_gen, bool need_path);
 int plan_ready(ppp_handle h);
-int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stride_bytes = 0, bool may_defer = false);
+int refresh_bounds_and_plan(ppp_handle h, const char *raw = nullptr, size_t stride_bytes = 0, bool may_defer = false, bool resident = false);
+/* ppp_set_cloud_device for points that are in resident units already (the mesh sampler's): the same conversion pass, without its x1000 */
+int set_cloud_resident(ppp_handle h, const float *xyz_dev, size_t n, const float *viewpoint);
 
 #define HIPCHK(h, expr)                                                                               \
     do {                                                                                              \

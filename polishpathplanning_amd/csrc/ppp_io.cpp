@@ -1,6 +1,6 @@
 /*
- * ppp_io.cpp -- host-side file formats of the reference: PCD v0.7 in, config.txt in,
- * pathFile out.  No device code; part of libppp_hip.so so the drop-in classes (ppp_host.cpp)
+ * ppp_io.cpp -- host-side file formats: the reference's (PCD v0.7 in, config.txt in,
+ * pathFile out) and STL, the mesh of a nominal part.  No device code; part of libppp_hip.so so the drop-in classes (ppp_host.cpp)
  * and the bindings share one implementation.
  */
 #include "../../include/ppp_hip.h"
@@ -470,6 +470,131 @@ static int save_pcd_rgb_impl(const char *path, const float *xyz, const unsigned 
     return PPP_OK;
 }
 
+/* ---- STL: the triangle soup of a CAD export ---- */
+static bool token_is(const char *t, const char *te, const char *word)
+{
+    for (; t < te && *word; ++t, ++word) if (std::tolower((unsigned char)*t) != *word) return false;
+    return t == te && !*word;
+}
+
+static int load_stl_impl(const char *path, float **verts9, size_t *n_tris)
+{
+    if (!path || !verts9 || !n_tris) return PPP_ERR_ARG;
+    *verts9 = nullptr; *n_tris = 0;
+    std::ifstream f(path, std::ios::binary);
+    if (!f.is_open()) return PPP_ERR_IO;
+    f.seekg(0, std::ios::end);
+    const std::streamoff fsize = f.tellg();
+    if (fsize < 0) return PPP_ERR_IO;
+    const size_t size = (size_t)fsize;
+    f.seekg(0);
+    /* binary when the size is what the count at byte 80 says: tested before the word `solid`, which binary headers may start with */
+    if (size >= 84) {
+        unsigned char head[84];
+        f.read((char *)head, 84);
+        if (f.gcount() != 84) return PPP_ERR_IO;
+        uint32_t count;
+        memcpy(&count, head + 80, 4);
+        if (size == 84 + 50 * (size_t)count) {
+            std::unique_ptr<unsigned char[]> rec(new unsigned char[50 * std::max<size_t>(count, 1)]);
+            float *out = (float *)malloc(sizeof(float) * 9 * std::max<size_t>(count, 1));
+            if (!out) return PPP_ERR_IO;
+            f.read((char *)rec.get(), (std::streamsize)(50 * (size_t)count));
+            if ((size_t)f.gcount() != 50 * (size_t)count) { free(out); return PPP_ERR_IO; }
+            for (size_t i = 0; i < count; ++i) memcpy(out + 9 * i, rec.get() + 50 * i + 12, 36); /* (the stored normal is not read) */
+            *verts9 = out; *n_tris = count;
+            return PPP_OK;
+        }
+        f.clear();
+        f.seekg(0);
+    }
+    /* ASCII: tokens separated by blanks (any control character counts as one), keywords in any case.  `vertex` takes three
+       numbers; a facet closes with three vertices; the text opens with `solid` and closes with `endsolid` (a file cut short
+       lacks it).  Everything else -- names, `facet normal nx ny nz`, `outer loop` -- is skipped. */
+    std::unique_ptr<char[]> text(new char[size + 1]);
+    f.read(text.get(), (std::streamsize)size);
+    if ((size_t)f.gcount() != size) return PPP_ERR_IO;
+    const char *p = text.get(), *end = p + size;
+    auto next = [&](const char **t, const char **te) {
+        while (p < end && (unsigned char)*p <= ' ') ++p;
+        *t = p;
+        while (p < end && (unsigned char)*p > ' ') ++p;
+        *te = p;
+        return *t < *te;
+    };
+    const char *t, *te;
+    if (!next(&t, &te) || !token_is(t, te, "solid")) return PPP_ERR_IO;
+    std::vector<float> v;
+    int in_facet = -1; /* vertices of the open facet; -1: none open */
+    bool closed = false;
+    while (next(&t, &te)) {
+        if (closed) { if (token_is(t, te, "solid")) closed = false; continue; } /* (the name after endsolid; a further solid of the same file) */
+        if (token_is(t, te, "facet")) {
+            if (in_facet >= 0) return PPP_ERR_IO;
+            in_facet = 0;
+        } else if (token_is(t, te, "vertex")) {
+            if (in_facet < 0 || in_facet >= 3) return PPP_ERR_IO;
+            for (int d = 0; d < 3; ++d) {
+                if (!next(&t, &te)) return PPP_ERR_IO;
+                const unsigned char c0 = (unsigned char)std::tolower((unsigned char)*t);
+                if (!((c0 >= '0' && c0 <= '9') || c0 == '+' || c0 == '-' || c0 == '.' || c0 == 'n' || c0 == 'i')) return PPP_ERR_IO;
+                const char *tok_end;
+                v.push_back(parse_float_token(t, te, &tok_end));
+            }
+            ++in_facet;
+        } else if (token_is(t, te, "endfacet")) {
+            if (in_facet != 3) return PPP_ERR_IO;
+            in_facet = -1;
+        } else if (token_is(t, te, "endsolid")) {
+            if (in_facet >= 0) return PPP_ERR_IO;
+            closed = true;
+        }
+    }
+    if (!closed || in_facet >= 0 || v.size() % 9) return PPP_ERR_IO;
+    float *out = (float *)malloc(sizeof(float) * std::max<size_t>(v.size(), 1));
+    if (!out) return PPP_ERR_IO;
+    if (!v.empty()) memcpy(out, v.data(), sizeof(float) * v.size());
+    *verts9 = out; *n_tris = v.size() / 9;
+    return PPP_OK;
+}
+
+static int save_stl_impl(const char *path, const float *verts9, size_t n_tris, int binary)
+{
+    if (!path || (!verts9 && n_tris) || binary < 0 || binary > 1) return PPP_ERR_ARG;
+    if (n_tris > 0xffffffffull) return PPP_ERR_CAPACITY;
+    FILE *f = fopen(path, "wb");
+    if (!f) return PPP_ERR_IO;
+    bool ok = true;
+    if (binary) {
+        char head[80];
+        memset(head, 0, sizeof(head));
+        snprintf(head, sizeof(head), "binary STL (libppp_hip)"); /* (never `solid`: some readers decide on that word alone) */
+        const uint32_t count = (uint32_t)n_tris;
+        ok = fwrite(head, 1, 80, f) == 80 && fwrite(&count, 4, 1, f) == 1;
+    } else ok = fprintf(f, "solid ppp\n") > 0;
+    for (size_t i = 0; i < n_tris && ok; ++i) {
+        const float *a = verts9 + 9 * i, *b = a + 3, *c = a + 6;
+        const double e1[3] = {(double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2]};
+        const double e2[3] = {(double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2]};
+        const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        const double A2 = std::sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        float nf[3] = {0.f, 0.f, 0.f};
+        if (A2 > 0.0 && std::isfinite(A2)) for (int d = 0; d < 3; ++d) nf[d] = (float)(n[d] / A2);
+        if (binary) {
+            unsigned char rec[50];
+            memcpy(rec, nf, 12);
+            memcpy(rec + 12, a, 36);
+            rec[48] = rec[49] = 0;
+            ok = fwrite(rec, 1, 50, f) == 50;
+        } else {
+            ok = fprintf(f, " facet normal %.9g %.9g %.9g\n  outer loop\n   vertex %.9g %.9g %.9g\n   vertex %.9g %.9g %.9g\n   vertex %.9g %.9g %.9g\n"
+                            "  endloop\n endfacet\n", nf[0], nf[1], nf[2], a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2]) > 0;
+        }
+    }
+    if (!binary && ok) ok = fprintf(f, "endsolid ppp\n") > 0;
+    return (fclose(f) == 0 && ok) ? PPP_OK : PPP_ERR_IO;
+}
+
 void ppp_default_config(ppp_config *c)
 {   /* config.txt:1-13 */
     memset(c, 0, sizeof(*c));
@@ -680,6 +805,14 @@ int ppp_save_pcd(const char *path, const float *xyz, size_t n, size_t stride_flo
 int ppp_save_pcd_rgb(const char *path, const float *xyz, const unsigned char *rgb, size_t n, const float viewpoint[7], int binary)
 {
     try { return save_pcd_rgb_impl(path, xyz, rgb, n, viewpoint, binary); } catch (...) { return PPP_ERR_IO; }
+}
+int ppp_load_stl(const char *path, float **verts9, size_t *n_tris)
+{
+    try { return load_stl_impl(path, verts9, n_tris); } catch (...) { if (verts9) *verts9 = nullptr; if (n_tris) *n_tris = 0; return PPP_ERR_IO; }
+}
+int ppp_save_stl(const char *path, const float *verts9, size_t n_tris, int binary)
+{
+    try { return save_stl_impl(path, verts9, n_tris, binary); } catch (...) { return PPP_ERR_IO; }
 }
 int ppp_read_config(const char *path, ppp_config *c)
 {

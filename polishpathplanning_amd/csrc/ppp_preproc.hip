@@ -1,7 +1,8 @@
 /*
  * ppp_preproc.hip -- the preprocessing calls of the C ABI (include/ppp_hip.h) on the resident cloud: ppp_trans2center, ppp_transform_cloud,
  * ppp_remove_outlier, ppp_voxel_down, ppp_smooth_mls, and what they share (the opening, the adoption of the filtered cloud,
- * the sensor-frame copy of an aligned cloud).  The unit owns the kernels of ppp_preproc.h and ppp_align.h; of the handle and
+ * the sensor-frame copy of an aligned cloud); and ppp_set_cloud_mesh, which makes a resident cloud of a triangle mesh.  The unit
+ * owns the kernels of ppp_preproc.h, ppp_align.h and ppp_mesh.h; of the handle and
  * the plan it sees what ppp_handle.h declares.  Compiled with the engine's flags.
  */
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
@@ -11,6 +12,7 @@
 #include "ppp_preproc.h"
 #include "ppp_align.h"
 #include "ppp_sort.h"
+#include "ppp_mesh.h"
 #include <cstring>
 
 extern "C" {
@@ -312,6 +314,122 @@ int ppp_smooth_mls(ppp_handle h, double search_radius, int order, size_t *n_out)
     if (rc) return rc;
     if (n_out) *n_out = (size_t)n_kept;
     return adopt_cloud(h, X2, Y2, Z2, (size_t)n_kept);
+}
+
+/* ---- a triangle mesh sampled into the resident cloud (ppp_mesh.h) ---- */
+void ppp_default_mesh_params(ppp_mesh_params *mp)
+{
+    if (!mp) return;
+    mp->pitch = 0.5f; mp->facing = PPP_MESH_ALL;
+}
+
+namespace {
+/* a scan of the sampler, under the handle's kernel timers like a launch */
+static int mesh_scan(ppp_handle h, const char *name, DevBuf<char> &tmp, const unsigned *in, unsigned *out, size_t n)
+{
+    size_t bytes = 0;
+    HIPCHK(h, ppp_scan_exclusive_u32(nullptr, &bytes, in, out, n, h->stream));
+    HIPCHK(h, tmp.ensure(bytes));
+    KTimer *t = h->timing ? timer_for(h, name) : nullptr;
+    if (t) (void)hipEventRecord(t->e0[t->used], h->stream);
+    const hipError_t e = ppp_scan_exclusive_u32(tmp.p, &bytes, in, out, n, h->stream);
+    if (t) { (void)hipEventRecord(t->e1[t->used], h->stream); t->used++; }
+    HIPCHK(h, e);
+    return PPP_OK;
+}
+constexpr size_t MESH_CLOUD_MAX = 0x7fffffffu / 8; /* the points of a resident cloud (set_cloud_common) */
+} // namespace
+
+int ppp_set_cloud_mesh(ppp_handle h, const float *verts, size_t n_verts, const int *tris, size_t n_tris, const ppp_mesh_params *mp,
+                       const float *viewpoint, int *tri_index, size_t cap, ppp_mesh_stats *stats)
+{
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h) return PPP_ERR_ARG;
+    if (!verts || !mp) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: vertices and parameters are required");
+    if (!(mp->pitch > 0.f) || !std::isfinite(mp->pitch)) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: the pitch must be positive and finite");
+    if (mp->facing != PPP_MESH_ALL && mp->facing != PPP_MESH_FRONT) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: facing is PPP_MESH_ALL or PPP_MESH_FRONT");
+    if (n_tris == 0) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: no triangle");
+    if (!tris && (n_verts % 3 || n_verts / 3 != n_tris)) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: a soup (tris == NULL) has three vertices per triangle");
+    if (n_tris > MESH_CLOUD_MAX || n_verts > MESH_CLOUD_MAX) return fail(h, PPP_ERR_CAPACITY, "set_cloud_mesh: mesh too large");
+    if (stats) stats->triangles = n_tris;
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcs = settle(h); if (rcs) return rcs; }
+    if (h->part_given) return fail(h, PPP_ERR_UNSUPPORTED, "set_cloud_mesh: this handle holds a part (ppp_set_cloud_part): a mesh is sampled whole");
+    size_t samples = 0;
+    { /* scratch, freed before the plan of the new cloud */
+        DevBuf<char> raw, tmp;
+        DevBuf<float> V;
+        DevBuf<int> T, tri_dev;
+        DevBuf<unsigned> R, row_off, M, col_off, cnt;
+        const size_t nv = std::max<size_t>(n_verts, 1);
+        hipError_t e = raw.ensure(12 * nv);
+        if (e == hipSuccess) e = V.ensure(3 * nv);
+        if (e == hipSuccess && tris) e = T.ensure(3 * n_tris);
+        if (e == hipSuccess) e = R.ensure(n_tris + 1);
+        if (e == hipSuccess) e = row_off.ensure(n_tris + 1);
+        if (e == hipSuccess) e = cnt.ensure(2);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("set_cloud_mesh buffers: ") + hipGetErrorString(e));
+        /* the vertices become resident ones by the conversion of every cloud (k_ingest) */
+        if (n_verts) {
+            HIPCHK(h, hipMemcpyAsync(raw.p, verts, 12 * n_verts, hipMemcpyHostToDevice, h->stream));
+#ifdef PPP_KERNELS_FOREIGN /* (the engine's kernel, instantiated here: ppp_kernels.h) */
+            LAUNCH(h, "k_ingest", k_ingest<>, (unsigned)((n_verts + 255) / 256), 256, 0, raw.p, (size_t)12, (int)n_verts, h->P.change_range, V.p, V.p + nv, V.p + 2 * nv);
+#else
+            LAUNCH(h, "k_ingest", k_ingest, (unsigned)((n_verts + 255) / 256), 256, 0, raw.p, (size_t)12, (int)n_verts, h->P.change_range, V.p, V.p + nv, V.p + 2 * nv);
+#endif
+        }
+        if (tris) HIPCHK(h, hipMemcpyAsync(T.p, tris, 12 * n_tris, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(cnt.p, 0, 2 * sizeof(unsigned), h->stream));
+        MeshArgs A;
+        A.Vx = V.p; A.Vy = V.p + nv; A.Vz = V.p + 2 * nv; A.n_verts = (int)n_verts;
+        A.tris = tris ? T.p : nullptr; A.n_tris = (int)n_tris;
+        A.pitch = (double)mp->pitch; A.front = mp->facing == PPP_MESH_FRONT;
+        for (int d = 0; d < 3; ++d) A.vp[d] = viewpoint ? (double)viewpoint[d] : 0.0;
+        LAUNCH(h, "k_mesh_rows", k_mesh_rows, (unsigned)((n_tris + 1 + MESH_T - 1) / MESH_T), MESH_T, 0, A, R.p, cnt.p);
+        { int rc = mesh_scan(h, "mesh_scan_rows", tmp, R.p, row_off.p, n_tris + 1); if (rc) return rc; }
+        unsigned hcnt[2] = {0, 0}, rows = 0;
+        HIPCHK(h, hipMemcpyAsync(hcnt, cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(&rows, row_off.p + n_tris, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (stats) { stats->degenerate = hcnt[0]; stats->culled = hcnt[1]; stats->sampled = n_tris - hcnt[0] - hcnt[1]; stats->rows = rows; }
+        if (rows == 0) return fail(h, PPP_ERR_ARG, "set_cloud_mesh: no sample: every triangle is degenerate or culled");
+        if (rows > MESH_CLOUD_MAX) return fail(h, PPP_ERR_CAPACITY, "set_cloud_mesh: too many rows for a resident cloud: the pitch is too small for this mesh");
+        e = M.ensure((size_t)rows + 1);
+        if (e == hipSuccess) e = col_off.ensure((size_t)rows + 1);
+        if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("set_cloud_mesh buffers: ") + hipGetErrorString(e));
+        LAUNCH(h, "k_mesh_cols", k_mesh_cols, (unsigned)(((size_t)rows + 1 + MESH_T - 1) / MESH_T), MESH_T, 0, A, row_off.p, rows, M.p);
+        { int rc = mesh_scan(h, "mesh_scan_cols", tmp, M.p, col_off.p, (size_t)rows + 1); if (rc) return rc; }
+        unsigned total = 0;
+        HIPCHK(h, hipMemcpyAsync(&total, col_off.p + rows, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (stats) stats->samples = total;
+        if (total > MESH_CLOUD_MAX) return fail(h, PPP_ERR_CAPACITY, "set_cloud_mesh: too many samples for a resident cloud: the pitch is too small for this mesh");
+        samples = total;
+        const size_t k = tri_index ? std::min(cap, samples) : 0;
+        /* the samples land where the points of ppp_set_cloud do: the handle's staging buffer, as packed records */
+        HIPCHK(h, h->scratch.ensure(12 * samples));
+        if (k) HIPCHK(h, tri_dev.ensure(samples));
+        LAUNCH(h, "k_mesh_fill", k_mesh_fill, (unsigned)((samples + MESH_T - 1) / MESH_T), MESH_T, 0, A, row_off.p, col_off.p, rows, total,
+               (float *)h->scratch.p, k ? tri_dev.p : nullptr);
+        if (k) HIPCHK(h, hipMemcpyAsync(tri_index, tri_dev.p, k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    /* ... and go the way those points go, their conversion without the x1000: plan, bounds, viewpoint, caches as ppp_set_cloud leaves them */
+    return set_cloud_resident(h, (const float *)h->scratch.p, samples, viewpoint);
+}
+
+int ppp_set_cloud_stl(ppp_handle h, const char *path, const ppp_mesh_params *mp, const float *viewpoint, ppp_mesh_stats *stats)
+{
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h) return PPP_ERR_ARG;
+    if (!path) return fail(h, PPP_ERR_ARG, "set_cloud_stl: no file name");
+    float *v9 = nullptr;
+    size_t nt = 0;
+    int rc = ppp_load_stl(path, &v9, &nt);
+    if (rc != PPP_OK) return fail(h, rc, std::string("not a readable STL file: ") + path);
+    rc = ppp_set_cloud_mesh(h, v9, 3 * nt, nullptr, nt, mp, viewpoint, nullptr, 0, stats);
+    ppp_free(v9);
+    return rc;
 }
 
 } // extern "C"

@@ -80,6 +80,7 @@ EXPORTS = [
     "ppp_write_path_file", "ppp_run_batch_async", "ppp_sync_batch", "ppp_get_stream", "ppp_gather_waypoints", "ppp_get_cloud", "ppp_remove_outlier", "ppp_voxel_down", "ppp_smooth_mls", "ppp_trans2center", "ppp_get_waypoint_counts", "ppp_copy_stage_to_device", "ppp_finish_path_async",
     "ppp_save_pcd_rgb", "ppp_range_interval", "ppp_set_cloud_part", "ppp_spline_create", "ppp_spline_restart", "ppp_spline_eval", "ppp_spline_range", "ppp_spline_destroy",
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
+    "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -257,6 +258,12 @@ def lib():
         L.ppp_set_cloud_pcd.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_float)]
         L.ppp_pcd_probe.argtypes = [C.c_char_p, C.c_void_p]
         L.ppp_get_fast_path.argtypes = [vp, ip]
+        L.ppp_default_mesh_params.argtypes = [C.POINTER(MeshParams)]
+        L.ppp_default_mesh_params.restype = None
+        L.ppp_set_cloud_mesh.argtypes = [vp, fp, sz, ip, sz, C.POINTER(MeshParams), fp, ip, sz, C.POINTER(MeshStats)]
+        L.ppp_set_cloud_stl.argtypes = [vp, C.c_char_p, C.POINTER(MeshParams), fp, C.POINTER(MeshStats)]
+        L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
+        L.ppp_save_stl.argtypes = [C.c_char_p, fp, sz, C.c_int]
         _lib = L
     return _lib
 
@@ -292,6 +299,43 @@ def load_pcd(path):
     xyz = np.ctypeslib.as_array(p, shape=(max(n.value, 1) * 3,))[: n.value * 3].reshape(-1, 3).copy()
     L.ppp_free(p)
     return xyz, vp
+
+
+MESH_ALL, MESH_FRONT = 0, 1  # PPP_MESH_*
+
+
+class MeshParams(C.Structure):  # ppp_mesh_params
+    _fields_ = [("pitch", C.c_float), ("facing", C.c_int)]
+
+
+class MeshStats(C.Structure):  # ppp_mesh_stats
+    _fields_ = [("triangles", C.c_size_t), ("sampled", C.c_size_t), ("degenerate", C.c_size_t), ("culled", C.c_size_t),
+                ("rows", C.c_size_t), ("samples", C.c_size_t)]
+
+
+def _mesh_stats(st):
+    return {k: int(getattr(st, k)) for k, _ in MeshStats._fields_}
+
+
+def load_stl(path):
+    """ppp_load_stl: the triangles of a binary or ASCII STL file as a soup, float32 [n_tris, 3, 3] (triangle, vertex, xyz)."""
+    L = lib()
+    p = C.POINTER(C.c_float)()
+    n = C.c_size_t()
+    rc = L.ppp_load_stl(path.encode(), C.byref(p), C.byref(n))
+    if rc:
+        raise PPPError(rc, "cannot read STL %s" % path)
+    v = np.ctypeslib.as_array(p, shape=(max(n.value, 1) * 9,))[: n.value * 9].reshape(-1, 3, 3).copy()
+    L.ppp_free(p)
+    return v
+
+
+def save_stl(path, verts9, binary=True):
+    """ppp_save_stl: a soup (anything that reshapes to n_tris x 9 floats) as a binary or ASCII STL file."""
+    v = np.ascontiguousarray(verts9, np.float32).reshape(-1, 9)
+    rc = lib().ppp_save_stl(path.encode(), _f(v), v.shape[0], 1 if binary else 0)
+    if rc:
+        raise PPPError(rc, "cannot write STL %s" % path)
 
 
 class PlannerQueue:
@@ -1169,6 +1213,48 @@ class Engine:
         self._chk(self.L.ppp_set_cloud_pcd(self.h, path.encode(), C.byref(n), _f(vp)))
         self.n = n.value
         return n.value, vp
+
+    def _mesh_params(self, pitch, facing):
+        mp = MeshParams()
+        self.L.ppp_default_mesh_params(C.byref(mp))
+        mp.pitch, mp.facing = float(pitch), int(facing)
+        return mp
+
+    def set_cloud_mesh(self, verts, tris=None, pitch=0.5, facing=MESH_ALL, viewpoint=None, tri_index=False):
+        """ppp_set_cloud_mesh: the surface of a triangle mesh, sampled on the device at about 1 / pitch^2 (resident units), becomes the
+        resident cloud.  verts [n_verts, 3] in the file's units, tris [n_tris, 3] indices or None for a soup (three vertices per
+        triangle).  Returns the stats as a dict, with "tri_index" (the triangle of every sample) in it when asked.  A refused call
+        fills "stats" of the PPPError it raises."""
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        n_tris = verts.shape[0] // 3 if tris is None else None
+        ti = None
+        if tris is not None:
+            ti = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+            n_tris = ti.shape[0]
+        vp = None if viewpoint is None else _f(np.ascontiguousarray(viewpoint, np.float32))
+        mp, st = self._mesh_params(pitch, facing), MeshStats()
+        args = (self.h, _f(verts), verts.shape[0], None if ti is None else _i(ti), n_tris, C.byref(mp), vp)
+        try:
+            self._chk(self.L.ppp_set_cloud_mesh(*args, None, 0, C.byref(st)))
+        except PPPError as e:
+            e.stats = _mesh_stats(st)
+            raise
+        out = _mesh_stats(st)
+        self.n = out["samples"]
+        if tri_index:  # (the count is known only now: a second sampling, the same bits)
+            idx = np.empty(max(self.n, 1), np.int32)
+            self._chk(self.L.ppp_set_cloud_mesh(*args, _i(idx), self.n, C.byref(st)))
+            out["tri_index"] = idx[:self.n]
+        return out
+
+    def set_cloud_stl(self, path, pitch=0.5, facing=MESH_ALL, viewpoint=None):
+        """ppp_set_cloud_stl: set_cloud_mesh of the soup of an STL file.  Returns the stats as a dict."""
+        vp = None if viewpoint is None else _f(np.ascontiguousarray(viewpoint, np.float32))
+        mp, st = self._mesh_params(pitch, facing), MeshStats()
+        self._chk(self.L.ppp_set_cloud_stl(self.h, path.encode(), C.byref(mp), vp, C.byref(st)))
+        out = _mesh_stats(st)
+        self.n = out["samples"]
+        return out
 
     def range_interval(self, min_x, max_x):
         """(lo, hi, S): the planner-unit x interval this handle's slice range indexes for a cloud with these x bounds."""
