@@ -1410,7 +1410,10 @@ def test_voxel_down_matches_the_oracle(engine_mod, oracle_mod, leaf):
 def test_mls_smooth_matches_the_oracle(engine_mod, oracle_mod, order):
     """SectPath::smooth (Smooth = true; pcl::MovingLeastSquares order 3 radius 15): the same points survive, coordinates
     equal to the last float bit but for rare 1-ulp cases (f64 sums grouped differently), and the plan on the smoothed
-    cloud agrees within the waypoint tolerance."""
+    cloud agrees within the waypoint tolerance.
+    Measured by test_filter_adversaries.sheet_sample(oracle_mod, 2000) (float64 in ascending and in reversed neighbour order,
+    longdouble, at 2 000 points of this cloud drawn by default_rng(8)): at orders 1, 2 and 3 none of them rounds to different
+    float32 triples, a share below 5e-4."""
     pts, cfg = synth.make_config("small_40k")
     rng = np.random.default_rng(8)
     pts = pts.copy()
