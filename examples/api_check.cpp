@@ -4,7 +4,10 @@
 //                                    (Spline.h:10-42: constructor, point, miny/bigy, restart, copies by value).
 //   api_check cloud.pcd position mesh.stl  -> also the mesh calls: a two-triangle plate written with ppp_save_stl, read back with
 //                                    ppp_load_stl, sampled through ppp::Planner::set_mesh (ppp_set_cloud_mesh, ppp_default_mesh_params)
-//                                    and through Planner::open of the file (ppp_set_cloud_stl): both give the same cloud.
+//                                    and through Planner::open of the file (ppp_set_cloud_stl): both give the same cloud;
+//                                    and the exact calls: ppp::TriMesh of the file and of the arrays (ppp_trimesh_create_stl,
+//                                    ppp_trimesh_create, ppp_default_trimesh_params, ppp_trimesh_destroy), one point through
+//                                    ppp_trimesh_nearest, the sampled cloud through Planner::mesh_deviation (ppp_get_mesh_deviation).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -68,6 +71,22 @@ int main(int argc, char **argv)
         if (ok) ok = ppp_set_cloud_stl(b.handle(), argv[3], &mp, nullptr, &st2) == PPP_OK;
         ppp_free(back);
         std::printf("mesh %d %zu %zu %zu %zu %zu\n", ok ? 1 : 0, nt, st1.samples, st2.samples, n1, n2);
+        // the same plate as triangles: a point 2 mm above its middle, and the sampled cloud against its own mesh
+        ppp_trimesh_params tp;
+        ppp_default_trimesh_params(&tp);
+        ppp::TriMesh m1, m2;
+        const float q[3] = {20.f, 15.f, 1502.f}; /* resident units: mm */
+        double dist = -1, dev = 0;
+        int tri = -2;
+        unsigned char region = 0, status = 0;
+        ppp_mesh_deviation_stats ms = {};
+        ppp_deviation_params dp;
+        ppp_default_deviation_params(&dp);
+        bool ok2 = ok && m1.open_stl(a.handle(), argv[3], &tp) == PPP_OK && m2.create(a.handle(), plate, 6, nullptr, 2, &tp) == PPP_OK;
+        if (ok2) ok2 = ppp_trimesh_nearest(m2.get(), q, 1, 5.f, &dist, nullptr, &dev, &tri, &region, &status) == PPP_OK;
+        if (ok2) ok2 = a.mesh_deviation(m1, ms, dp);
+        std::printf("trimesh %d %zu %zu %d %d %d %.9g %.9g %zu %zu %.9g\n", ok2 ? 1 : 0, m1.stats().indexed, m2.stats().indexed, tri, (int)region, (int)status, dist,
+                    dev, ms.dev.matched, ms.on_face, ms.dev.matched ? ms.max_distance : -1.0);
     }
     return 0;
 }

@@ -13,6 +13,8 @@
 // PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP), before the path is planned and before the deviation is taken; PPP_REGISTER_KEEP=<share below 1> beside PPP_REGISTER=1 runs the trimmed loop instead (every evaluation keeps that share of its pairs with the smallest pair distance: for a scan with a clamp, a burr or an edge the reference does not have; the kept and the paired counts and the cut are printed); PPP_REGISTER=global does so from an unknown pose (PPP_REGISTER_CANDIDATES, _STRIDE, _COARSE_MAXDIST).  PPP_REGISTER=robust weighs every pair by Tukey's biweight of its point-to-plane residual, scaled by the median absolute residual of each evaluation (no share to choose; PPP_REGISTER_TUNE, _SIGMA_MIN; the used and the paired counts, the median and sigma are printed).  Dynamic_adjustment = false in the config plans the same walk without the adjustment.
 // A name that ends in .stl (any case) is a triangle mesh, the nominal part as a CAD export: its surface is sampled on the device into the cloud (PPP_MESH_PITCH, default 0.5 mm; PPP_MESH_FACING=front keeps
 // the triangles that face the origin).  PPP_DEVIATION=<reference.stl> ./connect scan.pcd measures (and with PPP_REGISTER registers) the scan against the mesh; ./connect part.stl plans on the nominal itself.
+// PPP_DEVIATION=<reference.stl> PPP_DEVIATION_EXACT=1 measures against the triangles themselves (ppp_get_mesh_deviation: the closest point on the nearest triangle, along that facet's normal; no pitch):
+// the same block, plus the closest points by region; PPP_TRIMESH_CELL sets the grid's cell (0 = automatic; the numbers do not depend on it), PPP_TRIMESH_ORIENT=viewpoint turns every facet normal to the origin's side.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -52,7 +54,9 @@ int main(int argc, char **argv)
     if (con && con[0] == '1') path_planner.get_path_contacts();
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
-    if (reference) path_planner.get_deviation(*reference); /* before the schedules: they take its target */
+    const char *exact = std::getenv("PPP_DEVIATION_EXACT");
+    if (reference && exact && exact[0] == '1' && ppp::Planner::is_stl_name(devf)) path_planner.get_mesh_deviation(devf); /* against the triangles */
+    else if (reference) path_planner.get_deviation(*reference); /* before the schedules: they take its target */
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();
     const char *fed = std::getenv("PPP_PATH_FEED");

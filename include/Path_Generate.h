@@ -86,6 +86,9 @@ public:
        (ppp_get_deviation; max_dist, smooth_radius, allowance and gain from PPP_DEVIATION_MAXDIST, _SMOOTH, _ALLOWANCE, _GAIN).
        Needs no pass.  The target map is kept: get_path_dwell() and get_path_feed() after it steer the removal towards it */
     void get_deviation(const path_generater &ref) { planner.print_deviation(ref.planner, ppp::Planner::deviation_params_env(), &deviation_target); }
+    /* get_deviation() against the triangles of the STL file `stl` themselves (ppp_get_mesh_deviation; PPP_TRIMESH_CELL,
+       PPP_TRIMESH_ORIENT=viewpoint): the same lines, and the closest points by region */
+    void get_mesh_deviation(const std::string &stl) { planner.print_mesh_deviation(stl, ppp::Planner::deviation_params_env(), &deviation_target); }
     /* this planner's cloud, the scan, registered to the cloud of ref by point-to-plane ICP from the identity (ppp_register;
        max_dist, iterations and min_step from PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP): prints the pairs and the rms before
        and after, the steps, the locked unknowns and T, and moves the cloud by T when the loop converged (ppp_transform_cloud:

@@ -161,8 +161,8 @@ int ppp_get_cloud(ppp_handle h, float *xyz, size_t cap, size_t *n);
  * sample at all (every triangle degenerate or culled); PPP_ERR_CAPACITY: more rows or samples than a resident cloud holds
  * ((2^31 - 1) / 8 points, as ppp_set_cloud); PPP_ERR_UNSUPPORTED: the handle holds a part (ppp_set_cloud_part).  A refused call
  * leaves the resident cloud and the plan as they were.
- * Not here: the handle's normals stay the PCA normals of its samples (not the facets'), vertices are not welded, and no call
- * measures a point against a triangle.
+ * Not here: the handle's normals stay the PCA normals of its samples (not the facets'), and vertices are not welded.  A point is
+ * measured against the triangles themselves by ppp_trimesh_nearest and ppp_get_mesh_deviation, further down.
  * ppp_set_cloud_stl: ppp_load_stl + ppp_set_cloud_mesh of the soup; PPP_ERR_IO for a file that cannot be read. */
 enum { PPP_MESH_ALL = 0, PPP_MESH_FRONT = 1 };
 typedef struct { float pitch; int facing; } ppp_mesh_params;      /* defaults 0.5, PPP_MESH_ALL */
@@ -489,6 +489,86 @@ void ppp_default_deviation_params(ppp_deviation_params *dp);   /* +INFINITY, 0, 
 int  ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp,
                        double *deviation, double *smoothed, int *ref_index, unsigned char *status,
                        double *target, size_t cap, ppp_deviation_stats *stats);
+/* The nominal as a resident triangle mesh, and the exact deviation of a scan against it: the closest point on
+   the nearest triangle and the distance along that facet's own normal.  No pitch, no estimated normal.
+   ppp_trimesh_create: h lends its device, its stream and its change_range; verts / tris are ppp_set_cloud_mesh's (tris NULL = a
+   soup, n_verts must be 3 n_tris) and every vertex goes through the same conversion (the x1000 when change_range is set,
+   non-finite -> NaN).  After the call the mesh owns its buffers: it depends neither on h nor on any cloud, and nothing that
+   replaces, moves or preprocesses a resident cloud touches it.  ppp_trimesh_destroy(NULL) is allowed.
+   The triangle frame is 7s's (above): the vertices rotated cyclically so that (p0, p1) is the longest edge, e1 = p1 - p0,
+   e2 = p2 - p0, N = e1 x e2, A2 = sqrt((Nx Nx + Ny Ny) + Nz Nz).  Degenerate -- counted, never indexed, never returned -- is
+   7s's set: an index outside [0, n_verts), a coordinate that is not finite, A2 zero or not finite.  The facet normal is
+   n = (Nx / A2, Ny / A2, Nz / A2); with PPP_TRIMESH_VIEWPOINT it is negated when ((Nx (vx - p0x) + Ny (vy - p0y)) + Nz (vz -
+   p0z)) < 0, v = viewpoint in resident units (NULL = the origin); a value of exactly 0 keeps the winding.
+   The indexed triangles are listed in a uniform grid of cubic cells of side `cell` over their bounding box, every triangle in
+   every cell its axis-aligned box overlaps.  cell = 0 chooses it: the mean longest box side of the indexed triangles, doubled
+   until the grid has at most 2^24 cells and fewer than 2^31 - 1 (triangle, cell) pairs.  THE ANSWERS DO NOT DEPEND ON cell:
+   the grid decides which triangles a query looks at, not what it finds.  stats: triangles = n_tris = indexed + degenerate;
+   cells per axis; pairs and the longest list of one cell; the cell used; the box (resident units).  stats is filled as far as
+   the call got.
+   PPP_ERR_ARG: out, verts or tp NULL, cell negative or not finite, unknown orient, n_tris == 0, a soup with n_verts != 3 n_tris,
+   nothing indexed; PPP_ERR_CAPACITY: more triangles or vertices than (2^31 - 1) / 8, a given cell that breaks either bound
+   (never a silent change); PPP_ERR_IO (create_stl = ppp_load_stl + create): a file that cannot be read.  *out is NULL after
+   every refusal.
+
+   The search.  All arithmetic is in double, on resident floats widened to double, one rounding per written operation;
+   dot(u, v) = (ux vx + uy vy) + uz vz.  For a query p and a triangle in its rotated frame a = p0, b = p1, c = p2 the closest
+   point x is Ericson's region walk:
+     ab = b - a, ac = c - a, ap = p - a;  d1 = dot(ab, ap), d2 = dot(ac, ap)
+     if d1 <= 0 and d2 <= 0:                       x = a                                   (vertex)
+     bp = p - b;  d3 = dot(ab, bp), d4 = dot(ac, bp)
+     if d3 >= 0 and d4 <= d3:                      x = b                                   (vertex)
+     vc = d1 d4 - d3 d2
+     if vc <= 0 and d1 >= 0 and d3 <= 0:           v = d1 / (d1 - d3);  x = a + ab v       (edge)
+     cp = p - c;  d5 = dot(ab, cp), d6 = dot(ac, cp)
+     if d6 >= 0 and d5 <= d6:                      x = c                                   (vertex)
+     vb = d5 d2 - d1 d6
+     if vb <= 0 and d2 >= 0 and d6 <= 0:           w = d2 / (d2 - d6);  x = a + ac w       (edge)
+     va = d3 d6 - d5 d4
+     if va <= 0 and (d4 - d3) >= 0 and (d5 - d6) >= 0:
+                                                   w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  x = b + (c - b) w   (edge)
+     else:  den = 1 / ((va + vb) + vc);  v = vb den;  w = vc den;  x = (a + ab v) + ac w   (face)
+     e = p - x;  D2 = (ex ex + ey ey) + ez ez
+   the first test that holds decides.  The winner f* is the indexed triangle with the smallest (D2, f), f its index in the
+   caller's list: a tie goes to the lower index.  md2 = (double)max_dist * (double)max_dist (+INFINITY: no limit).
+     status     PPP_DEV_DROPPED if the query is not finite; PPP_DEV_TOO_FAR if no indexed triangle has D2 <= md2 (a triangle at
+                exactly md2 matches); otherwise PPP_DEV_MATCHED.  PPP_DEV_NO_NORMAL cannot occur.
+     matched    tri_index = f*; region = 0 face, 1 edge, 2 vertex; distance = sqrt(D2); closest = x (three doubles);
+                deviation = ((ex nx) + ey ny) + ez nz with f*'s facet normal n.  In the face region the deviation is the signed
+                distance; on an edge or a vertex it is the component along the winning facet's normal -- 7j's convention, "along
+                the normal of the nearest reference element" --, and distance and region say which case applies.  Pseudonormals
+                and inside / outside of closed meshes are out of scope.
+     otherwise  tri_index -1, region 255, every double the one quiet NaN of the deviation maps.
+   Minima over (D2, f) have no order: the maps are the same bits in every run and for every cell.
+   ppp_trimesh_nearest: the primitive.  n packed xyz points in RESIDENT units (no x1000) against the mesh, on the mesh's own
+   stream; every output may be NULL; blocks.  PPP_ERR_ARG: m NULL, xyz NULL with n > 0, max_dist not > 0.
+   ppp_get_mesh_deviation: the search over h's resident cloud (its points in the handle's slab order), then ppp_get_deviation's
+   own tail: smoothed, target and every field of stats->dev are defined by that call's comment word for word, with MATCHED
+   read as "matched to a triangle", no_normal = 0 and max_dist2 = (float)D2 of the farthest matched point.  on_face + on_edge
+   + on_vertex = matched; max_distance = the largest distance (NaN when nothing matched).  Each map receives its first
+   min(cap, n) entries; every output may be NULL, cap = 0 asks for the statistics alone.  Needs a cloud and parameters, not a
+   pass; builds h's slab index where it is missing; runs on h's stream, blocks, keeps nothing.
+   PPP_ERR_ARG: m or dp NULL, ppp_get_deviation's conditions on dp (the integer-sum guard included), no cloud, a mesh on another
+   device than h.  PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+typedef struct ppp_trimesh_s *ppp_trimesh;
+enum { PPP_TRIMESH_WINDING = 0, PPP_TRIMESH_VIEWPOINT = 1 };
+typedef struct { float cell; int orient; } ppp_trimesh_params;          /* defaults 0 (= automatic), PPP_TRIMESH_WINDING */
+typedef struct { size_t triangles, indexed, degenerate; size_t cells[3]; size_t pairs, max_per_cell;
+                 float cell; float mn[3], mx[3]; } ppp_trimesh_stats;
+void ppp_default_trimesh_params(ppp_trimesh_params *tp);
+int  ppp_trimesh_create(ppp_handle h, const float *verts, size_t n_verts, const int *tris, size_t n_tris,
+                        const ppp_trimesh_params *tp, const float *viewpoint, ppp_trimesh *out, ppp_trimesh_stats *stats);
+int  ppp_trimesh_create_stl(ppp_handle h, const char *path, const ppp_trimesh_params *tp, const float *viewpoint,
+                            ppp_trimesh *out, ppp_trimesh_stats *stats);
+void ppp_trimesh_destroy(ppp_trimesh m);
+int  ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist,
+                         double *distance, double *closest, double *deviation, int *tri_index,
+                         unsigned char *region, unsigned char *status);
+typedef struct { ppp_deviation_stats dev; size_t on_face, on_edge, on_vertex; double max_distance; } ppp_mesh_deviation_stats;
+int  ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp,
+                            double *deviation, double *smoothed, double *distance, int *tri_index,
+                            unsigned char *region, unsigned char *status, double *target, size_t cap,
+                            ppp_mesh_deviation_stats *stats);
 /* Registration of a scan to a reference cloud: point-to-plane ICP.  h holds the scan, ref the nominal
    cloud (or the scan before the process); the result T = (R | t), row-major 3 x 4 in double, carries a resident point of h into
    ref's frame.  ppp_get_deviation does not register; these calls do, and ppp_transform_cloud applies their result.  ICP is a

@@ -111,6 +111,56 @@ private:
     }
 };
 
+/* A resident triangle mesh with its grid (ppp_trimesh): the nominal part as triangles, for the exact deviation.
+   Made on a handle's device; it owns its buffers and needs that handle no longer.  Move-only. */
+class TriMesh {
+public:
+    TriMesh() = default;
+    ~TriMesh() { ppp_trimesh_destroy(m_); }
+    TriMesh(const TriMesh &) = delete;
+    TriMesh &operator=(const TriMesh &) = delete;
+    TriMesh(TriMesh &&o) noexcept : m_(o.m_), st_(o.st_) { o.m_ = nullptr; }
+    TriMesh &operator=(TriMesh &&o) noexcept
+    {
+        if (this != &o) { ppp_trimesh_destroy(m_); m_ = o.m_; st_ = o.st_; o.m_ = nullptr; }
+        return *this;
+    }
+    /* ppp_default_trimesh_params with what the environment sets: PPP_TRIMESH_CELL (resident units; 0 = automatic) and
+       PPP_TRIMESH_ORIENT=viewpoint (every facet normal towards the viewpoint, the origin) */
+    static ppp_trimesh_params params_from_env()
+    {
+        ppp_trimesh_params tp;
+        ppp_default_trimesh_params(&tp);
+        if (const char *v = std::getenv("PPP_TRIMESH_CELL")) tp.cell = (float)std::atof(v);
+        if (const char *v = std::getenv("PPP_TRIMESH_ORIENT")) tp.orient = std::string(v) == "viewpoint" ? PPP_TRIMESH_VIEWPOINT : PPP_TRIMESH_WINDING;
+        return tp;
+    }
+    /* the mesh a caller holds in arrays (tris == nullptr: a soup), or an STL file; tp == nullptr: params_from_env().  The return
+       value is ppp_trimesh_create's code; a mesh held before is released first */
+    int create(ppp_handle h, const float *verts, size_t n_verts, const int *tris, size_t n_tris, const ppp_trimesh_params *tp = nullptr,
+               const float *viewpoint = nullptr)
+    {
+        const ppp_trimesh_params env = params_from_env();
+        ppp_trimesh_destroy(m_);
+        m_ = nullptr;
+        return ppp_trimesh_create(h, verts, n_verts, tris, n_tris, tp ? tp : &env, viewpoint, &m_, &st_);
+    }
+    int open_stl(ppp_handle h, const std::string &name, const ppp_trimesh_params *tp = nullptr, const float *viewpoint = nullptr)
+    {
+        const ppp_trimesh_params env = params_from_env();
+        ppp_trimesh_destroy(m_);
+        m_ = nullptr;
+        return ppp_trimesh_create_stl(h, name.c_str(), tp ? tp : &env, viewpoint, &m_, &st_);
+    }
+    ppp_trimesh get() const { return m_; }
+    explicit operator bool() const { return m_ != nullptr; }
+    const ppp_trimesh_stats &stats() const { return st_; }
+
+private:
+    ppp_trimesh m_ = nullptr;
+    ppp_trimesh_stats st_ = {};
+};
+
 /* One engine handle + the state every planner class of the reference keeps. */
 class Planner {
 public:
@@ -496,6 +546,45 @@ public:
         }
         return rc == PPP_OK ? true : report(rc);
     }
+    /* deviation() against the triangles themselves (ppp_get_mesh_deviation): per scan point the closest point on the
+       nearest triangle of mesh and the offset's component along that facet's own normal -- no pitch, no estimated normal --, then
+       deviation()'s smoothing, target and statistics; st.on_face / on_edge / on_vertex say where the closest points lie.  The maps
+       asked for come by cloud index */
+    bool mesh_deviation(const TriMesh &mesh, ppp_mesh_deviation_stats &st, const ppp_deviation_params &dp, std::vector<double> *target = nullptr,
+                        std::vector<double> *smoothed = nullptr, std::vector<unsigned char> *status = nullptr, std::vector<double> *distance = nullptr,
+                        std::vector<unsigned char> *region = nullptr)
+    {
+        size_t n = 0;
+        int rc = (target || smoothed || status || distance || region) ? ppp_num_points(h_, &n) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (target) target->assign(n, 0.0);
+            if (smoothed) smoothed->assign(n, 0.0);
+            if (status) status->assign(n, (unsigned char)PPP_DEV_DROPPED);
+            if (distance) distance->assign(n, 0.0);
+            if (region) region->assign(n, (unsigned char)255);
+            rc = ppp_get_mesh_deviation(h_, mesh.get(), &dp, nullptr, smoothed ? smoothed->data() : nullptr, distance ? distance->data() : nullptr, nullptr,
+                                        region ? region->data() : nullptr, status ? status->data() : nullptr, target ? target->data() : nullptr, n, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* print_deviation()'s three lines for the STL file `name` measured as triangles (TriMesh::params_from_env()), and a fourth:
+       the closest points by region and the largest distance */
+    void print_mesh_deviation(const std::string &name, const ppp_deviation_params &dp, std::vector<double> *target = nullptr)
+    {
+        TriMesh mesh;
+        ppp_mesh_deviation_stats ms = {};
+        const int rc = mesh.open_stl(h_, name);
+        if (rc == PPP_ERR_IO) std::fprintf(stderr, "Cloudn't read file!\n");
+        else if (rc != PPP_OK) report(rc);
+        else
+            std::fprintf(stderr, "ppp: %s: %zu triangles (%zu degenerate) in %zu x %zu x %zu cells of %g: %zu pairs, %zu at most in a cell\n", name.c_str(),
+                         mesh.stats().triangles, mesh.stats().degenerate, mesh.stats().cells[0], mesh.stats().cells[1], mesh.stats().cells[2],
+                         (double)mesh.stats().cell, mesh.stats().pairs, mesh.stats().max_per_cell);
+        if (rc != PPP_OK || !mesh_deviation(mesh, ms, dp, target)) { ms = ppp_mesh_deviation_stats{}; if (target) target->clear(); }
+        print_deviation_lines(ms.dev, dp);
+        std::printf("deviation: closest points: %zu on a face, %zu on an edge, %zu on a vertex; largest distance %f mm\n", ms.on_face, ms.on_edge,
+                    ms.on_vertex, ms.dev.matched ? ms.max_distance : 0.0);
+    }
     /* deviation() for the points this planner owns (ppp_get_deviation_tile): this planner holds the scan with a
        slice range (or whole: it then owns everything), ref the reference, whole or a slice range that covers the owned interval
        widened by halo >= dp.max_dist + dp.smooth_radius.  part is what ppp_merge_deviation_tiles takes, with the maps asked for
@@ -545,6 +634,10 @@ public:
     {
         ppp_deviation_stats st = {};
         if (!deviation(ref, st, dp, target)) { st = ppp_deviation_stats{}; if (target) target->clear(); }
+        print_deviation_lines(st, dp);
+    }
+    static void print_deviation_lines(const ppp_deviation_stats &st, const ppp_deviation_params &dp)
+    {
         const bool any = st.matched > 0;
         std::printf("deviation: %zu points: %zu matched, %zu too far, %zu without a normal, %zu dropped\n", st.n, st.matched, st.too_far, st.no_normal,
                     st.dropped);

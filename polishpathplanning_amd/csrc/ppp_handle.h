@@ -6,7 +6,8 @@
  *   ppp_engine.hip   the handle, the plan and the passes, graphs and batches, the getters and the API mirrors; it defines
  *                    every helper declared here
  *   ppp_contact.hip  the contact queries: coverage, path coverage, path contacts, the contact field, the regions, the schedules
- *   ppp_scan.hip     the calls that hold a scan against a reference cloud: the deviation map, the registrations, their tiles
+ *   ppp_scan.hip     the calls that hold a scan against a reference cloud: the deviation map, the registrations, their tiles;
+ *                    the resident triangle mesh and the exact deviation against it
  *   ppp_preproc.hip  the four preprocessing calls on the resident cloud, and the mesh sampler that makes one (ppp_set_cloud_mesh)
  *
  * A helper that only one unit calls is static in that unit and is not declared here.
@@ -15,6 +16,7 @@
 #include "ppp_window_decl.h" /* WinArgs (ppp_kernels.h with it) */
 #include "ppp_dynamic.h"     /* DynParams */
 #include "ppp_compact.h"
+#include "ppp_sort.h"
 #include "../../include/ppp_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -288,14 +290,15 @@ struct ppp_handle_s {
     /* deviation of this handle's cloud against another handle's (ppp_get_deviation): by cloud index the deviation, its local
        mean, its fixed-point term, the float d2, the reference index, the status and the target; the statistics' accumulators and
        the workgroups' parts of the two fixed-order sums.  Nothing is kept between calls: the reference may have changed.
-       ppp_get_deviation_tile runs in the same buffers, with the owned map beside them. */
+       ppp_get_deviation_tile runs in the same buffers, with the owned map beside them; ppp_get_mesh_deviation too (ref_index
+       holds the triangle), with the distance and region maps and the four words of their statistics beside them. */
     struct Deviation {
-        DevBuf<double> dev, smoothed, target, psum;
+        DevBuf<double> dev, smoothed, target, psum, dist;
         DevBuf<long long> fix;
         DevBuf<float> d2;
         DevBuf<int> ref_index;
-        DevBuf<unsigned char> status, owned;
-        DevBuf<unsigned long long> acc;
+        DevBuf<unsigned char> status, owned, region;
+        DevBuf<unsigned long long> acc, macc;
     } deviation;
     /* registration of this handle's cloud to another handle's (ppp_get_registration_terms, ppp_register): the chain's transforms
        (12 doubles each), the 29 integer sums of every evaluation, the rows and the control words (IcpCtl, as ints).  Nothing is
@@ -606,6 +609,20 @@ int set_cloud_resident(ppp_handle h, const float *xyz_dev, size_t n, const float
         hipError_t _le = hipGetLastError();                                                           \
         if (_le != hipSuccess) return fail((h), PPP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(_le)); \
     } while (0)
+
+/* a device-wide exclusive scan (ppp_sort.h) on the handle's stream, under its kernel timers like a launch; tmp: the scan's scratch */
+static inline int scan_exclusive(ppp_handle h, const char *name, DevBuf<char> &tmp, const unsigned *in, unsigned *out, size_t n)
+{
+    size_t bytes = 0;
+    HIPCHK(h, ppp_scan_exclusive_u32(nullptr, &bytes, in, out, n, h->stream));
+    HIPCHK(h, tmp.ensure(bytes));
+    KTimer *t = h->timing ? timer_for(h, name) : nullptr;
+    if (t) (void)hipEventRecord(t->e0[t->used], h->stream);
+    const hipError_t e = ppp_scan_exclusive_u32(tmp.p, &bytes, in, out, n, h->stream);
+    if (t) { (void)hipEventRecord(t->e1[t->used], h->stream); t->used++; }
+    HIPCHK(h, e);
+    return PPP_OK;
+}
 
 /* Launch-geometry / search-radius overrides of the tuning scripts (tools/_run_*.sh): read only by builds made with -DPPP_TUNING
    (make variant NAME=tune DEFS=-DPPP_TUNING); the product library ignores them, so a stray variable cannot change a plan. */

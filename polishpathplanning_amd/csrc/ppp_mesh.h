@@ -22,6 +22,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+/* ppp_preproc.hip owns the sampler's kernels.  ppp_scan.hip includes this header for the triangle frame (mesh_triangle,
+   mesh_owner) and defines PPP_MESH_KERNELS_FOREIGN: the kernels are templates there and, never launched, never instantiated
+   (PPP_KERNEL's idiom, ppp_kernels.h). */
+#ifdef PPP_MESH_KERNELS_FOREIGN
+#define PPP_MESH_KERNEL template <typename PPP_NEVER_ = void> __global__
+#else
+#define PPP_MESH_KERNEL __global__
+#endif
+
 #define MESH_T 256
 /* counts above this are written as this: the sums then saturate (ppp_scan_exclusive_u32) and the host refuses them */
 #define MESH_COUNT_MAX 0x80000000u
@@ -92,7 +101,7 @@ __device__ inline bool mesh_triangle(const MeshArgs &A, int f, double p0[3], dou
 
 /* one thread per triangle: R, or 0 for a triangle that is skipped (counted in cnt[0] degenerate, cnt[1] culled).  Thread
    n_tris writes the closing 0 whose scan is the total. */
-__global__ void __launch_bounds__(MESH_T) k_mesh_rows(MeshArgs A, unsigned *__restrict__ R, unsigned *cnt)
+PPP_MESH_KERNEL void __launch_bounds__(MESH_T) k_mesh_rows(MeshArgs A, unsigned *__restrict__ R, unsigned *cnt)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f > A.n_tris) return;
@@ -117,7 +126,7 @@ __global__ void __launch_bounds__(MESH_T) k_mesh_rows(MeshArgs A, unsigned *__re
 }
 
 /* one thread per row: M_r.  Thread `rows` writes the closing 0. */
-__global__ void __launch_bounds__(MESH_T) k_mesh_cols(MeshArgs A, const unsigned *__restrict__ row_off, unsigned rows, unsigned *__restrict__ M)
+PPP_MESH_KERNEL void __launch_bounds__(MESH_T) k_mesh_cols(MeshArgs A, const unsigned *__restrict__ row_off, unsigned rows, unsigned *__restrict__ M)
 {
     const unsigned g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g > rows) return;
@@ -132,7 +141,7 @@ __global__ void __launch_bounds__(MESH_T) k_mesh_cols(MeshArgs A, const unsigned
 }
 
 /* one thread per sample: its row, its triangle, its point (xyz packed: consecutive threads write consecutive records) */
-__global__ void __launch_bounds__(MESH_T) k_mesh_fill(MeshArgs A, const unsigned *__restrict__ row_off, const unsigned *__restrict__ col_off,
+PPP_MESH_KERNEL void __launch_bounds__(MESH_T) k_mesh_fill(MeshArgs A, const unsigned *__restrict__ row_off, const unsigned *__restrict__ col_off,
                                                       unsigned rows, unsigned samples, float *__restrict__ xyz, int *__restrict__ tri_index)
 {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;

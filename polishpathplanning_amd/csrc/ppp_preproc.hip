@@ -324,19 +324,6 @@ void ppp_default_mesh_params(ppp_mesh_params *mp)
 }
 
 namespace {
-/* a scan of the sampler, under the handle's kernel timers like a launch */
-static int mesh_scan(ppp_handle h, const char *name, DevBuf<char> &tmp, const unsigned *in, unsigned *out, size_t n)
-{
-    size_t bytes = 0;
-    HIPCHK(h, ppp_scan_exclusive_u32(nullptr, &bytes, in, out, n, h->stream));
-    HIPCHK(h, tmp.ensure(bytes));
-    KTimer *t = h->timing ? timer_for(h, name) : nullptr;
-    if (t) (void)hipEventRecord(t->e0[t->used], h->stream);
-    const hipError_t e = ppp_scan_exclusive_u32(tmp.p, &bytes, in, out, n, h->stream);
-    if (t) { (void)hipEventRecord(t->e1[t->used], h->stream); t->used++; }
-    HIPCHK(h, e);
-    return PPP_OK;
-}
 constexpr size_t MESH_CLOUD_MAX = 0x7fffffffu / 8; /* the points of a resident cloud (set_cloud_common) */
 } // namespace
 
@@ -386,7 +373,7 @@ int ppp_set_cloud_mesh(ppp_handle h, const float *verts, size_t n_verts, const i
         A.pitch = (double)mp->pitch; A.front = mp->facing == PPP_MESH_FRONT;
         for (int d = 0; d < 3; ++d) A.vp[d] = viewpoint ? (double)viewpoint[d] : 0.0;
         LAUNCH(h, "k_mesh_rows", k_mesh_rows, (unsigned)((n_tris + 1 + MESH_T - 1) / MESH_T), MESH_T, 0, A, R.p, cnt.p);
-        { int rc = mesh_scan(h, "mesh_scan_rows", tmp, R.p, row_off.p, n_tris + 1); if (rc) return rc; }
+        { int rc = scan_exclusive(h, "mesh_scan_rows", tmp, R.p, row_off.p, n_tris + 1); if (rc) return rc; }
         unsigned hcnt[2] = {0, 0}, rows = 0;
         HIPCHK(h, hipMemcpyAsync(hcnt, cnt.p, sizeof(hcnt), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(&rows, row_off.p + n_tris, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
@@ -398,7 +385,7 @@ int ppp_set_cloud_mesh(ppp_handle h, const float *verts, size_t n_verts, const i
         if (e == hipSuccess) e = col_off.ensure((size_t)rows + 1);
         if (e != hipSuccess) return fail(h, PPP_ERR_HIP, std::string("set_cloud_mesh buffers: ") + hipGetErrorString(e));
         LAUNCH(h, "k_mesh_cols", k_mesh_cols, (unsigned)(((size_t)rows + 1 + MESH_T - 1) / MESH_T), MESH_T, 0, A, row_off.p, rows, M.p);
-        { int rc = mesh_scan(h, "mesh_scan_cols", tmp, M.p, col_off.p, (size_t)rows + 1); if (rc) return rc; }
+        { int rc = scan_exclusive(h, "mesh_scan_cols", tmp, M.p, col_off.p, (size_t)rows + 1); if (rc) return rc; }
         unsigned total = 0;
         HIPCHK(h, hipMemcpyAsync(&total, col_off.p + rows, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));

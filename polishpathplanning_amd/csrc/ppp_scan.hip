@@ -1,7 +1,8 @@
 /*
  * ppp_scan.hip -- the calls of the C ABI (include/ppp_hip.h) that hold a scan against a reference cloud: the deviation map, its
  * tiles and their merge, the registration chain, its trimmed and its robust form, the cloud moments and the global registration,
- * and the registration, the trimmed and the robust registration of a scan held as slice-range tiles.  The unit owns the kernels of ppp_deviation.h,
+ * the registration, the trimmed and the robust registration of a scan held as slice-range tiles, and the resident triangle mesh
+ * with its exact point-to-triangle search and deviation map (ppp_trimesh.h).  The unit owns the kernels of ppp_deviation.h,
  * ppp_deviation_tile.h, ppp_registration.h, ppp_trimmed.h, ppp_robust.h, ppp_registration_tile.h, ppp_trimmed_tile.h and ppp_robust_tile.h; of the handle it sees
  * what ppp_handle.h declares, and it shares ppp_query_host.h with ppp_contact.hip.  Compiled with the engine's flags: the host
  * and the device step share icp_solve and icp_compose, one IEEE rounding per written operation on both sides.
@@ -9,6 +10,7 @@
 #ifndef PPP_SINGLE_TU /* (a diagnostic build includes this file into the engine's unit) */
 #define PPP_KERNELS_FOREIGN /* ppp_kernels.h, ppp_dynamic.h, ppp_compact.h: types and device helpers only -- their kernels are the engine's */
 #define PPP_CONTACT_KERNELS_FOREIGN /* ppp_contact.h likewise: its kernels are ppp_contact.hip's */
+#define PPP_MESH_KERNELS_FOREIGN /* ppp_mesh.h likewise: the sampler's kernels are ppp_preproc.hip's */
 #endif
 #include "ppp_query_host.h"
 #include "ppp_deviation.h"
@@ -19,6 +21,8 @@
 #include "ppp_registration_tile.h"
 #include "ppp_trimmed_tile.h"
 #include "ppp_robust_tile.h"
+#include "ppp_trimesh.h"
+#include "ppp_sort.h"
 #include <cstring>
 
 /* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
@@ -71,12 +75,20 @@ static int deviation_side(ppp_handle h, ppp_handle side, const char *who, const 
 }
 
 /* both deviation calls' checks before they look at a handle, in the order they fire; w: the call's name, halo: the tile call's */
+static int deviation_params_ok(ppp_handle h, const ppp_deviation_params &P, const std::string &w, const float *halo);
 static int deviation_call_ok(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, const std::string &w, const float *halo)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!ref || !dp) return fail(h, PPP_ERR_ARG, w + ": no reference handle or no parameters");
-    const ppp_deviation_params &P = *dp;
+    const int rc = deviation_params_ok(h, *dp, w, halo);
+    if (rc) return rc;
+    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the two handles are on different devices");
+    return PPP_OK;
+}
+/* ... those of them that read the parameters alone (the mesh call's too: it has no reference handle) */
+static int deviation_params_ok(ppp_handle h, const ppp_deviation_params &P, const std::string &w, const float *halo)
+{
     if (!(P.max_dist > 0.f)) return fail(h, PPP_ERR_ARG, w + (halo ? ": max_dist must be > 0" : ": max_dist must be > 0 (+INFINITY: no limit)"));
     if (halo && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": a tile needs a finite max_dist: the halo must hold every partner");
     if (!(P.smooth_radius >= 0.f && std::isfinite(P.smooth_radius))) return fail(h, PPP_ERR_ARG, w + ": smooth_radius must be finite and >= 0");
@@ -85,7 +97,6 @@ static int deviation_call_ok(ppp_handle h, ppp_handle ref, const ppp_deviation_p
     if (!halo && P.smooth_radius > 0.f && !std::isfinite(P.max_dist)) return fail(h, PPP_ERR_ARG, w + ": smoothing needs a finite max_dist");
     if (halo && !(*halo >= P.max_dist + P.smooth_radius && *halo <= 3.402823466e+38f))
         return fail(h, PPP_ERR_ARG, w + ": halo must be finite and at least max_dist + smooth_radius");
-    if (ref->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the two handles are on different devices");
     return PPP_OK;
 }
 
@@ -115,6 +126,43 @@ static int deviation_copy_out(ppp_handle h, size_t k, const double *v, double *d
     return PPP_OK;
 }
 
+/* The tail of a deviation call behind its search (ppp_get_mesh_deviation runs it too): status, deviation, its
+   fixed-point term and the float d2 are in h's buffers and the accumulators are clear; k_dev_smooth where asked, k_dev_target
+   and k_dev_stats on the scan's stream, the one wait, and the statistics.  *v: the map the target was taken from. */
+static int deviation_tail(ppp_handle h, const ppp_deviation_params &P, const MapParts &parts, const char *what, ppp_deviation_stats *stats, const double **v_out)
+{
+    auto &D = h->deviation;
+    const bool smooth = P.smooth_radius > 0.f;
+    const size_t N = h->n, N1 = std::max<size_t>(N, 1);
+    const int grid = parts.grid, per = parts.per, nq = h->hmeta.n_sorted;
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    if (nq > 0 && smooth)
+        LAUNCH(h, "k_dev_smooth", k_dev_smooth, (unsigned)((nq + DEV_T - 1) / DEV_T), DEV_T, 0, contact_index(h), nq, P.smooth_radius * P.smooth_radius, D.status.p,
+               D.fix.p, D.smoothed.p);
+    LAUNCH(h, "k_dev_target", k_dev_target, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, 2 * (size_t)h->num_cus), DEV_T, 0, D.status.p,
+           D.dev.p, v, D.d2.p, (int)N, P.allowance, P.gain, D.target.p, D.acc.p);
+    LAUNCH(h, "k_dev_stats", k_dev_stats, (unsigned)grid, PCON_T, 0, D.status.p, v, D.target.p, (int)N, per, D.acc.p, D.psum.p, D.psum.p + grid);
+    unsigned long long acc[DEV_ACC_WORDS];
+    std::vector<double> psum(2 * (size_t)grid);
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, psum.data(), D.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc[0] + acc[1] + acc[2] + acc[3] != N || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
+        return fail(h, PPP_ERR_HIP, std::string(what) + ": statistics corrupt");
+    if (stats) {
+        ppp_deviation_stats st = {};
+        dev_stats_words(st, N, acc);
+        st.dropped = (size_t)acc[3];
+        double sq = 0.0;
+        for (int g = 0; g < grid; ++g) { sq += psum[(size_t)g]; st.target_sum += psum[(size_t)grid + g]; }
+        st.mean_dev = st.matched ? (double)(long long)acc[DEV_ACC_FIXSUM] / (double)st.matched * (1.0 / DEV_FIXED) : (double)NAN;
+        st.rms_dev = st.matched ? std::sqrt(sq / (double)st.matched) : (double)NAN;
+        for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[DEV_ACC_BINS + b];
+        *stats = st;
+    }
+    *v_out = v;
+    return PPP_OK;
+}
+
 /* The deviation map: the reference's index and normal field on its own stream, one wait for that stream, then
    k_dev_nearest, k_dev_smooth where asked, k_dev_target and k_dev_stats back to back on the scan's stream, and one wait. */
 int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *dp, double *deviation, double *smoothed, int *ref_index,
@@ -134,42 +182,19 @@ int ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params *
     auto &D = h->deviation;
     const size_t N1 = std::max<size_t>(N, 1);
     const MapParts parts(h, N);
-    const int grid = parts.grid, per = parts.per, nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    const int grid = parts.grid, nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
     HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1));
     HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS)); HIPCHK(h, D.psum.ensure(2 * (size_t)grid));
     if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
-    double *v = smooth ? D.smoothed.p : D.dev.p;
     HIPCHK(h, hipMemsetAsync(D.status.p, PPP_DEV_DROPPED, N1, h->stream)); /* points outside the index: not finite */
     HIPCHK(h, hipMemsetAsync(D.ref_index.p, 0xff, N1 * sizeof(int), h->stream));
     HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEV_ACC_WORDS * sizeof(unsigned long long), h->stream));
-    const unsigned gq = (unsigned)((nq + DEV_T - 1) / DEV_T);
-    if (nq > 0) {
-        LAUNCH(h, "k_dev_nearest", k_dev_nearest, gq, DEV_T, 0, h->sorted4.p, nq, contact_index(ref), nref, P.max_dist * P.max_dist, D.dev.p, D.fix.p,
-               D.d2.p, D.ref_index.p, D.status.p);
-        if (smooth)
-            LAUNCH(h, "k_dev_smooth", k_dev_smooth, gq, DEV_T, 0, contact_index(h), nq, P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p,
-                   D.smoothed.p);
-    }
-    LAUNCH(h, "k_dev_target", k_dev_target, (unsigned)std::min<size_t>((N1 + DEV_T - 1) / DEV_T, 2 * (size_t)h->num_cus), DEV_T, 0, D.status.p,
-           D.dev.p, v, D.d2.p, (int)N, P.allowance, P.gain, D.target.p, D.acc.p);
-    LAUNCH(h, "k_dev_stats", k_dev_stats, (unsigned)grid, PCON_T, 0, D.status.p, v, D.target.p, (int)N, per, D.acc.p, D.psum.p, D.psum.p + grid);
-    unsigned long long acc[DEV_ACC_WORDS];
-    std::vector<double> psum(2 * (size_t)grid);
-    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
-    HIPCHK(h, copy_sync(h, psum.data(), D.psum.p, psum.size() * sizeof(double), hipMemcpyDeviceToHost));
-    if (acc[0] + acc[1] + acc[2] + acc[3] != N || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0])
-        return fail(h, PPP_ERR_HIP, "deviation: statistics corrupt");
-    if (stats) {
-        ppp_deviation_stats st = {};
-        dev_stats_words(st, N, acc);
-        st.dropped = (size_t)acc[3];
-        double sq = 0.0;
-        for (int g = 0; g < grid; ++g) { sq += psum[(size_t)g]; st.target_sum += psum[(size_t)grid + g]; }
-        st.mean_dev = st.matched ? (double)(long long)acc[DEV_ACC_FIXSUM] / (double)st.matched * (1.0 / DEV_FIXED) : (double)NAN;
-        st.rms_dev = st.matched ? std::sqrt(sq / (double)st.matched) : (double)NAN;
-        for (int b = 0; b < PPP_CONTACT_BINS; ++b) st.hist[b] = (size_t)acc[DEV_ACC_BINS + b];
-        *stats = st;
-    }
+    if (nq > 0)
+        LAUNCH(h, "k_dev_nearest", k_dev_nearest, (unsigned)((nq + DEV_T - 1) / DEV_T), DEV_T, 0, h->sorted4.p, nq, contact_index(ref), nref, P.max_dist * P.max_dist,
+               D.dev.p, D.fix.p, D.d2.p, D.ref_index.p, D.status.p);
+    const double *v = nullptr;
+    rc = deviation_tail(h, P, parts, "deviation", stats, &v);
+    if (rc) return rc;
     return deviation_copy_out(h, std::min(cap, N), v, deviation, smoothed, ref_index, status, target);
 }
 
@@ -1554,6 +1579,295 @@ int ppp_register_robust_tiles(const ppp_handle *hs, const ppp_handle *refs, size
     }
     const size_t k = std::min(row_cap, last + 1);
     if (rows && k) memcpy(rows, out.data(), k * sizeof(ppp_robust_registration_row));
+    return PPP_OK;
+}
+
+/* ---- the resident triangle mesh and the exact deviation against it (ppp_trimesh.h) ---- */
+} // extern "C"
+
+/* The mesh owns its buffers and a stream of its own: after ppp_trimesh_create it needs neither the handle nor any cloud. */
+struct ppp_trimesh_s {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf<TriRec> rec;
+    DevBuf<unsigned> cell_start;
+    DevBuf<int> cell_rec;
+    TriGrid G = {};
+    ~ppp_trimesh_s() { if (stream) (void)hipStreamDestroy(stream); }
+};
+
+namespace {
+constexpr size_t TRIMESH_MAX = 0x7fffffffu / 8; /* triangles and vertices: ppp_set_cloud_mesh's limit */
+
+/* the grid's dimensions for this cell; false: more than TM_MAX_CELLS cells */
+static bool trimesh_dims(const double *mn, const double *mx, double cell, int *dim)
+{
+    double cells = 1.0;
+    for (int d = 0; d < 3; ++d) {
+        const double c = std::floor((mx[d] - mn[d]) / cell) + 1.0; /* tm_cell of the upper corner, + 1 */
+        if (!(c <= (double)TM_MAX_CELLS)) return false;
+        dim[d] = (int)c;
+        cells *= c;
+    }
+    return cells <= (double)TM_MAX_CELLS;
+}
+
+static TmOut trimesh_outputs(double *distance, double *closest, double *deviation, long long *fix, float *d2f, int *tri_index, unsigned char *region,
+                             unsigned char *status)
+{
+    TmOut O;
+    O.distance = distance; O.closest = closest; O.deviation = deviation; O.fix = fix; O.d2f = d2f; O.tri_index = tri_index; O.region = region; O.status = status;
+    return O;
+}
+} // namespace
+
+extern "C" {
+
+void ppp_default_trimesh_params(ppp_trimesh_params *tp)
+{
+    if (!tp) return;
+    tp->cell = 0.f; tp->orient = PPP_TRIMESH_WINDING;
+}
+
+void ppp_trimesh_destroy(ppp_trimesh m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    delete m;
+}
+
+int ppp_trimesh_create(ppp_handle h, const float *verts, size_t n_verts, const int *tris, size_t n_tris, const ppp_trimesh_params *tp,
+                       const float *viewpoint, ppp_trimesh *out, ppp_trimesh_stats *stats)
+{
+    if (out) *out = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h) return PPP_ERR_ARG;
+    if (!out) return fail(h, PPP_ERR_ARG, "trimesh: out is NULL");
+    if (!verts || !tp) return fail(h, PPP_ERR_ARG, "trimesh: vertices and parameters are required");
+    const bool automatic = tp->cell == 0.f;
+    if (!automatic && (!(tp->cell > 0.f) || !std::isfinite(tp->cell))) return fail(h, PPP_ERR_ARG, "trimesh: cell must be 0 (automatic) or positive and finite");
+    if (tp->orient != PPP_TRIMESH_WINDING && tp->orient != PPP_TRIMESH_VIEWPOINT) return fail(h, PPP_ERR_ARG, "trimesh: orient is PPP_TRIMESH_WINDING or PPP_TRIMESH_VIEWPOINT");
+    if (n_tris == 0) return fail(h, PPP_ERR_ARG, "trimesh: no triangle");
+    if (!tris && (n_verts % 3 || n_verts / 3 != n_tris)) return fail(h, PPP_ERR_ARG, "trimesh: a soup (tris == NULL) has three vertices per triangle");
+    if (n_tris > TRIMESH_MAX || n_verts > TRIMESH_MAX) return fail(h, PPP_ERR_CAPACITY, "trimesh: mesh too large");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::unique_ptr<ppp_trimesh_s> m(new ppp_trimesh_s);
+    m->device = h->device;
+    ppp_trimesh_stats st = {};
+    st.triangles = n_tris;
+    DevBuf<char> raw, tmp;
+    DevBuf<float> V;
+    DevBuf<int> T, val;
+    DevBuf<unsigned> valid, rank, cnt, off, key, key_sorted, words;
+    DevBuf<unsigned long long> side_sum;
+    const size_t nv = std::max<size_t>(n_verts, 1);
+    HIPCHK(h, raw.ensure(12 * nv)); HIPCHK(h, V.ensure(3 * nv)); HIPCHK(h, valid.ensure(n_tris + 1)); HIPCHK(h, rank.ensure(n_tris + 1));
+    HIPCHK(h, words.ensure(8)); HIPCHK(h, side_sum.ensure(1));
+    if (tris) HIPCHK(h, T.ensure(3 * n_tris));
+    /* the vertices become resident ones by the conversion of every cloud (k_ingest), as ppp_set_cloud_mesh's do */
+    if (n_verts) {
+        HIPCHK(h, hipMemcpyAsync(raw.p, verts, 12 * n_verts, hipMemcpyHostToDevice, h->stream));
+#ifdef PPP_KERNELS_FOREIGN /* (the engine's kernel, instantiated here: ppp_kernels.h) */
+        LAUNCH(h, "k_ingest", k_ingest<>, (unsigned)((n_verts + 255) / 256), 256, 0, raw.p, (size_t)12, (int)n_verts, h->P.change_range, V.p, V.p + nv, V.p + 2 * nv);
+#else
+        LAUNCH(h, "k_ingest", k_ingest, (unsigned)((n_verts + 255) / 256), 256, 0, raw.p, (size_t)12, (int)n_verts, h->P.change_range, V.p, V.p + nv, V.p + 2 * nv);
+#endif
+    }
+    if (tris) HIPCHK(h, hipMemcpyAsync(T.p, tris, 12 * n_tris, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(words.p, 0, 8 * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(side_sum.p, 0, sizeof(unsigned long long), h->stream));
+    MeshArgs A;
+    A.Vx = V.p; A.Vy = V.p + nv; A.Vz = V.p + 2 * nv; A.n_verts = (int)n_verts;
+    A.tris = tris ? T.p : nullptr; A.n_tris = (int)n_tris;
+    A.pitch = 0.0; A.front = 0;
+    for (int d = 0; d < 3; ++d) A.vp[d] = viewpoint ? (double)viewpoint[d] : 0.0;
+    LAUNCH(h, "k_tm_bounds", k_tm_bounds, (unsigned)((n_tris + 1 + TM_T - 1) / TM_T), TM_T, 0, A, valid.p, words.p);
+    int rc = scan_exclusive(h, "trimesh_scan_rank", tmp, valid.p, rank.p, n_tris + 1);
+    if (rc) return rc;
+    unsigned bb[6] = {0, 0, 0, 0, 0, 0}, indexed = 0;
+    HIPCHK(h, hipMemcpyAsync(bb, words.p, sizeof(bb), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&indexed, rank.p + n_tris, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (indexed > n_tris) return fail(h, PPP_ERR_HIP, "trimesh: counts corrupt");
+    st.indexed = indexed; st.degenerate = n_tris - indexed;
+    if (stats) *stats = st;
+    if (indexed == 0) return fail(h, PPP_ERR_ARG, "trimesh: nothing to index: every triangle is degenerate");
+    TriGrid &G = m->G;
+    double extent = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        st.mn[d] = ordered_unkey(~bb[d]); st.mx[d] = ordered_unkey(bb[3 + d]);
+        G.mn[d] = (double)st.mn[d]; G.mx[d] = (double)st.mx[d];
+        G.vp[d] = A.vp[d];
+        extent = std::max(extent, G.mx[d] - G.mn[d]);
+    }
+    if (!(extent > 0.0) || !std::isfinite(extent)) return fail(h, PPP_ERR_HIP, "trimesh: bounds corrupt");
+    G.by_viewpoint = tp->orient == PPP_TRIMESH_VIEWPOINT;
+    G.indexed = (int)indexed;
+    HIPCHK(h, m->rec.ensure(indexed));
+    G.rec = m->rec.p;
+    LAUNCH(h, "k_tm_records", k_tm_records, (unsigned)((n_tris + TM_T - 1) / TM_T), TM_T, 0, A, rank.p, m->rec.p);
+    const unsigned grec = (unsigned)(((size_t)indexed + 1 + TM_T - 1) / TM_T);
+    float cell = tp->cell;
+    if (automatic) { /* the mean longest box side of the indexed triangles (an integer sum: the same in every run) */
+        LAUNCH(h, "k_tm_sides", k_tm_sides, grec, TM_T, 0, G, extent, side_sum.p);
+        unsigned long long sum = 0;
+        HIPCHK(h, copy_sync(h, &sum, side_sum.p, sizeof(sum), hipMemcpyDeviceToHost));
+        cell = (float)((double)sum / (double)indexed / TM_SIDE_SCALE * extent);
+        if (!(cell > 0.f) || !std::isfinite(cell)) cell = (float)extent;
+        if (!(cell > 0.f) || !std::isfinite(cell)) return fail(h, PPP_ERR_ARG, "trimesh: no cell for this mesh's extent");
+    }
+    HIPCHK(h, cnt.ensure((size_t)indexed + 1)); HIPCHK(h, off.ensure((size_t)indexed + 1));
+    unsigned pairs = 0;
+    for (;;) { /* an automatic cell doubles until the grid and the pair list fit; a given one is refused */
+        G.cell = (double)cell;
+        bool fits = std::isfinite(cell) && trimesh_dims(G.mn, G.mx, G.cell, G.dim);
+        if (!fits && !automatic) return fail(h, PPP_ERR_CAPACITY, "trimesh: this cell makes more than 2^24 cells");
+        if (fits) {
+            LAUNCH(h, "k_tm_count", k_tm_count, grec, TM_T, 0, G, cnt.p);
+            rc = scan_exclusive(h, "trimesh_scan_pairs", tmp, cnt.p, off.p, (size_t)indexed + 1);
+            if (rc) return rc;
+            HIPCHK(h, copy_sync(h, &pairs, off.p + indexed, sizeof(unsigned), hipMemcpyDeviceToHost));
+            fits = pairs <= TM_MAX_PAIRS;
+            if (!fits && !automatic) return fail(h, PPP_ERR_CAPACITY, "trimesh: this cell makes 2^31 - 1 (triangle, cell) pairs or more");
+        }
+        if (fits) break;
+        if (!std::isfinite(cell)) return fail(h, PPP_ERR_CAPACITY, "trimesh: no cell fits this mesh");
+        cell *= 2.f;
+    }
+    if (pairs < indexed) return fail(h, PPP_ERR_HIP, "trimesh: pair count corrupt");
+    const size_t cells = (size_t)G.dim[0] * (size_t)G.dim[1] * (size_t)G.dim[2];
+    HIPCHK(h, key.ensure(pairs)); HIPCHK(h, key_sorted.ensure(pairs)); HIPCHK(h, val.ensure(pairs));
+    HIPCHK(h, m->cell_rec.ensure(pairs)); HIPCHK(h, m->cell_start.ensure(cells + 1));
+    LAUNCH(h, "k_tm_pairs", k_tm_pairs, (unsigned)(((size_t)pairs + TM_T - 1) / TM_T), TM_T, 0, G, off.p, pairs, key.p, val.p);
+    {
+        int end_bit = 1;
+        while (end_bit < 32 && (cells - 1) >> end_bit) ++end_bit;
+        size_t bytes = 0;
+        HIPCHK(h, ppp_sort_pairs_u32(nullptr, &bytes, key.p, key_sorted.p, val.p, m->cell_rec.p, pairs, end_bit, h->stream));
+        HIPCHK(h, tmp.ensure(bytes));
+        KTimer *t = h->timing ? timer_for(h, "trimesh_sort_pairs") : nullptr;
+        if (t) (void)hipEventRecord(t->e0[t->used], h->stream);
+        const hipError_t e = ppp_sort_pairs_u32(tmp.p, &bytes, key.p, key_sorted.p, val.p, m->cell_rec.p, pairs, end_bit, h->stream);
+        if (t) { (void)hipEventRecord(t->e1[t->used], h->stream); t->used++; }
+        HIPCHK(h, e);
+    }
+    LAUNCH(h, "k_tm_cell_start", k_tm_cell_start, (unsigned)((cells + 1 + TM_T - 1) / TM_T), TM_T, 0, key_sorted.p, pairs, (unsigned)cells, m->cell_start.p);
+    HIPCHK(h, hipMemsetAsync(words.p, 0, sizeof(unsigned), h->stream));
+    LAUNCH(h, "k_tm_max_per_cell", k_tm_max_per_cell, (unsigned)((cells + TM_T - 1) / TM_T), TM_T, 0, m->cell_start.p, (unsigned)cells, words.p);
+    unsigned most = 0;
+    HIPCHK(h, copy_sync(h, &most, words.p, sizeof(unsigned), hipMemcpyDeviceToHost)); /* the wait: the scratch may go */
+    G.cell_start = m->cell_start.p; G.cell_rec = m->cell_rec.p;
+    HIPCHK(h, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    for (int d = 0; d < 3; ++d) st.cells[d] = (size_t)G.dim[d];
+    st.pairs = pairs; st.max_per_cell = most; st.cell = cell;
+    if (stats) *stats = st;
+    *out = m.release();
+    return PPP_OK;
+}
+
+int ppp_trimesh_create_stl(ppp_handle h, const char *path, const ppp_trimesh_params *tp, const float *viewpoint, ppp_trimesh *out, ppp_trimesh_stats *stats)
+{
+    if (out) *out = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h) return PPP_ERR_ARG;
+    if (!path) return fail(h, PPP_ERR_ARG, "trimesh: no file name");
+    float *v9 = nullptr;
+    size_t nt = 0;
+    int rc = ppp_load_stl(path, &v9, &nt);
+    if (rc != PPP_OK) return fail(h, rc, std::string("not a readable STL file: ") + path);
+    rc = ppp_trimesh_create(h, v9, 3 * nt, nullptr, nt, tp, viewpoint, out, stats);
+    ppp_free(v9);
+    return rc;
+}
+
+/* The primitive: the caller's points up, k_mesh_nearest on the mesh's own stream, the maps down.  No handle: an error is its code. */
+int ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist, double *distance, double *closest, double *deviation, int *tri_index,
+                        unsigned char *region, unsigned char *status)
+{
+    if (!m || (!xyz && n) || !(max_dist > 0.f)) return PPP_ERR_ARG;
+    if (n > 0x7fffffffu / 8) return PPP_ERR_CAPACITY;
+    if (n == 0) return PPP_OK;
+#define TM_CHK(expr) do { if ((expr) != hipSuccess) return PPP_ERR_HIP; } while (0)
+    TM_CHK(hipSetDevice(m->device));
+    DevBuf<float> q;
+    DevBuf<double> d_dist, d_close, d_dev;
+    DevBuf<int> d_tri;
+    DevBuf<unsigned char> d_region, d_status;
+    TM_CHK(q.ensure(3 * n)); TM_CHK(d_status.ensure(n));
+    if (distance) TM_CHK(d_dist.ensure(n));
+    if (closest) TM_CHK(d_close.ensure(3 * n));
+    if (deviation) TM_CHK(d_dev.ensure(n));
+    if (tri_index) TM_CHK(d_tri.ensure(n));
+    if (region) TM_CHK(d_region.ensure(n));
+    TM_CHK(hipMemcpyAsync(q.p, xyz, 12 * n, hipMemcpyHostToDevice, m->stream));
+    const double md2 = (double)max_dist * (double)max_dist;
+    const TmOut O = trimesh_outputs(d_dist.p, d_close.p, d_dev.p, nullptr, nullptr, d_tri.p, d_region.p, d_status.p);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mesh_nearest, dim3((unsigned)((n + TM_T - 1) / TM_T)), dim3(TM_T), 0, m->stream, (const float4 *)nullptr, (const float *)q.p, (int)n, m->G,
+                       md2, O);
+    TM_CHK(hipGetLastError());
+    if (distance) TM_CHK(hipMemcpyAsync(distance, d_dist.p, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (closest) TM_CHK(hipMemcpyAsync(closest, d_close.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (deviation) TM_CHK(hipMemcpyAsync(deviation, d_dev.p, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (tri_index) TM_CHK(hipMemcpyAsync(tri_index, d_tri.p, n * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (region) TM_CHK(hipMemcpyAsync(region, d_region.p, n, hipMemcpyDeviceToHost, m->stream));
+    if (status) TM_CHK(hipMemcpyAsync(status, d_status.p, n, hipMemcpyDeviceToHost, m->stream));
+    TM_CHK(hipStreamSynchronize(m->stream));
+#undef TM_CHK
+    return PPP_OK;
+}
+
+/* The exact deviation map: the scan's slab index, k_tm_fill and k_mesh_nearest over its points in slab order,
+   then ppp_get_deviation's own tail (deviation_tail) and the counts by region, all on the scan's stream; one wait. */
+int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *deviation, double *smoothed, double *distance, int *tri_index,
+                           unsigned char *region, unsigned char *status, double *target, size_t cap, ppp_mesh_deviation_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!m || !dp) return fail(h, PPP_ERR_ARG, "mesh deviation: no mesh or no parameters");
+    int rc = deviation_params_ok(h, *dp, "mesh deviation", nullptr);
+    if (rc) return rc;
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "mesh deviation: the mesh is on another device than the handle");
+    const ppp_deviation_params P = *dp;
+    const bool smooth = P.smooth_radius > 0.f;
+    rc = deviation_side(h, h, "the scan", "mesh deviation");
+    if (rc) return rc;
+    const size_t N = h->n;
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "mesh deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    const MapParts parts(h, N);
+    const int nq = h->hmeta.n_sorted;
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1)); HIPCHK(h, D.dist.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.region.ensure(N1)); HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS));
+    HIPCHK(h, D.psum.ensure(2 * (size_t)parts.grid)); HIPCHK(h, D.macc.ensure(4));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEV_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(D.macc.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    const unsigned gn = (unsigned)std::min<size_t>((N1 + TM_T - 1) / TM_T, 2 * (size_t)h->num_cus);
+    LAUNCH(h, "k_tm_fill", k_tm_fill, gn, TM_T, 0, (int)N, D.dist.p, D.ref_index.p, D.region.p, D.status.p); /* points outside the index: not finite */
+    if (nq > 0) {
+        const TmOut O = trimesh_outputs(D.dist.p, nullptr, D.dev.p, D.fix.p, D.d2.p, D.ref_index.p, D.region.p, D.status.p);
+        LAUNCH(h, "k_mesh_nearest", k_mesh_nearest, (unsigned)((nq + TM_T - 1) / TM_T), TM_T, 0, (const float4 *)h->sorted4.p, (const float *)nullptr, nq, m->G,
+               (double)P.max_dist * (double)P.max_dist, O);
+    }
+    LAUNCH(h, "k_tm_region_stats", k_tm_region_stats, gn, TM_T, 0, (int)N, D.status.p, D.region.p, D.dist.p, D.macc.p);
+    const double *v = nullptr;
+    ppp_mesh_deviation_stats st = {};
+    rc = deviation_tail(h, P, parts, "mesh deviation", &st.dev, &v);
+    if (rc) return rc;
+    unsigned long long macc[4];
+    HIPCHK(h, copy_sync(h, macc, D.macc.p, sizeof(macc), hipMemcpyDeviceToHost));
+    if (macc[0] + macc[1] + macc[2] != st.dev.matched) return fail(h, PPP_ERR_HIP, "mesh deviation: statistics corrupt");
+    st.on_face = (size_t)macc[0]; st.on_edge = (size_t)macc[1]; st.on_vertex = (size_t)macc[2];
+    st.max_distance = (double)NAN;
+    if (st.dev.matched) memcpy(&st.max_distance, &macc[3], sizeof(double));
+    if (stats) *stats = st;
+    const size_t k = std::min(cap, N);
+    rc = deviation_copy_out(h, k, v, deviation, smoothed, tri_index, status, target);
+    if (rc) return rc;
+    if (distance && k) HIPCHK(h, copy_sync(h, distance, D.dist.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (region && k) HIPCHK(h, copy_sync(h, region, D.region.p, k, hipMemcpyDeviceToHost));
     return PPP_OK;
 }
 

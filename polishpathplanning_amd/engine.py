@@ -81,6 +81,7 @@ EXPORTS = [
     "ppp_save_pcd_rgb", "ppp_range_interval", "ppp_set_cloud_part", "ppp_spline_create", "ppp_spline_restart", "ppp_spline_eval", "ppp_spline_range", "ppp_spline_destroy",
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
     "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
+    "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -262,6 +263,15 @@ def lib():
         L.ppp_default_mesh_params.restype = None
         L.ppp_set_cloud_mesh.argtypes = [vp, fp, sz, ip, sz, C.POINTER(MeshParams), fp, ip, sz, C.POINTER(MeshStats)]
         L.ppp_set_cloud_stl.argtypes = [vp, C.c_char_p, C.POINTER(MeshParams), fp, C.POINTER(MeshStats)]
+        ubp = C.POINTER(C.c_ubyte)
+        L.ppp_default_trimesh_params.argtypes = [C.POINTER(TriMeshParams)]
+        L.ppp_default_trimesh_params.restype = None
+        L.ppp_trimesh_create.argtypes = [vp, fp, sz, ip, sz, C.POINTER(TriMeshParams), fp, C.POINTER(vp), C.POINTER(TriMeshStats)]
+        L.ppp_trimesh_create_stl.argtypes = [vp, C.c_char_p, C.POINTER(TriMeshParams), fp, C.POINTER(vp), C.POINTER(TriMeshStats)]
+        L.ppp_trimesh_destroy.argtypes = [vp]
+        L.ppp_trimesh_destroy.restype = None
+        L.ppp_trimesh_nearest.argtypes = [vp, fp, sz, C.c_float, dp, dp, dp, ip, ubp, ubp]
+        L.ppp_get_mesh_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, dp, sz, C.POINTER(MeshDeviationStats)]
         L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
         L.ppp_save_stl.argtypes = [C.c_char_p, fp, sz, C.c_int]
         _lib = L
@@ -315,6 +325,67 @@ class MeshStats(C.Structure):  # ppp_mesh_stats
 
 def _mesh_stats(st):
     return {k: int(getattr(st, k)) for k, _ in MeshStats._fields_}
+
+
+TRIMESH_WINDING, TRIMESH_VIEWPOINT = 0, 1  # PPP_TRIMESH_*
+REGION_FACE, REGION_EDGE, REGION_VERTEX, REGION_NONE = 0, 1, 2, 255  # the region map of the exact search
+
+
+class TriMeshParams(C.Structure):  # ppp_trimesh_params
+    _fields_ = [("cell", C.c_float), ("orient", C.c_int)]
+
+
+class TriMeshStats(C.Structure):  # ppp_trimesh_stats
+    _fields_ = [("triangles", C.c_size_t), ("indexed", C.c_size_t), ("degenerate", C.c_size_t), ("cells", C.c_size_t * 3),
+                ("pairs", C.c_size_t), ("max_per_cell", C.c_size_t), ("cell", C.c_float), ("mn", C.c_float * 3), ("mx", C.c_float * 3)]
+
+
+def _trimesh_stats(st):
+    out = {k: int(getattr(st, k)) for k in ("triangles", "indexed", "degenerate", "pairs", "max_per_cell")}
+    out["cells"] = tuple(int(v) for v in st.cells)
+    out["cell"] = float(st.cell)
+    out["mn"] = np.array(st.mn[:], np.float32)
+    out["mx"] = np.array(st.mx[:], np.float32)
+    return out
+
+
+class TriMesh:
+    """A resident triangle mesh with its grid (ppp_trimesh): made by Engine.trimesh() / Engine.trimesh_stl(), independent of the
+    engine afterwards.  stats: triangles, indexed, degenerate, cells, pairs, max_per_cell, cell, mn, mx."""
+
+    def __init__(self, handle, stats):
+        self.L = lib()
+        self.m = handle
+        self.stats = stats
+
+    def nearest(self, xyz, max_dist=float("inf")):
+        """(distance float64[n], closest float64[n, 3], deviation float64[n], tri_index int32[n], region uint8[n], status uint8[n])
+        of n points in RESIDENT units against the mesh (ppp_trimesh_nearest): the closest point on the nearest triangle, its
+        distance, the component of the offset along that facet's normal, the region of the triangle it lies in (REGION_FACE,
+        REGION_EDGE, REGION_VERTEX) and DEV_MATCHED / DEV_TOO_FAR / DEV_DROPPED.  NaN, -1 and REGION_NONE where not matched."""
+        q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = q.shape[0]
+        dist, dev = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+        close = np.zeros((max(n, 1), 3), np.float64)
+        tri = np.zeros(max(n, 1), np.int32)
+        region, status = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        ub = C.POINTER(C.c_ubyte)
+        rc = self.L.ppp_trimesh_nearest(self.m, _f(q), n, float(max_dist), _d(dist), _d(close), _d(dev), _i(tri), region.ctypes.data_as(ub),
+                                        status.ctypes.data_as(ub))
+        if rc:
+            raise PPPError(rc, "ppp_trimesh_nearest failed")
+        return dist[:n], close[:n], dev[:n], tri[:n], region[:n], status[:n]
+
+    def close(self):
+        if self.m:
+            self.L.ppp_trimesh_destroy(self.m)
+            self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def load_stl(path):
@@ -470,6 +541,11 @@ def _deviation_stats(st):
     stats = {k: getattr(st, k) for k, _ in DeviationStats._fields_ if k != "hist"}
     stats["hist"] = np.array(st.hist[:], np.int64)
     return stats
+
+
+class MeshDeviationStats(C.Structure):
+    """ppp_mesh_deviation_stats"""
+    _fields_ = [("dev", DeviationStats), ("on_face", C.c_size_t), ("on_edge", C.c_size_t), ("on_vertex", C.c_size_t), ("max_distance", C.c_double)]
 
 
 def merge_deviation_tiles(tiles):
@@ -1255,6 +1331,63 @@ class Engine:
         out = _mesh_stats(st)
         self.n = out["samples"]
         return out
+
+    def _trimesh(self, call, *args, cell=0.0, orient=TRIMESH_WINDING, viewpoint=None):
+        vp = None if viewpoint is None else _f(np.ascontiguousarray(viewpoint, np.float32))
+        tp, st, m = TriMeshParams(), TriMeshStats(), C.c_void_p()
+        self.L.ppp_default_trimesh_params(C.byref(tp))
+        tp.cell, tp.orient = float(cell), int(orient)
+        try:
+            self._chk(call(self.h, *args, C.byref(tp), vp, C.byref(m), C.byref(st)))
+        except PPPError as e:
+            e.stats = _trimesh_stats(st)
+            e.handle = m.value
+            raise
+        return TriMesh(m, _trimesh_stats(st))
+
+    def trimesh(self, verts, tris=None, cell=0.0, orient=TRIMESH_WINDING, viewpoint=None):
+        """ppp_trimesh_create: a TriMesh of verts [n_verts, 3] in the file's units (they go through this engine's conversion, the
+        x1000 under change_range) and tris [n_tris, 3] indices, or None for a soup.  cell 0 chooses the grid's cell; the answers do
+        not depend on it.  orient TRIMESH_VIEWPOINT turns every facet normal to the viewpoint's side (resident units, None =
+        origin).  The mesh lives on this engine's device and needs the engine no longer.  A refused call fills "stats" of the
+        PPPError it raises."""
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        ti = None if tris is None else np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+        n_tris = verts.shape[0] // 3 if ti is None else ti.shape[0]
+        return self._trimesh(self.L.ppp_trimesh_create, _f(verts), verts.shape[0], None if ti is None else _i(ti), n_tris, cell=cell, orient=orient,
+                             viewpoint=viewpoint)
+
+    def trimesh_stl(self, path, cell=0.0, orient=TRIMESH_WINDING, viewpoint=None):
+        """ppp_trimesh_create_stl: trimesh() of the soup of an STL file."""
+        return self._trimesh(self.L.ppp_trimesh_create_stl, path.encode(), cell=cell, orient=orient, viewpoint=viewpoint)
+
+    def mesh_deviation(self, mesh, max_dist=float("inf"), smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(deviation float64[n], smoothed float64[n], distance float64[n], tri_index int32[n], region uint8[n], status uint8[n],
+        target float64[n], stats dict) of this engine's cloud, the scan, against the TriMesh `mesh` (ppp_get_mesh_deviation): per
+        scan point the closest point on the nearest triangle within max_dist mm, its distance, and the offset's component along
+        that facet's own normal; then deviation()'s smoothing, target and statistics, unchanged.  stats: deviation()'s fields
+        (no_normal is 0, max_dist2 the float of the largest squared distance) and on_face, on_edge, on_vertex, max_distance.
+        maps=False returns seven Nones and stats"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = MeshDeviationStats()
+        dev = sm = dist = idx = region = status = target = None
+        m = mesh.m if mesh is not None else None
+        if not maps:
+            self._chk(self.L.ppp_get_mesh_deviation(self.h, m, C.byref(dp), None, None, None, None, None, None, None, 0, C.byref(st)))
+        else:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            dev, sm, dist, target = (np.zeros(max(n, 1), np.float64) for _ in range(4))
+            idx = np.zeros(max(n, 1), np.int32)
+            region, status = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+            ub = C.POINTER(C.c_ubyte)
+            self._chk(self.L.ppp_get_mesh_deviation(self.h, m, C.byref(dp), _d(dev), _d(sm), _d(dist), _i(idx), region.ctypes.data_as(ub),
+                                                    status.ctypes.data_as(ub), _d(target), n, C.byref(st)))
+            dev, sm, dist, idx, region, status, target = dev[:n], sm[:n], dist[:n], idx[:n], region[:n], status[:n], target[:n]
+        stats = _deviation_stats(st.dev)
+        stats.update(on_face=int(st.on_face), on_edge=int(st.on_edge), on_vertex=int(st.on_vertex), max_distance=float(st.max_distance))
+        return dev, sm, dist, idx, region, status, target, stats
 
     def range_interval(self, min_x, max_x):
         """(lo, hi, S): the planner-unit x interval this handle's slice range indexes for a cloud with these x bounds."""
