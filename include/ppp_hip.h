@@ -1333,6 +1333,14 @@ int ppp_set_side_by_side(ppp_handle h, int handles);
  * member planned this same form, none bins through the staged form and the batch's slices together are no launch of several rounds
  * of workgroups; otherwise in the 1024-thread form.  The getter does not report a batch's launch. */
 int ppp_get_binning_form(ppp_handle h, int *threads, int *points_per_thread);
+/* The wave priorities (0..3, the hardware's; 0 is what a wave starts with) that THIS HANDLE'S plan launches the window pass with: the
+ * binning, the per-slice and the finish launch.  All 0 for a pass alone and on the slab-index path.  Where ppp_set_side_by_side
+ * announced two or more handles and the windows are small (the condition of the 512-thread slice workgroups), the finish launch --
+ * the last link of a pass's chain of three dependent launches, the one the handle's next pass waits for -- runs above the waves
+ * of the passes next door; the other two stay at 0 (raising the per-slice launch was measured to change nothing).  Priorities
+ * order instruction issue only: the lists are the same bit for bit.  As ppp_get_binning_form, the getter reports the handle's own
+ * launches, not a batch's. */
+int ppp_get_launch_priorities(ppp_handle h, int *binning, int *per_slice, int *finish);
 /* The engine has two launch sequences for the same hot path, with the same results up to the last bits of the normals'
  * float sums (both within the tolerances of tests/): the WINDOW path (three launches: every point binned once into the
  * window of its slice, one fused per-slice kernel, the finish; kd pairing, no dynamic adjustment / alignment, tool steps

@@ -334,6 +334,21 @@ static void win_pick_scatter(ppp_handle h, long long wgs, int n_src)
     h->win_scat_threads = T; h->win_ppt = ppt;
 }
 
+/* Wave priority of the by-value finish launch (WinArgs.prio, ppp_window.h win_prio_raise): raised only under the conditions that narrow
+   the slice workgroup above -- passes that share the device, windows small enough that a CU holds a neighbouring pass's workgroups
+   beside a slice workgroup.  A pass alone launches with 0: no priority instruction runs.  The binning and per-slice launches stay at
+   the priority a wave starts with (0), whoever they run beside.  Measured on 1 M points / 256 slices, three handles, 1000 steps,
+   ms per step in one visit (profiles/sbs_priority_ab.txt): parent 0.02629; the per-slice launch's pose phase raised and nothing
+   else 0.02631; finish raised 0.02524-0.02537, whether to 1, 2 or 3 and whatever the per-slice launch runs at. */
+#define PPP_WIN_PRIO_FINISH 1
+static void win_pick_prio(ppp_handle h, long long wgs)
+{
+    h->win_prio_finish = 0;
+    if (h->side_by_side < 2 || win_throughput_launch(h, wgs) || h->win_capw > 3072) return;
+    h->win_prio_finish = PPP_WIN_PRIO_FINISH;
+    if (const char *ev = tuning_env("PPP_WIN_PRIO")) { const int v = atoi(ev); if (v >= 0 && v <= 3) h->win_prio_finish = v; } /* tuning runs only */
+}
+
 /* The window path (ppp_window.h) for this plan, when it applies: kd pairing without dynamic adjustment or alignment, windows
    [Px - pad, Px + pad] that do not overlap (tool steps of about 2 pad + 2 mm and more) and that fit a workgroup's LDS.  Everything
    else -- and every pass the window path hands back -- runs on the slab index.  Sizes come from the cached bounds, as the slab
@@ -444,6 +459,7 @@ static int plan_window(ppp_handle h, int S, double per)
         if (win_scatter_lds_bytes(S, h->win_ppt_alone, WSC_T, true) + 2048 > (size_t)h->max_lds) { h->win_staged = false; h->win_ppt_alone = 8; }
     }
     win_pick_scatter(h, std::max(1, h->se - h->sb), n_src);
+    win_pick_prio(h, std::max(1, h->se - h->sb));
     h->win_gs = std::max(1, (n_src + h->win_ppt * h->win_scat_threads - 1) / (h->win_ppt * h->win_scat_threads));
     if (h->win_staged) h->win_gs = std::min(h->win_gs, std::max(1, h->num_cus)); /* the staged form loops over its chunks: a workgroup per CU (its LDS admits no second) */
     h->win_pad = pad; h->win_capw = capw; h->win_cap_el = cap_el; h->win_NB = NB; h->win_NBc = NBc; h->win_threads = T;
@@ -553,6 +569,7 @@ static int enqueue_window_finish(ppp_handle h, bool finish_lists)
 {
     WinArgs A = win_args(h);
     A.stage_lists = finish_lists ? 1 : 0;
+    A.prio = h->win_prio_finish;
     if (h->quiet_finish) A.meta_host = nullptr; /* (win_publish_meta: no arrival counters, no write to pinned memory) */
     LAUNCH(h, "k_win_finish", k_win_finish, A.g_finish, SMF_T, sizeof(int) * ((size_t)A.nkept + 2), A);
     return PPP_OK;
@@ -2837,6 +2854,18 @@ int ppp_get_binning_form(ppp_handle h, int *threads, int *points_per_thread)
     const bool win = h->have_cloud && h->win_path;
     *threads = win ? h->win_scat_threads : 0;
     *points_per_thread = win ? h->win_ppt : 0;
+    return PPP_OK;
+}
+
+int ppp_get_launch_priorities(ppp_handle h, int *binning, int *per_slice, int *finish)
+{
+    if (!h || !binning || !per_slice || !finish) return PPP_ERR_ARG;
+    if (h->have_cloud) { HIPCHK(h, hipSetDevice(h->device)); int rcs = settle(h); if (rcs) return rcs; }
+    if (h->have_cloud && !h->pass.planned()) { int rc = make_plan(h); if (rc) return rc; }
+    const bool win = h->have_cloud && h->win_path;
+    *binning = 0;
+    *per_slice = 0;
+    *finish = win ? h->win_prio_finish : 0;
     return PPP_OK;
 }
 

@@ -405,6 +405,7 @@ struct ppp_handle_s {
     int win_NBc_thr = 0; /* y-buckets per class in launches of several workgroups per CU: the most that cost no workgroup its place in the LDS */
     int win_capw = 0, win_cap_el = 0, win_NB = 0, win_NBc = 0, win_stride = 1, win_threads = 256, win_ppt = 4, win_gs = 1;
     int win_scat_threads = WSC_T; /* threads of a binning workgroup (win_pick_scatter: narrower where passes share the device) */
+    int win_prio_finish = 0;      /* WinArgs.prio of the by-value finish launch (win_pick_prio: 0 for a pass alone) */
     int win_ppt_alone = 4;        /* points per thread of the 1024-thread form: what a batch falls back to whose members chose different forms */
     int win_rec_lds = 0; /* waypoint records parked in the slice workgroup's LDS (0: in global slots) */
     int win_nkept = 0, win_first_kept = 0, win_el_expect = 0;

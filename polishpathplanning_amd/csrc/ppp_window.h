@@ -168,6 +168,20 @@ __device__ __forceinline__ void win_scatter_body(const WinArgs &A, const int bx)
    memory (vmcnt counts loads and stores alike on this target, so __syncthreads() would sit out the prefetch below). */
 __device__ __forceinline__ void win_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+/* Wave priority of the finish launch where passes share the device (WinArgs.prio; the engine's win_pick_prio): a CU's SIMDs then hold
+   the finish waves of one pass next to the per-slice and binning waves of its neighbours, and the instruction arbiter picks by
+   priority first, by age second.  The finish launch is the last and shortest link of a pass's chain, and the handle's next pass
+   waits for it.  The priority instruction is scalar and ignores the execution mask; `p` comes from the launch arguments, the same
+   in every wave.  It changes no value anywhere.  (Measured, profiles/sbs_priority_ab.txt: the same on the per-slice launch, from its
+   entry or in its pose phase, moves nothing; the finish waves keep theirs to the end -- dropped ahead of the filter it is half
+   the gain.) */
+__device__ __forceinline__ void win_prio_raise(const int p)
+{
+    if (p == 1) __builtin_amdgcn_s_setprio(1);
+    else if (p == 2) __builtin_amdgcn_s_setprio(2);
+    else if (p == 3) __builtin_amdgcn_s_setprio(3);
+}
+
 /* The staged binning of a large cloud as a LOOP: a workgroup takes chunks bx, bx + nwg, ... of PPT x blockDim points.  Its LDS
    stage admits one workgroup per CU, whose phases -- points from memory, ranks, reservations, stage, stores -- used to follow one
    another with the memory pipes idle in between; here the next chunk's points are requested as soon as the reservations of the
@@ -1317,6 +1331,9 @@ __device__ __forceinline__ void win_finish_body(const WinArgs &A, const int bx)
                     for (int i = 0; i < 3; ++i) t[i] = R[i][0] * ee[0] + R[i][1] * ee[1] + R[i][2] * ee[2] + p[i] * 1.f;
                     p[0] = t[0]; p[1] = t[1]; p[2] = t[2];
                 }
+#ifdef WIN_PRIO_DROP_AT_STORES /* (A/B builds: the raised priority of win_prio_raise given back ahead of the launch's last stores; no better, profiles/sbs_priority_ab.txt) */
+                if (A.prio) __builtin_amdgcn_s_setprio(0);
+#endif
                 for (int d = 0; d < 6; ++d) A.wp_out[6 * (size_t)g + d] = p[d];
                 if (copy2 && !in_order) for (int d = 0; d < 6; ++d) A.out2[6 * (size_t)g + d] = p[d];
             }
@@ -1535,7 +1552,12 @@ __device__ __forceinline__ void win_publish_meta(const WinArgs &A)
     for (int q = threadIdx.x; q < (int)(sizeof(DevMeta) / sizeof(int)); q += blockDim.x) dst[q] = __hip_atomic_load(src + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x == 0) __hip_atomic_store(A.fin_ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__global__ void __launch_bounds__(SMF_T) k_win_finish(WinArgs A) { win_finish_body<false>(A, blockIdx.x); win_publish_meta(A); }
+__global__ void __launch_bounds__(SMF_T) k_win_finish(WinArgs A)
+{
+    win_prio_raise(A.prio);
+    win_finish_body<false>(A, blockIdx.x);
+    win_publish_meta(A);
+}
 __global__ void __launch_bounds__(SMF_T) k_win_finish_b(const WinArgs *__restrict__ mem)
 {
     const WinArgs &A = mem[blockIdx.y];

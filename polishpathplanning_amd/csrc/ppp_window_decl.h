@@ -40,6 +40,7 @@ struct WinArgs {
     int rec_lds; /* waypoint records in the slice workgroup's LDS (the pairing scratch the knots leave free): waypoints per word row; 0: in the waypoints' global slots (wps_rec) */
     int g_scatter, g_slice, g_finish; /* workgroups of this workpiece per launch */
     int finish; /* 0: a slice-range handle stops after HandEyeTransform (the list is compacted only) */
+    int prio; /* wave priority (1..3) that the by-value finish launch of a pass that shares the device raises its waves to (win_prio_raise); 0, and in every other launch: the waves stay at the priority they start with */
     int stage_lists; /* 1: the finish launch also writes wp_pre / wp_smooth (a slice-range handle's and the in-order finish's launch always does); 0: k_win_stage_lists makes them when somebody asks */
     int *win_cnt;
     float4 *win_pts;

@@ -82,7 +82,7 @@ EXPORTS = [
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
     "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
-    "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
+    "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
 
@@ -122,6 +122,7 @@ def lib():
         L.ppp_set_cloud_device_async.argtypes = [vp, vp, sz, sz, fp]
         L.ppp_set_side_by_side.argtypes = [vp, C.c_int]
         L.ppp_get_binning_form.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.ppp_get_launch_priorities.argtypes = [vp] + [C.POINTER(C.c_int)] * 3
         L.ppp_queue_create.argtypes = [C.c_int, C.c_int, C.POINTER(Params), C.POINTER(vp)]
         L.ppp_queue_destroy.argtypes = [vp]; L.ppp_queue_destroy.restype = None
         L.ppp_queue_submit.argtypes = [vp, vp, sz, sz, fp, C.POINTER(C.c_longlong)]
@@ -1243,6 +1244,13 @@ class Engine:
         t, p = C.c_int(), C.c_int()
         self._chk(self.L.ppp_get_binning_form(self.h, C.byref(t), C.byref(p)))
         return t.value, p.value
+
+    def launch_priorities(self):
+        """ppp_get_launch_priorities: the wave priorities (binning, per-slice, finish) the current plan launches the window pass with;
+        all 0 for a pass alone and on the slab-index path."""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(self.L.ppp_get_launch_priorities(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def fast_path(self):
         """True when the current plan runs the window path (three launches), False for the slab-index path."""
