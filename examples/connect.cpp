@@ -15,6 +15,8 @@
 // the triangles that face the origin).  PPP_DEVIATION=<reference.stl> ./connect scan.pcd measures (and with PPP_REGISTER registers) the scan against the mesh; ./connect part.stl plans on the nominal itself.
 // PPP_DEVIATION=<reference.stl> PPP_DEVIATION_EXACT=1 measures against the triangles themselves (ppp_get_mesh_deviation: the closest point on the nearest triangle, along that facet's normal; no pitch):
 // the same block, plus the closest points by region; PPP_TRIMESH_CELL sets the grid's cell (0 = automatic; the numbers do not depend on it), PPP_TRIMESH_ORIENT=viewpoint turns every facet normal to the origin's side.
+// PPP_REGISTER=mesh PPP_DEVIATION=<reference.stl> registers against the triangles themselves (ppp_register_mesh: the exact closest point, the facet's own normal; no pitch, no estimated normal):
+// ppp_register's lines, and the cloud moved by T; PPP_REGISTER=1 with an STL still registers against its samples.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -46,6 +48,7 @@ int main(int argc, char **argv)
     }
     if (reference && reg && std::string(reg) == "global") path_planner.register_global_to(*reference); /* from an unknown pose */
     if (reference && reg && std::string(reg) == "robust") path_planner.register_robust_to(*reference); /* Tukey weights: no keep to choose */
+    if (reference && reg && std::string(reg) == "mesh" && ppp::Planner::is_stl_name(devf)) path_planner.register_to_mesh(devf); /* on the facets, not on their samples */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");

@@ -94,6 +94,9 @@ public:
        and after, the steps, the locked unknowns and T, and moves the cloud by T when the loop converged (ppp_transform_cloud:
        plan again afterwards).  ICP needs a start within the basin: a fixturing error, not an unknown pose */
     void register_to(const path_generater &ref) { planner.print_registration(ref.planner, ppp::Planner::registration_params_env()); }
+    /* register_to() against the triangles of the STL file `stl` themselves (ppp_register_mesh): the exact closest
+       point and the facet's own normal, no pitch; the same lines */
+    void register_to_mesh(const std::string &stl) { planner.print_mesh_registration(stl, ppp::Planner::registration_params_env()); }
     /* register_to() with the trimmed loop (ppp_register_trimmed; keep from PPP_REGISTER_KEEP, 0.8 where it is not set): a line
        with the kept and the paired counts and the cut, then register_to()'s lines over the kept pairs */
     void register_trimmed_to(const path_generater &ref) { planner.print_registration(ref.planner, ppp::Planner::trimmed_registration_params_env()); }

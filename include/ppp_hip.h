@@ -641,6 +641,36 @@ int  ppp_get_registration_terms(ppp_handle h, ppp_handle ref, const ppp_registra
                                 ppp_registration_row *row, ppp_registration_stats *stats);
 int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *rp, const double *T0_12,
                   ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats);
+/* Registration of a scan to the triangle mesh itself: point-to-plane ICP on the facets that
+   ppp_get_mesh_deviation measures against.  h holds the scan, m is a ppp_trimesh; no pitch, no sampled cloud and no estimated
+   normal enter the fit.  Everything is ppp_register's, word for word, except:
+     centre     mn, mx = the mesh's box (m's ppp_trimesh_stats mn / mx, floats widened): c[d] = (mn[d] + mx[d]) * 0.5;
+                Ln = (((ex + ey) + ez) * 0.5) + (double)max_dist, e = mx - mn
+     shift      ppp_register's (n = cloud->size() of h, the product max_dist * max_dist in float); shift < 16 is refused
+     moved      p'[r] = ((T[4r] px + T[4r+1] py) + T[4r+2] pz) + T[4r+3] in double, and THE QUERY IS p' ITSELF, in double, not its
+                float (at T = identity p' is the point's float widened, exactly); a p' that is not finite is no pair
+     pair       f* = the nearest indexed triangle of m to p' by (D2, f) -- the search of ppp_get_mesh_deviation's comment, the
+                brute force's answer over all indexed triangles whatever the cell -- with x its closest point; a pair where
+                D2 <= (double)max_dist * (double)max_dist (inclusive).  Every region pairs: face, edge and vertex
+     terms      q = x (double); n = (Nx / A2, Ny / A2, Nz / A2) of f*'s frame; e = p' - x; r = ((ex nx) + ey ny) + ez nz; u, a, J and
+                the 21 + 6 + 1 words with llrint(... 2^shift) are ppp_register's expressions on these doubles
+     orientation  PPP_TRIMESH_WINDING or _VIEWPOINT is NOT applied, and need not be: n -> -n negates J and r together, a
+                negation is exact, so every product J_i J_k, J_i r and r r is the same double either way, and so is every word:
+                a mesh made with either orientation gives the same rows
+   Solve, step, composition, the loop's endings, rows and stats are ppp_register's.  On an edge or a vertex the normal is the
+   winning facet's (pseudonormals are out of scope), and the scan's overhang beyond an open mesh's border pairs there with the
+   border facet's normal as long as it lies within max_dist (no pair is rejected on the border).  Trimmed and robust weights,
+   tiles over slice ranges and a global start from the mesh are not offered here.
+   ppp_get_mesh_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; ppp_register_mesh runs the loop
+   from T0_12; row, rows and stats are filled as ppp_get_registration_terms and ppp_register fill them.  Both build h's slab index
+   where it is missing, enqueue the whole chain (iterations + 1 evaluations, iterations steps) on h's stream and wait once; the
+   mesh is read-only after its create call.  Neither changes h's cloud, plan or stored results, nor the mesh.
+   PPP_ERR_ARG: m or rp NULL; rows NULL with row_cap > 0; ppp_register's parameter ranges; a T entry that is not finite; no cloud
+   on h; a mesh on another device than h; shift < 16.  PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+int  ppp_get_mesh_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T12,
+                                     ppp_registration_row *row, ppp_registration_stats *stats);
+int  ppp_register_mesh(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T0_12,
+                       ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats);
 /* Trimmed registration: ppp_register's loop in which only the share `keep` of an evaluation's pairs
    with the smallest pair distance enters its sums (trimmed ICP, Chetverikov et al.).  A scan from a cell carries what the
    reference does not show -- a clamp pad, a strip of the table, a burr, an edge -- within max_dist of it; such points pair, pull

@@ -685,6 +685,40 @@ public:
         ppp_registration_stats st = {};
         const bool ran = register_to(ref, st, rp);
         if (!ran) st = ppp_registration_stats{};
+        return print_registration_lines(st, rp, ran, apply);
+    }
+    /* point-to-plane ICP of this planner's cloud, the scan, to the triangles of mesh themselves (ppp_register_mesh):
+       register_to() with the exact closest point and the facet's own normal in the place of a sample and its estimated normal --
+       no pitch enters the fit, and it is taken on the facets mesh_deviation() measures against.  st, T0 and rows as register_to()'s */
+    bool register_mesh(const TriMesh &mesh, ppp_registration_stats &st, const ppp_registration_params &rp, const double *T0 = nullptr,
+                       std::vector<ppp_registration_row> *rows = nullptr)
+    {
+        if (rows) rows->assign((size_t)(rp.iterations > 0 ? rp.iterations : 0) + 1, ppp_registration_row{});
+        int rc = ppp_register_mesh(h_, mesh.get(), &rp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, &st);
+        if (rc != PPP_OK) { if (rows) rows->clear(); return report(rc); }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* print_registration() for the STL file `name` registered to as triangles (TriMesh::params_from_env()): the grid's line on
+       stderr, register_mesh() from the identity, print_registration()'s five lines and, with apply, the cloud moved */
+    bool print_mesh_registration(const std::string &name, const ppp_registration_params &rp, bool apply = true)
+    {
+        TriMesh mesh;
+        ppp_registration_stats st = {};
+        const int rc = mesh.open_stl(h_, name);
+        if (rc == PPP_ERR_IO) std::fprintf(stderr, "Cloudn't read file!\n");
+        else if (rc != PPP_OK) report(rc);
+        else
+            std::fprintf(stderr, "ppp: %s: %zu triangles (%zu degenerate) in %zu x %zu x %zu cells of %g: %zu pairs, %zu at most in a cell\n", name.c_str(),
+                         mesh.stats().triangles, mesh.stats().degenerate, mesh.stats().cells[0], mesh.stats().cells[1], mesh.stats().cells[2],
+                         (double)mesh.stats().cell, mesh.stats().pairs, mesh.stats().max_per_cell);
+        const bool ran = rc == PPP_OK && register_mesh(mesh, st, rp);
+        if (!ran) st = ppp_registration_stats{};
+        return print_registration_lines(st, rp, ran, apply);
+    }
+    /* print_registration()'s five lines on the statistics of a chain that ran (or did not), and its move of the cloud */
+    bool print_registration_lines(const ppp_registration_stats &st, const ppp_registration_params &rp, bool ran, bool apply)
+    {
         std::printf("registration: %zu of %zu points paired, rms %f mm; after %d steps %zu paired, rms %f mm\n", st.pairs_before, st.indexed,
                     st.pairs_before ? st.rms_before : 0.0, st.steps, st.pairs_after, st.pairs_after ? st.rms_after : 0.0);
         std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",

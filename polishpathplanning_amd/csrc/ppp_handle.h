@@ -317,7 +317,7 @@ struct ppp_handle_s {
         DevBuf<float4> queries;
         /* ppp_register_trimmed: per query in slab order the reference point of its pair and the key of the pair's d2 (the last
            evaluation's), per evaluation the three digit histograms and the cut (TrimCut, as words), and the two maps by cloud
-           index */
+           index.  ppp_register_mesh keeps the winning record of every query of the current evaluation in key */
         DevBuf<float4> partner;
         DevBuf<unsigned> key, hist, cuts;
         DevBuf<unsigned char> tstatus;

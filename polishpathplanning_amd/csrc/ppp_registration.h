@@ -170,6 +170,27 @@ __device__ __attribute__((always_inline)) inline void icp_add_terms(unsigned lon
     a[ICP_E] += (unsigned long long)llrint((r * r) * F.scale);
 }
 
+/* the same 29 terms for a partner and a normal that are doubles already (k_mesh_reg_terms: the closest point on a triangle and
+   the facet's own normal): the float4 form's expressions, operation for operation, without its widening casts */
+__device__ __attribute__((always_inline)) inline void icp_add_terms(unsigned long long *a, const double *m, const double *q, const double *n,
+                                                                   const IcpFrame &F)
+{
+    const double nx = n[0], ny = n[1], nz = n[2];
+    const double ex = m[0] - q[0], ey = m[1] - q[1], ez = m[2] - q[2];
+    const double r = ((ex * nx) + ey * ny) + ez * nz;
+    const double ux = (m[0] - F.c[0]) / F.Ln, uy = (m[1] - F.c[1]) / F.Ln, uz = (m[2] - F.c[2]) / F.Ln;
+    const double J[6] = {uy * nz - uz * ny, uz * nx - ux * nz, ux * ny - uy * nx, nx, ny, nz};
+    a[ICP_PAIRS] += 1;
+    int w = ICP_A;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int k = i; k < 6; ++k, ++w) a[w] += (unsigned long long)llrint((J[i] * J[k]) * F.scale);
+        a[ICP_B + i] += (unsigned long long)llrint((J[i] * r) * F.scale);
+    }
+    a[ICP_E] += (unsigned long long)llrint((r * r) * F.scale);
+}
+
 /* the threads' words of a workgroup of T threads into acc: over the wave, over the workgroup through LDS, and one 64-bit
    integer atomic per non-zero word */
 template <int T>

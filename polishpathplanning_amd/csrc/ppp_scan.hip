@@ -22,6 +22,7 @@
 #include "ppp_trimmed_tile.h"
 #include "ppp_robust_tile.h"
 #include "ppp_trimesh.h"
+#include "ppp_mesh_registration.h"
 #include "ppp_sort.h"
 #include <cstring>
 
@@ -287,6 +288,39 @@ static void trimmed_row(ppp_trimmed_registration_row &o, const ppp_registration_
     memcpy(&o.trim_d2, &tau, sizeof(float));
 }
 
+/* What ppp_register's chain and ppp_register_mesh's have in common on either side of their launches.  chain_open: room for
+   `evals` evaluations in h->registration's buffers, the words and the control block cleared on h's stream, T at the chain's head.
+   chain_collect: the one wait, the control words' and the sums' sanity checks (w: the call's name), and the rows R[0 .. C.steps],
+   the last of them from the evaluation no step kernel follows where the chain used up its iterations. */
+static int chain_open(ppp_handle h, size_t evals, const double *T)
+{
+    auto &G = h->registration;
+    HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ICP_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * evals * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.T.p, T, 12 * sizeof(double), hipMemcpyHostToDevice));
+    return PPP_OK;
+}
+
+static int chain_collect(ppp_handle h, const char *w, int iterations, int nq, IcpCtl &C, std::vector<ppp_registration_row> &R)
+{
+    auto &G = h->registration;
+    HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
+    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, std::string(w) + ": control words corrupt");
+    const size_t last = (size_t)C.steps;
+    R.resize(last + 1);
+    HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    if (!C.done) { /* the evaluation behind the last step: no step kernel follows it */
+        unsigned long long acc[ICP_WORDS];
+        double Tl[12];
+        HIPCHK(h, copy_sync(h, acc, G.acc.p + ICP_WORDS * last, sizeof(acc), hipMemcpyDeviceToHost));
+        HIPCHK(h, copy_sync(h, Tl, G.T.p + 12 * last, sizeof(Tl), hipMemcpyDeviceToHost));
+        icp_row_terms(&R[last], Tl, acc);
+    }
+    if (R[0].pairs > (size_t)std::max(nq, 0) || R[last].pairs > (size_t)std::max(nq, 0)) return fail(h, PPP_ERR_HIP, std::string(w) + ": sums corrupt");
+    return PPP_OK;
+}
+
 /* The registration chain: the reference's index and normal field on its own stream, one wait for that stream,
    then iterations + 1 evaluations (k_reg_terms) and iterations steps (k_reg_step) back to back on the scan's stream -- the
    transforms, the sums and the rows stay on the device, a chain that has ended turns the rest of its launches into returns --
@@ -324,11 +358,9 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
     const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
     auto &G = h->registration;
     const size_t evals = (size_t)iterations + 1;
-    HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ICP_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
+    rc = chain_open(h, evals, T);
+    if (rc) return rc;
     IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
-    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ICP_WORDS * evals * sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
-    HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
     /* grid-stride: the workgroups, and with them the atomics of an evaluation, are capped by the device, not by the cloud */
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus));
     const size_t N1 = std::max<size_t>(N, 1);
@@ -364,19 +396,10 @@ static int registration_chain(ppp_handle h, ppp_handle ref, const ppp_registrati
     if (trim)
         LAUNCH(h, "k_trim_scatter", k_trim_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, ctl, cuts, (int)evals, (int)N1, G.tstatus.p, G.td2.p);
     IcpCtl C;
-    HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
-    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, "registration: control words corrupt");
+    std::vector<ppp_registration_row> R;
+    rc = chain_collect(h, "registration", iterations, nq, C, R);
+    if (rc) return rc;
     const size_t last = (size_t)C.steps;
-    std::vector<ppp_registration_row> R(last + 1);
-    HIPCHK(h, copy_sync(h, R.data(), G.rows.p, (last + 1) * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
-    if (!C.done) { /* the evaluation behind the last step: no step kernel follows it */
-        unsigned long long acc[ICP_WORDS];
-        double Tl[12];
-        HIPCHK(h, copy_sync(h, acc, G.acc.p + ICP_WORDS * last, sizeof(acc), hipMemcpyDeviceToHost));
-        HIPCHK(h, copy_sync(h, Tl, G.T.p + 12 * last, sizeof(Tl), hipMemcpyDeviceToHost));
-        icp_row_terms(&R[last], Tl, acc);
-    }
-    if (R[0].pairs > (size_t)std::max(nq, 0) || R[last].pairs > (size_t)std::max(nq, 0)) return fail(h, PPP_ERR_HIP, "registration: sums corrupt");
     if (stats) *stats = registration_stats(R, C, N, (size_t)nq, shift, F.c, F.Ln);
     const size_t k = std::min(row_cap, last + 1);
     if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
@@ -1869,6 +1892,82 @@ int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_para
     if (distance && k) HIPCHK(h, copy_sync(h, distance, D.dist.p, k * sizeof(double), hipMemcpyDeviceToHost));
     if (region && k) HIPCHK(h, copy_sync(h, region, D.region.p, k, hipMemcpyDeviceToHost));
     return PPP_OK;
+}
+
+/* The mesh registration chain: registration_chain's shape with the mesh in the reference's place -- the scan's
+   slab index, then iterations + 1 evaluations (k_mesh_reg_search and k_mesh_reg_sum; k_mesh_reg_terms in a fused build) and iterations steps (k_reg_step, unchanged) back to back on the
+   scan's stream, in h->registration's buffers, and one wait.  The mesh is read-only since its create call waited: nothing to
+   wait for on its side.  !loop: the one evaluation of ppp_get_mesh_registration_terms. */
+static int mesh_registration_chain(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T0, bool loop,
+                                   ppp_registration_row *rows, size_t row_cap, ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!m || !rp) return fail(h, PPP_ERR_ARG, "mesh registration: no mesh or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "mesh registration: rows is NULL with row_cap > 0");
+    const ppp_registration_params P = *rp;
+    IcpFrame F;
+    int rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, "mesh registration", T0, T);
+    if (rc) return rc;
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "mesh registration: the mesh is on another device than the handle");
+    rc = deviation_side(h, h, "the scan", "mesh registration");
+    if (rc) return rc;
+    const int shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "mesh registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    const TriGrid &M = m->G;
+    const float mn[3] = {(float)M.mn[0], (float)M.mn[1], (float)M.mn[2]}, mx[3] = {(float)M.mx[0], (float)M.mx[1], (float)M.mx[2]}; /* (floats, widened: exact) */
+    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    const double md2 = (double)P.max_dist * (double)P.max_dist;
+    const size_t N = h->n;
+    const int nq = h->hmeta.n_sorted;
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    rc = chain_open(h, evals, T);
+    if (rc) return rc;
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    /* grid-stride under MESH_REG_GRID_CUS workgroups per compute unit (0: a thread per query); the words do not depend on it */
+    const size_t cap = MESH_REG_GRID_CUS ? (size_t)MESH_REG_GRID_CUS * (size_t)h->num_cus : (size_t)0x7fffffff;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)std::max(nq, 0) + ICP_T - 1) / ICP_T, cap));
+#if MESH_REG_SPLIT
+    HIPCHK(h, G.key.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1))); /* the winning record per query (the trimmed chain's key buffer) */
+    const unsigned gsearch = (unsigned)std::max<size_t>(1, ((size_t)std::max(nq, 0) + TM_T - 1) / TM_T);
+#endif
+    for (int k = 0; k <= iterations; ++k) {
+#if MESH_REG_SPLIT
+        LAUNCH(h, "k_mesh_reg_search", k_mesh_reg_search, gsearch, TM_T, 0, (const float4 *)h->sorted4.p, nq, M, md2, G.T.p + 12 * (size_t)k, ctl, G.key.p);
+        LAUNCH(h, "k_mesh_reg_sum", k_mesh_reg_sum, grid, ICP_T, 0, (const float4 *)h->sorted4.p, nq, M, F, G.T.p + 12 * (size_t)k, ctl, G.key.p,
+               G.acc.p + ICP_WORDS * (size_t)k);
+#else
+        LAUNCH(h, "k_mesh_reg_terms", k_mesh_reg_terms, grid, ICP_T, 0, (const float4 *)h->sorted4.p, nq, M, F, md2, G.T.p + 12 * (size_t)k, ctl,
+               G.acc.p + ICP_WORDS * (size_t)k);
+#endif
+        if (k < iterations)
+            LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, G.acc.p + ICP_WORDS * (size_t)k, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    IcpCtl C;
+    std::vector<ppp_registration_row> R;
+    rc = chain_collect(h, "mesh registration", iterations, nq, C, R);
+    if (rc) return rc;
+    if (stats) *stats = registration_stats(R, C, N, (size_t)nq, shift, F.c, F.Ln);
+    const size_t k = std::min(row_cap, (size_t)C.steps + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    return PPP_OK;
+}
+
+int ppp_get_mesh_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                                    ppp_registration_stats *stats)
+{
+    return mesh_registration_chain(h, m, rp, T12, false, row, row ? 1 : 0, stats);
+}
+
+int ppp_register_mesh(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T0_12, ppp_registration_row *rows, size_t row_cap,
+                      ppp_registration_stats *stats)
+{
+    return mesh_registration_chain(h, m, rp, T0_12, true, rows, row_cap, stats);
 }
 
 } // extern "C"

@@ -82,6 +82,7 @@ EXPORTS = [
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
     "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
+    "ppp_get_mesh_registration_terms", "ppp_register_mesh",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -273,6 +274,8 @@ def lib():
         L.ppp_trimesh_destroy.restype = None
         L.ppp_trimesh_nearest.argtypes = [vp, fp, sz, C.c_float, dp, dp, dp, ip, ubp, ubp]
         L.ppp_get_mesh_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, dp, sz, C.POINTER(MeshDeviationStats)]
+        L.ppp_get_mesh_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
+        L.ppp_register_mesh.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
         L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
         L.ppp_save_stl.argtypes = [C.c_char_p, fp, sz, C.c_int]
         _lib = L
@@ -1396,6 +1399,34 @@ class Engine:
         stats = _deviation_stats(st.dev)
         stats.update(on_face=int(st.on_face), on_edge=int(st.on_edge), on_vertex=int(st.on_vertex), max_distance=float(st.max_distance))
         return dev, sm, dist, idx, region, status, target, stats
+
+    def mesh_registration_terms(self, mesh, T=None, max_dist=2.0, lock_eps=1e-9):
+        """(row, stats) of one evaluation of the point-to-plane terms of this engine's cloud, the scan, moved by T (3 x 4, None:
+        the identity), against the TriMesh `mesh` (ppp_get_mesh_registration_terms): the partner of a moved point is the closest
+        point on its nearest triangle within max_dist mm, the normal that facet's own.  row and stats as registration_terms()
+        gives them; no step is taken"""
+        rp = RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps))
+        row, st = RegistrationRow(), RegistrationStats()
+        t = _t12(T)
+        m = mesh.m if mesh is not None else None
+        self._chk(self.L.ppp_get_mesh_registration_terms(self.h, m, C.byref(rp), None if t is None else _d(t), C.byref(row), C.byref(st)))
+        return _registration_row(row), _registration_stats(st)
+
+    def register_mesh(self, mesh, T0=None, rows=True, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9):
+        """(T float64[3, 4], rows, stats): point-to-plane ICP of this engine's cloud, the scan, to the triangles of the TriMesh
+        `mesh` themselves (ppp_register_mesh), started at T0 (None: the identity): register()'s loop with the exact closest point
+        and the facet's own normal in the place of a sample and its estimated normal, so that neither a pitch nor a smeared crease
+        enters the fit.  T, rows and stats as register() gives them; rows=False asks for none, an integer caps their number.
+        Neither the cloud nor the mesh is changed"""
+        rp = RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps))
+        cap = max(int(iterations), 0) + 1 if rows is True else (0 if rows is False else int(rows))
+        out = (RegistrationRow * max(cap, 1))()
+        st = RegistrationStats()
+        t = _t12(T0)
+        m = mesh.m if mesh is not None else None
+        self._chk(self.L.ppp_register_mesh(self.h, m, C.byref(rp), None if t is None else _d(t), out if cap else None, cap, C.byref(st)))
+        stats = _registration_stats(st)
+        return stats["T"].copy(), [_registration_row(out[k]) for k in range(min(cap, st.steps + 1))], stats
 
     def range_interval(self, min_x, max_x):
         """(lo, hi, S): the planner-unit x interval this handle's slice range indexes for a cloud with these x bounds."""
