@@ -17,6 +17,8 @@
 // the same block, plus the closest points by region; PPP_TRIMESH_CELL sets the grid's cell (0 = automatic; the numbers do not depend on it), PPP_TRIMESH_ORIENT=viewpoint turns every facet normal to the origin's side.
 // PPP_REGISTER=mesh PPP_DEVIATION=<reference.stl> registers against the triangles themselves (ppp_register_mesh: the exact closest point, the facet's own normal; no pitch, no estimated normal):
 // ppp_register's lines, and the cloud moved by T; PPP_REGISTER=1 with an STL still registers against its samples.
+// PPP_REGISTER=mesh-robust PPP_DEVIATION=<part.stl> does so under the robust loop's weights (ppp_register_mesh_robust; PPP_REGISTER_TUNE, _SIGMA_MIN): for a scan that shows a
+// clamp or a strip of the table within reach of the part; PPP_REGISTER=robust's lines with the facets' numbers.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -49,6 +51,7 @@ int main(int argc, char **argv)
     if (reference && reg && std::string(reg) == "global") path_planner.register_global_to(*reference); /* from an unknown pose */
     if (reference && reg && std::string(reg) == "robust") path_planner.register_robust_to(*reference); /* Tukey weights: no keep to choose */
     if (reference && reg && std::string(reg) == "mesh" && ppp::Planner::is_stl_name(devf)) path_planner.register_to_mesh(devf); /* on the facets, not on their samples */
+    if (reference && reg && std::string(reg) == "mesh-robust" && ppp::Planner::is_stl_name(devf)) path_planner.register_robust_to_mesh(devf); /* the facets under Tukey weights */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");

@@ -7,6 +7,8 @@
 // PPP_REGISTER=1 beside it registers the cloud to that reference first, before the path is planned (pairs, rms before and after, steps, locked unknowns, T); PPP_REGISTER_KEEP=<share below 1> beside PPP_REGISTER=1 runs the trimmed loop instead (every evaluation keeps that share of its pairs with the smallest pair distance: for a scan with a clamp, a burr or an edge the reference does not have; the kept and the paired counts and the cut are printed); PPP_REGISTER=global does so from an unknown pose.  PPP_REGISTER=robust weighs every pair by Tukey's biweight of its point-to-plane residual, scaled by the median absolute residual of each evaluation (no share to choose; PPP_REGISTER_TUNE, _SIGMA_MIN).
 // PPP_REGISTER=mesh PPP_DEVIATION=<reference.stl> registers against the triangles themselves (ppp_register_mesh: the exact closest point, the facet's own normal; no pitch, no estimated normal):
 // ppp_register's lines, and the cloud moved by T; PPP_REGISTER=1 with an STL still registers against its samples.
+// PPP_REGISTER=mesh-robust PPP_DEVIATION=<part.stl> does so under the robust loop's weights (ppp_register_mesh_robust; PPP_REGISTER_TUNE, _SIGMA_MIN): for a scan that shows a
+// clamp or a strip of the table within reach of the part; PPP_REGISTER=robust's lines with the facets' numbers.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -41,6 +43,7 @@ int main(int argc, char **argv)
     if (reference && reg && std::string(reg) == "global") path_planner.register_global_to(*reference); /* from an unknown pose */
     if (reference && reg && std::string(reg) == "robust") path_planner.register_robust_to(*reference); /* Tukey weights: no keep to choose */
     if (reference && reg && std::string(reg) == "mesh" && ppp::Planner::is_stl_name(devf)) path_planner.register_to_mesh(devf); /* on the facets, not on their samples */
+    if (reference && reg && std::string(reg) == "mesh-robust" && ppp::Planner::is_stl_name(devf)) path_planner.register_robust_to_mesh(devf); /* the facets under Tukey weights */
     path_planner.GenPath();
     path_planner.getPath();
     const char *cov = std::getenv("PPP_PATH_COVERAGE");

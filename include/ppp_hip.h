@@ -659,8 +659,8 @@ int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *r
                 a mesh made with either orientation gives the same rows
    Solve, step, composition, the loop's endings, rows and stats are ppp_register's.  On an edge or a vertex the normal is the
    winning facet's (pseudonormals are out of scope), and the scan's overhang beyond an open mesh's border pairs there with the
-   border facet's normal as long as it lies within max_dist (no pair is rejected on the border).  Trimmed and robust weights,
-   tiles over slice ranges and a global start from the mesh are not offered here.
+   border facet's normal as long as it lies within max_dist (no pair is rejected on the border).  Robust weights are
+   ppp_register_mesh_robust's (below); trimmed weights, tiles over slice ranges and a global start from the mesh are not offered.
    ppp_get_mesh_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; ppp_register_mesh runs the loop
    from T0_12; row, rows and stats are filled as ppp_get_registration_terms and ppp_register fill them.  Both build h's slab index
    where it is missing, enqueue the whole chain (iterations + 1 evaluations, iterations steps) on h's stream and wait once; the
@@ -774,6 +774,48 @@ int  ppp_register_robust(ppp_handle h, ppp_handle ref, const ppp_robust_registra
                          ppp_robust_registration_row *rows, size_t row_cap,
                          unsigned char *status, float *weight, double *residual, size_t cap,
                          ppp_registration_stats *stats);
+/* Robust registration of a scan to the triangle mesh itself: ppp_register_mesh's pairs on the
+   facets under ppp_register_robust's weights, for a scan that shows what the mesh does not -- a clamp pad, a strip of the
+   table, a burr -- within max_dist of it.  No struct or enum is new: the parameters, the row and PPP_ROBUST_* are
+   ppp_register_robust's.
+     centre, shift, moved, pair   ppp_register_mesh's, word for word: the frame from the mesh's box; ppp_register's shift,
+                shift < 16 refused; the query is the moved point p' itself, in double; the winner is the nearest indexed
+                triangle by (D2, f) with its exact closest point x; a pair where D2 <= (double)max_dist * (double)max_dist
+                (inclusive), in every region; paired = their number
+     residual   r = ((ex nx) + ey ny) + ez nz with e = p' - x and n = N / A2 of the winning record's own frame:
+                ppp_register_mesh's double
+     key, scale, weight, terms    ppp_register_robust's, word for word: the key is the bits of (float)fabs(r); k =
+                ppp_trim_rank(0.5, paired) through the three digit histograms; sigma = max(1.4826 * m, sigma_min), cs = tune *
+                sigma; w as there; 30 words, each product times w before llrint(... 2^shift), with ppp_register_mesh's u and J on
+                doubles; used = the pairs with w > 0, which is what the step reads as its pairs.  paired == 0: median_abs is the
+                float quiet NaN 0x7fc00000, sigma the double quiet NaN 0x7ff8000000000000, and no step is taken
+     rows, stats, maps, endings   ppp_register_robust's: row.pairs = paired; rms_* = sqrt((double)E / (double)weight_sum); the maps
+                by cloud index of h from the LAST evaluation; PPP_ROBUST_DROPPED for a point that is not finite,
+                PPP_ROBUST_UNPAIRED for one without a pair and for one whose moved point is not finite
+     orientation  PPP_TRIMESH_WINDING or _VIEWPOINT is NOT applied.  Flipping a facet negates r and J together: |r|, the key, w
+                (even in r) and every product are unchanged, so every word and every row is the same either way.  The residual
+                MAP is signed by the record's own normal (its winding as given), so it is negated where the facet is flipped
+   tune == +INFINITY weighs every pair 1: rows[k].row, T and stats are ppp_register_mesh's bits from the same start.  Every
+   output is the same for every grid cell of the mesh, and the same bits in every run.  The estimator's limit is
+   ppp_register_robust's: the median residual must belong to the part that shows the mesh (with 35 % of the scan raised by 1.5 mm
+   it does not, and the fit stays tilted).  Trimmed weights, tiles over slice ranges, a global start from the mesh,
+   pseudonormals and border rejection are not offered.
+   ppp_get_mesh_robust_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; its maps are that
+   evaluation's.  rows, row, the maps and stats may be NULL (rows with row_cap = 0; the maps with any cap).  The whole chain -- per
+   evaluation the grid walk, paid once, with the residual, the key and the top digit's histogram, two passes over the stored
+   keys, the weighted sums over the stored winners, the step -- is enqueued at once on h's stream with one wait at its end.
+   Neither call changes h's cloud, plan or stored results, nor the mesh.
+   PPP_ERR_ARG: m or bp NULL; rows NULL with row_cap > 0; ppp_register's parameter ranges; tune NaN or <= 0 (+INFINITY is
+   allowed); sigma_min not finite or < 0; a T entry that is not finite; no cloud on h; a mesh on another device than h;
+   shift < 16.  PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+int  ppp_get_mesh_robust_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_robust_registration_params *bp, const double *T12,
+                                            ppp_robust_registration_row *row,
+                                            unsigned char *status, float *weight, double *residual, size_t cap,
+                                            ppp_registration_stats *stats);
+int  ppp_register_mesh_robust(ppp_handle h, ppp_trimesh m, const ppp_robust_registration_params *bp, const double *T0_12,
+                              ppp_robust_registration_row *rows, size_t row_cap,
+                              unsigned char *status, float *weight, double *residual, size_t cap,
+                              ppp_registration_stats *stats);
 /* T applied to the resident cloud: T12 (row-major 3 x 4, NULL: the identity) is rounded to float and every finite point
    becomes m0 x + (m1 y + (m2 z + m3)) per row, pcl::transformPointCloud's arithmetic; a point that is not finite passes
    unchanged.  The cloud has changed: bounds, plan, index and every stored result are withdrawn, as after ppp_trans2center.

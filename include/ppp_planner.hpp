@@ -705,6 +705,13 @@ public:
     {
         TriMesh mesh;
         ppp_registration_stats st = {};
+        const bool ran = open_mesh_for_registration(mesh, name) && register_mesh(mesh, st, rp);
+        if (!ran) st = ppp_registration_stats{};
+        return print_registration_lines(st, rp, ran, apply);
+    }
+    /* the STL file `name` as the triangles a registration runs against: its grid's line on stderr, or why it could not be had */
+    bool open_mesh_for_registration(TriMesh &mesh, const std::string &name)
+    {
         const int rc = mesh.open_stl(h_, name);
         if (rc == PPP_ERR_IO) std::fprintf(stderr, "Cloudn't read file!\n");
         else if (rc != PPP_OK) report(rc);
@@ -712,9 +719,7 @@ public:
             std::fprintf(stderr, "ppp: %s: %zu triangles (%zu degenerate) in %zu x %zu x %zu cells of %g: %zu pairs, %zu at most in a cell\n", name.c_str(),
                          mesh.stats().triangles, mesh.stats().degenerate, mesh.stats().cells[0], mesh.stats().cells[1], mesh.stats().cells[2],
                          (double)mesh.stats().cell, mesh.stats().pairs, mesh.stats().max_per_cell);
-        const bool ran = rc == PPP_OK && register_mesh(mesh, st, rp);
-        if (!ran) st = ppp_registration_stats{};
-        return print_registration_lines(st, rp, ran, apply);
+        return rc == PPP_OK;
     }
     /* print_registration()'s five lines on the statistics of a chain that ran (or did not), and its move of the cloud */
     bool print_registration_lines(const ppp_registration_stats &st, const ppp_registration_params &rp, bool ran, bool apply)
@@ -831,6 +836,13 @@ public:
         std::vector<ppp_robust_registration_row> rows;
         const bool ran = register_robust_to(ref, st, bp, nullptr, &rows);
         if (!ran) st = ppp_registration_stats{};
+        return print_robust_registration_lines(st, bp, rows, ran, apply);
+    }
+    /* the robust print_registration()'s six lines on the statistics and the rows of a chain that ran (or did not), and its move of
+       the cloud */
+    bool print_robust_registration_lines(const ppp_registration_stats &st, const ppp_robust_registration_params &bp,
+                                         const std::vector<ppp_robust_registration_row> &rows, bool ran, bool apply)
+    {
         const ppp_robust_registration_row none = {};
         const ppp_robust_registration_row &first = rows.empty() ? none : rows.front(), &last = rows.empty() ? none : rows.back();
         std::printf("registration: robust, tune %f: %zu of %zu pairs used, median %f mm, sigma %f mm; after %d steps %zu of %zu, median %f mm, sigma %f mm\n",
@@ -842,6 +854,46 @@ public:
                     st.converged ? "converged" : (ran && st.steps == bp.icp.iterations ? "out of iterations" : "no step possible"), st.locked);
         for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
         return ran && apply && st.converged && transform_cloud(st.T);
+    }
+    /* robust point-to-plane ICP to the triangles of mesh themselves (ppp_register_mesh_robust): register_mesh()'s
+       pairs -- the exact closest point, the facet's own normal -- under register_robust_to()'s weights, for a scan that shows a clamp
+       or a strip of the table within max_dist of the part.  st, T0, rows and the maps as register_robust_to()'s; the residual map is
+       signed by the facets' winding */
+    bool register_mesh_robust(const TriMesh &mesh, ppp_registration_stats &st, const ppp_robust_registration_params &bp, const double *T0 = nullptr,
+                              std::vector<ppp_robust_registration_row> *rows = nullptr, std::vector<unsigned char> *status = nullptr,
+                              std::vector<float> *weight = nullptr, std::vector<double> *residual = nullptr)
+    {
+        if (rows) rows->assign((size_t)(bp.icp.iterations > 0 ? bp.icp.iterations : 0) + 1, ppp_robust_registration_row{});
+        size_t n = 0;
+        if (status || weight || residual) {
+            int rc = ppp_num_points(h_, &n);
+            if (rc != PPP_OK) return report(rc);
+            if (status) status->assign(n, PPP_ROBUST_DROPPED);
+            if (weight) weight->assign(n, 0.f);
+            if (residual) residual->assign(n, 0.0);
+        }
+        int rc = ppp_register_mesh_robust(h_, mesh.get(), &bp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, status ? status->data() : nullptr,
+                                          weight ? weight->data() : nullptr, residual ? residual->data() : nullptr, n, &st);
+        if (rc != PPP_OK) {
+            if (rows) rows->clear();
+            if (status) status->clear();
+            if (weight) weight->clear();
+            if (residual) residual->clear();
+            return report(rc);
+        }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* print_mesh_registration() with the robust loop: the grid's line on stderr, register_mesh_robust() from the identity, the
+       robust print_registration()'s six lines and, with apply, the cloud moved */
+    bool print_mesh_robust_registration(const std::string &name, const ppp_robust_registration_params &bp, bool apply = true)
+    {
+        TriMesh mesh;
+        ppp_registration_stats st = {};
+        std::vector<ppp_robust_registration_row> rows;
+        const bool ran = open_mesh_for_registration(mesh, name) && register_mesh_robust(mesh, st, bp, nullptr, &rows);
+        if (!ran) st = ppp_registration_stats{};
+        return print_robust_registration_lines(st, bp, rows, ran, apply);
     }
     /* global registration of this planner's cloud, the scan, to the cloud of ref (ppp_register_global): the starts
        the two clouds' principal frames imply, a coarse chain from each side by side, the fine chain from the cheapest.  st.fine.T

@@ -76,6 +76,9 @@ public:
     /* register_to() with the robust loop (ppp_register_robust; tune from PPP_REGISTER_TUNE, sigma_min from PPP_REGISTER_SIGMA_MIN,
        4.685 and 1e-4 mm where they are not set): a line with the used / paired counts, the median and sigma, then register_to()'s */
     void register_robust_to(const RobotPath &ref) { planner.print_registration(ref.planner, ppp::Planner::robust_registration_params_env()); }
+    /* register_to_mesh() with the robust loop (ppp_register_mesh_robust): the facets' exact geometry under
+       register_robust_to()'s weights, tune and sigma_min from the same variables */
+    void register_robust_to_mesh(const std::string &stl) { planner.print_mesh_robust_registration(stl, ppp::Planner::robust_registration_params_env()); }
     void register_global_to(const RobotPath &ref) { planner.print_global_registration(ref.planner, ppp::Planner::global_registration_params_env()); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */

@@ -325,6 +325,9 @@ struct ppp_handle_s {
         /* ppp_register_robust: with partner, key, hist, cuts, tstatus and td2 (the weight map) above, per query in slab order
            the residual of its pair, per evaluation sigma, and the residual map by cloud index */
         DevBuf<double> rres, rsigma, rresid;
+        /* ppp_register_mesh_robust: with key, hist, cuts, the maps and the three above, per query in slab order the winning
+           record of its pair (key holds the residual's key there, so the record needs room of its own) */
+        DevBuf<unsigned> mwin;
         /* ppp_get_registration_terms_tile, ppp_register_tiles: the frame the tile's kernel reads, and pinned host memory for
            the transform on its way to the device and the words on their way back */
         DevBuf<IcpFrame> tframe;

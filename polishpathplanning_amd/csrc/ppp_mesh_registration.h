@@ -6,6 +6,8 @@
  * doubles) -- as two launches, k_mesh_reg_search and k_mesh_reg_sum, or as the fused k_mesh_reg_terms (MESH_REG_SPLIT).  The step
  * is k_reg_step, unchanged; the host's chain has registration_chain's shape.  Nothing here estimates a normal or knows a pitch:
  * the fit is taken on the facets that ppp_get_mesh_deviation measures against.
+ * Robust weights on these pairs are ppp_mesh_robust.h's; trimmed weights, tiles, a global start from the mesh,
+ * pseudonormals and border rejection are not offered.
  * The facet's orientation is not applied: n -> -n flips J and r together, so every product J_i J_k, J_i r, r r is the same
  * double either way, and so is every word.
  */

@@ -23,6 +23,7 @@
 #include "ppp_robust_tile.h"
 #include "ppp_trimesh.h"
 #include "ppp_mesh_registration.h"
+#include "ppp_mesh_robust.h"
 #include "ppp_sort.h"
 #include <cstring>
 
@@ -453,71 +454,40 @@ void ppp_default_robust_registration_params(ppp_robust_registration_params *bp)
     bp->tune = 4.685; bp->sigma_min = 1e-4;
 }
 
-/* The robust chain (DESIGN.md §7q): registration_chain's shape -- the reference's index and normal field on its own stream, one
-   wait for that stream, then iterations + 1 evaluations and iterations steps back to back on the scan's stream, and one wait --
-   in which an evaluation is k_rob_pair, k_trim_narrow<1>, k_trim_narrow<2> at keep 0.5 and k_rob_terms, its ROB_WORDS words
-   the weighted sums with `used` in word 0, which is what k_reg_step reads as its pairs; k_rob_scatter follows the chain.
-   !loop: the one evaluation of ppp_get_robust_registration_terms. */
-static int robust_chain(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T0, bool loop,
-                        ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
-                        ppp_registration_stats *stats)
+/* What ppp_register_robust's chain and ppp_register_mesh_robust's have in common on either side of their launches, as chain_open
+   and chain_collect are for the unweighted pair.  robust_open: room for `evals` evaluations of ROB_WORDS words, their histograms,
+   cuts and sigmas, the per-query keys and residuals and the three maps in h->registration's buffers; the words, the control
+   block, the histograms, the cuts and the sigmas cleared on h's stream (every evaluation has histograms of its own: one clear
+   before the chain, none between iterations); T at the chain's head; k_rob_fill over the maps.  robust_collect: the one wait, the
+   sanity checks (w: the call's name), then the rows, the statistics and the maps as ppp_register_robust hands them out. */
+static int robust_open(ppp_handle h, size_t evals, int nq, const double *T)
 {
-    if (!h) return PPP_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!ref || !bp) return fail(h, PPP_ERR_ARG, "robust registration: no reference handle or no parameters");
-    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "robust registration: rows is NULL with row_cap > 0");
-    if (!(bp->tune > 0.0)) return fail(h, PPP_ERR_ARG, "robust registration: tune must be > 0 (+INFINITY: every weight is 1)");
-    if (!(bp->sigma_min >= 0.0 && std::isfinite(bp->sigma_min))) return fail(h, PPP_ERR_ARG, "robust registration: sigma_min must be finite and >= 0");
-    const ppp_registration_params P = bp->icp;
-    const RobScale S = {bp->tune, bp->sigma_min};
-    IcpFrame F;
-    int rc = registration_params_ok(h, P, F);
-    if (rc) return rc;
-    const int iterations = loop ? P.iterations : 0;
-    double T[12];
-    rc = opening_transform(h, "robust registration", T0, T);
-    if (rc) return rc;
-    int shift = 0;
-    rc = registration_setup(h, ref, P, F, shift);
-    if (rc) return rc;
-    const size_t N = h->n, N1 = std::max<size_t>(N, 1);
-    const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
-    const size_t nq1 = std::max<size_t>((size_t)std::max(nq, 0), 1);
     auto &G = h->registration;
-    const size_t evals = (size_t)iterations + 1;
+    const size_t N1 = std::max<size_t>(h->n, 1), nq1 = std::max<size_t>((size_t)std::max(nq, 0), 1);
     static_assert(sizeof(TrimCut) == 8 * sizeof(unsigned), "TrimCut is eight words");
     HIPCHK(h, G.T.ensure(12 * evals)); HIPCHK(h, G.acc.ensure(ROB_WORDS * evals)); HIPCHK(h, G.rows.ensure(evals)); HIPCHK(h, G.ctl.ensure(8));
-    HIPCHK(h, G.partner.ensure(nq1)); HIPCHK(h, G.key.ensure(nq1)); HIPCHK(h, G.rres.ensure(nq1));
+    HIPCHK(h, G.key.ensure(nq1)); HIPCHK(h, G.rres.ensure(nq1));
     HIPCHK(h, G.hist.ensure(TRIM_WORDS * evals)); HIPCHK(h, G.cuts.ensure(8 * evals)); HIPCHK(h, G.rsigma.ensure(evals));
     HIPCHK(h, G.tstatus.ensure(N1)); HIPCHK(h, G.td2.ensure(N1)); HIPCHK(h, G.rresid.ensure(N1));
-    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
-    TrimCut *cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
     HIPCHK(h, hipMemsetAsync(G.acc.p, 0, ROB_WORDS * evals * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(G.ctl.p, 0, 8 * sizeof(int), h->stream));
-    /* every evaluation has histograms of its own: one clear on the stream before the chain, none between iterations */
     HIPCHK(h, hipMemsetAsync(G.hist.p, 0, TRIM_WORDS * evals * sizeof(unsigned), h->stream));
     HIPCHK(h, hipMemsetAsync(G.cuts.p, 0, 8 * evals * sizeof(unsigned), h->stream));
     HIPCHK(h, hipMemsetAsync(G.rsigma.p, 0, evals * sizeof(double), h->stream));
-    HIPCHK(h, copy_sync(h, G.T.p, T, sizeof(T), hipMemcpyHostToDevice));
-    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus));
+    HIPCHK(h, copy_sync(h, G.T.p, T, 12 * sizeof(double), hipMemcpyHostToDevice));
     LAUNCH(h, "k_rob_fill", k_rob_fill, (unsigned)std::min<size_t>((N1 + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus), TRIM_T, 0, (int)N1, G.tstatus.p,
            G.td2.p, G.rresid.p); /* points outside the index: not finite */
-    for (int k = 0; k <= iterations; ++k) {
-        unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
-        unsigned long long *acc = G.acc.p + ROB_WORDS * (size_t)k;
-        LAUNCH(h, "k_rob_pair", k_rob_pair, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
-               G.rres.p, G.key.p, hist);
-        LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, ROB_KEEP, cuts + k);
-        LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, ROB_KEEP, cuts + k);
-        LAUNCH(h, "k_rob_terms", k_rob_terms, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), F, S, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
-               G.rres.p, G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.rsigma.p + k, acc);
-        if (k < iterations) LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, acc, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
-    }
-    LAUNCH(h, "k_rob_scatter", k_rob_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, G.rres.p, ctl, cuts, G.rsigma.p, S, (int)evals, (int)N1,
-           G.tstatus.p, G.td2.p, G.rresid.p);
+    return PPP_OK;
+}
+
+static int robust_collect(ppp_handle h, const char *w, int iterations, int nq, int shift, const IcpFrame &F, ppp_robust_registration_row *rows,
+                          size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap, ppp_registration_stats *stats)
+{
+    auto &G = h->registration;
+    const size_t N = h->n;
     IcpCtl C;
     HIPCHK(h, copy_sync(h, &C, G.ctl.p, sizeof(C), hipMemcpyDeviceToHost)); /* the one wait */
-    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, "robust registration: control words corrupt");
+    if (!chain_ctl_ok(C, iterations)) return fail(h, PPP_ERR_HIP, std::string(w) + ": control words corrupt");
     const size_t last = (size_t)C.steps;
     std::vector<ppp_registration_row> R(last + 1);
     std::vector<unsigned long long> acc(ROB_WORDS * (last + 1));
@@ -534,15 +504,15 @@ static int robust_chain(ppp_handle h, ppp_handle ref, const ppp_robust_registrat
     }
     std::vector<ppp_robust_registration_row> out(last + 1);
     for (size_t i = 0; i <= last; ++i) {
-        const unsigned long long *w = acc.data() + ROB_WORDS * i;
-        if (cut[i].paired > (unsigned)std::max(nq, 0) || w[ROB_USED] > cut[i].paired || R[i].pairs != (size_t)w[ROB_USED])
-            return fail(h, PPP_ERR_HIP, "robust registration: sums corrupt");
+        const unsigned long long *a = acc.data() + ROB_WORDS * i;
+        if (cut[i].paired > (unsigned)std::max(nq, 0) || a[ROB_USED] > cut[i].paired || R[i].pairs != (size_t)a[ROB_USED])
+            return fail(h, PPP_ERR_HIP, std::string(w) + ": sums corrupt");
         ppp_robust_registration_row &o = out[i];
         memset(&o, 0, sizeof(o)); /* the padding too: rows compare as bytes */
         o.row = R[i];
         o.row.pairs = cut[i].paired; /* the step kernel read `used` there */
-        o.used = (size_t)w[ROB_USED];
-        o.weight_sum = (long long)w[ROB_WSUM];
+        o.used = (size_t)a[ROB_USED];
+        o.weight_sum = (long long)a[ROB_WSUM];
         memcpy(&o.median_abs, &cut[i].tau, sizeof(float));
         o.sigma = sigma[i];
         R[i].pairs = cut[i].paired;
@@ -559,6 +529,66 @@ static int robust_chain(ppp_handle h, ppp_handle ref, const ppp_robust_registrat
     if (weight && m) HIPCHK(h, copy_sync(h, weight, G.td2.p, m * sizeof(float), hipMemcpyDeviceToHost));
     if (residual && m) HIPCHK(h, copy_sync(h, residual, G.rresid.p, m * sizeof(double), hipMemcpyDeviceToHost));
     return PPP_OK;
+}
+
+/* the two parameters a robust chain has beside ppp_register's, checked (w: the call's name) */
+static int robust_params_ok(ppp_handle h, const char *w, const ppp_robust_registration_params *bp)
+{
+    if (!(bp->tune > 0.0)) return fail(h, PPP_ERR_ARG, std::string(w) + ": tune must be > 0 (+INFINITY: every weight is 1)");
+    if (!(bp->sigma_min >= 0.0 && std::isfinite(bp->sigma_min))) return fail(h, PPP_ERR_ARG, std::string(w) + ": sigma_min must be finite and >= 0");
+    return PPP_OK;
+}
+
+/* The robust chain (DESIGN.md §7q): registration_chain's shape -- the reference's index and normal field on its own stream, one
+   wait for that stream, then iterations + 1 evaluations and iterations steps back to back on the scan's stream, and one wait --
+   in which an evaluation is k_rob_pair, k_trim_narrow<1>, k_trim_narrow<2> at keep 0.5 and k_rob_terms, its ROB_WORDS words
+   the weighted sums with `used` in word 0, which is what k_reg_step reads as its pairs; k_rob_scatter follows the chain.
+   !loop: the one evaluation of ppp_get_robust_registration_terms. */
+static int robust_chain(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T0, bool loop,
+                        ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
+                        ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!ref || !bp) return fail(h, PPP_ERR_ARG, "robust registration: no reference handle or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "robust registration: rows is NULL with row_cap > 0");
+    int rc = robust_params_ok(h, "robust registration", bp);
+    if (rc) return rc;
+    const ppp_registration_params P = bp->icp;
+    const RobScale S = {bp->tune, bp->sigma_min};
+    IcpFrame F;
+    rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, "robust registration", T0, T);
+    if (rc) return rc;
+    int shift = 0;
+    rc = registration_setup(h, ref, P, F, shift);
+    if (rc) return rc;
+    const int nq = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    HIPCHK(h, G.partner.ensure(std::max<size_t>((size_t)std::max(nq, 0), 1)));
+    rc = robust_open(h, evals, nq, T);
+    if (rc) return rc;
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    TrimCut *cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)nq + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus));
+    for (int k = 0; k <= iterations; ++k) {
+        unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+        unsigned long long *acc = G.acc.p + ROB_WORDS * (size_t)k;
+        LAUNCH(h, "k_rob_pair", k_rob_pair, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), nref, F, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+               G.rres.p, G.key.p, hist);
+        LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_rob_terms", k_rob_terms, grid, TRIM_T, 0, h->sorted4.p, nq, contact_index(ref), F, S, G.T.p + 12 * (size_t)k, ctl, G.partner.p,
+               G.rres.p, G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.rsigma.p + k, acc);
+        if (k < iterations) LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, acc, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    LAUNCH(h, "k_rob_scatter", k_rob_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, G.rres.p, ctl, cuts, G.rsigma.p, S, (int)evals,
+           (int)std::max<size_t>(h->n, 1), G.tstatus.p, G.td2.p, G.rresid.p);
+    return robust_collect(h, "robust registration", iterations, nq, shift, F, rows, row_cap, status, weight, residual, cap, stats);
 }
 
 int ppp_get_robust_registration_terms(ppp_handle h, ppp_handle ref, const ppp_robust_registration_params *bp, const double *T12,
@@ -1968,6 +1998,86 @@ int ppp_register_mesh(ppp_handle h, ppp_trimesh m, const ppp_registration_params
                       ppp_registration_stats *stats)
 {
     return mesh_registration_chain(h, m, rp, T0_12, true, rows, row_cap, stats);
+}
+
+/* The robust mesh chain: mesh_registration_chain's setup -- the scan's slab index, the frame from the mesh's box,
+   ppp_register's shift -- and robust_chain's shape on it: robust_open, then iterations + 1 evaluations (k_mesh_rob_pair, the walk
+   paid once; k_mesh_rob_digit0, unless the walk counts the digit itself: MESH_ROB_DIGIT_PASS; k_trim_narrow<1> and <2> at keep 0.5; k_mesh_rob_terms) and
+   iterations steps (k_reg_step on the 30 words: `used` is word 0) back to back on the scan's stream, k_rob_scatter, and
+   robust_collect's one wait.  !loop: the one evaluation of ppp_get_mesh_robust_registration_terms. */
+static int mesh_robust_chain(ppp_handle h, ppp_trimesh m, const ppp_robust_registration_params *bp, const double *T0, bool loop,
+                             ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
+                             ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!m || !bp) return fail(h, PPP_ERR_ARG, "robust mesh registration: no mesh or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "robust mesh registration: rows is NULL with row_cap > 0");
+    int rc = robust_params_ok(h, "robust mesh registration", bp);
+    if (rc) return rc;
+    const ppp_registration_params P = bp->icp;
+    const RobScale S = {bp->tune, bp->sigma_min};
+    IcpFrame F;
+    rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, "robust mesh registration", T0, T);
+    if (rc) return rc;
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "robust mesh registration: the mesh is on another device than the handle");
+    rc = deviation_side(h, h, "the scan", "robust mesh registration");
+    if (rc) return rc;
+    const int shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "robust mesh registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    const TriGrid &M = m->G;
+    const float mn[3] = {(float)M.mn[0], (float)M.mn[1], (float)M.mn[2]}, mx[3] = {(float)M.mx[0], (float)M.mx[1], (float)M.mx[2]}; /* (floats, widened: exact) */
+    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    const double md2 = (double)P.max_dist * (double)P.max_dist;
+    const int nq = h->hmeta.n_sorted;
+    const size_t nqs = (size_t)std::max(nq, 0);
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    HIPCHK(h, G.mwin.ensure(std::max<size_t>(nqs, 1)));
+    rc = robust_open(h, evals, nq, T);
+    if (rc) return rc;
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    TrimCut *cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+    const unsigned gpair = (unsigned)std::max<size_t>(1, (nqs + TM_T - 1) / TM_T); /* a thread per query */
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nqs + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus));
+    /* grid-stride under MESH_ROB_GRID_CUS workgroups per compute unit (0: a thread per query); the words do not depend on it */
+    const size_t tcap = MESH_ROB_GRID_CUS ? (size_t)MESH_ROB_GRID_CUS * (size_t)h->num_cus : (size_t)0x7fffffff;
+    const unsigned gterms = (unsigned)std::max<size_t>(1, std::min<size_t>((nqs + TRIM_T - 1) / TRIM_T, tcap));
+    for (int k = 0; k <= iterations; ++k) {
+        unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+        unsigned long long *acc = G.acc.p + ROB_WORDS * (size_t)k;
+        LAUNCH(h, "k_mesh_rob_pair", k_mesh_rob_pair, gpair, TM_T, 0, (const float4 *)h->sorted4.p, nq, M, md2, G.T.p + 12 * (size_t)k, ctl, G.mwin.p,
+               G.rres.p, G.key.p, hist);
+#if MESH_ROB_DIGIT_PASS
+        LAUNCH(h, "k_mesh_rob_digit0", k_mesh_rob_digit0, grid, TRIM_T, 0, G.key.p, nq, ctl, hist);
+#endif
+        LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, ROB_KEEP, cuts + k);
+        LAUNCH(h, "k_mesh_rob_terms", k_mesh_rob_terms, gterms, TRIM_T, 0, (const float4 *)h->sorted4.p, nq, M, F, S, G.T.p + 12 * (size_t)k, ctl, G.mwin.p,
+               G.rres.p, G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k, G.rsigma.p + k, acc);
+        if (k < iterations) LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, acc, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    LAUNCH(h, "k_rob_scatter", k_rob_scatter, grid, TRIM_T, 0, h->sorted4.p, nq, G.key.p, G.rres.p, ctl, cuts, G.rsigma.p, S, (int)evals,
+           (int)std::max<size_t>(h->n, 1), G.tstatus.p, G.td2.p, G.rresid.p);
+    return robust_collect(h, "robust mesh registration", iterations, nq, shift, F, rows, row_cap, status, weight, residual, cap, stats);
+}
+
+int ppp_get_mesh_robust_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_robust_registration_params *bp, const double *T12,
+                                           ppp_robust_registration_row *row, unsigned char *status, float *weight, double *residual, size_t cap,
+                                           ppp_registration_stats *stats)
+{
+    return mesh_robust_chain(h, m, bp, T12, false, row, row ? 1 : 0, status, weight, residual, cap, stats);
+}
+
+int ppp_register_mesh_robust(ppp_handle h, ppp_trimesh m, const ppp_robust_registration_params *bp, const double *T0_12,
+                             ppp_robust_registration_row *rows, size_t row_cap, unsigned char *status, float *weight, double *residual, size_t cap,
+                             ppp_registration_stats *stats)
+{
+    return mesh_robust_chain(h, m, bp, T0_12, true, rows, row_cap, status, weight, residual, cap, stats);
 }
 
 } // extern "C"

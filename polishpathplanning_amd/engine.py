@@ -82,7 +82,7 @@ EXPORTS = [
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
     "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
-    "ppp_get_mesh_registration_terms", "ppp_register_mesh",
+    "ppp_get_mesh_registration_terms", "ppp_register_mesh", "ppp_get_mesh_robust_registration_terms", "ppp_register_mesh_robust",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -196,6 +196,8 @@ def lib():
                                                         fp, dp, sz, C.POINTER(RegistrationStats)]
         L.ppp_register_robust.argtypes = [vp, vp, C.POINTER(RobustRegistrationParams), dp, C.POINTER(RobustRegistrationRow), sz, C.POINTER(C.c_ubyte), fp, dp,
                                           sz, C.POINTER(RegistrationStats)]
+        L.ppp_get_mesh_robust_registration_terms.argtypes = L.ppp_get_robust_registration_terms.argtypes
+        L.ppp_register_mesh_robust.argtypes = L.ppp_register_robust.argtypes
         L.ppp_trim_select.argtypes = [C.POINTER(C.c_uint), sz, sz, C.POINTER(C.c_uint), C.POINTER(sz)]
         L.ppp_trim_rank.argtypes = [C.c_double, sz]
         L.ppp_trim_rank.restype = sz
@@ -1899,21 +1901,42 @@ class Engine:
         n = nn.value
         return n, np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float64)
 
-    def robust_registration_terms(self, ref, T=None, tune=4.685, sigma_min=1e-4, max_dist=2.0, lock_eps=1e-9, maps=True):
-        """(row, status uint8[n], weight float32[n], residual float64[n], stats) of one evaluation of register_robust()'s weighted
-        terms at T (3 x 4, None: the identity) against the cloud of the engine `ref` (ppp_get_robust_registration_terms): no step
-        is taken; row and the maps as register_robust() gives them.  maps=False returns None for the three maps"""
+    def _robust_terms(self, call, against, T, tune, sigma_min, max_dist, lock_eps, maps):
+        """one evaluation by `call` (ppp_get_robust_registration_terms or its mesh form) against the handle `against`"""
         bp = RobustRegistrationParams(RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps)), float(tune), float(sigma_min))
         row, st = RobustRegistrationRow(), RegistrationStats()
         t = _t12(T)
         n, status, weight, residual = self._robust_maps(maps)
-        self._chk(self.L.ppp_get_robust_registration_terms(self.h, ref.h, C.byref(bp), None if t is None else _d(t), C.byref(row),
-                                                           None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                                           None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
-                                                           None if residual is None else _d(residual), n, C.byref(st)))
+        self._chk(call(self.h, against, C.byref(bp), None if t is None else _d(t), C.byref(row),
+                       None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                       None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
+                       None if residual is None else _d(residual), n, C.byref(st)))
         if maps:
             status, weight, residual = status[:n], weight[:n], residual[:n]
         return _robust_registration_row(row), status, weight, residual, _registration_stats(st)
+
+    def _robust_loop(self, call, against, tune, sigma_min, max_dist, iterations, min_step, lock_eps, T0, maps):
+        """the loop by `call` (ppp_register_robust or its mesh form) against the handle `against`"""
+        bp = RobustRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(tune), float(sigma_min))
+        cap = max(int(iterations), 0) + 1
+        rows = (RobustRegistrationRow * cap)()
+        st = RegistrationStats()
+        t = _t12(T0)
+        n, status, weight, residual = self._robust_maps(maps)
+        self._chk(call(self.h, against, C.byref(bp), None if t is None else _d(t), rows, cap,
+                       None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                       None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
+                       None if residual is None else _d(residual), n, C.byref(st)))
+        stats = _registration_stats(st)
+        if maps:
+            status, weight, residual = status[:n], weight[:n], residual[:n]
+        return stats["T"].copy(), [_robust_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, weight, residual, stats
+
+    def robust_registration_terms(self, ref, T=None, tune=4.685, sigma_min=1e-4, max_dist=2.0, lock_eps=1e-9, maps=True):
+        """(row, status uint8[n], weight float32[n], residual float64[n], stats) of one evaluation of register_robust()'s weighted
+        terms at T (3 x 4, None: the identity) against the cloud of the engine `ref` (ppp_get_robust_registration_terms): no step
+        is taken; row and the maps as register_robust() gives them.  maps=False returns None for the three maps"""
+        return self._robust_terms(self.L.ppp_get_robust_registration_terms, ref.h, T, tune, sigma_min, max_dist, lock_eps, maps)
 
     def register_robust(self, ref, tune=4.685, sigma_min=1e-4, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
         """(T float64[3, 4], rows, status uint8[n], weight float32[n], residual float64[n], stats): robust point-to-plane ICP
@@ -1926,20 +1949,22 @@ class Engine:
         weighted rms.  tune = inf is register() bit for bit.  It needs the median residual to lie on the part that shows the
         reference: with a third of the scan off it does not recover the motion (register_trimmed with a known keep does).
         maps=False returns None for the three maps"""
-        bp = RobustRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)), float(tune), float(sigma_min))
-        cap = max(int(iterations), 0) + 1
-        rows = (RobustRegistrationRow * cap)()
-        st = RegistrationStats()
-        t = _t12(T0)
-        n, status, weight, residual = self._robust_maps(maps)
-        self._chk(self.L.ppp_register_robust(self.h, ref.h, C.byref(bp), None if t is None else _d(t), rows, cap,
-                                             None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                             None if weight is None else weight.ctypes.data_as(C.POINTER(C.c_float)),
-                                             None if residual is None else _d(residual), n, C.byref(st)))
-        stats = _registration_stats(st)
-        if maps:
-            status, weight, residual = status[:n], weight[:n], residual[:n]
-        return stats["T"].copy(), [_robust_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, weight, residual, stats
+        return self._robust_loop(self.L.ppp_register_robust, ref.h, tune, sigma_min, max_dist, iterations, min_step, lock_eps, T0, maps)
+
+    def mesh_robust_registration_terms(self, mesh, T=None, tune=4.685, sigma_min=1e-4, max_dist=2.0, lock_eps=1e-9, maps=True):
+        """robust_registration_terms() against the triangles of the TriMesh `mesh` (ppp_get_mesh_robust_registration_terms): one
+        evaluation of register_mesh_robust()'s weighted terms at T, no step; the same five results"""
+        m = mesh.m if mesh is not None else None
+        return self._robust_terms(self.L.ppp_get_mesh_robust_registration_terms, m, T, tune, sigma_min, max_dist, lock_eps, maps)
+
+    def register_mesh_robust(self, mesh, tune=4.685, sigma_min=1e-4, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, maps=True):
+        """(T, rows, status, weight, residual, stats) as register_robust() gives them, against the triangles of the TriMesh `mesh`
+        themselves (ppp_register_mesh_robust): register_mesh()'s pairs -- the moved point in double, the exact closest point of its
+        nearest triangle, that facet's own normal -- under register_robust()'s weights, for a scan that shows a clamp or a strip of
+        the table within max_dist of the part.  tune = inf is register_mesh() bit for bit.  A mesh of either orientation gives the
+        same rows; the residual map is signed by the facets' winding.  Neither the cloud nor the mesh is changed"""
+        m = mesh.m if mesh is not None else None
+        return self._robust_loop(self.L.ppp_register_mesh_robust, m, tune, sigma_min, max_dist, iterations, min_step, lock_eps, T0, maps)
 
     register_trimmed_tiles = staticmethod(register_trimmed_tiles)   # Engine.register_trimmed_tiles(engines, refs, ...): the module's function
     register_robust_tiles = staticmethod(register_robust_tiles)     # Engine.register_robust_tiles(engines, refs, ...) likewise
