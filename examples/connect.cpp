@@ -14,7 +14,8 @@
 // A name that ends in .stl (any case) is a triangle mesh, the nominal part as a CAD export: its surface is sampled on the device into the cloud (PPP_MESH_PITCH, default 0.5 mm; PPP_MESH_FACING=front keeps
 // the triangles that face the origin).  PPP_DEVIATION=<reference.stl> ./connect scan.pcd measures (and with PPP_REGISTER registers) the scan against the mesh; ./connect part.stl plans on the nominal itself.
 // PPP_DEVIATION=<reference.stl> PPP_DEVIATION_EXACT=1 measures against the triangles themselves (ppp_get_mesh_deviation: the closest point on the nearest triangle, along that facet's normal; no pitch):
-// the same block, plus the closest points by region; PPP_TRIMESH_CELL sets the grid's cell (0 = automatic; the numbers do not depend on it), PPP_TRIMESH_ORIENT=viewpoint turns every facet normal to the origin's side.
+// the same block, plus the closest points by region; PPP_DEVIATION_EXACT=signed takes the signed distance instead (ppp_get_mesh_signed_deviation: the sign of the angle-weighted pseudonormal of the feature
+// the closest point lies on): the topology's counts first, a warning line when the mesh is not closed, and the points by sign and flag behind the block; PPP_TRIMESH_CELL sets the grid's cell (0 = automatic; the numbers do not depend on it), PPP_TRIMESH_ORIENT=viewpoint turns every facet normal to the origin's side.
 // PPP_REGISTER=mesh PPP_DEVIATION=<reference.stl> registers against the triangles themselves (ppp_register_mesh: the exact closest point, the facet's own normal; no pitch, no estimated normal):
 // ppp_register's lines, and the cloud moved by T; PPP_REGISTER=1 with an STL still registers against its samples.
 // PPP_REGISTER=mesh-robust PPP_DEVIATION=<part.stl> does so under the robust loop's weights (ppp_register_mesh_robust; PPP_REGISTER_TUNE, _SIGMA_MIN): for a scan that shows a
@@ -61,7 +62,8 @@ int main(int argc, char **argv)
     const char *rem = std::getenv("PPP_PATH_REMOVAL");
     if (rem && rem[0] == '1') path_planner.get_path_removal();
     const char *exact = std::getenv("PPP_DEVIATION_EXACT");
-    if (reference && exact && exact[0] == '1' && ppp::Planner::is_stl_name(devf)) path_planner.get_mesh_deviation(devf); /* against the triangles */
+    if (reference && exact && !std::strcmp(exact, "signed") && ppp::Planner::is_stl_name(devf)) path_planner.get_mesh_signed_deviation(devf); /* ... with the pseudonormals' sign */
+    else if (reference && exact && exact[0] == '1' && ppp::Planner::is_stl_name(devf)) path_planner.get_mesh_deviation(devf); /* against the triangles */
     else if (reference) path_planner.get_deviation(*reference); /* before the schedules: they take its target */
     const char *dwl = std::getenv("PPP_PATH_DWELL");
     if (dwl && dwl[0] == '1') path_planner.get_path_dwell();

@@ -132,6 +132,9 @@ public:
     /* get_deviation() against the triangles of the STL file `stl` themselves (ppp_get_mesh_deviation; PPP_TRIMESH_CELL,
        PPP_TRIMESH_ORIENT=viewpoint): the same lines, and the closest points by region */
     void get_mesh_deviation(const std::string &stl) { planner.print_mesh_deviation(stl, ppp::Planner::deviation_params_env(), &deviation_target); }
+    /* get_mesh_deviation() with the signed distance (ppp_get_mesh_signed_deviation): the topology's counts, a warning where the
+       mesh is not closed, the same lines from the signed distance, and the points by sign and flag */
+    void get_mesh_signed_deviation(const std::string &stl) { planner.print_mesh_deviation(stl, ppp::Planner::deviation_params_env(), &deviation_target, true); }
     /* this planner's cloud, the scan, registered to the cloud of ref by point-to-plane ICP from the identity (ppp_register;
        max_dist, iterations and min_step from PPP_REGISTER_MAXDIST, _ITERATIONS, _MINSTEP): prints the pairs and the rms before
        and after, the steps, the locked unknowns and T, and moves the cloud by T when the loop converged (ppp_transform_cloud:

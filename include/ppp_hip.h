@@ -537,7 +537,7 @@ int  ppp_get_deviation(ppp_handle h, ppp_handle ref, const ppp_deviation_params 
                 deviation = ((ex nx) + ey ny) + ez nz with f*'s facet normal n.  In the face region the deviation is the signed
                 distance; on an edge or a vertex it is the component along the winning facet's normal -- 7j's convention, "along
                 the normal of the nearest reference element" --, and distance and region say which case applies.  Pseudonormals
-                and inside / outside of closed meshes are out of scope.
+                and inside / outside of closed meshes: ppp_trimesh_signed_nearest, below.
      otherwise  tri_index -1, region 255, every double the one quiet NaN of the deviation maps.
    Minima over (D2, f) have no order: the maps are the same bits in every run and for every cell.
    ppp_trimesh_nearest: the primitive.  n packed xyz points in RESIDENT units (no x1000) against the mesh, on the mesh's own
@@ -569,6 +569,76 @@ int  ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_par
                             double *deviation, double *smoothed, double *distance, int *tri_index,
                             unsigned char *region, unsigned char *status, double *target, size_t cap,
                             ppp_mesh_deviation_stats *stats);
+/* Signed distance to a triangle mesh: welded topology, angle-weighted pseudonormals (Baerentzen and Aanaes), and the sign they
+   give the exact search's distance.  ppp_trimesh_nearest and ppp_get_mesh_deviation are untouched; these are
+   calls beside them.
+   The topology is built once per mesh, on the mesh's stream, in the mesh's own buffers (freed by ppp_trimesh_destroy):
+   explicitly by ppp_trimesh_topology, or by the first of the other three calls that needs it.  Only indexed triangles take
+   part.  All arithmetic is in double on resident floats widened to double, one rounding per written operation;
+   dot(u, v) = (ux vx + uy vy) + uz vz, cross(u, v) = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx), |u| = sqrt(dot(u, u)).
+     corner     corner k (0, 1, 2: the caller's corner order) of triangle f (the caller's list) has the corner index 3 f + k.
+     weld       two corners are one vertex when their resident floats compare equal on all three axes (-0 equals +0; no
+                tolerance).  The vertex id is the smallest corner index at that position.
+     half-edge  half-edge k of f runs from corner k to corner (k + 1) % 3; where PPP_TRIMESH_VIEWPOINT negated f's normal it
+                runs the other way.  An edge is the unordered pair of vertex ids; its id is the smallest 3 f + k among its
+                half-edges.
+     class      PPP_EDGE_BORDER: one half-edge; PPP_EDGE_MANIFOLD: two that run in opposite directions;
+                PPP_EDGE_INCONSISTENT: two that run the same way; PPP_EDGE_NONMANIFOLD: more than two.
+     vertex bits  PPP_VERTEX_BORDER: on a border edge; PPP_VERTEX_IRREGULAR: on an inconsistent or a non-manifold edge.
+     n_f        f's facet normal exactly as the search forms it (N / A2 of the rotated frame, negated by the orient rule).
+     edge pseudonormal    s = (0, 0, 0); for its half-edges in ascending 3 f + k: s = s + n_f, per component.
+     vertex pseudonormal  s = (0, 0, 0); for its corners in ascending 3 f + k: s = s + alpha n_f, per component, with
+                alpha = atan2(|cross(u, v)|, dot(u, v)), u = corner (k + 1) % 3 - corner k, v = corner (k + 2) % 3 - corner k.
+                Both are left unnormalised: only the sign of a product with them is used.
+   Every sum has a fixed order: the values are the same bits in every run and for every cell.
+   ppp_trimesh_topology_stats: the counts of vertices, edges, edges by class, border and irregular vertices; closed = 1 when
+   there is no border, inconsistent or non-manifold edge -- ONLY THEN does the sign below mean inside (negative) / outside of
+   a solid whose facets are wound counter-clockwise seen from outside.
+   ppp_trimesh_get_topology: per triangle and corner of the caller's list, the first min(cap, n_tris) triangles, [cap][3] each:
+   vertex_id and edge_id (of half-edge k) as corner indices, edge_class, vertex_bits, and [cap][3][3] the vertex's and the edge's
+   pseudonormal.  A degenerate triangle's rows are -1, 255 and NaN.  Every output may be NULL; stats too.
+   PPP_ERR_ARG (both): m NULL.
+
+   The signed query.  Behind the search (k_mesh_nearest, unchanged) one more launch, a thread per query: for a MATCHED query it
+   walks the winner f* again (the same inputs and arithmetic: the same x, D2 and region) and notes the feature x lies on;
+     g          face: n_f*; edge: that edge's pseudonormal; vertex: that vertex's pseudonormal;
+     s          dot(e, g), e = p - x;
+     signed_distance  copysign(distance, s) when s > 0 or s < 0 and g is not the zero vector; otherwise copysign(distance,
+                deviation) -- the search's deviation, a +0 counts as positive -- and PPP_MESH_SIGN_FALLBACK is set (a query on
+                the mesh itself, an edge whose facets cancel);
+     feature    0 .. 2: the caller's corner x is; 3 + k: x lies on the caller's half-edge k; 6: in the face;
+     flags      PPP_MESH_SIGN_BORDER: x is on a border edge or a border vertex; PPP_MESH_SIGN_IRREGULAR: on an inconsistent or
+                non-manifold edge, or an irregular vertex; PPP_MESH_SIGN_FALLBACK: as above;
+     pseudonormal  g, three doubles.
+   A query that is not matched gets NaN, feature 255, flags 0.
+   ppp_trimesh_signed_nearest: ppp_trimesh_nearest with the four maps in front; its own six outputs are that call's bits.  Every
+   output may be NULL.  PPP_ERR_ARG: m NULL, xyz NULL with n > 0, max_dist not > 0.
+   ppp_get_mesh_signed_deviation: ppp_get_mesh_deviation word for word with signed_distance in the place of deviation: the sign
+   launch rewrites the deviation map and its fixed-point term before the tail runs, so smoothed, target and every field of
+   stats->mesh.dev are computed from the signed distance; distance, tri_index, region, status, on_face / on_edge / on_vertex
+   and max_distance are ppp_get_mesh_deviation's.  feature and flags as above (255 and 0 where not matched).  Of the matched
+   points: on_border, irregular and fallback count the flags, negative those with signed_distance < 0, positive those > 0.
+   Cap semantics and refusals are ppp_get_mesh_deviation's: PPP_ERR_ARG: m or dp NULL, ppp_get_deviation's conditions on dp, no
+   cloud, a mesh on another device than h; PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+enum { PPP_EDGE_BORDER = 0, PPP_EDGE_MANIFOLD = 1, PPP_EDGE_INCONSISTENT = 2, PPP_EDGE_NONMANIFOLD = 3 };
+enum { PPP_VERTEX_BORDER = 1, PPP_VERTEX_IRREGULAR = 2 };
+enum { PPP_MESH_SIGN_BORDER = 1, PPP_MESH_SIGN_IRREGULAR = 2, PPP_MESH_SIGN_FALLBACK = 4 };
+typedef struct { size_t vertices, edges, border_edges, manifold_edges, inconsistent_edges, nonmanifold_edges,
+                 border_vertices, irregular_vertices; int closed; } ppp_trimesh_topology_stats;
+int  ppp_trimesh_topology(ppp_trimesh m, ppp_trimesh_topology_stats *stats);
+int  ppp_trimesh_get_topology(ppp_trimesh m, int *vertex_id, int *edge_id, unsigned char *edge_class,
+                              unsigned char *vertex_bits, double *vertex_normal, double *edge_normal, size_t cap,
+                              ppp_trimesh_topology_stats *stats);
+int  ppp_trimesh_signed_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist,
+                                double *signed_distance, double *pseudonormal, unsigned char *feature, unsigned char *flags,
+                                double *distance, double *closest, double *deviation, int *tri_index,
+                                unsigned char *region, unsigned char *status);
+typedef struct { ppp_mesh_deviation_stats mesh; size_t on_border, irregular, fallback, negative, positive; } ppp_mesh_signed_deviation_stats;
+int  ppp_get_mesh_signed_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp,
+                                   double *signed_distance, double *smoothed, double *distance, int *tri_index,
+                                   unsigned char *region, unsigned char *feature, unsigned char *flags,
+                                   unsigned char *status, double *target, size_t cap,
+                                   ppp_mesh_signed_deviation_stats *stats);
 /* Registration of a scan to a reference cloud: point-to-plane ICP.  h holds the scan, ref the nominal
    cloud (or the scan before the process); the result T = (R | t), row-major 3 x 4 in double, carries a resident point of h into
    ref's frame.  ppp_get_deviation does not register; these calls do, and ppp_transform_cloud applies their result.  ICP is a

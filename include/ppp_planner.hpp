@@ -155,6 +155,24 @@ public:
     ppp_trimesh get() const { return m_; }
     explicit operator bool() const { return m_ != nullptr; }
     const ppp_trimesh_stats &stats() const { return st_; }
+    /* the welded topology (ppp_trimesh_topology / ppp_trimesh_get_topology), built by the first call: the counts, and
+       where asked the maps per triangle and corner of the caller's list -- ids as corner indices 3 f + k, the edge's class, the
+       vertex's bits, [3] doubles per corner for each pseudonormal.  The return value is the call's code */
+    int topology(ppp_trimesh_topology_stats &st, std::vector<int> *vertex_id = nullptr, std::vector<int> *edge_id = nullptr,
+                 std::vector<unsigned char> *edge_class = nullptr, std::vector<unsigned char> *vertex_bits = nullptr,
+                 std::vector<double> *vertex_normal = nullptr, std::vector<double> *edge_normal = nullptr) const
+    {
+        const size_t c = 3 * st_.triangles;
+        if (vertex_id) vertex_id->assign(c, -1);
+        if (edge_id) edge_id->assign(c, -1);
+        if (edge_class) edge_class->assign(c, (unsigned char)255);
+        if (vertex_bits) vertex_bits->assign(c, (unsigned char)255);
+        if (vertex_normal) vertex_normal->assign(3 * c, 0.0);
+        if (edge_normal) edge_normal->assign(3 * c, 0.0);
+        return ppp_trimesh_get_topology(m_, vertex_id ? vertex_id->data() : nullptr, edge_id ? edge_id->data() : nullptr,
+                                        edge_class ? edge_class->data() : nullptr, vertex_bits ? vertex_bits->data() : nullptr,
+                                        vertex_normal ? vertex_normal->data() : nullptr, edge_normal ? edge_normal->data() : nullptr, st_.triangles, &st);
+    }
 
 private:
     ppp_trimesh m_ = nullptr;
@@ -567,9 +585,34 @@ public:
         }
         return rc == PPP_OK ? true : report(rc);
     }
+    /* mesh_deviation() with the signed distance in the deviation's place (ppp_get_mesh_signed_deviation): the
+       distance to the closest point with the sign of the offset's product with the angle-weighted pseudonormal of the feature it
+       lies on -- inside / outside where the mesh is closed (TriMesh::topology()).  feature and flags by cloud index where asked */
+    bool mesh_signed_deviation(const TriMesh &mesh, ppp_mesh_signed_deviation_stats &st, const ppp_deviation_params &dp, std::vector<double> *target = nullptr,
+                               std::vector<double> *smoothed = nullptr, std::vector<unsigned char> *status = nullptr, std::vector<double> *distance = nullptr,
+                               std::vector<unsigned char> *region = nullptr, std::vector<unsigned char> *feature = nullptr,
+                               std::vector<unsigned char> *flags = nullptr)
+    {
+        size_t n = 0;
+        int rc = (target || smoothed || status || distance || region || feature || flags) ? ppp_num_points(h_, &n) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (target) target->assign(n, 0.0);
+            if (smoothed) smoothed->assign(n, 0.0);
+            if (status) status->assign(n, (unsigned char)PPP_DEV_DROPPED);
+            if (distance) distance->assign(n, 0.0);
+            if (region) region->assign(n, (unsigned char)255);
+            if (feature) feature->assign(n, (unsigned char)255);
+            if (flags) flags->assign(n, (unsigned char)0);
+            rc = ppp_get_mesh_signed_deviation(h_, mesh.get(), &dp, nullptr, smoothed ? smoothed->data() : nullptr, distance ? distance->data() : nullptr, nullptr,
+                                               region ? region->data() : nullptr, feature ? feature->data() : nullptr, flags ? flags->data() : nullptr,
+                                               status ? status->data() : nullptr, target ? target->data() : nullptr, n, &st);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
     /* print_deviation()'s three lines for the STL file `name` measured as triangles (TriMesh::params_from_env()), and a fourth:
-       the closest points by region and the largest distance */
-    void print_mesh_deviation(const std::string &name, const ppp_deviation_params &dp, std::vector<double> *target = nullptr)
+       the closest points by region and the largest distance.  is_signed: the signed distance (mesh_signed_deviation()), with the
+       topology's counts before the block, a warning where the mesh is not closed, and a fifth line: the points by flag and sign */
+    void print_mesh_deviation(const std::string &name, const ppp_deviation_params &dp, std::vector<double> *target = nullptr, bool is_signed = false)
     {
         TriMesh mesh;
         ppp_mesh_deviation_stats ms = {};
@@ -580,10 +623,24 @@ public:
             std::fprintf(stderr, "ppp: %s: %zu triangles (%zu degenerate) in %zu x %zu x %zu cells of %g: %zu pairs, %zu at most in a cell\n", name.c_str(),
                          mesh.stats().triangles, mesh.stats().degenerate, mesh.stats().cells[0], mesh.stats().cells[1], mesh.stats().cells[2],
                          (double)mesh.stats().cell, mesh.stats().pairs, mesh.stats().max_per_cell);
-        if (rc != PPP_OK || !mesh_deviation(mesh, ms, dp, target)) { ms = ppp_mesh_deviation_stats{}; if (target) target->clear(); }
+        ppp_mesh_signed_deviation_stats ss = {};
+        if (is_signed) {
+            ppp_trimesh_topology_stats ts = {};
+            const int trc = rc == PPP_OK ? mesh.topology(ts) : rc;
+            if (rc == PPP_OK && trc != PPP_OK) std::fprintf(stderr, "ppp: %s: the topology could not be built (code %d)\n", name.c_str(), trc);
+            std::printf("topology: %zu vertices, %zu edges: %zu manifold, %zu border, %zu inconsistent, %zu non-manifold; %zu border and %zu irregular vertices\n",
+                        ts.vertices, ts.edges, ts.manifold_edges, ts.border_edges, ts.inconsistent_edges, ts.nonmanifold_edges, ts.border_vertices,
+                        ts.irregular_vertices);
+            if (!ts.closed) std::printf("topology: warning: the mesh is not closed: the sign does not mean inside / outside\n");
+            if (rc != PPP_OK || trc != PPP_OK || !mesh_signed_deviation(mesh, ss, dp, target)) { ss = ppp_mesh_signed_deviation_stats{}; if (target) target->clear(); }
+            ms = ss.mesh;
+        } else if (rc != PPP_OK || !mesh_deviation(mesh, ms, dp, target)) { ms = ppp_mesh_deviation_stats{}; if (target) target->clear(); }
         print_deviation_lines(ms.dev, dp);
         std::printf("deviation: closest points: %zu on a face, %zu on an edge, %zu on a vertex; largest distance %f mm\n", ms.on_face, ms.on_edge,
                     ms.on_vertex, ms.dev.matched ? ms.max_distance : 0.0);
+        if (is_signed)
+            std::printf("deviation: signed: %zu outside, %zu inside; %zu on the border, %zu on irregular features, %zu by the facet's side\n", ss.positive,
+                        ss.negative, ss.on_border, ss.irregular, ss.fallback);
     }
     /* deviation() for the points this planner owns (ppp_get_deviation_tile): this planner holds the scan with a
        slice range (or whole: it then owns everything), ref the reference, whole or a slice range that covers the owned interval

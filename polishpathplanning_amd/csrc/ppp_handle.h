@@ -291,14 +291,15 @@ struct ppp_handle_s {
        mean, its fixed-point term, the float d2, the reference index, the status and the target; the statistics' accumulators and
        the workgroups' parts of the two fixed-order sums.  Nothing is kept between calls: the reference may have changed.
        ppp_get_deviation_tile runs in the same buffers, with the owned map beside them; ppp_get_mesh_deviation too (ref_index
-       holds the triangle), with the distance and region maps and the four words of their statistics beside them. */
+       holds the triangle), with the distance and region maps and the four words of their statistics beside them;
+       ppp_get_mesh_signed_deviation adds the feature and flags maps and the five words of their counts. */
     struct Deviation {
         DevBuf<double> dev, smoothed, target, psum, dist;
         DevBuf<long long> fix;
         DevBuf<float> d2;
         DevBuf<int> ref_index;
-        DevBuf<unsigned char> status, owned, region;
-        DevBuf<unsigned long long> acc, macc;
+        DevBuf<unsigned char> status, owned, region, feature, flags;
+        DevBuf<unsigned long long> acc, macc, sacc;
     } deviation;
     /* registration of this handle's cloud to another handle's (ppp_get_registration_terms, ppp_register): the chain's transforms
        (12 doubles each), the 29 integer sums of every evaluation, the rows and the control words (IcpCtl, as ints).  Nothing is

@@ -71,8 +71,8 @@ __device__ inline unsigned mesh_count(double quotient)
 }
 
 /* the vertices of triangle f, rotated: p0, p1 span the longest edge.  false: an index out of range or a coordinate that is not
-   finite.  *longest = that edge's squared length. */
-__device__ inline bool mesh_triangle(const MeshArgs &A, int f, double p0[3], double p1[3], double p2[3], double *longest)
+   finite.  *longest = that edge's squared length; *rot (where asked): the caller's corner that became p0. */
+__device__ inline bool mesh_triangle(const MeshArgs &A, int f, double p0[3], double p1[3], double p2[3], double *longest, int *rot = nullptr)
 {
     int id[3];
     if (A.tris) { id[0] = A.tris[3 * (size_t)f]; id[1] = A.tris[3 * (size_t)f + 1]; id[2] = A.tris[3 * (size_t)f + 2]; }
@@ -90,6 +90,7 @@ __device__ inline bool mesh_triangle(const MeshArgs &A, int f, double p0[3], dou
     const double ab = mesh_len2(v[0], v[1]), bc = mesh_len2(v[1], v[2]), ca = mesh_len2(v[2], v[0]);
     const int first = (ab >= bc && ab >= ca) ? 0 : (bc >= ca ? 1 : 2);
     *longest = first == 0 ? ab : (first == 1 ? bc : ca);
+    if (rot) *rot = first;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         p0[d] = first == 0 ? v[0][d] : (first == 1 ? v[1][d] : v[2][d]);

@@ -22,10 +22,12 @@
 #include "ppp_trimmed_tile.h"
 #include "ppp_robust_tile.h"
 #include "ppp_trimesh.h"
+#include "ppp_trimesh_topology.h"
 #include "ppp_mesh_registration.h"
 #include "ppp_mesh_robust.h"
 #include "ppp_sort.h"
 #include <cstring>
+#include <mutex>
 
 /* what the deviation accumulator words [0 .. 9] say in the whole-cloud call's statistics or a tile's (a template: C++ linkage) */
 template <typename Stats>
@@ -1646,6 +1648,16 @@ struct ppp_trimesh_s {
     DevBuf<unsigned> cell_start;
     DevBuf<int> cell_rec;
     TriGrid G = {};
+    int n_tris = 0;
+    /* the welded topology (ppp_trimesh_topology.h): built once, by the first call that needs it */
+    std::mutex topo_lock;
+    bool topo_built = false;
+    ppp_trimesh_topology_stats topo_stats = {};
+    TriTopo T = {};
+    DevBuf<int> rec_of, vslot, eslot, table;
+    DevBuf<unsigned char> eclass;
+    DevBuf<unsigned> vbits;
+    DevBuf<double> vpn, epn;
     ~ppp_trimesh_s() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
@@ -1813,6 +1825,7 @@ int ppp_trimesh_create(ppp_handle h, const float *verts, size_t n_verts, const i
     HIPCHK(h, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     for (int d = 0; d < 3; ++d) st.cells[d] = (size_t)G.dim[d];
     st.pairs = pairs; st.max_per_cell = most; st.cell = cell;
+    m->n_tris = (int)n_tris;
     if (stats) *stats = st;
     *out = m.release();
     return PPP_OK;
@@ -1833,25 +1846,148 @@ int ppp_trimesh_create_stl(ppp_handle h, const char *path, const ppp_trimesh_par
     return rc;
 }
 
-/* The primitive: the caller's points up, k_mesh_nearest on the mesh's own stream, the maps down.  No handle: an error is its code. */
-int ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist, double *distance, double *closest, double *deviation, int *tri_index,
-                        unsigned char *region, unsigned char *status)
+/* The welded topology of m (ppp_trimesh_topology.h), built once under the mesh's lock on the mesh's stream: the
+   corner keys, three stable passes, the vertex runs; the half-edge pairs, two stable passes, the edge runs; the table and the
+   vertex counts; one wait.  h (may be NULL): a handle whose kernel timers, where they are on, bracket each step. */
+static int trimesh_topology_build(ppp_trimesh m, ppp_handle h)
+{
+    std::lock_guard<std::mutex> lock(m->topo_lock);
+    if (m->topo_built) return PPP_OK;
+#define TT_CHK(expr) do { if ((expr) != hipSuccess) return PPP_ERR_HIP; } while (0)
+    TT_CHK(hipSetDevice(m->device));
+    const size_t R = (size_t)m->G.indexed, S = 3 * R;
+    const int slots = (int)S;
+    const unsigned grid = (unsigned)((S + TT_T - 1) / TT_T);
+    DevBuf<unsigned> kx, ky, kz, ka, kb;
+    DevBuf<int> va, vb;
+    DevBuf<unsigned char> up;
+    DevBuf<unsigned long long> cnt;
+    DevBuf<char> tmp;
+    TT_CHK(kx.ensure(S)); TT_CHK(ky.ensure(S)); TT_CHK(kz.ensure(S)); TT_CHK(ka.ensure(S)); TT_CHK(kb.ensure(S));
+    TT_CHK(va.ensure(S)); TT_CHK(vb.ensure(S)); TT_CHK(up.ensure(S)); TT_CHK(cnt.ensure(TT_WORDS));
+    TT_CHK(m->rec_of.ensure((size_t)m->n_tris)); TT_CHK(m->vslot.ensure(S)); TT_CHK(m->eslot.ensure(S)); TT_CHK(m->table.ensure(6 * R));
+    TT_CHK(m->eclass.ensure(S)); TT_CHK(m->vbits.ensure(S)); TT_CHK(m->vpn.ensure(3 * S)); TT_CHK(m->epn.ensure(3 * S));
+    TT_CHK(hipMemsetAsync(m->rec_of.p, 0xff, (size_t)m->n_tris * sizeof(int), m->stream)); /* -1: degenerate */
+    TT_CHK(hipMemsetAsync(m->vbits.p, 0, S * sizeof(unsigned), m->stream));
+    TT_CHK(hipMemsetAsync(m->eclass.p, 0xff, S, m->stream));
+    TT_CHK(hipMemsetAsync(cnt.p, 0, TT_WORDS * sizeof(unsigned long long), m->stream));
+    auto timed = [&](const char *name, auto &&step) -> hipError_t {
+        KTimer *t = h && h->timing ? timer_for(h, name) : nullptr;
+        if (t) (void)hipEventRecord(t->e0[t->used], m->stream);
+        (void)hipGetLastError();
+        hipError_t e = step();
+        if (e == hipSuccess) e = hipGetLastError();
+        if (t) { (void)hipEventRecord(t->e1[t->used], m->stream); t->used++; }
+        return e;
+    };
+#define TT_LAUNCH(name, kern, ...) TT_CHK(timed(name, [&]() { hipLaunchKernelGGL(kern, dim3(grid), dim3(TT_T), 0, m->stream, __VA_ARGS__); return hipSuccess; }))
+    auto sort = [&](const unsigned *key_in, const int *val_in, int *val_out, int end_bit) -> hipError_t {
+        size_t bytes = 0;
+        hipError_t e = ppp_sort_pairs_u32(nullptr, &bytes, key_in, ka.p, val_in, val_out, S, end_bit, m->stream);
+        if (e == hipSuccess) e = tmp.ensure(bytes);
+        if (e != hipSuccess) return e;
+        return timed("trimesh_topology_sort", [&]() { return ppp_sort_pairs_u32(tmp.p, &bytes, key_in, ka.p, val_in, val_out, S, end_bit, m->stream); });
+    };
+    const TriRec *rec = m->rec.p;
+    TT_LAUNCH("k_tt_corners", k_tt_corners, rec, slots, kx.p, ky.p, kz.p, va.p, m->rec_of.p);
+    TT_CHK(sort(kz.p, va.p, vb.p, 32));
+    TT_LAUNCH("k_tt_gather", k_tt_gather, slots, (const unsigned *)ky.p, (const int *)vb.p, kb.p);
+    TT_CHK(sort(kb.p, vb.p, va.p, 32));
+    TT_LAUNCH("k_tt_gather", k_tt_gather, slots, (const unsigned *)kx.p, (const int *)va.p, kb.p);
+    TT_CHK(sort(kb.p, va.p, vb.p, 32));
+    TT_LAUNCH("k_tt_vertices", k_tt_vertices, m->G, slots, (const int *)vb.p, (const unsigned *)kx.p, (const unsigned *)ky.p, (const unsigned *)kz.p, m->vslot.p,
+              m->vpn.p, cnt.p);
+    int id_bits = 1;
+    while (id_bits < 32 && (S - 1) >> id_bits) ++id_bits;
+    TT_LAUNCH("k_tt_halfedges", k_tt_halfedges, m->G, slots, (const int *)m->vslot.p, kx.p, ky.p, up.p, va.p); /* kx: the smaller id, ky: the larger */
+    TT_CHK(sort(ky.p, va.p, vb.p, id_bits));
+    TT_LAUNCH("k_tt_gather", k_tt_gather, slots, (const unsigned *)kx.p, (const int *)vb.p, kb.p);
+    TT_CHK(sort(kb.p, vb.p, va.p, id_bits));
+    TT_LAUNCH("k_tt_edges", k_tt_edges, m->G, slots, (const int *)va.p, (const unsigned *)kx.p, (const unsigned *)ky.p, (const unsigned char *)up.p, m->eslot.p,
+              m->eclass.p, m->epn.p, m->vbits.p, cnt.p);
+    TT_LAUNCH("k_tt_table", k_tt_table, rec, slots, (const int *)m->vslot.p, (const int *)m->eslot.p, (const unsigned *)m->vbits.p, m->table.p, cnt.p);
+#undef TT_LAUNCH
+    unsigned long long c[TT_WORDS];
+    TT_CHK(hipMemcpyAsync(c, cnt.p, sizeof(c), hipMemcpyDeviceToHost, m->stream));
+    TT_CHK(hipStreamSynchronize(m->stream)); /* the wait: the scratch may go */
+#undef TT_CHK
+    if (c[0] == 0 || c[0] > S || c[1] == 0 || c[1] > S || c[2] + c[3] + c[4] + c[5] != c[1] || c[6] > c[0] || c[7] > c[0]) return PPP_ERR_HIP;
+    ppp_trimesh_topology_stats &st = m->topo_stats;
+    st.vertices = (size_t)c[0]; st.edges = (size_t)c[1]; st.border_edges = (size_t)c[2]; st.manifold_edges = (size_t)c[3];
+    st.inconsistent_edges = (size_t)c[4]; st.nonmanifold_edges = (size_t)c[5]; st.border_vertices = (size_t)c[6]; st.irregular_vertices = (size_t)c[7];
+    st.closed = c[2] == 0 && c[4] == 0 && c[5] == 0;
+    TriTopo &T = m->T;
+    T.rec_of = m->rec_of.p; T.vslot = m->vslot.p; T.eslot = m->eslot.p; T.eclass = m->eclass.p; T.vbits = m->vbits.p; T.vpn = m->vpn.p; T.epn = m->epn.p;
+    T.table = m->table.p; T.n_tris = m->n_tris;
+    m->topo_built = true;
+    return PPP_OK;
+}
+
+int ppp_trimesh_topology(ppp_trimesh m, ppp_trimesh_topology_stats *stats)
+{
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!m) return PPP_ERR_ARG;
+    const int rc = trimesh_topology_build(m, nullptr);
+    if (rc == PPP_OK && stats) *stats = m->topo_stats;
+    return rc;
+}
+
+int ppp_trimesh_get_topology(ppp_trimesh m, int *vertex_id, int *edge_id, unsigned char *edge_class, unsigned char *vertex_bits, double *vertex_normal,
+                             double *edge_normal, size_t cap, ppp_trimesh_topology_stats *stats)
+{
+    const int rc = ppp_trimesh_topology(m, stats);
+    if (rc) return rc;
+    const size_t k = std::min(cap, (size_t)m->n_tris);
+    if (k == 0 || !(vertex_id || edge_id || edge_class || vertex_bits || vertex_normal || edge_normal)) return PPP_OK;
+#define TM_CHK(expr) do { if ((expr) != hipSuccess) return PPP_ERR_HIP; } while (0)
+    TM_CHK(hipSetDevice(m->device));
+    DevBuf<int> d_v, d_e;
+    DevBuf<unsigned char> d_c, d_b;
+    DevBuf<double> d_vn, d_en;
+    TM_CHK(d_v.ensure(3 * k)); TM_CHK(d_e.ensure(3 * k)); TM_CHK(d_c.ensure(3 * k)); TM_CHK(d_b.ensure(3 * k)); TM_CHK(d_vn.ensure(9 * k)); TM_CHK(d_en.ensure(9 * k));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_tt_export, dim3((unsigned)((k + TT_T - 1) / TT_T)), dim3(TT_T), 0, m->stream, (const TriRec *)m->rec.p, m->T, (int)k, d_v.p, d_e.p, d_c.p, d_b.p,
+                       d_vn.p, d_en.p);
+    TM_CHK(hipGetLastError());
+    if (vertex_id) TM_CHK(hipMemcpyAsync(vertex_id, d_v.p, 3 * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (edge_id) TM_CHK(hipMemcpyAsync(edge_id, d_e.p, 3 * k * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    if (edge_class) TM_CHK(hipMemcpyAsync(edge_class, d_c.p, 3 * k, hipMemcpyDeviceToHost, m->stream));
+    if (vertex_bits) TM_CHK(hipMemcpyAsync(vertex_bits, d_b.p, 3 * k, hipMemcpyDeviceToHost, m->stream));
+    if (vertex_normal) TM_CHK(hipMemcpyAsync(vertex_normal, d_vn.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    if (edge_normal) TM_CHK(hipMemcpyAsync(edge_normal, d_en.p, 9 * k * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    TM_CHK(hipStreamSynchronize(m->stream));
+#undef TM_CHK
+    return PPP_OK;
+}
+
+/* The primitive: the caller's points up, k_mesh_nearest on the mesh's own stream, the maps down.  No handle: an error is its
+   code.  sign: ppp_trimesh_signed_nearest's four maps -- the topology where it is missing, and k_mesh_sign behind the search. */
+struct TrimeshSignMaps { double *signed_distance, *pseudonormal; unsigned char *feature, *flags; };
+static int trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist, const TrimeshSignMaps *sign, double *distance, double *closest,
+                           double *deviation, int *tri_index, unsigned char *region, unsigned char *status)
 {
     if (!m || (!xyz && n) || !(max_dist > 0.f)) return PPP_ERR_ARG;
     if (n > 0x7fffffffu / 8) return PPP_ERR_CAPACITY;
+    if (sign) { const int rc = trimesh_topology_build(m, nullptr); if (rc) return rc; }
     if (n == 0) return PPP_OK;
 #define TM_CHK(expr) do { if ((expr) != hipSuccess) return PPP_ERR_HIP; } while (0)
     TM_CHK(hipSetDevice(m->device));
     DevBuf<float> q;
-    DevBuf<double> d_dist, d_close, d_dev;
+    DevBuf<double> d_dist, d_close, d_dev, d_signed, d_pn;
     DevBuf<int> d_tri;
-    DevBuf<unsigned char> d_region, d_status;
+    DevBuf<unsigned char> d_region, d_status, d_feature, d_flags;
     TM_CHK(q.ensure(3 * n)); TM_CHK(d_status.ensure(n));
     if (distance) TM_CHK(d_dist.ensure(n));
     if (closest) TM_CHK(d_close.ensure(3 * n));
     if (deviation) TM_CHK(d_dev.ensure(n));
-    if (tri_index) TM_CHK(d_tri.ensure(n));
+    if (tri_index || sign) TM_CHK(d_tri.ensure(n));
     if (region) TM_CHK(d_region.ensure(n));
+    if (sign) {
+        TM_CHK(d_signed.ensure(n));
+        if (sign->pseudonormal) TM_CHK(d_pn.ensure(3 * n));
+        if (sign->feature) TM_CHK(d_feature.ensure(n));
+        if (sign->flags) TM_CHK(d_flags.ensure(n));
+    }
     TM_CHK(hipMemcpyAsync(q.p, xyz, 12 * n, hipMemcpyHostToDevice, m->stream));
     const double md2 = (double)max_dist * (double)max_dist;
     const TmOut O = trimesh_outputs(d_dist.p, d_close.p, d_dev.p, nullptr, nullptr, d_tri.p, d_region.p, d_status.p);
@@ -1859,6 +1995,18 @@ int ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dis
     hipLaunchKernelGGL(k_mesh_nearest, dim3((unsigned)((n + TM_T - 1) / TM_T)), dim3(TM_T), 0, m->stream, (const float4 *)nullptr, (const float *)q.p, (int)n, m->G,
                        md2, O);
     TM_CHK(hipGetLastError());
+    if (sign) {
+        TmSignOut SO;
+        SO.signed_distance = d_signed.p; SO.pseudonormal = d_pn.p; SO.dev = nullptr; SO.fix = nullptr; SO.feature = d_feature.p; SO.flags = d_flags.p;
+        SO.tri_index = d_tri.p; SO.status = d_status.p;
+        hipLaunchKernelGGL(k_mesh_sign, dim3((unsigned)((n + TM_T - 1) / TM_T)), dim3(TM_T), 0, m->stream, (const float4 *)nullptr, (const float *)q.p, (int)n, m->G,
+                           m->T, SO);
+        TM_CHK(hipGetLastError());
+        if (sign->signed_distance) TM_CHK(hipMemcpyAsync(sign->signed_distance, d_signed.p, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (sign->pseudonormal) TM_CHK(hipMemcpyAsync(sign->pseudonormal, d_pn.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        if (sign->feature) TM_CHK(hipMemcpyAsync(sign->feature, d_feature.p, n, hipMemcpyDeviceToHost, m->stream));
+        if (sign->flags) TM_CHK(hipMemcpyAsync(sign->flags, d_flags.p, n, hipMemcpyDeviceToHost, m->stream));
+    }
     if (distance) TM_CHK(hipMemcpyAsync(distance, d_dist.p, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
     if (closest) TM_CHK(hipMemcpyAsync(closest, d_close.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
     if (deviation) TM_CHK(hipMemcpyAsync(deviation, d_dev.p, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
@@ -1870,23 +2018,45 @@ int ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dis
     return PPP_OK;
 }
 
+int ppp_trimesh_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist, double *distance, double *closest, double *deviation, int *tri_index,
+                        unsigned char *region, unsigned char *status)
+{
+    return trimesh_nearest(m, xyz, n, max_dist, nullptr, distance, closest, deviation, tri_index, region, status);
+}
+
+int ppp_trimesh_signed_nearest(ppp_trimesh m, const float *xyz, size_t n, float max_dist, double *signed_distance, double *pseudonormal, unsigned char *feature,
+                               unsigned char *flags, double *distance, double *closest, double *deviation, int *tri_index, unsigned char *region,
+                               unsigned char *status)
+{
+    const TrimeshSignMaps sign = {signed_distance, pseudonormal, feature, flags};
+    return trimesh_nearest(m, xyz, n, max_dist, &sign, distance, closest, deviation, tri_index, region, status);
+}
+
 /* The exact deviation map: the scan's slab index, k_tm_fill and k_mesh_nearest over its points in slab order,
    then ppp_get_deviation's own tail (deviation_tail) and the counts by region, all on the scan's stream; one wait. */
-int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *deviation, double *smoothed, double *distance, int *tri_index,
-                           unsigned char *region, unsigned char *status, double *target, size_t cap, ppp_mesh_deviation_stats *stats)
+struct MeshSignMaps { unsigned char *feature, *flags; ppp_mesh_signed_deviation_stats *stats; };
+static int mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, const MeshSignMaps *sign, double *deviation, double *smoothed,
+                          double *distance, int *tri_index, unsigned char *region, unsigned char *status, double *target, size_t cap,
+                          ppp_mesh_deviation_stats *stats)
 {
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!m || !dp) return fail(h, PPP_ERR_ARG, "mesh deviation: no mesh or no parameters");
-    int rc = deviation_params_ok(h, *dp, "mesh deviation", nullptr);
+    const std::string w = sign ? "mesh signed deviation" : "mesh deviation";
+    if (!m || !dp) return fail(h, PPP_ERR_ARG, w + ": no mesh or no parameters");
+    int rc = deviation_params_ok(h, *dp, w, nullptr);
     if (rc) return rc;
-    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "mesh deviation: the mesh is on another device than the handle");
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the mesh is on another device than the handle");
     const ppp_deviation_params P = *dp;
     const bool smooth = P.smooth_radius > 0.f;
-    rc = deviation_side(h, h, "the scan", "mesh deviation");
+    rc = deviation_side(h, h, "the scan", w.c_str());
     if (rc) return rc;
     const size_t N = h->n;
-    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, "mesh deviation: max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, w + ": max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    if (sign) { /* the topology on the mesh's stream, waited for: read-only from here on */
+        rc = trimesh_topology_build(m, h);
+        if (rc) return fail(h, rc, w + ": the mesh's topology could not be built");
+        HIPCHK(h, hipSetDevice(h->device));
+    }
     auto &D = h->deviation;
     const size_t N1 = std::max<size_t>(N, 1);
     const MapParts parts(h, N);
@@ -1905,13 +2075,25 @@ int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_para
                (double)P.max_dist * (double)P.max_dist, O);
     }
     LAUNCH(h, "k_tm_region_stats", k_tm_region_stats, gn, TM_T, 0, (int)N, D.status.p, D.region.p, D.dist.p, D.macc.p);
+    if (sign) { /* the signed distance takes the deviation's place, in the map and in its fixed-point term, before the tail reads them */
+        HIPCHK(h, D.feature.ensure(N1)); HIPCHK(h, D.flags.ensure(N1)); HIPCHK(h, D.sacc.ensure(5));
+        HIPCHK(h, hipMemsetAsync(D.sacc.p, 0, 5 * sizeof(unsigned long long), h->stream));
+        LAUNCH(h, "k_tm_sign_fill", k_tm_sign_fill, gn, TM_T, 0, (int)N, D.feature.p, D.flags.p);
+        if (nq > 0) {
+            TmSignOut SO;
+            SO.signed_distance = D.dev.p; SO.pseudonormal = nullptr; SO.dev = nullptr; SO.fix = D.fix.p; SO.feature = D.feature.p; SO.flags = D.flags.p;
+            SO.tri_index = D.ref_index.p; SO.status = D.status.p;
+            LAUNCH(h, "k_mesh_sign", k_mesh_sign, (unsigned)((nq + TM_T - 1) / TM_T), TM_T, 0, (const float4 *)h->sorted4.p, (const float *)nullptr, nq, m->G, m->T, SO);
+        }
+        LAUNCH(h, "k_tm_sign_stats", k_tm_sign_stats, gn, TM_T, 0, (int)N, D.status.p, D.flags.p, D.dev.p, D.sacc.p);
+    }
     const double *v = nullptr;
     ppp_mesh_deviation_stats st = {};
-    rc = deviation_tail(h, P, parts, "mesh deviation", &st.dev, &v);
+    rc = deviation_tail(h, P, parts, w.c_str(), &st.dev, &v);
     if (rc) return rc;
     unsigned long long macc[4];
     HIPCHK(h, copy_sync(h, macc, D.macc.p, sizeof(macc), hipMemcpyDeviceToHost));
-    if (macc[0] + macc[1] + macc[2] != st.dev.matched) return fail(h, PPP_ERR_HIP, "mesh deviation: statistics corrupt");
+    if (macc[0] + macc[1] + macc[2] != st.dev.matched) return fail(h, PPP_ERR_HIP, w + ": statistics corrupt");
     st.on_face = (size_t)macc[0]; st.on_edge = (size_t)macc[1]; st.on_vertex = (size_t)macc[2];
     st.max_distance = (double)NAN;
     if (st.dev.matched) memcpy(&st.max_distance, &macc[3], sizeof(double));
@@ -1921,7 +2103,35 @@ int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_para
     if (rc) return rc;
     if (distance && k) HIPCHK(h, copy_sync(h, distance, D.dist.p, k * sizeof(double), hipMemcpyDeviceToHost));
     if (region && k) HIPCHK(h, copy_sync(h, region, D.region.p, k, hipMemcpyDeviceToHost));
+    if (sign) {
+        unsigned long long sacc[5];
+        HIPCHK(h, copy_sync(h, sacc, D.sacc.p, sizeof(sacc), hipMemcpyDeviceToHost));
+        if (sacc[3] + sacc[4] > st.dev.matched) return fail(h, PPP_ERR_HIP, w + ": statistics corrupt");
+        if (sign->stats) {
+            ppp_mesh_signed_deviation_stats &ss = *sign->stats;
+            ss.mesh = st;
+            ss.on_border = (size_t)sacc[0]; ss.irregular = (size_t)sacc[1]; ss.fallback = (size_t)sacc[2]; ss.negative = (size_t)sacc[3]; ss.positive = (size_t)sacc[4];
+        }
+        if (sign->feature && k) HIPCHK(h, copy_sync(h, sign->feature, D.feature.p, k, hipMemcpyDeviceToHost));
+        if (sign->flags && k) HIPCHK(h, copy_sync(h, sign->flags, D.flags.p, k, hipMemcpyDeviceToHost));
+    }
     return PPP_OK;
+}
+
+int ppp_get_mesh_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *deviation, double *smoothed, double *distance, int *tri_index,
+                           unsigned char *region, unsigned char *status, double *target, size_t cap, ppp_mesh_deviation_stats *stats)
+{
+    return mesh_deviation(h, m, dp, nullptr, deviation, smoothed, distance, tri_index, region, status, target, cap, stats);
+}
+
+/* The signed deviation map: ppp_get_mesh_deviation's launches with k_mesh_sign (and the fill and the counts of
+   its two maps) between the search and the tail. */
+int ppp_get_mesh_signed_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *signed_distance, double *smoothed, double *distance,
+                                  int *tri_index, unsigned char *region, unsigned char *feature, unsigned char *flags, unsigned char *status, double *target,
+                                  size_t cap, ppp_mesh_signed_deviation_stats *stats)
+{
+    const MeshSignMaps sign = {feature, flags, stats};
+    return mesh_deviation(h, m, dp, &sign, signed_distance, smoothed, distance, tri_index, region, status, target, cap, nullptr);
 }
 
 /* The mesh registration chain: registration_chain's shape with the mesh in the reference's place -- the scan's

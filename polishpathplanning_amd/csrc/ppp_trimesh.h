@@ -21,8 +21,9 @@
 #define TM_MAX_PAIRS 0x7ffffffeu /* the pair list stays below 2^31 - 1 */
 #define TM_SIDE_SCALE 4294967296.0 /* 2^32: a box side over the mesh's largest extent, in fixed point */
 
-/* one record per indexed triangle, three 16-byte loads: the nine rotated resident floats and f, the index in the caller's list */
-struct TriRec { float4 a, b, c; }; /* a = (p0x p0y p0z p1x), b = (p1y p1z p2x p2y), c = (p2z, f as bits, 0, 0) */
+/* one record per indexed triangle, three 16-byte loads: the nine rotated resident floats, f, the index in the caller's list, and
+   rot, the caller's corner that the rotation made p0 (the search does not read it: the topology does, ppp_trimesh_topology.h) */
+struct TriRec { float4 a, b, c; }; /* a = (p0x p0y p0z p1x), b = (p1y p1z p2x p2y), c = (p2z, f as bits, rot as bits, 0) */
 static_assert(sizeof(TriRec) == 48, "a record is 48 bytes");
 
 /* the grid as the kernels see it: by value */
@@ -101,11 +102,12 @@ __global__ void __launch_bounds__(TM_T) k_tm_records(MeshArgs A, const unsigned 
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= A.n_tris || rank[f + 1] == rank[f]) return;
     double p0[3], p1[3], p2[3], longest = 0.0;
-    (void)mesh_triangle(A, f, p0, p1, p2, &longest); /* (an indexed triangle passed every test) */
+    int rot = 0;
+    (void)mesh_triangle(A, f, p0, p1, p2, &longest, &rot); /* (an indexed triangle passed every test) */
     TriRec R;
     R.a = make_float4((float)p0[0], (float)p0[1], (float)p0[2], (float)p1[0]);
     R.b = make_float4((float)p1[1], (float)p1[2], (float)p2[0], (float)p2[1]);
-    R.c = make_float4((float)p2[2], __int_as_float(f), 0.f, 0.f);
+    R.c = make_float4((float)p2[2], __int_as_float(f), __int_as_float(rot), 0.f);
     rec[rank[f]] = R;
 }
 

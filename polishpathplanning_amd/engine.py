@@ -82,6 +82,7 @@ EXPORTS = [
     "ppp_set_fast_path", "ppp_get_fast_path", "ppp_set_plan_reuse", "ppp_set_cloud_pcd", "ppp_pcd_probe", "ppp_set_cloud_device_async",
     "ppp_default_mesh_params", "ppp_set_cloud_mesh", "ppp_set_cloud_stl", "ppp_load_stl", "ppp_save_stl",
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
+    "ppp_trimesh_topology", "ppp_trimesh_get_topology", "ppp_trimesh_signed_nearest", "ppp_get_mesh_signed_deviation",
     "ppp_get_mesh_registration_terms", "ppp_register_mesh", "ppp_get_mesh_robust_registration_terms", "ppp_register_mesh_robust",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
@@ -276,6 +277,11 @@ def lib():
         L.ppp_trimesh_destroy.restype = None
         L.ppp_trimesh_nearest.argtypes = [vp, fp, sz, C.c_float, dp, dp, dp, ip, ubp, ubp]
         L.ppp_get_mesh_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, dp, sz, C.POINTER(MeshDeviationStats)]
+        L.ppp_trimesh_topology.argtypes = [vp, C.POINTER(TriMeshTopologyStats)]
+        L.ppp_trimesh_get_topology.argtypes = [vp, ip, ip, ubp, ubp, dp, dp, sz, C.POINTER(TriMeshTopologyStats)]
+        L.ppp_trimesh_signed_nearest.argtypes = [vp, fp, sz, C.c_float, dp, dp, ubp, ubp, dp, dp, dp, ip, ubp, ubp]
+        L.ppp_get_mesh_signed_deviation.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, ubp, ubp, dp, sz,
+                                                    C.POINTER(MeshSignedDeviationStats)]
         L.ppp_get_mesh_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
         L.ppp_register_mesh.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
         L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
@@ -335,6 +341,10 @@ def _mesh_stats(st):
 
 TRIMESH_WINDING, TRIMESH_VIEWPOINT = 0, 1  # PPP_TRIMESH_*
 REGION_FACE, REGION_EDGE, REGION_VERTEX, REGION_NONE = 0, 1, 2, 255  # the region map of the exact search
+EDGE_BORDER, EDGE_MANIFOLD, EDGE_INCONSISTENT, EDGE_NONMANIFOLD = 0, 1, 2, 3  # PPP_EDGE_*
+VERTEX_BORDER, VERTEX_IRREGULAR = 1, 2  # PPP_VERTEX_*
+MESH_SIGN_BORDER, MESH_SIGN_IRREGULAR, MESH_SIGN_FALLBACK = 1, 2, 4  # PPP_MESH_SIGN_*
+FEATURE_FACE, FEATURE_NONE = 6, 255  # the feature map of the signed search: 0 .. 2 a corner, 3 .. 5 a half-edge
 
 
 class TriMeshParams(C.Structure):  # ppp_trimesh_params
@@ -344,6 +354,11 @@ class TriMeshParams(C.Structure):  # ppp_trimesh_params
 class TriMeshStats(C.Structure):  # ppp_trimesh_stats
     _fields_ = [("triangles", C.c_size_t), ("indexed", C.c_size_t), ("degenerate", C.c_size_t), ("cells", C.c_size_t * 3),
                 ("pairs", C.c_size_t), ("max_per_cell", C.c_size_t), ("cell", C.c_float), ("mn", C.c_float * 3), ("mx", C.c_float * 3)]
+
+
+class TriMeshTopologyStats(C.Structure):  # ppp_trimesh_topology_stats
+    _fields_ = [(k, C.c_size_t) for k in ("vertices", "edges", "border_edges", "manifold_edges", "inconsistent_edges", "nonmanifold_edges",
+                                          "border_vertices", "irregular_vertices")] + [("closed", C.c_int)]
 
 
 def _trimesh_stats(st):
@@ -381,6 +396,48 @@ class TriMesh:
         if rc:
             raise PPPError(rc, "ppp_trimesh_nearest failed")
         return dist[:n], close[:n], dev[:n], tri[:n], region[:n], status[:n]
+
+    def topology(self, maps=True):
+        """(stats dict, arrays dict) of the mesh's welded topology (ppp_trimesh_topology / ppp_trimesh_get_topology), built on
+        the first call.  stats: vertices, edges, border_edges, manifold_edges, inconsistent_edges, nonmanifold_edges,
+        border_vertices, irregular_vertices, closed.  arrays, per triangle and corner of the caller's list: vertex_id int32[nt, 3],
+        edge_id int32[nt, 3] (corner indices 3 f + k), edge_class uint8[nt, 3] (EDGE_*), vertex_bits uint8[nt, 3] (VERTEX_*),
+        vertex_normal and edge_normal float64[nt, 3, 3] (the pseudonormals, not normalised); -1, 255 and NaN for a degenerate
+        triangle.  maps=False: the stats and None."""
+        st = TriMeshTopologyStats()
+        ub = C.POINTER(C.c_ubyte)
+        arrays = None
+        if not maps:
+            rc = self.L.ppp_trimesh_topology(self.m, C.byref(st))
+        else:
+            nt = self.stats["triangles"]
+            arrays = dict(vertex_id=np.zeros((nt, 3), np.int32), edge_id=np.zeros((nt, 3), np.int32), edge_class=np.zeros((nt, 3), np.uint8),
+                          vertex_bits=np.zeros((nt, 3), np.uint8), vertex_normal=np.zeros((nt, 3, 3), np.float64), edge_normal=np.zeros((nt, 3, 3), np.float64))
+            rc = self.L.ppp_trimesh_get_topology(self.m, _i(arrays["vertex_id"]), _i(arrays["edge_id"]), arrays["edge_class"].ctypes.data_as(ub),
+                                                 arrays["vertex_bits"].ctypes.data_as(ub), _d(arrays["vertex_normal"]), _d(arrays["edge_normal"]), nt, C.byref(st))
+        if rc:
+            raise PPPError(rc, "ppp_trimesh_topology failed")
+        return {k: int(getattr(st, k)) for k, _ in TriMeshTopologyStats._fields_}, arrays
+
+    def signed_nearest(self, xyz, max_dist=float("inf")):
+        """(signed_distance float64[n], pseudonormal float64[n, 3], feature uint8[n], flags uint8[n]) and then nearest()'s six maps,
+        bit for bit (ppp_trimesh_signed_nearest): the distance with the sign of the offset's product with the angle-weighted
+        pseudonormal of the feature the closest point lies on (a corner 0 .. 2, a half-edge 3 .. 5, FEATURE_FACE), and
+        MESH_SIGN_BORDER / MESH_SIGN_IRREGULAR / MESH_SIGN_FALLBACK.  Negative means inside only where topology()'s closed is 1.
+        NaN, FEATURE_NONE and 0 where not matched."""
+        q = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = q.shape[0]
+        n1 = max(n, 1)
+        sd, dist, dev = (np.zeros(n1, np.float64) for _ in range(3))
+        pn, close = np.zeros((n1, 3), np.float64), np.zeros((n1, 3), np.float64)
+        tri = np.zeros(n1, np.int32)
+        feature, flags, region, status = (np.zeros(n1, np.uint8) for _ in range(4))
+        ub = C.POINTER(C.c_ubyte)
+        rc = self.L.ppp_trimesh_signed_nearest(self.m, _f(q), n, float(max_dist), _d(sd), _d(pn), feature.ctypes.data_as(ub), flags.ctypes.data_as(ub),
+                                               _d(dist), _d(close), _d(dev), _i(tri), region.ctypes.data_as(ub), status.ctypes.data_as(ub))
+        if rc:
+            raise PPPError(rc, "ppp_trimesh_signed_nearest failed")
+        return sd[:n], pn[:n], feature[:n], flags[:n], dist[:n], close[:n], dev[:n], tri[:n], region[:n], status[:n]
 
     def close(self):
         if self.m:
@@ -552,6 +609,12 @@ def _deviation_stats(st):
 class MeshDeviationStats(C.Structure):
     """ppp_mesh_deviation_stats"""
     _fields_ = [("dev", DeviationStats), ("on_face", C.c_size_t), ("on_edge", C.c_size_t), ("on_vertex", C.c_size_t), ("max_distance", C.c_double)]
+
+
+class MeshSignedDeviationStats(C.Structure):
+    """ppp_mesh_signed_deviation_stats"""
+    _fields_ = [("mesh", MeshDeviationStats), ("on_border", C.c_size_t), ("irregular", C.c_size_t), ("fallback", C.c_size_t), ("negative", C.c_size_t),
+                ("positive", C.c_size_t)]
 
 
 def merge_deviation_tiles(tiles):
@@ -1401,6 +1464,36 @@ class Engine:
         stats = _deviation_stats(st.dev)
         stats.update(on_face=int(st.on_face), on_edge=int(st.on_edge), on_vertex=int(st.on_vertex), max_distance=float(st.max_distance))
         return dev, sm, dist, idx, region, status, target, stats
+
+    def mesh_signed_deviation(self, mesh, max_dist=float("inf"), smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(signed_distance float64[n], smoothed float64[n], distance float64[n], tri_index int32[n], region uint8[n], feature
+        uint8[n], flags uint8[n], status uint8[n], target float64[n], stats dict): mesh_deviation() with the signed distance of
+        TriMesh.signed_nearest() in the deviation's place (ppp_get_mesh_signed_deviation): smoothed, target and the statistics are
+        computed from it.  stats: mesh_deviation()'s fields and on_border, irregular, fallback, negative, positive.  maps=False
+        returns nine Nones and stats"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = MeshSignedDeviationStats()
+        sd = sm = dist = idx = region = feature = flags = status = target = None
+        m = mesh.m if mesh is not None else None
+        if not maps:
+            self._chk(self.L.ppp_get_mesh_signed_deviation(self.h, m, C.byref(dp), None, None, None, None, None, None, None, None, None, 0, C.byref(st)))
+        else:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            n1 = max(n, 1)
+            sd, sm, dist, target = (np.zeros(n1, np.float64) for _ in range(4))
+            idx = np.zeros(n1, np.int32)
+            region, feature, flags, status = (np.zeros(n1, np.uint8) for _ in range(4))
+            ub = C.POINTER(C.c_ubyte)
+            self._chk(self.L.ppp_get_mesh_signed_deviation(self.h, m, C.byref(dp), _d(sd), _d(sm), _d(dist), _i(idx), region.ctypes.data_as(ub),
+                                                           feature.ctypes.data_as(ub), flags.ctypes.data_as(ub), status.ctypes.data_as(ub), _d(target), n,
+                                                           C.byref(st)))
+            sd, sm, dist, idx, region, feature, flags, status, target = (a[:n] for a in (sd, sm, dist, idx, region, feature, flags, status, target))
+        stats = _deviation_stats(st.mesh.dev)
+        stats.update(on_face=int(st.mesh.on_face), on_edge=int(st.mesh.on_edge), on_vertex=int(st.mesh.on_vertex), max_distance=float(st.mesh.max_distance),
+                     on_border=int(st.on_border), irregular=int(st.irregular), fallback=int(st.fallback), negative=int(st.negative), positive=int(st.positive))
+        return sd, sm, dist, idx, region, feature, flags, status, target, stats
 
     def mesh_registration_terms(self, mesh, T=None, max_dist=2.0, lock_eps=1e-9):
         """(row, stats) of one evaluation of the point-to-plane terms of this engine's cloud, the scan, moved by T (3 x 4, None:
