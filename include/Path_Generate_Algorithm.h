@@ -153,6 +153,9 @@ public:
        register_robust_to()'s weights, tune and sigma_min from the same variables */
     void register_robust_to_mesh(const std::string &stl) { planner.print_mesh_robust_registration(stl, ppp::Planner::robust_registration_params_env()); }
     void register_global_to(const SectPath &ref) { planner.print_global_registration(ref.planner, ppp::Planner::global_registration_params_env()); }
+    /* register_global_to() against the triangles of the STL file `stl` themselves (ppp_register_mesh_global): the
+       mesh's area frame against the scan's point frame, the coarse chains and the fine chain on the facets; no pitch, no normal field */
+    void register_global_to_mesh(const std::string &stl) { planner.print_mesh_global_registration(stl, ppp::Planner::global_registration_params_env()); }
     /* what the contact model says about the workpiece itself, before or apart from any path: the points with a contact width,
        its smallest / mean / largest half width, the points narrower than the slice step (ppp_get_contact_field) */
     void get_contact_field() { planner.print_contact_field(); }

@@ -730,7 +730,8 @@ int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *r
    Solve, step, composition, the loop's endings, rows and stats are ppp_register's.  On an edge or a vertex the normal is the
    winning facet's (pseudonormals are out of scope), and the scan's overhang beyond an open mesh's border pairs there with the
    border facet's normal as long as it lies within max_dist (no pair is rejected on the border).  Robust weights are
-   ppp_register_mesh_robust's (below); trimmed weights, tiles over slice ranges and a global start from the mesh are not offered.
+   ppp_register_mesh_robust's (below), the start from an unknown pose is ppp_register_mesh_global's (further down); trimmed weights
+   and tiles over slice ranges are not offered.
    ppp_get_mesh_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; ppp_register_mesh runs the loop
    from T0_12; row, rows and stats are filled as ppp_get_registration_terms and ppp_register fill them.  Both build h's slab index
    where it is missing, enqueue the whole chain (iterations + 1 evaluations, iterations steps) on h's stream and wait once; the
@@ -868,8 +869,8 @@ int  ppp_register_robust(ppp_handle h, ppp_handle ref, const ppp_robust_registra
    tune == +INFINITY weighs every pair 1: rows[k].row, T and stats are ppp_register_mesh's bits from the same start.  Every
    output is the same for every grid cell of the mesh, and the same bits in every run.  The estimator's limit is
    ppp_register_robust's: the median residual must belong to the part that shows the mesh (with 35 % of the scan raised by 1.5 mm
-   it does not, and the fit stays tilted).  Trimmed weights, tiles over slice ranges, a global start from the mesh,
-   pseudonormals and border rejection are not offered.
+   it does not, and the fit stays tilted).  Trimmed weights, tiles over slice ranges, pseudonormals and
+   border rejection are not offered; the start from an unknown pose is ppp_register_mesh_global's (further down).
    ppp_get_mesh_robust_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; its maps are that
    evaluation's.  rows, row, the maps and stats may be NULL (rows with row_cap = 0; the maps with any cap).  The whole chain -- per
    evaluation the grid walk, paid once, with the residual, the key and the top digit's histogram, two passes over the stored
@@ -980,6 +981,49 @@ void ppp_default_global_registration_params(ppp_global_registration_params *gp);
 int  ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registration_params *gp,
                          ppp_registration_candidate *cands, size_t cand_cap, ppp_registration_row *rows, size_t row_cap,
                          ppp_global_registration_stats *stats);
+/* Global registration to the triangle mesh itself: the start ppp_register_mesh needs, from the scan
+   and the mesh alone -- no sampled cloud, no pitch, no normal field, no second handle.  ppp_register_global's rule with the
+   reference side replaced: the mesh's frame is that of its SURFACE, from ten order-free integer sums over the indexed triangles
+   (a vertex-weighted frame would be pulled towards the fillets of a CAD export, where the facets are small).
+     moments    mn, mx = the mesh's box (ppp_trimesh_stats mn / mx, floats widened); c, L by ppp_get_cloud_moments' expressions;
+                per indexed triangle, on the rotated resident floats of ppp_trimesh_create's frame widened to double:
+                u_i = (p_i - c) / L for the three corners; N = (u1 - u0) x (u2 - u0), component by component e1y e2z - e1z e2y,
+                e1z e2x - e1x e2z, e1x e2y - e1y e2x; a = sqrt((Nx Nx + Ny Ny) + Nz Nz) * 0.5; s = (u0 + u1) + u2;
+                q_dk = ((u0_d u0_k + u1_d u1_k) + u2_d u2_k) + s_d s_k for dk = xx xy xz yy yz zz (a <= 2 sqrt 3, |q| <= 12);
+                ms = min(40, 54 - clog2(max(2, n_tris))), n_tris the caller's triangle count; words[0] = W0 = the sum of
+                llrint(a 2^ms), words[1 + d] = the sum of llrint((a s_d) 2^ms), words[4 ..] = the sums of llrint((a q_dk) 2^ms),
+                in signed 64-bit integers.  The integrals of u_d and of u_d u_k over a triangle are a s_d / 3 and a q_dk / 12.
+     frame      m_d = (double)S1_d / (3.0 * (double)W0); C_dk = (double)S2_dk / (12.0 * (double)W0) - m_d m_k; from there
+                ppp_get_cloud_moments' frame unchanged: the Jacobi sweeps, the ordering, the signs, mean = c + L m,
+                eigenvalues = (lambda L) L
+     coarse     the starts of ppp_registration_starts(scan = h's point frame, ref = the mesh's area frame); the queries of
+                ppp_register_global; from every start a chain of ppp_register_mesh with the parameters `coarse` on those queries,
+                with ppp_register_mesh's c and Ln (the mesh's box) and shift (coarse.max_dist, n = cloud->size() of h): with
+                stride 1 each chain IS ppp_register_mesh from that start, bit for bit
+     cost, fine ppp_register_global's cost, winner, tie rule and second_cost; the fine chain is ppp_register_mesh with the
+                parameters `fine` from the winner's T: rows and stats.fine are that call's
+   ppp_trimesh_get_moments fills *frame for the mesh (one kernel and one wait on the mesh's own stream): ppp_cloud_frame is
+   reused, with count = the indexed triangles and words[0] = W0, the area in fixed point -- NOT a count: for these words
+   ppp_cloud_frame_from_moments is not the inverse, ppp_mesh_frame_from_moments is (host only; the words do not hold the
+   triangle count, so it sets count = 0; every other member is ppp_trimesh_get_moments').  ppp_register_mesh_global builds h's
+   slab index where it is missing, takes both frames, enqueues coarse.iterations + 1 evaluations (a search and a sum launch
+   each) and coarse.iterations steps of all starts back to back on h's stream, waits once, then runs the fine chain.  stats.ref
+   is the mesh's area frame, stats.scan the scan's point frame; cands, rows and stats otherwise as ppp_register_global fills
+   them.  Neither the cloud, the plan, the mesh nor any stored result changes.  The same bits in every run, for every grid cell.
+   Limits: the scan must cover the same extent as the mesh at an even density -- the scan's frame weighs points, the mesh's
+   weighs area (ppp_voxel_down evens a scan); a closed mesh scanned from one side does not qualify; a part that is symmetric
+   under one of the 24 motions is ambiguous, as for ppp_register_global; the fine chain has no robust weights: with a
+   contaminated scan run ppp_register_mesh_robust from stats.fine.T.
+   PPP_ERR_ARG: ppp_register_global's refusals for gp, `coarse`, `fine`, candidates, stride, cands and rows, and "no query
+   left"; m NULL; a mesh on another device than h; shift < 16 for either parameter set; no indexed point on h or L == 0 on its
+   cloud; W0 <= 0 (or L == 0) on the mesh; a start that is not finite.  ppp_trimesh_get_moments: m or frame NULL, W0 <= 0.
+   ppp_mesh_frame_from_moments: a NULL argument, words[0] <= 0, ms outside [0, 62], L not finite and > 0.
+   PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+int  ppp_trimesh_get_moments(ppp_trimesh m, ppp_cloud_frame *frame);
+int  ppp_mesh_frame_from_moments(const long long *words10, int ms, const double *c3, double L, ppp_cloud_frame *frame);
+int  ppp_register_mesh_global(ppp_handle h, ppp_trimesh m, const ppp_global_registration_params *gp,
+                              ppp_registration_candidate *cands, size_t cand_cap, ppp_registration_row *rows, size_t row_cap,
+                              ppp_global_registration_stats *stats);
 /* The contact field of the resident cloud: for every cloud point i, compute_transform + Area2Cloud
    evaluated AT the point (query = its resident float coordinates, after the x1000 and any preprocessing).
      curv5[5*i..]  = what ppp_principal_curvatures_at returns for that query

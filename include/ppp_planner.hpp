@@ -984,6 +984,32 @@ public:
         ppp_global_registration_stats g = {};
         const bool ran = register_global_to(ref, g, gp);
         if (!ran) g = ppp_global_registration_stats{};
+        return print_global_registration_lines(g, gp, ran, apply);
+    }
+    /* global registration of this planner's cloud, the scan, to the triangles of mesh themselves (ppp_register_mesh_global;
+       DESIGN.md 7x): register_global_to() with the mesh's area frame in the place of a cloud's point frame and register_mesh()'s
+       chains in the place of register_to()'s -- no sampled cloud, no pitch, no normal field.  st and cands as register_global_to()'s */
+    bool register_mesh_global(const TriMesh &mesh, ppp_global_registration_stats &st, const ppp_global_registration_params &gp,
+                              std::vector<ppp_registration_candidate> *cands = nullptr)
+    {
+        if (cands) cands->assign((size_t)(gp.candidates > 0 ? gp.candidates : 0), ppp_registration_candidate{});
+        int rc = ppp_register_mesh_global(h_, mesh.get(), &gp, cands ? cands->data() : nullptr, cands ? cands->size() : 0, nullptr, 0, &st);
+        if (rc != PPP_OK) { if (cands) cands->clear(); return report(rc); }
+        return true;
+    }
+    /* print_global_registration() for the STL file `name` registered to as triangles: the grid's line on stderr,
+       register_mesh_global(), print_global_registration()'s lines and, with apply, the cloud moved */
+    bool print_mesh_global_registration(const std::string &name, const ppp_global_registration_params &gp, bool apply = true)
+    {
+        TriMesh mesh;
+        ppp_global_registration_stats g = {};
+        const bool ran = open_mesh_for_registration(mesh, name) && register_mesh_global(mesh, g, gp);
+        if (!ran) g = ppp_global_registration_stats{};
+        return print_global_registration_lines(g, gp, ran, apply);
+    }
+    /* print_global_registration()'s seven lines on the statistics of a call that ran (or did not), and its move of the cloud */
+    bool print_global_registration_lines(const ppp_global_registration_stats &g, const ppp_global_registration_params &gp, bool ran, bool apply)
+    {
         const ppp_registration_stats &st = g.fine;
         std::printf("global registration: %d starts on %zu queries; eigenvalues %f %f %f mm^2 against %f %f %f\n", g.candidates, g.queries,
                     g.scan.eigenvalues[0], g.scan.eigenvalues[1], g.scan.eigenvalues[2], g.ref.eigenvalues[0], g.ref.eigenvalues[1], g.ref.eigenvalues[2]);

@@ -335,6 +335,24 @@ __host__ __device__ inline int mom_shift(size_t n)
     return s < 40 ? s : 40;
 }
 
+/* the threads' ten words of a workgroup of MOM_T threads into acc: icp_flush's pattern (k_cloud_moments, k_mesh_moments) */
+__device__ __attribute__((always_inline)) inline void mom_flush(unsigned long long *a, unsigned long long (*s_a)[MOM_WORDS],
+                                                               unsigned long long *__restrict__ acc)
+{
+#pragma unroll
+    for (int w = 0; w < MOM_WORDS; ++w) a[w] = wave_sum(a[w]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int w = 0; w < MOM_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
+    }
+    __syncthreads();
+    if (threadIdx.x < MOM_WORDS) {
+        unsigned long long s = 0;
+        for (int v = 0; v < MOM_T / 64; ++v) s += s_a[v][threadIdx.x];
+        if (s) atomicAdd(acc + threadIdx.x, s);
+    }
+}
+
 /* A thread per indexed point in slab order, grid-stride: u = ((double)p - c) / L, the ten words rounded to 2^-ms (F.scale =
    2^ms) into the thread's 64-bit integers, added over the wave, over the workgroup through LDS, and by one 64-bit integer
    atomic per workgroup and non-zero word: k_reg_terms's pattern.  |u_d| <= 1 and n 2^ms <= 2^60: no word overflows. */
@@ -356,40 +374,20 @@ __global__ void __launch_bounds__(MOM_T) k_cloud_moments(const float4 *__restric
             for (int k = d; k < 3; ++k, ++w) a[w] += (unsigned long long)llrint((u[d] * u[k]) * F.scale);
         }
     }
-#pragma unroll
-    for (int w = 0; w < MOM_WORDS; ++w) a[w] = wave_sum(a[w]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int w = 0; w < MOM_WORDS; ++w) s_a[threadIdx.x >> 6][w] = a[w];
-    }
-    __syncthreads();
-    if (threadIdx.x < MOM_WORDS) {
-        unsigned long long s = 0;
-        for (int v = 0; v < MOM_T / 64; ++v) s += s_a[v][threadIdx.x];
-        if (s) atomicAdd(acc + threadIdx.x, s);
-    }
+    mom_flush(a, s_a, acc);
 }
 
-/* B.74: the frame the ten words imply.  Mean and covariance of u in double; the eigenpairs by MOM_SWEEPS cyclic Jacobi sweeps
-   over the pairs (0,1), (0,2), (1,2) -- a pair whose off-diagonal entry is zero is skipped; theta = (a_qq - a_pp) / (2 a_pq),
+/* B.74 behind the mean m and the covariance A of u (A is used up): the eigenpairs by MOM_SWEEPS cyclic Jacobi sweeps over the
+   pairs (0,1), (0,2), (1,2) -- a pair whose off-diagonal entry is zero is skipped; theta = (a_qq - a_pp) / (2 a_pq),
    t = sgn(theta) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0,
    the third index r: (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq), every row k of V likewise -- + - * / and sqrt, one
    rounding per written operation; eigenvalues descending, a tie to the lower original column; the first two axes signed so
-   that the component of largest magnitude is positive (the lowest index on a tie), the third their cross product.
-   false: no point, or L not finite and > 0. */
-inline bool cloud_frame_from_words(const long long *words, int ms, const double *c, double L, ppp_cloud_frame *f)
+   that the component of largest magnitude is positive (the lowest index on a tie), the third their cross product; mean =
+   c + L m, eigenvalues = (lambda L) L.  Both the points' frame (cloud_frame_from_words) and the surface's
+   (mesh_frame_from_words, ppp_mesh_registration.h) end here. */
+inline void frame_from_mean_cov(const double *m, double (*A)[3], const double *c, double L, ppp_cloud_frame *f)
 {
-    if (words[0] <= 0 || !(L > 0.0) || !(L < INFINITY) || ms < 0 || ms > 62) return false;
-    f->count = (size_t)words[0]; f->ms = ms; f->L = L;
-    for (int d = 0; d < 3; ++d) f->c[d] = c[d];
-    for (int w = 0; w < MOM_WORDS; ++w) f->words[w] = words[w];
-    double inv = 1.0;
-    for (int i = 0; i < ms; ++i) inv = inv * 0.5; /* 2^-ms */
-    const double cnt = (double)words[0];
-    double m[3], A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int d = 0; d < 3; ++d) m[d] = ((double)words[1 + d] / cnt) * inv;
-    for (int d = 0, w = 4; d < 3; ++d)
-        for (int k = d; k < 3; ++k, ++w) A[d][k] = A[k][d] = ((double)words[w] / cnt) * inv - m[d] * m[k];
+    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     static const int PQ[3][3] = {{0, 1, 2}, {0, 2, 1}, {1, 2, 0}};
     for (int sweep = 0; sweep < MOM_SWEEPS; ++sweep)
         for (int e = 0; e < 3; ++e) {
@@ -431,6 +429,24 @@ inline bool cloud_frame_from_words(const long long *words, int ms, const double 
         f->eigenvalues[d] = (A[ord[d]][ord[d]] * L) * L;
         for (int k = 0; k < 3; ++k) f->axes[3 * d + k] = ax[k][d];
     }
+}
+
+/* B.74: the frame the ten words of a cloud's points imply: mean and covariance of u in double, then frame_from_mean_cov.
+   false: no point, or L not finite and > 0. */
+inline bool cloud_frame_from_words(const long long *words, int ms, const double *c, double L, ppp_cloud_frame *f)
+{
+    if (words[0] <= 0 || !(L > 0.0) || !(L < INFINITY) || ms < 0 || ms > 62) return false;
+    f->count = (size_t)words[0]; f->ms = ms; f->L = L;
+    for (int d = 0; d < 3; ++d) f->c[d] = c[d];
+    for (int w = 0; w < MOM_WORDS; ++w) f->words[w] = words[w];
+    double inv = 1.0;
+    for (int i = 0; i < ms; ++i) inv = inv * 0.5; /* 2^-ms */
+    const double cnt = (double)words[0];
+    double m[3], A[3][3];
+    for (int d = 0; d < 3; ++d) m[d] = ((double)words[1 + d] / cnt) * inv;
+    for (int d = 0, w = 4; d < 3; ++d)
+        for (int k = d; k < 3; ++k, ++w) A[d][k] = A[k][d] = ((double)words[w] / cnt) * inv - m[d] * m[k];
+    frame_from_mean_cov(m, A, c, L, f);
     return true;
 }
 

@@ -669,6 +669,116 @@ void ppp_default_global_registration_params(ppp_global_registration_params *gp)
     ppp_default_registration_params(&gp->fine);
 }
 
+/* What ppp_register_global and ppp_register_mesh_global have in common on either side of their coarse launches (w: the call's
+   name).  global_params_ok: the refusals for the caller's arrays and for gp; F and Ffine take what the two parameter sets set.
+   coarse_open: the starts the two frames imply (B.75), room for K chains in h->registration's buffers, the queries compacted
+   once (StrideSel), the words and the control blocks cleared on h's stream, every chain's start at its head.  coarse_collect: the
+   one wait, the sanity checks, the candidate table with B.76's cost, the winner and second_cost.  global_results: the
+   statistics behind the fine chain and the caller's share of the table. */
+struct CoarseStage {
+    int K = 0, iterations = 0, nq = 0;
+    size_t evals = 0, tstride = 0, astride = 0;
+    std::vector<double> T, T0;
+    IcpCtl *ctl = nullptr;
+    std::vector<ppp_registration_candidate> cands;
+    int winner = 0;
+    long long second = -1;
+};
+
+static int global_params_ok(ppp_handle h, const std::string &w, const ppp_global_registration_params &P, const void *cands, size_t cand_cap,
+                            const void *rows, size_t row_cap, IcpFrame &F, IcpFrame &Ffine)
+{
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, w + ": rows is NULL with row_cap > 0");
+    if (!cands && cand_cap) return fail(h, PPP_ERR_ARG, w + ": cands is NULL with cand_cap > 0");
+    if (P.candidates != 4 && P.candidates != 24) return fail(h, PPP_ERR_ARG, w + ": candidates must be 4 or 24");
+    if (P.stride < 1) return fail(h, PPP_ERR_ARG, w + ": stride must be >= 1");
+    const int rc = registration_params_ok(h, P.coarse, F);
+    return rc ? rc : registration_params_ok(h, P.fine, Ffine);
+}
+
+static int coarse_open(ppp_handle h, const std::string &w, const ppp_global_registration_params &P, const ppp_cloud_frame &scan, const ppp_cloud_frame &ref,
+                       CoarseStage &S)
+{
+    const int K = S.K = P.candidates;
+    S.iterations = P.coarse.iterations;
+    const size_t evals = S.evals = (size_t)S.iterations + 1;
+    S.tstride = 12 * evals; S.astride = ICP_WORDS * evals;
+    S.T.assign((size_t)K * evals * 12, 0.0); S.T0.resize((size_t)K * 12);
+    registration_starts(&scan, &ref, K, S.T0.data());
+    for (double v : S.T0) if (!std::isfinite(v)) return fail(h, PPP_ERR_ARG, w + ": a start has an entry that is not finite");
+    for (int s = 0; s < K; ++s) memcpy(&S.T[(size_t)s * evals * 12], &S.T0[(size_t)s * 12], 12 * sizeof(double));
+    const int ns = h->hmeta.n_sorted;
+    auto &G = h->registration;
+    const size_t ns1 = (size_t)std::max(ns, 1);
+    HIPCHK(h, G.queries.ensure(ns1)); HIPCHK(h, G.qcnt.ensure((ns1 + COMPACT_CHUNK - 1) / COMPACT_CHUNK + 1));
+    HIPCHK(h, G.mT.ensure(S.T.size())); HIPCHK(h, G.macc.ensure(ICP_WORDS * evals * K)); HIPCHK(h, G.mrows.ensure(evals * K)); HIPCHK(h, G.mctl.ensure(5 * (size_t)K));
+    int nq = 0;
+    if (ns > 0) {
+        const int nblocks = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
+        StrideSel sel = {h->sorted4.p, P.stride, G.queries.p};
+        const int rc = compact(h, sel, ns, G.qcnt.p, G.qcnt.p + nblocks, [&](int kept) -> int {
+            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, w + ": query count corrupt");
+            nq = kept;
+            return PPP_OK;
+        });
+        if (rc) return rc;
+    }
+    if (nq <= 0) return fail(h, PPP_ERR_ARG, w + ": no query left (no indexed point has a cloud index that is a multiple of stride)");
+    S.nq = nq;
+    HIPCHK(h, hipMemsetAsync(G.macc.p, 0, ICP_WORDS * evals * K * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.mctl.p, 0, 5 * (size_t)K * sizeof(int), h->stream));
+    HIPCHK(h, copy_sync(h, G.mT.p, S.T.data(), S.T.size() * sizeof(double), hipMemcpyHostToDevice));
+    S.ctl = reinterpret_cast<IcpCtl *>(G.mctl.p);
+    return PPP_OK;
+}
+
+static int coarse_collect(ppp_handle h, const std::string &w, const IcpFrame &F, CoarseStage &S)
+{
+    const int K = S.K, nq = S.nq;
+    const size_t evals = S.evals;
+    auto &G = h->registration;
+    std::vector<IcpCtl> C((size_t)K);
+    std::vector<ppp_registration_row> R(evals * K);
+    std::vector<unsigned long long> acc(ICP_WORDS * evals * K);
+    HIPCHK(h, copy_sync(h, C.data(), G.mctl.p, C.size() * sizeof(IcpCtl), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, R.data(), G.mrows.p, R.size() * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, acc.data(), G.macc.p, acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, copy_sync(h, S.T.data(), G.mT.p, S.T.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const long long far = llrint((double)F.md2 * F.scale);
+    std::vector<ppp_registration_candidate> &cd = S.cands;
+    cd.assign((size_t)K, ppp_registration_candidate{});
+    int win = 0;
+    for (int s = 0; s < K; ++s) {
+        const IcpCtl &c = C[(size_t)s];
+        if (!chain_ctl_ok(c, S.iterations)) return fail(h, PPP_ERR_HIP, w + ": control words corrupt");
+        const size_t first = (size_t)s * evals, last = first + (size_t)c.steps;
+        if (!c.done) icp_row_terms(&R[last], &S.T[12 * last], &acc[ICP_WORDS * last]); /* the evaluation behind the last step: no step kernel follows it */
+        if (R[first].pairs > (size_t)nq || R[last].pairs > (size_t)nq) return fail(h, PPP_ERR_HIP, w + ": sums corrupt");
+        ppp_registration_candidate &o = cd[(size_t)s];
+        o.index = s;
+        memcpy(o.T0, &S.T0[12 * (size_t)s], sizeof(o.T0)); memcpy(o.T, R[last].T, sizeof(o.T));
+        o.steps = c.steps; o.converged = c.converged; o.locked = c.locked;
+        o.pairs0 = R[first].pairs; o.E0 = R[first].E; o.pairs = R[last].pairs; o.E = R[last].E;
+        o.cost = o.E + (long long)((size_t)nq - o.pairs) * far;
+        if (o.cost < cd[(size_t)win].cost) win = s;
+    }
+    long long second = -1;
+    for (int s = 0; s < K; ++s)
+        if (memcmp(cd[(size_t)s].T, cd[(size_t)win].T, sizeof(cd[0].T)) != 0 && (second < 0 || cd[(size_t)s].cost < second)) second = cd[(size_t)s].cost;
+    S.winner = win; S.second = second;
+    return PPP_OK;
+}
+
+static void global_results(const CoarseStage &S, int shift, ppp_global_registration_stats &st, ppp_global_registration_stats *stats,
+                           ppp_registration_candidate *cands, size_t cand_cap)
+{
+    st.queries = (size_t)S.nq; st.shift = shift; st.candidates = S.K; st.winner = S.winner;
+    st.winner_cost = S.cands[(size_t)S.winner].cost; st.second_cost = S.second;
+    if (stats) *stats = st;
+    const size_t k = std::min(cand_cap, (size_t)S.K);
+    if (cands && k) memcpy(cands, S.cands.data(), k * sizeof(ppp_registration_candidate));
+}
+
 /* Global registration: both clouds' moments, the starts their frames imply, then every start's coarse chain
    side by side -- coarse.iterations + 1 launches of k_reg_terms_multi and coarse.iterations of k_reg_step_multi back to back
    on h's stream, on the queries compacted once -- one wait, the winner by cost on the host, and registration_chain from it. */
@@ -678,15 +788,9 @@ int ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registrat
     if (!h) return PPP_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     if (!ref || !gp) return fail(h, PPP_ERR_ARG, "global registration: no reference handle or no parameters");
-    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, "global registration: rows is NULL with row_cap > 0");
-    if (!cands && cand_cap) return fail(h, PPP_ERR_ARG, "global registration: cands is NULL with cand_cap > 0");
     const ppp_global_registration_params P = *gp;
-    if (P.candidates != 4 && P.candidates != 24) return fail(h, PPP_ERR_ARG, "global registration: candidates must be 4 or 24");
-    if (P.stride < 1) return fail(h, PPP_ERR_ARG, "global registration: stride must be >= 1");
     IcpFrame F, Ffine;
-    int rc = registration_params_ok(h, P.coarse, F);
-    if (rc) return rc;
-    rc = registration_params_ok(h, P.fine, Ffine);
+    int rc = global_params_ok(h, "global registration", P, cands, cand_cap, rows, row_cap, F, Ffine);
     if (rc) return rc;
     int shift = 0;
     rc = registration_setup(h, ref, P.coarse, F, shift);
@@ -698,78 +802,25 @@ int ppp_register_global(ppp_handle h, ppp_handle ref, const ppp_global_registrat
     if (rc) return rc;
     if (ref == h) st.ref = st.scan;
     else { rc = cloud_moments(h, ref, "the reference", &st.ref); if (rc) return rc; }
-    const int K = P.candidates, iterations = P.coarse.iterations;
-    const size_t evals = (size_t)iterations + 1;
-    std::vector<double> T((size_t)K * evals * 12, 0.0), T0((size_t)K * 12);
-    registration_starts(&st.scan, &st.ref, K, T0.data());
-    for (double v : T0) if (!std::isfinite(v)) return fail(h, PPP_ERR_ARG, "global registration: a start has an entry that is not finite");
-    for (int s = 0; s < K; ++s) memcpy(&T[(size_t)s * evals * 12], &T0[(size_t)s * 12], 12 * sizeof(double));
-    const int ns = h->hmeta.n_sorted, nref = ref->hmeta.n_sorted;
+    CoarseStage S;
+    rc = coarse_open(h, "global registration", P, st.scan, st.ref, S);
+    if (rc) return rc;
+    const int K = S.K, nq = S.nq, nref = ref->hmeta.n_sorted;
     auto &G = h->registration;
-    const size_t ns1 = (size_t)std::max(ns, 1);
-    HIPCHK(h, G.queries.ensure(ns1)); HIPCHK(h, G.qcnt.ensure((ns1 + COMPACT_CHUNK - 1) / COMPACT_CHUNK + 1));
-    HIPCHK(h, G.mT.ensure(T.size())); HIPCHK(h, G.macc.ensure(ICP_WORDS * evals * K)); HIPCHK(h, G.mrows.ensure(evals * K)); HIPCHK(h, G.mctl.ensure(5 * (size_t)K));
-    int nq = 0;
-    if (ns > 0) {
-        const int nblocks = (ns + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
-        StrideSel sel = {h->sorted4.p, P.stride, G.queries.p};
-        rc = compact(h, sel, ns, G.qcnt.p, G.qcnt.p + nblocks, [&](int kept) -> int {
-            if (kept < 0 || kept > ns) return fail(h, PPP_ERR_HIP, "global registration: query count corrupt");
-            nq = kept;
-            return PPP_OK;
-        });
-        if (rc) return rc;
-    }
-    if (nq <= 0) return fail(h, PPP_ERR_ARG, "global registration: no query left (no indexed point has a cloud index that is a multiple of stride)");
-    HIPCHK(h, hipMemsetAsync(G.macc.p, 0, ICP_WORDS * evals * K * sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(G.mctl.p, 0, 5 * (size_t)K * sizeof(int), h->stream));
-    HIPCHK(h, copy_sync(h, G.mT.p, T.data(), T.size() * sizeof(double), hipMemcpyHostToDevice));
-    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.mctl.p);
     /* all starts together stay at two workgroups per CU, and never below one per start */
     const size_t per = std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, 2 * (size_t)h->num_cus / (size_t)K));
-    const size_t tstride = 12 * evals, astride = ICP_WORDS * evals;
-    for (int k = 0; k <= iterations; ++k) {
+    for (int k = 0; k <= S.iterations; ++k) {
         LAUNCH(h, "k_reg_terms_multi", k_reg_terms_multi, dim3((unsigned)per, (unsigned)K), ICP_T, 0, G.queries.p, nq, contact_index(ref), nref, F,
-               G.mT.p + 12 * (size_t)k, tstride, ctl, G.macc.p + ICP_WORDS * (size_t)k, astride);
-        if (k < iterations)
-            LAUNCH(h, "k_reg_step_multi", k_reg_step_multi, K, 64, 0, G.macc.p + ICP_WORDS * (size_t)k, astride, F, G.mT.p + 12 * (size_t)k, tstride,
-                   G.mrows.p + k, evals, ctl);
+               G.mT.p + 12 * (size_t)k, S.tstride, S.ctl, G.macc.p + ICP_WORDS * (size_t)k, S.astride);
+        if (k < S.iterations)
+            LAUNCH(h, "k_reg_step_multi", k_reg_step_multi, K, 64, 0, G.macc.p + ICP_WORDS * (size_t)k, S.astride, F, G.mT.p + 12 * (size_t)k, S.tstride,
+                   G.mrows.p + k, S.evals, S.ctl);
     }
-    std::vector<IcpCtl> C((size_t)K);
-    std::vector<ppp_registration_row> R(evals * K);
-    std::vector<unsigned long long> acc(ICP_WORDS * evals * K);
-    HIPCHK(h, copy_sync(h, C.data(), G.mctl.p, C.size() * sizeof(IcpCtl), hipMemcpyDeviceToHost)); /* the one wait */
-    HIPCHK(h, copy_sync(h, R.data(), G.mrows.p, R.size() * sizeof(ppp_registration_row), hipMemcpyDeviceToHost));
-    HIPCHK(h, copy_sync(h, acc.data(), G.macc.p, acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(h, copy_sync(h, T.data(), G.mT.p, T.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const long long far = llrint((double)F.md2 * F.scale);
-    std::vector<ppp_registration_candidate> cd((size_t)K);
-    int win = 0;
-    for (int s = 0; s < K; ++s) {
-        const IcpCtl &c = C[(size_t)s];
-        if (!chain_ctl_ok(c, iterations)) return fail(h, PPP_ERR_HIP, "global registration: control words corrupt");
-        const size_t first = (size_t)s * evals, last = first + (size_t)c.steps;
-        if (!c.done) icp_row_terms(&R[last], &T[12 * last], &acc[ICP_WORDS * last]); /* the evaluation behind the last step: no step kernel follows it */
-        if (R[first].pairs > (size_t)nq || R[last].pairs > (size_t)nq) return fail(h, PPP_ERR_HIP, "global registration: sums corrupt");
-        ppp_registration_candidate &o = cd[(size_t)s];
-        o = ppp_registration_candidate{};
-        o.index = s;
-        memcpy(o.T0, &T0[12 * (size_t)s], sizeof(o.T0)); memcpy(o.T, R[last].T, sizeof(o.T));
-        o.steps = c.steps; o.converged = c.converged; o.locked = c.locked;
-        o.pairs0 = R[first].pairs; o.E0 = R[first].E; o.pairs = R[last].pairs; o.E = R[last].E;
-        o.cost = o.E + (long long)((size_t)nq - o.pairs) * far;
-        if (o.cost < cd[(size_t)win].cost) win = s;
-    }
-    long long second = -1;
-    for (int s = 0; s < K; ++s)
-        if (memcmp(cd[(size_t)s].T, cd[(size_t)win].T, sizeof(cd[0].T)) != 0 && (second < 0 || cd[(size_t)s].cost < second)) second = cd[(size_t)s].cost;
-    rc = registration_chain(h, ref, &P.fine, cd[(size_t)win].T, true, rows, row_cap, &st.fine);
+    rc = coarse_collect(h, "global registration", F, S);
     if (rc) return rc;
-    st.queries = (size_t)nq; st.shift = shift; st.candidates = K; st.winner = win;
-    st.winner_cost = cd[(size_t)win].cost; st.second_cost = second;
-    if (stats) *stats = st;
-    const size_t k = std::min(cand_cap, (size_t)K);
-    if (cands && k) memcpy(cands, cd.data(), k * sizeof(ppp_registration_candidate));
+    rc = registration_chain(h, ref, &P.fine, S.cands[(size_t)S.winner].T, true, rows, row_cap, &st.fine);
+    if (rc) return rc;
+    global_results(S, shift, st, stats, cands, cand_cap);
     return PPP_OK;
 }
 
@@ -1642,7 +1693,7 @@ int ppp_register_robust_tiles(const ppp_handle *hs, const ppp_handle *refs, size
 
 /* The mesh owns its buffers and a stream of its own: after ppp_trimesh_create it needs neither the handle nor any cloud. */
 struct ppp_trimesh_s {
-    int device = 0;
+    int device = 0, num_cus = 1;
     hipStream_t stream = nullptr;
     DevBuf<TriRec> rec;
     DevBuf<unsigned> cell_start;
@@ -1650,6 +1701,9 @@ struct ppp_trimesh_s {
     TriGrid G = {};
     int n_tris = 0;
     /* the welded topology (ppp_trimesh_topology.h): built once, by the first call that needs it */
+    /* ppp_trimesh_get_moments: the ten words, and the lock its callers take turns under */
+    std::mutex mom_lock;
+    DevBuf<unsigned long long> mom;
     std::mutex topo_lock;
     bool topo_built = false;
     ppp_trimesh_topology_stats topo_stats = {};
@@ -1717,7 +1771,7 @@ int ppp_trimesh_create(ppp_handle h, const float *verts, size_t n_verts, const i
     if (n_tris > TRIMESH_MAX || n_verts > TRIMESH_MAX) return fail(h, PPP_ERR_CAPACITY, "trimesh: mesh too large");
     HIPCHK(h, hipSetDevice(h->device));
     std::unique_ptr<ppp_trimesh_s> m(new ppp_trimesh_s);
-    m->device = h->device;
+    m->device = h->device; m->num_cus = h->num_cus;
     ppp_trimesh_stats st = {};
     st.triangles = n_tris;
     DevBuf<char> raw, tmp;
@@ -2134,6 +2188,26 @@ int ppp_get_mesh_signed_deviation(ppp_handle h, ppp_trimesh m, const ppp_deviati
     return mesh_deviation(h, m, dp, &sign, signed_distance, smoothed, distance, tri_index, region, status, target, cap, nullptr);
 }
 
+/* What a chain against the mesh needs before its first launch (w: the call's name): the mesh on the handle's device, the
+   scan's slab index, ppp_register's shift (B.68), and the rest of F from the mesh's box (B.126). */
+static void mesh_box_floats(const TriGrid &M, float *mn, float *mx)
+{
+    for (int d = 0; d < 3; ++d) { mn[d] = (float)M.mn[d]; mx[d] = (float)M.mx[d]; } /* (floats, widened: exact) */
+}
+
+static int mesh_registration_setup(ppp_handle h, ppp_trimesh m, const char *w, const ppp_registration_params &P, IcpFrame &F, int &shift)
+{
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, std::string(w) + ": the mesh is on another device than the handle");
+    const int rc = deviation_side(h, h, "the scan", w);
+    if (rc) return rc;
+    shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, std::string(w) + ": fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    float mn[3], mx[3];
+    mesh_box_floats(m->G, mn, mx);
+    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    return PPP_OK;
+}
+
 /* The mesh registration chain: registration_chain's shape with the mesh in the reference's place -- the scan's
    slab index, then iterations + 1 evaluations (k_mesh_reg_search and k_mesh_reg_sum; k_mesh_reg_terms in a fused build) and iterations steps (k_reg_step, unchanged) back to back on the
    scan's stream, in h->registration's buffers, and one wait.  The mesh is read-only since its create call waited: nothing to
@@ -2153,14 +2227,10 @@ static int mesh_registration_chain(ppp_handle h, ppp_trimesh m, const ppp_regist
     double T[12];
     rc = opening_transform(h, "mesh registration", T0, T);
     if (rc) return rc;
-    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "mesh registration: the mesh is on another device than the handle");
-    rc = deviation_side(h, h, "the scan", "mesh registration");
+    int shift = 0;
+    rc = mesh_registration_setup(h, m, "mesh registration", P, F, shift);
     if (rc) return rc;
-    const int shift = icp_shift(h->n, F.md2);
-    if (shift < 16) return fail(h, PPP_ERR_ARG, "mesh registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
     const TriGrid &M = m->G;
-    const float mn[3] = {(float)M.mn[0], (float)M.mn[1], (float)M.mn[2]}, mx[3] = {(float)M.mx[0], (float)M.mx[1], (float)M.mx[2]}; /* (floats, widened: exact) */
-    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
     const double md2 = (double)P.max_dist * (double)P.max_dist;
     const size_t N = h->n;
     const int nq = h->hmeta.n_sorted;
@@ -2210,6 +2280,130 @@ int ppp_register_mesh(ppp_handle h, ppp_trimesh m, const ppp_registration_params
     return mesh_registration_chain(h, m, rp, T0_12, true, rows, row_cap, stats);
 }
 
+/* The area moments of the mesh.  mesh_moments_frame: the centre, the length and the fixed point of B.135
+   from the mesh's box; mesh_moments_result: the frame the ten words imply.  ppp_trimesh_get_moments runs k_mesh_moments on the
+   mesh's own stream into the mesh's own ten words, under a lock (calls on one mesh from several threads take turns), and waits
+   once; no handle: an error is its code.  ppp_register_mesh_global runs the same kernel on h's stream into h's words, under h's
+   kernel timers (handle_mesh_moments): the mesh is read-only, so either stream gives the same words. */
+static bool mesh_moments_frame(ppp_trimesh m, MomFrame &F, int &ms)
+{
+    ms = mesh_mom_shift((size_t)m->n_tris);
+    float mn[3], mx[3];
+    mesh_box_floats(m->G, mn, mx);
+    frame_from_bounds(mn, mx, 0.0, ms, F.c, &F.L, &F.scale); /* (+ 0.0 changes no bit of an extent) */
+    return F.L > 0.0 && std::isfinite(F.L);
+}
+
+static unsigned mesh_moments_grid(ppp_trimesh m, int num_cus)
+{
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)m->G.indexed + MOM_T - 1) / MOM_T, 2 * (size_t)num_cus));
+}
+
+static bool mesh_moments_result(ppp_trimesh m, const unsigned long long *acc, const MomFrame &F, int ms, ppp_cloud_frame *frame)
+{
+    long long words[MOM_WORDS];
+    for (int i = 0; i < MOM_WORDS; ++i) words[i] = (long long)acc[i];
+    return mesh_frame_from_words(words, (size_t)m->G.indexed, ms, F.c, F.L, frame);
+}
+
+int ppp_trimesh_get_moments(ppp_trimesh m, ppp_cloud_frame *frame)
+{
+    if (!m || !frame) return PPP_ERR_ARG;
+    MomFrame F;
+    int ms = 0;
+    if (!mesh_moments_frame(m, F, ms)) return PPP_ERR_ARG;
+    unsigned long long acc[MOM_WORDS];
+    {
+        std::lock_guard<std::mutex> lock(m->mom_lock);
+        if (hipSetDevice(m->device) != hipSuccess || m->mom.ensure(MOM_WORDS) != hipSuccess) return PPP_ERR_HIP;
+        if (hipMemsetAsync(m->mom.p, 0, sizeof(acc), m->stream) != hipSuccess) return PPP_ERR_HIP;
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(k_mesh_moments, dim3(mesh_moments_grid(m, m->num_cus)), dim3(MOM_T), 0, m->stream, m->G, F, m->mom.p);
+        if (hipGetLastError() != hipSuccess) return PPP_ERR_HIP;
+        if (hipMemcpyAsync(acc, m->mom.p, sizeof(acc), hipMemcpyDeviceToHost, m->stream) != hipSuccess) return PPP_ERR_HIP;
+        if (hipStreamSynchronize(m->stream) != hipSuccess) return PPP_ERR_HIP;
+    }
+    return mesh_moments_result(m, acc, F, ms, frame) ? PPP_OK : PPP_ERR_ARG;
+}
+
+/* the mesh's area frame for a call on h (w: its name): k_mesh_moments on h's stream into h's ten words, one wait */
+static int handle_mesh_moments(ppp_handle h, ppp_trimesh m, const std::string &w, ppp_cloud_frame *frame)
+{
+    MomFrame F;
+    int ms = 0;
+    if (!mesh_moments_frame(m, F, ms)) return fail(h, PPP_ERR_ARG, w + ": the box of the mesh has no extent (L == 0)");
+    auto &G = h->registration;
+    HIPCHK(h, G.mom.ensure(MOM_WORDS));
+    HIPCHK(h, hipMemsetAsync(G.mom.p, 0, MOM_WORDS * sizeof(unsigned long long), h->stream));
+    LAUNCH(h, "k_mesh_moments", k_mesh_moments, mesh_moments_grid(m, h->num_cus), MOM_T, 0, m->G, F, G.mom.p);
+    unsigned long long acc[MOM_WORDS];
+    HIPCHK(h, copy_sync(h, acc, G.mom.p, sizeof(acc), hipMemcpyDeviceToHost));
+    if (!mesh_moments_result(m, acc, F, ms, frame))
+        return fail(h, PPP_ERR_ARG, w + ": the mesh has no area at its moments' fixed point (W0 <= 0)");
+    return PPP_OK;
+}
+
+int ppp_mesh_frame_from_moments(const long long *words10, int ms, const double *c3, double L, ppp_cloud_frame *frame)
+{
+    if (!words10 || !c3 || !frame) return PPP_ERR_ARG;
+    return mesh_frame_from_words(words10, 0, ms, c3, L, frame) ? PPP_OK : PPP_ERR_ARG; /* (the words do not hold the count) */
+}
+
+/* Global registration to the mesh: ppp_register_global's shape with the mesh in the reference's place -- the
+   scan's point moments and the mesh's area moments, the starts the two frames imply, then every start's coarse chain side by
+   side: coarse.iterations + 1 launches each of k_mesh_reg_search_multi and k_mesh_reg_sum_multi and coarse.iterations of
+   k_reg_step_multi back to back on h's stream, on the queries compacted once -- one wait, the winner by cost on the host, and
+   mesh_registration_chain from it. */
+int ppp_register_mesh_global(ppp_handle h, ppp_trimesh m, const ppp_global_registration_params *gp, ppp_registration_candidate *cands, size_t cand_cap,
+                             ppp_registration_row *rows, size_t row_cap, ppp_global_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const char *w = "mesh global registration";
+    if (!m || !gp) return fail(h, PPP_ERR_ARG, std::string(w) + ": no mesh or no parameters");
+    const ppp_global_registration_params P = *gp;
+    IcpFrame F, Ffine;
+    int rc = global_params_ok(h, w, P, cands, cand_cap, rows, row_cap, F, Ffine);
+    if (rc) return rc;
+    int shift = 0;
+    rc = mesh_registration_setup(h, m, w, P.coarse, F, shift);
+    if (rc) return rc;
+    if (icp_shift(h->n, Ffine.md2) < 16)
+        return fail(h, PPP_ERR_ARG, std::string(w) + ": fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    ppp_global_registration_stats st = {};
+    rc = cloud_moments(h, h, "the scan", &st.scan);
+    if (rc) return rc;
+    rc = handle_mesh_moments(h, m, w, &st.ref);
+    if (rc) return rc;
+    CoarseStage S;
+    rc = coarse_open(h, w, P, st.scan, st.ref, S);
+    if (rc) return rc;
+    const int K = S.K, nq = S.nq;
+    auto &G = h->registration;
+    const TriGrid &M = m->G;
+    const double md2 = (double)P.coarse.max_dist * (double)P.coarse.max_dist;
+    HIPCHK(h, G.mwin.ensure((size_t)K * (size_t)nq)); /* the winning record per start and query */
+    const unsigned gsearch = (unsigned)(((size_t)nq + TM_T - 1) / TM_T);
+    /* the sum: all starts together under MESH_REG_GRID_CUS workgroups per CU (0: no cap), and never below one per start */
+    const size_t cap = MESH_REG_GRID_CUS ? (size_t)MESH_REG_GRID_CUS * (size_t)h->num_cus / (size_t)K : (size_t)0x7fffffff;
+    const size_t per = std::max<size_t>(1, std::min<size_t>(((size_t)nq + ICP_T - 1) / ICP_T, cap));
+    for (int k = 0; k <= S.iterations; ++k) {
+        LAUNCH(h, "k_mesh_reg_search_multi", k_mesh_reg_search_multi, dim3(gsearch, (unsigned)K), TM_T, 0, (const float4 *)G.queries.p, nq, M, md2,
+               G.mT.p + 12 * (size_t)k, S.tstride, S.ctl, G.mwin.p);
+        LAUNCH(h, "k_mesh_reg_sum_multi", k_mesh_reg_sum_multi, dim3((unsigned)per, (unsigned)K), ICP_T, 0, (const float4 *)G.queries.p, nq, M, F,
+               G.mT.p + 12 * (size_t)k, S.tstride, S.ctl, G.mwin.p, G.macc.p + ICP_WORDS * (size_t)k, S.astride);
+        if (k < S.iterations)
+            LAUNCH(h, "k_reg_step_multi", k_reg_step_multi, K, 64, 0, G.macc.p + ICP_WORDS * (size_t)k, S.astride, F, G.mT.p + 12 * (size_t)k, S.tstride,
+                   G.mrows.p + k, S.evals, S.ctl);
+    }
+    rc = coarse_collect(h, w, F, S);
+    if (rc) return rc;
+    rc = mesh_registration_chain(h, m, &P.fine, S.cands[(size_t)S.winner].T, true, rows, row_cap, &st.fine);
+    if (rc) return rc;
+    global_results(S, shift, st, stats, cands, cand_cap);
+    return PPP_OK;
+}
+
 /* The robust mesh chain: mesh_registration_chain's setup -- the scan's slab index, the frame from the mesh's box,
    ppp_register's shift -- and robust_chain's shape on it: robust_open, then iterations + 1 evaluations (k_mesh_rob_pair, the walk
    paid once; k_mesh_rob_digit0, unless the walk counts the digit itself: MESH_ROB_DIGIT_PASS; k_trim_narrow<1> and <2> at keep 0.5; k_mesh_rob_terms) and
@@ -2234,14 +2428,10 @@ static int mesh_robust_chain(ppp_handle h, ppp_trimesh m, const ppp_robust_regis
     double T[12];
     rc = opening_transform(h, "robust mesh registration", T0, T);
     if (rc) return rc;
-    if (m->device != h->device) return fail(h, PPP_ERR_ARG, "robust mesh registration: the mesh is on another device than the handle");
-    rc = deviation_side(h, h, "the scan", "robust mesh registration");
+    int shift = 0;
+    rc = mesh_registration_setup(h, m, "robust mesh registration", P, F, shift);
     if (rc) return rc;
-    const int shift = icp_shift(h->n, F.md2);
-    if (shift < 16) return fail(h, PPP_ERR_ARG, "robust mesh registration: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
     const TriGrid &M = m->G;
-    const float mn[3] = {(float)M.mn[0], (float)M.mn[1], (float)M.mn[2]}, mx[3] = {(float)M.mx[0], (float)M.mx[1], (float)M.mx[2]}; /* (floats, widened: exact) */
-    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
     const double md2 = (double)P.max_dist * (double)P.max_dist;
     const int nq = h->hmeta.n_sorted;
     const size_t nqs = (size_t)std::max(nq, 0);

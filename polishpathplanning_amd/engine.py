@@ -84,6 +84,7 @@ EXPORTS = [
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
     "ppp_trimesh_topology", "ppp_trimesh_get_topology", "ppp_trimesh_signed_nearest", "ppp_get_mesh_signed_deviation",
     "ppp_get_mesh_registration_terms", "ppp_register_mesh", "ppp_get_mesh_robust_registration_terms", "ppp_register_mesh_robust",
+    "ppp_trimesh_get_moments", "ppp_mesh_frame_from_moments", "ppp_register_mesh_global",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -284,6 +285,10 @@ def lib():
                                                     C.POINTER(MeshSignedDeviationStats)]
         L.ppp_get_mesh_registration_terms.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationStats)]
         L.ppp_register_mesh.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz, C.POINTER(RegistrationStats)]
+        L.ppp_trimesh_get_moments.argtypes = [vp, C.POINTER(CloudFrame)]
+        L.ppp_mesh_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
+        L.ppp_register_mesh_global.argtypes = [vp, vp, C.POINTER(GlobalRegistrationParams), C.POINTER(RegistrationCandidate), sz, C.POINTER(RegistrationRow), sz,
+                                               C.POINTER(GlobalRegistrationStats)]
         L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
         L.ppp_save_stl.argtypes = [C.c_char_p, fp, sz, C.c_int]
         _lib = L
@@ -438,6 +443,16 @@ class TriMesh:
         if rc:
             raise PPPError(rc, "ppp_trimesh_signed_nearest failed")
         return sd[:n], pn[:n], feature[:n], flags[:n], dist[:n], close[:n], dev[:n], tri[:n], region[:n], status[:n]
+
+    def moments(self):
+        """ppp_trimesh_get_moments: the frame dict of the mesh's SURFACE (cloud_moments()'s keys): count is the indexed triangles,
+        words[0] the area in the fixed point 2^ms and the other nine words the area moments, so mesh_frame_from_moments(), not
+        cloud_frame_from_moments(), is what turns these words into the frame"""
+        f = CloudFrame()
+        rc = self.L.ppp_trimesh_get_moments(self.m, C.byref(f))
+        if rc:
+            raise PPPError(rc, "ppp_trimesh_get_moments failed")
+        return _cloud_frame(f)
 
     def close(self):
         if self.m:
@@ -1048,6 +1063,18 @@ def cloud_frame_from_moments(words, ms, c, L):
     rc = lib().ppp_cloud_frame_from_moments(w, int(ms), cc, float(L), C.byref(f))
     if rc:
         raise PPPError(rc, "ppp_cloud_frame_from_moments: bad arguments")
+    return _cloud_frame(f)
+
+
+def mesh_frame_from_moments(words, ms, c, L):
+    """ppp_mesh_frame_from_moments (host only, no device): the frame dict of the ten area words of TriMesh.moments(), their
+    fixed point 2^ms, the box centre c and the length L; count is 0: the words do not hold it"""
+    w = (C.c_longlong * 10)(*[int(v) for v in words])
+    cc = (C.c_double * 3)(*[float(v) for v in c])
+    f = CloudFrame()
+    rc = lib().ppp_mesh_frame_from_moments(w, int(ms), cc, float(L), C.byref(f))
+    if rc:
+        raise PPPError(rc, "ppp_mesh_frame_from_moments: bad arguments")
     return _cloud_frame(f)
 
 
@@ -2076,6 +2103,17 @@ class Engine:
         (10, 8, 1e-3, 1e-9) and (2, 30, 1e-6, 1e-9).  cands: one dict per start (index, T0, T, steps, converged, locked, pairs0,
         pairs, E0, E, cost); rows: the fine chain's; stats: fine (register()'s stats), scan / ref (frame dicts), queries, shift,
         candidates, winner, winner_cost, second_cost"""
+        return self._register_global(self.L.ppp_register_global, ref.h, candidates, stride, coarse, fine)
+
+    def register_mesh_global(self, mesh, candidates=24, stride=16, coarse=None, fine=None):
+        """(T, cands, rows, stats) as register_global() gives them: ppp_register_mesh_global of this engine's cloud, the scan, to
+        the triangles of the TriMesh `mesh` themselves, from the scan and the mesh alone: stats["ref"] is the mesh's area frame
+        (TriMesh.moments()), every coarse chain is register_mesh() with `coarse` on every stride-th point, the fine chain is
+        register_mesh() with `fine` from the cheapest start's end"""
+        m = getattr(mesh, "m", mesh)
+        return self._register_global(self.L.ppp_register_mesh_global, m, candidates, stride, coarse, fine)
+
+    def _register_global(self, call, against, candidates, stride, coarse, fine):
         gp = GlobalRegistrationParams()
         self.L.ppp_default_global_registration_params(C.byref(gp))
         gp.candidates, gp.stride = int(candidates), int(stride)
@@ -2089,7 +2127,7 @@ class Engine:
         cands = (RegistrationCandidate * ncand)()
         rows = (RegistrationRow * cap)()
         st = GlobalRegistrationStats()
-        self._chk(self.L.ppp_register_global(self.h, ref.h, C.byref(gp), cands, ncand, rows, cap, C.byref(st)))
+        self._chk(call(self.h, against, C.byref(gp), cands, ncand, rows, cap, C.byref(st)))
         stats = dict(fine=_registration_stats(st.fine), scan=_cloud_frame(st.scan), ref=_cloud_frame(st.ref), queries=int(st.queries),
                      shift=int(st.shift), candidates=int(st.candidates), winner=int(st.winner), winner_cost=int(st.winner_cost),
                      second_cost=int(st.second_cost))
