@@ -20,6 +20,9 @@
 // ppp_register's lines, and the cloud moved by T; PPP_REGISTER=1 with an STL still registers against its samples.
 // PPP_REGISTER=mesh-robust PPP_DEVIATION=<part.stl> does so under the robust loop's weights (ppp_register_mesh_robust; PPP_REGISTER_TUNE, _SIGMA_MIN): for a scan that shows a
 // clamp or a strip of the table within reach of the part; PPP_REGISTER=robust's lines with the facets' numbers.
+// PPP_REGISTER=mesh-trimmed PPP_DEVIATION=<part.stl> does so under the trimmed loop's cut (ppp_register_mesh_trimmed; PPP_REGISTER_KEEP, default 0.8): for a scan more contaminated than
+// the median bears; PPP_REGISTER_BORDER=reject also drops every pair whose closest point lies on the border of an open mesh (the scan's overhang): a line with the kept, the
+// paired and the on-border counts and the cut before and after, then PPP_REGISTER_KEEP's lines with the facets' numbers.
 // PPP_REGISTER=mesh-global PPP_DEVIATION=<part.stl> registers against the triangles from an unknown pose (ppp_register_mesh_global: the mesh's area frame, the
 // coarse chains and the fine chain on the facets; PPP_REGISTER_CANDIDATES, _STRIDE, _COARSE_MAXDIST): PPP_REGISTER=global's lines with the facets' numbers.
 #include <cstdlib>
@@ -55,6 +58,7 @@ int main(int argc, char **argv)
     if (reference && reg && std::string(reg) == "robust") path_planner.register_robust_to(*reference); /* Tukey weights: no keep to choose */
     if (reference && reg && std::string(reg) == "mesh" && ppp::Planner::is_stl_name(devf)) path_planner.register_to_mesh(devf); /* on the facets, not on their samples */
     if (reference && reg && std::string(reg) == "mesh-robust" && ppp::Planner::is_stl_name(devf)) path_planner.register_robust_to_mesh(devf); /* the facets under Tukey weights */
+    if (reference && reg && std::string(reg) == "mesh-trimmed" && ppp::Planner::is_stl_name(devf)) path_planner.register_trimmed_to_mesh(devf); /* the facets under the cut, the border rejected on request */
     if (reference && reg && std::string(reg) == "mesh-global" && ppp::Planner::is_stl_name(devf)) path_planner.register_global_to_mesh(devf); /* the facets, from an unknown pose */
     path_planner.GenPath();
     path_planner.getPath();

@@ -729,9 +729,9 @@ int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *r
                 a mesh made with either orientation gives the same rows
    Solve, step, composition, the loop's endings, rows and stats are ppp_register's.  On an edge or a vertex the normal is the
    winning facet's (pseudonormals are out of scope), and the scan's overhang beyond an open mesh's border pairs there with the
-   border facet's normal as long as it lies within max_dist (no pair is rejected on the border).  Robust weights are
-   ppp_register_mesh_robust's (below), the start from an unknown pose is ppp_register_mesh_global's (further down); trimmed weights
-   and tiles over slice ranges are not offered.
+   border facet's normal as long as it lies within max_dist (no pair is rejected on the border here).  Robust weights are
+   ppp_register_mesh_robust's, trimmed weights and the rejection of border pairs ppp_register_mesh_trimmed's (both below), the
+   start from an unknown pose is ppp_register_mesh_global's (further down); tiles over slice ranges are not offered.
    ppp_get_mesh_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; ppp_register_mesh runs the loop
    from T0_12; row, rows and stats are filled as ppp_get_registration_terms and ppp_register fill them.  Both build h's slab index
    where it is missing, enqueue the whole chain (iterations + 1 evaluations, iterations steps) on h's stream and wait once; the
@@ -869,8 +869,9 @@ int  ppp_register_robust(ppp_handle h, ppp_handle ref, const ppp_robust_registra
    tune == +INFINITY weighs every pair 1: rows[k].row, T and stats are ppp_register_mesh's bits from the same start.  Every
    output is the same for every grid cell of the mesh, and the same bits in every run.  The estimator's limit is
    ppp_register_robust's: the median residual must belong to the part that shows the mesh (with 35 % of the scan raised by 1.5 mm
-   it does not, and the fit stays tilted).  Trimmed weights, tiles over slice ranges, pseudonormals and
-   border rejection are not offered; the start from an unknown pose is ppp_register_mesh_global's (further down).
+   it does not, and the fit stays tilted): there ppp_register_mesh_trimmed (below) with a known keep is the
+   tool, and it rejects border pairs too.  Tiles over slice ranges and pseudonormals are not offered; the start from an unknown
+   pose is ppp_register_mesh_global's (further down).
    ppp_get_mesh_robust_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; its maps are that
    evaluation's.  rows, row, the maps and stats may be NULL (rows with row_cap = 0; the maps with any cap).  The whole chain -- per
    evaluation the grid walk, paid once, with the residual, the key and the top digit's histogram, two passes over the stored
@@ -887,6 +888,68 @@ int  ppp_register_mesh_robust(ppp_handle h, ppp_trimesh m, const ppp_robust_regi
                               ppp_robust_registration_row *rows, size_t row_cap,
                               unsigned char *status, float *weight, double *residual, size_t cap,
                               ppp_registration_stats *stats);
+/* Trimmed registration of a scan to the triangle mesh itself, with border-pair rejection:
+   ppp_register_mesh's candidates on the facets under ppp_register_trimmed's cut, for a scan that is heavily contaminated -- more
+   than the median of ppp_register_mesh_robust bears -- and whose share `keep` that shows the mesh is known; and, with
+   border = PPP_MESH_BORDER_REJECT, for a scan that shows more than an open mesh does: a candidate whose closest point lies on
+   the mesh's border is no pair (Turk and Levoy), whatever its point-to-plane residual against the border facet's extrapolated
+   plane would be.
+     centre, shift, moved, candidate   ppp_register_mesh's, word for word: the frame from the mesh's box; ppp_register's shift,
+                shift < 16 refused; the query is the moved point p' itself, in double; the winner f* is the nearest indexed
+                triangle by (D2, f) with its exact closest point x; a candidate where D2 <= (double)max_dist * (double)max_dist
+                (inclusive), in every region
+     border     PPP_MESH_BORDER_PAIR: every candidate is a pair, as in ppp_register_mesh; no topology is built and on_border is 0.
+                PPP_MESH_BORDER_REJECT: the mesh's welded topology is built where it is missing, as
+                ppp_get_mesh_signed_deviation builds it; the winner's record is walked once more for the feature x lies on --
+                the same inputs and the same arithmetic, so x, D2 and the region are the walk's bits --; a candidate is NO pair
+                where that feature is a vertex with PPP_VERTEX_BORDER or an edge of class PPP_EDGE_BORDER: exactly where
+                ppp_get_mesh_signed_deviation sets PPP_MESH_SIGN_BORDER.  Its status is PPP_MESH_TRIM_BORDER, its d2 the float
+                NaN 0x7fc00000, it is counted in on_border and is not part of paired.  Inconsistent and non-manifold features
+                are not rejected.  On a mesh whose topology has no border edge _REJECT gives _PAIR's bits
+     key        the bit pattern of (float)D2, the walk's double narrowed once, as a 32-bit unsigned integer: never negative and
+                never NaN, and round-to-nearest is monotone, so the keys order as the distances do; ties are kept together
+     cut        ppp_register_trimmed's: k = ppp_trim_rank(keep, paired), tau = the k-th smallest key through the three digit
+                histograms, KEPT = the pairs with key <= tau, kept >= k; trim_d2 = the float with the bits of tau, the float
+                quiet NaN 0x7fc00000 when paired == 0
+     terms      ppp_register_mesh's 29 words -- q = x, n = N / A2 of f*'s frame, u and J on doubles -- over the KEPT pairs only,
+                row.pairs = kept
+     the rest   solve, step, composition and the loop's endings are ppp_register's with pairs read as kept ("fewer than 6
+                pairs" is kept < 6); stats is ppp_register's with pairs_* = kept and rms_* over the kept pairs
+     maps       status and d2, by cloud index of h, the first min(cap, n) entries, of the LAST evaluation (the one at the
+                result, rows[steps]): PPP_TRIM_DROPPED and NaN for a point that is not finite, PPP_TRIM_UNPAIRED and NaN for one
+                without a candidate (a moved point that is not finite too), PPP_MESH_TRIM_BORDER and NaN for a candidate
+                rejected on the border, else PPP_TRIM_KEPT or PPP_TRIM_TRIMMED and the key's float (every NaN is 0x7fc00000)
+     orientation  PPP_TRIMESH_WINDING or _VIEWPOINT is NOT applied, and need not be, for ppp_register_mesh's reason; the class
+                of an edge with one half-edge does not depend on a direction, so the BORDER set is the same either way
+   With keep == 1 and _PAIR, rows[k].trim.row, T and stats are ppp_register_mesh's bits from the same start.  Every output is the
+   same for every grid cell of the mesh, and the same bits in every run.  Tiles over slice ranges and pseudonormals inside the
+   loop are not offered; the start from an unknown pose is ppp_register_mesh_global's (further down).
+   ppp_get_mesh_trimmed_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; its maps are that
+   evaluation's.  rows, row, the maps and stats may be NULL (rows with row_cap = 0; the maps with any cap).  The whole chain -- per
+   evaluation the grid walk, paid once, with the key, the top digit's histogram, two passes over the stored keys, the sums over
+   the stored winners, the step -- is enqueued at once on h's stream with one wait at its end.  Neither call changes h's cloud,
+   plan or stored results; the mesh gains its topology under _REJECT and is otherwise unchanged.
+   PPP_ERR_ARG: m or mp NULL; rows NULL with row_cap > 0; ppp_register's parameter ranges; keep NaN, <= 0 or > 1; border neither
+   of the two values; a T entry that is not finite; no cloud on h; a mesh on another device than h; shift < 16.
+   PPP_ERR_UNSUPPORTED: a slice-range or a part handle. */
+enum { PPP_MESH_BORDER_PAIR = 0, PPP_MESH_BORDER_REJECT = 1 };
+typedef struct {
+    ppp_trimmed_registration_params trim;   /* ppp_register_trimmed's: icp's four and keep in (0, 1] */
+    int border;                             /* PPP_MESH_BORDER_PAIR (as ppp_register_mesh) or _REJECT */
+} ppp_mesh_trimmed_registration_params;     /* defaults: ppp_default_trimmed_registration_params, PPP_MESH_BORDER_PAIR */
+typedef struct {
+    ppp_trimmed_registration_row trim;      /* row over the KEPT pairs, paired, trim_d2 */
+    size_t on_border;                       /* candidates rejected on the border at row.T; 0 under _PAIR */
+} ppp_mesh_trimmed_registration_row;
+enum { PPP_MESH_TRIM_BORDER = 4 };          /* beside PPP_TRIM_KEPT .. PPP_TRIM_DROPPED, unchanged */
+
+void ppp_default_mesh_trimmed_registration_params(ppp_mesh_trimmed_registration_params *mp);
+int  ppp_get_mesh_trimmed_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp,
+                                             const double *T12, ppp_mesh_trimmed_registration_row *row,
+                                             unsigned char *status, float *d2, size_t cap, ppp_registration_stats *stats);
+int  ppp_register_mesh_trimmed(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp,
+                               const double *T0_12, ppp_mesh_trimmed_registration_row *rows, size_t row_cap,
+                               unsigned char *status, float *d2, size_t cap, ppp_registration_stats *stats);
 /* T applied to the resident cloud: T12 (row-major 3 x 4, NULL: the identity) is rounded to float and every finite point
    becomes m0 x + (m1 y + (m2 z + m3)) per row, pcl::transformPointCloud's arithmetic; a point that is not finite passes
    unchanged.  The cloud has changed: bounds, plan, index and every stored result are withdrawn, as after ppp_trans2center.

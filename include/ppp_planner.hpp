@@ -952,6 +952,64 @@ public:
         if (!ran) st = ppp_registration_stats{};
         return print_robust_registration_lines(st, bp, rows, ran, apply);
     }
+    /* trimmed point-to-plane ICP to the triangles of mesh themselves (ppp_register_mesh_trimmed): register_mesh()'s
+       candidates -- the exact closest point, the facet's own normal -- of which only the share mp.trim.keep with the smallest
+       distance enters an evaluation's sums, for a scan more contaminated than register_mesh_robust()'s median bears; with
+       mp.border == PPP_MESH_BORDER_REJECT a candidate whose closest point lies on the mesh's border is no pair (the scan's
+       overhang beyond an open mesh).  st, T0 and rows as register_trimmed_to()'s, the rows with on_border; status and d2, when
+       asked for, the last evaluation's maps by cloud index (PPP_TRIM_*, PPP_MESH_TRIM_BORDER) */
+    bool register_mesh_trimmed(const TriMesh &mesh, ppp_registration_stats &st, const ppp_mesh_trimmed_registration_params &mp, const double *T0 = nullptr,
+                               std::vector<ppp_mesh_trimmed_registration_row> *rows = nullptr, std::vector<unsigned char> *status = nullptr,
+                               std::vector<float> *d2 = nullptr)
+    {
+        if (rows) rows->assign((size_t)(mp.trim.icp.iterations > 0 ? mp.trim.icp.iterations : 0) + 1, ppp_mesh_trimmed_registration_row{});
+        size_t n = 0;
+        if (status || d2) {
+            int rc = ppp_num_points(h_, &n);
+            if (rc != PPP_OK) return report(rc);
+            if (status) status->assign(n, PPP_TRIM_DROPPED);
+            if (d2) d2->assign(n, 0.f);
+        }
+        int rc = ppp_register_mesh_trimmed(h_, mesh.get(), &mp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, status ? status->data() : nullptr,
+                                           d2 ? d2->data() : nullptr, n, &st);
+        if (rc != PPP_OK) { if (rows) rows->clear(); if (status) status->clear(); if (d2) d2->clear(); return report(rc); }
+        if (rows) rows->resize(std::min(rows->size(), (size_t)st.steps + 1));
+        return true;
+    }
+    /* trimmed_registration_params_env() -- keep from PPP_REGISTER_KEEP, 0.8 where it is not set -- with the border rule from
+       PPP_REGISTER_BORDER: "reject" is PPP_MESH_BORDER_REJECT, anything else or unset PPP_MESH_BORDER_PAIR */
+    static ppp_mesh_trimmed_registration_params mesh_trimmed_registration_params_env()
+    {
+        ppp_mesh_trimmed_registration_params mp;
+        ppp_default_mesh_trimmed_registration_params(&mp);
+        mp.trim = trimmed_registration_params_env();
+        const char *v = std::getenv("PPP_REGISTER_BORDER");
+        mp.border = v && std::string(v) == "reject" ? PPP_MESH_BORDER_REJECT : PPP_MESH_BORDER_PAIR;
+        return mp;
+    }
+    /* print_mesh_registration() with the trimmed loop: the grid's line on stderr, register_mesh_trimmed() from the identity, a line
+       with the kept, the paired and the on-border counts and the cut (a distance, mm) before and after, then print_registration()'s
+       lines over the kept pairs and, with apply, the cloud moved */
+    bool print_mesh_trimmed_registration(const std::string &name, const ppp_mesh_trimmed_registration_params &mp, bool apply = true)
+    {
+        TriMesh mesh;
+        ppp_registration_stats st = {};
+        std::vector<ppp_mesh_trimmed_registration_row> rows;
+        const bool ran = open_mesh_for_registration(mesh, name) && register_mesh_trimmed(mesh, st, mp, nullptr, &rows);
+        if (!ran) st = ppp_registration_stats{};
+        const ppp_mesh_trimmed_registration_row none = {};
+        const ppp_mesh_trimmed_registration_row &first = rows.empty() ? none : rows.front(), &last = rows.empty() ? none : rows.back();
+        std::printf("registration: trimmed to the mesh, keep %f, border %s: %zu of %zu pairs kept, %zu on the border, cut %f mm; after %d steps %zu of %zu, "
+                    "%zu on the border, cut %f mm\n", mp.trim.keep, mp.border == PPP_MESH_BORDER_REJECT ? "reject" : "pair", first.trim.row.pairs,
+                    first.trim.paired, first.on_border, first.trim.paired ? std::sqrt((double)first.trim.trim_d2) : 0.0, st.steps, last.trim.row.pairs,
+                    last.trim.paired, last.on_border, last.trim.paired ? std::sqrt((double)last.trim.trim_d2) : 0.0);
+        std::printf("registration: %zu of %zu points kept, rms %f mm; after %d steps %zu kept, rms %f mm\n", st.pairs_before, st.indexed,
+                    st.pairs_before ? st.rms_before : 0.0, st.steps, st.pairs_after, st.pairs_after ? st.rms_after : 0.0);
+        std::printf("registration: %s, locked unknowns 0x%02x (rotation x y z, translation x y z from bit 0)\n",
+                    st.converged ? "converged" : (ran && st.steps == mp.trim.icp.iterations ? "out of iterations" : "no step possible"), st.locked);
+        for (int r = 0; r < 3; ++r) std::printf("registration: T %f %f %f %f\n", st.T[4 * r], st.T[4 * r + 1], st.T[4 * r + 2], st.T[4 * r + 3]);
+        return ran && apply && st.converged && transform_cloud(st.T);
+    }
     /* global registration of this planner's cloud, the scan, to the cloud of ref (ppp_register_global): the starts
        the two clouds' principal frames imply, a coarse chain from each side by side, the fine chain from the cheapest.  st.fine.T
        carries a scan point into ref's frame; cands, when asked for, receives one entry per start.  Needs no pass and no start,

@@ -79,6 +79,10 @@ public:
     /* register_to_mesh() with the robust loop (ppp_register_mesh_robust): the facets' exact geometry under
        register_robust_to()'s weights, tune and sigma_min from the same variables */
     void register_robust_to_mesh(const std::string &stl) { planner.print_mesh_robust_registration(stl, ppp::Planner::robust_registration_params_env()); }
+    /* register_to_mesh() with the trimmed loop (ppp_register_mesh_trimmed): the facets' exact geometry under
+       register_trimmed_to()'s cut, keep from PPP_REGISTER_KEEP (0.8 where it is not set); PPP_REGISTER_BORDER=reject drops the
+       candidates whose closest point lies on the mesh's border: a line with the kept, the paired and the on-border counts and the cut */
+    void register_trimmed_to_mesh(const std::string &stl) { planner.print_mesh_trimmed_registration(stl, ppp::Planner::mesh_trimmed_registration_params_env()); }
     void register_global_to(const RobotPath &ref) { planner.print_global_registration(ref.planner, ppp::Planner::global_registration_params_env()); }
     /* register_global_to() against the triangles of the STL file `stl` themselves (ppp_register_mesh_global): the
        mesh's area frame against the scan's point frame, the coarse chains and the fine chain on the facets; no pitch, no normal field */

@@ -6,8 +6,8 @@
  * doubles) -- as two launches, k_mesh_reg_search and k_mesh_reg_sum, or as the fused k_mesh_reg_terms (MESH_REG_SPLIT).  The step
  * is k_reg_step, unchanged; the host's chain has registration_chain's shape.  Nothing here estimates a normal or knows a pitch:
  * the fit is taken on the facets that ppp_get_mesh_deviation measures against.
- * Robust weights on these pairs are ppp_mesh_robust.h's; trimmed weights, tiles, pseudonormals and border
- * rejection are not offered.
+ * Robust weights on these pairs are ppp_mesh_robust.h's, trimmed weights and border rejection
+ * ppp_mesh_trimmed.h's; tiles and pseudonormals are not offered.
  * The global start from the mesh (ppp_trimesh_get_moments, ppp_register_mesh_global): k_mesh_moments, the ten
  * integer words of the surface's area moments, and mesh_frame_from_words, the frame they imply; k_mesh_reg_search_multi and
  * k_mesh_reg_sum_multi, K chains side by side on the queries StrideSel compacts once, with k_reg_step_multi for the steps.

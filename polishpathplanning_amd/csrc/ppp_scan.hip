@@ -25,6 +25,7 @@
 #include "ppp_trimesh_topology.h"
 #include "ppp_mesh_registration.h"
 #include "ppp_mesh_robust.h"
+#include "ppp_mesh_trimmed.h"
 #include "ppp_sort.h"
 #include <cstring>
 #include <mutex>
@@ -2478,6 +2479,127 @@ int ppp_register_mesh_robust(ppp_handle h, ppp_trimesh m, const ppp_robust_regis
                              ppp_registration_stats *stats)
 {
     return mesh_robust_chain(h, m, bp, T0_12, true, rows, row_cap, status, weight, residual, cap, stats);
+}
+
+void ppp_default_mesh_trimmed_registration_params(ppp_mesh_trimmed_registration_params *mp)
+{
+    if (!mp) return;
+    ppp_default_trimmed_registration_params(&mp->trim);
+    mp->border = PPP_MESH_BORDER_PAIR;
+}
+
+/* The trimmed mesh chain: mesh_registration_chain's setup -- the scan's slab index, the frame from the mesh's box,
+   ppp_register's shift -- and, under PPP_MESH_BORDER_REJECT, the mesh's welded topology where it is missing (on the mesh's stream,
+   waited for: read-only from here on); then registration_chain's trimmed shape on it: iterations + 1 evaluations (k_mesh_trim_pair,
+   the walk paid once; k_mesh_trim_digit0; k_trim_narrow<1> and <2> at keep; k_mesh_trim_terms) and iterations steps (k_reg_step on
+   the kept pairs' 29 words) back to back on the scan's stream, k_mesh_trim_scatter, and chain_collect's one wait.  !loop: the one
+   evaluation of ppp_get_mesh_trimmed_registration_terms. */
+static int mesh_trimmed_chain(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp, const double *T0, bool loop,
+                              ppp_mesh_trimmed_registration_row *rows, size_t row_cap, unsigned char *status, float *d2, size_t cap,
+                              ppp_registration_stats *stats)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const char *w = "trimmed mesh registration";
+    if (!m || !mp) return fail(h, PPP_ERR_ARG, std::string(w) + ": no mesh or no parameters");
+    if (!rows && row_cap) return fail(h, PPP_ERR_ARG, std::string(w) + ": rows is NULL with row_cap > 0");
+    const double keep = mp->trim.keep;
+    if (!(keep > 0.0 && keep <= 1.0)) return fail(h, PPP_ERR_ARG, std::string(w) + ": keep must be in (0, 1]");
+    if (mp->border != PPP_MESH_BORDER_PAIR && mp->border != PPP_MESH_BORDER_REJECT)
+        return fail(h, PPP_ERR_ARG, std::string(w) + ": border must be PPP_MESH_BORDER_PAIR or PPP_MESH_BORDER_REJECT");
+    const bool reject = mp->border == PPP_MESH_BORDER_REJECT;
+    const ppp_registration_params P = mp->trim.icp;
+    IcpFrame F;
+    int rc = registration_params_ok(h, P, F);
+    if (rc) return rc;
+    const int iterations = loop ? P.iterations : 0;
+    double T[12];
+    rc = opening_transform(h, w, T0, T);
+    if (rc) return rc;
+    int shift = 0;
+    rc = mesh_registration_setup(h, m, w, P, F, shift);
+    if (rc) return rc;
+    if (reject) {
+        rc = trimesh_topology_build(m, h);
+        if (rc) return fail(h, rc, std::string(w) + ": the mesh's topology could not be built");
+        HIPCHK(h, hipSetDevice(h->device));
+    }
+    const TriGrid &M = m->G;
+    const TriTopo topo = reject ? m->T : TriTopo{};
+    const double md2 = (double)P.max_dist * (double)P.max_dist;
+    const size_t N = h->n, N1 = std::max<size_t>(N, 1);
+    const int nq = h->hmeta.n_sorted;
+    const size_t nqs = (size_t)std::max(nq, 0);
+    auto &G = h->registration;
+    const size_t evals = (size_t)iterations + 1;
+    rc = chain_open(h, evals, T);
+    if (rc) return rc;
+    static_assert(sizeof(TrimCut) == 8 * sizeof(unsigned), "TrimCut is eight words");
+    HIPCHK(h, G.mwin.ensure(std::max<size_t>(nqs, 1))); HIPCHK(h, G.key.ensure(std::max<size_t>(nqs, 1)));
+    HIPCHK(h, G.hist.ensure(TRIM_WORDS * evals)); HIPCHK(h, G.cuts.ensure(8 * evals));
+    HIPCHK(h, G.tstatus.ensure(N1)); HIPCHK(h, G.td2.ensure(N1));
+    /* every evaluation has histograms and a cut of its own: one clear on the stream before the chain, none between iterations */
+    HIPCHK(h, hipMemsetAsync(G.hist.p, 0, TRIM_WORDS * evals * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.cuts.p, 0, 8 * evals * sizeof(unsigned), h->stream));
+    HIPCHK(h, hipMemsetAsync(G.tstatus.p, PPP_TRIM_DROPPED, N1, h->stream)); /* points outside the index: not finite */
+    HIPCHK(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(G.td2.p), (int)TRIM_NAN, N1, h->stream));
+    IcpCtl *ctl = reinterpret_cast<IcpCtl *>(G.ctl.p);
+    TrimCut *cuts = reinterpret_cast<TrimCut *>(G.cuts.p);
+    const unsigned gpair = (unsigned)std::max<size_t>(1, (nqs + TM_T - 1) / TM_T); /* a thread per query */
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nqs + TRIM_T - 1) / TRIM_T, 2 * (size_t)h->num_cus));
+    /* grid-stride under MESH_TRIM_GRID_CUS workgroups per compute unit (0: a thread per query); the words do not depend on it */
+    const size_t tcap = MESH_TRIM_GRID_CUS ? (size_t)MESH_TRIM_GRID_CUS * (size_t)h->num_cus : (size_t)0x7fffffff;
+    const unsigned gterms = (unsigned)std::max<size_t>(1, std::min<size_t>((nqs + TRIM_T - 1) / TRIM_T, tcap));
+    const float4 *q4 = (const float4 *)h->sorted4.p;
+    for (int k = 0; k <= iterations; ++k) {
+        unsigned *hist = G.hist.p + TRIM_WORDS * (size_t)k;
+        const double *Tk = G.T.p + 12 * (size_t)k;
+        if (reject) LAUNCH(h, "k_mesh_trim_pair<reject>", k_mesh_trim_pair<true>, gpair, TM_T, 0, q4, nq, M, topo, md2, Tk, ctl, G.mwin.p, G.key.p);
+        else LAUNCH(h, "k_mesh_trim_pair<pair>", k_mesh_trim_pair<false>, gpair, TM_T, 0, q4, nq, M, topo, md2, Tk, ctl, G.mwin.p, G.key.p);
+        LAUNCH(h, "k_mesh_trim_digit0", k_mesh_trim_digit0, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, &cuts[k].pad);
+        LAUNCH(h, "k_trim_narrow<1>", k_trim_narrow<1>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist, hist + TRIM_B0, keep, cuts + k);
+        LAUNCH(h, "k_trim_narrow<2>", k_trim_narrow<2>, grid, TRIM_T, 0, G.key.p, nq, ctl, hist + TRIM_B0, hist + TRIM_B0 + TRIM_B1, keep, cuts + k);
+        LAUNCH(h, "k_mesh_trim_terms", k_mesh_trim_terms, gterms, TRIM_T, 0, q4, nq, M, F, Tk, ctl, G.mwin.p, G.key.p, hist + TRIM_B0 + TRIM_B1, cuts + k,
+               G.acc.p + ICP_WORDS * (size_t)k);
+        if (k < iterations) LAUNCH(h, "k_reg_step", k_reg_step, 1, 64, 0, G.acc.p + ICP_WORDS * (size_t)k, F, G.T.p + 12 * (size_t)k, G.rows.p + k, ctl);
+    }
+    LAUNCH(h, "k_mesh_trim_scatter", k_mesh_trim_scatter, grid, TRIM_T, 0, q4, nq, G.key.p, ctl, cuts, (int)evals, (int)N1, G.tstatus.p, G.td2.p);
+    IcpCtl C;
+    std::vector<ppp_registration_row> R;
+    rc = chain_collect(h, w, iterations, nq, C, R);
+    if (rc) return rc;
+    const size_t last = (size_t)C.steps;
+    if (stats) *stats = registration_stats(R, C, N, (size_t)nq, shift, F.c, F.Ln);
+    std::vector<TrimCut> cut(last + 1);
+    HIPCHK(h, copy_sync(h, cut.data(), G.cuts.p, (last + 1) * sizeof(TrimCut), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i <= last; ++i)
+        if ((size_t)cut[i].paired + (size_t)cut[i].pad > nqs || R[i].pairs > cut[i].paired || (cut[i].paired && R[i].pairs < cut[i].k) ||
+            (!reject && cut[i].pad))
+            return fail(h, PPP_ERR_HIP, std::string(w) + ": cut corrupt");
+    const size_t k = std::min(row_cap, last + 1);
+    for (size_t i = 0; rows && i < k; ++i) {
+        memset(&rows[i], 0, sizeof(rows[i])); /* the padding too: rows compare as bytes */
+        trimmed_row(rows[i].trim, R[i], cut[i].paired, cut[i].tau);
+        rows[i].on_border = cut[i].pad;
+    }
+    const size_t mcap = std::min(cap, N);
+    if (status && mcap) HIPCHK(h, copy_sync(h, status, G.tstatus.p, mcap, hipMemcpyDeviceToHost));
+    if (d2 && mcap) HIPCHK(h, copy_sync(h, d2, G.td2.p, mcap * sizeof(float), hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_mesh_trimmed_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp, const double *T12,
+                                            ppp_mesh_trimmed_registration_row *row, unsigned char *status, float *d2, size_t cap,
+                                            ppp_registration_stats *stats)
+{
+    return mesh_trimmed_chain(h, m, mp, T12, false, row, row ? 1 : 0, status, d2, cap, stats);
+}
+
+int ppp_register_mesh_trimmed(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp, const double *T0_12,
+                              ppp_mesh_trimmed_registration_row *rows, size_t row_cap, unsigned char *status, float *d2, size_t cap,
+                              ppp_registration_stats *stats)
+{
+    return mesh_trimmed_chain(h, m, mp, T0_12, true, rows, row_cap, status, d2, cap, stats);
 }
 
 } // extern "C"

@@ -84,6 +84,7 @@ EXPORTS = [
     "ppp_default_trimesh_params", "ppp_trimesh_create", "ppp_trimesh_create_stl", "ppp_trimesh_destroy", "ppp_trimesh_nearest", "ppp_get_mesh_deviation",
     "ppp_trimesh_topology", "ppp_trimesh_get_topology", "ppp_trimesh_signed_nearest", "ppp_get_mesh_signed_deviation",
     "ppp_get_mesh_registration_terms", "ppp_register_mesh", "ppp_get_mesh_robust_registration_terms", "ppp_register_mesh_robust",
+    "ppp_default_mesh_trimmed_registration_params", "ppp_get_mesh_trimmed_registration_terms", "ppp_register_mesh_trimmed",
     "ppp_trimesh_get_moments", "ppp_mesh_frame_from_moments", "ppp_register_mesh_global",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
@@ -200,6 +201,12 @@ def lib():
                                           sz, C.POINTER(RegistrationStats)]
         L.ppp_get_mesh_robust_registration_terms.argtypes = L.ppp_get_robust_registration_terms.argtypes
         L.ppp_register_mesh_robust.argtypes = L.ppp_register_robust.argtypes
+        L.ppp_default_mesh_trimmed_registration_params.argtypes = [C.POINTER(MeshTrimmedRegistrationParams)]
+        L.ppp_default_mesh_trimmed_registration_params.restype = None
+        L.ppp_get_mesh_trimmed_registration_terms.argtypes = [vp, vp, C.POINTER(MeshTrimmedRegistrationParams), dp, C.POINTER(MeshTrimmedRegistrationRow),
+                                                              C.POINTER(C.c_ubyte), fp, sz, C.POINTER(RegistrationStats)]
+        L.ppp_register_mesh_trimmed.argtypes = [vp, vp, C.POINTER(MeshTrimmedRegistrationParams), dp, C.POINTER(MeshTrimmedRegistrationRow), sz,
+                                                C.POINTER(C.c_ubyte), fp, sz, C.POINTER(RegistrationStats)]
         L.ppp_trim_select.argtypes = [C.POINTER(C.c_uint), sz, sz, C.POINTER(C.c_uint), C.POINTER(sz)]
         L.ppp_trim_rank.argtypes = [C.c_double, sz]
         L.ppp_trim_rank.restype = sz
@@ -713,6 +720,27 @@ def _trimmed_registration_row(r):
     out["paired"] = int(r.paired)
     out["trim_d2"] = float(r.trim_d2)
     out["trim_bits"] = int(np.array([r.trim_d2], np.float32).view(np.uint32)[0])
+    return out
+
+
+class MeshTrimmedRegistrationParams(C.Structure):
+    """ppp_mesh_trimmed_registration_params"""
+    _fields_ = [("trim", TrimmedRegistrationParams), ("border", C.c_int)]
+
+
+class MeshTrimmedRegistrationRow(C.Structure):
+    """ppp_mesh_trimmed_registration_row"""
+    _fields_ = [("trim", TrimmedRegistrationRow), ("on_border", C.c_size_t)]
+
+
+MESH_BORDER_PAIR, MESH_BORDER_REJECT = range(2)  # PPP_MESH_BORDER_*
+MESH_TRIM_BORDER = 4                             # PPP_MESH_TRIM_BORDER, beside TRIM_KEPT .. TRIM_DROPPED
+
+
+def _mesh_trimmed_registration_row(r):
+    """a MeshTrimmedRegistrationRow as a dict: _trimmed_registration_row's fields with on_border"""
+    out = _trimmed_registration_row(r.trim)
+    out["on_border"] = int(r.on_border)
     return out
 
 
@@ -2085,6 +2113,53 @@ class Engine:
         same rows; the residual map is signed by the facets' winding.  Neither the cloud nor the mesh is changed"""
         m = mesh.m if mesh is not None else None
         return self._robust_loop(self.L.ppp_register_mesh_robust, m, tune, sigma_min, max_dist, iterations, min_step, lock_eps, T0, maps)
+
+    def _mesh_trimmed(self, call, loop, mesh, T, keep, border, max_dist, iterations, min_step, lock_eps, maps):
+        """the evaluation (loop False) or the loop by `call` against the TriMesh `mesh`"""
+        mp = MeshTrimmedRegistrationParams(TrimmedRegistrationParams(RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps)),
+                                                                     float(keep)), int(border))
+        cap = max(int(iterations), 0) + 1 if loop else 1
+        rows = (MeshTrimmedRegistrationRow * cap)()
+        st = RegistrationStats()
+        t = _t12(T)
+        status = d2 = None
+        n = 0
+        if maps:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            status = np.zeros(max(n, 1), np.uint8)
+            d2 = np.zeros(max(n, 1), np.float32)
+        args = [self.h, mesh.m if mesh is not None else None, C.byref(mp), None if t is None else _d(t), rows] + ([cap] if loop else [])
+        self._chk(call(*args, None if status is None else status.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                       None if d2 is None else d2.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(st)))
+        if maps:
+            status, d2 = status[:n], d2[:n]
+        return [_mesh_trimmed_registration_row(rows[k]) for k in range(min(cap, st.steps + 1))], status, d2, _registration_stats(st)
+
+    def mesh_trimmed_registration_terms(self, mesh, T=None, keep=0.8, border=MESH_BORDER_PAIR, max_dist=2.0, lock_eps=1e-9, maps=True):
+        """(row, status uint8[n], d2 float32[n], stats) of one evaluation of register_mesh_trimmed()'s terms at T (3 x 4, None: the
+        identity) against the triangles of the TriMesh `mesh` (ppp_get_mesh_trimmed_registration_terms): no step is taken; row
+        and the maps as register_mesh_trimmed() gives them.  maps=False returns None for the two maps"""
+        rows, status, d2, stats = self._mesh_trimmed(self.L.ppp_get_mesh_trimmed_registration_terms, False, mesh, T, keep, border, max_dist, 1, 0.0,
+                                                     lock_eps, maps)
+        return rows[0], status, d2, stats
+
+    def register_mesh_trimmed(self, mesh, keep=0.8, border=MESH_BORDER_PAIR, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None,
+                              maps=True):
+        """(T float64[3, 4], rows, status uint8[n], d2 float32[n], stats): trimmed point-to-plane ICP against the triangles of the
+        TriMesh `mesh` themselves (ppp_register_mesh_trimmed): register_mesh()'s candidates -- the moved point in double, the exact
+        closest point of its nearest triangle, that facet's own normal -- of which only the share `keep` with the smallest
+        distance enters an evaluation's sums: the tool for a scan more contaminated than register_mesh_robust()'s median bears.
+        border = MESH_BORDER_REJECT drops, before the cut, every candidate whose closest point lies on a border edge or a border
+        vertex of the mesh's welded topology (built where it is missing): the scan's overhang beyond an open mesh.  rows[k]:
+        register_trimmed()'s row (pairs = kept, paired, trim_d2, trim_bits) with on_border; status / d2 describe the last
+        evaluation by cloud index: TRIM_KEPT, TRIM_TRIMMED, TRIM_UNPAIRED, TRIM_DROPPED, MESH_TRIM_BORDER and the key's float
+        (NaN without a pair).  keep = 1 with MESH_BORDER_PAIR is register_mesh() bit for bit.  maps=False returns None for the
+        two maps.  The cloud is not changed"""
+        rows, status, d2, stats = self._mesh_trimmed(self.L.ppp_register_mesh_trimmed, True, mesh, T0, keep, border, max_dist, iterations, min_step,
+                                                     lock_eps, maps)
+        return stats["T"].copy(), rows, status, d2, stats
 
     register_trimmed_tiles = staticmethod(register_trimmed_tiles)   # Engine.register_trimmed_tiles(engines, refs, ...): the module's function
     register_robust_tiles = staticmethod(register_robust_tiles)     # Engine.register_robust_tiles(engines, refs, ...) likewise

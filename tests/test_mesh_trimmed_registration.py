@@ -1,0 +1,842 @@
+"""Trimmed registration of a scan to the triangle mesh itself, with border-pair rejection (ppp_get_mesh_trimmed_registration_terms,
+ppp_register_mesh_trimmed): ppp_register_mesh's candidates on the facets under ppp_register_trimmed's cut.
+
+The yardstick is restate_mesh_trimmed_terms(): the search and the frame of restate_mesh_terms() of tests/test_mesh_registration.py
+-- the moved points in double, the brute force over ALL valid triangles with the first minimum, the box's frame -- with the winner,
+its closest point, D2 and the walk's branch kept; the border class from restate_topology()'s tables of
+tests/test_trimesh_topology.py and BRANCH_FEATURE, the feature each branch of the walk stands for; the key np.float32(D2) read as
+uint32; the cut by the exact rank (a sort); the words by restate_mesh_terms()'s arithmetic on the kept subset.  It knows nothing of
+a grid, a histogram or a sentinel.  Every comparison of the engine with the restatement is for equal bytes."""
+import ctypes
+import functools
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_registration import ALL_LOCKED, IDENTITY, NAN, apply, frame, motion_about, restate_step, rms_of, rows_equal, stats_equal
+from test_path_dwell import same
+from test_trimesh import BRANCH_REGION, VIEWPOINT, closest_on_triangles, frames, sheet
+from test_mesh_registration import (KW0, MOTION, flat_case, flat_restated, mesh_box, part_way, restate_mesh_terms, restate_register_mesh, scan_engine,
+                                    surface, wavy_case, wavy_restated)
+from test_mesh_robust_registration import (BEYOND_X, DIRTY, DIRTY_ITERATIONS, N_DIRTY, PLAIN_CLEAN_MM, clean_error, dirty_case, dirty_robust_restated,
+                                           flat_points)
+from test_trimmed_registration import NAN32_BITS, digit_heights, f32_from_bits, maps_equal, part_handle, trim_rank, trows_equal
+from test_trimesh_topology import BORDER, BRANCH_FEATURE, V_BORDER, cube, restate_topology, sheet_with_hole
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KEPT, TRIMMED, UNPAIRED, DROPPED, ON_BORDER = range(5)                        # PPP_TRIM_* and PPP_MESH_TRIM_BORDER
+PAIR, REJECT = 0, 1                                                           # PPP_MESH_BORDER_*
+INF = float("inf")
+
+
+# ---------------------------------------------------------------- the restatement
+
+
+def border_of(topo, f, branch):
+    """bool[len(f)]: the closest point's feature (the walk's branch on triangle f's rotated frame) is a vertex with the border bit or
+    an edge of class border -- the condition of PPP_MESH_SIGN_BORDER in restate_signed() of tests/test_trimesh_topology.py"""
+    out = np.zeros(len(f), bool)
+    for i, (ff, br) in enumerate(zip(f, branch)):
+        feat, rot = int(BRANCH_FEATURE[br]), int(topo["rot"][ff])
+        if feat < 3:
+            out[i] = bool(int(topo["vertex_bits"][ff, (feat + rot) % 3]) & V_BORDER)
+        elif feat < 6:
+            out[i] = int(topo["edge_class"][ff, (rot + {3: 0, 5: 1, 4: 2}[feat]) % 3]) == BORDER
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _topology(vbytes, tbytes):
+    return restate_topology(np.frombuffer(vbytes, np.float32).reshape(-1, 3), np.frombuffer(tbytes, np.int32).reshape(-1, 3))
+
+
+def topology_of(rv, tris):
+    return _topology(np.ascontiguousarray(rv, np.float32).tobytes(), np.ascontiguousarray(tris, np.int32).tobytes())
+
+
+def restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep=0.8, border=PAIR, chunk=256):
+    """One evaluation: restate_mesh_terms()'s dict over the KEPT pairs (pairs = kept) with paired, k, trim_bits (tau; the float quiet
+    NaN without a pair), on_border, status uint8[n] and d2 float32[n] by cloud index; region uint8[kept] for the census"""
+    P = np.ascontiguousarray(P, np.float32)
+    T = np.asarray(T, np.float64).reshape(3, 4)
+    n = len(P)
+    mn, mx, (a, b, c, N, A2) = mesh_box(rv, tris)
+    fi = np.nonzero(frames(rv, tris)[5])[0]                                  # the caller's index of every valid triangle
+    cen, Ln, shift, _ = frame(mn, mx, n, max_dist)
+    md2 = float(np.float32(max_dist)) * float(np.float32(max_dist))
+    scale = 2.0 ** shift
+    finite = np.isfinite(P).all(axis=1)
+    rows = np.nonzero(finite)[0]                                              # the indexed points of the scan
+    p = P[rows].astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        m = np.stack([((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3] for r in range(3)], axis=1)
+    ok = np.isfinite(m).all(axis=1)
+    cand = np.zeros(len(rows), bool)
+    win = np.zeros(len(rows), np.int64)
+    X = np.zeros((len(rows), 3))
+    best = np.zeros(len(rows))
+    branch = np.zeros(len(rows), np.int64)
+    for s in range(0, len(rows), chunk):
+        sel = np.nonzero(ok[s:s + chunk])[0] + s
+        if not len(sel) or not len(a):
+            continue
+        x, D2, br = closest_on_triangles(m[sel][:, None, :], a[None], b[None], c[None])
+        j = D2.argmin(axis=1)                                                # the first minimum: the lowest f
+        i = np.arange(len(sel))
+        hit = D2[i, j] <= md2
+        cand[sel[hit]] = True
+        win[sel[hit]] = j[hit]
+        X[sel[hit]] = x[i, j][hit]
+        best[sel[hit]] = D2[i, j][hit]
+        branch[sel[hit]] = br[i, j][hit]
+    onb = np.zeros(len(rows), bool)
+    if border == REJECT:
+        at = np.nonzero(cand)[0]
+        onb[at] = border_of(topology_of(rv, tris), fi[win[at]], branch[at])
+    pair = cand & ~onb
+    keys = np.zeros(len(rows), np.uint32)
+    keys[pair] = best[pair].astype(np.float32).view(np.uint32)
+    paired = int(pair.sum())
+    k = trim_rank(keep, paired)
+    if paired:
+        tau = int(np.sort(keys[pair])[k - 1])
+        kept = pair & (keys <= np.uint32(tau))
+    else:
+        tau, kept = NAN32_BITS, pair
+    mm, xx, f = m[kept], X[kept], win[kept]
+    nn = N[f] / A2[f][:, None]
+    e = mm - xx
+    r = ((e[:, 0] * nn[:, 0]) + e[:, 1] * nn[:, 1]) + e[:, 2] * nn[:, 2]
+    u = (mm - cen[None, :]) / Ln
+    J = [u[:, 1] * nn[:, 2] - u[:, 2] * nn[:, 1], u[:, 2] * nn[:, 0] - u[:, 0] * nn[:, 2], u[:, 0] * nn[:, 1] - u[:, 1] * nn[:, 0],
+         nn[:, 0], nn[:, 1], nn[:, 2]]
+    fix = lambda v: int(np.rint(v * scale).astype(np.int64).sum(dtype=np.int64))
+    A = np.array([fix(J[i] * J[q]) for i in range(6) for q in range(i, 6)], np.int64)
+    bb = np.array([fix(J[i] * r) for i in range(6)], np.int64)
+    status = np.full(n, UNPAIRED, np.uint8)
+    status[~finite] = DROPPED
+    status[rows[pair]] = TRIMMED
+    status[rows[kept]] = KEPT
+    status[rows[onb]] = ON_BORDER
+    d2 = np.full(n, np.nan, np.float32)
+    d2[rows[pair]] = keys[pair].view(np.float32)
+    assert int(kept.sum()) >= k
+    return dict(T=T.copy(), pairs=int(kept.sum()), A=A, b=bb, E=fix(r * r), shift=shift, centre=cen, length=Ln, n=n, indexed=len(rows), paired=paired,
+                k=k, trim_bits=tau, on_border=int(onb.sum()), status=status, d2=d2, region=BRANCH_REGION[branch[kept]])
+
+
+def restate_register_mesh_trimmed(P, rv, tris, keep=0.8, border=PAIR, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+    """(T, rows, status, d2, stats) as Engine.register_mesh_trimmed gives them: restate_register_mesh()'s loop -- pairs read as kept --
+    over restate_mesh_trimmed_terms()"""
+    T = IDENTITY.copy() if T0 is None else np.asarray(T0, np.float64).reshape(3, 4).copy()
+    rows, converged, locked, stop = [], 0, 0, False
+    while True:
+        row = restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep, border)
+        row.update(locked=ALL_LOCKED, step2=NAN)
+        rows.append(row)
+        if stop or len(rows) > iterations:
+            break
+        if row["pairs"] >= 6 and not np.any(row["b"]):
+            converged = 1
+            break
+        step = restate_step(row, row["centre"], row["length"], lock_eps)
+        if step is None:
+            break
+        mask, _, T, step2 = step
+        row.update(locked=mask, step2=step2)
+        locked |= mask
+        if step2 < min_step * min_step:
+            converged, stop = 1, True
+    first, last = rows[0], rows[-1]
+    stats = dict(n=first["n"], indexed=first["indexed"], steps=len(rows) - 1, converged=converged, locked=locked, shift=first["shift"],
+                 centre=first["centre"], length=first["length"], T=last["T"].copy(), pairs_before=first["pairs"], pairs_after=last["pairs"],
+                 rms_before=rms_of(first, first["shift"]), rms_after=rms_of(last, first["shift"]))
+    return last["T"].copy(), rows, last["status"], last["d2"], stats
+
+
+# ---------------------------------------------------------------- the cases
+
+# the worst coordinate error over the clean points, mm, by the bit-exact restatement under DIRTY (12 iterations; test_what_the_cut_is_
+# for prints and pins them), measured 2026-10-21: the 13.7 % case at keep 0.8, the 35 % case at keep 0.6; the robust loop's on the 35 %
+# case is dirty_robust_restated(BEYOND_X)'s
+TRIMMED_CLEAN_MM = 0.05490545124197155
+TRIMMED_HEAVY_MM = 0.05670257942266499
+ROBUST_HEAVY_MM = 0.871693492811062
+# the curved-overhang case: the worst coordinate error over the points inside the sheet, mm, under OVERHANG
+OVERHANG_PAIR_MM = 0.16955762900744986
+OVERHANG_REJECT_MM = 0.043334700342311905
+OVERHANG = dict(keep=0.9, max_dist=15.0, iterations=DIRTY_ITERATIONS)
+OVERHANG_MM = 10.0                                                            # four facets (the pitch is 2.5 mm)
+N_OVERHANG = 1200
+
+
+@functools.lru_cache(maxsize=None)
+def dirty_trimmed_restated(raise_below, keep):
+    v, t, scan, moved, raised = dirty_case(raise_below)
+    return restate_register_mesh_trimmed(moved, v, t, keep=keep, **DIRTY)
+
+
+@functools.lru_cache(maxsize=None)
+def overhang_case():
+    """(verts, tris, scan float64[n, 3] before the motion, moved float32[n, 3]: what the engine gets, inside bool[n]): the wavy sheet of
+    768 facets (0 .. 60 by 0 .. 40 mm) and a scan that CONTINUES surface() OVERHANG_MM past the sides x = 0 and y = 0 -- the part goes on
+    there, the mesh of "the face to polish" does not --, noise +-0.05 mm, moved by MOTION.  Under max_dist 15 every point of the
+    overhang pairs with a border facet; nobody writes to them"""
+    v, t = wavy_case()[:2]
+    rng = np.random.default_rng(23)
+    x, y = rng.uniform(-OVERHANG_MM, 60.0, N_OVERHANG), rng.uniform(-OVERHANG_MM, 40.0, N_OVERHANG)
+    z = surface(x, y) + rng.uniform(-0.05, 0.05, N_OVERHANG)
+    scan = np.stack([x, y, z], axis=1)
+    inside = (x > 0.0) & (x < 60.0) & (y > 0.0) & (y < 40.0)
+    Tm = motion_about(MOTION["c"], MOTION["deg"], MOTION["shift"])
+    R, tt = Tm[:, :3], Tm[:, 3]
+    moved = ((scan - tt) @ R).astype(np.float32)
+    for arr in (scan, moved, inside):
+        arr.setflags(write=False)
+    return v, t, scan, moved, inside
+
+
+@functools.lru_cache(maxsize=None)
+def overhang_restated(border):
+    v, t, scan, moved, inside = overhang_case()
+    return restate_register_mesh_trimmed(moved, v, t, border=border, **OVERHANG)
+
+
+def inside_error(T, moved, scan, inside):
+    return float(np.abs(apply(T, moved[inside]) - scan[inside]).max())
+
+
+def lattice_over(lo, hi, pitch, z):
+    """a lattice of float32 points at height z over [lo, hi]^2: coordinates k * pitch, exact in float for a pitch that is a dyadic"""
+    g = np.arange(lo, hi + pitch / 2, pitch, dtype=np.float64)
+    gx, gy = np.meshgrid(g, g, indexing="ij")
+    pts = np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, z)], axis=1).astype(np.float32)
+    assert np.array_equal(pts[:, :2].astype(np.float64), np.stack([gx.ravel(), gy.ravel()], axis=1))
+    return pts
+
+
+# ---------------------------------------------------------------- CPU
+
+PARAMS_DECL = ("enum { PPP_MESH_BORDER_PAIR = 0, PPP_MESH_BORDER_REJECT = 1 };\n"
+               "typedef struct {\n"
+               "    ppp_trimmed_registration_params trim;   /* ppp_register_trimmed's: icp's four and keep in (0, 1] */\n"
+               "    int border;                             /* PPP_MESH_BORDER_PAIR (as ppp_register_mesh) or _REJECT */\n"
+               "} ppp_mesh_trimmed_registration_params;")
+ROW_DECL = ("typedef struct {\n"
+            "    ppp_trimmed_registration_row trim;      /* row over the KEPT pairs, paired, trim_d2 */\n"
+            "    size_t on_border;                       /* candidates rejected on the border at row.T; 0 under _PAIR */\n"
+            "} ppp_mesh_trimmed_registration_row;\n"
+            "enum { PPP_MESH_TRIM_BORDER = 4 };")
+FUNC_DECLS = ("void ppp_default_mesh_trimmed_registration_params(ppp_mesh_trimmed_registration_params *mp);",
+              "int  ppp_get_mesh_trimmed_registration_terms(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp,\n"
+              "                                             const double *T12, ppp_mesh_trimmed_registration_row *row,\n"
+              "                                             unsigned char *status, float *d2, size_t cap, ppp_registration_stats *stats);",
+              "int  ppp_register_mesh_trimmed(ppp_handle h, ppp_trimesh m, const ppp_mesh_trimmed_registration_params *mp,\n"
+              "                               const double *T0_12, ppp_mesh_trimmed_registration_row *rows, size_t row_cap,\n"
+              "                               unsigned char *status, float *d2, size_t cap, ppp_registration_stats *stats);")
+
+
+def test_header_declares_and_engine_exports_mesh_trimmed_registration(engine_mod, tmp_path):
+    hdr = open(os.path.join(ROOT, "include", "ppp_hip.h")).read()
+    for decl in (PARAMS_DECL, ROW_DECL) + FUNC_DECLS:
+        assert decl in hdr, decl
+    assert "DESIGN.md 7y" in hdr and "PPP_MESH_SIGN_BORDER" in hdr
+    assert "enum { PPP_TRIM_KEPT = 0, PPP_TRIM_TRIMMED = 1, PPP_TRIM_UNPAIRED = 2, PPP_TRIM_DROPPED = 3 };" in hdr      # unchanged
+    assert hdr.count("} ppp_trimmed_registration_params;") == 1 and hdr.count("} ppp_trimmed_registration_row;") == 1
+    E = engine_mod
+    L = ctypes.CDLL(E.LIB_PATH)
+    for sym in ("ppp_default_mesh_trimmed_registration_params", "ppp_get_mesh_trimmed_registration_terms", "ppp_register_mesh_trimmed"):
+        assert sym in E.EXPORTS and hasattr(L, sym)
+    for m in ("mesh_trimmed_registration_terms", "register_mesh_trimmed"):
+        assert hasattr(E.Engine, m)
+    assert (E.MESH_BORDER_PAIR, E.MESH_BORDER_REJECT, E.MESH_TRIM_BORDER) == (0, 1, 4)
+    L.ppp_default_mesh_trimmed_registration_params.argtypes = [ctypes.POINTER(E.MeshTrimmedRegistrationParams)]
+    L.ppp_default_mesh_trimmed_registration_params.restype = None
+    mp = E.MeshTrimmedRegistrationParams()
+    mp.border = 7
+    L.ppp_default_mesh_trimmed_registration_params(ctypes.byref(mp))
+    L.ppp_default_mesh_trimmed_registration_params(None)
+    assert (mp.trim.keep, mp.border, mp.trim.icp.iterations, mp.trim.icp.max_dist) == (0.8, 0, 30, 2.0)
+    planner = open(os.path.join(ROOT, "include", "ppp_planner.hpp")).read()
+    assert "register_mesh_trimmed(" in planner and "print_mesh_trimmed_registration(" in planner and "mesh_trimmed_registration_params_env(" in planner
+    for h in ("Path_Generate.h", "Path_Generate_Algorithm.h", "robot_path.h"):
+        assert "register_trimmed_to_mesh(" in open(os.path.join(ROOT, "include", h)).read(), h
+    src = tmp_path / "c99.c"
+    src.write_text('#include "ppp_hip.h"\nint main(void) {\n'
+                   '    void (*d)(ppp_mesh_trimmed_registration_params *) = ppp_default_mesh_trimmed_registration_params;\n'
+                   '    int (*f)(ppp_handle, ppp_trimesh, const ppp_mesh_trimmed_registration_params *, const double *, ppp_mesh_trimmed_registration_row *,\n'
+                   '             unsigned char *, float *, size_t, ppp_registration_stats *) = ppp_get_mesh_trimmed_registration_terms;\n'
+                   '    int (*g)(ppp_handle, ppp_trimesh, const ppp_mesh_trimmed_registration_params *, const double *, ppp_mesh_trimmed_registration_row *, size_t,\n'
+                   '             unsigned char *, float *, size_t, ppp_registration_stats *) = ppp_register_mesh_trimmed;\n'
+                   '    ppp_mesh_trimmed_registration_row r;\n'
+                   '    r.on_border = PPP_MESH_TRIM_BORDER + PPP_MESH_BORDER_REJECT + PPP_MESH_BORDER_PAIR;\n'
+                   '    return d == 0 || f == 0 || g == 0 || r.on_border == 0;\n}\n')
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
+    lay = tmp_path / "layout.c"
+    lay.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ppp_hip.h"\nint main(void) {\n'
+                   '    printf("%zu %zu %zu %zu\\n", sizeof(ppp_mesh_trimmed_registration_params), offsetof(ppp_mesh_trimmed_registration_params, border),\n'
+                   '           sizeof(ppp_mesh_trimmed_registration_row), offsetof(ppp_mesh_trimmed_registration_row, on_border));\n    return 0;\n}\n')
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(lay), "-o", str(tmp_path / "layout")])
+    got = [int(x) for x in subprocess.check_output([str(tmp_path / "layout")]).split()]
+    assert got == [ctypes.sizeof(E.MeshTrimmedRegistrationParams), E.MeshTrimmedRegistrationParams.border.offset,
+                   ctypes.sizeof(E.MeshTrimmedRegistrationRow), E.MeshTrimmedRegistrationRow.on_border.offset]
+
+
+def test_examples_build_with_the_mesh_trimmed_switch(engine_mod):
+    for ex in ("connect.cpp", "robot.cpp"):
+        src = open(os.path.join(ROOT, "examples", ex)).read()
+        assert '"mesh-trimmed"' in src and "register_trimmed_to_mesh(" in src and "register_robust_to_mesh(" in src, ex
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), "connect", "connect1", "robot", "main", "api_check"])
+    for exe in ("connect", "connect1", "robot", "main", "api_check"):
+        assert os.access(os.path.join(ROOT, "examples", exe), os.X_OK)
+
+
+def test_keep_one_restates_the_mesh_loop():
+    """with keep = 1 and PAIR every candidate is kept: rows, T and stats are restate_register_mesh()'s, bit for bit, on the wavy case
+    (3 iterations: the identity holds per evaluation) and on the flat one to its end"""
+    v, t, scan, moved, Tm = wavy_case()
+    T, rows, status, d2, st = restate_register_mesh_trimmed(moved, v, t, keep=1.0, iterations=3)
+    wT, wrows, wst = restate_register_mesh(moved, v, t, iterations=3)
+    rows_equal(rows, wrows)
+    stats_equal(st, wst)
+    assert same(T, wT) and st["steps"] == 3
+    for row, want in zip(rows, wrows):
+        assert row["paired"] == row["pairs"] == row["k"] and row["on_border"] == 0 and np.array_equal(row["region"], want["region"])
+    assert not np.any(status == TRIMMED) and int((status == KEPT).sum()) == rows[-1]["pairs"]
+    assert rows[-1]["trim_bits"] == int(d2[status == KEPT].view(np.uint32).max())
+    v, t, scan, T0 = flat_case()
+    T, rows, _, _, st = restate_register_mesh_trimmed(scan, v, t, keep=1.0, T0=T0)
+    wT, wrows, wst = flat_restated()
+    rows_equal(rows, wrows)
+    stats_equal(st, wst)
+    assert same(T, wT)
+
+
+def outside_open(pts, lo, hi):
+    """the float coordinates lie outside the open rectangle (lo, hi)^2: a point exactly above the outline counts as on it"""
+    x, y = pts[:, 0].astype(np.float64), pts[:, 1].astype(np.float64)
+    return ~((x > lo) & (x < hi) & (y > lo) & (y < hi))
+
+
+def test_census_of_the_border_rule():
+    """The exactly planar sheet(8, 8, 4.0), 0 .. 32 mm both ways, and a 0.5 mm lattice 0.3 above it from -1.5 to 33.5: the closest
+    point of a point over the open rectangle is its foot, on a face or on an interior edge or vertex (the lattice passes over every
+    grid line and every diagonal); of any other point it is on the outline.  BORDER is exactly the second kind.  Then the flat sheet
+    with a hole: the points over the hole, its rim included, are BORDER too.  On the closed cube nothing is."""
+    v, t = sheet(8, 8, 4.0)
+    pts = lattice_over(-1.5, 33.5, 0.5, 0.3)
+    row = restate_mesh_trimmed_terms(pts, v, t, 3.0, IDENTITY, keep=1.0, border=REJECT)   # (the corners lie 2.14 mm off)
+    out = outside_open(pts, 0.0, 32.0)
+    print("points %d, outside the open rectangle %d; on_border %d paired %d" % (len(pts), int(out.sum()), row["on_border"], row["paired"]))
+    assert np.array_equal(row["status"] == ON_BORDER, out) and row["on_border"] == int(out.sum()) > 0
+    assert np.all(row["status"][~out] == KEPT) and row["paired"] == int((~out).sum())
+    on_lines = (pts[:, 0] % 4 == 0) | (pts[:, 1] % 4 == 0) | (pts[:, 0] % 4 == pts[:, 1] % 4)
+    assert int((on_lines & ~out).sum()) > 100                               # interior edges and vertices: never BORDER
+    assert np.all(np.isnan(row["d2"][out])) and not np.any(np.isnan(row["d2"][~out]))
+    plain = restate_mesh_trimmed_terms(pts, v, t, 3.0, IDENTITY, keep=1.0, border=PAIR)
+    assert plain["on_border"] == 0 and plain["paired"] == len(pts) and not np.any(plain["status"] == ON_BORDER)
+    # the hole: cells 4 <= i < 6, 3 <= j < 5 of a 2 mm pitch are missing: the open rectangle (8, 12) x (6, 10) has no triangle over it
+    v, t = sheet_with_hole(wave=0.0)
+    pts = lattice_over(-1.0, 21.0, 0.25, 0.3)
+    pts = pts[pts[:, 1] <= 17.0]
+    row = restate_mesh_trimmed_terms(pts, v, t, 3.0, IDENTITY, keep=1.0, border=REJECT)
+    x, y = pts[:, 0].astype(np.float64), pts[:, 1].astype(np.float64)
+    off = ~((x > 0) & (x < 20) & (y > 0) & (y < 16)) | ((x >= 8) & (x <= 12) & (y >= 6) & (y <= 10))
+    print("with the hole: points %d, off the mesh or on its outlines %d; on_border %d" % (len(pts), int(off.sum()), row["on_border"]))
+    assert np.array_equal(row["status"] == ON_BORDER, off) and int(((x > 8) & (x < 12) & (y > 6) & (y < 10)).sum()) > 100
+    # the cube: closed, no border edge
+    v, t = cube(size=10.0)
+    rng = np.random.default_rng(5)
+    shell = (rng.uniform(-1.0, 11.0, (400, 3))).astype(np.float32)
+    a = restate_register_mesh_trimmed(shell, v, t, border=REJECT, iterations=2)
+    b = restate_register_mesh_trimmed(shell, v, t, border=PAIR, iterations=2)
+    assert restate_topology(v, t)["stats"]["closed"] == 1
+    trows_equal(a[1], b[1])
+    assert same(a[0], b[0]) and a[2].tobytes() == b[2].tobytes() and a[3].tobytes() == b[3].tobytes() and not np.any(a[2] == ON_BORDER)
+    assert all(r["on_border"] == 0 for r in a[1]) and a[1][0]["paired"] > 100
+
+
+def test_what_the_cut_is_for():
+    """The contaminated case of tests/test_mesh_robust_registration.py under its DIRTY (12 iterations).  13.7 % raised, keep 0.8: every
+    raised point that pairs at the result is TRIMMED, and the clean points end closer than under the plain loop (PLAIN_CLEAN_MM).
+    35 % raised -- beyond the median, as that module's test asserts --, keep 0.6: the clean points end closer than under the robust
+    loop."""
+    v, t, scan, moved, raised = dirty_case()
+    T, rows, status, d2, st = dirty_trimmed_restated(7.0, 0.8)
+    e = clean_error(T, moved, scan, raised)
+    print("13.7 %%: keep 0.8: steps %d converged %d kept %d of %d, cut %r mm^2; clean error %r mm (plain %r)"
+          % (st["steps"], st["converged"], rows[-1]["pairs"], rows[-1]["paired"], float(f32_from_bits(rows[-1]["trim_bits"])), e, PLAIN_CLEAN_MM))
+    assert np.all(status[raised] != KEPT) and np.all((status[raised] == TRIMMED) | (status[raised] == UNPAIRED)) and np.any(status[raised] == TRIMMED)
+    assert e < PLAIN_CLEAN_MM
+    v, t, scan, moved, raised = dirty_case(BEYOND_X)
+    T, rows, status, d2, st = dirty_trimmed_restated(BEYOND_X, 0.6)
+    eh = clean_error(T, moved, scan, raised)
+    er = clean_error(dirty_robust_restated(BEYOND_X)[0], moved, scan, raised)
+    print("%.1f %%: keep 0.6: steps %d converged %d kept %d of %d; clean error %r mm (robust %r)"
+          % (100.0 * raised.sum() / N_DIRTY, st["steps"], st["converged"], rows[-1]["pairs"], rows[-1]["paired"], eh, er))
+    assert eh < er
+    assert same(e, TRIMMED_CLEAN_MM) and same(eh, TRIMMED_HEAVY_MM) and same(er, ROBUST_HEAVY_MM)     # the constants are the measurement
+
+
+def test_border_rejection_on_a_curved_overhang():
+    """overhang_case() under OVERHANG: the same keep, with and without the rule.  Under PAIR the overhang pairs with the border facets
+    -- within 15 mm all of it -- and the cut by distance removes only its far part; what stays measures against tangent planes that
+    the part left behind, and pulls.  Under REJECT none of it is a pair, and the points inside the sheet end closer."""
+    v, t, scan, moved, inside = overhang_case()
+    made = restate_mesh_trimmed_terms(scan.astype(np.float32), v, t, OVERHANG["max_dist"], IDENTITY, keep=1.0, border=REJECT)
+    print("where the scan was made: %d of %d on the border, %d paired" % (made["on_border"], len(scan), made["paired"]))
+    assert made["on_border"] + made["paired"] == len(scan)                   # all of the overhang pairs without the rule
+    assert made["on_border"] >= int((~inside).sum()) > 0.15 * len(scan)                 # more than 1 - keep: the cut alone cannot remove it
+    out = {}
+    for border in (PAIR, REJECT):
+        T, rows, status, d2, st = overhang_restated(border)
+        out[border] = inside_error(T, moved, scan, inside)
+        print("border %d: steps %d converged %d kept %d paired %d on_border %d; error inside %r mm"
+              % (border, st["steps"], st["converged"], rows[-1]["pairs"], rows[-1]["paired"], rows[-1]["on_border"], out[border]))
+    assert out[REJECT] < out[PAIR]
+    assert same(out[PAIR], OVERHANG_PAIR_MM) and same(out[REJECT], OVERHANG_REJECT_MM)                # the constants are the measurement
+    status = overhang_restated(REJECT)[2]
+    far = (scan[:, 0] < -0.5) | (scan[:, 1] < -0.5)                           # clear of the outline by more than the fit's error
+    assert np.all(status[far] == ON_BORDER) and int(far.sum()) > 300
+
+
+# ---------------------------------------------------------------- GPU
+
+MROW_EXACT = ("on_border",)
+
+
+def mrows_equal(got, want):
+    trows_equal(got, want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        for f in MROW_EXACT:
+            assert g[f] == w[f], (k, f, g[f], w[f])
+
+
+def terms_parity(s, mesh, v, t, T=None, max_dist=2.0, lock_eps=1e-9, want=None, **kw):
+    """Engine.mesh_trimmed_registration_terms against restate_mesh_trimmed_terms on the engine's own cloud: the row, the maps, stats"""
+    if want is None:
+        want = restate_mesh_trimmed_terms(s.cloud(), v, t, max_dist, IDENTITY if T is None else T, **kw)
+    want = dict(want, locked=ALL_LOCKED, step2=NAN)
+    row, status, d2, st = s.mesh_trimmed_registration_terms(mesh, T=T, max_dist=max_dist, lock_eps=lock_eps, **kw)
+    mrows_equal([row], [want])
+    maps_equal(status, d2, want["status"], want["d2"])
+    assert st["steps"] == 0 and st["converged"] == 0 and st["pairs_before"] == st["pairs_after"] == row["pairs"] and st["shift"] == want["shift"]
+    assert same(st["rms_before"], rms_of(want, want["shift"])) and same(st["rms_after"], rms_of(want, want["shift"])) and same(st["T"], want["T"])
+    assert same(st["centre"], want["centre"]) and same(st["length"], want["length"]) and st["indexed"] == want["indexed"] and st["n"] == want["n"]
+    return row, status, d2, want
+
+
+def chain_parity(s, mesh, v, t, want=None, **kw):
+    got = s.register_mesh_trimmed(mesh, **kw)
+    if want is None:
+        want = restate_register_mesh_trimmed(s.cloud(), v, t, **kw)
+    T, rows, status, d2, st = got
+    print("steps %d (want %d) converged %d (want %d) kept %r paired %r on_border %r cut %r" % (st["steps"], want[4]["steps"], st["converged"], want[4]["converged"],
+          [w["pairs"] for w in rows], [w["paired"] for w in rows], [w["on_border"] for w in rows], [w["trim_d2"] for w in rows]))
+    mrows_equal(rows, want[1])
+    stats_equal(st, want[4])
+    maps_equal(status, d2, want[2], want[3])
+    assert same(T, want[0]) and same(T, rows[-1]["T"]) and rows[-1]["locked"] == ALL_LOCKED and math.isnan(rows[-1]["step2"])
+    return got, want
+
+
+FLAT_PART_WAY = motion_about([16.0, 16.0, 0.0], (0.5, -0.4, 0.3), (0.1, -0.05, 0.2))
+
+
+@functools.lru_cache(maxsize=None)
+def flat_overhang():
+    """the planar sheet(8, 8, 4.0) and a 1 mm lattice 0.3 above it that reaches 1.5 mm past every side: 1 296 points"""
+    v, t = sheet(8, 8, 4.0)
+    pts = lattice_over(-1.5, 33.5, 1.0, 0.3)
+    pts.setflags(write=False)
+    return v, t, pts
+
+
+@functools.lru_cache(maxsize=None)
+def terms_restated(case, border, at):
+    """the evaluations test_terms_match_the_restatement compares with, made once for its three cells"""
+    if case == "wavy":
+        v, t, _, pts, _ = wavy_case()
+        T, md = (IDENTITY, part_way(2.0 / 3.0))[at], 2.0
+    else:
+        v, t, pts = flat_overhang()
+        T, md = (IDENTITY, FLAT_PART_WAY)[at], 3.0
+    return restate_mesh_trimmed_terms(pts, v, t, md, T, keep=0.8, border=border)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cell", [0.0, 0.9, 25.0])
+def test_terms_match_the_restatement(engine_mod, cell):
+    for case in ("wavy", "flat"):
+        if case == "wavy":
+            v, t, _, pts, _ = wavy_case()
+            Ts, md = (None, part_way(2.0 / 3.0)), 2.0
+        else:
+            v, t, pts = flat_overhang()
+            Ts, md = (None, FLAT_PART_WAY), 3.0
+        s = scan_engine(engine_mod, pts)
+        mesh = s.trimesh(v, t, cell=cell)
+        print("%s: grid %r cell %r" % (case, mesh.stats["cells"], mesh.stats["cell"]))
+        for border in (PAIR, REJECT):
+            for at, T in enumerate(Ts):
+                want = terms_restated(case, border, at)
+                row, status, d2, _ = terms_parity(s, mesh, v, t, T=T, max_dist=md, keep=0.8, border=border, want=want)
+                print("border %d at %d: kept %d paired %d on_border %d cut %r" % (border, at, row["pairs"], row["paired"], row["on_border"], row["trim_d2"]))
+                assert 6 <= row["pairs"] <= row["paired"] and (row["on_border"] > 0) == (border == REJECT)
+                assert row["pairs"] < row["paired"] or (case, at) == ("flat", 0)    # (there every kept distance is 0.3: one tie, all kept)
+                assert int((status == ON_BORDER).sum()) == row["on_border"] and int((status == KEPT).sum()) == row["pairs"]
+                again = s.mesh_trimmed_registration_terms(mesh, T=T, max_dist=md, keep=0.8, border=border)        # the same bits in every run
+                assert same(again[:3], (row, status, d2))
+        mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_chain_matches_the_restatement_on_the_contaminated_case(engine_mod):
+    v, t, scan, moved, raised = dirty_case()
+    s = scan_engine(engine_mod, moved)
+    mesh = s.trimesh(v, t)
+    (T, rows, status, d2, st), _ = chain_parity(s, mesh, v, t, want=dirty_trimmed_restated(7.0, 0.8), keep=0.8, **DIRTY)
+    assert same(clean_error(T, moved, scan, raised), TRIMMED_CLEAN_MM)       # the census's error, reached by the engine's T
+    assert np.all(status[raised] != KEPT) and rows[-1]["pairs"] < rows[-1]["paired"] and rows[-1]["on_border"] == 0
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_chain_matches_the_restatement_on_the_curved_overhang(engine_mod):
+    v, t, scan, moved, inside = overhang_case()
+    s = scan_engine(engine_mod, moved)
+    mesh = s.trimesh(v, t)
+    (T, rows, status, d2, st), _ = chain_parity(s, mesh, v, t, want=overhang_restated(REJECT), border=REJECT, **OVERHANG)
+    assert same(inside_error(T, moved, scan, inside), OVERHANG_REJECT_MM)
+    assert rows[-1]["on_border"] > 300 and st["steps"] >= 3
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["wavy", "flat"])
+def test_keep_one_without_the_rule_is_register_mesh_bit_for_bit(engine_mod, case):
+    if case == "wavy":
+        v, t, _, pts, _ = wavy_case()
+        T0 = None
+    else:
+        v, t, pts, T0 = flat_case()
+    s = scan_engine(engine_mod, pts)
+    mesh = s.trimesh(v, t)
+    T, rows, st = s.register_mesh(mesh, T0=T0)
+    mT, mrows, status, d2, mst = s.register_mesh_trimmed(mesh, keep=1.0, border=PAIR, T0=T0)
+    assert st["steps"] >= 1
+    rows_equal(mrows, rows)
+    stats_equal(mst, st)
+    assert same(mT, T)
+    for w in mrows:
+        assert w["paired"] == w["pairs"] and w["on_border"] == 0
+    assert not np.any(status == TRIMMED) and not np.any(status == ON_BORDER) and int((status == KEPT).sum()) == mrows[-1]["pairs"]
+    assert mrows[-1]["trim_bits"] == int(d2[status == KEPT].view(np.uint32).max())
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_a_closed_mesh_has_no_border_to_reject_on(engine_mod):
+    v, t = cube(size=10.0)
+    rng = np.random.default_rng(5)
+    shell = rng.uniform(-1.0, 11.0, (400, 3)).astype(np.float32)
+    s = scan_engine(engine_mod, shell)
+    mesh = s.trimesh(v, t)
+    a, _ = chain_parity(s, mesh, v, t, border=REJECT, iterations=3)
+    b = s.register_mesh_trimmed(mesh, border=PAIR, iterations=3)
+    assert same(a, b) and a[1][0]["paired"] > 100 and not np.any(a[2] == ON_BORDER)
+    stats, _ = mesh.topology(maps=False)
+    assert stats["closed"] == 1 and stats["border_edges"] == 0
+    mesh.close(); s.close()
+
+
+def tied_heights(run=7):
+    """digit_heights()'s ten heights, each `run` times, interleaved: runs of equal keys whose distinct values straddle the bin edges of
+    the low, the middle and the top digit"""
+    return np.tile(digit_heights(), run)
+
+
+@pytest.mark.gpu
+def test_cut_on_ties_and_digit_edges(engine_mod):
+    """the planar sheet: D2 of a point strictly inside it is z * z, exact in double for these heights, and the key its float.  The rank
+    is put on the first and on the last member of every run of equal keys, on 1 and on paired: every tie is kept, kept >= k"""
+    v, t = sheet(8, 8, 4.0)
+    z = tied_heights()
+    run, paired = 7, len(z)
+    keys = np.sort((z.astype(np.float64) ** 2).astype(np.float32).view(np.uint32))
+    distinct = np.unique(keys)
+    assert len(distinct) == 10 and len({int(k) >> 21 for k in distinct}) >= 3 and len({int(k) >> 10 for k in distinct}) >= 6
+    s = engine_mod.Engine(0, **KW0)
+    s.set_cloud(flat_points(z))
+    mesh = s.trimesh(v, t)
+    ranks = sorted({1, paired} | {run * j + 1 for j in range(10)} | {run * j + run for j in range(10)})
+    for k in ranks:
+        keep = (k - 0.5) / paired                                            # ceil(keep * paired) = k
+        assert trim_rank(keep, paired) == k
+        for border in (PAIR, REJECT):                                        # strictly inside: the rule rejects nothing
+            row, status, d2, want = terms_parity(s, mesh, v, t, max_dist=3.0, lock_eps=1e-3, keep=keep, border=border)
+            j = (k - 1) // run
+            assert want["k"] == k and row["paired"] == paired and row["pairs"] == run * (j + 1) >= k and row["trim_bits"] == int(distinct[j])
+            assert row["on_border"] == 0
+    row, status, d2, want = terms_parity(s, mesh, v, t, max_dist=3.0, lock_eps=1e-3, keep=1.0)
+    assert row["pairs"] == paired and np.all(status == KEPT) and np.array_equal(d2, (z.astype(np.float64) ** 2).astype(np.float32))
+    mesh.close(); s.close()
+
+
+def few_kept_scan(k):
+    """k points of the contaminated case's clean part well inside the mesh, 20 more 50 mm above it"""
+    v, t, scan, moved, raised = dirty_case()
+    inside = np.nonzero((scan[:, 0] > 10) & (scan[:, 0] < 55) & (scan[:, 1] > 5) & (scan[:, 1] < 35) & ~raised)[0]
+    far = scan[inside[40:60]] + np.array([0.0, 0.0, 50.0])
+    return np.concatenate([scan[inside[:k]], far]).astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [0, 5, 6, 7])
+def test_few_pairs(engine_mod, k):
+    """k pairs, all kept at keep = 1: no step below 6; without a pair the cut is the float NaN and the maps hold no number"""
+    v, t = dirty_case()[:2]
+    s = scan_engine(engine_mod, few_kept_scan(k))
+    mesh = s.trimesh(v, t)
+    (T, rows, status, d2, st), _ = chain_parity(s, mesh, v, t, T0=part_way(0.1), iterations=3, keep=1.0, border=REJECT)
+    assert rows[0]["pairs"] == rows[0]["paired"] == k and st["indexed"] == k + 20 and rows[0]["on_border"] == 0
+    assert int((status == KEPT).sum()) == rows[-1]["pairs"] and int((status == UNPAIRED).sum()) == k + 20 - rows[-1]["paired"]
+    if k == 0:
+        assert rows[0]["trim_bits"] == NAN32_BITS and math.isnan(st["rms_before"]) and np.all(np.isnan(d2))
+    if k < 6:
+        assert st["steps"] == 0 and st["converged"] == 0 and len(rows) == 1 and same(T, part_way(0.1))
+    else:
+        assert st["steps"] >= 1
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_every_candidate_rejected_on_the_border(engine_mod):
+    """points over the outside of the planar sheet only: every candidate's closest point is on the outline"""
+    v, t, pts = flat_overhang()
+    out = pts[outside_open(pts, 0.0, 32.0)]
+    s = scan_engine(engine_mod, out)
+    mesh = s.trimesh(v, t)
+    (T, rows, status, d2, st), _ = chain_parity(s, mesh, v, t, border=REJECT, max_dist=3.0, iterations=3)
+    assert rows[0]["paired"] == 0 and rows[0]["pairs"] == 0 and rows[0]["on_border"] == len(out) > 100 and rows[0]["trim_bits"] == NAN32_BITS
+    assert st["steps"] == 0 and len(rows) == 1 and np.all(status == ON_BORDER) and np.all(d2.view(np.uint32) == NAN32_BITS)
+    (T, rows, status, d2, st), _ = chain_parity(s, mesh, v, t, border=PAIR, max_dist=3.0, iterations=1, lock_eps=1e-3)
+    assert rows[0]["paired"] == len(out) and rows[0]["on_border"] == 0
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_scatter_with_a_long_run_dropped_unpaired_and_border_points(engine_mod):
+    """more than 2 x 256 points, not a multiple of 64: every seventh not finite (DROPPED), the wavy case's raised tenth beyond max_dist
+    (UNPAIRED), its 3 mm overhang (BORDER); then cap < n, and NULL maps"""
+    v, t, _, moved, _ = wavy_case()
+    pts = moved[:843].copy()
+    pts[3::7, 1] = np.nan
+    pts[5::49, 0] = np.inf
+    s = scan_engine(engine_mod, pts)
+    mesh = s.trimesh(v, t)
+    assert len(pts) > 2 * 256 and len(pts) % 64 != 0
+    (T, rows, status, d2, st), want = chain_parity(s, mesh, v, t, border=REJECT, iterations=3)
+    bad = ~np.isfinite(pts).all(axis=1)
+    assert st["n"] == 843 and st["indexed"] == 843 - int(bad.sum()) and np.all(status[bad] == DROPPED) and not np.any(status[~bad] == DROPPED)
+    for code in (KEPT, TRIMMED, UNPAIRED, ON_BORDER):
+        assert np.any(status == code), code
+    E = engine_mod
+    mp = E.MeshTrimmedRegistrationParams(E.TrimmedRegistrationParams(E.RegistrationParams(2.0, 3, 1e-6, 1e-9), 0.8), REJECT)
+    raw = E.RegistrationStats()
+    st8 = np.full(600, 0xA5, np.uint8); d8 = np.full(600, 7.0, np.float32)
+    ub, fp = ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_float)
+    assert s.L.ppp_register_mesh_trimmed(s.h, mesh.m, ctypes.byref(mp), None, None, 0, st8.ctypes.data_as(ub), d8.ctypes.data_as(fp), 517, ctypes.byref(raw)) == 0
+    assert st8[:517].tobytes() == status[:517].tobytes() and d8[:517].tobytes() == d2[:517].tobytes()
+    assert np.all(st8[517:] == 0xA5) and np.all(d8[517:] == 7.0)
+    stats_equal(E._registration_stats(raw), st)
+    raw2 = E.RegistrationStats()
+    assert s.L.ppp_register_mesh_trimmed(s.h, mesh.m, ctypes.byref(mp), None, None, 0, None, None, 843, ctypes.byref(raw2)) == 0
+    assert s.L.ppp_register_mesh_trimmed(s.h, mesh.m, ctypes.byref(mp), None, None, 0, None, None, 0, None) == 0
+    stats_equal(E._registration_stats(raw2), st)
+    got = s.register_mesh_trimmed(mesh, border=REJECT, iterations=3, maps=False)
+    assert got[2] is None and got[3] is None and same(got[0], T)
+    mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_orientation_changes_neither_the_rows_nor_the_border_set(engine_mod):
+    """the same triangles under PPP_TRIMESH_VIEWPOINT from below, which turns every facet over: the records are the same, the normal's
+    sign enters no word, and an edge with one half-edge is a border edge in either direction"""
+    for v, t, pts, md in (wavy_case()[:2] + (wavy_case()[3], 2.0), flat_overhang() + (3.0,)):
+        s = scan_engine(engine_mod, pts)
+        mesh = s.trimesh(v, t)
+        turned = s.trimesh(v, t, orient=VIEWPOINT, viewpoint=(30.0, 20.0, -500.0))
+        assert np.all(turned.nearest(np.ascontiguousarray(v[::5] + np.float32([0, 0, 0.25])), 1.0)[2] < 0)   # its normals point down
+        for border in (PAIR, REJECT):
+            a = s.register_mesh_trimmed(mesh, border=border, max_dist=md, iterations=3)
+            b = s.register_mesh_trimmed(turned, border=border, max_dist=md, iterations=3)
+            assert same(a, b) and (a[1][0]["on_border"] > 0) == (border == REJECT)
+        turned.close(); mesh.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_same_bits_on_fresh_handles_and_nothing_stored_is_touched(engine_mod):
+    v, t, scan, moved, inside = overhang_case()
+    kw = dict(max_dist=OVERHANG["max_dist"], iterations=3)
+    out = []
+    for _ in range(2):
+        s = scan_engine(engine_mod, moved)
+        mesh = s.trimesh(v, t)
+        dev0 = s.mesh_deviation(mesh)
+        reg0 = s.register_mesh(mesh, iterations=3)
+        rob0 = s.register_mesh_robust(mesh, iterations=3)
+        cloud0 = s.cloud().copy()
+        near0 = mesh.nearest(np.ascontiguousarray(moved[::7]), 2.0)
+        s.enable_timing(True)
+        s.kernel_times()
+        pair = s.register_mesh_trimmed(mesh, border=PAIR, **kw)
+        times = s.kernel_times()
+        assert "k_mesh_trim_pair<pair>" in times and not any(k.startswith("k_tt_") for k in times), sorted(times)   # no topology is built
+        rej = s.register_mesh_trimmed(mesh, border=REJECT, **kw)
+        times = s.kernel_times()
+        assert "k_mesh_trim_pair<reject>" in times and "k_tt_corners" in times and "k_mesh_trim_scatter" in times, sorted(times)
+        assert same(s.register_mesh_trimmed(mesh, border=REJECT, **kw), rej)
+        assert not any(k.startswith("k_tt_") for k in s.kernel_times())      # built once
+        s.enable_timing(False)
+        out.append((pair, rej))
+        s.mesh_trimmed_registration_terms(mesh, T=part_way(0.5), border=REJECT)
+        assert same(s.mesh_deviation(mesh), dev0) and same(s.register_mesh(mesh, iterations=3), reg0) and same(s.cloud(), cloud0)
+        assert same(s.register_mesh_robust(mesh, iterations=3), rob0) and same(mesh.nearest(np.ascontiguousarray(moved[::7]), 2.0), near0)
+        assert same(s.register_mesh_trimmed(mesh, border=PAIR, **kw), pair)
+        mesh.close(); s.close()
+    assert same(out[0], out[1]) and out[0][1][4]["steps"] >= 3 and not same(out[0][0][0], out[0][1][0])
+    # the plan of a handle that has one survives both calls
+    from polishpathplanning_amd import synth
+    pts, cfg = synth.make_config("tiny_5k")
+    w = engine_mod.Engine(0, tool_radius=cfg["tool_radius"], walk=1)
+    w.set_cloud(pts)
+    S = w.gen_path(); W = w.get_path(); wp = w.waypoints().copy()
+    mesh = w.trimesh(v, t)
+    w.register_mesh_trimmed(mesh, border=REJECT, iterations=2)
+    w.mesh_trimmed_registration_terms(mesh)
+    assert (w.gen_path(), w.get_path()) == (S, W) and same(w.waypoints(), wp)
+    mesh.close(); w.close()
+
+
+@pytest.mark.gpu
+def test_refusals(engine_mod):
+    from polishpathplanning_amd import synth
+    from polishpathplanning_amd.robot_path import slice_ranges
+    E = engine_mod
+    v, t, _, moved, _ = wavy_case()
+    s = scan_engine(engine_mod, moved)
+    mesh = s.trimesh(v, t)
+    L = s.L
+    dp = ctypes.POINTER(ctypes.c_double)
+    good = dict(max_dist=2.0, iterations=3, min_step=1e-6, lock_eps=1e-9, keep=0.8, border=REJECT)
+
+    def raw(h, m, T0=None, rows=None, cap=0, params=True, **k):
+        p = dict(good, **k)
+        mp = E.MeshTrimmedRegistrationParams(E.TrimmedRegistrationParams(E.RegistrationParams(p["max_dist"], p["iterations"], p["min_step"], p["lock_eps"]),
+                                                                         p["keep"]), p["border"])
+        st, row = E.RegistrationStats(), E.MeshTrimmedRegistrationRow()
+        t12 = None if T0 is None else np.ascontiguousarray(np.asarray(T0, np.float64).reshape(12))
+        tp = None if t12 is None else t12.ctypes.data_as(dp)
+        a = L.ppp_register_mesh_trimmed(h.h, m, ctypes.byref(mp) if params else None, tp, rows, cap, None, None, 0, ctypes.byref(st))
+        b = L.ppp_get_mesh_trimmed_registration_terms(h.h, m, ctypes.byref(mp) if params else None, tp, ctypes.byref(row), None, None, 0, ctypes.byref(st))
+        return a, b
+
+    def refused(code, h=None, m=mesh.m, loop_only=False, **k):
+        h = h or s
+        a, b = raw(h, m, **k)
+        text = L.ppp_last_error(h.h).decode()
+        assert a == code and (loop_only or b == code), (k, a, b, text)
+        assert text, k                                                       # the last-error text is set
+        assert raw(s, mesh.m) == (0, 0)                                      # and the handle still works
+
+    refused(E.ERR_ARG, m=None)
+    refused(E.ERR_ARG, params=False)
+    for bad in (dict(keep=0.0), dict(keep=-0.5), dict(keep=NAN), dict(keep=1.0000001), dict(keep=INF), dict(border=2), dict(border=-1),
+                dict(max_dist=0.0), dict(max_dist=INF), dict(max_dist=NAN), dict(lock_eps=0.0), dict(lock_eps=1.0), dict(min_step=-1.0)):
+        refused(E.ERR_ARG, **bad)
+    for bad in (dict(iterations=0), dict(iterations=65)):
+        refused(E.ERR_ARG, loop_only=True, **bad)
+    Tb = IDENTITY.copy(); Tb[1, 2] = NAN
+    refused(E.ERR_ARG, T0=Tb)
+    refused(E.ERR_ARG, loop_only=True, rows=None, cap=1)
+    refused(E.ERR_ARG, max_dist=3.0e6)                                        # shift < 16: n max_dist^2 leaves too few fractional bits
+    assert raw(s, mesh.m, keep=1.0, border=PAIR) == (0, 0)
+    assert L.ppp_register_mesh_trimmed(None, mesh.m, None, None, None, 0, None, None, 0, None) == E.ERR_ARG
+    empty = E.Engine(0, **KW0)                                               # a handle without a cloud
+    a, b = raw(empty, mesh.m)
+    assert a == b == E.ERR_ARG and L.ppp_last_error(empty.h).decode()
+    empty.close()
+    pts, cfg = synth.make_config("tiny_5k")
+    w = E.Engine(0, tool_radius=cfg["tool_radius"], walk=1)
+    w.set_cloud(pts)
+    S = w.gen_path()
+    lo, hi = slice_ranges(S, 2)[1]
+    h = E.Engine(0, tool_radius=cfg["tool_radius"], walk=1, slice_begin=lo, slice_end=hi)
+    h.set_cloud(pts)
+    part = part_handle(engine_mod, w, pts, cfg)
+    for bad in (h, part):
+        a, b = raw(bad, mesh.m)
+        assert a == b == E.ERR_UNSUPPORTED and L.ppp_last_error(bad.h).decode()
+    assert raw(w, mesh.m) == (0, 0)                                          # the whole-cloud handle of the same cloud is served
+    chain_parity(s, mesh, v, t, iterations=2, border=REJECT)                 # every refusal leaves a later good call working
+    for e in (part, w, h, s):
+        e.close()
+    mesh.close()
+
+
+@pytest.mark.gpu
+def test_a_mesh_on_another_device_is_refused(engine_mod):
+    from test_deviation_tiles import device_count
+    if device_count() < 2:
+        pytest.skip("needs two GPUs in one process: this machine shows %d" % device_count())
+    E = engine_mod
+    v, t, _, moved, _ = wavy_case()
+    s = scan_engine(engine_mod, moved)
+    other = E.Engine(1, **KW0)
+    far = other.trimesh(v, t)
+    for call in (s.register_mesh_trimmed, s.mesh_trimmed_registration_terms):
+        with pytest.raises(E.PPPError) as ex:
+            call(far)
+        assert ex.value.code == E.ERR_ARG
+    far.close(); other.close(); s.close()
+
+
+@pytest.mark.gpu
+def test_connect_registers_trimmed_against_the_triangles(engine_mod, tmp_path):
+    """PPP_REGISTER=mesh-trimmed PPP_REGISTER_KEEP=0.8 PPP_REGISTER_BORDER=reject PPP_DEVIATION=<part.stl> ./connect <scan.pcd>: exit
+    status 0, the trimmed line with ppp_register_mesh_trimmed's numbers, ppp_register's lines behind it -- the last carries the T the
+    Engine call gives -- and the deviation taken behind them"""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), "connect"])
+    v, t, scan, moved, raised = dirty_case()
+    soup = v[t]                                                              # float32[768, 3, 3]; millimetres, as the scan
+    stl, scan_pcd = str(tmp_path / "part.stl"), str(tmp_path / "scan.pcd")
+    engine_mod.save_stl(stl, soup)
+    engine_mod.save_pcd(scan_pcd, moved, binary=True)
+    conf = tmp_path / "config.txt"
+    conf.write_text("Tool_Radius = 6\npathFile = %s\nPathResolution = 7\nRPYresolution = 7\nEnd effector length = 0.3\n"
+                    "Smooth = false\nAlignment = false\nChangeRange = false\nRemoveOutlier = false\nDynamic_adjustment = false\n"
+                    "Adjust_Threshold = 1\ntoolthickness = 10\ndepth = 0.01\n" % str(tmp_path / "wp.txt"))
+    exe = os.path.join(ROOT, "examples", "connect")
+    env = {k: val for k, val in os.environ.items() if not k.startswith("PPP_")}
+    env.update(PPP_CONFIG=str(conf), PPP_DEVIATION=stl, PPP_REGISTER="mesh-trimmed", PPP_REGISTER_KEEP="0.8", PPP_REGISTER_BORDER="reject",
+               PPP_DEVIATION_EXACT="1")
+    run = subprocess.run([exe, scan_pcd], env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert run.returncode == 0, run.stderr
+    out = run.stdout.splitlines()
+    reg = [ln for ln in out if ln.startswith("registration: ")]
+    print("\n".join(reg))
+    s = scan_engine(engine_mod, moved)
+    mesh = s.trimesh_stl(stl)
+    T, rows, status, d2, st = s.register_mesh_trimmed(mesh, keep=0.8, border=REJECT)
+    want = ("registration: trimmed to the mesh, keep %f, border reject: %d of %d pairs kept, %d on the border, cut %f mm; after %d steps %d of %d, %d on the border, cut %f mm"
+            % (0.8, rows[0]["pairs"], rows[0]["paired"], rows[0]["on_border"], math.sqrt(rows[0]["trim_d2"]), st["steps"], rows[-1]["pairs"],
+               rows[-1]["paired"], rows[-1]["on_border"], math.sqrt(rows[-1]["trim_d2"])))
+    assert reg[0] == want and st["steps"] >= 1 and rows[-1]["pairs"] < rows[-1]["paired"] and rows[-1]["on_border"] > 0
+    assert reg[-3:] == ["registration: T %f %f %f %f" % tuple(T[r]) for r in range(3)] and len(reg) == 6 and st["converged"] == 1   # the cloud is moved by it
+    dev = [ln for ln in out if ln.startswith("deviation: ")]
+    assert dev and " matched, " in dev[0] and out.index(dev[0]) > out.index(reg[-1])
+    mesh.close(); s.close()
