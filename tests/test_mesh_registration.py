@@ -39,10 +39,12 @@ def mesh_box(rv, tris):
     return mn.astype(np.float32), mx.astype(np.float32), (p0[fi], p1[fi], p2[fi], N[fi], A2[fi])
 
 
-def restate_mesh_terms(P, rv, tris, max_dist, T, flip=False, chunk=256):
+def restate_mesh_terms(P, rv, tris, max_dist, T, flip=False, chunk=256, search=None):
     """One evaluation, as restate_terms() of tests/test_registration.py gives it: dict(T, pairs, A, b, E, shift, centre, length, n,
     indexed) and, for the census, moved float64[indexed, 3], paired bool[indexed], region uint8[pairs].  P float32[n, 3] the scan,
-    rv / tris the mesh's resident vertices and indices, T float64[3, 4]; flip: every facet normal negated"""
+    rv / tris the mesh's resident vertices and indices, T float64[3, 4]; flip: every facet normal negated.  search: the brute force
+    below made by the caller -- search(m, ok, (a, b, c), md2) gives (paired, win, X, D2, branch) of the moved points m float64[indexed, 3]
+    as the loop leaves them, zeros without a pair --, so that evaluations at one T share it (tests/test_mesh_registration_adversaries.py)"""
     P = np.ascontiguousarray(P, np.float32)
     T = np.asarray(T, np.float64).reshape(3, 4)
     n = len(P)
@@ -59,7 +61,9 @@ def restate_mesh_terms(P, rv, tris, max_dist, T, flip=False, chunk=256):
     win = np.zeros(len(rows), np.int64)
     X = np.zeros((len(rows), 3))
     branch = np.zeros(len(rows), np.int64)
-    for s in range(0, len(rows), chunk):
+    if search is not None:
+        paired, win, X, _, branch = search(m, ok, (a, b, c), md2)
+    for s in range(0, len(rows) if search is None else 0, chunk):
         sel = np.nonzero(ok[s:s + chunk])[0] + s
         if not len(sel) or not len(a):
             continue
@@ -87,13 +91,13 @@ def restate_mesh_terms(P, rv, tris, max_dist, T, flip=False, chunk=256):
                 moved=m, paired=paired, region=BRANCH_REGION[branch[paired]])
 
 
-def restate_register_mesh(P, rv, tris, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+def restate_register_mesh(P, rv, tris, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, search=None):
     """(T, rows, stats) as Engine.register_mesh gives them: restate_register()'s loop of tests/test_registration.py over
     restate_mesh_terms()"""
     T = IDENTITY.copy() if T0 is None else np.asarray(T0, np.float64).reshape(3, 4).copy()
     rows, converged, locked, stop = [], 0, 0, False
     while True:
-        row = restate_mesh_terms(P, rv, tris, max_dist, T)
+        row = restate_mesh_terms(P, rv, tris, max_dist, T, search=search)
         row.update(locked=ALL_LOCKED, step2=NAN)
         rows.append(row)
         if stop or len(rows) > iterations:

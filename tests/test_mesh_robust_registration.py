@@ -31,10 +31,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ---------------------------------------------------------------- the restatement
 
 
-def restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune=TUNE, sigma_min=SIGMA_MIN, flip=False, chunk=256):
+def restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune=TUNE, sigma_min=SIGMA_MIN, flip=False, chunk=256, search=None):
     """One evaluation as restate_robust_terms() of tests/test_robust_registration.py gives it -- T, pairs (= paired), the weighted A / b /
     E, weight_sum, used, k, median_bits, sigma, shift, centre, length, n, indexed, status uint8[n], weight float32[n], residual
-    float64[n] by cloud index -- on restate_mesh_terms()'s pairs; region uint8[pairs] for the census.  flip: every facet turned over"""
+    float64[n] by cloud index -- on restate_mesh_terms()'s pairs; region uint8[pairs] for the census.  flip: every facet turned over;
+    search: restate_mesh_terms()'s"""
     P = np.ascontiguousarray(P, np.float32)
     T = np.asarray(T, np.float64).reshape(3, 4)
     n = len(P)
@@ -52,7 +53,9 @@ def restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune=TUNE, sigma_min=SIG
     win = np.zeros(len(rows), np.int64)
     X = np.zeros((len(rows), 3))
     branch = np.zeros(len(rows), np.int64)
-    for s in range(0, len(rows), chunk):
+    if search is not None:
+        paired, win, X, _, branch = search(m, ok, (a, b, c), md2)
+    for s in range(0, len(rows) if search is None else 0, chunk):
         sel = np.nonzero(ok[s:s + chunk])[0] + s
         if not len(sel) or not len(a):
             continue
@@ -99,13 +102,14 @@ def restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune=TUNE, sigma_min=SIG
                 region=BRANCH_REGION[branch[paired]])
 
 
-def restate_register_mesh_robust(P, rv, tris, tune=TUNE, sigma_min=SIGMA_MIN, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, flip=False):
+def restate_register_mesh_robust(P, rv, tris, tune=TUNE, sigma_min=SIGMA_MIN, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, flip=False,
+                                 search=None):
     """(T, rows, status, weight, residual, stats) as Engine.register_mesh_robust gives them: restate_register_robust()'s loop of
     tests/test_robust_registration.py -- "fewer than 6 pairs" read as used < 6 -- over restate_mesh_robust_terms()"""
     T = IDENTITY.copy() if T0 is None else np.asarray(T0, np.float64).reshape(3, 4).copy()
     rows, converged, locked, stop = [], 0, 0, False
     while True:
-        row = restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune, sigma_min, flip)
+        row = restate_mesh_robust_terms(P, rv, tris, max_dist, T, tune, sigma_min, flip, search=search)
         row.update(locked=ALL_LOCKED, step2=NAN)
         rows.append(row)
         if stop or len(rows) > iterations:
@@ -323,10 +327,12 @@ def test_orientation_negates_the_residual_map_alone():
 # ---------------------------------------------------------------- GPU
 
 
-def terms_parity(s, mesh, v, t, T=None, max_dist=2.0, lock_eps=1e-9, **kw):
-    """Engine.mesh_robust_registration_terms against restate_mesh_robust_terms on the engine's own cloud: the row, the maps, stats"""
-    want = restate_mesh_robust_terms(s.cloud(), v, t, max_dist, IDENTITY if T is None else T, **kw)
-    want.update(locked=ALL_LOCKED, step2=NAN)
+def terms_parity(s, mesh, v, t, T=None, max_dist=2.0, lock_eps=1e-9, want=None, **kw):
+    """Engine.mesh_robust_registration_terms against restate_mesh_robust_terms on the engine's own cloud (want: that evaluation, made
+    by the caller): the row, the maps, stats"""
+    if want is None:
+        want = restate_mesh_robust_terms(s.cloud(), v, t, max_dist, IDENTITY if T is None else T, **kw)
+    want = dict(want, locked=ALL_LOCKED, step2=NAN)
     row, status, weight, residual, st = s.mesh_robust_registration_terms(mesh, T=T, max_dist=max_dist, lock_eps=lock_eps, **kw)
     brows_equal([row], [want])
     maps_equal((status, weight, residual), (want["status"], want["weight"], want["residual"]))
@@ -336,9 +342,10 @@ def terms_parity(s, mesh, v, t, T=None, max_dist=2.0, lock_eps=1e-9, **kw):
     return row, status, weight, residual, want
 
 
-def chain_parity(s, mesh, v, t, **kw):
+def chain_parity(s, mesh, v, t, want=None, **kw):
     got = s.register_mesh_robust(mesh, **kw)
-    want = restate_register_mesh_robust(s.cloud(), v, t, **kw)
+    if want is None:
+        want = restate_register_mesh_robust(s.cloud(), v, t, **kw)
     T, rows, status, weight, residual, st = got
     print("steps %d (want %d) converged %d (want %d) used %r paired %r sigma %r" % (st["steps"], want[5]["steps"], st["converged"], want[5]["converged"],
                                                                                  [w["used"] for w in rows], [w["pairs"] for w in rows], [w["sigma"] for w in rows]))

@@ -54,12 +54,16 @@ def _topology(vbytes, tbytes):
 
 
 def topology_of(rv, tris):
+    """restate_topology()'s tables by the CALLER's triangle number, made once per mesh.  Degenerate triangles may stand in the list, as
+    ppp_trimesh_topology.h takes them: they weld nothing and make no half-edge, and their rows hold -1 / 255 / NaN; the valid subset is
+    not needed (border_of() reads the rows of winners only, and a winner is valid)"""
     return _topology(np.ascontiguousarray(rv, np.float32).tobytes(), np.ascontiguousarray(tris, np.int32).tobytes())
 
 
-def restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep=0.8, border=PAIR, chunk=256):
+def restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep=0.8, border=PAIR, chunk=256, search=None):
     """One evaluation: restate_mesh_terms()'s dict over the KEPT pairs (pairs = kept) with paired, k, trim_bits (tau; the float quiet
-    NaN without a pair), on_border, status uint8[n] and d2 float32[n] by cloud index; region uint8[kept] for the census"""
+    NaN without a pair), on_border, status uint8[n] and d2 float32[n] by cloud index; region uint8[kept] for the census.  search:
+    restate_mesh_terms()'s, here for the candidates"""
     P = np.ascontiguousarray(P, np.float32)
     T = np.asarray(T, np.float64).reshape(3, 4)
     n = len(P)
@@ -79,7 +83,9 @@ def restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep=0.8, border=PAIR, 
     X = np.zeros((len(rows), 3))
     best = np.zeros(len(rows))
     branch = np.zeros(len(rows), np.int64)
-    for s in range(0, len(rows), chunk):
+    if search is not None:
+        cand, win, X, best, branch = search(m, ok, (a, b, c), md2)
+    for s in range(0, len(rows) if search is None else 0, chunk):
         sel = np.nonzero(ok[s:s + chunk])[0] + s
         if not len(sel) or not len(a):
             continue
@@ -128,13 +134,13 @@ def restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep=0.8, border=PAIR, 
                 k=k, trim_bits=tau, on_border=int(onb.sum()), status=status, d2=d2, region=BRANCH_REGION[branch[kept]])
 
 
-def restate_register_mesh_trimmed(P, rv, tris, keep=0.8, border=PAIR, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+def restate_register_mesh_trimmed(P, rv, tris, keep=0.8, border=PAIR, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None, search=None):
     """(T, rows, status, d2, stats) as Engine.register_mesh_trimmed gives them: restate_register_mesh()'s loop -- pairs read as kept --
     over restate_mesh_trimmed_terms()"""
     T = IDENTITY.copy() if T0 is None else np.asarray(T0, np.float64).reshape(3, 4).copy()
     rows, converged, locked, stop = [], 0, 0, False
     while True:
-        row = restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep, border)
+        row = restate_mesh_trimmed_terms(P, rv, tris, max_dist, T, keep, border, search=search)
         row.update(locked=ALL_LOCKED, step2=NAN)
         rows.append(row)
         if stop or len(rows) > iterations:
