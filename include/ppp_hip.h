@@ -731,7 +731,8 @@ int  ppp_register(ppp_handle h, ppp_handle ref, const ppp_registration_params *r
    winning facet's (pseudonormals are out of scope), and the scan's overhang beyond an open mesh's border pairs there with the
    border facet's normal as long as it lies within max_dist (no pair is rejected on the border here).  Robust weights are
    ppp_register_mesh_robust's, trimmed weights and the rejection of border pairs ppp_register_mesh_trimmed's (both below), the
-   start from an unknown pose is ppp_register_mesh_global's (further down); tiles over slice ranges are not offered.
+   start from an unknown pose is ppp_register_mesh_global's (further down); tiles over slice ranges are ppp_register_mesh_tiles's
+   (further down).
    ppp_get_mesh_registration_terms evaluates once at T12 (NULL: the identity) and takes no step; ppp_register_mesh runs the loop
    from T0_12; row, rows and stats are filled as ppp_get_registration_terms and ppp_register fill them.  Both build h's slab index
    where it is missing, enqueue the whole chain (iterations + 1 evaluations, iterations steps) on h's stream and wait once; the
@@ -1434,6 +1435,79 @@ int    ppp_register_robust_tiles(const ppp_handle *hs, const ppp_handle *refs, s
                                  unsigned char *const *status, float *const *weight, double *const *residual,
                                  unsigned char *const *owned, size_t cap,
                                  ppp_register_tiles_stats *stats);
+/* ---- the mesh calls for the points a handle owns ----
+   The exact deviation (unsigned and signed) and the plain point-to-plane registration against a resident triangle mesh, for a
+   scan held as slice-range tiles.  The mesh is resident whole on every device, so nothing on the reference's side needs a halo,
+   a range condition or a refusal: only the scan's own smoothing reaches across a seam.
+   ppp_get_mesh_deviation_tile / ppp_get_mesh_signed_deviation_tile (B.144-B.146): ppp_get_mesh_deviation /
+   ppp_get_mesh_signed_deviation for the points h owns.  h: a slice-range handle of the scan (it holds the whole cloud and
+   indexes its range plus range_margin), or a whole-cloud handle, which owns every indexed point; ownership is ppp_range_owned's
+   rule and no other.  m: a mesh on h's device.  There is no halo argument: the call evaluates the scan's indexed points in
+   W(smooth_radius), ppp_get_deviation_tile's widened interval, and h must index it unless its index reaches the cloud's end on
+   that side -- decided on the host from h's plan, before any launch: PPP_ERR_ARG, never a silent change of a smoothed value.
+     maps      by cloud index of h, the first min(cap, n) entries.  For every OWNED point every map holds exactly the bits the
+               whole-cloud call gives for the same cloud on a whole-cloud handle with the same dp and a mesh of the same
+               triangles (whatever its cell).  Every other point has status PPP_DEV_DROPPED, tri_index -1, region and feature
+               255, deviation / signed_distance, smoothed and distance the NaN, target +0, flags 0 and owned[i] = 0.  The halo
+               points the smoothing needed are evaluated, enter the owned points' integer sums and are reported nowhere.
+     part      dev: ppp_get_deviation_tile's part over the owned points (evaluated = owned + halo points; a tile's launches
+               cover the index positions of the slabs that meet W(smooth_radius), not n); on_face, on_edge, on_vertex and
+               max_distance (NaN when matched == 0) over the owned matched points; the signed call adds on_border, irregular,
+               fallback, negative and positive over them.
+   Needs a cloud and parameters, not a pass; builds what the whole-cloud call builds (the signed call the mesh's topology where
+   it is missing), keeps nothing and changes nothing stored on the handle.  Every output may be NULL.  PPP_ERR_ARG as the
+   whole-cloud call, and the range condition above; PPP_ERR_UNSUPPORTED for a part handle (ppp_set_cloud_part).
+   ppp_merge_mesh_deviation_tiles / ppp_merge_mesh_signed_deviation_tiles (B.147; host only, no handle): the whole cloud's
+   ppp_mesh_deviation_stats / ppp_mesh_signed_deviation_stats, bit for bit, from the parts and maps of ranges that tile the walk.
+   dev is ppp_merge_deviation_tiles' result on the parts' dev and the maps v (the smoothed map: the deviation or signed distance
+   where smooth_radius == 0), status, target, owned; the counts add; max_distance is the maximum, NaN when nothing matched.
+   PPP_ERR_ARG: what ppp_merge_deviation_tiles refuses (a point two tiles own among it), a part whose counts by region do not
+   add up to its matched points, a max_distance that is negative or NaN on a part that matched.
+   ppp_get_mesh_registration_terms_tile (B.148): ppp_get_mesh_registration_terms over the points h owns; ownership goes by the
+   resident, unmoved x.  row: T = T12 (NULL: the identity), pairs / A / b / E over the owned points' pairs, locked 63, step2 NaN.
+   part: ppp_get_registration_terms_tile's, with centre and length from the mesh's box and shift from n = cloud->size() of h, as
+   ppp_register_mesh defines them.  There is no range condition and no PPP_ERR_CAPACITY: the mesh is whole.  The rows and parts
+   go through ppp_merge_registration_terms and ppp_registration_step unchanged.
+   ppp_register_mesh_tiles (B.149): ppp_register_mesh's loop over tiles, ppp_register_tiles's in shape: hs[i] holds the scan
+   with range i, ms[i] is the mesh on hs[i]'s device (one mesh may stand in every slot when all tiles share a device); meshes in
+   different slots must agree on triangles, indexed and the box, bit for bit.  Per evaluation T goes to every tile's device,
+   the search and the sum are enqueued on every tile's own stream, the words come back with one asynchronous copy per tile, the
+   host waits for all tiles, merges, steps and records the row: one host round trip per evaluation, where ppp_register_mesh has
+   none.  For ranges that tile the walk T, every row and every field of stats->reg are the bits of ppp_register_mesh on a
+   whole-cloud handle with the same parameters and T0.  A tile's error ends the loop and is returned (the text on that tile's
+   handle), with its index in stats->failed_tile (-1 otherwise).  PPP_ERR_ARG: ppp_register_tiles's and ppp_register_mesh's
+   refusals, a NULL mesh, meshes that disagree.  PPP_ERR_UNSUPPORTED: a part handle.
+   The whole-cloud calls still refuse a slice-range handle; the robust and trimmed mesh loops have no tiled form yet. */
+typedef struct {
+    ppp_deviation_tile_stats dev;
+    size_t on_face, on_edge, on_vertex;  /* the owned matched points by region */
+    double max_distance;                 /* over them; NaN when dev.matched == 0 */
+} ppp_mesh_deviation_tile_stats;
+typedef struct {
+    ppp_mesh_deviation_tile_stats mesh;
+    size_t on_border, irregular, fallback, negative, positive;
+} ppp_mesh_signed_deviation_tile_stats;
+int ppp_get_mesh_deviation_tile(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp,
+                                double *deviation, double *smoothed, double *distance, int *tri_index,
+                                unsigned char *region, unsigned char *status, double *target, unsigned char *owned,
+                                size_t cap, ppp_mesh_deviation_tile_stats *part);
+int ppp_get_mesh_signed_deviation_tile(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp,
+                                       double *signed_distance, double *smoothed, double *distance, int *tri_index,
+                                       unsigned char *region, unsigned char *feature, unsigned char *flags,
+                                       unsigned char *status, double *target, unsigned char *owned,
+                                       size_t cap, ppp_mesh_signed_deviation_tile_stats *part);
+int ppp_merge_mesh_deviation_tiles(size_t tiles, const ppp_mesh_deviation_tile_stats *parts, const double *const *v,
+                                   const unsigned char *const *status, const double *const *target,
+                                   const unsigned char *const *owned, ppp_mesh_deviation_stats *stats);
+int ppp_merge_mesh_signed_deviation_tiles(size_t tiles, const ppp_mesh_signed_deviation_tile_stats *parts,
+                                          const double *const *v, const unsigned char *const *status,
+                                          const double *const *target, const unsigned char *const *owned,
+                                          ppp_mesh_signed_deviation_stats *stats);
+int ppp_get_mesh_registration_terms_tile(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp,
+                                         const double *T12, ppp_registration_row *row, ppp_registration_part *part);
+int ppp_register_mesh_tiles(const ppp_handle *hs, const ppp_trimesh *ms, size_t count,
+                            const ppp_registration_params *rp, const double *T0_12, ppp_registration_row *rows,
+                            size_t row_cap, ppp_register_tiles_stats *stats);
 /* Spline::point(y) of slice s (include/Spline.h:22-25): xyz[3*i..] */
 int ppp_eval_spline(ppp_handle h, int s, const double *y, size_t k, double *xyz);
 

@@ -673,6 +673,39 @@ public:
         const int rc = ppp_get_registration_terms_tile(h_, ref.h_, &rp, T12, &row, &part);
         return rc == PPP_OK ? true : report(rc);
     }
+    /* mesh_deviation() for the points this planner owns (ppp_get_mesh_deviation_tile): this planner holds the scan
+       with a slice range (or whole: it then owns everything), mesh lives on its device.  The mesh is whole, so there is no halo:
+       only this planner's range_margin must cover dp.smooth_radius.  part is what ppp_merge_mesh_deviation_tiles takes, with the
+       maps asked for here: smoothed, status, target and owned, by cloud index */
+    bool mesh_deviation_tile(const TriMesh &mesh, ppp_mesh_deviation_tile_stats &part, const ppp_deviation_params &dp,
+                             std::vector<double> *target = nullptr, std::vector<double> *smoothed = nullptr,
+                             std::vector<unsigned char> *status = nullptr, std::vector<unsigned char> *owned = nullptr,
+                             std::vector<double> *distance = nullptr, std::vector<unsigned char> *region = nullptr)
+    {
+        size_t n = 0;
+        int rc = (target || smoothed || status || owned || distance || region) ? ppp_num_points(h_, &n) : PPP_OK;
+        if (rc == PPP_OK) {
+            if (target) target->assign(n, 0.0);
+            if (smoothed) smoothed->assign(n, 0.0);
+            if (status) status->assign(n, (unsigned char)PPP_DEV_DROPPED);
+            if (owned) owned->assign(n, (unsigned char)0);
+            if (distance) distance->assign(n, 0.0);
+            if (region) region->assign(n, (unsigned char)255);
+            rc = ppp_get_mesh_deviation_tile(h_, mesh.get(), &dp, nullptr, smoothed ? smoothed->data() : nullptr, distance ? distance->data() : nullptr,
+                                             nullptr, region ? region->data() : nullptr, status ? status->data() : nullptr,
+                                             target ? target->data() : nullptr, owned ? owned->data() : nullptr, n, &part);
+        }
+        return rc == PPP_OK ? true : report(rc);
+    }
+    /* the registration terms at T12 (nullptr: the identity) against the triangles of mesh over the points this planner owns
+       (ppp_get_mesh_registration_terms_tile).  row and part are what ppp_merge_registration_terms and
+       ppp_registration_step take, unchanged; the mesh is whole, so no range condition exists */
+    bool mesh_registration_terms_tile(const TriMesh &mesh, ppp_registration_row &row, ppp_registration_part &part, const ppp_registration_params &rp,
+                                      const double *T12 = nullptr)
+    {
+        const int rc = ppp_get_mesh_registration_terms_tile(h_, mesh.get(), &rp, T12, &row, &part);
+        return rc == PPP_OK ? true : report(rc);
+    }
     /* ppp_default_deviation_params with what the environment sets of PPP_DEVIATION_MAXDIST, PPP_DEVIATION_SMOOTH,
        PPP_DEVIATION_ALLOWANCE and PPP_DEVIATION_GAIN (the example programs' knobs) */
     static ppp_deviation_params deviation_params_env()
@@ -1420,6 +1453,29 @@ inline bool register_robust_tiles(std::vector<Planner *> &tiles, std::vector<Pla
         if (weight) weight->clear();
         if (residual) residual->clear();
         if (owned) owned->clear();
+        const ppp_handle at = hs[st.failed_tile >= 0 ? (size_t)st.failed_tile : 0];
+        std::fprintf(stderr, "ppp error %d: tile %d: %s\n", rc, st.failed_tile, at ? ppp_last_error(at) : "no handle");
+        return false;
+    }
+    if (rows) rows->resize(std::min(rows->size(), (size_t)st.reg.steps + 1));
+    return true;
+}
+
+/* register_mesh() for a scan held as slice-range planners (ppp_register_mesh_tiles): tiles[i] holds the scan with
+   range i, meshes[i] is the mesh on its device (one TriMesh may stand in every slot when all tiles share a device).  st.reg is
+   register_mesh()'s st, bit for bit, for ranges that tile the walk; every evaluation is a host round trip.  A tile's error is
+   reported with its index */
+inline bool register_mesh_tiles(std::vector<Planner *> &tiles, std::vector<TriMesh *> &meshes, ppp_register_tiles_stats &st,
+                                const ppp_registration_params &rp, const double *T0 = nullptr, std::vector<ppp_registration_row> *rows = nullptr)
+{
+    if (tiles.empty() || meshes.size() != tiles.size()) { std::fprintf(stderr, "ppp error %d: register_mesh_tiles: one mesh per tile\n", PPP_ERR_ARG); return false; }
+    std::vector<ppp_handle> hs;
+    std::vector<ppp_trimesh> ms;
+    for (size_t i = 0; i < tiles.size(); ++i) { hs.push_back(tiles[i] ? tiles[i]->handle() : nullptr); ms.push_back(meshes[i] ? meshes[i]->get() : nullptr); }
+    if (rows) rows->assign((size_t)(rp.iterations > 0 ? rp.iterations : 0) + 1, ppp_registration_row{});
+    const int rc = ppp_register_mesh_tiles(hs.data(), ms.data(), hs.size(), &rp, T0, rows ? rows->data() : nullptr, rows ? rows->size() : 0, &st);
+    if (rc != PPP_OK) {
+        if (rows) rows->clear();
         const ppp_handle at = hs[st.failed_tile >= 0 ? (size_t)st.failed_tile : 0];
         std::fprintf(stderr, "ppp error %d: tile %d: %s\n", rc, st.failed_tile, at ? ppp_last_error(at) : "no handle");
         return false;

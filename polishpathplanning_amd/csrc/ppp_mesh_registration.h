@@ -7,7 +7,8 @@
  * is k_reg_step, unchanged; the host's chain has registration_chain's shape.  Nothing here estimates a normal or knows a pitch:
  * the fit is taken on the facets that ppp_get_mesh_deviation measures against.
  * Robust weights on these pairs are ppp_mesh_robust.h's, trimmed weights and border rejection
- * ppp_mesh_trimmed.h's; tiles and pseudonormals are not offered.
+ * ppp_mesh_trimmed.h's; the plain evaluation and loop over slice-range tiles are ppp_mesh_tile.h's;
+ * the robust and trimmed loops over tiles and pseudonormals are not offered.
  * The global start from the mesh (ppp_trimesh_get_moments, ppp_register_mesh_global): k_mesh_moments, the ten
  * integer words of the surface's area moments, and mesh_frame_from_words, the frame they imply; k_mesh_reg_search_multi and
  * k_mesh_reg_sum_multi, K chains side by side on the queries StrideSel compacts once, with k_reg_step_multi for the steps.
@@ -69,26 +70,36 @@ __global__ void __launch_bounds__(ICP_T) k_mesh_reg_terms(const float4 *__restri
 #define MESH_REG_NONE 0xffffffffu
 
 /* k_mesh_reg_search's body for query `at`, k_mesh_reg_sum's for workgroup `block` of `blocks`: one chain's evaluation at T.  The
-   single chain's kernels and the side-by-side ones call them, so a row is the same bits from either (reg_terms_body's way). */
-__device__ __forceinline__ void mesh_reg_search_body(const float4 *__restrict__ q4, int nq, const TriGrid &G, double md2, const double *__restrict__ T,
-        unsigned *__restrict__ win, int at)
+   single chain's kernels and the side-by-side ones call them, so a row is the same bits from either (reg_terms_body's way).
+   TILE (k_mesht_reg_search, k_mesht_reg_sum; ppp_mesh_tile.h): the queries are the positions [pos0, nq) of the
+   index, win[at - pos0] is a position's word, and a position whose resident, unmoved x `own` does not own (B.36) writes
+   MESH_REG_NONE and counts nowhere; *mine takes the thread's count of owned positions.  The whole-cloud kernels pass pos0 = 0 and
+   compile no test. */
+template <bool TILE>
+__device__ __forceinline__ void mesh_reg_search_body(const float4 *__restrict__ q4, int pos0, int nq, const TileRange &own, const TriGrid &G, double md2,
+        const double *__restrict__ T, unsigned *__restrict__ win, int at)
 {
     if (at >= nq) return;
-    double t[12], m[3];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = T[i];
-    icp_move(t, q4[at], m);
+    const float4 q = q4[at];
     unsigned w = MESH_REG_NONE;
-    if (isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2])) {
-        TmBest B;
-        tm_nearest(G, m, md2, B);
-        if (B.r >= 0 && B.D2 <= md2) w = (unsigned)B.r;
+    if (!TILE || own.owned(q.x)) {
+        double t[12], m[3];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) t[i] = T[i];
+        icp_move(t, q, m);
+        if (isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2])) {
+            TmBest B;
+            tm_nearest(G, m, md2, B);
+            if (B.r >= 0 && B.D2 <= md2) w = (unsigned)B.r;
+        }
     }
-    win[at] = w;
+    win[at - pos0] = w;
 }
 
-__device__ __forceinline__ void mesh_reg_sum_body(const float4 *__restrict__ q4, int nq, const TriGrid &G, const IcpFrame &F, const double *__restrict__ T,
-        const unsigned *__restrict__ win, unsigned long long *__restrict__ acc, int block, int blocks)
+template <bool TILE>
+__device__ __forceinline__ void mesh_reg_sum_body(const float4 *__restrict__ q4, int pos0, int nq, const TileRange &own, const TriGrid &G, const IcpFrame &F,
+        const double *__restrict__ T, const unsigned *__restrict__ win, unsigned long long *__restrict__ acc, int block, int blocks,
+        unsigned long long *mine)
 {
     __shared__ unsigned long long s_a[ICP_T / 64][ICP_WORDS];
     unsigned long long a[ICP_WORDS];
@@ -97,8 +108,9 @@ __device__ __forceinline__ void mesh_reg_sum_body(const float4 *__restrict__ q4,
     double t[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) t[i] = T[i];
-    for (int at = block * ICP_T + threadIdx.x; at < nq; at += blocks * ICP_T) {
-        const unsigned r = win[at];
+    for (int at = pos0 + block * ICP_T + threadIdx.x; at < nq; at += blocks * ICP_T) {
+        if (TILE) *mine += own.owned(q4[at].x);
+        const unsigned r = win[at - pos0];
         if (r >= (unsigned)G.indexed) continue; /* (MESH_REG_NONE too) */
         double m[3], p0[3], p1[3], p2[3], N[3], x[3], D2;
         int f;
@@ -112,18 +124,21 @@ __device__ __forceinline__ void mesh_reg_sum_body(const float4 *__restrict__ q4,
     icp_flush<ICP_T>(a, s_a, acc);
 }
 
+/* what the whole-cloud kernels hand the bodies for `own`: everything (never read: TILE is false) */
+__device__ __forceinline__ TileRange mesh_reg_whole() { return TileRange{-INFINITY, INFINITY, -INFINITY, INFINITY}; }
+
 __global__ void __launch_bounds__(TM_T) k_mesh_reg_search(const float4 *__restrict__ q4, int nq, const TriGrid G, double md2, const double *__restrict__ T,
         const IcpCtl *__restrict__ ctl, unsigned *__restrict__ win)
 {
     if (ctl->done) return;
-    mesh_reg_search_body(q4, nq, G, md2, T, win, blockIdx.x * TM_T + threadIdx.x);
+    mesh_reg_search_body<false>(q4, 0, nq, mesh_reg_whole(), G, md2, T, win, blockIdx.x * TM_T + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(ICP_T) k_mesh_reg_sum(const float4 *__restrict__ q4, int nq, const TriGrid G, const IcpFrame F, const double *__restrict__ T,
         const IcpCtl *__restrict__ ctl, const unsigned *__restrict__ win, unsigned long long *__restrict__ acc)
 {
     if (ctl->done) return;
-    mesh_reg_sum_body(q4, nq, G, F, T, win, acc, blockIdx.x, gridDim.x);
+    mesh_reg_sum_body<false>(q4, 0, nq, mesh_reg_whole(), G, F, T, win, acc, blockIdx.x, gridDim.x, nullptr);
 }
 
 /* K chains side by side (ppp_register_mesh_global): start blockIdx.y evaluates at its own transform -- T, ctl and
@@ -135,14 +150,15 @@ __global__ void __launch_bounds__(TM_T) k_mesh_reg_search_multi(const float4 *__
         size_t tstride, const IcpCtl *__restrict__ ctl, unsigned *__restrict__ win)
 {
     if (ctl[blockIdx.y].done) return;
-    mesh_reg_search_body(q4, nq, G, md2, T + blockIdx.y * tstride, win + (size_t)blockIdx.y * (size_t)nq, blockIdx.x * TM_T + threadIdx.x);
+    mesh_reg_search_body<false>(q4, 0, nq, mesh_reg_whole(), G, md2, T + blockIdx.y * tstride, win + (size_t)blockIdx.y * (size_t)nq, blockIdx.x * TM_T + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(ICP_T) k_mesh_reg_sum_multi(const float4 *__restrict__ q4, int nq, const TriGrid G, const IcpFrame F, const double *__restrict__ T,
         size_t tstride, const IcpCtl *__restrict__ ctl, const unsigned *__restrict__ win, unsigned long long *__restrict__ acc, size_t astride)
 {
     if (ctl[blockIdx.y].done) return;
-    mesh_reg_sum_body(q4, nq, G, F, T + blockIdx.y * tstride, win + (size_t)blockIdx.y * (size_t)nq, acc + blockIdx.y * astride, blockIdx.x, gridDim.x);
+    mesh_reg_sum_body<false>(q4, 0, nq, mesh_reg_whole(), G, F, T + blockIdx.y * tstride, win + (size_t)blockIdx.y * (size_t)nq, acc + blockIdx.y * astride, blockIdx.x,
+                             gridDim.x, nullptr);
 }
 
 /* ---------------------------------------------------------------------------------------------------------------------- */

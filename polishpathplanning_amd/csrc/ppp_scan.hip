@@ -26,6 +26,7 @@
 #include "ppp_mesh_registration.h"
 #include "ppp_mesh_robust.h"
 #include "ppp_mesh_trimmed.h"
+#include "ppp_mesh_tile.h"
 #include "ppp_sort.h"
 #include <cstring>
 #include <mutex>
@@ -994,6 +995,8 @@ struct RegtTile {
     int pos0 = 0, pos1 = 0, rb0 = 0, rb1 = 0, nref = 0;
     unsigned grid = 1;
     ppp_registration_part part;
+    ppp_trimesh mesh = nullptr; /* ppp_register_mesh_tiles: the mesh in the reference's place (ref stays NULL), k_mesht_reg_search's grid */
+    unsigned gsearch = 1;
 };
 
 /* the tile's pinned memory: REGT_WORDS words coming back, then the 12 doubles of T going out */
@@ -2279,6 +2282,330 @@ int ppp_register_mesh(ppp_handle h, ppp_trimesh m, const ppp_registration_params
                       ppp_registration_stats *stats)
 {
     return mesh_registration_chain(h, m, rp, T0_12, true, rows, row_cap, stats);
+}
+
+/* ---- the mesh calls for the points a handle owns (ppp_mesh_tile.h) ---- */
+
+/* The exact deviation map of the points h owns (B.144-B.146): the plan, the range check on the host, the index, then k_mesht_fill,
+   k_mesht_nearest, k_mesht_sign in the signed call, k_mesht_stats, k_devt_smooth where asked and k_devt_target back to back on the
+   scan's stream, and one wait.  The mesh is whole: nothing on its side is checked against a range.  The buffers are
+   ppp_get_mesh_deviation's: nothing is kept. */
+struct MeshTileSignMaps { unsigned char *feature, *flags; ppp_mesh_signed_deviation_tile_stats *part; };
+static int mesh_deviation_tile(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, const MeshTileSignMaps *sign, double *deviation, double *smoothed,
+                               double *distance, int *tri_index, unsigned char *region, unsigned char *status, double *target, unsigned char *owned,
+                               size_t cap, ppp_mesh_deviation_tile_stats *part)
+{
+    if (!h) return PPP_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    const std::string w = sign ? "mesh signed deviation tile" : "mesh deviation tile";
+    if (!m || !dp) return fail(h, PPP_ERR_ARG, w + ": no mesh or no parameters");
+    int rc = deviation_params_ok(h, *dp, w, nullptr);
+    if (rc) return rc;
+    if (m->device != h->device) return fail(h, PPP_ERR_ARG, w + ": the mesh is on another device than the handle");
+    const ppp_deviation_params P = *dp;
+    const bool smooth = P.smooth_radius > 0.f;
+    rc = deviation_side_cloud(h, h, w + ": the scan", true);
+    if (rc) return rc;
+    const size_t N = h->n;
+    if (deviation_sum_overflows(P, N)) return fail(h, PPP_ERR_ARG, w + ": max_dist 2^24 n reaches 2^62: the smoothing's integer sum could overflow");
+    /* from the plan alone, before an index is built or a kernel launched: what is evaluated is the owned interval widened by
+       smooth_radius, and the scan's handle must index it */
+    TileRange T;
+    rc = tile_range(h, 0.f, T);
+    if (rc) return rc;
+    widened(T, P.smooth_radius, T.ev_lo, T.ev_hi);
+    if (leaves_indexed_range(h, T.ev_lo, T.ev_hi))
+        return fail(h, PPP_ERR_ARG, w + ": the owned interval widened by smooth_radius reaches beyond the scan's indexed slice range: raise range_margin");
+    rc = deviation_side_index(h, h, w + ": the scan", false);
+    if (rc) return rc;
+    if (sign) { /* the topology on the mesh's stream, waited for: read-only from here on */
+        rc = trimesh_topology_build(m, h);
+        if (rc) return fail(h, rc, w + ": the mesh's topology could not be built");
+        HIPCHK(h, hipSetDevice(h->device));
+    }
+    int pos0, pos1, hb0, hb1;
+    rc = tile_positions(h, T, pos0, pos1);
+    if (rc) return rc;
+    sorted_slabs(h, hb0, hb1);
+    auto &D = h->deviation;
+    const size_t N1 = std::max<size_t>(N, 1);
+    HIPCHK(h, D.dev.ensure(N1)); HIPCHK(h, D.target.ensure(N1)); HIPCHK(h, D.fix.ensure(N1)); HIPCHK(h, D.d2.ensure(N1)); HIPCHK(h, D.dist.ensure(N1));
+    HIPCHK(h, D.ref_index.ensure(N1)); HIPCHK(h, D.status.ensure(N1)); HIPCHK(h, D.region.ensure(N1)); HIPCHK(h, D.owned.ensure(N1));
+    HIPCHK(h, D.acc.ensure(DEV_ACC_WORDS)); HIPCHK(h, D.macc.ensure(MESHT_ACC_WORDS));
+    if (smooth) HIPCHK(h, D.smoothed.ensure(N1));
+    if (sign) { HIPCHK(h, D.feature.ensure(N1)); HIPCHK(h, D.flags.ensure(N1)); }
+    double *v = smooth ? D.smoothed.p : D.dev.p;
+    HIPCHK(h, hipMemsetAsync(D.acc.p, 0, DEVT_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(D.macc.p, 0, MESHT_ACC_WORDS * sizeof(unsigned long long), h->stream));
+    const size_t cap_grid = 2 * (size_t)h->num_cus;
+    LAUNCH(h, "k_mesht_fill", k_mesht_fill, (unsigned)std::min<size_t>((N1 + TM_T - 1) / TM_T, cap_grid), TM_T, 0, (int)N, D.dev.p,
+           smooth ? D.smoothed.p : nullptr, D.target.p, D.dist.p, D.ref_index.p, D.region.p, sign ? D.feature.p : nullptr, sign ? D.flags.p : nullptr,
+           D.status.p, D.owned.p);
+    if (pos1 > pos0) {
+        const size_t gq = ((size_t)(pos1 - pos0) + TM_T - 1) / TM_T;
+        static_assert(TM_T == DEV_T, "one grid for the search and the smoothing");
+        const TmOut O = trimesh_outputs(D.dist.p, nullptr, D.dev.p, D.fix.p, D.d2.p, D.ref_index.p, D.region.p, D.status.p);
+        LAUNCH(h, "k_mesht_nearest", k_mesht_nearest, (unsigned)gq, TM_T, 0, (const float4 *)h->sorted4.p, pos0, pos1, T, m->G,
+               (double)P.max_dist * (double)P.max_dist, O, D.owned.p);
+        if (sign) { /* the signed distance takes the deviation's place, in the map and in its fixed-point term, before the smoothing reads them */
+            TmSignOut SO;
+            SO.signed_distance = D.dev.p; SO.pseudonormal = nullptr; SO.dev = nullptr; SO.fix = D.fix.p; SO.feature = D.feature.p; SO.flags = D.flags.p;
+            SO.tri_index = D.ref_index.p; SO.status = D.status.p;
+            LAUNCH(h, "k_mesht_sign", k_mesht_sign, (unsigned)gq, TM_T, 0, (const float4 *)h->sorted4.p, pos0, pos1, T, m->G, m->T, SO);
+        }
+        LAUNCH(h, "k_mesht_stats", k_mesht_stats, (unsigned)std::min(gq, cap_grid), TM_T, 0, (const float4 *)h->sorted4.p, pos0, pos1, T, D.status.p,
+               D.region.p, D.dist.p, sign ? D.flags.p : nullptr, D.dev.p, D.macc.p);
+        if (smooth)
+            LAUNCH(h, "k_devt_smooth", k_devt_smooth, (unsigned)gq, DEV_T, 0, contact_index(h), pos0, pos1, T, hb0, hb1,
+                   P.smooth_radius * P.smooth_radius, D.status.p, D.fix.p, D.smoothed.p);
+        LAUNCH(h, "k_devt_target", k_devt_target, (unsigned)std::min(gq, cap_grid), DEV_T, 0, h->sorted4.p, pos0, pos1, T, D.status.p, D.dev.p, v,
+               D.d2.p, D.ref_index.p, P.allowance, P.gain, D.target.p, D.acc.p);
+    }
+    unsigned long long acc[DEVT_ACC_WORDS], macc[MESHT_ACC_WORDS];
+    HIPCHK(h, copy_sync(h, acc, D.acc.p, sizeof(acc), hipMemcpyDeviceToHost)); /* the one wait */
+    HIPCHK(h, copy_sync(h, macc, D.macc.p, sizeof(macc), hipMemcpyDeviceToHost));
+    const unsigned long long own = acc[0] + acc[1] + acc[2];
+    if (own + acc[DEVT_ACC_HALO] > (unsigned long long)(pos1 - pos0) || acc[DEV_ACC_PROUD] > acc[0] || acc[DEV_ACC_BELOW] > acc[0] ||
+        macc[0] + macc[1] + macc[2] != acc[0] || macc[MESHT_ACC_SIGN + 3] + macc[MESHT_ACC_SIGN + 4] > acc[0])
+        return fail(h, PPP_ERR_HIP, w + ": statistics corrupt");
+    ppp_mesh_deviation_tile_stats st = {};
+    dev_stats_words(st.dev, N, acc);
+    st.dev.owned = (size_t)own; st.dev.evaluated = (size_t)(own + acc[DEVT_ACC_HALO]);
+    if (st.dev.matched) st.dev.fix_sum = (long long)acc[DEV_ACC_FIXSUM];
+    st.dev.own_lo = T.own_lo; st.dev.own_hi = T.own_hi;
+    st.dev.sum_parts = MapParts(h, N).grid;
+    st.on_face = (size_t)macc[0]; st.on_edge = (size_t)macc[1]; st.on_vertex = (size_t)macc[2];
+    st.max_distance = (double)NAN;
+    if (st.dev.matched) memcpy(&st.max_distance, &macc[MESHT_ACC_FAR], sizeof(double));
+    if (part) *part = st;
+    if (sign && sign->part) {
+        ppp_mesh_signed_deviation_tile_stats &ss = *sign->part;
+        ss = ppp_mesh_signed_deviation_tile_stats{};
+        ss.mesh = st;
+        ss.on_border = (size_t)macc[MESHT_ACC_SIGN]; ss.irregular = (size_t)macc[MESHT_ACC_SIGN + 1]; ss.fallback = (size_t)macc[MESHT_ACC_SIGN + 2];
+        ss.negative = (size_t)macc[MESHT_ACC_SIGN + 3]; ss.positive = (size_t)macc[MESHT_ACC_SIGN + 4];
+    }
+    const size_t k = std::min(cap, N);
+    rc = deviation_copy_out(h, k, v, deviation, smoothed, tri_index, status, target, owned);
+    if (rc) return rc;
+    if (distance && k) HIPCHK(h, copy_sync(h, distance, D.dist.p, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (region && k) HIPCHK(h, copy_sync(h, region, D.region.p, k, hipMemcpyDeviceToHost));
+    if (sign && sign->feature && k) HIPCHK(h, copy_sync(h, sign->feature, D.feature.p, k, hipMemcpyDeviceToHost));
+    if (sign && sign->flags && k) HIPCHK(h, copy_sync(h, sign->flags, D.flags.p, k, hipMemcpyDeviceToHost));
+    return PPP_OK;
+}
+
+int ppp_get_mesh_deviation_tile(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *deviation, double *smoothed, double *distance,
+                                int *tri_index, unsigned char *region, unsigned char *status, double *target, unsigned char *owned, size_t cap,
+                                ppp_mesh_deviation_tile_stats *part)
+{
+    return mesh_deviation_tile(h, m, dp, nullptr, deviation, smoothed, distance, tri_index, region, status, target, owned, cap, part);
+}
+
+int ppp_get_mesh_signed_deviation_tile(ppp_handle h, ppp_trimesh m, const ppp_deviation_params *dp, double *signed_distance, double *smoothed,
+                                       double *distance, int *tri_index, unsigned char *region, unsigned char *feature, unsigned char *flags,
+                                       unsigned char *status, double *target, unsigned char *owned, size_t cap,
+                                       ppp_mesh_signed_deviation_tile_stats *part)
+{
+    const MeshTileSignMaps sign = {feature, flags, part};
+    return mesh_deviation_tile(h, m, dp, &sign, signed_distance, smoothed, distance, tri_index, region, status, target, owned, cap, nullptr);
+}
+
+/* The merges (B.147; host only): dev by ppp_merge_deviation_tiles' own routine, which also refuses what it refuses; the counts
+   add; max_distance is the maximum of the parts that matched (doubles >= +0 order as their bits), the NaN when none did.  A part
+   whose counts by region do not add up to its matched points is not a tile's. */
+int ppp_merge_mesh_deviation_tiles(size_t tiles, const ppp_mesh_deviation_tile_stats *parts, const double *const *v, const unsigned char *const *status,
+                                   const double *const *target, const unsigned char *const *owned, ppp_mesh_deviation_stats *stats)
+{
+    if (!tiles || !parts || !stats) return PPP_ERR_ARG;
+    std::vector<ppp_deviation_tile_stats> dev(tiles);
+    ppp_mesh_deviation_stats st = {};
+    unsigned long long far = 0;
+    for (size_t t = 0; t < tiles; ++t) {
+        const ppp_mesh_deviation_tile_stats &p = parts[t];
+        dev[t] = p.dev;
+        if (p.on_face + p.on_edge + p.on_vertex != p.dev.matched) return PPP_ERR_ARG;
+        st.on_face += p.on_face; st.on_edge += p.on_edge; st.on_vertex += p.on_vertex;
+        if (!p.dev.matched) continue;
+        if (!(p.max_distance >= 0.0)) return PPP_ERR_ARG; /* (a NaN too) */
+        unsigned long long bits;
+        memcpy(&bits, &p.max_distance, sizeof(bits));
+        far = std::max(far, bits & 0x7fffffffffffffffull); /* (-0 as +0) */
+    }
+    const int rc = ppp_merge_deviation_tiles(tiles, dev.data(), v, status, target, owned, &st.dev);
+    if (rc) return rc;
+    st.max_distance = (double)NAN;
+    if (st.dev.matched) memcpy(&st.max_distance, &far, sizeof(double));
+    *stats = st;
+    return PPP_OK;
+}
+
+int ppp_merge_mesh_signed_deviation_tiles(size_t tiles, const ppp_mesh_signed_deviation_tile_stats *parts, const double *const *v,
+                                          const unsigned char *const *status, const double *const *target, const unsigned char *const *owned,
+                                          ppp_mesh_signed_deviation_stats *stats)
+{
+    if (!tiles || !parts || !stats) return PPP_ERR_ARG;
+    std::vector<ppp_mesh_deviation_tile_stats> mesh(tiles);
+    ppp_mesh_signed_deviation_stats st = {};
+    for (size_t t = 0; t < tiles; ++t) {
+        const ppp_mesh_signed_deviation_tile_stats &p = parts[t];
+        mesh[t] = p.mesh;
+        if (p.negative + p.positive > p.mesh.dev.matched || p.on_border > p.mesh.dev.matched || p.irregular > p.mesh.dev.matched ||
+            p.fallback > p.mesh.dev.matched)
+            return PPP_ERR_ARG;
+        st.on_border += p.on_border; st.irregular += p.irregular; st.fallback += p.fallback; st.negative += p.negative; st.positive += p.positive;
+    }
+    const int rc = ppp_merge_mesh_deviation_tiles(tiles, mesh.data(), v, status, target, owned, &st.mesh);
+    if (rc) return rc;
+    *stats = st;
+    return PPP_OK;
+}
+
+/* What a tile of a mesh registration needs before its first evaluation (B.148): the checks, the plan, the scan's index, the frame
+   from the mesh's box (B.126) and the shift of the WHOLE scan (B.68), the positions, the grids, the buffers, and the frame on the
+   device.  The mesh is whole and read-only since its create call waited: no range condition, nothing to build on its side. */
+static int mesht_prepare(RegtTile &t, const ppp_registration_params &P, IcpFrame F)
+{
+    ppp_handle h = t.h;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (t.mesh->device != h->device) return fail(h, PPP_ERR_ARG, "mesh registration tile: the mesh is on another device than the handle");
+    int rc = deviation_side_cloud(h, h, "mesh registration tile: the scan", true);
+    if (rc) return rc;
+    const int shift = icp_shift(h->n, F.md2);
+    if (shift < 16) return fail(h, PPP_ERR_ARG, "mesh registration tile: fewer than 16 fractional bits are left (n max_dist^2 too large): the integer sums could overflow");
+    rc = tile_range(h, 0.f, t.own);
+    if (rc) return rc;
+    rc = deviation_side_index(h, h, "mesh registration tile: the scan", false);
+    if (rc) return rc;
+    float mn[3], mx[3];
+    mesh_box_floats(t.mesh->G, mn, mx);
+    frame_from_bounds(mn, mx, (double)P.max_dist, shift, F.c, &F.Ln, &F.scale);
+    rc = tile_positions(h, t.own, t.pos0, t.pos1);
+    if (rc) return rc;
+    const size_t np = (size_t)(t.pos1 - t.pos0);
+    const size_t cap = MESH_REG_GRID_CUS ? (size_t)MESH_REG_GRID_CUS * (size_t)h->num_cus : (size_t)0x7fffffff;
+    t.grid = (unsigned)std::max<size_t>(1, std::min<size_t>((np + ICP_T - 1) / ICP_T, cap));
+    t.gsearch = (unsigned)std::max<size_t>(1, (np + TM_T - 1) / TM_T);
+    ppp_registration_part &p = t.part;
+    p = ppp_registration_part{};
+    p.evaluated = np;
+    p.own_lo = t.own.own_lo; p.own_hi = t.own.own_hi;
+    p.n = h->n; p.shift = shift;
+    for (int d = 0; d < 3; ++d) p.centre[d] = F.c[d];
+    p.length = F.Ln;
+    auto &G = h->registration;
+    HIPCHK(h, G.T.ensure(12)); HIPCHK(h, G.acc.ensure(REGT_WORDS)); HIPCHK(h, G.tframe.ensure(1)); HIPCHK(h, G.tpin.ensure(REGT_WORDS + 12));
+    HIPCHK(h, G.key.ensure(std::max<size_t>(np, 1))); /* the winning record per position (the whole-cloud chain's buffer) */
+    HIPCHK(h, copy_sync(h, G.tframe.p, &F, sizeof(F), hipMemcpyHostToDevice));
+    return PPP_OK;
+}
+
+/* one evaluation of a tile at T, enqueued on its handle's stream: T to the device, the words cleared, k_mesht_reg_search,
+   k_mesht_reg_sum, the words back to pinned memory.  Nobody waits here. */
+static int mesht_enqueue(RegtTile &t, const double *T, double md2)
+{
+    ppp_handle h = t.h;
+    auto &G = h->registration;
+    HIPCHK(h, hipSetDevice(h->device));
+    memcpy(regt_pinned_T(t), T, 12 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(G.T.p, regt_pinned_T(t), 12 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(G.acc.p, 0, REGT_WORDS * sizeof(unsigned long long), h->stream));
+    if (t.pos1 > t.pos0) {
+        LAUNCH(h, "k_mesht_reg_search", k_mesht_reg_search, t.gsearch, TM_T, 0, (const float4 *)h->sorted4.p, t.pos0, t.pos1, t.own, t.mesh->G, md2, G.T.p,
+               G.key.p);
+        LAUNCH(h, "k_mesht_reg_sum", k_mesht_reg_sum, t.grid, ICP_T, 0, (const float4 *)h->sorted4.p, t.pos0, t.pos1, t.own, t.mesh->G, G.tframe.p, G.T.p,
+               G.key.p, G.acc.p);
+    }
+    HIPCHK(h, hipMemcpyAsync(G.tpin.p, G.acc.p, REGT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    return PPP_OK;
+}
+
+/* the wait for a tile's evaluation, and its row: the words' sanity, the terms.  No refusal: the mesh is whole. */
+static int mesht_collect(RegtTile &t, const double *T, ppp_registration_row *row)
+{
+    ppp_handle h = t.h;
+    int rc = regt_wait(t);
+    if (rc) return rc;
+    const unsigned long long *w = h->registration.tpin.p;
+    if (w[REGT_OWNED] > (unsigned long long)(t.pos1 - t.pos0) || w[ICP_PAIRS] > w[REGT_OWNED]) return fail(h, PPP_ERR_HIP, "mesh registration tile: sums corrupt");
+    t.part.owned = (size_t)w[REGT_OWNED];
+    *row = ppp_registration_row{};
+    icp_row_terms(row, T, w);
+    return PPP_OK;
+}
+
+int ppp_get_mesh_registration_terms_tile(ppp_handle h, ppp_trimesh m, const ppp_registration_params *rp, const double *T12, ppp_registration_row *row,
+                                         ppp_registration_part *part)
+{
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h, rp, T12, F, T);
+    if (rc) return rc;
+    if (!m) return fail(h, PPP_ERR_ARG, "mesh registration tile: no mesh");
+    RegtTile t;
+    t.h = h; t.mesh = m;
+    rc = mesht_prepare(t, *rp, F);
+    if (rc) return rc;
+    rc = mesht_enqueue(t, T, (double)rp->max_dist * (double)rp->max_dist);
+    if (rc) return rc;
+    ppp_registration_row r;
+    rc = mesht_collect(t, T, &r);
+    if (rc) return rc;
+    if (row) *row = r;
+    if (part) *part = t.part;
+    return PPP_OK;
+}
+
+/* do two meshes hold one surface as the frame and the search see it?  the triangle counts and the box, bit for bit */
+static bool mesht_same_mesh(const ppp_trimesh a, const ppp_trimesh b)
+{
+    return a->n_tris == b->n_tris && a->G.indexed == b->G.indexed && memcmp(a->G.mn, b->G.mn, sizeof(a->G.mn)) == 0 && memcmp(a->G.mx, b->G.mx, sizeof(a->G.mx)) == 0;
+}
+
+/* The tiled loop against the mesh (B.149): ppp_register_tiles's, with the mesh in every reference's place -- regt_loop with an
+   evaluation that is k_mesht_reg_search and k_mesht_reg_sum per tile, one copy back and one wait per tile, then the merge and the
+   step on the host. */
+int ppp_register_mesh_tiles(const ppp_handle *hs, const ppp_trimesh *ms, size_t count, const ppp_registration_params *rp, const double *T0_12,
+                            ppp_registration_row *rows, size_t row_cap, ppp_register_tiles_stats *stats)
+{
+    if (stats) { *stats = ppp_register_tiles_stats{}; stats->failed_tile = -1; }
+    if (!hs || !ms || !count || !hs[0]) return PPP_ERR_ARG;
+    ppp_handle h0 = hs[0];
+    IcpFrame F = {};
+    double T[12];
+    int rc = regt_call_ok(h0, rp, T0_12, F, T);
+    if (rc) return rc;
+    const ppp_registration_params P = *rp;
+    const double md2 = (double)P.max_dist * (double)P.max_dist;
+    RegtCall call = {"mesh registration tiles", stats};
+    if (!rows && row_cap) return fail(h0, PPP_ERR_ARG, "mesh registration tiles: rows is NULL with row_cap > 0");
+    for (size_t i = 0; i < count; ++i) {
+        if (!hs[i] || !ms[i]) return fail(h0, PPP_ERR_ARG, "mesh registration tiles: a NULL handle or mesh");
+        for (size_t k = 0; k < i; ++k) if (hs[k] == hs[i]) return fail(h0, PPP_ERR_ARG, "mesh registration tiles: a scan handle stands in two slots");
+        if (!mesht_same_mesh(ms[i], ms[0])) return fail(h0, PPP_ERR_ARG, "mesh registration tiles: the meshes disagree on their triangles or their box");
+    }
+    call.tiles.assign(count, RegtTile()); call.part_rows.resize(count); call.parts.resize(count);
+    for (size_t i = 0; i < count; ++i) {
+        RegtTile &t = call.tiles[i];
+        t.h = hs[i]; t.mesh = ms[i];
+        rc = mesht_prepare(t, P, F);
+        if (rc) return call.failed(i, rc);
+    }
+    std::vector<ppp_registration_row> R;
+    IcpCtl C = {};
+    rc = regt_loop(P, F, T, R, C, call.whole, [&](int, ppp_registration_row &rw) {
+        const int e = regt_pass(call, [&](RegtTile &t) { return mesht_enqueue(t, T, md2); }, [&](RegtTile &t, size_t i) {
+            const int ec = mesht_collect(t, T, &call.part_rows[i]);
+            call.parts[i] = t.part;
+            return ec;
+        });
+        return e ? e : regt_merged(h0, call, T, rw);
+    });
+    if (rc) return rc;
+    if (stats) stats->reg = registration_stats(R, C, call.whole.n, call.whole.owned, call.whole.shift, call.whole.centre, call.whole.length);
+    const size_t k = std::min(row_cap, (size_t)C.steps + 1);
+    if (rows && k) memcpy(rows, R.data(), k * sizeof(ppp_registration_row));
+    return PPP_OK;
 }
 
 /* The area moments of the mesh.  mesh_moments_frame: the centre, the length and the fixed point of B.135

@@ -337,14 +337,10 @@ struct TmOut {
     unsigned char *region, *status;
 };
 
-__global__ void __launch_bounds__(TM_T) k_mesh_nearest(const float4 *__restrict__ q4, const float *__restrict__ xyz, int nq, const TriGrid G, double md2, TmOut O)
+/* k_mesh_nearest's body for one query (qx, qy, qz) whose entries go to `id`: the whole-cloud kernel and the tile form
+   (k_mesht_nearest, ppp_mesh_tile.h) call it, so a point's entries are the same bits from either (mesh_reg_search_body's way). */
+__device__ __forceinline__ void mesh_nearest_body(float qx, float qy, float qz, int id, const TriGrid &G, double md2, const TmOut &O)
 {
-    const int t = blockIdx.x * TM_T + threadIdx.x;
-    if (t >= nq) return;
-    float qx, qy, qz;
-    int id = t;
-    if (q4) { const float4 q = q4[t]; qx = q.x; qy = q.y; qz = q.z; id = idx_of(q); }
-    else { qx = xyz[3 * (size_t)t]; qy = xyz[3 * (size_t)t + 1]; qz = xyz[3 * (size_t)t + 2]; }
     const double p[3] = {(double)qx, (double)qy, (double)qz};
     int st = PPP_DEV_DROPPED;
     TmBest B;
@@ -376,6 +372,17 @@ __global__ void __launch_bounds__(TM_T) k_mesh_nearest(const float4 *__restrict_
     if (O.deviation) O.deviation[id] = dev;
     if (hit && O.fix) O.fix[id] = llrint(dev * DEV_FIXED);
     if (hit && O.d2f) O.d2f[id] = (float)B.D2;
+}
+
+__global__ void __launch_bounds__(TM_T) k_mesh_nearest(const float4 *__restrict__ q4, const float *__restrict__ xyz, int nq, const TriGrid G, double md2, TmOut O)
+{
+    const int t = blockIdx.x * TM_T + threadIdx.x;
+    if (t >= nq) return;
+    float qx, qy, qz;
+    int id = t;
+    if (q4) { const float4 q = q4[t]; qx = q.x; qy = q.y; qz = q.z; id = idx_of(q); }
+    else { qx = xyz[3 * (size_t)t]; qy = xyz[3 * (size_t)t + 1]; qz = xyz[3 * (size_t)t + 2]; }
+    mesh_nearest_body(qx, qy, qz, id, G, md2, O);
 }
 
 /* what the maps hold where the search does not write: a thread per cloud index */

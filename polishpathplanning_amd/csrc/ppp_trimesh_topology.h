@@ -303,14 +303,10 @@ struct TmSignOut {
     const unsigned char *status;
 };
 
-__global__ void __launch_bounds__(TM_T) k_mesh_sign(const float4 *__restrict__ q4, const float *__restrict__ xyz, int nq, const TriGrid G, const TriTopo T, TmSignOut O)
+/* k_mesh_sign's body for one query whose entries go to `id`: the whole-cloud kernel and the tile form (k_mesht_sign,
+   ppp_mesh_tile.h) call it: equal bits from equal code. */
+__device__ __forceinline__ void mesh_sign_body(float qx, float qy, float qz, int id, const TriGrid &G, const TriTopo &T, const TmSignOut &O)
 {
-    const int t = blockIdx.x * TM_T + threadIdx.x;
-    if (t >= nq) return;
-    float qx, qy, qz;
-    int id = t;
-    if (q4) { const float4 q = q4[t]; qx = q.x; qy = q.y; qz = q.z; id = idx_of(q); }
-    else { qx = xyz[3 * (size_t)t]; qy = xyz[3 * (size_t)t + 1]; qz = xyz[3 * (size_t)t + 2]; }
     const int f = O.status[id] == PPP_DEV_MATCHED ? O.tri_index[id] : -1;
     const int r = f >= 0 && f < T.n_tris ? T.rec_of[f] : -1;
     double sd = dev_nan(), g[3] = {dev_nan(), dev_nan(), dev_nan()};
@@ -351,6 +347,17 @@ __global__ void __launch_bounds__(TM_T) k_mesh_sign(const float4 *__restrict__ q
     if (O.flags) O.flags[id] = (unsigned char)flags;
     if (r >= 0 && O.dev) O.dev[id] = sd;
     if (r >= 0 && O.fix) O.fix[id] = llrint(sd * DEV_FIXED);
+}
+
+__global__ void __launch_bounds__(TM_T) k_mesh_sign(const float4 *__restrict__ q4, const float *__restrict__ xyz, int nq, const TriGrid G, const TriTopo T, TmSignOut O)
+{
+    const int t = blockIdx.x * TM_T + threadIdx.x;
+    if (t >= nq) return;
+    float qx, qy, qz;
+    int id = t;
+    if (q4) { const float4 q = q4[t]; qx = q.x; qy = q.y; qz = q.z; id = idx_of(q); }
+    else { qx = xyz[3 * (size_t)t]; qy = xyz[3 * (size_t)t + 1]; qz = xyz[3 * (size_t)t + 2]; }
+    mesh_sign_body(qx, qy, qz, id, G, T, O);
 }
 
 /* what the signed maps hold where the sign kernel does not write (points outside the slab index): a thread per cloud index */

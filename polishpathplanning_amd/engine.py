@@ -86,6 +86,8 @@ EXPORTS = [
     "ppp_get_mesh_registration_terms", "ppp_register_mesh", "ppp_get_mesh_robust_registration_terms", "ppp_register_mesh_robust",
     "ppp_default_mesh_trimmed_registration_params", "ppp_get_mesh_trimmed_registration_terms", "ppp_register_mesh_trimmed",
     "ppp_trimesh_get_moments", "ppp_mesh_frame_from_moments", "ppp_register_mesh_global",
+    "ppp_get_mesh_deviation_tile", "ppp_get_mesh_signed_deviation_tile", "ppp_merge_mesh_deviation_tiles", "ppp_merge_mesh_signed_deviation_tiles",
+    "ppp_get_mesh_registration_terms_tile", "ppp_register_mesh_tiles",
     "ppp_set_side_by_side", "ppp_get_binning_form", "ppp_get_launch_priorities", "ppp_queue_create", "ppp_queue_destroy", "ppp_queue_submit", "ppp_queue_wait", "ppp_queue_lanes", "ppp_queue_lane", "ppp_queue_last_error",
 ]
 
@@ -296,6 +298,16 @@ def lib():
         L.ppp_mesh_frame_from_moments.argtypes = [C.POINTER(C.c_longlong), C.c_int, dp, C.c_double, C.POINTER(CloudFrame)]
         L.ppp_register_mesh_global.argtypes = [vp, vp, C.POINTER(GlobalRegistrationParams), C.POINTER(RegistrationCandidate), sz, C.POINTER(RegistrationRow), sz,
                                                C.POINTER(GlobalRegistrationStats)]
+        L.ppp_get_mesh_deviation_tile.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, dp, ubp, sz, C.POINTER(MeshDeviationTileStats)]
+        L.ppp_get_mesh_signed_deviation_tile.argtypes = [vp, vp, C.POINTER(DeviationParams), dp, dp, dp, ip, ubp, ubp, ubp, ubp, dp, ubp, sz,
+                                                         C.POINTER(MeshSignedDeviationTileStats)]
+        L.ppp_merge_mesh_deviation_tiles.argtypes = [sz, C.POINTER(MeshDeviationTileStats), C.POINTER(dp), C.POINTER(ubp), C.POINTER(dp), C.POINTER(ubp),
+                                                     C.POINTER(MeshDeviationStats)]
+        L.ppp_merge_mesh_signed_deviation_tiles.argtypes = [sz, C.POINTER(MeshSignedDeviationTileStats), C.POINTER(dp), C.POINTER(ubp), C.POINTER(dp),
+                                                            C.POINTER(ubp), C.POINTER(MeshSignedDeviationStats)]
+        L.ppp_get_mesh_registration_terms_tile.argtypes = [vp, vp, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), C.POINTER(RegistrationPart)]
+        L.ppp_register_mesh_tiles.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, C.POINTER(RegistrationParams), dp, C.POINTER(RegistrationRow), sz,
+                                              C.POINTER(RegisterTilesStats)]
         L.ppp_load_stl.argtypes = [C.c_char_p, C.POINTER(fp), szp]
         L.ppp_save_stl.argtypes = [C.c_char_p, fp, sz, C.c_int]
         _lib = L
@@ -639,6 +651,82 @@ class MeshSignedDeviationStats(C.Structure):
                 ("positive", C.c_size_t)]
 
 
+class MeshDeviationTileStats(C.Structure):
+    """ppp_mesh_deviation_tile_stats"""
+    _fields_ = [("dev", DeviationTileStats), ("on_face", C.c_size_t), ("on_edge", C.c_size_t), ("on_vertex", C.c_size_t), ("max_distance", C.c_double)]
+
+
+class MeshSignedDeviationTileStats(C.Structure):
+    """ppp_mesh_signed_deviation_tile_stats"""
+    _fields_ = [("mesh", MeshDeviationTileStats), ("on_border", C.c_size_t), ("irregular", C.c_size_t), ("fallback", C.c_size_t), ("negative", C.c_size_t),
+                ("positive", C.c_size_t)]
+
+
+_MESH_TILE_FIELDS = ("on_face", "on_edge", "on_vertex", "max_distance")
+_MESH_SIGNED_TILE_FIELDS = ("on_border", "irregular", "fallback", "negative", "positive")
+
+
+def _mesh_tile_part(st, signed_st=None):
+    """a MeshDeviationTileStats (and the signed struct around it) as one flat dict: deviation_tile()'s part, the counts by region
+    and max_distance, and the signed call's five counts"""
+    part = {k: getattr(st.dev, k) for k, _ in DeviationTileStats._fields_}
+    part.update({k: getattr(st, k) for k in _MESH_TILE_FIELDS})
+    if signed_st is not None:
+        part.update({k: getattr(signed_st, k) for k in _MESH_SIGNED_TILE_FIELDS})
+    return part
+
+
+def _merge_mesh_tiles(tiles, signed):
+    L = lib()
+    T = len(tiles)
+    ub, dpp = C.POINTER(C.c_ubyte), C.POINTER(C.c_double)
+    # (signed_distance | deviation, smoothed, distance, tri_index, region, [feature, flags,] status, target, owned, part)
+    keep = [(np.ascontiguousarray(t[1], np.float64), np.ascontiguousarray(t[-4], np.uint8), np.ascontiguousarray(t[-3], np.float64),
+             np.ascontiguousarray(t[-2], np.uint8)) for t in tiles]
+    vv = (dpp * max(T, 1))(*[_d(k[0]) for k in keep])
+    ss = (ub * max(T, 1))(*[k[1].ctypes.data_as(ub) for k in keep])
+    tt = (dpp * max(T, 1))(*[_d(k[2]) for k in keep])
+    oo = (ub * max(T, 1))(*[k[3].ctypes.data_as(ub) for k in keep])
+    parts = ((MeshSignedDeviationTileStats if signed else MeshDeviationTileStats) * max(T, 1))()
+    for i, t in enumerate(tiles):
+        part = t[-1]
+        mesh = parts[i].mesh if signed else parts[i]
+        for f, _ in DeviationTileStats._fields_:
+            setattr(mesh.dev, f, part[f])
+        for f in _MESH_TILE_FIELDS:
+            setattr(mesh, f, part[f])
+        if signed:
+            for f in _MESH_SIGNED_TILE_FIELDS:
+                setattr(parts[i], f, part[f])
+        if any(len(a) != part["n"] for a in keep[i]):
+            raise PPPError(ERR_ARG, "merge of mesh deviation tiles: tile %d's maps do not hold n entries" % i)
+    st = MeshSignedDeviationStats() if signed else MeshDeviationStats()
+    call = L.ppp_merge_mesh_signed_deviation_tiles if signed else L.ppp_merge_mesh_deviation_tiles
+    rc = call(T, parts, vv, ss, tt, oo, C.byref(st))
+    if rc:
+        raise PPPError(rc, "merge of mesh deviation tiles: a point owned twice, a part that is not its maps', or tiles that do not belong together")
+    mesh = st.mesh if signed else st
+    stats = _deviation_stats(mesh.dev)
+    stats.update(on_face=int(mesh.on_face), on_edge=int(mesh.on_edge), on_vertex=int(mesh.on_vertex), max_distance=float(mesh.max_distance))
+    if signed:
+        stats.update({k: int(getattr(st, k)) for k in _MESH_SIGNED_TILE_FIELDS})
+    return stats, st
+
+
+def merge_mesh_deviation_tiles(tiles):
+    """Engine.mesh_deviation()'s stats dict of the whole cloud, bit for bit, from the tiles of ranges that tile the walk
+    (ppp_merge_mesh_deviation_tiles: host only).  tiles = a sequence of Engine.mesh_deviation_tile() results.  deviation()'s
+    fields merge as merge_deviation_tiles() merges them, the counts by region add, max_distance is the maximum (NaN when nothing
+    matched)"""
+    return _merge_mesh_tiles(tiles, False)[0]
+
+
+def merge_mesh_signed_deviation_tiles(tiles):
+    """Engine.mesh_signed_deviation()'s stats dict of the whole cloud, bit for bit, from a sequence of
+    Engine.mesh_signed_deviation_tile() results (ppp_merge_mesh_signed_deviation_tiles: host only)"""
+    return _merge_mesh_tiles(tiles, True)[0]
+
+
 def merge_deviation_tiles(tiles):
     """ppp_deviation_stats of the whole cloud, as Engine.deviation()'s dict and bit for bit, from the tiles of ranges that tile the
     walk (ppp_merge_deviation_tiles: host only).  tiles = a sequence of Engine.deviation_tile() results (deviation, smoothed,
@@ -860,6 +948,33 @@ def register_tiles(engines, refs, max_dist=2.0, iterations=30, min_step=1e-6, lo
     st = RegisterTilesStats()
     t = _t12(T0)
     rc = lib().ppp_register_tiles(hs, rs, k, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st))
+    if rc:
+        at = st.failed_tile if st.failed_tile >= 0 else 0
+        text = engines[at].L.ppp_last_error(engines[at].h).decode() if k else "no tile"
+        raise PPPError(rc, "tile %d: %s" % (st.failed_tile, text))
+    stats = _registration_stats(st.reg)
+    return stats["T"].copy(), [_registration_row(rows[i]) for i in range(min(cap, st.reg.steps + 1))], stats
+
+
+def register_mesh_tiles(engines, meshes, max_dist=2.0, iterations=30, min_step=1e-6, lock_eps=1e-9, T0=None):
+    """(T float64[3, 4], rows, stats) as Engine.register_mesh() gives them, bit for bit, for a scan held as slice-range engines
+    (ppp_register_mesh_tiles): engines[i] holds the scan with range i, meshes[i] is the TriMesh on its device (one TriMesh may
+    stand in every slot when all engines share a device; meshes may also be that one TriMesh).  The mesh is whole, so no range
+    condition exists and no call is refused for one.  Every evaluation is a host round trip: the tiles' words come back, the host
+    merges, solves and steps.  A tile's error is raised with its index in the message"""
+    engines = list(engines)
+    meshes = [meshes] * len(engines) if isinstance(meshes, TriMesh) else list(meshes)
+    if len(meshes) != len(engines):
+        raise PPPError(ERR_ARG, "register_mesh_tiles: one mesh per tile")
+    k = len(engines)
+    hs = (C.c_void_p * max(k, 1))(*[e.h for e in engines])
+    ms = (C.c_void_p * max(k, 1))(*[None if m is None else m.m for m in meshes])
+    rp = RegistrationParams(float(max_dist), int(iterations), float(min_step), float(lock_eps))
+    cap = max(int(iterations), 0) + 1
+    rows = (RegistrationRow * cap)()
+    st = RegisterTilesStats()
+    t = _t12(T0)
+    rc = lib().ppp_register_mesh_tiles(hs, ms, k, C.byref(rp), None if t is None else _d(t), rows, cap, C.byref(st))
     if rc:
         at = st.failed_tile if st.failed_tile >= 0 else 0
         text = engines[at].L.ppp_last_error(engines[at].h).decode() if k else "no tile"
@@ -1577,6 +1692,76 @@ class Engine:
         self._chk(self.L.ppp_register_mesh(self.h, m, C.byref(rp), None if t is None else _d(t), out if cap else None, cap, C.byref(st)))
         stats = _registration_stats(st)
         return stats["T"].copy(), [_registration_row(out[k]) for k in range(min(cap, st.steps + 1))], stats
+
+    def mesh_deviation_tile(self, mesh, max_dist=float("inf"), smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(deviation, smoothed, distance, tri_index, region, status, target, owned uint8[n], part dict): mesh_deviation() for the
+        points this engine OWNS -- a slice-range engine of the scan, or a whole-cloud one, which owns every indexed point -- against
+        the TriMesh `mesh` on this engine's device (ppp_get_mesh_deviation_tile).  The maps go by cloud index; an owned point's
+        entries are mesh_deviation()'s bits on a whole-cloud engine, every other point has DEV_DROPPED, -1, 255, NaN, 0 and owned
+        0.  The mesh is whole, so there is no halo: only this engine's range_margin must cover smooth_radius.  part:
+        deviation_tile()'s fields and on_face, on_edge, on_vertex, max_distance -- what merge_mesh_deviation_tiles() takes.
+        maps=False returns eight Nones and part"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = MeshDeviationTileStats()
+        dev = sm = dist = idx = region = status = target = owned = None
+        m = mesh.m if mesh is not None else None
+        if not maps:
+            self._chk(self.L.ppp_get_mesh_deviation_tile(self.h, m, C.byref(dp), None, None, None, None, None, None, None, None, 0, C.byref(st)))
+        else:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            n1 = max(n, 1)
+            dev, sm, dist, target = (np.zeros(n1, np.float64) for _ in range(4))
+            idx = np.zeros(n1, np.int32)
+            region, status, owned = (np.zeros(n1, np.uint8) for _ in range(3))
+            ub = C.POINTER(C.c_ubyte)
+            self._chk(self.L.ppp_get_mesh_deviation_tile(self.h, m, C.byref(dp), _d(dev), _d(sm), _d(dist), _i(idx), region.ctypes.data_as(ub),
+                                                         status.ctypes.data_as(ub), _d(target), owned.ctypes.data_as(ub), n, C.byref(st)))
+            dev, sm, dist, idx, region, status, target, owned = (a[:n] for a in (dev, sm, dist, idx, region, status, target, owned))
+        return dev, sm, dist, idx, region, status, target, owned, _mesh_tile_part(st)
+
+    def mesh_signed_deviation_tile(self, mesh, max_dist=float("inf"), smooth_radius=0.0, allowance=0.0, gain=1.0, maps=True):
+        """(signed_distance, smoothed, distance, tri_index, region, feature, flags, status, target, owned uint8[n], part dict):
+        mesh_signed_deviation() for the points this engine OWNS (ppp_get_mesh_signed_deviation_tile); mesh_deviation_tile()'s
+        rules, with feature 255 and flags 0 for a point that is not owned.  part: mesh_deviation_tile()'s fields and on_border,
+        irregular, fallback, negative, positive -- what merge_mesh_signed_deviation_tiles() takes.  maps=False returns ten Nones
+        and part"""
+        dp = DeviationParams(float(max_dist), float(smooth_radius), float(allowance), float(gain))
+        st = MeshSignedDeviationTileStats()
+        sd = sm = dist = idx = region = feature = flags = status = target = owned = None
+        m = mesh.m if mesh is not None else None
+        if not maps:
+            self._chk(self.L.ppp_get_mesh_signed_deviation_tile(self.h, m, C.byref(dp), None, None, None, None, None, None, None, None, None, None, 0,
+                                                                C.byref(st)))
+        else:
+            nn = C.c_size_t()
+            self._chk(self.L.ppp_num_points(self.h, C.byref(nn)))
+            n = nn.value
+            n1 = max(n, 1)
+            sd, sm, dist, target = (np.zeros(n1, np.float64) for _ in range(4))
+            idx = np.zeros(n1, np.int32)
+            region, feature, flags, status, owned = (np.zeros(n1, np.uint8) for _ in range(5))
+            ub = C.POINTER(C.c_ubyte)
+            self._chk(self.L.ppp_get_mesh_signed_deviation_tile(self.h, m, C.byref(dp), _d(sd), _d(sm), _d(dist), _i(idx), region.ctypes.data_as(ub),
+                                                                feature.ctypes.data_as(ub), flags.ctypes.data_as(ub), status.ctypes.data_as(ub), _d(target),
+                                                                owned.ctypes.data_as(ub), n, C.byref(st)))
+            sd, sm, dist, idx, region, feature, flags, status, target, owned = (a[:n] for a in (sd, sm, dist, idx, region, feature, flags, status, target,
+                                                                                                owned))
+        return sd, sm, dist, idx, region, feature, flags, status, target, owned, _mesh_tile_part(st.mesh, st)
+
+    def mesh_registration_terms_tile(self, mesh, T=None, max_dist=2.0, lock_eps=1e-9):
+        """(row, part): mesh_registration_terms() over the points this engine OWNS -- a slice-range engine of the scan, or a
+        whole-cloud one -- against the TriMesh `mesh` on this engine's device (ppp_get_mesh_registration_terms_tile).  row as
+        mesh_registration_terms() gives it; part = dict(owned, evaluated, own_lo, own_hi, n, shift, centre, length), the frame
+        from the mesh's box and the shift from the whole scan: what merge_registration_terms() and registration_step() take,
+        unchanged.  The mesh is whole: no range condition, never ERR_CAPACITY"""
+        rp = RegistrationParams(float(max_dist), 1, 0.0, float(lock_eps))
+        row, part = RegistrationRow(), RegistrationPart()
+        t = _t12(T)
+        m = mesh.m if mesh is not None else None
+        self._chk(self.L.ppp_get_mesh_registration_terms_tile(self.h, m, C.byref(rp), None if t is None else _d(t), C.byref(row), C.byref(part)))
+        return _registration_row(row), _registration_part(part)
 
     def range_interval(self, min_x, max_x):
         """(lo, hi, S): the planner-unit x interval this handle's slice range indexes for a cloud with these x bounds."""
